@@ -26,6 +26,14 @@ child passed -- otherwise the same measurement runs with its collectives on gloo
 "fallback": ...).  If not even the rendezvous works, rank 0 drives all N devices in-process through the C ABI
 (moe_kg_batch_multi) and the other ranks exit.  After the timed region rank 0 recomputes every restart on its own GPU and
 reports the largest difference to the gathered results ("determinism"; restarts are bit-identical, MC shards <= 1e-12).
+
+A plain run does only what the headline line needs: set-up, warm-up, the K timed steps, the result line (its `roofline` read
+from the timed steps' own kernel times, with the committed HBM traffic beside them).  Everything else it can measure or check --
+the determinism recompute, the batch-1 / batch-8 / MC-sharded extras, the in-run PMC passes, the covariance-build and K(X,X)
+probes, the sustained FP64 rate, the other BASELINE configurations and the CPU reference baseline -- runs only with `--full`
+(the `--no-*` options then drop single parts of it).  `--dump-outputs DIR` writes what the last timed step returned to its
+caller (KG values and gradients of every restart; a suggestion's point and KG) as DIR/<name>.npy in float64; the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -175,6 +183,13 @@ def cpu_baseline_c5(w, log):
             "measurements": rows,
             "sample": "reference ComputeGradKnowledgeGradient (1 core) at n = 250, 500, 1000 (N = 1000, 2000, 4000) with %d and %d MC "
                       "samples, extrapolated to N = %d, M = %d" % (M1, M2, int(Nc), w.M)}
+
+
+def dump_outputs(dirname, **arrays):
+    """--dump-outputs: one DIR/<name>.npy (float64) per array the timed path returned in its last step."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def committed_traffic():
@@ -331,6 +346,8 @@ def run_suggest(args, rank, local_rank, world, comm, log):
     local_elapsed = time.perf_counter() - t0
     fence()
     elapsed = comm.max_over_ranks(time.perf_counter() - t0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, best_point=pt, best_kg=np.array([val]))
     trace = mapi.multistart_trace()
     pts_all = comm.gather_floats(list(pt.ravel()) + [val])
     if rank != 0:
@@ -368,7 +385,7 @@ def run_suggest(args, rank, local_rank, world, comm, log):
     if ex is not None:
         out["exchange"] = {"provider": type(ex).__name__, "calls_per_suggestion": ex.calls / float(steps), "doubles_per_call": ex.doubles / float(max(ex.calls, 1)),
                            "ms_per_call": 1e3 * ex.seconds / max(ex.calls, 1), "s_per_suggestion": ex.seconds / steps}
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         try:
             from oracle import ref
             assert ref.available() and hasattr(ref.lib(), "ref_kg_mcmc_multistart_mt")
@@ -569,7 +586,14 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the extra roofline probes (K(X,X) builds, sustained FP64 rate)")
     ap.add_argument("--no-determinism", action="store_true",
                     help="skip the recompute-and-compare check (profiling runs: every kg_mc_kernel launch is then a timed step's)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every extra measurement and check (CPU baseline, determinism, batch-1, "
+                         "MC shard, PMC passes, roofline probes, the other configurations); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -700,6 +724,8 @@ def main():
     fence()
     elapsed = comm.max_over_ranks(time.perf_counter() - t0)
     assert np.all(np.isfinite(kg)) and np.all(np.isfinite(grad))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, kg=kg, grad=grad)
 
     eff_world = world if multi_fallback is None else len(gps)
     if multi_fallback is not None:
@@ -719,7 +745,7 @@ def main():
         extras["collective_us_per_step"] = {"max_over_ranks": cmax, "rank0": coll_us,
                                             "what": "dist.gather_restarts: pack, host->device, all_gather of %d x %d doubles, device->host, unpack"
                                                     % (R, 2 + w.q * w.d)}
-    if args.no_determinism:
+    if args.no_determinism or not args.full:
         pass
     elif cw > 1 and args.shard == "restarts":
         # cross-rank determinism: rank 0 recomputes EVERY restart of the last step on its own GPU in one call and
@@ -741,7 +767,7 @@ def main():
         dmax = max(float(np.abs(rb["kg_sum"] / w.M - kg[:k]).max()), float(np.abs(rb["grad_sum"] / w.M - grad[:k]).max())) / sc
         extras["determinism"] = {"max_rel_diff_vs_separate_call": dmax, "ok": bool(dmax <= 1e-12), "restarts": k,
                                  "note": "the first %d restarts of the step evaluated in a call of their own" % k}
-    if cw > 1 and args.shard == "restarts" and not args.no_mc_shard:
+    if args.full and cw > 1 and args.shard == "restarts" and not args.no_mc_shard:
         # MC-sample sharding of ONE evaluation at a time (strong scaling of the single-evaluation latency): every rank takes an
         # even-aligned slice of the 10k samples, ONE all_reduce of 1 + q d doubles per evaluation
         one = w.Xq_restarts[:1]
@@ -763,7 +789,7 @@ def main():
             extras["mc_shard"]["max_rel_diff_vs_unsharded"] = max(float(np.abs(kgm - r1["kg_sum"] / w.M).max()),
                                                                   float(np.abs(gradm - r1["grad_sum"] / w.M).max())) / sc
         fence()
-    if not args.no_batch1 and args.shard == "restarts" and multi_fallback is None:
+    if args.full and not args.no_batch1 and args.shard == "restarts" and multi_fallback is None:
         # one evaluation per call (what compute_grad_knowledge_gradient does): the batch-1 latency next to the batched rate
         one = my_restarts[:1]
         ksteps = max(20, args.steps)
@@ -812,18 +838,19 @@ def main():
         # (a3/a4: GP build, posterior queries, the d-KG tail) is measured live on an N x M shape of the size the tail used to
         # build -- N = n training rows x 80 000 columns, 640 MB at C3 -- through moe_cov_build_probe (HIP events on the
         # library's stream around `repeat` launches).
-        Rp = min(Rl, 8)
-        probe_pts = np.random.default_rng(7).uniform(size=(Rp * n_local, w.d))
-        cov_launch_ms, cov_bytes_launch = G.cov_build_probe(probe_pts, repeat=10)
-        cov_bytes = cov_bytes_launch / Rp                                   # 8[nA d + nB d + nA nB]
-        cov_tbs = cov_bytes_launch / (cov_launch_ms * 1e-3) / 1e12 if cov_launch_ms > 0 else 0.0
+        if args.full:
+            Rp = min(Rl, 8)
+            probe_pts = np.random.default_rng(7).uniform(size=(Rp * n_local, w.d))
+            cov_launch_ms, cov_bytes_launch = G.cov_build_probe(probe_pts, repeat=10)
+            cov_bytes = cov_bytes_launch / Rp                                   # 8[nA d + nB d + nA nB]
+            cov_tbs = cov_bytes_launch / (cov_launch_ms * 1e-3) / 1e12 if cov_launch_ms > 0 else 0.0
         # (which MC kernel the library launched for this shape: wave-per-sample, workgroup-per-sample, or streamed-weights -- r3)
         kinfo = G.last_kernel_info()
         mc_kernel = {0: "kg_mc_kernel", 1: "kg_mc_block_kernel", 2: "kg_mc_stream_kernel"}[kinfo["variant"]]
         if kinfo["variant"] == 0 and kinfo.get("lane"):
             mc_kernel = "kg_mc_lane_kernel"   # r5: the lane-parked form of the LDS-table kernel (csrc/kg_mc_lane.hpp)
-        pmc, traffic_src = (None, "skipped (--no-traffic)")
-        if world == 1 and not args.no_traffic:
+        pmc, traffic_src = (None, "skipped (--no-traffic)" if args.full else "measured with --full")
+        if args.full and world == 1 and not args.no_traffic:
             pmc, traffic_src = measure_traffic(args.config if args.derivs is None else "%s:g=%d" % (args.config, args.derivs), Rl, log)
         if pmc is None:
             pmc = committed_traffic()
@@ -896,22 +923,23 @@ def main():
                                  "entries share one sqrt / exp) -- / HIP-event kernel time on the library's stream; one launch "
                                  "covers all evaluations of a step; traffic = HBM bytes per launch (PMC), tiny next to the "
                                  "compute time"},
-            "roofline_cov_build": {"bound": "hbm", "achieved": cov_tbs * 1e3, "peak": HBM_PEAK_TBS * 1e3, "unit": "GB/s",
-                                   "frac": cov_tbs / HBM_PEAK_TBS,
-                                   # (r5: tools/prof_kg.py's probe launch has this very shape -- min(R, 8) x M columns -- whatever R)
-                                   "traffic": (pmc.get("cov_build_kernel") or {}).get("hbm_bytes_per_launch"),
-                                   "traffic_source": traffic_src,
-                                   "kernel": "cov_build_kernel, N x M = %d x %d, measured by moe_cov_build_probe (the q-KG "
-                                             "tail itself no longer writes this matrix: it recomputes the entries where "
-                                             "they are consumed)" % (w.n, Rp * n_local),
-                                   "avg_launch_ms": cov_launch_ms, "bytes_per_launch": cov_bytes_launch,
-                                   "bytes_per_eval_equiv": cov_bytes},
             "kernel_ms_per_eval": {"mc": mc_ms, "cov_build": ms_cov / args.steps, "tail": ms_tail / args.steps,
                                    "state_host": ms_state / args.steps},
             "rccl_preflight_s": comm.preflight_s,
         }
+        if args.full:
+            out["roofline_cov_build"] = {"bound": "hbm", "achieved": cov_tbs * 1e3, "peak": HBM_PEAK_TBS * 1e3, "unit": "GB/s",
+                                         "frac": cov_tbs / HBM_PEAK_TBS,
+                                         # (r5: tools/prof_kg.py's probe launch has this very shape -- min(R, 8) x M columns -- whatever R)
+                                         "traffic": (pmc.get("cov_build_kernel") or {}).get("hbm_bytes_per_launch"),
+                                         "traffic_source": traffic_src,
+                                         "kernel": "cov_build_kernel, N x M = %d x %d, measured by moe_cov_build_probe (the q-KG "
+                                                   "tail itself no longer writes this matrix: it recomputes the entries where "
+                                                   "they are consumed)" % (w.n, Rp * n_local),
+                                         "avg_launch_ms": cov_launch_ms, "bytes_per_launch": cov_bytes_launch,
+                                         "bytes_per_eval_equiv": cov_bytes}
         out.update(extras)
-        if not args.no_extras:
+        if args.full and not args.no_extras:
             try:   # what the chip sustains on pure FP64 FMA chains (the clock does not hold 2.4 GHz under FP64 load)
                 sus = mapi.fp64_rate(local_rank)
                 out["roofline"]["sustained_fma_tflops"] = sus
@@ -920,18 +948,19 @@ def main():
                     out["roofline"]["executed_frac_of_sustained"] = executed["achieved"] / sus
             except Exception as e:  # pragma: no cover
                 log("fp64_rate failed: %s" % e)
-        if not args.no_extras and world == 1 and hasattr(mapi, "kxx_build_probe"):
+        if args.full and not args.no_extras and world == 1 and hasattr(mapi, "kxx_build_probe"):
             try:
                 out["roofline_cov_build_kxx"] = mapi.kxx_build_probe(log)
             except Exception as e:  # pragma: no cover
                 log("kxx_build_probe failed: %s" % e)
         # r6: scalars a driver that trims nested objects still records, and every other BASELINE configuration in one object
-        out["cov_build_frac"] = out["roofline_cov_build"]["frac"]
+        if args.full:
+            out["cov_build_frac"] = out["roofline_cov_build"]["frac"]
         if isinstance(out.get("roofline_cov_build_kxx"), dict):
             kx = out["roofline_cov_build_kxx"]
             fr = [v.get("frac") for v in kx.values() if isinstance(v, dict) and v.get("frac") is not None] if "frac" not in kx else [kx["frac"]]
             out["kxx_frac"] = max(fr) if fr else None
-        if not args.no_extras and world == 1 and args.config in ("C3", "C4") and multi_fallback is None:
+        if args.full and not args.no_extras and world == 1 and args.config in ("C3", "C4") and multi_fallback is None:
             G.close()   # (the headline GP: its workspaces go back to the pool before the other configurations build theirs)
             t_side = time.perf_counter()
             out["configs"] = side_configs(local_rank, log, c5_traffic=not args.no_traffic)
@@ -942,10 +971,10 @@ def main():
             for key, field in (("C5", "evals_per_s"), ("C5", "frac"), ("suggest", "s_per_suggestion"), ("suggest_c3", "s_per_suggestion"), ("C2", "value_grad_us"), ("C1", "mean_1pt_us")):
                 if field in out["configs"].get(key, {}):
                     out["%s_%s" % (key.lower(), field)] = out["configs"][key][field]
-        if not args.no_cpu_baseline and world == 1 and args.config == "C5" and args.derivs is None:
+        if args.full and not args.no_cpu_baseline and world == 1 and args.config == "C5" and args.derivs is None:
             out["cpu_baseline"] = cpu_baseline_c5(w, log)
             out["speedup_vs_cpu_one_core"] = value / out["cpu_baseline"]["value"]
-        elif not args.no_cpu_baseline and world == 1 and args.derivs is None:  # reported baseline: rank 0 at N = 1 only
+        elif args.full and not args.no_cpu_baseline and world == 1 and args.derivs is None:  # reported baseline: rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(w, best, args.cpu_sample_mc, log)
             out["speedup_vs_cpu_best"] = value / out["cpu_baseline"]["value"]
             if "one_core_evals_per_s" in out["cpu_baseline"]:

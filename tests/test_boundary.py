@@ -2,6 +2,7 @@
 ``moe.build.GPP`` for the hot path, with the same positional signatures; cornell_moe_amd.cpp_wrappers mirrors the reference's
 wrapper classes.  CPU-only checks here (no compute); the GPU flow is tests/test_gpu_boundary.py."""
 import inspect
+import json
 import os
 import re
 
@@ -9,6 +10,10 @@ import numpy as np
 import pytest
 
 REF_WRAPPERS = "/root/reference/moe/optimal_learning/python/cpp_wrappers"
+# what _scan_reference_wrappers() finds in the reference's wrapper files, stored so that the checks below run without the tree:
+#   python -c "import json, sys; sys.path.insert(0, 'tests'); import test_boundary as t; \
+#              json.dump(t._scan_reference_wrappers(), open(t.WRAPPER_CALLS, 'w'), indent=0)"
+WRAPPER_CALLS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_wrapper_calls.json")
 
 # (GPP name, number of positional arguments) of the boost::python exports on the hot path, with the reference line that
 # defines each wrapper's parameter list.
@@ -66,44 +71,56 @@ def test_gpp_exports_and_arity():
     assert gd._as_tuple() == (1, 7, 1, 3, 0.0, 1.0, 0.1, 1e-10)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_WRAPPERS), reason="reference tree not present (GPU box)")
-def test_every_hot_path_binding_of_the_reference_wrappers_exists():
-    """Static scan of the reference's own wrapper files: each C_GP.<name> they use on the hot path resolves in our module."""
-    from cornell_moe_amd import GPP
-    in_scope = ["knowledge_gradient.py", "expected_improvement.py", "gaussian_process.py", "domain.py", "optimization.py",
-                "covariance.py", "knowledge_gradient_mcmc.py", "expected_improvement_mcmc.py"]
-    out_of_scope = set()
-    missing = []
-    for fn in in_scope:
-        src = open(os.path.join(REF_WRAPPERS, fn)).read()
-        for name in sorted(set(re.findall(r"C_GP\.([A-Za-z_]+)", src))):
-            if name not in out_of_scope and not hasattr(GPP, name):
-                missing.append((fn, name))
-    assert not missing, missing
-
-
-@pytest.mark.skipif(not os.path.isdir(REF_WRAPPERS), reason="reference tree not present (GPU box)")
-def test_call_sites_of_the_reference_wrappers_fit_our_signatures():
-    """Every ``C_GP.<name>(...)`` call in the reference's hot-path wrapper files passes an argument count our function of that
-    name accepts (ast scan of the reference sources; nothing is imported from them)."""
+def _scan_reference_wrappers():
+    """Static scan of the reference's own wrapper files (nothing is imported from them): every C_GP.<name> used on the hot path
+    as [file, name], and every ``C_GP.<name>(...)`` call as [file, name, number of arguments passed] (ast)."""
     import ast
-    from cornell_moe_amd import GPP
-    checked = 0
+    uses = []
+    for fn in ["knowledge_gradient.py", "expected_improvement.py", "gaussian_process.py", "domain.py", "optimization.py",
+               "covariance.py", "knowledge_gradient_mcmc.py", "expected_improvement_mcmc.py"]:
+        src = open(os.path.join(REF_WRAPPERS, fn)).read()
+        uses += [[fn, name] for name in sorted(set(re.findall(r"C_GP\.([A-Za-z_]+)", src)))]
+    calls = []
     for fn in ("knowledge_gradient.py", "expected_improvement.py", "gaussian_process.py", "knowledge_gradient_mcmc.py",
                "expected_improvement_mcmc.py"):
         tree = ast.parse(open(os.path.join(REF_WRAPPERS, fn)).read())
         for node in ast.walk(tree):
-            if not (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute)
-                    and isinstance(node.func.value, ast.Name) and node.func.value.id == "C_GP"):
-                continue
-            obj = getattr(GPP, node.func.attr)
-            params = list(inspect.signature(obj.__init__ if inspect.isclass(obj) else obj).parameters.values())
-            if inspect.isclass(obj):
-                params = params[1:]
-            required = [p for p in params if p.default is inspect.Parameter.empty]
-            n = len(node.args) + len(node.keywords)
-            assert len(required) <= n <= len(params), (fn, node.func.attr, n, len(required), len(params))
-            checked += 1
+            if (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and isinstance(node.func.value, ast.Name)
+                    and node.func.value.id == "C_GP"):
+                calls.append([fn, node.func.attr, len(node.args) + len(node.keywords)])
+    return {"uses": uses, "calls": calls}
+
+
+def _reference_wrapper_calls():
+    """The scan as stored in tests/golden/ref_wrapper_calls.json; where the reference tree is present it must still find the same."""
+    with open(WRAPPER_CALLS) as fh:
+        stored = json.load(fh)
+    if os.path.isdir(REF_WRAPPERS):
+        assert _scan_reference_wrappers() == stored
+    return stored
+
+
+def test_every_hot_path_binding_of_the_reference_wrappers_exists():
+    """Each C_GP.<name> the reference's wrapper files use on the hot path resolves in our module."""
+    from cornell_moe_amd import GPP
+    out_of_scope = set()
+    missing = [(fn, name) for fn, name in _reference_wrapper_calls()["uses"] if name not in out_of_scope and not hasattr(GPP, name)]
+    assert not missing, missing
+
+
+def test_call_sites_of_the_reference_wrappers_fit_our_signatures():
+    """Every ``C_GP.<name>(...)`` call in the reference's hot-path wrapper files passes an argument count our function of that
+    name accepts."""
+    from cornell_moe_amd import GPP
+    checked = 0
+    for fn, name, n in _reference_wrapper_calls()["calls"]:
+        obj = getattr(GPP, name)
+        params = list(inspect.signature(obj.__init__ if inspect.isclass(obj) else obj).parameters.values())
+        if inspect.isclass(obj):
+            params = params[1:]
+        required = [p for p in params if p.default is inspect.Parameter.empty]
+        assert len(required) <= n <= len(params), (fn, name, n, len(required), len(params))
+        checked += 1
     assert checked >= 30
 
 

@@ -17,7 +17,7 @@ def _run(extra_env, *flags, gpus=2):
     env = dict(os.environ, **extra_env)
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1",
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--full",
                           "--no-cpu-baseline", "--no-traffic", "--no-extras"] + list(flags), env=env, stdout=subprocess.PIPE,
                          stderr=subprocess.PIPE, universal_newlines=True, timeout=900)
     assert res.returncode == 0, res.stderr[-2000:]

@@ -337,9 +337,13 @@ def test_normal_stream_pinned_to_reference_build():
 @pytest.mark.skipif(not ref.available(), reason="oracle/_ref not built (reference tree absent)")
 def test_simplex_fixtures_reproduce_from_the_live_reference():
     """r4: tests/golden/ref_simplex_kg.npz is what the reference's own SimplexIntersectTensorProductDomain instantiations return
-    (oracle/ref_harness.cpp: ref_kg_dom, ref_kg_multistart_dom) -- one evaluation and one driver run recomputed here, bit for bit;
-    the same evaluation over the tensor product gives the fixture's other KG (the simplex run is not the default run by accident)."""
+    (oracle/ref_harness.cpp: ref_kg_dom, ref_kg_multistart_dom) -- one evaluation and one driver run recomputed here;
+    the same evaluation over the tensor product gives the fixture's other KG (the simplex run is not the default run by accident).
+    The reference builds with -march=native, so a build on another host differs from the fixture's in the last bits, and its
+    20-step inner optimisations then stop ~1e-7 apart: the outputs are held to the stated FP64 tolerances (helpers.TOL,
+    helpers.kg_tolerances), not bit for bit."""
     import os
+    import types
     from helpers import GOLDEN
     z = np.load(os.path.join(os.path.dirname(GOLDEN), "ref_simplex_kg.npz"))
     g = lambda name: z["e0_in_%s" % name]  # noqa: E731
@@ -348,11 +352,15 @@ def test_simplex_fixtures_reproduce_from_the_live_reference():
     args = (tuple(g("inner_gd")), g("bounds")[: 2 * (d - f)], g("discrete"), g("Xq"), g("Xp") if int(g("p")) else None, M,
             float(g("best_so_far")), g("normals"))
     r = R.kg(*args, num_fidelity=f, domain_type=1)
-    assert r["kg"] == float(z["e0_out_kg"]) and np.array_equal(r["grad"], z["e0_out_grad"]) and np.array_equal(r["best_point"], z["e0_out_best_point"])
-    assert R.kg(*args, num_fidelity=f, domain_type=0, want_grad=False)["kg"] == float(z["e0_out_kg_tensor"])
+    gtol, ptol = kg_tolerances(types.SimpleNamespace(inp={"inner_gd": g("inner_gd")},
+                                                     out={"kg": z["e0_out_kg"], "grad_kg": z["e0_out_grad"]}))
+    assert rel(r["kg"], float(z["e0_out_kg"])) <= TOL["kg"]
+    assert np.abs(r["grad"] - z["e0_out_grad"]).max() <= gtol and np.abs(r["best_point"] - z["e0_out_best_point"]).max() <= ptol
+    assert rel(R.kg(*args, num_fidelity=f, domain_type=0, want_grad=False)["kg"], float(z["e0_out_kg_tensor"])) <= TOL["kg"]
     assert abs(float(z["e0_out_kg"]) - float(z["e0_out_kg_tensor"])) > 1e-3
     g = lambda name: z["m0_in_%s" % name]  # noqa: E731
     R = ref.RefGP(1, float(g("alpha")), g("lengths"), g("X"), g("y"), g("noise"), [])
     best, found = R.kg_multistart(tuple(g("outer_gd")), tuple(g("inner_gd")), g("bounds"), g("discrete"), g("starts"), None, int(g("M")),
                                   float(g("best_so_far")), int(g("rng_seed")), domain_type=1)
-    assert np.array_equal(best, z["m0_out_best_point"]) and found == bool(z["m0_out_found"])
+    ms_ptol = kg_tolerances(types.SimpleNamespace(inp={"inner_gd": g("inner_gd")}, out={"kg": 0.0, "grad_kg": np.zeros(1)}))[1]
+    assert np.abs(best - z["m0_out_best_point"]).max() <= ms_ptol and found == bool(z["m0_out_found"])
