@@ -373,9 +373,8 @@ void GpDev::mean_of_points(const double* pts, int k, double* mu, double* grad) {
   // r6, the latency path (compute_posterior_mean one candidate at a time): the kernel reads the few query points from the pinned
   // staging buffer and writes its results into the pinned result buffer -- pinned host memory is device-visible -- so the call is ONE
   // kernel and one wait instead of copy + kernel + copy (C1: 23.5 -> see profiles/r06_al_*).  Larger queries keep the copies: a
-  // workgroup re-reads nothing of its point, but k x (1 + dp) doubles over PCIe in single stores stop paying.  MOE_GP_ZERO_COPY=0: copies.
-  static const bool zero_copy_on = !(std::getenv("MOE_GP_ZERO_COPY") && std::getenv("MOE_GP_ZERO_COPY")[0] == '0');
-  if (zero_copy_on && k <= 64 && Recorder::current() == nullptr) {
+  // workgroup re-reads nothing of its point, but k x (1 + dp) doubles over PCIe in single stores stop paying.
+  if (k <= 64 && Recorder::current() == nullptr) {
     launch_mean(cp, dX.p, n, derivs, dKinvY.p, hStateIn.p, k, mean, want_grad, hStateOut.p, stream);
   } else {
     dPts.upload(hStateIn.p, (size_t)k * dp, stream);
@@ -415,13 +414,9 @@ void GpDev::add_points_unchecked(const double* pts, const double* vals, int k) {
   y.insert(y.end(), vals, vals + (size_t)k * (1 + g));
   n += k;
   // A few new points against an existing factorisation: append a block row to L and L^-1 (O(N^2 k)) instead of
-  // rebuilding (O(N^3)).  MOE_GP_APPEND=0 forces the rebuild (A/B and tests).
-  static const bool allow_append = [] {
-    const char* e = std::getenv("MOE_GP_APPEND");
-    return !(e && std::atoi(e) == 0);
-  }();
+  // rebuilding (O(N^3)).
   const int N1 = N0 + kk;
-  if (!allow_append || n0 == 0 || N1 > ldL) {
+  if (n0 == 0 || N1 > ldL) {
     rebuild();
     return;
   }
@@ -588,8 +583,7 @@ KgStateEnqueued enqueue_kg_state_batch(GpDev& gp, const double* U_all, int u, in
   launch_tri_gemm_cols('T', N, (int)cm, m, gp.dLinv.p, gp.ldL, gp.dVE.p, N, gp.dWE.p, N, gp.dEK.p, s);
   const size_t n_kk = (size_t)E * m * m, n_x = (size_t)E * R * m;
   gp.dGram.reserve(n_kk + n_x + ctot);
-  static const bool defer_env = !(std::getenv("MOE_KG_GRAM_IN_STATE") != nullptr && std::atoi(std::getenv("MOE_KG_GRAM_IN_STATE")) == 0);
-  const bool defer = defer_env && m <= 8;  // (the latency path: q-KG with a handful of points)
+  const bool defer = m <= 8;  // (the latency path: q-KG with a handful of points)
   const int s_kk = launch_gram_batch(E, m, 0, 0, N, gp.dVE.p, N, gp.dGram.p, gp.dEK.p, s, defer);
   const int s_x = launch_gram_cross_batch(E, m, ng, A, N, gp.dE.p, N, gp.dWE.p, N, gp.dGram.p + n_kk, gp.dEK.p + part_kk, s, defer);
   launch_gemm_tn((int)ctot, 1, N, gp.dE.p, N, gp.dKinvY.p, N, gp.dGram.p + n_kk + n_x, (int)ctot, s);

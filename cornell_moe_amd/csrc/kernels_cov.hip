@@ -329,11 +329,7 @@ void cov_build_dp(const CovParams& cp, const double* A, int nA, const DerivList&
   const int rows = nA * (1 + dA.g);
   // column tile of a workgroup: 16 B points; the triangular build visits half the tiles and would leave the chip with ~2 workgroups
   // per CU at N = 8000 -- 2 points per workgroup there (r4, TB/s of stores by the symmetric byte count, N = 8000 / 26 000: 16 columns 2.4 / 2.7, 8: 3.2 / 3.6, 4: 3.9 / 4.5, 2: 4.1 / 4.8, 1: 3.8 / 5.0)
-  static const int kxx_cols = [] {
-    const char* v = std::getenv("MOE_KXX_COLS");
-    return (v && *v) ? std::max(1, std::min(kCovCols, std::atoi(v))) : 2;
-  }();
-  const int cpw = lower_only ? kxx_cols : kCovCols;
+  const int cpw = lower_only ? 2 : kCovCols;
   dim3 grid((nB + cpw - 1) / cpw, (rows + kCovRows - 1) / kCovRows);
   if (grid.x == 0 || grid.y == 0) return;
   if (dA.g > 0 && value_fast_path()) {  // thread per point, rows transposed through LDS (MOE_COV_FAST=0: the row-per-thread kernel)

@@ -282,45 +282,20 @@ void tile_gemm(int M, int Ncols, int K, const double* A, long lda, const double*
   if (M <= 0 || Ncols <= 0) return;
   // Skinny outputs: smaller tiles give the chip more workgroups to place.
   const long blocks64 = (long)((M + 63) / 64) * ((Ncols + 63) / 64);
-  static const long min_blocks = [] {
-    const char* v = std::getenv("MOE_GEMM_MFMA_MIN_BLOCKS");
-    return (v && *v) ? std::atol(v) : 48L;
-  }();
-  if (blocks64 >= min_blocks) {
+  if (blocks64 >= 48) {
     dim3 grid((M + 63) / 64, (Ncols + 63) / 64);
     // mfma_gemm_kernel: x = column tile, y = row tile -- or, for the triangular modes with enough rows, a PAIR of row
     // tiles (p, R - 1 - p) whose K ranges add up to the same total for every workgroup
-    static const int pair_env = [] {
-      const char* v = std::getenv("MOE_GEMM_PAIR_ROWS");
-      return (v && *v) ? std::atoi(v) : 1;
-    }();
-    const int pair_rows = (pair_env != 0 && (MODE == 1 || MODE == 2) && grid.x >= 16 && (long)grid.x * grid.y >= 512) ? 1 : 0;
+    const int pair_rows = ((MODE == 1 || MODE == 2) && grid.x >= 16 && (long)grid.x * grid.y >= 512) ? 1 : 0;
     const dim3 mgrid(grid.y, pair_rows ? (grid.x + 1) / 2 : grid.x);
-    static const bool use_mfma = [] {
-      const char* v = std::getenv("MOE_GEMM_MFMA");
-      return !(v && *v == '0');
-    }();
-    if (use_mfma) {
-      int xmul = 1;
-      for (int cand : {37, 41, 43, 47, 53, 59})
-        if ((int)grid.x % cand != 0) {
-          xmul = cand;
-          break;
-        }
-      static const int tk = [] {
-        const char* v = std::getenv("MOE_GEMM_TK");
-        return (v && *v) ? std::atoi(v) : 16;
-      }();
-      if (tk == 32)
-        MOE_LAUNCH((mfma_gemm_kernel<MODE, NEG, 32>), mgrid, dim3(256), 0, s, M, Ncols, K, A, lda, B, ldb, C, ldc, xmul, pair_rows,
-                           0L, 0L, 0L, 0, 0, tri_scale);
-      else
-        MOE_LAUNCH((mfma_gemm_kernel<MODE, NEG, 16>), mgrid, dim3(256), 0, s, M, Ncols, K, A, lda, B, ldb, C, ldc, xmul, pair_rows,
-                           0L, 0L, 0L, 0, 0, tri_scale);
-    }
-    else
-      launch_kernel_ens<tile_gemm_kernel_body<64, 64, MODE, 16, NEG>, 256>(tile_gemm_kernel<64, 64, MODE, 16, NEG>, grid, dim3(256), 0, s, M, Ncols, K, A,
-                                                                           lda, B, ldb, C, ldc);
+    int xmul = 1;
+    for (int cand : {37, 41, 43, 47, 53, 59})
+      if ((int)grid.x % cand != 0) {
+        xmul = cand;
+        break;
+      }
+    MOE_LAUNCH((mfma_gemm_kernel<MODE, NEG, 16>), mgrid, dim3(256), 0, s, M, Ncols, K, A, lda, B, ldb, C, ldc, xmul, pair_rows,
+               0L, 0L, 0L, 0, 0, tri_scale);
   } else {
     dim3 grid((M + 31) / 32, (Ncols + 15) / 16);
     launch_kernel_ens<tile_gemm_kernel_body<32, 16, MODE, 128, NEG>, 256>(tile_gemm_kernel<32, 16, MODE, 128, NEG>, grid, dim3(256), 0, s, M, Ncols, K, A,
@@ -1006,11 +981,7 @@ size_t tri_cols_work_doubles(int N, int c) { return (size_t)tri_cols_slices(N, n
 void launch_tri_gemm_cols(char op, int N, int c, int cols_per_problem, const double* T, long ldt, const double* B, long ldb,
                           double* C, long ldc, double* work, hipStream_t s) {
   if (N <= 0 || c <= 0) return;
-  static const int mode = [] {
-    const char* v = std::getenv("MOE_TRI_COLS");  // 0: the plain tiled kernels (A/B runs)
-    return (v && *v) ? std::atoi(v) : 1;
-  }();
-  if (mode == 0 || N < 128) {  // (tiny factors: one or two row tiles, the plain tiled kernel)
+  if (N < 128) {  // (tiny factors: one or two row tiles, the plain tiled kernel)
     launch_tri_gemm(op, N, c, T, ldt, B, ldb, C, ldc, s);
     return;
   }
@@ -1035,21 +1006,11 @@ void launch_tri_gemm_cols(char op, int N, int c, int cols_per_problem, const dou
   const int slices = tri_cols_slices(N, &KS);
   const dim3 grid((c + 63) / 64, (N + 63) / 64, slices);
   const dim3 sgrid((N + 255) / 256, c);
-  static const int tk = [] {
-    const char* v = std::getenv("MOE_TRI_SPLITK_TK");
-    return (v && *v) ? std::atoi(v) : 16;
-  }();
   if (op == 'N') {
-    if (tk == 32)
-      launch_kernel_ens<tri_splitk_kernel_body<1, 32>, 256>(tri_splitk_kernel<1, 32>, grid, dim3(256), 0, s, N, c, KS, T, ldt, B, ldb, work);
-    else
-      launch_kernel_ens<tri_splitk_kernel_body<1, 16>, 256>(tri_splitk_kernel<1, 16>, grid, dim3(256), 0, s, N, c, KS, T, ldt, B, ldb, work);
+    launch_kernel_ens<tri_splitk_kernel_body<1, 16>, 256>(tri_splitk_kernel<1, 16>, grid, dim3(256), 0, s, N, c, KS, T, ldt, B, ldb, work);
     launch_kernel_ens<tri_splitk_sum_kernel_body<1>, 256>(tri_splitk_sum_kernel<1>, sgrid, dim3(256), 0, s, N, c, KS, slices, (const double*)work, C, ldc);
   } else {
-    if (tk == 32)
-      launch_kernel_ens<tri_splitk_kernel_body<2, 32>, 256>(tri_splitk_kernel<2, 32>, grid, dim3(256), 0, s, N, c, KS, T, ldt, B, ldb, work);
-    else
-      launch_kernel_ens<tri_splitk_kernel_body<2, 16>, 256>(tri_splitk_kernel<2, 16>, grid, dim3(256), 0, s, N, c, KS, T, ldt, B, ldb, work);
+    launch_kernel_ens<tri_splitk_kernel_body<2, 16>, 256>(tri_splitk_kernel<2, 16>, grid, dim3(256), 0, s, N, c, KS, T, ldt, B, ldb, work);
     launch_kernel_ens<tri_splitk_sum_kernel_body<2>, 256>(tri_splitk_sum_kernel<2>, sgrid, dim3(256), 0, s, N, c, KS, slices, (const double*)work, C, ldc);
   }
   MOE_HIP_CHECK(hipGetLastError());
@@ -1091,11 +1052,7 @@ void launch_tri_gram_strided(int N, int c, int stride, const double* T, long ldt
 void launch_tri_gemm_skinny(char op, int N, int c, const double* T, long ldt, const double* B, long ldb, double* C,
                             long ldc, hipStream_t s) {
   if (N <= 0 || c <= 0) return;
-  static const bool skinny = [] {
-    const char* v = std::getenv("MOE_TRI_SKINNY");
-    return !(v && *v == '0');
-  }();
-  if (!skinny || c > 16 || N < 128) {
+  if (c > 16 || N < 128) {
     launch_tri_gemm(op, N, c, T, ldt, B, ldb, C, ldc, s);
     return;
   }
@@ -1272,10 +1229,7 @@ int launch_gram_batch(int E, int m, int ng, int A, int K, const double* V, long 
 //     and 8 x more flops per byte is what lets the MFMA tiles run compute-bound.
 // Same pivot rule (1e-16, gpp_linear_algebra.cpp:118) and the same error report as the one-level path.
 // ---------------------------------------------------------------------------------------------------------------------
-#ifndef MOE_CHOL_OUTER
-#define MOE_CHOL_OUTER 512
-#endif
-constexpr int kOuter = MOE_CHOL_OUTER;
+constexpr int kOuter = 512;
 
 // Diagonal 64 x 64 block: factor AND invert, 256 threads, everything in LDS, in 16-column sub-steps:
 //   (1) the 16 x 16 diagonal sub-block is factored and inverted by 16 lanes holding one row each in registers (16 unrolled

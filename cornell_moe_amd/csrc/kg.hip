@@ -25,6 +25,7 @@
 #include <mutex>
 #include <thread>
 #include <memory>
+#include <optional>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
@@ -458,7 +459,7 @@ inline int zc_sum_lanes(int m) {  // lanes that share an entry of ZC in kg_zc_su
 // r5: for small m and few chunks the sum of the partials is taken by kg_finish_kernel itself (one launch less on the latency path)
 inline bool zc_sum_in_finish(int m, int num_local) {
   const long chunks = (num_local + zc_chunk_len(m) - 1) / zc_chunk_len(m);
-  return m <= 8 && chunks * m * m <= 16384 && env_int("MOE_KG_ZC_IN_FINISH", 1) != 0;
+  return m <= 8 && chunks * m * m <= 16384;
 }
 
 // host side of the two: part = E * chunks * m * m doubles of workspace
@@ -1017,10 +1018,12 @@ struct EventTimer {
   }
 };
 
-int env_int(const char* name, int dflt) {
+std::optional<int> env_opt(const char* name) {  // unset and empty: no value
   const char* v = std::getenv(name);
-  return (v && *v) ? std::atoi(v) : dflt;
+  if (v && *v) return std::atoi(v);
+  return std::nullopt;
 }
+int env_int(const char* name, int dflt) { return env_opt(name).value_or(dflt); }
 
 // z, beta = L^-T z and the discretised-set winner of EVERY sample (they depend on the normal draws alone): one wavefront
 // per sample, grid-stride, the same device functions the MC kernels use -- so the values are the ones they would compute.
@@ -1203,7 +1206,7 @@ void launch_sample_weights(const KgMcParams& P, double* V, hipStream_t s, bool t
   // r6: `table_only` -- the consumer (the streamed-weights kernel) has no in-kernel form of the weights whose bits the table would have
   // to reproduce -- takes the matrix-pipe kernel from m = 16 on: per (row, sample) entry the fma version's loop is one dependent chain
   // of m fmas behind a scalar-load round trip and the previous store's acknowledgement (1.17 ms per 2.56 GB at C5 = 2.2 TB/s)
-  const bool mfma = P.v_slots1 == 1 + P.g && (P.m > 64 || (table_only && P.m >= 16 && env_int("MOE_KG_TABLE_MFMA", 1) != 0));
+  const bool mfma = P.v_slots1 == 1 + P.g && (P.m > 64 || (table_only && P.m >= 16));
   if (mfma) {
     MOE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kg_table128_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)g128::kSmemBytes));
@@ -1271,43 +1274,97 @@ void launch_mc_block(const KgMcParams& P, int dp, int G, int tr, int num_lds_til
   }
 }
 
-}  // namespace
+// q-KG fast path: the gradient tail never materialises the N x M covariance matrix (see launch_fused_tail).  A function of the
+// evaluation's shape and MOE_KG_FUSED_TAIL -- kg_launch (plan_mc) and kg_max_batch both ask here, so they cannot disagree.
+bool fused_tail_taken(bool want_grad, int g, int m) { return want_grad && g == 0 && m <= 8 && env_int("MOE_KG_FUSED_TAIL", 1) != 0; }
+// samples per TB partial of the gradient tail
+int tail_chunk_len(bool fused_tail, int m) { return fused_tail ? kFusedChunk : (m > 64 ? kTbChunkWide : kTbChunk); }
 
-// Everything up to and including the asynchronous launches on gp.stream; the returned object's collect() waits for the
-// stream and assembles the results.  Launching on several GPs (MCMC ensemble members, each with its own stream and
-// workspaces) before collecting any of them overlaps one member's host algebra with the others' kernels.
-KgPending kg_launch(GpDev& gp, int num_fidelity, const moe_gd_params_t& gd, const double* bounds, const double* discrete, int P,
-                    const double* Xq_all, int num_evals, const double* Xp, int q, int p, int num_mc, double best_so_far,
-                    const double* normals, int first_sample, int num_local, bool want_grad, bool want_best_points,
-                    double weight_table_gb, const double* disc_head) {
-  gp.use_device();
-  hipStream_t s = gp.stream;
-  const int d = gp.d, dp = gp.dp, f = num_fidelity, u = q + p, n = gp.n, g = gp.g, g1 = 1 + gp.g, N = gp.N;
-  const int E = num_evals;
-  const int m = u * g1;
+// The shape of one kg_launch: the union of u = q + p points with 1 + g rows each (m rows), A = u + P points in the discretised set,
+// `size` = d - num_fidelity coordinates the inner optimisations move, E evaluations of num_local samples each.
+struct KgDims {
+  int d, dp, f, size, n, g, g1, N;
+  int q, p, u, m, A, E, ngrad, qd;
+  int num_mc, first_sample, num_local;
+  bool want_grad, simplex;
+};
+
+KgDims check_kg_args(const GpDev& gp, int f, const moe_gd_params_t& gd, int P, int E, int q, int p, int num_mc, int first_sample,
+                     int num_local, bool want_grad) {
+  KgDims k;
+  k.d = gp.d, k.dp = gp.dp, k.f = f, k.n = gp.n, k.g = gp.g, k.g1 = 1 + gp.g, k.N = gp.N;
+  k.q = q, k.p = p, k.u = q + p, k.m = k.u * k.g1, k.A = k.u + P, k.E = E;
+  k.ngrad = want_grad ? q * k.g1 * k.d : 0;
+  k.qd = q * k.d;
+  k.num_mc = num_mc, k.first_sample = first_sample, k.num_local = num_local;
+  k.want_grad = want_grad;
   if (q <= 0) throw Error(MOE_ERR_BOUNDS, "num_to_sample must be positive", q, 1, 1e9);
   if (p < 0) throw Error(MOE_ERR_BOUNDS, "num_being_sampled must be non-negative", p, 0, 1e9);
   if (E <= 0) throw Error(MOE_ERR_BOUNDS, "num_evals must be positive", E, 1, 1e9);
-  if (m > kMaxMB)
-    throw Error(MOE_ERR_BOUNDS, "(q + p)(1 + num_derivatives) > 128 is not supported by the device kernels", m, 1, kMaxMB);
-  if (g > 12) throw Error(MOE_ERR_BOUNDS, "d-KG with more than 12 observed derivatives is not supported by the device kernels", g, 0, 12);
-  if (f < 0 || f >= d) throw Error(MOE_ERR_BOUNDS, "num_fidelity out of range", f, 0, d - 1);
+  if (k.m > kMaxMB)
+    throw Error(MOE_ERR_BOUNDS, "(q + p)(1 + num_derivatives) > 128 is not supported by the device kernels", k.m, 1, kMaxMB);
+  if (k.g > 12) throw Error(MOE_ERR_BOUNDS, "d-KG with more than 12 observed derivatives is not supported by the device kernels", k.g, 0, 12);
+  if (f < 0 || f >= k.d) throw Error(MOE_ERR_BOUNDS, "num_fidelity out of range", f, 0, k.d - 1);
   if (num_mc <= 0) throw Error(MOE_ERR_BOUNDS, "num_mc must be positive", num_mc, 1, 1e12);
   if (first_sample < 0 || (first_sample & 1) || num_local <= 0 || first_sample + num_local > num_mc)
     throw Error(MOE_ERR_INVALID_VALUE, "MC shard must be an even-aligned slice of [0, num_mc)", first_sample, 0, 0);
   if (gd.max_num_steps <= 0) throw Error(MOE_ERR_BOUNDS, "max_num_steps must be positive", gd.max_num_steps, 1, 1e9);
-  const int size = d - f;
+  k.size = k.d - f;
   if (gd.domain_type != MOE_DOMAIN_TENSOR_PRODUCT && gd.domain_type != MOE_DOMAIN_SIMPLEX)
     throw Error(MOE_ERR_INVALID_VALUE, "unknown domain_type (0 = tensor product, 1 = simplex)", gd.domain_type, 0, 1);
-  const bool simplex = gd.domain_type == MOE_DOMAIN_SIMPLEX;  // the inner optimisations' domain (r4)
-  const int A = u + P;
+  k.simplex = gd.domain_type == MOE_DOMAIN_SIMPLEX;  // the inner optimisations' domain (r4)
+  return k;
+}
+
+// How the MC step of one kg_launch runs: which kernel, its launch geometry, the passes around it, and the form of the gradient tail.
+struct McPlan {
+  int G = 0;                  // derivative-weight slots of the MC kernel instantiation
+  int ntiles = 0;             // 64-point tiles of the n + u points
+  int variant = 0;            // 0: wave-per-sample (LDS slabs), 1: workgroup-per-sample, 2: streamed weights
+  bool xlds = true;           // variant 0: the coordinate table in LDS
+  bool far_frame = false;     // the frame is wider than MOE_KG_DOT_MAX_RADIUS2: direct-difference kernels, single-trial passes
+  bool wide_frame = false;    // ... or d > 16: no coordinate table in LDS either way
+  bool small_lane = false;    // a small shape with few samples: the lane-parked kernel's single-trial passes
+  bool lane_kernel = false;   // variant 0 in its lane-parked form (kg_mc_lane.hpp)
+  int waves = 0, blocks = 0;  // wavefronts per workgroup, workgroups
+  size_t shm = 0;             // dynamic LDS bytes (variants 0, 2)
+  int tr = -1, num_lds_tiles = 0;  // variant 1: register tiles per wave, tiles in LDS
+  int wide_lds_tiles = 0;     // leading tiles of the coordinate table kept in LDS (WideEval)
+  int pair_rows = 0;          // the coordinate table in row pairs
+  int rec_head = 0;           // doubles of the record head [L | mu_disc | C_disc | disc] (the lane-parked kernel's LDS copy)
+  int multi_trial = 0;        // KgMcParams::multi_trial
+  bool prep = false;          // the sample pre-pass runs (beta, best_j)
+  bool weight_table = false;  // the per-sample weight table is built
+  long v_stride = 0;          // its doubles per sample, and its slots per point
+  int v_slots1 = 0;
+  bool fused_tail = false;    // the T-free q-KG tail
+  int chunk_len = 0;          // samples per TB partial of the tail
+};
+
+// Every decision about how the MC step runs, from the evaluation's shape, the GP, the points of the call and the switches read at the
+// top (tests set them per call to reach shipped paths at small sizes, or to compare two shipped forms).  Allocates and launches nothing.
+McPlan plan_mc(const GpDev& gp, const KgDims& k, const double* bounds, const double* Xq_all, const double* Xp, double weight_table_gb) {
+  const double max_radius2 = (double)env_int("MOE_KG_DOT_MAX_RADIUS2", 10000);
+  const bool lane_on = env_int("MOE_KG_LANE", 1) != 0;
+  const long small_lane_max_samples = env_int("MOE_KG_SMALL_LANE_MAX_SAMPLES", 1024);
+  const bool small_multi = env_int("MOE_KG_SMALL_MULTI", 1) != 0;
+  const std::optional<int> forced_tr = env_opt("MOE_KG_TR");
+  const std::optional<int> forced_variant = env_opt("MOE_KG_VARIANT");
+  const int prep_mode = env_int("MOE_KG_PREP", -1);  // 1: the sample pre-pass for every kernel, 0: only where it is mandatory
+  const bool stream_weights = env_int("MOE_KG_STREAM_WEIGHTS", 1) != 0;
+  // the weight table's cap: the caller's share of the workspace budget (kg_evaluate_batch, kg_mcmc_sums), 4 GB for a bare kg_launch
+  const double v_cap = std::getenv("MOE_KG_V_MAX_GB") ? (double)env_int("MOE_KG_V_MAX_GB", 4)
+                                                      : (weight_table_gb >= 0.0 ? weight_table_gb : 4.0);
+  McPlan pl;
+  pl.fused_tail = fused_tail_taken(k.want_grad, k.g, k.m);
+
+  const int d = k.d, dp = k.dp, n = k.n, g = k.g, m = k.m, u = k.u, A = k.A, E = k.E, num_local = k.num_local;
   // derivative-weight slots of the MC kernel instantiation: one per observed derivative up to 4, then 8 or 12 (unused slots
   // carry zero weights); more than 4 always take the workgroup-per-sample kernel
   // (d > 16: slot counts {0, 4, 8, 12} only -- kg_mc.hpp launch_dp_wide)
   const bool wide_dp = dp > 16;
   const int G = wide_dp ? (g == 0 ? 0 : (g <= 4 ? 4 : (g <= 8 ? 8 : 12))) : (g <= 4 ? g : (g <= 8 ? 8 : 12));
   const int ntiles = (n + u + 63) / 64;
-  const int ngrad = want_grad ? q * g1 * d : 0;
 
   // ---- MC launch geometry: workgroup = `waves` wavefronts sharing one LDS coordinate table ----
   const size_t tab_bytes = sizeof(double) * (size_t)ntiles * (dp + 1) * 64;  // LDS copy: + the |x|^2 row (kg_mc.hpp eval_loop)
@@ -1332,18 +1389,18 @@ KgPending kg_launch(GpDev& gp, int num_fidelity, const moe_gd_params_t& gd, cons
     // in a batch, or in another rank's shard (r3, ADVICE: moe_kg_batch_multi / dist.py promise bit-identical restarts).  Only a
     // point_to_sample outside the box (or a fidelity coordinate, which has no inner bound) adds its own distance.
     double rad2 = 0.0;
-    for (int k = 0; k < d; ++k) {
-      const double c = gp.x_mean[k];
-      double ext = gp.x_ext[k];
-      if (k < size) ext = std::max(ext, std::max(std::fabs(bounds[2 * k] - c), std::fabs(bounds[2 * k + 1] - c)));
-      for (size_t i = 0; i < (size_t)E * q; ++i) {
-        const double v = Xq_all[i * d + k];
-        if (k >= size || v < bounds[2 * k] || v > bounds[2 * k + 1]) ext = std::max(ext, std::fabs(v - c));
+    for (int kk = 0; kk < d; ++kk) {
+      const double c = gp.x_mean[kk];
+      double ext = gp.x_ext[kk];
+      if (kk < k.size) ext = std::max(ext, std::max(std::fabs(bounds[2 * kk] - c), std::fabs(bounds[2 * kk + 1] - c)));
+      for (size_t i = 0; i < (size_t)E * k.q; ++i) {
+        const double v = Xq_all[i * d + kk];
+        if (kk >= k.size || v < bounds[2 * kk] || v > bounds[2 * kk + 1]) ext = std::max(ext, std::fabs(v - c));
       }
-      for (int i = 0; i < p; ++i) ext = std::max(ext, std::fabs(Xp[(size_t)i * d + k] - c));
-      rad2 += (ext * gp.cp.inv_l[k]) * (ext * gp.cp.inv_l[k]);
+      for (int i = 0; i < k.p; ++i) ext = std::max(ext, std::fabs(Xp[(size_t)i * d + kk] - c));
+      rad2 += (ext * gp.cp.inv_l[kk]) * (ext * gp.cp.inv_l[kk]);
     }
-    wide_frame = !(rad2 <= (double)env_int("MOE_KG_DOT_MAX_RADIUS2", 10000));
+    wide_frame = !(rad2 <= max_radius2);
     far_frame = wide_frame;
     // d > 16: the coordinate table of the wave-per-sample kernel would take (dp + 1) 512 bytes per tile; that kernel is built
     // without it there, so these shapes take the same route as a wide frame
@@ -1364,19 +1421,18 @@ KgPending kg_launch(GpDev& gp, int num_fidelity, const moe_gd_params_t& gd, cons
   // 0.0249 ms per evaluation), hence the sample bound.  (The lane-parked kernel's MULTI-trial passes would be faster still -- 0.17 s --
   // but their dot-form distances move the end points of the reference's 100-step x 10-restart fixtures by up to 1.01e-6, beyond the
   // 1e-6 those fixtures are held to: not taken.)  `profiles/r05_z_*`.
-  const bool small_shape = ntiles <= env_int("MOE_KG_SMALL_TILES", 2) && dp <= env_int("MOE_KG_SMALL_DP", 4);
+  const bool small_shape = ntiles <= 2 && dp <= 4;
   // r6: decided from the evaluation's OWN sample count, not from the call's -- which kernel an evaluation takes never
   // depends on the batch or the rank it is evaluated in (the two kernels agree bit for bit on the tested shapes; the promise of
   // batch-independent bits no longer rests on that)
   // (a simplex inner domain: the lane-parked kernel at every sample count -- the 16-wavefront instantiation has no simplex update)
-  const bool small_lane = small_shape && env_int("MOE_KG_LANE", 1) != 0 &&
-                          (simplex || (long)num_local <= (long)env_int("MOE_KG_SMALL_LANE_MAX_SAMPLES", 1024));
+  const bool small_lane = small_shape && lane_on && (k.simplex || (long)num_local <= small_lane_max_samples);
   const int max_waves = (small_shape && !small_lane) ? 16 : 8;
   int waves = 0;
   if (tab_bytes + slab_bytes <= lds_max) waves = (int)std::min<size_t>(max_waves, (lds_max - tab_bytes) / slab_bytes);
   // (3 wavefronts per CU on the LDS table still beat the workgroup-per-sample kernel without derivative observations --
   //  n = 1500, d = 8: 2.1 vs 3.1 ms per evaluation; with 2 they lose -- n = 1700: 3.6 vs 3.4)
-  const int min_xlds_waves = env_int("MOE_KG_MIN_XLDS_WAVES", 4);  // (r2: 4 -- with 3 the streaming kernel and its 8 wavefronts win, n = 1500: 1.15 vs 1.44 ms)
+  const int min_xlds_waves = 4;  // (r2: 4 -- with 3 the streaming kernel and its 8 wavefronts win, n = 1500: 1.15 vs 1.44 ms)
   if (waves < min_xlds_waves || wide_frame) {  // coordinates stay in L2: more wavefronts per workgroup fit
     const int w2 = (int)std::min<size_t>(8, lds_max / slab_stream_bytes);
     if (w2 > waves || wide_frame) {  // (the instantiation without the LDS table is built for <= 8 wavefronts)
@@ -1399,7 +1455,7 @@ KgPending kg_launch(GpDev& gp, int num_fidelity, const moe_gd_params_t& gd, cons
       break;
     }
   }
-  if (!wide_dp) tr = env_int("MOE_KG_TR", tr);
+  if (!wide_dp && forced_tr) tr = *forced_tr;
   if (tr >= 0) num_lds_tiles = std::max(0, ntiles - bwaves * tr);
   int variant = (xlds && waves >= min_xlds_waves) ? 0 : (tr >= 0 ? 1 : 0);
   // Without derivative observations the wave-per-sample kernel streaming its coordinates from L2 now beats the workgroup-per-sample
@@ -1414,10 +1470,7 @@ KgPending kg_launch(GpDev& gp, int num_fidelity, const moe_gd_params_t& gd, cons
   // Variant 2, the streamed-weights wave-per-sample kernel (kg_mc.hpp kg_mc_stream_kernel), takes what would go to the
   // workgroup-per-sample kernel whenever the per-sample weight table (fantasy points and tile padding included) fits its cap and
   // every derivative slot is an observed derivative (a point's table rows ARE its weights)
-  const int prep_mode = env_int("MOE_KG_PREP", -1);
   const long v_stride_tiles = (long)ntiles * 64 * (1 + G);  // (the table of the streamed-weights kernel: 1 + G slots per point)
-  const double v_cap = std::getenv("MOE_KG_V_MAX_GB") ? (double)env_int("MOE_KG_V_MAX_GB", 4)
-                                                      : (weight_table_gb >= 0.0 ? weight_table_gb : 4.0);
   // (the size test is per EVALUATION: which kernel an evaluation takes must not depend on the batch it shares a call with -- the
   //  callers size their batches with kg_max_batch, which budgets every evaluation's table)
   // (r4: 8 and 12 observed derivatives and m > 64 too -- the kernel itself needs neither m nor beta once the sample pre-pass and the
@@ -1425,7 +1478,7 @@ KgPending kg_launch(GpDev& gp, int num_fidelity, const moe_gd_params_t& gd, cons
   // (r4: and any number of observed derivatives up to the slot count -- the table pads a point's weights to 1 + G)
   const bool stream_ok = prep_mode != 0 &&
                          8.0 * (double)v_stride_tiles * (double)num_local / 1e9 <= v_cap;
-  if (stream_ok && env_int("MOE_KG_STREAM_WEIGHTS", 1) != 0) {
+  if (stream_ok && stream_weights) {
     // (r3, ms of MC per evaluation, `profiles/r03_variant2_sweep.txt`: C5 7.9 -> 5.0; d = 12, g = 3, q = 8, M = 4000: n = 1200 1.24 -> 0.68 against the
     //  workgroup-per-sample kernel, n = 800 0.80 -> 0.48 against the wave-per-sample kernel streaming its coordinates with five weight
     //  slabs in LDS; without derivative observations it pays once fewer than five slabs fit: n = 6000, d = 8 5.79 -> 4.96, but n = 3000
@@ -1437,61 +1490,53 @@ KgPending kg_launch(GpDev& gp, int num_fidelity, const moe_gd_params_t& gd, cons
     //  slabs: 0.49 -> 0.33; but n = 400, d = 8, g = 2 on eight waves: 0.18 against 0.20 -- stays)
     else if (variant == 0 && xlds && G > 0 && (dp >= 12 || waves < 8)) variant = 2;
   }
-  {
-    const int forced = env_int("MOE_KG_VARIANT", variant);
-    if (forced == 2 && !stream_ok)
+  if (forced_variant) {
+    if (*forced_variant == 2 && !stream_ok)
       throw Error(MOE_ERR_RUNTIME, "the streamed-weights MC kernel needs the weight table within its cap");
     // (shapes the LDS-slab wave-per-sample kernel is not built for keep to the other two)
-    if (!(forced == 0 && (G > 4 || m > kMaxM))) variant = forced;
+    if (!(*forced_variant == 0 && (G > 4 || m > kMaxM))) variant = *forced_variant;
   }
   if (variant == 0 && waves < 1)
     throw Error(MOE_ERR_RUNTIME, "training set too large for the MC kernel (one sample's weights exceed LDS)");
-  const int num_cu = gp.num_cu;
   size_t shm = 0;
   int wg_per_cu = 1, wide_lds_tiles = 0;
   // r5: the lane-parked form of the LDS-table kernel (kg_mc_lane.hpp) wherever it holds as many wavefronts: its LDS also carries the
   // evaluation's record head [L | mu_disc | C_disc | disc] (the same for every evaluation of a call and every batch: the choice
   // depends on the evaluation's shape alone).  Same results bit for bit (MOE_KG_LANE=0: the frame line search of rounds 2-4).
   auto even = [](int v) { return (v + 1) & ~1; };
-  const int rec_head = even(m * m) + even(A) + even(A * m) + even(A * size);
+  const int rec_head = even(m * m) + even(A) + even(A * m) + even(A * k.size);
   bool lane_kernel = false;
-  if (variant == 0 && xlds && waves <= 8 && dp <= 16 && env_int("MOE_KG_LANE", 1) != 0) {
-    const size_t lane_fixed = kg_mc_lane_fixed_bytes(dp, rec_head);
-    const int wl = std::min(waves, env_int("MOE_KG_WAVES", waves));
-    lane_kernel = wl >= 1 && lane_fixed + tab_bytes + (size_t)wl * slab_bytes + pad_bytes <= (size_t)160 * 1024;
-  }
+  if (variant == 0 && xlds && waves <= 8 && dp <= 16 && lane_on)
+    lane_kernel = kg_mc_lane_fixed_bytes(dp, rec_head) + tab_bytes + (size_t)waves * slab_bytes + pad_bytes <= (size_t)160 * 1024;
   // the simplex update (simplex_limit) lives in the lane-parked line search (r6) and in line_search_lds -- the streamed-weights and the
   // workgroup-per-sample kernel; the frame line search of the other wave-per-sample instantiations has none
-  if (simplex && variant == 0 && !lane_kernel) variant = stream_ok ? 2 : 1;
+  if (k.simplex && variant == 0 && !lane_kernel) variant = stream_ok ? 2 : 1;
   if (variant == 1 && (tr < 0 || kg_mc_block_lds_bytes(dp, G, num_lds_tiles) > (size_t)160 * 1024))
     throw Error(MOE_ERR_RUNTIME, "point set too large for the workgroup-per-sample MC kernel");
   if (variant == 0) {
-    waves = std::max(1, std::min(waves, env_int("MOE_KG_WAVES", waves)));
     shm = (lane_kernel ? kg_mc_lane_fixed_bytes(dp, rec_head) : fixed_bytes) +
           (xlds ? tab_bytes + (size_t)waves * slab_bytes : (size_t)waves * slab_stream_bytes) + pad_bytes;
     wg_per_cu = std::max(1, std::min((int)((size_t)160 * 1024 / shm), (waves > 8 ? 16 : 8) / waves));
     if (mc::wide_eval(dp, xlds)) {  // what the slabs leave of a workgroup's share of LDS holds the leading tiles of the table (kg_mc.hpp WideEval)
       const size_t share = (size_t)160 * 1024 / wg_per_cu;
       wide_lds_tiles = (int)std::min<size_t>((size_t)ntiles, (share - shm) / (sizeof(double) * dp * 64));
-      wide_lds_tiles = std::max(0, std::min(wide_lds_tiles, env_int("MOE_KG_WIDE_LDS_TILES", wide_lds_tiles)));
       shm += sizeof(double) * (size_t)wide_lds_tiles * dp * 64;
     }
   } else if (variant == 2) {
-    waves = std::max(1, std::min(8, env_int("MOE_KG_WAVES", 8)));
+    waves = 8;
     shm = sizeof(double) * (kExpTabLen + (size_t)waves * mc::kWideScratch);
     wide_lds_tiles = (int)std::min<size_t>((size_t)ntiles, ((size_t)160 * 1024 - shm) / (sizeof(double) * dp * 64));
-    wide_lds_tiles = std::max(0, std::min(wide_lds_tiles, env_int("MOE_KG_WIDE_LDS_TILES", wide_lds_tiles)));
     shm += sizeof(double) * (size_t)wide_lds_tiles * dp * 64;
   } else {
     waves = bwaves;
   }
-  int blocks = num_cu * wg_per_cu;
+  int blocks = gp.num_cu * wg_per_cu;
   if (blocks >= E) blocks = (blocks / E) * E;  // the same number of workgroups for every evaluation
   // r5, wave-per-sample kernels: no more workgroups per evaluation than its samples need for the same number of rounds -- 128 samples
   // on 12 workgroups of 8 wavefronts are two rounds, and so they are on 8; the CUs left alone go to whatever else is running (the other
   // members of an MCMC ensemble: a suggestion at the headline GP size 0.574 -> 0.540 s; alone on the chip 0.0136 vs 0.0140 ms per
   // evaluation, `profiles/r05_blk_*`).  Which wavefront takes which sample never mattered to the result.
-  if (variant != 1 && blocks >= E && waves > 0 && env_int("MOE_KG_COMPACT_GRID", 1) != 0) {
+  if (variant != 1 && blocks >= E && waves > 0) {
     const long wpe = blocks / E, per_round = wpe * waves;
     const long rounds = (num_local + per_round - 1) / per_round;
     const long need = (num_local + rounds * waves - 1) / (rounds * waves);
@@ -1503,76 +1548,101 @@ KgPending kg_launch(GpDev& gp, int num_fidelity, const moe_gd_params_t& gd, cons
   // chip with them, too: 16 members x 20 evaluations x 8 workgroups were ten rounds of workgroups whose wavefronts drew two samples
   // each -- every workgroup ends on its slowest wavefront, a quarter of the kernel's time.  Four draws per wavefront there.
   if (ensemble_members_hint() > 1 && variant != 1 && blocks >= E && waves > 0) {
-    const long tickets = env_int("MOE_KG_ENS_TICKETS", 4);
-    const long k = std::max<long>(1, (num_local + tickets * waves - 1) / (tickets * waves));
-    blocks = (int)std::min<long>(blocks, k * E);
+    const long tickets = 4;
+    const long kb = std::max<long>(1, (num_local + tickets * waves - 1) / (tickets * waves));
+    blocks = (int)std::min<long>(blocks, kb * E);
   }
-  blocks = env_int("MOE_KG_BLOCKS", blocks);
 
-  const auto wall0 = std::chrono::steady_clock::now();
+  pl.G = G;
+  pl.ntiles = ntiles;
+  pl.variant = variant;
+  pl.xlds = xlds;
+  pl.far_frame = far_frame;
+  pl.wide_frame = wide_frame;
+  pl.small_lane = small_lane;
+  pl.lane_kernel = lane_kernel;
+  pl.waves = waves;
+  pl.blocks = blocks;
+  pl.shm = shm;
+  pl.tr = tr;
+  pl.num_lds_tiles = num_lds_tiles;
+  pl.wide_lds_tiles = wide_lds_tiles;
+  pl.pair_rows = (wide_dp || variant == 2 || (variant == 0 && mc::wide_eval(dp, xlds))) ? 1 : 0;
+  pl.rec_head = rec_head;
+  pl.multi_trial = (far_frame || small_lane) ? 0 : 1;
+  // r6: the small shapes on the lane-parked kernel take their Armijo trials several per sweep, too -- each trial computed exactly as
+  // a single-trial pass computes it (kg_mc.hpp eval_multi_exact: same bits as one trial per pass; MOE_KG_SMALL_MULTI=0: one per pass)
+  if (small_lane && !far_frame && variant == 0 && lane_kernel && dp == 4 && small_multi) pl.multi_trial = 2;
+  // the sample pre-pass (beta and the discretised-set winner of every sample, computed with the whole chip): for the
+  // workgroup-per-sample kernel, where seven wavefronts would wait for one; the wave-per-sample kernel hides those loads
+  // behind the other wavefront of its SIMD (measured: no difference at C3), so it only takes the pre-pass on request
+  // (MOE_KG_PREP=1; MOE_KG_PREP=0: never); more components than lanes need it (thread-per-sample pre-pass)
+  pl.prep = m > kMaxM || (prep_mode != 0 && (variant >= 1 || prep_mode == 1));
+  pl.v_stride = (variant == 2) ? v_stride_tiles : k.N;
+  pl.v_slots1 = (variant == 2) ? 1 + G : k.g1;
+  // the weight table: N doubles per sample (1.28 GB per evaluation at C5); beyond its cap the samples compute their weights in the
+  // kernel (workgroup-per-sample kernel only: the streamed-weights one is not chosen beyond the cap)
+  pl.weight_table = variant >= 1 && pl.prep && 8.0 * (double)pl.v_stride * (double)num_local / 1e9 <= v_cap;  // (per evaluation, as above)
+  if (variant == 2 && !(pl.weight_table && pl.prep))
+    throw Error(MOE_ERR_RUNTIME, "streamed-weights MC kernel selected without its weight table");
+  pl.chunk_len = tail_chunk_len(pl.fused_tail, m);
+  return pl;
+}
 
-  // ---- 1. state set-up for the whole batch ----
-  std::vector<double> U_all((size_t)E * u * d), extra_all((size_t)E * A * d), disc_all((size_t)E * A * size);
-  for (int e = 0; e < E; ++e) {
-    double* U = &U_all[(size_t)e * u * d];
-    const double* Xq = Xq_all + (size_t)e * q * d;
-    // union of points, discretised set = [Xu without fidelity dims ; discrete points]  (.cpp:246-261)
-    std::copy(Xq, Xq + (size_t)q * d, U);
-    if (p > 0) std::copy(Xp, Xp + (size_t)p * d, U + (size_t)q * d);
-    double* ds = &disc_all[(size_t)e * A * size];
-    // (disc_head: the state this evaluation runs on was BUILT at other points_to_sample and moved here with SetCurrentPoint,
-    //  which leaves the discretised set behind -- .cpp:232-243 vs 259-261; the reference's multistart drivers do that)
-    for (int i = 0; i < u; ++i) {
-      const double* src = (disc_head != nullptr && i < q) ? disc_head + (size_t)i * d : U + (size_t)i * d;
-      std::copy(src, src + size, ds + (size_t)i * size);
-    }
-    std::copy(discrete, discrete + (size_t)P * size, ds + (size_t)u * size);
-    double* ex = &extra_all[(size_t)e * A * d];
-    for (int j = 0; j < A; ++j) {
-      for (int k = 0; k < size; ++k) ex[(size_t)j * d + k] = ds[(size_t)j * size + k];
-      for (int k = size; k < d; ++k) ex[(size_t)j * d + k] = 1.0;
-    }
-  }
-  // ---- table-row order of the dimensions ----
+// table-row order of the dimensions: the GP's observed-derivative dimensions first (so derivative weight a multiplies row a), then
+// the remaining dimensions in ascending order; padded rows map to themselves (their lengths are 0).  Frame of the coordinate tables.
+TabParams table_rows(const GpDev& gp, const KgDims& k, int G, const double* Xq_all, const double* Xp, const double* disc_head) {
+  const int d = k.d;
   TabParams tp;
-  {
-    // table-row order: the GP's observed-derivative dimensions first (so derivative weight a multiplies row a), then
-    // the remaining dimensions in ascending order; padded rows map to themselves (their lengths are 0)
-    std::vector<int> order;
-    std::vector<bool> used(kMaxDimPadded, false);
-    for (int a = 0; a < g; ++a) {
-      if (used[gp.derivs.idx[a]]) throw Error(MOE_ERR_INVALID_VALUE, "duplicate derivative index", gp.derivs.idx[a], 0, 0);
-      order.push_back(gp.derivs.idx[a]);
-      used[gp.derivs.idx[a]] = true;
-    }
-    for (int k = 0; k < kMaxDimPadded; ++k)  // derivative dims are < d <= dp, so rows [0, dp) are a permutation of [0, dp)
-      if (!used[k]) order.push_back(k);
-    if (dp < G) throw Error(MOE_ERR_RUNTIME, "padded dimension smaller than the derivative-slot count");
-    for (int r = 0; r < kMaxDimPadded; ++r) {
-      tp.perm[r] = order[r];
-      // frame scale: the Matern kernel's sqrt(5) is folded into it (kg_mc.hpp radial3)
-      tp.inv_lp[r] = gp.cp.inv_l[order[r]] * (gp.cp.type == MOE_COV_MATERN_NU_2P5 ? 2.236067977499789696409173668731276235 : 1.0);
-      const double c = (order[r] < d) ? gp.x_mean[order[r]] : 0.0;  // training-set mean of the row's coordinate (0 for pad rows)
-      tp.center[r] = c;
-      // the MC kernels' exponent arithmetic covers |x - c| / l up to kTableExtent for every tabulated point
-      if (order[r] < d) {
-        const int k = order[r];
-        double ext = gp.x_ext[k];
-        for (int e = 0; e < E; ++e) {
-          for (int i = 0; i < q; ++i) ext = std::max(ext, std::fabs(Xq_all[((size_t)e * q + i) * d + k] - c));
-        }
-        for (int i = 0; i < p; ++i) ext = std::max(ext, std::fabs(Xp[(size_t)i * d + k] - c));
-        if (disc_head != nullptr)
-          for (int i = 0; i < q; ++i) ext = std::max(ext, std::fabs(disc_head[(size_t)i * d + k] - c));
-        if (!(ext * tp.inv_lp[r] <= mc::kTableExtent))
-          throw Error(MOE_ERR_BOUNDS, "length scale too small for the extent of the points (|x - mean| / length > 1e5)",
-                      ext * tp.inv_lp[r], 0.0, mc::kTableExtent);
+  std::vector<int> order;
+  std::vector<bool> used(kMaxDimPadded, false);
+  for (int a = 0; a < k.g; ++a) {
+    if (used[gp.derivs.idx[a]]) throw Error(MOE_ERR_INVALID_VALUE, "duplicate derivative index", gp.derivs.idx[a], 0, 0);
+    order.push_back(gp.derivs.idx[a]);
+    used[gp.derivs.idx[a]] = true;
+  }
+  for (int r = 0; r < kMaxDimPadded; ++r)  // derivative dims are < d <= dp, so rows [0, dp) are a permutation of [0, dp)
+    if (!used[r]) order.push_back(r);
+  if (k.dp < G) throw Error(MOE_ERR_RUNTIME, "padded dimension smaller than the derivative-slot count");
+  for (int r = 0; r < kMaxDimPadded; ++r) {
+    tp.perm[r] = order[r];
+    // frame scale: the Matern kernel's sqrt(5) is folded into it (kg_mc.hpp radial3)
+    tp.inv_lp[r] = gp.cp.inv_l[order[r]] * (gp.cp.type == MOE_COV_MATERN_NU_2P5 ? 2.236067977499789696409173668731276235 : 1.0);
+    const double c = (order[r] < d) ? gp.x_mean[order[r]] : 0.0;  // training-set mean of the row's coordinate (0 for pad rows)
+    tp.center[r] = c;
+    // the MC kernels' exponent arithmetic covers |x - c| / l up to kTableExtent for every tabulated point
+    if (order[r] < d) {
+      const int kk = order[r];
+      double ext = gp.x_ext[kk];
+      for (int e = 0; e < k.E; ++e) {
+        for (int i = 0; i < k.q; ++i) ext = std::max(ext, std::fabs(Xq_all[((size_t)e * k.q + i) * d + kk] - c));
       }
+      for (int i = 0; i < k.p; ++i) ext = std::max(ext, std::fabs(Xp[(size_t)i * d + kk] - c));
+      if (disc_head != nullptr)
+        for (int i = 0; i < k.q; ++i) ext = std::max(ext, std::fabs(disc_head[(size_t)i * d + kk] - c));
+      if (!(ext * tp.inv_lp[r] <= mc::kTableExtent))
+        throw Error(MOE_ERR_BOUNDS, "length scale too small for the extent of the points (|x - mean| / length > 1e5)",
+                    ext * tp.inv_lp[r], 0.0, mc::kTableExtent);
     }
   }
-  // ---- per-evaluation records: the host fills what it knows (discretised set, padded union points); mu, the factor of
-  // Var + noise, the discretised set's mu_n / c_j and the best posterior mean are written by kg_state_kernel ----
+  return tp;
+}
+
+// The per-evaluation records in the host-side assembly area gp.hKgIn (it travels inside the state set-up's staging buffer): the host
+// fills what it knows (discretised set, padded union points); mu, the factor of Var + noise, the discretised set's mu_n / c_j and the
+// best posterior mean are written by kg_state_kernel.  Behind the records: [2 kMaxDimPadded] bounds | [kMaxDimPadded] frame centre |
+// [kMaxDimPadded] frame scale, table-row order (the MC kernels read them one row per lane).
+struct KgRecords {
   KgRec rec;
+  int rec_bp = 0;              // offset of the best posterior mean
+  size_t blob_size = 0, o_bounds = 0;
+  unsigned int free_mask = 0;  // table-row order: the rows the inner optimisations move
+};
+KgRecords fill_records(GpDev& gp, const KgDims& k, const McPlan& pl, const TabParams& tp, const double* bounds,
+                       const std::vector<double>& U_all, const std::vector<double>& disc_all) {
+  const int m = k.m, A = k.A, size = k.size, d = k.d, dp = k.dp;
+  KgRecords R;
+  KgRec& rec = R.rec;
   int off = 0;
   auto take = [&](int cnt) {
     const int o = off;
@@ -1583,31 +1653,27 @@ KgPending kg_launch(GpDev& gp, int num_fidelity, const moe_gd_params_t& gd, cons
   rec.mu_disc = take(A);
   rec.C_disc = take(A * m);
   rec.disc = take(A * size);
-  if (off != rec_head) throw Error(MOE_ERR_RUNTIME, "record head layout mismatch (lane-parked MC kernel)");
-  rec.XuP = take(u * dp);
-  const int rec_bp = take(1);
+  if (off != pl.rec_head) throw Error(MOE_ERR_RUNTIME, "record head layout mismatch (lane-parked MC kernel)");
+  rec.XuP = take(k.u * dp);
+  R.rec_bp = take(1);
   rec.Mk = 0;
   rec.stride = off;
-  // behind the records: [2 kMaxDimPadded] bounds | [kMaxDimPadded] frame centre | [kMaxDimPadded] frame scale, table-row order
-  // (the MC kernels read them one row per lane)
-  const size_t blob_size = (size_t)rec.stride * E + 4 * kMaxDimPadded;
-  const size_t o_bounds = (size_t)rec.stride * E;
-  const long num_norm = (long)((num_mc + 1) / 2) * m;
-  gp.hKgIn.reserve(blob_size);  // (host-side assembly area; it travels inside the state set-up's staging buffer)
+  R.blob_size = (size_t)rec.stride * k.E + 4 * kMaxDimPadded;
+  R.o_bounds = (size_t)rec.stride * k.E;
+  gp.hKgIn.reserve(R.blob_size);
   double* blob = gp.hKgIn.p;
-  std::memset(blob, 0, sizeof(double) * blob_size);
-  unsigned int free_mask = 0;  // table-row order: bounds of row r = bounds of original dimension perm[r]
+  std::memset(blob, 0, sizeof(double) * R.blob_size);
   // (simplex inner domain, SimplexIntersectTensorProductDomain's constructor, gpp_domain.cpp:107-141: the box clipped to the unit
   //  hypercube; an empty intersection is the reference's BoundsException)
   std::vector<double> box(bounds, bounds + 2 * (size_t)size);
-  if (simplex) {
+  if (k.simplex) {
     double corner_sum = 0.0;
     bool empty = false;
-    for (int k = 0; k < size; ++k) {
-      box[2 * k] = std::fmax(bounds[2 * k], 0.0);
-      box[2 * k + 1] = std::fmin(bounds[2 * k + 1], 1.0);
-      empty = empty || box[2 * k] > box[2 * k + 1];
-      corner_sum += box[2 * k];
+    for (int kk = 0; kk < size; ++kk) {
+      box[2 * kk] = std::fmax(bounds[2 * kk], 0.0);
+      box[2 * kk + 1] = std::fmin(bounds[2 * kk + 1], 1.0);
+      empty = empty || box[2 * kk] > box[2 * kk + 1];
+      corner_sum += box[2 * kk];
     }
     if (corner_sum >= 1.0 || empty)
       throw Error(MOE_ERR_BOUNDS,
@@ -1615,67 +1681,47 @@ KgPending kg_launch(GpDev& gp, int num_fidelity, const moe_gd_params_t& gd, cons
                   "boxes do not intersect.",
                   corner_sum, 0.0, 1.0);
   }
-  for (int r = 0; r < kMaxDimPadded; ++r) {
-    const int k = tp.perm[r];
-    if (k < size) {
-      blob[o_bounds + 2 * r] = box[2 * k];
-      blob[o_bounds + 2 * r + 1] = box[2 * k + 1];
-      free_mask |= 1u << r;
+  for (int r = 0; r < kMaxDimPadded; ++r) {  // bounds of row r = bounds of original dimension perm[r]
+    const int kk = tp.perm[r];
+    if (kk < size) {
+      blob[R.o_bounds + 2 * r] = box[2 * kk];
+      blob[R.o_bounds + 2 * r + 1] = box[2 * kk + 1];
+      R.free_mask |= 1u << r;
     }
-    blob[o_bounds + 2 * kMaxDimPadded + r] = tp.center[r];
-    blob[o_bounds + 3 * kMaxDimPadded + r] = tp.inv_lp[r];
+    blob[R.o_bounds + 2 * kMaxDimPadded + r] = tp.center[r];
+    blob[R.o_bounds + 3 * kMaxDimPadded + r] = tp.inv_lp[r];
   }
-  for (int e = 0; e < E; ++e) {
-    const double* U = &U_all[(size_t)e * u * d];
+  for (int e = 0; e < k.E; ++e) {
+    const double* U = &U_all[(size_t)e * k.u * d];
     double* r = &blob[(size_t)rec.stride * e];
     std::copy(&disc_all[(size_t)e * A * size], &disc_all[(size_t)(e + 1) * A * size], r + rec.disc);
-    for (int i = 0; i < u; ++i)
-      for (int k = 0; k < d; ++k) r[rec.XuP + (size_t)i * dp + k] = U[(size_t)i * d + k];
+    for (int i = 0; i < k.u; ++i)
+      for (int kk = 0; kk < d; ++kk) r[rec.XuP + (size_t)i * dp + kk] = U[(size_t)i * d + kk];
   }
+  return R;
+}
 
-  DerivList none;
-  none.g = 0;
-  for (int i = 0; i < kMaxDerivs; ++i) none.idx[i] = 0;
-  auto timers = std::make_shared<std::array<EventTimer, 4>>();
-  EventTimer &t_mc = (*timers)[0], &t_cov = (*timers)[1], &t_tail = (*timers)[2], &t_state = (*timers)[3];
-  t_state.start(s);
-  // everything N-sized of the state, left on the device (gp.hip): no wait, no download -- the m x m algebra follows as kernels.
-  // The records and the normal draws ride down in the same host->device copy as the points (r4: one copy per call instead of three).
-  StateAppendix apx;
-  apx.doubles = blob_size + (size_t)num_norm;
-  apx.fill = [&](double* dst) {
-    std::memcpy(dst, blob, sizeof(double) * blob_size);
-    std::memcpy(dst + blob_size, normals, sizeof(double) * num_norm);
-  };
-  const KgStateEnqueued se = enqueue_kg_state_batch(gp, U_all.data(), u, want_grad ? q : 0, extra_all.data(), A, E, &apx);
-  const BatchLayout& bl = se.bl;
-  double* dBlobP = const_cast<double*>(gp.dAppendix);  // (kg_state_kernel completes the records in place)
-  const double* dNormalsP = gp.dAppendix + blob_size;
-
-  // ---- device buffers ----
-  DevBuf<double>&dTab = gp.kTab, &dBestPoint = gp.kBestPoint, &dBestValue = gp.kBestValue, &dBeta = gp.kBeta, &dT = gp.kT, &dC = gp.kC,
-  &dTB = gp.kTB, &dOut = gp.kOut;
-  DevBuf<unsigned long long>& dCounters = gp.kCounters;
-  // ---- the m x m algebra of the state, on the device (kg_state.hip) ----
-  const int qd = q * d;
-  const int tri = m * (m + 1) / 2;
-  gp.kStateI.reserve((size_t)2 * E);
-  gp.kStateD.reserve((size_t)E * qd * (1 + (want_grad ? tri : 0)) + (size_t)E * (1 + qd + 3) + (size_t)E * tri);
+// the m x m algebra of the state, on the device (kg_state.hip): launched behind the state set-up, completing the records in place
+KgStateParams launch_state_algebra(GpDev& gp, const KgDims& k, const KgStateEnqueued& se, const KgRecords& R, double* dBlobP,
+                                   double best_so_far, hipStream_t s) {
+  const int m = k.m, tri = m * (m + 1) / 2;
+  gp.kStateI.reserve((size_t)2 * k.E);
+  gp.kStateD.reserve((size_t)k.E * k.qd * (1 + (k.want_grad ? tri : 0)) + (size_t)k.E * (1 + k.qd + 3) + (size_t)k.E * tri);
   KgStateParams sp;
   sp.cp = gp.cp;
   sp.derivs = gp.derivs;
-  for (int b = 0; b <= kMaxDerivs; ++b) sp.noise[b] = (b < g1) ? gp.noise[b] : 0.0;
+  for (int b = 0; b <= kMaxDerivs; ++b) sp.noise[b] = (b < k.g1) ? gp.noise[b] : 0.0;
   sp.mean = gp.mean;
   sp.best_so_far = best_so_far;
-  sp.E = E;
-  sp.u = u;
-  sp.q = q;
+  sp.E = k.E;
+  sp.u = k.u;
+  sp.q = k.q;
   sp.m = m;
-  sp.g = g;
-  sp.d = d;
-  sp.dp = dp;
-  sp.A = A;
-  sp.ng = ngrad;
+  sp.g = k.g;
+  sp.d = k.d;
+  sp.dp = k.dp;
+  sp.A = k.A;
+  sp.ng = k.ngrad;
   sp.gkk = se.gkk;
   sp.gx = se.gx;
   sp.gkk_slices = se.gkk_slices;
@@ -1684,87 +1730,57 @@ KgPending kg_launch(GpDev& gp, int num_fidelity, const moe_gd_params_t& gd, cons
   sp.U = se.U;
   sp.extra = se.extra;
   sp.blob = dBlobP;
-  sp.rec_stride = rec.stride;
-  sp.rec_L = rec.L;
-  sp.rec_mu_disc = rec.mu_disc;
-  sp.rec_C_disc = rec.C_disc;
-  sp.rec_bp = rec_bp;
+  sp.rec_stride = R.rec.stride;
+  sp.rec_L = R.rec.L;
+  sp.rec_mu_disc = R.rec.mu_disc;
+  sp.rec_C_disc = R.rec.C_disc;
+  sp.rec_bp = R.rec_bp;
   sp.flags = gp.kStateI.p;
-  sp.winner = gp.kStateI.p + E;
+  sp.winner = gp.kStateI.p + k.E;
   sp.gmu = gp.kStateD.p;
-  sp.dL = gp.kStateD.p + (size_t)E * qd;
-  double* dFin = gp.kStateD.p + (size_t)E * qd * (1 + (want_grad ? tri : 0));
+  sp.dL = gp.kStateD.p + (size_t)k.E * k.qd;
   launch_kg_state(sp, s);
-  if (want_grad) launch_kg_dchol(sp, s);
-  const long tab_stride = (long)ntiles * dp * 64;
-  dTab.reserve((size_t)tab_stride * E + (size_t)dp * 64);  // + one tile: eval_loop's last prefetch reads past the end
-  dBestPoint.reserve((size_t)E * num_local * dp);
-  dBestValue.reserve((size_t)E * num_local);
-  dBeta.reserve((size_t)E * num_local * m + 64);  // + a zeroed pad: kg_sample_weights_kernel reads whole 16/32/64-blocks
-  // [2 E] pass counters | [E] sample-ticket counters, one 128-byte line each (kTicketStride unsigned ints)
-  const size_t n_ctr = (size_t)2 * E + (size_t)E * (kTicketStride / 2) + 32;  // (+16 alignment slack, +16 profiling words)
-  dCounters.reserve(n_ctr);
-  const int out_stride = 1 + m * m + 2 * ngrad;
-  dOut.reserve((size_t)out_stride * E);
-  // q-KG fast path: the N x M covariance matrix of the tail is never materialised (see launch_fused_tail)
-  const bool fused_tail = want_grad && g == 0 && m <= 8 && env_int("MOE_KG_FUSED_TAIL", 1) != 0;
-  const int chunk_len = fused_tail ? kFusedChunk : (m > 64 ? kTbChunkWide : kTbChunk);
-  const int chunks = (num_local + chunk_len - 1) / chunk_len;
-  if (want_grad) {
-    if (!fused_tail) dT.reserve((size_t)N * E * num_local);
-    dC.reserve((size_t)E * num_local * m);
-    dTB.reserve((size_t)E * (chunks + 1) * m * N + (size_t)E * ngrad * kDirSlices);  // chunk partials + their sum + DIR partials
-  }
+  if (k.want_grad) launch_kg_dchol(sp, s);
+  return sp;
+}
 
-  // ---- coordinate tables ----
-  {
-    dim3 grid((unsigned)((tab_stride + 255) / 256), E);
-    const double *dXp = gp.dX.p, *dUnionP = gp.dUnion;
-    double* dTabP = dTab.p;
-    unsigned long long* dCtrP = dCounters.p;
-    const int pair_rows = (wide_dp || variant == 2 || (variant == 0 && mc::wide_eval(dp, xlds))) ? 1 : 0;
-    launch_kernel_ens<build_xs_tab_kernel_body, 256>(build_xs_tab_kernel, grid, dim3(256), 0, s, dXp, n, dUnionP, u, dp, ntiles, tp, dTabP, tab_stride,
-                                                     pair_rows, dCtrP, (long)n_ctr);
-    MOE_HIP_CHECK(hipGetLastError());
-  }
-  t_state.stop(s);
-
-  // ---- 2. MC kernel ----
+// The MC step: its parameters, the sample pre-pass and the weight table where the plan has them, the MC kernel.
+KgMcParams launch_mc_step(GpDev& gp, const KgDims& k, const McPlan& pl, const moe_gd_params_t& gd, const TabParams& tp,
+                          const KgRecords& R, double* dBlobP, const double* dNormalsP, const BatchLayout& bl, long tab_stride,
+                          size_t n_ctr, EventTimer& t_mc, hipStream_t s) {
+  const int E = k.E, N = k.N, m = k.m, dp = k.dp, num_local = k.num_local;
   KgMcParams mp;
   mp.cov_type = gp.cp.type;
-  mp.dim = d;
+  mp.dim = k.d;
   mp.alpha = gp.cp.alpha;
   for (int r = 0; r < kMaxDimPadded; ++r) {
     mp.inv_lp[r] = tp.inv_lp[r];
     mp.perm[r] = tp.perm[r];
     mp.center[r] = tp.center[r];
   }
-  mp.n = n;
-  mp.g = g;
+  mp.n = k.n;
+  mp.g = k.g;
   mp.N = N;
-  mp.u = u;
+  mp.u = k.u;
   mp.m = m;
-  mp.f = f;
-  mp.A = A;
-  mp.ntiles = ntiles;
+  mp.f = k.f;
+  mp.A = k.A;
+  mp.ntiles = pl.ntiles;
   mp.E = E;
   mp.mean = gp.mean;
-  mp.multi_trial = (far_frame || small_lane) ? 0 : env_int("MOE_KG_MULTI_TRIAL", 1);  // (0: A/B runs)
-  // r6: the small shapes on the lane-parked kernel take their Armijo trials several per sweep, too -- each trial computed exactly as
-  // a single-trial pass computes it (kg_mc.hpp eval_multi_exact: same bits as one trial per pass; MOE_KG_SMALL_MULTI=0: one per pass)
-  if (small_lane && !far_frame && variant == 0 && lane_kernel && dp == 4 && env_int("MOE_KG_SMALL_MULTI", 1) != 0) mp.multi_trial = 2;
-  mp.XsTab = dTab.p;
+  mp.multi_trial = pl.multi_trial;
+  mp.XsTab = gp.kTab.p;
   mp.tab_stride = tab_stride;
-  mp.wide_lds_tiles = wide_lds_tiles;
+  mp.wide_lds_tiles = pl.wide_lds_tiles;
   mp.KinvY = gp.dKinvY.p;
   mp.W = gp.dWE.p + bl.col_kstar0(0) * N;
   mp.w_stride = (long)m * N;
   mp.blob = dBlobP;
-  mp.rec = rec;
-  mp.bounds = dBlobP + o_bounds;
-  mp.free_mask = free_mask;
+  mp.rec = R.rec;
+  mp.bounds = dBlobP + R.o_bounds;
+  mp.free_mask = R.free_mask;
   mp.normals = dNormalsP;
-  mp.first_sample = first_sample;
+  mp.first_sample = k.first_sample;
   mp.num_local = num_local;
   mp.max_num_steps = gd.max_num_steps;
   mp.max_num_restarts = gd.max_num_restarts;
@@ -1772,124 +1788,112 @@ KgPending kg_launch(GpDev& gp, int num_fidelity, const moe_gd_params_t& gd, cons
   mp.pre_mult = gd.pre_mult;
   mp.max_relative_change = gd.max_relative_change;
   // (gpp_domain.cpp:245-247: the simplex update never lands precisely on a wall -- kRelativeChangeEpsilonTweak)
-  if (simplex && mp.max_relative_change == 1.0) mp.max_relative_change -= 4.0 * 2.220446049250313e-16;
-  mp.simplex = simplex ? 1 : 0;
-  mp.inv_sqrt_size = 1.0 / std::sqrt((double)size);
+  if (k.simplex && mp.max_relative_change == 1.0) mp.max_relative_change -= 4.0 * 2.220446049250313e-16;
+  mp.simplex = k.simplex ? 1 : 0;
+  mp.inv_sqrt_size = 1.0 / std::sqrt((double)k.size);
   for (int r = 0; r < kMaxDimPadded; ++r) mp.inv_perm[r] = 0;
   for (int r = 0; r < kMaxDimPadded; ++r)
     if (tp.perm[r] >= 0 && tp.perm[r] < kMaxDimPadded) mp.inv_perm[tp.perm[r]] = r;
   mp.tolerance = gd.tolerance;
-  mp.best_point = dBestPoint.p;
-  mp.best_value = dBestValue.p;
-  mp.beta = dBeta.p;
-  mp.counters = dCounters.p;
-  mp.next_sample = reinterpret_cast<unsigned int*>(dCounters.p + (((size_t)2 * E + 15) / 16) * 16);  // 128-byte aligned
-  mp.prof = dCounters.p + n_ctr - 16;
+  mp.best_point = gp.kBestPoint.p;
+  mp.best_value = gp.kBestValue.p;
+  mp.beta = gp.kBeta.p;
+  mp.counters = gp.kCounters.p;
+  mp.next_sample = reinterpret_cast<unsigned int*>(gp.kCounters.p + (((size_t)2 * E + 15) / 16) * 16);  // 128-byte aligned
+  mp.prof = gp.kCounters.p + n_ctr - 16;
   t_mc.start(s);
   mp.best_j = nullptr;
   mp.V = nullptr;
-  // the sample pre-pass (beta and the discretised-set winner of every sample, computed with the whole chip): for the
-  // workgroup-per-sample kernel, where seven wavefronts would wait for one; the wave-per-sample kernel hides those loads
-  // behind the other wavefront of its SIMD (measured: no difference at C3), so it only takes the pre-pass on request
-  // (MOE_KG_PREP=1; MOE_KG_PREP=0: never)
-  if (m > kMaxM || (prep_mode != 0 && (variant >= 1 || prep_mode == 1))) {
-    gp.kBestJ.reserve((size_t)E * num_local);
+  const long total = (long)E * num_local;
+  if (pl.prep) {
+    gp.kBestJ.reserve((size_t)total);
     mp.best_j = gp.kBestJ.p;
-    const long total = (long)E * num_local;
     int* best_j_p = gp.kBestJ.p;
     if (m > kMaxM) {  // more components than lanes: thread-per-sample pre-pass (mandatory there)
       launch_kernel_ens<kg_sample_prep_generic_kernel_body, 64>(kg_sample_prep_generic_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, s, mp, best_j_p);
     } else {
-      const int pb = (int)std::min<long>((total + 3) / 4, (long)num_cu * 8);
+      const int pb = (int)std::min<long>((total + 3) / 4, (long)gp.num_cu * 8);
       launch_kernel_ens<kg_sample_prep_kernel_body, 256>(kg_sample_prep_kernel, dim3(pb), dim3(256), 0, s, mp, best_j_p);
     }
     MOE_HIP_CHECK(hipGetLastError());
   }
-  mp.v_stride = (variant == 2) ? v_stride_tiles : N;
-  mp.v_slots1 = (variant == 2) ? 1 + G : g1;
-  if (variant >= 1 && mp.best_j != nullptr) {
-    const long total = (long)E * num_local;
-    // the weight table: N doubles per sample (1.28 GB per evaluation at C5); beyond its cap -- the caller's share of the
-    // workspace budget (kg_evaluate_batch, kg_mcmc_sums), MOE_KG_V_MAX_GB (default 4) for a bare kg_launch -- the samples
-    // compute their weights in the kernel (workgroup-per-sample kernel only: the streamed-weights one is not chosen beyond the cap)
-    const double v_gb = 8.0 * (double)mp.v_stride * (double)num_local / 1e9;  // (per evaluation, as above)
-    if (v_gb <= v_cap) {  // (m > 64: the table kernel takes the columns of W 64 at a time, r4)
-      gp.kV.reserve((size_t)mp.v_stride * (size_t)total + (size_t)64 * mp.v_slots1);  // (+ one tile: the sweeps prefetch one tile ahead)
-      memset_async(dBeta.p + (size_t)total * m, 0, sizeof(double) * 64, s);
-      mp.V = gp.kV.p;
-      launch_sample_weights(mp, gp.kV.p, s, variant == 2);
-    }
+  mp.v_stride = pl.v_stride;
+  mp.v_slots1 = pl.v_slots1;
+  if (pl.weight_table) {  // (m > 64: the table kernel takes the columns of W 64 at a time, r4)
+    gp.kV.reserve((size_t)mp.v_stride * (size_t)total + (size_t)64 * mp.v_slots1);  // (+ one tile: the sweeps prefetch one tile ahead)
+    memset_async(gp.kBeta.p + (size_t)total * m, 0, sizeof(double) * 64, s);
+    mp.V = gp.kV.p;
+    launch_sample_weights(mp, gp.kV.p, s, pl.variant == 2);
   }
-  if (variant == 2 && (mp.V == nullptr || mp.best_j == nullptr))
-    throw Error(MOE_ERR_RUNTIME, "streamed-weights MC kernel selected without its weight table");
-  if (variant == 0 && lane_kernel)
-    launch_mc_lane(mp, dp, G, rec_head, blocks, waves, shm, s);
-  else if (variant == 0)
-    launch_mc(mp, dp, G, xlds, blocks, waves, shm, s);
-  else if (variant == 2)
-    launch_mc_stream(mp, dp, G, blocks, waves, shm, s);
+  if (pl.variant == 0 && pl.lane_kernel)
+    launch_mc_lane(mp, dp, pl.G, pl.rec_head, pl.blocks, pl.waves, pl.shm, s);
+  else if (pl.variant == 0)
+    launch_mc(mp, dp, pl.G, pl.xlds, pl.blocks, pl.waves, pl.shm, s);
+  else if (pl.variant == 2)
+    launch_mc_stream(mp, dp, pl.G, pl.blocks, pl.waves, pl.shm, s);
   else
-    launch_mc_block(mp, dp, G, tr, num_lds_tiles, blocks, waves, s);
+    launch_mc_block(mp, dp, pl.G, pl.tr, pl.num_lds_tiles, pl.blocks, pl.waves, s);
   t_mc.stop(s);
-  {
-    // (bits 1 / 2 of the second word, r4: the frame-extent decisions -- a domain box or point set wider than 100 length scales
-    //  silently costs the LDS-table kernel and the multi-trial passes; this is where a caller can see it)
-    const int info[8] = {variant, ((variant == 0 && xlds) ? 1 : 0) | (far_frame ? 2 : 0) | (wide_frame ? 4 : 0) | (lane_kernel ? 8 : 0), waves, variant == 1 ? tr : wide_lds_tiles, mp.V != nullptr ? 1 : 0, 0, blocks,
-                         mp.best_j != nullptr ? 1 : 0};
-    std::copy(info, info + 8, gp.last_info);
-  }
+  return mp;
+}
 
-  // ---- 3. gradient tail ----
+// The gradient tail (T-free for q-KG, else through the materialised N x M covariance matrix T), or the sum of the samples' values.
+KgTailParams launch_tail_step(GpDev& gp, const KgDims& k, const McPlan& pl, const KgMcParams& mp, const KgRecords& R,
+                              double* dBlobP, const double* dNormalsP, const BatchLayout& bl, double* dFin, int out_stride,
+                              EventTimer& t_cov, EventTimer& t_tail, hipStream_t s) {
+  const int E = k.E, N = k.N, n = k.n, m = k.m, num_local = k.num_local;
   KgTailParams tl;
   tl.cp = gp.cp;
   tl.derivs = gp.derivs;
-  tl.u = u;
-  tl.q = q;
+  tl.u = k.u;
+  tl.q = k.q;
   tl.m = m;
-  tl.g = g;
+  tl.g = k.g;
   tl.N = N;
   tl.E = E;
   tl.num_local = num_local;
-  tl.first_sample = first_sample;
-  tl.ngrad = ngrad;
-  tl.chunks = chunks;
-  tl.chunk_len = chunk_len;
+  tl.first_sample = k.first_sample;
+  tl.ngrad = k.ngrad;
+  tl.chunks = (num_local + pl.chunk_len - 1) / pl.chunk_len;
+  tl.chunk_len = pl.chunk_len;
   tl.sw_chunk = ((long)E * num_local / kSwChunk >= 1024) ? kSwChunk : 16;
-  tl.T = dT.p;
+  tl.T = gp.kT.p;
   tl.SW = nullptr;
   tl.W = mp.W;
   tl.w_stride = mp.w_stride;
   tl.Gm = gp.dE.p + bl.col_grad0(0) * N;  // dK*/dXq itself: K^-1 goes onto the m columns of TB instead (launch_gtb)
-  tl.g_stride = (long)ngrad * N;
+  tl.g_stride = (long)k.ngrad * N;
   tl.Linv = gp.dLinv.p;
   tl.ldL = gp.ldL;
   tl.tri_work = gp.dEK.p;  // (reserved by enqueue_kg_state_batch; the state's own use of it is behind us in stream order)
   tl.work = gp.dVE.p;  // [2][N x E m]: enqueue_kg_state_batch reserves it; V = L^-1 K* is not needed any more
   tl.blob = dBlobP;
-  tl.rec = rec;
-  tl.rec_bp = rec_bp;
-  tl.best_point = dBestPoint.p;
-  tl.best_value = dBestValue.p;
-  tl.beta = dBeta.p;
+  tl.rec = R.rec;
+  tl.rec_bp = R.rec_bp;
+  tl.best_point = gp.kBestPoint.p;
+  tl.best_value = gp.kBestValue.p;
+  tl.beta = gp.kBeta.p;
   tl.normals = dNormalsP;
-  tl.C = dC.p;
-  tl.TBpart = dTB.p;
-  tl.out = dOut.p;
+  tl.C = gp.kC.p;
+  tl.TBpart = gp.kTB.p;
+  tl.out = gp.kOut.p;
   tl.out_stride = out_stride;
-  gp.last_info[5] = fused_tail ? 1 : 0;
-  if (fused_tail) {
+  if (pl.fused_tail) {
     t_cov.start(s);
     t_cov.stop(s);  // no covariance matrix is built on this path
     t_tail.start(s);
-    const int slices = fused_tail_slices(E, num_local, n, num_cu, m, dp);
+    const int slices = fused_tail_slices(E, num_local, n, gp.num_cu, m, k.dp);
     gp.kSW.reserve((size_t)E * num_local * slices * 8);  // [E][num_local][slices][MU <= 8]
     launch_fused_tail(tl, gp.dX.p, n, gp.kSW.p, slices, s);
     // (r4: m > 64 too -- one workgroup per entry of ZC walking every sample with a stride of m doubles took 1.8 ms per evaluation at m = 104)
     gp.kZcPart.reserve((size_t)E * ((num_local + zc_chunk_len(m) - 1) / zc_chunk_len(m)) * m * m);
     launch_zc(tl, gp.kZcPart.p, s, !zc_sum_in_finish(m, num_local));
-  } else if (want_grad) {
+  } else if (k.want_grad) {
+    DerivList none;
+    none.g = 0;
+    for (int i = 0; i < kMaxDerivs; ++i) none.idx[i] = 0;
     t_cov.start(s);
-    launch_cov_build(gp.cp, gp.dX.p, n, gp.derivs, dBestPoint.p, E * num_local, none, nullptr, dT.p, N, 0, s, true);
+    launch_cov_build(gp.cp, gp.dX.p, n, gp.derivs, gp.kBestPoint.p, E * num_local, none, nullptr, gp.kT.p, N, 0, s, true);
     t_cov.stop(s);
     t_tail.start(s);
     if (m > 8 || (size_t)N * m * sizeof(double) > 96 * 1024) {
@@ -1901,17 +1905,15 @@ KgPending kg_launch(GpDev& gp, int num_fidelity, const moe_gd_params_t& gd, cons
       // 63 workgroups walking 125 dependent stages, eight times per call).  The slice count is a function of (m, N) alone.
       const int sw_slices = N >= 1024 ? 8 : (N >= 256 ? 4 : 1);  // (m > 64 too: the stretch point's 104 x 20 000 over N = 26 000 walked 1625 stages unsplit)
       if (sw_slices > 1) gp.kSWpart.reserve((size_t)sw_slices * m * num_local * E);
-      if (m > 64 && sw_slices > 1) {  // (T is set in `tl` below: the kernel takes W / T / strides from it)
-        KgTailParams tq = tl;
-        tq.T = dT.p;
+      if (m > 64 && sw_slices > 1) {  // (the kernel takes W / T / strides from `tl`)
         MOE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kg_sw128_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                           (int)g128::kSmemBytes));
         double* sw_part_p = gp.kSWpart.p;
-        launch_kernel_ens<kg_sw128_kernel_body, 256, 2>(kg_sw128_kernel, dim3((num_local + g128::TM - 1) / g128::TM, sw_slices, E), dim3(256), g128::kSmemBytes, s, tq,
+        launch_kernel_ens<kg_sw128_kernel_body, 256, 2>(kg_sw128_kernel, dim3((num_local + g128::TM - 1) / g128::TM, sw_slices, E), dim3(256), g128::kSmemBytes, s, tl,
                    sw_part_p, sw_slices);
         launch_sum_slices(gp.kSWpart.p, sw_slices, (long)m * num_local * E, gp.kSW.p, s);
       } else {
-        launch_gemm_tn_splitk(m, num_local, N, tl.W, N, dT.p, N, gp.kSW.p, gp.kSWpart.p, sw_slices, s, E, tl.w_stride, (long)num_local * N);
+        launch_gemm_tn_splitk(m, num_local, N, tl.W, N, gp.kT.p, N, gp.kSW.p, gp.kSWpart.p, sw_slices, s, E, tl.w_stride, (long)num_local * N);
       }
       tl.SW = gp.kSW.p;
     }
@@ -1920,44 +1922,54 @@ KgPending kg_launch(GpDev& gp, int num_fidelity, const moe_gd_params_t& gd, cons
     gp.kZcPart.reserve((size_t)E * ((num_local + zc_chunk_len(m) - 1) / zc_chunk_len(m)) * m * m);
     launch_zc(tl, gp.kZcPart.p, s, !zc_sum_in_finish(m, num_local));
   } else {
-    const unsigned long long* ctr_p = dCounters.p;
+    const unsigned long long* ctr_p = gp.kCounters.p;
     const int* flags_p = gp.kStateI.p;
     launch_kernel_ens<kg_sum_kernel_body, 256>(kg_sum_kernel, dim3(E), dim3(256), 0, s, tl, dFin, ctr_p, flags_p);
   }
   MOE_HIP_CHECK(hipGetLastError());
-  // ---- grad KG from the sample sums, on the device (kg_state.hip) ----
-  if (want_grad) {
-    KgFinishParams fp;
-    fp.E = E;
-    fp.q = q;
-    fp.m = m;
-    fp.g = g;
-    fp.d = d;
-    fp.ng = ngrad;
-    fp.num_mc = num_mc;
-    fp.first_sample = first_sample;
-    fp.blob = dBlobP;
-    fp.rec_stride = rec.stride;
-    fp.rec_L = rec.L;
-    fp.out = dOut.p;
-    fp.out_stride = out_stride;
-    fp.winner = sp.winner;
-    fp.gmu = sp.gmu;
-    fp.dL = sp.dL;
-    fp.fin = dFin;
-    fp.counters = dCounters.p;
-    fp.flags = gp.kStateI.p;
-    fp.dir_part = dir_partials(tl);
-    fp.dir_slices = dir_slices(num_local);
-    fp.zc_part = zc_sum_in_finish(m, num_local) ? gp.kZcPart.p : nullptr;
-    fp.zc_chunks = (num_local + zc_chunk_len(m) - 1) / zc_chunk_len(m);
-    fp.zc_gs = zc_sum_lanes(m);
-    fp.best_value = dBestValue.p;
-    fp.num_local = num_local;
-    fp.rec_bp = rec_bp;
-    launch_kg_finish(fp, dFin + (size_t)E * (1 + qd + 3), s);
-    t_tail.stop(s);
-  }
+  return tl;
+}
+
+// grad KG from the sample sums, on the device (kg_state.hip)
+void launch_grad_finish(GpDev& gp, const KgDims& k, const KgStateParams& sp, const KgTailParams& tl, const KgRecords& R, double* dBlobP,
+                        double* dFin, int out_stride, hipStream_t s) {
+  const int m = k.m, num_local = k.num_local;
+  KgFinishParams fp;
+  fp.E = k.E;
+  fp.q = k.q;
+  fp.m = m;
+  fp.g = k.g;
+  fp.d = k.d;
+  fp.ng = k.ngrad;
+  fp.num_mc = k.num_mc;
+  fp.first_sample = k.first_sample;
+  fp.blob = dBlobP;
+  fp.rec_stride = R.rec.stride;
+  fp.rec_L = R.rec.L;
+  fp.out = gp.kOut.p;
+  fp.out_stride = out_stride;
+  fp.winner = sp.winner;
+  fp.gmu = sp.gmu;
+  fp.dL = sp.dL;
+  fp.fin = dFin;
+  fp.counters = gp.kCounters.p;
+  fp.flags = gp.kStateI.p;
+  fp.dir_part = dir_partials(tl);
+  fp.dir_slices = dir_slices(num_local);
+  fp.zc_part = zc_sum_in_finish(m, num_local) ? gp.kZcPart.p : nullptr;
+  fp.zc_chunks = (num_local + zc_chunk_len(m) - 1) / zc_chunk_len(m);
+  fp.zc_gs = zc_sum_lanes(m);
+  fp.best_value = gp.kBestValue.p;
+  fp.num_local = num_local;
+  fp.rec_bp = R.rec_bp;
+  launch_kg_finish(fp, dFin + (size_t)k.E * (1 + k.qd + 3), s);
+}
+
+// The results of one kg_launch through pinned memory, and the collect() that waits for them.
+KgPending enqueue_results(GpDev& gp, const KgDims& k, const double* dFin, size_t n_ctr, bool want_best_points,
+                          std::shared_ptr<std::array<EventTimer, 4>> timers, std::chrono::steady_clock::time_point wall0, hipStream_t s) {
+  const int E = k.E, m = k.m, d = k.d, dp = k.dp, num_local = k.num_local, qd = k.qd;
+  const bool want_grad = k.want_grad;
   // results through pinned memory in ONE copy: per evaluation kg_sum | grad_sum (q d) | value passes | gradient passes | flag
   const int fin_stride = (want_grad ? 1 + qd : 1) + 3;
   const size_t n_out = (size_t)fin_stride * E;
@@ -1966,13 +1978,13 @@ KgPending kg_launch(GpDev& gp, int num_fidelity, const moe_gd_params_t& gd, cons
   copy_async(out, dFin, sizeof(double) * n_out, hipMemcpyDeviceToHost, s, true);  // (hKgOut: pinned)
 #if MOE_BLOCK_PROF
   auto prof_p = std::make_shared<std::vector<unsigned long long>>(16);
-  copy_async(prof_p->data(), dCounters.p + n_ctr - 16, sizeof(unsigned long long) * 16, hipMemcpyDeviceToHost, s);
+  copy_async(prof_p->data(), gp.kCounters.p + n_ctr - 16, sizeof(unsigned long long) * 16, hipMemcpyDeviceToHost, s);
 #endif
   const bool fetch_bp = want_best_points && E == 1;
   auto bp_p = std::make_shared<std::vector<double>>();
   if (fetch_bp) {
     bp_p->resize((size_t)num_local * dp);
-    dBestPoint.download(bp_p->data(), bp_p->size(), s);
+    gp.kBestPoint.download(bp_p->data(), bp_p->size(), s);
   }
   GpDev* gpp = &gp;
   KgPending pending;
@@ -2046,14 +2058,127 @@ KgPending kg_launch(GpDev& gp, int num_fidelity, const moe_gd_params_t& gd, cons
   return pending;
 }
 
+}  // namespace
+
+// Everything up to and including the asynchronous launches on gp.stream; the returned object's collect() waits for the
+// stream and assembles the results.  Launching on several GPs (MCMC ensemble members, each with its own stream and
+// workspaces) before collecting any of them overlaps one member's host algebra with the others' kernels.
+KgPending kg_launch(GpDev& gp, int num_fidelity, const moe_gd_params_t& gd, const double* bounds, const double* discrete, int P,
+                    const double* Xq_all, int num_evals, const double* Xp, int q, int p, int num_mc, double best_so_far,
+                    const double* normals, int first_sample, int num_local, bool want_grad, bool want_best_points,
+                    double weight_table_gb, const double* disc_head) {
+  gp.use_device();
+  hipStream_t s = gp.stream;
+  const KgDims k = check_kg_args(gp, num_fidelity, gd, P, num_evals, q, p, num_mc, first_sample, num_local, want_grad);
+  const int d = k.d, dp = k.dp, u = k.u, m = k.m, A = k.A, E = k.E, size = k.size, N = k.N, qd = k.qd;
+  const McPlan pl = plan_mc(gp, k, bounds, Xq_all, Xp, weight_table_gb);
+
+  const auto wall0 = std::chrono::steady_clock::now();
+
+  // ---- 1. state set-up for the whole batch ----
+  std::vector<double> U_all((size_t)E * u * d), extra_all((size_t)E * A * d), disc_all((size_t)E * A * size);
+  for (int e = 0; e < E; ++e) {
+    double* U = &U_all[(size_t)e * u * d];
+    const double* Xq = Xq_all + (size_t)e * q * d;
+    // union of points, discretised set = [Xu without fidelity dims ; discrete points]  (.cpp:246-261)
+    std::copy(Xq, Xq + (size_t)q * d, U);
+    if (p > 0) std::copy(Xp, Xp + (size_t)p * d, U + (size_t)q * d);
+    double* ds = &disc_all[(size_t)e * A * size];
+    // (disc_head: the state this evaluation runs on was BUILT at other points_to_sample and moved here with SetCurrentPoint,
+    //  which leaves the discretised set behind -- .cpp:232-243 vs 259-261; the reference's multistart drivers do that)
+    for (int i = 0; i < u; ++i) {
+      const double* src = (disc_head != nullptr && i < q) ? disc_head + (size_t)i * d : U + (size_t)i * d;
+      std::copy(src, src + size, ds + (size_t)i * size);
+    }
+    std::copy(discrete, discrete + (size_t)P * size, ds + (size_t)u * size);
+    double* ex = &extra_all[(size_t)e * A * d];
+    for (int j = 0; j < A; ++j) {
+      for (int kk = 0; kk < size; ++kk) ex[(size_t)j * d + kk] = ds[(size_t)j * size + kk];
+      for (int kk = size; kk < d; ++kk) ex[(size_t)j * d + kk] = 1.0;
+    }
+  }
+  const TabParams tp = table_rows(gp, k, pl.G, Xq_all, Xp, disc_head);
+  const KgRecords R = fill_records(gp, k, pl, tp, bounds, U_all, disc_all);
+  const double* blob = gp.hKgIn.p;
+  const size_t blob_size = R.blob_size;
+  const long num_norm = (long)((num_mc + 1) / 2) * m;
+
+  auto timers = std::make_shared<std::array<EventTimer, 4>>();
+  EventTimer &t_mc = (*timers)[0], &t_cov = (*timers)[1], &t_tail = (*timers)[2], &t_state = (*timers)[3];
+  t_state.start(s);
+  // everything N-sized of the state, left on the device (gp.hip): no wait, no download -- the m x m algebra follows as kernels.
+  // The records and the normal draws ride down in the same host->device copy as the points (r4: one copy per call instead of three).
+  StateAppendix apx;
+  apx.doubles = blob_size + (size_t)num_norm;
+  apx.fill = [&](double* dst) {
+    std::memcpy(dst, blob, sizeof(double) * blob_size);
+    std::memcpy(dst + blob_size, normals, sizeof(double) * num_norm);
+  };
+  const KgStateEnqueued se = enqueue_kg_state_batch(gp, U_all.data(), u, want_grad ? q : 0, extra_all.data(), A, E, &apx);
+  double* dBlobP = const_cast<double*>(gp.dAppendix);  // (kg_state_kernel completes the records in place)
+  const double* dNormalsP = gp.dAppendix + blob_size;
+  const KgStateParams sp = launch_state_algebra(gp, k, se, R, dBlobP, best_so_far, s);
+  double* dFin = gp.kStateD.p + (size_t)E * qd * (1 + (want_grad ? m * (m + 1) / 2 : 0));
+
+  // ---- device buffers ----
+  const long tab_stride = (long)pl.ntiles * dp * 64;
+  gp.kTab.reserve((size_t)tab_stride * E + (size_t)dp * 64);  // + one tile: eval_loop's last prefetch reads past the end
+  gp.kBestPoint.reserve((size_t)E * num_local * dp);
+  gp.kBestValue.reserve((size_t)E * num_local);
+  gp.kBeta.reserve((size_t)E * num_local * m + 64);  // + a zeroed pad: kg_sample_weights_kernel reads whole 16/32/64-blocks
+  // [2 E] pass counters | [E] sample-ticket counters, one 128-byte line each (kTicketStride unsigned ints)
+  const size_t n_ctr = (size_t)2 * E + (size_t)E * (kTicketStride / 2) + 32;  // (+16 alignment slack, +16 profiling words)
+  gp.kCounters.reserve(n_ctr);
+  const int out_stride = 1 + m * m + 2 * k.ngrad;
+  gp.kOut.reserve((size_t)out_stride * E);
+  if (want_grad) {
+    const int chunks = (num_local + pl.chunk_len - 1) / pl.chunk_len;
+    if (!pl.fused_tail) gp.kT.reserve((size_t)N * E * num_local);
+    gp.kC.reserve((size_t)E * num_local * m);
+    gp.kTB.reserve((size_t)E * (chunks + 1) * m * N + (size_t)E * k.ngrad * kDirSlices);  // chunk partials + their sum + DIR partials
+  }
+
+  // ---- coordinate tables ----
+  {
+    dim3 grid((unsigned)((tab_stride + 255) / 256), E);
+    const double *dXp = gp.dX.p, *dUnionP = gp.dUnion;
+    double* dTabP = gp.kTab.p;
+    unsigned long long* dCtrP = gp.kCounters.p;
+    launch_kernel_ens<build_xs_tab_kernel_body, 256>(build_xs_tab_kernel, grid, dim3(256), 0, s, dXp, k.n, dUnionP, u, dp, pl.ntiles, tp, dTabP, tab_stride,
+                                                     pl.pair_rows, dCtrP, (long)n_ctr);
+    MOE_HIP_CHECK(hipGetLastError());
+  }
+  t_state.stop(s);
+
+  // ---- 2. MC kernel ----
+  const KgMcParams mp = launch_mc_step(gp, k, pl, gd, tp, R, dBlobP, dNormalsP, se.bl, tab_stride, n_ctr, t_mc, s);
+  {
+    // (bits 1 / 2 of the second word, r4: the frame-extent decisions -- a domain box or point set wider than 100 length scales
+    //  silently costs the LDS-table kernel and the multi-trial passes; this is where a caller can see it)
+    const int info[8] = {pl.variant,
+                         ((pl.variant == 0 && pl.xlds) ? 1 : 0) | (pl.far_frame ? 2 : 0) | (pl.wide_frame ? 4 : 0) | (pl.lane_kernel ? 8 : 0),
+                         pl.waves, pl.variant == 1 ? pl.tr : pl.wide_lds_tiles, pl.weight_table ? 1 : 0, pl.fused_tail ? 1 : 0, pl.blocks,
+                         pl.prep ? 1 : 0};
+    std::copy(info, info + 8, gp.last_info);
+  }
+
+  // ---- 3. gradient tail ----
+  const KgTailParams tl = launch_tail_step(gp, k, pl, mp, R, dBlobP, dNormalsP, se.bl, dFin, out_stride, t_cov, t_tail, s);
+  if (want_grad) {
+    launch_grad_finish(gp, k, sp, tl, R, dBlobP, dFin, out_stride, s);
+    t_tail.stop(s);
+  }
+  return enqueue_results(gp, k, dFin, n_ctr, want_best_points, timers, wall0, s);
+}
+
 // How many evaluations one kg_launch may carry on this GP within `budget_gb` of device workspace (>= 1): the state
 // matrices E / VE / WE, the materialised tail matrix T (d-KG and m > 8) with its TB partials, the per-sample outputs.
 // A d-KG evaluation at C5 is 1.4 GB (N x M doubles of T alone), so a 200-start multistart cannot go down in one piece.
 int kg_max_batch(const GpDev& gp, int P, int q, int p, int num_local, bool want_grad, double budget_gb) {
   const double N = gp.N, g1 = 1 + gp.g, u = q + p, m = u * g1, A = u + P;
   const double ngrad = want_grad ? q * g1 * gp.d : 0.0;
-  const bool fused = want_grad && gp.g == 0 && m <= 8;
-  const double chunks = std::ceil((double)num_local / (fused ? kFusedChunk : (m > 64 ? kTbChunkWide : kTbChunk)));
+  const bool fused = fused_tail_taken(want_grad, gp.g, (int)m);
+  const double chunks = std::ceil((double)num_local / tail_chunk_len(fused, (int)m));
   // state matrix E (all columns), V = L^-1 K* with the tail's K^-1 TB workspace behind it, W = K^-1 K*; the packed d chol / d Xq
   double doubles = N * (m + ngrad + A) + 3.0 * N * m + (double)num_local * (gp.dp + 1 + 2 * m) +
                    (want_grad ? (double)q * gp.d * m * (m + 1) / 2 : 0.0);

@@ -32,16 +32,6 @@ namespace moe {
 #ifndef MOE_BLOCK_PROF
 #define MOE_BLOCK_PROF 0
 #endif
-// Gradient passes with dot-product distances (eval_loop GDOT): 5 fewer instructions per point, but the gradient then carries the
-// cancellation of sum coef x - q sum coef; where the inner optimiser is run to convergence (100 steps x 10 restarts, the
-// reference's own ping-test settings) the end points drift to 1.4e-6 from the reference's instead of 1e-7.  Off.
-#ifndef MOE_KG_GRAD_DOT
-#define MOE_KG_GRAD_DOT 0
-#endif
-// radial3's square root: 1 = seed + one Heron step (<= 36 ulp, two instructions less per covariance entry), 0 = correctly rounded
-#ifndef MOE_KG_FAST_SQRT
-#define MOE_KG_FAST_SQRT 1
-#endif
 #if MOE_BLOCK_PROF
 #define MOE_PROF_T(var) const unsigned long long var = __builtin_amdgcn_s_memtime()
 #define MOE_PROF_ADD(dst, a, b) dst += (b) - (a)
@@ -323,11 +313,7 @@ __device__ __forceinline__ void radial3(double r2, const double* __restrict__ et
     first = base;
     second = base;
   } else {
-#if MOE_KG_FAST_SQRT
-    const double a = sqrt_pos_fast(r2);
-#else
-    const double a = sqrt_pos(r2);
-#endif
+    const double a = sqrt_pos_fast(r2);  // (seed + one Heron step: <= 36 ulp, two instructions less per covariance entry)
     const double e = exp_nonpos_tab(-a, etab);
     base = e * fma(a, fma(a, 1.0 / 3.0, 1.0), 1.0);  // e^-a (1 + a + a^2/3)
     first = NEED_FIRST ? (1.0 / 3.0) * (e * (a + 1.0)) : 0.0;
@@ -368,12 +354,10 @@ __device__ __forceinline__ double eval_loop(const double* __restrict__ xs, const
                                             const double* __restrict__ etab, int ntiles, double mean,
                                             const double (&xq_in)[DP], const double* inv_lp, double (&grad)[DP], int lane,
                                             double* __restrict__ scr = nullptr) {
-  // GDOT: the gradient pass in dot-product form too (no derivative observations): r2 from the |x|^2 row, and
-  //   grad = sum_j coef_j (x_j - q) = sum_j coef_j x_j - q sum_j coef_j
-  // needs no differences at all -- DP fmas + one add per point instead of DP subtractions + 2 DP fmas (in the centred frame
-  // the two terms are of the size of the gradient itself: same argument as for the distances).
-  constexpr bool GDOT = MOE_KG_GRAD_DOT && WG && XL && G == 0;
-  constexpr bool DOT = XL && (!WG || GDOT);  // squared distance from the |x|^2 row
+  // (gradient passes keep the direct differences: in dot-product form, grad = sum_j coef_j x_j - q sum_j coef_j, the gradient carries
+  //  the cancellation of the two terms, and where the inner optimiser runs to convergence -- 100 steps x 10 restarts, the reference's
+  //  own ping-test settings -- the end points drift to 1.4e-6 from the reference's instead of 1e-7)
+  constexpr bool DOT = XL && !WG;  // squared distance from the |x|^2 row
   constexpr int XR = DP + (XL ? 1 : 0);  // rows per coordinate tile
   double q2[DP], xq[DP];
   double qq;
@@ -399,7 +383,7 @@ __device__ __forceinline__ double eval_loop(const double* __restrict__ xs, const
   // (all inside the ball of radius sqrt(32) * kTableExtent): every covariance underflows to exactly 0 and the posterior mean
   // IS the prior mean -- the pass is skipped.  Closer than that, sqrt(r2) * 64 / ln2 < 2^31: exp_nonpos_tab is in range.
   if (!WG && !(uniform(qq) <= kFarRadius * kFarRadius)) return -mean;  // (uniform: a scalar branch, and the callers' Armijo decisions stay scalar)
-  double accf = 0.0, accs = 0.0;
+  double accf = 0.0;
   double accg[DP];
   double accd[G > 0 ? G : 1];
 #pragma unroll
@@ -456,12 +440,7 @@ __device__ __forceinline__ double eval_loop(const double* __restrict__ xs, const
     }
     accf = fma(w0, base, accf);
     if (G > 0) accf = fma(first, sd, accf);
-    if (GDOT) {
-      const double coef = w0 * first;
-      accs += coef;
-#pragma unroll
-      for (int k = 0; k < DP; ++k) accg[k] = fma(coef, cx[k], accg[k]);
-    } else if (WG) {
+    if (WG) {
       double coef = w0 * first;
       if (G > 0) {
         coef = fma(second, sd, coef);
@@ -475,20 +454,6 @@ __device__ __forceinline__ double eval_loop(const double* __restrict__ xs, const
     for (int k = 0; k < NX; ++k) cx[k] = nx[k];
 #pragma unroll
     for (int a = 0; a < 1 + G; ++a) cw[a] = nw[a];
-  }
-  if (GDOT) {
-    double sg[DP], sf, ss;
-    if (scr != nullptr)
-      wave_sum_packed_lds<DP>(accg, scr, lane, sg);
-    else
-      wave_sum_packed<DP>(accg, sg);
-    wave_sum2_uniform(accf, accs, sf, ss);
-#pragma unroll
-    for (int k = 0; k < DP; ++k) {
-      const double v = fma(-xq[k], ss, sg[k]);  // sum coef x_k - q_k sum coef
-      grad[k] = FRAMEG ? -v : -(v * inv_lp[k]);
-    }
-    return -(mean + sf);
   }
   const double mu = mean + wave_sum_uniform(accf);
   if (WG) {
@@ -801,23 +766,12 @@ __device__ __forceinline__ void from_table_order(const double (&v)[DP], const in
   }
 }
 
-#ifndef MOE_KG_STREAM_TRIALS
-#define MOE_KG_STREAM_TRIALS 8
-#endif
-// (one trial more than the previous step consumed in a step's first sweep: measured slower everywhere -- C5 MC 4.22 -> 4.44 ms, d = 16 at
-//  n = 1000 0.188 -> 0.197 -- kept as a switch, off)
-#ifndef MOE_KG_STREAM_PRED_EXTRA
-#define MOE_KG_STREAM_PRED_EXTRA 0
-#endif
-#ifndef MOE_KG_LDS_CARRY
-#define MOE_KG_LDS_CARRY 1
-#endif
-#ifndef MOE_KG_STREAM_FIRST
-#define MOE_KG_STREAM_FIRST 6
-#endif
-#ifndef MOE_KG_STREAM_FOLLOWUP
-#define MOE_KG_STREAM_FOLLOWUP 4
-#endif
+// Armijo trials of the streamed sweeps (line_search_lds, WideEval::kMaxTrials): at most per sweep, in a sample's first sweep, per
+// follow-up batch.  (One trial more than the previous step consumed in a step's first sweep: measured slower everywhere -- C5 MC
+// 4.22 -> 4.44 ms, d = 16 at n = 1000 0.188 -> 0.197.)
+constexpr int kStreamTrials = 8;
+constexpr int kStreamFirst = 6;
+constexpr int kStreamFollowup = 4;
 constexpr int kPartLen = 48;  // doubles per partial slot of a packed reduction: f | DP gradient sums | sum of coefficients | G derivative sums (<= 1 + 32 + 1 + 12)
 constexpr int kLsRows = 6;    // line-search vectors per wave in LDS (line_search_lds): x | masked gradient | step | x at restart start | x0 and dv of the trial line (frame)
 // per-wave LDS scratch of the wide-dimension evaluator (WideEval, d > 16) behind the z / beta scratch of a weight slab
@@ -1365,7 +1319,7 @@ __device__ __forceinline__ double line_search_lds(const KgMcParams& P, EV& ev, d
   for (int k = 0; k < DP; ++k) gp[k] = 0.0;
   // Armijo trials the previous step of this sample consumed (>= 2): the size of the next step's first batch.  (A sample's first step:
   // two -- or six where a sweep is bound by the weight stream, the streamed-weights kernel: a bracket there is ~6 trials long.)
-  int pred = (EV::kMaxTrials > 5) ? MOE_KG_STREAM_FIRST : 2;
+  int pred = (EV::kMaxTrials > 5) ? kStreamFirst : 2;
 #if MOE_BLOCK_PROF
   ev.seg_last = __builtin_amdgcn_s_memtime();
   ev.seg_tot = ev.c_tot;
@@ -1459,9 +1413,9 @@ __device__ __forceinline__ double line_search_lds(const KgMcParams& P, EV& ev, d
           }
           // follow-up batches: pairs -- or fours where a sweep is bound by the weight stream, not by its trials (streamed-weights
           // kernel: kMaxTrials > 5), so that a bracket longer than predicted costs one more sweep, not two or three
-          batch = (EV::kMaxTrials > 5) ? MOE_KG_STREAM_FOLLOWUP : 2;
+          batch = (EV::kMaxTrials > 5) ? kStreamFollowup : 2;
         }
-        pred = max(2, min(search + 1 + ((EV::kMaxTrials > 5) ? MOE_KG_STREAM_PRED_EXTRA : 0), EV::kMaxTrials));
+        pred = max(2, min(search + 1, EV::kMaxTrials));
 #if MOE_BLOCK_PROF
         ev.seg_mark(1);  // (1: the Armijo loop outside its passes: dispatch, decisions)
 #endif
@@ -1491,7 +1445,7 @@ __device__ __forceinline__ double line_search_lds(const KgMcParams& P, EV& ev, d
       double gn_l = 0.0;
       if (changed) {
         if (lane_id < DP) sF[lane_id] = ((sX[lane_id] + sS[lane_id]) - c_l) * s_l;
-        if (MOE_KG_LDS_CARRY && (istep + 1 < P.max_num_steps || restart + 1 < P.max_num_restarts)) {
+        if (istep + 1 < P.max_num_steps || restart + 1 < P.max_num_restarts) {
           obj2 = ev.eval_p_lane(sF, s_l, gn_l);
           carried = true;
         } else {
@@ -1545,7 +1499,7 @@ __device__ __forceinline__ double line_search_lds(const KgMcParams& P, EV& ev, d
 //   value passes (T trials along one line):   x0, dv (2 DP) + a ring of PF rows + T accumulators  -- 80 + T doubles at DP = 32
 //   gradient pass:                            xq, grad sums (2 DP) + the tile's rows (DP)          -- 96 doubles at DP = 32; the
 //     gradient is accumulated as sum_j coef_j x_j - q sum_j coef_j (the centred frame keeps both terms of the size of the
-//     gradient: see eval_loop GDOT), so a row is dead -- and refilled from the next tile -- right after its fma.
+//     gradient), so a row is dead -- and refilled from the next tile -- right after its fma.
 // The table of the wide dimensions holds the rows in PAIRS, [tile][DP / 2][64][2]: a lane fetches rows 2i, 2i + 1 of its point
 // with one 16-byte load (8-byte loads run at 0.54 - 0.70x the 16-byte rate out of L2, and these passes are bound by exactly
 // that stream: ~200 KB per sweep and wave at n = 1000, d = 24).  The first `ntl` tiles are served from an LDS copy shared by
@@ -1600,7 +1554,7 @@ struct WideEval {
   // C5), so a step's whole bracket goes into ONE sweep whenever the previous step's bracket predicts up to eight trials.
   // (the L2-streamed sweeps of 16 / 24 rows gain too -- n = 1000: d = 16 0.257 -> 0.230 ms, d = 24 0.306 -> 0.296; at 32 rows the eight
   //  accumulators cost more registers than the saved sweeps give back: 0.403 -> 0.429 -- r3, `profiles/r03_dim_sweep_after.txt`)
-  static constexpr int kMaxTrials = (WS || DP <= 24) ? MOE_KG_STREAM_TRIALS : 5;
+  static constexpr int kMaxTrials = (WS || DP <= 24) ? kStreamTrials : 5;
   static constexpr int HP = DP / 2;                        // row pairs per tile
   static constexpr int PF2 = (HP <= 8) ? HP : ((HP % 8 == 0) ? 8 : 6);  // ring depth in row pairs
   static_assert(HP % PF2 == 0 && PF2 <= HP, "ring slots must be static");

@@ -64,8 +64,6 @@ struct EnsArena {
 constexpr size_t kEnsCopyMaxBytes = (size_t)4 << 20;
 
 bool ens_copy_mergeable(const std::vector<Recorder>& recs, size_t pos) {
-  static const bool on = !(std::getenv("MOE_ENS_COPY") != nullptr && std::atoi(std::getenv("MOE_ENS_COPY")) == 0);
-  if (!on) return false;
   for (const Recorder& r : recs) {
     const LaunchOp& o = r.ops[pos];
     if (!o.host_pinned || o.copy.bytes % 8 != 0 || o.copy.bytes > kEnsCopyMaxBytes) return false;
