@@ -272,16 +272,33 @@ class GaussianProcess(object):
         return list(mean + L @ w)
 
     def sample_global_optima(self, num_optima, inner_number, domain_bounds):
-        raise OptimalLearningException("sample_global_optima (PES support code) is outside the hot path (SURVEY 8, out of scope)")
+        """SampleGlobalOptimaFromGP (gpp_math.cpp:1853-1870): for each of num_optima sets, inner_number candidates uniform in the box
+        domain_bounds ([lo_0, hi_0, lo_1, hi_1, ...], what cppify(domain.domain_bounds) marshals), one joint draw of the posterior
+        at them, and the candidate where the draw is smallest; the flat list [num_optima * dim].  All sets run on the device in one
+        batch (moe_gp_sample_global_optima).  The candidates come from a generator derived from the GP's seed and a per-seed call
+        counter, the normals from the GP's own stream after what sample_point_from_gp has taken -- so after set_explicit_seed(s) the
+        same calls return the same points -- but neither stream is the reference's (Boost, rand() % 10000)."""
+        num_optima, inner_number = int(num_optima), int(inner_number)
+        if num_optima <= 0 or inner_number <= 0:
+            raise BoundsException("num_optima and inner_number must be positive", min(num_optima, inner_number), 1, 0)
+        bounds = _flat(domain_bounds, 2 * self.dim).reshape(self.dim, 2)
+        rng = np.random.default_rng([self._seed, self._optima_calls])
+        self._optima_calls += 1
+        cand = rng.uniform(bounds[:, 0], bounds[:, 1], size=(num_optima, inner_number, self.dim))
+        count = num_optima * inner_number
+        z = _api.normal_draws(self._seed, self._drawn + count)[self._drawn:]
+        self._drawn += count
+        points, _, _ = self._dev.sample_global_optima(cand, z.reshape(num_optima, inner_number))
+        return list(points.ravel())
 
     def set_explicit_seed(self, seed):
-        self._seed, self._drawn = int(seed) & 0xFFFFFFFF, 0
+        self._seed, self._drawn, self._optima_calls = int(seed) & 0xFFFFFFFF, 0, 0
 
     def set_randomized_seed(self, seed):
         self.set_explicit_seed(_randomized_seed(seed, 0))
 
     def reset_to_most_recent_seed(self):
-        self._drawn = 0
+        self._drawn = self._optima_calls = 0
 
     def print_historical_data(self):
         print(self._X)

@@ -54,6 +54,8 @@ SIGNATURES = {
     "moe_gp_grad_mean": (C.c_int, [_GP, dp, C.c_int, dp, _EP]),
     "moe_gp_variance": (C.c_int, [_GP, dp, C.c_int, dp, _EP]),
     "moe_gp_cholesky_variance": (C.c_int, [_GP, dp, C.c_int, dp, _EP]),
+    "moe_gp_sample_points": (C.c_int, [_GP, dp, C.c_int, dp, C.c_int, dp, ip, ip, _EP]),
+    "moe_gp_sample_global_optima": (C.c_int, [_GP, dp, C.c_int, C.c_int, dp, dp, ip, ip, _EP]),
     "moe_gp_grad_variance": (C.c_int, [_GP, dp, C.c_int, C.c_int, dp, _EP]),
     "moe_gp_grad_cholesky_variance": (C.c_int, [_GP, dp, C.c_int, C.c_int, dp, _EP]),
     "moe_posterior_mean": (C.c_int, [_GP, C.c_int, dp, dp, dp, _EP]),

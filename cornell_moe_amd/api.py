@@ -264,6 +264,37 @@ class DeviceGP(object):
         return self._q(_lib.load().moe_gp_grad_cholesky_variance, pts,
                        lambda k: self.d * (k * (1 + self.g)) ** 2 * num_derivs, int(num_derivs))
 
+    def sample_points(self, pts, normals):
+        """moe_gp_sample_points: joint posterior draws of the function values at pts [C][dim], one per row of normals [D][C].
+        Returns (values [D][C] = mu + L z, argmin [D] by the reference's rule (-1: candidate 0 is the minimum), failed_pivot: 0 or
+        the failing pivot + 1 -- a failed factorisation is handled as include/moe_hip.h describes, not raised)."""
+        pts, pp = _d(pts)
+        C_ = pts.reshape(-1, self.d).shape[0]
+        normals = np.ascontiguousarray(normals, dtype=np.float64).reshape(-1, C_)
+        D = normals.shape[0]
+        values = np.zeros((D, C_))
+        argmin = np.zeros(D, dtype=np.int32)
+        failed = C.c_int(0)
+        err = _lib.MoeError()
+        _check(_lib.load().moe_gp_sample_points(self._h, pp, C_, normals.ctypes.data_as(dp), D, values.ctypes.data_as(dp),
+                                                argmin.ctypes.data_as(ip), C.byref(failed), C.byref(err)), err)
+        return values, argmin, failed.value
+
+    def sample_global_optima(self, candidates, normals):
+        """moe_gp_sample_global_optima: candidates [E][C][dim], normals [E][C] (one draw per set), all sets in one batch.
+        Returns (points [E][dim], index [E] (-1: candidate 0, which is then the point), failed_pivot [E])."""
+        cand = np.ascontiguousarray(candidates, dtype=np.float64)
+        E, C_ = cand.shape[0], cand.shape[1]
+        normals = np.ascontiguousarray(normals, dtype=np.float64).reshape(E, C_)
+        points = np.zeros((E, self.d))
+        index = np.zeros(E, dtype=np.int32)
+        failed = np.zeros(E, dtype=np.int32)
+        err = _lib.MoeError()
+        _check(_lib.load().moe_gp_sample_global_optima(self._h, cand.ctypes.data_as(dp), C_, E, normals.ctypes.data_as(dp),
+                                                       points.ctypes.data_as(dp), index.ctypes.data_as(ip),
+                                                       failed.ctypes.data_as(ip), C.byref(err)), err)
+        return points, index, failed
+
     def mix_covariance(self, pts, derivs2=()):
         pts, pp = _d(pts)
         k = pts.reshape(-1, self.d).shape[0]

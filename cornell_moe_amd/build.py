@@ -15,7 +15,8 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "lib", "libmoe_hip.so")
 SOURCES = ["kernels_cov.hip", "kernels_linalg.hip", "host_math.hip", "gp.hip", "kg.hip", "kg_state.hip", "kg_mc_dp4.hip", "kg_mc_dp8.hip",
-           "kg_mc_dp12.hip", "kg_mc_dp16.hip", "kg_mc_dp4b.hip", "kg_mc_dp8b.hip", "kg_mc_dp12b.hip", "kg_mc_dp16b.hip", "kg_mc_dp24.hip", "kg_mc_dp32.hip", "multistart.hip", "mcmc.hip", "ei.hip", "api.hip", "rccl_comm.hip", "query_grad.hip"]
+           "kg_mc_dp12.hip", "kg_mc_dp16.hip", "kg_mc_dp4b.hip", "kg_mc_dp8b.hip", "kg_mc_dp12b.hip", "kg_mc_dp16b.hip", "kg_mc_dp24.hip", "kg_mc_dp32.hip", "multistart.hip", "mcmc.hip", "ei.hip", "api.hip", "rccl_comm.hip", "query_grad.hip",
+           "sample.hip"]
 HEADERS = ["common.hpp", "launch.hpp", "kernels.hpp", "gemm128.hpp", "device_cov.hpp", "fastmath.hpp", "host_math.hpp", "gp.hpp", "kg.hpp", "kg_mc.hpp", "kg_mc_lane.hpp", "kg_state.hpp",
            os.path.join("..", "..", "include", "moe_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
@@ -31,6 +32,15 @@ def _hipcc():
         if cand and (os.path.isabs(cand) and os.path.exists(cand) or not os.path.isabs(cand)):
             return cand
     return "hipcc"
+
+
+def _max_jobs():
+    """Concurrent hipcc processes: MAX_JOBS (default 16), never more than the sources or the CPUs."""
+    try:
+        jobs = int(os.environ.get("MAX_JOBS", "16"))
+    except ValueError:
+        jobs = 16
+    return max(1, min(jobs, len(SOURCES), os.cpu_count() or 1))
 
 
 def _newest_header():
@@ -52,7 +62,7 @@ def _compile(src, force):
 def build(force=False, verbose=False):
     os.makedirs(OBJ, exist_ok=True)
     os.makedirs(os.path.dirname(LIB), exist_ok=True)
-    with concurrent.futures.ThreadPoolExecutor(max_workers=min(os.cpu_count() or 4, len(SOURCES))) as ex:
+    with concurrent.futures.ThreadPoolExecutor(max_workers=_max_jobs()) as ex:
         results = list(ex.map(lambda s: _compile(s, force), SOURCES))
     objs = [r[0] for r in results]
     rebuilt = any(r[1] for r in results)

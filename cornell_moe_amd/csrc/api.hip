@@ -222,6 +222,33 @@ int moe_gp_cholesky_variance(const moe_gp_t* gp_c, const double* pts, int num_pt
   });
 }
 
+int moe_gp_sample_points(const moe_gp_t* gp_c, const double* pts, int num_pts, const double* normals, int num_draws, double* values,
+                         int* argmin, int* failed_pivot, moe_error_t* err) {
+  return guarded(err, [&] {
+    std::unique_lock<std::mutex> lk;
+    moe::GpDev& gp = lock_gp(gp_c, lk);
+    moe::sample_points_on_device(gp, pts, num_pts, 1, normals, num_draws, moe::reference_quirks(), values, argmin, failed_pivot);
+  });
+}
+
+int moe_gp_sample_global_optima(const moe_gp_t* gp_c, const double* candidates, int inner_number, int num_optima,
+                                const double* normals, double* points_optima, int* index, int* failed_pivot, moe_error_t* err) {
+  return guarded(err, [&] {
+    std::unique_lock<std::mutex> lk;
+    moe::GpDev& gp = lock_gp(gp_c, lk);
+    require(points_optima != nullptr && index != nullptr, "NULL argument");
+    std::vector<double> values((size_t)std::max(num_optima, 0) * std::max(inner_number, 0));
+    moe::sample_points_on_device(gp, candidates, inner_number, num_optima, normals, 1, moe::reference_quirks(), values.data(), index,
+                                 failed_pivot);
+    const int d = gp.d;
+    for (int i = 0; i < num_optima; ++i) {
+      // index -1 (candidate 0 is the minimum): the reference reads before its array here (gpp_math.cpp:1866); candidate 0 it is
+      const double* best = candidates + ((size_t)i * inner_number + std::max(index[i], 0)) * d;
+      std::copy(best, best + d, points_optima + (size_t)i * d);
+    }
+  });
+}
+
 int moe_gp_grad_variance(const moe_gp_t* gp_c, const double* pts, int num_pts, int num_derivs, double* out,
                          moe_error_t* err) {
   return guarded(err, [&] {

@@ -599,6 +599,26 @@ KgStateEnqueued enqueue_kg_state_batch(GpDev& gp, const double* U_all, int u, in
   return se;
 }
 
+void enqueue_sample_state_batch(GpDev& gp, const double* U_all, int C, int E, const StateAppendix* apx) {
+  gp.use_device();
+  hipStream_t s = gp.stream;
+  DerivList none;
+  none.g = 0;
+  for (int i = 0; i < kMaxDerivs; ++i) none.idx[i] = 0;
+  StateLayout lay;
+  BatchLayout bl;
+  build_state_matrix(gp, U_all, C, none, 0, nullptr, 0, E, &lay, &bl, apx);
+  const int N = gp.N;
+  const long cm = (long)E * C;
+  const size_t nG = (size_t)E * C * C;
+  gp.dVE.reserve((size_t)N * cm);
+  gp.dEK.reserve(std::max((size_t)E * gram_batch_slices(E, C, N) * C * C, tri_cols_work_doubles(N, (int)cm)));
+  gp.dGram.reserve(nG + cm);
+  launch_tri_gemm_cols('N', N, (int)cm, C, gp.dLinv.p, gp.ldL, gp.dE.p, N, gp.dVE.p, N, gp.dEK.p, s);
+  launch_gram_batch(E, C, 0, 0, N, gp.dVE.p, N, gp.dGram.p, gp.dEK.p, s);
+  launch_gemm_tn((int)cm, 1, N, gp.dE.p, N, gp.dKinvY.p, N, gp.dGram.p + nG, (int)cm, s);
+}
+
 namespace {
 // var = Kss - gram in place (Kss in `var`), col-major m x m
 __global__ __launch_bounds__(256) void var_sub_kernel(double* __restrict__ var, const double* __restrict__ gram, long n) {

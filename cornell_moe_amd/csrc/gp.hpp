@@ -54,6 +54,10 @@ struct GpDev {
                                   // the arrival counters non-zero, so the next call clears them first
   DevBuf<int> kBestJ, kStateI;   // kStateI: singular flags | winners of a KG batch (kg_state.hip)
   DevBuf<double> kStateD;        // grad mu | d chol / d Xq (packed) | final [kg_sum | grad] per evaluation
+  // joint posterior sampling (sample.hip): the candidate sets' covariances, then factors [E][C][C]; the draws [E][D][C] followed by
+  // their argmin [E][D]; the factorisations' status words [E] and the resumed factorisations' [E]
+  DevBuf<double> sMat, sOut;
+  DevBuf<int> sInfo;
   int num_cu = 256;
   // per-dimension mean and max |x - mean| of the training points (refreshed by rebuild() and by the append path of add_points):
   // the frame centre of the KG coordinate tables and the extent the kernel selection needs, so that an evaluation does not
@@ -169,6 +173,18 @@ inline int device_variance_min_m(bool cholesky) {
   return (v && *v) ? std::atoi(v) : (cholesky ? kDeviceVarianceMinM : kDeviceVarianceMinMPlain);
 }
 void variance_on_device(GpDev& gp, const double* pts, int k, bool cholesky, double* out);
+// Joint posterior sampling (SamplePointsFromGP, gpp_math.cpp:1800-1848) of E candidate sets of C points each, function values only.
+// The value-only state of every set in one pass -- V = L^-1 K* through the per-problem triangular kernels, so that a set's bits do
+// not depend on the batch it shares: gram = V^T V [E][C][C] followed by ek = K*^T K^-1 (y - mean) [E C] in gp.dGram; the padded
+// points at gp.dUnion, the appendix at gp.dAppendix.  No sync.
+void enqueue_sample_state_batch(GpDev& gp, const double* U_all, int C, int E, const StateAppendix* apx);
+// sample.hip: values[E][D][C] = mu + L z for the D normal vectors normals[E][D][C] of each set, L the factor of the set's C x C
+// posterior covariance; argmin[E][D] by the reference's rule (-1 when candidate 0 is the minimum); failed[E] = 0 or the failing
+// pivot + 1.  stop_at_failure: ComputeCholeskyFactorL's early stop (gpp_linear_algebra.cpp:117-143) -- the partial factor with the
+// trailing Schur complement in place is L; otherwise a failing pivot's column is zeroed and the factorisation goes on (the
+// semidefinite continuation that comment names).
+void sample_points_on_device(GpDev& gp, const double* pts, int C, int E, const double* normals, int D, bool stop_at_failure,
+                             double* values, int* argmin, int* failed);
 // r6 (query_grad.hip): ComputeGradVarianceOfPoints / ComputeGradCholeskyVarianceOfPoints (gpp_math.cpp:1267-1474) for the first
 // `num_derivs` of the `num_pts` points, the m x m x d algebra on the device: out[num_derivs][d m m] in the reference's layout.
 void grad_variance_on_device(GpDev& gp, const double* pts, int num_pts, int num_derivs, bool cholesky, double* out);

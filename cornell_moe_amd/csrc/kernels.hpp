@@ -139,8 +139,12 @@ void launch_cholesky_append(int N0, int kk, double* L, long ldl, double* Linv, l
 // In-place blocked Cholesky of `batch` matrices A + b * a_stride (N x N lower triangles, lda); the inverses of the diagonal
 // blocks go to Linv + b * l_stride (N x N layout, ldl; only the 64 x 64 diagonal blocks are written -- no full inverse
 // factor).  info[b]: 0 or failing pivot + 1.  Every step is ONE launch over the batch (grid.z).
+// one_level: the one-level kernels at every N.  Their state after a failed pivot p (info = p + 1) is well defined: the columns
+// before p's block of kCholBatchBlock are factored, and the lower triangle from that block on holds the Schur complement left by
+// them (sample.hip resumes from there).  The default picks the two-level factorisation for large N.
+constexpr int kCholBatchBlock = 64;
 void launch_cholesky_batch(int N, double* A, long lda, long a_stride, double* Linv, long ldl, long l_stride, int* info,
-                           int batch, hipStream_t s, double* scratch = nullptr);
+                           int batch, hipStream_t s, double* scratch = nullptr, bool one_level = false);
 // The log-likelihood's quadratic form comes out of the same factorisation: with the centred data as an extra ROW N of the
 // matrix (corner 1e100) the factor's row N is v^T = (L^-1 yc)^T, and yc^T K^-1 yc = |v|^2 -- no triangular solve.
 // launch_ll_border writes that row; launch_ll_terms_batch returns out[b] = (sum log L_ii, |v|^2) over i, j < N.

@@ -505,6 +505,7 @@ __global__ __launch_bounds__(256) void gram_cross_batch_kernel(GramMap gm, int K
 // Blocked Cholesky (lower, in place) with explicit inverse factor.
 // ------------------------------------------------------------------------------------------------------------------
 constexpr int NB = 64;
+static_assert(NB == kCholBatchBlock, "kernels.hpp names the one-level factorisation's column block");
 
 // Factor the nb x nb diagonal block at (k0,k0); write L_kk back (strict upper zeroed) and its inverse into Linv's
 // diagonal block.  One wavefront, everything fully unrolled so that lane t keeps ROW t of the block in registers (static
@@ -2177,9 +2178,9 @@ __global__ __launch_bounds__(256) void ll_terms_batch_kernel(const double* __res
 }  // namespace
 
 void launch_cholesky_batch(int N, double* A, long lda, long a_stride, double* Linv, long ldl, long l_stride, int* info,
-                           int batch, hipStream_t s, double* scratch) {
+                           int batch, hipStream_t s, double* scratch, bool one_level) {
   MOE_HIP_CHECK(hipMemsetAsync(info, 0, sizeof(int) * batch, s));
-  {
+  if (!one_level) {
     // large matrices (the log likelihood at C5's N = 8000): the two-level factorisation with its look-ahead schedule, one matrix
     // after the other -- a single factorisation fills the chip there, and the one-level batch kernels below are 125 steps of a
     // 150 us register-resident diagonal kernel

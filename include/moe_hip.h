@@ -120,6 +120,28 @@ int moe_gp_variance(const moe_gp_t* gp, const double* pts, int num_pts, double* 
 /* compute_cholesky_variance_of_points: chol of the above (lower; strict upper holds the variance leftovers exactly like
  * ComputeCholeskyFactorL leaves them); MOE_ERR_SINGULAR on failure */
 int moe_gp_cholesky_variance(const moe_gp_t* gp, const double* pts, int num_pts, double* out, moe_error_t* err);
+/* Joint posterior sampling -> GaussianProcess::SamplePointsFromGP (gpp_math.cpp:1800-1848), num_draws draws sharing one candidate
+ * set and one factor.  Function values only, whatever derivatives the GP observes (the reference passes no derivative rows):
+ *   values[num_draws][num_pts] = mu + L normals[d], L the Cholesky factor of the num_pts x num_pts posterior covariance;
+ *   argmin[num_draws]: best = y[0], index -1, replaced on a strictly smaller value (so -1 when candidate 0 is the minimum);
+ *   failed_pivot: 0, or the failing pivot + 1.  A failed factorisation is no error (the reference never raises here):
+ *     reference quirks on (the default, moe_set_reference_quirks) -> ComputeCholeskyFactorL's early stop
+ *     (gpp_linear_algebra.cpp:117-143): the columns before the pivot factored, the lower triangle of the trailing Schur
+ *     complement in place, and that matrix is L;  quirks off -> the semidefinite continuation: the failing column is zeroed and
+ *     the factorisation goes on.
+ * MOE_ERR_BOUNDS only for num_pts <= 0 or num_draws <= 0.  No size limit beyond device memory: about
+ * 8 (3 C^2 + 2 N C + 2 D C) bytes for C = num_pts candidates, D = num_draws and N = num_sampled (1 + num_derivatives)
+ * (covariance / factor, Gram matrix, K* and L^-1 K*, normals and draws). */
+int moe_gp_sample_points(const moe_gp_t* gp, const double* pts, int num_pts, const double* normals, int num_draws, double* values,
+                         int* argmin, int* failed_pivot, moe_error_t* err);
+/* GaussianProcess::SampleGlobalOptimaFromGP (gpp_math.cpp:1853-1870) on caller-drawn candidates: candidates[num_optima][inner_number][dim]
+ * and normals[num_optima][inner_number], one draw per candidate set; all sets in one batch (one upload, one stream, one wait) and a
+ * set's result does not depend on the others.  points_optima[num_optima][dim] = the set's candidate at its argmin; index[num_optima]
+ * and failed_pivot[num_optima] as moe_gp_sample_points' argmin and failed_pivot.  DEVIATION: for an index of -1 the reference reads
+ * before its candidate array (undefined behaviour); here the optimum is candidate 0 and index reports -1.  Bytes per set: as above
+ * with D = 1. */
+int moe_gp_sample_global_optima(const moe_gp_t* gp, const double* candidates, int inner_number, int num_optima, const double* normals,
+                                double* points_optima, int* index, int* failed_pivot, moe_error_t* err);
 /* compute_grad_variance_of_points -> ComputeGradVarianceOfPoints (gpp_math.cpp:1359-1373); out[num_derivs][m][m][dim] */
 int moe_gp_grad_variance(const moe_gp_t* gp, const double* pts, int num_pts, int num_derivs, double* out, moe_error_t* err);
 /* compute_grad_cholesky_variance_of_points -> ComputeGradCholeskyVarianceOfPoints (gpp_math.cpp:1454-1474) */
