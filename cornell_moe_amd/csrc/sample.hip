@@ -28,6 +28,15 @@ namespace {
 
 constexpr int kTrmmMinDraws = 8;       // from this many draws per set the draws are a TRMM on the FP64 matrix pipe (tile_gemm)
 constexpr int kMaxSetsPerPass = 2048;  // grid.z of the batched kernels (sets x K slices of the Gram kernel) stays below 65 536
+constexpr int kMaxGridY = 65535;
+
+// Sets per pass, from (N, C) alone -- never from E, so that a set's results do not depend on its batch.  Where V = L^-1 K* takes the
+// split-K kernels (launch_tri_gemm_cols: N >= 128, more than 16 columns per problem) the sum over the K slices runs one grid row
+// per candidate of the whole pass: grid.y = sets x C must stay within the 65 536 the device advertises.
+int sets_per_pass(int N, int C) {
+  if (N >= 128 && C > 16) return std::max(1, std::min(kMaxSetsPerPass, kMaxGridY / C));
+  return kMaxSetsPerPass;
+}
 
 __global__ __launch_bounds__(256) void sub_kernel(double* __restrict__ var, const double* __restrict__ gram, long n) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
@@ -157,7 +166,7 @@ void enqueue_draws(double mean, int C, int D, int e0, int ne, const double* dL, 
   MOE_HIP_CHECK(hipGetLastError());
 }
 
-// one pass over E <= kMaxSetsPerPass sets
+// one pass over E <= sets_per_pass(N, C) sets
 void sample_pass(GpDev& gp, const double* pts, int C, int E, const double* normals, int D, bool stop_at_failure, double* values,
                  int* argmin, int* failed) {
   hipStream_t s = gp.stream;
@@ -232,8 +241,9 @@ void sample_points_on_device(GpDev& gp, const double* pts, int C, int E, const d
   if (pts == nullptr || normals == nullptr || values == nullptr || argmin == nullptr || failed == nullptr)
     throw Error(MOE_ERR_RUNTIME, "NULL argument");
   gp.use_device();
-  for (int e0 = 0; e0 < E; e0 += kMaxSetsPerPass) {
-    const int ne = std::min(kMaxSetsPerPass, E - e0);
+  const int per_pass = sets_per_pass(gp.N, C);
+  for (int e0 = 0; e0 < E; e0 += per_pass) {
+    const int ne = std::min(per_pass, E - e0);
     const size_t DC = (size_t)D * C;
     sample_pass(gp, pts + (size_t)e0 * C * gp.d, C, ne, normals + e0 * DC, D, stop_at_failure, values + e0 * DC,
                 argmin + (size_t)e0 * D, failed + e0);
