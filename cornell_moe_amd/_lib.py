@@ -22,6 +22,13 @@ class GdParams(C.Structure):
                 ("max_relative_change", C.c_double), ("tolerance", C.c_double), ("domain_type", C.c_int)]
 
 
+class Prior(C.Structure):  # moe_prior_t
+    _fields_ = [("kind", C.c_int), ("a", C.c_double), ("b", C.c_double)]
+
+
+PRIOR_NONE, PRIOR_TOPHAT, PRIOR_NORMAL, PRIOR_HORSESHOE, PRIOR_LOGNORMAL, PRIOR_FIXED = 0, 1, 2, 3, 4, 5
+
+
 class KgStats(C.Structure):
     _fields_ = [("posterior_mean_evals", C.c_longlong), ("posterior_grad_evals", C.c_longlong), ("ms_state", C.c_double),
                 ("ms_mc", C.c_double), ("ms_tail", C.c_double)]
@@ -107,6 +114,7 @@ SIGNATURES = {
     "moe_ll_grad": (C.c_int, [C.c_void_p, dp, dp, _EP]),
     "moe_ll_ascend": (C.c_int, [C.c_void_p, C.POINTER(GdParams), dp, dp, dp, _EP]),
     "moe_ll_multistart": (C.c_int, [C.c_void_p, C.POINTER(GdParams), dp, dp, C.c_int, dp, dp, ip, _EP]),
+    "moe_ll_mcmc": (C.c_int, [C.c_void_p, C.POINTER(Prior), C.c_int, C.c_int, C.c_double, dp, dp, ip, dp, dp, dp, dp, dp, ip, _EP]),
     "moe_posterior_mean_optimize": (C.c_int, [_GP, C.c_int, C.POINTER(GdParams), dp, dp, dp, dp, _EP]),
     "moe_latin_hypercube": (C.c_int, [C.c_uint, dp, C.c_int, C.c_int, dp]),
     "moe_gp_mix_covariance": (C.c_int, [_GP, dp, C.c_int, ip, C.c_int, dp, _EP]),

@@ -849,3 +849,56 @@ class LogLikelihood(object):
         err = _lib.MoeError()
         _check(_lib.load().moe_ll_grad(self._h, h.ctypes.data_as(dp), out.ctypes.data_as(dp), C.byref(err)), err)
         return out
+
+    def mcmc(self, priors, p0, u_stretch, partner, u_accept, stretch_a=2.0, diagnostics=True):
+        """moe_ll_mcmc on this handle: see ll_mcmc."""
+        return ll_mcmc(self, priors, p0, u_stretch, partner, u_accept, stretch_a=stretch_a, diagnostics=diagnostics)
+
+
+def stretch_tables(rng, num_steps, num_walkers):
+    """The random tables of a stretch-move chain from a numpy.random.RandomState: per half-step W/2 uniforms for z, W/2
+    partner indices in [0, W/2), W/2 uniforms for the accept -- in that order.  Returns (u_stretch, partner, u_accept), each
+    [num_steps][2][W/2]."""
+    T, H = int(num_steps), int(num_walkers) // 2
+    u_stretch, partner, u_accept = np.zeros((T, 2, H)), np.zeros((T, 2, H), dtype=np.int32), np.zeros((T, 2, H))
+    for t in range(T):
+        for h in range(2):
+            u_stretch[t, h] = rng.rand(H)
+            partner[t, h] = rng.randint(H, size=H)
+            u_accept[t, h] = rng.rand(H)
+    return u_stretch, partner, u_accept
+
+
+def ll_mcmc(ll, priors, p0, u_stretch, partner, u_accept, stretch_a=2.0, diagnostics=True):
+    """moe_ll_mcmc: the stretch-move ensemble sampler over log-space hyper-parameters, the whole chain on the device.
+    ll: a LogLikelihood; priors: nh rows (kind, a, b) (_lib.PRIOR_*); p0 [W][nh]; the tables [T][2][W/2] (stretch_tables).
+    Returns a dict: chain [T][W][nh], lnprob [T][W], lnprob0 [W] and, with diagnostics, proposal_lnprob [T][W], accepted [T][W]."""
+    nh = 1 + ll.d + 1 + ll.g
+    table = [(int(k), float(a), float(b)) for k, a, b in priors]
+    if len(table) != nh:
+        raise BoundsException("the prior table needs one row per hyper-parameter", len(table), nh, nh)
+    p0 = np.ascontiguousarray(p0, dtype=np.float64)
+    if p0.ndim != 2 or p0.shape[1] != nh:
+        raise BoundsException("p0 must be [num_walkers][%d]" % nh, p0.shape[-1] if p0.ndim else 0, nh, nh)
+    W = p0.shape[0]
+    u_stretch = np.ascontiguousarray(u_stretch, dtype=np.float64)
+    u_accept = np.ascontiguousarray(u_accept, dtype=np.float64)
+    partner = np.ascontiguousarray(partner, dtype=np.int32)
+    T = u_stretch.shape[0] if u_stretch.ndim == 3 else 0
+    for name, a in (("u_stretch", u_stretch), ("partner", partner), ("u_accept", u_accept)):
+        if a.shape != (T, 2, W // 2):
+            raise BoundsException("%s must be [num_steps][2][num_walkers / 2]" % name, a.size, T * 2 * (W // 2), T * 2 * (W // 2))
+    pr = (_lib.Prior * nh)(*[_lib.Prior(k, a, b) for k, a, b in table])
+    chain, lnprob, lnprob0 = np.zeros((T, W, nh)), np.zeros((T, W)), np.zeros(W)
+    prop = np.zeros((T, W)) if diagnostics else None
+    acc = np.zeros((T, W), dtype=np.int32) if diagnostics else None
+    err = _lib.MoeError()
+    _check(_lib.load().moe_ll_mcmc(ll._h, pr, W, T, float(stretch_a), p0.ctypes.data_as(dp), u_stretch.ctypes.data_as(dp),
+                                   partner.ctypes.data_as(ip), u_accept.ctypes.data_as(dp), chain.ctypes.data_as(dp),
+                                   lnprob.ctypes.data_as(dp), lnprob0.ctypes.data_as(dp),
+                                   prop.ctypes.data_as(dp) if diagnostics else None,
+                                   acc.ctypes.data_as(ip) if diagnostics else None, C.byref(err)), err)
+    out = dict(chain=chain, lnprob=lnprob, lnprob0=lnprob0)
+    if diagnostics:
+        out.update(proposal_lnprob=prop, accepted=acc)
+    return out

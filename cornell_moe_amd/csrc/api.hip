@@ -79,6 +79,9 @@ struct moe_ll {
   hipStream_t stream = nullptr;
   moe::DevBuf<double> dX, dYc, dA, dLinv, dNoise, dOut, dScratch;
   moe::DevBuf<int> dInfo;
+  // moe_ll_mcmc: the call's inputs and outputs (one copy each way) and the sampler's state
+  moe::DevBuf<double> dMcIn, dMcOut, dMcWork;
+  moe::DevBuf<moe::CovParams> dMcCov;
   ~moe_ll() {
     if (stream) {
       (void)hipSetDevice(device);
@@ -1072,24 +1075,28 @@ int moe_ll_evaluate(moe_ll_t* ll, const double* hyperparameters_all, int num_set
 }  // extern "C"
 
 namespace {
+// The handle's stream and the device copies of its data (padded points, centred values), made on first use.
+void ll_ensure_device(moe_ll_t* ll) {
+  if (ll->stream) return;
+  const int g1 = 1 + ll->g, d = ll->d, n = ll->n, dp = moe::padded_dim(d);
+  MOE_HIP_CHECK(hipStreamCreate(&ll->stream));
+  std::vector<double> Xp((size_t)n * dp, 0.0), yc(ll->y);
+  for (int i = 0; i < n; ++i)
+    for (int k = 0; k < d; ++k) Xp[(size_t)i * dp + k] = ll->X[(size_t)i * d + k];
+  double mean = 0.0;  // centred on the mean of the function values (gpp_model_selection.cpp:555-563)
+  for (int i = 0; i < n; ++i) mean += ll->y[(size_t)i * g1];
+  mean /= n;
+  for (int i = 0; i < n; ++i) yc[(size_t)i * g1] -= mean;
+  ll->dX.upload(Xp.data(), Xp.size(), ll->stream);
+  ll->dYc.upload(yc.data(), yc.size(), ll->stream);
+  MOE_HIP_CHECK(hipStreamSynchronize(ll->stream));
+}
+
 void ll_evaluate_locked(moe_ll_t* ll, const double* hyperparameters_all, int num_sets, double* values) {
   {
     MOE_HIP_CHECK(hipSetDevice(ll->device));
     const int g1 = 1 + ll->g, d = ll->d, n = ll->n, N = n * g1, stride = 1 + d + g1;
-    const int dp = moe::padded_dim(d);
-    if (!ll->stream) {
-      MOE_HIP_CHECK(hipStreamCreate(&ll->stream));
-      std::vector<double> Xp((size_t)n * dp, 0.0), yc(ll->y);
-      for (int i = 0; i < n; ++i)
-        for (int k = 0; k < d; ++k) Xp[(size_t)i * dp + k] = ll->X[(size_t)i * d + k];
-      double mean = 0.0;  // centred on the mean of the function values (gpp_model_selection.cpp:555-563)
-      for (int i = 0; i < n; ++i) mean += ll->y[(size_t)i * g1];
-      mean /= n;
-      for (int i = 0; i < n; ++i) yc[(size_t)i * g1] -= mean;
-      ll->dX.upload(Xp.data(), Xp.size(), ll->stream);
-      ll->dYc.upload(yc.data(), yc.size(), ll->stream);
-      MOE_HIP_CHECK(hipStreamSynchronize(ll->stream));
-    }
+    ll_ensure_device(ll);
     hipStream_t s = ll->stream;
     moe::DerivList dl;
     dl.g = ll->g;
@@ -1155,6 +1162,154 @@ int moe_ll_grad(moe_ll_t* ll, const double* hyperparameters, double* grad, moe_e
     require(ll != nullptr && hyperparameters != nullptr && grad != nullptr, "NULL argument");
     std::lock_guard<std::mutex> lk(ll->mu);
     ll_grad_locked(ll, hyperparameters, grad);
+  });
+}
+
+}  // extern "C"
+
+namespace {
+// moe_ll_mcmc with the handle locked (include/moe_hip.h).  Everything between the upload and the final wait is enqueued on the
+// handle's stream: per half-step the proposals, one covariance launch and one batched factorisation per pass, the accept.
+void ll_mcmc_locked(moe_ll_t* ll, const moe_prior_t* priors, int W, int T, double stretch_a, const double* p0, const double* u_stretch,
+                    const int* partner, const double* u_accept, double* chain, double* lnprob, double* lnprob0, double* proposal_lnprob,
+                    int* accepted) {
+  const int g1 = 1 + ll->g, d = ll->d, n = ll->n, N = n * g1, nh = 1 + d + g1, H = W / 2;
+  if (W <= 0 || (W % 2) != 0 || W < 2 * nh)
+    throw moe::Error(MOE_ERR_BOUNDS, "num_walkers must be even and at least twice the number of hyper-parameters", W, 2 * nh, 1e9);
+  if (T < 0) throw moe::Error(MOE_ERR_BOUNDS, "num_steps must not be negative", T, 0, 1e9);
+  if ((double)T * W * (nh + 4) > 1.0e9) throw moe::Error(MOE_ERR_BOUNDS, "chain too long for one call", (double)T * W * (nh + 4), 0, 1e9);
+  if (!(stretch_a > 1.0) || !std::isfinite(stretch_a)) throw moe::Error(MOE_ERR_BOUNDS, "stretch_a must be > 1", stretch_a, 1.0, INFINITY);
+  int nh_free = 0;
+  for (int k = 0; k < nh; ++k) {
+    const moe_prior_t& pr = priors[k];
+    if (pr.kind < MOE_PRIOR_NONE || pr.kind > MOE_PRIOR_FIXED) throw moe::Error(MOE_ERR_BOUNDS, "unknown prior kind", pr.kind, 0, MOE_PRIOR_FIXED);
+    const bool bad = (pr.kind == MOE_PRIOR_TOPHAT && !(pr.b > pr.a)) || (pr.kind == MOE_PRIOR_NORMAL && !(pr.b > 0.0)) ||
+                     (pr.kind == MOE_PRIOR_HORSESHOE && !(pr.a > 0.0)) || (pr.kind == MOE_PRIOR_LOGNORMAL && !(pr.a > 0.0)) ||
+                     (pr.kind == MOE_PRIOR_FIXED && !(std::fabs(pr.a) <= 20.0));
+    if (bad) throw moe::Error(MOE_ERR_INVALID_VALUE, "prior parameters out of range", pr.a, pr.b, k);
+    if (pr.kind != MOE_PRIOR_FIXED) ++nh_free;
+  }
+  const size_t TW = (size_t)T * W;
+  for (size_t i = 0; i < TW; ++i)  // (the kernels index walkers with these)
+    if (partner[i] < 0 || partner[i] >= H) throw moe::Error(MOE_ERR_BOUNDS, "partner index out of range", partner[i], 0, H - 1);
+
+  MOE_HIP_CHECK(hipSetDevice(ll->device));
+  ll_ensure_device(ll);
+  hipStream_t s = ll->stream;
+  moe::DerivList dl;
+  dl.g = ll->g;
+  for (int i = 0; i < moe::kMaxDerivs; ++i) dl.idx[i] = (i < ll->g) ? ll->derivs[i] : 0;
+
+  // the inputs as one block of doubles: p0 | u_stretch | u_accept | priors | partner (ints)
+  static_assert(sizeof(moe_prior_t) == 3 * sizeof(double), "moe_prior_t is (int, pad, double, double)");
+  const size_t o_p0 = 0, o_us = o_p0 + (size_t)W * nh, o_ua = o_us + TW, o_pr = o_ua + TW, o_pt = o_pr + 3 * (size_t)nh,
+               n_in = o_pt + (TW + 1) / 2;
+  std::vector<double> in(n_in, 0.0);
+  std::memcpy(&in[o_p0], p0, sizeof(double) * W * nh);
+  if (TW > 0) {
+    std::memcpy(&in[o_us], u_stretch, sizeof(double) * TW);
+    std::memcpy(&in[o_ua], u_accept, sizeof(double) * TW);
+    std::memcpy(&in[o_pt], partner, sizeof(int) * TW);
+  }
+  std::memcpy(&in[o_pr], priors, sizeof(moe_prior_t) * nh);
+  ll->dMcIn.upload(in.data(), n_in, s);
+  // the outputs likewise: chain | lnprob | lnprob0 | proposal_lnprob | accepted (ints)
+  const size_t o_ch = 0, o_lp = o_ch + TW * nh, o_l0 = o_lp + TW, o_pl = o_l0 + W, o_ac = o_pl + TW, n_out = o_ac + (TW + 1) / 2;
+  ll->dMcOut.reserve(n_out);
+  // the sampler's state: walkers | lnp | prop | prior | zterm | noise
+  const size_t o_w = 0, o_ln = o_w + (size_t)W * nh, o_pp = o_ln + W, o_pi = o_pp + (size_t)H * nh, o_z = o_pi + H, o_nz = o_z + H,
+               n_work = o_nz + (size_t)H * g1;
+  ll->dMcWork.reserve(n_work);
+  ll->dMcCov.reserve(H);
+  moe::copy_async(ll->dMcWork.p + o_w, ll->dMcIn.p + o_p0, sizeof(double) * W * nh, hipMemcpyDeviceToDevice, s);
+
+  moe::HmcState st;
+  st.W = W;
+  st.H = H;
+  st.nh = nh;
+  st.d = d;
+  st.dp = moe::padded_dim(d);
+  st.g1 = g1;
+  st.cov_type = ll->cov_type;
+  st.nh_free = nh_free;
+  st.quirks = moe::reference_quirks() ? 1 : 0;
+  st.stretch_a = stretch_a;
+  st.priors = reinterpret_cast<const moe_prior_t*>(ll->dMcIn.p + o_pr);
+  st.u_stretch = ll->dMcIn.p + o_us;
+  st.partner = reinterpret_cast<const int*>(ll->dMcIn.p + o_pt);
+  st.u_accept = ll->dMcIn.p + o_ua;
+  st.walkers = ll->dMcWork.p + o_w;
+  st.lnp = ll->dMcWork.p + o_ln;
+  st.prop = ll->dMcWork.p + o_pp;
+  st.prior = ll->dMcWork.p + o_pi;
+  st.zterm = ll->dMcWork.p + o_z;
+  st.cps = ll->dMcCov.p;
+  st.noise = ll->dMcWork.p + o_nz;
+  st.chain = ll->dMcOut.p + o_ch;
+  st.lnprob = ll->dMcOut.p + o_lp;
+  st.lnprob0 = ll->dMcOut.p + o_l0;
+  st.proposal_lnprob = ll->dMcOut.p + o_pl;
+  st.accepted = reinterpret_cast<int*>(ll->dMcOut.p + o_ac);
+
+  // every proposal is a bordered (N + 1) x (N + 1) factorisation; as many per pass as ll_evaluate_locked's ~2 GB allow, at most 64.
+  // MOE_MCMC_PASS_SETS (tests): fewer.  The factorisation kernels are chosen from N alone, not from the pass size (a pass of ONE
+  // matrix would otherwise take launch_cholesky_batch's two-level route from N = 256 on), so a result does not depend on the pass
+  // it was computed in.
+  const int Np = N + 1;
+  const long lda = ((long)Np + 15) / 16 * 16;
+  const long mat = lda * Np;
+  int B = (int)std::max<long>(1, std::min<long>(64, (long)(2.0e9 / (16.0 * (double)mat))));
+  if (const char* env = std::getenv("MOE_MCMC_PASS_SETS"))
+    if (std::atoi(env) > 0) B = std::min(B, std::atoi(env));
+  B = std::min(B, H);
+  const bool one_level = Np < 2048;
+  ll->dA.reserve((size_t)mat * B);
+  ll->dLinv.reserve((size_t)mat * B);
+  ll->dOut.reserve((size_t)2 * H);
+  ll->dInfo.reserve(H);
+  ll->dScratch.reserve(moe::chol_scratch_doubles(Np));
+  auto half_step = [&](int step, int half) {
+    moe::launch_hmc_propose(st, step, half, s);
+    for (int b0 = 0; b0 < H; b0 += B) {
+      const int nb = std::min(B, H - b0);
+      moe::launch_hmc_cov_batch(st.dp, st.cps + b0, st.noise + (size_t)b0 * g1, ll->dX.p, n, dl, ll->dA.p, lda, mat, nb, one_level, s);
+      moe::launch_ll_border(ll->dA.p, lda, mat, N, ll->dYc.p, nb, s);
+      moe::launch_cholesky_batch(Np, ll->dA.p, lda, mat, ll->dLinv.p, lda, mat, ll->dInfo.p + b0, nb, s, ll->dScratch.p, one_level);
+      moe::launch_ll_terms_batch(ll->dA.p, lda, mat, N, ll->dOut.p + (size_t)2 * b0, nb, s);
+    }
+    moe::launch_hmc_accept(st, ll->dOut.p, ll->dInfo.p, N, step, half, s);
+  };
+  for (int half = 0; half < 2; ++half) half_step(-1, half);  // lnprob0
+  for (int t = 0; t < T; ++t)
+    for (int half = 0; half < 2; ++half) half_step(t, half);
+  std::vector<double> out(n_out);
+  ll->dMcOut.download(out.data(), n_out, s);
+  MOE_HIP_CHECK(hipStreamSynchronize(s));
+  for (int w = 0; w < W; ++w)
+    if (!std::isfinite(out[o_l0 + w]))
+      throw moe::Error(MOE_ERR_INVALID_VALUE, "an initial walker has no finite log posterior", w, out[o_l0 + w], 0.0);
+  std::memcpy(lnprob0, &out[o_l0], sizeof(double) * W);
+  if (TW > 0) {
+    std::memcpy(chain, &out[o_ch], sizeof(double) * TW * nh);
+    std::memcpy(lnprob, &out[o_lp], sizeof(double) * TW);
+    if (proposal_lnprob) std::memcpy(proposal_lnprob, &out[o_pl], sizeof(double) * TW);
+    if (accepted) std::memcpy(accepted, &out[o_ac], sizeof(int) * TW);
+  }
+}
+}  // namespace
+
+extern "C" {
+
+int moe_ll_mcmc(moe_ll_t* ll, const moe_prior_t* priors, int num_walkers, int num_steps, double stretch_a, const double* p0,
+                const double* u_stretch, const int* partner, const double* u_accept, double* chain, double* lnprob, double* lnprob0,
+                double* proposal_lnprob, int* accepted, moe_error_t* err) {
+  return guarded(err, [&] {
+    require(ll != nullptr && priors != nullptr && p0 != nullptr && lnprob0 != nullptr, "NULL argument");
+    require(num_steps <= 0 || (u_stretch != nullptr && partner != nullptr && u_accept != nullptr && chain != nullptr && lnprob != nullptr),
+            "NULL argument");
+    std::lock_guard<std::mutex> lk(ll->mu);
+    ll_mcmc_locked(ll, priors, num_walkers, num_steps, stretch_a, p0, u_stretch, partner, u_accept, chain, lnprob, lnprob0,
+                   proposal_lnprob, accepted);
   });
 }
 

@@ -151,4 +151,36 @@ void launch_cholesky_batch(int N, double* A, long lda, long a_stride, double* Li
 void launch_ll_border(double* A, long lda, long a_stride, int N, const double* yc, int batch, hipStream_t s);
 void launch_ll_terms_batch(const double* A, long lda, long a_stride, int N, double* out, int batch, hipStream_t s);
 
+// ---- the hyper-parameter ensemble sampler (moe_ll_mcmc; kernels in hyper_mcmc.hip, the loop in api.hip) ----
+// Everything a half-step's kernels read and write, all in device memory; H = W / 2 walkers move per half-step.
+struct HmcState {
+  int W, H, nh, d, dp, g1, cov_type, nh_free, quirks;
+  double stretch_a;
+  const moe_prior_t* priors;  // [nh]
+  const double* u_stretch;    // [T][2][H]
+  const int* partner;         // [T][2][H], each in [0, H)
+  const double* u_accept;     // [T][2][H]
+  double* walkers;            // [W][nh] current positions (log space)
+  double* lnp;                // [W] their log posterior
+  double* prop;               // [H][nh] the half-step's proposals
+  double* prior;              // [H] log prior of a proposal; -inf: rejected by the box or the prior
+  double* zterm;              // [H] (nh_free - 1) ln z
+  CovParams* cps;             // [H] linear-space covariance parameters of the proposals
+  double* noise;              // [H][g1] noise variances + 1e-6
+  double* chain;              // [T][W][nh]
+  double* lnprob;             // [T][W]
+  double* lnprob0;            // [W]
+  double* proposal_lnprob;    // [T][W] or NULL
+  int* accepted;              // [T][W] or NULL
+};
+// step >= 0: the proposals of half-step (step, half) from the stretch move; step < 0: the walkers of `half` themselves (the initial
+// evaluation).  FIXED coordinates applied, box and prior evaluated, covariance parameters written.
+void launch_hmc_propose(const HmcState& st, int step, int half, hipStream_t s);
+// out + b * set_stride (N x N, ld) = K(X, X; cps[b]) + diag(noise[b]) for b < sets, ONE launch; lower_only: rows >= columns only
+void launch_hmc_cov_batch(int dp, const CovParams* cps, const double* noise, const double* X, int n, const DerivList& dl, double* out,
+                          long ld, long set_stride, int sets, bool lower_only, hipStream_t s);
+// terms[H][2] / info[H]: what launch_ll_terms_batch / launch_cholesky_batch left for the H proposals.  step >= 0: decide and append
+// row `step` of the outputs; step < 0: store the walkers (FIXED applied) and lnprob0.
+void launch_hmc_accept(const HmcState& st, const double* terms, const int* info, int N, int step, int half, hipStream_t s);
+
 }  // namespace moe

@@ -466,6 +466,58 @@ int moe_ll_multistart(moe_ll_t* ll, const moe_gd_params_t* gd_params, const doub
 int moe_ll_ascend(moe_ll_t* ll, const moe_gd_params_t* gd_params, const double* domain_log10, const double* x0, double* end_point,
                   moe_error_t* err);
 
+/* ---- hyper-parameter sampling: GaussianProcessLogLikelihoodMCMC.train() (python/cpp_wrappers/log_likelihood_mcmc.py:170-239),
+ * which hands its log posterior to emcee.EnsembleSampler.  moe_ll_mcmc is that sampler -- the affine-invariant ensemble sampler with
+ * the stretch move (Goodman & Weare 2010) -- with the whole chain resident on the device: one upload, one stream of kernels for all
+ * num_steps steps, one wait, one download.
+ *
+ * State: num_walkers = W walkers of nh = 1 + dim + 1 + g log-space coordinates theta = log(alpha, lengths[dim], noise[1 + g]).
+ * W must be even and >= 2 nh (MOE_ERR_BOUNDS; the wrapper's default is max(n_hypers, 2 nh), log_likelihood_mcmc.py:122).
+ *
+ * Log posterior of a walker: -inf if any |theta_k| > 20 (log_likelihood_mcmc.py:286) or the log prior is -inf; otherwise
+ * log prior(theta) + the log marginal likelihood at exp(theta) exactly as moe_ll_evaluate defines it (1e-6 on the diagonal, values
+ * centred, -inf on a failed pivot).
+ *
+ * The prior is a table of nh entries (kind, a, b), one per coordinate, in log space; the per-coordinate terms are added
+ * (default_priors.py:27-36), -inf wins over +inf.  With moe_set_reference_quirks(1), the default, NORMAL and HORSESHOE are what the
+ * reference computes; with quirks off they are what it intends:
+ *   MOE_PRIOR_NONE                  0
+ *   MOE_PRIOR_TOPHAT    (min, max)  0 inside [min, max], -inf outside                                    (base_prior.py:120-123)
+ *   MOE_PRIOR_NORMAL    (mean, sd)  quirks: the normal DENSITY, not its log (base_prior.py:354, sic); off: the log density
+ *   MOE_PRIOR_HORSESHOE (scale)     quirks: ln ln(1 + 3 (scale / theta)^2) of the LOG-SPACE coordinate, +inf at theta = 0
+ *                                   (base_prior.py:199-201, sic); off: the same formula of exp(theta)
+ *   MOE_PRIOR_LOGNORMAL (sd, mean)  scipy.stats.lognorm.logpdf(theta, sd, loc=mean)                      (base_prior.py:281)
+ *   MOE_PRIOR_FIXED     (value)     the coordinate is set to `value` in every proposal before it is evaluated, and stored so; it adds
+ *                                   nothing.  This is the wrapper's noisy=False (noise pinned at log 1e-8, log_likelihood_mcmc.py:288-289)
+ * DefaultPrior (default_priors.py:19-35) is NORMAL(0, 1) on alpha, TOPHAT(-2, 3) on the lengths, HORSESHOE(0.1) on the noises.
+ *
+ * One step is two half-steps: walkers [0, W/2) move against [W/2, W), then the second half against the updated first.  For walker s
+ * of the moving half, at index i of half-step (t, h) of the tables below:
+ *   c = walker partner[t][h][i] of the other half;   z = ((a - 1) u_stretch[t][h][i] + 1)^2 / a   (a = stretch_a > 1; emcee's is 2);
+ *   proposal = c - z (c - s);   ln r = (nh_free - 1) ln z + lnp(proposal) - lnp(s),   nh_free = the coordinates that are not FIXED;
+ *   accepted iff ln r > ln u_accept[t][h][i], and always when lnp(proposal) = +inf.
+ * Randomness crosses the ABI as tables, as everywhere in this library: u_stretch, u_accept [num_steps][2][W/2] uniforms in [0, 1),
+ * partner [num_steps][2][W/2] integers in [0, W/2) (MOE_ERR_BOUNDS otherwise).
+ *
+ * p0[W][nh]: the initial walkers.  Each must have a finite log posterior: otherwise MOE_ERR_INVALID_VALUE (payload: the first such
+ * walker's index, its log posterior) and the outputs are undefined.
+ * chain[num_steps][W][nh] and lnprob[num_steps][W]: positions and log posteriors AFTER step t.  lnprob0[W]: of p0.
+ * proposal_lnprob[num_steps][W] (or NULL): the log posterior of the proposal made for walker w in step t, accepted or not;
+ * accepted[num_steps][W] (or NULL): 1 / 0.  num_steps = 0 evaluates lnprob0 only. */
+#define MOE_PRIOR_NONE 0
+#define MOE_PRIOR_TOPHAT 1
+#define MOE_PRIOR_NORMAL 2
+#define MOE_PRIOR_HORSESHOE 3
+#define MOE_PRIOR_LOGNORMAL 4
+#define MOE_PRIOR_FIXED 5
+typedef struct moe_prior {
+  int kind; /* MOE_PRIOR_* */
+  double a, b;
+} moe_prior_t;
+int moe_ll_mcmc(moe_ll_t* ll, const moe_prior_t* priors, int num_walkers, int num_steps, double stretch_a, const double* p0,
+                const double* u_stretch, const int* partner, const double* u_accept, double* chain, double* lnprob, double* lnprob0,
+                double* proposal_lnprob, int* accepted, moe_error_t* err);
+
 /* ---- covariance assembly (exposed for parity tests and the HBM-roofline measurement) ----
  * BuildMixCovarianceMatrix (gpp_math.cpp:309-335, 469-479): out[N x num_pts*(1+g2)] col-major = K(X, pts) with
  * derivative blocks; derivs2[g2] are the derivative observations carried by `pts`. */
