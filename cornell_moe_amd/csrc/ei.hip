@@ -3,8 +3,9 @@
 // ExpectedImprovementEvaluator::ComputeExpectedImprovement / ComputeGradExpectedImprovement (gpp_math.cpp:1991-2126):
 //   V = Var(Xu) + 1e-6 I,  L = chol(V),  per sample: y = mu + L z,  I = max(0, max_j (best_so_far - y_j)),  w = argmax;
 //   EI = sum I / M;   grad EI[k,:] = (1/M) sum_{I>0} ( -[w == k] grad mu_k  -  sum_j dL[w][j]/dXs_k z_j ).
-// One lane per MC sample (the per-sample work is O(u^2), u <= 16); sums are block-reduced in a fixed order and finished
-// by a single workgroup, so results are bitwise reproducible.
+// One lane per MC sample (the per-sample work is O(u^2), u <= 64: the sample loop is unrolled for 16, 32 or 64 points; the u x u
+// algebra in front of it runs on the device up to u = 16 and on the host above); sums are block-reduced in a fixed order and
+// finished by a single workgroup, so results are bitwise reproducible.
 #include <cmath>
 #include <cstring>
 
