@@ -248,6 +248,19 @@ class GaussianProcess(object):
     def compute_grad_cholesky_variance_of_points(self, points_to_sample, num_to_sample, num_derivatives):
         return list(self._dev.grad_cholesky_variance(self._pts(points_to_sample, num_to_sample), num_derivatives))
 
+    def compute_mean_and_std_of_points(self, points_to_sample, num_to_sample):
+        """Marginal posterior mean and standard deviation of the function value at each point (moe_gp_mean_std; not in the
+        reference): the flat list [mean_0 .. mean_{k-1}, std_0 .. std_{k-1}].  std_i is entry [0,0] of
+        compute_cholesky_variance_of_points of point i alone; the k x k covariance is never formed."""
+        mean, std = self._dev.mean_std(self._pts(points_to_sample, num_to_sample))
+        return list(mean) + list(std)
+
+    def lower_confidence_bound_select(self, candidate_pts, num_candidates, num_to_sample):
+        """The selection of cpp_wrappers/lower_confidence_bound.py on the device (moe_gp_lcb_select): the flat list
+        [num_to_sample * dim] of the picked candidates.  This GP is not modified."""
+        _, points, _ = self._dev.lcb_select(self._pts(candidate_pts, num_candidates), num_to_sample)
+        return list(points.ravel())
+
     def add_sampled_points(self, new_points, new_points_value, num_new_points):
         pts = self._pts(new_points, num_new_points)
         vals = _flat(new_points_value, num_new_points * (1 + self._g)).reshape(num_new_points, 1 + self._g)

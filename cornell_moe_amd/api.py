@@ -295,6 +295,36 @@ class DeviceGP(object):
                                                        failed.ctypes.data_as(ip), C.byref(err)), err)
         return points, index, failed
 
+    def mean_std(self, pts):
+        """moe_gp_mean_std: marginal posterior (mean [C], std [C]) of the function value at pts [C][dim]; the C x C covariance is
+        never formed.  SingularMatrixException(1, i) for the first candidate i whose variance fails the pivot rule."""
+        pts, pp = _d(pts)
+        C_ = pts.reshape(-1, self.d).shape[0]
+        mean = np.zeros(C_)
+        std = np.zeros(C_)
+        err = _lib.MoeError()
+        _check(_lib.load().moe_gp_mean_std(self._h, pp, C_, mean.ctypes.data_as(dp), std.ctypes.data_as(dp), C.byref(err)), err)
+        return mean, std
+
+    def lcb_select(self, candidates, q, want_surface=False):
+        """moe_gp_lcb_select: batch lower-confidence-bound selection of q of the candidates [C][dim] on the device; this GP is not
+        modified.  Returns (index [q], points [q][dim], num_kept), with want_surface also (mean [C], std [C]) behind them."""
+        cand, cp = _d(candidates)
+        C_ = cand.reshape(-1, self.d).shape[0]
+        q = int(q)
+        index = np.zeros(max(q, 1), dtype=np.int32)
+        points = np.zeros((max(q, 1), self.d))
+        mean = np.zeros(C_) if want_surface else None
+        std = np.zeros(C_) if want_surface else None
+        kept = C.c_int(0)
+        err = _lib.MoeError()
+        _check(_lib.load().moe_gp_lcb_select(self._h, cp, C_, q, index.ctypes.data_as(ip), points.ctypes.data_as(dp),
+                                             mean.ctypes.data_as(dp) if want_surface else None,
+                                             std.ctypes.data_as(dp) if want_surface else None, C.byref(kept), C.byref(err)), err)
+        if want_surface:
+            return index, points, kept.value, mean, std
+        return index, points, kept.value
+
     def mix_covariance(self, pts, derivs2=()):
         pts, pp = _d(pts)
         k = pts.reshape(-1, self.d).shape[0]

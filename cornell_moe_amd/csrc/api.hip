@@ -252,6 +252,26 @@ int moe_gp_sample_global_optima(const moe_gp_t* gp_c, const double* candidates, 
   });
 }
 
+int moe_gp_mean_std(const moe_gp_t* gp_c, const double* candidates, int num_candidates, double* mean_out, double* std_out,
+                    moe_error_t* err) {
+  return guarded(err, [&] {
+    std::unique_lock<std::mutex> lk;
+    moe::GpDev& gp = lock_gp(gp_c, lk);
+    moe::mean_std_on_device(gp, candidates, num_candidates, mean_out, std_out);
+  });
+}
+
+int moe_gp_lcb_select(const moe_gp_t* gp_c, const double* candidates, int num_candidates, int num_to_sample, int* index_out,
+                      double* points_out, double* mean_out, double* std_out, int* num_kept_out, moe_error_t* err) {
+  return guarded(err, [&] {
+    std::unique_lock<std::mutex> lk;
+    moe::GpDev& gp = lock_gp(gp_c, lk);
+    moe::lcb_select_on_device(gp, candidates, num_candidates, num_to_sample, index_out, points_out, mean_out, std_out, num_kept_out);
+  });
+}
+
+int moe_lcb_pass_size(int num_rows, int num_candidates) { return moe::lcb_pass_size(num_rows, num_candidates); }
+
 int moe_gp_grad_variance(const moe_gp_t* gp_c, const double* pts, int num_pts, int num_derivs, double* out,
                          moe_error_t* err) {
   return guarded(err, [&] {

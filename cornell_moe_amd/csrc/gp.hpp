@@ -58,6 +58,9 @@ struct GpDev {
   // their argmin [E][D]; the factorisations' status words [E] and the resumed factorisations' [E]
   DevBuf<double> sMat, sOut;
   DevBuf<int> sInfo;
+  // marginal mean / std and LCB selection (lcb.hip): the call's doubles (results first: one copy back) and integers
+  DevBuf<double> lcbD;
+  DevBuf<int> lcbI;
   int num_cu = 256;
   // per-dimension mean and max |x - mean| of the training points (refreshed by rebuild() and by the append path of add_points):
   // the frame centre of the KG coordinate tables and the extent the kernel selection needs, so that an evaluation does not
@@ -185,6 +188,15 @@ void enqueue_sample_state_batch(GpDev& gp, const double* U_all, int C, int E, co
 // semidefinite continuation that comment names).
 void sample_points_on_device(GpDev& gp, const double* pts, int C, int E, const double* normals, int D, bool stop_at_failure,
                              double* values, int* argmin, int* failed);
+// lcb.hip: marginal posterior mean and standard deviation of the function value at C points, C x C never formed; a candidate whose
+// variance fails the pivot rule (var > 1e-16) raises MOE_ERR_SINGULAR with payload (1, index of the first such candidate).
+// Candidates go through in passes of lcb_pass_size(N, C), a function of (N, C) alone.
+int lcb_pass_size(int N, int C);
+void mean_std_on_device(GpDev& gp, const double* pts, int C, double* mean_out, double* std_out);
+// lower_confidence_bound_optimization (cpp_wrappers/lower_confidence_bound.py) on the device; the GP is not modified.  index_out[q];
+// points_out[q][d], mean_out[C], std_out[C], num_kept_out may be NULL.
+void lcb_select_on_device(GpDev& gp, const double* pts, int C, int q, int* index_out, double* points_out, double* mean_out,
+                          double* std_out, int* num_kept_out);
 // r6 (query_grad.hip): ComputeGradVarianceOfPoints / ComputeGradCholeskyVarianceOfPoints (gpp_math.cpp:1267-1474) for the first
 // `num_derivs` of the `num_pts` points, the m x m x d algebra on the device: out[num_derivs][d m m] in the reference's layout.
 void grad_variance_on_device(GpDev& gp, const double* pts, int num_pts, int num_derivs, bool cholesky, double* out);

@@ -195,6 +195,19 @@ def check_optimisers():
     return bool(ok and abs(at_end - val) <= 1e-9 * max(1.0, abs(val)) and at_end >= at_starts.max() - 1e-9)
 
 
+def check_lcb():
+    """lcb_select with q = 1 is the argmin of mean - std from mean_std, and std^2 is the diagonal of the variance matrix."""
+    rng, X, y, hyper = _problem(seed=18)
+    G = api.DeviceGP(hyper, X, y, [0.01])
+    cand = rng.uniform(size=(300, 3))
+    mean, std = G.mean_std(cand)
+    index, points, kept = G.lcb_select(cand, 1)
+    ok = index[0] == int(np.argmin(mean - std)) and np.array_equal(points[0], cand[index[0]])
+    ok = ok and kept == int(np.sum(mean - std <= np.min(mean + std)))
+    var = G.variance(cand[:8]).reshape(8, 8)
+    return bool(ok and _close(std[:8] ** 2, np.diag(var), 1e-10) and _close(mean[:8], G.mean(cand[:8]), 1e-10))
+
+
 CHECKS = (
     ("linear algebra: Cholesky factor and inverse factor", check_linear_algebra),
     ("ping GP mean", check_ping_gp_mean),
@@ -206,6 +219,7 @@ CHECKS = (
     ("ping log marginal likelihood", check_ping_log_likelihood),
     ("random number sources and Latin hypercube", check_random_sources),
     ("optimisers: posterior-mean descent, q-KG multistart", check_optimisers),
+    ("LCB selection: q = 1 is the argmin of mean - std, std^2 the variance diagonal", check_lcb),
 )
 
 

@@ -142,6 +142,42 @@ int moe_gp_sample_points(const moe_gp_t* gp, const double* pts, int num_pts, con
  * with D = 1. */
 int moe_gp_sample_global_optima(const moe_gp_t* gp, const double* candidates, int inner_number, int num_optima, const double* normals,
                                 double* points_optima, int* index, int* failed_pivot, moe_error_t* err);
+/* Marginal posterior mean and standard deviation of the FUNCTION VALUE at each of num_candidates points, without the
+ * num_candidates^2 covariance: mean_out[i] is what moe_gp_mean returns, std_out[i] = sqrt(var_i) with
+ * var_i = k(c_i, c_i) - |L^-1 k*(c_i)|^2 over all N = num_sampled (1 + num_derivatives) training rows -- entry [0,0] of
+ * moe_gp_cholesky_variance of that single point.  A candidate whose var fails the pivot rule (var > 1e-16,
+ * gpp_linear_algebra.cpp:117-143) makes the call fail with MOE_ERR_SINGULAR, payload (1, index of the first such candidate):
+ * what a loop of compute_cholesky_variance_of_points over the candidates raises there.
+ * DEVIATION: with derivative observations the reference also factors the candidate's own derivative rows and can fail on one of
+ * their pivots; those rows are not formed here.
+ * No limit on num_candidates beyond memory: candidates go through in passes of moe_lcb_pass_size(N, num_candidates), a function
+ * of those two numbers alone, and every kernel is chosen from them alone, so a candidate's bits do not depend on its neighbours.
+ * MOE_ERR_BOUNDS for num_candidates < 1. */
+int moe_gp_mean_std(const moe_gp_t* gp, const double* candidates, int num_candidates, double* mean_out, double* std_out,
+                    moe_error_t* err);
+int moe_lcb_pass_size(int num_rows, int num_candidates);
+/* lower_confidence_bound_optimization (cpp_wrappers/lower_confidence_bound.py) on the device: one copy down, one wait, one copy
+ * back, and the handle is NEVER modified (the reference appends its picks to the caller's GP; cornell_moe_amd's Python function of
+ * the same name does that under reference quirks).
+ *   1. mean, std as moe_gp_mean_std; target = mean - std, ucb = mean + std;
+ *   2. index_out[0] = first index of min(target) (numpy argmin);
+ *   3. kept set = {i : target_i <= min(ucb)} in candidate order, its size in *num_kept_out;
+ *   4. for t = 1 .. num_to_sample - 1: the 1 + num_derivatives observation rows of candidate index_out[t-1] join the data with
+ *      the GP's own noise variances (values play no part); index_out[t] = first index of the largest conditional std over the
+ *      kept set.  A kept set smaller than num_to_sample re-picks points, as the reference does.
+ * points_out[num_to_sample][dim] = the picked candidates; mean_out / std_out [num_candidates] (step 1's) -- each of the four
+ * optional outputs may be NULL.
+ * MOE_ERR_SINGULAR: a candidate failing step 1's pivot rule (payload as moe_gp_mean_std), or a conditioning block whose Schur
+ * pivot is <= 1e-16 -- the reference's add_sampled_points raising on a noiseless duplicate (payload: rows of the extended matrix,
+ * failing leading minor).
+ * DEVIATIONS: the one of moe_gp_mean_std; the reference's SamplePoint carries a noise of 0.25 that its own add_sampled_points
+ * ignores (gaussian_process.py:334-339 passes no noise on), so the GP's own noise applies here too; in the rounds a kept
+ * candidate whose conditional variance has dropped to the pivot threshold or below (the noiseless pick itself) counts with
+ * std = sqrt(max(var, 0)) where the reference's per-candidate factorisation would raise.
+ * Limits: 1 <= num_to_sample <= 64 at every num_derivatives and dim <= 32, num_candidates >= 1 (MOE_ERR_BOUNDS otherwise).
+ * Memory: 8 num_candidates (N + (num_to_sample - 1)(1 + num_derivatives) + 5) bytes besides a pass's K*. */
+int moe_gp_lcb_select(const moe_gp_t* gp, const double* candidates, int num_candidates, int num_to_sample, int* index_out,
+                      double* points_out, double* mean_out, double* std_out, int* num_kept_out, moe_error_t* err);
 /* compute_grad_variance_of_points -> ComputeGradVarianceOfPoints (gpp_math.cpp:1359-1373); out[num_derivs][m][m][dim] */
 int moe_gp_grad_variance(const moe_gp_t* gp, const double* pts, int num_pts, int num_derivs, double* out, moe_error_t* err);
 /* compute_grad_cholesky_variance_of_points -> ComputeGradCholeskyVarianceOfPoints (gpp_math.cpp:1454-1474) */
