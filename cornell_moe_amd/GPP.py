@@ -674,30 +674,33 @@ def evaluate_EI_mcmc_at_point_list(gaussian_process_mcmc, initial_guesses, point
 _LL_CACHE = {}  # data fingerprint -> api.LogLikelihood: a sampler evaluates thousands of hyper-parameter sets on the same data
 
 
-def _ll_handle(points_sampled, points_sampled_value, dim, num_sampled, derivatives, num_derivatives):
+def _ll_handle(points_sampled, points_sampled_value, dim, num_sampled, derivatives, num_derivatives,
+               objective=LogLikelihoodTypes.log_marginal_likelihood):
     X = _flat(points_sampled, dim * num_sampled).reshape(num_sampled, dim)
     y = _flat(points_sampled_value, num_sampled * (1 + num_derivatives)).reshape(num_sampled, 1 + num_derivatives)
     derivs = tuple(int(v) for v in list(derivatives)[:num_derivatives])
-    key = (X.tobytes(), y.tobytes(), derivs)
+    key = (X.tobytes(), y.tobytes(), derivs, int(objective))
     h = _LL_CACHE.get(key)
     if h is None:
         if len(_LL_CACHE) >= 4:
             _LL_CACHE.clear()
-        h = _LL_CACHE[key] = _api.LogLikelihood(X, y, derivs)
+        h = _LL_CACHE[key] = _api.LogLikelihood(X, y, derivs, objective=int(objective))
     return h
 
 
 def _check_objective(objective_type):
-    if int(objective_type) != int(LogLikelihoodTypes.log_marginal_likelihood):
+    """The objective as the device's integer (its MOE_LL_* values are LogLikelihoodTypes'); anything else is refused."""
+    if int(objective_type) not in (int(LogLikelihoodTypes.log_marginal_likelihood), int(LogLikelihoodTypes.leave_one_out_log_likelihood)):
         raise OptimalLearningException("ERROR: invalid objective mode choice. Setting log likelihood to -DBL_MAX.")
+    return int(objective_type)
 
 
 def compute_log_likelihood(points_sampled, points_sampled_value, dim, num_sampled, objective_type, hyperparameters, derivatives,
                            num_derivatives, noise_variance):
     """ComputeLogLikelihoodWrapper (gpp_python_model_selection.cpp:43-69): log marginal likelihood with a Matern-5/2 kernel;
     hyperparameters = [alpha, [lengths]] (cpp_utils.cppify_hyperparameters)."""
-    _check_objective(objective_type)
-    h = _ll_handle(points_sampled, points_sampled_value, dim, num_sampled, derivatives, num_derivatives)
+    objective = _check_objective(objective_type)
+    h = _ll_handle(points_sampled, points_sampled_value, dim, num_sampled, derivatives, num_derivatives, objective)
     hyper = np.r_[float(hyperparameters[0]), _flat(hyperparameters[1], dim), _flat(noise_variance, 1 + num_derivatives)]
     return float(h.evaluate(hyper[None, :])[0])
 
@@ -706,8 +709,8 @@ def compute_hyperparameter_grad_log_likelihood(points_sampled, points_sampled_va
                                                hyperparameters, derivatives, num_derivatives, noise_variance):
     """ComputeHyperparameterGradLogLikelihoodWrapper (gpp_python_model_selection.cpp:88-135): list of
     1 + dim + 1 + num_derivatives partials wrt (alpha, lengths, noise variances), Matern-5/2 kernel."""
-    _check_objective(objective_type)
-    h = _ll_handle(points_sampled, points_sampled_value, dim, num_sampled, derivatives, num_derivatives)
+    objective = _check_objective(objective_type)
+    h = _ll_handle(points_sampled, points_sampled_value, dim, num_sampled, derivatives, num_derivatives, objective)
     hyper = np.r_[float(hyperparameters[0]), _flat(hyperparameters[1], dim), _flat(noise_variance, 1 + num_derivatives)]
     return list(h.grad(hyper))
 
@@ -717,8 +720,8 @@ def evaluate_log_likelihood_at_hyperparameter_list(hyperparameter_list, points_s
                                                    num_derivatives, num_multistarts, max_num_threads, status):
     """EvaluateLogLikelihoodAtHyperparameterListWrapper (gpp_python_model_selection.cpp:281-340): hyperparameter_list is
     flat [num_multistarts][1 + dim + 1 + num_derivatives]."""
-    _check_objective(objective_mode)
-    h = _ll_handle(points_sampled, points_sampled_value, dim, num_sampled, derivatives, num_derivatives)
+    objective = _check_objective(objective_mode)
+    h = _ll_handle(points_sampled, points_sampled_value, dim, num_sampled, derivatives, num_derivatives, objective)
     width = 1 + dim + 1 + num_derivatives
     vals = h.evaluate(_flat(hyperparameter_list, width * num_multistarts).reshape(num_multistarts, width))
     status["evaluate_log_marginal_likelihood_at_hyperparameter_list"] = bool(len(vals) > 0 and np.max(vals) > -np.inf)
@@ -743,8 +746,8 @@ def multistart_hyperparameter_optimization(optimizer_parameters, hyperparameter_
     stepped together on the device (moe_ll_multistart); null: the Latin-hypercube value search (:1342-1363) over num_random_samples
     points.  status gets the reference's key."""
     opt = optimizer_parameters
-    _check_objective(getattr(opt, "objective_type", LogLikelihoodTypes.log_marginal_likelihood))
-    h = _ll_handle(points_sampled, points_sampled_value, dim, num_sampled, derivatives, num_derivatives)
+    objective = _check_objective(getattr(opt, "objective_type", LogLikelihoodTypes.log_marginal_likelihood))
+    h = _ll_handle(points_sampled, points_sampled_value, dim, num_sampled, derivatives, num_derivatives, objective)
     nh = 1 + dim + 1 + num_derivatives
     dom = _flat(hyperparameter_domain, 2 * nh).reshape(nh, 2)
     if int(opt.optimizer_type) == int(OptimizerTypes.gradient_descent):

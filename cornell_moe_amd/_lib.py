@@ -27,6 +27,7 @@ class Prior(C.Structure):  # moe_prior_t
 
 
 PRIOR_NONE, PRIOR_TOPHAT, PRIOR_NORMAL, PRIOR_HORSESHOE, PRIOR_LOGNORMAL, PRIOR_FIXED = 0, 1, 2, 3, 4, 5
+LL_LOG_MARGINAL, LL_LEAVE_ONE_OUT = 0, 1  # MOE_LL_*: the values of the reference's LogLikelihoodTypes
 
 
 class KgStats(C.Structure):
@@ -115,6 +116,9 @@ SIGNATURES = {
     "moe_ll_destroy": (C.c_int, [C.c_void_p]),
     "moe_ll_evaluate": (C.c_int, [C.c_void_p, dp, C.c_int, dp, _EP]),
     "moe_ll_grad": (C.c_int, [C.c_void_p, dp, dp, _EP]),
+    "moe_ll_set_objective": (C.c_int, [C.c_void_p, C.c_int, _EP]),
+    "moe_ll_get_objective": (C.c_int, [C.c_void_p]),
+    "moe_ll_loo_predict": (C.c_int, [C.c_void_p, dp, dp, dp, _EP]),
     "moe_ll_ascend": (C.c_int, [C.c_void_p, C.POINTER(GdParams), dp, dp, dp, _EP]),
     "moe_ll_multistart": (C.c_int, [C.c_void_p, C.POINTER(GdParams), dp, dp, C.c_int, dp, dp, ip, _EP]),
     "moe_ll_mcmc": (C.c_int, [C.c_void_p, C.POINTER(Prior), C.c_int, C.c_int, C.c_double, dp, dp, ip, dp, dp, dp, dp, dp, ip, _EP]),

@@ -812,10 +812,11 @@ def kg_mcmc_multistart_multi(mcmc, num_workers, outer_params, inner_params, boun
 
 
 class LogLikelihood(object):
-    """Log marginal likelihood of fixed data under varying hyper-parameters (moe_ll_*): the evaluator a hyper-parameter
-    sampler calls thousands of times (LogMarginalLikelihoodEvaluator, gpp_model_selection.cpp:540-612)."""
+    """Log likelihood of fixed data under varying hyper-parameters (moe_ll_*): the evaluator a hyper-parameter
+    sampler calls thousands of times (LogMarginalLikelihoodEvaluator, gpp_model_selection.cpp:540-612).  objective:
+    _lib.LL_LOG_MARGINAL (the default) or _lib.LL_LEAVE_ONE_OUT -- what evaluate, grad, ascend, multistart and mcmc compute."""
 
-    def __init__(self, X, y, derivatives=(), cov_type=_lib.COV_MATERN_NU_2P5, device=0):
+    def __init__(self, X, y, derivatives=(), cov_type=_lib.COV_MATERN_NU_2P5, device=0, objective=_lib.LL_LOG_MARGINAL):
         X = np.ascontiguousarray(X, dtype=np.float64)
         self.n, self.d = X.shape
         self.derivatives = [int(v) for v in derivatives]
@@ -827,6 +828,27 @@ class LogLikelihood(object):
         _check(_lib.load().moe_ll_create(int(cov_type), X.ctypes.data_as(dp), y.ctypes.data_as(dp),
                                          dv.ctypes.data_as(ip) if self.g else None, self.g, self.d, self.n, int(device),
                                          C.byref(self._h), C.byref(err)), err)
+        if int(objective) != _lib.LL_LOG_MARGINAL:
+            self.set_objective(objective)
+
+    @property
+    def objective(self):
+        return int(_lib.load().moe_ll_get_objective(self._h))
+
+    def set_objective(self, objective):
+        """moe_ll_set_objective: _lib.LL_LOG_MARGINAL or _lib.LL_LEAVE_ONE_OUT (BoundsException otherwise)."""
+        err = _lib.MoeError()
+        _check(_lib.load().moe_ll_set_objective(self._h, int(objective), C.byref(err)), err)
+
+    def loo_predict(self, hyperparameters):
+        """moe_ll_loo_predict: the leave-one-out predictive (mean, var), each [n][1 + g], of every observation at one
+        hyper-parameter set [1 + dim + 1 + g], whatever the handle's objective."""
+        h = np.ascontiguousarray(hyperparameters, dtype=np.float64).reshape(1 + self.d + 1 + self.g)
+        mean, var = np.zeros((self.n, 1 + self.g)), np.zeros((self.n, 1 + self.g))
+        err = _lib.MoeError()
+        _check(_lib.load().moe_ll_loo_predict(self._h, h.ctypes.data_as(dp), mean.ctypes.data_as(dp), var.ctypes.data_as(dp),
+                                              C.byref(err)), err)
+        return mean, var
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:

@@ -74,10 +74,12 @@ struct moe_ll {
   std::vector<double> X, y;
   std::vector<int> derivs;
   std::mutex mu;                   // calls on one handle are serialised, like moe_gp_t's
-  std::unique_ptr<moe::GpDev> gp;  // moe_ll_grad's factorisation (with the inverse factor)
+  int objective = MOE_LL_LOG_MARGINAL;  // MOE_LL_*: what evaluate / grad / ascend / multistart / mcmc compute
+  std::unique_ptr<moe::GpDev> gp;  // moe_ll_grad's and moe_ll_loo_predict's factorisation (with the inverse factor)
   // moe_ll_evaluate: batches of bordered factorisations (kernels.hpp launch_cholesky_batch)
   hipStream_t stream = nullptr;
   moe::DevBuf<double> dX, dYc, dA, dLinv, dNoise, dOut, dScratch;
+  moe::DevBuf<double> dLoo;  // the leave-one-out terms' per-row vectors (kernels.hpp launch_loo_terms_batch)
   moe::DevBuf<int> dInfo;
   // moe_ll_mcmc: the call's inputs and outputs (one copy each way) and the sampler's state
   moe::DevBuf<double> dMcIn, dMcOut, dMcWork;
@@ -1149,7 +1151,13 @@ void ll_evaluate_locked(moe_ll_t* ll, const double* hyperparameters_all, int num
       moe::launch_ll_border(ll->dA.p, lda, mat, N, ll->dYc.p, nb, s);
       ll->dScratch.reserve(moe::chol_scratch_doubles(Np));
       moe::launch_cholesky_batch(Np, ll->dA.p, lda, mat, ll->dLinv.p, lda, mat, ll->dInfo.p, nb, s, ll->dScratch.p);
-      moe::launch_ll_terms_batch(ll->dA.p, lda, mat, N, ll->dOut.p, nb, s);
+      if (ll->objective == MOE_LL_LEAVE_ONE_OUT) {
+        // (the diagonal-block inverses in dLinv have served the factorisation: the full inverse factors take their place)
+        ll->dLoo.reserve(moe::loo_terms_work_doubles(N) * (size_t)B);
+        moe::launch_loo_terms_batch(ll->dA.p, lda, mat, N, ll->dLinv.p, lda, mat, ll->dLoo.p, ll->dInfo.p, ll->dOut.p, nb, s);
+      } else {
+        moe::launch_ll_terms_batch(ll->dA.p, lda, mat, N, ll->dOut.p, nb, s);
+      }
       ll->dOut.download(out.data(), (size_t)2 * nb, s);
       ll->dInfo.download(info.data(), nb, s);
       MOE_HIP_CHECK(hipStreamSynchronize(s));
@@ -1160,18 +1168,24 @@ void ll_evaluate_locked(moe_ll_t* ll, const double* hyperparameters_all, int num
   }
 }
 
+// The handle's GP factorised at one hyper-parameter set (MOE_ERR_SINGULAR if K + noise is singular).
+void ll_factor_locked(moe_ll_t* ll, const double* hyperparameters) {
+  const int g1 = 1 + ll->g;
+  std::vector<double> noise(g1);
+  for (int a = 0; a < g1; ++a) noise[a] = hyperparameters[1 + ll->d + a] + 1.0e-6;  // gpp_model_selection.cpp:546-549
+  if (!ll->gp)
+    ll->gp.reset(new moe::GpDev(hyperparameters, ll->cov_type, ll->X.data(), ll->y.data(), noise.data(),
+                                ll->derivs.empty() ? nullptr : ll->derivs.data(), ll->g, ll->d, ll->n, ll->device));
+  else
+    ll->gp->set_hyperparameters(hyperparameters, noise.data());
+}
+
 void ll_grad_locked(moe_ll_t* ll, const double* hyperparameters, double* grad) {
-  {
-    const int g1 = 1 + ll->g;
-    std::vector<double> noise(g1);
-    for (int a = 0; a < g1; ++a) noise[a] = hyperparameters[1 + ll->d + a] + 1.0e-6;  // gpp_model_selection.cpp:546-549
-    if (!ll->gp)
-      ll->gp.reset(new moe::GpDev(hyperparameters, ll->cov_type, ll->X.data(), ll->y.data(), noise.data(),
-                                  ll->derivs.empty() ? nullptr : ll->derivs.data(), ll->g, ll->d, ll->n, ll->device));
-    else
-      ll->gp->set_hyperparameters(hyperparameters, noise.data());
+  ll_factor_locked(ll, hyperparameters);
+  if (ll->objective == MOE_LL_LEAVE_ONE_OUT)
+    moe::grad_loo_log_likelihood(*ll->gp, grad);
+  else
     ll->gp->grad_log_marginal_likelihood(grad);
-  }
 }
 }  // namespace
 
@@ -1182,6 +1196,27 @@ int moe_ll_grad(moe_ll_t* ll, const double* hyperparameters, double* grad, moe_e
     require(ll != nullptr && hyperparameters != nullptr && grad != nullptr, "NULL argument");
     std::lock_guard<std::mutex> lk(ll->mu);
     ll_grad_locked(ll, hyperparameters, grad);
+  });
+}
+
+int moe_ll_set_objective(moe_ll_t* ll, int objective, moe_error_t* err) {
+  return guarded(err, [&] {
+    require(ll != nullptr, "NULL argument");
+    if (objective != MOE_LL_LOG_MARGINAL && objective != MOE_LL_LEAVE_ONE_OUT)
+      throw moe::Error(MOE_ERR_BOUNDS, "unknown log-likelihood objective", objective, MOE_LL_LOG_MARGINAL, MOE_LL_LEAVE_ONE_OUT);
+    std::lock_guard<std::mutex> lk(ll->mu);
+    ll->objective = objective;
+  });
+}
+
+int moe_ll_get_objective(const moe_ll_t* ll) { return ll != nullptr ? ll->objective : MOE_LL_LOG_MARGINAL; }
+
+int moe_ll_loo_predict(moe_ll_t* ll, const double* hyperparameters, double* mean_out, double* var_out, moe_error_t* err) {
+  return guarded(err, [&] {
+    require(ll != nullptr && hyperparameters != nullptr && mean_out != nullptr && var_out != nullptr, "NULL argument");
+    std::lock_guard<std::mutex> lk(ll->mu);
+    ll_factor_locked(ll, hyperparameters);
+    moe::loo_predict_on_device(*ll->gp, mean_out, var_out);
   });
 }
 
@@ -1288,6 +1323,8 @@ void ll_mcmc_locked(moe_ll_t* ll, const moe_prior_t* priors, int W, int T, doubl
   ll->dOut.reserve((size_t)2 * H);
   ll->dInfo.reserve(H);
   ll->dScratch.reserve(moe::chol_scratch_doubles(Np));
+  const bool loo = ll->objective == MOE_LL_LEAVE_ONE_OUT;
+  if (loo) ll->dLoo.reserve(moe::loo_terms_work_doubles(N) * (size_t)B);
   auto half_step = [&](int step, int half) {
     moe::launch_hmc_propose(st, step, half, s);
     for (int b0 = 0; b0 < H; b0 += B) {
@@ -1295,7 +1332,11 @@ void ll_mcmc_locked(moe_ll_t* ll, const moe_prior_t* priors, int W, int T, doubl
       moe::launch_hmc_cov_batch(st.dp, st.cps + b0, st.noise + (size_t)b0 * g1, ll->dX.p, n, dl, ll->dA.p, lda, mat, nb, one_level, s);
       moe::launch_ll_border(ll->dA.p, lda, mat, N, ll->dYc.p, nb, s);
       moe::launch_cholesky_batch(Np, ll->dA.p, lda, mat, ll->dLinv.p, lda, mat, ll->dInfo.p + b0, nb, s, ll->dScratch.p, one_level);
-      moe::launch_ll_terms_batch(ll->dA.p, lda, mat, N, ll->dOut.p + (size_t)2 * b0, nb, s);
+      if (loo)
+        moe::launch_loo_terms_batch(ll->dA.p, lda, mat, N, ll->dLinv.p, lda, mat, ll->dLoo.p, ll->dInfo.p + b0,
+                                    ll->dOut.p + (size_t)2 * b0, nb, s);
+      else
+        moe::launch_ll_terms_batch(ll->dA.p, lda, mat, N, ll->dOut.p + (size_t)2 * b0, nb, s);
     }
     moe::launch_hmc_accept(st, ll->dOut.p, ll->dInfo.p, N, step, half, s);
   };

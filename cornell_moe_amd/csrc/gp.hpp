@@ -61,6 +61,8 @@ struct GpDev {
   // marginal mean / std and LCB selection (lcb.hip): the call's doubles (results first: one copy back) and integers
   DevBuf<double> lcbD;
   DevBuf<int> lcbI;
+  // leave-one-out predictions and gradient (loo.hip): K^-1, the scaled columns B, M and the per-row vectors
+  DevBuf<double> looD;
   int num_cu = 256;
   // per-dimension mean and max |x - mean| of the training points (refreshed by rebuild() and by the append path of add_points):
   // the frame centre of the KG coordinate tables and the extent the kernel selection needs, so that an evaluation does not
@@ -197,6 +199,11 @@ void mean_std_on_device(GpDev& gp, const double* pts, int C, double* mean_out, d
 // points_out[q][d], mean_out[C], std_out[C], num_kept_out may be NULL.
 void lcb_select_on_device(GpDev& gp, const double* pts, int C, int q, int* index_out, double* points_out, double* mean_out,
                           double* std_out, int* num_kept_out);
+// loo.hip: leave-one-out cross-validation on the GP's current factorisation, every one of the N = n (1 + g) scalar observations left
+// out by itself.  mean_out / var_out [n][1 + g]: the LOO predictive mean (function values in the caller's units) and variance.
+void loo_predict_on_device(GpDev& gp, double* mean_out, double* var_out);
+// d L_LOO / d [alpha, lengths[d], noise variances[1 + g]], the conventions of GpDev::grad_log_marginal_likelihood.
+void grad_loo_log_likelihood(GpDev& gp, double* grad);
 // r6 (query_grad.hip): ComputeGradVarianceOfPoints / ComputeGradCholeskyVarianceOfPoints (gpp_math.cpp:1267-1474) for the first
 // `num_derivs` of the `num_pts` points, the m x m x d algebra on the device: out[num_derivs][d m m] in the reference's layout.
 void grad_variance_on_device(GpDev& gp, const double* pts, int num_pts, int num_derivs, bool cholesky, double* out);

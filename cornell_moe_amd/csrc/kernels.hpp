@@ -150,6 +150,15 @@ void launch_cholesky_batch(int N, double* A, long lda, long a_stride, double* Li
 // launch_ll_border writes that row; launch_ll_terms_batch returns out[b] = (sum log L_ii, |v|^2) over i, j < N.
 void launch_ll_border(double* A, long lda, long a_stride, int N, const double* yc, int batch, hipStream_t s);
 void launch_ll_terms_batch(const double* A, long lda, long a_stride, int N, double* out, int batch, hipStream_t s);
+// The leave-one-out objective's terms from the same bordered factors (loo.hip): X + b * x_stride (N x N, ldx; lower) receives
+// L_b^-1 of the leading N x N block, and out[b] = (-sum_i 1/2 log kappa_i, sum_i alpha_i^2 / kappa_i) with kappa = diag K^-1 (the
+// squared column norms of L^-1) and alpha = L^-T (row N of the factor) = K^-1 yc -- so that -1/2 out[1] - out[0] - 1/2 N log 2 pi,
+// the combination launch_ll_terms_batch's consumers form, is the LOO log pseudo-likelihood.  X may be the buffer that held the
+// factorisation's diagonal-block inverses.  info[b] != 0 (a failed pivot): the matrix is skipped and out[b] is meaningless.
+// work: batch * loo_terms_work_doubles(N) doubles.
+size_t loo_terms_work_doubles(int N);
+void launch_loo_terms_batch(const double* A, long lda, long a_stride, int N, double* X, long ldx, long x_stride, double* work,
+                            const int* info, double* out, int batch, hipStream_t s);
 
 // ---- the hyper-parameter ensemble sampler (moe_ll_mcmc; kernels in hyper_mcmc.hip, the loop in api.hip) ----
 // Everything a half-step's kernels read and write, all in device memory; H = W / 2 walkers move per half-step.

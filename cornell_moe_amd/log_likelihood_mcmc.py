@@ -152,7 +152,8 @@ class GaussianProcessLogLikelihoodMCMC(object):
     def _handle(self):
         if self._ll is None:
             X, y = self._data()
-            self._ll = api.LogLikelihood(X, y, self._derivatives, cov_type=self._cov_type, device=self._device)
+            self._ll = api.LogLikelihood(X, y, self._derivatives, cov_type=self._cov_type, device=self._device,
+                                         objective=int(self.objective_type))
         return self._ll
 
     def prior_table(self):

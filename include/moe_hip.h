@@ -501,6 +501,28 @@ int moe_ll_multistart(moe_ll_t* ll, const moe_gd_params_t* gd_params, const doub
  * or not it improved on the start. */
 int moe_ll_ascend(moe_ll_t* ll, const moe_gd_params_t* gd_params, const double* domain_log10, const double* x0, double* end_point,
                   moe_error_t* err);
+/* ---- the leave-one-out objective: LogLikelihoodTypes.leave_one_out_log_likelihood (GaussianProcessLeaveOneOutLogLikelihood,
+ * python/cpp_wrappers/log_likelihood.py:447; Rasmussen & Williams 5.4.2).  With K = K(X, X) + diag(noise + 1e-6), yc the values
+ * centred as for the marginal likelihood (the mean is NOT re-estimated per fold), alpha = K^-1 yc and kappa_i = (K^-1)_ii, each of the
+ * N = num_sampled (1 + g) scalar observations -- a function value or one observed partial derivative -- is left out by itself:
+ *   mu_i = yc_i - alpha_i / kappa_i,   var_i = 1 / kappa_i,
+ *   L_LOO(theta) = sum_i [ 1/2 log kappa_i - 1/2 alpha_i^2 / kappa_i - 1/2 log 2 pi ].
+ * A handle has an objective, MOE_LL_LOG_MARGINAL (0, what it starts with) or MOE_LL_LEAVE_ONE_OUT (1) -- the values of the
+ * reference's LogLikelihoodTypes -- which selects what moe_ll_evaluate, moe_ll_grad, moe_ll_ascend, moe_ll_multistart and moe_ll_mcmc
+ * compute; everything else about those calls (layouts, the 1e-6, -infinity on a failed pivot, MOE_ERR_SINGULAR from the gradient) is
+ * as documented with them.  moe_ll_set_objective: MOE_ERR_BOUNDS for any other value.
+ * Gradient under MOE_LL_LEAVE_ONE_OUT: with c_i = alpha_i / kappa_i, e_i = 1/2 (1 + alpha_i^2 / kappa_i) / kappa_i, u = K^-1 c and
+ * M = K^-1 diag(e) K^-1,  d L_LOO / d theta = sum_ab (u_a alpha_b - M_ab) (dK / d theta)_ab, with moe_ll_grad's convention for
+ * dK / d (alpha, lengths) (only the function-value block depends on them) and its restriction (derivative observations: Matern-5/2
+ * only, MOE_ERR_INVALID_VALUE otherwise).  The value and the predictions are provided for both kernels at every g. */
+#define MOE_LL_LOG_MARGINAL 0
+#define MOE_LL_LEAVE_ONE_OUT 1
+int moe_ll_set_objective(moe_ll_t* ll, int objective, moe_error_t* err);
+int moe_ll_get_objective(const moe_ll_t* ll);
+/* mean_out / var_out [num_sampled][1 + g]: the LOO predictive mean and variance of every observation at ONE hyper-parameter set,
+ * whatever the handle's objective (which the call does not change).  The means of function values are in the caller's units (the
+ * centring mean added back); those of derivative observations need none.  A singular K + noise is MOE_ERR_SINGULAR. */
+int moe_ll_loo_predict(moe_ll_t* ll, const double* hyperparameters, double* mean_out, double* var_out, moe_error_t* err);
 
 /* ---- hyper-parameter sampling: GaussianProcessLogLikelihoodMCMC.train() (python/cpp_wrappers/log_likelihood_mcmc.py:170-239),
  * which hands its log posterior to emcee.EnsembleSampler.  moe_ll_mcmc is that sampler -- the affine-invariant ensemble sampler with
