@@ -48,6 +48,7 @@ struct GpDev {
   PinnedBuf<double> hYc;  // y - mean on its way to the device, and the factorisation's status word on its way back
   // reusable workspaces of the KG evaluator (kg.hip)
   DevBuf<double> kBlob, kNormals, kTab, kBestPoint, kBestValue, kBeta, kT, kC, kTB, kOut, kSW, kSWpart, kZcPart, kV;
+  DevBuf<double> kStartTab;  // the start table of the line searches, [E][A][1 + m][dp + 1] (kg.hip: kg_start_table_kernel)
   DevBuf<unsigned long long> kCounters;
   DevBuf<unsigned int> kEiTicket;  // arrival counters of ei_mc_kernel's fused final sum (ei.hip)
   bool ei_ticket_dirty = false;  // a launch of ei_mc_kernel was enqueued and its completion not yet seen: an aborted launch leaves
@@ -73,7 +74,8 @@ struct GpDev {
   double last_ms[5] = {0, 0, 0, 0, 0};
   // which MC kernel the last KG launch took (moe_last_kernel_info): variant (0 wave-per-sample, 1 workgroup-per-sample) |
   // coordinate table in LDS | wavefronts per workgroup | register tiles per wavefront (variant 1) | streamed per-sample weight
-  // table | T-free gradient tail | workgroups | sample pre-pass
+  // table | T-free gradient tail | workgroups | sample pre-pass; bits 1 .. 4 of the second word: far frame | wide frame | lane-parked
+  // kernel | the line searches took their first gradient from the start table
   int last_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
   GpDev(const double* hyper, int cov_type, const double* X_in, const double* y_in, const double* noise_in,

@@ -1089,6 +1089,141 @@ __global__ __launch_bounds__(64) void kg_sample_prep_generic_kernel(KgMcParams P
   kg_sample_prep_generic_kernel_body::run(MOE_VBLOCK, MOE_VGRID, nullptr, P, best_j);
 }
 
+// The START TABLE of an evaluation without derivative observations (mc::start_from_table, kg_mc.hpp): for every discretised point x_c
+// -- where the line searches start -- the coefficients of [1 ; beta] in f = -mu_after(x_c) and in its frame gradient:
+//   column 0:      -(mean + sum_j alpha KinvY_j b_j)              | -sum_j alpha KinvY_j b'_j (x_j - x_c)_k
+//   column 1 + l:  -(alpha b_{n+l} - sum_j alpha W_jl b_j)        | the same with b' (x - x_c)_k
+// (b, b' = radial3's base and first-derivative coefficient of |x_j - x_c|^2, j over the training points, n + l = fantasy point l): the
+// sums of a value + gradient pass (grad_pass_parked) with the sample's weights alpha (KinvY - W beta | beta) taken apart by beta's
+// components.  The kernel reads what the pass reads -- the frame table XsTab, KinvY, W -- through radial3, so an entry differs from
+// the pass's sum by the order of additions alone.
+// One WAVEFRONT per (discretised point, group of kStartCols<DP> columns, evaluation): every lane walks the tiles in order (one fma
+// chain per sum), then the fixed butterfly -- the order depends on n + u and DP alone, never on the batch or the ensemble.  A group's
+// columns share the radial terms, and at m <= 4 (q-KG up to four points; DP <= 8) one group is all there is.
+template <int DP>
+constexpr int kStartCols = DP <= 8 ? 5 : (DP <= 12 ? 3 : 2);
+
+template <int DP, int COV>
+__device__ __forceinline__ void start_table_sums(const KgMcParams& P, const double* __restrict__ xg, const double* __restrict__ We,
+                                                 const double* __restrict__ etab, const double (&xq)[DP], int col0, int lane,
+                                                 double* __restrict__ out) {
+  constexpr int CG = kStartCols<DP>;
+  const int n = P.n, u = P.u, m = P.m, ntiles = P.ntiles;
+  double accf[CG], accg[CG][DP];
+#pragma unroll
+  for (int i = 0; i < CG; ++i) {
+    accf[i] = 0.0;
+#pragma unroll
+    for (int k = 0; k < DP; ++k) accg[i][k] = 0.0;
+  }
+  // column col0 + i reads W's column col0 + i - 1 (clamped: a column beyond m, or column 0 here, is masked below)
+  long wcol[CG];
+#pragma unroll
+  for (int i = 0; i < CG; ++i) wcol[i] = (long)min(max(col0 + i - 1, 0), m - 1) * P.N;
+  for (int t0 = 0; t0 < ntiles; t0 += 2) {
+    // the loads of two tiles in one batch (clamped addresses: always valid)
+    double cx[2][DP], wv[2][CG];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int t = min(t0 + h, ntiles - 1);
+      const long row = min(t * 64 + lane, n - 1);
+#pragma unroll
+      for (int k = 0; k < DP; ++k) cx[h][k] = xg[((long)t * DP + k) * 64 + lane];
+#pragma unroll
+      for (int i = 0; i < CG; ++i) wv[h][i] = (col0 + i == 0) ? P.KinvY[row] : -We[row + wcol[i]];
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int t = t0 + h;
+      if (t < ntiles) {
+        const int j = t * 64 + lane;
+        double diff[DP];
+        double r2 = 1.0e-300;
+#pragma unroll
+        for (int k = 0; k < DP; ++k) {
+          diff[k] = cx[h][k] - xq[k];
+          r2 = fma(diff[k], diff[k], r2);
+        }
+        double base, first, second;
+        mc::radial3<COV, true, false>(r2, etab, base, first, second);
+#pragma unroll
+        for (int i = 0; i < CG; ++i) {
+          const int col = col0 + i;
+          double w = wv[h][i];
+          if (j >= n) w = (col >= 1 && j - n == col - 1 && j < n + u) ? 1.0 : 0.0;  // fantasy point l carries beta_l; padding nothing
+          if (col > m) w = 0.0;
+          w *= P.alpha;
+          accf[i] = fma(w, base, accf[i]);
+          const double coef = w * first;
+#pragma unroll
+          for (int k = 0; k < DP; ++k) accg[i][k] = fma(coef, diff[k], accg[i][k]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < CG; ++i) {
+    const int col = col0 + i;
+    const double f = mc::wave_sum_uniform(accf[i]);
+    double v = -((col == 0 ? P.mean : 0.0) + f);  // entry DP: the value
+#pragma unroll
+    for (int k = 0; k < DP; ++k) {
+      const double gk = mc::wave_sum_uniform(accg[i][k]);
+      v = (lane == k) ? -gk : v;
+    }
+    if (col <= m && lane <= DP) out[(long)col * (DP + 1) + lane] = v;
+  }
+}
+
+template <int DP>
+struct kg_start_table_kernel_body {
+  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, const KgMcParams& P, double* __restrict__ tab) {
+    __shared__ double etab[kExpTabLen];
+    const int lane = threadIdx.x;
+    const int c = blockIdx.x, col0 = blockIdx.y * kStartCols<DP>, e = blockIdx.z;
+    const int size = P.dim - P.f;
+    etab[lane] = kExp2Tab64[lane];  // (kExpTabLen == 64 == the workgroup)
+    __syncthreads();
+    const double* rec = P.blob + (long)e * P.rec.stride;
+    // the discretised point in the frame, as the line searches enter it: its coordinates on the optimised rows, 1 on fidelity rows,
+    // 0 on pads (.cpp:353-357)
+    double xq[DP];
+#pragma unroll
+    for (int k = 0; k < DP; ++k) {
+      const int pk = P.perm[k];
+      const double xo = (pk < size) ? rec[P.rec.disc + c * size + min(pk, size - 1)] : ((pk < P.dim) ? 1.0 : 0.0);
+      xq[k] = (xo - P.center[k]) * P.inv_lp[k];
+    }
+    const double* xg = P.XsTab + (long)e * P.tab_stride;
+    const double* We = P.W + (long)e * P.w_stride;
+    double* out = tab + (long)e * P.start_stride + (long)c * (1 + P.m) * (DP + 1);
+    if (P.cov_type == MOE_COV_SQUARE_EXPONENTIAL)
+      start_table_sums<DP, MOE_COV_SQUARE_EXPONENTIAL>(P, xg, We, etab, xq, col0, lane, out);
+    else
+      start_table_sums<DP, MOE_COV_MATERN_NU_2P5>(P, xg, We, etab, xq, col0, lane, out);
+  }
+};
+template <int DP>
+__global__ __launch_bounds__(64) void kg_start_table_kernel(KgMcParams P, double* __restrict__ tab) {
+  kg_start_table_kernel_body<DP>::run(MOE_VBLOCK, MOE_VGRID, nullptr, P, tab);
+}
+
+template <int DP>
+void launch_start_table_dp(const KgMcParams& P, double* tab, hipStream_t s) {
+  const dim3 grid((unsigned)P.A, (unsigned)((1 + P.m + kStartCols<DP> - 1) / kStartCols<DP>), (unsigned)P.E);
+  launch_kernel_ens<kg_start_table_kernel_body<DP>, 64>(kg_start_table_kernel<DP>, grid, dim3(64), 0, s, P, tab);
+  MOE_HIP_CHECK(hipGetLastError());
+}
+void launch_start_table(const KgMcParams& P, int dp, double* tab, hipStream_t s) {
+  switch (dp) {
+    case 4: launch_start_table_dp<4>(P, tab, s); break;
+    case 8: launch_start_table_dp<8>(P, tab, s); break;
+    case 12: launch_start_table_dp<12>(P, tab, s); break;
+    case 16: launch_start_table_dp<16>(P, tab, s); break;
+    default: throw Error(MOE_ERR_RUNTIME, "the start table is built for padded dimensions up to 16");
+  }
+}
+
 // Per-sample weights of the training rows for every sample, V[(e, sl)][r] = scale_a (KinvY[r] - sum_c W_e[r, c] beta[(e, sl), c])
 // (r = (j, a); scale_0 = alpha, scale_a = -alpha / l_{d_a}): what point_weights computes inside the MC kernel, same
 // operation order, hence the same bits.  Inside the workgroup-per-sample kernel that computation reads all of W_e
@@ -1334,6 +1469,7 @@ struct McPlan {
   int rec_head = 0;           // doubles of the record head [L | mu_disc | C_disc | disc] (the lane-parked kernel's LDS copy)
   int multi_trial = 0;        // KgMcParams::multi_trial
   bool prep = false;          // the sample pre-pass runs (beta, best_j)
+  bool start_table = false;   // the line searches take their first gradient from the start table (kg_start_table_kernel)
   bool weight_table = false;  // the per-sample weight table is built
   long v_stride = 0;          // its doubles per sample, and its slots per point
   int v_slots1 = 0;
@@ -1586,6 +1722,9 @@ McPlan plan_mc(const GpDev& gp, const KgDims& k, const double* bounds, const dou
   if (variant == 2 && !(pl.weight_table && pl.prep))
     throw Error(MOE_ERR_RUNTIME, "streamed-weights MC kernel selected without its weight table");
   pl.chunk_len = tail_chunk_len(pl.fused_tail, m);
+  // the start table: the LDS-table wave-per-sample kernels (lane-parked and frame line search) without derivative observations -- decided
+  // by the evaluation's shape alone, like the kernel itself
+  pl.start_table = variant == 0 && xlds && g == 0 && G == 0;
   return pl;
 }
 
@@ -1747,7 +1886,7 @@ KgStateParams launch_state_algebra(GpDev& gp, const KgDims& k, const KgStateEnqu
 // The MC step: its parameters, the sample pre-pass and the weight table where the plan has them, the MC kernel.
 KgMcParams launch_mc_step(GpDev& gp, const KgDims& k, const McPlan& pl, const moe_gd_params_t& gd, const TabParams& tp,
                           const KgRecords& R, double* dBlobP, const double* dNormalsP, const BatchLayout& bl, long tab_stride,
-                          size_t n_ctr, EventTimer& t_mc, hipStream_t s) {
+                          size_t n_ctr, EventTimer& t_state, EventTimer& t_mc, hipStream_t s) {
   const int E = k.E, N = k.N, m = k.m, dp = k.dp, num_local = k.num_local;
   KgMcParams mp;
   mp.cov_type = gp.cp.type;
@@ -1801,9 +1940,21 @@ KgMcParams launch_mc_step(GpDev& gp, const KgDims& k, const McPlan& pl, const mo
   mp.counters = gp.kCounters.p;
   mp.next_sample = reinterpret_cast<unsigned int*>(gp.kCounters.p + (((size_t)2 * E + 15) / 16) * 16);  // 128-byte aligned
   mp.prof = gp.kCounters.p + n_ctr - 16;
-  t_mc.start(s);
   mp.best_j = nullptr;
   mp.V = nullptr;
+  mp.v_stride = pl.v_stride;
+  mp.v_slots1 = pl.v_slots1;
+  mp.start_tab = nullptr;
+  mp.start_stride = 0;
+  if (pl.start_table) {  // the last kernel of the state phase: it reads the coordinate tables, K^-1 y, W and the records' discretised set
+    mp.start_stride = (long)k.A * (1 + m) * (dp + 1);
+    gp.kStartTab.reserve((size_t)mp.start_stride * E);
+    double* start_tab_p = gp.kStartTab.p;
+    launch_start_table(mp, dp, start_tab_p, s);
+    mp.start_tab = start_tab_p;
+  }
+  t_state.stop(s);
+  t_mc.start(s);
   const long total = (long)E * num_local;
   if (pl.prep) {
     gp.kBestJ.reserve((size_t)total);
@@ -1817,8 +1968,6 @@ KgMcParams launch_mc_step(GpDev& gp, const KgDims& k, const McPlan& pl, const mo
     }
     MOE_HIP_CHECK(hipGetLastError());
   }
-  mp.v_stride = pl.v_stride;
-  mp.v_slots1 = pl.v_slots1;
   if (pl.weight_table) {  // (m > 64: the table kernel takes the columns of W 64 at a time, r4)
     gp.kV.reserve((size_t)mp.v_stride * (size_t)total + (size_t)64 * mp.v_slots1);  // (+ one tile: the sweeps prefetch one tile ahead)
     memset_async(gp.kBeta.p + (size_t)total * m, 0, sizeof(double) * 64, s);
@@ -2148,15 +2297,15 @@ KgPending kg_launch(GpDev& gp, int num_fidelity, const moe_gd_params_t& gd, cons
                                                      pl.pair_rows, dCtrP, (long)n_ctr);
     MOE_HIP_CHECK(hipGetLastError());
   }
-  t_state.stop(s);
 
-  // ---- 2. MC kernel ----
-  const KgMcParams mp = launch_mc_step(gp, k, pl, gd, tp, R, dBlobP, dNormalsP, se.bl, tab_stride, n_ctr, t_mc, s);
+  // ---- 2. MC kernel (the start table in front of it closes the state phase) ----
+  const KgMcParams mp = launch_mc_step(gp, k, pl, gd, tp, R, dBlobP, dNormalsP, se.bl, tab_stride, n_ctr, t_state, t_mc, s);
   {
     // (bits 1 / 2 of the second word, r4: the frame-extent decisions -- a domain box or point set wider than 100 length scales
     //  silently costs the LDS-table kernel and the multi-trial passes; this is where a caller can see it)
     const int info[8] = {pl.variant,
-                         ((pl.variant == 0 && pl.xlds) ? 1 : 0) | (pl.far_frame ? 2 : 0) | (pl.wide_frame ? 4 : 0) | (pl.lane_kernel ? 8 : 0),
+                         ((pl.variant == 0 && pl.xlds) ? 1 : 0) | (pl.far_frame ? 2 : 0) | (pl.wide_frame ? 4 : 0) | (pl.lane_kernel ? 8 : 0) |
+                             (pl.start_table ? 16 : 0),
                          pl.waves, pl.variant == 1 ? pl.tr : pl.wide_lds_tiles, pl.weight_table ? 1 : 0, pl.fused_tail ? 1 : 0, pl.blocks,
                          pl.prep ? 1 : 0};
     std::copy(info, info + 8, gp.last_info);

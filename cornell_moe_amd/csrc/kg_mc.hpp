@@ -99,6 +99,8 @@ struct KgMcParams {
                                  // more derivative slots than the GP observes (g = 5 .. 7 -> 8, 9 .. 11 -> 12: the extra slots hold 0)
   const int* best_j;             // [E][num_local] start point of every sample's line search, precomputed with beta by
                                  // kg_sample_prep_kernel (kg.hip); NULL = each sample computes them itself
+  const double* start_tab;       // [E][A][1 + m][DP + 1] the start table (kg_start_table_kernel, kg.hip; mc::start_from_table), or NULL:
+  long start_stride;             // f and grad f at the discretised points as (1 + m)-term dot products with [1 ; beta]
 };
 
 // Launchers (one translation unit per padded dimension).  `waves` = wavefronts per workgroup, `shm` = dynamic LDS bytes.
@@ -274,6 +276,32 @@ __device__ __forceinline__ double uniform(double v) {
   const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
   const int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
   return __hiloint2double(hi, lo);
+}
+
+// The first gradient of a sample's line search from the evaluation's START TABLE (kg_start_table_kernel, kg.hip).  A line search
+// starts at a discretised point x_c, and mu_after,i(x) = mu_n(x) + cov_n(Xu, x)^T beta_i is linear in the sample's beta: f = -mu_after
+// and its frame gradient at x_c are (1 + m)-term dot products whose coefficients depend on the evaluation alone.  `row` = the table
+// row of x_c, [1 + m][DP + 1] doubles: column 0 the mu_n part, column 1 + l the coefficient of beta_l; entry k < DP the frame gradient's
+// row k, entry DP the value -- signs and alpha folded so that the sums ARE what a value + gradient pass at x_c returns.  `beta` = the
+// wave's copy of beta (0 beyond m).  Lane k <= DP returns entry k (lanes beyond DP repeat entry DP): ascending l, one fma each --
+// the one operation order of every kernel that takes the table (lane-parked and frame line search: same bits).
+template <int DP>
+__device__ __forceinline__ double start_from_table(const double* __restrict__ row,
+                                                   const volatile __attribute__((address_space(3))) double* beta, int m, int lane) {
+  constexpr int RS = DP + 1;
+  const double* p = row + min(lane, DP);
+  double v = p[0];
+  for (int c0 = 0; c0 < m; c0 += 4) {  // four columns requested together (column index clamped to m - 1; beta is 0 beyond m)
+    const double t0 = p[(1 + c0) * RS];
+    const double t1 = p[(1 + min(c0 + 1, m - 1)) * RS];
+    const double t2 = p[(1 + min(c0 + 2, m - 1)) * RS];
+    const double t3 = p[(1 + min(c0 + 3, m - 1)) * RS];
+    v = fma(t0, beta[c0], v);
+    v = fma(t1, beta[min(c0 + 1, kMaxM - 1)], v);
+    v = fma(t2, beta[min(c0 + 2, kMaxM - 1)], v);
+    v = fma(t3, beta[min(c0 + 3, kMaxM - 1)], v);
+  }
+  return v;
 }
 
 // A coordinate in the frame of the tables: centred, then scaled.
@@ -1039,7 +1067,7 @@ __device__ __forceinline__ void fill_frame_constants(const KgMcParams& P, double
 template <int DP, int G, class EV>
 __device__ __forceinline__ double line_search_frame(const KgMcParams& P, const double* __restrict__ cst, double* __restrict__ scr,
                                                     EV& ev, double (&x)[DP], unsigned long long& n_val,
-                                                    unsigned long long& n_grad) {
+                                                    unsigned long long& n_grad, const double* __restrict__ start_row = nullptr) {
   typedef const volatile __attribute__((address_space(3))) double* cst_ptr;  // (volatile: read where used, never hoisted)
   cst_ptr C = (cst_ptr)cst;
   const int lane_id = (int)(threadIdx.x & 63u);
@@ -1097,6 +1125,12 @@ __device__ __forceinline__ double line_search_frame(const KgMcParams& P, const d
       if (have_g) {
         f0 = f_carried;
         have_g = false;
+      } else if (G == 0 && start_row != nullptr && restart == 0 && istep == 0) {
+        // the sample's first gradient, at its discretised point: from the start table (beta still sits behind the rows of `scr`)
+        const double v = start_from_table<DP>(start_row, S + kMaxM, P.m, lane_id);
+        f0 = lane_value(v, DP);
+#pragma unroll
+        for (int k = 0; k < DP; ++k) gf[k] = lane_value(v, k);
       } else {
         f0 = ev.eval_grad_frame(xf, gf);
       }
@@ -2007,7 +2041,10 @@ __device__ __forceinline__ void kg_sample(const KgMcParams& P, int e, int sl, co
     fcur = line_search_lds<DP, G>(P, ev, st, x, n_val, n_grad);
   } else {
     WaveEval<DP, G, SMALL, XL> ev{xs, aw, etab, P.ntiles, P.cov_type, P.mean, P.inv_lp, lane, zb + DP};
-    fcur = line_search_frame<DP, G>(P, cst, zb, ev, x, n_val, n_grad);  // (z / beta scratch is idle by now)
+    // (z / beta scratch is idle by now -- but for beta, which the start table's row is multiplied with before the first pass)
+    const double* start_row =
+        (G == 0 && XL && P.start_tab != nullptr) ? P.start_tab + (long)e * P.start_stride + (long)best_j * (1 + m) * (DP + 1) : nullptr;
+    fcur = line_search_frame<DP, G>(P, cst, zb, ev, x, n_val, n_grad, start_row);
 #if MOE_BLOCK_PROF
     {
       const unsigned long long w4 = __builtin_amdgcn_s_memtime();

@@ -309,6 +309,8 @@ __device__ __forceinline__ void kg_sample_lane(const KgMcParams& P, int e, int s
     // rows of the wave's scratch (z / beta are spent): three broadcast rows of kMaxLaneDP + 1, the gradient sums and their dump area
     lds_rw_ptr R0 = Z, R2 = Z + (kMaxLaneDP + 1), R3 = Z + 2 * (kMaxLaneDP + 1), R1 = Z + 3 * (kMaxLaneDP + 1);
     static_assert(3 * (kMaxLaneDP + 1) + 2 * kMaxLaneDP + 4 <= 2 * kMaxM, "line-search rows exceed the wave's scratch");
+    const double* start_row =
+        (G == 0 && P.start_tab != nullptr) ? P.start_tab + (long)e * P.start_stride + (long)best_j * (1 + m) * (DP + 1) : nullptr;
     double xf_l = (xo_l - c_l) * s_l;  // the iterate in the frame: it only feeds the evaluator (see line_search_frame)
     double gf_l = 0.0;
     bool have_g = false;  // a clamped step's f(x + step) and the next iteration's gradient are ONE pass, carried over
@@ -323,6 +325,10 @@ __device__ __forceinline__ void kg_sample_lane(const KgMcParams& P, int e, int s
           f0 = f_carried;
           gf_l = g_carried_l;
           have_g = false;
+        } else if (G == 0 && start_row != nullptr && restart == 0 && istep == 0) {
+          // the sample's first gradient, at its discretised point: from the start table (no pass has touched beta's row yet)
+          gf_l = start_from_table<DP>(start_row, Z + kMaxM, m, lane);
+          f0 = lane_value(gf_l, DP);
         } else {
           double xq[DP];
           lane_broadcast<DP>(xf_l, R0, lane, xq);
