@@ -526,6 +526,48 @@ class GaussianProcessMCMC(object):
     num_sampled = property(lambda self: self._dev.n)
 
 
+# ---- the ensemble-averaged posterior mean and the recommendation step (not in the reference's GPP: there PosteriorMeanMCMC loops
+# over compute_posterior_mean member by member and the descent runs in Python, examples/main.py:243-260) ----
+def compute_posterior_mean_mcmc(gaussian_process_mcmc, num_fidelity, points_to_sample):
+    """-(mean over the ensemble of the posterior mean) at one point [dim - num_fidelity], fidelity coordinates pinned to 1
+    (moe_posterior_mean_mcmc_batch; not in the reference): what PosteriorMeanMCMC.compute_posterior_mean_mcmc sums up from
+    num_mcmc compute_posterior_mean calls, in one device call."""
+    gp = gaussian_process_mcmc
+    return float(_api.posterior_mean_mcmc(gp._dev, _flat(points_to_sample, gp.dim - num_fidelity), int(num_fidelity))[0])
+
+
+def compute_grad_posterior_mean_mcmc(gaussian_process_mcmc, num_fidelity, points_to_sample):
+    """The gradient of compute_posterior_mean_mcmc over the dim - num_fidelity free coordinates, as a flat list (not in the
+    reference)."""
+    gp = gaussian_process_mcmc
+    return list(_api.posterior_mean_mcmc(gp._dev, _flat(points_to_sample, gp.dim - num_fidelity), int(num_fidelity),
+                                         want_grad=True)[1].ravel())
+
+
+def evaluate_posterior_mean_mcmc_at_point_list(gaussian_process_mcmc, num_fidelity, points, num_points):
+    """compute_posterior_mean_mcmc at num_points points (flat [num_points][dim - num_fidelity]) in one device call: the flat list
+    of the values (not in the reference; its examples loop over the points)."""
+    gp = gaussian_process_mcmc
+    size = gp.dim - int(num_fidelity)
+    pts = _flat(points, size * num_points).reshape(num_points, size)
+    return list(_api.posterior_mean_mcmc(gp._dev, pts, int(num_fidelity)))
+
+
+def posterior_mean_mcmc_optimization(gaussian_process_mcmc, num_fidelity, optimizer_parameters, domain_bounds, candidates,
+                                     num_candidates, num_starts=1):
+    """The recommendation step of examples/main.py:243-260 on the device (moe_posterior_mean_mcmc_recommend; not in the reference):
+    screen the candidates (flat [num_candidates][dim - num_fidelity]) on the averaged posterior mean, run the reference's Python
+    gradient descent from the num_starts best, keep the screened candidate unless the descent did at least as well.  Returns the
+    flat list of the point's dim - num_fidelity free coordinates.  Only tensor-product domains (BoundsException otherwise)."""
+    gp = gaussian_process_mcmc
+    size = gp.dim - int(num_fidelity)
+    cand = _flat(candidates, size * num_candidates).reshape(num_candidates, size)
+    gd = tuple(_gd_params(optimizer_parameters)) + (int(getattr(optimizer_parameters, "domain_type", 0)),)
+    res = _api.recommend(gp._dev, cand, gd, _flat(domain_bounds, 2 * size),
+                         num_fidelity=int(num_fidelity), num_starts=int(num_starts))
+    return list(res["point"])
+
+
 def _kg_mcmc(gp_mcmc, num_fidelity, optimizer_parameters, domain_bounds, discrete_pts, points_to_sample, points_being_sampled,
              num_pts, num_to_sample, num_being_sampled, max_int_steps, best_so_far, randomness_source, want_grad):
     gp = gp_mcmc

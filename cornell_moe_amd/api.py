@@ -763,6 +763,63 @@ class DeviceGPMCMC(object):
         return out.reshape(q, self.d), val.value, bool(found.value)
 
 
+def _ensemble_handles(gps):
+    """(ctypes array of handles, count, dim) of an MCMC ensemble: a DeviceGPMCMC or a sequence of DeviceGP over the same data."""
+    members = list(gps.gps) if isinstance(gps, DeviceGPMCMC) else list(gps)
+    arr = (C.c_void_p * max(len(members), 1))(*[g._h.value for g in members])
+    return arr, len(members), (members[0].d if members else 0), members
+
+
+def posterior_mean_mcmc(gps, points, num_fidelity=0, want_grad=False):
+    """moe_posterior_mean_mcmc_batch: f = -(mean over the members of the posterior mean), fidelity coordinates pinned to 1, at
+    points [P][dim - num_fidelity] in one device call.  Returns value [P], with want_grad (value, grad [P][dim - num_fidelity])."""
+    arr, E, d, keep = _ensemble_handles(gps)
+    size = d - int(num_fidelity)
+    if E > 0 and not 0 < size <= d:
+        raise BoundsException("num_fidelity out of range", num_fidelity, 0, d - 1)
+    points, pp = _d(points)
+    P = points.reshape(-1, max(size, 1)).shape[0]
+    value = np.zeros(P)
+    grad = np.zeros((P, max(size, 1))) if want_grad else None
+    err = _lib.MoeError()
+    _check(_lib.load().moe_posterior_mean_mcmc_batch(arr, E, int(num_fidelity), pp, P, value.ctypes.data_as(dp),
+                                                     grad.ctypes.data_as(dp) if want_grad else None, C.byref(err)), err)
+    return (value, grad) if want_grad else value
+
+
+def recommend(gps, candidates, gd_params, domain_bounds, num_fidelity=0, num_starts=1, want_values=False, want_path=False):
+    """moe_posterior_mean_mcmc_recommend: screen the candidates [C][dim - num_fidelity] on the ensemble-averaged posterior mean,
+    descend from the num_starts best (the reference's Python gradient descent, on the device), keep the screened candidate unless
+    the descent did at least as well.  Returns a dict: point [size], value, screened_index, refined, end_points [num_starts][size],
+    and with want_values candidate_values [C], with want_path path [num_starts][max_num_steps + 1][size]."""
+    arr, E, d, keep = _ensemble_handles(gps)
+    size = d - int(num_fidelity)
+    if E > 0 and not 0 < size <= d:
+        raise BoundsException("num_fidelity out of range", num_fidelity, 0, d - 1)
+    g = DeviceGP._gd(gd_params)
+    cand, cp = _d(candidates)
+    C_ = cand.reshape(-1, max(size, 1)).shape[0]
+    bounds, bp = _d(domain_bounds)
+    S = int(num_starts)
+    point = np.zeros(max(size, 1))
+    ends = np.zeros((max(S, 1), max(size, 1)))
+    values = np.zeros(C_) if want_values else None
+    path = np.zeros((max(S, 1), max(g.max_num_steps, 0) + 1, max(size, 1))) if want_path else None
+    value, index, refined = C.c_double(0.0), C.c_int(0), C.c_int(0)
+    err = _lib.MoeError()
+    _check(_lib.load().moe_posterior_mean_mcmc_recommend(arr, E, int(num_fidelity), C.byref(g), bp, cp, C_, S,
+                                                         point.ctypes.data_as(dp), C.byref(value), C.byref(index), C.byref(refined),
+                                                         values.ctypes.data_as(dp) if want_values else None,
+                                                         ends.ctypes.data_as(dp), path.ctypes.data_as(dp) if want_path else None,
+                                                         C.byref(err)), err)
+    out = dict(point=point, value=value.value, screened_index=index.value, refined=bool(refined.value), end_points=ends)
+    if want_values:
+        out["candidate_values"] = values
+    if want_path:
+        out["path"] = path
+    return out
+
+
 def kg_multistart_multi(gps, outer_params, inner_params, bounds, discrete, starts, Xp, num_mc, best_so_far, normals,
                         gradient_ascent=True, num_fidelity=0):
     """moe_kg_multistart_multi (r5): the outer optimiser with its restarts dealt to `gps` -- DeviceGP objects holding the same GP on

@@ -755,6 +755,42 @@ int moe_kg_mcmc_batch(const moe_gp_t* const* gps, int num_mcmc, int num_fidelity
   });
 }
 
+int moe_posterior_mean_mcmc_batch(const moe_gp_t* const* gps, int num_mcmc, int num_fidelity, const double* points, int num_points,
+                                  double* value_out, double* grad_out, moe_error_t* err) {
+  return guarded(err, [&] {
+    require(gps != nullptr, "gps is NULL");
+    if (num_mcmc < 1) throw moe::Error(MOE_ERR_BOUNDS, "num_mcmc must be positive", num_mcmc, 1, 1e9);
+    require(points != nullptr, "NULL argument");
+    if (num_points < 1) throw moe::Error(MOE_ERR_BOUNDS, "the number of points must be positive", num_points, 1, 1e9);
+    if (num_fidelity < 0) throw moe::Error(MOE_ERR_BOUNDS, "num_fidelity out of range", num_fidelity, 0, moe::kMaxDimPadded - 1);
+    const auto locks = lock_ensemble(gps, num_mcmc);
+    const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
+    moe::posterior_mean_mcmc_batch(v, num_fidelity, points, num_points, value_out, grad_out);
+  });
+}
+
+int moe_posterior_mean_mcmc_recommend(const moe_gp_t* const* gps, int num_mcmc, int num_fidelity, const moe_gd_params_t* gd,
+                                      const double* domain_bounds, const double* candidates, int num_candidates, int num_starts,
+                                      double* point_out, double* value_out, int* screened_index_out, int* refined_out,
+                                      double* candidate_values_out, double* end_points_out, double* path_out, moe_error_t* err) {
+  return guarded(err, [&] {
+    require(gps != nullptr, "gps is NULL");
+    if (num_mcmc < 1) throw moe::Error(MOE_ERR_BOUNDS, "num_mcmc must be positive", num_mcmc, 1, 1e9);
+    require(gd && domain_bounds && candidates && point_out, "NULL argument");
+    if (num_candidates < 1) throw moe::Error(MOE_ERR_BOUNDS, "the number of candidates must be positive", num_candidates, 1, 1e9);
+    if (num_starts < 1 || num_starts > num_candidates)
+      throw moe::Error(MOE_ERR_BOUNDS, "num_starts out of range", num_starts, 1, num_candidates);
+    if (gd->max_num_steps < 1) throw moe::Error(MOE_ERR_BOUNDS, "max_num_steps must be positive", gd->max_num_steps, 1, 1e9);
+    if (gd->domain_type != MOE_DOMAIN_TENSOR_PRODUCT)
+      throw moe::Error(MOE_ERR_BOUNDS, "the recommendation supports tensor-product domains only", gd->domain_type, 0, 0);
+    if (num_fidelity < 0) throw moe::Error(MOE_ERR_BOUNDS, "num_fidelity out of range", num_fidelity, 0, moe::kMaxDimPadded - 1);
+    const auto locks = lock_ensemble(gps, num_mcmc);
+    const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
+    moe::posterior_mean_mcmc_recommend(v, num_fidelity, *gd, domain_bounds, candidates, num_candidates, num_starts, point_out,
+                                       value_out, screened_index_out, refined_out, candidate_values_out, end_points_out, path_out);
+  });
+}
+
 int moe_kg_mcmc_finalize(double* kg, double* grad_kg, const double* points_to_sample_all, int num_evals, int num_to_sample,
                          int dim, int num_fidelity, int total_num_mcmc) {
   if (!kg || !points_to_sample_all || num_evals <= 0 || num_to_sample <= 0 || dim <= 0 || num_fidelity < 0 ||

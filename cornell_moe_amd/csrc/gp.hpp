@@ -64,6 +64,10 @@ struct GpDev {
   DevBuf<int> lcbI;
   // leave-one-out predictions and gradient (loo.hip): K^-1, the scaled columns B, M and the per-row vectors
   DevBuf<double> looD;
+  // the ensemble-averaged posterior mean and the recommendation (recommend.hip; held by the ensemble's first member): the call's
+  // doubles (results first: one copy back) and the start indices
+  DevBuf<double> recD;
+  DevBuf<int> recI;
   int num_cu = 256;
   // per-dimension mean and max |x - mean| of the training points (refreshed by rebuild() and by the append path of add_points):
   // the frame centre of the KG coordinate tables and the extent the kernel selection needs, so that an evaluation does not
@@ -206,6 +210,16 @@ void lcb_select_on_device(GpDev& gp, const double* pts, int C, int q, int* index
 void loo_predict_on_device(GpDev& gp, double* mean_out, double* var_out);
 // d L_LOO / d [alpha, lengths[d], noise variances[1 + g]], the conventions of GpDev::grad_log_marginal_likelihood.
 void grad_loo_log_likelihood(GpDev& gp, double* grad);
+// recommend.hip: f(p) = -(1/E) sum_e mu_e(p, fidelity coordinates 1) and its gradient over the free coordinates at P points
+// [P][d - num_fidelity], for the E members `gps` (same data, same device); value_out [P] / grad_out [P][d - num_fidelity] may be NULL.
+void posterior_mean_mcmc_batch(const std::vector<GpDev*>& gps, int num_fidelity, const double* pts, int P, double* value_out,
+                               double* grad_out);
+// recommend.hip: screen C candidates, descend from the S best, pick, keep or fall back (moe_posterior_mean_mcmc_recommend); the
+// caller has validated gd, C and S.
+void posterior_mean_mcmc_recommend(const std::vector<GpDev*>& gps, int num_fidelity, const moe_gd_params_t& gd,
+                                   const double* domain_bounds, const double* candidates, int C, int S, double* point_out,
+                                   double* value_out, int* screened_index_out, int* refined_out, double* candidate_values_out,
+                                   double* end_points_out, double* path_out);
 // r6 (query_grad.hip): ComputeGradVarianceOfPoints / ComputeGradCholeskyVarianceOfPoints (gpp_math.cpp:1267-1474) for the first
 // `num_derivs` of the `num_pts` points, the m x m x d algebra on the device: out[num_derivs][d m m] in the reference's layout.
 void grad_variance_on_device(GpDev& gp, const double* pts, int num_pts, int num_derivs, bool cholesky, double* out);

@@ -16,6 +16,7 @@ _ROOT = __import__("os").path.dirname(__import__("os").path.dirname(__import__("
 sys.path.insert(0, _ROOT)
 sys.path.insert(0, __import__("os").path.join(_ROOT, "tests"))  # the wrapper mirror is test infrastructure (tests/wrappers_mirror.py);
 from cornell_moe_amd import GPP  # noqa: E402                     # with the reference installed, its own cpp_wrappers take this place
+from cornell_moe_amd.posterior_mean_mcmc import recommend_point  # noqa: E402
 import wrappers_mirror as cw  # noqa: E402
 
 
@@ -114,6 +115,9 @@ def main():
               "(KG %.4g, found=%s); suggested %s; best observed %.4f; reported point %s f=%.4f; smallest lower bound at %s" % (
                   it, t1 - t0, t2 - t1, t3 - t2, voi, list(status.values()), np.round(nxt, 3).tolist(), y.min(),
                   np.round(report, 3).tolist(), float(branin(report)), np.round(screened, 3).tolist()), flush=True)
+        # the refined report: the same screening followed by the descent of examples/main.py:243-260 (py_sgd_params_ps), one device call
+        refined = recommend_point(models, [[0.0, 1.0]] * dim, pts, (1, 1000, 3, 15, 0.7, 1.0, 0.02, 1.0e-10))
+        print("iteration %d: refined report %s f=%.4f" % (it, np.round(refined, 3).tolist(), float(branin(refined))), flush=True)
     return y
 
 

@@ -347,6 +347,46 @@ int moe_kg_mcmc_batch(const moe_gp_t* const* gps, int num_mcmc, int num_fidelity
                       int total_num_mcmc, double* kg, double* grad_kg, moe_error_t* err);
 int moe_kg_mcmc_finalize(double* kg, double* grad_kg, const double* points_to_sample_all, int num_evals, int num_to_sample,
                          int dim, int num_fidelity, int total_num_mcmc);
+/* ---- the ensemble-averaged posterior mean and the recommendation step (examples/main.py:142-157, 243-260) ----
+ * PosteriorMeanMCMC.compute_posterior_mean_mcmc / compute_grad_posterior_mean_mcmc (cpp_wrappers/knowledge_gradient_mcmc.py:109-155)
+ * at num_points points[num_points][dim - num_fidelity] in one launch, one copy down, one wait and one copy back:
+ *   value_out[p] = -(1 / num_mcmc) sum_e mu_e(point_p, fidelity coordinates = 1), grad_out[p][dim - num_fidelity] its gradient over
+ * the free coordinates -- the sign and fidelity conventions of moe_posterior_mean.  The members are summed in ascending order and
+ * the sum is then divided by num_mcmc, as the reference does.  Either output may be NULL.
+ * The members must share dim, the sampled points and the observed-derivative list, and live on one device (MOE_ERR_INVALID_VALUE
+ * otherwise, as moe_kg_mcmc_batch).  Every reduction has a fixed order: the bits of a point's result depend neither on its
+ * neighbours nor on num_points.  Points go through in launches of 16 384, whatever (N, num_mcmc, num_points).  No limit on
+ * num_points or num_mcmc beyond memory; dim <= 32 and num_derivatives <= 12 as everywhere.  No handle is modified.
+ * Errors: gps or points NULL, a NULL handle -> MOE_ERR_RUNTIME; num_mcmc < 1, num_points < 1, num_fidelity outside [0, dim) ->
+ * MOE_ERR_BOUNDS. */
+int moe_posterior_mean_mcmc_batch(const moe_gp_t* const* gps, int num_mcmc, int num_fidelity, const double* points, int num_points,
+                                  double* value_out, double* grad_out, moe_error_t* err);
+/* The whole recommendation on the device: one copy down, one stream of kernels, one wait, one copy back; no handle is modified.
+ * size = dim - num_fidelity, f = the objective of moe_posterior_mean_mcmc_batch, candidates[num_candidates][size].
+ *   1. screen: f at every candidate (candidate_values_out); i0 = *screened_index_out = the first index of the largest f
+ *      (numpy.argmin of the averaged mean, main.py:252);
+ *   2. starts: the num_starts candidates with the largest f, equal values by index (the reference: num_starts = 1, candidate i0);
+ *   3. descent from each start, python_version/optimization.py GradientDescentOptimizer.optimize (:444-527) literally: x_0 = the
+ *      start; for i = 1 .. T = max_num_steps: a_i = pre_mult i^-gamma (computed on the host with pow), step = a_i grad f(x_{i-1}),
+ *      each coordinate limited as python_version/domain.py:187-200 (dist = fmin(x - lo, hi - x); |step| > max_relative_change dist
+ *      -> step = copysign(max_relative_change dist, step)), x_i = x_{i-1} + step.  The end point is the mean of the last k steps,
+ *      _get_averaging_range's k (:416-442): num_steps_averaged < 0 or > T -> T, 0 -> 1; x_0 is never included.
+ *      max_num_restarts, tolerance and num_multistarts are IGNORED, as the reference's Python optimiser ignores them: no restarts,
+ *      no tolerance stop;
+ *   4. pick: f at every end point; the winner is the first of the largest (MultistartOptimizer.optimize's strict compare, :595-603);
+ *   5. keep or fall back (main.py:259-260): -f(winner) > -f(candidate i0) -> point_out = candidate i0, *refined_out = 0; otherwise
+ *      point_out = the winner, *refined_out = 1.  *value_out = f(point_out).
+ * point_out[size]; end_points_out[num_starts][size] and path_out[num_starts][max_num_steps + 1][size] (x_0 .. x_T of every start)
+ * may be NULL, as may value_out, screened_index_out, refined_out and candidate_values_out.
+ * The descent of a start belongs to one workgroup: its bits do not depend on the other starts in the call.
+ * Errors, in this order: gps NULL -> MOE_ERR_RUNTIME; num_mcmc < 1 -> MOE_ERR_BOUNDS; gd, domain_bounds, candidates or point_out
+ * NULL -> MOE_ERR_RUNTIME; num_candidates < 1, num_starts outside [1, num_candidates], max_num_steps < 1, domain_type other than
+ * MOE_DOMAIN_TENSOR_PRODUCT (only tensor-product domains are supported), num_fidelity outside [0, dim) -> MOE_ERR_BOUNDS; a NULL
+ * handle -> MOE_ERR_RUNTIME; mismatched members as above. */
+int moe_posterior_mean_mcmc_recommend(const moe_gp_t* const* gps, int num_mcmc, int num_fidelity, const moe_gd_params_t* gd,
+                                      const double* domain_bounds, const double* candidates, int num_candidates, int num_starts,
+                                      double* point_out, double* value_out, int* screened_index_out, int* refined_out,
+                                      double* candidate_values_out, double* end_points_out, double* path_out, moe_error_t* err);
 /* compute_expected_improvement_mcmc / compute_grad_expected_improvement_mcmc / evaluate_EI_mcmc_at_point_list
  * (gpp_python_expected_improvement_mcmc.cpp:42-108 -> ExpectedImprovementMCMCEvaluator,
  * gpp_expected_improvement_mcmc_optimization.cpp:48-88); analytic != 0 takes the 1,0-EI evaluator (:136-176; needs
