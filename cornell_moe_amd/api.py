@@ -820,6 +820,48 @@ def recommend(gps, candidates, gd_params, domain_bounds, num_fidelity=0, num_sta
     return out
 
 
+TRACE_EXTRA = 6  # trace columns behind the point: f0 | halvings | limiter changed | rejected | stopped by norm | state
+
+
+def minimize_member_means(gps, candidates, gd, bounds, num_fidelity=0, want_means=False, want_trace=False):
+    """moe_posterior_mean_members_minimize: for every member of the ensemble by itself, screen the candidates on the member's
+    posterior mean (fidelity coordinates pinned to 1), run ComputeOptimalPosteriorMean's line search from the best on the device,
+    keep the start if the search ended worse.  candidates [C][size] (one set for all members) or [E][C][size] (member e's own
+    set), size = dim - num_fidelity.  Returns a dict: best_points [E][size], best_values [E], start_index [E], fell_back [E]
+    (bool); with want_means means [E][C]; with want_trace trace [E][max_num_restarts][max_num_steps][size + 6] (moe_hip.h)."""
+    arr, E, d, keep = _ensemble_handles(gps)
+    size = d - int(num_fidelity)
+    if E > 0 and not 0 < size <= d:
+        raise BoundsException("num_fidelity out of range", num_fidelity, 0, d - 1)
+    g = DeviceGP._gd(gd)
+    cand = np.ascontiguousarray(candidates, dtype=np.float64)
+    per_member = cand.ndim == 3
+    if per_member and cand.shape[0] != E:
+        raise InvalidValueException("per-member candidates need one set per member", cand.shape[0], E, 0)
+    C_ = cand.reshape(-1, max(size, 1)).shape[0] // (max(E, 1) if per_member else 1)
+    bounds, bp = _d(bounds)
+    En, R, T = max(E, 1), max(g.max_num_restarts, 0), max(g.max_num_steps, 0)
+    points = np.zeros((En, max(size, 1)))
+    values = np.zeros(En)
+    index = np.zeros(En, dtype=np.int32)
+    fell = np.zeros(En, dtype=np.int32)
+    means = np.zeros((En, max(C_, 1))) if want_means else None
+    trace = np.zeros((En, R, T, max(size, 1) + TRACE_EXTRA)) if want_trace else None
+    err = _lib.MoeError()
+    _check(_lib.load().moe_posterior_mean_members_minimize(arr, E, int(num_fidelity), C.byref(g), bp, cand.ctypes.data_as(dp), C_,
+                                                           1 if per_member else 0, points.ctypes.data_as(dp),
+                                                           values.ctypes.data_as(dp), index.ctypes.data_as(_lib.ip),
+                                                           fell.ctypes.data_as(_lib.ip),
+                                                           means.ctypes.data_as(dp) if want_means else None,
+                                                           trace.ctypes.data_as(dp) if want_trace else None, C.byref(err)), err)
+    out = dict(best_points=points, best_values=values, start_index=index.astype(np.int64), fell_back=fell.astype(bool))
+    if want_means:
+        out["means"] = means
+    if want_trace:
+        out["trace"] = trace
+    return out
+
+
 def kg_multistart_multi(gps, outer_params, inner_params, bounds, discrete, starts, Xp, num_mc, best_so_far, normals,
                         gradient_ascent=True, num_fidelity=0):
     """moe_kg_multistart_multi (r5): the outer optimiser with its restarts dealt to `gps` -- DeviceGP objects holding the same GP on

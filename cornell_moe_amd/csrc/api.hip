@@ -791,6 +791,27 @@ int moe_posterior_mean_mcmc_recommend(const moe_gp_t* const* gps, int num_mcmc, 
   });
 }
 
+int moe_posterior_mean_members_minimize(const moe_gp_t* const* gps, int num_mcmc, int num_fidelity, const moe_gd_params_t* gd,
+                                        const double* domain_bounds, const double* candidates, int num_candidates, int per_member,
+                                        double* best_points, double* best_values, int* start_index, int* fell_back,
+                                        double* means_out, double* trace_out, moe_error_t* err) {
+  return guarded(err, [&] {
+    require(gps != nullptr, "gps is NULL");
+    if (num_mcmc < 1) throw moe::Error(MOE_ERR_BOUNDS, "num_mcmc must be positive", num_mcmc, 1, 1e9);
+    require(gd && domain_bounds && candidates && best_points, "NULL argument");
+    if (num_candidates < 1) throw moe::Error(MOE_ERR_BOUNDS, "the number of candidates must be positive", num_candidates, 1, 1e9);
+    if (num_fidelity < 0) throw moe::Error(MOE_ERR_BOUNDS, "num_fidelity out of range", num_fidelity, 0, moe::kMaxDimPadded - 1);
+    if (gd->max_num_steps < 1) throw moe::Error(MOE_ERR_BOUNDS, "max_num_steps must be positive", gd->max_num_steps, 1, 1e9);
+    if (gd->max_num_restarts < 1) throw moe::Error(MOE_ERR_BOUNDS, "max_num_restarts must be positive", gd->max_num_restarts, 1, 1e9);
+    if (gd->domain_type != MOE_DOMAIN_TENSOR_PRODUCT)
+      throw moe::Error(MOE_ERR_BOUNDS, "the members' minimisation supports tensor-product domains only", gd->domain_type, 0, 0);
+    const auto locks = lock_ensemble(gps, num_mcmc);
+    const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
+    moe::posterior_mean_members_minimize(v, num_fidelity, *gd, domain_bounds, candidates, num_candidates, per_member != 0,
+                                         best_points, best_values, start_index, fell_back, means_out, trace_out);
+  });
+}
+
 int moe_kg_mcmc_finalize(double* kg, double* grad_kg, const double* points_to_sample_all, int num_evals, int num_to_sample,
                          int dim, int num_fidelity, int total_num_mcmc) {
   if (!kg || !points_to_sample_all || num_evals <= 0 || num_to_sample <= 0 || dim <= 0 || num_fidelity < 0 ||

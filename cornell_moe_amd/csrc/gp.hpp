@@ -68,6 +68,10 @@ struct GpDev {
   // doubles (results first: one copy back) and the start indices
   DevBuf<double> recD;
   DevBuf<int> recI;
+  // every member's posterior-mean minimiser (pm_members.hip; held by the ensemble's first member): the call's doubles (results
+  // first: one copy back) and the start indices
+  DevBuf<double> pmmD;
+  DevBuf<int> pmmI;
   int num_cu = 256;
   // per-dimension mean and max |x - mean| of the training points (refreshed by rebuild() and by the append path of add_points):
   // the frame centre of the KG coordinate tables and the extent the kernel selection needs, so that an evaluation does not
@@ -220,6 +224,13 @@ void posterior_mean_mcmc_recommend(const std::vector<GpDev*>& gps, int num_fidel
                                    const double* domain_bounds, const double* candidates, int C, int S, double* point_out,
                                    double* value_out, int* screened_index_out, int* refined_out, double* candidate_values_out,
                                    double* end_points_out, double* path_out);
+// pm_members.hip: for every member by itself, screen its C candidates (candidates [C][size], or per_member [E][C][size]), run
+// posterior_mean_optimize's line search from the best on the device, keep or fall back (moe_posterior_mean_members_minimize); the
+// caller has validated gd and C.  means_out [E][C] and trace_out [E][restarts steps][size + 6] may be NULL.
+void posterior_mean_members_minimize(const std::vector<GpDev*>& gps, int num_fidelity, const moe_gd_params_t& gd,
+                                     const double* domain_bounds, const double* candidates, int C, bool per_member,
+                                     double* best_points, double* best_values, int* start_index, int* fell_back, double* means_out,
+                                     double* trace_out);
 // r6 (query_grad.hip): ComputeGradVarianceOfPoints / ComputeGradCholeskyVarianceOfPoints (gpp_math.cpp:1267-1474) for the first
 // `num_derivs` of the `num_pts` points, the m x m x d algebra on the device: out[num_derivs][d m m] in the reference's layout.
 void grad_variance_on_device(GpDev& gp, const double* pts, int num_pts, int num_derivs, bool cholesky, double* out);

@@ -387,6 +387,45 @@ int moe_posterior_mean_mcmc_recommend(const moe_gp_t* const* gps, int num_mcmc, 
                                       const double* domain_bounds, const double* candidates, int num_candidates, int num_starts,
                                       double* point_out, double* value_out, int* screened_index_out, int* refined_out,
                                       double* candidate_values_out, double* end_points_out, double* path_out, moe_error_t* err);
+/* ---- every member's own posterior-mean minimiser: the per-member discretisation of a KG-MCMC iteration (examples/main.py:172-197) ----
+ * For each of the num_mcmc members BY ITSELF (nothing is averaged), in one device call -- one copy down, one stream of kernels, one
+ * wait, one copy back; no handle is modified.  size = dim - num_fidelity; mu_e = member e's posterior mean of the function value with
+ * the num_fidelity trailing coordinates pinned to 1 (the POSITIVE mean: no sign flip on the outputs).
+ *   1. screen: mu_e at each of num_candidates candidates -- candidates[num_candidates][size] shared by the members (per_member == 0)
+ *      or candidates[num_mcmc][num_candidates][size], member e's own set (per_member != 0).  start_index[e] = the first index of the
+ *      smallest mu_e (numpy.argmin's rule: a NaN counts as smaller than every number).  means_out[num_mcmc][num_candidates] (may be
+ *      NULL) are the screened means.  Candidates go through in launches of 16 384 per member.
+ *   2. descend: ComputeOptimalPosteriorMean from that candidate, with the decisions of moe_posterior_mean_optimize in its order:
+ *      for r < max_num_restarts, for i < max_num_steps: f0, g = value and gradient of f = -mu_e at x; alpha = pre_mult (i + 1)^-gamma
+ *      (a table computed on the host with pow); at most 30 trials x + alpha g, accepted when f_trial - f0 > alpha |g|^2 / 2, alpha
+ *      halved otherwise; the step alpha g limited per coordinate by TensorProductDomain::LimitUpdate (max_relative_change; halved
+ *      when it would leave the domain); no move and the end of the restart when all 30 trials failed or the limited step is zero;
+ *      f re-evaluated at x + step when the limiter changed the step; the end of the restart when that value <= f0; otherwise x +=
+ *      step, and the end of the restart when |step| < tolerance / max_num_steps.  After a restart: stop unless it moved x by more
+ *      than tolerance.
+ *   3. keep or fall back (main.py:191-193): mu_e(end) > mu_e(start candidate) -> best_points[e] = that candidate, fell_back[e] = 1;
+ *      otherwise best_points[e] = the end point, fell_back[e] = 0.  best_values[e] = mu_e(best_points[e]).
+ *      A step of 2. is taken only after f rose (the trial test, and value > f0 where the limiter changed the step), so mu_e(end) <=
+ *      mu_e(start) by construction: fell_back[e] = 1 is unreachable short of a rounding error as large as the whole improvement.
+ *      The rule is kept because the reference keeps it.
+ * best_points[num_mcmc][size]; best_values[num_mcmc], start_index[num_mcmc], fell_back[num_mcmc] may be NULL.
+ * trace_out (may be NULL): [num_mcmc][max_num_restarts][max_num_steps][size + 6], one row per step of the line search:
+ *   x after the step (size) | f0 | halvings taken (30: every trial failed) | 1 if the limiter changed the step | 1 if rejected by
+ *   value <= f0 | 1 if stopped by the step norm | state: 0 the step was not reached, 1 accepted, 2 ended without a move (30 failed
+ *   trials or a zero step), 3 rejected.
+ * An evaluation's sums have a fixed order that depends on the number of sampled points alone: a member's outputs carry the same bits
+ * whatever num_mcmc, the other members and -- for the screened means -- num_candidates and the other candidates.
+ * The members must share dim, the sampled points and the observed-derivative list, and live on one device.  Tensor-product domains
+ * only: domain_type = MOE_DOMAIN_SIMPLEX is refused.  num_steps_averaged and num_multistarts are ignored, as in
+ * moe_posterior_mean_optimize.  dim <= 32, num_mcmc <= 65 535.
+ * Errors, in this order, everything that needs no handle before a handle is touched: gps NULL -> MOE_ERR_RUNTIME; num_mcmc < 1 ->
+ * MOE_ERR_BOUNDS; gd, domain_bounds, candidates or best_points NULL -> MOE_ERR_RUNTIME; num_candidates < 1, num_fidelity < 0,
+ * max_num_steps < 1, max_num_restarts < 1, domain_type other than MOE_DOMAIN_TENSOR_PRODUCT -> MOE_ERR_BOUNDS; a NULL handle ->
+ * MOE_ERR_RUNTIME; num_fidelity >= dim -> MOE_ERR_BOUNDS; mismatched members -> MOE_ERR_INVALID_VALUE. */
+int moe_posterior_mean_members_minimize(const moe_gp_t* const* gps, int num_mcmc, int num_fidelity, const moe_gd_params_t* gd,
+                                        const double* domain_bounds, const double* candidates, int num_candidates, int per_member,
+                                        double* best_points, double* best_values, int* start_index, int* fell_back,
+                                        double* means_out, double* trace_out, moe_error_t* err);
 /* compute_expected_improvement_mcmc / compute_grad_expected_improvement_mcmc / evaluate_EI_mcmc_at_point_list
  * (gpp_python_expected_improvement_mcmc.cpp:42-108 -> ExpectedImprovementMCMCEvaluator,
  * gpp_expected_improvement_mcmc_optimization.cpp:48-88); analytic != 0 takes the 1,0-EI evaluator (:136-176; needs
