@@ -365,7 +365,9 @@ int moe_posterior_mean_mcmc_batch(const moe_gp_t* const* gps, int num_mcmc, int 
  * size = dim - num_fidelity, f = the objective of moe_posterior_mean_mcmc_batch, candidates[num_candidates][size].
  *   1. screen: f at every candidate (candidate_values_out); i0 = *screened_index_out = the first index of the largest f
  *      (numpy.argmin of the averaged mean, main.py:252);
- *   2. starts: the num_starts candidates with the largest f, equal values by index (the reference: num_starts = 1, candidate i0);
+ *   2. starts: the num_starts candidates with the largest f, equal values by index (the reference: num_starts = 1, candidate i0).
+ *      NaN values are never picked: neither i0 nor a start is a candidate whose f is NaN while a candidate with a number is left
+ *      (with nothing left to pick a round answers candidate 0);
  *   3. descent from each start, python_version/optimization.py GradientDescentOptimizer.optimize (:444-527) literally: x_0 = the
  *      start; for i = 1 .. T = max_num_steps: a_i = pre_mult i^-gamma (computed on the host with pow), step = a_i grad f(x_{i-1}),
  *      each coordinate limited as python_version/domain.py:187-200 (dist = fmin(x - lo, hi - x); |step| > max_relative_change dist

@@ -250,6 +250,24 @@ def gpu_cases():
     ]
 
 
+def edge_cases():
+    """the cases of tests/test_gpu_pm_members_edges.py, gpu_cases()'s layout: every padded dimension above 8 (d = 9 .. 32 pad to 12, 16,
+    24, 24, 32, 32), one with two observed derivatives and a fidelity coordinate, LONG_INNER cut to 12 steps at d = 32 (its second
+    restart moves), and main.py's parameters with a pre_mult small enough for steps that the limiter leaves alone"""
+    import sampling_reference as sr
+    SE, MATERN = sr.COV_SQUARE_EXPONENTIAL, sr.COV_MATERN_NU_2P5
+    return [
+        (1, 20, 9, 2, MATERN, (), 0, 30, MAIN_INNER),
+        (0, 20, 16, 2, SE, (), 0, 30, MAIN_INNER),
+        (1, 20, 17, 2, MATERN, (), 0, 30, MAIN_INNER),
+        (1, 20, 24, 2, SE, (), 0, 30, MAIN_INNER),
+        (1, 20, 25, 2, MATERN, (0, 2), 1, 30, MAIN_INNER),
+        (1, 20, 32, 2, SE, (), 0, 30, MAIN_INNER),
+        (2, 20, 32, 2, MATERN, (), 0, 30, LONG_INNER[:1] + (12,) + LONG_INNER[2:]),
+        (0, 20, 24, 2, MATERN, (), 0, 30, MAIN_INNER[:5] + (1.0e-3,) + MAIN_INNER[6:]),
+    ]
+
+
 def case_problem(case, dtype=LD):
     """(members, arrays, bounds, candidates) of a case: the candidates are uniform draws followed by the sampled points, as main.py
     screens them"""

@@ -289,3 +289,101 @@ def make_ensemble(seed, n, d, E, cov_type, derivs=(), noise=1e-2, dtype=LD):
     noises = [np.full(g1, noise * rng.uniform(0.5, 2.0)) for _ in range(E)]
     members = [Member(cov_type, hypers[e], X, y, noises[e], derivs, dtype) for e in range(E)]
     return members, dict(X=X, y=y, hypers=hypers, noises=noises, derivs=list(derivs), cov_type=cov_type)
+
+
+# ---- the cases of tests/test_gpu_recommend_edges.py; tests/test_recommend_reference.py asserts their margins on the CPU ----
+EDGE_GD = GdParams(6, 3, 0.7, 1.0, 0.02)       # clamped: a_i |grad f| exceeds 0.02 of the distance to the nearer face at every step
+EDGE_GD_FREE = GdParams(6, 3, 0.7, 0.02, 0.5)  # a small pre_mult in the interior: the clamp is inactive at every step
+EDGE_GD_3 = GdParams(3, 3, 0.7, 0.02, 0.5)
+EDGE_GD_1 = GdParams(1, 0, 0.7, 0.02, 0.5)
+
+EdgeCase = collections.namedtuple("EdgeCase", "kind seed n d E cov derivs num_fidelity C S gd")
+
+
+def edge_cases():
+    """kind: 'descent' (every padded dimension; E = 3 leaves wavefronts idle at W = 8 and W = 4, E = 5 makes a second member group
+    at W = 4), 'small' (n = 1, 2: n = 1 observes derivatives, for a single function value equals the constant mean and f is flat),
+    'lds' (the training points at, below and above the LDS-staging limits), 'select' (more candidates than threads), 'ties' and 'nan'
+    (the selection's base sets)."""
+    SE, MATERN = sr.COV_SQUARE_EXPONENTIAL, sr.COV_MATERN_NU_2P5
+    cases = [
+        EdgeCase("descent", 0, 20, 8, 3, MATERN, (), 0, 6, 2, EDGE_GD),
+        EdgeCase("descent", 0, 20, 16, 5, SE, (), 0, 6, 2, EDGE_GD_FREE),
+        EdgeCase("descent", 0, 20, 17, 3, MATERN, (), 0, 6, 2, EDGE_GD),
+        EdgeCase("descent", 0, 20, 24, 5, SE, (), 0, 6, 2, EDGE_GD_FREE),
+        EdgeCase("descent", 0, 20, 25, 5, MATERN, (0, 2), 1, 6, 2, EDGE_GD),
+        EdgeCase("descent", 0, 20, 32, 3, SE, (), 0, 6, 2, EDGE_GD),
+    ]
+    for d, derivs in ((3, (0, 2)), (32, (1, 31))):
+        for n in (1, 2):
+            for E in (1, 17):
+                cases.append(EdgeCase("small", 0, n, d, E, MATERN, derivs if n == 1 else (), 0, 3, 1, EDGE_GD_3))
+    for d, n in ((3, 30), (32, 192), (32, 193), (32, 384), (32, 385)):
+        cases.append(EdgeCase("lds", 0, n, d, 2, MATERN if n % 2 else SE, (), 0, 4, 1, EDGE_GD_3))
+    for C in (257, 600):
+        for S in (2, 7):
+            cases.append(EdgeCase("select", 0, 12, 2, 2, MATERN, (), 0, C, S, EDGE_GD_1))
+    cases.append(EdgeCase("ties", 0, 12, 2, 2, SE, (), 0, 256, 4, EDGE_GD_1))
+    cases.append(EdgeCase("nan", 0, 12, 2, 2, MATERN, (), 0, 300, 3, EDGE_GD_1))
+    return cases
+
+
+def edge_id(c):
+    return "%s-seed%d-n%d-d%d-E%d-C%d-S%d" % (c.kind, c.seed, c.n, c.d, c.E, c.C, c.S)
+
+
+def edge_problem(case, dtype=LD):
+    """(members, arrays, bounds, candidates) of an edge case: candidates uniform in [0.1, 0.9]^size"""
+    members, a = make_ensemble(case.seed, case.n, case.d, case.E, case.cov, case.derivs, dtype=dtype)
+    size = case.d - case.num_fidelity
+    rng = np.random.default_rng(2000 + case.seed)
+    cand = rng.uniform(0.1, 0.9, size=(case.C, size))
+    return members, a, np.array([[0.0, 1.0]] * size), cand
+
+
+def clamp_kinds(ens, gd, bounds, paths):
+    """{True, False} over the steps of extended()'s paths: whether the clamp changed any coordinate of the step, with the smallest
+    |a_i |grad f| - limit| met (the margin of that decision)"""
+    bounds = np.asarray(bounds, dtype=np.float64).reshape(ens.size, 2)
+    steps = step_sizes(gd)
+    kinds, low = set(), np.inf
+    for path in paths:
+        for i in range(1, gd.max_num_steps + 1):
+            x = path[i - 1]
+            step = LD(steps[i - 1]) * ens.f(x[None, :], True)[1][0]
+            limit = LD(gd.max_relative_change) * np.fmin(x - bounds[:, 0].astype(LD), bounds[:, 1].astype(LD) - x)
+            kinds.add(bool(np.any(np.fabs(step) > limit)))
+            low = min(low, float(np.min(np.abs(np.fabs(step) - limit))))
+    return kinds, low
+
+
+def ties_problem(case):
+    """(members, arrays, bounds, candidates [256 + 128], the picks num_starts = 4 must give, their margins): behind the case's 256
+    candidates 128 copies of the worst of them (never picked), among which one copy each of the second-best and of the third-best, in
+    a slot that pm_select_kernel gives to a thread of another wavefront than the original's (index i belongs to thread i % 256)."""
+    members, a, bounds, cand = edge_problem(case)
+    fc = Ensemble(members, case.num_fidelity).f(cand)[0]
+    order = top_indices(fc, len(fc))
+    best, second, third = int(order[0]), int(order[1]), int(order[2])
+    extra = np.repeat(cand[order[-1]:order[-1] + 1], 128, axis=0)
+
+    def slot(i, k):
+        return (64 if (i % 256) // 64 == 0 else 0) + k
+
+    extra[slot(second, 1)] = cand[second]
+    extra[slot(third, 2)] = cand[third]
+    picks = [best, second, 256 + slot(second, 1), third]
+    margins = [float(fc[order[k]] - fc[order[k + 1]]) for k in range(4)]
+    return members, a, bounds, np.vstack([cand, extra]), picks, margins
+
+
+def nan_problem(case, where):
+    """(members, arrays, bounds, candidates with a NaN coordinate in candidate `where`, the starts among the others, margins at rank
+    1 and at the cut among the others)"""
+    members, a, bounds, cand = edge_problem(case)
+    cand[where, -1] = np.nan
+    keep = np.array([i for i in range(case.C) if i != where])
+    fc = Ensemble(members, case.num_fidelity).f(cand[keep])[0]
+    order = top_indices(fc, len(fc))
+    margins = [float(fc[order[0]] - fc[order[1]]), float(fc[order[case.S - 1]] - fc[order[case.S]])]
+    return members, a, bounds, cand, keep[order[:case.S]], margins

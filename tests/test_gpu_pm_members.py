@@ -56,6 +56,10 @@ SCREEN_CASES = [
 
 @pytest.mark.parametrize("case", SCREEN_CASES, ids=lambda c: "E%d-d%d-cov%d-g%d-f%d-C%d-pm%d" % (c[0], c[1], c[2], len(c[3]), c[4], c[6], c[7]))
 def test_screened_means_and_start_index(case):
+    _check_screen(case)
+
+
+def _check_screen(case):
     E, d, cov, derivs, nf, ns, C_, per_member = case
     size = d - nf
     for n in ns:

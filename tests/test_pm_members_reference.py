@@ -189,3 +189,34 @@ def test_python_layers_exist():
     from cornell_moe_amd import api, discretisation
     assert callable(api.minimize_member_means) and callable(discretisation.kg_discrete_points)
     assert callable(discretisation.member_posterior_mean_minima)
+
+
+# ---- the inputs of tests/test_gpu_pm_members_edges.py: every decision margin on the CPU ----
+_edge_ids = lambda c: "seed%d-d%d-g%d-f%d-T%d-R%d-pre%g" % (c[0], c[2], len(c[5]), c[6], c[8][1], c[8][2], c[8][5])  # noqa: E731
+
+
+@pytest.mark.parametrize("case", pr.edge_cases(), ids=_edge_ids)
+def test_edge_case_margins(case):
+    members, a, bounds, cand = pr.case_problem(case)
+    for member in members:
+        res = pr.run(member, case[6], case[8], bounds, cand)
+        print("start %d, %d steps, smallest margins %s" % (res.start_index, len(res.steps), sorted(res.margins, key=lambda m: m[1])[:2]))
+        assert pr.min_margin(res) >= MARGIN, "choose another seed: a decision of this case is closer than the checkers' own error"
+        assert not res.fell_back
+
+
+def test_edge_descents_cover_clamped_free_halved_steps_and_a_second_restart_that_moves():
+    changed, halvings, restarts, padded = set(), 0, set(), set()
+    for case in pr.edge_cases():
+        members, a, bounds, cand = pr.case_problem(case)
+        d = case[2]
+        padded.add((d + 3) // 4 * 4 if d <= 16 else (d + 7) // 8 * 8)
+        for member in members:
+            for r, i, s in pr.run(member, case[6], case[8], bounds, cand).steps:
+                changed.add(s.changed)
+                halvings = max(halvings, s.halvings)
+                if s.state == 1 and s.moved:
+                    restarts.add(r)
+    assert changed == {True, False} and halvings > 0 and 1 in restarts and padded == {12, 16, 24, 32}
+    assert any(len(c[5]) == 2 and c[6] == 1 and c[2] > 16 for c in pr.edge_cases())
+    assert any(c[2] == 32 and c[8][1:3] == (12, 2) for c in pr.edge_cases())

@@ -200,3 +200,36 @@ def test_bad_arguments_are_refused_without_a_device(lib):
     assert rec(none, 1, 0, _gd(), 4, 1) == _lib.MOE_ERR_RUNTIME and b"NULL GP handle" in err.message
     assert lib.moe_posterior_mean_mcmc_recommend(none, 1, 0, None, p, p, 4, 1, p, None, None, None, None, None, None,
                                                  None) == _lib.MOE_ERR_RUNTIME
+
+
+# ---- the inputs of tests/test_gpu_recommend_edges.py: every decision margin on the CPU ----
+@pytest.mark.parametrize("case", rr.edge_cases(), ids=rr.edge_id)
+def test_edge_case_margins(case):
+    if case.kind == "ties":
+        margins = rr.ties_problem(case)[5]
+    elif case.kind == "nan":
+        margins = rr.nan_problem(case, 0)[5] + rr.nan_problem(case, case.C - 1)[5]
+    else:
+        members, a, bounds, cand = rr.edge_problem(case)
+        ens = rr.Ensemble(members, case.num_fidelity)
+        want = rr.extended(ens, case.gd, bounds, cand, case.S)
+        margins = list(want.margins)
+        if case.kind == "descent":
+            margins.append(rr.clamp_kinds(ens, case.gd, bounds, want.paths)[1])
+    print("margins %s" % np.array(margins))
+    assert min(margins) >= 1e-7, "choose another seed: a decision of this case is closer than the checkers' own error"
+
+
+def test_edge_descents_cover_a_clamped_and_a_free_step_and_every_padded_dimension():
+    kinds, padded, shapes = set(), set(), set()
+    for case in rr.edge_cases():
+        if case.kind != "descent":
+            continue
+        members, a, bounds, cand = rr.edge_problem(case)
+        ens = rr.Ensemble(members, case.num_fidelity)
+        kinds |= rr.clamp_kinds(ens, case.gd, bounds, rr.extended(ens, case.gd, bounds, cand, case.S).paths)[0]
+        padded.add((case.d + 3) // 4 * 4 if case.d <= 16 else (case.d + 7) // 8 * 8)
+        shapes.add((case.cov, len(case.derivs), case.num_fidelity))
+        assert case.n == 20 and case.E in (3, 5) and case.S == 2 and case.gd[:2] == (6, 3)
+    assert kinds == {True, False} and padded == {8, 16, 24, 32}
+    assert {s[0] for s in shapes} == {SE, MATERN} and (MATERN, 2, 1) in shapes
