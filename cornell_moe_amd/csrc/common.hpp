@@ -9,6 +9,7 @@
 #include <mutex>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -303,5 +304,18 @@ inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 // Padded dimension the kernels are instantiated for: multiples of 4 up to 16, then 24 and 32 (padded coordinates are 0 and carry
 // inverse length 0, so they drop out of every distance and gradient).
 inline int padded_dim(int d) { return d <= 16 ? round_up(d, 4) : round_up(d, 8); }
+// f(std::integral_constant<int, DP>{}) for the padded dimension dp: the one fan-out from a run-time dp to a template on DP
+template <class F>
+void dispatch_dp(int dp, F&& f) {
+  switch (dp) {
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 8: f(std::integral_constant<int, 8>{}); break;
+    case 12: f(std::integral_constant<int, 12>{}); break;
+    case 16: f(std::integral_constant<int, 16>{}); break;
+    case 24: f(std::integral_constant<int, 24>{}); break;
+    case 32: f(std::integral_constant<int, 32>{}); break;
+    default: throw Error(MOE_ERR_RUNTIME, "unsupported padded dimension");
+  }
+}
 
 }  // namespace moe

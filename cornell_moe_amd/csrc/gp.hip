@@ -228,15 +228,7 @@ void GpDev::grad_log_marginal_likelihood(double* grad) {
   const size_t nblocks = (size_t)((n + 255) / 256) * ((n + 63) / 64);
   dE.reserve(nblocks * (1 + dp) + (size_t)(1 + dp + g1));
   double* out = dE.p + nblocks * (1 + dp);
-  switch (dp) {
-    case 4: launch_ll_grad<4>(cp, dX.p, n, g1, dKinvY.p, dVE.p, n, kdiag, dE.p, out, stream); break;
-    case 8: launch_ll_grad<8>(cp, dX.p, n, g1, dKinvY.p, dVE.p, n, kdiag, dE.p, out, stream); break;
-    case 12: launch_ll_grad<12>(cp, dX.p, n, g1, dKinvY.p, dVE.p, n, kdiag, dE.p, out, stream); break;
-    case 16: launch_ll_grad<16>(cp, dX.p, n, g1, dKinvY.p, dVE.p, n, kdiag, dE.p, out, stream); break;
-    case 24: launch_ll_grad<24>(cp, dX.p, n, g1, dKinvY.p, dVE.p, n, kdiag, dE.p, out, stream); break;
-    case 32: launch_ll_grad<32>(cp, dX.p, n, g1, dKinvY.p, dVE.p, n, kdiag, dE.p, out, stream); break;
-    default: throw Error(MOE_ERR_BOUNDS, "unsupported padded dimension", dp, 4, 16);
-  }
+  dispatch_dp(dp, [&](auto DP) { launch_ll_grad<DP>(cp, dX.p, n, g1, dKinvY.p, dVE.p, n, kdiag, dE.p, out, stream); });
   std::vector<double> h((size_t)(1 + dp + g1));
   MOE_HIP_CHECK(hipMemcpyAsync(h.data(), out, sizeof(double) * h.size(), hipMemcpyDeviceToHost, stream));
   MOE_HIP_CHECK(hipStreamSynchronize(stream));

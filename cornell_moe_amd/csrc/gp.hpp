@@ -214,6 +214,20 @@ void lcb_select_on_device(GpDev& gp, const double* pts, int C, int q, int* index
 void loo_predict_on_device(GpDev& gp, double* mean_out, double* var_out);
 // d L_LOO / d [alpha, lengths[d], noise variances[1 + g]], the conventions of GpDev::grad_log_marginal_likelihood.
 void grad_loo_log_likelihood(GpDev& gp, double* grad);
+// what a member of an ensemble contributes to recommend.hip's and pm_members.hip's kernels: its covariance, K^-1 (y - mean)
+// [n (1 + g)] and the constant mean; the members' records travel as a table in front of the call's other operands
+struct PmMember {
+  CovParams cp;
+  const double* kinvy;
+  double mean;
+};
+static_assert(sizeof(PmMember) % sizeof(double) == 0, "the member table travels inside a buffer of doubles");
+// recommend.hip, for the ensemble calls below: the members `gps` must be non-NULL GPs of one dim, observed-derivative list, set of
+// sampled points and device, and 0 <= num_fidelity < dim (MOE_ERR_BOUNDS / MOE_ERR_RUNTIME / MOE_ERR_INVALID_VALUE otherwise) ...
+void check_pm_members(const std::vector<GpDev*>& gps, int num_fidelity);
+// ... and the call's operands in the first member's pinned staging buffer hStateIn, one copy down: [member table (PmMember) | `rows` points [rows][d - num_fidelity] padded to dp, fidelity coordinates 1, padding 0 | room for `extra` doubles];
+// returns the offset (in doubles) of the extras.
+size_t stage_pm_inputs(const std::vector<GpDev*>& gps, int num_fidelity, const double* pts, size_t rows, size_t extra);
 // recommend.hip: f(p) = -(1/E) sum_e mu_e(p, fidelity coordinates 1) and its gradient over the free coordinates at P points
 // [P][d - num_fidelity], for the E members `gps` (same data, same device); value_out [P] / grad_out [P][d - num_fidelity] may be NULL.
 void posterior_mean_mcmc_batch(const std::vector<GpDev*>& gps, int num_fidelity, const double* pts, int P, double* value_out,

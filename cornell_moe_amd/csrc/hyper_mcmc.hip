@@ -231,15 +231,7 @@ void launch_hmc_propose(const HmcState& st, int step, int half, hipStream_t s) {
 void launch_hmc_cov_batch(int dp, const CovParams* cps, const double* noise, const double* X, int n, const DerivList& dl, double* out,
                           long ld, long set_stride, int sets, bool lower_only, hipStream_t s) {
   if (sets <= 0 || n <= 0) return;
-  switch (dp) {
-    case 4: hmc_cov_batch_dp<4>(cps, noise, X, n, dl, out, ld, set_stride, sets, lower_only, s); break;
-    case 8: hmc_cov_batch_dp<8>(cps, noise, X, n, dl, out, ld, set_stride, sets, lower_only, s); break;
-    case 12: hmc_cov_batch_dp<12>(cps, noise, X, n, dl, out, ld, set_stride, sets, lower_only, s); break;
-    case 16: hmc_cov_batch_dp<16>(cps, noise, X, n, dl, out, ld, set_stride, sets, lower_only, s); break;
-    case 24: hmc_cov_batch_dp<24>(cps, noise, X, n, dl, out, ld, set_stride, sets, lower_only, s); break;
-    case 32: hmc_cov_batch_dp<32>(cps, noise, X, n, dl, out, ld, set_stride, sets, lower_only, s); break;
-    default: throw Error(MOE_ERR_RUNTIME, "unsupported padded dimension");
-  }
+  dispatch_dp(dp, [&](auto DP) { hmc_cov_batch_dp<DP>(cps, noise, X, n, dl, out, ld, set_stride, sets, lower_only, s); });
   MOE_HIP_CHECK(hipGetLastError());
 }
 

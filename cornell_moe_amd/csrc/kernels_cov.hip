@@ -386,15 +386,7 @@ void launch_debug_math(const double* x, int n, double* e, double* r, hipStream_t
 void launch_cov_build(const CovParams& cp, const double* A, int nA, const DerivList& dA, const double* B, int nB,
                       const DerivList& dB, const double* diag_noise, double* out, long ld, long col0, hipStream_t s,
                       bool streaming, bool lower_only) {
-  switch (cp.dp) {
-    case 4: cov_build_dp<4>(cp, A, nA, dA, B, nB, dB, diag_noise, out, ld, col0, s, streaming, lower_only); break;
-    case 8: cov_build_dp<8>(cp, A, nA, dA, B, nB, dB, diag_noise, out, ld, col0, s, streaming, lower_only); break;
-    case 12: cov_build_dp<12>(cp, A, nA, dA, B, nB, dB, diag_noise, out, ld, col0, s, streaming, lower_only); break;
-    case 16: cov_build_dp<16>(cp, A, nA, dA, B, nB, dB, diag_noise, out, ld, col0, s, streaming, lower_only); break;
-    case 24: cov_build_dp<24>(cp, A, nA, dA, B, nB, dB, diag_noise, out, ld, col0, s, streaming, lower_only); break;
-    case 32: cov_build_dp<32>(cp, A, nA, dA, B, nB, dB, diag_noise, out, ld, col0, s, streaming, lower_only); break;
-    default: throw Error(MOE_ERR_RUNTIME, "unsupported padded dimension");
-  }
+  dispatch_dp(cp.dp, [&](auto DP) { cov_build_dp<DP>(cp, A, nA, dA, B, nB, dB, diag_noise, out, ld, col0, s, streaming, lower_only); });
   MOE_HIP_CHECK(hipGetLastError());
 }
 
@@ -420,52 +412,25 @@ void cov_build_pair_dp(const CovParams& cp, const double* A, int nA, const doubl
 // what two launch_cov_build calls write.
 void launch_cov_build_pair(const CovParams& cp, const double* A, int nA, const double* B, int nB1, long col1, int nB2, long col2,
                            double* out, long ld, hipStream_t s) {
-  switch (cp.dp) {
-    case 4: cov_build_pair_dp<4>(cp, A, nA, B, nB1, col1, nB2, col2, out, ld, s); break;
-    case 8: cov_build_pair_dp<8>(cp, A, nA, B, nB1, col1, nB2, col2, out, ld, s); break;
-    case 12: cov_build_pair_dp<12>(cp, A, nA, B, nB1, col1, nB2, col2, out, ld, s); break;
-    case 16: cov_build_pair_dp<16>(cp, A, nA, B, nB1, col1, nB2, col2, out, ld, s); break;
-    case 24: cov_build_pair_dp<24>(cp, A, nA, B, nB1, col1, nB2, col2, out, ld, s); break;
-    case 32: cov_build_pair_dp<32>(cp, A, nA, B, nB1, col1, nB2, col2, out, ld, s); break;
-    default: throw Error(MOE_ERR_RUNTIME, "unsupported padded dimension");
-  }
+  dispatch_dp(cp.dp, [&](auto DP) { cov_build_pair_dp<DP>(cp, A, nA, B, nB1, col1, nB2, col2, out, ld, s); });
   MOE_HIP_CHECK(hipGetLastError());
 }
 
 void launch_mean(const CovParams& cp, const double* X, int n, const DerivList& dX, const double* KinvY, const double* P,
                  int nP, double mean, bool want_grad, double* out, hipStream_t s) {
   if (nP <= 0) return;
-#define MOE_MEAN_CASE(DPV)                                                                                                \
-  case DPV:                                                                                                               \
-    if (want_grad)                                                                                                        \
-      MOE_LAUNCH((mean_kernel<DPV, true>), dim3(nP), dim3(256), 0, s, cp, X, n, dX, KinvY, P, mean, out);        \
-    else                                                                                                                  \
-      MOE_LAUNCH((mean_kernel<DPV, false>), dim3(nP), dim3(256), 0, s, cp, X, n, dX, KinvY, P, mean, out);       \
-    break;
-  switch (cp.dp) {
-    MOE_MEAN_CASE(4)
-    MOE_MEAN_CASE(8)
-    MOE_MEAN_CASE(12)
-    MOE_MEAN_CASE(16)
-    MOE_MEAN_CASE(24)
-    MOE_MEAN_CASE(32)
-    default: throw Error(MOE_ERR_RUNTIME, "unsupported padded dimension");
-  }
-#undef MOE_MEAN_CASE
+  dispatch_dp(cp.dp, [&](auto DP) {
+    if (want_grad)
+      MOE_LAUNCH((mean_kernel<DP, true>), dim3(nP), dim3(256), 0, s, cp, X, n, dX, KinvY, P, mean, out);
+    else
+      MOE_LAUNCH((mean_kernel<DP, false>), dim3(nP), dim3(256), 0, s, cp, X, n, dX, KinvY, P, mean, out);
+  });
   MOE_HIP_CHECK(hipGetLastError());
 }
 
 void launch_grad_kstar(const CovParams& cp, const double* X, int n, const DerivList& dX, const double* P, int nP,
                        const DerivList& dP, double* out, long ld, long col0, hipStream_t s) {
-  switch (cp.dp) {
-    case 4: grad_kstar_dp<4>(cp, X, n, dX, P, nP, dP, out, ld, col0, s); break;
-    case 8: grad_kstar_dp<8>(cp, X, n, dX, P, nP, dP, out, ld, col0, s); break;
-    case 12: grad_kstar_dp<12>(cp, X, n, dX, P, nP, dP, out, ld, col0, s); break;
-    case 16: grad_kstar_dp<16>(cp, X, n, dX, P, nP, dP, out, ld, col0, s); break;
-    case 24: grad_kstar_dp<24>(cp, X, n, dX, P, nP, dP, out, ld, col0, s); break;
-    case 32: grad_kstar_dp<32>(cp, X, n, dX, P, nP, dP, out, ld, col0, s); break;
-    default: throw Error(MOE_ERR_RUNTIME, "unsupported padded dimension");
-  }
+  dispatch_dp(cp.dp, [&](auto DP) { grad_kstar_dp<DP>(cp, X, n, dX, P, nP, dP, out, ld, col0, s); });
   MOE_HIP_CHECK(hipGetLastError());
 }
 

@@ -399,15 +399,7 @@ void grad_loo_log_likelihood(GpDev& gp, double* grad) {
   wt.M = M;
   wt.ldm = n;
   wt.g1 = g1;
-  switch (dp) {
-    case 4: launch_loo_grad<4>(cp, Xp, n, g1, wt, mdiag, part, out, s); break;
-    case 8: launch_loo_grad<8>(cp, Xp, n, g1, wt, mdiag, part, out, s); break;
-    case 12: launch_loo_grad<12>(cp, Xp, n, g1, wt, mdiag, part, out, s); break;
-    case 16: launch_loo_grad<16>(cp, Xp, n, g1, wt, mdiag, part, out, s); break;
-    case 24: launch_loo_grad<24>(cp, Xp, n, g1, wt, mdiag, part, out, s); break;
-    case 32: launch_loo_grad<32>(cp, Xp, n, g1, wt, mdiag, part, out, s); break;
-    default: throw Error(MOE_ERR_BOUNDS, "unsupported padded dimension", dp, 4, 32);
-  }
+  dispatch_dp(dp, [&](auto DP) { launch_loo_grad<DP>(cp, Xp, n, g1, wt, mdiag, part, out, s); });
   std::vector<double> h((size_t)(1 + dp + g1));
   MOE_HIP_CHECK(hipMemcpyAsync(h.data(), out, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s));
   MOE_HIP_CHECK(hipStreamSynchronize(s));

@@ -33,18 +33,11 @@ constexpr int kPmmThreads = 256;   // the row stride of an evaluation
 constexpr int kPmmTraceExtra = 6;  // trace columns behind the point: f0 | halvings | limiter changed | rejected | stopped by norm | state
 constexpr int kPmmHead = 3;        // result columns in front of the point: start index | fell back | value
 
-// what a member contributes: its covariance, K^-1 (y - mean) [n (1 + g)] and the constant mean
-struct PmmMember {
-  CovParams cp;
-  const double* kinvy;
-  double mean;
-};
-static_assert(sizeof(PmmMember) % sizeof(double) == 0, "the member table travels inside a buffer of doubles");
 static_assert(sizeof(CovParams) % sizeof(unsigned int) == 0, "the descent copies a member's covariance into LDS by words");
 
 struct PmmData {
-  const PmmMember* members;  // [E]
-  const double* X;           // [n][DP]: the members share the data
+  const PmMember* members;  // [E]
+  const double* X;          // [n][DP]: the members share the data
   DerivList dX;
   int n, size;  // size = dim - num_fidelity: the free coordinates
 };
@@ -117,7 +110,7 @@ __global__ __launch_bounds__(kPmmThreads) void pmm_screen_kernel(PmmData T, cons
   const long c = (long)c0 + blockIdx.x;
   if (c >= C) return;
   if (tid < DP) pt[tid] = cand[((long)e * member_stride + c) * DP + tid];
-  const PmmMember& m = T.members[e];
+  const PmMember& m = T.members[e];
   pmm_eval<DP, false>(m.cp, m.kinvy, m.mean, T.X, T.n, T.dX, pt, red, tot);
   if (tid == 0) means[(long)e * C + c] = tot[0];
 }
@@ -324,42 +317,20 @@ void posterior_mean_members_minimize(const std::vector<GpDev*>& gps, int num_fid
                                      const double* domain_bounds, const double* candidates, int C, bool per_member,
                                      double* best_points, double* best_values, int* start_index, int* fell_back, double* means_out,
                                      double* trace_out) {
-  if (gps.empty()) throw Error(MOE_ERR_BOUNDS, "num_mcmc must be positive", 0, 1, 1e9);
-  for (const GpDev* g : gps)
-    if (g == nullptr) throw Error(MOE_ERR_RUNTIME, "NULL GP handle in the MCMC ensemble");
+  check_pm_members(gps, num_fidelity);
   GpDev& gp = *gps[0];
-  if (num_fidelity < 0 || num_fidelity >= gp.d) throw Error(MOE_ERR_BOUNDS, "num_fidelity out of range", num_fidelity, 0, gp.d - 1);
-  for (const GpDev* g : gps) {
-    if (g->d != gp.d || g->g != gp.g || !std::equal(g->derivs.idx, g->derivs.idx + g->g, gp.derivs.idx))
-      throw Error(MOE_ERR_INVALID_VALUE, "MCMC ensemble members must share dim and the observed-derivative list", g->d, gp.d, 0);
-    if (g->n != gp.n || g->X != gp.X)
-      throw Error(MOE_ERR_INVALID_VALUE, "MCMC ensemble members must share the sampled points", g->n, gp.n, 0);
-    if (g->device != gp.device) throw Error(MOE_ERR_INVALID_VALUE, "MCMC ensemble members must live on one device", g->device, gp.device, 0);
-  }
   if ((long)gps.size() > 65535) throw Error(MOE_ERR_BOUNDS, "num_mcmc out of range", (double)gps.size(), 1, 65535);
   gp.use_device();
   hipStream_t s = gp.stream;
   const int E = (int)gps.size(), dp = gp.dp, size = gp.d - num_fidelity, T_steps = gd.max_num_steps, R = gd.max_num_restarts;
   // one copy down: [member table | candidates (padded, fidelity coordinates 1) | alpha_0 (T) | bounds (2 size)]
   const size_t rows = (size_t)C * (per_member ? E : 1);
-  const size_t nTab = (size_t)E * sizeof(PmmMember) / sizeof(double), nCand = rows * dp;
-  const size_t nIn = nTab + nCand + (size_t)T_steps + 2 * (size_t)size;
-  gp.hStateIn.reserve(nIn);
-  for (int e = 0; e < E; ++e) {
-    PmmMember m;
-    std::memset(&m, 0, sizeof(m));
-    m.cp = gps[e]->cp;
-    m.kinvy = gps[e]->dKinvY.p;
-    m.mean = gps[e]->mean;
-    std::memcpy(reinterpret_cast<unsigned char*>(gp.hStateIn.p) + (size_t)e * sizeof(PmmMember), &m, sizeof(m));
-  }
-  double* hc = gp.hStateIn.p + nTab;
-  for (size_t i = 0; i < rows; ++i)
-    for (int k = 0; k < dp; ++k) hc[i * dp + k] = (k < size) ? candidates[i * size + k] : (k < gp.d ? 1.0 : 0.0);
-  double* hx = hc + nCand;
+  const size_t nExtra = (size_t)T_steps + 2 * (size_t)size;
+  const size_t off = stage_pm_inputs(gps, num_fidelity, candidates, rows, nExtra);
+  double* hx = gp.hStateIn.p + off;
   for (int i = 0; i < T_steps; ++i) hx[i] = gd.pre_mult * std::pow((double)(i + 1), -gd.gamma);  // (the host's pow, as the host loop)
   std::copy(domain_bounds, domain_bounds + 2 * (size_t)size, hx + T_steps);
-  gp.dStateIn.upload(gp.hStateIn.p, nIn, s, true);
+  gp.dStateIn.upload(gp.hStateIn.p, off + nExtra, s, true);
   // the call's doubles, results first (one copy back): [out E (3 + dp) | means E C | trace E R T (size + 6)]
   const size_t tw = (size_t)size + kPmmTraceExtra;
   const size_t nOut = (size_t)E * (kPmmHead + dp), nMeans = (size_t)E * C;
@@ -368,16 +339,16 @@ void posterior_mean_members_minimize(const std::vector<GpDev*>& gps, int num_fid
   gp.pmmI.reserve((size_t)E);
   if (nTrace) MOE_HIP_CHECK(hipMemsetAsync(gp.pmmD.p + nOut + nMeans, 0, sizeof(double) * nTrace, s));
   PmmData T;
-  T.members = reinterpret_cast<const PmmMember*>(gp.dStateIn.p);
+  T.members = reinterpret_cast<const PmMember*>(gp.dStateIn.p);
   T.X = gp.dX.p;
   T.dX = gp.derivs;
   T.n = gp.n;
   T.size = size;
   PmmDescent D;
   D.start_index = gp.pmmI.p;
-  D.cand = gp.dStateIn.p + nTab;
+  D.cand = gp.dStateIn.p + (off - rows * dp);
   D.member_stride = per_member ? C : 0;
-  D.alpha0 = D.cand + nCand;
+  D.alpha0 = gp.dStateIn.p + off;
   D.bounds = D.alpha0 + T_steps;
   D.means = gp.pmmD.p + nOut;
   D.C = C;
@@ -389,15 +360,7 @@ void posterior_mean_members_minimize(const std::vector<GpDev*>& gps, int num_fid
   D.out = gp.pmmD.p;
   D.trace = nTrace ? gp.pmmD.p + nOut + nMeans : nullptr;
   double* dMeans = gp.pmmD.p + nOut;
-  switch (dp) {
-    case 4: launch_dp<4>(T, D, E, dMeans, gp.pmmI.p, s); break;
-    case 8: launch_dp<8>(T, D, E, dMeans, gp.pmmI.p, s); break;
-    case 12: launch_dp<12>(T, D, E, dMeans, gp.pmmI.p, s); break;
-    case 16: launch_dp<16>(T, D, E, dMeans, gp.pmmI.p, s); break;
-    case 24: launch_dp<24>(T, D, E, dMeans, gp.pmmI.p, s); break;
-    case 32: launch_dp<32>(T, D, E, dMeans, gp.pmmI.p, s); break;
-    default: throw Error(MOE_ERR_RUNTIME, "unsupported padded dimension");
-  }
+  dispatch_dp(dp, [&](auto DP) { launch_dp<DP>(T, D, E, dMeans, gp.pmmI.p, s); });
   const size_t nBack = nOut + ((means_out || trace_out) ? nMeans : 0) + nTrace;
   gp.hStateOut.reserve(nBack);
   gp.pmmD.download(gp.hStateOut.p, nBack, s);

@@ -31,14 +31,6 @@ namespace {
 
 constexpr int kPmPass = 16384;  // points per launch of pm_batch_kernel (moe_hip.h: moe_posterior_mean_mcmc_batch)
 
-// what a member contributes: its covariance, K^-1 (y - mean) [n (1 + g)] and the constant mean
-struct PmMember {
-  CovParams cp;
-  const double* kinvy;
-  double mean;
-};
-static_assert(sizeof(PmMember) % sizeof(double) == 0, "the member table travels inside a buffer of doubles");
-
 struct PmEnsemble {
   const PmMember* members;  // [E]
   const double* X;          // [n][DP]: the members share the data
@@ -267,41 +259,6 @@ __global__ void pm_pick_kernel(int S, int DP, const int* __restrict__ index, con
   for (int k = 0; k < DP; ++k) head[4 + k] = src[k];
 }
 
-void check_members(const std::vector<GpDev*>& gps, int num_fidelity) {
-  if (gps.empty()) throw Error(MOE_ERR_BOUNDS, "num_mcmc must be positive", 0, 1, 1e9);
-  const GpDev* g0 = gps[0];
-  for (const GpDev* g : gps) {
-    if (g == nullptr) throw Error(MOE_ERR_RUNTIME, "NULL GP handle in the MCMC ensemble");
-    if (g->d != g0->d || g->g != g0->g || !std::equal(g->derivs.idx, g->derivs.idx + g->g, g0->derivs.idx))
-      throw Error(MOE_ERR_INVALID_VALUE, "MCMC ensemble members must share dim and the observed-derivative list", g->d, g0->d, 0);
-    if (g->n != g0->n || g->X != g0->X)
-      throw Error(MOE_ERR_INVALID_VALUE, "MCMC ensemble members must share the sampled points", g->n, g0->n, 0);
-    if (g->device != g0->device) throw Error(MOE_ERR_INVALID_VALUE, "MCMC ensemble members must live on one device", g->device, g0->device, 0);
-  }
-  if (num_fidelity < 0 || num_fidelity >= g0->d) throw Error(MOE_ERR_BOUNDS, "num_fidelity out of range", num_fidelity, 0, g0->d - 1);
-}
-
-// the call's operands in the first member's pinned staging buffer, one copy down: [member table | points (padded, fidelity
-// coordinates 1) | extra doubles]; returns the offset (in doubles) of the extras
-size_t stage_inputs(const std::vector<GpDev*>& gps, int num_fidelity, const double* pts, int P, size_t extra) {
-  GpDev& gp = *gps[0];
-  const int E = (int)gps.size(), dp = gp.dp, size = gp.d - num_fidelity;
-  const size_t nTab = (size_t)E * sizeof(PmMember) / sizeof(double), nP = (size_t)P * dp;
-  gp.hStateIn.reserve(nTab + nP + extra);
-  for (int e = 0; e < E; ++e) {
-    PmMember m;
-    std::memset(&m, 0, sizeof(m));
-    m.cp = gps[e]->cp;
-    m.kinvy = gps[e]->dKinvY.p;
-    m.mean = gps[e]->mean;
-    std::memcpy(reinterpret_cast<unsigned char*>(gp.hStateIn.p) + (size_t)e * sizeof(PmMember), &m, sizeof(m));
-  }
-  double* hp = gp.hStateIn.p + nTab;
-  for (size_t i = 0; i < (size_t)P; ++i)
-    for (int k = 0; k < dp; ++k) hp[i * dp + k] = (k < size) ? pts[i * size + k] : (k < gp.d ? 1.0 : 0.0);
-  return nTab + nP;
-}
-
 PmEnsemble ensemble_of(const std::vector<GpDev*>& gps, int num_fidelity, const double* d_in) {
   const GpDev& gp = *gps[0];
   PmEnsemble T;
@@ -332,15 +289,7 @@ void batch_dp(const PmEnsemble& T, const double* dP, int P, bool want_grad, doub
 }
 
 void launch_batch(int dp, const PmEnsemble& T, const double* dP, int P, bool want_grad, double* dValue, double* dGrad, hipStream_t s) {
-  switch (dp) {
-    case 4: batch_dp<4>(T, dP, P, want_grad, dValue, dGrad, s); break;
-    case 8: batch_dp<8>(T, dP, P, want_grad, dValue, dGrad, s); break;
-    case 12: batch_dp<12>(T, dP, P, want_grad, dValue, dGrad, s); break;
-    case 16: batch_dp<16>(T, dP, P, want_grad, dValue, dGrad, s); break;
-    case 24: batch_dp<24>(T, dP, P, want_grad, dValue, dGrad, s); break;
-    case 32: batch_dp<32>(T, dP, P, want_grad, dValue, dGrad, s); break;
-    default: throw Error(MOE_ERR_RUNTIME, "unsupported padded dimension");
-  }
+  dispatch_dp(dp, [&](auto DP) { batch_dp<DP>(T, dP, P, want_grad, dValue, dGrad, s); });
 }
 
 // MOE_RECOMMEND_XLDS=1: the descent stages the training points in LDS where they fit (A/B runs; same bits either way)
@@ -365,22 +314,47 @@ void descent_dp(const PmEnsemble& T, const PmDescent& D, int S, hipStream_t s) {
 }
 
 void launch_descent(int dp, const PmEnsemble& T, const PmDescent& D, int S, hipStream_t s) {
-  switch (dp) {
-    case 4: descent_dp<4>(T, D, S, s); break;
-    case 8: descent_dp<8>(T, D, S, s); break;
-    case 12: descent_dp<12>(T, D, S, s); break;
-    case 16: descent_dp<16>(T, D, S, s); break;
-    case 24: descent_dp<24>(T, D, S, s); break;
-    case 32: descent_dp<32>(T, D, S, s); break;
-    default: throw Error(MOE_ERR_RUNTIME, "unsupported padded dimension");
-  }
+  dispatch_dp(dp, [&](auto DP) { descent_dp<DP>(T, D, S, s); });
 }
 
 }  // namespace
 
+void check_pm_members(const std::vector<GpDev*>& gps, int num_fidelity) {
+  if (gps.empty()) throw Error(MOE_ERR_BOUNDS, "num_mcmc must be positive", 0, 1, 1e9);
+  const GpDev* g0 = gps[0];
+  for (const GpDev* g : gps) {
+    if (g == nullptr) throw Error(MOE_ERR_RUNTIME, "NULL GP handle in the MCMC ensemble");
+    if (g->d != g0->d || g->g != g0->g || !std::equal(g->derivs.idx, g->derivs.idx + g->g, g0->derivs.idx))
+      throw Error(MOE_ERR_INVALID_VALUE, "MCMC ensemble members must share dim and the observed-derivative list", g->d, g0->d, 0);
+    if (g->n != g0->n || g->X != g0->X)
+      throw Error(MOE_ERR_INVALID_VALUE, "MCMC ensemble members must share the sampled points", g->n, g0->n, 0);
+    if (g->device != g0->device) throw Error(MOE_ERR_INVALID_VALUE, "MCMC ensemble members must live on one device", g->device, g0->device, 0);
+  }
+  if (num_fidelity < 0 || num_fidelity >= g0->d) throw Error(MOE_ERR_BOUNDS, "num_fidelity out of range", num_fidelity, 0, g0->d - 1);
+}
+
+size_t stage_pm_inputs(const std::vector<GpDev*>& gps, int num_fidelity, const double* pts, size_t rows, size_t extra) {
+  GpDev& gp = *gps[0];
+  const int E = (int)gps.size(), dp = gp.dp, size = gp.d - num_fidelity;
+  const size_t nTab = (size_t)E * sizeof(PmMember) / sizeof(double), nP = rows * dp;
+  gp.hStateIn.reserve(nTab + nP + extra);
+  for (int e = 0; e < E; ++e) {
+    PmMember m;
+    std::memset(&m, 0, sizeof(m));
+    m.cp = gps[e]->cp;
+    m.kinvy = gps[e]->dKinvY.p;
+    m.mean = gps[e]->mean;
+    std::memcpy(reinterpret_cast<unsigned char*>(gp.hStateIn.p) + (size_t)e * sizeof(PmMember), &m, sizeof(m));
+  }
+  double* hp = gp.hStateIn.p + nTab;
+  for (size_t i = 0; i < rows; ++i)
+    for (int k = 0; k < dp; ++k) hp[i * dp + k] = (k < size) ? pts[i * size + k] : (k < gp.d ? 1.0 : 0.0);
+  return nTab + nP;
+}
+
 void posterior_mean_mcmc_batch(const std::vector<GpDev*>& gps, int num_fidelity, const double* pts, int P, double* value_out,
                                double* grad_out) {
-  check_members(gps, num_fidelity);
+  check_pm_members(gps, num_fidelity);
   if (P < 1) throw Error(MOE_ERR_BOUNDS, "the number of points must be positive", P, 1, 1e9);
   if (pts == nullptr) throw Error(MOE_ERR_RUNTIME, "NULL argument");
   if (value_out == nullptr && grad_out == nullptr) return;
@@ -388,7 +362,7 @@ void posterior_mean_mcmc_batch(const std::vector<GpDev*>& gps, int num_fidelity,
   gp.use_device();
   hipStream_t s = gp.stream;
   const int size = gp.d - num_fidelity;
-  const size_t nIn = stage_inputs(gps, num_fidelity, pts, P, 0);
+  const size_t nIn = stage_pm_inputs(gps, num_fidelity, pts, P, 0);
   gp.dStateIn.upload(gp.hStateIn.p, nIn, s, true);
   const PmEnsemble T = ensemble_of(gps, num_fidelity, gp.dStateIn.p);
   const double* dP = gp.dStateIn.p + (nIn - (size_t)P * gp.dp);
@@ -407,7 +381,7 @@ void posterior_mean_mcmc_recommend(const std::vector<GpDev*>& gps, int num_fidel
                                    const double* domain_bounds, const double* candidates, int C, int S, double* point_out,
                                    double* value_out, int* screened_index_out, int* refined_out, double* candidate_values_out,
                                    double* end_points_out, double* path_out) {
-  check_members(gps, num_fidelity);
+  check_pm_members(gps, num_fidelity);
   GpDev& gp = *gps[0];
   gp.use_device();
   hipStream_t s = gp.stream;
@@ -416,7 +390,7 @@ void posterior_mean_mcmc_recommend(const std::vector<GpDev*>& gps, int num_fidel
   const int window = (nsa < 0 || nsa > T_steps) ? T_steps : (nsa == 0 ? 1 : nsa);  // _get_averaging_range (:435-442)
   // one copy down: [member table | candidates | a_i (T) | bounds (2 size)]
   const size_t nExtra = (size_t)T_steps + 2 * (size_t)size;
-  const size_t off = stage_inputs(gps, num_fidelity, candidates, C, nExtra);
+  const size_t off = stage_pm_inputs(gps, num_fidelity, candidates, C, nExtra);
   double* hx = gp.hStateIn.p + off;
   for (int i = 1; i <= T_steps; ++i) hx[i - 1] = gd.pre_mult * std::pow((double)i, -gd.gamma);
   std::copy(domain_bounds, domain_bounds + 2 * (size_t)size, hx + T_steps);

@@ -86,6 +86,9 @@ def _check_screen(case):
         one = api.minimize_member_means([gps[e]], (cand[e] if per_member else cand)[c:c + 1], ONE_STEP, _unit(size), num_fidelity=nf,
                                         want_means=True)
         assert one["means"][0, 0] == res["means"][e, c]
+        # ... and the bits of the GP's own posterior-mean query: mean_kernel makes the same evaluation in the same order
+        point = np.concatenate([(cand[e] if per_member else cand)[c], np.ones(nf)])
+        assert res["means"][e, c] == gps[e].mean(point[None])[0]
         assert all(np.array_equal(u, g.mean(probe)) for u, g in zip(before, gps))  # the handles answer as before
 
 
