@@ -325,6 +325,29 @@ class DeviceGP(object):
             return index, points, kept.value, mean, std
         return index, points, kept.value
 
+    def kg_discrete(self, discrete, points, best_so_far, num_fidelity=0, want_grad=True, want_active=False):
+        """moe_gp_kg_discrete: the exact discretised one-point knowledge gradient of points [C][dim] over the discrete set
+        [A][dim - num_fidelity] (a lower bound of the continuous knowledge gradient), for a GP without derivative observations.
+        Returns kg [C], with want_grad (kg, grad [C][dim]), with want_active the number of lines on the envelope [C] behind them.
+        SingularMatrixException(1, i) for the first candidate i with Sigma_n(x, x) + noise <= 1e-16."""
+        nf = int(num_fidelity)
+        size = self.d - nf
+        if not 0 < size <= self.d:
+            size = self.d  # (the library refuses num_fidelity; the shapes only have to be readable)
+        disc, dcp = _d(discrete)
+        pts, pp = _d(points)
+        A = disc.reshape(-1, size).shape[0]
+        C_ = pts.reshape(-1, self.d).shape[0]
+        kg = np.zeros(max(C_, 1))
+        grad = np.zeros((max(C_, 1), self.d)) if want_grad else None
+        active = np.zeros(max(C_, 1), dtype=np.int32) if want_active else None
+        err = _lib.MoeError()
+        _check(_lib.load().moe_gp_kg_discrete(self._h, nf, dcp, A, pp, C_, float(best_so_far), 1 if want_grad else 0,
+                                              kg.ctypes.data_as(dp), grad.ctypes.data_as(dp) if want_grad else None,
+                                              active.ctypes.data_as(ip) if want_active else None, C.byref(err)), err)
+        out = (kg,) + ((grad,) if want_grad else ()) + ((active,) if want_active else ())
+        return out[0] if len(out) == 1 else out
+
     def mix_covariance(self, pts, derivs2=()):
         pts, pp = _d(pts)
         k = pts.reshape(-1, self.d).shape[0]
@@ -785,6 +808,24 @@ def posterior_mean_mcmc(gps, points, num_fidelity=0, want_grad=False):
     _check(_lib.load().moe_posterior_mean_mcmc_batch(arr, E, int(num_fidelity), pp, P, value.ctypes.data_as(dp),
                                                      grad.ctypes.data_as(dp) if want_grad else None, C.byref(err)), err)
     return (value, grad) if want_grad else value
+
+
+def kg_discrete_mcmc(gps, discrete_all, points, best_so_far_all, num_fidelity=0, want_grad=True):
+    """The ensemble average of DeviceGP.kg_discrete, every member with its own discrete set discrete_all[e] [A_e][dim - num_fidelity]
+    and best value best_so_far_all[e], as KG-MCMC averages its members: the members' results are added in member order and divided
+    by their number.  Returns kg [C], with want_grad (kg, grad [C][dim])."""
+    members = list(gps.gps) if isinstance(gps, DeviceGPMCMC) else list(gps)
+    if not members or len(discrete_all) != len(members) or len(best_so_far_all) != len(members):
+        raise BoundsException("one discrete set and one best value per ensemble member", len(discrete_all), len(members), len(members))
+    kg = grad = None
+    for g, disc, best in zip(members, discrete_all, best_so_far_all):
+        res = g.kg_discrete(disc, points, best, num_fidelity=num_fidelity, want_grad=want_grad)
+        k, gr = res if want_grad else (res, None)
+        kg = k if kg is None else kg + k
+        if want_grad:
+            grad = gr if grad is None else grad + gr
+    kg = kg / len(members)
+    return (kg, grad / len(members)) if want_grad else kg
 
 
 def recommend(gps, candidates, gd_params, domain_bounds, num_fidelity=0, num_starts=1, want_values=False, want_path=False):

@@ -274,6 +274,20 @@ int moe_gp_lcb_select(const moe_gp_t* gp_c, const double* candidates, int num_ca
 
 int moe_lcb_pass_size(int num_rows, int num_candidates) { return moe::lcb_pass_size(num_rows, num_candidates); }
 
+int moe_gp_kg_discrete(const moe_gp_t* gp_c, int num_fidelity, const double* discrete, int num_discrete, const double* points,
+                       int num_points, double best_so_far, int want_grad, double* kg, double* grad, int* num_active,
+                       moe_error_t* err) {
+  return guarded(err, [&] {
+    moe::check_kg_discrete_shapes(num_fidelity, num_discrete, num_points);  // (what needs no handle, before the handle is touched)
+    std::unique_lock<std::mutex> lk;
+    moe::GpDev& gp = lock_gp(gp_c, lk);
+    moe::kg_discrete_on_device(gp, num_fidelity, discrete, num_discrete, points, num_points, best_so_far, want_grad != 0, kg, grad,
+                               num_active);
+  });
+}
+
+int moe_kg1_pass_size(int num_rows, int num_discrete) { return moe::kg1_pass_size(num_rows, num_discrete); }
+
 int moe_gp_grad_variance(const moe_gp_t* gp_c, const double* pts, int num_pts, int num_derivs, double* out,
                          moe_error_t* err) {
   return guarded(err, [&] {

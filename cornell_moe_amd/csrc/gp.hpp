@@ -64,6 +64,9 @@ struct GpDev {
   DevBuf<int> lcbI;
   // leave-one-out predictions and gradient (loo.hip): K^-1, the scaled columns B, M and the per-row vectors
   DevBuf<double> looD;
+  // the discretised one-point knowledge gradient (kg1.hip): the call's doubles (results first: one copy back) and integers
+  DevBuf<double> kg1D;
+  DevBuf<int> kg1I;
   // the ensemble-averaged posterior mean and the recommendation (recommend.hip; held by the ensemble's first member): the call's
   // doubles (results first: one copy back) and the start indices
   DevBuf<double> recD;
@@ -209,6 +212,13 @@ void mean_std_on_device(GpDev& gp, const double* pts, int C, double* mean_out, d
 // points_out[q][d], mean_out[C], std_out[C], num_kept_out may be NULL.
 void lcb_select_on_device(GpDev& gp, const double* pts, int C, int q, int* index_out, double* points_out, double* mean_out,
                           double* std_out, int* num_kept_out);
+// kg1.hip: the exact discretised one-point knowledge gradient (moe_gp_kg_discrete) of C candidates [C][d] over A discrete points
+// [A][d - num_fidelity]; grad_out [C][d] (want_grad) and nact_out [C] may be NULL.  check_kg_discrete_shapes: the limits that need no
+// GP (MOE_ERR_BOUNDS).  Candidates go through in passes of kg1_pass_size(N, A).
+int kg1_pass_size(int N, int A);
+void check_kg_discrete_shapes(int num_fidelity, int A, int C);
+void kg_discrete_on_device(GpDev& gp, int num_fidelity, const double* discrete, int A, const double* pts, int C, double best,
+                           bool want_grad, double* kg_out, double* grad_out, int* nact_out);
 // loo.hip: leave-one-out cross-validation on the GP's current factorisation, every one of the N = n (1 + g) scalar observations left
 // out by itself.  mean_out / var_out [n][1 + g]: the LOO predictive mean (function values in the caller's units) and variance.
 void loo_predict_on_device(GpDev& gp, double* mean_out, double* var_out);

@@ -178,6 +178,32 @@ int moe_lcb_pass_size(int num_rows, int num_candidates);
  * Memory: 8 num_candidates (N + (num_to_sample - 1)(1 + num_derivatives) + 5) bytes besides a pass's K*. */
 int moe_gp_lcb_select(const moe_gp_t* gp, const double* candidates, int num_candidates, int num_to_sample, int* index_out,
                       double* points_out, double* mean_out, double* std_out, int* num_kept_out, moe_error_t* err);
+/* The exact discretised one-point knowledge gradient (Frazier, Powell & Dayanik 2009) of num_points candidates [dim] over ONE
+ * discrete set of num_discrete points [dim - num_fidelity], for a GP WITHOUT derivative observations; no counterpart in the
+ * reference's boundary (its knowledge gradient is Monte Carlo at every q).  With x^ = the candidate with its last num_fidelity
+ * coordinates set to 1, the discrete points padded the same way, Z = {x^} u discrete, mu_n / Sigma_n the posterior mean (what
+ * moe_gp_mean returns) and covariance and sigma^2 = noise_variance[0]:
+ *   s^2(x) = Sigma_n(x, x) + sigma^2,  a_z = mu_n(z),  b_z(x) = Sigma_n(z, x) / s(x)
+ *   kg[i] = min(best_so_far, mu_n(x^_i)) - E[min_{z in Z} (a_z + b_z(x_i) Z)],  Z ~ N(0, 1)
+ * -- the fantasy of gpp_knowledge_gradient_optimization.cpp:83-107 / :298-316 conditioned on with noise sigma^2, evaluated
+ * exactly: the lines are sorted by slope, the lower envelope is scanned, and the segments' normal probabilities are summed.  It is
+ * a LOWER BOUND of the continuous knowledge gradient the Monte-Carlo evaluators estimate (their inner minimum runs over the
+ * whole domain, not over Z).  grad[i][dim] (want_grad != 0) is the gradient in ALL dim coordinates of the candidate, exact by the
+ * envelope theorem away from ties; num_active[i] (may be NULL) the number of lines on the envelope.  Among lines of equal slope
+ * the smallest intercept survives and among exact duplicates the lowest index (x^ before the discrete points), so duplicates in
+ * the set, x^ in the set and a permutation of the set leave every bit of kg unchanged; a candidate's bits do not depend on how
+ * many candidates share the call (passes of moe_kg1_pass_size(N, num_discrete) candidates).
+ * One copy down, one wait, one copy back; the handle is never modified.
+ * Limits (MOE_ERR_BOUNDS, checked in this order before the device is touched): num_points >= 1; 1 <= num_discrete <= 4095 (the
+ * num_discrete + 1 lines of a candidate are sorted in the LDS of one workgroup, 20 bytes each); num_fidelity >= 0; then, with the
+ * handle: num_fidelity < dim; num_derivatives == 0 -- with derivative observations the fantasy has 1 + num_derivatives dimensions
+ * and the quantity is not a minimum of lines (payload (num_derivatives, 0, 0)).
+ * MOE_ERR_SINGULAR, payload (1, i): the first candidate i with s^2 <= 1e-16 (the pivot rule), reported after the wait.
+ * Memory: 8 N num_discrete bytes for the set, and per pass 8 P (6 N + 2.5 num_discrete) bytes, P = the pass size. */
+int moe_gp_kg_discrete(const moe_gp_t* gp, int num_fidelity, const double* discrete, int num_discrete, const double* points,
+                       int num_points, double best_so_far, int want_grad, double* kg, double* grad, int* num_active,
+                       moe_error_t* err);
+int moe_kg1_pass_size(int num_rows, int num_discrete);
 /* compute_grad_variance_of_points -> ComputeGradVarianceOfPoints (gpp_math.cpp:1359-1373); out[num_derivs][m][m][dim] */
 int moe_gp_grad_variance(const moe_gp_t* gp, const double* pts, int num_pts, int num_derivs, double* out, moe_error_t* err);
 /* compute_grad_cholesky_variance_of_points -> ComputeGradCholeskyVarianceOfPoints (gpp_math.cpp:1454-1474) */
