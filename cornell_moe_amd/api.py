@@ -828,6 +828,75 @@ def kg_discrete_mcmc(gps, discrete_all, points, best_so_far_all, num_fidelity=0,
     return (kg, grad / len(members)) if want_grad else kg
 
 
+def _kg_discrete_members(gps, discrete_all, best_so_far_all, num_fidelity):
+    """(handles, count, dim, members kept alive, sets back to back, their sizes, best values) of the ensemble forms of kg_discrete;
+    a single DeviceGP counts as a list of one"""
+    if isinstance(gps, DeviceGP):
+        gps = [gps]
+    arr, E, d, keep = _ensemble_handles(gps)
+    if E == 0 or len(discrete_all) != E or len(best_so_far_all) != E:
+        raise BoundsException("one discrete set and one best value per ensemble member", len(discrete_all), E, E)
+    size = d - int(num_fidelity)
+    if not 0 < size <= d:
+        size = d  # (the library refuses num_fidelity; the shapes only have to be readable)
+    sets = [np.ascontiguousarray(s, dtype=np.float64).reshape(-1, size) for s in discrete_all]
+    disc = np.ascontiguousarray(np.vstack(sets))
+    counts = np.ascontiguousarray([s.shape[0] for s in sets], dtype=np.int32)
+    best = np.ascontiguousarray(best_so_far_all, dtype=np.float64).ravel()
+    return arr, E, d, keep, disc, counts, best
+
+
+def kg_discrete_ensemble(gps, discrete_all, points, best_so_far_all, num_fidelity=0, want_grad=True):
+    """moe_kg_discrete_mcmc: what kg_discrete_mcmc returns, bit for bit, in one device call for the whole ensemble (one upload, one
+    stream, one wait; every kernel launched once for all members where their launches line up).  gps: a DeviceGPMCMC, a list of
+    DeviceGP (they need not share their sampled points) or one DeviceGP.  Returns kg [C], with want_grad (kg, grad [C][dim]).
+    SingularMatrixException(e, i): member e, candidate i."""
+    arr, E, d, keep, disc, counts, best = _kg_discrete_members(gps, discrete_all, best_so_far_all, num_fidelity)
+    pts, pp = _d(points)
+    C_ = pts.reshape(-1, d).shape[0]
+    kg = np.zeros(max(C_, 1))
+    grad = np.zeros((max(C_, 1), d)) if want_grad else None
+    err = _lib.MoeError()
+    _check(_lib.load().moe_kg_discrete_mcmc(arr, E, int(num_fidelity), disc.ctypes.data_as(dp), counts.ctypes.data_as(ip),
+                                            best.ctypes.data_as(dp), pp, C_, 1 if want_grad else 0, kg.ctypes.data_as(dp),
+                                            grad.ctypes.data_as(dp) if want_grad else None, C.byref(err)), err)
+    return (kg, grad) if want_grad else kg
+
+
+def kg_discrete_multistart(gps, gd_params, bounds, discrete_all, best_so_far_all, starts, num_fidelity=0, gradient_ascent=True,
+                           want_path=False):
+    """moe_kg_discrete_mcmc_multistart: one suggestion by the ensemble-averaged discretised knowledge gradient -- the value at
+    every start [S][dim], the 20 best kept, restarted gradient ascent on all of them on the device, the value at every end point,
+    the best one returned.  Returns a dict: point [dim], value, found, start_values [S], and with gradient_ascent kept_index [K],
+    end_points [K][dim], end_values [K], steps_taken [K] (None without), with want_path path [K][restarts steps + 1][dim]."""
+    arr, E, d, keep, disc, counts, best = _kg_discrete_members(gps, discrete_all, best_so_far_all, num_fidelity)
+    g = DeviceGP._gd(gd_params)
+    bounds, bp = _d(bounds)
+    starts, sp = _d(starts)
+    S = starts.reshape(-1, d).shape[0]
+    K = max(min(S, 20), 1)
+    rows = max(g.max_num_restarts, 0) * max(g.max_num_steps, 0) + 1
+    point = np.zeros(d)
+    start_values = np.zeros(max(S, 1))
+    kept = np.zeros(K, dtype=np.int32)
+    ends, end_values = np.zeros((K, d)), np.zeros(K)
+    steps = np.zeros(K, dtype=np.int32)
+    path = np.zeros((K, rows, d)) if (want_path and gradient_ascent) else None
+    value, found = C.c_double(0.0), C.c_int(0)
+    err = _lib.MoeError()
+    _check(_lib.load().moe_kg_discrete_mcmc_multistart(
+        arr, E, int(num_fidelity), C.byref(g), bp, disc.ctypes.data_as(dp), counts.ctypes.data_as(ip), best.ctypes.data_as(dp), sp, S,
+        1 if gradient_ascent else 0, point.ctypes.data_as(dp), C.byref(value), C.byref(found), start_values.ctypes.data_as(dp),
+        kept.ctypes.data_as(ip), ends.ctypes.data_as(dp), end_values.ctypes.data_as(dp),
+        path.ctypes.data_as(dp) if path is not None else None, steps.ctypes.data_as(ip), C.byref(err)), err)
+    out = {"point": point, "value": value.value, "found": bool(found.value), "start_values": start_values,
+           "kept_index": kept if gradient_ascent else None, "end_points": ends if gradient_ascent else None,
+           "end_values": end_values if gradient_ascent else None, "steps_taken": steps if gradient_ascent else None}
+    if want_path:
+        out["path"] = path
+    return out
+
+
 def recommend(gps, candidates, gd_params, domain_bounds, num_fidelity=0, num_starts=1, want_values=False, want_path=False):
     """moe_posterior_mean_mcmc_recommend: screen the candidates [C][dim - num_fidelity] on the ensemble-averaged posterior mean,
     descend from the num_starts best (the reference's Python gradient descent, on the device), keep the screened candidate unless

@@ -67,6 +67,10 @@ struct GpDev {
   // the discretised one-point knowledge gradient (kg1.hip): the call's doubles (results first: one copy back) and integers
   DevBuf<double> kg1D;
   DevBuf<int> kg1I;
+  // its ensemble forms (kg1_opt.hip; held by the ensemble's first member): the call's doubles (results first: one copy back) and
+  // integers (the members' failure words first)
+  DevBuf<double> kg1oD;
+  DevBuf<int> kg1oI;
   // the ensemble-averaged posterior mean and the recommendation (recommend.hip; held by the ensemble's first member): the call's
   // doubles (results first: one copy back) and the start indices
   DevBuf<double> recD;
@@ -219,6 +223,45 @@ int kg1_pass_size(int N, int A);
 void check_kg_discrete_shapes(int num_fidelity, int A, int C);
 void kg_discrete_on_device(GpDev& gp, int num_fidelity, const double* discrete, int A, const double* pts, int C, double best,
                            bool want_grad, double* kg_out, double* grad_out, int* nact_out);
+// The same in the parts the ensemble forms (kg1_opt.hip) share with it.  Kg1Member: where one GP's set, per-pass scratch and
+// results live for a call of at most C candidates -- everything inside the GP's own kg1D / kg1I (results first: [fail | kg C |
+// active C | grad C d]), dE and dEK, so that the members of an ensemble never share a buffer.
+struct Kg1Member {
+  GpDev* gp = nullptr;
+  int nf = 0, A = 0, n2 = 0, C = 0, per_pass = 0, widest = 0;
+  bool with_grad = false, fid = false;
+  double best = 0.0;
+  const double* dPA = nullptr;  // the set [A][dp], fidelity coordinates 1 (the caller's upload)
+  double *dOut = nullptr, *dKg = nullptr, *dAct = nullptr, *dGrad = nullptr;
+  double *dVA = nullptr, *dAA = nullptr;  // V_A = L^-1 K(X, A) [N][A], a_A = mu_n(A)
+  double *dVx = nullptr, *dVh = nullptr, *dT = nullptr, *dU = nullptr, *dMuh = nullptr, *dS2 = nullptr, *dB0 = nullptr, *dS = nullptr,
+         *dHw = nullptr, *dScal = nullptr;
+  int *iFail = nullptr, *iHid = nullptr;
+  size_t out_doubles() const { return 1 + 2 * (size_t)C + (with_grad ? (size_t)C * gp->d : 0); }
+};
+// the handle's checks of moe_gp_kg_discrete (num_fidelity < dim, no derivative observations), the buffers and their layout; nothing
+// is launched.  fail (may be NULL: the member's own word) is where a candidate failing the pivot rule leaves its index.
+void check_kg_discrete_member(const GpDev& gp, int num_fidelity);
+Kg1Member kg1_member(GpDev& gp, int num_fidelity, int A, int C, double best, bool with_grad, int* fail = nullptr);
+// "set, once": K(X, A), V_A, a_A on stream s (m.dPA must be set)
+void kg1_prepare_set(const Kg1Member& m, hipStream_t s);
+// nc <= m.widest candidates Px [nc][dp] (Ph: the same with fidelity coordinates 1; Px itself without fidelity) already on the
+// device -> m.dKg / m.dAct / m.dGrad [c0 ..), on stream s.  No host memory is touched and nothing waits: every launch can be
+// recorded (launch.hpp).  with_grad = false leaves the gradient out (the value's bits are the same).
+void kg1_eval_pass(const Kg1Member& m, const double* Px, const double* Ph, int nc, int c0, bool with_grad, hipStream_t s);
+// ... the same for C <= m.C candidates, pass after pass of m.per_pass
+void kg1_eval_points(const Kg1Member& m, const double* Px, const double* Ph, int C, bool with_grad, hipStream_t s);
+void kg1_clear_fail(int* fail, int count, hipStream_t s);  // INT_MAX: no candidate has failed
+// kg1_opt.hip: the ensemble average (moe_kg_discrete_mcmc) and its multistart ascent (moe_kg_discrete_mcmc_multistart); the caller
+// has made the checks that need no handle (check_kg_discrete_ensemble_shapes).  discrete_all: the members' sets back to back.
+void check_kg_discrete_ensemble_shapes(int num_mcmc, int num_fidelity, const int* num_discrete, int num_points);
+void kg_discrete_mcmc_on_device(const std::vector<GpDev*>& gps, int num_fidelity, const double* discrete_all, const int* num_discrete,
+                                const double* best_so_far, const double* pts, int C, bool want_grad, double* kg_out, double* grad_out);
+void kg_discrete_mcmc_multistart(const std::vector<GpDev*>& gps, int num_fidelity, const moe_gd_params_t& outer,
+                                 const double* domain_bounds, const double* discrete_all, const int* num_discrete,
+                                 const double* best_so_far, const double* starts, int num_starts, int do_gradient_ascent,
+                                 double* best_point, double* best_value, int* found, double* start_values, int* kept_index,
+                                 double* end_points, double* end_values, double* path, int* steps_taken);
 // loo.hip: leave-one-out cross-validation on the GP's current factorisation, every one of the N = n (1 + g) scalar observations left
 // out by itself.  mean_out / var_out [n][1 + g]: the LOO predictive mean (function values in the caller's units) and variance.
 void loo_predict_on_device(GpDev& gp, double* mean_out, double* var_out);

@@ -69,6 +69,22 @@ void set_reference_quirks(int on);  // < 0: back to the environment's setting
 bool ensemble_launches();
 void set_ensemble_launches(int on);  // < 0: back to the environment's setting (MOE_ENS_LAUNCH)
 void ensemble_launch_stats(long long* out4);
+void ensemble_stats_add(int which, long long count);  // which: the index into moe_ensemble_launch_stats' four counters
+// The recordings of the members' chains zipped (mcmc.hip), in two halves for a caller that issues ONE recording many times
+// (kg1_opt.hip: every step of an ascent): ensemble_zip decides position by position how it is issued and sends the argument tables
+// through the arena on stream z (false, nothing sent: the recordings do not line up or too few positions merge);
+// ensemble_issue launches, reading those tables.  The arena must not be written between the two.
+struct EnsArena {
+  PinnedBuf<unsigned char>& host;
+  DevBuf<unsigned char>& dev;
+};
+struct EnsZip {
+  std::vector<char> how;    // per position: 0 member after member, 1 ensemble twin, 2 copy kernel
+  std::vector<size_t> off;  // the position's table inside the arena
+  int merged = 0;
+};
+bool ensemble_zip(const std::vector<Recorder>& recs, hipStream_t z, EnsArena& arena, EnsZip* zip);
+void ensemble_issue(const std::vector<Recorder>& recs, const EnsZip& zip, hipStream_t z, EnsArena& arena);
 // how many ensemble members share the launches being recorded on this thread (1: none) -- kg_launch sizes its MC grid for its share
 int ensemble_members_hint();
 void set_ensemble_members_hint(int members);

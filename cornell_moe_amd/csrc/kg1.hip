@@ -14,6 +14,10 @@
 //     gradient t = sum_j w_j V_{z_j} over the envelope's lines, two columns per     kg1_t_kernel, launch_tri_gemm_cols ('T'),
 //              candidate through L^-T, then one pass over X per candidate           kg1_grad_kernel                                      2 N^2 C
 //
+// The host side comes in parts that kg1_opt.hip (the ensemble average and its multistart ascent) shares: kg1_member (checks, buffers,
+// layout), kg1_prepare_set ("once"), kg1_eval_pass / kg1_eval_points (a pass of candidates already in device memory, results left
+// there, every launch recordable: the five kernels of this file have the body + wrapper form of launch.hpp), then the copy back.
+//
 // Bits.  The triangular products take the split-K family at every column count (N < 128: the tiled kernel in chunks that never reach
 // its other branch), the slopes are serial fused multiply-add chains over the rows in row order, the slope of x^'s own line is the
 // same chain, and the envelope's sums run in the sorted order of the lines.  So a candidate's result does not depend on how many
@@ -47,71 +51,77 @@ constexpr int kScal = 4;               // per candidate: P_0, w_0, sum_j w_j b_j
 
 // one wavefront per candidate: s^2 = k(x, x) + noise - |v_x|^2 with the lanes striding over the rows, and by lane 0 the slope
 // numerator of x^'s own line, Sigma_n(x^, x) = k(x^, x) - v_x^ . v_x, as the chain kg1_slope_kernel runs for the lines of A
-__global__ __launch_bounds__(256) void kg1_cand_kernel(int N, int ncols, int col0, int dp, const CovParams cp, double noise,
-                                                       const double* __restrict__ Px, const double* __restrict__ Ph,
-                                                       const double* __restrict__ Vx, const double* __restrict__ Vh,
-                                                       double* __restrict__ s2_out, double* __restrict__ b0_out, int* __restrict__ fail) {
-  const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (c >= ncols) return;
-  const double* vx = Vx + (size_t)c * N;
-  double ss = 0.0;
-  for (int r = lane; r < N; r += 64) ss = fma(vx[r], vx[r], ss);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);
-  if (lane != 0) return;
-  const double* vh = Vh + (size_t)c * N;
-  double dot = 0.0;
-  for (int r = 0; r < N; ++r) dot = fma(vh[r], vx[r], dot);
-  const PointDiff df{Ph + (size_t)c * dp, Px + (size_t)c * dp};
-  const double var = (radial_scalars(cp.type, cp.alpha, 0.0).base - ss) + noise;
-  s2_out[c] = var;
-  b0_out[c] = pair_radial(cp, df, dp).base - dot;
-  if (!(var > kPivotMin)) atomicMin(fail, col0 + c);  // the first failing candidate of the call
+struct kg1_cand_kernel_body {
+  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, int N, int ncols, int col0, int dp, const CovParams& cp, double noise, const double* __restrict__ Px, const double* __restrict__ Ph, const double* __restrict__ Vx, const double* __restrict__ Vh, double* __restrict__ s2_out, double* __restrict__ b0_out, int* __restrict__ fail) {
+    const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (c >= ncols) return;
+    const double* vx = Vx + (size_t)c * N;
+    double ss = 0.0;
+    for (int r = lane; r < N; r += 64) ss = fma(vx[r], vx[r], ss);
+  #pragma unroll
+    for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);
+    if (lane != 0) return;
+    const double* vh = Vh + (size_t)c * N;
+    double dot = 0.0;
+    for (int r = 0; r < N; ++r) dot = fma(vh[r], vx[r], dot);
+    const PointDiff df{Ph + (size_t)c * dp, Px + (size_t)c * dp};
+    const double var = (radial_scalars(cp.type, cp.alpha, 0.0).base - ss) + noise;
+    s2_out[c] = var;
+    b0_out[c] = pair_radial(cp, df, dp).base - dot;
+    if (!(var > kPivotMin)) atomicMin(fail, col0 + c);  // the first failing candidate of the call
+  }
+};
+__global__ __launch_bounds__(256) void kg1_cand_kernel(int N, int ncols, int col0, int dp, const CovParams cp, double noise, const double* __restrict__ Px, const double* __restrict__ Ph, const double* __restrict__ Vx, const double* __restrict__ Vh, double* __restrict__ s2_out, double* __restrict__ b0_out, int* __restrict__ fail) {
+  kg1_cand_kernel_body::run(MOE_VBLOCK, MOE_VGRID, nullptr, N, ncols, col0, dp, cp, noise, Px, Ph, Vx, Vh, s2_out, b0_out, fail);
 }
 
 // S[z + c A] = V_A[:, z] . V_x[:, c]: 64 x 64 outputs per workgroup, 4 x 4 per thread, the rows staged 32 at a time.  Every output is
 // ONE accumulator that takes its products in row order (rows past N add exact zeros).
-__global__ __launch_bounds__(256) void kg1_slope_kernel(int N, int A, int nc, const double* __restrict__ VA, const double* __restrict__ Vx,
-                                                        double* __restrict__ S) {
-  __shared__ double As[32][65];
-  __shared__ double Bs[32][65];
-  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4, rr = tid & 31, q = tid >> 5;
-  const int z0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
-  double acc[4][4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = 0.0;
-  for (int r0 = 0; r0 < N; r0 += 32) {
-    const int r = r0 + rr;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int col = q + 8 * i;
-      As[rr][col] = (r < N && z0 + col < A) ? VA[r + (size_t)(z0 + col) * N] : 0.0;
-      Bs[rr][col] = (r < N && c0 + col < nc) ? Vx[r + (size_t)(c0 + col) * N] : 0.0;
+struct kg1_slope_kernel_body {
+  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, int N, int A, int nc, const double* __restrict__ VA, const double* __restrict__ Vx, double* __restrict__ S) {
+    __shared__ double As[32][65];
+    __shared__ double Bs[32][65];
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4, rr = tid & 31, q = tid >> 5;
+    const int z0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
+    double acc[4][4];
+  #pragma unroll
+    for (int a = 0; a < 4; ++a)
+  #pragma unroll
+      for (int b = 0; b < 4; ++b) acc[a][b] = 0.0;
+    for (int r0 = 0; r0 < N; r0 += 32) {
+      const int r = r0 + rr;
+  #pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int col = q + 8 * i;
+        As[rr][col] = (r < N && z0 + col < A) ? VA[r + (size_t)(z0 + col) * N] : 0.0;
+        Bs[rr][col] = (r < N && c0 + col < nc) ? Vx[r + (size_t)(c0 + col) * N] : 0.0;
+      }
+      __syncthreads();
+  #pragma unroll 8
+      for (int kk = 0; kk < 32; ++kk) {
+        double fa[4], fb[4];
+  #pragma unroll
+        for (int a = 0; a < 4; ++a) fa[a] = As[kk][tx + 16 * a];
+  #pragma unroll
+        for (int b = 0; b < 4; ++b) fb[b] = Bs[kk][ty + 16 * b];
+  #pragma unroll
+        for (int a = 0; a < 4; ++a)
+  #pragma unroll
+          for (int b = 0; b < 4; ++b) acc[a][b] = fma(fa[a], fb[b], acc[a][b]);
+      }
+      __syncthreads();
     }
-    __syncthreads();
-#pragma unroll 8
-    for (int kk = 0; kk < 32; ++kk) {
-      double fa[4], fb[4];
-#pragma unroll
-      for (int a = 0; a < 4; ++a) fa[a] = As[kk][tx + 16 * a];
-#pragma unroll
-      for (int b = 0; b < 4; ++b) fb[b] = Bs[kk][ty + 16 * b];
-#pragma unroll
-      for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = fma(fa[a], fb[b], acc[a][b]);
-    }
-    __syncthreads();
+  #pragma unroll
+    for (int a = 0; a < 4; ++a)
+  #pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        const int z = z0 + tx + 16 * a, c = c0 + ty + 16 * b;
+        if (z < A && c < nc) S[z + (size_t)c * A] = acc[a][b];
+      }
   }
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const int z = z0 + tx + 16 * a, c = c0 + ty + 16 * b;
-      if (z < A && c < nc) S[z + (size_t)c * A] = acc[a][b];
-    }
+};
+__global__ __launch_bounds__(256) void kg1_slope_kernel(int N, int A, int nc, const double* __restrict__ VA, const double* __restrict__ Vx, double* __restrict__ S) {
+  kg1_slope_kernel_body::run(MOE_VBLOCK, MOE_VGRID, nullptr, N, A, nc, VA, Vx, S);
 }
 
 // the order of the lines: larger slope first, then smaller intercept, then lower index
@@ -144,264 +154,264 @@ __device__ __forceinline__ double kg1_block_sum(double v, double* s_red) {
 // sorted run survives, so the smallest intercept and among exact duplicates the lowest index); then every thread takes segments:
 //   P_j = Phi(c_j) - Phi(c_j-1),  w_j = phi(c_j-1) - phi(c_j),  E[min] = sum_j a_j P_j + b_j w_j
 // hull_w / hull_id [nc][A + 1]: the envelope's w_j and line indices in slope order; scal [nc][kScal].
-__global__ __launch_bounds__(256) void kg1_envelope_kernel(int A, int n2, int dp, int col0, const CovParams cp, double best,
-                                                           const double* __restrict__ PA, const double* __restrict__ Px,
-                                                           const double* __restrict__ aA, const double* __restrict__ muh,
-                                                           const double* __restrict__ s2, const double* __restrict__ b0,
-                                                           const double* __restrict__ S, double* __restrict__ kg_out,
-                                                           double* __restrict__ nact_out, double* __restrict__ hull_w,
-                                                           int* __restrict__ hull_id, double* __restrict__ scal) {
-  extern __shared__ double kg1_smem[];
-  __shared__ double s_red[4];
-  __shared__ double s_line0[2];
-  __shared__ int s_count;
-  double* sb = kg1_smem;
-  double* sa = kg1_smem + n2;
-  int* si = reinterpret_cast<int*>(kg1_smem + 2 * (size_t)n2);
-  const int c = blockIdx.x, tid = threadIdx.x;
-  const double var = s2[c];
-  if (!(var > kPivotMin)) {  // (the call fails on this candidate; the gradient kernels see no lines)
+struct kg1_envelope_kernel_body {
+  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, int A, int n2, int dp, int col0, const CovParams& cp, double best, const double* __restrict__ PA, const double* __restrict__ Px, const double* __restrict__ aA, const double* __restrict__ muh, const double* __restrict__ s2, const double* __restrict__ b0, const double* __restrict__ S, double* __restrict__ kg_out, double* __restrict__ nact_out, double* __restrict__ hull_w, int* __restrict__ hull_id, double* __restrict__ scal) {
+    extern __shared__ double kg1_smem[];
+    __shared__ double s_red[4];
+    __shared__ double s_line0[2];
+    __shared__ int s_count;
+    double* sb = kg1_smem;
+    double* sa = kg1_smem + n2;
+    int* si = reinterpret_cast<int*>(kg1_smem + 2 * (size_t)n2);
+    const int c = blockIdx.x, tid = threadIdx.x;
+    const double var = s2[c];
+    if (!(var > kPivotMin)) {  // (the call fails on this candidate; the gradient kernels see no lines)
+      if (tid == 0) {
+        kg_out[col0 + c] = NAN;
+        nact_out[col0 + c] = 0.0;
+        for (int k = 0; k < kScal; ++k) scal[(size_t)c * kScal + k] = 0.0;
+      }
+      return;
+    }
+    const double s = sqrt(var);
+    const double* x = Px + (size_t)c * dp;
+    for (int i = tid; i < n2; i += 256) {
+      double b = -INFINITY, a = INFINITY;
+      int id = INT_MAX;
+      if (i == 0) {
+        b = b0[c] / s;
+        a = muh[c];
+        id = 0;
+      } else if (i <= A) {
+        const PointDiff df{PA + (size_t)(i - 1) * dp, x};
+        b = (pair_radial(cp, df, dp).base - S[(i - 1) + (size_t)c * A]) / s;
+        a = aA[i - 1];
+        id = i;
+      }
+      sb[i] = b;
+      sa[i] = a;
+      si[i] = id;
+    }
     if (tid == 0) {
-      kg_out[col0 + c] = NAN;
-      nact_out[col0 + c] = 0.0;
-      for (int k = 0; k < kScal; ++k) scal[(size_t)c * kScal + k] = 0.0;
+      s_line0[0] = 0.0;
+      s_line0[1] = 0.0;
     }
-    return;
-  }
-  const double s = sqrt(var);
-  const double* x = Px + (size_t)c * dp;
-  for (int i = tid; i < n2; i += 256) {
-    double b = -INFINITY, a = INFINITY;
-    int id = INT_MAX;
-    if (i == 0) {
-      b = b0[c] / s;
-      a = muh[c];
-      id = 0;
-    } else if (i <= A) {
-      const PointDiff df{PA + (size_t)(i - 1) * dp, x};
-      b = (pair_radial(cp, df, dp).base - S[(i - 1) + (size_t)c * A]) / s;
-      a = aA[i - 1];
-      id = i;
-    }
-    sb[i] = b;
-    sa[i] = a;
-    si[i] = id;
-  }
-  if (tid == 0) {
-    s_line0[0] = 0.0;
-    s_line0[1] = 0.0;
-  }
-  __syncthreads();
-  for (int k = 2; k <= n2; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int t = tid; t < (n2 >> 1); t += 256) {
-        const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
-        const double b1 = sb[lo], a1 = sa[lo], b2 = sb[hi], a2 = sa[hi];
-        const int i1 = si[lo], i2 = si[hi];
-        const bool up = (lo & k) == 0;
-        if (up ? line_before(b2, a2, i2, b1, a1, i1) : line_before(b1, a1, i1, b2, a2, i2)) {
-          sb[lo] = b2;
-          sa[lo] = a2;
-          si[lo] = i2;
-          sb[hi] = b1;
-          sa[hi] = a1;
-          si[hi] = i1;
+    __syncthreads();
+    for (int k = 2; k <= n2; k <<= 1)
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        for (int t = tid; t < (n2 >> 1); t += 256) {
+          const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
+          const double b1 = sb[lo], a1 = sa[lo], b2 = sb[hi], a2 = sa[hi];
+          const int i1 = si[lo], i2 = si[hi];
+          const bool up = (lo & k) == 0;
+          if (up ? line_before(b2, a2, i2, b1, a1, i1) : line_before(b1, a1, i1, b2, a2, i2)) {
+            sb[lo] = b2;
+            sa[lo] = a2;
+            si[lo] = i2;
+            sb[hi] = b1;
+            sa[hi] = a1;
+            si[hi] = i1;
+          }
         }
+        __syncthreads();
       }
-      __syncthreads();
-    }
-  if (tid == 0) {
-    // lines p before q (b_p > b_q) cross at (a_q - a_p) / (b_p - b_q), q is the lower one to the right of it.  The top of the stack
-    // goes when the new line overtakes the line below the top no later than the top did (compared cross-multiplied: both
-    // denominators are positive).
-    int sp = 0;
-    double prev_b = NAN, bt = 0.0, at = 0.0, bu = 0.0, au = 0.0;  // top of the stack and the line below it
-    for (int i = 0; i <= A; ++i) {
-      const double bi = sb[i], ai = sa[i];
-      const int idi = si[i];
-      if (i > 0 && bi == prev_b) continue;
-      prev_b = bi;
-      while (sp >= 2 && (ai - au) * (bu - bt) <= (at - au) * (bu - bi)) {
-        --sp;
-        bt = bu;
-        at = au;
-        if (sp >= 2) {
-          bu = sb[sp - 2];
-          au = sa[sp - 2];
+    if (tid == 0) {
+      // lines p before q (b_p > b_q) cross at (a_q - a_p) / (b_p - b_q), q is the lower one to the right of it.  The top of the stack
+      // goes when the new line overtakes the line below the top no later than the top did (compared cross-multiplied: both
+      // denominators are positive).
+      int sp = 0;
+      double prev_b = NAN, bt = 0.0, at = 0.0, bu = 0.0, au = 0.0;  // top of the stack and the line below it
+      for (int i = 0; i <= A; ++i) {
+        const double bi = sb[i], ai = sa[i];
+        const int idi = si[i];
+        if (i > 0 && bi == prev_b) continue;
+        prev_b = bi;
+        while (sp >= 2 && (ai - au) * (bu - bt) <= (at - au) * (bu - bi)) {
+          --sp;
+          bt = bu;
+          at = au;
+          if (sp >= 2) {
+            bu = sb[sp - 2];
+            au = sa[sp - 2];
+          }
         }
+        sb[sp] = bi;
+        sa[sp] = ai;
+        si[sp] = idi;
+        ++sp;
+        bu = bt;
+        au = at;
+        bt = bi;
+        at = ai;
       }
-      sb[sp] = bi;
-      sa[sp] = ai;
-      si[sp] = idi;
-      ++sp;
-      bu = bt;
-      au = at;
-      bt = bi;
-      at = ai;
+      s_count = sp;
     }
-    s_count = sp;
-  }
-  __syncthreads();
-  const int k = s_count;
-  double val = 0.0, wb = 0.0;
-  for (int j = tid; j < k; j += 256) {
-    const double bj = sb[j], aj = sa[j];
-    const double lo = (j == 0) ? -INFINITY : (aj - sa[j - 1]) / (sb[j - 1] - bj);
-    const double hi = (j == k - 1) ? INFINITY : (sa[j + 1] - aj) / (bj - sb[j + 1]);
-    const double P = normal_cdf_diff(lo, hi), w = normal_pdf(lo) - normal_pdf(hi);
-    val += fma(bj, w, aj * P);
-    wb = fma(w, bj, wb);
-    hull_w[(size_t)c * (A + 1) + j] = w;
-    hull_id[(size_t)c * (A + 1) + j] = si[j];
-    if (si[j] == 0) {
-      s_line0[0] = P;
-      s_line0[1] = w;
+    __syncthreads();
+    const int k = s_count;
+    double val = 0.0, wb = 0.0;
+    for (int j = tid; j < k; j += 256) {
+      const double bj = sb[j], aj = sa[j];
+      const double lo = (j == 0) ? -INFINITY : (aj - sa[j - 1]) / (sb[j - 1] - bj);
+      const double hi = (j == k - 1) ? INFINITY : (sa[j + 1] - aj) / (bj - sb[j + 1]);
+      const double P = normal_cdf_diff(lo, hi), w = normal_pdf(lo) - normal_pdf(hi);
+      val += fma(bj, w, aj * P);
+      wb = fma(w, bj, wb);
+      hull_w[(size_t)c * (A + 1) + j] = w;
+      hull_id[(size_t)c * (A + 1) + j] = si[j];
+      if (si[j] == 0) {
+        s_line0[0] = P;
+        s_line0[1] = w;
+      }
+    }
+    val = kg1_block_sum(val, s_red);
+    wb = kg1_block_sum(wb, s_red);
+    if (tid == 0) {
+      const double a0 = muh[c];
+      kg_out[col0 + c] = fmin(best, a0) - val;
+      nact_out[col0 + c] = (double)k;
+      scal[(size_t)c * kScal + 0] = s_line0[0];
+      scal[(size_t)c * kScal + 1] = s_line0[1];
+      scal[(size_t)c * kScal + 2] = wb;
+      scal[(size_t)c * kScal + 3] = (a0 < best) ? 1.0 : 0.0;
     }
   }
-  val = kg1_block_sum(val, s_red);
-  wb = kg1_block_sum(wb, s_red);
-  if (tid == 0) {
-    const double a0 = muh[c];
-    kg_out[col0 + c] = fmin(best, a0) - val;
-    nact_out[col0 + c] = (double)k;
-    scal[(size_t)c * kScal + 0] = s_line0[0];
-    scal[(size_t)c * kScal + 1] = s_line0[1];
-    scal[(size_t)c * kScal + 2] = wb;
-    scal[(size_t)c * kScal + 3] = (a0 < best) ? 1.0 : 0.0;
-  }
+};
+__global__ __launch_bounds__(256) void kg1_envelope_kernel(int A, int n2, int dp, int col0, const CovParams cp, double best, const double* __restrict__ PA, const double* __restrict__ Px, const double* __restrict__ aA, const double* __restrict__ muh, const double* __restrict__ s2, const double* __restrict__ b0, const double* __restrict__ S, double* __restrict__ kg_out, double* __restrict__ nact_out, double* __restrict__ hull_w, int* __restrict__ hull_id, double* __restrict__ scal) {
+  kg1_envelope_kernel_body::run(MOE_VBLOCK, MOE_VGRID, nullptr, A, n2, dp, col0, cp, best, PA, Px, aA, muh, s2, b0, S, kg_out, nact_out, hull_w, hull_id, scal);
 }
 
 // One workgroup per candidate: t = sum_j w_j V_{z_j} over the envelope's lines (x^'s line brings v_x^), then the two right-hand sides
 // of the gradient's triangular product, T[:, 2 c] = t / s - (sum_j w_j b_j / s^2) v_x and T[:, 2 c + 1] = (w_0 / s) v_x.
-__global__ __launch_bounds__(256) void kg1_t_kernel(int N, int A, const double* __restrict__ VA, const double* __restrict__ Vx,
-                                                    const double* __restrict__ Vh, const double* __restrict__ s2,
-                                                    const double* __restrict__ nact, int col0, const double* __restrict__ hull_w,
-                                                    const int* __restrict__ hull_id, const double* __restrict__ scal,
-                                                    double* __restrict__ T) {
-  __shared__ double s_w[256];
-  __shared__ int s_id[256];
-  const int c = blockIdx.x, tid = threadIdx.x;
-  const int k = (int)nact[col0 + c];
-  double* t1 = T + (size_t)(2 * c) * N;
-  double* t2 = t1 + N;
-  if (k == 0) {
-    for (int r = tid; r < N; r += 256) {
-      t1[r] = 0.0;
-      t2[r] = 0.0;
-    }
-    return;
-  }
-  const double var = s2[c], s = sqrt(var);
-  const double w0 = scal[(size_t)c * kScal + 1], swb = scal[(size_t)c * kScal + 2];
-  const double* vx = Vx + (size_t)c * N;
-  const double* vh = Vh + (size_t)c * N;
-  const int sweeps = (N + 255) / 256;
-  for (int sw = 0; sw < sweeps; ++sw) {
-    const int r = sw * 256 + tid;
-    double t = 0.0;
-    for (int j0 = 0; j0 < k; j0 += 256) {
-      __syncthreads();
-      if (j0 + tid < k) {
-        s_w[tid] = hull_w[(size_t)c * (A + 1) + j0 + tid];
-        s_id[tid] = hull_id[(size_t)c * (A + 1) + j0 + tid];
+struct kg1_t_kernel_body {
+  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, int N, int A, const double* __restrict__ VA, const double* __restrict__ Vx, const double* __restrict__ Vh, const double* __restrict__ s2, const double* __restrict__ nact, int col0, const double* __restrict__ hull_w, const int* __restrict__ hull_id, const double* __restrict__ scal, double* __restrict__ T) {
+    __shared__ double s_w[256];
+    __shared__ int s_id[256];
+    const int c = blockIdx.x, tid = threadIdx.x;
+    const int k = (int)nact[col0 + c];
+    double* t1 = T + (size_t)(2 * c) * N;
+    double* t2 = t1 + N;
+    if (k == 0) {
+      for (int r = tid; r < N; r += 256) {
+        t1[r] = 0.0;
+        t2[r] = 0.0;
       }
-      __syncthreads();
-      const int nj = min(256, k - j0);
-      if (r < N)
-        for (int j = 0; j < nj; ++j) {
-          const int id = s_id[j];
-          t = fma(s_w[j], (id == 0) ? vh[r] : VA[r + (size_t)(id - 1) * N], t);
-        }
+      return;
     }
-    if (r < N) {
-      t1[r] = t / s - (swb / var) * vx[r];
-      t2[r] = (w0 / s) * vx[r];
+    const double var = s2[c], s = sqrt(var);
+    const double w0 = scal[(size_t)c * kScal + 1], swb = scal[(size_t)c * kScal + 2];
+    const double* vx = Vx + (size_t)c * N;
+    const double* vh = Vh + (size_t)c * N;
+    const int sweeps = (N + 255) / 256;
+    for (int sw = 0; sw < sweeps; ++sw) {
+      const int r = sw * 256 + tid;
+      double t = 0.0;
+      for (int j0 = 0; j0 < k; j0 += 256) {
+        __syncthreads();
+        if (j0 + tid < k) {
+          s_w[tid] = hull_w[(size_t)c * (A + 1) + j0 + tid];
+          s_id[tid] = hull_id[(size_t)c * (A + 1) + j0 + tid];
+        }
+        __syncthreads();
+        const int nj = min(256, k - j0);
+        if (r < N)
+          for (int j = 0; j < nj; ++j) {
+            const int id = s_id[j];
+            t = fma(s_w[j], (id == 0) ? vh[r] : VA[r + (size_t)(id - 1) * N], t);
+          }
+      }
+      if (r < N) {
+        t1[r] = t / s - (swb / var) * vx[r];
+        t2[r] = (w0 / s) * vx[r];
+      }
     }
   }
+};
+__global__ __launch_bounds__(256) void kg1_t_kernel(int N, int A, const double* __restrict__ VA, const double* __restrict__ Vx, const double* __restrict__ Vh, const double* __restrict__ s2, const double* __restrict__ nact, int col0, const double* __restrict__ hull_w, const int* __restrict__ hull_id, const double* __restrict__ scal, double* __restrict__ T) {
+  kg1_t_kernel_body::run(MOE_VBLOCK, MOE_VGRID, nullptr, N, A, VA, Vx, Vh, s2, nact, col0, hull_w, hull_id, scal, T);
 }
 
 // One workgroup per candidate: the gradient from the two solved columns U = L^-T T, K^-1 (y - mean) and the envelope's lines.
 // FID: fidelity coordinates present -- x^ differs from x, its sums run separately and stay off the fidelity coordinates.
 template <int DP, bool FID>
-__global__ __launch_bounds__(256) void kg1_grad_kernel(int n, int A, int d, int nf, int col0, const CovParams cp,
-                                                       const double* __restrict__ X, const double* __restrict__ kinvy,
-                                                       const double* __restrict__ PA, const double* __restrict__ Px,
-                                                       const double* __restrict__ Ph, const double* __restrict__ U,
-                                                       const double* __restrict__ s2, const double* __restrict__ nact,
-                                                       const double* __restrict__ hull_w, const int* __restrict__ hull_id,
-                                                       const double* __restrict__ scal, double* __restrict__ grad) {
-  __shared__ double s_part[4][DP];
-  const int c = blockIdx.x, tid = threadIdx.x;
-  const int k = (int)nact[col0 + c];
-  double* out = grad + (size_t)(col0 + c) * d;
-  if (k == 0) {
-    if (tid < d) out[tid] = NAN;
-    return;
-  }
-  const double s = sqrt(s2[c]);
-  const double cb = scal[(size_t)c * kScal + 3] - scal[(size_t)c * kScal + 0];  // [mu_n(x^) < best] - P_0
-  const double* u1 = U + (size_t)(2 * c) * n;
-  const double* u2 = u1 + n;
-  double x[DP], xh[DP], g[DP];
-#pragma unroll
-  for (int i = 0; i < DP; ++i) {
-    x[i] = Px[(size_t)c * DP + i];
-    xh[i] = FID ? Ph[(size_t)c * DP + i] : x[i];
-    g[i] = 0.0;
-  }
-  for (int r = tid; r < n; r += 256) {
-    const double* xr = X + (size_t)r * DP;
-    double diff[DP], r2 = 0.0;
-#pragma unroll
-    for (int i = 0; i < DP; ++i) {
-      diff[i] = xr[i] - x[i];
-      r2 = fma(diff[i] * diff[i], cp.inv_l2[i], r2);
+struct kg1_grad_kernel_body {
+  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, int n, int A, int d, int nf, int col0, const CovParams& cp, const double* __restrict__ X, const double* __restrict__ kinvy, const double* __restrict__ PA, const double* __restrict__ Px, const double* __restrict__ Ph, const double* __restrict__ U, const double* __restrict__ s2, const double* __restrict__ nact, const double* __restrict__ hull_w, const int* __restrict__ hull_id, const double* __restrict__ scal, double* __restrict__ grad) {
+    __shared__ double s_part[4][DP];
+    const int c = blockIdx.x, tid = threadIdx.x;
+    const int k = (int)nact[col0 + c];
+    double* out = grad + (size_t)(col0 + c) * d;
+    if (k == 0) {
+      if (tid < d) out[tid] = NAN;
+      return;
     }
-    const double ch = fma(cb, kinvy[r], u2[r]);
-    const double f = radial_scalars(cp.type, cp.alpha, r2).first * (FID ? u1[r] : u1[r] + ch);
-#pragma unroll
-    for (int i = 0; i < DP; ++i) g[i] = fma(f, diff[i] * cp.inv_l2[i], g[i]);
-    if (FID) {
-      double r2h = 0.0;
-#pragma unroll
+    const double s = sqrt(s2[c]);
+    const double cb = scal[(size_t)c * kScal + 3] - scal[(size_t)c * kScal + 0];  // [mu_n(x^) < best] - P_0
+    const double* u1 = U + (size_t)(2 * c) * n;
+    const double* u2 = u1 + n;
+    double x[DP], xh[DP], g[DP];
+  #pragma unroll
+    for (int i = 0; i < DP; ++i) {
+      x[i] = Px[(size_t)c * DP + i];
+      xh[i] = FID ? Ph[(size_t)c * DP + i] : x[i];
+      g[i] = 0.0;
+    }
+    for (int r = tid; r < n; r += 256) {
+      const double* xr = X + (size_t)r * DP;
+      double diff[DP], r2 = 0.0;
+  #pragma unroll
       for (int i = 0; i < DP; ++i) {
-        diff[i] = xr[i] - xh[i];
-        r2h = fma(diff[i] * diff[i], cp.inv_l2[i], r2h);
+        diff[i] = xr[i] - x[i];
+        r2 = fma(diff[i] * diff[i], cp.inv_l2[i], r2);
       }
-      const double fh = radial_scalars(cp.type, cp.alpha, r2h).first * ch;
-#pragma unroll
-      for (int i = 0; i < DP; ++i)
-        if (i < d - nf) g[i] = fma(fh, diff[i] * cp.inv_l2[i], g[i]);
+      const double ch = fma(cb, kinvy[r], u2[r]);
+      const double f = radial_scalars(cp.type, cp.alpha, r2).first * (FID ? u1[r] : u1[r] + ch);
+  #pragma unroll
+      for (int i = 0; i < DP; ++i) g[i] = fma(f, diff[i] * cp.inv_l2[i], g[i]);
+      if (FID) {
+        double r2h = 0.0;
+  #pragma unroll
+        for (int i = 0; i < DP; ++i) {
+          diff[i] = xr[i] - xh[i];
+          r2h = fma(diff[i] * diff[i], cp.inv_l2[i], r2h);
+        }
+        const double fh = radial_scalars(cp.type, cp.alpha, r2h).first * ch;
+  #pragma unroll
+        for (int i = 0; i < DP; ++i)
+          if (i < d - nf) g[i] = fma(fh, diff[i] * cp.inv_l2[i], g[i]);
+      }
     }
-  }
-  for (int j = tid; j < k; j += 256) {
-    const int id = hull_id[(size_t)c * (A + 1) + j];
-    const double* z = (id == 0) ? Ph + (size_t)c * DP : PA + (size_t)(id - 1) * DP;
-    double diff[DP], r2 = 0.0;
-#pragma unroll
+    for (int j = tid; j < k; j += 256) {
+      const int id = hull_id[(size_t)c * (A + 1) + j];
+      const double* z = (id == 0) ? Ph + (size_t)c * DP : PA + (size_t)(id - 1) * DP;
+      double diff[DP], r2 = 0.0;
+  #pragma unroll
+      for (int i = 0; i < DP; ++i) {
+        diff[i] = z[i] - x[i];
+        r2 = fma(diff[i] * diff[i], cp.inv_l2[i], r2);
+      }
+      const double f = -radial_scalars(cp.type, cp.alpha, r2).first * hull_w[(size_t)c * (A + 1) + j] / s;
+  #pragma unroll
+      for (int i = 0; i < DP; ++i) g[i] = fma(f, diff[i] * cp.inv_l2[i], g[i]);
+    }
+  #pragma unroll
     for (int i = 0; i < DP; ++i) {
-      diff[i] = z[i] - x[i];
-      r2 = fma(diff[i] * diff[i], cp.inv_l2[i], r2);
+  #pragma unroll
+      for (int off = 32; off > 0; off >>= 1) g[i] += __shfl_xor(g[i], off, 64);
     }
-    const double f = -radial_scalars(cp.type, cp.alpha, r2).first * hull_w[(size_t)c * (A + 1) + j] / s;
-#pragma unroll
-    for (int i = 0; i < DP; ++i) g[i] = fma(f, diff[i] * cp.inv_l2[i], g[i]);
+    if ((tid & 63) == 0) {
+  #pragma unroll
+      for (int i = 0; i < DP; ++i) s_part[tid >> 6][i] = g[i];
+    }
+    __syncthreads();
+    if (tid < d) out[tid] = (s_part[0][tid] + s_part[1][tid]) + (s_part[2][tid] + s_part[3][tid]);
   }
-#pragma unroll
-  for (int i = 0; i < DP; ++i) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) g[i] += __shfl_xor(g[i], off, 64);
-  }
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int i = 0; i < DP; ++i) s_part[tid >> 6][i] = g[i];
-  }
-  __syncthreads();
-  if (tid < d) out[tid] = (s_part[0][tid] + s_part[1][tid]) + (s_part[2][tid] + s_part[3][tid]);
+};
+template <int DP, bool FID>
+__global__ __launch_bounds__(256) void kg1_grad_kernel(int n, int A, int d, int nf, int col0, const CovParams cp, const double* __restrict__ X, const double* __restrict__ kinvy, const double* __restrict__ PA, const double* __restrict__ Px, const double* __restrict__ Ph, const double* __restrict__ U, const double* __restrict__ s2, const double* __restrict__ nact, const double* __restrict__ hull_w, const int* __restrict__ hull_id, const double* __restrict__ scal, double* __restrict__ grad) {
+  kg1_grad_kernel_body<DP, FID>::run(MOE_VBLOCK, MOE_VGRID, nullptr, n, A, d, nf, col0, cp, X, kinvy, PA, Px, Ph, U, s2, nact, hull_w, hull_id, scal, grad);
 }
 
-__global__ void kg1_init_kernel(int* __restrict__ fail) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) *fail = INT_MAX;
+__global__ void kg1_init_kernel(int* __restrict__ fail, int count) {
+  if (blockIdx.x == 0 && (int)threadIdx.x < count) fail[threadIdx.x] = INT_MAX;
 }
 
 // the first failing candidate as a double in front of the results: one copy back
@@ -418,15 +428,15 @@ DerivList no_derivs() {
 
 // op(L^-1) B for c independent columns, the kernel family fixed by N alone (never by c): below 128 rows the tiled kernel in chunks
 // that stay under its switch to the matrix-pipe kernel, from 128 rows the split-K kernels at every column count
-void tri_cols(GpDev& gp, char op, int c, const double* B, double* Cout) {
+void tri_cols(GpDev& gp, char op, int c, const double* B, double* Cout, hipStream_t s) {
   const int N = gp.N;
   if (N < 128) {
     for (int k0 = 0; k0 < c; k0 += kKg1TinyCols) {
       const int nk = std::min(kKg1TinyCols, c - k0);
-      launch_tri_gemm_cols(op, N, nk, nk, gp.dLinv.p, gp.ldL, B + (size_t)k0 * N, N, Cout + (size_t)k0 * N, N, nullptr, gp.stream);
+      launch_tri_gemm_cols(op, N, nk, nk, gp.dLinv.p, gp.ldL, B + (size_t)k0 * N, N, Cout + (size_t)k0 * N, N, nullptr, s);
     }
   } else {
-    launch_tri_gemm_cols(op, N, c, 17, gp.dLinv.p, gp.ldL, B, N, Cout, N, gp.dEK.p, gp.stream);
+    launch_tri_gemm_cols(op, N, c, 17, gp.dLinv.p, gp.ldL, B, N, Cout, N, gp.dEK.p, s);
   }
 }
 
@@ -446,26 +456,140 @@ void check_kg_discrete_shapes(int num_fidelity, int A, int C) {
   if (num_fidelity < 0) throw Error(MOE_ERR_BOUNDS, "num_fidelity out of range", num_fidelity, 0, 1e9);
 }
 
-void kg_discrete_on_device(GpDev& gp, int nf, const double* discrete, int A, const double* pts, int C, double best, bool want_grad,
-                           double* kg_out, double* grad_out, int* nact_out) {
-  check_kg_discrete_shapes(nf, A, C);
+void check_kg_discrete_member(const GpDev& gp, int nf) {
   if (nf >= gp.d) throw Error(MOE_ERR_BOUNDS, "num_fidelity out of range", nf, 0, gp.d - 1);
   if (gp.g > 0)
     throw Error(MOE_ERR_BOUNDS,
                 "the discretised one-point knowledge gradient needs a GP without derivative observations: with them the fantasy "
                 "has 1 + num_derivatives dimensions and the quantity is not a minimum of lines",
                 gp.g, 0, 0);
+}
+
+Kg1Member kg1_member(GpDev& gp, int nf, int A, int C, double best, bool with_grad, int* fail) {
+  check_kg_discrete_shapes(nf, A, C);
+  check_kg_discrete_member(gp, nf);
+  gp.use_device();
+  Kg1Member m;
+  m.gp = &gp;
+  m.nf = nf;
+  m.A = A;
+  m.C = C;
+  m.best = best;
+  m.with_grad = with_grad;
+  m.fid = nf > 0;
+  m.per_pass = kg1_pass_size(gp.N, A);
+  m.widest = std::min(m.per_pass, C);
+  m.n2 = 2;
+  while (m.n2 < A + 1) m.n2 <<= 1;
+  const int N = gp.N;
+  const size_t nA = (size_t)A, nC = (size_t)C, nW = (size_t)m.widest;
+  // doubles: [fail | kg C | active C | grad C d] (the copy back) | V_A N A | a_A A | per pass: V_x, V_x^ N W each | T, U N 2W each |
+  //          mu_n(x^), s^2, slope numerator of x^ W each | slopes A W | envelope weights (A + 1) W | scalars kScal W
+  const size_t nOut = m.out_doubles();
+  const size_t nV = (size_t)N * nW;
+  gp.kg1D.reserve(nOut + (size_t)N * nA + nA + (m.fid ? 2 : 1) * nV + (with_grad ? 4 * nV : 0) + 3 * nW + nA * nW + (nA + 1) * nW +
+                  kScal * nW);
+  gp.kg1I.reserve(1 + (nA + 1) * nW);
+  m.dOut = gp.kg1D.p;
+  m.dKg = m.dOut + 1;
+  m.dAct = m.dKg + nC;
+  m.dGrad = m.dAct + nC;
+  m.dVA = m.dOut + nOut;
+  m.dAA = m.dVA + (size_t)N * nA;
+  m.dVx = m.dAA + nA;
+  m.dVh = m.fid ? m.dVx + nV : m.dVx;
+  m.dT = m.dVh + nV;
+  m.dU = m.dT + (with_grad ? 2 * nV : 0);
+  m.dMuh = m.dU + (with_grad ? 2 * nV : 0);
+  m.dS2 = m.dMuh + nW;
+  m.dB0 = m.dS2 + nW;
+  m.dS = m.dB0 + nW;
+  m.dHw = m.dS + nA * nW;
+  m.dScal = m.dHw + (nA + 1) * nW;
+  m.iFail = fail != nullptr ? fail : gp.kg1I.p;
+  m.iHid = gp.kg1I.p + 1;
+  gp.dE.reserve((size_t)N * std::max(nA, nW));
+  if (N >= 128) gp.dEK.reserve(tri_cols_work_doubles(N, (int)std::max(nA, 2 * nW)));
+  MOE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kg1_envelope_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)(kKg1MaxLines * (2 * sizeof(double) + sizeof(int)))));
+  return m;
+}
+
+void kg1_clear_fail(int* fail, int count, hipStream_t s) {
+  if (count < 1 || count > 1024) throw Error(MOE_ERR_RUNTIME, "kg1_clear_fail: between 1 and 1024 words");
+  MOE_LAUNCH(kg1_init_kernel, dim3(1), dim3(1024), 0, s, fail, count);
+  MOE_HIP_CHECK(hipGetLastError());
+}
+
+void kg1_prepare_set(const Kg1Member& m, hipStream_t s) {
+  GpDev& gp = *m.gp;
+  const DerivList none = no_derivs();
+  launch_cov_build(gp.cp, gp.dX.p, gp.n, none, m.dPA, m.A, none, nullptr, gp.dE.p, gp.N, 0, s);
+  tri_cols(gp, 'N', m.A, gp.dE.p, m.dVA, s);
+  launch_mean(gp.cp, gp.dX.p, gp.n, none, gp.dKinvY.p, m.dPA, m.A, gp.mean, false, m.dAA, s);
+}
+
+void kg1_eval_pass(const Kg1Member& m, const double* Px, const double* Ph, int nc, int c0, bool with_grad, hipStream_t s) {
+  GpDev& gp = *m.gp;
+  if (nc < 1 || nc > m.widest || c0 < 0 || c0 + nc > m.C || (with_grad && !m.with_grad))
+    throw Error(MOE_ERR_RUNTIME, "kg1_eval_pass: the pass does not fit the member's buffers");
+  const int N = gp.N, n = gp.n, d = gp.d, dp = gp.dp, A = m.A, nf = m.nf;
+  const DerivList none = no_derivs();
+  const size_t shm = (size_t)m.n2 * (2 * sizeof(double) + sizeof(int));
+  const dim3 b256(256);
+  launch_cov_build(gp.cp, gp.dX.p, n, none, Px, nc, none, nullptr, gp.dE.p, N, 0, s);
+  tri_cols(gp, 'N', nc, gp.dE.p, m.dVx, s);
+  if (m.fid) {
+    launch_cov_build(gp.cp, gp.dX.p, n, none, Ph, nc, none, nullptr, gp.dE.p, N, 0, s);
+    tri_cols(gp, 'N', nc, gp.dE.p, m.dVh, s);
+  }
+  launch_mean(gp.cp, gp.dX.p, n, none, gp.dKinvY.p, Ph, nc, gp.mean, false, m.dMuh, s);
+  launch_kernel_ens<kg1_cand_kernel_body, 256>(kg1_cand_kernel, dim3((unsigned)((nc + 3) / 4)), b256, 0, s, N, nc, c0, dp, gp.cp,
+                                               gp.noise[0], Px, Ph, (const double*)m.dVx, (const double*)m.dVh, m.dS2, m.dB0, m.iFail);
+  launch_kernel_ens<kg1_slope_kernel_body, 256>(kg1_slope_kernel, dim3((unsigned)((A + 63) / 64), (unsigned)((nc + 63) / 64)), b256, 0, s,
+                                                N, A, nc, (const double*)m.dVA, (const double*)m.dVx, m.dS);
+  launch_kernel_ens<kg1_envelope_kernel_body, 256>(kg1_envelope_kernel, dim3((unsigned)nc), b256, shm, s, A, m.n2, dp, c0, gp.cp, m.best,
+                                                   m.dPA, Px, (const double*)m.dAA, (const double*)m.dMuh, (const double*)m.dS2,
+                                                   (const double*)m.dB0, (const double*)m.dS, m.dKg, m.dAct, m.dHw, m.iHid, m.dScal);
+  MOE_HIP_CHECK(hipGetLastError());
+  if (!with_grad) return;
+  launch_kernel_ens<kg1_t_kernel_body, 256>(kg1_t_kernel, dim3((unsigned)nc), b256, 0, s, N, A, (const double*)m.dVA, (const double*)m.dVx,
+                                            (const double*)m.dVh, (const double*)m.dS2, (const double*)m.dAct, c0, (const double*)m.dHw,
+                                            (const int*)m.iHid, (const double*)m.dScal, m.dT);
+  tri_cols(gp, 'T', 2 * nc, m.dT, m.dU, s);
+  dispatch_dp(dp, [&](auto DP) {
+    if (m.fid)
+      launch_kernel_ens<kg1_grad_kernel_body<DP, true>, 256>(kg1_grad_kernel<DP, true>, dim3((unsigned)nc), b256, 0, s, n, A, d, nf, c0, gp.cp,
+                                                             (const double*)gp.dX.p, (const double*)gp.dKinvY.p, m.dPA, Px, Ph,
+                                                             (const double*)m.dU, (const double*)m.dS2, (const double*)m.dAct,
+                                                             (const double*)m.dHw, (const int*)m.iHid, (const double*)m.dScal, m.dGrad);
+    else
+      launch_kernel_ens<kg1_grad_kernel_body<DP, false>, 256>(kg1_grad_kernel<DP, false>, dim3((unsigned)nc), b256, 0, s, n, A, d, nf, c0, gp.cp,
+                                                              (const double*)gp.dX.p, (const double*)gp.dKinvY.p, m.dPA, Px, Ph,
+                                                              (const double*)m.dU, (const double*)m.dS2, (const double*)m.dAct,
+                                                              (const double*)m.dHw, (const int*)m.iHid, (const double*)m.dScal, m.dGrad);
+  });
+  MOE_HIP_CHECK(hipGetLastError());
+}
+
+void kg1_eval_points(const Kg1Member& m, const double* Px, const double* Ph, int C, bool with_grad, hipStream_t s) {
+  const int dp = m.gp->dp;
+  for (int c0 = 0; c0 < C; c0 += m.per_pass)
+    kg1_eval_pass(m, Px + (size_t)c0 * dp, Ph + (size_t)c0 * dp, std::min(m.per_pass, C - c0), c0, with_grad, s);
+}
+
+// prepare the set, evaluate pass after pass, copy back: one upload, one stream, one wait
+void kg_discrete_on_device(GpDev& gp, int nf, const double* discrete, int A, const double* pts, int C, double best, bool want_grad,
+                           double* kg_out, double* grad_out, int* nact_out) {
+  check_kg_discrete_shapes(nf, A, C);
+  check_kg_discrete_member(gp, nf);
   if (discrete == nullptr || pts == nullptr || kg_out == nullptr || (want_grad && grad_out == nullptr))
     throw Error(MOE_ERR_RUNTIME, "NULL argument");
-  gp.use_device();
+  Kg1Member m = kg1_member(gp, nf, A, C, best, want_grad);
   hipStream_t s = gp.stream;
-  const int N = gp.N, n = gp.n, d = gp.d, dp = gp.dp, size = d - nf;
-  const int per_pass = kg1_pass_size(N, A), widest = std::min(per_pass, C);
-  const bool fid = nf > 0;
-  const size_t nA = (size_t)A, nC = (size_t)C, nW = (size_t)widest;
-  const DerivList none = no_derivs();
-  int n2 = 2;
-  while (n2 < A + 1) n2 <<= 1;
+  const int d = gp.d, dp = gp.dp, size = d - nf;
+  const bool fid = m.fid;
+  const size_t nA = (size_t)A, nC = (size_t)C;
 
   // one copy down: [A discrete points, fidelity coordinates 1 | C candidates | C candidates with fidelity coordinates 1], padded
   const size_t nIn = (nA + nC * (fid ? 2 : 1)) * dp;
@@ -480,82 +604,16 @@ void kg_discrete_on_device(GpDev& gp, int nf, const double* discrete, int A, con
       if (fid) h[(nA + nC + i) * dp + k] = (k >= size && k < d) ? 1.0 : v;
     }
   gp.dStateIn.upload(h, nIn, s, true);
-  const double* dPA = gp.dStateIn.p;
-  const double* dPx = dPA + nA * dp;
+  m.dPA = gp.dStateIn.p;
+  const double* dPx = m.dPA + nA * dp;
   const double* dPh = fid ? dPx + nC * dp : dPx;
 
-  // doubles: [fail | kg C | active C | grad C d] (the copy back) | V_A N A | a_A A | per pass: V_x, V_x^ N W each | T, U N 2W each |
-  //          mu_n(x^), s^2, slope numerator of x^ W each | slopes A W | envelope weights (A + 1) W | scalars kScal W
-  const size_t nOut = 1 + 2 * nC + (want_grad ? nC * d : 0);
-  const size_t nV = (size_t)N * nW;
-  gp.kg1D.reserve(nOut + (size_t)N * nA + nA + (fid ? 2 : 1) * nV + (want_grad ? 4 * nV : 0) + 3 * nW + nA * nW + (nA + 1) * nW +
-                  kScal * nW);
-  gp.kg1I.reserve(1 + (nA + 1) * nW);
-  double* dOut = gp.kg1D.p;
-  double* dKg = dOut + 1;
-  double* dAct = dKg + nC;
-  double* dGrad = dAct + nC;
-  double* dVA = dOut + nOut;
-  double* dAA = dVA + (size_t)N * nA;
-  double* dVx = dAA + nA;
-  double* dVh = fid ? dVx + nV : dVx;
-  double* dT = dVh + nV;
-  double* dU = dT + (want_grad ? 2 * nV : 0);
-  double* dMuh = dU + (want_grad ? 2 * nV : 0);
-  double* dS2 = dMuh + nW;
-  double* dB0 = dS2 + nW;
-  double* dS = dB0 + nW;
-  double* dHw = dS + nA * nW;
-  double* dScal = dHw + (nA + 1) * nW;
-  int* iFail = gp.kg1I.p;
-  int* iHid = iFail + 1;
-
-  gp.dE.reserve((size_t)N * std::max(nA, nW));
-  if (N >= 128) gp.dEK.reserve(tri_cols_work_doubles(N, (int)std::max(nA, 2 * nW)));
-  const size_t shm = (size_t)n2 * (2 * sizeof(double) + sizeof(int));
-  MOE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kg1_envelope_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)(kKg1MaxLines * (2 * sizeof(double) + sizeof(int)))));
-
-  MOE_LAUNCH_NOW(kg1_init_kernel, dim3(1), dim3(64), 0, s, iFail);
-  launch_cov_build(gp.cp, gp.dX.p, n, none, dPA, A, none, nullptr, gp.dE.p, N, 0, s);
-  tri_cols(gp, 'N', A, gp.dE.p, dVA);
-  launch_mean(gp.cp, gp.dX.p, n, none, gp.dKinvY.p, dPA, A, gp.mean, false, dAA, s);
-  for (int c0 = 0; c0 < C; c0 += per_pass) {
-    const int nc = std::min(per_pass, C - c0);
-    const double* Px = dPx + (size_t)c0 * dp;
-    const double* Ph = dPh + (size_t)c0 * dp;
-    launch_cov_build(gp.cp, gp.dX.p, n, none, Px, nc, none, nullptr, gp.dE.p, N, 0, s);
-    tri_cols(gp, 'N', nc, gp.dE.p, dVx);
-    if (fid) {
-      launch_cov_build(gp.cp, gp.dX.p, n, none, Ph, nc, none, nullptr, gp.dE.p, N, 0, s);
-      tri_cols(gp, 'N', nc, gp.dE.p, dVh);
-    }
-    launch_mean(gp.cp, gp.dX.p, n, none, gp.dKinvY.p, Ph, nc, gp.mean, false, dMuh, s);
-    MOE_LAUNCH_NOW(kg1_cand_kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, s, N, nc, c0, dp, gp.cp, gp.noise[0], Px, Ph,
-                   (const double*)dVx, (const double*)dVh, dS2, dB0, iFail);
-    MOE_LAUNCH_NOW(kg1_slope_kernel, dim3((unsigned)((A + 63) / 64), (unsigned)((nc + 63) / 64)), dim3(256), 0, s, N, A, nc,
-                   (const double*)dVA, (const double*)dVx, dS);
-    MOE_LAUNCH_NOW(kg1_envelope_kernel, dim3((unsigned)nc), dim3(256), shm, s, A, n2, dp, c0, gp.cp, best, dPA, Px, (const double*)dAA,
-                   (const double*)dMuh, (const double*)dS2, (const double*)dB0, (const double*)dS, dKg, dAct, dHw, iHid, dScal);
-    MOE_HIP_CHECK(hipGetLastError());
-    if (!want_grad) continue;
-    MOE_LAUNCH_NOW(kg1_t_kernel, dim3((unsigned)nc), dim3(256), 0, s, N, A, (const double*)dVA, (const double*)dVx, (const double*)dVh,
-                   (const double*)dS2, (const double*)dAct, c0, (const double*)dHw, (const int*)iHid, (const double*)dScal, dT);
-    tri_cols(gp, 'T', 2 * nc, dT, dU);
-    dispatch_dp(dp, [&](auto DP) {
-      if (fid)
-        MOE_LAUNCH_NOW((kg1_grad_kernel<DP, true>), dim3((unsigned)nc), dim3(256), 0, s, n, A, d, nf, c0, gp.cp, (const double*)gp.dX.p,
-                       (const double*)gp.dKinvY.p, dPA, Px, Ph, (const double*)dU, (const double*)dS2, (const double*)dAct,
-                       (const double*)dHw, (const int*)iHid, (const double*)dScal, dGrad);
-      else
-        MOE_LAUNCH_NOW((kg1_grad_kernel<DP, false>), dim3((unsigned)nc), dim3(256), 0, s, n, A, d, nf, c0, gp.cp, (const double*)gp.dX.p,
-                       (const double*)gp.dKinvY.p, dPA, Px, Ph, (const double*)dU, (const double*)dS2, (const double*)dAct,
-                       (const double*)dHw, (const int*)iHid, (const double*)dScal, dGrad);
-    });
-    MOE_HIP_CHECK(hipGetLastError());
-  }
-  MOE_LAUNCH_NOW(kg1_pack_kernel, dim3(1), dim3(64), 0, s, (const int*)iFail, dOut);
+  kg1_clear_fail(m.iFail, 1, s);
+  kg1_prepare_set(m, s);
+  kg1_eval_points(m, dPx, dPh, C, want_grad, s);
+  MOE_LAUNCH_NOW(kg1_pack_kernel, dim3(1), dim3(64), 0, s, (const int*)m.iFail, m.dOut);
   MOE_HIP_CHECK(hipGetLastError());
+  const size_t nOut = m.out_doubles();
   gp.hStateOut.reserve(nOut);
   gp.kg1D.download(gp.hStateOut.p, nOut, s);
   MOE_HIP_CHECK(hipStreamSynchronize(s));

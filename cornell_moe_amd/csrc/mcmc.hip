@@ -51,16 +51,12 @@ void ensemble_launch_stats(long long* out4) {
   for (int i = 0; i < 4; ++i) out4[i] = g_ens_stats[i].load();
 }
 
-namespace {
 // ---- ensemble-wide launches (r6; launch.hpp) ----
 // The recordings of the members' evaluation chains, zipped: position by position ONE launch of a kernel's ensemble twin over all
 // members (their argument records side by side in a device table), one copy kernel for their small pinned copies, everything else
 // member after member -- on ONE stream.  Returns false (nothing launched) when the recordings do not line up or too few positions
 // merge to be worth the members' concurrency on their own streams.
-struct EnsArena {
-  PinnedBuf<unsigned char>& host;
-  DevBuf<unsigned char>& dev;
-};
+namespace {
 constexpr size_t kEnsCopyMaxBytes = (size_t)4 << 20;
 
 bool ens_copy_mergeable(const std::vector<Recorder>& recs, size_t pos) {
@@ -70,11 +66,18 @@ bool ens_copy_mergeable(const std::vector<Recorder>& recs, size_t pos) {
   }
   return true;
 }
+}  // namespace
 
-bool replay_ensemble(const std::vector<Recorder>& recs, hipStream_t z, EnsArena& arena, int* merged_out) {
+void ensemble_stats_add(int which, long long count) { g_ens_stats[which] += count; }
+
+// the first half of replay_ensemble: how every position is issued, and the argument tables on their way to the device (stream z)
+bool ensemble_zip(const std::vector<Recorder>& recs, hipStream_t z, EnsArena& arena, EnsZip* zip) {
   const size_t M = recs.size(), L = recs[0].ops.size();
-  std::vector<char> how(L, 0);  // 0: member after member, 1: ensemble twin, 2: copy kernel
-  std::vector<size_t> off(L, 0);
+  std::vector<char>& how = zip->how;  // 0: member after member, 1: ensemble twin, 2: copy kernel
+  std::vector<size_t>& off = zip->off;
+  how.assign(L, 0);
+  off.assign(L, 0);
+  zip->merged = 0;
   size_t total = 0, merged = 0;
   for (const Recorder& r : recs)
     if (r.ops.size() != L) return false;
@@ -105,7 +108,7 @@ bool replay_ensemble(const std::vector<Recorder>& recs, hipStream_t z, EnsArena&
       ++merged;
     }
   }
-  if (merged_out) *merged_out = (int)merged;
+  zip->merged = (int)merged;
   if (merged * 10 < L * 6) return false;
   arena.host.reserve(total);
   arena.dev.reserve(total);
@@ -118,20 +121,36 @@ bool replay_ensemble(const std::vector<Recorder>& recs, hipStream_t z, EnsArena&
     }
   }
   MOE_HIP_CHECK(hipMemcpyAsync(arena.dev.p, arena.host.p, total, hipMemcpyHostToDevice, z));
+  return true;
+}
+
+// the second half: the launches, reading the tables ensemble_zip sent (as often as the caller likes while the tables stay put)
+void ensemble_issue(const std::vector<Recorder>& recs, const EnsZip& zip, hipStream_t z, EnsArena& arena) {
+  const size_t M = recs.size(), L = recs[0].ops.size();
   for (size_t k = 0; k < L; ++k) {
     const LaunchOp& a = recs[0].ops[k];
-    if (how[k] == 1) {
-      a.ens_launch(arena.dev.p + off[k], (int)M, a.grid, a.block, a.shm, z);
-    } else if (how[k] == 2) {
+    if (zip.how[k] == 1) {
+      a.ens_launch(arena.dev.p + zip.off[k], (int)M, a.grid, a.block, a.shm, z);
+    } else if (zip.how[k] == 2) {
       size_t most = 0;
       for (size_t i = 0; i < M; ++i) most = std::max(most, recs[i].ops[k].copy.bytes);
       const unsigned bx = (unsigned)std::max<size_t>(1, std::min<size_t>(64, (most / 8 + 1023) / 1024));
-      ens_copy_kernel<0><<<dim3(bx, (unsigned)M), dim3(256), 0, z>>>((const CopyEntry*)(arena.dev.p + off[k]));
+      ens_copy_kernel<0><<<dim3(bx, (unsigned)M), dim3(256), 0, z>>>((const CopyEntry*)(arena.dev.p + zip.off[k]));
     } else {
       for (size_t i = 0; i < M; ++i) recs[i].ops[k].run(z);
     }
   }
   MOE_HIP_CHECK(hipGetLastError());
+}
+
+namespace {
+
+bool replay_ensemble(const std::vector<Recorder>& recs, hipStream_t z, EnsArena& arena, int* merged_out) {
+  EnsZip zip;
+  const bool ok = ensemble_zip(recs, z, arena, &zip);
+  if (merged_out) *merged_out = zip.merged;
+  if (!ok) return false;
+  ensemble_issue(recs, zip, z, arena);
   return true;
 }
 

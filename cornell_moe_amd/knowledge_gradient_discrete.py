@@ -9,6 +9,9 @@ domain, this one over {the candidate with its fidelity coordinates at 1} and A.
 ``DiscreteKnowledgeGradient`` carries the method names python_version/optimization.py's GradientDescentOptimizer calls
 (``problem_size``, ``current_point``, ``compute_objective_function``, ``compute_grad_objective_function``), the way
 ``PosteriorMeanMCMC`` of this package does.  Every evaluation is one ``moe_gp_kg_discrete`` call (csrc/kg1.hip).
+
+``multistart_discrete_knowledge_gradient_optimization`` is the whole suggestion under a hyper-parameter ensemble in one library
+call (csrc/kg1_opt.hip): what the reference's examples/main.py asks ``gen_sample_from_qkg_mcmc`` for, at q = 1 and deterministic.
 """
 import numpy as np
 
@@ -84,3 +87,15 @@ class DiscreteKnowledgeGradient(object):
 
     def compute_hessian_objective_function(self, **kwargs):
         raise NotImplementedError('Currently we cannot compute the hessian of the knowledge gradient.')
+
+
+def multistart_discrete_knowledge_gradient_optimization(gps, discrete_all, best_so_far_all, bounds, gd_params, num_multistarts, seed,
+                                                        num_fidelity=0):
+    """The next point to sample under the ensemble ``gps`` (an api.DeviceGPMCMC, a list of api.DeviceGP or one api.DeviceGP): the
+    multistart gradient ascent of the ensemble-averaged discretised knowledge gradient from ``num_multistarts`` Latin-hypercube
+    starts in ``bounds`` [dim][2] (moe_latin_hypercube with ``seed``), member e over its own set discrete_all[e] and best value
+    best_so_far_all[e].  Returns (point [dim], value, found)."""
+    from . import api
+    starts = api.latin_hypercube(seed, bounds, num_multistarts)
+    res = api.kg_discrete_multistart(gps, gd_params, bounds, discrete_all, best_so_far_all, starts, num_fidelity=num_fidelity)
+    return res["point"], res["value"], res["found"]

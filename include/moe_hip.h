@@ -204,6 +204,62 @@ int moe_gp_kg_discrete(const moe_gp_t* gp, int num_fidelity, const double* discr
                        int num_points, double best_so_far, int want_grad, double* kg, double* grad, int* num_active,
                        moe_error_t* err);
 int moe_kg1_pass_size(int num_rows, int num_discrete);
+/* moe_gp_kg_discrete averaged over an ensemble of num_mcmc GPs (one per hyper-parameter sample), every member e with its own
+ * discrete set of num_discrete[e] points -- discrete_all holds the sets back to back, member e's [num_discrete[e]][dim -
+ * num_fidelity] -- and its own best_so_far[e]:
+ *   kg[i] = (KG_0(x_i) + KG_1(x_i) + ... + KG_{E-1}(x_i)) / E,  grad[i][dim] the same sum of the members' gradients
+ * The members are added in member order and the sum is divided once; a member's term carries the bits moe_gp_kg_discrete returns
+ * for it (the same kernels in the same passes), so the result is, bit for bit, the members' results added up on the host.
+ * One copy down, one stream (the first member's), one wait, one copy back.  Every member's chain of kernels is recorded and each
+ * kernel is launched once for all members where their launches line up (same N, same padded line count; moe_set_ensemble_launches,
+ * counted in moe_ensemble_launch_stats), member after member otherwise: the same bits either way.
+ * The members need NOT share their sampled points or their number; they share dim and the device, and none has derivative
+ * observations.  No counterpart in the reference's boundary.
+ * Errors, in this order, everything that needs no handle before a handle is touched: num_mcmc outside 1 .. 1024 -> MOE_ERR_BOUNDS;
+ * a NULL array (gps, discrete_all, num_discrete, best_so_far, points, kg, grad with want_grad) -> MOE_ERR_RUNTIME; the first
+ * num_discrete[e] outside 1 .. 4095 -> MOE_ERR_BOUNDS, payload (num_discrete[e], 1, 4095); num_points < 1 -> MOE_ERR_BOUNDS;
+ * num_fidelity < 0 -> MOE_ERR_BOUNDS; a NULL handle -> MOE_ERR_RUNTIME; num_fidelity >= dim -> MOE_ERR_BOUNDS; a member of another
+ * dim, then of another device -> MOE_ERR_INVALID_VALUE, payload (its value, the first member's, the member); a member with
+ * derivative observations -> MOE_ERR_BOUNDS, payload (num_derivatives, 0, 0); a handle listed twice -> MOE_ERR_INVALID_VALUE (every
+ * member keeps its own workspaces).
+ * MOE_ERR_SINGULAR, payload (e, i): the first member e in which a candidate has s^2 <= 1e-16, and the first such candidate i of
+ * that member; reported after the wait. */
+int moe_kg_discrete_mcmc(const moe_gp_t* const* gps, int num_mcmc, int num_fidelity, const double* discrete_all,
+                         const int* num_discrete, const double* best_so_far, const double* points, int num_points, int want_grad,
+                         double* kg, double* grad, moe_error_t* err);
+/* One suggestion by the ensemble-averaged discretised knowledge gradient: the multistart gradient ascent of the drivers above
+ * (MultistartOptimizer over GradientDescentOptimizer, gpp_optimization.hpp:619-705, 1472-1546) with moe_kg_discrete_mcmc's plain
+ * ensemble mean as the objective, q = 1, and the whole loop on the device.  It has NO counterpart in the reference: no fidelity-cost
+ * division, none of the KG-MCMC state behaviour moe_set_reference_quirks governs, and the objective is exact, not Monte Carlo.
+ *   1. screening: the value at every start [num_starts][dim] (start_values, may be NULL); with do_gradient_ascent == 0 the best
+ *      start by a strict compare in list order is returned (best_point seeded with the first start) and the outputs of 2. - 3. are
+ *      left untouched.
+ *   2. the K = min(20, num_starts) best starts are kept in the reference's order and tie rule (lowest kept value first, equal
+ *      values by descending index; kept_index[K]); best_point is seeded with the first of them.
+ *   3. ascent of all kept starts at once, R = max_num_restarts rounds of T = max_num_steps steps: with alpha_i = pre_mult
+ *      (i + 1)^-gamma, step = alpha_i grad, limited per coordinate by TensorProductDomain::LimitUpdate (max_relative_change of the
+ *      distance to the nearer bound; halved, or half-way to the bound, where it would leave the domain), x += step; a start stops
+ *      for the round when |step| < tolerance / T and for good when a round moved it by no more than tolerance; the ascent ends
+ *      when no start is left.  A stopped start is still evaluated and its update masked.
+ *   4. the value at every end point (end_points[K][dim], end_values[K]); the first of the largest is returned (strict compare,
+ *      against -infinity: found = 0 only if every value is NaN).
+ * path (may be NULL): [K][R T + 1][dim], row 0 the start, row 1 + r T + i the point after step i of round r (a stopped start
+ * repeats its point).  steps_taken[K]: the steps a start took while running.  All of these may be NULL.
+ * The update is the host drivers' arithmetic operation for operation (no fused multiply-add), so the path is, bit for bit, the one
+ * a host loop over moe_kg_discrete_mcmc walks.  The set phase (K(X, A_e), L^-1 K(X, A_e), mu_n(A_e)) runs once per member for the
+ * whole call.  One copy down; the host waits once after the screening (it picks the kept starts), once per restart round (the count
+ * of starts still alive) and once at the end.  Ensemble-wide launches as in moe_kg_discrete_mcmc, a step's recording made once and
+ * issued every step.
+ * Errors, in this order: those of moe_kg_discrete_mcmc that need no handle (outer, domain_bounds, starts, best_point, best_value
+ * and found among the arrays that must not be NULL; num_starts for num_points); max_num_steps < 1 with do_gradient_ascent != 0 ->
+ * MOE_ERR_BOUNDS; domain_type other than MOE_DOMAIN_TENSOR_PRODUCT -> MOE_ERR_INVALID_VALUE; then those that need the handles.
+ * MOE_ERR_SINGULAR, payload (e, i): member e, and the index i of the start (screening: into starts; later: into the kept starts)
+ * whose s^2 <= 1e-16 at any step; reported at the next wait. */
+int moe_kg_discrete_mcmc_multistart(const moe_gp_t* const* gps, int num_mcmc, int num_fidelity, const moe_gd_params_t* outer,
+                                    const double* domain_bounds, const double* discrete_all, const int* num_discrete,
+                                    const double* best_so_far, const double* starts, int num_starts, int do_gradient_ascent,
+                                    double* best_point, double* best_value, int* found, double* start_values, int* kept_index,
+                                    double* end_points, double* end_values, double* path, int* steps_taken, moe_error_t* err);
 /* compute_grad_variance_of_points -> ComputeGradVarianceOfPoints (gpp_math.cpp:1359-1373); out[num_derivs][m][m][dim] */
 int moe_gp_grad_variance(const moe_gp_t* gp, const double* pts, int num_pts, int num_derivs, double* out, moe_error_t* err);
 /* compute_grad_cholesky_variance_of_points -> ComputeGradCholeskyVarianceOfPoints (gpp_math.cpp:1454-1474) */
