@@ -15,6 +15,7 @@
 //      GTB = (K^-1 dK*/dXq)^T TB,  from which the host assembles
 //        grad KG[k,dd] = ( [winner = k] M grad mu_k  -  sum_b (DIR - GTB)[(k,b),dd]  +  < L^-1 dL/dXq_k,dd , ZC > ) / M.
 //      This is  sum_i z_i^T d(c_i)/dXq_k  of the reference (gpp_math.cpp:1601-1651) with the sum over samples pulled inside.
+//      (q-KG, m <= 8: T is never written and, by default, c_i never formed -- ZC = L^T (KB - TB^T W) L^-T, see launch_fused_tail.)
 // All reductions use fixed orders, so results are bitwise reproducible for a given shard layout.
 #include "kg.hpp"
 
@@ -535,6 +536,11 @@ inline double* dir_partials(const KgTailParams& P) {
   return P.TBpart + (long)P.E * (P.chunks + 1) * (long)P.m * P.N;
 }
 
+// (T-free tail, S_W-free form) the KB chunk partials [E][chunks][m][m] behind the DIR partials (the host reserves E chunks m m doubles more)
+__host__ __device__ inline double* kb_partials(const KgTailParams& P) {
+  return P.TBpart + (long)P.E * (P.chunks + 1) * (long)P.m * P.N + (long)P.E * P.ngrad * kDirSlices;
+}
+
 template <int DP>
 void launch_dir(const KgTailParams& P, hipStream_t s) {
   const int slices = dir_slices(P.num_local);
@@ -608,6 +614,8 @@ void launch_tail(const KgTailParams& P, hipStream_t s) {
 // re-read per entry through HBM: at C3 the covariance build + S_W + TB kernels took 86 us per evaluation, these two take
 // about half.  Operands that are uniform over the workgroup (the point tile in the first kernel, the sample chunk in the
 // second) are staged in LDS pre-scaled by 1/length and read as broadcasts.
+// By default only the second of the two runs (the S_W-free form further down: ZC from the chunk sums, no per-sample quantity);
+// MOE_KG_FUSED_ONE_PASS=0 keeps both, with kg_fused_c_kernel and the ZC chunk partials behind them, as the comparator of the tests.
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int kFusedTile = 256;  // points (kernel A) / samples (kernel B, at most: KgTailParams::chunk_len) staged per LDS tile
 
@@ -725,9 +733,12 @@ __global__ __launch_bounds__(256) void kg_fused_c_kernel(KgTailParams P, const d
 }
 
 // thread = training point: TBpart[e][chunk][c][row] = sum over the chunk's samples of K(X_row, x*_i) beta_i[c]
+// kb_rows > 0 (the S_W-free form below; kb_rows = m): the evaluation's union points follow the training points as rows n .. n + m - 1
+// of the same launch -- the same contraction at Xu_r, KBpart[e][chunk][c][r] = alpha sum_i beta_i[c] k(Xu_r, x*_i), through the same
+// radial_base on the same scaled differences as kg_fused_c_kernel's k(Xu_r, x*_i).  A training point's sums do not depend on kb_rows.
 template <int DP, int MU, int COV>
 struct kg_fused_point_kernel_body {
-  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, const KgTailParams& P, const double* __restrict__ X, int n) {
+  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, const KgTailParams& P, const double* __restrict__ X, int n, int kb_rows) {
     __shared__ double etab[kExpTabLen];
     __shared__ double St[kFusedTile][DP];
     __shared__ double Bt[kFusedTile][MU];
@@ -745,10 +756,12 @@ struct kg_fused_point_kernel_body {
       Bt[ii][c] = (ii < cnt && c < m) ? P.beta[((long)e * P.num_local + i0 + ii) * m + c] : 0.0;
     }
     __syncthreads();
+    if (row >= n + kb_rows) return;  // (no barrier below)
     const bool ok = row < n;
+    const double* __restrict__ xp = ok ? X + (long)row * DP : P.blob + (long)e * P.rec.stride + P.rec.XuP + (long)(row - n) * DP;
     double xr[DP], acc[MU];
   #pragma unroll
-    for (int k = 0; k < DP; ++k) xr[k] = ok ? X[(long)row * DP + k] * P.cp.inv_l[k] : 0.0;
+    for (int k = 0; k < DP; ++k) xr[k] = xp[k] * P.cp.inv_l[k];
   #pragma unroll
     for (int c = 0; c < MU; ++c) acc[c] = 0.0;
   #pragma unroll 2
@@ -768,166 +781,137 @@ struct kg_fused_point_kernel_body {
   #pragma unroll
       for (int c = 0; c < MU; ++c)
         if (c < m) dst[(long)c * P.N + row] = P.cp.alpha * acc[c];
+    } else {
+      double* dst = kb_partials(P) + ((long)e * P.chunks + chunk) * m * m;
+  #pragma unroll
+      for (int c = 0; c < MU; ++c)
+        if (c < m) dst[c * m + (row - n)] = P.cp.alpha * acc[c];
     }
   }
 };
 template <int DP, int MU, int COV>
-__global__ __launch_bounds__(256) void kg_fused_point_kernel(KgTailParams P, const double* __restrict__ X, int n) {
-  kg_fused_point_kernel_body<DP, MU, COV>::run(MOE_VBLOCK, MOE_VGRID, nullptr, P, X, n);
+__global__ __launch_bounds__(256) void kg_fused_point_kernel(KgTailParams P, const double* __restrict__ X, int n, int kb_rows) {
+  kg_fused_point_kernel_body<DP, MU, COV>::run(MOE_VBLOCK, MOE_VGRID, nullptr, P, X, n, kb_rows);
 }
 
-// Both contractions of T in ONE pass (r6; m <= 4, d <= 8: the headline): every entry K(X_row, x*_i) is computed once and used for
-// the TB partial of its point AND the S_W partial of its sample (the two kernels above compute every entry twice).  A wavefront
-// is an 8 x 8 grid -- lane = 8 a + b: point slot a, sample slot b -- that walks the chunk's 128 samples eight at a time (si; the
-// sample's coordinates and beta in registers) against its 32 points eight at a time (pi; coordinates and the row of W from LDS):
-// the S_W sums of a sample live across the pi loop and are added up over the eight point slots once per si; the TB sums of the
-// 4 x 8 points live in registers (4 MU doubles per lane) across the whole walk and are added up over the eight sample slots once
-// per wavefront.  The eight wavefronts' S_W sums meet in LDS and are added in wavefront order: SWpart[e][i][point block][c], one
-// partial per 256 points, summed in block order by kg_fused_c_kernel.  Every order is fixed and a function of (n, num_local)
-// alone: an evaluation's bits do not depend on its batch.
-// Measured at C3 (64 evaluations per launch): 1.71 ms against 0.93 + 0.89 ms of the two kernels on the same box, not the 0.95 the
-// instruction count promises (46 VALU instructions per 64 entries): with both operands varying over the lanes every entry costs
-// 7.5 ds_read_b128 where the two-kernel forms read one broadcast row, and the LDS pipe (1.05 ms) and the vector ALU (0.81 ms)
-// overlap badly at four wavefronts per SIMD.  Forms tried and dropped (profiles/r06_aj_*): 64 points per wavefront on four
-// wavefronts (two per SIMD: 1.68 ms), two samples per lane against one point read (half the LDS traffic, 256 VGPRs: 1.99 ms),
-// the wavefront's points held in registers (no LDS reads in the loop, two wavefronts per SIMD: 2.05 ms).
-template <int DP, int MU, int COV>
-struct kg_fused_pair_kernel_body {
-  static constexpr int SB = kFusedChunk / 8;  // sample blocks of eight
-  static constexpr int SROW = DP + 2;         // row stride of the staged points: eight rows 16-byte aligned on distinct banks
-  static constexpr int NW = 8, PB = 4;        // wavefronts per workgroup, point blocks of eight per wavefront: 8 x 32 = 256 points
-  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, const KgTailParams& P, const double* __restrict__ X, int n, double* __restrict__ SWpart) {
-    static_assert(MU <= 4 && kFusedChunk == 128, "4 point blocks x MU sums per lane");
-    __shared__ double etab[kExpTabLen];
-    __shared__ __attribute__((aligned(16))) double St[kFusedChunk][SROW];
-    __shared__ __attribute__((aligned(16))) double Bt[kFusedChunk][MU];
-    __shared__ __attribute__((aligned(16))) double Xt[256][SROW];
-    __shared__ __attribute__((aligned(16))) double Wt[256][MU];
-    __shared__ double Sx[NW][kFusedChunk][MU];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int a = lane >> 3, b = lane & 7;
-    const int chunk = blockIdx.y, e = blockIdx.z, m = P.m, N = P.N;
-    const int i0 = chunk * P.chunk_len, cnt = min(P.num_local - i0, P.chunk_len);  // (chunk_len == kFusedChunk)
-    const long w0 = (long)e * P.num_local + i0;
-    const int row0 = blockIdx.x * 256;
-    if (threadIdx.x < kExpTabLen) etab[threadIdx.x] = kExp2Tab64[threadIdx.x];
-    for (int t = threadIdx.x; t < kFusedChunk * DP; t += 64 * NW) {
-      const int ii = t / DP, k = t % DP;
-      St[ii][k] = (ii < cnt) ? P.best_point[(w0 + ii) * DP + k] * P.cp.inv_l[k] : 0.0;
+// The S_W-free form of the T-free tail (the default: MOE_KG_FUSED_ONE_PASS=1; every shape of the T-free path).  S_W,i = W^T T_i is
+// only ever used in c_i = L^-1 alpha (k(Xu, x*_i) - S_W,i), and c_i only in ZC = sum_i z_i c_i^T.  With z_i = L^T beta_i (the MC
+// kernel's own beta_i = L^-T z_i) the sum over the samples moves inside:
+//     ZC = L^T ( KB - TB^T W ) L^-T,    KB[c][r] = alpha sum_i beta_i[c] k(Xu_r, x*_i),    TB = the alpha-scaled sum GTB already uses,
+// so the second contraction of T (kg_fused_sample_kernel, or the one-pass kg_fused_pair_kernel that held both sets of partial sums
+// in registers and was LDS-bound at low occupancy: 1.71 ms per 64 C3 evaluations against kg_fused_point_kernel's 0.89) and every
+// per-sample quantity of the tail (S_W, c_i, the ZC chunk partials) drop out: KB is the TB contraction at m more rows of the point
+// kernel, TB^T W is m m dot products of length N per evaluation.  The gradient changes by rounding only; where the posterior
+// covariance between Xu and x* is far below the prior one the subtraction happens after the sum over the samples instead of inside
+// every sample (tests/test_gpu_sw_free_tail.py bounds that case against the CPU oracle).
+// One workgroup per evaluation: thread = row (stride 256) with all m x m products in registers, a fixed butterfly per wavefront and
+// the four wavefronts added as (0 + 1) + (2 + 3); the KB chunk partials by groups of m m lanes striding the chunks, the groups added
+// in order.  Every order is a function of (N, m, num_local) alone.  Then A = L^T B and ZC = A L^-T by substitution along each row.
+template <int MU>
+struct kg_zc_direct_kernel_body {
+  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, const KgTailParams& P, const double* __restrict__ TBsum) {
+    __shared__ double red[4][MU * MU], kbs[256], Bs[MU * MU], As[MU * MU];
+    const int e = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int m = P.m, N = P.N, mm = m * m;
+    const double* __restrict__ tb = TBsum + (long)e * m * N;
+    const double* __restrict__ We = P.W + (long)e * P.w_stride;
+    double acc[MU][MU];
+  #pragma unroll
+    for (int c = 0; c < MU; ++c)
+  #pragma unroll
+      for (int r = 0; r < MU; ++r) acc[c][r] = 0.0;
+  #pragma unroll 2
+    for (int row = tid; row < N; row += 256) {
+      double t[MU], w[MU];
+  #pragma unroll
+      for (int c = 0; c < MU; ++c) {  // (m is uniform; columns beyond it feed sums that are never read)
+        t[c] = (c < m) ? tb[(long)c * N + row] : 0.0;
+        w[c] = (c < m) ? We[(long)c * N + row] : 0.0;
+      }
+  #pragma unroll
+      for (int c = 0; c < MU; ++c)
+  #pragma unroll
+        for (int r = 0; r < MU; ++r) acc[c][r] = fma(t[c], w[r], acc[c][r]);
     }
-    for (int t = threadIdx.x; t < kFusedChunk * MU; t += 64 * NW) {
-      const int ii = t / MU, c = t % MU;
-      Bt[ii][c] = (ii < cnt && c < m) ? P.beta[(w0 + ii) * m + c] : 0.0;  // zero beta: padded samples drop out of TB
-    }
-    for (int t = threadIdx.x; t < 256 * DP; t += 64 * NW) {
-      const int jj = t / DP, k = t % DP;
-      Xt[jj][k] = (row0 + jj < n) ? X[(long)(row0 + jj) * DP + k] * P.cp.inv_l[k] : 0.0;
-    }
+  #pragma unroll
+    for (int c = 0; c < MU; ++c)
+  #pragma unroll
+      for (int r = 0; r < MU; ++r) {
+        const double v = wave_sum64(acc[c][r]);
+        if (lane == 0) red[wave][c * MU + r] = v;
+      }
     {
-      const double* We = P.W + (long)e * P.w_stride;
-      for (int t = threadIdx.x; t < 256 * MU; t += 64 * NW) {
-        const int jj = t % 256, c = t / 256;  // W_e is [N x m] col-major: consecutive jj are contiguous
-        Wt[jj][c] = (row0 + jj < n && c < m) ? We[(long)c * N + row0 + jj] : 0.0;  // zero weight: padded points drop out of S_W
+      const int groups = 256 / mm;  // >= 4
+      const int o = tid % mm, g = tid / mm;
+      const double* __restrict__ kp = kb_partials(P) + (long)e * P.chunks * mm + o;
+      double v = 0.0;
+      if (g < groups) {
+  #pragma unroll 4
+        for (int ch = g; ch < P.chunks; ch += groups) v += kp[(long)ch * mm];
       }
+      kbs[tid] = v;
     }
     __syncthreads();
-    double tb[PB][MU];
-  #pragma unroll
-    for (int pi = 0; pi < PB; ++pi)
-  #pragma unroll
-      for (int c = 0; c < MU; ++c) tb[pi][c] = 0.0;
-    const int jw = wave * (8 * PB) + a;
-  #pragma unroll 1
-    for (int si = 0; si < SB; ++si) {
-      const int ii = si * 8 + b;
-      int hold = 0;
-      asm volatile("" : "+v"(hold));  // (an index the optimiser cannot see through: the point tile is READ per sample block -- kept in registers, 4 x 8 points
-                                      //  cost 80 VGPRs and with them half the wavefronts: 1.71 -> 2.05 ms per 64 evaluations at C3)
-      double xs[DP], bs[MU], sw[MU];
-  #pragma unroll
-      for (int k = 0; k < DP; ++k) xs[k] = St[ii][k];
-  #pragma unroll
-      for (int c = 0; c < MU; ++c) {
-        bs[c] = Bt[ii][c];
-        sw[c] = 0.0;
-      }
-  #pragma unroll
-      for (int pi = 0; pi < PB; ++pi) {
-        const int jj = jw + pi * 8 + hold;
-        double r2 = 1.0e-300;
-  #pragma unroll
-        for (int k = 0; k < DP; ++k) {
-          const double dlt = Xt[jj][k] - xs[k];
-          r2 = fma(dlt, dlt, r2);
-        }
-        const double t = radial_base<COV>(r2, etab);
-  #pragma unroll
-        for (int c = 0; c < MU; ++c) {
-          tb[pi][c] = fma(t, bs[c], tb[pi][c]);
-          sw[c] = fma(Wt[jj][c], t, sw[c]);
-        }
-      }
-      // S_W partial of sample ii over this wavefront's 32 points: the eight point slots added up (lanes b, b + 8, ...)
-  #pragma unroll
-      for (int c = 0; c < MU; ++c) {
-        double v = sw[c];
-        v += __shfl_xor(v, 8, 64);
-        v += __shfl_xor(v, 16, 64);
-        v += __shfl_xor(v, 32, 64);
-        if (a == 0) Sx[wave][ii][c] = v;
-      }
+    if (tid < mm) {
+      const int groups = 256 / mm;
+      const int c = tid / m, r = tid - c * m;
+      double kb = 0.0;
+      for (int g = 0; g < groups; ++g) kb += kbs[g * mm + tid];
+      const int o = c * MU + r;
+      Bs[tid] = kb - ((red[0][o] + red[1][o]) + (red[2][o] + red[3][o]));
     }
-    // TB partial of point jw + 8 pi: the eight sample slots added up (lanes 8 a .. 8 a + 7)
-    double* dst = P.TBpart + ((long)e * P.chunks + chunk) * m * N;
-  #pragma unroll
-    for (int pi = 0; pi < PB; ++pi)
-  #pragma unroll
-      for (int c = 0; c < MU; ++c) {
-        double v = tb[pi][c];
-        v += __shfl_xor(v, 1, 64);
-        v += __shfl_xor(v, 2, 64);
-        v += __shfl_xor(v, 4, 64);
-        const int row = row0 + jw + pi * 8;
-        if (b == 0 && c < m && row < n) dst[(long)c * N + row] = P.cp.alpha * v;
-      }
     __syncthreads();
-    const int slices = gridDim.x;
-    for (int t = threadIdx.x; t < kFusedChunk * MU; t += 64 * NW) {
-      const int ii = t / MU, c = t % MU;
-      if (ii < cnt) {
-        double v = Sx[0][ii][c];
+    const double* Lsm = P.blob + (long)e * P.rec.stride + P.rec.L;  // m x m, column-major, lower
+    if (tid < mm) {  // A[a][r] = sum_{c >= a} L[c][a] B[c][r]
+      const int a = tid / m, r = tid - a * m;
+      double v = 0.0;
+      for (int c = a; c < m; ++c) v = fma(Lsm[c + a * m], Bs[c * m + r], v);
+      As[tid] = v;
+    }
+    __syncthreads();
+    if (tid < m) {  // row tid of ZC L^T = A, ascending columns
+      double* out = P.out + (long)e * P.out_stride + 1;
+      double zc[MU];
   #pragma unroll
-        for (int wv = 1; wv < NW; ++wv) v += Sx[wv][ii][c];
-        SWpart[((w0 + ii) * slices + blockIdx.x) * MU + c] = v;
+      for (int j = 0; j < MU; ++j) {
+        zc[j] = 0.0;
+        if (j < m) {
+          double v = As[tid * m + j];
+  #pragma unroll
+          for (int k = 0; k < MU; ++k)
+            if (k < j) v = fma(-zc[k], Lsm[j + k * m], v);
+          zc[j] = v / Lsm[j + j * m];
+          out[tid + j * m] = zc[j];
+        }
       }
     }
   }
 };
-template <int DP, int MU, int COV>
-__global__ __launch_bounds__(512, 2) void kg_fused_pair_kernel(KgTailParams P, const double* __restrict__ X, int n, double* __restrict__ SWpart) {
-  kg_fused_pair_kernel_body<DP, MU, COV>::run(MOE_VBLOCK, MOE_VGRID, nullptr, P, X, n, SWpart);
+template <int MU>
+__global__ __launch_bounds__(256) void kg_zc_direct_kernel(KgTailParams P, const double* __restrict__ TBsum) {
+  kg_zc_direct_kernel_body<MU>::run(MOE_VBLOCK, MOE_VGRID, nullptr, P, TBsum);
 }
 
-// whether an evaluation's T-free tail takes the one-pass kernel (a function of its shape alone), and how many S_W partials a sample then has
-inline bool fused_tail_one_pass(int m, int dp) { return m <= 4 && dp <= 8 && env_int("MOE_KG_FUSED_ONE_PASS", 1) != 0; }
+// which form the T-free tail takes: a switch of the process, never a function of the batch
+inline bool fused_tail_sw_free() { return env_int("MOE_KG_FUSED_ONE_PASS", 1) != 0; }
 
 template <int DP, int MU, int COV>
 void launch_fused_tail_cov(const KgTailParams& P, const double* X, int n, double* SWpart, int slices, hipStream_t s) {
-  dim3 ga((P.num_local + 255) / 256, P.E, slices), gc((P.num_local + 255) / 256, P.E), gb((n + 255) / 256, P.chunks, P.E);
-  if constexpr (MU <= 4 && DP <= 8) {
-    if (fused_tail_one_pass(P.m, DP)) {  // (slices == gb.x: fused_tail_slices)
-      launch_kernel_ens<kg_fused_pair_kernel_body<DP, MU, COV>, 512, 2>(kg_fused_pair_kernel<DP, MU, COV>, gb, dim3(512), 0, s, P, X, n, SWpart);
-      launch_kernel_ens<kg_fused_c_kernel_body<DP, MU, COV>, 256>(kg_fused_c_kernel<DP, MU, COV>, gc, dim3(256), 0, s, P, SWpart, (int)gb.x);
-      launch_dir<DP>(P, s);
-      launch_gtb(P, s);
-      MOE_HIP_CHECK(hipGetLastError());
-      return;
-    }
+  if (fused_tail_sw_free()) {
+    dim3 gb((n + P.m + 255) / 256, P.chunks, P.E);  // (the m union rows behind the training points)
+    launch_kernel_ens<kg_fused_point_kernel_body<DP, MU, COV>, 256>(kg_fused_point_kernel<DP, MU, COV>, gb, dim3(256), 0, s, P, X, n, P.m);
+    launch_dir<DP>(P, s);
+    launch_gtb(P, s);
+    const double* TBsum = P.TBpart + (long)P.E * P.chunks * (long)P.m * P.N;  // (launch_gtb)
+    launch_kernel_ens<kg_zc_direct_kernel_body<MU>, 256>(kg_zc_direct_kernel<MU>, dim3(P.E), dim3(256), 0, s, P, TBsum);
+    MOE_HIP_CHECK(hipGetLastError());
+    return;
   }
+  dim3 ga((P.num_local + 255) / 256, P.E, slices), gc((P.num_local + 255) / 256, P.E), gb((n + 255) / 256, P.chunks, P.E);
   launch_kernel_ens<kg_fused_sample_kernel_body<DP, MU, COV>, 256>(kg_fused_sample_kernel<DP, MU, COV>, ga, dim3(256), 0, s, P, X, n, SWpart);
   launch_kernel_ens<kg_fused_c_kernel_body<DP, MU, COV>, 256>(kg_fused_c_kernel<DP, MU, COV>, gc, dim3(256), 0, s, P, SWpart, slices);
   launch_dir<DP>(P, s);
-  launch_kernel_ens<kg_fused_point_kernel_body<DP, MU, COV>, 256>(kg_fused_point_kernel<DP, MU, COV>, gb, dim3(256), 0, s, P, X, n);
+  launch_kernel_ens<kg_fused_point_kernel_body<DP, MU, COV>, 256>(kg_fused_point_kernel<DP, MU, COV>, gb, dim3(256), 0, s, P, X, n, 0);
   launch_gtb(P, s);
   MOE_HIP_CHECK(hipGetLastError());
 }
@@ -942,8 +926,7 @@ void launch_fused_tail_inst(const KgTailParams& P, const double* X, int n, doubl
 
 // number of point slices of kg_fused_sample_kernel: enough wavefronts for ~4 per SIMD when ONE evaluation runs alone.  It does not
 // depend on the batch size: the slices are summed in order, so an evaluation's bits would otherwise change with its batch.
-int fused_tail_slices(int /*E*/, int num_local, int n, int num_cu, int m, int dp) {
-  if (fused_tail_one_pass(m, dp)) return (n + 255) / 256;  // the one-pass kernel: one S_W partial per block of 256 points
+int fused_tail_slices(int /*E*/, int num_local, int n, int num_cu) {
   const long waves = (long)((num_local + 255) / 256) * 4;
   const long want = (long)num_cu * 4 * 4;
   int s = (int)std::min<long>(8, std::max<long>(1, (want + waves - 1) / waves));
@@ -2031,12 +2014,15 @@ KgTailParams launch_tail_step(GpDev& gp, const KgDims& k, const McPlan& pl, cons
     t_cov.start(s);
     t_cov.stop(s);  // no covariance matrix is built on this path
     t_tail.start(s);
-    const int slices = fused_tail_slices(E, num_local, n, gp.num_cu, m, k.dp);
-    gp.kSW.reserve((size_t)E * num_local * slices * 8);  // [E][num_local][slices][MU <= 8]
-    launch_fused_tail(tl, gp.dX.p, n, gp.kSW.p, slices, s);
-    // (r4: m > 64 too -- one workgroup per entry of ZC walking every sample with a stride of m doubles took 1.8 ms per evaluation at m = 104)
-    gp.kZcPart.reserve((size_t)E * ((num_local + zc_chunk_len(m) - 1) / zc_chunk_len(m)) * m * m);
-    launch_zc(tl, gp.kZcPart.p, s, !zc_sum_in_finish(m, num_local));
+    if (fused_tail_sw_free()) {  // no per-sample workspace: ZC comes from the chunk sums (kg_zc_direct_kernel)
+      launch_fused_tail(tl, gp.dX.p, n, nullptr, 0, s);
+    } else {
+      const int slices = fused_tail_slices(E, num_local, n, gp.num_cu);
+      gp.kSW.reserve((size_t)E * num_local * slices * 8);  // [E][num_local][slices][MU <= 8]
+      launch_fused_tail(tl, gp.dX.p, n, gp.kSW.p, slices, s);
+      gp.kZcPart.reserve((size_t)E * ((num_local + zc_chunk_len(m) - 1) / zc_chunk_len(m)) * m * m);
+      launch_zc(tl, gp.kZcPart.p, s, !zc_sum_in_finish(m, num_local));
+    }
   } else if (k.want_grad) {
     DerivList none;
     none.g = 0;
@@ -2081,7 +2067,7 @@ KgTailParams launch_tail_step(GpDev& gp, const KgDims& k, const McPlan& pl, cons
 
 // grad KG from the sample sums, on the device (kg_state.hip)
 void launch_grad_finish(GpDev& gp, const KgDims& k, const KgStateParams& sp, const KgTailParams& tl, const KgRecords& R, double* dBlobP,
-                        double* dFin, int out_stride, hipStream_t s) {
+                        double* dFin, int out_stride, bool zc_direct, hipStream_t s) {
   const int m = k.m, num_local = k.num_local;
   KgFinishParams fp;
   fp.E = k.E;
@@ -2105,7 +2091,8 @@ void launch_grad_finish(GpDev& gp, const KgDims& k, const KgStateParams& sp, con
   fp.flags = gp.kStateI.p;
   fp.dir_part = dir_partials(tl);
   fp.dir_slices = dir_slices(num_local);
-  fp.zc_part = zc_sum_in_finish(m, num_local) ? gp.kZcPart.p : nullptr;
+  fp.zc_part = (!zc_direct && zc_sum_in_finish(m, num_local)) ? gp.kZcPart.p : nullptr;
+  fp.zc_direct = zc_direct ? gp.kOut.p + 1 : nullptr;  // (kg_zc_direct_kernel left ZC itself there; kg_sum is still the finish kernel's)
   fp.zc_chunks = (num_local + zc_chunk_len(m) - 1) / zc_chunk_len(m);
   fp.zc_gs = zc_sum_lanes(m);
   fp.best_value = gp.kBestValue.p;
@@ -2280,11 +2267,13 @@ KgPending kg_launch(GpDev& gp, int num_fidelity, const moe_gd_params_t& gd, cons
   gp.kCounters.reserve(n_ctr);
   const int out_stride = 1 + m * m + 2 * k.ngrad;
   gp.kOut.reserve((size_t)out_stride * E);
+  const bool sw_free = pl.fused_tail && fused_tail_sw_free();  // the T-free tail without its per-sample W^T T sums
   if (want_grad) {
     const int chunks = (num_local + pl.chunk_len - 1) / pl.chunk_len;
     if (!pl.fused_tail) gp.kT.reserve((size_t)N * E * num_local);
-    gp.kC.reserve((size_t)E * num_local * m);
-    gp.kTB.reserve((size_t)E * (chunks + 1) * m * N + (size_t)E * k.ngrad * kDirSlices);  // chunk partials + their sum + DIR partials
+    if (!sw_free) gp.kC.reserve((size_t)E * num_local * m);
+    // chunk partials + their sum + DIR partials + (S_W-free tail) KB chunk partials
+    gp.kTB.reserve((size_t)E * (chunks + 1) * m * N + (size_t)E * k.ngrad * kDirSlices + (sw_free ? (size_t)E * chunks * m * m : 0));
   }
 
   // ---- coordinate tables ----
@@ -2314,7 +2303,7 @@ KgPending kg_launch(GpDev& gp, int num_fidelity, const moe_gd_params_t& gd, cons
   // ---- 3. gradient tail ----
   const KgTailParams tl = launch_tail_step(gp, k, pl, mp, R, dBlobP, dNormalsP, se.bl, dFin, out_stride, t_cov, t_tail, s);
   if (want_grad) {
-    launch_grad_finish(gp, k, sp, tl, R, dBlobP, dFin, out_stride, s);
+    launch_grad_finish(gp, k, sp, tl, R, dBlobP, dFin, out_stride, sw_free, s);
     t_tail.stop(s);
   }
   return enqueue_results(gp, k, dFin, n_ctr, want_best_points, timers, wall0, s);

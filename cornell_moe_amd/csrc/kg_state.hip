@@ -339,7 +339,9 @@ struct kg_finish_small_kernel_body {
     const int idx = blockIdx.x, e = blockIdx.y, tid = threadIdx.x;
     const int m = P.m, qd = P.q * P.d;
     const int tri = m * (m + 1) / 2;
-    {
+    if (P.zc_part == nullptr) {  // (uniform) ZC as kg_zc_direct_kernel left it
+      if (tid < m * m) zcs[tid] = P.zc_direct[(long)e * P.out_stride + tid];
+    } else {
       const int gs = P.zc_gs, per_block = 256 / gs;
       for (int base = 0; base < m * m; base += per_block) {
         const int oo = base + tid / gs, g = tid % gs;
@@ -425,7 +427,7 @@ void launch_kg_dchol(const KgStateParams& P, hipStream_t s) {
 }
 
 void launch_kg_finish(const KgFinishParams& P, double* Y, hipStream_t s) {
-  if (P.zc_part != nullptr) {  // (m <= 8: the caller did not launch kg_zc_sum_kernel)
+  if (P.zc_part != nullptr || P.zc_direct != nullptr) {  // (m <= 8: the caller did not launch kg_zc_sum_kernel)
     launch_kernel_ens<kg_finish_small_kernel_body, 256>(kg_finish_small_kernel, dim3(P.q * P.d, P.E), dim3(256), 0, s, P);
   } else {
     const size_t shm = sizeof(double) * (size_t)P.m * (P.m + 1);

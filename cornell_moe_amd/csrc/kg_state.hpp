@@ -59,12 +59,15 @@ struct KgFinishParams {
   // sum) -- that kernel is then not launched.  Otherwise both are read from `out`.
   const double* zc_part;
   int zc_chunks, zc_gs;
+  // zc_part == NULL and zc_direct != NULL (the T-free tail's S_W-free form, m <= 8): ZC itself, m x m column-major, of evaluation e at
+  // zc_direct + e * out_stride; the one-launch finish reads it instead of summing chunk partials and forms kg_sum exactly as above.
+  const double* zc_direct;
   const double* best_value;  // [E][num_local]
   int num_local, rec_bp;
 };
 // grad KG from the sample sums: < L^-1 dL, ZC > taken as < dL, L^-T tril(ZC) > (one m-column back substitution per evaluation
 // instead of q d m forward ones), the DIR - GTB terms and the winner's grad mu.  Y: E m (m + 1) / 2 doubles of workspace.  Two kernels
-// (Y, then a wavefront per gradient component); for m <= 8 with zc_part set ONE, which also takes kg_zc_sum_kernel's place (r5).
+// (Y, then a wavefront per gradient component); for m <= 8 with zc_part or zc_direct set ONE, which also takes kg_zc_sum_kernel's place (r5).
 void launch_kg_finish(const KgFinishParams& P, double* Y, hipStream_t s);
 
 }  // namespace moe
