@@ -72,6 +72,12 @@ SIGNATURES = {
     "moe_kg_discrete_mcmc": (C.c_int, [_GPA, C.c_int, C.c_int, dp, ip, dp, dp, C.c_int, C.c_int, dp, dp, _EP]),
     "moe_kg_discrete_mcmc_multistart": (C.c_int, [_GPA, C.c_int, C.c_int, C.POINTER(GdParams), dp, dp, ip, dp, dp, C.c_int, C.c_int,
                                                   dp, dp, ip, dp, ip, dp, dp, dp, ip, _EP]),
+    "moe_gp_kg_discrete_last_active": (C.c_int, [_GP, C.c_int, ip, _EP]),
+    "moe_kg_discrete_mcmc_pending": (C.c_int, [_GPA, C.c_int, C.c_int, dp, ip, dp, dp, C.c_int, dp, C.c_int, C.c_int, dp, dp, _EP]),
+    "moe_kg_discrete_mcmc_multistart_pending": (C.c_int, [_GPA, C.c_int, C.c_int, C.POINTER(GdParams), dp, dp, ip, dp, dp, C.c_int, dp,
+                                                          C.c_int, C.c_int, dp, dp, ip, dp, ip, dp, dp, dp, ip, _EP]),
+    "moe_kg_discrete_mcmc_suggest": (C.c_int, [_GPA, C.c_int, C.c_int, C.POINTER(GdParams), dp, dp, ip, dp, dp, C.c_int, dp, C.c_int,
+                                               C.c_int, C.c_int, dp, dp, ip, _EP]),
     "moe_gp_grad_variance": (C.c_int, [_GP, dp, C.c_int, C.c_int, dp, _EP]),
     "moe_gp_grad_cholesky_variance": (C.c_int, [_GP, dp, C.c_int, C.c_int, dp, _EP]),
     "moe_posterior_mean": (C.c_int, [_GP, C.c_int, dp, dp, dp, _EP]),

@@ -325,11 +325,26 @@ class DeviceGP(object):
             return index, points, kept.value, mean, std
         return index, points, kept.value
 
-    def kg_discrete(self, discrete, points, best_so_far, num_fidelity=0, want_grad=True, want_active=False):
+    def kg_discrete(self, discrete, points, best_so_far, num_fidelity=0, want_grad=True, want_active=False,
+                    points_being_sampled=None):
         """moe_gp_kg_discrete: the exact discretised one-point knowledge gradient of points [C][dim] over the discrete set
         [A][dim - num_fidelity] (a lower bound of the continuous knowledge gradient), for a GP without derivative observations.
         Returns kg [C], with want_grad (kg, grad [C][dim]), with want_active the number of lines on the envelope [C] behind them.
-        SingularMatrixException(1, i) for the first candidate i with Sigma_n(x, x) + noise <= 1e-16."""
+        SingularMatrixException(1, i) for the first candidate i with Sigma_n(x, x) + noise <= 1e-16.
+        points_being_sampled [p][dim] (None or empty: the call and bits of before): the posterior covariance is conditioned on these
+        pending points, the posterior mean is not (moe_kg_discrete_mcmc_pending with this GP as an ensemble of one;
+        SingularMatrixException(0, j) for a pending point j that makes the conditioned covariance singular)."""
+        if _num_pending(points_being_sampled, self.d):
+            res = kg_discrete_ensemble(self, [discrete], points, [best_so_far], num_fidelity=num_fidelity, want_grad=want_grad,
+                                       points_being_sampled=points_being_sampled)
+            out = (res if want_grad else (res,))
+            if want_active:
+                C_ = out[0].shape[0]
+                active = np.zeros(C_, dtype=np.int32)
+                err = _lib.MoeError()
+                _check(_lib.load().moe_gp_kg_discrete_last_active(self._h, C_, active.ctypes.data_as(ip), C.byref(err)), err)
+                out = tuple(out) + (active,)
+            return out[0] if len(out) == 1 else tuple(out)
         nf = int(num_fidelity)
         size = self.d - nf
         if not 0 < size <= self.d:
@@ -828,6 +843,13 @@ def kg_discrete_mcmc(gps, discrete_all, points, best_so_far_all, num_fidelity=0,
     return (kg, grad / len(members)) if want_grad else kg
 
 
+def _num_pending(points_being_sampled, d):
+    """the number of pending points [p][dim] (0 for None or an empty array)"""
+    if points_being_sampled is None:
+        return 0
+    return int(np.asarray(points_being_sampled, dtype=np.float64).size // max(int(d), 1))
+
+
 def _kg_discrete_members(gps, discrete_all, best_so_far_all, num_fidelity):
     """(handles, count, dim, members kept alive, sets back to back, their sizes, best values) of the ensemble forms of kg_discrete;
     a single DeviceGP counts as a list of one"""
@@ -846,17 +868,27 @@ def _kg_discrete_members(gps, discrete_all, best_so_far_all, num_fidelity):
     return arr, E, d, keep, disc, counts, best
 
 
-def kg_discrete_ensemble(gps, discrete_all, points, best_so_far_all, num_fidelity=0, want_grad=True):
+def kg_discrete_ensemble(gps, discrete_all, points, best_so_far_all, num_fidelity=0, want_grad=True, points_being_sampled=None):
     """moe_kg_discrete_mcmc: what kg_discrete_mcmc returns, bit for bit, in one device call for the whole ensemble (one upload, one
     stream, one wait; every kernel launched once for all members where their launches line up).  gps: a DeviceGPMCMC, a list of
     DeviceGP (they need not share their sampled points) or one DeviceGP.  Returns kg [C], with want_grad (kg, grad [C][dim]).
-    SingularMatrixException(e, i): member e, candidate i."""
+    SingularMatrixException(e, i): member e, candidate i.
+    points_being_sampled [p][dim] (None or empty: the symbol and bits of before): moe_kg_discrete_mcmc_pending -- every member's
+    posterior covariance conditioned on the pending points, its mean left alone; SingularMatrixException(e, j) for pending point j."""
     arr, E, d, keep, disc, counts, best = _kg_discrete_members(gps, discrete_all, best_so_far_all, num_fidelity)
     pts, pp = _d(points)
     C_ = pts.reshape(-1, d).shape[0]
     kg = np.zeros(max(C_, 1))
     grad = np.zeros((max(C_, 1), d)) if want_grad else None
     err = _lib.MoeError()
+    p = _num_pending(points_being_sampled, d)
+    if p:
+        pend, pendp = _d(points_being_sampled)
+        _check(_lib.load().moe_kg_discrete_mcmc_pending(arr, E, int(num_fidelity), disc.ctypes.data_as(dp), counts.ctypes.data_as(ip),
+                                                        best.ctypes.data_as(dp), pendp, p, pp, C_, 1 if want_grad else 0,
+                                                        kg.ctypes.data_as(dp), grad.ctypes.data_as(dp) if want_grad else None,
+                                                        C.byref(err)), err)
+        return (kg, grad) if want_grad else kg
     _check(_lib.load().moe_kg_discrete_mcmc(arr, E, int(num_fidelity), disc.ctypes.data_as(dp), counts.ctypes.data_as(ip),
                                             best.ctypes.data_as(dp), pp, C_, 1 if want_grad else 0, kg.ctypes.data_as(dp),
                                             grad.ctypes.data_as(dp) if want_grad else None, C.byref(err)), err)
@@ -864,11 +896,13 @@ def kg_discrete_ensemble(gps, discrete_all, points, best_so_far_all, num_fidelit
 
 
 def kg_discrete_multistart(gps, gd_params, bounds, discrete_all, best_so_far_all, starts, num_fidelity=0, gradient_ascent=True,
-                           want_path=False):
+                           want_path=False, points_being_sampled=None):
     """moe_kg_discrete_mcmc_multistart: one suggestion by the ensemble-averaged discretised knowledge gradient -- the value at
     every start [S][dim], the 20 best kept, restarted gradient ascent on all of them on the device, the value at every end point,
     the best one returned.  Returns a dict: point [dim], value, found, start_values [S], and with gradient_ascent kept_index [K],
-    end_points [K][dim], end_values [K], steps_taken [K] (None without), with want_path path [K][restarts steps + 1][dim]."""
+    end_points [K][dim], end_values [K], steps_taken [K] (None without), with want_path path [K][restarts steps + 1][dim].
+    points_being_sampled [p][dim] (None or empty: the symbol and bits of before): moe_kg_discrete_mcmc_multistart_pending, the same
+    ascent on the knowledge gradient conditioned on the pending points."""
     arr, E, d, keep, disc, counts, best = _kg_discrete_members(gps, discrete_all, best_so_far_all, num_fidelity)
     g = DeviceGP._gd(gd_params)
     bounds, bp = _d(bounds)
@@ -884,17 +918,46 @@ def kg_discrete_multistart(gps, gd_params, bounds, discrete_all, best_so_far_all
     path = np.zeros((K, rows, d)) if (want_path and gradient_ascent) else None
     value, found = C.c_double(0.0), C.c_int(0)
     err = _lib.MoeError()
-    _check(_lib.load().moe_kg_discrete_mcmc_multistart(
-        arr, E, int(num_fidelity), C.byref(g), bp, disc.ctypes.data_as(dp), counts.ctypes.data_as(ip), best.ctypes.data_as(dp), sp, S,
-        1 if gradient_ascent else 0, point.ctypes.data_as(dp), C.byref(value), C.byref(found), start_values.ctypes.data_as(dp),
-        kept.ctypes.data_as(ip), ends.ctypes.data_as(dp), end_values.ctypes.data_as(dp),
-        path.ctypes.data_as(dp) if path is not None else None, steps.ctypes.data_as(ip), C.byref(err)), err)
+    tail = (sp, S, 1 if gradient_ascent else 0, point.ctypes.data_as(dp), C.byref(value), C.byref(found), start_values.ctypes.data_as(dp),
+            kept.ctypes.data_as(ip), ends.ctypes.data_as(dp), end_values.ctypes.data_as(dp),
+            path.ctypes.data_as(dp) if path is not None else None, steps.ctypes.data_as(ip), C.byref(err))
+    head = (arr, E, int(num_fidelity), C.byref(g), bp, disc.ctypes.data_as(dp), counts.ctypes.data_as(ip), best.ctypes.data_as(dp))
+    p = _num_pending(points_being_sampled, d)
+    if p:
+        pend, pendp = _d(points_being_sampled)
+        _check(_lib.load().moe_kg_discrete_mcmc_multistart_pending(*(head + (pendp, p) + tail)), err)
+    else:
+        _check(_lib.load().moe_kg_discrete_mcmc_multistart(*(head + tail)), err)
     out = {"point": point, "value": value.value, "found": bool(found.value), "start_values": start_values,
            "kept_index": kept if gradient_ascent else None, "end_points": ends if gradient_ascent else None,
            "end_values": end_values if gradient_ascent else None, "steps_taken": steps if gradient_ascent else None}
     if want_path:
         out["path"] = path
     return out
+
+
+def kg_discrete_suggest(gps, gd_params, bounds, discrete_all, best_so_far_all, starts, num_to_sample, num_fidelity=0,
+                        gradient_ascent=True, points_being_sampled=None):
+    """moe_kg_discrete_mcmc_suggest: num_to_sample points greedily by the ensemble-averaged discretised knowledge gradient -- round t
+    is kg_discrete_multistart from the same starts [S][dim] with the pending points points_being_sampled [p][dim] (may be None)
+    followed by the points of the rounds before, bit for bit, in one device call: the set phase runs once and a round appends one
+    row to every member's extension.  p + num_to_sample - 1 <= 64.  Returns a dict: points [q][dim], values [q], found [q]."""
+    arr, E, d, keep, disc, counts, best = _kg_discrete_members(gps, discrete_all, best_so_far_all, num_fidelity)
+    g = DeviceGP._gd(gd_params)
+    bounds, bp = _d(bounds)
+    starts, sp = _d(starts)
+    S = starts.reshape(-1, d).shape[0]
+    q = int(num_to_sample)
+    p = _num_pending(points_being_sampled, d)
+    pend, pendp = _d(points_being_sampled) if p else (None, None)
+    points, values = np.zeros((max(q, 1), d)), np.zeros(max(q, 1))
+    found = np.zeros(max(q, 1), dtype=np.int32)
+    err = _lib.MoeError()
+    _check(_lib.load().moe_kg_discrete_mcmc_suggest(
+        arr, E, int(num_fidelity), C.byref(g), bp, disc.ctypes.data_as(dp), counts.ctypes.data_as(ip), best.ctypes.data_as(dp), pendp, p,
+        sp, S, 1 if gradient_ascent else 0, q, points.ctypes.data_as(dp), values.ctypes.data_as(dp), found.ctypes.data_as(ip),
+        C.byref(err)), err)
+    return {"points": points, "values": values, "found": found.astype(bool)}
 
 
 def recommend(gps, candidates, gd_params, domain_bounds, num_fidelity=0, num_starts=1, want_values=False, want_path=False):

@@ -286,6 +286,14 @@ int moe_gp_kg_discrete(const moe_gp_t* gp_c, int num_fidelity, const double* dis
   });
 }
 
+int moe_gp_kg_discrete_last_active(const moe_gp_t* gp_c, int num_points, int* num_active, moe_error_t* err) {
+  return guarded(err, [&] {
+    std::unique_lock<std::mutex> lk;
+    moe::GpDev& gp = lock_gp(gp_c, lk);
+    moe::kg_discrete_last_active(gp, num_points, num_active);
+  });
+}
+
 int moe_kg1_pass_size(int num_rows, int num_discrete) { return moe::kg1_pass_size(num_rows, num_discrete); }
 
 int moe_gp_grad_variance(const moe_gp_t* gp_c, const double* pts, int num_pts, int num_derivs, double* out,
@@ -860,6 +868,72 @@ int moe_kg_discrete_mcmc_multistart(const moe_gp_t* const* gps, int num_mcmc, in
     moe::kg_discrete_mcmc_multistart(v, num_fidelity, *outer, domain_bounds, discrete_all, num_discrete, best_so_far, starts, num_starts,
                                      do_gradient_ascent, best_point, best_value, found, start_values, kept_index, end_points,
                                      end_values, path, steps_taken);
+  });
+}
+
+int moe_kg_discrete_mcmc_pending(const moe_gp_t* const* gps, int num_mcmc, int num_fidelity, const double* discrete_all,
+                                 const int* num_discrete, const double* best_so_far, const double* points_being_sampled,
+                                 int num_being_sampled, const double* points, int num_points, int want_grad, double* kg, double* grad,
+                                 moe_error_t* err) {
+  return guarded(err, [&] {
+    if (num_mcmc < 1 || num_mcmc > 1024) throw moe::Error(MOE_ERR_BOUNDS, "num_mcmc must be between 1 and 1024", num_mcmc, 1, 1024);
+    require(gps && discrete_all && num_discrete && best_so_far && points && kg && (want_grad == 0 || grad), "NULL argument");
+    moe::check_kg_discrete_ensemble_shapes(num_mcmc, num_fidelity, num_discrete, num_points);  // (what needs no handle)
+    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, 1);
+    const auto locks = lock_ensemble(gps, num_mcmc);
+    const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
+    moe::kg_discrete_mcmc_on_device(v, num_fidelity, discrete_all, num_discrete, best_so_far, points, num_points, want_grad != 0, kg,
+                                    grad, points_being_sampled, num_being_sampled);
+  });
+}
+
+int moe_kg_discrete_mcmc_multistart_pending(const moe_gp_t* const* gps, int num_mcmc, int num_fidelity, const moe_gd_params_t* outer,
+                                            const double* domain_bounds, const double* discrete_all, const int* num_discrete,
+                                            const double* best_so_far, const double* points_being_sampled, int num_being_sampled,
+                                            const double* starts, int num_starts, int do_gradient_ascent, double* best_point,
+                                            double* best_value, int* found, double* start_values, int* kept_index,
+                                            double* end_points, double* end_values, double* path, int* steps_taken,
+                                            moe_error_t* err) {
+  return guarded(err, [&] {
+    if (num_mcmc < 1 || num_mcmc > 1024) throw moe::Error(MOE_ERR_BOUNDS, "num_mcmc must be between 1 and 1024", num_mcmc, 1, 1024);
+    require(gps && outer && domain_bounds && discrete_all && num_discrete && best_so_far && starts && best_point && best_value && found,
+            "NULL argument");
+    moe::check_kg_discrete_ensemble_shapes(num_mcmc, num_fidelity, num_discrete, num_starts);
+    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, 1);
+    if (do_gradient_ascent != 0 && outer->max_num_steps < 1)
+      throw moe::Error(MOE_ERR_BOUNDS, "max_num_steps must be positive", outer->max_num_steps, 1, 1e9);
+    if (outer->domain_type != MOE_DOMAIN_TENSOR_PRODUCT)
+      throw moe::Error(MOE_ERR_INVALID_VALUE, "the discretised knowledge gradient's ascent supports tensor-product domains only",
+                       outer->domain_type, 0, 0);
+    const auto locks = lock_ensemble(gps, num_mcmc);
+    const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
+    moe::kg_discrete_mcmc_multistart(v, num_fidelity, *outer, domain_bounds, discrete_all, num_discrete, best_so_far, starts, num_starts,
+                                     do_gradient_ascent, best_point, best_value, found, start_values, kept_index, end_points,
+                                     end_values, path, steps_taken, points_being_sampled, num_being_sampled);
+  });
+}
+
+int moe_kg_discrete_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, int num_fidelity, const moe_gd_params_t* outer,
+                                 const double* domain_bounds, const double* discrete_all, const int* num_discrete,
+                                 const double* best_so_far, const double* points_being_sampled, int num_being_sampled,
+                                 const double* starts, int num_starts, int do_gradient_ascent, int num_to_sample, double* best_points,
+                                 double* best_values, int* found, moe_error_t* err) {
+  return guarded(err, [&] {
+    if (num_mcmc < 1 || num_mcmc > 1024) throw moe::Error(MOE_ERR_BOUNDS, "num_mcmc must be between 1 and 1024", num_mcmc, 1, 1024);
+    require(gps && outer && domain_bounds && discrete_all && num_discrete && best_so_far && starts && best_points && best_values && found,
+            "NULL argument");
+    moe::check_kg_discrete_ensemble_shapes(num_mcmc, num_fidelity, num_discrete, num_starts);
+    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, num_to_sample);
+    if (do_gradient_ascent != 0 && outer->max_num_steps < 1)
+      throw moe::Error(MOE_ERR_BOUNDS, "max_num_steps must be positive", outer->max_num_steps, 1, 1e9);
+    if (outer->domain_type != MOE_DOMAIN_TENSOR_PRODUCT)
+      throw moe::Error(MOE_ERR_INVALID_VALUE, "the discretised knowledge gradient's ascent supports tensor-product domains only",
+                       outer->domain_type, 0, 0);
+    const auto locks = lock_ensemble(gps, num_mcmc);
+    const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
+    moe::kg_discrete_mcmc_suggest(v, num_fidelity, *outer, domain_bounds, discrete_all, num_discrete, best_so_far, starts, num_starts,
+                                  do_gradient_ascent, points_being_sampled, num_being_sampled, num_to_sample, best_points,
+                                  best_values, found);
   });
 }
 

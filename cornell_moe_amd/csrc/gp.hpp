@@ -67,6 +67,7 @@ struct GpDev {
   // the discretised one-point knowledge gradient (kg1.hip): the call's doubles (results first: one copy back) and integers
   DevBuf<double> kg1D;
   DevBuf<int> kg1I;
+  int kg1LastC = 0;  // the candidates kg1D was last laid out for (kg_discrete_last_active)
   // its ensemble forms (kg1_opt.hip; held by the ensemble's first member): the call's doubles (results first: one copy back) and
   // integers (the members' failure words first)
   DevBuf<double> kg1oD;
@@ -223,6 +224,8 @@ int kg1_pass_size(int N, int A);
 void check_kg_discrete_shapes(int num_fidelity, int A, int C);
 void kg_discrete_on_device(GpDev& gp, int num_fidelity, const double* discrete, int A, const double* pts, int C, double best,
                            bool want_grad, double* kg_out, double* grad_out, int* nact_out);
+// the number of lines on the envelope of each of the C candidates the GP last evaluated (alone or as a member of an ensemble call)
+void kg_discrete_last_active(GpDev& gp, int C, int* nact_out);
 // The same in the parts the ensemble forms (kg1_opt.hip) share with it.  Kg1Member: where one GP's set, per-pass scratch and
 // results live for a call of at most C candidates -- everything inside the GP's own kg1D / kg1I (results first: [fail | kg C |
 // active C | grad C d]), dE and dEK, so that the members of an ensemble never share a buffer.
@@ -237,12 +240,36 @@ struct Kg1Member {
   double *dVx = nullptr, *dVh = nullptr, *dT = nullptr, *dU = nullptr, *dMuh = nullptr, *dS2 = nullptr, *dB0 = nullptr, *dS = nullptr,
          *dHw = nullptr, *dScal = nullptr;
   int *iFail = nullptr, *iHid = nullptr;
+  // pending points (kg1_pending.hip): the conditioned GP's pcap rows of room beside the member's own factor, p of them in use.  ld = N +
+  // pcap is the leading dimension of V_A, V_x, V_x^, T and U: a column is [L^-1 k(X, z) ; r_z], the pending rows under the member's.
+  int p = 0, pcap = 0, ld = 0;
+  const double* dPP = nullptr;  // the pending points [pcap][dp] (the caller's upload; rows past p filled as they are picked)
+  double* dXe = nullptr;        // X u P [N + pcap][dp]
+  double* dKe = nullptr;        // [K^-1 (y - mean) ; 0]
+  double* dVP = nullptr;        // column j [ld]: L^-1 k(X, P_j), then row j of L_P with its diagonal
+  int* iFailP = nullptr;        // the first pending point whose Schur pivot fails the pivot rule
   size_t out_doubles() const { return 1 + 2 * (size_t)C + (with_grad ? (size_t)C * gp->d : 0); }
 };
 // the handle's checks of moe_gp_kg_discrete (num_fidelity < dim, no derivative observations), the buffers and their layout; nothing
 // is launched.  fail (may be NULL: the member's own word) is where a candidate failing the pivot rule leaves its index.
 void check_kg_discrete_member(const GpDev& gp, int num_fidelity);
-Kg1Member kg1_member(GpDev& gp, int num_fidelity, int A, int C, double best, bool with_grad, int* fail = nullptr);
+// pending_room > 0: room for that many pending points (fail_pending: where the first failing one leaves its index).
+Kg1Member kg1_member(GpDev& gp, int num_fidelity, int A, int C, double best, bool with_grad, int* fail = nullptr,
+                     int pending_room = 0, int* fail_pending = nullptr);
+// op(L^-1) B for c columns, the kernel family fixed by the GP's N alone: a column's bits do not depend on c or the leading dimensions
+void tri_cols(GpDev& gp, char op, int c, const double* B, long ldb, double* Cout, long ldc, hipStream_t s);
+// kg1_pending.hip -- the posterior covariance conditioned on pending points, as an extension of at most kKg1MaxPending rows beside
+// the member's factor (the handle is never modified, no (N + p)^2 matrix is formed):
+//   kg1_pending_begin   X u P and [K^-1 (y - mean) ; 0] for the gradient's pass over the rows; m.dPP must be set, m.p becomes 0
+//   kg1_pending_append  `count` more points of m.dPP join: L^-1 k(X, P_j), row j of L_P (pivot rule: m.iFailP), their rows of X u P;
+//                       set_ready: the set's V_A gains their rows (otherwise kg1_prepare_set forms all of them)
+//   kg1_pending_rows    rows i0 .. i1 - 1 of r_z = L_P^-1 (k(P, z) - V_P^T v_z) under the ncols columns V of the points Z [ncols][dp]
+//   kg1_pending_back    u_P = L_P^-T t_P into m.dU and t -= V_P u_P on the member's rows of m.dT, for ncols columns
+constexpr int kKg1MaxPending = 64;
+void kg1_pending_begin(Kg1Member& m, hipStream_t s);
+void kg1_pending_append(Kg1Member& m, int count, bool set_ready, hipStream_t s);
+void kg1_pending_rows(const Kg1Member& m, const double* Z, double* V, int ncols, int i0, int i1, hipStream_t s);
+void kg1_pending_back(const Kg1Member& m, int ncols, hipStream_t s);
 // "set, once": K(X, A), V_A, a_A on stream s (m.dPA must be set)
 void kg1_prepare_set(const Kg1Member& m, hipStream_t s);
 // nc <= m.widest candidates Px [nc][dp] (Ph: the same with fidelity coordinates 1; Px itself without fidelity) already on the
@@ -256,12 +283,22 @@ void kg1_clear_fail(int* fail, int count, hipStream_t s);  // INT_MAX: no candid
 // has made the checks that need no handle (check_kg_discrete_ensemble_shapes).  discrete_all: the members' sets back to back.
 void check_kg_discrete_ensemble_shapes(int num_mcmc, int num_fidelity, const int* num_discrete, int num_points);
 void kg_discrete_mcmc_on_device(const std::vector<GpDev*>& gps, int num_fidelity, const double* discrete_all, const int* num_discrete,
-                                const double* best_so_far, const double* pts, int C, bool want_grad, double* kg_out, double* grad_out);
+                                const double* best_so_far, const double* pts, int C, bool want_grad, double* kg_out, double* grad_out,
+                                const double* pending = nullptr, int num_pending = 0);
 void kg_discrete_mcmc_multistart(const std::vector<GpDev*>& gps, int num_fidelity, const moe_gd_params_t& outer,
                                  const double* domain_bounds, const double* discrete_all, const int* num_discrete,
                                  const double* best_so_far, const double* starts, int num_starts, int do_gradient_ascent,
                                  double* best_point, double* best_value, int* found, double* start_values, int* kept_index,
-                                 double* end_points, double* end_values, double* path, int* steps_taken);
+                                 double* end_points, double* end_values, double* path, int* steps_taken,
+                                 const double* pending = nullptr, int num_pending = 0);
+// ... with pending points [num_pending][dim] (kg1_pending.hip; 0: the launches of before), and num_to_sample points greedily, each
+// round the ascent with the points picked so far appended to the pending ones; check_kg_discrete_pending: what needs no handle.
+void check_kg_discrete_pending(const double* pending, int num_pending, int num_to_sample);
+void kg_discrete_mcmc_suggest(const std::vector<GpDev*>& gps, int num_fidelity, const moe_gd_params_t& outer,
+                              const double* domain_bounds, const double* discrete_all, const int* num_discrete,
+                              const double* best_so_far, const double* starts, int num_starts, int do_gradient_ascent,
+                              const double* pending, int num_pending, int num_to_sample, double* best_points, double* best_values,
+                              int* found);
 // loo.hip: leave-one-out cross-validation on the GP's current factorisation, every one of the N = n (1 + g) scalar observations left
 // out by itself.  mean_out / var_out [n][1 + g]: the LOO predictive mean (function values in the caller's units) and variance.
 void loo_predict_on_device(GpDev& gp, double* mean_out, double* var_out);

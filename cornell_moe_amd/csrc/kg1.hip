@@ -17,6 +17,8 @@
 // The host side comes in parts that kg1_opt.hip (the ensemble average and its multistart ascent) shares: kg1_member (checks, buffers,
 // layout), kg1_prepare_set ("once"), kg1_eval_pass / kg1_eval_points (a pass of candidates already in device memory, results left
 // there, every launch recordable: the five kernels of this file have the body + wrapper form of launch.hpp), then the copy back.
+// With pending points (kg1_pending.hip) a member's columns carry p more rows under the N of its own factor: the kernels take the
+// number of rows and the columns' leading dimension apart, and the pass calls kg1_pending_rows / kg1_pending_back where m.p > 0.
 //
 // Bits.  The triangular products take the split-K family at every column count (N < 128: the tiled kernel in chunks that never reach
 // its other branch), the slopes are serial fused multiply-add chains over the rows in row order, the slope of x^'s own line is the
@@ -52,16 +54,16 @@ constexpr int kScal = 4;               // per candidate: P_0, w_0, sum_j w_j b_j
 // one wavefront per candidate: s^2 = k(x, x) + noise - |v_x|^2 with the lanes striding over the rows, and by lane 0 the slope
 // numerator of x^'s own line, Sigma_n(x^, x) = k(x^, x) - v_x^ . v_x, as the chain kg1_slope_kernel runs for the lines of A
 struct kg1_cand_kernel_body {
-  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, int N, int ncols, int col0, int dp, const CovParams& cp, double noise, const double* __restrict__ Px, const double* __restrict__ Ph, const double* __restrict__ Vx, const double* __restrict__ Vh, double* __restrict__ s2_out, double* __restrict__ b0_out, int* __restrict__ fail) {
+  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, int N, int ld, int ncols, int col0, int dp, const CovParams& cp, double noise, const double* __restrict__ Px, const double* __restrict__ Ph, const double* __restrict__ Vx, const double* __restrict__ Vh, double* __restrict__ s2_out, double* __restrict__ b0_out, int* __restrict__ fail) {
     const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (c >= ncols) return;
-    const double* vx = Vx + (size_t)c * N;
+    const double* vx = Vx + (size_t)c * ld;
     double ss = 0.0;
     for (int r = lane; r < N; r += 64) ss = fma(vx[r], vx[r], ss);
   #pragma unroll
     for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off, 64);
     if (lane != 0) return;
-    const double* vh = Vh + (size_t)c * N;
+    const double* vh = Vh + (size_t)c * ld;
     double dot = 0.0;
     for (int r = 0; r < N; ++r) dot = fma(vh[r], vx[r], dot);
     const PointDiff df{Ph + (size_t)c * dp, Px + (size_t)c * dp};
@@ -71,14 +73,14 @@ struct kg1_cand_kernel_body {
     if (!(var > kPivotMin)) atomicMin(fail, col0 + c);  // the first failing candidate of the call
   }
 };
-__global__ __launch_bounds__(256) void kg1_cand_kernel(int N, int ncols, int col0, int dp, const CovParams cp, double noise, const double* __restrict__ Px, const double* __restrict__ Ph, const double* __restrict__ Vx, const double* __restrict__ Vh, double* __restrict__ s2_out, double* __restrict__ b0_out, int* __restrict__ fail) {
-  kg1_cand_kernel_body::run(MOE_VBLOCK, MOE_VGRID, nullptr, N, ncols, col0, dp, cp, noise, Px, Ph, Vx, Vh, s2_out, b0_out, fail);
+__global__ __launch_bounds__(256) void kg1_cand_kernel(int N, int ld, int ncols, int col0, int dp, const CovParams cp, double noise, const double* __restrict__ Px, const double* __restrict__ Ph, const double* __restrict__ Vx, const double* __restrict__ Vh, double* __restrict__ s2_out, double* __restrict__ b0_out, int* __restrict__ fail) {
+  kg1_cand_kernel_body::run(MOE_VBLOCK, MOE_VGRID, nullptr, N, ld, ncols, col0, dp, cp, noise, Px, Ph, Vx, Vh, s2_out, b0_out, fail);
 }
 
 // S[z + c A] = V_A[:, z] . V_x[:, c]: 64 x 64 outputs per workgroup, 4 x 4 per thread, the rows staged 32 at a time.  Every output is
 // ONE accumulator that takes its products in row order (rows past N add exact zeros).
 struct kg1_slope_kernel_body {
-  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, int N, int A, int nc, const double* __restrict__ VA, const double* __restrict__ Vx, double* __restrict__ S) {
+  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, int N, int ld, int A, int nc, const double* __restrict__ VA, const double* __restrict__ Vx, double* __restrict__ S) {
     __shared__ double As[32][65];
     __shared__ double Bs[32][65];
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4, rr = tid & 31, q = tid >> 5;
@@ -93,8 +95,8 @@ struct kg1_slope_kernel_body {
   #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const int col = q + 8 * i;
-        As[rr][col] = (r < N && z0 + col < A) ? VA[r + (size_t)(z0 + col) * N] : 0.0;
-        Bs[rr][col] = (r < N && c0 + col < nc) ? Vx[r + (size_t)(c0 + col) * N] : 0.0;
+        As[rr][col] = (r < N && z0 + col < A) ? VA[r + (size_t)(z0 + col) * ld] : 0.0;
+        Bs[rr][col] = (r < N && c0 + col < nc) ? Vx[r + (size_t)(c0 + col) * ld] : 0.0;
       }
       __syncthreads();
   #pragma unroll 8
@@ -120,8 +122,8 @@ struct kg1_slope_kernel_body {
       }
   }
 };
-__global__ __launch_bounds__(256) void kg1_slope_kernel(int N, int A, int nc, const double* __restrict__ VA, const double* __restrict__ Vx, double* __restrict__ S) {
-  kg1_slope_kernel_body::run(MOE_VBLOCK, MOE_VGRID, nullptr, N, A, nc, VA, Vx, S);
+__global__ __launch_bounds__(256) void kg1_slope_kernel(int N, int ld, int A, int nc, const double* __restrict__ VA, const double* __restrict__ Vx, double* __restrict__ S) {
+  kg1_slope_kernel_body::run(MOE_VBLOCK, MOE_VGRID, nullptr, N, ld, A, nc, VA, Vx, S);
 }
 
 // the order of the lines: larger slope first, then smaller intercept, then lower index
@@ -283,13 +285,13 @@ __global__ __launch_bounds__(256) void kg1_envelope_kernel(int A, int n2, int dp
 // One workgroup per candidate: t = sum_j w_j V_{z_j} over the envelope's lines (x^'s line brings v_x^), then the two right-hand sides
 // of the gradient's triangular product, T[:, 2 c] = t / s - (sum_j w_j b_j / s^2) v_x and T[:, 2 c + 1] = (w_0 / s) v_x.
 struct kg1_t_kernel_body {
-  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, int N, int A, const double* __restrict__ VA, const double* __restrict__ Vx, const double* __restrict__ Vh, const double* __restrict__ s2, const double* __restrict__ nact, int col0, const double* __restrict__ hull_w, const int* __restrict__ hull_id, const double* __restrict__ scal, double* __restrict__ T) {
+  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, int N, int ld, int A, const double* __restrict__ VA, const double* __restrict__ Vx, const double* __restrict__ Vh, const double* __restrict__ s2, const double* __restrict__ nact, int col0, const double* __restrict__ hull_w, const int* __restrict__ hull_id, const double* __restrict__ scal, double* __restrict__ T) {
     __shared__ double s_w[256];
     __shared__ int s_id[256];
     const int c = blockIdx.x, tid = threadIdx.x;
     const int k = (int)nact[col0 + c];
-    double* t1 = T + (size_t)(2 * c) * N;
-    double* t2 = t1 + N;
+    double* t1 = T + (size_t)(2 * c) * ld;
+    double* t2 = t1 + ld;
     if (k == 0) {
       for (int r = tid; r < N; r += 256) {
         t1[r] = 0.0;
@@ -299,8 +301,8 @@ struct kg1_t_kernel_body {
     }
     const double var = s2[c], s = sqrt(var);
     const double w0 = scal[(size_t)c * kScal + 1], swb = scal[(size_t)c * kScal + 2];
-    const double* vx = Vx + (size_t)c * N;
-    const double* vh = Vh + (size_t)c * N;
+    const double* vx = Vx + (size_t)c * ld;
+    const double* vh = Vh + (size_t)c * ld;
     const int sweeps = (N + 255) / 256;
     for (int sw = 0; sw < sweeps; ++sw) {
       const int r = sw * 256 + tid;
@@ -316,7 +318,7 @@ struct kg1_t_kernel_body {
         if (r < N)
           for (int j = 0; j < nj; ++j) {
             const int id = s_id[j];
-            t = fma(s_w[j], (id == 0) ? vh[r] : VA[r + (size_t)(id - 1) * N], t);
+            t = fma(s_w[j], (id == 0) ? vh[r] : VA[r + (size_t)(id - 1) * ld], t);
           }
       }
       if (r < N) {
@@ -326,15 +328,15 @@ struct kg1_t_kernel_body {
     }
   }
 };
-__global__ __launch_bounds__(256) void kg1_t_kernel(int N, int A, const double* __restrict__ VA, const double* __restrict__ Vx, const double* __restrict__ Vh, const double* __restrict__ s2, const double* __restrict__ nact, int col0, const double* __restrict__ hull_w, const int* __restrict__ hull_id, const double* __restrict__ scal, double* __restrict__ T) {
-  kg1_t_kernel_body::run(MOE_VBLOCK, MOE_VGRID, nullptr, N, A, VA, Vx, Vh, s2, nact, col0, hull_w, hull_id, scal, T);
+__global__ __launch_bounds__(256) void kg1_t_kernel(int N, int ld, int A, const double* __restrict__ VA, const double* __restrict__ Vx, const double* __restrict__ Vh, const double* __restrict__ s2, const double* __restrict__ nact, int col0, const double* __restrict__ hull_w, const int* __restrict__ hull_id, const double* __restrict__ scal, double* __restrict__ T) {
+  kg1_t_kernel_body::run(MOE_VBLOCK, MOE_VGRID, nullptr, N, ld, A, VA, Vx, Vh, s2, nact, col0, hull_w, hull_id, scal, T);
 }
 
 // One workgroup per candidate: the gradient from the two solved columns U = L^-T T, K^-1 (y - mean) and the envelope's lines.
 // FID: fidelity coordinates present -- x^ differs from x, its sums run separately and stay off the fidelity coordinates.
 template <int DP, bool FID>
 struct kg1_grad_kernel_body {
-  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, int n, int A, int d, int nf, int col0, const CovParams& cp, const double* __restrict__ X, const double* __restrict__ kinvy, const double* __restrict__ PA, const double* __restrict__ Px, const double* __restrict__ Ph, const double* __restrict__ U, const double* __restrict__ s2, const double* __restrict__ nact, const double* __restrict__ hull_w, const int* __restrict__ hull_id, const double* __restrict__ scal, double* __restrict__ grad) {
+  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, int n, int ld, int A, int d, int nf, int col0, const CovParams& cp, const double* __restrict__ X, const double* __restrict__ kinvy, const double* __restrict__ PA, const double* __restrict__ Px, const double* __restrict__ Ph, const double* __restrict__ U, const double* __restrict__ s2, const double* __restrict__ nact, const double* __restrict__ hull_w, const int* __restrict__ hull_id, const double* __restrict__ scal, double* __restrict__ grad) {
     __shared__ double s_part[4][DP];
     const int c = blockIdx.x, tid = threadIdx.x;
     const int k = (int)nact[col0 + c];
@@ -345,8 +347,8 @@ struct kg1_grad_kernel_body {
     }
     const double s = sqrt(s2[c]);
     const double cb = scal[(size_t)c * kScal + 3] - scal[(size_t)c * kScal + 0];  // [mu_n(x^) < best] - P_0
-    const double* u1 = U + (size_t)(2 * c) * n;
-    const double* u2 = u1 + n;
+    const double* u1 = U + (size_t)(2 * c) * ld;
+    const double* u2 = u1 + ld;
     double x[DP], xh[DP], g[DP];
   #pragma unroll
     for (int i = 0; i < DP; ++i) {
@@ -406,8 +408,8 @@ struct kg1_grad_kernel_body {
   }
 };
 template <int DP, bool FID>
-__global__ __launch_bounds__(256) void kg1_grad_kernel(int n, int A, int d, int nf, int col0, const CovParams cp, const double* __restrict__ X, const double* __restrict__ kinvy, const double* __restrict__ PA, const double* __restrict__ Px, const double* __restrict__ Ph, const double* __restrict__ U, const double* __restrict__ s2, const double* __restrict__ nact, const double* __restrict__ hull_w, const int* __restrict__ hull_id, const double* __restrict__ scal, double* __restrict__ grad) {
-  kg1_grad_kernel_body<DP, FID>::run(MOE_VBLOCK, MOE_VGRID, nullptr, n, A, d, nf, col0, cp, X, kinvy, PA, Px, Ph, U, s2, nact, hull_w, hull_id, scal, grad);
+__global__ __launch_bounds__(256) void kg1_grad_kernel(int n, int ld, int A, int d, int nf, int col0, const CovParams cp, const double* __restrict__ X, const double* __restrict__ kinvy, const double* __restrict__ PA, const double* __restrict__ Px, const double* __restrict__ Ph, const double* __restrict__ U, const double* __restrict__ s2, const double* __restrict__ nact, const double* __restrict__ hull_w, const int* __restrict__ hull_id, const double* __restrict__ scal, double* __restrict__ grad) {
+  kg1_grad_kernel_body<DP, FID>::run(MOE_VBLOCK, MOE_VGRID, nullptr, n, ld, A, d, nf, col0, cp, X, kinvy, PA, Px, Ph, U, s2, nact, hull_w, hull_id, scal, grad);
 }
 
 __global__ void kg1_init_kernel(int* __restrict__ fail, int count) {
@@ -426,21 +428,21 @@ DerivList no_derivs() {
   return d;
 }
 
+}  // namespace
+
 // op(L^-1) B for c independent columns, the kernel family fixed by N alone (never by c): below 128 rows the tiled kernel in chunks
 // that stay under its switch to the matrix-pipe kernel, from 128 rows the split-K kernels at every column count
-void tri_cols(GpDev& gp, char op, int c, const double* B, double* Cout, hipStream_t s) {
+void tri_cols(GpDev& gp, char op, int c, const double* B, long ldb, double* Cout, long ldc, hipStream_t s) {
   const int N = gp.N;
   if (N < 128) {
     for (int k0 = 0; k0 < c; k0 += kKg1TinyCols) {
       const int nk = std::min(kKg1TinyCols, c - k0);
-      launch_tri_gemm_cols(op, N, nk, nk, gp.dLinv.p, gp.ldL, B + (size_t)k0 * N, N, Cout + (size_t)k0 * N, N, nullptr, s);
+      launch_tri_gemm_cols(op, N, nk, nk, gp.dLinv.p, gp.ldL, B + (size_t)k0 * ldb, ldb, Cout + (size_t)k0 * ldc, ldc, nullptr, s);
     }
   } else {
-    launch_tri_gemm_cols(op, N, c, 17, gp.dLinv.p, gp.ldL, B, N, Cout, N, gp.dEK.p, s);
+    launch_tri_gemm_cols(op, N, c, 17, gp.dLinv.p, gp.ldL, B, ldb, Cout, ldc, gp.dEK.p, s);
   }
 }
-
-}  // namespace
 
 // Candidates per pass, from N and A alone: a pass's columns of V stay within 2^24 doubles and its A x pass slope matrix within 2^22,
 // a multiple of 64 between 64 and 4096.
@@ -465,7 +467,7 @@ void check_kg_discrete_member(const GpDev& gp, int nf) {
                 gp.g, 0, 0);
 }
 
-Kg1Member kg1_member(GpDev& gp, int nf, int A, int C, double best, bool with_grad, int* fail) {
+Kg1Member kg1_member(GpDev& gp, int nf, int A, int C, double best, bool with_grad, int* fail, int pcap, int* fail_pending) {
   check_kg_discrete_shapes(nf, A, C);
   check_kg_discrete_member(gp, nf);
   gp.use_device();
@@ -482,20 +484,24 @@ Kg1Member kg1_member(GpDev& gp, int nf, int A, int C, double best, bool with_gra
   m.n2 = 2;
   while (m.n2 < A + 1) m.n2 <<= 1;
   const int N = gp.N;
-  const size_t nA = (size_t)A, nC = (size_t)C, nW = (size_t)m.widest;
+  m.pcap = pcap;
+  m.ld = N + pcap;  // (the columns of V, T and U keep room for the pending rows under the member's own)
+  const size_t nA = (size_t)A, nC = (size_t)C, nW = (size_t)m.widest, nL = (size_t)m.ld;
   // doubles: [fail | kg C | active C | grad C d] (the copy back) | V_A N A | a_A A | per pass: V_x, V_x^ N W each | T, U N 2W each |
-  //          mu_n(x^), s^2, slope numerator of x^ W each | slopes A W | envelope weights (A + 1) W | scalars kScal W
+  //          mu_n(x^), s^2, slope numerator of x^ W each | slopes A W | envelope weights (A + 1) W | scalars kScal W |
+  //          with pending points (kg1_pending.hip): X u P (N + pcap) dp | [K^-1 (y - mean) ; 0] N + pcap | the extension (N + pcap) pcap
   const size_t nOut = m.out_doubles();
-  const size_t nV = (size_t)N * nW;
-  gp.kg1D.reserve(nOut + (size_t)N * nA + nA + (m.fid ? 2 : 1) * nV + (with_grad ? 4 * nV : 0) + 3 * nW + nA * nW + (nA + 1) * nW +
-                  kScal * nW);
-  gp.kg1I.reserve(1 + (nA + 1) * nW);
+  const size_t nV = nL * nW;
+  gp.kg1D.reserve(nOut + nL * nA + nA + (m.fid ? 2 : 1) * nV + (with_grad ? 4 * nV : 0) + 3 * nW + nA * nW + (nA + 1) * nW +
+                  kScal * nW + (pcap > 0 ? nL * ((size_t)gp.dp + 1 + (size_t)pcap) : 0));
+  gp.kg1I.reserve(2 + (nA + 1) * nW);
+  gp.kg1LastC = C;
   m.dOut = gp.kg1D.p;
   m.dKg = m.dOut + 1;
   m.dAct = m.dKg + nC;
   m.dGrad = m.dAct + nC;
   m.dVA = m.dOut + nOut;
-  m.dAA = m.dVA + (size_t)N * nA;
+  m.dAA = m.dVA + nL * nA;
   m.dVx = m.dAA + nA;
   m.dVh = m.fid ? m.dVx + nV : m.dVx;
   m.dT = m.dVh + nV;
@@ -506,13 +512,31 @@ Kg1Member kg1_member(GpDev& gp, int nf, int A, int C, double best, bool with_gra
   m.dS = m.dB0 + nW;
   m.dHw = m.dS + nA * nW;
   m.dScal = m.dHw + (nA + 1) * nW;
+  if (pcap > 0) {
+    m.dXe = m.dScal + kScal * nW;
+    m.dKe = m.dXe + nL * (size_t)gp.dp;
+    m.dVP = m.dKe + nL;
+  }
   m.iFail = fail != nullptr ? fail : gp.kg1I.p;
-  m.iHid = gp.kg1I.p + 1;
-  gp.dE.reserve((size_t)N * std::max(nA, nW));
-  if (N >= 128) gp.dEK.reserve(tri_cols_work_doubles(N, (int)std::max(nA, 2 * nW)));
+  m.iFailP = fail_pending != nullptr ? fail_pending : gp.kg1I.p + 1;
+  m.iHid = gp.kg1I.p + 2;
+  gp.dE.reserve((size_t)N * std::max(std::max(nA, nW), (size_t)pcap));
+  if (N >= 128) gp.dEK.reserve(tri_cols_work_doubles(N, (int)std::max(std::max(nA, 2 * nW), (size_t)pcap)));
   MOE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kg1_envelope_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)(kKg1MaxLines * (2 * sizeof(double) + sizeof(int)))));
   return m;
+}
+
+void kg_discrete_last_active(GpDev& gp, int C, int* nact_out) {
+  if (C < 1 || C != gp.kg1LastC)
+    throw Error(MOE_ERR_BOUNDS, "num_points must be the number of candidates of the GP's last discretised knowledge-gradient call", C,
+                gp.kg1LastC, gp.kg1LastC);
+  if (nact_out == nullptr) throw Error(MOE_ERR_RUNTIME, "NULL argument");
+  gp.use_device();
+  gp.hStateOut.reserve((size_t)C);
+  MOE_HIP_CHECK(hipMemcpyAsync(gp.hStateOut.p, gp.kg1D.p + 1 + (size_t)C, sizeof(double) * (size_t)C, hipMemcpyDeviceToHost, gp.stream));
+  MOE_HIP_CHECK(hipStreamSynchronize(gp.stream));
+  for (int i = 0; i < C; ++i) nact_out[i] = (int)gp.hStateOut.p[i];
 }
 
 void kg1_clear_fail(int* fail, int count, hipStream_t s) {
@@ -525,47 +549,54 @@ void kg1_prepare_set(const Kg1Member& m, hipStream_t s) {
   GpDev& gp = *m.gp;
   const DerivList none = no_derivs();
   launch_cov_build(gp.cp, gp.dX.p, gp.n, none, m.dPA, m.A, none, nullptr, gp.dE.p, gp.N, 0, s);
-  tri_cols(gp, 'N', m.A, gp.dE.p, m.dVA, s);
+  tri_cols(gp, 'N', m.A, gp.dE.p, gp.N, m.dVA, m.ld, s);
   launch_mean(gp.cp, gp.dX.p, gp.n, none, gp.dKinvY.p, m.dPA, m.A, gp.mean, false, m.dAA, s);
+  if (m.p > 0) kg1_pending_rows(m, m.dPA, m.dVA, m.A, 0, m.p, s);
 }
 
 void kg1_eval_pass(const Kg1Member& m, const double* Px, const double* Ph, int nc, int c0, bool with_grad, hipStream_t s) {
   GpDev& gp = *m.gp;
   if (nc < 1 || nc > m.widest || c0 < 0 || c0 + nc > m.C || (with_grad && !m.with_grad))
     throw Error(MOE_ERR_RUNTIME, "kg1_eval_pass: the pass does not fit the member's buffers");
-  const int N = gp.N, n = gp.n, d = gp.d, dp = gp.dp, A = m.A, nf = m.nf;
+  // R rows of X u P under the columns' leading dimension; without pending points the member's own N rows, the kernels of before
+  const int N = gp.N, n = gp.n, d = gp.d, dp = gp.dp, A = m.A, nf = m.nf, R = N + m.p, ld = m.ld;
+  const double* Xr = m.p > 0 ? m.dXe : gp.dX.p;
+  const double* Kr = m.p > 0 ? m.dKe : gp.dKinvY.p;
   const DerivList none = no_derivs();
   const size_t shm = (size_t)m.n2 * (2 * sizeof(double) + sizeof(int));
   const dim3 b256(256);
   launch_cov_build(gp.cp, gp.dX.p, n, none, Px, nc, none, nullptr, gp.dE.p, N, 0, s);
-  tri_cols(gp, 'N', nc, gp.dE.p, m.dVx, s);
+  tri_cols(gp, 'N', nc, gp.dE.p, N, m.dVx, ld, s);
+  if (m.p > 0) kg1_pending_rows(m, Px, m.dVx, nc, 0, m.p, s);
   if (m.fid) {
     launch_cov_build(gp.cp, gp.dX.p, n, none, Ph, nc, none, nullptr, gp.dE.p, N, 0, s);
-    tri_cols(gp, 'N', nc, gp.dE.p, m.dVh, s);
+    tri_cols(gp, 'N', nc, gp.dE.p, N, m.dVh, ld, s);
+    if (m.p > 0) kg1_pending_rows(m, Ph, m.dVh, nc, 0, m.p, s);
   }
   launch_mean(gp.cp, gp.dX.p, n, none, gp.dKinvY.p, Ph, nc, gp.mean, false, m.dMuh, s);
-  launch_kernel_ens<kg1_cand_kernel_body, 256>(kg1_cand_kernel, dim3((unsigned)((nc + 3) / 4)), b256, 0, s, N, nc, c0, dp, gp.cp,
+  launch_kernel_ens<kg1_cand_kernel_body, 256>(kg1_cand_kernel, dim3((unsigned)((nc + 3) / 4)), b256, 0, s, R, ld, nc, c0, dp, gp.cp,
                                                gp.noise[0], Px, Ph, (const double*)m.dVx, (const double*)m.dVh, m.dS2, m.dB0, m.iFail);
   launch_kernel_ens<kg1_slope_kernel_body, 256>(kg1_slope_kernel, dim3((unsigned)((A + 63) / 64), (unsigned)((nc + 63) / 64)), b256, 0, s,
-                                                N, A, nc, (const double*)m.dVA, (const double*)m.dVx, m.dS);
+                                                R, ld, A, nc, (const double*)m.dVA, (const double*)m.dVx, m.dS);
   launch_kernel_ens<kg1_envelope_kernel_body, 256>(kg1_envelope_kernel, dim3((unsigned)nc), b256, shm, s, A, m.n2, dp, c0, gp.cp, m.best,
                                                    m.dPA, Px, (const double*)m.dAA, (const double*)m.dMuh, (const double*)m.dS2,
                                                    (const double*)m.dB0, (const double*)m.dS, m.dKg, m.dAct, m.dHw, m.iHid, m.dScal);
   MOE_HIP_CHECK(hipGetLastError());
   if (!with_grad) return;
-  launch_kernel_ens<kg1_t_kernel_body, 256>(kg1_t_kernel, dim3((unsigned)nc), b256, 0, s, N, A, (const double*)m.dVA, (const double*)m.dVx,
+  launch_kernel_ens<kg1_t_kernel_body, 256>(kg1_t_kernel, dim3((unsigned)nc), b256, 0, s, R, ld, A, (const double*)m.dVA, (const double*)m.dVx,
                                             (const double*)m.dVh, (const double*)m.dS2, (const double*)m.dAct, c0, (const double*)m.dHw,
                                             (const int*)m.iHid, (const double*)m.dScal, m.dT);
-  tri_cols(gp, 'T', 2 * nc, m.dT, m.dU, s);
+  if (m.p > 0) kg1_pending_back(m, 2 * nc, s);  // (L'^-T: the pending block first, then the member's own on the corrected rows)
+  tri_cols(gp, 'T', 2 * nc, m.dT, ld, m.dU, ld, s);
   dispatch_dp(dp, [&](auto DP) {
     if (m.fid)
-      launch_kernel_ens<kg1_grad_kernel_body<DP, true>, 256>(kg1_grad_kernel<DP, true>, dim3((unsigned)nc), b256, 0, s, n, A, d, nf, c0, gp.cp,
-                                                             (const double*)gp.dX.p, (const double*)gp.dKinvY.p, m.dPA, Px, Ph,
+      launch_kernel_ens<kg1_grad_kernel_body<DP, true>, 256>(kg1_grad_kernel<DP, true>, dim3((unsigned)nc), b256, 0, s, R, ld, A, d, nf, c0, gp.cp,
+                                                             Xr, Kr, m.dPA, Px, Ph,
                                                              (const double*)m.dU, (const double*)m.dS2, (const double*)m.dAct,
                                                              (const double*)m.dHw, (const int*)m.iHid, (const double*)m.dScal, m.dGrad);
     else
-      launch_kernel_ens<kg1_grad_kernel_body<DP, false>, 256>(kg1_grad_kernel<DP, false>, dim3((unsigned)nc), b256, 0, s, n, A, d, nf, c0, gp.cp,
-                                                              (const double*)gp.dX.p, (const double*)gp.dKinvY.p, m.dPA, Px, Ph,
+      launch_kernel_ens<kg1_grad_kernel_body<DP, false>, 256>(kg1_grad_kernel<DP, false>, dim3((unsigned)nc), b256, 0, s, R, ld, A, d, nf, c0, gp.cp,
+                                                              Xr, Kr, m.dPA, Px, Ph,
                                                               (const double*)m.dU, (const double*)m.dS2, (const double*)m.dAct,
                                                               (const double*)m.dHw, (const int*)m.iHid, (const double*)m.dScal, m.dGrad);
   });

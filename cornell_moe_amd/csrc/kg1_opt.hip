@@ -13,6 +13,9 @@
 // The ascent is multistart() / gradient_ascent() of multistart.hip operation for operation: value at every start, top_k_order on the
 // host (the one wait of the screening), T steps per restart round with a stopped start evaluated and MASKED (a candidate's bits do not
 // depend on who shares its pass), value at every end point, strict compare.
+// With pending points (kg1_pending.hip; moe_kg_discrete_mcmc_pending, moe_kg_discrete_mcmc_multistart_pending) stage() also builds every
+// member's extension before its set phase; moe_kg_discrete_mcmc_suggest stages once and runs the ascent (ascend()) once per point of
+// the batch, appending the picked point to every member's extension in between.
 //
 // Bits.  A member's evaluation is kg1.hip's own kernels in kg1.hip's own pass structure, launched by itself or as the member's share of
 // an ensemble twin: the same instructions on the same operands.  The mean adds the members in member order and divides once.  The
@@ -22,6 +25,7 @@
 #include <climits>
 #include <cmath>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "gp.hpp"
@@ -172,6 +176,10 @@ struct Kg1Ensemble {
   const double* dPts = nullptr;
   const double* dPtsH = nullptr;
   int* iFail = nullptr;  // [E] in the first member's kg1oI
+  // pending points (kg1_pending.hip): p of pcap in use; with room for them the members' pending failure words [E] follow iFail, and
+  // W = 2 E words travel where E do without
+  int p = 0, pcap = 0, W = 0;
+  double* dPending = nullptr;  // [pcap][dp] inside the one upload
 };
 
 // one evaluation of the ensemble, recorded once and issued as often as the caller likes (the buffers it names stay put)
@@ -239,7 +247,8 @@ void check_members(const std::vector<GpDev*>& gps, int nf) {
 //   [kg pointers E | grad pointers E | bounds 2 d | set of member 0 .. E - 1, padded | points C dp | the same, fidelity 1 (fid)]
 // extra_ints: integers of the caller behind the E failure words in the first member's kg1oI.
 void stage(Kg1Ensemble& T, const std::vector<GpDev*>& gps, int nf, const double* discrete_all, const int* num_discrete,
-           const double* best_so_far, const double* bounds, const double* pts, int C, bool with_grad, size_t extra_ints) {
+           const double* best_so_far, const double* bounds, const double* pts, int C, bool with_grad, size_t extra_ints,
+           const double* pending = nullptr, int p = 0, int pcap = 0) {
   GpDev& g0 = *gps[0];
   T.gps = gps;
   T.E = (int)gps.size();
@@ -251,16 +260,21 @@ void stage(Kg1Ensemble& T, const std::vector<GpDev*>& gps, int nf, const double*
   T.z = g0.stream;
   T.ens = ensemble_launches() && T.E > 1;
   const int E = T.E, d = T.d, dp = T.dp, size = d - nf;
-  g0.kg1oI.reserve((size_t)E + extra_ints);
+  T.p = 0;
+  T.pcap = pcap;
+  T.W = pcap > 0 ? 2 * E : E;
+  g0.kg1oI.reserve((size_t)T.W + extra_ints);
   T.iFail = g0.kg1oI.p;
   size_t nSets = 0;
   for (int e = 0; e < E; ++e) nSets += (size_t)num_discrete[e];
   const size_t nC = (size_t)C, oBounds = 2 * (size_t)E, oSets = oBounds + 2 * (size_t)d, oPts = oSets + nSets * dp;
-  const size_t nIn = oPts + nC * dp * (T.fid ? 2 : 1);
+  const size_t oPend = oPts + nC * dp * (T.fid ? 2 : 1);
+  const size_t nIn = oPend + (size_t)pcap * dp;
   g0.hStateIn.reserve(nIn);
   g0.dStateIn.reserve(nIn);
   T.mem.clear();
-  for (int e = 0; e < E; ++e) T.mem.push_back(kg1_member(*gps[e], nf, num_discrete[e], C, best_so_far[e], with_grad, T.iFail + e));
+  for (int e = 0; e < E; ++e) T.mem.push_back(kg1_member(*gps[e], nf, num_discrete[e], C, best_so_far[e], with_grad, T.iFail + e, pcap,
+                                                         pcap > 0 ? T.iFail + E + e : nullptr));
   double* h = g0.hStateIn.p;
   static_assert(sizeof(const double*) == sizeof(double), "the pointer tables travel inside a buffer of doubles");
   for (int e = 0; e < E; ++e) {
@@ -283,14 +297,26 @@ void stage(Kg1Ensemble& T, const std::vector<GpDev*>& gps, int nf, const double*
       h[oPts + i * dp + k] = v;
       if (T.fid) h[oPts + (nC + i) * dp + k] = (k >= size && k < d) ? 1.0 : v;
     }
+  for (size_t i = 0; i < (size_t)pcap; ++i)  // (the pending points as given, fidelity coordinates included; the rest joins on the device)
+    for (int k = 0; k < dp; ++k) h[oPend + i * dp + k] = (i < (size_t)p && k < d) ? pending[i * d + k] : 0.0;
   g0.dStateIn.upload(h, nIn, T.z, true);
+  T.dPending = g0.dStateIn.p + oPend;
   T.dKgTab = reinterpret_cast<const double* const*>(dIn);
   T.dGradTab = reinterpret_cast<const double* const*>(dIn + E);
   T.dBounds = dIn + oBounds;
   T.dPts = dIn + oPts;
   T.dPtsH = T.fid ? T.dPts + nC * dp : T.dPts;
   kg1_clear_fail(T.iFail, E, T.z);
-  for (const Kg1Member& m : T.mem) kg1_prepare_set(m, T.z);
+  if (pcap > 0) kg1_clear_fail(T.iFail + E, E, T.z);
+  for (Kg1Member& m : T.mem) {
+    if (pcap > 0) {
+      m.dPP = T.dPending;
+      kg1_pending_begin(m, T.z);
+      if (p > 0) kg1_pending_append(m, p, false, T.z);
+    }
+    kg1_prepare_set(m, T.z);
+  }
+  T.p = p;
 }
 
 void launch_mean_of_members(const Kg1Ensemble& T, const double* const* tab, long n, double* out) {
@@ -299,9 +325,16 @@ void launch_mean_of_members(const Kg1Ensemble& T, const double* const* tab, long
 }
 
 // after a wait: the first member with a candidate that failed the pivot rule
-void throw_if_singular(const Kg1Ensemble& T, const double* fail_words) {
+template <class Word>
+void throw_if_singular(const Kg1Ensemble& T, const Word* fail_words) {
+  for (int e = T.E; e < T.W; ++e)  // (a failed extension spoils every candidate of its member: it is reported first)
+    if (fail_words[e] < (Word)INT_MAX)
+      throw Error(MOE_ERR_SINGULAR,
+                  "the covariance conditioned on points_being_sampled is singular: pending point " +
+                      std::to_string((int)fail_words[e]) + " of the combined list repeats a pending or sampled point with 0 noise.",
+                  e - T.E, (int)fail_words[e]);
   for (int e = 0; e < T.E; ++e)
-    if (fail_words[e] < (double)INT_MAX)
+    if (fail_words[e] < (Word)INT_MAX)
       throw Error(MOE_ERR_SINGULAR,
                   "GP-Variance matrix singular. Check for duplicate points_to_sample or points_to_sample "
                   "duplicating points_sampled with 0 noise.",
@@ -318,17 +351,19 @@ void check_kg_discrete_ensemble_shapes(int num_mcmc, int num_fidelity, const int
 }
 
 void kg_discrete_mcmc_on_device(const std::vector<GpDev*>& gps, int nf, const double* discrete_all, const int* num_discrete,
-                                const double* best_so_far, const double* pts, int C, bool want_grad, double* kg_out, double* grad_out) {
+                                const double* best_so_far, const double* pts, int C, bool want_grad, double* kg_out, double* grad_out,
+                                const double* pending, int num_pending) {
   check_members(gps, nf);
   GpDev& g0 = *gps[0];
   Kg1Ensemble T;
-  const int E = (int)gps.size(), d = g0.d;
-  // the call's doubles, all of them the copy back: [failure words E | kg C | grad C d]
+  const int d = g0.d;
+  const int E = num_pending > 0 ? 2 * (int)gps.size() : (int)gps.size();  // (the failure words in front of the results: Kg1Ensemble::W)
+  // the call's doubles, all of them the copy back: [failure words | kg C | grad C d]
   const size_t nOut = (size_t)E + (size_t)C * (want_grad ? 1 + d : 1);
   g0.use_device();
   g0.kg1oD.reserve(nOut);
   g0.hStateOut.reserve(nOut);
-  stage(T, gps, nf, discrete_all, num_discrete, best_so_far, nullptr, pts, C, want_grad, 0);
+  stage(T, gps, nf, discrete_all, num_discrete, best_so_far, nullptr, pts, C, want_grad, 0, pending, num_pending, num_pending);
   Kg1Recording rec;
   evaluate(T, rec, T.dPts, T.dPtsH, C, want_grad);
   double* dOut = g0.kg1oD.p;
@@ -344,32 +379,28 @@ void kg_discrete_mcmc_on_device(const std::vector<GpDev*>& gps, int nf, const do
   if (want_grad) std::memcpy(grad_out, o + E + C, sizeof(double) * (size_t)C * d);
 }
 
-void kg_discrete_mcmc_multistart(const std::vector<GpDev*>& gps, int nf, const moe_gd_params_t& outer, const double* domain_bounds,
-                                 const double* discrete_all, const int* num_discrete, const double* best_so_far,
-                                 const double* starts, int num_starts, int do_gradient_ascent, double* best_point,
-                                 double* best_value, int* found, double* start_values, int* kept_index, double* end_points,
-                                 double* end_values, double* path, int* steps_taken) {
-  check_members(gps, nf);
-  GpDev& g0 = *gps[0];
-  Kg1Ensemble T;
-  const int E = (int)gps.size(), d = g0.d, dp = g0.dp, S = num_starts;
+namespace {
+
+// One multistart ascent of an ensemble that is staged (stage(): the starts are T.dPts, the set phase has run, the pending points in
+// use are the members' p): screening, the kept starts, the rounds, the end values.  Returns where the returned point lies in device
+// memory, padded [dp] -- a greedy batch appends it to the pending points without a trip through the host.
+const double* ascend(Kg1Ensemble& T, const moe_gd_params_t& outer, const double* starts, int num_starts, int do_gradient_ascent,
+                     double* best_point, double* best_value, int* found, double* start_values, int* kept_index, double* end_points,
+                     double* end_values, double* path, int* steps_taken) {
+  GpDev& g0 = *T.gps[0];
+  const int E = T.E, W = T.W, d = T.d, dp = T.dp, S = num_starts;
   const int R = std::max(outer.max_num_restarts, 0), Tn = outer.max_num_steps;
   const bool ascent = do_gradient_ascent != 0;
   const int Kmax = ascent ? std::min(S, kMaxKept) : 0;  // (top_k_order keeps at most 20)
   const int rows = R * Tn + 1;
   const bool want_path = ascent && path != nullptr;
-  // the call's doubles: [words: failure E, steps Kmax | values S | X Kmax dp | path Kmax rows d] (the copies back) | X^, X_begin Kmax dp
-  const size_t nWords = (size_t)E + Kmax, oVals = nWords, oX = oVals + S, oPath = oX + (size_t)Kmax * dp;
+  // the call's doubles: [words: failure W, steps Kmax | values S | X Kmax dp | path Kmax rows d] (the copies back) | X^, X_begin Kmax dp
+  const size_t nWords = (size_t)W + Kmax, oVals = nWords, oX = oVals + S, oPath = oX + (size_t)Kmax * dp;
   const size_t nBack = oPath + (want_path ? (size_t)Kmax * rows * d : 0);
-  g0.use_device();
-  g0.kg1oD.reserve(nBack + 2 * (size_t)Kmax * dp);
-  g0.hStateOut.reserve(nBack);
-  // integers behind the failure words: [alive count | steps Kmax | order, running, alive Kmax each]
-  stage(T, gps, nf, discrete_all, num_discrete, best_so_far, domain_bounds, starts, S, ascent && R > 0, 1 + 4 * (size_t)Kmax);
   hipStream_t z = T.z;
   double* dD = g0.kg1oD.p;
   double* dVals = dD + oVals;
-  int* iCount = T.iFail + E;
+  int* iCount = T.iFail + W;
   int* iSteps = iCount + 1;
   int* iOrder = iSteps + Kmax;
   double* h = g0.hStateOut.p;
@@ -378,7 +409,7 @@ void kg_discrete_mcmc_multistart(const std::vector<GpDev*>& gps, int nf, const m
   Kg1Recording screen;
   evaluate(T, screen, T.dPts, T.dPtsH, S, false);
   launch_mean_of_members(T, T.dKgTab, S, dVals);
-  MOE_LAUNCH_NOW(kg1_words_kernel, dim3(1), dim3(256), 0, z, (const int*)T.iFail, E, dD);
+  MOE_LAUNCH_NOW(kg1_words_kernel, dim3(1), dim3(256), 0, z, (const int*)T.iFail, W, dD);
   MOE_HIP_CHECK(hipGetLastError());
   g0.kg1oD.download(h, oVals + S, z);
   MOE_HIP_CHECK(hipStreamSynchronize(z));
@@ -388,14 +419,16 @@ void kg_discrete_mcmc_multistart(const std::vector<GpDev*>& gps, int nf, const m
   *found = 0;
   *best_value = -INFINITY;
   if (!ascent) {
+    int best_s = 0;
     std::copy(starts, starts + d, best_point);  // seeded with the first point of the list, as multistart() does
     for (int s = 0; s < S; ++s)
       if (vals[s] > *best_value) {
         *best_value = vals[s];
         std::copy(starts + (size_t)s * d, starts + (size_t)(s + 1) * d, best_point);
         *found = 1;
+        best_s = s;
       }
-    return;
+    return T.dPts + (size_t)best_s * dp;
   }
 
   // the kept starts in the reference's order, uploaded; their points gathered on the device
@@ -403,6 +436,7 @@ void kg_discrete_mcmc_multistart(const std::vector<GpDev*>& gps, int nf, const m
   const int K = (int)order.size();
   if (K > Kmax) throw Error(MOE_ERR_RUNTIME, "top_k_order kept more starts than the ascent has room for");
   std::copy(starts + (size_t)order[0] * d, starts + (size_t)(order[0] + 1) * d, best_point);
+  const double* dBest = T.dPts + (size_t)order[0] * dp;
   int* hOrder = reinterpret_cast<int*>(g0.hStateIn.p);  // (the upload it carried has been waited for)
   std::copy(order.begin(), order.end(), hOrder);
   MOE_HIP_CHECK(hipMemcpyAsync(iOrder, hOrder, sizeof(int) * (size_t)K, hipMemcpyHostToDevice, z));
@@ -411,7 +445,7 @@ void kg_discrete_mcmc_multistart(const std::vector<GpDev*>& gps, int nf, const m
   a.E = E;
   a.d = d;
   a.dp = dp;
-  a.size = d - nf;
+  a.size = d - T.nf;
   a.grad = T.dGradTab;
   a.bounds = T.dBounds;
   a.X = dD + oX;
@@ -439,24 +473,19 @@ void kg_discrete_mcmc_multistart(const std::vector<GpDev*>& gps, int nf, const m
     }
     MOE_LAUNCH_NOW(kg1_round_kernel, dim3(1), dim3(64), 0, z, a, outer.tolerance);
     MOE_HIP_CHECK(hipGetLastError());
-    MOE_HIP_CHECK(hipMemcpyAsync(hWords, T.iFail, sizeof(int) * ((size_t)E + 1), hipMemcpyDeviceToHost, z));
+    MOE_HIP_CHECK(hipMemcpyAsync(hWords, T.iFail, sizeof(int) * ((size_t)W + 1), hipMemcpyDeviceToHost, z));
     MOE_HIP_CHECK(hipStreamSynchronize(z));
     rows_done = (r + 1) * Tn;
-    for (int e = 0; e < E; ++e)
-      if (hWords[e] != INT_MAX)
-        throw Error(MOE_ERR_SINGULAR,
-                    "GP-Variance matrix singular. Check for duplicate points_to_sample or points_to_sample "
-                    "duplicating points_sampled with 0 noise.",
-                    e, hWords[e]);
-    alive = hWords[E];
+    throw_if_singular(T, hWords);
+    alive = hWords[W];
   }
 
   // the value at every end point, and everything back in one copy
   Kg1Recording last;
   evaluate(T, last, a.X, a.Xh, K, false);
   launch_mean_of_members(T, T.dKgTab, K, dVals);
-  MOE_LAUNCH_NOW(kg1_words_kernel, dim3(1), dim3(256), 0, z, (const int*)T.iFail, E, dD);
-  MOE_LAUNCH_NOW(kg1_words_kernel, dim3(1), dim3(256), 0, z, (const int*)iSteps, K, dD + E);
+  MOE_LAUNCH_NOW(kg1_words_kernel, dim3(1), dim3(256), 0, z, (const int*)T.iFail, W, dD);
+  MOE_LAUNCH_NOW(kg1_words_kernel, dim3(1), dim3(256), 0, z, (const int*)iSteps, K, dD + W);
   MOE_HIP_CHECK(hipGetLastError());
   g0.kg1oD.download(h, nBack, z);
   MOE_HIP_CHECK(hipStreamSynchronize(z));
@@ -464,7 +493,7 @@ void kg_discrete_mcmc_multistart(const std::vector<GpDev*>& gps, int nf, const m
   for (int k = 0; k < K; ++k) {
     const double* xk = h + oX + (size_t)k * dp;
     if (kept_index) kept_index[k] = order[k];
-    if (steps_taken) steps_taken[k] = (int)h[E + k];
+    if (steps_taken) steps_taken[k] = (int)h[W + k];
     if (end_points) std::copy(xk, xk + d, end_points + (size_t)k * d);
     if (end_values) end_values[k] = h[oVals + k];
     if (want_path) {
@@ -477,7 +506,62 @@ void kg_discrete_mcmc_multistart(const std::vector<GpDev*>& gps, int nf, const m
       *best_value = h[oVals + k];
       std::copy(xk, xk + d, best_point);
       *found = 1;
+      dBest = a.X + (size_t)k * dp;
     }
+  }
+  return dBest;
+}
+
+// the buffers of ascend() and the one upload; pcap: room for pending points, the first p of them the caller's
+void stage_ascent(Kg1Ensemble& T, const std::vector<GpDev*>& gps, int nf, const moe_gd_params_t& outer, const double* domain_bounds,
+                  const double* discrete_all, const int* num_discrete, const double* best_so_far, const double* starts, int S,
+                  bool ascent, bool want_path, const double* pending, int p, int pcap) {
+  check_members(gps, nf);
+  GpDev& g0 = *gps[0];
+  const int E = (int)gps.size(), W = pcap > 0 ? 2 * E : E, d = g0.d, dp = g0.dp;
+  const int R = std::max(outer.max_num_restarts, 0), Tn = outer.max_num_steps;
+  const int Kmax = ascent ? std::min(S, kMaxKept) : 0;
+  const size_t nBack = (size_t)W + Kmax + S + (size_t)Kmax * dp + (want_path ? (size_t)Kmax * (R * Tn + 1) * d : 0);
+  g0.use_device();
+  g0.kg1oD.reserve(nBack + 2 * (size_t)Kmax * dp);
+  g0.hStateOut.reserve(nBack);
+  // integers behind the failure words: [alive count | steps Kmax | order, running, alive Kmax each]
+  stage(T, gps, nf, discrete_all, num_discrete, best_so_far, domain_bounds, starts, S, ascent && R > 0, 1 + 4 * (size_t)Kmax, pending, p,
+        pcap);
+}
+
+}  // namespace
+
+void kg_discrete_mcmc_multistart(const std::vector<GpDev*>& gps, int nf, const moe_gd_params_t& outer, const double* domain_bounds,
+                                 const double* discrete_all, const int* num_discrete, const double* best_so_far,
+                                 const double* starts, int num_starts, int do_gradient_ascent, double* best_point,
+                                 double* best_value, int* found, double* start_values, int* kept_index, double* end_points,
+                                 double* end_values, double* path, int* steps_taken, const double* pending, int num_pending) {
+  Kg1Ensemble T;
+  const bool ascent = do_gradient_ascent != 0;
+  stage_ascent(T, gps, nf, outer, domain_bounds, discrete_all, num_discrete, best_so_far, starts, num_starts, ascent,
+               ascent && path != nullptr, pending, num_pending, num_pending);
+  ascend(T, outer, starts, num_starts, do_gradient_ascent, best_point, best_value, found, start_values, kept_index, end_points,
+         end_values, path, steps_taken);
+}
+
+// q points greedily: round t is the ascent above with the caller's pending points and the t points already picked; the set phase
+// runs once, a round appends one column to every member's extension and one row under its set.
+void kg_discrete_mcmc_suggest(const std::vector<GpDev*>& gps, int nf, const moe_gd_params_t& outer, const double* domain_bounds,
+                              const double* discrete_all, const int* num_discrete, const double* best_so_far, const double* starts,
+                              int num_starts, int do_gradient_ascent, const double* pending, int num_pending, int num_to_sample,
+                              double* best_points, double* best_values, int* found) {
+  Kg1Ensemble T;
+  stage_ascent(T, gps, nf, outer, domain_bounds, discrete_all, num_discrete, best_so_far, starts, num_starts, do_gradient_ascent != 0,
+               false, pending, num_pending, num_pending + num_to_sample - 1);
+  const int d = T.d;
+  for (int t = 0; t < num_to_sample; ++t) {
+    const double* dBest = ascend(T, outer, starts, num_starts, do_gradient_ascent, best_points + (size_t)t * d, best_values + t,
+                                 found + t, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (t + 1 == num_to_sample) break;
+    copy_async(T.dPending + (size_t)T.p * T.dp, dBest, sizeof(double) * (size_t)T.dp, hipMemcpyDeviceToDevice, T.z);
+    for (Kg1Member& m : T.mem) kg1_pending_append(m, 1, true, T.z);
+    T.p += 1;
   }
 }
 

@@ -11,7 +11,9 @@ domain, this one over {the candidate with its fidelity coordinates at 1} and A.
 ``PosteriorMeanMCMC`` of this package does.  Every evaluation is one ``moe_gp_kg_discrete`` call (csrc/kg1.hip).
 
 ``multistart_discrete_knowledge_gradient_optimization`` is the whole suggestion under a hyper-parameter ensemble in one library
-call (csrc/kg1_opt.hip): what the reference's examples/main.py asks ``gen_sample_from_qkg_mcmc`` for, at q = 1 and deterministic.
+call (csrc/kg1_opt.hip): what the reference's examples/main.py asks ``gen_sample_from_qkg_mcmc`` for, deterministic; with
+``num_to_sample`` = q > 1 the q points are picked greedily, and ``points_being_sampled`` names experiments that are running: the
+posterior covariance is conditioned on the pending points, the posterior mean is not (csrc/kg1_pending.hip).
 """
 import numpy as np
 
@@ -35,7 +37,8 @@ def _observed_values(gaussian_process):
 
 
 class DiscreteKnowledgeGradient(object):
-    def __init__(self, gaussian_process, discrete_pts, num_fidelity=0, best_so_far=None, points_to_sample=None):
+    def __init__(self, gaussian_process, discrete_pts, num_fidelity=0, best_so_far=None, points_to_sample=None,
+                 points_being_sampled=None):
         self._gaussian_process = gaussian_process
         self._dev = _device_gp(gaussian_process)
         self._num_fidelity = int(num_fidelity)
@@ -43,6 +46,8 @@ class DiscreteKnowledgeGradient(object):
         self._discrete_pts = np.ascontiguousarray(discrete_pts, dtype=np.float64).reshape(-1, self._dim - self._num_fidelity)
         self._best_so_far = float(np.min(_observed_values(gaussian_process))) if best_so_far is None else float(best_so_far)
         self._points_to_sample = np.zeros((1, self._dim)) if points_to_sample is None else np.copy(np.atleast_2d(points_to_sample))
+        self._points_being_sampled = (np.zeros((0, self._dim)) if points_being_sampled is None else
+                                      np.ascontiguousarray(points_being_sampled, dtype=np.float64).reshape(-1, self._dim))
         self.objective_type = None
 
     @property
@@ -73,7 +78,7 @@ class DiscreteKnowledgeGradient(object):
         """kg [C] of points [C][dim] in one device call; with want_grad (kg, grad [C][dim])"""
         points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, self._dim)
         return self._dev.kg_discrete(self._discrete_pts, points, self._best_so_far, num_fidelity=self._num_fidelity,
-                                     want_grad=want_grad)
+                                     want_grad=want_grad, points_being_sampled=self._points_being_sampled)
 
     def compute_knowledge_gradient(self, force_monte_carlo=False):
         return float(self.evaluate_at_point_list(self._points_to_sample.ravel()[:self._dim])[0])
@@ -90,12 +95,19 @@ class DiscreteKnowledgeGradient(object):
 
 
 def multistart_discrete_knowledge_gradient_optimization(gps, discrete_all, best_so_far_all, bounds, gd_params, num_multistarts, seed,
-                                                        num_fidelity=0):
+                                                        num_fidelity=0, num_to_sample=None, points_being_sampled=None):
     """The next point to sample under the ensemble ``gps`` (an api.DeviceGPMCMC, a list of api.DeviceGP or one api.DeviceGP): the
     multistart gradient ascent of the ensemble-averaged discretised knowledge gradient from ``num_multistarts`` Latin-hypercube
     starts in ``bounds`` [dim][2] (moe_latin_hypercube with ``seed``), member e over its own set discrete_all[e] and best value
-    best_so_far_all[e].  Returns (point [dim], value, found)."""
+    best_so_far_all[e].  Returns (point [dim], value, found).
+    With ``num_to_sample`` = q or ``points_being_sampled`` [p][dim] given: q points greedily (api.kg_discrete_suggest), each round
+    conditioned on the pending points and on the points picked before; returns (points [q][dim], values [q], found [q])."""
     from . import api
     starts = api.latin_hypercube(seed, bounds, num_multistarts)
+    if num_to_sample is not None or points_being_sampled is not None:
+        res = api.kg_discrete_suggest(gps, gd_params, bounds, discrete_all, best_so_far_all, starts,
+                                      1 if num_to_sample is None else num_to_sample, num_fidelity=num_fidelity,
+                                      points_being_sampled=points_being_sampled)
+        return res["points"], res["values"], res["found"]
     res = api.kg_discrete_multistart(gps, gd_params, bounds, discrete_all, best_so_far_all, starts, num_fidelity=num_fidelity)
     return res["point"], res["value"], res["found"]

@@ -204,6 +204,11 @@ int moe_gp_kg_discrete(const moe_gp_t* gp, int num_fidelity, const double* discr
                        int num_points, double best_so_far, int want_grad, double* kg, double* grad, int* num_active,
                        moe_error_t* err);
 int moe_kg1_pass_size(int num_rows, int num_discrete);
+/* num_active[num_points]: the number of lines on the envelope of each candidate of the LAST discretised knowledge-gradient
+ * evaluation this GP took part in (moe_gp_kg_discrete, or as a member of moe_kg_discrete_mcmc / moe_kg_discrete_mcmc_pending, which
+ * have no such output), read back from the GP's workspace.  num_points must be that call's (MOE_ERR_BOUNDS, payload (num_points,
+ * that call's, that call's)); a NULL handle or array -> MOE_ERR_RUNTIME. */
+int moe_gp_kg_discrete_last_active(const moe_gp_t* gp, int num_points, int* num_active, moe_error_t* err);
 /* moe_gp_kg_discrete averaged over an ensemble of num_mcmc GPs (one per hyper-parameter sample), every member e with its own
  * discrete set of num_discrete[e] points -- discrete_all holds the sets back to back, member e's [num_discrete[e]][dim -
  * num_fidelity] -- and its own best_so_far[e]:
@@ -260,6 +265,62 @@ int moe_kg_discrete_mcmc_multistart(const moe_gp_t* const* gps, int num_mcmc, in
                                     const double* best_so_far, const double* starts, int num_starts, int do_gradient_ascent,
                                     double* best_point, double* best_value, int* found, double* start_values, int* kept_index,
                                     double* end_points, double* end_values, double* path, int* steps_taken, moe_error_t* err);
+/* moe_kg_discrete_mcmc with pending points: points_being_sampled [num_being_sampled][dim], FULL points with their fidelity
+ * coordinates as given, whose experiments are running.  The posterior COVARIANCE of every member is conditioned on them (with the
+ * member's noise sigma^2) and the posterior MEAN is left alone -- the Kriging-believer fantasy of Ginsbourger et al. 2008 (the
+ * believed values are mu_n(P), so K'^-1 (y' - mean) = [K^-1 (y - mean) ; 0] exactly; the reference's docstrings still describe it,
+ * gpp_python_expected_improvement.cpp:452-469).  With V_P = L^-1 k(X, P), L_P L_P^T = k(P, P) + sigma^2 I - V_P^T V_P and
+ * r_z = L_P^-1 (k(P, z) - V_P^T v_z):
+ *   Sigma(z, x | P) = k(z, x) - v_z . v_x - r_z . r_x
+ * and kg / grad are moe_kg_discrete_mcmc's, word for word, with Sigma_n replaced by Sigma(. | P): s^2, the slopes, the tie rules,
+ * best_so_far, x^'s line, the envelope-theorem gradient over the N + num_being_sampled rows (P does not move with x), the members
+ * added in member order and divided once.  An ensemble of one is the single-GP form.
+ * The pending rows are an extension of at most 64 rows beside each member's own factor: no handle is modified and no matrix of
+ * N + num_being_sampled rows is formed.  A slope is one fused multiply-add chain over the member's rows in row order and then the
+ * pending rows in order, the same chain for x^'s line and the set's, so the duplicate and tie rules of moe_gp_kg_discrete hold bit
+ * for bit; a candidate's bits do not depend on how many share the call.  With num_being_sampled == 0 the call issues exactly the
+ * kernels of moe_kg_discrete_mcmc and returns its bits.  One copy down, one wait, one copy back.
+ * Errors, in this order: those of moe_kg_discrete_mcmc up to and including num_fidelity < 0; num_being_sampled outside 0 .. 64 ->
+ * MOE_ERR_BOUNDS, payload (num_being_sampled, 0, 64); points_being_sampled NULL with num_being_sampled > 0 -> MOE_ERR_RUNTIME; all
+ * of these before a handle is touched; then those of moe_kg_discrete_mcmc that need the handles.
+ * MOE_ERR_SINGULAR after the wait: payload (e, j) with a message that names the pending point -- the first member e whose
+ * extension has a Schur pivot <= 1e-16, and the first such pending point j (a noise-free member and a pending point repeating a
+ * pending or sampled point); reported before, and otherwise as, moe_kg_discrete_mcmc's candidate case (payload (e, i), its text).
+ * Memory: per member 8 (N + 64) (num_being_sampled + dim + 1) bytes besides moe_gp_kg_discrete's with N + num_being_sampled rows. */
+int moe_kg_discrete_mcmc_pending(const moe_gp_t* const* gps, int num_mcmc, int num_fidelity, const double* discrete_all,
+                                 const int* num_discrete, const double* best_so_far, const double* points_being_sampled,
+                                 int num_being_sampled, const double* points, int num_points, int want_grad, double* kg, double* grad,
+                                 moe_error_t* err);
+/* moe_kg_discrete_mcmc_multistart with moe_kg_discrete_mcmc_pending's objective: the same screening, top-20 rule, on-device step,
+ * rounds, end values and optional outputs.  The extension is built once, before the set phase.  With num_being_sampled == 0 the
+ * kernels and bits of moe_kg_discrete_mcmc_multistart.
+ * Errors, in this order: those of moe_kg_discrete_mcmc_multistart up to and including num_fidelity < 0; num_being_sampled, then
+ * points_being_sampled as above; max_num_steps; domain_type; then those that need the handles.  MOE_ERR_SINGULAR as above, at the
+ * next wait; a candidate's payload as in moe_kg_discrete_mcmc_multistart. */
+int moe_kg_discrete_mcmc_multistart_pending(const moe_gp_t* const* gps, int num_mcmc, int num_fidelity, const moe_gd_params_t* outer,
+                                            const double* domain_bounds, const double* discrete_all, const int* num_discrete,
+                                            const double* best_so_far, const double* points_being_sampled, int num_being_sampled,
+                                            const double* starts, int num_starts, int do_gradient_ascent, double* best_point,
+                                            double* best_value, int* found, double* start_values, int* kept_index,
+                                            double* end_points, double* end_values, double* path, int* steps_taken,
+                                            moe_error_t* err);
+/* num_to_sample points greedily by the ensemble-averaged discretised knowledge gradient: round t = 0 .. num_to_sample - 1 is
+ * moe_kg_discrete_mcmc_multistart_pending from the same starts [num_starts][dim] with pending points = points_being_sampled
+ * followed by the points x_0 .. x_{t-1} of the rounds before, and writes best_points[t][dim], best_values[t], found[t]: bit for bit
+ * what num_to_sample calls of that function return when each is fed its predecessors' points.
+ * The set phase runs once per member for the whole call.  Round t >= 1 appends ONE row to each member's extension -- one triangular
+ * product with one column, one row of L_P, one new row of r under the set's columns: O(N^2 + N num_discrete[e]), nothing is rebuilt
+ * -- and the picked point reaches the extension inside device memory.  One copy down; the host waits as often as
+ * moe_kg_discrete_mcmc_multistart does per round, and no more.
+ * Errors, in this order: those of moe_kg_discrete_mcmc_multistart_pending, with, directly after num_being_sampled: num_to_sample
+ * < 1 or num_being_sampled + num_to_sample - 1 > 64 -> MOE_ERR_BOUNDS, payload (num_to_sample, 1, 65 - num_being_sampled); and
+ * best_points, best_values, found among the arrays that must not be NULL.  MOE_ERR_SINGULAR as above: the pending index counts the
+ * caller's points first, then the rounds' picks. */
+int moe_kg_discrete_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, int num_fidelity, const moe_gd_params_t* outer,
+                                 const double* domain_bounds, const double* discrete_all, const int* num_discrete,
+                                 const double* best_so_far, const double* points_being_sampled, int num_being_sampled,
+                                 const double* starts, int num_starts, int do_gradient_ascent, int num_to_sample, double* best_points,
+                                 double* best_values, int* found, moe_error_t* err);
 /* compute_grad_variance_of_points -> ComputeGradVarianceOfPoints (gpp_math.cpp:1359-1373); out[num_derivs][m][m][dim] */
 int moe_gp_grad_variance(const moe_gp_t* gp, const double* pts, int num_pts, int num_derivs, double* out, moe_error_t* err);
 /* compute_grad_cholesky_variance_of_points -> ComputeGradCholeskyVarianceOfPoints (gpp_math.cpp:1454-1474) */
