@@ -41,16 +41,22 @@ __device__ __forceinline__ double exp_nonpos(double x) {
 // measured no faster: its lookups collide on LDS banks where the 64-entry table's mostly broadcast; and it costs 3.5 KB.)  <= 1.5 ulp (tools/mathcheck.hip).  Valid for -2.3e7 < x <= 0 (k must fit
 // 32 bits: beyond that the exponent wraps and the result can be anything, including inf) -- callers bound the argument:
 // sqrt(5) r <= 1e7 by construction of the tables (kg_mc.hpp to_frame / kTableExtent), -r2/2 by an explicit fmax.
-__device__ __forceinline__ double exp_nonpos_tab(double x, const double* __restrict__ tab64) {
+// In two halves, so that a caller with several independent arguments can issue all their table reads before the first polynomial
+// (kg_mc.hpp: the lookup-first tile loops).  Head: the reduction; returns the table index, r and k.  Finish: the polynomial on r, the
+// loaded T = tab64[index], the scaling.  exp_nonpos_tab is the composition, operation for operation.
+__device__ __forceinline__ int exp_nonpos_tab_head(double x, double& r, int& k) {
   const double kMagic = 6755399441055744.0;  // 1.5 * 2^52
   const double t = fma(x, 92.33248261689366, kMagic);  // 64 / ln2
   const double kf = t - kMagic;
   // (one-term reduction: ln2/64 as a double is 3.3e-17 relative off, i.e. r is off by |x| 3.3e-17 and e^x by the same RELATIVE
   //  amount -- |x| e^x 3.3e-17 <= 1.3e-17 absolute for x <= 0, a tenth of an ulp of the O(1) covariances it feeds; the lo term
   //  of the hi/lo split that used to follow cost one FP64 instruction per covariance entry)
-  const double r = fma(kf, -0.010830424696249145, x);  // ln2 / 64
-  const int k = __double2loint(t);  // low mantissa word of t = k (two's complement)
-  const double T = tab64[k & 63];
+  r = fma(kf, -0.010830424696249145, x);  // ln2 / 64
+  k = __double2loint(t);  // low mantissa word of t = k (two's complement)
+  return k & 63;
+}
+
+__device__ __forceinline__ double exp_nonpos_tab_finish(double T, double r, int k) {
   const double r2 = r * r;
   double q = 1.0 / 120.0;
   q = fma(q, r, 1.0 / 24.0);
@@ -58,6 +64,13 @@ __device__ __forceinline__ double exp_nonpos_tab(double x, const double* __restr
   q = fma(q, r, 0.5);
   const double sx = fma(r2, q, r);  // e^r - 1
   return ldexp(fma(T, sx, T), k >> 6);
+}
+
+__device__ __forceinline__ double exp_nonpos_tab(double x, const double* __restrict__ tab64) {
+  double r;
+  int k;
+  const int j = exp_nonpos_tab_head(x, r, k);
+  return exp_nonpos_tab_finish(tab64[j], r, k);
 }
 
 // sqrt(s) for s > 0 (no clamp; callers guarantee s >= 1e-300): v_rsq_f64 seed, one Newton step, one Heron

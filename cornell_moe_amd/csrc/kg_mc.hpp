@@ -332,21 +332,44 @@ __device__ __forceinline__ void clamp_query(double (&xq)[DP]) {
 // the frame's scale is sqrt(5) / length (KgMcParams::inv_lp carries the sqrt(5)), so r2 here is 5 r^2 and a = sqrt(r2) needs
 // no multiplication; with differences that are sqrt(5) times larger the derivative coefficients shrink by 5 and 25:
 //   d base / d q'_k = (1/3) e^-a (1 + a) (x'_k - q'_k),   d first / d (x' - q')_k = -(1/3) e^-a (x' - q')_k.
-template <int COV, bool NEED_FIRST, bool NEED_SECOND>
-__device__ __forceinline__ void radial3(double r2, const double* __restrict__ etab, double& base, double& first,
-                                        double& second) {
+// In two halves (fastmath.hpp: exp_nonpos_tab_head / _finish).  Head: the distance -> exp argument chain and the table read, through
+// `etab` as the caller types it -- a volatile LDS pointer (lds_tile_ptr) in the lookup-first tile loops, whose reads then keep their
+// program order among the tile reads.  Finish: the polynomial, the scaling and the covariance factors.  radial3 is the composition.
+struct RadialHead {
+  double T, a, r;  // the table entry | sqrt(r2) (Matern) | the reduced exp argument
+  int k;
+};
+template <int COV, class TabPtr>
+__device__ __forceinline__ RadialHead radial3_head(double r2, TabPtr etab) {
   // r2 >= 1e-300 by construction (the distance accumulation starts from 1e-300, see eval_loop)
+  RadialHead h;
   if (COV == MOE_COV_SQUARE_EXPONENTIAL) {
-    base = exp_nonpos_tab(fmax(-0.5 * r2, -1000.0), etab);  // (r2 can reach 1e13 here: keep the table exp in range)
+    h.a = 0.0;
+    h.T = etab[exp_nonpos_tab_head(fmax(-0.5 * r2, -1000.0), h.r, h.k)];  // (r2 can reach 1e13 here: keep the table exp in range)
+  } else {
+    h.a = sqrt_pos_fast(r2);  // (seed + one Heron step: <= 36 ulp, two instructions less per covariance entry)
+    h.T = etab[exp_nonpos_tab_head(-h.a, h.r, h.k)];
+  }
+  return h;
+}
+template <int COV, bool NEED_FIRST, bool NEED_SECOND>
+__device__ __forceinline__ void radial3_finish(const RadialHead& h, double& base, double& first, double& second) {
+  const double e = exp_nonpos_tab_finish(h.T, h.r, h.k);
+  if (COV == MOE_COV_SQUARE_EXPONENTIAL) {
+    base = e;
     first = base;
     second = base;
   } else {
-    const double a = sqrt_pos_fast(r2);  // (seed + one Heron step: <= 36 ulp, two instructions less per covariance entry)
-    const double e = exp_nonpos_tab(-a, etab);
+    const double a = h.a;
     base = e * fma(a, fma(a, 1.0 / 3.0, 1.0), 1.0);  // e^-a (1 + a + a^2/3)
     first = NEED_FIRST ? (1.0 / 3.0) * (e * (a + 1.0)) : 0.0;
     second = NEED_SECOND ? (1.0 / 3.0) * e : 0.0;
   }
+}
+template <int COV, bool NEED_FIRST, bool NEED_SECOND>
+__device__ __forceinline__ void radial3(double r2, const double* __restrict__ etab, double& base, double& first,
+                                        double& second) {
+  radial3_finish<COV, NEED_FIRST, NEED_SECOND>(radial3_head<COV>(r2, etab), base, first, second);
 }
 
 // One pass over the n + u points for the wave's sample: returns f = -mu_after(x) and (if WG) grad f in table-row order.
@@ -377,7 +400,7 @@ struct tile_ptr<true> {
 // Q2IN (value passes of the frame line search): `xq_in` holds q2 = -2 x (what the dot-product distances multiply the table rows
 // with), so a trial point costs DP fmas to set up instead of DP frame conversions + DP scalings.  FRAMEG: the gradient is
 // returned with respect to the FRAME coordinates (not multiplied by the frame scale).
-template <int DP, int G, bool WG, int COV, bool SMALL, bool XL, bool Q2IN = false, bool FRAMEG = false>
+template <int DP, int G, bool WG, int COV, bool SMALL, bool XL, bool Q2IN = false, bool FRAMEG = false, bool LF = false>
 __device__ __forceinline__ double eval_loop(const double* __restrict__ xs, const double* __restrict__ aw,
                                             const double* __restrict__ etab, int ntiles, double mean,
                                             const double (&xq_in)[DP], const double* inv_lp, double (&grad)[DP], int lane,
@@ -386,6 +409,7 @@ __device__ __forceinline__ double eval_loop(const double* __restrict__ xs, const
   //  the cancellation of the two terms, and where the inner optimiser runs to convergence -- 100 steps x 10 restarts, the reference's
   //  own ping-test settings -- the end points drift to 1.4e-6 from the reference's instead of 1e-7)
   constexpr bool DOT = XL && !WG;  // squared distance from the |x|^2 row
+  constexpr bool LFX = LF && XL;  // lookup-first order of the tile loop (LDS table only; the caller asks for it: kg_mc_lane.hpp)
   constexpr int XR = DP + (XL ? 1 : 0);  // rows per coordinate tile
   double q2[DP], xq[DP];
   double qq;
@@ -435,10 +459,12 @@ __device__ __forceinline__ double eval_loop(const double* __restrict__ xs, const
     // the last iteration prefetches one tile past the end -- the host pads both arrays by one tile, the values are unused
     xt += XR * 64;
     wt += (1 + G) * 64;
+    if (!LFX) {
 #pragma unroll
-    for (int k = 0; k < NX; ++k) nx[k] = xt[k * 64];
+      for (int k = 0; k < NX; ++k) nx[k] = xt[k * 64];
 #pragma unroll
-    for (int a = 0; a < 1 + G; ++a) nw[a] = wt[a * 64];
+      for (int a = 0; a < 1 + G; ++a) nw[a] = wt[a * 64];
+    }
     double diff[DP];
     double r2;
     if (DOT) {
@@ -460,7 +486,18 @@ __device__ __forceinline__ double eval_loop(const double* __restrict__ xs, const
     }
     const double w0 = cw[0];  // alpha * (function-value weight)
     double base, first, second;
-    radial3<COV, (WG || G > 0), (WG && G > 0)>(r2, etab, base, first, second);
+    if (LFX) {
+      // the exp-table read goes out BEFORE the next tile's reads (volatile LDS reads keep their order, and LDS returns in
+      // order), so the wait in front of the finish leaves the prefetch in flight instead of draining it every tile
+      const RadialHead h = radial3_head<COV>(r2, (lds_tile_ptr)etab);
+#pragma unroll
+      for (int k = 0; k < NX; ++k) nx[k] = xt[k * 64];
+#pragma unroll
+      for (int a = 0; a < 1 + G; ++a) nw[a] = wt[a * 64];
+      radial3_finish<COV, (WG || G > 0), (WG && G > 0)>(h, base, first, second);
+    } else {
+      radial3<COV, (WG || G > 0), (WG && G > 0)>(r2, etab, base, first, second);
+    }
     double sd = 0.0;  // sum_a w_a diff[a]  (derivative-observation weights; table rows a < G are the observed dims)
     if (G > 0) {
 #pragma unroll
@@ -503,15 +540,15 @@ __device__ __forceinline__ double eval_loop(const double* __restrict__ xs, const
 
 // The covariance type is wave-uniform: branch ONCE per pass (a branch inside the tile loop would split it into basic blocks
 // and stop the scheduler from interleaving the independent per-tile dependency chains).
-template <int DP, int G, bool WG, bool SMALL, bool XL, bool Q2IN = false, bool FRAMEG = false>
+template <int DP, int G, bool WG, bool SMALL, bool XL, bool Q2IN = false, bool FRAMEG = false, bool LF = false>
 __device__ __forceinline__ double eval_pass(const double* __restrict__ xs, const double* __restrict__ aw,
                                             const double* __restrict__ etab, int ntiles, int cov_type, double mean,
                                             const double (&xq)[DP], const double* inv_lp, double (&grad)[DP], int lane,
                                             double* __restrict__ scr = nullptr) {
   if (cov_type == MOE_COV_SQUARE_EXPONENTIAL)
-    return eval_loop<DP, G, WG, MOE_COV_SQUARE_EXPONENTIAL, SMALL, XL, Q2IN, FRAMEG>(xs, aw, etab, ntiles, mean, xq, inv_lp, grad,
+    return eval_loop<DP, G, WG, MOE_COV_SQUARE_EXPONENTIAL, SMALL, XL, Q2IN, FRAMEG, LF>(xs, aw, etab, ntiles, mean, xq, inv_lp, grad,
                                                                                       lane, scr);
-  return eval_loop<DP, G, WG, MOE_COV_MATERN_NU_2P5, SMALL, XL, Q2IN, FRAMEG>(xs, aw, etab, ntiles, mean, xq, inv_lp, grad, lane,
+  return eval_loop<DP, G, WG, MOE_COV_MATERN_NU_2P5, SMALL, XL, Q2IN, FRAMEG, LF>(xs, aw, etab, ntiles, mean, xq, inv_lp, grad, lane,
                                                                                  scr);
 }
 
@@ -531,7 +568,7 @@ __device__ __forceinline__ double eval_pass(const double* __restrict__ xs, const
 // fma per trial), multiplied by the first-derivative coefficient of the trial's distance.
 // (eval_multi_loop_s: the three sums |x2|^2, x2.d2, |d2|^2 -- fixed along a trial line -- handed in by a caller that forms them once
 //  per bracket, kg_mc_lane.hpp; eval_multi_loop forms them itself, in the same order)
-template <int DP, int COV, int T, bool SMALL, bool XL = true, int G = 0>
+template <int DP, int COV, int T, bool SMALL, bool XL = true, int G = 0, bool LF = false>
 __device__ __forceinline__ bool eval_multi_loop_s(const double* __restrict__ xs, const double* __restrict__ aw,
                                                   const double* __restrict__ etab, int ntiles, double mean, const double (&x2)[DP],
                                                   const double (&d2)[DP], double sxx, double sxd, double sdd, double alpha0, int lane,
@@ -565,62 +602,121 @@ __device__ __forceinline__ bool eval_multi_loop_s(const double* __restrict__ xs,
 #pragma unroll
     for (int t = 0; t < T; ++t) tt[t] = (al[t] * al[t]) * (0.25 * sdd);  // alpha_t^2 |dv|^2
   }
-#pragma unroll(SMALL ? 1 : 2)  // (four tiles for few trials: +-0.3 %, r5)
-  for (int tile = 0; tile < ntiles; ++tile) {
-    double nx[NX], nwa[WR];
-    xt += NX * 64;  // (one tile of padding behind both arrays: see eval_loop)
-    wt += WR * 64;
+  if constexpr (LF && XL) {
+    // Lookup-first order (LDS table; the caller asks for it: kg_mc_lane.hpp kLaneLookupFirst).  Per tile: the heads of all T trials and
+    // their T exp-table reads, back to back; THEN the next tile's reads; then the finishes, whose polynomials need no table entry and
+    // cover the one round trip a tile now waits for (the reads are volatile LDS reads: they keep this order, LDS returns in order, and
+    // the wait before the first finish leaves the prefetch in flight).
+    // one_tile ADVANCES xt / wt to the next tile, adds the current tile's terms to acc[] and leaves the next tile's rows in cx[] / cwa[].
+    auto one_tile = [&]() __attribute__((always_inline)) {
+      double nx[NX], nwa[WR];
+      xt += NX * 64;  // (one tile of padding behind both arrays: see eval_loop)
+      wt += WR * 64;
+      const double cw = cwa[0];
+      double sdA = 0.0, sdB = 0.0;  // derivative-weight sum of trial t: sdA - alpha_t sdB (see the loop below)
+      if (G > 0) {
 #pragma unroll
-    for (int k = 0; k < NX; ++k) nx[k] = xt[k * 64];
-#pragma unroll
-    for (int a = 0; a < WR; ++a) nwa[a] = wt[a * 64];
-    const double cw = cwa[0];
-    // derivative-weight sum of trial t: sum_a w_a (x_ja - x0_a - alpha_t dv_a) = sdA - alpha_t sdB
-    double sdA = 0.0, sdB = 0.0;
-    if (G > 0) {
-#pragma unroll
-      for (int a = 0; a < G; ++a) {
-        sdA = fma(cwa[1 + a], cx[a] - x0[a], sdA);
-        sdB = fma(cwa[1 + a], dv[a], sdB);
+        for (int a = 0; a < G; ++a) {
+          sdA = fma(cwa[1 + a], cx[a] - x0[a], sdA);
+          sdB = fma(cwa[1 + a], dv[a], sdB);
+        }
       }
-    }
-    if (XL) {
-      double p0 = cx[XL ? DP : 0];
+      double p0 = cx[DP];
 #pragma unroll
       for (int k = 0; k < DP; ++k) p0 = fma(cx[k], x2[k], p0);
       double p1 = cx[0] * d2[0];
 #pragma unroll
       for (int k = 1; k < DP; ++k) p1 = fma(cx[k], d2[k], p1);
+      RadialHead h[T];
 #pragma unroll
       for (int t = 0; t < T; ++t) {
         const double r2 = fmax(fma(al[t], p1, p0 + qq[t]), 1.0e-300);
-        double base, first, second;
-        radial3<COV, (G > 0), false>(r2, etab, base, first, second);
-        acc[t] = fma(cw, base, acc[t]);
-        if (G > 0) acc[t] = fma(first, fma(-al[t], sdB, sdA), acc[t]);
+        h[t] = radial3_head<COV>(r2, (lds_tile_ptr)etab);
       }
-    } else {
-      double A = 1.0e-300, B = 0.0;
 #pragma unroll
-      for (int k = 0; k < DP; ++k) {
-        const double d0 = cx[k] - x0[k];
-        A = fma(d0, d0, A);
-        B = fma(d0, dv[k], B);
-      }
-      const double mB2 = -2.0 * B;
+      for (int k = 0; k < NX; ++k) nx[k] = xt[k * 64];
+#pragma unroll
+      for (int a = 0; a < WR; ++a) nwa[a] = wt[a * 64];
+      // (left to itself the scheduler runs some tiles' trials as a chain of head / read / wait / finish again)
+      __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int t = 0; t < T; ++t) {
-        const double r2 = fmax(fma(al[t], mB2, A + tt[t]), 1.0e-300);
         double base, first, second;
-        radial3<COV, (G > 0), false>(r2, etab, base, first, second);
+        radial3_finish<COV, (G > 0), false>(h[t], base, first, second);
         acc[t] = fma(cw, base, acc[t]);
         if (G > 0) acc[t] = fma(first, fma(-al[t], sdB, sdA), acc[t]);
       }
+#pragma unroll
+      for (int k = 0; k < NX; ++k) cx[k] = nx[k];
+#pragma unroll
+      for (int a = 0; a < WR; ++a) cwa[a] = nwa[a];
+    };
+    // two tiles per iteration by hand: sched_barrier is a convergent operation, and the unroller leaves a loop with one and a
+    // run-time trip count alone
+    int tile = 0;
+    for (; tile + 1 < ntiles; tile += 2) {
+      one_tile();
+      one_tile();
     }
+    if (tile < ntiles) one_tile();
+  } else {
+#pragma unroll(SMALL ? 1 : 2)  // (four tiles for few trials: +-0.3 %, r5)
+    for (int tile = 0; tile < ntiles; ++tile) {
+      double nx[NX], nwa[WR];
+      xt += NX * 64;  // (one tile of padding behind both arrays: see eval_loop)
+      wt += WR * 64;
 #pragma unroll
-    for (int k = 0; k < NX; ++k) cx[k] = nx[k];
+      for (int k = 0; k < NX; ++k) nx[k] = xt[k * 64];
 #pragma unroll
-    for (int a = 0; a < WR; ++a) cwa[a] = nwa[a];
+      for (int a = 0; a < WR; ++a) nwa[a] = wt[a * 64];
+      const double cw = cwa[0];
+      // derivative-weight sum of trial t: sum_a w_a (x_ja - x0_a - alpha_t dv_a) = sdA - alpha_t sdB
+      double sdA = 0.0, sdB = 0.0;
+      if (G > 0) {
+#pragma unroll
+        for (int a = 0; a < G; ++a) {
+          sdA = fma(cwa[1 + a], cx[a] - x0[a], sdA);
+          sdB = fma(cwa[1 + a], dv[a], sdB);
+        }
+      }
+      if (XL) {
+        double p0 = cx[XL ? DP : 0];
+#pragma unroll
+        for (int k = 0; k < DP; ++k) p0 = fma(cx[k], x2[k], p0);
+        double p1 = cx[0] * d2[0];
+#pragma unroll
+        for (int k = 1; k < DP; ++k) p1 = fma(cx[k], d2[k], p1);
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+          const double r2 = fmax(fma(al[t], p1, p0 + qq[t]), 1.0e-300);
+          double base, first, second;
+          radial3<COV, (G > 0), false>(r2, etab, base, first, second);
+          acc[t] = fma(cw, base, acc[t]);
+          if (G > 0) acc[t] = fma(first, fma(-al[t], sdB, sdA), acc[t]);
+        }
+      } else {
+        double A = 1.0e-300, B = 0.0;
+#pragma unroll
+        for (int k = 0; k < DP; ++k) {
+          const double d0 = cx[k] - x0[k];
+          A = fma(d0, d0, A);
+          B = fma(d0, dv[k], B);
+        }
+        const double mB2 = -2.0 * B;
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+          const double r2 = fmax(fma(al[t], mB2, A + tt[t]), 1.0e-300);
+          double base, first, second;
+          radial3<COV, (G > 0), false>(r2, etab, base, first, second);
+          acc[t] = fma(cw, base, acc[t]);
+          if (G > 0) acc[t] = fma(first, fma(-al[t], sdB, sdA), acc[t]);
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < NX; ++k) cx[k] = nx[k];
+#pragma unroll
+      for (int a = 0; a < WR; ++a) cwa[a] = nwa[a];
+    }
   }
   // T wave sums, folded four / two at a time (packed reductions above)
   double sum[T];
@@ -648,7 +744,7 @@ __device__ __forceinline__ bool eval_multi_loop_s(const double* __restrict__ xs,
 // For the small shapes whose end points the reference's 100-step x 10-restart fixtures pin: there the line decomposition's rounding moved
 // them by 1.01e-6 (kg.hip), so until r6 those shapes ran one trial per pass.  LDS table only.  Returns false without evaluating when a
 // trial lies beyond kFarRadius (the single-trial pass returns the prior mean there: the caller falls back to it).
-template <int DP, int COV, int T, int G>
+template <int DP, int COV, int T, int G, bool LF = false>
 __device__ __forceinline__ bool eval_multi_exact(const double* __restrict__ xs, const double* __restrict__ aw,
                                                  const double* __restrict__ etab, int ntiles, double mean, const double (&x2)[DP],
                                                  const double (&d2)[DP], double alpha0, int lane, double (&f)[T]) {
@@ -686,25 +782,53 @@ __device__ __forceinline__ bool eval_multi_exact(const double* __restrict__ xs, 
     double nx[NX], nw[WR];
     xt += NX * 64;  // (one tile of padding behind both arrays: see eval_loop)
     wt += WR * 64;
-#pragma unroll
-    for (int k = 0; k < NX; ++k) nx[k] = xt[k * 64];
-#pragma unroll
-    for (int a = 0; a < WR; ++a) nw[a] = wt[a * 64];
     const double w0 = cw[0];
+    if (!LF) {
 #pragma unroll
-    for (int t = 0; t < T; ++t) {
-      double r2 = cx[DP] + qq[t];
+      for (int k = 0; k < NX; ++k) nx[k] = xt[k * 64];
 #pragma unroll
-      for (int k = 0; k < DP; ++k) r2 = fma(cx[k], q2[t][k], r2);
-      r2 = fmax(r2, 1.0e-300);
-      double base, first, second;
-      radial3<COV, (G > 0), false>(r2, etab, base, first, second);
-      acc[t] = fma(w0, base, acc[t]);
-      if (G > 0) {
-        double sd = 0.0;
+      for (int a = 0; a < WR; ++a) nw[a] = wt[a * 64];
 #pragma unroll
-        for (int a = 0; a < G; ++a) sd = fma(cw[1 + a], cx[a] - xq[t][a], sd);
-        acc[t] = fma(first, sd, acc[t]);
+      for (int t = 0; t < T; ++t) {
+        double r2 = cx[DP] + qq[t];
+#pragma unroll
+        for (int k = 0; k < DP; ++k) r2 = fma(cx[k], q2[t][k], r2);
+        r2 = fmax(r2, 1.0e-300);
+        double base, first, second;
+        radial3<COV, (G > 0), false>(r2, etab, base, first, second);
+        acc[t] = fma(w0, base, acc[t]);
+        if (G > 0) {
+          double sd = 0.0;
+#pragma unroll
+          for (int a = 0; a < G; ++a) sd = fma(cw[1 + a], cx[a] - xq[t][a], sd);
+          acc[t] = fma(first, sd, acc[t]);
+        }
+      }
+    } else {
+      RadialHead h[T];  // (lookup-first, as in eval_multi_loop_s: T heads and table reads, the next tile's reads, T finishes)
+#pragma unroll
+      for (int t = 0; t < T; ++t) {
+        double r2 = cx[DP] + qq[t];
+#pragma unroll
+        for (int k = 0; k < DP; ++k) r2 = fma(cx[k], q2[t][k], r2);
+        r2 = fmax(r2, 1.0e-300);
+        h[t] = radial3_head<COV>(r2, (lds_tile_ptr)etab);
+      }
+#pragma unroll
+      for (int k = 0; k < NX; ++k) nx[k] = xt[k * 64];
+#pragma unroll
+      for (int a = 0; a < WR; ++a) nw[a] = wt[a * 64];
+#pragma unroll
+      for (int t = 0; t < T; ++t) {
+        double base, first, second;
+        radial3_finish<COV, (G > 0), false>(h[t], base, first, second);
+        acc[t] = fma(w0, base, acc[t]);
+        if (G > 0) {
+          double sd = 0.0;
+#pragma unroll
+          for (int a = 0; a < G; ++a) sd = fma(cw[1 + a], cx[a] - xq[t][a], sd);
+          acc[t] = fma(first, sd, acc[t]);
+        }
       }
     }
 #pragma unroll

@@ -28,6 +28,14 @@ constexpr int kLaneGradUnroll = 4;  // tiles unrolled in the gradient pass (r5 A
 // (closed r5 A/Bs, `profiles/r05_a_lane_ab.txt`, `r05_b_unroll_variants_ab.txt`: a pass's wave-uniform operands as SCALAR registers --
 //  v_readfirstlane -- against wave-uniform vector registers +-0.5 %; kernel arguments re-read per sample against held -1 %)
 
+// Which instantiations run their tile loops lookup-first (kg_mc.hpp: eval_multi_loop_s; the T heads of a tile live at once cost
+// ~24 VGPRs): those the compiler's resource report shows free of scratch with it -- padded dimension <= 8, at most one derivative
+// slot, the line-decomposed sweep.  With two or more slots, at DP = 12 / 16, in the exact small-shape sweep and in the ensemble twins
+// (launch.hpp: their argument table costs ~15 VGPRs more) the order spilt 12-220 bytes per lane: they keep one lookup at a time.
+// The two orders give the same bits (tests/test_gpu_kg_lookup_order.py).
+template <int DP, int G, bool EXACT>
+constexpr bool kLaneLookupFirst = DP <= 8 && G <= 1 && !EXACT;
+
 constexpr int kLaneCstRows = 8;  // s | 1 / s | centre | pinned value | lower bound | upper bound (original units) | perm | free (1 / 0)
 constexpr int kMaxLaneDP = 16;
 
@@ -79,7 +87,7 @@ __device__ __forceinline__ double wave_max_uniform(double v) {
 
 // Value + gradient pass with the gradient returned LANE-PARKED (lane k < DP: d f / d x'_k in the frame): eval_loop<DP, G, true, COV,
 // false, true, false, true> of kg_mc.hpp with the read-back of the packed sums changed -- lane k reads sum k.  `S` = 2 kMaxLaneDP doubles of scratch.
-template <int DP, int G, int COV>
+template <int DP, int G, int COV, bool LF>
 __device__ __forceinline__ double grad_pass_parked(const double* __restrict__ xs, const double* __restrict__ aw,
                                                    const double* __restrict__ etab, int ntiles, double mean, const double (&xq)[DP],
                                                    lds_rw_ptr S, int lane, double& g_l) {
@@ -104,10 +112,12 @@ __device__ __forceinline__ double grad_pass_parked(const double* __restrict__ xs
     double nx[DP], nw[WR];
     xt += XR * 64;
     wt += WR * 64;
+    if (!LF) {
 #pragma unroll
-    for (int k = 0; k < DP; ++k) nx[k] = xt[k * 64];
+      for (int k = 0; k < DP; ++k) nx[k] = xt[k * 64];
 #pragma unroll
-    for (int a = 0; a < WR; ++a) nw[a] = wt[a * 64];
+      for (int a = 0; a < WR; ++a) nw[a] = wt[a * 64];
+    }
     double diff[DP];
     double r2 = 1.0e-300;
 #pragma unroll
@@ -117,7 +127,16 @@ __device__ __forceinline__ double grad_pass_parked(const double* __restrict__ xs
     }
     const double w0 = cw[0];
     double base, first, second;
-    radial3<COV, true, (G > 0)>(r2, etab, base, first, second);
+    if (LF) {
+      const RadialHead h = radial3_head<COV>(r2, (lds_tile_ptr)etab);  // (lookup-first: the table read ahead of the prefetch, eval_loop)
+#pragma unroll
+      for (int k = 0; k < DP; ++k) nx[k] = xt[k * 64];
+#pragma unroll
+      for (int a = 0; a < WR; ++a) nw[a] = wt[a * 64];
+      radial3_finish<COV, true, (G > 0)>(h, base, first, second);
+    } else {
+      radial3<COV, true, (G > 0)>(r2, etab, base, first, second);
+    }
     double sd = 0.0;
     if (G > 0) {
 #pragma unroll
@@ -168,7 +187,7 @@ __device__ __forceinline__ double grad_pass_parked(const double* __restrict__ xs
 // the evaluation's record head [L | mu_disc | C_disc | disc] (offsets as in KgRec).
 // EXACT (r6): the Armijo trials of a bracket in one sweep, each computed as a single-trial pass computes it (eval_multi_exact) -- the
 // instantiation of the small shapes (kg.hip: small_lane), whose passes were single-trial until then; same bits.
-template <int DP, int G, bool EXACT>
+template <int DP, int G, bool EXACT, bool LF>
 __device__ __forceinline__ void kg_sample_lane(const KgMcParams& P, int e, int sl, const double* __restrict__ xs,
                                                double* __restrict__ aw, double* __restrict__ zb, const double* __restrict__ etab,
                                                const double* __restrict__ cst, const double* __restrict__ rc, int lane,
@@ -334,8 +353,8 @@ __device__ __forceinline__ void kg_sample_lane(const KgMcParams& P, int e, int s
           lane_broadcast<DP>(xf_l, R0, lane, xq);
           make_scalar<DP>(xq);
           f0 = (cov_type == MOE_COV_SQUARE_EXPONENTIAL)
-                   ? grad_pass_parked<DP, G, MOE_COV_SQUARE_EXPONENTIAL>(xs, aw, etab, ntiles, mean, xq, R1, lane, gf_l)
-                   : grad_pass_parked<DP, G, MOE_COV_MATERN_NU_2P5>(xs, aw, etab, ntiles, mean, xq, R1, lane, gf_l);
+                   ? grad_pass_parked<DP, G, MOE_COV_SQUARE_EXPONENTIAL, LF>(xs, aw, etab, ntiles, mean, xq, R1, lane, gf_l)
+                   : grad_pass_parked<DP, G, MOE_COV_MATERN_NU_2P5, LF>(xs, aw, etab, ntiles, mean, xq, R1, lane, gf_l);
         }
         f0 = uniform(f0);  // (tells the compiler: the Armijo decisions below are scalar branches)
         n_grad++;
@@ -387,12 +406,12 @@ __device__ __forceinline__ void kg_sample_lane(const KgMcParams& P, int e, int s
   {                                                                                                                                     \
     double ft[T];                                                                                                                       \
     if constexpr (EXACT)                                                                                                                \
-      evaluated = se ? eval_multi_exact<DP, MOE_COV_SQUARE_EXPONENTIAL, T, G>(xs, aw, etab, ntiles, mean, x2, d2, alpha_n, lane, ft)    \
-                     : eval_multi_exact<DP, MOE_COV_MATERN_NU_2P5, T, G>(xs, aw, etab, ntiles, mean, x2, d2, alpha_n, lane, ft);        \
+      evaluated = se ? eval_multi_exact<DP, MOE_COV_SQUARE_EXPONENTIAL, T, G, LF>(xs, aw, etab, ntiles, mean, x2, d2, alpha_n, lane, ft)    \
+                     : eval_multi_exact<DP, MOE_COV_MATERN_NU_2P5, T, G, LF>(xs, aw, etab, ntiles, mean, x2, d2, alpha_n, lane, ft);        \
     else                                                                                                                                \
-      evaluated = se ? eval_multi_loop_s<DP, MOE_COV_SQUARE_EXPONENTIAL, T, false, true, G>(xs, aw, etab, ntiles, mean, x2, d2, sxx,    \
+      evaluated = se ? eval_multi_loop_s<DP, MOE_COV_SQUARE_EXPONENTIAL, T, false, true, G, LF>(xs, aw, etab, ntiles, mean, x2, d2, sxx,    \
                                                                                             sxd, sdd, alpha_n, lane, ft)               \
-                     : eval_multi_loop_s<DP, MOE_COV_MATERN_NU_2P5, T, false, true, G>(xs, aw, etab, ntiles, mean, x2, d2, sxx, sxd,    \
+                     : eval_multi_loop_s<DP, MOE_COV_MATERN_NU_2P5, T, false, true, G, LF>(xs, aw, etab, ntiles, mean, x2, d2, sxx, sxd,    \
                                                                                        sdd, alpha_n, lane, ft);                        \
     if (evaluated) {                                                                                                                    \
       _Pragma("unroll") for (int t = 0; t < T; ++t) {                                                                                   \
@@ -422,7 +441,7 @@ __device__ __forceinline__ void kg_sample_lane(const KgMcParams& P, int e, int s
               double q2[DP], unused[DP];
 #pragma unroll
               for (int k = 0; k < DP; ++k) q2[k] = fma(alpha_n, d2[k], x2[k]);
-              ftrial = eval_pass<DP, G, false, false, true, true, false>(xs, aw, etab, ntiles, cov_type, mean, q2, nullptr, unused, lane);
+              ftrial = eval_pass<DP, G, false, false, true, true, false, LF>(xs, aw, etab, ntiles, cov_type, mean, q2, nullptr, unused, lane);
               n_val++;
               if (ftrial - f0 > 0.5 * alpha_n * norm) {
                 done = true;
@@ -464,13 +483,13 @@ __device__ __forceinline__ void kg_sample_lane(const KgMcParams& P, int e, int s
             lane_broadcast<DP>(xf_l + st_l, R0, lane, xq);
             make_scalar<DP>(xq);
             obj2 = (cov_type == MOE_COV_SQUARE_EXPONENTIAL)
-                       ? grad_pass_parked<DP, G, MOE_COV_SQUARE_EXPONENTIAL>(xs, aw, etab, ntiles, mean, xq, R1, lane, gn_l)
-                       : grad_pass_parked<DP, G, MOE_COV_MATERN_NU_2P5>(xs, aw, etab, ntiles, mean, xq, R1, lane, gn_l);
+                       ? grad_pass_parked<DP, G, MOE_COV_SQUARE_EXPONENTIAL, LF>(xs, aw, etab, ntiles, mean, xq, R1, lane, gn_l)
+                       : grad_pass_parked<DP, G, MOE_COV_MATERN_NU_2P5, LF>(xs, aw, etab, ntiles, mean, xq, R1, lane, gn_l);
             carried = true;
           } else {
             double q2[DP], unused[DP];
             lane_broadcast<DP>(fma(-2.0, st_l, x2_l), R0, lane, q2);
-            obj2 = eval_pass<DP, G, false, false, true, true, false>(xs, aw, etab, ntiles, cov_type, mean, q2, nullptr, unused, lane);
+            obj2 = eval_pass<DP, G, false, false, true, true, false, LF>(xs, aw, etab, ntiles, cov_type, mean, q2, nullptr, unused, lane);
             n_val++;
           }
         }
@@ -521,7 +540,7 @@ __device__ __forceinline__ void kg_sample_lane(const KgMcParams& P, int e, int s
 // (weights [ntiles (1 + G) 64] + 2 kMaxM doubles of scratch) | one weight tile of padding.  Built for the LDS coordinate table, 8 waves.
 // (r6: the body as a device function -- launch.hpp -- so that the members of a GP ensemble share one launch; `argbase`: where this
 //  member's arguments lie, the kernarg segment or its record in the ensemble twin's table)
-template <int DP, int G, bool EXACT = false>
+template <int DP, int G, bool EXACT = false, bool LF = false>
 struct kg_mc_lane_kernel_body {
 static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void* argbase, const KgMcParams& P, int rec_head) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -572,7 +591,7 @@ static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridD
       // (P is the kernel's first argument: offset 0 of the segment)
       const __attribute__((address_space(4))) KgMcParams* Pk = (const __attribute__((address_space(4))) KgMcParams*)argbase;
       asm volatile("" : "+s"(Pk));
-      kg_sample_lane<DP, G, EXACT>(*(const KgMcParams*)Pk, e, (int)sl, coords, aw, zb, smem, cst, rc, lane, tot_val, tot_grad);
+      kg_sample_lane<DP, G, EXACT, LF>(*(const KgMcParams*)Pk, e, (int)sl, coords, aw, zb, smem, cst, rc, lane, tot_val, tot_grad);
     }
     if (lane == 0 && (tot_val | tot_grad) != 0) {
       atomicAdd(&P.counters[2 * e], (unsigned long long)tot_val);
@@ -584,7 +603,7 @@ static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridD
 };
 template <int DP, int G, bool EXACT = false>
 __global__ __launch_bounds__(kLaneMaxThreads) void kg_mc_lane_kernel(KgMcParams P, int rec_head) {
-  kg_mc_lane_kernel_body<DP, G, EXACT>::run(MOE_VBLOCK, MOE_VGRID, (const void*)__builtin_amdgcn_kernarg_segment_ptr(), P, rec_head);
+  kg_mc_lane_kernel_body<DP, G, EXACT, kLaneLookupFirst<DP, G, EXACT>>::run(MOE_VBLOCK, MOE_VGRID, (const void*)__builtin_amdgcn_kernarg_segment_ptr(), P, rec_head);
 }
 
 // LDS bytes of a workgroup of `waves` wavefronts (host side: kg.hip's geometry)
@@ -598,6 +617,7 @@ template <int DP, int G, bool EXACT = false>
 inline void launch_lane_inst(const KgMcParams& P, int rec_head, int blocks, int waves, size_t shm, hipStream_t s) {
   auto kern = kg_mc_lane_kernel<DP, G, EXACT>;
   MOE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+  // (the ensemble twin is built on the body WITHOUT the lookup-first order: see kLaneLookupFirst)
   launch_kernel_ens<kg_mc_lane_kernel_body<DP, G, EXACT>, kLaneMaxThreads>(kern, dim3(blocks), dim3(waves * 64), shm, s, P, rec_head);
   MOE_HIP_CHECK(hipGetLastError());
 }
