@@ -960,6 +960,96 @@ def kg_discrete_suggest(gps, gd_params, bounds, discrete_all, best_so_far_all, s
     return {"points": points, "values": values, "found": found.astype(bool)}
 
 
+def _ei_analytic_members(gps, best_so_far):
+    """(handles, count, dim, members kept alive, best values [E]) of the ensemble forms of the analytic expected improvement; a single
+    DeviceGP counts as a list of one"""
+    if isinstance(gps, DeviceGP):
+        gps = [gps]
+    arr, E, d, keep = _ensemble_handles(gps)
+    best = np.ascontiguousarray(best_so_far, dtype=np.float64).ravel()
+    if E == 0 or best.size != E:
+        raise BoundsException("one best value per ensemble member", best.size, E, E)
+    return arr, E, d, keep, best
+
+
+def ei_analytic_ensemble(gps, points, best_so_far, points_being_sampled=None, want_grad=True):
+    """moe_ei_analytic_mcmc: the analytic one-point expected improvement averaged over the ensemble at points [C][dim], in one device
+    call (one upload, one stream, one wait), member e against best_so_far[e].  points_being_sampled [p][dim] (None or empty: none):
+    every member's posterior covariance is conditioned on the pending points, its mean left alone, and the believed values join the
+    member's best value.  gps: a DeviceGPMCMC, a list of DeviceGP or one DeviceGP.  Returns ei [C], with want_grad (ei, grad
+    [C][dim]).  SingularMatrixException(e, j): member e, pending point j; a candidate never raises."""
+    arr, E, d, keep, best = _ei_analytic_members(gps, best_so_far)
+    pts, pp = _d(points)
+    C_ = pts.reshape(-1, d).shape[0]
+    ei = np.zeros(max(C_, 1))
+    grad = np.zeros((max(C_, 1), d)) if want_grad else None
+    p = _num_pending(points_being_sampled, d)
+    pend, pendp = _d(points_being_sampled) if p else (None, None)
+    err = _lib.MoeError()
+    _check(_lib.load().moe_ei_analytic_mcmc(arr, E, best.ctypes.data_as(dp), pendp, p, pp, C_, 1 if want_grad else 0,
+                                            ei.ctypes.data_as(dp), grad.ctypes.data_as(dp) if want_grad else None, C.byref(err)), err)
+    return (ei, grad) if want_grad else ei
+
+
+def ei_analytic_multistart(gps, gd_params, bounds, best_so_far, starts, gradient_ascent=True, want_path=False,
+                           points_being_sampled=None):
+    """moe_ei_analytic_mcmc_multistart: one suggestion by the ensemble-averaged analytic expected improvement -- the value at every
+    start [S][dim], the 20 best kept, restarted gradient ascent on all of them on the device, the value at every end point, the best
+    one returned.  The dict of kg_discrete_multistart: point [dim], value, found, start_values [S], and with gradient_ascent
+    kept_index [K], end_points [K][dim], end_values [K], steps_taken [K] (None without), with want_path path [K][restarts steps +
+    1][dim]."""
+    arr, E, d, keep, best = _ei_analytic_members(gps, best_so_far)
+    g = DeviceGP._gd(gd_params)
+    bounds, bp = _d(bounds)
+    starts, sp = _d(starts)
+    S = starts.reshape(-1, d).shape[0]
+    K = max(min(S, 20), 1)
+    rows = max(g.max_num_restarts, 0) * max(g.max_num_steps, 0) + 1
+    point = np.zeros(d)
+    start_values = np.zeros(max(S, 1))
+    kept = np.zeros(K, dtype=np.int32)
+    ends, end_values = np.zeros((K, d)), np.zeros(K)
+    steps = np.zeros(K, dtype=np.int32)
+    path = np.zeros((K, rows, d)) if (want_path and gradient_ascent) else None
+    value, found = C.c_double(0.0), C.c_int(0)
+    p = _num_pending(points_being_sampled, d)
+    pend, pendp = _d(points_being_sampled) if p else (None, None)
+    err = _lib.MoeError()
+    _check(_lib.load().moe_ei_analytic_mcmc_multistart(
+        arr, E, C.byref(g), bp, best.ctypes.data_as(dp), pendp, p, sp, S, 1 if gradient_ascent else 0, point.ctypes.data_as(dp),
+        C.byref(value), C.byref(found), start_values.ctypes.data_as(dp), kept.ctypes.data_as(ip), ends.ctypes.data_as(dp),
+        end_values.ctypes.data_as(dp), path.ctypes.data_as(dp) if path is not None else None, steps.ctypes.data_as(ip), C.byref(err)),
+        err)
+    out = {"point": point, "value": value.value, "found": bool(found.value), "start_values": start_values,
+           "kept_index": kept if gradient_ascent else None, "end_points": ends if gradient_ascent else None,
+           "end_values": end_values if gradient_ascent else None, "steps_taken": steps if gradient_ascent else None}
+    if want_path:
+        out["path"] = path
+    return out
+
+
+def ei_analytic_suggest(gps, gd_params, bounds, best_so_far, starts, num_to_sample, gradient_ascent=True, points_being_sampled=None):
+    """moe_ei_analytic_mcmc_suggest: num_to_sample points greedily by the ensemble-averaged analytic expected improvement -- round t
+    is ei_analytic_multistart from the same starts [S][dim] with the pending points points_being_sampled [p][dim] (may be None)
+    followed by the points of the rounds before, bit for bit, in one device call.  p + num_to_sample - 1 <= 64.  Returns a dict:
+    points [q][dim], values [q], found [q]."""
+    arr, E, d, keep, best = _ei_analytic_members(gps, best_so_far)
+    g = DeviceGP._gd(gd_params)
+    bounds, bp = _d(bounds)
+    starts, sp = _d(starts)
+    S = starts.reshape(-1, d).shape[0]
+    q = int(num_to_sample)
+    p = _num_pending(points_being_sampled, d)
+    pend, pendp = _d(points_being_sampled) if p else (None, None)
+    points, values = np.zeros((max(q, 1), d)), np.zeros(max(q, 1))
+    found = np.zeros(max(q, 1), dtype=np.int32)
+    err = _lib.MoeError()
+    _check(_lib.load().moe_ei_analytic_mcmc_suggest(
+        arr, E, C.byref(g), bp, best.ctypes.data_as(dp), pendp, p, sp, S, 1 if gradient_ascent else 0, q, points.ctypes.data_as(dp),
+        values.ctypes.data_as(dp), found.ctypes.data_as(ip), C.byref(err)), err)
+    return {"points": points, "values": values, "found": found.astype(bool)}
+
+
 def recommend(gps, candidates, gd_params, domain_bounds, num_fidelity=0, num_starts=1, want_values=False, want_path=False):
     """moe_posterior_mean_mcmc_recommend: screen the candidates [C][dim - num_fidelity] on the ensemble-averaged posterior mean,
     descend from the num_starts best (the reference's Python gradient descent, on the device), keep the screened candidate unless

@@ -937,6 +937,67 @@ int moe_kg_discrete_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, int n
   });
 }
 
+int moe_ei1_pass_size(int num_rows) { return moe::ei1_pass_size(num_rows); }
+
+int moe_ei_analytic_mcmc(const moe_gp_t* const* gps, int num_mcmc, const double* best_so_far, const double* points_being_sampled,
+                         int num_being_sampled, const double* points, int num_points, int want_grad, double* ei, double* grad,
+                         moe_error_t* err) {
+  return guarded(err, [&] {
+    if (num_mcmc < 1 || num_mcmc > 1024) throw moe::Error(MOE_ERR_BOUNDS, "num_mcmc must be between 1 and 1024", num_mcmc, 1, 1024);
+    require(gps && best_so_far && points && ei && (want_grad == 0 || grad), "NULL argument");
+    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_points);  // (what needs no handle)
+    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, 1);
+    const auto locks = lock_ensemble(gps, num_mcmc);
+    const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
+    moe::ei_analytic_mcmc_on_device(v, best_so_far, points, num_points, want_grad != 0, ei, grad, points_being_sampled,
+                                    num_being_sampled);
+  });
+}
+
+int moe_ei_analytic_mcmc_multistart(const moe_gp_t* const* gps, int num_mcmc, const moe_gd_params_t* outer, const double* domain_bounds,
+                                    const double* best_so_far, const double* points_being_sampled, int num_being_sampled,
+                                    const double* starts, int num_starts, int do_gradient_ascent, double* best_point,
+                                    double* best_value, int* found, double* start_values, int* kept_index, double* end_points,
+                                    double* end_values, double* path, int* steps_taken, moe_error_t* err) {
+  return guarded(err, [&] {
+    if (num_mcmc < 1 || num_mcmc > 1024) throw moe::Error(MOE_ERR_BOUNDS, "num_mcmc must be between 1 and 1024", num_mcmc, 1, 1024);
+    require(gps && outer && domain_bounds && best_so_far && starts && best_point && best_value && found, "NULL argument");
+    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_starts);
+    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, 1);
+    if (do_gradient_ascent != 0 && outer->max_num_steps < 1)
+      throw moe::Error(MOE_ERR_BOUNDS, "max_num_steps must be positive", outer->max_num_steps, 1, 1e9);
+    if (outer->domain_type != MOE_DOMAIN_TENSOR_PRODUCT)
+      throw moe::Error(MOE_ERR_INVALID_VALUE, "the analytic expected improvement's ascent supports tensor-product domains only",
+                       outer->domain_type, 0, 0);
+    const auto locks = lock_ensemble(gps, num_mcmc);
+    const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
+    moe::ei_analytic_mcmc_multistart(v, *outer, domain_bounds, best_so_far, starts, num_starts, do_gradient_ascent, best_point,
+                                     best_value, found, start_values, kept_index, end_points, end_values, path, steps_taken,
+                                     points_being_sampled, num_being_sampled);
+  });
+}
+
+int moe_ei_analytic_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, const moe_gd_params_t* outer, const double* domain_bounds,
+                                 const double* best_so_far, const double* points_being_sampled, int num_being_sampled,
+                                 const double* starts, int num_starts, int do_gradient_ascent, int num_to_sample, double* best_points,
+                                 double* best_values, int* found, moe_error_t* err) {
+  return guarded(err, [&] {
+    if (num_mcmc < 1 || num_mcmc > 1024) throw moe::Error(MOE_ERR_BOUNDS, "num_mcmc must be between 1 and 1024", num_mcmc, 1, 1024);
+    require(gps && outer && domain_bounds && best_so_far && starts && best_points && best_values && found, "NULL argument");
+    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_starts);
+    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, num_to_sample);
+    if (do_gradient_ascent != 0 && outer->max_num_steps < 1)
+      throw moe::Error(MOE_ERR_BOUNDS, "max_num_steps must be positive", outer->max_num_steps, 1, 1e9);
+    if (outer->domain_type != MOE_DOMAIN_TENSOR_PRODUCT)
+      throw moe::Error(MOE_ERR_INVALID_VALUE, "the analytic expected improvement's ascent supports tensor-product domains only",
+                       outer->domain_type, 0, 0);
+    const auto locks = lock_ensemble(gps, num_mcmc);
+    const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
+    moe::ei_analytic_mcmc_suggest(v, *outer, domain_bounds, best_so_far, starts, num_starts, do_gradient_ascent, points_being_sampled,
+                                  num_being_sampled, num_to_sample, best_points, best_values, found);
+  });
+}
+
 int moe_kg_mcmc_finalize(double* kg, double* grad_kg, const double* points_to_sample_all, int num_evals, int num_to_sample,
                          int dim, int num_fidelity, int total_num_mcmc) {
   if (!kg || !points_to_sample_all || num_evals <= 0 || num_to_sample <= 0 || dim <= 0 || num_fidelity < 0 ||

@@ -1,0 +1,409 @@
+// cornell_moe_amd/csrc/ei1.hip -- the analytic one-point expected improvement (OnePotentialSampleExpectedImprovementEvaluator,
+// gpp_math.cpp:2195-2259) averaged over a hyper-parameter ensemble, with pending points, its multistart ascent and greedy q-point
+// batches, on the device (moe_ei_analytic_mcmc, moe_ei_analytic_mcmc_multistart, moe_ei_analytic_mcmc_suggest): the EI twin of
+// kg1_opt.hip, sharing its ascent (kg1_ascent.hpp) and the pending-row extension (kg1_pending.hip).
+//
+// Member e: posterior mean mu_e, posterior covariance of the latent function conditioned on the pending points P with the member's
+// noise on P's diagonal (the Kriging-believer fantasy: the mean is left alone), believed best b'_e = min(b_e, min_j mu_e(P_j)).  With
+// v'_x = [L^-1 k(X, x) ; r_x] the column of x under the conditioned factor (kg1_pending.hip):
+//   var = k(x, x) - v'_x . v'_x,  t = b' - mu(x),  sigma = sqrt(max(DBL_MIN, var)),  c = t / sigma
+//   EI  = max(0, t Phi(c) + sigma phi(c))
+//   grad EI = -Phi(c_g) grad mu + phi(c_g) grad var / (2 sigma_g),  sigma_g = sqrt(max(150 eps^2, var)),  c_g = t / sigma_g
+// (the reference's two variance floors; the d c / d x terms of its d_a + d_b cancel).  With w = L'^-T v'_x, grad var = -2 sum_r w_r
+// grad_x k(row_r, x) over the rows X u P, so
+//   grad EI = sum_r coef_r grad_x k(row_r, x),  coef_r = -Phi(c_g) [K^-1 (y - mean) ; 0]_r - (phi(c_g) / sigma_g) w_r
+// -- ONE column per candidate through L'^-T and one pass over the rows: 2 N^2 + O(N (p + d)) per candidate, not N^2 dim.
+//
+// Once per call and member: the extension (kg1_pending_begin / kg1_pending_append), mu(P) (launch_mean), b' (ei1_best_kernel).
+// Per pass of ei1_pass_size(N) candidates already in device memory, nothing waits and no host memory is touched (recordable):
+//   K(X, x)                        launch_cov_build
+//   V_x = L^-1 K(X, x)             tri_cols ('N')
+//   mu(x)                          launch_mean
+//   r_x under V_x                  kg1_pending_rows            (p > 0)
+//   var, EI, Phi(c_g), the column (phi(c_g) / sigma_g) v'_x    ei1_cand_kernel
+//   L'^-T of that column           kg1_pending_back (p > 0), tri_cols ('T')
+//   the gradient                   ei1_grad_kernel<DP>
+//
+// Bits.  The triangular products are tri_cols (the kernel family fixed by N alone), var is ONE fused multiply-add chain over the
+// member's rows in row order and then the pending rows in order, the gradient's sums have a fixed shape: a candidate's bits do not
+// depend on who shares its pass, its call or its ascent step.  The ensemble mean, the step and the rounds are kg1_ascent.hpp's.
+// A candidate never raises: the two floors are the reference's behaviour.  Only a pending point whose Schur pivot fails raises.
+#include <cfloat>
+
+#include "device_cov.hpp"
+#include "kg1_ascent.hpp"
+
+namespace moe {
+
+namespace {
+
+constexpr double kMinVarEI = DBL_MIN;                                  // gpp_math.hpp:1316
+constexpr double kMinVarGradEI = 150.0 * DBL_EPSILON * DBL_EPSILON;  // gpp_math.hpp:1323
+
+__device__ __forceinline__ double ei1_pdf(double x) { return 0.3989422804014326779399460599343818684759 * exp(-0.5 * x * x); }
+// Phi through erfc on the side of x's sign: no cancellation in either tail
+__device__ __forceinline__ double ei1_cdf(double x) {
+  const double r = 0.7071067811865475244008443621048490392848;
+  return (x <= 0.0) ? 0.5 * erfc(-x * r) : 1.0 - 0.5 * erfc(x * r);
+}
+
+// b' = min(b, mu(P_0), ..., mu(P_count-1)); first == 0: b is the believed best as it stands (a greedy batch's next pick joins)
+__global__ void ei1_best_kernel(double b, int first, const double* __restrict__ mu, int count, double* __restrict__ out) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  double v = first != 0 ? b : *out;
+  for (int j = 0; j < count; ++j) v = fmin(v, mu[j]);
+  *out = v;
+}
+
+// One wavefront per candidate.  var = k(x, x) - sum_r v_r^2 as ONE fused multiply-add chain over the R = N + p rows in order: the
+// lanes load 64 rows at a time and every lane runs the whole chain on the broadcast entries (rows past R add exact zeros).  Then the
+// scalars, and with want_grad the column (phi(c_g) / sigma_g) v'_x for the transposed triangular product.
+struct ei1_cand_kernel_body {
+  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, int R, int ld, int ncols, int col0, const CovParams& cp, int want_grad, const double* __restrict__ best, const double* __restrict__ mu, const double* __restrict__ Vx, double* __restrict__ ei_out, double* __restrict__ cdf_out, double* __restrict__ T) {
+    const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (c >= ncols) return;
+    const double* v = Vx + (size_t)c * ld;
+    double ss = 0.0;
+    for (int r0 = 0; r0 < R; r0 += 64) {
+      const double x = (r0 + lane < R) ? v[r0 + lane] : 0.0;
+  #pragma unroll
+      for (int i = 0; i < 64; ++i) {
+        const double xi = __shfl(x, i, 64);
+        ss = fma(xi, xi, ss);
+      }
+    }
+    const double var = radial_scalars(cp.type, cp.alpha, 0.0).base - ss;
+    const double t = *best - mu[c];
+    if (lane == 0) {
+      const double sigma = sqrt(fmax(kMinVarEI, var));
+      const double cc = t / sigma;
+      ei_out[col0 + c] = fmax(0.0, t * ei1_cdf(cc) + sigma * ei1_pdf(cc));
+    }
+    if (want_grad == 0) return;
+    const double sg = sqrt(fmax(kMinVarGradEI, var));
+    const double cg = t / sg;
+    const double w = ei1_pdf(cg) / sg;
+    if (lane == 0) cdf_out[c] = ei1_cdf(cg);
+    double* tc = T + (size_t)c * ld;
+    for (int r = lane; r < R; r += 64) tc[r] = w * v[r];
+  }
+};
+__global__ __launch_bounds__(256) void ei1_cand_kernel(int R, int ld, int ncols, int col0, const CovParams cp, int want_grad, const double* __restrict__ best, const double* __restrict__ mu, const double* __restrict__ Vx, double* __restrict__ ei_out, double* __restrict__ cdf_out, double* __restrict__ T) {
+  ei1_cand_kernel_body::run(MOE_VBLOCK, MOE_VGRID, nullptr, R, ld, ncols, col0, cp, want_grad, best, mu, Vx, ei_out, cdf_out, T);
+}
+
+// One workgroup per candidate: grad EI = sum_r coef_r grad_x k(row_r, x) over the R rows of X u P, coef_r = -Phi(c_g) kinvy_r - u_r
+// with u = L'^-T [(phi(c_g) / sigma_g) v'_x]; the threads stride over the rows, then a fixed butterfly and the four wavefronts' sums.
+template <int DP>
+struct ei1_grad_kernel_body {
+  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, int R, int ld, int d, int col0, const CovParams& cp, const double* __restrict__ X, const double* __restrict__ kinvy, const double* __restrict__ Px, const double* __restrict__ U, const double* __restrict__ cdf, double* __restrict__ grad) {
+    __shared__ double s_part[4][DP];
+    const int c = blockIdx.x, tid = threadIdx.x;
+    const double* u = U + (size_t)c * ld;
+    const double ncdf = -cdf[c];
+    double x[DP], g[DP];
+  #pragma unroll
+    for (int i = 0; i < DP; ++i) {
+      x[i] = Px[(size_t)c * DP + i];
+      g[i] = 0.0;
+    }
+    for (int r = tid; r < R; r += 256) {
+      const double* xr = X + (size_t)r * DP;
+      double diff[DP], r2 = 0.0;
+  #pragma unroll
+      for (int i = 0; i < DP; ++i) {
+        diff[i] = xr[i] - x[i];
+        r2 = fma(diff[i] * diff[i], cp.inv_l2[i], r2);
+      }
+      const double f = radial_scalars(cp.type, cp.alpha, r2).first * fma(ncdf, kinvy[r], -u[r]);
+  #pragma unroll
+      for (int i = 0; i < DP; ++i) g[i] = fma(f, diff[i] * cp.inv_l2[i], g[i]);
+    }
+  #pragma unroll
+    for (int i = 0; i < DP; ++i) {
+  #pragma unroll
+      for (int off = 32; off > 0; off >>= 1) g[i] += __shfl_xor(g[i], off, 64);
+    }
+    if ((tid & 63) == 0) {
+  #pragma unroll
+      for (int i = 0; i < DP; ++i) s_part[tid >> 6][i] = g[i];
+    }
+    __syncthreads();
+    if (tid < d) grad[(size_t)(col0 + c) * d + tid] = (s_part[0][tid] + s_part[1][tid]) + (s_part[2][tid] + s_part[3][tid]);
+  }
+};
+template <int DP>
+__global__ __launch_bounds__(256) void ei1_grad_kernel(int R, int ld, int d, int col0, const CovParams cp, const double* __restrict__ X, const double* __restrict__ kinvy, const double* __restrict__ Px, const double* __restrict__ U, const double* __restrict__ cdf, double* __restrict__ grad) {
+  ei1_grad_kernel_body<DP>::run(MOE_VBLOCK, MOE_VGRID, nullptr, R, ld, d, col0, cp, X, kinvy, Px, U, cdf, grad);
+}
+
+DerivList no_derivs() {
+  DerivList d;
+  d.g = 0;
+  for (int i = 0; i < kMaxDerivs; ++i) d.idx[i] = 0;
+  return d;
+}
+
+// Where one GP's per-pass scratch and results live for a call of at most C candidates, inside the GP's own kg1D (results first:
+// [EI C | grad C d]), dE and dEK: Kg1Member with an empty set (A = 0; dAA holds mu(P), dScal Phi(c_g), dMuh mu(x)).
+Kg1Member ei1_member(GpDev& gp, int C, double best, bool with_grad, int* fail, int pcap, int* fail_pending) {
+  gp.use_device();
+  Kg1Member m;
+  m.gp = &gp;
+  m.C = C;
+  m.best = best;
+  m.with_grad = with_grad;
+  m.per_pass = ei1_pass_size(gp.N);
+  m.widest = std::min(m.per_pass, C);
+  const int N = gp.N;
+  m.pcap = pcap;
+  m.ld = N + pcap;
+  const size_t nC = (size_t)C, nW = (size_t)m.widest, nL = (size_t)m.ld, nV = nL * nW, nP = (size_t)pcap;
+  const size_t nOut = nC * (with_grad ? 1 + (size_t)gp.d : 1);
+  gp.kg1D.reserve(nOut + 1 + (nP + 1) + nV + (with_grad ? 2 * nV : 0) + 2 * nW + (pcap > 0 ? nL * ((size_t)gp.dp + 1 + nP) : 0));
+  gp.kg1LastC = 0;  // (kg1D no longer holds a knowledge-gradient call's envelope counts)
+  m.dOut = gp.kg1D.p;
+  m.dKg = m.dOut;
+  m.dGrad = m.dKg + nC;
+  m.dBp = m.dOut + nOut;
+  m.dAA = m.dBp + 1;
+  m.dVx = m.dAA + nP + 1;
+  m.dVh = m.dVx;
+  m.dT = m.dVx + nV;
+  m.dU = m.dT + (with_grad ? nV : 0);
+  m.dMuh = m.dU + (with_grad ? nV : 0);
+  m.dScal = m.dMuh + nW;
+  if (pcap > 0) {
+    m.dXe = m.dScal + nW;
+    m.dKe = m.dXe + nL * (size_t)gp.dp;
+    m.dVP = m.dKe + nL;
+  }
+  m.iFail = fail;
+  m.iFailP = fail_pending != nullptr ? fail_pending : fail;
+  gp.dE.reserve((size_t)N * std::max(nW, std::max(nP, (size_t)1)));
+  if (N >= 128) gp.dEK.reserve(tri_cols_work_doubles(N, (int)std::max(nW, std::max(nP, (size_t)1))));
+  return m;
+}
+
+void ei1_eval_pass(const Kg1Member& m, const double* Px, int nc, int c0, bool with_grad, hipStream_t s) {
+  GpDev& gp = *m.gp;
+  if (nc < 1 || nc > m.widest || c0 < 0 || c0 + nc > m.C || (with_grad && !m.with_grad))
+    throw Error(MOE_ERR_RUNTIME, "ei1_eval_pass: the pass does not fit the member's buffers");
+  const int N = gp.N, n = gp.n, d = gp.d, dp = gp.dp, R = N + m.p, ld = m.ld;
+  const double* Xr = m.p > 0 ? m.dXe : gp.dX.p;
+  const double* Kr = m.p > 0 ? m.dKe : gp.dKinvY.p;
+  const DerivList none = no_derivs();
+  const dim3 b256(256);
+  launch_cov_build(gp.cp, gp.dX.p, n, none, Px, nc, none, nullptr, gp.dE.p, N, 0, s);
+  tri_cols(gp, 'N', nc, gp.dE.p, N, m.dVx, ld, s);
+  launch_mean(gp.cp, gp.dX.p, n, none, gp.dKinvY.p, Px, nc, gp.mean, false, m.dMuh, s);
+  if (m.p > 0) kg1_pending_rows(m, Px, m.dVx, nc, 0, m.p, s);
+  launch_kernel_ens<ei1_cand_kernel_body, 256>(ei1_cand_kernel, dim3((unsigned)((nc + 3) / 4)), b256, 0, s, R, ld, nc, c0, gp.cp,
+                                               with_grad ? 1 : 0, (const double*)m.dBp, (const double*)m.dMuh, (const double*)m.dVx,
+                                               m.dKg, m.dScal, m.dT);
+  MOE_HIP_CHECK(hipGetLastError());
+  if (!with_grad) return;
+  if (m.p > 0) kg1_pending_back(m, nc, s);  // (L'^-T: the pending block first, then the member's own on the corrected rows)
+  tri_cols(gp, 'T', nc, m.dT, ld, m.dU, ld, s);
+  dispatch_dp(dp, [&](auto DP) {
+    launch_kernel_ens<ei1_grad_kernel_body<DP>, 256>(ei1_grad_kernel<DP>, dim3((unsigned)nc), b256, 0, s, R, ld, d, c0, gp.cp, Xr, Kr, Px,
+                                                     (const double*)m.dU, (const double*)m.dScal, m.dGrad);
+  });
+  MOE_HIP_CHECK(hipGetLastError());
+}
+
+// (Ph: kg1_ascent.hpp's second view of the points, the same as Px where there are no fidelity coordinates)
+void ei1_eval_points(const Kg1Member& m, const double* Px, const double*, int C, bool with_grad, hipStream_t s) {
+  const int dp = m.gp->dp;
+  for (int c0 = 0; c0 < C; c0 += m.per_pass) ei1_eval_pass(m, Px + (size_t)c0 * dp, std::min(m.per_pass, C - c0), c0, with_grad, s);
+}
+
+void check_members(const std::vector<GpDev*>& gps) {
+  const GpDev* g0 = gps[0];
+  for (size_t e = 0; e < gps.size(); ++e) {
+    const GpDev* g = gps[e];
+    if (g->d != g0->d) throw Error(MOE_ERR_INVALID_VALUE, "MCMC ensemble members must share dim", g->d, g0->d, (double)e);
+    if (g->device != g0->device)
+      throw Error(MOE_ERR_INVALID_VALUE, "MCMC ensemble members must live on one device", g->device, g0->device, (double)e);
+  }
+  for (size_t e = 0; e < gps.size(); ++e) {
+    if (gps[e]->g > 0)
+      throw Error(MOE_ERR_BOUNDS,
+                  "the ensemble analytic expected improvement needs GPs without derivative observations: a pending experiment "
+                  "would observe derivatives too",
+                  gps[e]->g, 0, 0);
+    for (size_t f = 0; f < e; ++f)
+      if (gps[f] == gps[e])
+        throw Error(MOE_ERR_INVALID_VALUE, "an MCMC ensemble member is listed twice (every member keeps its own workspaces)", (double)e,
+                    (double)f, 0);
+  }
+}
+
+// mu(P_j0 .. j0 + count - 1) and their part in b' for every member
+void join_believed_best(Kg1Ensemble& T, int j0, int count, bool first) {
+  const DerivList none = no_derivs();
+  for (Kg1Member& m : T.mem) {
+    GpDev& gp = *m.gp;
+    if (count > 0)
+      launch_mean(gp.cp, gp.dX.p, gp.n, none, gp.dKinvY.p, T.dPending + (size_t)j0 * T.dp, count, gp.mean, false, m.dAA, T.z);
+    MOE_LAUNCH_NOW(ei1_best_kernel, dim3(1), dim3(64), 0, T.z, m.best, first ? 1 : 0, (const double*)m.dAA, count, m.dBp);
+  }
+  MOE_HIP_CHECK(hipGetLastError());
+}
+
+// The members' layouts and the one upload: [EI pointers E | grad pointers E | bounds 2 d | points C dp | pending points pcap dp];
+// then every member's extension and believed best.  extra_ints: integers of the caller behind the failure words in the first
+// member's kg1oI (kg1_opt.hip: stage()).
+void stage(Kg1Ensemble& T, const std::vector<GpDev*>& gps, const double* best_so_far, const double* bounds, const double* pts, int C,
+           bool with_grad, size_t extra_ints, const double* pending, int p, int pcap) {
+  GpDev& g0 = *gps[0];
+  T.gps = gps;
+  T.E = (int)gps.size();
+  T.d = g0.d;
+  T.dp = g0.dp;
+  T.nf = 0;
+  T.fid = false;
+  T.eval_points = ei1_eval_points;
+  g0.use_device();
+  T.z = g0.stream;
+  T.ens = ensemble_launches() && T.E > 1;
+  const int E = T.E, d = T.d, dp = T.dp;
+  T.p = 0;
+  T.pcap = pcap;
+  T.W = pcap > 0 ? 2 * E : E;
+  g0.kg1oI.reserve((size_t)T.W + extra_ints);
+  T.iFail = g0.kg1oI.p;
+  const size_t nC = (size_t)C, oBounds = 2 * (size_t)E, oPts = oBounds + 2 * (size_t)d, oPend = oPts + nC * dp;
+  const size_t nIn = oPend + (size_t)pcap * dp;
+  g0.hStateIn.reserve(nIn);
+  g0.dStateIn.reserve(nIn);
+  T.mem.clear();
+  for (int e = 0; e < E; ++e)
+    T.mem.push_back(ei1_member(*gps[e], C, best_so_far[e], with_grad, T.iFail + e, pcap, pcap > 0 ? T.iFail + E + e : nullptr));
+  double* h = g0.hStateIn.p;
+  static_assert(sizeof(const double*) == sizeof(double), "the pointer tables travel inside a buffer of doubles");
+  for (int e = 0; e < E; ++e) {
+    const double* pk = T.mem[e].dKg;
+    const double* pg = T.mem[e].dGrad;
+    std::memcpy(h + e, &pk, sizeof(pk));
+    std::memcpy(h + E + e, &pg, sizeof(pg));
+  }
+  for (int k = 0; k < 2 * d; ++k) h[oBounds + k] = bounds != nullptr ? bounds[k] : 0.0;
+  for (size_t i = 0; i < nC; ++i)
+    for (int k = 0; k < dp; ++k) h[oPts + i * dp + k] = (k < d) ? pts[i * d + k] : 0.0;
+  for (size_t i = 0; i < (size_t)pcap; ++i)
+    for (int k = 0; k < dp; ++k) h[oPend + i * dp + k] = (i < (size_t)p && k < d) ? pending[i * d + k] : 0.0;
+  g0.dStateIn.upload(h, nIn, T.z, true);
+  const double* dIn = g0.dStateIn.p;
+  T.dPending = g0.dStateIn.p + oPend;
+  T.dKgTab = reinterpret_cast<const double* const*>(dIn);
+  T.dGradTab = reinterpret_cast<const double* const*>(dIn + E);
+  T.dBounds = dIn + oBounds;
+  T.dPts = dIn + oPts;
+  T.dPtsH = T.dPts;
+  kg1_clear_fail(T.iFail, E, T.z);
+  if (pcap > 0) kg1_clear_fail(T.iFail + E, E, T.z);
+  for (Kg1Member& m : T.mem) {
+    if (pcap > 0) {
+      m.dPP = T.dPending;
+      kg1_pending_begin(m, T.z);
+      if (p > 0) kg1_pending_append(m, p, false, T.z);
+    }
+  }
+  join_believed_best(T, 0, p, true);
+  T.p = p;
+}
+
+// the buffers of ascend() (kg1_ascent.hpp) and the one upload; pcap: room for pending points, the first p of them the caller's
+void stage_ascent(Kg1Ensemble& T, const std::vector<GpDev*>& gps, const moe_gd_params_t& outer, const double* domain_bounds,
+                  const double* best_so_far, const double* starts, int S, bool ascent, bool want_path, const double* pending, int p,
+                  int pcap) {
+  check_members(gps);
+  GpDev& g0 = *gps[0];
+  const int E = (int)gps.size(), W = pcap > 0 ? 2 * E : E, d = g0.d, dp = g0.dp;
+  const int R = std::max(outer.max_num_restarts, 0), Tn = outer.max_num_steps;
+  const int Kmax = ascent ? std::min(S, kMaxKept) : 0;
+  const size_t nBack = (size_t)W + Kmax + S + (size_t)Kmax * dp + (want_path ? (size_t)Kmax * (R * Tn + 1) * d : 0);
+  g0.use_device();
+  g0.kg1oD.reserve(nBack + 2 * (size_t)Kmax * dp);
+  g0.hStateOut.reserve(nBack);
+  // integers behind the failure words: [alive count | steps Kmax | order, running, alive Kmax each]
+  stage(T, gps, best_so_far, domain_bounds, starts, S, ascent && R > 0, 1 + 4 * (size_t)Kmax, pending, p, pcap);
+}
+
+}  // namespace
+
+// Candidates per pass, from N alone: a pass's columns of V stay within 2^24 doubles, a multiple of 64 between 64 and 4096.
+int ei1_pass_size(int N) {
+  const long cap_v = ((long)1 << 24) / std::max(N, 1);
+  return (int)std::max<long>(64, std::min<long>(4096, cap_v / 64 * 64));
+}
+
+void check_ei_analytic_mcmc_shapes(int num_mcmc, int num_points) {
+  if (num_mcmc < 1 || num_mcmc > 1024) throw Error(MOE_ERR_BOUNDS, "num_mcmc must be between 1 and 1024", num_mcmc, 1, 1024);
+  if (num_points < 1) throw Error(MOE_ERR_BOUNDS, "the number of candidates must be positive", num_points, 1, 1e9);
+}
+
+void ei_analytic_mcmc_on_device(const std::vector<GpDev*>& gps, const double* best_so_far, const double* pts, int C, bool want_grad,
+                                double* ei_out, double* grad_out, const double* pending, int num_pending) {
+  check_members(gps);
+  GpDev& g0 = *gps[0];
+  Kg1Ensemble T;
+  const int d = g0.d;
+  const int W = num_pending > 0 ? 2 * (int)gps.size() : (int)gps.size();  // (the failure words in front of the results: Kg1Ensemble::W)
+  // the call's doubles, all of them the copy back: [failure words | EI C | grad C d]
+  const size_t nOut = (size_t)W + (size_t)C * (want_grad ? 1 + d : 1);
+  g0.use_device();
+  g0.kg1oD.reserve(nOut);
+  g0.hStateOut.reserve(nOut);
+  stage(T, gps, best_so_far, nullptr, pts, C, want_grad, 0, pending, num_pending, num_pending);
+  Kg1Recording rec;
+  evaluate(T, rec, T.dPts, T.dPtsH, C, want_grad);
+  double* dOut = g0.kg1oD.p;
+  launch_mean_of_members(T, T.dKgTab, C, dOut + W);
+  if (want_grad) launch_mean_of_members(T, T.dGradTab, (long)C * d, dOut + W + C);
+  MOE_LAUNCH_NOW(kg1_words_kernel, dim3(1), dim3(256), 0, T.z, (const int*)T.iFail, W, dOut);
+  MOE_HIP_CHECK(hipGetLastError());
+  g0.kg1oD.download(g0.hStateOut.p, nOut, T.z);
+  MOE_HIP_CHECK(hipStreamSynchronize(T.z));
+  const double* o = g0.hStateOut.p;
+  throw_if_singular(T, o);
+  std::memcpy(ei_out, o + W, sizeof(double) * (size_t)C);
+  if (want_grad) std::memcpy(grad_out, o + W + C, sizeof(double) * (size_t)C * d);
+}
+
+void ei_analytic_mcmc_multistart(const std::vector<GpDev*>& gps, const moe_gd_params_t& outer, const double* domain_bounds,
+                                 const double* best_so_far, const double* starts, int num_starts, int do_gradient_ascent,
+                                 double* best_point, double* best_value, int* found, double* start_values, int* kept_index,
+                                 double* end_points, double* end_values, double* path, int* steps_taken, const double* pending,
+                                 int num_pending) {
+  Kg1Ensemble T;
+  const bool ascent = do_gradient_ascent != 0;
+  stage_ascent(T, gps, outer, domain_bounds, best_so_far, starts, num_starts, ascent, ascent && path != nullptr, pending, num_pending,
+               num_pending);
+  ascend(T, outer, starts, num_starts, do_gradient_ascent, best_point, best_value, found, start_values, kept_index, end_points,
+         end_values, path, steps_taken);
+}
+
+// q points greedily: round t is the ascent above with the caller's pending points and the t points already picked; a round appends
+// one column to every member's extension and one value mu_e(pick) to its believed best, both inside device memory.
+void ei_analytic_mcmc_suggest(const std::vector<GpDev*>& gps, const moe_gd_params_t& outer, const double* domain_bounds,
+                              const double* best_so_far, const double* starts, int num_starts, int do_gradient_ascent,
+                              const double* pending, int num_pending, int num_to_sample, double* best_points, double* best_values,
+                              int* found) {
+  Kg1Ensemble T;
+  stage_ascent(T, gps, outer, domain_bounds, best_so_far, starts, num_starts, do_gradient_ascent != 0, false, pending, num_pending,
+               num_pending + num_to_sample - 1);
+  const int d = T.d;
+  for (int t = 0; t < num_to_sample; ++t) {
+    const double* dBest = ascend(T, outer, starts, num_starts, do_gradient_ascent, best_points + (size_t)t * d, best_values + t,
+                                 found + t, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (t + 1 == num_to_sample) break;
+    copy_async(T.dPending + (size_t)T.p * T.dp, dBest, sizeof(double) * (size_t)T.dp, hipMemcpyDeviceToDevice, T.z);
+    for (Kg1Member& m : T.mem) kg1_pending_append(m, 1, false, T.z);
+    join_believed_best(T, T.p, 1, false);
+    T.p += 1;
+  }
+}
+
+}  // namespace moe

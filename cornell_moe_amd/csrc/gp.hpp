@@ -248,6 +248,7 @@ struct Kg1Member {
   double* dKe = nullptr;        // [K^-1 (y - mean) ; 0]
   double* dVP = nullptr;        // column j [ld]: L^-1 k(X, P_j), then row j of L_P with its diagonal
   int* iFailP = nullptr;        // the first pending point whose Schur pivot fails the pivot rule
+  double* dBp = nullptr;        // ei1.hip: the member's believed best b' = min(best, min_j mu(P_j)), in device memory
   size_t out_doubles() const { return 1 + 2 * (size_t)C + (with_grad ? (size_t)C * gp->d : 0); }
 };
 // the handle's checks of moe_gp_kg_discrete (num_fidelity < dim, no derivative observations), the buffers and their layout; nothing
@@ -296,6 +297,23 @@ void kg_discrete_mcmc_multistart(const std::vector<GpDev*>& gps, int num_fidelit
 void check_kg_discrete_pending(const double* pending, int num_pending, int num_to_sample);
 void kg_discrete_mcmc_suggest(const std::vector<GpDev*>& gps, int num_fidelity, const moe_gd_params_t& outer,
                               const double* domain_bounds, const double* discrete_all, const int* num_discrete,
+                              const double* best_so_far, const double* starts, int num_starts, int do_gradient_ascent,
+                              const double* pending, int num_pending, int num_to_sample, double* best_points, double* best_values,
+                              int* found);
+// ei1.hip: the analytic one-point expected improvement averaged over an ensemble (moe_ei_analytic_mcmc), its multistart ascent
+// (moe_ei_analytic_mcmc_multistart) and greedy batches (moe_ei_analytic_mcmc_suggest), with pending points [num_pending][dim] by the
+// Kriging-believer fantasy of kg1_pending.hip; the caller has made the checks that need no handle (check_ei_analytic_mcmc_shapes,
+// check_kg_discrete_pending).  Candidates go through in passes of ei1_pass_size(N).
+int ei1_pass_size(int N);
+void check_ei_analytic_mcmc_shapes(int num_mcmc, int num_points);
+void ei_analytic_mcmc_on_device(const std::vector<GpDev*>& gps, const double* best_so_far, const double* pts, int C, bool want_grad,
+                                double* ei_out, double* grad_out, const double* pending, int num_pending);
+void ei_analytic_mcmc_multistart(const std::vector<GpDev*>& gps, const moe_gd_params_t& outer, const double* domain_bounds,
+                                 const double* best_so_far, const double* starts, int num_starts, int do_gradient_ascent,
+                                 double* best_point, double* best_value, int* found, double* start_values, int* kept_index,
+                                 double* end_points, double* end_values, double* path, int* steps_taken, const double* pending,
+                                 int num_pending);
+void ei_analytic_mcmc_suggest(const std::vector<GpDev*>& gps, const moe_gd_params_t& outer, const double* domain_bounds,
                               const double* best_so_far, const double* starts, int num_starts, int do_gradient_ascent,
                               const double* pending, int num_pending, int num_to_sample, double* best_points, double* best_values,
                               int* found);

@@ -30,7 +30,8 @@ def member_posterior_mean_minima(models, candidates, bounds, gd_params, num_fide
 
 def kg_discrete_points(models, shared_points, candidates, bounds, gd_params, num_fidelity=0):
     """main.py's ``discrete_pts_list``: per member the array [shared_points ; that member's posterior-mean minimiser], shape
-    (len(shared_points) + 1, dim - num_fidelity)."""
+    (len(shared_points) + 1, dim - num_fidelity).  A deterministic source of ``shared_points``:
+    expected_improvement_analytic.multistart_analytic_expected_improvement_optimization(models, ..., num_to_sample=10)."""
     res = member_posterior_mean_minima(models, candidates, bounds, gd_params, num_fidelity=num_fidelity)
     best = res["best_points"]
     shared = np.asarray(shared_points, dtype=np.float64).reshape(-1, best.shape[1])

@@ -321,6 +321,80 @@ int moe_kg_discrete_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, int n
                                  const double* best_so_far, const double* points_being_sampled, int num_being_sampled,
                                  const double* starts, int num_starts, int do_gradient_ascent, int num_to_sample, double* best_points,
                                  double* best_values, int* found, moe_error_t* err);
+/* The analytic one-point expected improvement (OnePotentialSampleExpectedImprovementEvaluator, gpp_math.cpp:2195-2259) averaged over
+ * an ensemble of num_mcmc GPs, with pending points, evaluated on the device: ei[i] and grad[i][dim] (want_grad != 0) at points
+ * [num_points][dim].  Member e has posterior mean mu_e, noise sigma^2_e = noise_variance[0] and best value best_so_far[e]; its
+ * posterior covariance of the latent function (no noise added to the variance) is conditioned on points_being_sampled
+ * [num_being_sampled][dim] with sigma^2_e on their diagonal and its mean is left alone -- moe_kg_discrete_mcmc_pending's fantasy,
+ * word for word: var_e(x) = k(x, x) - v_x . v_x - r_x . r_x.  The believed values join the incumbent,
+ *   b'_e = min(best_so_far[e], min_j mu_e(P_j))        (b'_e = best_so_far[e] without pending points)
+ * -- without this a greedy batch re-picks its own point, where var -> 0 and EI -> max(0, best - mu).  With t = b'_e - mu_e(x):
+ *   EI_e = max(0, t Phi(c) + sigma phi(c)),  sigma = sqrt(max(DBL_MIN, var_e)),  c = t / sigma
+ *   grad EI_e = -Phi(c_g) grad mu_e + phi(c_g) grad var_e / (2 sigma_g),  sigma_g = sqrt(max(150 eps^2, var_e)),  c_g = t / sigma_g
+ * (the reference's two floors and its unclamped gradient; P and b' do not move with x), and
+ *   ei[i] = (EI_0 + ... + EI_{E-1}) / E,  grad likewise: the members added in member order and divided once.
+ * There is no fidelity handling (the reference's EI has none).  The gradient costs one transposed triangular product with ONE
+ * column per candidate and one pass over the rows: 2 N^2 + O(N (num_being_sampled + dim)), not N^2 dim.
+ * A candidate's bits do not depend on how many share the call (passes of moe_ei1_pass_size(N) candidates), nor on want_grad, nor on
+ * ensemble-wide launches (moe_set_ensemble_launches); the ensemble's result is, bit for bit, the members' own results added up on
+ * the host in member order.  With num_being_sampled == 0 (points_being_sampled may be NULL) no pending kernel is issued.  One copy
+ * down, one stream (the first member's), one wait, one copy back; no handle is modified.
+ * Errors, in this order, everything that needs no handle before a handle or the device is touched: num_mcmc outside 1 .. 1024 ->
+ * MOE_ERR_BOUNDS; a NULL array (gps, best_so_far, points, ei, grad with want_grad) -> MOE_ERR_RUNTIME; num_points < 1 ->
+ * MOE_ERR_BOUNDS; num_being_sampled outside 0 .. 64 -> MOE_ERR_BOUNDS, payload (num_being_sampled, 0, 64); points_being_sampled NULL
+ * with num_being_sampled > 0 -> MOE_ERR_RUNTIME; a NULL handle -> MOE_ERR_RUNTIME; a member of another dim, then of another device ->
+ * MOE_ERR_INVALID_VALUE, payload (its value, the first member's, the member); a member with derivative observations ->
+ * MOE_ERR_BOUNDS, payload (num_derivatives, 0, 0) (a pending experiment would observe derivatives too); a handle listed twice ->
+ * MOE_ERR_INVALID_VALUE.
+ * MOE_ERR_SINGULAR only for a pending point: payload (e, j), the first member e whose extension has a Schur pivot <= 1e-16 and the
+ * first such pending point j; reported after the wait.  A candidate never raises: the two variance floors are the reference's. */
+int moe_ei_analytic_mcmc(const moe_gp_t* const* gps, int num_mcmc, const double* best_so_far, const double* points_being_sampled,
+                         int num_being_sampled, const double* points, int num_points, int want_grad, double* ei, double* grad,
+                         moe_error_t* err);
+/* The number of candidates per pass of the calls above and below: a function of the member's number of rows alone. */
+int moe_ei1_pass_size(int num_rows);
+/* One suggestion by moe_ei_analytic_mcmc's objective, q = 1, the whole loop on the device: moe_kg_discrete_mcmc_multistart_pending's
+ * ascent (its kernels are shared), in the same words:
+ *   1. screening: the value at every start [num_starts][dim] (start_values, may be NULL); with do_gradient_ascent == 0 the best
+ *      start by a strict compare in list order is returned (best_point seeded with the first start) and the outputs of 2. - 3. are
+ *      left untouched.
+ *   2. the K = min(20, num_starts) best starts are kept in the reference's order and tie rule (lowest kept value first, equal
+ *      values by descending index; kept_index[K]); best_point is seeded with the first of them.
+ *   3. ascent of all kept starts at once, R = max_num_restarts rounds of T = max_num_steps steps: with alpha_i = pre_mult
+ *      (i + 1)^-gamma, step = alpha_i grad, limited per coordinate by TensorProductDomain::LimitUpdate (max_relative_change of the
+ *      distance to the nearer bound; halved, or half-way to the bound, where it would leave the domain), x += step; a start stops
+ *      for the round when |step| < tolerance / T and for good when a round moved it by no more than tolerance; the ascent ends
+ *      when no start is left.  A stopped start is still evaluated and its update masked.
+ *   4. the value at every end point (end_points[K][dim], end_values[K]); the first of the largest is returned (strict compare,
+ *      against -infinity: found = 0 only if every value is NaN).
+ * path (may be NULL): [K][R T + 1][dim], row 0 the start, row 1 + r T + i the point after step i of round r (a stopped start
+ * repeats its point).  steps_taken[K]: the steps a start took while running.  All of these may be NULL.
+ * The update is the host drivers' arithmetic operation for operation (no fused multiply-add), so the path is, bit for bit, the one
+ * a host loop over moe_ei_analytic_mcmc walks.  The extensions and the believed bests are built once.  One copy down; the host
+ * waits once after the screening (it picks the kept starts), once per restart round (the count of starts still alive) and once at
+ * the end.  Ensemble-wide launches as in moe_ei_analytic_mcmc, a step's recording made once and issued every step.
+ * Errors, in this order: those of moe_ei_analytic_mcmc that need no handle (outer, domain_bounds, starts, best_point, best_value and
+ * found among the arrays that must not be NULL; num_starts for num_points); max_num_steps < 1 with do_gradient_ascent != 0 ->
+ * MOE_ERR_BOUNDS; domain_type other than MOE_DOMAIN_TENSOR_PRODUCT -> MOE_ERR_INVALID_VALUE; then those that need the handles.
+ * MOE_ERR_SINGULAR as above, at the next wait. */
+int moe_ei_analytic_mcmc_multistart(const moe_gp_t* const* gps, int num_mcmc, const moe_gd_params_t* outer, const double* domain_bounds,
+                                    const double* best_so_far, const double* points_being_sampled, int num_being_sampled,
+                                    const double* starts, int num_starts, int do_gradient_ascent, double* best_point,
+                                    double* best_value, int* found, double* start_values, int* kept_index, double* end_points,
+                                    double* end_values, double* path, int* steps_taken, moe_error_t* err);
+/* num_to_sample points greedily: round t = 0 .. num_to_sample - 1 is moe_ei_analytic_mcmc_multistart from the same starts with
+ * pending points = points_being_sampled followed by the picks x_0 .. x_{t-1} of the rounds before, and writes best_points[t][dim],
+ * best_values[t], found[t]: bit for bit what num_to_sample calls of that function return when each is fed its predecessors' points.
+ * Staged once; after round t ONE row joins each member's extension and one value mu_e(x_t) its believed best, the pick reaching both
+ * inside device memory.  The host waits as often as moe_kg_discrete_mcmc_suggest does, and no more.
+ * Errors, in this order: those of moe_ei_analytic_mcmc_multistart, with, directly after num_being_sampled: num_to_sample < 1 or
+ * num_being_sampled + num_to_sample - 1 > 64 -> MOE_ERR_BOUNDS, payload (num_to_sample, 1, 65 - num_being_sampled); and best_points,
+ * best_values, found among the arrays that must not be NULL.  MOE_ERR_SINGULAR as above: the pending index counts the caller's
+ * points first, then the rounds' picks. */
+int moe_ei_analytic_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, const moe_gd_params_t* outer, const double* domain_bounds,
+                                 const double* best_so_far, const double* points_being_sampled, int num_being_sampled,
+                                 const double* starts, int num_starts, int do_gradient_ascent, int num_to_sample, double* best_points,
+                                 double* best_values, int* found, moe_error_t* err);
 /* compute_grad_variance_of_points -> ComputeGradVarianceOfPoints (gpp_math.cpp:1359-1373); out[num_derivs][m][m][dim] */
 int moe_gp_grad_variance(const moe_gp_t* gp, const double* pts, int num_pts, int num_derivs, double* out, moe_error_t* err);
 /* compute_grad_cholesky_variance_of_points -> ComputeGradCholeskyVarianceOfPoints (gpp_math.cpp:1454-1474) */
