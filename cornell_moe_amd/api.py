@@ -976,8 +976,10 @@ def ei_analytic_ensemble(gps, points, best_so_far, points_being_sampled=None, wa
     """moe_ei_analytic_mcmc: the analytic one-point expected improvement averaged over the ensemble at points [C][dim], in one device
     call (one upload, one stream, one wait), member e against best_so_far[e].  points_being_sampled [p][dim] (None or empty: none):
     every member's posterior covariance is conditioned on the pending points, its mean left alone, and the believed values join the
-    member's best value.  gps: a DeviceGPMCMC, a list of DeviceGP or one DeviceGP.  Returns ei [C], with want_grad (ei, grad
-    [C][dim]).  SingularMatrixException(e, j): member e, pending point j; a candidate never raises."""
+    member's best value.  gps: a DeviceGPMCMC, a list of DeviceGP or one DeviceGP.  The members may observe derivatives (one list
+    for all of them, InvalidValueException otherwise): a pending point is then believed to return its value and those g derivatives,
+    1 + g rows with noise_variance[a] on row a, and p (1 + g) <= 64 (BoundsException(p, 0, 64 // (1 + g))).  Returns ei [C], with
+    want_grad (ei, grad [C][dim]).  SingularMatrixException(e, j): member e, pending point j; a candidate never raises."""
     arr, E, d, keep, best = _ei_analytic_members(gps, best_so_far)
     pts, pp = _d(points)
     C_ = pts.reshape(-1, d).shape[0]
@@ -997,7 +999,7 @@ def ei_analytic_multistart(gps, gd_params, bounds, best_so_far, starts, gradient
     start [S][dim], the 20 best kept, restarted gradient ascent on all of them on the device, the value at every end point, the best
     one returned.  The dict of kg_discrete_multistart: point [dim], value, found, start_values [S], and with gradient_ascent
     kept_index [K], end_points [K][dim], end_values [K], steps_taken [K] (None without), with want_path path [K][restarts steps +
-    1][dim]."""
+    1][dim].  Members with derivative observations as in ei_analytic_ensemble."""
     arr, E, d, keep, best = _ei_analytic_members(gps, best_so_far)
     g = DeviceGP._gd(gd_params)
     bounds, bp = _d(bounds)
@@ -1031,8 +1033,8 @@ def ei_analytic_multistart(gps, gd_params, bounds, best_so_far, starts, gradient
 def ei_analytic_suggest(gps, gd_params, bounds, best_so_far, starts, num_to_sample, gradient_ascent=True, points_being_sampled=None):
     """moe_ei_analytic_mcmc_suggest: num_to_sample points greedily by the ensemble-averaged analytic expected improvement -- round t
     is ei_analytic_multistart from the same starts [S][dim] with the pending points points_being_sampled [p][dim] (may be None)
-    followed by the points of the rounds before, bit for bit, in one device call.  p + num_to_sample - 1 <= 64.  Returns a dict:
-    points [q][dim], values [q], found [q]."""
+    followed by the points of the rounds before, bit for bit, in one device call.  p + num_to_sample - 1 <= 64; with g observed
+    derivatives per point (p + num_to_sample - 1) (1 + g) <= 64.  Returns a dict: points [q][dim], values [q], found [q]."""
     arr, E, d, keep, best = _ei_analytic_members(gps, best_so_far)
     g = DeviceGP._gd(gd_params)
     bounds, bp = _d(bounds)

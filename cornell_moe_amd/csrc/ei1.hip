@@ -28,6 +28,14 @@
 // member's rows in row order and then the pending rows in order, the gradient's sums have a fixed shape: a candidate's bits do not
 // depend on who shares its pass, its call or its ascent step.  The ensemble mean, the step and the rounds are kg1_ascent.hpp's.
 // A candidate never raises: the two floors are the reference's behaviour.  Only a pending point whose Schur pivot fails raises.
+//
+// Derivative observations (g = num_derivatives > 0, one list for every member).  The member's rows are its N = n (1 + g) observations,
+// point-major; a pending point is believed to return its value and its g partial derivatives at the member's posterior means, so it
+// adds 1 + g rows (noise[a] on row a) and the mean is still left alone; b' takes the believed function values only.  The candidate is
+// a function value, so K(X, x), mu(x) and the extension's rows take the member's derivative list on the rows' side alone, var, EI and
+// the coefficients are the same expressions over R = N + p (1 + g) rows, and grad_x k(row, x) of a derivative row is the covariance's
+// second-derivative block: ei1_grad_g_kernel strides over the n + p POINTS and applies a point's 1 + g coefficients to one set of
+// radial scalars.  A member with g = 0 issues exactly the launches above.  At most 64 extension rows: p (1 + g) <= 64.
 #include <cfloat>
 
 #include "device_cov.hpp"
@@ -137,6 +145,69 @@ __global__ __launch_bounds__(256) void ei1_grad_kernel(int R, int ld, int d, int
   ei1_grad_kernel_body<DP>::run(MOE_VBLOCK, MOE_VGRID, nullptr, R, ld, d, col0, cp, X, kinvy, Px, U, cdf, grad);
 }
 
+// The same for members with g = dl.g observed derivatives per point: the threads stride over the P = n + p POINTS of X u P, a
+// point's radial scalars are taken once and the 1 + g coefficients of its block of rows applied -- with e = (x_row - x) / l^2,
+//   grad_x cov(row (q, 0), x) = first e,   grad_x cov(row (q, b), x) = -second e_{i_b} e + first / l_{i_b}^2 unit(i_b)
+// (grad_cov_entry_g with a = 0 on x's side).  The derivative index i_b is a runtime value: e_{i_b} and the unit vector's entry go
+// through unrolled selects over DP, never through an indexed register array.  The reduction is the one above.
+template <int DP>
+struct ei1_grad_g_kernel_body {
+  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, int P, int ld, int d, int col0, const CovParams& cp, const DerivList& dl, const double* __restrict__ X, const double* __restrict__ kinvy, const double* __restrict__ Px, const double* __restrict__ U, const double* __restrict__ cdf, double* __restrict__ grad) {
+    __shared__ double s_part[4][DP];
+    const int c = blockIdx.x, tid = threadIdx.x, g1 = 1 + dl.g;
+    const double* u = U + (size_t)c * ld;
+    const double ncdf = -cdf[c];
+    double x[DP], g[DP];
+  #pragma unroll
+    for (int i = 0; i < DP; ++i) {
+      x[i] = Px[(size_t)c * DP + i];
+      g[i] = 0.0;
+    }
+    for (int q = tid; q < P; q += 256) {
+      const double* xr = X + (size_t)q * DP;
+      double e[DP], r2 = 0.0;
+  #pragma unroll
+      for (int i = 0; i < DP; ++i) {
+        const double diff = xr[i] - x[i];
+        r2 = fma(diff * diff, cp.inv_l2[i], r2);
+        e[i] = diff * cp.inv_l2[i];
+      }
+      const Radial rd = radial_scalars(cp.type, cp.alpha, r2);
+      const size_t r = (size_t)q * g1;
+      double f = rd.first * fma(ncdf, kinvy[r], -u[r]);
+      for (int b = 1; b < g1; ++b) {
+        const int ib = dl.idx[b - 1];
+        const double cb = fma(ncdf, kinvy[r + b], -u[r + b]);
+        const double t = cb * rd.first * cp.inv_l2[ib];
+        double eb = 0.0;
+  #pragma unroll
+        for (int i = 0; i < DP; ++i) {
+          eb = (i == ib) ? e[i] : eb;
+          g[i] += (i == ib) ? t : 0.0;
+        }
+        f = fma(-cb * rd.second, eb, f);
+      }
+  #pragma unroll
+      for (int i = 0; i < DP; ++i) g[i] = fma(f, e[i], g[i]);
+    }
+  #pragma unroll
+    for (int i = 0; i < DP; ++i) {
+  #pragma unroll
+      for (int off = 32; off > 0; off >>= 1) g[i] += __shfl_xor(g[i], off, 64);
+    }
+    if ((tid & 63) == 0) {
+  #pragma unroll
+      for (int i = 0; i < DP; ++i) s_part[tid >> 6][i] = g[i];
+    }
+    __syncthreads();
+    if (tid < d) grad[(size_t)(col0 + c) * d + tid] = (s_part[0][tid] + s_part[1][tid]) + (s_part[2][tid] + s_part[3][tid]);
+  }
+};
+template <int DP>
+__global__ __launch_bounds__(256) void ei1_grad_g_kernel(int P, int ld, int d, int col0, const CovParams cp, const DerivList dl, const double* __restrict__ X, const double* __restrict__ kinvy, const double* __restrict__ Px, const double* __restrict__ U, const double* __restrict__ cdf, double* __restrict__ grad) {
+  ei1_grad_g_kernel_body<DP>::run(MOE_VBLOCK, MOE_VGRID, nullptr, P, ld, d, col0, cp, dl, X, kinvy, Px, U, cdf, grad);
+}
+
 DerivList no_derivs() {
   DerivList d;
   d.g = 0;
@@ -145,7 +216,8 @@ DerivList no_derivs() {
 }
 
 // Where one GP's per-pass scratch and results live for a call of at most C candidates, inside the GP's own kg1D (results first:
-// [EI C | grad C d]), dE and dEK: Kg1Member with an empty set (A = 0; dAA holds mu(P), dScal Phi(c_g), dMuh mu(x)).
+// [EI C | grad C d]), dE and dEK: Kg1Member with an empty set (A = 0; dAA holds mu(P), dScal Phi(c_g), dMuh mu(x)).  pcap: room
+// for that many extension ROWS, a multiple of 1 + g.
 Kg1Member ei1_member(GpDev& gp, int C, double best, bool with_grad, int* fail, int pcap, int* fail_pending) {
   gp.use_device();
   Kg1Member m;
@@ -157,6 +229,7 @@ Kg1Member ei1_member(GpDev& gp, int C, double best, bool with_grad, int* fail, i
   m.widest = std::min(m.per_pass, C);
   const int N = gp.N;
   m.pcap = pcap;
+  m.g1 = 1 + gp.g;
   m.ld = N + pcap;
   const size_t nC = (size_t)C, nW = (size_t)m.widest, nL = (size_t)m.ld, nV = nL * nW, nP = (size_t)pcap;
   const size_t nOut = nC * (with_grad ? 1 + (size_t)gp.d : 1);
@@ -192,11 +265,11 @@ void ei1_eval_pass(const Kg1Member& m, const double* Px, int nc, int c0, bool wi
   const int N = gp.N, n = gp.n, d = gp.d, dp = gp.dp, R = N + m.p, ld = m.ld;
   const double* Xr = m.p > 0 ? m.dXe : gp.dX.p;
   const double* Kr = m.p > 0 ? m.dKe : gp.dKinvY.p;
-  const DerivList none = no_derivs();
+  const DerivList none = no_derivs();  // (the candidate is a function value)
   const dim3 b256(256);
-  launch_cov_build(gp.cp, gp.dX.p, n, none, Px, nc, none, nullptr, gp.dE.p, N, 0, s);
+  launch_cov_build(gp.cp, gp.dX.p, n, gp.derivs, Px, nc, none, nullptr, gp.dE.p, N, 0, s);
   tri_cols(gp, 'N', nc, gp.dE.p, N, m.dVx, ld, s);
-  launch_mean(gp.cp, gp.dX.p, n, none, gp.dKinvY.p, Px, nc, gp.mean, false, m.dMuh, s);
+  launch_mean(gp.cp, gp.dX.p, n, gp.derivs, gp.dKinvY.p, Px, nc, gp.mean, false, m.dMuh, s);
   if (m.p > 0) kg1_pending_rows(m, Px, m.dVx, nc, 0, m.p, s);
   launch_kernel_ens<ei1_cand_kernel_body, 256>(ei1_cand_kernel, dim3((unsigned)((nc + 3) / 4)), b256, 0, s, R, ld, nc, c0, gp.cp,
                                                with_grad ? 1 : 0, (const double*)m.dBp, (const double*)m.dMuh, (const double*)m.dVx,
@@ -206,8 +279,13 @@ void ei1_eval_pass(const Kg1Member& m, const double* Px, int nc, int c0, bool wi
   if (m.p > 0) kg1_pending_back(m, nc, s);  // (L'^-T: the pending block first, then the member's own on the corrected rows)
   tri_cols(gp, 'T', nc, m.dT, ld, m.dU, ld, s);
   dispatch_dp(dp, [&](auto DP) {
-    launch_kernel_ens<ei1_grad_kernel_body<DP>, 256>(ei1_grad_kernel<DP>, dim3((unsigned)nc), b256, 0, s, R, ld, d, c0, gp.cp, Xr, Kr, Px,
-                                                     (const double*)m.dU, (const double*)m.dScal, m.dGrad);
+    if (gp.g > 0)
+      launch_kernel_ens<ei1_grad_g_kernel_body<DP>, 256>(ei1_grad_g_kernel<DP>, dim3((unsigned)nc), b256, 0, s, n + m.p / m.g1, ld, d, c0,
+                                                         gp.cp, gp.derivs, Xr, Kr, Px, (const double*)m.dU, (const double*)m.dScal,
+                                                         m.dGrad);
+    else
+      launch_kernel_ens<ei1_grad_kernel_body<DP>, 256>(ei1_grad_kernel<DP>, dim3((unsigned)nc), b256, 0, s, R, ld, d, c0, gp.cp, Xr, Kr,
+                                                       Px, (const double*)m.dU, (const double*)m.dScal, m.dGrad);
   });
   MOE_HIP_CHECK(hipGetLastError());
 }
@@ -218,7 +296,8 @@ void ei1_eval_points(const Kg1Member& m, const double* Px, const double*, int C,
   for (int c0 = 0; c0 < C; c0 += m.per_pass) ei1_eval_pass(m, Px + (size_t)c0 * dp, std::min(m.per_pass, C - c0), c0, with_grad, s);
 }
 
-void check_members(const std::vector<GpDev*>& gps) {
+// pending_room: the pending points the call will hold at most (the caller's and a greedy batch's picks)
+void check_members(const std::vector<GpDev*>& gps, int pending_room) {
   const GpDev* g0 = gps[0];
   for (size_t e = 0; e < gps.size(); ++e) {
     const GpDev* g = gps[e];
@@ -227,25 +306,31 @@ void check_members(const std::vector<GpDev*>& gps) {
       throw Error(MOE_ERR_INVALID_VALUE, "MCMC ensemble members must live on one device", g->device, g0->device, (double)e);
   }
   for (size_t e = 0; e < gps.size(); ++e) {
-    if (gps[e]->g > 0)
-      throw Error(MOE_ERR_BOUNDS,
-                  "the ensemble analytic expected improvement needs GPs without derivative observations: a pending experiment "
-                  "would observe derivatives too",
-                  gps[e]->g, 0, 0);
+    const GpDev* g = gps[e];
+    if (g->g != g0->g || !std::equal(g->derivs.idx, g->derivs.idx + g->g, g0->derivs.idx))
+      throw Error(MOE_ERR_INVALID_VALUE,
+                  "MCMC ensemble members must share the observed-derivative list: a pending experiment observes the same derivatives "
+                  "under every member",
+                  g->g, g0->g, (double)e);
     for (size_t f = 0; f < e; ++f)
       if (gps[f] == gps[e])
         throw Error(MOE_ERR_INVALID_VALUE, "an MCMC ensemble member is listed twice (every member keeps its own workspaces)", (double)e,
                     (double)f, 0);
   }
+  const int g1 = 1 + g0->g;
+  if ((long)pending_room * g1 > kKg1MaxPending)
+    throw Error(MOE_ERR_BOUNDS,
+                "pending points (num_being_sampled + num_to_sample - 1) times (1 + num_derivatives) believed observations each "
+                "must fit 64 extension rows",
+                pending_room, 0, kKg1MaxPending / g1);
 }
 
-// mu(P_j0 .. j0 + count - 1) and their part in b' for every member
+// mu(P_j0 .. j0 + count - 1), the function values alone, and their part in b' for every member
 void join_believed_best(Kg1Ensemble& T, int j0, int count, bool first) {
-  const DerivList none = no_derivs();
   for (Kg1Member& m : T.mem) {
     GpDev& gp = *m.gp;
     if (count > 0)
-      launch_mean(gp.cp, gp.dX.p, gp.n, none, gp.dKinvY.p, T.dPending + (size_t)j0 * T.dp, count, gp.mean, false, m.dAA, T.z);
+      launch_mean(gp.cp, gp.dX.p, gp.n, gp.derivs, gp.dKinvY.p, T.dPending + (size_t)j0 * T.dp, count, gp.mean, false, m.dAA, T.z);
     MOE_LAUNCH_NOW(ei1_best_kernel, dim3(1), dim3(64), 0, T.z, m.best, first ? 1 : 0, (const double*)m.dAA, count, m.dBp);
   }
   MOE_HIP_CHECK(hipGetLastError());
@@ -279,7 +364,8 @@ void stage(Kg1Ensemble& T, const std::vector<GpDev*>& gps, const double* best_so
   g0.dStateIn.reserve(nIn);
   T.mem.clear();
   for (int e = 0; e < E; ++e)
-    T.mem.push_back(ei1_member(*gps[e], C, best_so_far[e], with_grad, T.iFail + e, pcap, pcap > 0 ? T.iFail + E + e : nullptr));
+    T.mem.push_back(ei1_member(*gps[e], C, best_so_far[e], with_grad, T.iFail + e, pcap * (1 + gps[e]->g),
+                               pcap > 0 ? T.iFail + E + e : nullptr));  // (pcap points: 1 + g rows each)
   double* h = g0.hStateIn.p;
   static_assert(sizeof(const double*) == sizeof(double), "the pointer tables travel inside a buffer of doubles");
   for (int e = 0; e < E; ++e) {
@@ -318,7 +404,7 @@ void stage(Kg1Ensemble& T, const std::vector<GpDev*>& gps, const double* best_so
 void stage_ascent(Kg1Ensemble& T, const std::vector<GpDev*>& gps, const moe_gd_params_t& outer, const double* domain_bounds,
                   const double* best_so_far, const double* starts, int S, bool ascent, bool want_path, const double* pending, int p,
                   int pcap) {
-  check_members(gps);
+  check_members(gps, pcap);
   GpDev& g0 = *gps[0];
   const int E = (int)gps.size(), W = pcap > 0 ? 2 * E : E, d = g0.d, dp = g0.dp;
   const int R = std::max(outer.max_num_restarts, 0), Tn = outer.max_num_steps;
@@ -346,7 +432,7 @@ void check_ei_analytic_mcmc_shapes(int num_mcmc, int num_points) {
 
 void ei_analytic_mcmc_on_device(const std::vector<GpDev*>& gps, const double* best_so_far, const double* pts, int C, bool want_grad,
                                 double* ei_out, double* grad_out, const double* pending, int num_pending) {
-  check_members(gps);
+  check_members(gps, num_pending);
   GpDev& g0 = *gps[0];
   Kg1Ensemble T;
   const int d = g0.d;

@@ -242,9 +242,10 @@ struct Kg1Member {
   int *iFail = nullptr, *iHid = nullptr;
   // pending points (kg1_pending.hip): the conditioned GP's pcap rows of room beside the member's own factor, p of them in use.  ld = N +
   // pcap is the leading dimension of V_A, V_x, V_x^, T and U: a column is [L^-1 k(X, z) ; r_z], the pending rows under the member's.
-  int p = 0, pcap = 0, ld = 0;
-  const double* dPP = nullptr;  // the pending points [pcap][dp] (the caller's upload; rows past p filled as they are picked)
-  double* dXe = nullptr;        // X u P [N + pcap][dp]
+  // A member with g observed derivatives (ei1.hip only) counts ROWS here: a pending point is g1 = 1 + g rows, p and pcap multiples of g1.
+  int p = 0, pcap = 0, ld = 0, g1 = 1;
+  const double* dPP = nullptr;  // the pending points [pcap / g1][dp] (the caller's upload; rows past p filled as they are picked)
+  double* dXe = nullptr;        // X u P, points [n + pcap / g1][dp]
   double* dKe = nullptr;        // [K^-1 (y - mean) ; 0]
   double* dVP = nullptr;        // column j [ld]: L^-1 k(X, P_j), then row j of L_P with its diagonal
   int* iFailP = nullptr;        // the first pending point whose Schur pivot fails the pivot rule
@@ -266,6 +267,8 @@ void tri_cols(GpDev& gp, char op, int c, const double* B, long ldb, double* Cout
 //                       set_ready: the set's V_A gains their rows (otherwise kg1_prepare_set forms all of them)
 //   kg1_pending_rows    rows i0 .. i1 - 1 of r_z = L_P^-1 (k(P, z) - V_P^T v_z) under the ncols columns V of the points Z [ncols][dp]
 //   kg1_pending_back    u_P = L_P^-T t_P into m.dU and t -= V_P u_P on the member's rows of m.dT, for ncols columns
+// With m.g1 = 1 + g > 1 (derivative observations; ei1.hip) a pending point is g1 extension rows and i0, i1 count rows: the limit is
+// kKg1MaxPending ROWS.
 constexpr int kKg1MaxPending = 64;
 void kg1_pending_begin(Kg1Member& m, hipStream_t s);
 void kg1_pending_append(Kg1Member& m, int count, bool set_ready, hipStream_t s);
@@ -303,7 +306,9 @@ void kg_discrete_mcmc_suggest(const std::vector<GpDev*>& gps, int num_fidelity, 
 // ei1.hip: the analytic one-point expected improvement averaged over an ensemble (moe_ei_analytic_mcmc), its multistart ascent
 // (moe_ei_analytic_mcmc_multistart) and greedy batches (moe_ei_analytic_mcmc_suggest), with pending points [num_pending][dim] by the
 // Kriging-believer fantasy of kg1_pending.hip; the caller has made the checks that need no handle (check_ei_analytic_mcmc_shapes,
-// check_kg_discrete_pending).  Candidates go through in passes of ei1_pass_size(N).
+// check_kg_discrete_pending).  Candidates go through in passes of ei1_pass_size(N).  Members may carry derivative observations (one
+// observed-derivative list for all of them): a pending point then believes its value and those derivatives, 1 + g rows, and
+// (num_pending + num_to_sample - 1) (1 + g) <= kKg1MaxPending (MOE_ERR_BOUNDS after the handle checks).
 int ei1_pass_size(int N);
 void check_ei_analytic_mcmc_shapes(int num_mcmc, int num_points);
 void ei_analytic_mcmc_on_device(const std::vector<GpDev*>& gps, const double* best_so_far, const double* pts, int C, bool want_grad,

@@ -6,7 +6,9 @@ reference averages it member after member on the host.  Here the ensemble mean, 
 batches of q > 1 points are one library call each (csrc/ei1.hip).  ``points_being_sampled`` names experiments that are running: each
 member's posterior covariance is conditioned on them, its posterior mean is left alone, and the believed values min_j mu_e(P_j)
 join the member's best value (the Kriging-believer fantasy of csrc/kg1_pending.hip), so a greedy batch does not re-pick its own
-points.
+points.  The GPs may carry derivative observations (the same list in every member): a pending point is then believed to return its
+value and those derivatives, 1 + num_derivatives rows of at most 64, and the best value defaults to the minimum of the observed
+FUNCTION values.
 
 ``AnalyticExpectedImprovementMCMC`` carries the method names python_version/optimization.py's GradientDescentOptimizer calls
 (``problem_size``, ``current_point``, ``compute_objective_function``, ``compute_grad_objective_function``), the way

@@ -343,9 +343,14 @@ int moe_kg_discrete_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, int n
  * MOE_ERR_BOUNDS; a NULL array (gps, best_so_far, points, ei, grad with want_grad) -> MOE_ERR_RUNTIME; num_points < 1 ->
  * MOE_ERR_BOUNDS; num_being_sampled outside 0 .. 64 -> MOE_ERR_BOUNDS, payload (num_being_sampled, 0, 64); points_being_sampled NULL
  * with num_being_sampled > 0 -> MOE_ERR_RUNTIME; a NULL handle -> MOE_ERR_RUNTIME; a member of another dim, then of another device ->
- * MOE_ERR_INVALID_VALUE, payload (its value, the first member's, the member); a member with derivative observations ->
- * MOE_ERR_BOUNDS, payload (num_derivatives, 0, 0) (a pending experiment would observe derivatives too); a handle listed twice ->
- * MOE_ERR_INVALID_VALUE.
+ * MOE_ERR_INVALID_VALUE, payload (its value, the first member's, the member); a member whose observed-derivative list is not the
+ * first member's -> MOE_ERR_INVALID_VALUE, payload (its num_derivatives, the first member's, the member); a handle listed twice ->
+ * MOE_ERR_INVALID_VALUE; num_being_sampled (1 + g) > 64 -> MOE_ERR_BOUNDS, payload (num_being_sampled, 0, 64 / (1 + g) rounded down).
+ * Derivative observations.  The members may observe g = num_derivatives partial derivatives at every sampled point (one list for
+ * all members).  A pending experiment then returns its value AND those derivatives: P_j contributes 1 + g rows to the conditioned
+ * covariance, row a with noise_variance[a] on its diagonal, all believed at the member's posterior means (so the mean is still left
+ * alone); only the believed function value mu_e(P_j) joins b'_e.  The candidate is a function value.  The extension holds 64 ROWS:
+ * num_being_sampled (1 + g) <= 64.  A member without derivative observations issues the launches it always did.
  * MOE_ERR_SINGULAR only for a pending point: payload (e, j), the first member e whose extension has a Schur pivot <= 1e-16 and the
  * first such pending point j; reported after the wait.  A candidate never raises: the two variance floors are the reference's. */
 int moe_ei_analytic_mcmc(const moe_gp_t* const* gps, int num_mcmc, const double* best_so_far, const double* points_being_sampled,
@@ -375,8 +380,9 @@ int moe_ei1_pass_size(int num_rows);
  * the end.  Ensemble-wide launches as in moe_ei_analytic_mcmc, a step's recording made once and issued every step.
  * Errors, in this order: those of moe_ei_analytic_mcmc that need no handle (outer, domain_bounds, starts, best_point, best_value and
  * found among the arrays that must not be NULL; num_starts for num_points); max_num_steps < 1 with do_gradient_ascent != 0 ->
- * MOE_ERR_BOUNDS; domain_type other than MOE_DOMAIN_TENSOR_PRODUCT -> MOE_ERR_INVALID_VALUE; then those that need the handles.
- * MOE_ERR_SINGULAR as above, at the next wait. */
+ * MOE_ERR_BOUNDS; domain_type other than MOE_DOMAIN_TENSOR_PRODUCT -> MOE_ERR_INVALID_VALUE; then those that need the handles, the
+ * row limit num_being_sampled (1 + g) <= 64 of members with g observed derivatives last.  MOE_ERR_SINGULAR as above, at the next
+ * wait. */
 int moe_ei_analytic_mcmc_multistart(const moe_gp_t* const* gps, int num_mcmc, const moe_gd_params_t* outer, const double* domain_bounds,
                                     const double* best_so_far, const double* points_being_sampled, int num_being_sampled,
                                     const double* starts, int num_starts, int do_gradient_ascent, double* best_point,
@@ -385,12 +391,14 @@ int moe_ei_analytic_mcmc_multistart(const moe_gp_t* const* gps, int num_mcmc, co
 /* num_to_sample points greedily: round t = 0 .. num_to_sample - 1 is moe_ei_analytic_mcmc_multistart from the same starts with
  * pending points = points_being_sampled followed by the picks x_0 .. x_{t-1} of the rounds before, and writes best_points[t][dim],
  * best_values[t], found[t]: bit for bit what num_to_sample calls of that function return when each is fed its predecessors' points.
- * Staged once; after round t ONE row joins each member's extension and one value mu_e(x_t) its believed best, the pick reaching both
+ * Staged once; after round t ONE row (1 + g rows of a member with g observed derivatives) joins each member's extension and one value mu_e(x_t) its believed best, the pick reaching both
  * inside device memory.  The host waits as often as moe_kg_discrete_mcmc_suggest does, and no more.
  * Errors, in this order: those of moe_ei_analytic_mcmc_multistart, with, directly after num_being_sampled: num_to_sample < 1 or
  * num_being_sampled + num_to_sample - 1 > 64 -> MOE_ERR_BOUNDS, payload (num_to_sample, 1, 65 - num_being_sampled); and best_points,
- * best_values, found among the arrays that must not be NULL.  MOE_ERR_SINGULAR as above: the pending index counts the caller's
- * points first, then the rounds' picks. */
+ * best_values, found among the arrays that must not be NULL.  With g observed derivatives a round appends 1 + g rows, and after
+ * the handle checks (num_being_sampled + num_to_sample - 1) (1 + g) > 64 -> MOE_ERR_BOUNDS, payload (num_being_sampled +
+ * num_to_sample - 1, 0, 64 / (1 + g) rounded down).  MOE_ERR_SINGULAR as above: the pending index counts the caller's points first,
+ * then the rounds' picks; it names the first point any of whose rows fails the pivot rule. */
 int moe_ei_analytic_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, const moe_gd_params_t* outer, const double* domain_bounds,
                                  const double* best_so_far, const double* points_being_sampled, int num_being_sampled,
                                  const double* starts, int num_starts, int do_gradient_ascent, int num_to_sample, double* best_points,

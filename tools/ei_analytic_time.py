@@ -3,13 +3,17 @@
 against DeviceGPMCMC.ei_multistart at q = 1 (moe_ei_mcmc_multistart: one batched state pass per member and step, every point's state
 copied back, mu, sigma^2, EI and grad EI finished per point in host code), on the same starts.  16 members, n = 500, d = 6, 200
 Latin-hypercube starts of which 20 are kept, 2 rounds of 50 steps.
-   python tools/ei_analytic_time.py [--out profiles/ei_analytic_time.txt] [--repeat 9]
+   python tools/ei_analytic_time.py [--out profiles/ei_analytic_time.txt] [--repeat 9] [--derivatives G]
+
+--derivatives G: every member also observes the first G partial derivatives at every point (N = n (1 + G) rows; G = 3 is the
+shape of BASELINE.json's d-KG configuration scaled to n = 500), the pending evaluation runs with p = 4 (16 extension rows at G = 3),
+and the lines are APPENDED to --out.  moe_ei_mcmc_multistart is the only other path such GPs have.
 
 Both run on the same build, alternated in one process, median of --repeat whole suggestions (host clock around calls that end in a
 device synchronise).  The two paths need not return the same point to the last bit (their arithmetic order differs): the distance
 between their end points is reported beside the times.  Then a greedy batch of q = 4 in one call (api.ei_analytic_suggest) against
 four calls of the ascent each fed its predecessors (the same bits, asserted), and one evaluation of 1024 candidates with p = 8
-pending points against p = 0.  No threshold is set; a ratio near or under 1 is a finding, not a failure."""
+pending points against p = 0 (p = 4 with --derivatives).  No threshold is set; a ratio near or under 1 is a finding, not a failure."""
 import os
 import subprocess
 import sys
@@ -43,6 +47,9 @@ def clocks(tag):
 
 E, N, D, STARTS, STEPS, ROUNDS, Q = 16, 500, 6, 200, 50, 2, 4
 repeat = int(sys.argv[sys.argv.index("--repeat") + 1]) if "--repeat" in sys.argv else 9
+G = int(sys.argv[sys.argv.index("--derivatives") + 1]) if "--derivatives" in sys.argv else 0
+DERIVS = tuple(range(G))
+PEND = 4 if G else 8
 gd = (STARTS, STEPS, ROUNDS, 0, 0.7, 1.0, 0.5, 1e-10)  # the outer parameters of examples/main.py
 
 
@@ -62,13 +69,15 @@ def host_calls(ens, bests, bounds, starts):
 clocks("before")
 rng = np.random.default_rng(0)
 X = rng.uniform(size=(N, D))
-y = np.sin(3 * X).sum(1, keepdims=True)
+y = np.hstack([np.sin(3 * X).sum(1, keepdims=True)] + [3 * np.cos(3 * X[:, i:i + 1]) for i in DERIVS])
 hypers = np.array([1.0] + [0.4] * D)[None, :] * np.exp(0.15 * rng.standard_normal((E, D + 1)))  # the spread of a hyper-parameter chain
-ens = api.DeviceGPMCMC(hypers, np.full((E, 1), 1e-2), X, y)
+ens = api.DeviceGPMCMC(hypers, np.full((E, 1 + G), 1e-2), X, y, DERIVS)
 bounds = np.array([[0.0, 1.0]] * D)
 starts = api.latin_hypercube(5, bounds, STARTS)
-bests = [float(y.min())] * E
+bests = [float(y[:, 0].min())] * E
 
+if G:
+    say("derivatives %s observed: N = %d rows per member" % (list(DERIVS), N * (1 + G)))
 say("%d members, n = %d, d = %d, %d starts -> 20 kept, %d x %d steps; whole suggestions, median / min of %d, alternated" % (
     E, N, D, STARTS, ROUNDS, STEPS, repeat))
 one = lambda: api.ei_analytic_multistart(ens, gd, bounds, bests, starts)  # noqa: E731
@@ -107,22 +116,22 @@ say("greedy q = %d: one call %s ms | %d calls %s ms (med/min) | ratio %.2fx" % (
 say("  EI of the %d picks: %s" % (Q, " ".join("%.6g" % v for v in values)))
 
 cand = np.random.default_rng(2).uniform(size=(1024, D))
-pend = np.random.default_rng(3).uniform(size=(8, D))
-t = {0: [], 8: []}
-for p in (0, 8):
+pend = np.random.default_rng(3).uniform(size=(PEND, D))
+t = {0: [], PEND: []}
+for p in (0, PEND):
     api.ei_analytic_ensemble(ens, cand, bests, points_being_sampled=pend[:p])  # workspaces
 for _ in range(repeat):
-    for p in (0, 8):
+    for p in (0, PEND):
         t0 = time.perf_counter()
         api.ei_analytic_ensemble(ens, cand, bests, points_being_sampled=pend[:p])
         t[p].append(1e3 * (time.perf_counter() - t0))
-say("1024 candidates with gradient, %d members: p = 0 %s ms, p = 8 %s ms (med/min), ratio %.2fx" % (
-    E, med_min(t[0]), med_min(t[8]), np.median(t[8]) / np.median(t[0])))
+say("1024 candidates with gradient, %d members: p = 0 %s ms, p = %d %s ms (med/min), ratio %.2fx" % (
+    E, med_min(t[0]), PEND, med_min(t[PEND]), np.median(t[PEND]) / np.median(t[0])))
 for g in ens.gps:
     g.close()
 clocks("after")
 if "--out" in sys.argv:
     path = sys.argv[sys.argv.index("--out") + 1]
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    with open(path, "w") as f:
+    with open(path, "a" if G else "w") as f:
         f.write("\n".join(lines) + "\n")
