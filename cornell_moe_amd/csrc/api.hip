@@ -5,6 +5,7 @@
 #include <cstring>
 #include <mutex>
 #include <random>
+#include <string>
 #include <condition_variable>
 #include <thread>
 
@@ -59,11 +60,18 @@ moe::GpDev& lock_gp(const moe_gp_t* gp_c, std::unique_lock<std::mutex>& lk) {
   return gp->dev;
 }
 
-moe::DerivList no_derivs() {
-  moe::DerivList d;
-  d.g = 0;
-  for (int i = 0; i < moe::kMaxDerivs; ++i) d.idx[i] = 0;
-  return d;
+// The preamble of the ensemble one-point acquisitions' entry points (moe_kg_discrete_mcmc*, moe_ei_analytic_mcmc*).
+void check_num_mcmc(int num_mcmc) {
+  if (num_mcmc < 1 || num_mcmc > 1024) throw moe::Error(MOE_ERR_BOUNDS, "num_mcmc must be between 1 and 1024", num_mcmc, 1, 1024);
+}
+
+// objective: whose ascent it is, as the message names it
+void check_ascent_params(const moe_gd_params_t* outer, int do_gradient_ascent, const char* objective) {
+  if (do_gradient_ascent != 0 && outer->max_num_steps < 1)
+    throw moe::Error(MOE_ERR_BOUNDS, "max_num_steps must be positive", outer->max_num_steps, 1, 1e9);
+  if (outer->domain_type != MOE_DOMAIN_TENSOR_PRODUCT)
+    throw moe::Error(MOE_ERR_INVALID_VALUE, std::string(objective) + "'s ascent supports tensor-product domains only",
+                     outer->domain_type, 0, 0);
 }
 
 }  // namespace
@@ -378,7 +386,7 @@ int moe_gp_mix_covariance(const moe_gp_t* gp_c, const double* pts, int num_pts, 
     std::unique_lock<std::mutex> lk;
     moe::GpDev& gp = lock_gp(gp_c, lk);
     gp.use_device();
-    moe::DerivList d2 = no_derivs();
+    moe::DerivList d2 = moe::no_derivs();
     require(g2 >= 0 && g2 <= moe::kMaxDerivs, "g2 out of range");
     d2.g = g2;
     for (int i = 0; i < g2; ++i) d2.idx[i] = derivs2[i];
@@ -405,10 +413,10 @@ int moe_cov_build_probe(const moe_gp_t* gp_c, const double* pts, int num_pts, in
     hipEvent_t e0, e1;
     MOE_HIP_CHECK(hipEventCreate(&e0));
     MOE_HIP_CHECK(hipEventCreate(&e1));
-    moe::launch_cov_build(gp.cp, gp.dX.p, gp.n, gp.derivs, dP.p, num_pts, no_derivs(), nullptr, dOut.p, gp.N, 0, gp.stream, true);
+    moe::launch_cov_build(gp.cp, gp.dX.p, gp.n, gp.derivs, dP.p, num_pts, moe::no_derivs(), nullptr, dOut.p, gp.N, 0, gp.stream, true);
     MOE_HIP_CHECK(hipEventRecord(e0, gp.stream));
     for (int r = 0; r < repeat; ++r)
-      moe::launch_cov_build(gp.cp, gp.dX.p, gp.n, gp.derivs, dP.p, num_pts, no_derivs(), nullptr, dOut.p, gp.N, 0, gp.stream, true);
+      moe::launch_cov_build(gp.cp, gp.dX.p, gp.n, gp.derivs, dP.p, num_pts, moe::no_derivs(), nullptr, dOut.p, gp.N, 0, gp.stream, true);
     MOE_HIP_CHECK(hipEventRecord(e1, gp.stream));
     MOE_HIP_CHECK(hipEventSynchronize(e1));
     float ms = 0.f;
@@ -837,15 +845,8 @@ int moe_posterior_mean_members_minimize(const moe_gp_t* const* gps, int num_mcmc
 int moe_kg_discrete_mcmc(const moe_gp_t* const* gps, int num_mcmc, int num_fidelity, const double* discrete_all,
                          const int* num_discrete, const double* best_so_far, const double* points, int num_points, int want_grad,
                          double* kg, double* grad, moe_error_t* err) {
-  return guarded(err, [&] {
-    if (num_mcmc < 1 || num_mcmc > 1024) throw moe::Error(MOE_ERR_BOUNDS, "num_mcmc must be between 1 and 1024", num_mcmc, 1, 1024);
-    require(gps && discrete_all && num_discrete && best_so_far && points && kg && (want_grad == 0 || grad), "NULL argument");
-    moe::check_kg_discrete_ensemble_shapes(num_mcmc, num_fidelity, num_discrete, num_points);  // (what needs no handle)
-    const auto locks = lock_ensemble(gps, num_mcmc);
-    const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
-    moe::kg_discrete_mcmc_on_device(v, num_fidelity, discrete_all, num_discrete, best_so_far, points, num_points, want_grad != 0, kg,
-                                    grad);
-  });
+  return moe_kg_discrete_mcmc_pending(gps, num_mcmc, num_fidelity, discrete_all, num_discrete, best_so_far, nullptr, 0, points,
+                                      num_points, want_grad, kg, grad, err);
 }
 
 int moe_kg_discrete_mcmc_multistart(const moe_gp_t* const* gps, int num_mcmc, int num_fidelity, const moe_gd_params_t* outer,
@@ -853,22 +854,10 @@ int moe_kg_discrete_mcmc_multistart(const moe_gp_t* const* gps, int num_mcmc, in
                                     const double* best_so_far, const double* starts, int num_starts, int do_gradient_ascent,
                                     double* best_point, double* best_value, int* found, double* start_values, int* kept_index,
                                     double* end_points, double* end_values, double* path, int* steps_taken, moe_error_t* err) {
-  return guarded(err, [&] {
-    if (num_mcmc < 1 || num_mcmc > 1024) throw moe::Error(MOE_ERR_BOUNDS, "num_mcmc must be between 1 and 1024", num_mcmc, 1, 1024);
-    require(gps && outer && domain_bounds && discrete_all && num_discrete && best_so_far && starts && best_point && best_value && found,
-            "NULL argument");
-    moe::check_kg_discrete_ensemble_shapes(num_mcmc, num_fidelity, num_discrete, num_starts);
-    if (do_gradient_ascent != 0 && outer->max_num_steps < 1)
-      throw moe::Error(MOE_ERR_BOUNDS, "max_num_steps must be positive", outer->max_num_steps, 1, 1e9);
-    if (outer->domain_type != MOE_DOMAIN_TENSOR_PRODUCT)
-      throw moe::Error(MOE_ERR_INVALID_VALUE, "the discretised knowledge gradient's ascent supports tensor-product domains only",
-                       outer->domain_type, 0, 0);
-    const auto locks = lock_ensemble(gps, num_mcmc);
-    const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
-    moe::kg_discrete_mcmc_multistart(v, num_fidelity, *outer, domain_bounds, discrete_all, num_discrete, best_so_far, starts, num_starts,
-                                     do_gradient_ascent, best_point, best_value, found, start_values, kept_index, end_points,
-                                     end_values, path, steps_taken);
-  });
+  return moe_kg_discrete_mcmc_multistart_pending(gps, num_mcmc, num_fidelity, outer, domain_bounds, discrete_all, num_discrete,
+                                                 best_so_far, nullptr, 0, starts, num_starts, do_gradient_ascent, best_point,
+                                                 best_value, found, start_values, kept_index, end_points, end_values, path,
+                                                 steps_taken, err);
 }
 
 int moe_kg_discrete_mcmc_pending(const moe_gp_t* const* gps, int num_mcmc, int num_fidelity, const double* discrete_all,
@@ -876,7 +865,7 @@ int moe_kg_discrete_mcmc_pending(const moe_gp_t* const* gps, int num_mcmc, int n
                                  int num_being_sampled, const double* points, int num_points, int want_grad, double* kg, double* grad,
                                  moe_error_t* err) {
   return guarded(err, [&] {
-    if (num_mcmc < 1 || num_mcmc > 1024) throw moe::Error(MOE_ERR_BOUNDS, "num_mcmc must be between 1 and 1024", num_mcmc, 1, 1024);
+    check_num_mcmc(num_mcmc);
     require(gps && discrete_all && num_discrete && best_so_far && points && kg && (want_grad == 0 || grad), "NULL argument");
     moe::check_kg_discrete_ensemble_shapes(num_mcmc, num_fidelity, num_discrete, num_points);  // (what needs no handle)
     moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, 1);
@@ -895,16 +884,12 @@ int moe_kg_discrete_mcmc_multistart_pending(const moe_gp_t* const* gps, int num_
                                             double* end_points, double* end_values, double* path, int* steps_taken,
                                             moe_error_t* err) {
   return guarded(err, [&] {
-    if (num_mcmc < 1 || num_mcmc > 1024) throw moe::Error(MOE_ERR_BOUNDS, "num_mcmc must be between 1 and 1024", num_mcmc, 1, 1024);
+    check_num_mcmc(num_mcmc);
     require(gps && outer && domain_bounds && discrete_all && num_discrete && best_so_far && starts && best_point && best_value && found,
             "NULL argument");
     moe::check_kg_discrete_ensemble_shapes(num_mcmc, num_fidelity, num_discrete, num_starts);
     moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, 1);
-    if (do_gradient_ascent != 0 && outer->max_num_steps < 1)
-      throw moe::Error(MOE_ERR_BOUNDS, "max_num_steps must be positive", outer->max_num_steps, 1, 1e9);
-    if (outer->domain_type != MOE_DOMAIN_TENSOR_PRODUCT)
-      throw moe::Error(MOE_ERR_INVALID_VALUE, "the discretised knowledge gradient's ascent supports tensor-product domains only",
-                       outer->domain_type, 0, 0);
+    check_ascent_params(outer, do_gradient_ascent, "the discretised knowledge gradient");
     const auto locks = lock_ensemble(gps, num_mcmc);
     const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
     moe::kg_discrete_mcmc_multistart(v, num_fidelity, *outer, domain_bounds, discrete_all, num_discrete, best_so_far, starts, num_starts,
@@ -919,16 +904,12 @@ int moe_kg_discrete_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, int n
                                  const double* starts, int num_starts, int do_gradient_ascent, int num_to_sample, double* best_points,
                                  double* best_values, int* found, moe_error_t* err) {
   return guarded(err, [&] {
-    if (num_mcmc < 1 || num_mcmc > 1024) throw moe::Error(MOE_ERR_BOUNDS, "num_mcmc must be between 1 and 1024", num_mcmc, 1, 1024);
+    check_num_mcmc(num_mcmc);
     require(gps && outer && domain_bounds && discrete_all && num_discrete && best_so_far && starts && best_points && best_values && found,
             "NULL argument");
     moe::check_kg_discrete_ensemble_shapes(num_mcmc, num_fidelity, num_discrete, num_starts);
     moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, num_to_sample);
-    if (do_gradient_ascent != 0 && outer->max_num_steps < 1)
-      throw moe::Error(MOE_ERR_BOUNDS, "max_num_steps must be positive", outer->max_num_steps, 1, 1e9);
-    if (outer->domain_type != MOE_DOMAIN_TENSOR_PRODUCT)
-      throw moe::Error(MOE_ERR_INVALID_VALUE, "the discretised knowledge gradient's ascent supports tensor-product domains only",
-                       outer->domain_type, 0, 0);
+    check_ascent_params(outer, do_gradient_ascent, "the discretised knowledge gradient");
     const auto locks = lock_ensemble(gps, num_mcmc);
     const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
     moe::kg_discrete_mcmc_suggest(v, num_fidelity, *outer, domain_bounds, discrete_all, num_discrete, best_so_far, starts, num_starts,
@@ -943,7 +924,7 @@ int moe_ei_analytic_mcmc(const moe_gp_t* const* gps, int num_mcmc, const double*
                          int num_being_sampled, const double* points, int num_points, int want_grad, double* ei, double* grad,
                          moe_error_t* err) {
   return guarded(err, [&] {
-    if (num_mcmc < 1 || num_mcmc > 1024) throw moe::Error(MOE_ERR_BOUNDS, "num_mcmc must be between 1 and 1024", num_mcmc, 1, 1024);
+    check_num_mcmc(num_mcmc);
     require(gps && best_so_far && points && ei && (want_grad == 0 || grad), "NULL argument");
     moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_points);  // (what needs no handle)
     moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, 1);
@@ -960,15 +941,11 @@ int moe_ei_analytic_mcmc_multistart(const moe_gp_t* const* gps, int num_mcmc, co
                                     double* best_value, int* found, double* start_values, int* kept_index, double* end_points,
                                     double* end_values, double* path, int* steps_taken, moe_error_t* err) {
   return guarded(err, [&] {
-    if (num_mcmc < 1 || num_mcmc > 1024) throw moe::Error(MOE_ERR_BOUNDS, "num_mcmc must be between 1 and 1024", num_mcmc, 1, 1024);
+    check_num_mcmc(num_mcmc);
     require(gps && outer && domain_bounds && best_so_far && starts && best_point && best_value && found, "NULL argument");
     moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_starts);
     moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, 1);
-    if (do_gradient_ascent != 0 && outer->max_num_steps < 1)
-      throw moe::Error(MOE_ERR_BOUNDS, "max_num_steps must be positive", outer->max_num_steps, 1, 1e9);
-    if (outer->domain_type != MOE_DOMAIN_TENSOR_PRODUCT)
-      throw moe::Error(MOE_ERR_INVALID_VALUE, "the analytic expected improvement's ascent supports tensor-product domains only",
-                       outer->domain_type, 0, 0);
+    check_ascent_params(outer, do_gradient_ascent, "the analytic expected improvement");
     const auto locks = lock_ensemble(gps, num_mcmc);
     const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
     moe::ei_analytic_mcmc_multistart(v, *outer, domain_bounds, best_so_far, starts, num_starts, do_gradient_ascent, best_point,
@@ -982,15 +959,11 @@ int moe_ei_analytic_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, const
                                  const double* starts, int num_starts, int do_gradient_ascent, int num_to_sample, double* best_points,
                                  double* best_values, int* found, moe_error_t* err) {
   return guarded(err, [&] {
-    if (num_mcmc < 1 || num_mcmc > 1024) throw moe::Error(MOE_ERR_BOUNDS, "num_mcmc must be between 1 and 1024", num_mcmc, 1, 1024);
+    check_num_mcmc(num_mcmc);
     require(gps && outer && domain_bounds && best_so_far && starts && best_points && best_values && found, "NULL argument");
     moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_starts);
     moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, num_to_sample);
-    if (do_gradient_ascent != 0 && outer->max_num_steps < 1)
-      throw moe::Error(MOE_ERR_BOUNDS, "max_num_steps must be positive", outer->max_num_steps, 1, 1e9);
-    if (outer->domain_type != MOE_DOMAIN_TENSOR_PRODUCT)
-      throw moe::Error(MOE_ERR_INVALID_VALUE, "the analytic expected improvement's ascent supports tensor-product domains only",
-                       outer->domain_type, 0, 0);
+    check_ascent_params(outer, do_gradient_ascent, "the analytic expected improvement");
     const auto locks = lock_ensemble(gps, num_mcmc);
     const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
     moe::ei_analytic_mcmc_suggest(v, *outer, domain_bounds, best_so_far, starts, num_starts, do_gradient_ascent, points_being_sampled,

@@ -1,7 +1,9 @@
 // cornell_moe_amd/csrc/ei1.hip -- the analytic one-point expected improvement (OnePotentialSampleExpectedImprovementEvaluator,
 // gpp_math.cpp:2195-2259) averaged over a hyper-parameter ensemble, with pending points, its multistart ascent and greedy q-point
 // batches, on the device (moe_ei_analytic_mcmc, moe_ei_analytic_mcmc_multistart, moe_ei_analytic_mcmc_suggest): the EI twin of
-// kg1_opt.hip, sharing its ascent (kg1_ascent.hpp) and the pending-row extension (kg1_pending.hip).
+// kg1_opt.hip.  The staging, the ascent and the drivers of the three entry points are the shared ones of kg1_ascent.hip (declared in
+// kg1_ascent.hpp), the pending-row extension is kg1_pending.hip's; this file keeps the kernels, a member's layout and chain, the
+// believed best, the row bound and the description of the objective.
 //
 // Member e: posterior mean mu_e, posterior covariance of the latent function conditioned on the pending points P with the member's
 // noise on P's diagonal (the Kriging-believer fantasy: the mean is left alone), believed best b'_e = min(b_e, min_j mu_e(P_j)).  With
@@ -26,7 +28,7 @@
 //
 // Bits.  The triangular products are tri_cols (the kernel family fixed by N alone), var is ONE fused multiply-add chain over the
 // member's rows in row order and then the pending rows in order, the gradient's sums have a fixed shape: a candidate's bits do not
-// depend on who shares its pass, its call or its ascent step.  The ensemble mean, the step and the rounds are kg1_ascent.hpp's.
+// depend on who shares its pass, its call or its ascent step.  The ensemble mean, the step and the rounds are kg1_ascent.hip's.
 // A candidate never raises: the two floors are the reference's behaviour.  Only a pending point whose Schur pivot fails raises.
 //
 // Derivative observations (g = num_derivatives > 0, one list for every member).  The member's rows are its N = n (1 + g) observations,
@@ -36,6 +38,7 @@
 // the coefficients are the same expressions over R = N + p (1 + g) rows, and grad_x k(row, x) of a derivative row is the covariance's
 // second-derivative block: ei1_grad_g_kernel strides over the n + p POINTS and applies a point's 1 + g coefficients to one set of
 // radial scalars.  A member with g = 0 issues exactly the launches above.  At most 64 extension rows: p (1 + g) <= 64.
+#include <algorithm>
 #include <cfloat>
 
 #include "device_cov.hpp"
@@ -208,13 +211,6 @@ __global__ __launch_bounds__(256) void ei1_grad_g_kernel(int P, int ld, int d, i
   ei1_grad_g_kernel_body<DP>::run(MOE_VBLOCK, MOE_VGRID, nullptr, P, ld, d, col0, cp, dl, X, kinvy, Px, U, cdf, grad);
 }
 
-DerivList no_derivs() {
-  DerivList d;
-  d.g = 0;
-  for (int i = 0; i < kMaxDerivs; ++i) d.idx[i] = 0;
-  return d;
-}
-
 // Where one GP's per-pass scratch and results live for a call of at most C candidates, inside the GP's own kg1D (results first:
 // [EI C | grad C d]), dE and dEK: Kg1Member with an empty set (A = 0; dAA holds mu(P), dScal Phi(c_g), dMuh mu(x)).  pcap: room
 // for that many extension ROWS, a multiple of 1 + g.
@@ -290,34 +286,25 @@ void ei1_eval_pass(const Kg1Member& m, const double* Px, int nc, int c0, bool wi
   MOE_HIP_CHECK(hipGetLastError());
 }
 
-// (Ph: kg1_ascent.hpp's second view of the points, the same as Px where there are no fidelity coordinates)
+// (Ph: the staging's second view of the points, the same as Px where there are no fidelity coordinates)
 void ei1_eval_points(const Kg1Member& m, const double* Px, const double*, int C, bool with_grad, hipStream_t s) {
   const int dp = m.gp->dp;
   for (int c0 = 0; c0 < C; c0 += m.per_pass) ei1_eval_pass(m, Px + (size_t)c0 * dp, std::min(m.per_pass, C - c0), c0, with_grad, s);
 }
 
-// pending_room: the pending points the call will hold at most (the caller's and a greedy batch's picks)
+// the members' own check (kg1_ascent.hpp: kg1_check_members), then the room for pending_room pending points (the caller's and a
+// greedy batch's picks)
+void check_member(const GpDev& g, const GpDev& g0, size_t e, int) {
+  if (g.g != g0.g || !std::equal(g.derivs.idx, g.derivs.idx + g.g, g0.derivs.idx))
+    throw Error(MOE_ERR_INVALID_VALUE,
+                "MCMC ensemble members must share the observed-derivative list: a pending experiment observes the same derivatives "
+                "under every member",
+                g.g, g0.g, (double)e);
+}
+
 void check_members(const std::vector<GpDev*>& gps, int pending_room) {
-  const GpDev* g0 = gps[0];
-  for (size_t e = 0; e < gps.size(); ++e) {
-    const GpDev* g = gps[e];
-    if (g->d != g0->d) throw Error(MOE_ERR_INVALID_VALUE, "MCMC ensemble members must share dim", g->d, g0->d, (double)e);
-    if (g->device != g0->device)
-      throw Error(MOE_ERR_INVALID_VALUE, "MCMC ensemble members must live on one device", g->device, g0->device, (double)e);
-  }
-  for (size_t e = 0; e < gps.size(); ++e) {
-    const GpDev* g = gps[e];
-    if (g->g != g0->g || !std::equal(g->derivs.idx, g->derivs.idx + g->g, g0->derivs.idx))
-      throw Error(MOE_ERR_INVALID_VALUE,
-                  "MCMC ensemble members must share the observed-derivative list: a pending experiment observes the same derivatives "
-                  "under every member",
-                  g->g, g0->g, (double)e);
-    for (size_t f = 0; f < e; ++f)
-      if (gps[f] == gps[e])
-        throw Error(MOE_ERR_INVALID_VALUE, "an MCMC ensemble member is listed twice (every member keeps its own workspaces)", (double)e,
-                    (double)f, 0);
-  }
-  const int g1 = 1 + g0->g;
+  kg1_check_members(gps, 0, check_member);
+  const int g1 = 1 + gps[0]->g;
   if ((long)pending_room * g1 > kKg1MaxPending)
     throw Error(MOE_ERR_BOUNDS,
                 "pending points (num_being_sampled + num_to_sample - 1) times (1 + num_derivatives) believed observations each "
@@ -336,85 +323,23 @@ void join_believed_best(Kg1Ensemble& T, int j0, int count, bool first) {
   MOE_HIP_CHECK(hipGetLastError());
 }
 
-// The members' layouts and the one upload: [EI pointers E | grad pointers E | bounds 2 d | points C dp | pending points pcap dp];
-// then every member's extension and believed best.  extra_ints: integers of the caller behind the failure words in the first
-// member's kg1oI (kg1_opt.hip: stage()).
-void stage(Kg1Ensemble& T, const std::vector<GpDev*>& gps, const double* best_so_far, const double* bounds, const double* pts, int C,
-           bool with_grad, size_t extra_ints, const double* pending, int p, int pcap) {
-  GpDev& g0 = *gps[0];
-  T.gps = gps;
-  T.E = (int)gps.size();
-  T.d = g0.d;
-  T.dp = g0.dp;
-  T.nf = 0;
-  T.fid = false;
-  T.eval_points = ei1_eval_points;
-  g0.use_device();
-  T.z = g0.stream;
-  T.ens = ensemble_launches() && T.E > 1;
-  const int E = T.E, d = T.d, dp = T.dp;
-  T.p = 0;
-  T.pcap = pcap;
-  T.W = pcap > 0 ? 2 * E : E;
-  g0.kg1oI.reserve((size_t)T.W + extra_ints);
-  T.iFail = g0.kg1oI.p;
-  const size_t nC = (size_t)C, oBounds = 2 * (size_t)E, oPts = oBounds + 2 * (size_t)d, oPend = oPts + nC * dp;
-  const size_t nIn = oPend + (size_t)pcap * dp;
-  g0.hStateIn.reserve(nIn);
-  g0.dStateIn.reserve(nIn);
-  T.mem.clear();
-  for (int e = 0; e < E; ++e)
-    T.mem.push_back(ei1_member(*gps[e], C, best_so_far[e], with_grad, T.iFail + e, pcap * (1 + gps[e]->g),
-                               pcap > 0 ? T.iFail + E + e : nullptr));  // (pcap points: 1 + g rows each)
-  double* h = g0.hStateIn.p;
-  static_assert(sizeof(const double*) == sizeof(double), "the pointer tables travel inside a buffer of doubles");
-  for (int e = 0; e < E; ++e) {
-    const double* pk = T.mem[e].dKg;
-    const double* pg = T.mem[e].dGrad;
-    std::memcpy(h + e, &pk, sizeof(pk));
-    std::memcpy(h + E + e, &pg, sizeof(pg));
-  }
-  for (int k = 0; k < 2 * d; ++k) h[oBounds + k] = bounds != nullptr ? bounds[k] : 0.0;
-  for (size_t i = 0; i < nC; ++i)
-    for (int k = 0; k < dp; ++k) h[oPts + i * dp + k] = (k < d) ? pts[i * d + k] : 0.0;
-  for (size_t i = 0; i < (size_t)pcap; ++i)
-    for (int k = 0; k < dp; ++k) h[oPend + i * dp + k] = (i < (size_t)p && k < d) ? pending[i * d + k] : 0.0;
-  g0.dStateIn.upload(h, nIn, T.z, true);
-  const double* dIn = g0.dStateIn.p;
-  T.dPending = g0.dStateIn.p + oPend;
-  T.dKgTab = reinterpret_cast<const double* const*>(dIn);
-  T.dGradTab = reinterpret_cast<const double* const*>(dIn + E);
-  T.dBounds = dIn + oBounds;
-  T.dPts = dIn + oPts;
-  T.dPtsH = T.dPts;
-  kg1_clear_fail(T.iFail, E, T.z);
-  if (pcap > 0) kg1_clear_fail(T.iFail + E, E, T.z);
-  for (Kg1Member& m : T.mem) {
-    if (pcap > 0) {
-      m.dPP = T.dPending;
-      kg1_pending_begin(m, T.z);
-      if (p > 0) kg1_pending_append(m, p, false, T.z);
-    }
-  }
-  join_believed_best(T, 0, p, true);
-  T.p = p;
+Kg1Member member(const Kg1Objective& o, GpDev& gp, int e, int C, bool with_grad, int* fail, int pcap, int* fail_pending) {
+  return ei1_member(gp, C, o.best_so_far[e], with_grad, fail, pcap * (1 + gp.g), fail_pending);  // (pcap points: 1 + g rows each)
 }
 
-// the buffers of ascend() (kg1_ascent.hpp) and the one upload; pcap: room for pending points, the first p of them the caller's
-void stage_ascent(Kg1Ensemble& T, const std::vector<GpDev*>& gps, const moe_gd_params_t& outer, const double* domain_bounds,
-                  const double* best_so_far, const double* starts, int S, bool ascent, bool want_path, const double* pending, int p,
-                  int pcap) {
-  check_members(gps, pcap);
-  GpDev& g0 = *gps[0];
-  const int E = (int)gps.size(), W = pcap > 0 ? 2 * E : E, d = g0.d, dp = g0.dp;
-  const int R = std::max(outer.max_num_restarts, 0), Tn = outer.max_num_steps;
-  const int Kmax = ascent ? std::min(S, kMaxKept) : 0;
-  const size_t nBack = (size_t)W + Kmax + S + (size_t)Kmax * dp + (want_path ? (size_t)Kmax * (R * Tn + 1) * d : 0);
-  g0.use_device();
-  g0.kg1oD.reserve(nBack + 2 * (size_t)Kmax * dp);
-  g0.hStateOut.reserve(nBack);
-  // integers behind the failure words: [alive count | steps Kmax | order, running, alive Kmax each]
-  stage(T, gps, best_so_far, domain_bounds, starts, S, ascent && R > 0, 1 + 4 * (size_t)Kmax, pending, p, pcap);
+// every member's extension stands: the believed best takes the caller's p pending points
+void all_extended(Kg1Ensemble& T, int p) { join_believed_best(T, 0, p, true); }
+
+// a pick joins every member's extension, then mu_e(pick) its believed best, both inside device memory
+void pick_appended(Kg1Ensemble& T) {
+  for (Kg1Member& m : T.mem) kg1_pending_append(m, 1, false, T.z);
+  join_believed_best(T, T.p, 1, false);
+}
+
+// No sets and no fidelity coordinates: the upload is [EI pointers E | grad pointers E | bounds 2 d | points C dp | pending points
+// pcap dp]; the extensions of all members first, then their believed bests.
+Kg1Objective objective(const double* best_so_far) {
+  return Kg1Objective{0, nullptr, nullptr, best_so_far, member, ei1_eval_points, nullptr, all_extended, pick_appended};
 }
 
 }  // namespace
@@ -433,29 +358,7 @@ void check_ei_analytic_mcmc_shapes(int num_mcmc, int num_points) {
 void ei_analytic_mcmc_on_device(const std::vector<GpDev*>& gps, const double* best_so_far, const double* pts, int C, bool want_grad,
                                 double* ei_out, double* grad_out, const double* pending, int num_pending) {
   check_members(gps, num_pending);
-  GpDev& g0 = *gps[0];
-  Kg1Ensemble T;
-  const int d = g0.d;
-  const int W = num_pending > 0 ? 2 * (int)gps.size() : (int)gps.size();  // (the failure words in front of the results: Kg1Ensemble::W)
-  // the call's doubles, all of them the copy back: [failure words | EI C | grad C d]
-  const size_t nOut = (size_t)W + (size_t)C * (want_grad ? 1 + d : 1);
-  g0.use_device();
-  g0.kg1oD.reserve(nOut);
-  g0.hStateOut.reserve(nOut);
-  stage(T, gps, best_so_far, nullptr, pts, C, want_grad, 0, pending, num_pending, num_pending);
-  Kg1Recording rec;
-  evaluate(T, rec, T.dPts, T.dPtsH, C, want_grad);
-  double* dOut = g0.kg1oD.p;
-  launch_mean_of_members(T, T.dKgTab, C, dOut + W);
-  if (want_grad) launch_mean_of_members(T, T.dGradTab, (long)C * d, dOut + W + C);
-  MOE_LAUNCH_NOW(kg1_words_kernel, dim3(1), dim3(256), 0, T.z, (const int*)T.iFail, W, dOut);
-  MOE_HIP_CHECK(hipGetLastError());
-  g0.kg1oD.download(g0.hStateOut.p, nOut, T.z);
-  MOE_HIP_CHECK(hipStreamSynchronize(T.z));
-  const double* o = g0.hStateOut.p;
-  throw_if_singular(T, o);
-  std::memcpy(ei_out, o + W, sizeof(double) * (size_t)C);
-  if (want_grad) std::memcpy(grad_out, o + W + C, sizeof(double) * (size_t)C * d);
+  kg1_ensemble_evaluate(objective(best_so_far), gps, pts, C, want_grad, ei_out, grad_out, pending, num_pending);
 }
 
 void ei_analytic_mcmc_multistart(const std::vector<GpDev*>& gps, const moe_gd_params_t& outer, const double* domain_bounds,
@@ -463,33 +366,19 @@ void ei_analytic_mcmc_multistart(const std::vector<GpDev*>& gps, const moe_gd_pa
                                  double* best_point, double* best_value, int* found, double* start_values, int* kept_index,
                                  double* end_points, double* end_values, double* path, int* steps_taken, const double* pending,
                                  int num_pending) {
-  Kg1Ensemble T;
-  const bool ascent = do_gradient_ascent != 0;
-  stage_ascent(T, gps, outer, domain_bounds, best_so_far, starts, num_starts, ascent, ascent && path != nullptr, pending, num_pending,
-               num_pending);
-  ascend(T, outer, starts, num_starts, do_gradient_ascent, best_point, best_value, found, start_values, kept_index, end_points,
-         end_values, path, steps_taken);
+  check_members(gps, num_pending);
+  kg1_ensemble_multistart(objective(best_so_far), gps, outer, domain_bounds, starts, num_starts, do_gradient_ascent, best_point,
+                          best_value, found, start_values, kept_index, end_points, end_values, path, steps_taken, pending, num_pending);
 }
 
-// q points greedily: round t is the ascent above with the caller's pending points and the t points already picked; a round appends
-// one column to every member's extension and one value mu_e(pick) to its believed best, both inside device memory.
+// q points greedily: a round appends one column to every member's extension and one value mu_e(pick) to its believed best.
 void ei_analytic_mcmc_suggest(const std::vector<GpDev*>& gps, const moe_gd_params_t& outer, const double* domain_bounds,
                               const double* best_so_far, const double* starts, int num_starts, int do_gradient_ascent,
                               const double* pending, int num_pending, int num_to_sample, double* best_points, double* best_values,
                               int* found) {
-  Kg1Ensemble T;
-  stage_ascent(T, gps, outer, domain_bounds, best_so_far, starts, num_starts, do_gradient_ascent != 0, false, pending, num_pending,
-               num_pending + num_to_sample - 1);
-  const int d = T.d;
-  for (int t = 0; t < num_to_sample; ++t) {
-    const double* dBest = ascend(T, outer, starts, num_starts, do_gradient_ascent, best_points + (size_t)t * d, best_values + t,
-                                 found + t, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    if (t + 1 == num_to_sample) break;
-    copy_async(T.dPending + (size_t)T.p * T.dp, dBest, sizeof(double) * (size_t)T.dp, hipMemcpyDeviceToDevice, T.z);
-    for (Kg1Member& m : T.mem) kg1_pending_append(m, 1, false, T.z);
-    join_believed_best(T, T.p, 1, false);
-    T.p += 1;
-  }
+  check_members(gps, num_pending + num_to_sample - 1);
+  kg1_ensemble_suggest(objective(best_so_far), gps, outer, domain_bounds, starts, num_starts, do_gradient_ascent, pending, num_pending,
+                       num_to_sample, best_points, best_values, found);
 }
 
 }  // namespace moe

@@ -32,6 +32,13 @@ struct DerivList {
   int g;
   int idx[kMaxDerivs];
 };
+// a point that carries no derivative observations (a candidate is a function value)
+inline DerivList no_derivs() {
+  DerivList d;
+  d.g = 0;
+  for (int i = 0; i < kMaxDerivs; ++i) d.idx[i] = 0;
+  return d;
+}
 
 // out[(i*(1+gA)+a) + (col0 + j*(1+gB)+b) * ld] = cov(A_i, B_j)[a, b]   (BuildMixCovarianceMatrix, gpp_math.cpp:309-335)
 // If diag_noise != nullptr (A == B, gA == gB): adds diag_noise[a] where row == col (gpp_math.cpp:426-455).

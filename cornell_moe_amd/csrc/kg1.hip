@@ -421,13 +421,6 @@ __global__ void kg1_pack_kernel(const int* __restrict__ fail, double* __restrict
   if (threadIdx.x == 0 && blockIdx.x == 0) out[0] = (double)*fail;
 }
 
-DerivList no_derivs() {
-  DerivList d;
-  d.g = 0;
-  for (int i = 0; i < kMaxDerivs; ++i) d.idx[i] = 0;
-  return d;
-}
-
 }  // namespace
 
 // op(L^-1) B for c independent columns, the kernel family fixed by N alone (never by c): below 128 rows the tiled kernel in chunks

@@ -386,13 +386,6 @@ __global__ void lcb_pack_kernel(const int* __restrict__ ints, int n, double* __r
   if (i < n) out[i] = (double)ints[i];
 }
 
-DerivList no_derivs() {
-  DerivList d;
-  d.g = 0;
-  for (int i = 0; i < kMaxDerivs; ++i) d.idx[i] = 0;
-  return d;
-}
-
 // the padded candidates, one copy down; returns their device address
 const double* upload_candidates(GpDev& gp, const double* pts, int C) {
   const size_t nP = (size_t)C * gp.dp;
