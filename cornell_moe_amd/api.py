@@ -1052,6 +1052,95 @@ def ei_analytic_suggest(gps, gd_params, bounds, best_so_far, starts, num_to_samp
     return {"points": points, "values": values, "found": found.astype(bool)}
 
 
+def _gibbon_members(gps, min_values):
+    """(handles, count, dim, members kept alive, min-values [E][K], K) of the ensemble forms of the min-value entropy acquisition; a
+    single DeviceGP counts as a list of one"""
+    if isinstance(gps, DeviceGP):
+        gps = [gps]
+    arr, E, d, keep = _ensemble_handles(gps)
+    mins = np.ascontiguousarray(min_values, dtype=np.float64)
+    if E == 0 or mins.size % E != 0 or (mins.ndim > 1 and mins.shape[0] != E):
+        raise BoundsException("one row of min-values per ensemble member", mins.shape[0] if mins.ndim else 0, E, E)
+    mins = mins.reshape(E, -1)
+    return arr, E, d, keep, mins, mins.shape[1]
+
+
+def gibbon_ensemble(gps, points, min_values, points_being_sampled=None, want_grad=True):
+    """moe_gibbon_mcmc: the min-value entropy acquisition GIBBON (for minimisation) averaged over the ensemble at points [C][dim], in
+    one device call, member e against its samples of the global minimum value min_values[e] ([E][K], 1 <= K <= 1024, all finite:
+    BoundsException(K, 1, 1024), InvalidValueException(value, member, index)).  points_being_sampled [p][dim] (None or empty: none):
+    every member's covariance is conditioned on the pending points and the value gains 1/2 log of the conditioned over the
+    unconditioned predictive variance, the exact greedy increment of GIBBON's batch term.  gps, derivative observations and the row
+    limit as in ei_analytic_ensemble.  Returns value [C], with want_grad (value, grad [C][dim]).  SingularMatrixException(e, j):
+    member e, pending point j; a candidate never raises."""
+    arr, E, d, keep, mins, K = _gibbon_members(gps, min_values)
+    pts, pp = _d(points)
+    C_ = pts.reshape(-1, d).shape[0]
+    value = np.zeros(max(C_, 1))
+    grad = np.zeros((max(C_, 1), d)) if want_grad else None
+    p = _num_pending(points_being_sampled, d)
+    pend, pendp = _d(points_being_sampled) if p else (None, None)
+    err = _lib.MoeError()
+    _check(_lib.load().moe_gibbon_mcmc(arr, E, mins.ctypes.data_as(dp), K, pendp, p, pp, C_, 1 if want_grad else 0,
+                                       value.ctypes.data_as(dp), grad.ctypes.data_as(dp) if want_grad else None, C.byref(err)), err)
+    return (value, grad) if want_grad else value
+
+
+def gibbon_multistart(gps, gd_params, bounds, min_values, starts, gradient_ascent=True, want_path=False, points_being_sampled=None):
+    """moe_gibbon_mcmc_multistart: one suggestion by the ensemble-averaged min-value entropy acquisition -- ei_analytic_multistart's
+    screening, kept starts, restarted ascent on the device and end-point selection, and its dict."""
+    arr, E, d, keep, mins, Kmin = _gibbon_members(gps, min_values)
+    g = DeviceGP._gd(gd_params)
+    bounds, bp = _d(bounds)
+    starts, sp = _d(starts)
+    S = starts.reshape(-1, d).shape[0]
+    K = max(min(S, 20), 1)
+    rows = max(g.max_num_restarts, 0) * max(g.max_num_steps, 0) + 1
+    point = np.zeros(d)
+    start_values = np.zeros(max(S, 1))
+    kept = np.zeros(K, dtype=np.int32)
+    ends, end_values = np.zeros((K, d)), np.zeros(K)
+    steps = np.zeros(K, dtype=np.int32)
+    path = np.zeros((K, rows, d)) if (want_path and gradient_ascent) else None
+    value, found = C.c_double(0.0), C.c_int(0)
+    p = _num_pending(points_being_sampled, d)
+    pend, pendp = _d(points_being_sampled) if p else (None, None)
+    err = _lib.MoeError()
+    _check(_lib.load().moe_gibbon_mcmc_multistart(
+        arr, E, C.byref(g), bp, mins.ctypes.data_as(dp), Kmin, pendp, p, sp, S, 1 if gradient_ascent else 0, point.ctypes.data_as(dp),
+        C.byref(value), C.byref(found), start_values.ctypes.data_as(dp), kept.ctypes.data_as(ip), ends.ctypes.data_as(dp),
+        end_values.ctypes.data_as(dp), path.ctypes.data_as(dp) if path is not None else None, steps.ctypes.data_as(ip), C.byref(err)),
+        err)
+    out = {"point": point, "value": value.value, "found": bool(found.value), "start_values": start_values,
+           "kept_index": kept if gradient_ascent else None, "end_points": ends if gradient_ascent else None,
+           "end_values": end_values if gradient_ascent else None, "steps_taken": steps if gradient_ascent else None}
+    if want_path:
+        out["path"] = path
+    return out
+
+
+def gibbon_suggest(gps, gd_params, bounds, min_values, starts, num_to_sample, gradient_ascent=True, points_being_sampled=None):
+    """moe_gibbon_mcmc_suggest: num_to_sample points greedily by the ensemble-averaged min-value entropy acquisition -- round t is
+    gibbon_multistart from the same starts [S][dim] with the pending points points_being_sampled [p][dim] (may be None) followed by
+    the points of the rounds before, bit for bit, in one device call; the limits of ei_analytic_suggest.  Returns a dict: points
+    [q][dim], values [q], found [q]."""
+    arr, E, d, keep, mins, Kmin = _gibbon_members(gps, min_values)
+    g = DeviceGP._gd(gd_params)
+    bounds, bp = _d(bounds)
+    starts, sp = _d(starts)
+    S = starts.reshape(-1, d).shape[0]
+    q = int(num_to_sample)
+    p = _num_pending(points_being_sampled, d)
+    pend, pendp = _d(points_being_sampled) if p else (None, None)
+    points, values = np.zeros((max(q, 1), d)), np.zeros(max(q, 1))
+    found = np.zeros(max(q, 1), dtype=np.int32)
+    err = _lib.MoeError()
+    _check(_lib.load().moe_gibbon_mcmc_suggest(
+        arr, E, C.byref(g), bp, mins.ctypes.data_as(dp), Kmin, pendp, p, sp, S, 1 if gradient_ascent else 0, q,
+        points.ctypes.data_as(dp), values.ctypes.data_as(dp), found.ctypes.data_as(ip), C.byref(err)), err)
+    return {"points": points, "values": values, "found": found.astype(bool)}
+
+
 def recommend(gps, candidates, gd_params, domain_bounds, num_fidelity=0, num_starts=1, want_values=False, want_path=False):
     """moe_posterior_mean_mcmc_recommend: screen the candidates [C][dim - num_fidelity] on the ensemble-averaged posterior mean,
     descend from the num_starts best (the reference's Python gradient descent, on the device), keep the screened candidate unless

@@ -60,7 +60,7 @@ moe::GpDev& lock_gp(const moe_gp_t* gp_c, std::unique_lock<std::mutex>& lk) {
   return gp->dev;
 }
 
-// The preamble of the ensemble one-point acquisitions' entry points (moe_kg_discrete_mcmc*, moe_ei_analytic_mcmc*).
+// The preamble of the ensemble one-point acquisitions' entry points (moe_kg_discrete_mcmc*, moe_ei_analytic_mcmc*, moe_gibbon_mcmc*).
 void check_num_mcmc(int num_mcmc) {
   if (num_mcmc < 1 || num_mcmc > 1024) throw moe::Error(MOE_ERR_BOUNDS, "num_mcmc must be between 1 and 1024", num_mcmc, 1, 1024);
 }
@@ -968,6 +968,60 @@ int moe_ei_analytic_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, const
     const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
     moe::ei_analytic_mcmc_suggest(v, *outer, domain_bounds, best_so_far, starts, num_starts, do_gradient_ascent, points_being_sampled,
                                   num_being_sampled, num_to_sample, best_points, best_values, found);
+  });
+}
+
+int moe_gibbon_mcmc(const moe_gp_t* const* gps, int num_mcmc, const double* min_values, int num_min_values,
+                    const double* points_being_sampled, int num_being_sampled, const double* points, int num_points, int want_grad,
+                    double* value, double* grad, moe_error_t* err) {
+  return guarded(err, [&] {
+    check_num_mcmc(num_mcmc);
+    require(gps && min_values && points && value && (want_grad == 0 || grad), "NULL argument");
+    moe::check_gibbon_min_values(min_values, num_mcmc, num_min_values);  // (what needs no handle)
+    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_points);
+    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, 1);
+    const auto locks = lock_ensemble(gps, num_mcmc);
+    const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
+    moe::gibbon_mcmc_on_device(v, min_values, num_min_values, points, num_points, want_grad != 0, value, grad, points_being_sampled,
+                               num_being_sampled);
+  });
+}
+
+int moe_gibbon_mcmc_multistart(const moe_gp_t* const* gps, int num_mcmc, const moe_gd_params_t* outer, const double* domain_bounds,
+                               const double* min_values, int num_min_values, const double* points_being_sampled,
+                               int num_being_sampled, const double* starts, int num_starts, int do_gradient_ascent,
+                               double* best_point, double* best_value, int* found, double* start_values, int* kept_index,
+                               double* end_points, double* end_values, double* path, int* steps_taken, moe_error_t* err) {
+  return guarded(err, [&] {
+    check_num_mcmc(num_mcmc);
+    require(gps && outer && domain_bounds && min_values && starts && best_point && best_value && found, "NULL argument");
+    moe::check_gibbon_min_values(min_values, num_mcmc, num_min_values);
+    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_starts);
+    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, 1);
+    check_ascent_params(outer, do_gradient_ascent, "the min-value entropy acquisition");
+    const auto locks = lock_ensemble(gps, num_mcmc);
+    const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
+    moe::gibbon_mcmc_multistart(v, *outer, domain_bounds, min_values, num_min_values, starts, num_starts, do_gradient_ascent,
+                                best_point, best_value, found, start_values, kept_index, end_points, end_values, path, steps_taken,
+                                points_being_sampled, num_being_sampled);
+  });
+}
+
+int moe_gibbon_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, const moe_gd_params_t* outer, const double* domain_bounds,
+                            const double* min_values, int num_min_values, const double* points_being_sampled, int num_being_sampled,
+                            const double* starts, int num_starts, int do_gradient_ascent, int num_to_sample, double* best_points,
+                            double* best_values, int* found, moe_error_t* err) {
+  return guarded(err, [&] {
+    check_num_mcmc(num_mcmc);
+    require(gps && outer && domain_bounds && min_values && starts && best_points && best_values && found, "NULL argument");
+    moe::check_gibbon_min_values(min_values, num_mcmc, num_min_values);
+    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_starts);
+    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, num_to_sample);
+    check_ascent_params(outer, do_gradient_ascent, "the min-value entropy acquisition");
+    const auto locks = lock_ensemble(gps, num_mcmc);
+    const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
+    moe::gibbon_mcmc_suggest(v, *outer, domain_bounds, min_values, num_min_values, starts, num_starts, do_gradient_ascent,
+                             points_being_sampled, num_being_sampled, num_to_sample, best_points, best_values, found);
   });
 }
 

@@ -3,7 +3,8 @@
 // batches, on the device (moe_ei_analytic_mcmc, moe_ei_analytic_mcmc_multistart, moe_ei_analytic_mcmc_suggest): the EI twin of
 // kg1_opt.hip.  The staging, the ascent and the drivers of the three entry points are the shared ones of kg1_ascent.hip (declared in
 // kg1_ascent.hpp), the pending-row extension is kg1_pending.hip's; this file keeps the kernels, a member's layout and chain, the
-// believed best, the row bound and the description of the objective.
+// believed best, the row bound and the description of the objective, and lends the layout, the members' check and the gradient's tail
+// to gibbon1.hip (ei1.hpp).
 //
 // Member e: posterior mean mu_e, posterior covariance of the latent function conditioned on the pending points P with the member's
 // noise on P's diagonal (the Kriging-believer fantasy: the mean is left alone), believed best b'_e = min(b_e, min_j mu_e(P_j)).  With
@@ -42,6 +43,7 @@
 #include <cfloat>
 
 #include "device_cov.hpp"
+#include "ei1.hpp"
 #include "kg1_ascent.hpp"
 
 namespace moe {
@@ -211,6 +213,8 @@ __global__ __launch_bounds__(256) void ei1_grad_g_kernel(int P, int ld, int d, i
   ei1_grad_g_kernel_body<DP>::run(MOE_VBLOCK, MOE_VGRID, nullptr, P, ld, d, col0, cp, dl, X, kinvy, Px, U, cdf, grad);
 }
 
+}  // namespace
+
 // Where one GP's per-pass scratch and results live for a call of at most C candidates, inside the GP's own kg1D (results first:
 // [EI C | grad C d]), dE and dEK: Kg1Member with an empty set (A = 0; dAA holds mu(P), dScal Phi(c_g), dMuh mu(x)).  pcap: room
 // for that many extension ROWS, a multiple of 1 + g.
@@ -254,24 +258,12 @@ Kg1Member ei1_member(GpDev& gp, int C, double best, bool with_grad, int* fail, i
   return m;
 }
 
-void ei1_eval_pass(const Kg1Member& m, const double* Px, int nc, int c0, bool with_grad, hipStream_t s) {
+void ei1_grad_tail(const Kg1Member& m, const double* Px, int nc, int c0, hipStream_t s) {
   GpDev& gp = *m.gp;
-  if (nc < 1 || nc > m.widest || c0 < 0 || c0 + nc > m.C || (with_grad && !m.with_grad))
-    throw Error(MOE_ERR_RUNTIME, "ei1_eval_pass: the pass does not fit the member's buffers");
-  const int N = gp.N, n = gp.n, d = gp.d, dp = gp.dp, R = N + m.p, ld = m.ld;
+  const int n = gp.n, d = gp.d, dp = gp.dp, R = gp.N + m.p, ld = m.ld;
   const double* Xr = m.p > 0 ? m.dXe : gp.dX.p;
   const double* Kr = m.p > 0 ? m.dKe : gp.dKinvY.p;
-  const DerivList none = no_derivs();  // (the candidate is a function value)
   const dim3 b256(256);
-  launch_cov_build(gp.cp, gp.dX.p, n, gp.derivs, Px, nc, none, nullptr, gp.dE.p, N, 0, s);
-  tri_cols(gp, 'N', nc, gp.dE.p, N, m.dVx, ld, s);
-  launch_mean(gp.cp, gp.dX.p, n, gp.derivs, gp.dKinvY.p, Px, nc, gp.mean, false, m.dMuh, s);
-  if (m.p > 0) kg1_pending_rows(m, Px, m.dVx, nc, 0, m.p, s);
-  launch_kernel_ens<ei1_cand_kernel_body, 256>(ei1_cand_kernel, dim3((unsigned)((nc + 3) / 4)), b256, 0, s, R, ld, nc, c0, gp.cp,
-                                               with_grad ? 1 : 0, (const double*)m.dBp, (const double*)m.dMuh, (const double*)m.dVx,
-                                               m.dKg, m.dScal, m.dT);
-  MOE_HIP_CHECK(hipGetLastError());
-  if (!with_grad) return;
   if (m.p > 0) kg1_pending_back(m, nc, s);  // (L'^-T: the pending block first, then the member's own on the corrected rows)
   tri_cols(gp, 'T', nc, m.dT, ld, m.dU, ld, s);
   dispatch_dp(dp, [&](auto DP) {
@@ -286,30 +278,41 @@ void ei1_eval_pass(const Kg1Member& m, const double* Px, int nc, int c0, bool wi
   MOE_HIP_CHECK(hipGetLastError());
 }
 
+namespace {
+
+void ei1_eval_pass(const Kg1Member& m, const double* Px, int nc, int c0, bool with_grad, hipStream_t s) {
+  GpDev& gp = *m.gp;
+  if (nc < 1 || nc > m.widest || c0 < 0 || c0 + nc > m.C || (with_grad && !m.with_grad))
+    throw Error(MOE_ERR_RUNTIME, "ei1_eval_pass: the pass does not fit the member's buffers");
+  const int N = gp.N, n = gp.n, R = N + m.p, ld = m.ld;
+  const DerivList none = no_derivs();  // (the candidate is a function value)
+  const dim3 b256(256);
+  launch_cov_build(gp.cp, gp.dX.p, n, gp.derivs, Px, nc, none, nullptr, gp.dE.p, N, 0, s);
+  tri_cols(gp, 'N', nc, gp.dE.p, N, m.dVx, ld, s);
+  launch_mean(gp.cp, gp.dX.p, n, gp.derivs, gp.dKinvY.p, Px, nc, gp.mean, false, m.dMuh, s);
+  if (m.p > 0) kg1_pending_rows(m, Px, m.dVx, nc, 0, m.p, s);
+  launch_kernel_ens<ei1_cand_kernel_body, 256>(ei1_cand_kernel, dim3((unsigned)((nc + 3) / 4)), b256, 0, s, R, ld, nc, c0, gp.cp,
+                                               with_grad ? 1 : 0, (const double*)m.dBp, (const double*)m.dMuh, (const double*)m.dVx,
+                                               m.dKg, m.dScal, m.dT);
+  MOE_HIP_CHECK(hipGetLastError());
+  if (!with_grad) return;
+  ei1_grad_tail(m, Px, nc, c0, s);
+}
+
 // (Ph: the staging's second view of the points, the same as Px where there are no fidelity coordinates)
 void ei1_eval_points(const Kg1Member& m, const double* Px, const double*, int C, bool with_grad, hipStream_t s) {
   const int dp = m.gp->dp;
   for (int c0 = 0; c0 < C; c0 += m.per_pass) ei1_eval_pass(m, Px + (size_t)c0 * dp, std::min(m.per_pass, C - c0), c0, with_grad, s);
 }
 
-// the members' own check (kg1_ascent.hpp: kg1_check_members), then the room for pending_room pending points (the caller's and a
-// greedy batch's picks)
+// the members' own check (kg1_ascent.hpp: kg1_check_members); ei1_check_members adds the room for pending_room pending points (the
+// caller's and a greedy batch's picks)
 void check_member(const GpDev& g, const GpDev& g0, size_t e, int) {
   if (g.g != g0.g || !std::equal(g.derivs.idx, g.derivs.idx + g.g, g0.derivs.idx))
     throw Error(MOE_ERR_INVALID_VALUE,
                 "MCMC ensemble members must share the observed-derivative list: a pending experiment observes the same derivatives "
                 "under every member",
                 g.g, g0.g, (double)e);
-}
-
-void check_members(const std::vector<GpDev*>& gps, int pending_room) {
-  kg1_check_members(gps, 0, check_member);
-  const int g1 = 1 + gps[0]->g;
-  if ((long)pending_room * g1 > kKg1MaxPending)
-    throw Error(MOE_ERR_BOUNDS,
-                "pending points (num_being_sampled + num_to_sample - 1) times (1 + num_derivatives) believed observations each "
-                "must fit 64 extension rows",
-                pending_room, 0, kKg1MaxPending / g1);
 }
 
 // mu(P_j0 .. j0 + count - 1), the function values alone, and their part in b' for every member
@@ -339,10 +342,20 @@ void pick_appended(Kg1Ensemble& T) {
 // No sets and no fidelity coordinates: the upload is [EI pointers E | grad pointers E | bounds 2 d | points C dp | pending points
 // pcap dp]; the extensions of all members first, then their believed bests.
 Kg1Objective objective(const double* best_so_far) {
-  return Kg1Objective{0, nullptr, nullptr, best_so_far, member, ei1_eval_points, nullptr, all_extended, pick_appended};
+  return Kg1Objective{0, nullptr, nullptr, best_so_far, member, ei1_eval_points, nullptr, all_extended, pick_appended, nullptr, 0};
 }
 
 }  // namespace
+
+void ei1_check_members(const std::vector<GpDev*>& gps, int pending_room) {
+  kg1_check_members(gps, 0, check_member);
+  const int g1 = 1 + gps[0]->g;
+  if ((long)pending_room * g1 > kKg1MaxPending)
+    throw Error(MOE_ERR_BOUNDS,
+                "pending points (num_being_sampled + num_to_sample - 1) times (1 + num_derivatives) believed observations each "
+                "must fit 64 extension rows",
+                pending_room, 0, kKg1MaxPending / g1);
+}
 
 // Candidates per pass, from N alone: a pass's columns of V stay within 2^24 doubles, a multiple of 64 between 64 and 4096.
 int ei1_pass_size(int N) {
@@ -357,7 +370,7 @@ void check_ei_analytic_mcmc_shapes(int num_mcmc, int num_points) {
 
 void ei_analytic_mcmc_on_device(const std::vector<GpDev*>& gps, const double* best_so_far, const double* pts, int C, bool want_grad,
                                 double* ei_out, double* grad_out, const double* pending, int num_pending) {
-  check_members(gps, num_pending);
+  ei1_check_members(gps, num_pending);
   kg1_ensemble_evaluate(objective(best_so_far), gps, pts, C, want_grad, ei_out, grad_out, pending, num_pending);
 }
 
@@ -366,7 +379,7 @@ void ei_analytic_mcmc_multistart(const std::vector<GpDev*>& gps, const moe_gd_pa
                                  double* best_point, double* best_value, int* found, double* start_values, int* kept_index,
                                  double* end_points, double* end_values, double* path, int* steps_taken, const double* pending,
                                  int num_pending) {
-  check_members(gps, num_pending);
+  ei1_check_members(gps, num_pending);
   kg1_ensemble_multistart(objective(best_so_far), gps, outer, domain_bounds, starts, num_starts, do_gradient_ascent, best_point,
                           best_value, found, start_values, kept_index, end_points, end_values, path, steps_taken, pending, num_pending);
 }
@@ -376,7 +389,7 @@ void ei_analytic_mcmc_suggest(const std::vector<GpDev*>& gps, const moe_gd_param
                               const double* best_so_far, const double* starts, int num_starts, int do_gradient_ascent,
                               const double* pending, int num_pending, int num_to_sample, double* best_points, double* best_values,
                               int* found) {
-  check_members(gps, num_pending + num_to_sample - 1);
+  ei1_check_members(gps, num_pending + num_to_sample - 1);
   kg1_ensemble_suggest(objective(best_so_far), gps, outer, domain_bounds, starts, num_starts, do_gradient_ascent, pending, num_pending,
                        num_to_sample, best_points, best_values, found);
 }

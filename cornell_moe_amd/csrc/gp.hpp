@@ -250,6 +250,8 @@ struct Kg1Member {
   double* dVP = nullptr;        // column j [ld]: L^-1 k(X, P_j), then row j of L_P with its diagonal
   int* iFailP = nullptr;        // the first pending point whose Schur pivot fails the pivot rule
   double* dBp = nullptr;        // ei1.hip: the member's believed best b' = min(best, min_j mu(P_j)), in device memory
+  const double* dExtra = nullptr;  // the objective's per-member block of the upload (gibbon1.hip: the member's min-values), [nExtra]
+  int nExtra = 0;
   size_t out_doubles() const { return 1 + 2 * (size_t)C + (with_grad ? (size_t)C * gp->d : 0); }
 };
 // the handle's checks of moe_gp_kg_discrete (num_fidelity < dim, no derivative observations), the buffers and their layout; nothing
@@ -322,6 +324,23 @@ void ei_analytic_mcmc_suggest(const std::vector<GpDev*>& gps, const moe_gd_param
                               const double* best_so_far, const double* starts, int num_starts, int do_gradient_ascent,
                               const double* pending, int num_pending, int num_to_sample, double* best_points, double* best_values,
                               int* found);
+// gibbon1.hip: the min-value entropy acquisition GIBBON averaged over an ensemble (moe_gibbon_mcmc), its multistart ascent
+// (moe_gibbon_mcmc_multistart) and greedy batches (moe_gibbon_mcmc_suggest): ei1.hip's three with the members' samples of the
+// minimum value min_values [E][num_min_values] in the place of best_so_far; the same pending points, passes, derivative-observing
+// members and row limit.  check_gibbon_min_values: what needs no handle (the count, then every value finite).
+constexpr int kGibbonMaxMinValues = 1024;
+void check_gibbon_min_values(const double* min_values, int num_mcmc, int num_min_values);
+void gibbon_mcmc_on_device(const std::vector<GpDev*>& gps, const double* min_values, int num_min_values, const double* pts, int C,
+                           bool want_grad, double* value_out, double* grad_out, const double* pending, int num_pending);
+void gibbon_mcmc_multistart(const std::vector<GpDev*>& gps, const moe_gd_params_t& outer, const double* domain_bounds,
+                            const double* min_values, int num_min_values, const double* starts, int num_starts, int do_gradient_ascent,
+                            double* best_point, double* best_value, int* found, double* start_values, int* kept_index,
+                            double* end_points, double* end_values, double* path, int* steps_taken, const double* pending,
+                            int num_pending);
+void gibbon_mcmc_suggest(const std::vector<GpDev*>& gps, const moe_gd_params_t& outer, const double* domain_bounds,
+                         const double* min_values, int num_min_values, const double* starts, int num_starts, int do_gradient_ascent,
+                         const double* pending, int num_pending, int num_to_sample, double* best_points, double* best_values,
+                         int* found);
 // loo.hip: leave-one-out cross-validation on the GP's current factorisation, every one of the N = n (1 + g) scalar observations left
 // out by itself.  mean_out / var_out [n][1 + g]: the LOO predictive mean (function values in the caller's units) and variance.
 void loo_predict_on_device(GpDev& gp, double* mean_out, double* var_out);

@@ -1,5 +1,5 @@
 // cornell_moe_amd/csrc/kg1_ascent.hip -- what the ensemble forms of the one-point acquisition functions share (kg1_opt.hip: the
-// discretised knowledge gradient; ei1.hip: the analytic expected improvement), compiled once: the ensemble mean, the multistart
+// discretised knowledge gradient; ei1.hip: the analytic expected improvement; gibbon1.hip: the min-value entropy acquisition), compiled once: the ensemble mean, the multistart
 // ascent's gather, step and round kernels, the recorded and zipped evaluation of the members' chains, the ascent itself (ascend()),
 // the staging of a call (stage(), stage_ascent()) and the three drivers behind the entry points (kg1_ascent.hpp).  None of it knows
 // the objective: a Kg1Objective says how a member is built, which chain evaluates it and what follows its extension.
@@ -206,9 +206,9 @@ void throw_if_singular(const Kg1Ensemble& T, const Word* fail_words) {
 
 // The members' layouts and the one upload:
 //   [value pointers E | grad pointers E | bounds 2 d | set of member 0 .. E - 1, padded | points C dp | the same, fidelity 1 (fid) |
-//    pending points pcap dp]
-// (an objective without sets and fidelity coordinates leaves those sections empty); then every member's extension by the first p
-// pending points and what the objective runs behind it.  extra_ints: integers of the caller behind the W failure words in the first
+//    pending points pcap dp | the members' extra doubles E num_member_extra]
+// (an objective without sets, fidelity coordinates or extra doubles leaves those sections empty); then every member's extension by
+// the first p pending points and what the objective runs behind it.  extra_ints: integers of the caller behind the W failure words in the first
 // member's kg1oI.
 void stage(Kg1Ensemble& T, const Kg1Objective& o, const double* bounds, const double* pts, int C, bool with_grad, size_t extra_ints,
            const double* pending, int p) {
@@ -222,7 +222,8 @@ void stage(Kg1Ensemble& T, const Kg1Objective& o, const double* bounds, const do
   for (int e = 0; e < E && num_discrete != nullptr; ++e) nSets += (size_t)num_discrete[e];
   const size_t nC = (size_t)C, oBounds = 2 * (size_t)E, oSets = oBounds + 2 * (size_t)d, oPts = oSets + nSets * dp;
   const size_t oPend = oPts + nC * dp * (T.fid ? 2 : 1);
-  const size_t nIn = oPend + (size_t)pcap * dp;
+  const size_t nX = o.member_extra != nullptr ? (size_t)o.num_member_extra : 0, oExtra = oPend + (size_t)pcap * dp;
+  const size_t nIn = oExtra + (size_t)E * nX;
   g0.hStateIn.reserve(nIn);
   g0.dStateIn.reserve(nIn);
   T.mem.clear();
@@ -252,6 +253,11 @@ void stage(Kg1Ensemble& T, const Kg1Objective& o, const double* bounds, const do
     }
   for (size_t i = 0; i < (size_t)pcap; ++i)  // (the pending points as given, fidelity coordinates included; the rest joins on the device)
     for (int k = 0; k < dp; ++k) h[oPend + i * dp + k] = (i < (size_t)p && k < d) ? pending[i * d + k] : 0.0;
+  if (nX > 0) std::memcpy(h + oExtra, o.member_extra, sizeof(double) * (size_t)E * nX);
+  for (int e = 0; e < E && nX > 0; ++e) {
+    T.mem[e].dExtra = dIn + oExtra + (size_t)e * nX;
+    T.mem[e].nExtra = (int)nX;
+  }
   g0.dStateIn.upload(h, nIn, T.z, true);
   T.dPending = g0.dStateIn.p + oPend;
   T.dKgTab = reinterpret_cast<const double* const*>(dIn);

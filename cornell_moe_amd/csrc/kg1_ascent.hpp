@@ -1,5 +1,5 @@
 // cornell_moe_amd/csrc/kg1_ascent.hpp -- what the ensemble forms of the one-point acquisition functions share (kg1_opt.hip: the
-// discretised knowledge gradient; ei1.hip: the analytic expected improvement), declared here and compiled once in kg1_ascent.hip:
+// discretised knowledge gradient; ei1.hip: the analytic expected improvement; gibbon1.hip: the min-value entropy acquisition), declared here and compiled once in kg1_ascent.hip:
 // the members' common checks, the staging of a call, the ensemble mean, the multistart ascent and the drivers behind the three
 // shapes of entry point (evaluate at points, multistart, greedy batch).  None of it knows the objective: kg1_opt.hip and ei1.hip
 // each describe theirs in a Kg1Objective.
@@ -48,7 +48,8 @@ struct Kg1Ensemble {
   Kg1AscentSizes sz = {};
 };
 
-// An objective as the staging and the drivers see it (the hooks but `member`, `eval_points` and `pick_appended` may be NULL).
+// An objective as the staging and the drivers see it (the hooks but `member`, `eval_points` and `pick_appended` may be NULL; the
+// third client is gibbon1.hip: the min-value entropy acquisition).
 struct Kg1Objective {
   int nf;                      // fidelity coordinates (0: one view of the points)
   const double* discrete_all;  // the members' discrete sets back to back [sum A_e][d - nf]; NULL: the objective has none
@@ -64,6 +65,10 @@ struct Kg1Objective {
   void (*all_extended)(Kg1Ensemble& T, int p);
   // a greedy batch has written its pick to row T.p of T.dPending: every member's extension takes it (T.p is raised afterwards)
   void (*pick_appended)(Kg1Ensemble& T);
+  // num_member_extra doubles per member that travel in the call's one upload, behind the pending points: [E][num_member_extra];
+  // member e's reach it as Kg1Member::dExtra / nExtra.  NULL: the objective has none and the upload is laid out without the block.
+  const double* member_extra;
+  int num_member_extra;
 };
 
 // One dim, one device, no member listed twice (MOE_ERR_INVALID_VALUE), behind num_fidelity < dim (MOE_ERR_BOUNDS); check_member:

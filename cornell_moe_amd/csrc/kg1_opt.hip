@@ -45,7 +45,7 @@ void pick_appended(Kg1Ensemble& T) {
 
 // (begin -> append -> the set phase, member after member; nothing left once every extension stands)
 Kg1Objective objective(int nf, const double* discrete_all, const int* num_discrete, const double* best_so_far) {
-  return Kg1Objective{nf, discrete_all, num_discrete, best_so_far, member, kg1_eval_points, kg1_prepare_set, nullptr, pick_appended};
+  return Kg1Objective{nf, discrete_all, num_discrete, best_so_far, member, kg1_eval_points, kg1_prepare_set, nullptr, pick_appended, nullptr, 0};
 }
 
 }  // namespace

@@ -403,6 +403,61 @@ int moe_ei_analytic_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, const
                                  const double* best_so_far, const double* points_being_sampled, int num_being_sampled,
                                  const double* starts, int num_starts, int do_gradient_ascent, int num_to_sample, double* best_points,
                                  double* best_values, int* found, moe_error_t* err);
+/* The min-value entropy acquisition GIBBON (Moss, Leslie, Gonzalez & Rayson, JMLR 2021: max-value entropy search, Wang & Jegelka
+ * 2017, made right under observation noise and for batches) for minimisation, averaged over an ensemble of num_mcmc GPs, with
+ * pending points, evaluated on the device: value[i] and grad[i][dim] (want_grad != 0) at points [num_points][dim].  Member e has
+ * posterior mean mu_e, noise sigma^2 = noise_variance[0] and the caller's samples of the global minimum VALUE m_k = min_values[e][k],
+ * k < num_min_values (for instance the minima of joint posterior draws at a candidate set, moe_gp_sample_points: an upper bound of the
+ * domain minimum that tightens with the set).  Its covariance is conditioned on points_being_sampled as in moe_ei_analytic_mcmc, word
+ * for word (the member's noise on their diagonal, the mean left alone, 1 + g rows per point under derivative observations).  With
+ * var0 = k(x, x) - v_x . v_x the unconditioned and varc = var0 - r_x . r_x the conditioned variance of the latent function:
+ *   s0 = max(DBL_MIN, var0),  sc = max(DBL_MIN, varc),  sigma0 = sqrt(s0),  rho^2 = s0 / (s0 + sigma^2),  gamma_k = (mu_e(x) - m_k) / sigma0
+ *   r(gamma) = phi(gamma) / Phi(gamma) = sqrt(2 / pi) / erfcx(-gamma / sqrt 2),   q_k = clamp(r_k (gamma_k + r_k), 0, 1)
+ *   G_k = -1/2 log1p(-min(rho^2 q_k, 1 - DBL_EPSILON))
+ *   alpha_e = [num_being_sampled > 0] 1/2 (log(sc + sigma^2) - log(s0 + sigma^2)) + (1 / num_min_values) sum_k G_k
+ *   value[i] = (alpha_0 + ... + alpha_{E-1}) / E,  grad likewise: the members added in member order and divided once.
+ * 1 - rho^2 q is Var(y | f >= m) / Var(y) of the noisy observation; the bracket is the exact greedy increment of GIBBON's batch term
+ * 1/2 log |R_B| (R: the correlation matrix of the batch's noisy predictive outputs), (varc + sigma^2) / (var0 + sigma^2) being the
+ * Schur complement of x over its marginal.  It tends to -infinity at a noise-free pending point: unlike plain max-value entropy
+ * search, whose value depends on gamma alone, a greedy batch does not re-pick its own point.  gamma and rho^2 take the unconditioned
+ * moments and the min-values stay fixed over the batch.
+ * The gradient is unclamped, P and m do not move with x, and max(150 eps^2, .) replaces both floors in its denominators and in the
+ * gamma and rho^2 of its factors (moe_ei_analytic_mcmc's second floor); it costs one transposed triangular product with ONE column per
+ * candidate, the kernels being moe_ei_analytic_mcmc's.
+ * Bits as in moe_ei_analytic_mcmc: a candidate's do not depend on how many share the call (passes of moe_ei1_pass_size(N)), on
+ * want_grad or on ensemble-wide launches; the ensemble's result is the members' own added on the host in member order; the terms
+ * are added in a fixed shape (lane l of 64 takes k = l, l + 64, ..., then a butterfly).  The min-values travel in the call's one
+ * upload.  One copy down, one stream, one wait, one copy back; no handle is modified.
+ * Errors, in this order, everything that needs no handle before a handle or the device is touched: num_mcmc outside 1 .. 1024 ->
+ * MOE_ERR_BOUNDS; a NULL array (gps, min_values, points, value, grad with want_grad) -> MOE_ERR_RUNTIME; num_min_values outside
+ * 1 .. 1024 -> MOE_ERR_BOUNDS, payload (num_min_values, 1, 1024); a min-value that is not finite -> MOE_ERR_INVALID_VALUE, payload
+ * (the value, member, index); then moe_ei_analytic_mcmc's from num_points < 1 on, in its order and with its payloads, the row limit
+ * num_being_sampled (1 + g) <= 64 last.  MOE_ERR_SINGULAR only for a pending point, payload (e, j), after the wait; a candidate
+ * never raises. */
+int moe_gibbon_mcmc(const moe_gp_t* const* gps, int num_mcmc, const double* min_values, int num_min_values,
+                    const double* points_being_sampled, int num_being_sampled, const double* points, int num_points, int want_grad,
+                    double* value, double* grad, moe_error_t* err);
+/* One suggestion by moe_gibbon_mcmc's objective, the whole loop on the device: moe_ei_analytic_mcmc_multistart's screening, top-20
+ * rule, restarted ascent and end-point selection, its outputs and their meaning (the kernels of the ascent are shared), so that the
+ * path is, bit for bit, the one a host loop over moe_gibbon_mcmc walks.
+ * Errors, in this order: those of moe_gibbon_mcmc that need no handle (outer, domain_bounds, starts, best_point, best_value and found
+ * among the arrays that must not be NULL; num_starts for num_points); max_num_steps < 1 with do_gradient_ascent != 0 ->
+ * MOE_ERR_BOUNDS; domain_type other than MOE_DOMAIN_TENSOR_PRODUCT -> MOE_ERR_INVALID_VALUE; then those that need the handles.
+ * MOE_ERR_SINGULAR as above, at the next wait. */
+int moe_gibbon_mcmc_multistart(const moe_gp_t* const* gps, int num_mcmc, const moe_gd_params_t* outer, const double* domain_bounds,
+                               const double* min_values, int num_min_values, const double* points_being_sampled,
+                               int num_being_sampled, const double* starts, int num_starts, int do_gradient_ascent,
+                               double* best_point, double* best_value, int* found, double* start_values, int* kept_index,
+                               double* end_points, double* end_values, double* path, int* steps_taken, moe_error_t* err);
+/* num_to_sample points greedily: round t is moe_gibbon_mcmc_multistart from the same starts with pending points =
+ * points_being_sampled followed by the picks of the rounds before -- bit for bit what num_to_sample calls of that function return
+ * when each is fed its predecessors' points; the sum of the rounds' brackets is GIBBON's batch term.  Staged once; a round appends
+ * ONE point (1 + g rows) to each member's extension inside device memory.
+ * Errors: those of moe_gibbon_mcmc_multistart with moe_ei_analytic_mcmc_suggest's additions (num_to_sample, the row limit). */
+int moe_gibbon_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, const moe_gd_params_t* outer, const double* domain_bounds,
+                            const double* min_values, int num_min_values, const double* points_being_sampled, int num_being_sampled,
+                            const double* starts, int num_starts, int do_gradient_ascent, int num_to_sample, double* best_points,
+                            double* best_values, int* found, moe_error_t* err);
 /* compute_grad_variance_of_points -> ComputeGradVarianceOfPoints (gpp_math.cpp:1359-1373); out[num_derivs][m][m][dim] */
 int moe_gp_grad_variance(const moe_gp_t* gp, const double* pts, int num_pts, int num_derivs, double* out, moe_error_t* err);
 /* compute_grad_cholesky_variance_of_points -> ComputeGradCholeskyVarianceOfPoints (gpp_math.cpp:1454-1474) */
