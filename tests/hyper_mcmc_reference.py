@@ -181,6 +181,19 @@ CASES = [
     ("fixed_noise_40_3_0", 1, 40, 3, 0, "fixed_noise", True, None, 10, 109),
     ("tophat_wall_12_2_0", 1, 12, 2, 0, "wall", True, None, 12, 110),
     ("box_12_2_0", 1, 12, 2, 0, "box", True, None, 12, 111),
+    # padded dimensions 12, 16, 24 and 32 of the covariance kernel, each with and without derivative observations (W = 2 nh up to 70)
+    ("matern_20_12_0", 1, 20, 12, 0, "default", True, None, 4, 201),
+    ("se_20_16_0", 0, 20, 16, 0, "default", True, None, 4, 202),
+    ("matern_20_17_2", 1, 20, 17, 2, "default", True, None, 3, 203),
+    ("se_20_24_0_noquirks", 0, 20, 24, 0, "default", False, None, 3, 204),
+    ("matern_12_32_1", 1, 12, 32, 1, "default", True, None, 3, 205),
+    ("se_20_25_0", 0, 20, 25, 0, "default", True, None, 3, 208),       # 32 without, 16 and 12 with derivative observations
+    ("matern_12_14_1", 1, 12, 14, 1, "default", True, None, 3, 209),
+    ("matern_12_10_1", 1, 12, 10, 1, "default", True, None, 3, 210),
+    # W / 2 = 66 proposals: a second workgroup of the propose and accept kernels, and two passes (64 + 2 sets) of the likelihood
+    ("matern_12_2_0_w132", 1, 12, 2, 0, "default", True, 132, 4, 206),
+    # n (1 + g) = 300 rows: a second row block of the covariance kernel with derivative observations
+    ("matern_100_3_2_rows300", 1, 100, 3, 2, "default", True, None, 3, 207),
 ]
 
 

@@ -36,6 +36,9 @@ CASES = [
     # a tolerance so loose that every start stops before the last step of a round: the device goes on with masked steps where the
     # host loop leaves the round
     Case("e4_n40_d3_all_stop_early", 12, 3, 0, (40, 40, 40, 40), (1, 12, 64, 129), (MATERN, SE, MATERN, SE), 48, 8, 2, 0.12, MAX_REL),
+    # padded dimensions 24 (with a fidelity coordinate) and 32: the gather, step and round kernels over every coordinate of dp
+    Case("e2_n20_d17_fid_s8", 51, 17, 1, (20, 20), (12, 12), (MATERN, SE), 8, 6, 2, 1e-10, MAX_REL),
+    Case("e3_n20_d32_s8", 52, 32, 0, (20, 20, 12), (12, 12, 12), (MATERN, SE, MATERN), 8, 4, 1, 1e-10, MAX_REL),
 ]
 LOOSE = ("e4_n40_d3_A1_12_64_129_s48_loose", "e3_n12_40_d3_fid_s48_loose")
 

@@ -42,6 +42,14 @@ GPU_CASES = [
     Case("n12_d2_A129_p8", 5, 12, 2, 129, 8, 0, MATERN, 1e-2, 5),
     Case("n130_d4_A12_p63_fid", 6, 130, 4, 12, 63, 1, MATERN, 1e-2, 5),
     Case("n20_d2_A12_p64", 7, 20, 2, 12, 64, 0, MATERN, 1e-2, 5),
+    # padded dimensions 16, 24 and 32: the pending rows and the gradient's back product over run-time dp
+    Case("n20_d16_A12_p3", 51, 20, 16, 12, 3, 0, MATERN, 1e-2, 5),
+    Case("n20_d24_A12_p3_se", 55, 20, 24, 12, 3, 0, SE, 1e-2, 5),  # (seed chosen on the CPU: smallest margin 1.6e-4)
+    Case("n20_d32_A12_p2_fid", 52, 20, 32, 12, 2, 1, MATERN, 1e-2, 5),
+    # tri_cols' K slice: 128 for 512 < N <= 1024, 192 beyond (six slices at 1032 rows); the 'T' product over ld = N + pcap
+    Case("n520_d3_A20_p2", 61, 520, 3, 20, 2, 0, MATERN, 1e-2, 5),
+    Case("n1030_d4_A20_p2", 62, 1030, 4, 20, 2, 0, MATERN, 1e-2, 3),
+    # (the last case stays last: tests/test_gpu_kg1_pending.py takes it by position)
     Case("n8_d2_A4095_p2", 28, 8, 2, 4095, 2, 0, MATERN, 1e-3, 1030),  # passes of 1024 candidates: C straddles one
 ]
 
@@ -93,12 +101,13 @@ def expected(case, T=LD):
 
 # ---- an ensemble: members of different N and different A_e, one list of pending points ----
 ENSEMBLE = dict(seed=21, d=3, nf=1, n=(12, 40, 20), A=(12, 64, 5), cov=(MATERN, SE, MATERN), factors=(1.0, 1.3, 0.8), p=3, C=6)
+# padded dimension 24 with a fidelity coordinate, two members of different N
+ENSEMBLE_WIDE = dict(seed=71, d=17, nf=1, n=(12, 20), A=(12, 12), cov=(MATERN, SE), factors=(1.0, 1.3), p=3, C=6)
 
 EnsembleProblem = collections.namedtuple("EnsembleProblem", "hyper X y noise cov discrete best points pending nf")
 
 
-def make_ensemble():
-    e = ENSEMBLE
+def make_ensemble(e=ENSEMBLE):
     rng = np.random.default_rng(8200 + e["seed"])
     X = rng.uniform(0, 1, size=(max(e["n"]), e["d"]))
     y = 0.3 * rng.normal(size=(max(e["n"]), 1))

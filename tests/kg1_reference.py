@@ -272,6 +272,17 @@ GPU_CASES = [
     Case("n8_d2_A4000", 7, 8, 2, 4000, MATERN, 1e-3, 0, 1),
     Case("n40_d8_A300_fid", 8, 40, 8, 300, MATERN, 1e-2, 1, 7),
     Case("n150_d6_A1000", 9, 150, 6, 1000, MATERN, 1e-2, 0, 7),
+    # padded dimensions 12 (with a fidelity coordinate), 16, 24 and 32, each with and without fidelity coordinates: every
+    # instantiation of the gradient kernel the cases above leave out; A = 63 / 64 / 65 around a wavefront of lines
+    Case("n20_d12_A63_fid", 45, 20, 12, 63, MATERN, 1e-2, 1, 7),
+    Case("n20_d16_A63", 41, 20, 16, 63, MATERN, 1e-2, 0, 7),
+    Case("n20_d17_A64_fid", 42, 20, 17, 64, SE, 1e-2, 1, 7),
+    Case("n24_d24_A65_fid2", 43, 24, 24, 65, MATERN, 1e-2, 2, 7),
+    Case("n20_d32_A63_fid", 44, 20, 32, 63, MATERN, 1e-2, 1, 7),
+    Case("n20_d18_A64", 46, 20, 18, 64, MATERN, 1e-2, 0, 7),  # (24 and 32 without a fidelity coordinate, d below the padded dimension)
+    Case("n20_d25_A65", 47, 20, 25, 65, SE, 1e-2, 0, 7),
+    Case("n20_d14_A63_fid", 48, 20, 14, 63, MATERN, 1e-2, 1, 7),  # (16 with a fidelity coordinate)
+    # (the last case stays last: tests/test_gpu_kg1.py takes it by position)
     Case("n300_d12_A4095", 10, 300, 12, 4095, MATERN, 1e-2, 0, 1027),  # passes of 1024 candidates: C straddles one
 ]
 

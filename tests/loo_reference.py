@@ -184,7 +184,7 @@ def brute_force(X, y, derivs, hyper, cov_type, dtype=np.longdouble):
 # ---- the problems of tests/test_gpu_loo.py (here so that the CPU suite checks the restatement on the same inputs) ----
 # (cov_type, n, d, g): N = n (1 + g) in {1, 2, 63, 64, 65, 129, 257} -- the 64-column and 256-row block edges of the gradient's
 # contraction and the 64-wide blocks of the factor and of its inverse; (d, g) in {(1,0), (3,0), (5,0), (3,2), (12,3)} -- padded
-# dimensions 4, 8, 12; both kernels where g = 0.
+# dimensions 4, 8, 12; both kernels where g = 0.  (Padded dimensions 16, 24, 32: WIDE_CASES below.)
 CASES = [
     (MATERN, 1, 1, 0), (SE, 1, 3, 0), (SE, 2, 3, 0), (MATERN, 2, 5, 0),
     (MATERN, 21, 3, 2), (SE, 63, 5, 0), (MATERN, 63, 1, 0),
@@ -194,6 +194,12 @@ CASES = [
     (MATERN, 257, 3, 0), (SE, 257, 5, 0),
 ]
 SE_DERIV_CASE = (SE, 21, 3, 2)   # value and predictions only: the gradient with derivative observations is Matern-5/2's
+# Padded dimensions 16, 24 and 32, at both ends of each (d = 13 / 16, 17 / 24, 25 / 32); N = 20, 30, 36 and 70 (a second 64-column
+# block at d = 32).  A list of its own: grad_gap() below, the bound of the device's gradient, stays a maximum over CASES alone.
+WIDE_CASES = [
+    (MATERN, 20, 13, 0), (SE, 20, 16, 0), (MATERN, 20, 17, 0), (SE, 30, 24, 0),
+    (MATERN, 12, 25, 2), (SE, 20, 32, 0), (MATERN, 70, 32, 0),
+]
 
 
 def case_id(case):

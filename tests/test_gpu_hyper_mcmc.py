@@ -8,6 +8,11 @@ half-step the DEVICE's state before it is taken, the proposal, prior and likelih
   * the decision is identical wherever |ln u - ln r| > 1e-8 max(1, |ln r|); decisions inside that band are skipped and at most
     1 in 1000 may be (tests/test_hyper_mcmc_reference.py confirms that the restated chains of these seeds have none);
   * chain, lnprob and accepted are consistent with the decisions bit for bit.
+Shapes (hyper_mcmc_reference.CASES): (n, d, g) from (12, 2, 0) to (300, 6, 0) and (25, 3, 2) -- padded dimensions 4 and 8 -- and
+(d, g) in {(10, 1), (12, 0), (14, 1), (16, 0), (17, 2), (24, 0), (25, 0), (32, 1)} -- padded dimensions 12, 16, 24, 32, each with and
+without derivative observations, up to 70 walkers; 132 walkers at d = 2 (66
+proposals per half-step: a second workgroup of the propose and accept kernels, passes of 64 + 2 factorisations); n (1 + g) = 300 rows
+with g = 2 (a second row block of the covariance kernel with derivative observations).
 """
 import os
 
@@ -44,7 +49,7 @@ def _close(got, want, rel):
 
 
 def check_transitions(c, res):
-    """-> (decisions compared, decisions skipped inside the band)"""
+    """-> (decisions compared, decisions skipped inside the band, worst |proposal_lnprob - want| / max(1, |want|) seen)"""
     post = R.Posterior(c["cov_type"], c["X"], c["y"], c["derivs"], c["table"], c["quirks"])
     us, pt, ua = c["tables"]
     T, W = us.shape[0], c["p0"].shape[0]
@@ -53,12 +58,15 @@ def check_transitions(c, res):
     for w in range(W):
         assert _close(lnp[w], post(walkers[w]), 1e-9), ("lnprob0", w, lnp[w], post(walkers[w]))
     compared = skipped = 0
+    worst = 0.0
     for t in range(T):
         for h in range(2):
             hs = R.half_step(walkers, lnp, h, us[t, h], pt[t, h], ua[t, h], c["table"], post)
             for i, w in enumerate(hs["index"]):
                 want_lp, got_lp = hs["proposal_lnprob"][i], res["proposal_lnprob"][t, w]
                 assert _close(got_lp, want_lp, 1e-9), ("proposal_lnprob", t, h, w, got_lp, want_lp)
+                if np.isfinite(want_lp):
+                    worst = max(worst, abs(got_lp - want_lp) / max(1.0, abs(want_lp)))
                 lnr, lnu, acc = hs["lnr"][i], hs["lnu"][i], bool(res["accepted"][t, w])
                 assert res["accepted"][t, w] in (0, 1)
                 if np.isfinite(lnr) and np.isfinite(lnu) and abs(lnu - lnr) <= 1e-8 * max(1.0, abs(lnr)):
@@ -75,15 +83,16 @@ def check_transitions(c, res):
                 walkers[w], lnp[w] = res["chain"][t, w], res["lnprob"][t, w]
         assert np.array_equal(res["chain"][t], walkers) and np.array_equal(res["lnprob"][t], lnp)
     assert skipped * 1000 <= compared + skipped, (skipped, compared)
-    return compared, skipped
+    return compared, skipped, worst
 
 
 @pytest.mark.parametrize("case", R.CASES, ids=[c[0] for c in R.CASES])
 def test_transitions_against_restatement(api, case):
     c = R.build_case(case)
     res = _run(api, c)
-    compared, skipped = check_transitions(c, res)
-    print("%s: %d decisions compared, %d skipped, acceptance %.2f" % (c["name"], compared, skipped, res["accepted"].mean()))
+    compared, skipped, worst = check_transitions(c, res)
+    print("%s: %d decisions compared, %d skipped, acceptance %.2f, worst proposal log posterior error %.3g (bound 1e-9)" % (
+        c["name"], compared, skipped, res["accepted"].mean(), worst))
     assert 0 < res["accepted"].sum() < res["accepted"].size
     d = c["X"].shape[1]
     if case[5] == "wall":  # proposals beyond the wall (inside the box) were made and rejected

@@ -1,6 +1,8 @@
 """The exact discretised one-point knowledge gradient on the device (csrc/kg1.hip: moe_gp_kg_discrete) against the long-double
 restatement of tests/kg1_reference.py, on the cases kg1_reference.GPU_CASES (tests/test_kg1_reference.py holds the float64
-restatement to the same cases on the CPU).
+restatement to the same cases on the CPU).  Shapes: d in {2, 3, 4, 6, 8, 12} with n up to 300 and A up to 4095 lines, and
+d in {12, 14, 16, 17, 18, 24, 25, 32} at n = 20 / 24, A = 63 / 64 / 65 -- padded dimensions 12, 16, 24, 32, each of them with fidelity
+coordinates (one or two) and without: every instantiation of the gradient kernel.
 
 Tolerances: with scale = max(1, max |a|, sqrt(alpha)), |KG - want| <= 1e-10 scale (the bound tests/test_gpu_lcb.py uses for
 continuous outputs) and |grad KG - want|_inf <= 1e-10 max(1, |want|_inf).  The number of lines on the envelope must be exact on every
@@ -60,7 +62,7 @@ def test_the_straddled_pass_is_the_one_the_library_uses():
     assert set(kr.make_problem(case).checked) >= {per_pass - 1, per_pass}
 
 
-@pytest.mark.parametrize("name", ["n5_d2_A255", "n20_d3_A63_fid", "n150_d6_A1000"])
+@pytest.mark.parametrize("name", ["n5_d2_A255", "n20_d3_A63_fid", "n150_d6_A1000", "n24_d24_A65_fid2"])
 def test_duplicates_a_permutation_and_the_candidate_itself_change_no_bit(name):
     case = [c for c in kr.GPU_CASES if c.name == name][0]
     p = kr.make_problem(case)
@@ -99,7 +101,7 @@ def test_one_discrete_point_is_the_two_line_closed_form():
     G.close()
 
 
-@pytest.mark.parametrize("name", ["n20_d3_A63_fid", "n70_d4_A64_se"])
+@pytest.mark.parametrize("name", ["n20_d3_A63_fid", "n70_d4_A64_se", "n24_d24_A65_fid2", "n20_d32_A63_fid"])
 def test_best_so_far_on_either_side_of_the_mean(name):
     """KG + E[min] = min(best, mu_n(x^)): moving best across mu_n(x^) moves KG by exactly what the minimum moves, and the gradient
     gains or loses grad mu_n(x^) (zero on the fidelity coordinates)."""

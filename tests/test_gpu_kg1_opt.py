@@ -1,6 +1,7 @@
 """The ensemble forms of the discretised one-point knowledge gradient on the device (csrc/kg1_opt.hip: moe_kg_discrete_mcmc,
 moe_kg_discrete_mcmc_multistart) on the cases of tests/kg1_opt_cases.py, whose inputs tests/test_kg1_opt_reference.py qualifies on
-the CPU.
+the CPU.  Shapes: d in {2, 3, 4} with one to four members, and d = 17 with a fidelity coordinate and d = 32 (padded dimensions 24
+and 32) with two and three members.
 
 The yardsticks: api.kg_discrete_mcmc (the host loop over the members, one moe_gp_kg_discrete call each) for the evaluator, bit for
 bit; tests/ms_restatement.py's optimiser with its evaluations made by api.kg_discrete_mcmc and its updates in numpy for the

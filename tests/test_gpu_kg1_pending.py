@@ -2,7 +2,10 @@
 moe_kg_discrete_mcmc_pending, moe_kg_discrete_mcmc_multistart_pending, moe_kg_discrete_mcmc_suggest) against the long-double
 restatement of tests/kg1_pending_reference.py, on the cases kg1_pending_reference.GPU_CASES, whose inputs
 tests/test_kg1_pending_reference.py qualifies on the CPU (float64 within 2.5e-11 scale of long double, every decision margin
->= 1e-7, P moves a checked candidate's value by >= 1e-4 scale: a device that ignored P fails here).
+>= 1e-7, P moves a checked candidate's value by >= 1e-4 scale: a device that ignored P fails here).  Shapes: d in {2, 3, 4} with n up
+to 130, A up to 4095 and up to 64 pending points; d in {16, 24, 32} at n = 20 (padded dimensions 16, 24, 32); n = 520 and 1030 (the
+128- and 192-wide K slices of the split-K triangular products); ensembles, the ascent and the greedy batch also at d = 17 with a
+fidelity coordinate and members of different N.
 
 Tolerances: tests/test_gpu_kg1.py's -- |KG - want| <= 1e-10 scale, |grad KG - want|_inf <= 1e-10 max(1, |want|_inf), the number of
 lines on the envelope exact.  Everything else is bit for bit: the new symbols with no pending point against their twins, a candidate
@@ -132,7 +135,16 @@ def test_the_straddled_pass_is_the_one_the_library_uses():
 
 
 def test_an_ensemble_of_three_against_long_double_launches_on_and_off():
-    ep = kp.make_ensemble()
+    _ensemble_against_long_double(kp.ENSEMBLE)
+
+
+def test_a_wide_ensemble_of_two_against_long_double_launches_on_and_off():
+    """d = 17 with a fidelity coordinate (padded dimension 24), members of 12 and 20 sampled points"""
+    _ensemble_against_long_double(kp.ENSEMBLE_WIDE)
+
+
+def _ensemble_against_long_double(spec):
+    ep = kp.make_ensemble(spec)
     want = kp.ensemble_expected(ep, ep.pending, LD)
     gps = [api.DeviceGP(ep.hyper[k], ep.X[k], ep.y[k], ep.noise[k], cov_type=ep.cov[k]) for k in range(len(ep.X))]
     runs = []
@@ -144,13 +156,17 @@ def test_an_ensemble_of_three_against_long_double_launches_on_and_off():
     assert np.array_equal(kg, runs[1][0]) and np.array_equal(grad, runs[1][1])
     e_v = max(abs(kg[i] - float(w[0])) / w[2] for i, w in enumerate(want))
     e_g = max(float(np.max(np.abs(grad[i] - w[1].astype(np.float64)))) / max(1.0, float(np.max(np.abs(w[1])))) for i, w in enumerate(want))
-    print("ensemble of 3: value error %.3g of the members' mean scale, gradient error %.3g (bounds 1e-10)" % (e_v, e_g))
+    print("ensemble of %d, d = %d: value error %.3g of the members' mean scale, gradient error %.3g (bounds 1e-10)" % (
+        len(gps), ep.points.shape[1], e_v, e_g))
     assert e_v <= 1e-10 and e_g <= 1e-10
     # the mean of the members' own calls, added in member order and divided once
     single = [g.kg_discrete(s, ep.points, b, num_fidelity=ep.nf, points_being_sampled=ep.pending)
               for g, s, b in zip(gps, ep.discrete, ep.best)]
-    assert np.array_equal(kg, ((single[0][0] + single[1][0]) + single[2][0]) / 3)
-    assert np.array_equal(grad, ((single[0][1] + single[1][1]) + single[2][1]) / 3)
+    sum_kg, sum_grad = single[0][0], single[0][1]
+    for one in single[1:]:
+        sum_kg, sum_grad = sum_kg + one[0], sum_grad + one[1]
+    assert np.array_equal(kg, sum_kg / len(gps))
+    assert np.array_equal(grad, sum_grad / len(gps))
     _close(gps)
 
 
@@ -176,7 +192,7 @@ def test_without_pending_points_every_new_symbol_is_its_twin():
 
 
 # ---- 3. duplicates in the set and the candidate itself, with pending points ----
-@pytest.mark.parametrize("name", ["n20_d3_A12_p2_fid", "n12_d2_A129_p8", "n130_d3_A65_p3"])
+@pytest.mark.parametrize("name", ["n20_d3_A12_p2_fid", "n12_d2_A129_p8", "n130_d3_A65_p3", "n20_d32_A12_p2_fid"])
 def test_duplicates_and_the_candidate_itself_change_no_bit(name):
     case = [c for c in kp.GPU_CASES if c.name == name][0]
     p = kp.make_problem(case)
@@ -242,8 +258,13 @@ def _host_loop(gps, p, pending):
             "end_values": end_vals, "steps_taken": steps, "path": path}
 
 
+# d = 17 with a fidelity coordinate (padded dimension 24) and members of different N: the batch appends each pick to the pending list
+# on the device as a padded row of dp coordinates
+WIDE_BATCH = kc.Case("e2_n12_20_d17_fid_s8", 53, 17, 1, (12, 20), (12, 12), (kc.MATERN, kc.SE), 8, 6, 2, 1e-10, kc.MAX_REL)
+
+
 def _opt_problem(name, num_pending):
-    case = [c for c in kc.CASES if c.name == name][0]
+    case = [c for c in kc.CASES + [WIDE_BATCH] if c.name == name][0]
     p = kc.make_problem(case)
     rng = np.random.default_rng(400 + num_pending)
     pending = rng.uniform(0.05, 0.95, size=(num_pending, case.d))
@@ -252,7 +273,7 @@ def _opt_problem(name, num_pending):
     return case, p, pending, gps
 
 
-@pytest.mark.parametrize("name", ["e3_n12_d2_A12_s8_tight", "e3_n12_40_d3_fid_s48_loose"])
+@pytest.mark.parametrize("name", ["e3_n12_d2_A12_s8_tight", "e3_n12_40_d3_fid_s48_loose", "e2_n20_d17_fid_s8"])
 def test_the_ascent_is_the_host_driven_loop_bit_for_bit(name):
     case, p, pending, gps = _opt_problem(name, 3)
     want = _host_loop(gps, p, pending)
@@ -271,7 +292,8 @@ def test_the_ascent_is_the_host_driven_loop_bit_for_bit(name):
     _close(gps)
 
 
-@pytest.mark.parametrize("name,num_pending", [("e3_n12_d2_A12_s8_tight", 0), ("e3_n12_40_d3_fid_s48_loose", 2)])
+@pytest.mark.parametrize("name,num_pending", [("e3_n12_d2_A12_s8_tight", 0), ("e3_n12_40_d3_fid_s48_loose", 2),
+                                              ("e2_n12_20_d17_fid_s8", 2)])
 def test_the_batch_is_the_ascent_fed_its_predecessors_bit_for_bit(name, num_pending):
     case, p, pending, gps = _opt_problem(name, max(num_pending, 1))
     pending = pending[:num_pending]

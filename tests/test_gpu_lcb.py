@@ -1,5 +1,6 @@
 """Marginal mean / std and batch lower-confidence-bound selection on the device (csrc/lcb.hip: moe_gp_mean_std, moe_gp_lcb_select)
-against tests/lcb_reference.py, at the smallest shapes that reach each branch.
+against tests/lcb_reference.py, at the smallest shapes that reach each branch: d in {2, 3, 4} throughout, d = 17 and 32 (padded
+dimensions 24 and 32) in test_wide_dimensions.
 
 Continuous outputs are held to the forward bound of the posterior-sampling tests against the extended-precision form:
 |mean - want| <= 1e-10 max(1, |want|) and |std^2 - var_want| <= 1e-10 max(1, alpha).  Indices must be equal exactly; every test
@@ -75,6 +76,19 @@ def test_split_k_state_and_several_rounds(n, C_, d, cov_type, seed):
     rng, G, P, hyper = _problem(seed, n, d, cov_type, length=0.5, y_scale=0.2)
     cand = rng.uniform(0, 1, size=(C_, d))
     _check(G, lr.extended(P, [1e-2], cand, 4), cand, 4, hyper[0], "N=%d C=%d d=%d" % (n, C_, d))
+
+
+@pytest.mark.parametrize("n,C_,d,cov_type", [(129, 40, 17, MATERN), (40, 17, 32, SE)])
+def test_wide_dimensions(n, C_, d, cov_type):
+    """Padded dimensions 24 and 32 of the radial sums (and split-K at N = 129), eight picks.  Lengths 0.1 + 0.25 sqrt(d): the default
+    0.4 makes K nearly diagonal at d = 32 and the selection trivial.  The indices are the only output of the rounds, so the seeds are
+    the ones of 1 .. 60 whose smallest decision margin is small while still 700 times the rule's 1e-7 (7.6e-5 with 31 of 40 kept,
+    7.7e-5 with 16 of 17 kept): an error in a covariance beyond that flips a pick."""
+    rng, G, P, hyper = _problem(WIDE_SEEDS[d], n, d, cov_type, length=0.1 + 0.25 * np.sqrt(d))
+    cand = rng.uniform(0, 1, size=(C_, d))
+    want = lr.extended(P, [1e-2], cand, 8)
+    assert 1 < want.kept < C_ and len(set(want.index.tolist())) == 8  # (something to drop, something to keep, eight different picks)
+    _check(G, want, cand, 8, hyper[0], "N=%d C=%d d=%d" % (n, C_, d))
 
 
 def test_kept_set_smaller_than_the_batch():
@@ -268,3 +282,4 @@ def test_run_cpp_tests_covers_the_selection():
 # seeds found on the CPU with lcb_reference.extended alone (tests/lcb_reference.py; no device involved)
 KEPT3_SEED = 16
 Q64_SEED = 0
+WIDE_SEEDS = {17: 6, 32: 8}

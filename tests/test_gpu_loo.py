@@ -2,7 +2,8 @@
 tests/loo_reference.py (long double; closed form and an independent brute force).
 
 Shapes (loo_reference.CASES): N = n (1 + g) in {1, 2, 63, 64, 65, 129, 257}, (d, g) in {(1,0), (3,0), (5,0), (3,2), (12,3)}, both
-kernels where g = 0.  Tolerances: values, predictions and sampler log posteriors 1e-9 max(1, |want|), the project's own for
+kernels where g = 0; (loo_reference.WIDE_CASES): d in {13, 16, 17, 24, 25, 32} -- padded dimensions 16, 24, 32 at both ends of
+each -- with N in {20, 30, 36, 70}, (d, g) = (25, 2) among them.  Tolerances: values, predictions and sampler log posteriors 1e-9 max(1, |want|), the project's own for
 moe_ll_evaluate (tests/test_gpu_hyper_mcmc.py).  Gradient: see test_gradient_against_closed_form.
 """
 import numpy as np
@@ -34,7 +35,7 @@ def _close(got, want, tol=TOL):
         return bool(np.all((got == want) | (np.abs(got - want) <= tol * np.maximum(1, np.abs(want)))))
 
 
-@pytest.mark.parametrize("case", R.CASES + [R.SE_DERIV_CASE], ids=R.case_id)
+@pytest.mark.parametrize("case", R.CASES + R.WIDE_CASES + [R.SE_DERIV_CASE], ids=R.case_id)
 def test_value_one_set(case):
     r, ll = _handle(case, LOO)
     got = ll.evaluate(r["hyper"][None, :])
@@ -58,7 +59,7 @@ def test_value_65_sets_and_a_singular_one(case):
     assert ll.evaluate(hyper[37:38])[0] == -np.inf
 
 
-@pytest.mark.parametrize("case", R.CASES + [R.SE_DERIV_CASE], ids=R.case_id)
+@pytest.mark.parametrize("case", R.CASES + R.WIDE_CASES + [R.SE_DERIV_CASE], ids=R.case_id)
 def test_predictions_against_brute_force(case):
     r, ll = _handle(case)   # the handle's objective stays 0
     before = ll.evaluate(r["hyper"][None, :])[0]
@@ -84,7 +85,7 @@ def test_predict_singular():
     assert _close(mean, r["bf_mu"])
 
 
-GRAD_CASES = [c for c in R.CASES]
+GRAD_CASES = R.CASES + R.WIDE_CASES   # (the bound below stays that of R.CASES alone)
 
 
 @pytest.mark.parametrize("case", GRAD_CASES, ids=R.case_id)
@@ -104,7 +105,7 @@ def test_gradient_against_closed_form(case):
     assert err <= bound, (err, bound, got, r["grad"])
 
 
-@pytest.mark.parametrize("case", [c for c in R.CASES if c[3] == 0], ids=R.case_id)
+@pytest.mark.parametrize("case", [c for c in R.CASES + R.WIDE_CASES if c[3] == 0], ids=R.case_id)
 def test_gradient_against_differences_of_the_device_value(case):
     r, ll = _handle(case, LOO)
     h = r["hyper"]

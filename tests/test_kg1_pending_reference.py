@@ -127,7 +127,15 @@ def test_every_gpu_case_qualifies(case):
 
 
 def test_the_ensemble_case_qualifies():
-    ep = kp.make_ensemble()
+    _ensemble_qualifies(kp.ENSEMBLE)
+
+
+def test_the_wide_ensemble_case_qualifies():
+    _ensemble_qualifies(kp.ENSEMBLE_WIDE)
+
+
+def _ensemble_qualifies(spec):
+    ep = kp.make_ensemble(spec)
     want, f8 = kp.ensemble_expected(ep, ep.pending, LD), kp.ensemble_expected(ep, ep.pending, np.float64)
     without = kp.ensemble_expected(ep, ep.pending[:0], LD)
     e_v = max(abs(float(a[0]) - float(b[0])) / b[2] for a, b in zip(f8, want))
