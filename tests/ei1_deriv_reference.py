@@ -235,6 +235,25 @@ def make_problem(case, p=None):
 PROBLEMS = [make_problem(c) for c in CASES]
 PROBLEMS_P0 = [make_problem(c, 0) for c in CASES]
 
+# padded dimensions 16 and 24 of ei1_grad_g_kernel (12 is reached above without a padded coordinate), and more than 256 points: a
+# second trip of its loop over the points, 520 rows (tri_cols' K slice 128).  From 256 points on the best value is the median of the
+# observed values (tests/ei1_reference.py: with the minimum EI and its gradient vanish and a 1e-10 test is empty).
+WIDE_CASES = [
+    # (seed chosen on the CPU for tests/gibbon_reference.py, which takes this case: candidates 0 and 1 lie low enough for gamma near 3)
+    Case("n10_d13_D0_12_p2", 30, 10, 13, (0, 12), 2, MATERN, 1e-2, 5, True, False),    # DP = 16, three padded coordinates
+    Case("n10_d20_D3_19_p2_se", 22, 10, 20, (3, 19), 2, SE, 1e-2, 5, True, False),      # DP = 24, four padded coordinates
+    Case("n260_d3_D1_p2", 23, 260, 3, (1,), 2, MATERN, 1e-2, 5, False, False),          # 260 points, 520 rows
+]
+
+
+def make_wide_problem(case, p=None):
+    q = make_problem(case, p)
+    return q._replace(best=float(np.median(q.y[:, 0]))) if case.n >= 256 else q
+
+
+WIDE_PROBLEMS = [make_wide_problem(c) for c in WIDE_CASES]
+WIDE_PROBLEMS_P0 = [make_wide_problem(c, 0) for c in WIDE_CASES]
+
 _WANT = {}
 
 

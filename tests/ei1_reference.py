@@ -47,9 +47,14 @@ def believed_best(base, pending, best):
 
 def evaluate(base, pending, x, best, y_max=0.0):
     """EI and its gradient at x for the model `base` conditioned on `pending` [p][dim] (may be empty)"""
-    T = base.T
     P = np.asarray(pending, dtype=np.float64).reshape(-1, base.X.shape[1])
-    model = kp.PendingModel(base, P) if len(P) else base
+    return evaluate_model(kp.PendingModel(base, P) if len(P) else base, base, P, x, best, y_max)
+
+
+def evaluate_model(model, base, P, x, best, y_max=0.0):
+    """the same with the conditioned model at hand (model = PendingModel(base, P), or base itself for an empty P): one factorisation
+    serves every candidate"""
+    T = base.T
     x = np.asarray(x, dtype=np.float64).reshape(1, -1)
     k = model.cov(model.X, x)[:, 0]
     v = model.fwd(k)
@@ -98,6 +103,30 @@ def problems():
 PROBLEMS = problems()
 BPRIME = "n40_d3_p4_bprime"
 
+# ---- padded dimensions 12, 16 and 24, a second 256-row trip of the gradient kernel, tri_cols' K slices under ld = N + pcap ----
+# From 256 rows on the best value is median(y): with min(y) and uniform candidates a GP on hundreds of points in 3 or 4 dimensions
+# has c below -5 everywhere, EI below 1e-8 and a gradient below 1e-6, and an absolute bound of 1e-10 scale would pass a device that
+# returned zeros.  With the median EI is 1e-2 .. 0.5 scale and the gradient of order 1 (tests/test_ei1_reference.py asserts both).
+_W10 = kp.Case("n20_d10_p3", 81, 20, 10, 1, 3, 0, MATERN, 1e-2, 5)        # DP = 12, two padded coordinates
+_W13 = kp.Case("n20_d13_p3_se", 82, 20, 13, 1, 3, 0, SE, 1e-2, 5)         # DP = 16, three padded coordinates
+_W20 = kp.Case("n20_d20_p3", 83, 20, 20, 1, 3, 0, MATERN, 1e-2, 5)        # DP = 24, four padded coordinates
+# (seed chosen on the CPU: b' = min(median, mu(P)) leaves every candidate an EI above 1e-2 scale; with most seeds two or three vanish)
+_W300 = kp.Case("n300_d3_p3", 92, 300, 3, 1, 3, 0, MATERN, 1e-2, 5)       # 303 rows: a second trip; K slice 64, five slices
+_W520 = kp.Case("n520_d3_p2", 85, 520, 3, 1, 2, 0, MATERN, 1e-2, 5)       # K slice 128
+_W1030 = kp.Case("n1030_d4_p2", 86, 1030, 4, 1, 2, 0, MATERN, 1e-2, 3)    # K slice 192
+
+
+def median_best(q):
+    return float(np.median(q.y))
+
+
+def wide_problems():
+    return [_from_kp(_W10), _from_kp(_W13), _from_kp(_W20), _from_kp(_W300, best=median_best), _from_kp(_W520, best=median_best),
+            _from_kp(_W1030, best=median_best), _from_kp(_W13, "n20_d13_p0_se", 0), _from_kp(_W300, "n300_d3_p0", 0, best=median_best)]
+
+
+WIDE_PROBLEMS = wide_problems()
+
 _WANT = {}
 
 
@@ -111,19 +140,22 @@ def expected(p, T=LD):
     if key not in _WANT:
         base = base_model(p, T)
         y_max = float(np.max(np.abs(p.y)))
-        with_p = {i: evaluate(base, p.pending, p.points[i], p.best, y_max) for i in p.checked}
-        without = {i: evaluate(base, p.pending[:0], p.points[i], p.best, y_max).value for i in p.checked}
+        P = np.asarray(p.pending, dtype=np.float64).reshape(-1, p.X.shape[1])
+        model = kp.PendingModel(base, P) if len(P) else base
+        with_p = {i: evaluate_model(model, base, P, p.points[i], p.best, y_max) for i in p.checked}
+        without = {i: evaluate_model(base, base, P[:0], p.points[i], p.best, y_max).value for i in p.checked}
         _WANT[key] = (with_p, without)
     return _WANT[key]
 
 
 # ---- a three-member ensemble: different hyper-parameters, different n on both sides of 128 rows, one list of pending points ----
 ENSEMBLE = dict(seed=51, d=3, n=(12, 130, 40), cov=(MATERN, SE, MATERN), factors=(1.0, 1.3, 0.8), p=3, C=6)
+# padded dimension 12; n on both sides of 256 and of 512 rows (tri_cols' K slices 64 and 128 beside a member below 128 rows)
+ENSEMBLE_WIDE = dict(seed=91, d=10, n=(20, 300, 600), cov=(MATERN, SE, MATERN), factors=(1.0, 1.3, 0.8), p=3, C=6)
 EnsembleProblem = collections.namedtuple("EnsembleProblem", "hyper X y noise cov best points pending")
 
 
-def make_ensemble():
-    e = ENSEMBLE
+def make_ensemble(e=ENSEMBLE):
     rng = np.random.default_rng(8200 + e["seed"])
     X = rng.uniform(0, 1, size=(max(e["n"]), e["d"]))
     y = 0.3 * rng.normal(size=(max(e["n"]), 1))
@@ -137,12 +169,21 @@ def make_ensemble():
     return EnsembleProblem(hyper, [X[:n] for n in e["n"]], [y[:n] for n in e["n"]], noise, e["cov"], best, points, pending)
 
 
+def ensemble_key(ep, pending, T):
+    return ("ensemble", ep.points.shape[1], tuple(len(x) for x in ep.X), len(pending), T)
+
+
 def ensemble_expected(ep, pending, T=LD):
-    """per candidate (mean of the members' values, mean of their gradients, the largest member scale)"""
+    """per candidate (mean of the members' values, mean of their gradients, the largest member scale), once per process"""
+    key = ensemble_key(ep, pending, T)
+    if key in _WANT:
+        return _WANT[key]
     bases = [kr.Model(ep.cov[k], ep.hyper[k], ep.X[k], ep.y[k], ep.noise[k], T) for k in range(len(ep.X))]
-    out = []
+    out = _WANT[key] = []
+    P = np.asarray(pending, dtype=np.float64).reshape(-1, ep.points.shape[1])
+    models = [kp.PendingModel(m, P) if len(P) else m for m in bases]
     for x in ep.points:
-        res = [evaluate(m, pending, x, b, float(np.max(np.abs(y)))) for m, b, y in zip(bases, ep.best, ep.y)]
+        res = [evaluate_model(mm, m, P, x, b, float(np.max(np.abs(y)))) for mm, m, b, y in zip(models, bases, ep.best, ep.y)]
         value, grad = T(0), np.zeros(len(x), dtype=T)
         for r in res:
             value, grad = value + r.value, grad + r.grad

@@ -179,7 +179,10 @@ def base_model(p, T=LD):
 # case's: the others lie so far from every pending point, or so far above every min-value (every gamma above about 4.5, up to 22:
 # the terms sum to less than 1e-5), that P or the min-values move their value by less than 1e-5 scale whatever the code does.  Value and gradient are compared at EVERY candidate all the same.
 _CHECKED = {"n40_d4_A64_p5_se": (0, 1, 2, 4), "n130_d3_A65_p3": (0, 1, 3), "n20_d32_p2": (0, 1, 3, 4), "n5_d2_g2_p1": (0, 1, 3, 4),
-            "n44_d3_g2_p3_noise1e-3": (0, 4), "n10_d2_p2_noise_free": (0, 2, 3, 4)}
+            "n44_d3_g2_p3_noise1e-3": (0, 4), "n10_d2_p2_noise_free": (0, 2, 3, 4),
+            # the wide cases: P moves the others by less than 1e-5 scale (in 13 dimensions they lie far from both pending points), and in
+            # the derivative case every gamma of candidates 2 to 4 lies above 3.6: the min-values move them by less than 6e-6
+            "n20_d13_p3_se": (0, 1, 2, 4), "n10_d13_D0_12_p2": (0, 1), "n300_d3_p3_near_the_lowest_K130": (0, 2, 3)}
 
 
 def _with_mins(name, q, derivs, K, seed):
@@ -231,6 +234,37 @@ def problems():
 
 PROBLEMS = problems()
 
+WIDE_N300 = "n300_d3_p3_near_the_lowest_K130"
+# (seeds chosen on the CPU: the min-values move every candidate by >= 2.7e-5 scale, P moves candidates 0, 2 and 3 by >= 4.9e-4)
+_G300 = kp.Case("n300_d3_p3", 84, 300, 3, 1, 3, 0, MATERN, 1e-2, 5)
+
+
+def _near_the_lowest():
+    """tests/ei1_reference.py's 300-point inputs with the candidates within 0.05 of the five sampled points of lowest y and pending
+    point 0 within 0.05 of candidate 0: with uniform candidates every gamma lies above 2, up to 25, and the min-values move some
+    candidates' values by less than 1e-10"""
+    q = er._from_kp(_G300)
+    rng = np.random.default_rng(9184)
+    low = np.argsort(q.y[:, 0])[:5]
+    points = np.clip(q.X[low] + rng.uniform(-0.05, 0.05, size=(5, q.X.shape[1])), 0.0, 1.0)
+    pending = q.pending.copy()
+    pending[0] = np.clip(points[0] + rng.uniform(-0.05, 0.05, size=q.X.shape[1]), 0.0, 1.0)
+    return _with_mins(WIDE_N300, q._replace(points=points, pending=pending), (), 130, 84)
+
+
+def wide_problems():
+    """padded dimensions 16 and 24 with K on both sides of 64, derivative rows at padded dimension 16, and 300 rows under 130
+    min-values: five 64-row trips of the candidate kernel's chain with N no multiple of 64, a third trip over the min-values"""
+    by_name = {q.name: q for q in er.WIDE_PROBLEMS}
+    out = [_with_mins(name, by_name[name], (), K, seed) for name, K, seed in (("n20_d13_p3_se", 65, 41), ("n20_d20_p3", 63, 42))]
+    q = ed.WIDE_PROBLEMS[0]
+    out.append(_with_mins(q.name, q, q.derivs, 64, 44))  # (seed chosen on the CPU: the min-values move candidates 0 and 1 by 3e-5)
+    out.append(_near_the_lowest())
+    return out
+
+
+WIDE_PROBLEMS = wide_problems()
+
 _WANT = {}
 
 
@@ -249,12 +283,12 @@ def expected(p, T=LD):
     return _WANT[key]
 
 
-# ---- ei1_reference's three-member ensemble (N = 12 / 130 / 40) with min-values of its own per member ----
+# ---- ei1_reference's three-member ensembles (N = 12 / 130 / 40; ENSEMBLE_WIDE: 20 / 300 / 600) with min-values of its own per member ----
 ENSEMBLE_K = 64
 
 
-def make_ensemble():
-    ep = er.make_ensemble()
+def make_ensemble(e=er.ENSEMBLE):
+    ep = er.make_ensemble(e)
     mins = np.array([draw_min_values(kr.Model(ep.cov[k], ep.hyper[k], ep.X[k], ep.y[k], ep.noise[k], np.float64), ENSEMBLE_K, 50 + k)
                      for k in range(len(ep.X))])
     return ep, mins
@@ -262,7 +296,7 @@ def make_ensemble():
 
 def ensemble_expected(ep, mins, pending, T=LD):
     """per candidate (mean of the members' values, mean of their gradients, the largest member scale)"""
-    key = ("ensemble", len(pending), T)
+    key = er.ensemble_key(ep, pending, T)
     if key not in _WANT:
         bases = [kr.Model(ep.cov[k], ep.hyper[k], ep.X[k], ep.y[k], ep.noise[k], T) for k in range(len(ep.X))]
         models = [conditioned(b, pending) for b in bases]

@@ -12,6 +12,7 @@ import ei1_deriv_reference as dr
 import ei1_reference as er
 import kg1_reference as kr
 from oracle import orc
+from test_ei1_reference import padded_dim, wide_magnitudes
 
 LD = dr.LD
 
@@ -36,6 +37,31 @@ def test_the_inputs_are_well_conditioned(p):
         assert moved[0] == 0.0 and moved[1] == 0.0
     if p.name == dr.BPRIME:
         assert want[p.checked[0]].bprime < p.best - 1e-3 and p.best == float(p.y[:, 0].max())
+
+
+@pytest.mark.parametrize("p", dr.WIDE_PROBLEMS + dr.WIDE_PROBLEMS_P0, ids=lambda p: p.name)
+def test_the_wide_inputs_are_well_conditioned(p):
+    test_the_inputs_are_well_conditioned(p)
+    want = dr.expected(p, LD)
+    wide_magnitudes(p.name, [(float(want[i].value) / want[i].scale, want[i].grad) for i in p.checked], p.X.shape[1])
+    if len(p.X) >= 256:
+        assert p.best == float(np.median(p.y[:, 0]))
+
+
+def test_the_wide_cases_reach_every_path():
+    names = [p.name for p in dr.WIDE_PROBLEMS + dr.WIDE_PROBLEMS_P0]
+    assert len(set(names)) == len(names) and not set(names) & {p.name for p in dr.PROBLEMS + dr.PROBLEMS_P0}
+    dims = {p.X.shape[1] for p in dr.WIDE_PROBLEMS}
+    assert {16, 24} <= {padded_dim(d) for d in dims} and any(d % 4 for d in dims)  # (12 is dr.PROBLEMS' d = 12 case)
+    assert {12, 16, 24} <= {padded_dim(p.X.shape[1]) for p in dr.PROBLEMS + dr.WIDE_PROBLEMS}
+    big = [p for p in dr.WIDE_PROBLEMS if len(p.X) + len(p.pending) > 256]  # (a second trip of the loop over the points)
+    assert big and all(len(p.derivs) >= 1 and 512 < p.y.size <= 1024 for p in big)  # (and tri_cols' K slice 128)
+    for p in dr.WIDE_PROBLEMS:
+        assert len(p.derivs) >= 1 and len(set(p.noise)) == len(p.noise) == 1 + len(p.derivs)
+        assert 0 in p.checked and np.max(np.abs(p.pending[0] - p.points[0])) <= 0.05
+    assert any(p.derivs[0] != 0 and p.X.shape[1] > 12 for p in dr.WIDE_PROBLEMS) and any(p.cov_type == dr.SE for p in dr.WIDE_PROBLEMS)
+    for p in dr.WIDE_PROBLEMS_P0:
+        assert len(p.pending) == 0
 
 
 def test_the_cases_reach_every_path():
@@ -68,9 +94,9 @@ def test_the_ensemble_is_well_conditioned():
     assert e_v <= 2.5e-11 and e_g <= 2.5e-11 and moved >= 1e-5
 
 
-@pytest.mark.parametrize("name", ["n5_d2_g2_p1", "n40_d4_D023_p5_se", "n20_d6_D05_p3", "n9_d12_g12_p2", dr.BPRIME])
+@pytest.mark.parametrize("name", ["n5_d2_g2_p1", "n40_d4_D023_p5_se", "n20_d6_D05_p3", "n9_d12_g12_p2", dr.BPRIME, "n10_d20_D3_19_p2_se"])
 def test_the_gradient_is_the_central_difference_of_the_value(name):
-    p = [q for q in dr.PROBLEMS if q.name == name][0]
+    p = [q for q in dr.PROBLEMS + dr.WIDE_PROBLEMS if q.name == name][0]
     base = dr.base_model(p, LD)
     model = dr.DerivPendingModel(base, p.pending)
     h, worst = 1e-6, 0.0

@@ -16,6 +16,35 @@ LD = er.LD
 dp, ip = _lib.dp, _lib.ip
 
 
+def padded_dim(d):
+    """the device's padded dimension (csrc/common.hpp): a multiple of 4 up to 16, of 8 beyond"""
+    return 4 * ((d + 3) // 4) if d <= 16 else 8 * ((d + 7) // 8)
+
+
+def wide_magnitudes(name, results, d, at_least=3):
+    """the conditions on the wide cases' inputs beyond tests/ei1_reference.PROBLEMS': `results` are (value / scale, gradient) of the
+    checked candidates in long double.  At `at_least` of them the value is >= 1e-3 scale and the gradient's largest entry >= 1e-2 (an
+    absolute bound of 1e-10 scale means ten digits there, and a device that returned zeros fails); from d = 10 on, at one of them
+    every one of the d gradient coordinates is >= 1e-6 in magnitude (a dropped coordinate exceeds the bound 1e4 times over)."""
+    big = [i for i, (v, g) in enumerate(results) if abs(v) >= 1e-3 and float(np.max(np.abs(g))) >= 1e-2]
+    smallest = max(float(np.min(np.abs(g))) for v, g in results)
+    print("%s: %d of %d checked candidates have |value| >= 1e-3 scale and |gradient| >= 1e-2; the best candidate's smallest gradient "
+          "coordinate is %.3g" % (name, len(big), len(results), smallest))
+    assert len(big) >= at_least
+    if d >= 10:
+        assert all(len(g) == d for v, g in results) and smallest >= 1e-6
+
+
+@pytest.mark.parametrize("p", er.WIDE_PROBLEMS, ids=lambda p: p.name)
+def test_the_wide_inputs_are_well_conditioned(p):
+    test_the_inputs_are_well_conditioned(p)
+    want, _ = er.expected(p, LD)
+    wide_magnitudes(p.name, [(float(want[i].value) / want[i].scale, want[i].grad) for i in p.checked], p.X.shape[1],
+                    3 if len(p.points) > 3 else 2)
+    if len(p.X) >= 256:
+        assert p.best == float(np.median(p.y))
+
+
 @pytest.mark.parametrize("p", er.PROBLEMS, ids=lambda p: p.name)
 def test_the_inputs_are_well_conditioned(p):
     want, without = er.expected(p, LD)
@@ -51,8 +80,30 @@ def test_the_cases_reach_every_path():
     assert len(e["n"]) == 3 and min(e["n"]) < 128 <= max(e["n"]) and len(set(e["factors"])) == 3
 
 
-def test_the_ensemble_is_well_conditioned():
-    ep = er.make_ensemble()
+def test_the_wide_cases_reach_every_path():
+    names = [p.name for p in er.WIDE_PROBLEMS]
+    assert len(set(names)) == len(names) and not set(names) & {p.name for p in er.PROBLEMS}
+    for pending in (True, False):  # with and without pending points
+        some = [p for p in er.WIDE_PROBLEMS if (len(p.pending) > 0) == pending]
+        assert any(padded_dim(p.X.shape[1]) > p.X.shape[1] > 8 for p in some)  # (padded coordinates beyond DP = 8)
+        assert any(len(p.X) + len(p.pending) > 256 for p in some)       # (a second trip of the gradient kernel's row loop)
+    padded = {padded_dim(p.X.shape[1]) for p in er.WIDE_PROBLEMS}
+    assert {12, 16, 24} <= padded
+    rows = [len(p.X) for p in er.WIDE_PROBLEMS if len(p.pending)]
+    assert any(256 < n <= 512 for n in rows) and any(512 < n <= 1024 for n in rows) and any(n > 1024 for n in rows)  # (K slices 64, 128, 192)
+    for p in er.WIDE_PROBLEMS:
+        if len(p.pending):
+            assert 0 in p.checked and np.max(np.abs(p.pending[0] - p.points[0])) <= 0.05
+    e = er.ENSEMBLE_WIDE
+    assert e["d"] == 10 and min(e["n"]) < 256 < sorted(e["n"])[1] <= 512 < max(e["n"]) and len(set(e["factors"])) == 3
+
+
+def test_the_wide_ensemble_is_well_conditioned():
+    test_the_ensemble_is_well_conditioned(er.ENSEMBLE_WIDE)
+
+
+def test_the_ensemble_is_well_conditioned(e=er.ENSEMBLE):
+    ep = er.make_ensemble(e)
     want, w64 = er.ensemble_expected(ep, ep.pending, LD), er.ensemble_expected(ep, ep.pending, np.float64)
     without = er.ensemble_expected(ep, ep.pending[:0], LD)
     e_v = max(abs(float(a[0]) - float(b[0])) / a[2] for a, b in zip(want, w64))
@@ -60,11 +111,13 @@ def test_the_ensemble_is_well_conditioned():
     moved = max(abs(float(a[0] - b[0])) / a[2] for a, b in zip(want, without))
     print("ensemble of 3: float64 against long double %.3g / %.3g; P moves EI by %.3g scale" % (e_v, e_g, moved))
     assert e_v <= 2.5e-11 and e_g <= 2.5e-11 and moved >= 1e-5
+    if e is er.ENSEMBLE_WIDE:
+        wide_magnitudes("the wide ensemble", [(float(a[0]) / a[2], a[1]) for a in want], e["d"])
 
 
-@pytest.mark.parametrize("name", ["n20_d3_A12_p2_fid", "n40_d4_A64_p5_se", "n20_d6_p0", er.BPRIME])
+@pytest.mark.parametrize("name", ["n20_d3_A12_p2_fid", "n40_d4_A64_p5_se", "n20_d6_p0", er.BPRIME, "n20_d13_p3_se"])
 def test_the_gradient_is_the_central_difference_of_the_value(name):
-    p = [q for q in er.PROBLEMS if q.name == name][0]
+    p = [q for q in er.PROBLEMS + er.WIDE_PROBLEMS if q.name == name][0]
     base = er.base_model(p, LD)
     h, worst = 1e-6, 0.0
     for i in p.checked[:3]:

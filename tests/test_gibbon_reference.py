@@ -13,6 +13,7 @@ import ei1_deriv_reference as ed
 import ei1_reference as er
 import gibbon_reference as gr
 from cornell_moe_amd import _lib, build as moe_build
+from test_ei1_reference import padded_dim, wide_magnitudes
 
 LD = gr.LD
 dp, ip = _lib.dp, _lib.ip
@@ -49,6 +50,33 @@ def test_the_inputs_are_well_conditioned(p):
         assert g_lo < 0.0
 
 
+@pytest.mark.parametrize("p", gr.WIDE_PROBLEMS, ids=lambda p: p.name)
+def test_the_wide_inputs_are_well_conditioned(p):
+    """two candidates, not three, have to carry a value and a gradient of size: a case may check as few as two (the condition
+    above), and the 1e-5 movement by the min-values already fails a device whose terms vanish"""
+    test_the_inputs_are_well_conditioned(p)
+    want = gr.expected(p, LD)[0]
+    wide_magnitudes(p.name, [(float(want[i].value) / want[i].scale, want[i].grad) for i in p.checked], p.X.shape[1], 2)
+
+
+def test_the_wide_cases_reach_every_path():
+    names = [p.name for p in gr.WIDE_PROBLEMS]
+    assert len(set(names)) == len(names) and not set(names) & {p.name for p in gr.PROBLEMS}
+    plain = {padded_dim(p.X.shape[1]) for p in gr.WIDE_PROBLEMS if not len(p.derivs)}
+    deriv = {padded_dim(p.X.shape[1]) for p in gr.WIDE_PROBLEMS if len(p.derivs)}
+    assert {16, 24} <= plain and 16 in deriv and any(p.X.shape[1] % 4 for p in gr.WIDE_PROBLEMS)
+    assert {63, 65} <= {len(p.mins) for p in gr.WIDE_PROBLEMS}
+    big = [p for p in gr.WIDE_PROBLEMS if len(p.mins) > 128]
+    assert big and all(p.y.size > 256 and p.y.size % 64 and len(p.pending) for p in big)  # (five row trips, the last one partial)
+    for p in gr.WIDE_PROBLEMS:
+        assert len(p.pending) and np.max(np.abs(p.pending[0] - p.points[0])) <= 0.05
+    p = [q for q in gr.WIDE_PROBLEMS if q.name == gr.WIDE_N300][0]
+    low = p.X[np.argsort(p.y[:, 0])[:5]]
+    assert np.max(np.abs(p.points - low)) <= 0.05
+    ep, mins = gr.make_ensemble(er.ENSEMBLE_WIDE)
+    assert [len(x) for x in ep.X] == [20, 300, 600] and ep.points.shape[1] == 10 and mins.shape == (3, gr.ENSEMBLE_K)
+
+
 def test_the_cases_reach_every_path():
     names = [p.name for p in gr.PROBLEMS]
     assert len(set(names)) == len(names) == 16 and names[:12] == [q.name for q in er.PROBLEMS]
@@ -65,8 +93,12 @@ def test_the_cases_reach_every_path():
     assert [len(x) for x in ep.X] == [12, 130, 40] and mins.shape == (3, gr.ENSEMBLE_K)
 
 
-def test_the_ensemble_is_well_conditioned():
-    ep, mins = gr.make_ensemble()
+def test_the_wide_ensemble_is_well_conditioned():
+    test_the_ensemble_is_well_conditioned(er.ENSEMBLE_WIDE)
+
+
+def test_the_ensemble_is_well_conditioned(e=er.ENSEMBLE):
+    ep, mins = gr.make_ensemble(e)
     want, w64 = gr.ensemble_expected(ep, mins, ep.pending, LD), gr.ensemble_expected(ep, mins, ep.pending, np.float64)
     without = gr.ensemble_expected(ep, mins, ep.pending[:0], LD)
     e_v = max(abs(float(a[0]) - float(b[0])) / a[2] for a, b in zip(want, w64))
@@ -74,11 +106,14 @@ def test_the_ensemble_is_well_conditioned():
     moved = max(abs(float(a[0] - b[0])) / a[2] for a, b in zip(want, without))
     print("ensemble of 3: float64 against long double %.3g / %.3g; P moves the value by %.3g scale" % (e_v, e_g, moved))
     assert e_v <= 2.5e-11 and e_g <= 2.5e-11 and moved >= 1e-5
+    if e is er.ENSEMBLE_WIDE:
+        wide_magnitudes("the wide ensemble", [(float(a[0]) / a[2], a[1]) for a in want], e["d"])
 
 
-@pytest.mark.parametrize("name", ["n20_d3_A12_p2_fid", "n40_d4_A64_p5_se", "n20_d6_p0", gr.NEGATIVE, gr.G2, gr.NOISE_FREE])
+@pytest.mark.parametrize("name", ["n20_d3_A12_p2_fid", "n40_d4_A64_p5_se", "n20_d6_p0", gr.NEGATIVE, gr.G2, gr.NOISE_FREE,
+                                  "n10_d13_D0_12_p2"])
 def test_the_gradient_is_the_central_difference_of_the_value(name):
-    p = [q for q in gr.PROBLEMS if q.name == name][0]
+    p = [q for q in gr.PROBLEMS + gr.WIDE_PROBLEMS if q.name == name][0]
     base = gr.base_model(p, LD)
     model = gr.conditioned(base, p.pending)
     h, worst = 1e-6, 0.0

@@ -1,6 +1,6 @@
 """The ensemble analytic expected improvement on the device (csrc/ei1.hip: moe_ei_analytic_mcmc, moe_ei_analytic_mcmc_multistart,
-moe_ei_analytic_mcmc_suggest) against the long-double restatement of tests/ei1_reference.py, on the cases ei1_reference.PROBLEMS,
-whose inputs tests/test_ei1_reference.py qualifies on the CPU (float64 within 2.5e-11 scale of long double, sigma >= 0.05
+moe_ei_analytic_mcmc_suggest) against the long-double restatement of tests/ei1_reference.py, on the cases ei1_reference.PROBLEMS
+and WIDE_PROBLEMS (padded dimensions 12 to 24, more than 256 rows, tri_cols' wider K slices), whose inputs tests/test_ei1_reference.py qualifies on the CPU (float64 within 2.5e-11 scale of long double, sigma >= 0.05
 sqrt(alpha), P moves a checked candidate's value by >= 1e-5 scale: a device that ignored P fails here).
 
 Tolerances: tests/test_gpu_kg1.py's for the same products and sums -- |EI - want| <= 1e-10 scale, |grad EI - want|_inf <= 1e-10
@@ -71,7 +71,7 @@ def _errors(ei, grad, want, checked):
 
 
 # ---- 1. value and gradient against long double ----
-@pytest.mark.parametrize("p", er.PROBLEMS, ids=lambda p: p.name)
+@pytest.mark.parametrize("p", er.PROBLEMS + er.WIDE_PROBLEMS, ids=lambda p: p.name)
 def test_against_the_long_double_restatement(p):
     want, without = er.expected(p)
     G = _gp(p)
@@ -164,12 +164,61 @@ def test_a_candidate_carries_its_bits_across_the_pass_boundary():
     G.close()
 
 
+# more than 4096 rows: the pass is no longer the 4096 cap but follows from N (2^24 doubles of V per pass), and a call of 4036
+# candidates is one pass of 4032 and one of 4.  (Seed chosen on the CPU: EI >= 1e-2 scale at all four checked candidates, and b'
+# binds; with most seeds mu(P) lies so far below the median that one or two of the four have an EI below 1e-4.)
+_N4097 = kp.Case("n4097_d4_p2_short_pass", 48, 4097, 4, 1, 2, 0, kr.MATERN, 1e-2, 4036)
+
+
+def short_pass_problem():
+    per_pass = _lib.load().moe_ei1_pass_size(_N4097.n)
+    assert per_pass == 4032 and _N4097.C == per_pass + 4
+    q = kp.make_problem(_N4097)
+    return er.Problem(_N4097.name, _N4097.cov_type, q.hyper, q.X, q.y, q.noise, q.points, q.pending, float(np.median(q.y)),
+                      (0, per_pass - 1, per_pass, _N4097.C - 1))
+
+
+def test_a_pass_shorter_than_4096_candidates_above_4096_rows():
+    """value-only against value + gradient and a candidate alone against itself in the batch, bit for bit, on both sides of the
+    boundary at 4032; those four candidates against tests/ei1_reference.py in FLOAT64 (a long-double factorisation of 4099 rows takes
+    minutes): 1e-9 scale in value and 1e-9 max(1, |want|) in gradient.  At N = 4097 the float64 restatement lies 6.9e-13 / 4.8e-12
+    from long double (one run in d = 2), so the bound is 200 times the reference's own error, and an offset or a width that is off
+    by one column moves a value by 1e-3 or more."""
+    p = short_pass_problem()
+    base = er.base_model(p, np.float64)
+    P = np.asarray(p.pending, dtype=np.float64)
+    model = kp.PendingModel(base, P)
+    y_max = float(np.max(np.abs(p.y)))
+    want = {i: er.evaluate_model(model, base, P, p.points[i], p.best, y_max) for i in p.checked}
+    big = [i for i in p.checked if float(want[i].value) >= 1e-3 * want[i].scale and float(np.max(np.abs(want[i].grad))) >= 1e-2]
+    assert len(big) == 4 and p.best == float(np.median(p.y)) and want[0].bprime < p.best - 1e-2
+    G = _gp(p)
+    for pending in (p.pending, None):
+        ei, grad = api.ei_analytic_ensemble(G, p.points, [p.best], points_being_sampled=pending)
+        assert np.all(np.isfinite(ei)) and np.all(np.isfinite(grad))
+        assert np.array_equal(api.ei_analytic_ensemble(G, p.points, [p.best], points_being_sampled=pending, want_grad=False), ei)
+        for i in p.checked:
+            e1, g1 = api.ei_analytic_ensemble(G, p.points[i:i + 1], [p.best], points_being_sampled=pending)
+            assert e1[0] == ei[i] and np.array_equal(g1[0], grad[i]), i
+        if pending is not None:
+            e_v, e_g = _errors(ei, grad, want, p.checked)
+            print("%s: value error %.3g scale, gradient error %.3g against the float64 restatement on both sides of the pass boundary "
+                  "(bounds 1e-9); EI / scale of the four %s" % (p.name, e_v, e_g, [float(want[i].value) / want[i].scale for i in p.checked]))
+            assert e_v <= 1e-9 and e_g <= 1e-9
+    G.close()
+
+
 def _ensemble_gps(ep):
     return [api.DeviceGP(ep.hyper[k], ep.X[k], ep.y[k], ep.noise[k], cov_type=ep.cov[k]) for k in range(len(ep.X))]
 
 
-def test_an_ensemble_of_three_against_long_double_and_its_members_launches_on_and_off():
-    ep = er.make_ensemble()
+def test_the_wide_ensemble_against_long_double_and_its_members_launches_on_and_off():
+    """padded dimension 12, members of 20, 300 and 600 rows: tri_cols' K slices 64 and 128 and a member below 128 rows in one call"""
+    test_an_ensemble_of_three_against_long_double_and_its_members_launches_on_and_off(er.ENSEMBLE_WIDE)
+
+
+def test_an_ensemble_of_three_against_long_double_and_its_members_launches_on_and_off(e=er.ENSEMBLE):
+    ep = er.make_ensemble(e)
     gps = _ensemble_gps(ep)
     for pending in (ep.pending, ep.pending[:0]):
         want = er.ensemble_expected(ep, pending, LD)
@@ -181,7 +230,8 @@ def test_an_ensemble_of_three_against_long_double_and_its_members_launches_on_an
         assert np.array_equal(ei, runs[1][0]) and np.array_equal(grad, runs[1][1])
         e_v = max(abs(ei[i] - float(w[0])) / w[2] for i, w in enumerate(want))
         e_g = max(float(np.max(np.abs(grad[i] - w[1].astype(np.float64)))) / max(1.0, float(np.max(np.abs(w[1])))) for i, w in enumerate(want))
-        print("ensemble of 3, %d pending: value error %.3g scale, gradient error %.3g (bounds 1e-10)" % (len(pending), e_v, e_g))
+        print("ensemble of 3 (d = %d, n = %s), %d pending: value error %.3g scale, gradient error %.3g (bounds 1e-10)" % (
+            e["d"], e["n"], len(pending), e_v, e_g))
         assert e_v <= 1e-10 and e_g <= 1e-10
         # the members' own E = 1 results, added on the host in member order and divided once
         single = [api.ei_analytic_ensemble(g, ep.points, [b], points_being_sampled=pending) for g, b in zip(gps, ep.best)]
@@ -211,10 +261,11 @@ def test_a_sampled_point_of_a_noise_free_gp_returns_zero_not_an_error():
 
 # ---- 5. the ascent against the host-driven loop ----
 MS = dict(starts=12, steps=6, restarts=2, gamma=0.7, pre_mult=1.0, max_rel=0.5)
+MS_WIDE = dict(MS, starts=6, steps=4, restarts=1)  # (the host-driven loop over 920 rows in 10 dimensions stays within seconds)
 
 
-def _ascent_problem(tolerance):
-    ep = er.make_ensemble()
+def _ascent_problem(tolerance, e=er.ENSEMBLE, MS=MS):
+    ep = er.make_ensemble(e)
     rng = np.random.default_rng(77)
     starts = rng.uniform(0.02, 0.98, size=(MS["starts"], ep.points.shape[1]))
     gd = (MS["starts"], MS["steps"], MS["restarts"], 0, MS["gamma"], MS["pre_mult"], MS["max_rel"], tolerance)
@@ -292,6 +343,44 @@ def test_the_ascent_is_the_host_driven_loop_bit_for_bit(tolerance):
     best = int(np.argmax(want["start_values"]))
     assert np.array_equal(none["point"], starts[best]) and none["value"] == want["start_values"][best] and none["found"]
     assert np.array_equal(none["start_values"], want["start_values"])
+    _close(gps)
+
+
+def test_the_ascent_on_the_wide_ensemble_is_the_host_driven_loop_bit_for_bit():
+    """the ascent's own staging and step at padded dimension 12 over members of 20, 300 and 600 rows"""
+    ep, starts, gd, bounds = _ascent_problem(1e-10, er.ENSEMBLE_WIDE, MS_WIDE)
+    gps = _ensemble_gps(ep)
+    pending = ep.pending[:2]
+    want = _host_loop(gps, ep, starts, gd, bounds, pending)
+    plain = api.ei_analytic_multistart(gps, gd, bounds, ep.best, starts)
+    assert not np.array_equal(plain["start_values"], want["start_values"])  # (the pending points are not ignored)
+    for on in (True, False):
+        with _Launches(on):
+            got = api.ei_analytic_multistart(gps, gd, bounds, ep.best, starts, want_path=True, points_being_sampled=pending)
+        diff = np.argwhere(np.any(got["path"] != want["path"], axis=2))
+        assert diff.size == 0, (on, "the paths part at (start, row)", diff[np.argmin(diff[:, 1])])
+        _same_run(got, want)
+    moved = float(np.max(np.abs(want["end_points"] - starts[want["kept_index"]])))
+    print("wide ensemble: %d kept starts, steps taken %s, value %.12g against the best start's %.12g; the ends lie up to %.3g from "
+          "their starts" % (len(want["kept_index"]), [int(k) for k in want["steps_taken"]], want["value"], want["start_values"].max(), moved))
+    assert want["found"] and len(want["kept_index"]) == MS_WIDE["starts"] and moved > 1e-3 and int(want["steps_taken"].max()) == 4
+    _close(gps)
+
+
+def test_the_batch_on_the_wide_ensemble_is_the_ascent_fed_its_predecessor_bit_for_bit():
+    ep, starts, gd, bounds = _ascent_problem(1e-10, er.ENSEMBLE_WIDE, MS_WIDE)
+    gps = _ensemble_gps(ep)
+    pending = ep.pending[:1]
+    first = api.ei_analytic_multistart(gps, gd, bounds, ep.best, starts, points_being_sampled=pending)
+    second = api.ei_analytic_multistart(gps, gd, bounds, ep.best, starts, points_being_sampled=np.vstack([pending, first["point"][None, :]]))
+    assert first["found"] and second["found"]
+    for on in (True, False):
+        with _Launches(on):
+            got = api.ei_analytic_suggest(gps, gd, bounds, ep.best, starts, 2, points_being_sampled=pending)
+        assert np.array_equal(got["points"], np.array([first["point"], second["point"]])), on
+        assert np.array_equal(got["values"], np.array([first["value"], second["value"]])) and np.all(got["found"])
+    print("wide ensemble: greedy values %.12g, %.12g; the second pick lies %.3g from the first" % (
+        first["value"], second["value"], float(np.max(np.abs(second["point"] - first["point"])))))
     _close(gps)
 
 

@@ -1,6 +1,6 @@
 """The ensemble analytic expected improvement of GPs with derivative observations on the device (csrc/ei1.hip with
 csrc/kg1_pending.hip's rows of 1 + g believed observations per pending point) against the long-double restatement of
-tests/ei1_deriv_reference.py, on its PROBLEMS with and without their pending points.  tests/test_ei1_deriv_reference.py qualifies the
+tests/ei1_deriv_reference.py, on its PROBLEMS and WIDE_PROBLEMS with and without their pending points.  tests/test_ei1_deriv_reference.py qualifies the
 inputs on the CPU: float64 within 2.5e-11 scale of long double, sigma >= 0.05 sqrt(alpha), and P, P's derivative rows and X's
 derivative observations each move a checked candidate's value by >= 1e-5 scale, so a device that dropped any of them fails here.
 
@@ -29,7 +29,7 @@ def _gp(p):
 
 
 # ---- 1. value and gradient against long double, with and without P ----
-@pytest.mark.parametrize("p", dr.PROBLEMS + dr.PROBLEMS_P0, ids=lambda p: p.name)
+@pytest.mark.parametrize("p", dr.PROBLEMS + dr.PROBLEMS_P0 + dr.WIDE_PROBLEMS + dr.WIDE_PROBLEMS_P0, ids=lambda p: p.name)
 def test_against_the_long_double_restatement(p):
     want = dr.expected(p)
     G = _gp(p)

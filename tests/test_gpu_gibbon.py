@@ -1,6 +1,6 @@
 """The ensemble min-value entropy acquisition GIBBON on the device (csrc/gibbon1.hip: moe_gibbon_mcmc, moe_gibbon_mcmc_multistart,
-moe_gibbon_mcmc_suggest) against the long-double restatement of tests/gibbon_reference.py, on the cases gibbon_reference.PROBLEMS,
-whose inputs tests/test_gibbon_reference.py qualifies on the CPU (float64 within 2.5e-11 scale of long double, gamma in [-6, 40],
+moe_gibbon_mcmc_suggest) against the long-double restatement of tests/gibbon_reference.py, on the cases gibbon_reference.PROBLEMS
+and WIDE_PROBLEMS, whose inputs tests/test_gibbon_reference.py qualifies on the CPU (float64 within 2.5e-11 scale of long double, gamma in [-6, 40],
 sigma0 >= 0.05 sqrt(alpha), P and the min-values each move a checked candidate's value by >= 1e-5 scale: a device that ignored
 either fails here).
 
@@ -15,6 +15,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import ei1_reference as er
 import gibbon_reference as gr
 import kg1_pending_reference as kp
 import kg1_reference as kr
@@ -71,7 +72,7 @@ def _errors(value, grad, want, which):
 
 
 # ---- 1. value and gradient against long double ----
-@pytest.mark.parametrize("p", gr.PROBLEMS, ids=lambda p: p.name)
+@pytest.mark.parametrize("p", gr.PROBLEMS + gr.WIDE_PROBLEMS, ids=lambda p: p.name)
 def test_against_the_long_double_restatement(p):
     want, without, _ = gr.expected(p)
     G = _gp(p)
@@ -122,12 +123,39 @@ def test_a_candidate_carries_its_bits_across_the_pass_boundary():
     G.close()
 
 
+def test_a_pass_shorter_than_4096_candidates_above_4096_rows():
+    """tests/test_gpu_ei1.py's 4097-row GP, where a pass holds 4032 candidates, under 64 min-values spread about the median of y
+    (gamma on both sides of 0): value-only against value + gradient and a candidate alone against itself in the batch, bit for bit,
+    on both sides of the boundary"""
+    from test_gpu_ei1 import short_pass_problem
+    q = short_pass_problem()
+    mins = q.best + np.linspace(-0.3, 0.1, 64)
+    G = api.DeviceGP(q.hyper, q.X, q.y, q.noise, cov_type=q.cov_type)
+    for pending in (q.pending, None):
+        value, grad = api.gibbon_ensemble(G, q.points, mins, points_being_sampled=pending)
+        assert np.all(np.isfinite(value)) and np.all(np.isfinite(grad))
+        assert np.array_equal(api.gibbon_ensemble(G, q.points, mins, points_being_sampled=pending, want_grad=False), value)
+        for i in q.checked:
+            v1, g1 = api.gibbon_ensemble(G, q.points[i:i + 1], mins, points_being_sampled=pending)
+            assert v1[0] == value[i] and np.array_equal(g1[0], grad[i]), i
+        print("%s, %s pending: values of the four %s, their largest |gradient| entries %s" % (
+            q.name, "2" if pending is not None else "no", [float(value[i]) for i in q.checked],
+            [float(np.max(np.abs(grad[i]))) for i in q.checked]))
+        assert all(abs(value[i]) > 1e-6 and np.max(np.abs(grad[i])) > 1e-6 for i in q.checked)  # (no comparison of zeros)
+    G.close()
+
+
 def _ensemble_gps(ep):
     return [api.DeviceGP(ep.hyper[k], ep.X[k], ep.y[k], ep.noise[k], cov_type=ep.cov[k]) for k in range(len(ep.X))]
 
 
-def test_an_ensemble_of_three_against_long_double_and_its_members_launches_on_and_off():
-    ep, mins = gr.make_ensemble()
+def test_the_wide_ensemble_against_long_double_and_its_members_launches_on_and_off():
+    """padded dimension 12, members of 20, 300 and 600 rows: tri_cols' K slices 64 and 128 and a member below 128 rows in one call"""
+    test_an_ensemble_of_three_against_long_double_and_its_members_launches_on_and_off(er.ENSEMBLE_WIDE)
+
+
+def test_an_ensemble_of_three_against_long_double_and_its_members_launches_on_and_off(e=er.ENSEMBLE):
+    ep, mins = gr.make_ensemble(e)
     gps = _ensemble_gps(ep)
     for pending in (ep.pending, ep.pending[:0]):
         want = gr.ensemble_expected(ep, mins, pending, LD)
@@ -139,7 +167,8 @@ def test_an_ensemble_of_three_against_long_double_and_its_members_launches_on_an
         assert np.array_equal(value, runs[1][0]) and np.array_equal(grad, runs[1][1])
         e_v = max(abs(value[i] - float(w[0])) / w[2] for i, w in enumerate(want))
         e_g = max(float(np.max(np.abs(grad[i] - w[1].astype(np.float64)))) / w[2] for i, w in enumerate(want))
-        print("ensemble of 3, %d pending: value error %.3g scale, gradient error %.3g scale (bounds 1e-10)" % (len(pending), e_v, e_g))
+        print("ensemble of 3 (d = %d, n = %s), %d pending: value error %.3g scale, gradient error %.3g scale (bounds 1e-10)" % (
+            e["d"], e["n"], len(pending), e_v, e_g))
         assert e_v <= 1e-10 and e_g <= 1e-10
         # the members' own E = 1 results, added on the host in member order and divided once
         single = [api.gibbon_ensemble(g, ep.points, m, points_being_sampled=pending) for g, m in zip(gps, mins)]
@@ -191,10 +220,11 @@ def test_a_sampled_point_of_a_noise_free_gp_has_a_finite_value_and_gradient():
 
 # ---- 4. the ascent against the host-driven loop ----
 MS = dict(starts=12, steps=6, restarts=2, gamma=0.7, pre_mult=1.0, max_rel=0.5)
+MS_WIDE = dict(MS, starts=6, steps=4, restarts=1)  # (the host-driven loop over 920 rows in 10 dimensions stays within seconds)
 
 
-def _ascent_problem(tolerance):
-    ep, mins = gr.make_ensemble()
+def _ascent_problem(tolerance, e=er.ENSEMBLE, MS=MS):
+    ep, mins = gr.make_ensemble(e)
     rng = np.random.default_rng(77)
     starts = rng.uniform(0.02, 0.98, size=(MS["starts"], ep.points.shape[1]))
     gd = (MS["starts"], MS["steps"], MS["restarts"], 0, MS["gamma"], MS["pre_mult"], MS["max_rel"], tolerance)
@@ -273,6 +303,44 @@ def test_the_ascent_is_the_host_driven_loop_bit_for_bit(tolerance):
     assert np.array_equal(none["point"], starts[best]) and none["value"] == want["start_values"][best] and none["found"]
     assert np.array_equal(none["start_values"], want["start_values"])
     assert none["kept_index"] is None and none["end_points"] is None
+    _close(gps)
+
+
+def test_the_ascent_on_the_wide_ensemble_is_the_host_driven_loop_bit_for_bit():
+    """the ascent's own staging and step at padded dimension 12 over members of 20, 300 and 600 rows"""
+    ep, mins, starts, gd, bounds = _ascent_problem(1e-10, er.ENSEMBLE_WIDE, MS_WIDE)
+    gps = _ensemble_gps(ep)
+    pending = ep.pending[:2]
+    want = _host_loop(gps, mins, starts, gd, bounds, pending)
+    plain = api.gibbon_multistart(gps, gd, bounds, mins, starts)
+    assert not np.array_equal(plain["start_values"], want["start_values"])  # (the pending points are not ignored)
+    for on in (True, False):
+        with _Launches(on):
+            got = api.gibbon_multistart(gps, gd, bounds, mins, starts, want_path=True, points_being_sampled=pending)
+        diff = np.argwhere(np.any(got["path"] != want["path"], axis=2))
+        assert diff.size == 0, (on, "the paths part at (start, row)", diff[np.argmin(diff[:, 1])])
+        _same_run(got, want)
+    moved = float(np.max(np.abs(want["end_points"] - starts[want["kept_index"]])))
+    print("wide ensemble: %d kept starts, steps taken %s, value %.12g against the best start's %.12g; the ends lie up to %.3g from "
+          "their starts" % (len(want["kept_index"]), [int(k) for k in want["steps_taken"]], want["value"], want["start_values"].max(), moved))
+    assert want["found"] and len(want["kept_index"]) == MS_WIDE["starts"] and moved > 1e-3 and int(want["steps_taken"].max()) == 4
+    _close(gps)
+
+
+def test_the_batch_on_the_wide_ensemble_is_the_ascent_fed_its_predecessor_bit_for_bit():
+    ep, mins, starts, gd, bounds = _ascent_problem(1e-10, er.ENSEMBLE_WIDE, MS_WIDE)
+    gps = _ensemble_gps(ep)
+    pending = ep.pending[:1]
+    first = api.gibbon_multistart(gps, gd, bounds, mins, starts, points_being_sampled=pending)
+    second = api.gibbon_multistart(gps, gd, bounds, mins, starts, points_being_sampled=np.vstack([pending, first["point"][None, :]]))
+    assert first["found"] and second["found"]
+    for on in (True, False):
+        with _Launches(on):
+            got = api.gibbon_suggest(gps, gd, bounds, mins, starts, 2, points_being_sampled=pending)
+        assert np.array_equal(got["points"], np.array([first["point"], second["point"]])), on
+        assert np.array_equal(got["values"], np.array([first["value"], second["value"]])) and np.all(got["found"])
+    print("wide ensemble: greedy values %.12g, %.12g; the second pick lies %.3g from the first" % (
+        first["value"], second["value"], float(np.max(np.abs(second["point"] - first["point"])))))
     _close(gps)
 
 
