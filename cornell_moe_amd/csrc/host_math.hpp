@@ -23,7 +23,6 @@ struct StateLayout {
   int c() const { return m + nd * (1 + gt) * d + A; }
   int col_kstar(int j, int b) const { return j * (1 + gt) + b; }
   int col_grad(int i, int a, int dd) const { return m + (i * (1 + gt) + a) * d + dd; }
-  int col_extra(int j) const { return m + nd * (1 + gt) * d + j; }
 };
 
 struct StateHost {

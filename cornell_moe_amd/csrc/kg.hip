@@ -6,7 +6,7 @@
 //      (tile GEMMs against the explicit inverse factor) -> Gram matrices; ONE device->host sync brings the c x c Grams back
 //      and the m x m algebra of PointsToSampleState / KnowledgeGradientState (gpp_math.cpp:600-653,
 //      gpp_knowledge_gradient_optimization.cpp:292-317) runs on the host (host_math.hip);
-//   2. MC kernel (kg_mc.hpp): persistent wavefronts, one MC sample at a time per wave, all E evaluations in one launch;
+//   2. MC kernel (kg_mc.hpp and its family headers kg_mc_{wave,lane,stream,block}.hpp): persistent wavefronts, one MC sample at a time per wave, all E evaluations in one launch;
 //   3. gradient tail (.cpp:199-225 restated so that nothing of size M x (q d) is ever formed):
 //        T   = K(X, x*_i) for every sample                      (covariance build, N x M per evaluation, HBM write-bound)
 //        c_i = L^-1 ( K(Xu, x*_i) - W^T T_i )                   (kg_sw_kernel: one wave per sample)
@@ -88,7 +88,7 @@ struct build_xs_tab_kernel_body {
       v = X[(long)j * dp + k];
     else if (j < n + u)
       v = XuAll[((long)e * u + (j - n)) * dp + k];
-    // (pair_rows: the rows of a point in pairs, [tile][dp / 2][64][2] -- one 16-byte load per lane and pair, kg_mc.hpp WideEval)
+    // (pair_rows: the rows of a point in pairs, [tile][dp / 2][64][2] -- one 16-byte load per lane and pair, kg_mc_lds.hpp WideEval)
     const long out = pair_rows ? (((long)t * (dp / 2) + (r >> 1)) * 64 + l) * 2 + (r & 1) : idx;
     tab[(long)e * tab_stride + out] = (v - tp.center[r]) * tp.inv_lp[r];
   }
@@ -1239,7 +1239,7 @@ struct kg_sample_weights_kernel_body {
     const double scale = (a == 0) ? P.alpha : -P.alpha * P.inv_lp[a > 0 ? a - 1 : 0];
     const int s0 = blockIdx.y * samples_per_block, s1 = min(P.num_local, s0 + samples_per_block);
     // rows behind the training set (v_stride > N: the streamed-weights MC kernel reads whole tiles): the fantasy points' weights are the
-    // sample's beta itself, scaled like a training row (kg_mc.hpp kg_sample), then zeros up to the end of the last tile
+    // sample's beta itself, scaled like a training row (kg_mc_wave.hpp kg_sample), then zeros up to the end of the last tile
     const int cf = r - P.N;
     const bool fantasy = cf >= 0 && cf < m;
     const double fscale = ((cf % g1) == 0) ? P.alpha : -P.alpha * P.inv_lp[max(cf % g1, 1) - 1];
@@ -1348,46 +1348,46 @@ void launch_sample_weights(const KgMcParams& P, double* V, hipStream_t s, bool t
 
 void launch_mc(const KgMcParams& P, int dp, int G, bool xlds, int blocks, int waves, size_t shm, hipStream_t s) {
   switch (dp) {
-    case 4: launch_kg_mc_dp4(P, G, xlds, blocks, waves, shm, s); break;
-    case 8: launch_kg_mc_dp8(P, G, xlds, blocks, waves, shm, s); break;
-    case 12: launch_kg_mc_dp12(P, G, xlds, blocks, waves, shm, s); break;
-    case 16: launch_kg_mc_dp16(P, G, xlds, blocks, waves, shm, s); break;
-    case 24: launch_kg_mc_dp24(P, G, xlds, blocks, waves, shm, s); break;
-    case 32: launch_kg_mc_dp32(P, G, xlds, blocks, waves, shm, s); break;
+    case 4: mc::launch_dp<4>(P, G, xlds, blocks, waves, shm, s); break;
+    case 8: mc::launch_dp<8>(P, G, xlds, blocks, waves, shm, s); break;
+    case 12: mc::launch_dp<12>(P, G, xlds, blocks, waves, shm, s); break;
+    case 16: mc::launch_dp<16>(P, G, xlds, blocks, waves, shm, s); break;
+    case 24: mc::launch_dp<24>(P, G, xlds, blocks, waves, shm, s); break;
+    case 32: mc::launch_dp<32>(P, G, xlds, blocks, waves, shm, s); break;
     default: throw Error(MOE_ERR_RUNTIME, "unsupported padded dimension");
   }
 }
 
 void launch_mc_lane(const KgMcParams& P, int dp, int G, int rec_head, int blocks, int waves, size_t shm, hipStream_t s) {
   switch (dp) {
-    case 4: launch_kg_mc_lane_dp4(P, G, rec_head, blocks, waves, shm, s); break;
-    case 8: launch_kg_mc_lane_dp8(P, G, rec_head, blocks, waves, shm, s); break;
-    case 12: launch_kg_mc_lane_dp12(P, G, rec_head, blocks, waves, shm, s); break;
-    case 16: launch_kg_mc_lane_dp16(P, G, rec_head, blocks, waves, shm, s); break;
+    case 4: mc::launch_lane_dp<4>(P, G, rec_head, blocks, waves, shm, s); break;
+    case 8: mc::launch_lane_dp<8>(P, G, rec_head, blocks, waves, shm, s); break;
+    case 12: mc::launch_lane_dp<12>(P, G, rec_head, blocks, waves, shm, s); break;
+    case 16: mc::launch_lane_dp<16>(P, G, rec_head, blocks, waves, shm, s); break;
     default: throw Error(MOE_ERR_RUNTIME, "unsupported padded dimension in the lane-parked MC kernel");
   }
 }
 
 void launch_mc_stream(const KgMcParams& P, int dp, int G, int blocks, int waves, size_t shm, hipStream_t s) {
   switch (dp) {
-    case 4: launch_kg_mc_stream_dp4(P, G, blocks, waves, shm, s); break;
-    case 8: launch_kg_mc_stream_dp8(P, G, blocks, waves, shm, s); break;
-    case 12: launch_kg_mc_stream_dp12(P, G, blocks, waves, shm, s); break;
-    case 16: launch_kg_mc_stream_dp16(P, G, blocks, waves, shm, s); break;
-    case 24: launch_kg_mc_stream_dp24(P, G, blocks, waves, shm, s); break;
-    case 32: launch_kg_mc_stream_dp32(P, G, blocks, waves, shm, s); break;
+    case 4: mc::launch_stream_dp<4>(P, G, blocks, waves, shm, s); break;
+    case 8: mc::launch_stream_dp<8>(P, G, blocks, waves, shm, s); break;
+    case 12: mc::launch_stream_dp<12>(P, G, blocks, waves, shm, s); break;
+    case 16: mc::launch_stream_dp<16>(P, G, blocks, waves, shm, s); break;
+    case 24: mc::launch_stream_dp<24>(P, G, blocks, waves, shm, s); break;
+    case 32: mc::launch_stream_dp<32>(P, G, blocks, waves, shm, s); break;
     default: throw Error(MOE_ERR_RUNTIME, "unsupported padded dimension");
   }
 }
 
 void launch_mc_block(const KgMcParams& P, int dp, int G, int tr, int num_lds_tiles, int blocks, int waves, hipStream_t s) {
   switch (dp) {
-    case 4: launch_kg_mc_block_dp4(P, G, tr, num_lds_tiles, blocks, waves, s); break;
-    case 8: launch_kg_mc_block_dp8(P, G, tr, num_lds_tiles, blocks, waves, s); break;
-    case 12: launch_kg_mc_block_dp12(P, G, tr, num_lds_tiles, blocks, waves, s); break;
-    case 16: launch_kg_mc_block_dp16(P, G, tr, num_lds_tiles, blocks, waves, s); break;
-    case 24: launch_kg_mc_block_dp24(P, G, tr, num_lds_tiles, blocks, waves, s); break;
-    case 32: launch_kg_mc_block_dp32(P, G, tr, num_lds_tiles, blocks, waves, s); break;
+    case 4: mc::launch_block_dp<4>(P, G, tr, num_lds_tiles, blocks, waves, s); break;
+    case 8: mc::launch_block_dp<8>(P, G, tr, num_lds_tiles, blocks, waves, s); break;
+    case 12: mc::launch_block_dp<12>(P, G, tr, num_lds_tiles, blocks, waves, s); break;
+    case 16: mc::launch_block_dp<16>(P, G, tr, num_lds_tiles, blocks, waves, s); break;
+    case 24: mc::launch_block_dp<24>(P, G, tr, num_lds_tiles, blocks, waves, s); break;
+    case 32: mc::launch_block_dp<32>(P, G, tr, num_lds_tiles, blocks, waves, s); break;
     default: throw Error(MOE_ERR_RUNTIME, "unsupported padded dimension");
   }
 }
@@ -1480,7 +1480,7 @@ McPlan plan_mc(const GpDev& gp, const KgDims& k, const double* bounds, const dou
   const int d = k.d, dp = k.dp, n = k.n, g = k.g, m = k.m, u = k.u, A = k.A, E = k.E, num_local = k.num_local;
   // derivative-weight slots of the MC kernel instantiation: one per observed derivative up to 4, then 8 or 12 (unused slots
   // carry zero weights); more than 4 always take the workgroup-per-sample kernel
-  // (d > 16: slot counts {0, 4, 8, 12} only -- kg_mc.hpp launch_dp_wide)
+  // (d > 16: slot counts {0, 4, 8, 12} only -- the DP > 16 sets of launch_dp / launch_block_dp / launch_stream_dp)
   const bool wide_dp = dp > 16;
   const int G = wide_dp ? (g == 0 ? 0 : (g <= 4 ? 4 : (g <= 8 ? 8 : 12))) : (g <= 4 ? g : (g <= 8 ? 8 : 12));
   const int ntiles = (n + u + 63) / 64;
@@ -1488,7 +1488,7 @@ McPlan plan_mc(const GpDev& gp, const KgDims& k, const double* bounds, const dou
   // ---- MC launch geometry: workgroup = `waves` wavefronts sharing one LDS coordinate table ----
   const size_t tab_bytes = sizeof(double) * (size_t)ntiles * (dp + 1) * 64;  // LDS copy: + the |x|^2 row (kg_mc.hpp eval_loop)
   const size_t slab_bytes = sizeof(double) * ((size_t)ntiles * (1 + G) * 64 + 2 * kMaxM);
-  // (streamed coordinates: + the wave's line-search vectors and packed-sum slot -- kg_mc.hpp WideEval)
+  // (streamed coordinates: + the wave's line-search vectors and packed-sum slot -- kg_mc_lds.hpp WideEval)
   const size_t slab_stream_bytes = slab_bytes + (mc::wide_eval(dp, false) ? sizeof(double) * mc::kWideScratch : 0);
   // the exp table sits in front of everything; one weight tile of padding at the very end (eval_loop prefetches one tile
   // past the last wave's slab)
@@ -1586,7 +1586,7 @@ McPlan plan_mc(const GpDev& gp, const KgDims& k, const double* bounds, const dou
   // d = 12, g = 3, q = 8, M = 4000: n = 800 0.86 vs 1.10 ms; with four (n = 1200) 1.28 vs 1.21
   if (G > 0 && G <= 4 && !far_frame && !xlds && waves >= 5) variant = 0;
   if (G > 4 || m > kMaxM) variant = 1;  // (the wave-per-sample kernel: up to four derivative slots, one lane per component)
-  // Variant 2, the streamed-weights wave-per-sample kernel (kg_mc.hpp kg_mc_stream_kernel), takes what would go to the
+  // Variant 2, the streamed-weights wave-per-sample kernel (kg_mc_stream.hpp kg_mc_stream_kernel), takes what would go to the
   // workgroup-per-sample kernel whenever the per-sample weight table (fantasy points and tile padding included) fits its cap and
   // every derivative slot is an observed derivative (a point's table rows ARE its weights)
   const long v_stride_tiles = (long)ntiles * 64 * (1 + G);  // (the table of the streamed-weights kernel: 1 + G slots per point)
@@ -1636,7 +1636,7 @@ McPlan plan_mc(const GpDev& gp, const KgDims& k, const double* bounds, const dou
     shm = (lane_kernel ? kg_mc_lane_fixed_bytes(dp, rec_head) : fixed_bytes) +
           (xlds ? tab_bytes + (size_t)waves * slab_bytes : (size_t)waves * slab_stream_bytes) + pad_bytes;
     wg_per_cu = std::max(1, std::min((int)((size_t)160 * 1024 / shm), (waves > 8 ? 16 : 8) / waves));
-    if (mc::wide_eval(dp, xlds)) {  // what the slabs leave of a workgroup's share of LDS holds the leading tiles of the table (kg_mc.hpp WideEval)
+    if (mc::wide_eval(dp, xlds)) {  // what the slabs leave of a workgroup's share of LDS holds the leading tiles of the table (kg_mc_lds.hpp WideEval)
       const size_t share = (size_t)160 * 1024 / wg_per_cu;
       wide_lds_tiles = (int)std::min<size_t>((size_t)ntiles, (share - shm) / (sizeof(double) * dp * 64));
       shm += sizeof(double) * (size_t)wide_lds_tiles * dp * 64;
@@ -2148,7 +2148,7 @@ KgPending enqueue_results(GpDev& gp, const KgDims& k, const double* dFin, size_t
       if (w[10] > 0 && w[8] > 0)  // workgroup-per-sample kernel: line_search_lds outside its passes, per pass
         std::fprintf(stderr, "[moe prof] outside the passes, cycles per pass: gradient post + trial-line set-up %.0f, Armijo dispatch / decisions %.0f, "
                      "LimitUpdate + re-evaluation set-up + step end %.0f\n", (double)w[13] / w[8], (double)w[14] / w[8], (double)w[15] / w[8]);
-      if (w[13] > 0 && w[10] == 0)  // wave-per-sample kernel (kg_mc.hpp kg_sample): clock ticks of lane 0 of every wave
+      if (w[13] > 0 && w[10] == 0)  // wave-per-sample kernel (kg_mc_wave.hpp kg_sample): clock ticks of lane 0 of every wave
         std::fprintf(stderr,
                      "[moe prof] wave-per-sample kernel, ticks per sample: z/beta %.0f  weights %.0f  scan %.0f  line search %.0f "
                      "(of which %.1f value passes x %.0f + %.1f gradient passes x %.0f)\n",

@@ -1,15 +1,8 @@
-// cornell_moe_amd/csrc/kg_mc_dp4b.hip -- instantiations of the KG Monte-Carlo kernels (kg_mc.hpp) for padded dimension 4: the
-// workgroup-per-sample and the streamed-weights kernels (the LDS-table kernels are in kg_mc_dp4.hip).
-#include "kg_mc.hpp"
+// cornell_moe_amd/csrc/kg_mc_dp4b.hip -- instantiations of the KG Monte-Carlo kernels for padded dimension 4: the
+// workgroup-per-sample (kg_mc_block.hpp) and the streamed-weights (kg_mc_stream.hpp) kernels (the LDS-table kernels are in
+// kg_mc_dp4.hip).
+#include "kg_mc_block.hpp"
+#include "kg_mc_stream.hpp"
 
-namespace moe {
-
-void launch_kg_mc_block_dp4(const KgMcParams& P, int G, int tr, int num_lds_tiles, int blocks, int waves, hipStream_t s) {
-  mc::launch_block_dp<4>(P, G, tr, num_lds_tiles, blocks, waves, s);
-}
-
-void launch_kg_mc_stream_dp4(const KgMcParams& P, int G, int blocks, int waves, size_t shm, hipStream_t s) {
-  mc::launch_stream_dp<4>(P, G, blocks, waves, shm, s);
-}
-
-}  // namespace moe
+template void moe::mc::launch_block_dp<4>(const moe::KgMcParams&, int, int, int, int, int, hipStream_t);
+template void moe::mc::launch_stream_dp<4>(const moe::KgMcParams&, int, int, int, size_t, hipStream_t);

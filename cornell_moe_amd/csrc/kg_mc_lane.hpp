@@ -1,7 +1,7 @@
-// cornell_moe_amd/csrc/kg_mc_lane.hpp -- round 5: the wave-per-sample MC kernel with its line search LANE-PARKED (included by
-// kg_mc.hpp, inside namespace moe::mc).
+// cornell_moe_amd/csrc/kg_mc_lane.hpp -- round 5: the wave-per-sample MC kernel with its line search LANE-PARKED (one of the
+// kernel families over the shared core kg_mc.hpp; instantiated by kg_mc_dp{4,8,12,16}.hip).
 //
-// kg_mc_kernel (kg_mc.hpp) keeps the wave-uniform vectors of a sample's line search -- the iterate, its gradient, the trial
+// kg_mc_kernel (kg_mc_wave.hpp) keeps the wave-uniform vectors of a sample's line search -- the iterate, its gradient, the trial
 // direction, the step: five arrays of DP doubles -- as wave-uniform VALUES, i.e. 10 DP vector registers that stay live across the
 // tile loops (which sit on the 256-register cliff), every operation on them DP instructions on 64 identical lanes, and the scalar
 // file around them spilt to VGPR lanes (472 spill slots: v_writelane / v_readlane, a vector-ALU slot each way).  Here lane r < DP
@@ -13,7 +13,7 @@
 //     between passes;
 //   * sums over the rows that the reference takes in coordinate order (|grad|^2, |step|^2, the restart displacement, and the
 //     three sums of a trial line) are taken in that order over the broadcast values: every number below has the bits the
-//     frame line search of kg_mc.hpp (line_search_frame) produces -- the two kernels can be compared bit for bit
+//     frame line search of kg_mc_wave.hpp (line_search_frame) produces -- the two kernels can be compared bit for bit
 //     (MOE_KG_LANE=0 selects the old one; tests/test_gpu_sweep.py::test_lane_kernel_bit_identical);
 //   * everything a sample reads that does not depend on the sample -- L, mu_n and L^-1 cov_n of the discretised set, the set
 //     itself, the bounds, the frame constants -- is copied to LDS once per workgroup and evaluation: a sample's set-up is one
@@ -21,6 +21,10 @@
 // Semantics: gpp_knowledge_gradient_optimization.cpp:164-196, 420-472; gpp_optimization.hpp:708-828, 1242-1283;
 // gpp_domain.cpp:64-105.
 #pragma once
+#include "kg_mc.hpp"
+
+namespace moe {
+namespace mc {
 
 // threads per workgroup the kernel is compiled for (512: two wavefronts per SIMD, up to 256 VGPRs)
 constexpr int kLaneMaxThreads = 512;
@@ -36,7 +40,6 @@ constexpr int kLaneGradUnroll = 4;  // tiles unrolled in the gradient pass (r5 A
 template <int DP, int G, bool EXACT>
 constexpr bool kLaneLookupFirst = DP <= 8 && G <= 1 && !EXACT;
 
-constexpr int kLaneCstRows = 8;  // s | 1 / s | centre | pinned value | lower bound | upper bound (original units) | perm | free (1 / 0)
 constexpr int kMaxLaneDP = 16;
 
 template <int DP>
@@ -85,8 +88,8 @@ __device__ __forceinline__ double wave_max_uniform(double v) {
   return fmax(fmax(r0, r1), fmax(r2, r3));
 }
 
-// Value + gradient pass with the gradient returned LANE-PARKED (lane k < DP: d f / d x'_k in the frame): eval_loop<DP, G, true, COV,
-// false, true, false, true> of kg_mc.hpp with the read-back of the packed sums changed -- lane k reads sum k.  `S` = 2 kMaxLaneDP doubles of scratch.
+// Value + gradient pass with the gradient returned LANE-PARKED (lane k < DP: d f / d x'_k in the frame): the gradient pass
+// eval_loop<DP, G, true, COV, false, true> of kg_mc.hpp with the read-back of the packed sums changed -- lane k reads sum k.  `S` = 2 kMaxLaneDP doubles of scratch.
 template <int DP, int G, int COV, bool LF>
 __device__ __forceinline__ double grad_pass_parked(const double* __restrict__ xs, const double* __restrict__ aw,
                                                    const double* __restrict__ etab, int ntiles, double mean, const double (&xq)[DP],
@@ -441,7 +444,7 @@ __device__ __forceinline__ void kg_sample_lane(const KgMcParams& P, int e, int s
               double q2[DP], unused[DP];
 #pragma unroll
               for (int k = 0; k < DP; ++k) q2[k] = fma(alpha_n, d2[k], x2[k]);
-              ftrial = eval_pass<DP, G, false, false, true, true, false, LF>(xs, aw, etab, ntiles, cov_type, mean, q2, nullptr, unused, lane);
+              ftrial = eval_pass<DP, G, false, false, true, LF>(xs, aw, etab, ntiles, cov_type, mean, q2, unused, lane);
               n_val++;
               if (ftrial - f0 > 0.5 * alpha_n * norm) {
                 done = true;
@@ -489,7 +492,7 @@ __device__ __forceinline__ void kg_sample_lane(const KgMcParams& P, int e, int s
           } else {
             double q2[DP], unused[DP];
             lane_broadcast<DP>(fma(-2.0, st_l, x2_l), R0, lane, q2);
-            obj2 = eval_pass<DP, G, false, false, true, true, false, LF>(xs, aw, etab, ntiles, cov_type, mean, q2, nullptr, unused, lane);
+            obj2 = eval_pass<DP, G, false, false, true, LF>(xs, aw, etab, ntiles, cov_type, mean, q2, unused, lane);
             n_val++;
           }
         }
@@ -606,13 +609,6 @@ __global__ __launch_bounds__(kLaneMaxThreads) void kg_mc_lane_kernel(KgMcParams 
   kg_mc_lane_kernel_body<DP, G, EXACT, kLaneLookupFirst<DP, G, EXACT>>::run(MOE_VBLOCK, MOE_VGRID, (const void*)__builtin_amdgcn_kernarg_segment_ptr(), P, rec_head);
 }
 
-// LDS bytes of a workgroup of `waves` wavefronts (host side: kg.hip's geometry)
-inline size_t lane_lds_bytes(int dp, int G, int ntiles, int rec_head, int waves) {
-  const size_t fixed = (size_t)kExpTabLen + (size_t)kLaneCstRows * dp + (size_t)((rec_head + 1) & ~1);
-  const size_t tab = (size_t)ntiles * (dp + 1) * 64;
-  return sizeof(double) * (fixed + tab + (size_t)waves * ((size_t)ntiles * (1 + G) * 64 + 2 * kMaxM) + (size_t)(1 + G) * 64);
-}
-
 template <int DP, int G, bool EXACT = false>
 inline void launch_lane_inst(const KgMcParams& P, int rec_head, int blocks, int waves, size_t shm, hipStream_t s) {
   auto kern = kg_mc_lane_kernel<DP, G, EXACT>;
@@ -622,29 +618,29 @@ inline void launch_lane_inst(const KgMcParams& P, int rec_head, int blocks, int 
   MOE_HIP_CHECK(hipGetLastError());
 }
 
-template <int DP>
-inline void launch_lane_dp(const KgMcParams& P, int G, int rec_head, int blocks, int waves, size_t shm, hipStream_t s) {
-  static_assert(DP <= kMaxLaneDP, "lane-parked line search: one scratch row holds kMaxLaneDP doubles");
-  if constexpr (DP == 4) {  // (the small shapes live here: padded dimension 4, one or two tiles -- kg.hip)
-    if (P.multi_trial == 2) {
-      switch (G) {
-        case 0: launch_lane_inst<DP, 0, true>(P, rec_head, blocks, waves, shm, s); break;
-        case 1: launch_lane_inst<DP, 1, true>(P, rec_head, blocks, waves, shm, s); break;
-        case 2: launch_lane_inst<DP, 2, true>(P, rec_head, blocks, waves, shm, s); break;
-        case 3: launch_lane_inst<DP, 3, true>(P, rec_head, blocks, waves, shm, s); break;
-        case 4: launch_lane_inst<DP, 4, true>(P, rec_head, blocks, waves, shm, s); break;
-        default: throw Error(MOE_ERR_RUNTIME, "unsupported derivative-slot count in the lane-parked MC kernel");
-      }
-      return;
-    }
+// one derivative-slot count (the small shapes live at padded dimension 4, one or two tiles -- kg.hip: only there are the exact
+// multi-trial passes, P.multi_trial == 2, built)
+template <int DP, int G>
+inline void launch_lane_g(const KgMcParams& P, int rec_head, int blocks, int waves, size_t shm, hipStream_t s) {
+  if constexpr (DP == 4) {
+    if (P.multi_trial == 2) return launch_lane_inst<DP, G, true>(P, rec_head, blocks, waves, shm, s);
   }
-  if (P.multi_trial == 2) throw Error(MOE_ERR_RUNTIME, "exact multi-trial passes are built for the padded dimension 4 only");
-  switch (G) {
-    case 0: launch_lane_inst<DP, 0>(P, rec_head, blocks, waves, shm, s); break;
-    case 1: launch_lane_inst<DP, 1>(P, rec_head, blocks, waves, shm, s); break;
-    case 2: launch_lane_inst<DP, 2>(P, rec_head, blocks, waves, shm, s); break;
-    case 3: launch_lane_inst<DP, 3>(P, rec_head, blocks, waves, shm, s); break;
-    case 4: launch_lane_inst<DP, 4>(P, rec_head, blocks, waves, shm, s); break;
-    default: throw Error(MOE_ERR_RUNTIME, "unsupported derivative-slot count in the lane-parked MC kernel");
-  }
+  launch_lane_inst<DP, G>(P, rec_head, blocks, waves, shm, s);
 }
+
+template <int DP>
+void launch_lane_dp(const KgMcParams& P, int G, int rec_head, int blocks, int waves, size_t shm, hipStream_t s) {
+  static_assert(DP <= kMaxLaneDP, "lane-parked line search: one scratch row holds kMaxLaneDP doubles");
+  if (DP != 4 && P.multi_trial == 2) throw Error(MOE_ERR_RUNTIME, "exact multi-trial passes are built for the padded dimension 4 only");
+  switch (G) {
+    case 0: return launch_lane_g<DP, 0>(P, rec_head, blocks, waves, shm, s);
+    case 1: return launch_lane_g<DP, 1>(P, rec_head, blocks, waves, shm, s);
+    case 2: return launch_lane_g<DP, 2>(P, rec_head, blocks, waves, shm, s);
+    case 3: return launch_lane_g<DP, 3>(P, rec_head, blocks, waves, shm, s);
+    case 4: return launch_lane_g<DP, 4>(P, rec_head, blocks, waves, shm, s);
+  }
+  throw Error(MOE_ERR_RUNTIME, "unsupported derivative-slot count in the lane-parked MC kernel");
+}
+
+}  // namespace mc
+}  // namespace moe

@@ -413,19 +413,6 @@ void ei_mcmc_batch(const std::vector<GpDev*>& gps, const double* Xq_all, int num
 
 namespace {
 
-// TensorProductDomain::LimitUpdate (gpp_domain.cpp:64-105) on one coordinate.
-double limit_update_coord(double lo, double hi, double max_relative_change, double x, double desired) {
-  double dist = std::fmin(x - lo, hi - x);
-  if (std::fabs(desired) > max_relative_change * dist) desired = std::copysign(max_relative_change * dist, desired);
-  const double next = x + desired;
-  if (next < lo) {
-    desired = (x + desired * 0.5 < lo) ? (lo - x) * 0.5 : desired * 0.5;
-  } else if (next > hi) {
-    desired = (x + desired * 0.5 > hi) ? (hi - x) * 0.5 : desired * 0.5;
-  }
-  return desired;
-}
-
 // ComputeCost / ComputeGradCost (.cpp:84-127) on the points the MCMC state holds; gcost[qd] (may be NULL).
 double fidelity_cost(const double* x, int q, int d, int num_fidelity, double* gcost) {
   if (gcost) std::fill(gcost, gcost + (size_t)q * d, 0.0);

@@ -322,7 +322,7 @@ def test_dkg_shape_properties(api, monkeypatch):
 
 
 def test_workgroup_per_sample_kernel_matches_wave_per_sample(api, monkeypatch):
-    """The two MC kernel variants (csrc/kg_mc.hpp: wave-per-sample with LDS tables, workgroup-per-sample with register
+    """The two MC kernel variants (csrc/kg_mc_wave.hpp: wave-per-sample with LDS tables; csrc/kg_mc_block.hpp: workgroup-per-sample with register
     tiles) implement the same algorithm with different summation trees: q-KG and d-KG results agree to rounding, and both
     match the oracle where it is affordable."""
     from cornell_moe_amd.workloads import make_workload
