@@ -1052,6 +1052,113 @@ def ei_analytic_suggest(gps, gd_params, bounds, best_so_far, starts, num_to_samp
     return {"points": points, "values": values, "found": found.astype(bool)}
 
 
+def _ei_constrained_members(gps, constraint_gps, thresholds, best_so_far):
+    """(objective handles, E, dim, GPs kept alive, constraint handles [K][E] flat or None, K, thresholds [K], best values [E]) of the
+    ensemble forms of the constrained expected improvement.  constraint_gps: K ensembles, each shaped like gps (a DeviceGPMCMC, a
+    list of DeviceGP or one DeviceGP), E members each; best values may be +inf."""
+    arr, E, d, keep, best = _ei_analytic_members(gps, best_so_far)
+    cons = [] if constraint_gps is None else list(constraint_gps)
+    K = len(cons)
+    tau = np.ascontiguousarray([] if thresholds is None else thresholds, dtype=np.float64).ravel()
+    if tau.size != K:
+        raise BoundsException("one threshold per constraint", tau.size, K, K)
+    flat = []
+    for c in cons:
+        members = [c] if isinstance(c, DeviceGP) else (list(c.gps) if isinstance(c, DeviceGPMCMC) else list(c))
+        if len(members) != E:
+            raise BoundsException("one constraint GP per ensemble member and constraint", len(members), E, E)
+        flat.extend(members)
+    carr = (C.c_void_p * max(len(flat), 1))(*[g._h.value for g in flat]) if K else None
+    return arr, E, d, (keep, flat), carr, K, tau, best
+
+
+def ei_constrained_ensemble(gps, constraint_gps, thresholds, points, best_so_far, points_being_sampled=None, want_grad=True,
+                            want_factors=False):
+    """moe_ei_constrained_mcmc: expected improvement times the probability of feasibility, averaged over the ensemble at points
+    [C][dim], in one device call.  Member e is the objective GP gps[e] and the constraint GPs constraint_gps[k][e], constraint k
+    satisfied where c_k(x) <= thresholds[k] (0 <= K <= 8; K = 0 with finite best values is ei_analytic_ensemble bit for bit).
+    best_so_far [E] is the best FEASIBLE value per member and may be +inf (no feasible observation yet: the member's acquisition is
+    its probability of feasibility).  points_being_sampled [p][dim] condition every GP's covariance; a pending point joins member
+    e's incumbent where the member believes it feasible.  Returns value [C], with want_grad (value, grad [C][dim]), and with
+    want_factors additionally factors [E][1 + K][C] (the improvement factor, then the K feasibility factors) as the last item.
+    SingularMatrixException(e (1 + K) + role, j): the GP, counted flat, and the pending point; a candidate never raises."""
+    arr, E, d, keep, carr, K, tau, best = _ei_constrained_members(gps, constraint_gps, thresholds, best_so_far)
+    pts, pp = _d(points)
+    C_ = pts.reshape(-1, d).shape[0]
+    value = np.zeros(max(C_, 1))
+    grad = np.zeros((max(C_, 1), d)) if want_grad else None
+    factors = np.zeros((E, 1 + K, max(C_, 1))) if want_factors else None
+    p = _num_pending(points_being_sampled, d)
+    pend, pendp = _d(points_being_sampled) if p else (None, None)
+    err = _lib.MoeError()
+    _check(_lib.load().moe_ei_constrained_mcmc(
+        arr, E, carr, K, tau.ctypes.data_as(dp) if K else None, best.ctypes.data_as(dp), pendp, p, pp, C_, 1 if want_grad else 0,
+        value.ctypes.data_as(dp), grad.ctypes.data_as(dp) if want_grad else None,
+        factors.ctypes.data_as(dp) if want_factors else None, C.byref(err)), err)
+    out = (value, grad) if want_grad else (value,)
+    if want_factors:
+        out = out + (factors,)
+    return out if len(out) > 1 else out[0]
+
+
+def ei_constrained_multistart(gps, constraint_gps, thresholds, gd_params, bounds, best_so_far, starts, gradient_ascent=True,
+                              want_path=False, points_being_sampled=None):
+    """moe_ei_constrained_mcmc_multistart: one suggestion by the ensemble-averaged constrained expected improvement --
+    ei_analytic_multistart's screening, 20 kept starts, restarted ascent on the device and end-point selection, and its dict."""
+    arr, E, d, keep, carr, K, tau, best = _ei_constrained_members(gps, constraint_gps, thresholds, best_so_far)
+    g = DeviceGP._gd(gd_params)
+    bounds, bp = _d(bounds)
+    starts, sp = _d(starts)
+    S = starts.reshape(-1, d).shape[0]
+    Kk = max(min(S, 20), 1)
+    rows = max(g.max_num_restarts, 0) * max(g.max_num_steps, 0) + 1
+    point = np.zeros(d)
+    start_values = np.zeros(max(S, 1))
+    kept = np.zeros(Kk, dtype=np.int32)
+    ends, end_values = np.zeros((Kk, d)), np.zeros(Kk)
+    steps = np.zeros(Kk, dtype=np.int32)
+    path = np.zeros((Kk, rows, d)) if (want_path and gradient_ascent) else None
+    value, found = C.c_double(0.0), C.c_int(0)
+    p = _num_pending(points_being_sampled, d)
+    pend, pendp = _d(points_being_sampled) if p else (None, None)
+    err = _lib.MoeError()
+    _check(_lib.load().moe_ei_constrained_mcmc_multistart(
+        arr, E, carr, K, tau.ctypes.data_as(dp) if K else None, C.byref(g), bp, best.ctypes.data_as(dp), pendp, p, sp, S,
+        1 if gradient_ascent else 0, point.ctypes.data_as(dp), C.byref(value), C.byref(found), start_values.ctypes.data_as(dp),
+        kept.ctypes.data_as(ip), ends.ctypes.data_as(dp), end_values.ctypes.data_as(dp),
+        path.ctypes.data_as(dp) if path is not None else None, steps.ctypes.data_as(ip), C.byref(err)), err)
+    out = {"point": point, "value": value.value, "found": bool(found.value), "start_values": start_values,
+           "kept_index": kept if gradient_ascent else None, "end_points": ends if gradient_ascent else None,
+           "end_values": end_values if gradient_ascent else None, "steps_taken": steps if gradient_ascent else None}
+    if want_path:
+        out["path"] = path
+    return out
+
+
+def ei_constrained_suggest(gps, constraint_gps, thresholds, gd_params, bounds, best_so_far, starts, num_to_sample,
+                           gradient_ascent=True, points_being_sampled=None):
+    """moe_ei_constrained_mcmc_suggest: num_to_sample points greedily by the ensemble-averaged constrained expected improvement --
+    round t is ei_constrained_multistart from the same starts [S][dim] with the pending points points_being_sampled [p][dim] (may be
+    None) followed by the points of the rounds before, bit for bit, in one device call.  (p + num_to_sample - 1) (1 + g) <= 64.
+    Returns a dict: points [q][dim], values [q], found [q]."""
+    arr, E, d, keep, carr, K, tau, best = _ei_constrained_members(gps, constraint_gps, thresholds, best_so_far)
+    g = DeviceGP._gd(gd_params)
+    bounds, bp = _d(bounds)
+    starts, sp = _d(starts)
+    S = starts.reshape(-1, d).shape[0]
+    q = int(num_to_sample)
+    p = _num_pending(points_being_sampled, d)
+    pend, pendp = _d(points_being_sampled) if p else (None, None)
+    points, values = np.zeros((max(q, 1), d)), np.zeros(max(q, 1))
+    found = np.zeros(max(q, 1), dtype=np.int32)
+    err = _lib.MoeError()
+    _check(_lib.load().moe_ei_constrained_mcmc_suggest(
+        arr, E, carr, K, tau.ctypes.data_as(dp) if K else None, C.byref(g), bp, best.ctypes.data_as(dp), pendp, p, sp, S,
+        1 if gradient_ascent else 0, q, points.ctypes.data_as(dp), values.ctypes.data_as(dp), found.ctypes.data_as(ip), C.byref(err)),
+        err)
+    return {"points": points, "values": values, "found": found.astype(bool)}
+
+
 def _gibbon_members(gps, min_values):
     """(handles, count, dim, members kept alive, min-values [E][K], K) of the ensemble forms of the min-value entropy acquisition; a
     single DeviceGP counts as a list of one"""

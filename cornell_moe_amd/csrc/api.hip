@@ -1025,6 +1025,79 @@ int moe_gibbon_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, const moe_
   });
 }
 
+// The GPs of a constrained call, flat and ordered [e][role]: role 0 the objective GP of member e, role k constraint k's.
+static std::vector<const moe_gp_t*> constrained_handles(const moe_gp_t* const* gps, int num_mcmc, const moe_gp_t* const* constraint_gps,
+                                                        int num_constraints) {
+  const int G = 1 + num_constraints;
+  std::vector<const moe_gp_t*> flat((size_t)num_mcmc * G);
+  for (int e = 0; e < num_mcmc; ++e) {
+    flat[(size_t)e * G] = gps[e];
+    for (int k = 0; k < num_constraints; ++k) flat[(size_t)e * G + 1 + k] = constraint_gps[(size_t)k * num_mcmc + e];
+  }
+  return flat;
+}
+
+int moe_ei_constrained_mcmc(const moe_gp_t* const* gps, int num_mcmc, const moe_gp_t* const* constraint_gps, int num_constraints,
+                            const double* thresholds, const double* best_so_far, const double* points_being_sampled,
+                            int num_being_sampled, const double* points, int num_points, int want_grad, double* value, double* grad,
+                            double* factors, moe_error_t* err) {
+  return guarded(err, [&] {
+    check_num_mcmc(num_mcmc);
+    require(gps && best_so_far && points && value && (want_grad == 0 || grad), "NULL argument");
+    moe::check_ei_constrained_shapes(num_mcmc, num_constraints, constraint_gps, thresholds, best_so_far);  // (what needs no handle)
+    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_points);
+    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, 1);
+    const std::vector<const moe_gp_t*> flat = constrained_handles(gps, num_mcmc, constraint_gps, num_constraints);
+    const auto locks = lock_ensemble(flat.data(), (int)flat.size());
+    const std::vector<moe::GpDev*> v = ensemble(flat.data(), (int)flat.size());
+    moe::ei_constrained_mcmc_on_device(v, num_constraints, thresholds, best_so_far, points, num_points, want_grad != 0, value, grad,
+                                       factors, points_being_sampled, num_being_sampled);
+  });
+}
+
+int moe_ei_constrained_mcmc_multistart(const moe_gp_t* const* gps, int num_mcmc, const moe_gp_t* const* constraint_gps,
+                                       int num_constraints, const double* thresholds, const moe_gd_params_t* outer,
+                                       const double* domain_bounds, const double* best_so_far, const double* points_being_sampled,
+                                       int num_being_sampled, const double* starts, int num_starts, int do_gradient_ascent,
+                                       double* best_point, double* best_value, int* found, double* start_values, int* kept_index,
+                                       double* end_points, double* end_values, double* path, int* steps_taken, moe_error_t* err) {
+  return guarded(err, [&] {
+    check_num_mcmc(num_mcmc);
+    require(gps && outer && domain_bounds && best_so_far && starts && best_point && best_value && found, "NULL argument");
+    moe::check_ei_constrained_shapes(num_mcmc, num_constraints, constraint_gps, thresholds, best_so_far);
+    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_starts);
+    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, 1);
+    check_ascent_params(outer, do_gradient_ascent, "the constrained expected improvement");
+    const std::vector<const moe_gp_t*> flat = constrained_handles(gps, num_mcmc, constraint_gps, num_constraints);
+    const auto locks = lock_ensemble(flat.data(), (int)flat.size());
+    const std::vector<moe::GpDev*> v = ensemble(flat.data(), (int)flat.size());
+    moe::ei_constrained_mcmc_multistart(v, num_constraints, thresholds, *outer, domain_bounds, best_so_far, starts, num_starts,
+                                        do_gradient_ascent, best_point, best_value, found, start_values, kept_index, end_points,
+                                        end_values, path, steps_taken, points_being_sampled, num_being_sampled);
+  });
+}
+
+int moe_ei_constrained_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, const moe_gp_t* const* constraint_gps,
+                                    int num_constraints, const double* thresholds, const moe_gd_params_t* outer,
+                                    const double* domain_bounds, const double* best_so_far, const double* points_being_sampled,
+                                    int num_being_sampled, const double* starts, int num_starts, int do_gradient_ascent,
+                                    int num_to_sample, double* best_points, double* best_values, int* found, moe_error_t* err) {
+  return guarded(err, [&] {
+    check_num_mcmc(num_mcmc);
+    require(gps && outer && domain_bounds && best_so_far && starts && best_points && best_values && found, "NULL argument");
+    moe::check_ei_constrained_shapes(num_mcmc, num_constraints, constraint_gps, thresholds, best_so_far);
+    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_starts);
+    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, num_to_sample);
+    check_ascent_params(outer, do_gradient_ascent, "the constrained expected improvement");
+    const std::vector<const moe_gp_t*> flat = constrained_handles(gps, num_mcmc, constraint_gps, num_constraints);
+    const auto locks = lock_ensemble(flat.data(), (int)flat.size());
+    const std::vector<moe::GpDev*> v = ensemble(flat.data(), (int)flat.size());
+    moe::ei_constrained_mcmc_suggest(v, num_constraints, thresholds, *outer, domain_bounds, best_so_far, starts, num_starts,
+                                     do_gradient_ascent, points_being_sampled, num_being_sampled, num_to_sample, best_points,
+                                     best_values, found);
+  });
+}
+
 int moe_kg_mcmc_finalize(double* kg, double* grad_kg, const double* points_to_sample_all, int num_evals, int num_to_sample,
                          int dim, int num_fidelity, int total_num_mcmc) {
   if (!kg || !points_to_sample_all || num_evals <= 0 || num_to_sample <= 0 || dim <= 0 || num_fidelity < 0 ||

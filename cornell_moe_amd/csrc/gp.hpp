@@ -252,6 +252,7 @@ struct Kg1Member {
   double* dBp = nullptr;        // ei1.hip: the member's believed best b' = min(best, min_j mu(P_j)), in device memory
   const double* dExtra = nullptr;  // the objective's per-member block of the upload (gibbon1.hip: the member's min-values), [nExtra]
   int nExtra = 0;
+  int role = 0;  // cei1.hip: 0 the objective GP of its member (best: the incumbent), k > 0 constraint k (best: its threshold)
   size_t out_doubles() const { return 1 + 2 * (size_t)C + (with_grad ? (size_t)C * gp->d : 0); }
 };
 // the handle's checks of moe_gp_kg_discrete (num_fidelity < dim, no derivative observations), the buffers and their layout; nothing
@@ -341,6 +342,27 @@ void gibbon_mcmc_suggest(const std::vector<GpDev*>& gps, const moe_gd_params_t& 
                          const double* min_values, int num_min_values, const double* starts, int num_starts, int do_gradient_ascent,
                          const double* pending, int num_pending, int num_to_sample, double* best_points, double* best_values,
                          int* found);
+// cei1.hip: the constrained expected improvement averaged over an ensemble (moe_ei_constrained_mcmc), its multistart ascent
+// (moe_ei_constrained_mcmc_multistart) and greedy batches (moe_ei_constrained_mcmc_suggest): ei1.hip's three over members of 1 + K
+// GPs each.  gps [E (1 + K)]: the sub-members ordered [e][role], role 0 the objective GP, role k constraint k (satisfied where
+// c_k <= thresholds[k - 1]); best_so_far [E] may hold +infinity.  check_ei_constrained_shapes: what needs no handle (K, the
+// product limit, the arrays K > 0 needs, finite thresholds, best_so_far neither NaN nor -infinity).  factors_out (may be NULL):
+// [E (1 + K)][C], the sub-members' factor values.
+constexpr int kCeiMaxConstraints = 8;
+void check_ei_constrained_shapes(int num_mcmc, int num_constraints, const void* constraint_gps, const double* thresholds,
+                                 const double* best_so_far);
+void ei_constrained_mcmc_on_device(const std::vector<GpDev*>& gps, int num_constraints, const double* thresholds,
+                                   const double* best_so_far, const double* pts, int C, bool want_grad, double* value_out,
+                                   double* grad_out, double* factors_out, const double* pending, int num_pending);
+void ei_constrained_mcmc_multistart(const std::vector<GpDev*>& gps, int num_constraints, const double* thresholds,
+                                    const moe_gd_params_t& outer, const double* domain_bounds, const double* best_so_far,
+                                    const double* starts, int num_starts, int do_gradient_ascent, double* best_point, double* best_value,
+                                    int* found, double* start_values, int* kept_index, double* end_points, double* end_values,
+                                    double* path, int* steps_taken, const double* pending, int num_pending);
+void ei_constrained_mcmc_suggest(const std::vector<GpDev*>& gps, int num_constraints, const double* thresholds,
+                                 const moe_gd_params_t& outer, const double* domain_bounds, const double* best_so_far,
+                                 const double* starts, int num_starts, int do_gradient_ascent, const double* pending, int num_pending,
+                                 int num_to_sample, double* best_points, double* best_values, int* found);
 // loo.hip: leave-one-out cross-validation on the GP's current factorisation, every one of the N = n (1 + g) scalar observations left
 // out by itself.  mean_out / var_out [n][1 + g]: the LOO predictive mean (function values in the caller's units) and variance.
 void loo_predict_on_device(GpDev& gp, double* mean_out, double* var_out);

@@ -1,5 +1,6 @@
 // cornell_moe_amd/csrc/kg1_ascent.hip -- what the ensemble forms of the one-point acquisition functions share (kg1_opt.hip: the
-// discretised knowledge gradient; ei1.hip: the analytic expected improvement; gibbon1.hip: the min-value entropy acquisition), compiled once: the ensemble mean, the multistart
+// discretised knowledge gradient; ei1.hip: the analytic expected improvement; gibbon1.hip: the min-value entropy acquisition;
+// cei1.hip: the constrained expected improvement), compiled once: the ensemble mean, the multistart
 // ascent's gather, step and round kernels, the recorded and zipped evaluation of the members' chains, the ascent itself (ascend()),
 // the staging of a call (stage(), stage_ascent()) and the three drivers behind the entry points (kg1_ascent.hpp).  None of it knows
 // the objective: a Kg1Objective says how a member is built, which chain evaluates it and what follows its extension.
@@ -51,6 +52,12 @@ __global__ __launch_bounds__(256) void kg1_mean_kernel(int E, long n, const doub
   double v = src[0][i];
   for (int e = 1; e < E; ++e) v = v + src[e][i];
   out[i] = v / (double)E;
+}
+
+// out[e][i] = src[e][i]: every member's own values side by side for the copy back (blockIdx.y: the member)
+__global__ __launch_bounds__(256) void kg1_members_kernel(long n, const double* const* __restrict__ src, double* __restrict__ out) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[(size_t)blockIdx.y * n + i] = src[blockIdx.y][i];
 }
 
 // the words of the call as doubles in front of the results: one copy back
@@ -187,6 +194,14 @@ void launch_mean_of_members(const Kg1Ensemble& T, const double* const* tab, long
   MOE_HIP_CHECK(hipGetLastError());
 }
 
+// the ensemble's value at C points from the members' results: the objective's own rule, or the mean of the members
+void launch_value_of_members(const Kg1Ensemble& T, int C, double* out) {
+  if (T.combine != nullptr)
+    T.combine(T, C, out, nullptr);
+  else
+    launch_mean_of_members(T, T.dKgTab, C, out);
+}
+
 // after a wait: the first member with a candidate that failed the pivot rule
 template <class Word>
 void throw_if_singular(const Kg1Ensemble& T, const Word* fail_words) {
@@ -206,8 +221,8 @@ void throw_if_singular(const Kg1Ensemble& T, const Word* fail_words) {
 
 // The members' layouts and the one upload:
 //   [value pointers E | grad pointers E | bounds 2 d | set of member 0 .. E - 1, padded | points C dp | the same, fidelity 1 (fid) |
-//    pending points pcap dp | the members' extra doubles E num_member_extra]
-// (an objective without sets, fidelity coordinates or extra doubles leaves those sections empty); then every member's extension by
+//    pending points pcap dp | the members' extra doubles E num_member_extra | the address of the combined gradient (T.combine)]
+// (an objective without sets, fidelity coordinates, extra doubles or a rule of its own leaves those sections empty); then every member's extension by
 // the first p pending points and what the objective runs behind it.  extra_ints: integers of the caller behind the W failure words in the first
 // member's kg1oI.
 void stage(Kg1Ensemble& T, const Kg1Objective& o, const double* bounds, const double* pts, int C, bool with_grad, size_t extra_ints,
@@ -223,7 +238,7 @@ void stage(Kg1Ensemble& T, const Kg1Objective& o, const double* bounds, const do
   const size_t nC = (size_t)C, oBounds = 2 * (size_t)E, oSets = oBounds + 2 * (size_t)d, oPts = oSets + nSets * dp;
   const size_t oPend = oPts + nC * dp * (T.fid ? 2 : 1);
   const size_t nX = o.member_extra != nullptr ? (size_t)o.num_member_extra : 0, oExtra = oPend + (size_t)pcap * dp;
-  const size_t nIn = oExtra + (size_t)E * nX;
+  const size_t oComb = oExtra + (size_t)E * nX, nIn = oComb + (T.combine != nullptr ? 1 : 0);
   g0.hStateIn.reserve(nIn);
   g0.dStateIn.reserve(nIn);
   T.mem.clear();
@@ -258,6 +273,11 @@ void stage(Kg1Ensemble& T, const Kg1Objective& o, const double* bounds, const do
     T.mem[e].dExtra = dIn + oExtra + (size_t)e * nX;
     T.mem[e].nExtra = (int)nX;
   }
+  if (T.combine != nullptr) {
+    const double* pc = T.dComb;
+    std::memcpy(h + oComb, &pc, sizeof(pc));
+    T.dCombTab = reinterpret_cast<const double* const*>(dIn + oComb);
+  }
   g0.dStateIn.upload(h, nIn, T.z, true);
   T.dPending = g0.dStateIn.p + oPend;
   T.dKgTab = reinterpret_cast<const double* const*>(dIn);
@@ -280,7 +300,8 @@ void stage(Kg1Ensemble& T, const Kg1Objective& o, const double* bounds, const do
 }
 
 // The buffers of ascend() -- T.sz, the one place their sizes are worked out -- and the one upload.  The call's doubles:
-//   [words: failure W, steps Kmax | values S | X Kmax dp | path Kmax rows d] (the copies back) | X^, X_begin Kmax dp
+//   [words: failure W, steps Kmax | values S | X Kmax dp | path Kmax rows d] (the copies back) | X^, X_begin Kmax dp |
+//   the combined gradient Kmax d (T.combine)
 // and its integers behind the failure words: [alive count | steps Kmax | order, running, alive Kmax each].
 void stage_ascent(Kg1Ensemble& T, const Kg1Objective& o, const moe_gd_params_t& outer, const double* domain_bounds,
                   const double* starts, int S, bool ascent, bool want_path, const double* pending, int p) {
@@ -294,8 +315,10 @@ void stage_ascent(Kg1Ensemble& T, const Kg1Objective& o, const moe_gd_params_t& 
   sz.oX = sz.oVals + S;
   sz.oPath = sz.oX + (size_t)sz.Kmax * T.dp;
   sz.nBack = sz.oPath + (want_path ? (size_t)sz.Kmax * sz.rows * T.d : 0);
-  g0.kg1oD.reserve(sz.nBack + 2 * (size_t)sz.Kmax * T.dp);
+  const size_t oComb = sz.nBack + 2 * (size_t)sz.Kmax * T.dp;
+  g0.kg1oD.reserve(oComb + (T.combine != nullptr ? (size_t)sz.Kmax * T.d : 0));
   g0.hStateOut.reserve(sz.nBack);
+  if (T.combine != nullptr) T.dComb = g0.kg1oD.p + oComb;
   stage(T, o, domain_bounds, starts, S, ascent && R > 0, 1 + 4 * (size_t)sz.Kmax, pending, p);
 }
 
@@ -323,7 +346,7 @@ const double* ascend(Kg1Ensemble& T, const moe_gd_params_t& outer, const double*
   // screening: the value at every start
   Kg1Recording screen;
   evaluate(T, screen, T.dPts, T.dPtsH, S, false);
-  launch_mean_of_members(T, T.dKgTab, S, dVals);
+  launch_value_of_members(T, S, dVals);
   MOE_LAUNCH_NOW(kg1_words_kernel, dim3(1), dim3(256), 0, z, (const int*)T.iFail, W, dD);
   MOE_HIP_CHECK(hipGetLastError());
   g0.kg1oD.download(h, oVals + S, z);
@@ -357,11 +380,11 @@ const double* ascend(Kg1Ensemble& T, const moe_gd_params_t& outer, const double*
   MOE_HIP_CHECK(hipMemcpyAsync(iOrder, hOrder, sizeof(int) * (size_t)K, hipMemcpyHostToDevice, z));
   Kg1Ascent a;
   a.K = K;
-  a.E = E;
+  a.E = T.combine != nullptr ? 1 : E;  // (the objective's own rule leaves ONE gradient, already divided: g / 1 is exact)
   a.d = d;
   a.dp = dp;
   a.size = d - T.nf;
-  a.grad = T.dGradTab;
+  a.grad = T.combine != nullptr ? T.dCombTab : T.dGradTab;
   a.bounds = T.dBounds;
   a.X = dD + oX;
   a.Xh = T.fid ? dD + nBack : a.X;
@@ -384,6 +407,7 @@ const double* ascend(Kg1Ensemble& T, const moe_gd_params_t& outer, const double*
     for (int i = 0; i < Tn; ++i) {
       const double alpha = outer.pre_mult * std::pow((double)(i + 1), -outer.gamma);
       evaluate(T, step, a.X, a.Xh, K, true);
+      if (T.combine != nullptr) T.combine(T, K, nullptr, T.dComb);
       MOE_LAUNCH_NOW(kg1_step_kernel, dim3(1), dim3(64), 0, z, a, alpha, outer.max_relative_change, step_tol, 1 + r * Tn + i);
     }
     MOE_LAUNCH_NOW(kg1_round_kernel, dim3(1), dim3(64), 0, z, a, outer.tolerance);
@@ -398,7 +422,7 @@ const double* ascend(Kg1Ensemble& T, const moe_gd_params_t& outer, const double*
   // the value at every end point, and everything back in one copy
   Kg1Recording last;
   evaluate(T, last, a.X, a.Xh, K, false);
-  launch_mean_of_members(T, T.dKgTab, K, dVals);
+  launch_value_of_members(T, K, dVals);
   MOE_LAUNCH_NOW(kg1_words_kernel, dim3(1), dim3(256), 0, z, (const int*)T.iFail, W, dD);
   MOE_LAUNCH_NOW(kg1_words_kernel, dim3(1), dim3(256), 0, z, (const int*)iSteps, K, dD + W);
   MOE_HIP_CHECK(hipGetLastError());
@@ -432,6 +456,11 @@ const double* ascend(Kg1Ensemble& T, const moe_gd_params_t& outer, const double*
 Kg1Ensemble::Kg1Ensemble(const std::vector<GpDev*>& members, const Kg1Objective& o, int pending_room)
     : gps(members), z(members[0]->stream), ens(ensemble_launches() && members.size() > 1), E((int)members.size()), d(members[0]->d),
       dp(members[0]->dp), nf(o.nf), eval_points(o.eval_points), fid(o.nf > 0), pcap(pending_room), W(pending_room > 0 ? 2 * E : E) {
+  if (o.combine != nullptr && o.group > 1) {
+    if (E % o.group != 0) throw Error(MOE_ERR_RUNTIME, "the members do not fill their groups");
+    combine = o.combine;
+    group = o.group;
+  }
   gps[0]->use_device();
 }
 
@@ -454,20 +483,28 @@ void kg1_check_members(const std::vector<GpDev*>& gps, int nf, void (*check_memb
 }
 
 void kg1_ensemble_evaluate(const Kg1Objective& o, const std::vector<GpDev*>& gps, const double* pts, int C, bool want_grad,
-                           double* value_out, double* grad_out, const double* pending, int num_pending) {
+                           double* value_out, double* grad_out, const double* pending, int num_pending, double* members_out) {
   Kg1Ensemble T(gps, o, num_pending);
   GpDev& g0 = *gps[0];
   const int d = T.d, W = T.W;
-  // the call's doubles, all of them the copy back: [failure words | value C | grad C d]
-  const size_t nOut = (size_t)W + (size_t)C * (want_grad ? 1 + d : 1);
+  // the call's doubles, all of them the copy back: [failure words | value C | grad C d | the members' values E C (members_out)]
+  const size_t oMem = (size_t)W + (size_t)C * (want_grad ? 1 + d : 1);
+  const size_t nOut = oMem + (members_out != nullptr ? (size_t)T.E * C : 0);
   g0.kg1oD.reserve(nOut);
   g0.hStateOut.reserve(nOut);
   stage(T, o, nullptr, pts, C, want_grad, 0, pending, num_pending);
   Kg1Recording rec;
   evaluate(T, rec, T.dPts, T.dPtsH, C, want_grad);
   double* dOut = g0.kg1oD.p;
-  launch_mean_of_members(T, T.dKgTab, C, dOut + W);
-  if (want_grad) launch_mean_of_members(T, T.dGradTab, (long)C * d, dOut + W + C);
+  if (T.combine != nullptr) {
+    T.combine(T, C, dOut + W, want_grad ? dOut + W + C : nullptr);
+  } else {
+    launch_mean_of_members(T, T.dKgTab, C, dOut + W);
+    if (want_grad) launch_mean_of_members(T, T.dGradTab, (long)C * d, dOut + W + C);
+  }
+  if (members_out != nullptr)
+    MOE_LAUNCH_NOW(kg1_members_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)T.E), dim3(256), 0, T.z, (long)C, T.dKgTab,
+                   dOut + oMem);
   MOE_LAUNCH_NOW(kg1_words_kernel, dim3(1), dim3(256), 0, T.z, (const int*)T.iFail, W, dOut);
   MOE_HIP_CHECK(hipGetLastError());
   g0.kg1oD.download(g0.hStateOut.p, nOut, T.z);
@@ -476,6 +513,7 @@ void kg1_ensemble_evaluate(const Kg1Objective& o, const std::vector<GpDev*>& gps
   throw_if_singular(T, out);
   std::memcpy(value_out, out + W, sizeof(double) * (size_t)C);
   if (want_grad) std::memcpy(grad_out, out + W + C, sizeof(double) * (size_t)C * d);
+  if (members_out != nullptr) std::memcpy(members_out, out + oMem, sizeof(double) * (size_t)T.E * C);
 }
 
 void kg1_ensemble_multistart(const Kg1Objective& o, const std::vector<GpDev*>& gps, const moe_gd_params_t& outer,

@@ -1,8 +1,9 @@
-// cornell_moe_amd/csrc/kg1_ascent.hpp -- what the ensemble forms of the one-point acquisition functions share (kg1_opt.hip: the
-// discretised knowledge gradient; ei1.hip: the analytic expected improvement; gibbon1.hip: the min-value entropy acquisition), declared here and compiled once in kg1_ascent.hip:
-// the members' common checks, the staging of a call, the ensemble mean, the multistart ascent and the drivers behind the three
-// shapes of entry point (evaluate at points, multistart, greedy batch).  None of it knows the objective: kg1_opt.hip and ei1.hip
-// each describe theirs in a Kg1Objective.
+// cornell_moe_amd/csrc/kg1_ascent.hpp -- what the ensemble forms of the one-point acquisition functions share, declared here and
+// compiled once in kg1_ascent.hip: the members' common checks, the staging of a call, the ensemble mean, the multistart ascent and
+// the drivers behind the three shapes of entry point (evaluate at points, multistart, greedy batch).  None of it knows the
+// objective; each client describes its own in a Kg1Objective.  The clients: kg1_opt.hip (the discretised knowledge gradient),
+// ei1.hip (the analytic expected improvement), gibbon1.hip (the min-value entropy acquisition) and cei1.hip (the constrained
+// expected improvement, whose members are groups of 1 + K GPs combined by its own rule in the place of the ensemble mean).
 #pragma once
 #include <vector>
 
@@ -45,11 +46,16 @@ struct Kg1Ensemble {
   // W = 2 E words travel where E do without
   int p = 0, pcap = 0, W = 0;
   double* dPending = nullptr;  // [pcap][dp] inside the one upload
+  // an objective that combines the members itself (Kg1Objective::combine; NULL: the ensemble mean): its hook, the members per
+  // group, the ascent's combined gradient [Kmax][d] behind the ascent's doubles and the one-entry table that names it
+  void (*combine)(const Kg1Ensemble& T, int C, double* value_out, double* grad_out) = nullptr;
+  int group = 1;
+  double* dComb = nullptr;
+  const double* const* dCombTab = nullptr;
   Kg1AscentSizes sz = {};
 };
 
-// An objective as the staging and the drivers see it (the hooks but `member`, `eval_points` and `pick_appended` may be NULL; the
-// third client is gibbon1.hip: the min-value entropy acquisition).
+// An objective as the staging and the drivers see it (the hooks but `member`, `eval_points` and `pick_appended` may be NULL).
 struct Kg1Objective {
   int nf;                      // fidelity coordinates (0: one view of the points)
   const double* discrete_all;  // the members' discrete sets back to back [sum A_e][d - nf]; NULL: the objective has none
@@ -69,6 +75,11 @@ struct Kg1Objective {
   // member e's reach it as Kg1Member::dExtra / nExtra.  NULL: the objective has none and the upload is laid out without the block.
   const double* member_extra;
   int num_member_extra;
+  // group > 1 and combine set: the E members are E / group groups of `group` consecutive members, and combine forms the ensemble's
+  // value [C] and / or gradient [C][d] (either may be NULL) from the members' dKg / dGrad (T.dKgTab, T.dGradTab) on T.z, in the
+  // place of the mean of the members.  With combine NULL or group <= 1 the drivers issue the launches they always did.
+  int group = 0;
+  void (*combine)(const Kg1Ensemble& T, int C, double* value_out, double* grad_out) = nullptr;
 };
 
 // One dim, one device, no member listed twice (MOE_ERR_INVALID_VALUE), behind num_fidelity < dim (MOE_ERR_BOUNDS); check_member:
@@ -76,9 +87,10 @@ struct Kg1Objective {
 void kg1_check_members(const std::vector<GpDev*>& gps, int nf, void (*check_member)(const GpDev& g, const GpDev& g0, size_t e, int nf));
 
 // The drivers (the members are checked).  Their arguments are those of kg_discrete_mcmc_on_device / _multistart / _suggest (gp.hpp)
-// without the objective's own.
+// without the objective's own.  members_out (may be NULL): every member's own value [E][C], in the same copy back.
 void kg1_ensemble_evaluate(const Kg1Objective& o, const std::vector<GpDev*>& gps, const double* pts, int C, bool want_grad,
-                           double* value_out, double* grad_out, const double* pending, int num_pending);
+                           double* value_out, double* grad_out, const double* pending, int num_pending,
+                           double* members_out = nullptr);
 void kg1_ensemble_multistart(const Kg1Objective& o, const std::vector<GpDev*>& gps, const moe_gd_params_t& outer,
                              const double* domain_bounds, const double* starts, int num_starts, int do_gradient_ascent,
                              double* best_point, double* best_value, int* found, double* start_values, int* kept_index,

@@ -458,6 +458,80 @@ int moe_gibbon_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, const moe_
                             const double* min_values, int num_min_values, const double* points_being_sampled, int num_being_sampled,
                             const double* starts, int num_starts, int do_gradient_ascent, int num_to_sample, double* best_points,
                             double* best_values, int* found, moe_error_t* err);
+/* The constrained expected improvement -- expected improvement times the probability of feasibility (Schonlau, Welch & Jones 1998;
+ * Gardner et al. 2014; Gelbart, Snoek & Adams 2014) -- for minimisation under K = num_constraints unknown constraints, averaged over
+ * an ensemble of E = num_mcmc joint hyper-samples, with pending points, evaluated on the device: value[i] and grad[i][dim] (want_grad
+ * != 0) at points [num_points][dim].  0 <= K <= 8.  Member e is a tuple of 1 + K GP handles: the objective GP gps[e] and the
+ * constraint GPs constraint_gps[k * num_mcmc + e] (one flat array [K][E]); constraint k is satisfied where c_k(x) <= thresholds[k].
+ * All GPs of a call share dim, the device and the observed-derivative list; they may differ in num_sampled, covariance type,
+ * hyper-parameters and noise.  No handle may appear twice anywhere in the call (every GP keeps its own workspaces).
+ * Pending points condition the covariance of EVERY GP of the call as in moe_ei_analytic_mcmc, word for word: the GP's own noise on
+ * their diagonal, its mean left alone, 1 + g rows per point under derivative observations, num_being_sampled (1 + g) <= 64.
+ * Per member e at x, with mu and var the posterior mean and the conditioned latent variance of the GP in question:
+ *   feasibility factor   F_{e,k} = Phi(z),  z = (tau_k - mu) / sigma,  sigma = sqrt(max(DBL_MIN, var)); Phi through erfc on the side
+ *                        of z's sign
+ *   its gradient         sigma_g = sqrt(max(150 eps^2, var)),  z_g = (tau_k - mu) / sigma_g,
+ *                        grad F = -(phi(z_g) / sigma_g) grad mu - (phi(z_g) z_g / (2 sigma_g^2)) grad var
+ *                        (moe_ei_analytic_mcmc's gradient form with (phi(z_g) / sigma_g, -phi(z_g) z_g / sigma_g^2) where it has
+ *                        (Phi(c_g), phi(c_g) / sigma_g): the same kernels serve)
+ *   improvement factor   EI_e exactly as in moe_ei_analytic_mcmc with the incumbent
+ *                        b'_e = min(best_so_far[e], min over the believed-feasible pending points j of mu_{e,0}(P_j)),
+ *                        P_j believed feasible under member e when mu_{e,k}(P_j) <= tau_k for every k
+ *                        (without the rule a greedy batch re-picks its own point, or lets a believed-infeasible pick lower the
+ *                        incumbent)
+ *   no feasible incumbent  best_so_far[e] may be +infinity ("no feasible observation yet"): while b'_e is +infinity the improvement
+ *                        factor is exactly 1 with a zero gradient, and the member's acquisition is its probability of feasibility;
+ *                        a believed-feasible pending point makes b'_e finite in the ordinary way
+ *   member value         A_e = EI_e F_{e,1} ... F_{e,K}, multiplied left to right; grad A_e by the product rule, each excluded
+ *                        product formed by the same left-to-right multiplication with its factor skipped, the terms added in the
+ *                        order objective, k = 1 .. K
+ *   ensemble             value[i] = (A_0 + ... + A_{E-1}) / E, grad likewise: members added in member order and divided once, no
+ *                        fused multiply-add anywhere in the product rule or the mean
+ * factors (may be NULL): [E][1 + K][num_points], the factor values EI_e, F_{e,1}, ..., F_{e,K} at every point; value[i] is, bit for
+ * bit, what the rule above makes of them on the host.  With K = 0 the call is moe_ei_analytic_mcmc bit for bit while every
+ * best_so_far[e] is finite.  A candidate's bits do not depend on how many share the call (passes of moe_ei1_pass_size(N) candidates),
+ * nor on want_grad, nor on ensemble-wide launches (the E (1 + K) GPs' chains are recorded and zipped where their shapes agree).
+ * One copy down, one stream (the first objective GP's), one wait, one copy back; no handle is modified.
+ * Errors, in this order, everything that needs no handle before a handle or the device is touched: num_mcmc outside 1 .. 1024 ->
+ * MOE_ERR_BOUNDS; a NULL array (gps, best_so_far, points, value, grad with want_grad) -> MOE_ERR_RUNTIME; num_constraints outside
+ * 0 .. 8 -> MOE_ERR_BOUNDS, payload (num_constraints, 0, 8); num_mcmc (1 + num_constraints) > 1024 -> MOE_ERR_BOUNDS, payload
+ * (num_mcmc, 1, 1024 / (1 + num_constraints) rounded down); constraint_gps or thresholds NULL with num_constraints > 0 ->
+ * MOE_ERR_RUNTIME; a threshold that is not finite -> MOE_ERR_INVALID_VALUE, payload (the value, k, 0); a best_so_far[e] that is NaN
+ * or -infinity -> MOE_ERR_INVALID_VALUE, payload (the value, e, 0); then moe_ei_analytic_mcmc's from num_points < 1 on, in its order
+ * and with its payloads, "member" counting the GPs flat as e (1 + K) + role (role 0: the objective GP, role k: constraint k): a
+ * NULL handle; a GP of another dim, then of another device; another observed-derivative list; a handle listed twice (a constraint
+ * handle equal to an objective handle included), payload (the later flat index, the earlier, 0); the row limit last.
+ * MOE_ERR_SINGULAR only for a pending point: payload (the flat index e (1 + K) + role of the first failing GP, the pending point),
+ * reported at the next wait.  A candidate never raises: the two variance floors are moe_ei_analytic_mcmc's. */
+int moe_ei_constrained_mcmc(const moe_gp_t* const* gps, int num_mcmc, const moe_gp_t* const* constraint_gps, int num_constraints,
+                            const double* thresholds, const double* best_so_far, const double* points_being_sampled,
+                            int num_being_sampled, const double* points, int num_points, int want_grad, double* value, double* grad,
+                            double* factors, moe_error_t* err);
+/* One suggestion by moe_ei_constrained_mcmc's objective, the whole loop on the device: moe_ei_analytic_mcmc_multistart's screening,
+ * top-20 rule, restarted ascent and end-point selection, its outputs and their meaning (the kernels of the ascent are shared; the
+ * product rule leaves ONE combined gradient per step, which the step kernel takes as a one-member ensemble), so that the path is,
+ * bit for bit, the one a host loop over moe_ei_constrained_mcmc walks.  Tensor-product domains only.  The host waits as often as
+ * moe_ei_analytic_mcmc_multistart does, and no more.
+ * Errors, in this order: those of moe_ei_constrained_mcmc that need no handle (outer, domain_bounds, starts, best_point, best_value
+ * and found among the arrays that must not be NULL; num_starts for num_points); max_num_steps < 1 with do_gradient_ascent != 0 ->
+ * MOE_ERR_BOUNDS; domain_type other than MOE_DOMAIN_TENSOR_PRODUCT -> MOE_ERR_INVALID_VALUE; then those that need the handles.
+ * MOE_ERR_SINGULAR as above, at the next wait. */
+int moe_ei_constrained_mcmc_multistart(const moe_gp_t* const* gps, int num_mcmc, const moe_gp_t* const* constraint_gps,
+                                       int num_constraints, const double* thresholds, const moe_gd_params_t* outer,
+                                       const double* domain_bounds, const double* best_so_far, const double* points_being_sampled,
+                                       int num_being_sampled, const double* starts, int num_starts, int do_gradient_ascent,
+                                       double* best_point, double* best_value, int* found, double* start_values, int* kept_index,
+                                       double* end_points, double* end_values, double* path, int* steps_taken, moe_error_t* err);
+/* num_to_sample points greedily: round t is moe_ei_constrained_mcmc_multistart from the same starts with pending points =
+ * points_being_sampled followed by the picks of the rounds before -- bit for bit what num_to_sample calls of that function return
+ * when each is fed its predecessors' points.  Staged once; a round appends ONE point (1 + g rows) to the extension of each of the
+ * E (1 + K) GPs, and where member e believes the pick feasible its believed value mu_{e,0}(x_t) joins b'_e, inside device memory.
+ * Errors: those of moe_ei_constrained_mcmc_multistart with moe_ei_analytic_mcmc_suggest's additions (num_to_sample, the row limit). */
+int moe_ei_constrained_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, const moe_gp_t* const* constraint_gps,
+                                    int num_constraints, const double* thresholds, const moe_gd_params_t* outer,
+                                    const double* domain_bounds, const double* best_so_far, const double* points_being_sampled,
+                                    int num_being_sampled, const double* starts, int num_starts, int do_gradient_ascent,
+                                    int num_to_sample, double* best_points, double* best_values, int* found, moe_error_t* err);
 /* compute_grad_variance_of_points -> ComputeGradVarianceOfPoints (gpp_math.cpp:1359-1373); out[num_derivs][m][m][dim] */
 int moe_gp_grad_variance(const moe_gp_t* gp, const double* pts, int num_pts, int num_derivs, double* out, moe_error_t* err);
 /* compute_grad_cholesky_variance_of_points -> ComputeGradCholeskyVarianceOfPoints (gpp_math.cpp:1454-1474) */
