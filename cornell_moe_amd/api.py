@@ -1159,6 +1159,111 @@ def ei_constrained_suggest(gps, constraint_gps, thresholds, gd_params, bounds, b
     return {"points": points, "values": values, "found": found.astype(bool)}
 
 
+def _ehvi_members(gps, gps2, reference_point, front):
+    """(objective-1 handles, objective-2 handles, E, dim, GPs kept alive, reference point [2], front [F][2] or None, F) of the
+    ensemble forms of the expected hypervolume improvement; gps and gps2 shaped alike (a DeviceGPMCMC, a list of DeviceGP or one
+    DeviceGP), E members each"""
+    if isinstance(gps, DeviceGP):
+        gps = [gps]
+    if isinstance(gps2, DeviceGP):
+        gps2 = [gps2]
+    arr, E, d, keep = _ensemble_handles(gps)
+    arr2, E2, d2, keep2 = _ensemble_handles(gps2)
+    if E == 0 or E2 != E:
+        raise BoundsException("one GP per ensemble member and objective", E2, E, E)
+    ref = np.ascontiguousarray(reference_point, dtype=np.float64).ravel()
+    if ref.size != 2:
+        raise BoundsException("the reference point has two coordinates", ref.size, 2, 2)
+    fr = np.ascontiguousarray([] if front is None else front, dtype=np.float64).reshape(-1, 2)
+    F = fr.shape[0]
+    return arr, arr2, E, d, (keep, keep2), ref, (fr if F else None), F
+
+
+def ehvi_ensemble(gps, gps2, reference_point, front, points, points_being_sampled=None, want_grad=True, want_member_values=False):
+    """moe_ehvi_mcmc: the two-objective expected hypervolume improvement (minimisation) averaged over the ensemble at points [C][dim],
+    in one device call.  Member e is gps[e] (objective 1) and gps2[e] (objective 2), without derivative observations.
+    reference_point [2]; front [F][2] (None or empty: none; F <= 960) sorted by the first objective ascending, mutually non-dominated
+    and strictly inside the reference point (pareto_front of expected_hypervolume_improvement.py returns that form).
+    points_being_sampled [p][dim] condition both GPs' covariances, and their believed outcomes join every member's own front.
+    Returns value [C], with want_grad (value, grad [C][dim]), and with want_member_values additionally the members' values [E][C] as
+    the last item.  SingularMatrixException(2 e + objective - 1, j): the GP, counted flat, and the pending point."""
+    arr, arr2, E, d, keep, ref, fr, F = _ehvi_members(gps, gps2, reference_point, front)
+    pts, pp = _d(points)
+    C_ = pts.reshape(-1, d).shape[0]
+    value = np.zeros(max(C_, 1))
+    grad = np.zeros((max(C_, 1), d)) if want_grad else None
+    members = np.zeros((E, max(C_, 1))) if want_member_values else None
+    p = _num_pending(points_being_sampled, d)
+    pend, pendp = _d(points_being_sampled) if p else (None, None)
+    err = _lib.MoeError()
+    _check(_lib.load().moe_ehvi_mcmc(
+        arr, arr2, E, ref.ctypes.data_as(dp), fr.ctypes.data_as(dp) if F else None, F, pendp, p, pp, C_, 1 if want_grad else 0,
+        value.ctypes.data_as(dp), grad.ctypes.data_as(dp) if want_grad else None,
+        members.ctypes.data_as(dp) if want_member_values else None, C.byref(err)), err)
+    out = (value, grad) if want_grad else (value,)
+    if want_member_values:
+        out = out + (members,)
+    return out if len(out) > 1 else out[0]
+
+
+def ehvi_multistart(gps, gps2, reference_point, front, gd_params, bounds, starts, gradient_ascent=True, want_path=False,
+                    points_being_sampled=None):
+    """moe_ehvi_mcmc_multistart: one suggestion by the ensemble-averaged expected hypervolume improvement -- ei_analytic_multistart's
+    screening, 20 kept starts, restarted ascent on the device and end-point selection, and its dict."""
+    arr, arr2, E, d, keep, ref, fr, F = _ehvi_members(gps, gps2, reference_point, front)
+    g = DeviceGP._gd(gd_params)
+    bounds, bp = _d(bounds)
+    starts, sp = _d(starts)
+    S = starts.reshape(-1, d).shape[0]
+    Kk = max(min(S, 20), 1)
+    rows = max(g.max_num_restarts, 0) * max(g.max_num_steps, 0) + 1
+    point = np.zeros(d)
+    start_values = np.zeros(max(S, 1))
+    kept = np.zeros(Kk, dtype=np.int32)
+    ends, end_values = np.zeros((Kk, d)), np.zeros(Kk)
+    steps = np.zeros(Kk, dtype=np.int32)
+    path = np.zeros((Kk, rows, d)) if (want_path and gradient_ascent) else None
+    value, found = C.c_double(0.0), C.c_int(0)
+    p = _num_pending(points_being_sampled, d)
+    pend, pendp = _d(points_being_sampled) if p else (None, None)
+    err = _lib.MoeError()
+    _check(_lib.load().moe_ehvi_mcmc_multistart(
+        arr, arr2, E, ref.ctypes.data_as(dp), fr.ctypes.data_as(dp) if F else None, F, C.byref(g), bp, pendp, p, sp, S,
+        1 if gradient_ascent else 0, point.ctypes.data_as(dp), C.byref(value), C.byref(found), start_values.ctypes.data_as(dp),
+        kept.ctypes.data_as(ip), ends.ctypes.data_as(dp), end_values.ctypes.data_as(dp),
+        path.ctypes.data_as(dp) if path is not None else None, steps.ctypes.data_as(ip), C.byref(err)), err)
+    out = {"point": point, "value": value.value, "found": bool(found.value), "start_values": start_values,
+           "kept_index": kept if gradient_ascent else None, "end_points": ends if gradient_ascent else None,
+           "end_values": end_values if gradient_ascent else None, "steps_taken": steps if gradient_ascent else None}
+    if want_path:
+        out["path"] = path
+    return out
+
+
+def ehvi_suggest(gps, gps2, reference_point, front, gd_params, bounds, starts, num_to_sample, gradient_ascent=True,
+                 points_being_sampled=None):
+    """moe_ehvi_mcmc_suggest: num_to_sample points greedily by the ensemble-averaged expected hypervolume improvement -- round t is
+    ehvi_multistart from the same starts [S][dim] with the pending points points_being_sampled [p][dim] (may be None) followed by
+    the points of the rounds before, bit for bit, in one device call.  p + num_to_sample - 1 <= 64.  Returns a dict: points
+    [q][dim], values [q], found [q]."""
+    arr, arr2, E, d, keep, ref, fr, F = _ehvi_members(gps, gps2, reference_point, front)
+    g = DeviceGP._gd(gd_params)
+    bounds, bp = _d(bounds)
+    starts, sp = _d(starts)
+    S = starts.reshape(-1, d).shape[0]
+    q = int(num_to_sample)
+    p = _num_pending(points_being_sampled, d)
+    pend, pendp = _d(points_being_sampled) if p else (None, None)
+    points, values = np.zeros((max(q, 1), d)), np.zeros(max(q, 1))
+    found = np.zeros(max(q, 1), dtype=np.int32)
+    err = _lib.MoeError()
+    _check(_lib.load().moe_ehvi_mcmc_suggest(
+        arr, arr2, E, ref.ctypes.data_as(dp), fr.ctypes.data_as(dp) if F else None, F, C.byref(g), bp, pendp, p, sp, S,
+        1 if gradient_ascent else 0, q, points.ctypes.data_as(dp), values.ctypes.data_as(dp), found.ctypes.data_as(ip), C.byref(err)),
+        err)
+    return {"points": points, "values": values, "found": found.astype(bool)}
+
+
 def _gibbon_members(gps, min_values):
     """(handles, count, dim, members kept alive, min-values [E][K], K) of the ensemble forms of the min-value entropy acquisition; a
     single DeviceGP counts as a list of one"""

@@ -1098,6 +1098,79 @@ int moe_ei_constrained_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, co
   });
 }
 
+// The GPs of a two-objective call, flat and ordered [e][objective]
+static std::vector<const moe_gp_t*> two_objective_handles(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, int num_mcmc) {
+  std::vector<const moe_gp_t*> flat(2 * (size_t)num_mcmc);
+  for (int e = 0; e < num_mcmc; ++e) {
+    flat[2 * (size_t)e] = gps[e];
+    flat[2 * (size_t)e + 1] = gps2[e];
+  }
+  return flat;
+}
+
+int moe_ehvi_mcmc(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, int num_mcmc, const double* reference_point,
+                  const double* front, int num_front, const double* points_being_sampled, int num_being_sampled, const double* points,
+                  int num_points, int want_grad, double* value, double* grad, double* member_values_out, moe_error_t* err) {
+  return guarded(err, [&] {
+    moe::check_ehvi_num_mcmc(num_mcmc);
+    require(gps && gps2 && reference_point && points && value && (want_grad == 0 || grad) && (num_front <= 0 || front), "NULL argument");
+    moe::check_ehvi_front(reference_point, front, num_front);  // (what needs no handle)
+    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_points);
+    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, 1);
+    const std::vector<const moe_gp_t*> flat = two_objective_handles(gps, gps2, num_mcmc);
+    const auto locks = lock_ensemble(flat.data(), (int)flat.size());
+    const std::vector<moe::GpDev*> v = ensemble(flat.data(), (int)flat.size());
+    moe::ehvi_mcmc_on_device(v, reference_point, front, num_front, points, num_points, want_grad != 0, value, grad, member_values_out,
+                             points_being_sampled, num_being_sampled);
+  });
+}
+
+int moe_ehvi_mcmc_multistart(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, int num_mcmc, const double* reference_point,
+                             const double* front, int num_front, const moe_gd_params_t* outer, const double* domain_bounds,
+                             const double* points_being_sampled, int num_being_sampled, const double* starts, int num_starts,
+                             int do_gradient_ascent, double* best_point, double* best_value, int* found, double* start_values,
+                             int* kept_index, double* end_points, double* end_values, double* path, int* steps_taken,
+                             moe_error_t* err) {
+  return guarded(err, [&] {
+    moe::check_ehvi_num_mcmc(num_mcmc);
+    require(gps && gps2 && reference_point && outer && domain_bounds && starts && best_point && best_value && found &&
+                (num_front <= 0 || front),
+            "NULL argument");
+    moe::check_ehvi_front(reference_point, front, num_front);
+    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_starts);
+    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, 1);
+    check_ascent_params(outer, do_gradient_ascent, "the expected hypervolume improvement");
+    const std::vector<const moe_gp_t*> flat = two_objective_handles(gps, gps2, num_mcmc);
+    const auto locks = lock_ensemble(flat.data(), (int)flat.size());
+    const std::vector<moe::GpDev*> v = ensemble(flat.data(), (int)flat.size());
+    moe::ehvi_mcmc_multistart(v, reference_point, front, num_front, *outer, domain_bounds, starts, num_starts, do_gradient_ascent,
+                              best_point, best_value, found, start_values, kept_index, end_points, end_values, path, steps_taken,
+                              points_being_sampled, num_being_sampled);
+  });
+}
+
+int moe_ehvi_mcmc_suggest(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, int num_mcmc, const double* reference_point,
+                          const double* front, int num_front, const moe_gd_params_t* outer, const double* domain_bounds,
+                          const double* points_being_sampled, int num_being_sampled, const double* starts, int num_starts,
+                          int do_gradient_ascent, int num_to_sample, double* best_points, double* best_values, int* found,
+                          moe_error_t* err) {
+  return guarded(err, [&] {
+    moe::check_ehvi_num_mcmc(num_mcmc);
+    require(gps && gps2 && reference_point && outer && domain_bounds && starts && best_points && best_values && found &&
+                (num_front <= 0 || front),
+            "NULL argument");
+    moe::check_ehvi_front(reference_point, front, num_front);
+    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_starts);
+    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, num_to_sample);
+    check_ascent_params(outer, do_gradient_ascent, "the expected hypervolume improvement");
+    const std::vector<const moe_gp_t*> flat = two_objective_handles(gps, gps2, num_mcmc);
+    const auto locks = lock_ensemble(flat.data(), (int)flat.size());
+    const std::vector<moe::GpDev*> v = ensemble(flat.data(), (int)flat.size());
+    moe::ehvi_mcmc_suggest(v, reference_point, front, num_front, *outer, domain_bounds, starts, num_starts, do_gradient_ascent,
+                           points_being_sampled, num_being_sampled, num_to_sample, best_points, best_values, found);
+  });
+}
+
 int moe_kg_mcmc_finalize(double* kg, double* grad_kg, const double* points_to_sample_all, int num_evals, int num_to_sample,
                          int dim, int num_fidelity, int total_num_mcmc) {
   if (!kg || !points_to_sample_all || num_evals <= 0 || num_to_sample <= 0 || dim <= 0 || num_fidelity < 0 ||

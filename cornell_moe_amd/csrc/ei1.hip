@@ -217,8 +217,8 @@ __global__ __launch_bounds__(256) void ei1_grad_g_kernel(int P, int ld, int d, i
 
 // Where one GP's per-pass scratch and results live for a call of at most C candidates, inside the GP's own kg1D (results first:
 // [EI C | grad C d]), dE and dEK: Kg1Member with an empty set (A = 0; dAA holds mu(P), dScal Phi(c_g), dMuh mu(x)).  pcap: room
-// for that many extension ROWS, a multiple of 1 + g.
-Kg1Member ei1_member(GpDev& gp, int C, double best, bool with_grad, int* fail, int pcap, int* fail_pending) {
+// for that many extension ROWS, a multiple of 1 + g.  outs: result sets back to back ([outs][C] values, [outs][C][d] gradients).
+Kg1Member ei1_member(GpDev& gp, int C, double best, bool with_grad, int* fail, int pcap, int* fail_pending, int outs) {
   gp.use_device();
   Kg1Member m;
   m.gp = &gp;
@@ -232,12 +232,12 @@ Kg1Member ei1_member(GpDev& gp, int C, double best, bool with_grad, int* fail, i
   m.g1 = 1 + gp.g;
   m.ld = N + pcap;
   const size_t nC = (size_t)C, nW = (size_t)m.widest, nL = (size_t)m.ld, nV = nL * nW, nP = (size_t)pcap;
-  const size_t nOut = nC * (with_grad ? 1 + (size_t)gp.d : 1);
+  const size_t nOut = (size_t)outs * nC * (with_grad ? 1 + (size_t)gp.d : 1);
   gp.kg1D.reserve(nOut + 1 + (nP + 1) + nV + (with_grad ? 2 * nV : 0) + 2 * nW + (pcap > 0 ? nL * ((size_t)gp.dp + 1 + nP) : 0));
   gp.kg1LastC = 0;  // (kg1D no longer holds a knowledge-gradient call's envelope counts)
   m.dOut = gp.kg1D.p;
   m.dKg = m.dOut;
-  m.dGrad = m.dKg + nC;
+  m.dGrad = m.dKg + (size_t)outs * nC;
   m.dBp = m.dOut + nOut;
   m.dAA = m.dBp + 1;
   m.dVx = m.dAA + nP + 1;

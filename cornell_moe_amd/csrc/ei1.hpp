@@ -11,8 +11,9 @@ namespace moe {
 
 // Where one GP's per-pass scratch and results live for a call of at most C candidates (Kg1Member with an empty set: dKg the values
 // [C], dGrad [C][d], dAA mu(P), dScal the candidates' scalars s, dMuh mu(x), dVx the columns, dT / dU the gradient's columns);
-// pcap: room for that many extension ROWS, a multiple of 1 + g.  Nothing is launched.
-Kg1Member ei1_member(GpDev& gp, int C, double best, bool with_grad, int* fail, int pcap, int* fail_pending);
+// pcap: room for that many extension ROWS, a multiple of 1 + g.  outs: that many result sets back to back, dKg [outs][C] and dGrad
+// [outs][C][d] (ehvi1.hip keeps mu and var, and their gradients, apart).  Nothing is launched.
+Kg1Member ei1_member(GpDev& gp, int C, double best, bool with_grad, int* fail, int pcap, int* fail_pending, int outs = 1);
 
 // One dim, one device, one observed-derivative list, no member listed twice; then pending_room (1 + g) <= kKg1MaxPending rows.
 void ei1_check_members(const std::vector<GpDev*>& gps, int pending_room);

@@ -72,6 +72,9 @@ struct GpDev {
   // integers (the members' failure words first)
   DevBuf<double> kg1oD;
   DevBuf<int> kg1oI;
+  // the expected hypervolume improvement (ehvi1.hip; held by the ensemble's first member): the caller's front, the members' fronts
+  // and their counts, the members' values and gradient coefficients
+  DevBuf<double> ehviD;
   // the ensemble-averaged posterior mean and the recommendation (recommend.hip; held by the ensemble's first member): the call's
   // doubles (results first: one copy back) and the start indices
   DevBuf<double> recD;
@@ -363,6 +366,27 @@ void ei_constrained_mcmc_suggest(const std::vector<GpDev*>& gps, int num_constra
                                  const moe_gd_params_t& outer, const double* domain_bounds, const double* best_so_far,
                                  const double* starts, int num_starts, int do_gradient_ascent, const double* pending, int num_pending,
                                  int num_to_sample, double* best_points, double* best_values, int* found);
+// ehvi1.hip: the two-objective expected hypervolume improvement averaged over an ensemble (moe_ehvi_mcmc), its multistart ascent
+// (moe_ehvi_mcmc_multistart) and greedy batches (moe_ehvi_mcmc_suggest): ei1.hip's three over members of two GPs each, gps [2 E]
+// ordered [e][objective], without derivative observations.  reference_point [2]; front [num_front][2] sorted by the first objective
+// ascending, mutually non-dominated, strictly inside the reference point.  check_ehvi_num_mcmc / check_ehvi_front: what needs no
+// handle.  member_values_out (may be NULL): [E][C], every member's own value A_e.
+constexpr int kEhviMaxFront = 960;
+constexpr int kEhviMaxMembers = 512;
+void check_ehvi_num_mcmc(int num_mcmc);
+void check_ehvi_front(const double* reference_point, const double* front, int num_front);
+void ehvi_mcmc_on_device(const std::vector<GpDev*>& gps, const double* reference_point, const double* front, int num_front,
+                         const double* pts, int C, bool want_grad, double* value_out, double* grad_out, double* member_values_out,
+                         const double* pending, int num_pending);
+void ehvi_mcmc_multistart(const std::vector<GpDev*>& gps, const double* reference_point, const double* front, int num_front,
+                          const moe_gd_params_t& outer, const double* domain_bounds, const double* starts, int num_starts,
+                          int do_gradient_ascent, double* best_point, double* best_value, int* found, double* start_values,
+                          int* kept_index, double* end_points, double* end_values, double* path, int* steps_taken,
+                          const double* pending, int num_pending);
+void ehvi_mcmc_suggest(const std::vector<GpDev*>& gps, const double* reference_point, const double* front, int num_front,
+                       const moe_gd_params_t& outer, const double* domain_bounds, const double* starts, int num_starts,
+                       int do_gradient_ascent, const double* pending, int num_pending, int num_to_sample, double* best_points,
+                       double* best_values, int* found);
 // loo.hip: leave-one-out cross-validation on the GP's current factorisation, every one of the N = n (1 + g) scalar observations left
 // out by itself.  mean_out / var_out [n][1 + g]: the LOO predictive mean (function values in the caller's units) and variance.
 void loo_predict_on_device(GpDev& gp, double* mean_out, double* var_out);

@@ -1,6 +1,6 @@
 // cornell_moe_amd/csrc/kg1_ascent.hip -- what the ensemble forms of the one-point acquisition functions share (kg1_opt.hip: the
 // discretised knowledge gradient; ei1.hip: the analytic expected improvement; gibbon1.hip: the min-value entropy acquisition;
-// cei1.hip: the constrained expected improvement), compiled once: the ensemble mean, the multistart
+// cei1.hip: the constrained expected improvement; ehvi1.hip: the expected hypervolume improvement), compiled once: the ensemble mean, the multistart
 // ascent's gather, step and round kernels, the recorded and zipped evaluation of the members' chains, the ascent itself (ascend()),
 // the staging of a call (stage(), stage_ascent()) and the three drivers behind the entry points (kg1_ascent.hpp).  None of it knows
 // the objective: a Kg1Objective says how a member is built, which chain evaluates it and what follows its extension.
@@ -460,7 +460,9 @@ Kg1Ensemble::Kg1Ensemble(const std::vector<GpDev*>& members, const Kg1Objective&
     if (E % o.group != 0) throw Error(MOE_ERR_RUNTIME, "the members do not fill their groups");
     combine = o.combine;
     group = o.group;
+    group_values = o.group_values;
   }
+  client = o.client;
   gps[0]->use_device();
 }
 
@@ -489,7 +491,8 @@ void kg1_ensemble_evaluate(const Kg1Objective& o, const std::vector<GpDev*>& gps
   const int d = T.d, W = T.W;
   // the call's doubles, all of them the copy back: [failure words | value C | grad C d | the members' values E C (members_out)]
   const size_t oMem = (size_t)W + (size_t)C * (want_grad ? 1 + d : 1);
-  const size_t nOut = oMem + (members_out != nullptr ? (size_t)T.E * C : 0);
+  const size_t nMem = (size_t)(T.group_values ? T.E / T.group : T.E) * C;
+  const size_t nOut = oMem + (members_out != nullptr ? nMem : 0);
   g0.kg1oD.reserve(nOut);
   g0.hStateOut.reserve(nOut);
   stage(T, o, nullptr, pts, C, want_grad, 0, pending, num_pending);
@@ -502,7 +505,9 @@ void kg1_ensemble_evaluate(const Kg1Objective& o, const std::vector<GpDev*>& gps
     launch_mean_of_members(T, T.dKgTab, C, dOut + W);
     if (want_grad) launch_mean_of_members(T, T.dGradTab, (long)C * d, dOut + W + C);
   }
-  if (members_out != nullptr)
+  if (members_out != nullptr && T.group_values)  // (the objective's combine has left its groups' values side by side)
+    copy_async(dOut + oMem, T.dGroupVals, sizeof(double) * nMem, hipMemcpyDeviceToDevice, T.z);
+  else if (members_out != nullptr)
     MOE_LAUNCH_NOW(kg1_members_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)T.E), dim3(256), 0, T.z, (long)C, T.dKgTab,
                    dOut + oMem);
   MOE_LAUNCH_NOW(kg1_words_kernel, dim3(1), dim3(256), 0, T.z, (const int*)T.iFail, W, dOut);
@@ -513,7 +518,7 @@ void kg1_ensemble_evaluate(const Kg1Objective& o, const std::vector<GpDev*>& gps
   throw_if_singular(T, out);
   std::memcpy(value_out, out + W, sizeof(double) * (size_t)C);
   if (want_grad) std::memcpy(grad_out, out + W + C, sizeof(double) * (size_t)C * d);
-  if (members_out != nullptr) std::memcpy(members_out, out + oMem, sizeof(double) * (size_t)T.E * C);
+  if (members_out != nullptr) std::memcpy(members_out, out + oMem, sizeof(double) * nMem);
 }
 
 void kg1_ensemble_multistart(const Kg1Objective& o, const std::vector<GpDev*>& gps, const moe_gd_params_t& outer,

@@ -3,7 +3,8 @@
 // the drivers behind the three shapes of entry point (evaluate at points, multistart, greedy batch).  None of it knows the
 // objective; each client describes its own in a Kg1Objective.  The clients: kg1_opt.hip (the discretised knowledge gradient),
 // ei1.hip (the analytic expected improvement), gibbon1.hip (the min-value entropy acquisition) and cei1.hip (the constrained
-// expected improvement, whose members are groups of 1 + K GPs combined by its own rule in the place of the ensemble mean).
+// expected improvement, whose members are groups of 1 + K GPs combined by its own rule in the place of the ensemble mean) and
+// ehvi1.hip (the two-objective expected hypervolume improvement: groups of two GPs and a Pareto front per group).
 #pragma once
 #include <vector>
 
@@ -52,6 +53,11 @@ struct Kg1Ensemble {
   int group = 1;
   double* dComb = nullptr;
   const double* const* dCombTab = nullptr;
+  // Kg1Objective::client, and with Kg1Objective::group_values the groups' own values [E / group][C] (C: the staged candidates) that
+  // combine leaves whenever it forms the value: the objective's all_extended hook says where they lie
+  const void* client = nullptr;
+  bool group_values = false;
+  const double* dGroupVals = nullptr;
   Kg1AscentSizes sz = {};
 };
 
@@ -80,6 +86,11 @@ struct Kg1Objective {
   // place of the mean of the members.  With combine NULL or group <= 1 the drivers issue the launches they always did.
   int group = 0;
   void (*combine)(const Kg1Ensemble& T, int C, double* value_out, double* grad_out) = nullptr;
+  // what the objective's hooks need of the call beside the members (Kg1Ensemble::client); nothing here reads it
+  const void* client = nullptr;
+  // with combine: kg1_ensemble_evaluate's members_out is the groups' own values [E / group][C], taken from Kg1Ensemble::dGroupVals,
+  // in the place of the members' [E][C]
+  bool group_values = false;
 };
 
 // One dim, one device, no member listed twice (MOE_ERR_INVALID_VALUE), behind num_fidelity < dim (MOE_ERR_BOUNDS); check_member:

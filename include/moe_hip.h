@@ -532,6 +532,65 @@ int moe_ei_constrained_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, co
                                     const double* domain_bounds, const double* best_so_far, const double* points_being_sampled,
                                     int num_being_sampled, const double* starts, int num_starts, int do_gradient_ascent,
                                     int num_to_sample, double* best_points, double* best_values, int* found, moe_error_t* err);
+/* The two-objective expected hypervolume improvement (EHVI; Emmerich, Giannakoglou & Naujoks 2006; Emmerich, Deutz & Klinkenberg
+ * 2011; Yang et al. 2019) averaged over a hyper-parameter ensemble, at points [num_points][dim], with pending points.  Minimisation.
+ * Member e is two GPs, gps[e] for objective 1 and gps2[e] for objective 2: one dim, one device, no derivative observations; their
+ * observation lists may differ.  reference_point [2] = (r1, r2); front [num_front][2] = (u_i, v_i), 0 <= num_front <= 960, finite,
+ * strictly inside the reference point, sorted u_1 < ... < u_F and mutually non-dominated, hence v_1 > ... > v_F (may be NULL with
+ * num_front = 0).  With u_0 = -infinity, u_{F+1} = r1, v_0 = r2, and mu_r, var_r the posterior mean and the conditioned latent
+ * variance of objective r's GP at x:
+ *   psi_r(t) = (t - mu_r) Phi(z) + sigma_r phi(z),  z = (t - mu_r) / sigma_r,  sigma_r = sqrt(max(DBL_MIN, var_r)),
+ *              psi_1(-infinity) = 0
+ *   member value   A_e = max(0, sum_{i = 0 .. F} [psi_1(u_{i+1}) - psi_1(u_i)] psi_2(v_i))
+ *   its gradient   through d psi / d mu = -Phi(z_g) and d psi / d var = phi(z_g) / (2 sigma_g), sigma_g = sqrt(max(150 eps^2, var))
+ *                  (moe_ei_analytic_mcmc's two floors), applied to grad mu_r and grad var_r of both GPs; 0 where A_e is clipped
+ *   ensemble       value[i] = (A_0 + ... + A_{E-1}) / E, grad likewise: members added in member order and divided once
+ * With num_front = 0 a member's value is the product of two analytic expected improvements with the incumbents r1 and r2.
+ * Pending points: both GPs' variances are conditioned on them as in moe_ei_analytic_mcmc (the means are left alone), and the believed
+ * outcome (mu_{e,1}(P_j), mu_{e,2}(P_j)) joins member e's OWN front, in the order of j, when it lies strictly inside the reference
+ * point and no front point (u, v) has u <= it and v <= it in both objectives; the front points it dominates leave.
+ * member_values_out (may be NULL): [E][num_points], every A_e; value[i] is, bit for bit, their mean formed in member order on the host.
+ * A candidate's bits do not depend on how many share the call (passes of moe_ei1_pass_size(N) candidates), nor on want_grad, nor on
+ * ensemble-wide launches; the strip sum's order is fixed by the front's size alone (csrc/ehvi1.hip).  No handle is modified.
+ * Errors, in this order, everything that needs no handle before a handle or the device is touched: num_mcmc outside 1 .. 512 ->
+ * MOE_ERR_BOUNDS, payload (num_mcmc, 1, 512); a NULL array (gps, gps2, reference_point, points, value, grad with want_grad, front
+ * with num_front > 0) -> MOE_ERR_RUNTIME; num_front outside 0 .. 960 -> MOE_ERR_BOUNDS, payload (num_front, 0, 960); a reference
+ * point that is not finite -> MOE_ERR_INVALID_VALUE, payload (the value, its index, 0); a front point that is not finite, not
+ * strictly inside the reference point, or not behind its predecessor in the order above -> MOE_ERR_INVALID_VALUE, payload (the
+ * point's index, 0, 0); num_points < 1 -> MOE_ERR_BOUNDS; num_being_sampled outside 0 .. 64 -> MOE_ERR_BOUNDS; points_being_sampled
+ * NULL with num_being_sampled > 0 -> MOE_ERR_RUNTIME; then, "member" counting the GPs flat as 2 e + objective - 1: a NULL handle ->
+ * MOE_ERR_RUNTIME; a GP of another dim, then of another device -> MOE_ERR_INVALID_VALUE; a GP with derivative observations ->
+ * MOE_ERR_INVALID_VALUE, payload (its num_derivatives, 0, the flat index); a handle listed twice (gps2[e] equal to some gps[f]
+ * included) -> MOE_ERR_INVALID_VALUE, payload (the later flat index, the earlier, 0).
+ * MOE_ERR_SINGULAR only for a pending point: payload (the flat index of the first failing GP, the pending point), reported at the
+ * next wait.  A candidate never raises. */
+int moe_ehvi_mcmc(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, int num_mcmc, const double* reference_point,
+                  const double* front, int num_front, const double* points_being_sampled, int num_being_sampled, const double* points,
+                  int num_points, int want_grad, double* value, double* grad, double* member_values_out, moe_error_t* err);
+/* One suggestion by moe_ehvi_mcmc's objective, the whole loop on the device: moe_ei_analytic_mcmc_multistart's screening, top-20
+ * rule, restarted ascent and end-point selection, its outputs and their meaning (the kernels of the ascent are shared; the strip
+ * rule leaves ONE combined gradient per step), so that the path is, bit for bit, the one a host loop over moe_ehvi_mcmc walks.
+ * Tensor-product domains only.
+ * Errors, in this order: those of moe_ehvi_mcmc that need no handle (outer, domain_bounds, starts, best_point, best_value and found
+ * among the arrays that must not be NULL; num_starts for num_points); max_num_steps < 1 with do_gradient_ascent != 0 ->
+ * MOE_ERR_BOUNDS; domain_type other than MOE_DOMAIN_TENSOR_PRODUCT -> MOE_ERR_INVALID_VALUE; then those that need the handles. */
+int moe_ehvi_mcmc_multistart(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, int num_mcmc, const double* reference_point,
+                             const double* front, int num_front, const moe_gd_params_t* outer, const double* domain_bounds,
+                             const double* points_being_sampled, int num_being_sampled, const double* starts, int num_starts,
+                             int do_gradient_ascent, double* best_point, double* best_value, int* found, double* start_values,
+                             int* kept_index, double* end_points, double* end_values, double* path, int* steps_taken,
+                             moe_error_t* err);
+/* num_to_sample points greedily: round t is moe_ehvi_mcmc_multistart from the same starts with pending points = points_being_sampled
+ * followed by the picks of the rounds before -- bit for bit what num_to_sample calls of that function return when each is fed its
+ * predecessors' points.  Staged once; a round appends ONE row to the extension of each of the 2 E GPs and the pick's believed
+ * outcome to every member's front, inside device memory.
+ * Errors: those of moe_ehvi_mcmc_multistart, with num_to_sample < 1 or num_being_sampled + num_to_sample - 1 > 64 -> MOE_ERR_BOUNDS
+ * behind num_being_sampled. */
+int moe_ehvi_mcmc_suggest(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, int num_mcmc, const double* reference_point,
+                          const double* front, int num_front, const moe_gd_params_t* outer, const double* domain_bounds,
+                          const double* points_being_sampled, int num_being_sampled, const double* starts, int num_starts,
+                          int do_gradient_ascent, int num_to_sample, double* best_points, double* best_values, int* found,
+                          moe_error_t* err);
 /* compute_grad_variance_of_points -> ComputeGradVarianceOfPoints (gpp_math.cpp:1359-1373); out[num_derivs][m][m][dim] */
 int moe_gp_grad_variance(const moe_gp_t* gp, const double* pts, int num_pts, int num_derivs, double* out, moe_error_t* err);
 /* compute_grad_cholesky_variance_of_points -> ComputeGradCholeskyVarianceOfPoints (gpp_math.cpp:1454-1474) */
