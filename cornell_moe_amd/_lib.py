@@ -123,6 +123,9 @@ SIGNATURES = {
                                                     ip, ip, dp, dp, dp, _EP]),
     "moe_posterior_mean_members_minimize": (C.c_int, [_GPA, C.c_int, C.c_int, C.POINTER(GdParams), dp, dp, C.c_int, C.c_int, dp, dp,
                                                       ip, ip, dp, dp, _EP]),
+    "moe_gp_paths_evaluate": (C.c_int, [_GPA, C.c_int, dp, dp, C.c_int, dp, dp, C.c_int, dp, C.c_int, C.c_int, dp, dp, _EP]),
+    "moe_gp_paths_minimize": (C.c_int, [_GPA, C.c_int, dp, dp, C.c_int, dp, dp, C.c_int, C.POINTER(GdParams), dp, dp, C.c_int, dp, dp,
+                                        ip, ip, dp, dp, _EP]),
     "moe_kg_mcmc_finalize": (C.c_int, [dp, dp, dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "moe_ei_mcmc_batch": (C.c_int, [_GPA, C.c_int, dp, C.c_int, dp, C.c_int, C.c_int, C.c_int, dp, dp, C.c_int, dp, dp, _EP]),
     "moe_kg_mcmc_multistart": (C.c_int, [_GPA, C.c_int, C.c_int, C.POINTER(GdParams), C.POINTER(GdParams), dp, dp, C.c_int, dp,

@@ -195,6 +195,7 @@ class DeviceGP(object):
                              C.byref(self._h), C.byref(err))
         _check(rc, err)
         self.device = device
+        self.cov_type = int(cov_type)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -1423,6 +1424,72 @@ def minimize_member_means(gps, candidates, gd, bounds, num_fidelity=0, want_mean
     out = dict(best_points=points, best_values=values, start_index=index.astype(np.int64), fell_back=fell.astype(bool))
     if want_means:
         out["means"] = means
+    if want_trace:
+        out["trace"] = trace
+    return out
+
+
+def _path_tables(E, d, n, frequencies, phases, weights, noise_normals):
+    """the tables of a paths call as contiguous doubles, and (M, S)"""
+    freq = np.ascontiguousarray(frequencies, dtype=np.float64).reshape(-1, max(d, 1))
+    M = freq.shape[0]
+    ph = np.ascontiguousarray(phases, dtype=np.float64).ravel()
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    z = np.ascontiguousarray(noise_normals, dtype=np.float64)
+    if ph.size != M or w.ndim != 3 or w.shape[0] != max(E, 1) or w.shape[2] != M:
+        raise InvalidValueException("the tables must be frequencies [M][dim], phases [M], weights [E][S][M]", ph.size, M, 0)
+    S = w.shape[1]
+    if z.shape != (max(E, 1), S, n):
+        raise InvalidValueException("noise_normals must be [E][S][num_sampled]", z.size, max(E, 1) * S * n, 0)
+    return freq, ph, w, z, M, S
+
+
+def paths_evaluate(gps, frequencies, phases, weights, noise_normals, points, want_grad=False):
+    """moe_gp_paths_evaluate: the posterior function paths f_s of every member of the ensemble (pathwise conditioning, moe_hip.h) at
+    points [C][dim] in one device call.  frequencies [M][dim] (unit scale, drawn for the members' covariance), phases [M], weights
+    [E][S][M], noise_normals [E][S][num_sampled].  Returns values [E][S][C], with want_grad (values, grad [E][S][C][dim])."""
+    arr, E, d, keep = _ensemble_handles(gps)
+    n = keep[0].n if keep else 0
+    freq, ph, w, z, M, S = _path_tables(E, d, n, frequencies, phases, weights, noise_normals)
+    pts, pp = _d(points)
+    C_ = pts.reshape(-1, max(d, 1)).shape[0]
+    values = np.zeros((max(E, 1), S, max(C_, 1)))
+    grad = np.zeros((max(E, 1), S, max(C_, 1), max(d, 1))) if want_grad else None
+    err = _lib.MoeError()
+    _check(_lib.load().moe_gp_paths_evaluate(arr, E, freq.ctypes.data_as(dp), ph.ctypes.data_as(dp), M, w.ctypes.data_as(dp),
+                                             z.ctypes.data_as(dp), S, pp, C_, 1 if want_grad else 0, values.ctypes.data_as(dp),
+                                             grad.ctypes.data_as(dp) if want_grad else None, C.byref(err)), err)
+    return (values, grad) if want_grad else values
+
+
+def paths_minimize(gps, frequencies, phases, weights, noise_normals, gd, bounds, candidates, want_screened=False, want_trace=False):
+    """moe_gp_paths_minimize: every path of every member screened at candidates [C][dim], minimised by minimize_member_means' line
+    search from its best candidate on the device, the start kept if the search ended worse.  The tables as in paths_evaluate.
+    Returns a dict: best_points [E][S][dim], best_values, start_index, fell_back (bool) [E][S]; with want_screened screened
+    [E][S][C]; with want_trace trace [E][S][max_num_restarts][max_num_steps][dim + 6] (moe_hip.h)."""
+    arr, E, d, keep = _ensemble_handles(gps)
+    n = keep[0].n if keep else 0
+    freq, ph, w, z, M, S = _path_tables(E, d, n, frequencies, phases, weights, noise_normals)
+    g = DeviceGP._gd(gd)
+    cand, cp = _d(candidates)
+    C_ = cand.reshape(-1, max(d, 1)).shape[0]
+    bounds, bp = _d(bounds)
+    En, R, T = max(E, 1), max(g.max_num_restarts, 0), max(g.max_num_steps, 0)
+    points = np.zeros((En, S, max(d, 1)))
+    values = np.zeros((En, S))
+    index = np.zeros((En, S), dtype=np.int32)
+    fell = np.zeros((En, S), dtype=np.int32)
+    screened = np.zeros((En, S, max(C_, 1))) if want_screened else None
+    trace = np.zeros((En, S, R, T, max(d, 1) + TRACE_EXTRA)) if want_trace else None
+    err = _lib.MoeError()
+    _check(_lib.load().moe_gp_paths_minimize(arr, E, freq.ctypes.data_as(dp), ph.ctypes.data_as(dp), M, w.ctypes.data_as(dp),
+                                             z.ctypes.data_as(dp), S, C.byref(g), bp, cp, C_, points.ctypes.data_as(dp),
+                                             values.ctypes.data_as(dp), index.ctypes.data_as(_lib.ip), fell.ctypes.data_as(_lib.ip),
+                                             screened.ctypes.data_as(dp) if want_screened else None,
+                                             trace.ctypes.data_as(dp) if want_trace else None, C.byref(err)), err)
+    out = dict(best_points=points, best_values=values, start_index=index.astype(np.int64), fell_back=fell.astype(bool))
+    if want_screened:
+        out["screened"] = screened
     if want_trace:
         out["trace"] = trace
     return out

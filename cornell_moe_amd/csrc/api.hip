@@ -842,6 +842,42 @@ int moe_posterior_mean_members_minimize(const moe_gp_t* const* gps, int num_mcmc
   });
 }
 
+int moe_gp_paths_evaluate(const moe_gp_t* const* gps, int num_mcmc, const double* frequencies, const double* phases, int num_features,
+                          const double* weights, const double* noise_normals, int num_paths, const double* points, int num_points,
+                          int want_grad, double* values, double* grad, moe_error_t* err) {
+  return guarded(err, [&] {
+    require(gps != nullptr, "gps is NULL");
+    moe::check_paths_shapes(num_features, num_paths, num_mcmc);  // (what needs no handle)
+    require(frequencies && phases && weights && noise_normals && points && values && (want_grad == 0 || grad), "NULL argument");
+    if (num_points < 1) throw moe::Error(MOE_ERR_BOUNDS, "the number of points must be positive", num_points, 1, 1e9);
+    const auto locks = lock_ensemble(gps, num_mcmc);
+    const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
+    moe::paths_evaluate(v, frequencies, phases, num_features, weights, noise_normals, num_paths, points, num_points, want_grad != 0,
+                        values, grad);
+  });
+}
+
+int moe_gp_paths_minimize(const moe_gp_t* const* gps, int num_mcmc, const double* frequencies, const double* phases, int num_features,
+                          const double* weights, const double* noise_normals, int num_paths, const moe_gd_params_t* gd,
+                          const double* domain_bounds, const double* candidates, int num_candidates, double* best_points,
+                          double* best_values, int* start_index, int* fell_back, double* screened_out, double* trace_out,
+                          moe_error_t* err) {
+  return guarded(err, [&] {
+    require(gps != nullptr, "gps is NULL");
+    moe::check_paths_shapes(num_features, num_paths, num_mcmc);
+    require(frequencies && phases && weights && noise_normals && gd && domain_bounds && candidates && best_points, "NULL argument");
+    if (num_candidates < 1) throw moe::Error(MOE_ERR_BOUNDS, "the number of candidates must be positive", num_candidates, 1, 1e9);
+    if (gd->max_num_steps < 1) throw moe::Error(MOE_ERR_BOUNDS, "max_num_steps must be positive", gd->max_num_steps, 1, 1e9);
+    if (gd->max_num_restarts < 1) throw moe::Error(MOE_ERR_BOUNDS, "max_num_restarts must be positive", gd->max_num_restarts, 1, 1e9);
+    if (gd->domain_type != MOE_DOMAIN_TENSOR_PRODUCT)
+      throw moe::Error(MOE_ERR_BOUNDS, "the paths' minimisation supports tensor-product domains only", gd->domain_type, 0, 0);
+    const auto locks = lock_ensemble(gps, num_mcmc);
+    const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
+    moe::paths_minimize(v, frequencies, phases, num_features, weights, noise_normals, num_paths, *gd, domain_bounds, candidates,
+                        num_candidates, best_points, best_values, start_index, fell_back, screened_out, trace_out);
+  });
+}
+
 int moe_kg_discrete_mcmc(const moe_gp_t* const* gps, int num_mcmc, int num_fidelity, const double* discrete_all,
                          const int* num_discrete, const double* best_so_far, const double* points, int num_points, int want_grad,
                          double* kg, double* grad, moe_error_t* err) {

@@ -83,6 +83,10 @@ struct GpDev {
   // first: one copy back) and the start indices
   DevBuf<double> pmmD;
   DevBuf<int> pmmI;
+  // posterior function paths (paths.hip; held by the ensemble's first member): the call's doubles (results first: one copy back,
+  // the paths' v and its scratch last) and the start indices
+  DevBuf<double> pathD;
+  DevBuf<int> pathI;
   int num_cu = 256;
   // per-dimension mean and max |x - mean| of the training points (refreshed by rebuild() and by the append path of add_points):
   // the frame centre of the KG coordinate tables and the extent the kernel selection needs, so that an evaluation does not
@@ -423,6 +427,23 @@ void posterior_mean_members_minimize(const std::vector<GpDev*>& gps, int num_fid
                                      const double* domain_bounds, const double* candidates, int C, bool per_member,
                                      double* best_points, double* best_values, int* start_index, int* fell_back, double* means_out,
                                      double* trace_out);
+// pm_members.hip's selection for any table of rows: index[r] = numpy.argmin(values[r][0 .. C)), one workgroup per row
+void launch_pmm_argmin(int rows, int C, const double* values, int* index, hipStream_t s);
+// paths.hip: posterior function paths by pathwise conditioning and their minimisers (moe_gp_paths_evaluate, moe_gp_paths_minimize).
+// frequencies [M][dim], phases [M], weights [E][S][M], noise_normals [E][S][n]; the members without derivative observations, of one
+// dim, device, set of sampled points and cov_type (MOE_ERR_INVALID_VALUE otherwise).  check_paths_shapes: what needs no handle.
+constexpr int kPathsMaxFeatures = 4096;
+constexpr int kPathsMaxPaths = 1024;
+void check_paths_shapes(int num_features, int num_paths, int num_mcmc);
+// values [E][S][C]; grad [E][S][C][dim] (want_grad)
+void paths_evaluate(const std::vector<GpDev*>& gps, const double* frequencies, const double* phases, int M, const double* weights,
+                    const double* noise_normals, int S, const double* pts, int C, bool want_grad, double* values, double* grad);
+// best_points [E][S][dim]; best_values / start_index / fell_back [E][S], screened_out [E][S][C] and trace_out
+// [E S][restarts steps][dim + 6] may be NULL; the caller has validated gd and C.
+void paths_minimize(const std::vector<GpDev*>& gps, const double* frequencies, const double* phases, int M, const double* weights,
+                    const double* noise_normals, int S, const moe_gd_params_t& gd, const double* domain_bounds, const double* candidates,
+                    int C, double* best_points, double* best_values, int* start_index, int* fell_back, double* screened_out,
+                    double* trace_out);
 // r6 (query_grad.hip): ComputeGradVarianceOfPoints / ComputeGradCholeskyVarianceOfPoints (gpp_math.cpp:1267-1474) for the first
 // `num_derivs` of the `num_pts` points, the m x m x d algebra on the device: out[num_derivs][d m m] in the reference's layout.
 void grad_variance_on_device(GpDev& gp, const double* pts, int num_pts, int num_derivs, bool cholesky, double* out);

@@ -23,15 +23,13 @@
 
 #include "device_cov.hpp"
 #include "gp.hpp"
+#include "pm_descent.hpp"
 
 namespace moe {
 
 namespace {
 
 constexpr int kPmmPass = 16384;    // candidates per launch of pmm_screen_kernel (moe_hip.h: moe_posterior_mean_members_minimize)
-constexpr int kPmmThreads = 256;   // the row stride of an evaluation
-constexpr int kPmmTraceExtra = 6;  // trace columns behind the point: f0 | halvings | limiter changed | rejected | stopped by norm | state
-constexpr int kPmmHead = 3;        // result columns in front of the point: start index | fell back | value
 
 static_assert(sizeof(CovParams) % sizeof(unsigned int) == 0, "the descent copies a member's covariance into LDS by words");
 
@@ -161,142 +159,38 @@ __global__ __launch_bounds__(256) void pmm_argmin_kernel(int C, const double* __
   }
 }
 
-struct PmmDescent {
-  const int* start_index;  // [E] into the member's candidates
-  const double* cand;      // [.][DP]
-  long member_stride;      // rows between the members' candidate sets (0: shared)
-  const double* alpha0;    // [T]: pre_mult (i + 1)^-gamma
-  const double* bounds;    // [size][2]
-  const double* means;     // [E][C]: the screened means
-  int C, T, R;             // candidates; max_num_steps; max_num_restarts
-  double max_relative_change, tolerance, step_tol;
-  double* out;    // [E][kPmmHead + DP]
-  double* trace;  // [E][R T][size + kPmmTraceExtra] (zeroed) or NULL
+// pmm_descend's evaluator (pm_descent.hpp): member e's posterior mean through pmm_eval
+template <int DP>
+struct PmmMeanEval {
+  const CovParams& cp;
+  const double* kinvy;
+  double mean;
+  const double* X;
+  int n;
+  const DerivList& dX;
+  template <bool GRAD>
+  __device__ __forceinline__ void eval(const double* p, double* red, double* tot) const {
+    pmm_eval<DP, GRAD>(cp, kinvy, mean, X, n, dX, p, red, tot);
+  }
 };
 
-// TensorProductDomain::LimitUpdate (gpp_domain.cpp:64-105) on one coordinate: multistart.hip's limit_update_1d
-__device__ __forceinline__ double pmm_limit_1d(double lo, double hi, double max_relative_change, double x, double desired) {
-#pragma clang fp contract(off)
-  const double dist = fmin(x - lo, hi - x);
-  if (fabs(desired) > max_relative_change * dist) desired = copysign(max_relative_change * dist, desired);
-  const double next = x + desired;
-  if (next < lo) {
-    desired = (x + desired * 0.5 < lo) ? (lo - x) * 0.5 : desired * 0.5;
-  } else if (next > hi) {
-    desired = (x + desired * 0.5 > hi) ? (hi - x) * 0.5 : desired * 0.5;
-  }
-  return desired;
-}
-
-// workgroup e: member e's whole optimisation, posterior_mean_optimize's loop (multistart.hip) decision for decision, on f = -mu_e.
-// The scalar algebra between evaluations is kept free of fused multiply-adds, as the host loop's is.
+// workgroup e: member e's whole optimisation (pm_descent.hpp: pmm_descend) on f = -mu_e
 template <int DP>
 __global__ __launch_bounds__(kPmmThreads) void pmm_descent_kernel(PmmData T, PmmDescent D) {
-#pragma clang fp contract(off)
   __shared__ double red[4 * (1 + DP)], tot[1 + DP], xs[DP], pt[DP], gs[DP], xb[DP];
   // the member's covariance and the observed-derivative list: read per training point by every evaluation, kept out of the scalar
   // registers (held there they spilled, and the spills brought scratch with them)
   __shared__ CovParams cp;
   __shared__ DerivList dX;
-  const int tid = threadIdx.x, e = blockIdx.x, size = T.size;
+  const int tid = threadIdx.x, e = blockIdx.x;
   {
     const unsigned int* src = reinterpret_cast<const unsigned int*>(&T.members[e].cp);
     unsigned int* dst = reinterpret_cast<unsigned int*>(&cp);
     for (int i = tid; i < (int)(sizeof(CovParams) / sizeof(unsigned int)); i += kPmmThreads) dst[i] = src[i];
   }
   if (tid == 0) dX = T.dX;
-  const double* kinvy = T.members[e].kinvy;
-  const double mean = T.members[e].mean;
-  const int start = D.start_index[e];
-  const long tw = size + kPmmTraceExtra;
-  double* trace = D.trace ? D.trace + (long)e * D.R * D.T * tw : nullptr;
-  if (tid < DP) xs[tid] = D.cand[((long)e * D.member_stride + start) * DP + tid];
-  for (int r = 0; r < D.R; ++r) {
-    __syncthreads();
-    if (tid < DP) xb[tid] = xs[tid];
-    for (int i = 0; i < D.T; ++i) {
-      pmm_eval<DP, true>(cp, kinvy, mean, T.X, T.n, dX, xs, red, tot);
-      const double f0 = -tot[0];
-      if (tid < DP) gs[tid] = (tid < size) ? -tot[1 + tid] : 0.0;
-      __syncthreads();
-      double alpha = D.alpha0[i];
-      double n2 = 0.0;
-      for (int k = 0; k < size; ++k) n2 += gs[k] * gs[k];
-      int search = 0;
-      double ftrial = f0;
-      for (; search < 30; ++search) {
-        if (tid < DP) pt[tid] = (tid < size) ? xs[tid] + alpha * gs[tid] : xs[tid];
-        pmm_eval<DP, false>(cp, kinvy, mean, T.X, T.n, dX, pt, red, tot);
-        ftrial = -tot[0];
-        if (ftrial - f0 > 0.5 * alpha * n2) break;
-        alpha *= 0.5;
-      }
-      bool changed = false, nonzero = false;
-      double mine = 0.0, s2 = 0.0;  // this thread's coordinate of the limited step; its squared norm
-      for (int k = 0; k < size; ++k) {
-        const double raw = alpha * gs[k];
-        const double st = pmm_limit_1d(D.bounds[2 * k], D.bounds[2 * k + 1], D.max_relative_change, xs[k], raw);
-        changed = changed || st != raw;
-        nonzero = nonzero || st != 0.0;
-        s2 += st * st;
-        if (k == tid) mine = st;
-      }
-      double* row = trace ? trace + ((long)r * D.T + i) * tw : nullptr;
-      if (row && tid == 0) {
-        row[size] = f0;
-        row[size + 1] = (double)search;
-        row[size + 2] = changed ? 1.0 : 0.0;
-      }
-      if (search == 30 || !nonzero) {
-        if (row && tid < size) row[tid] = xs[tid];
-        if (row && tid == 0) row[size + 5] = 2.0;  // ended without a move
-        break;
-      }
-      double obj2 = ftrial;
-      if (changed) {
-        if (tid < DP) pt[tid] = (tid < size) ? xs[tid] + mine : xs[tid];
-        pmm_eval<DP, false>(cp, kinvy, mean, T.X, T.n, dX, pt, red, tot);
-        obj2 = -tot[0];
-      }
-      if (obj2 <= f0) {
-        if (row && tid < size) row[tid] = xs[tid];
-        if (row && tid == 0) {
-          row[size + 3] = 1.0;
-          row[size + 5] = 3.0;  // rejected
-        }
-        break;
-      }
-      __syncthreads();  // (every thread has read xs)
-      if (tid < size) {
-        xs[tid] += mine;
-        if (row) row[tid] = xs[tid];
-      }
-      const bool stop = sqrt(s2) < D.step_tol;
-      if (row && tid == 0) {
-        row[size + 4] = stop ? 1.0 : 0.0;
-        row[size + 5] = 1.0;  // accepted
-      }
-      if (stop) break;
-    }
-    __syncthreads();
-    double s2 = 0.0;
-    for (int k = 0; k < size; ++k) {
-      const double v = xb[k] - xs[k];
-      s2 += v * v;
-    }
-    if (!(sqrt(s2) > D.tolerance)) break;
-  }
-  // keep or fall back (main.py:191-193), both means through the screening's evaluation
-  pmm_eval<DP, false>(cp, kinvy, mean, T.X, T.n, dX, xs, red, tot);
-  const double mu_end = tot[0], mu_start = D.means[(long)e * D.C + start];
-  const bool fall_back = mu_end > mu_start;
-  double* out = D.out + (long)e * (kPmmHead + DP);
-  if (tid == 0) {
-    out[0] = (double)start;
-    out[1] = fall_back ? 1.0 : 0.0;
-    out[2] = fall_back ? mu_start : mu_end;
-  }
-  if (tid < DP) out[kPmmHead + tid] = fall_back ? D.cand[((long)e * D.member_stride + start) * DP + tid] : xs[tid];
+  const PmmMeanEval<DP> ev{cp, T.members[e].kinvy, T.members[e].mean, T.X, T.n, dX};
+  pmm_descend<DP>(ev, D, e, (long)e * D.member_stride, T.size, red, tot, xs, pt, gs, xb);
 }
 
 template <int DP>
@@ -312,6 +206,11 @@ void launch_dp(const PmmData& T, PmmDescent D, int E, double* dMeans, int* dInde
 }
 
 }  // namespace
+
+void launch_pmm_argmin(int rows, int C, const double* values, int* index, hipStream_t s) {
+  MOE_LAUNCH_NOW(pmm_argmin_kernel, dim3((unsigned)rows), dim3(256), 0, s, C, values, index);
+  MOE_HIP_CHECK(hipGetLastError());
+}
 
 void posterior_mean_members_minimize(const std::vector<GpDev*>& gps, int num_fidelity, const moe_gd_params_t& gd,
                                      const double* domain_bounds, const double* candidates, int C, bool per_member,

@@ -841,6 +841,43 @@ int moe_posterior_mean_members_minimize(const moe_gp_t* const* gps, int num_mcmc
                                         const double* domain_bounds, const double* candidates, int num_candidates, int per_member,
                                         double* best_points, double* best_values, int* start_index, int* fell_back,
                                         double* means_out, double* trace_out, moe_error_t* err);
+/* Posterior function paths by pathwise conditioning (Wilson et al. 2020) on the factor each member holds, and their minimisers: the
+ * purpose of the reference's moe/optimal_learning/python/random_features.py (sample_gp_with_random_features,
+ * global_optimization_of_GP_approximation, sample_from_global_optima), NOT its weight-space posterior: no M x M or n x n system of
+ * the features is formed, and E[f_s(x)] = mu(x) exactly for every number of features.
+ * Member e (no derivative observations; signal variance alpha, lengths l, noise s^2 = noise_variance[0], constant mean m, sampled
+ * points X [n][dim], K = K(X, X) + s^2 I) and its path s:
+ *   om_i = frequencies_i / l (coordinate by coordinate),   g_s(x) = sqrt(2 alpha / M) sum_i w_si cos(om_i . x + phases_i)
+ *   v_s = K^-1 (y - m - g_s(X) - s z_s),                   f_s(x) = m + g_s(x) + sum_j v_sj k(x, X_j)
+ * with M = num_features, S = num_paths, w = weights [num_mcmc][S][M] and z = noise_normals [num_mcmc][S][n] standard normals.
+ * frequencies [M][dim] and phases [M] (uniform on [0, 2 pi)) are shared by every member and path of the call; the caller draws the
+ * frequencies for the members' covariance: standard normals for the squared exponential, standard normals divided by sqrt(u / 5),
+ * u ~ chi^2_5 (one u per feature), for Matern-5/2.  f_s(X_j) = y_j - s z_sj - s^2 v_sj identically.
+ * moe_gp_paths_evaluate: values [num_mcmc][S][num_points] and, with want_grad != 0, grad [num_mcmc][S][num_points][dim] at points
+ * [num_points][dim].
+ * moe_gp_paths_minimize: moe_posterior_mean_members_minimize with the path f_s in the place of the member's mean, for every one of
+ * the num_mcmc S paths: every path screened at the shared candidates [num_candidates][dim] (screened_out [num_mcmc][S][C]),
+ * start_index by numpy.argmin's rule, that call's line search on -f_s decision for decision, its keep-or-fall-back rule.
+ * best_points [num_mcmc][S][dim]; best_values, start_index, fell_back [num_mcmc][S], screened_out and trace_out
+ * ([num_mcmc S][max_num_restarts][max_num_steps][dim + 6], that call's columns) may be NULL.
+ * An evaluation's sums have a fixed order that depends on (M, n) alone: a (path, point) value carries the same bits whatever
+ * num_points, S, num_mcmc and want_grad share the call, and the descent starts from the screened bits.
+ * One copy down, one stream, one wait, one copy back; no handle is modified; scratch is pooled in the first member.
+ * Errors, in this order, everything that needs no handle before a handle or the device is touched: gps NULL -> MOE_ERR_RUNTIME;
+ * num_features outside 1 .. 4096, num_paths outside 1 .. 1024, num_mcmc outside 1 .. 1024, num_mcmc num_paths > 65 535 ->
+ * MOE_ERR_BOUNDS (payload: the value, the limits); a NULL table, points or output -> MOE_ERR_RUNTIME; num_points / num_candidates <
+ * 1, and for the minimiser max_num_steps < 1, max_num_restarts < 1, domain_type other than MOE_DOMAIN_TENSOR_PRODUCT ->
+ * MOE_ERR_BOUNDS; a NULL handle -> MOE_ERR_RUNTIME; members of different dim, device, sampled points or cov_type, then a member with
+ * derivative observations -> MOE_ERR_INVALID_VALUE (payload as in moe_ei_analytic_mcmc: the two values, the member).  There are no
+ * fidelity coordinates: every coordinate is free. */
+int moe_gp_paths_evaluate(const moe_gp_t* const* gps, int num_mcmc, const double* frequencies, const double* phases, int num_features,
+                          const double* weights, const double* noise_normals, int num_paths, const double* points, int num_points,
+                          int want_grad, double* values, double* grad, moe_error_t* err);
+int moe_gp_paths_minimize(const moe_gp_t* const* gps, int num_mcmc, const double* frequencies, const double* phases, int num_features,
+                          const double* weights, const double* noise_normals, int num_paths, const moe_gd_params_t* gd,
+                          const double* domain_bounds, const double* candidates, int num_candidates, double* best_points,
+                          double* best_values, int* start_index, int* fell_back, double* screened_out, double* trace_out,
+                          moe_error_t* err);
 /* compute_expected_improvement_mcmc / compute_grad_expected_improvement_mcmc / evaluate_EI_mcmc_at_point_list
  * (gpp_python_expected_improvement_mcmc.cpp:42-108 -> ExpectedImprovementMCMCEvaluator,
  * gpp_expected_improvement_mcmc_optimization.cpp:48-88); analytic != 0 takes the 1,0-EI evaluator (:136-176; needs
