@@ -869,42 +869,44 @@ def _kg_discrete_members(gps, discrete_all, best_so_far_all, num_fidelity):
     return arr, E, d, keep, disc, counts, best
 
 
-def kg_discrete_ensemble(gps, discrete_all, points, best_so_far_all, num_fidelity=0, want_grad=True, points_being_sampled=None):
-    """moe_kg_discrete_mcmc: what kg_discrete_mcmc returns, bit for bit, in one device call for the whole ensemble (one upload, one
-    stream, one wait; every kernel launched once for all members where their launches line up).  gps: a DeviceGPMCMC, a list of
-    DeviceGP (they need not share their sampled points) or one DeviceGP.  Returns kg [C], with want_grad (kg, grad [C][dim]).
-    SingularMatrixException(e, i): member e, candidate i.
-    points_being_sampled [p][dim] (None or empty: the symbol and bits of before): moe_kg_discrete_mcmc_pending -- every member's
-    posterior covariance conditioned on the pending points, its mean left alone; SingularMatrixException(e, j) for pending point j."""
-    arr, E, d, keep, disc, counts, best = _kg_discrete_members(gps, discrete_all, best_so_far_all, num_fidelity)
+def _acq1_pending(points_being_sampled, d):
+    """(array kept alive, ctypes pointer or None, p) of the pending points [p][dim] of an ensemble one-point acquisition"""
+    p = _num_pending(points_being_sampled, d)
+    pend, pendp = _d(points_being_sampled) if p else (None, None)
+    return pend, pendp, p
+
+
+def _acq1_evaluate(fn, pre, post, d, points, want_grad, points_being_sampled, extra_shape=None, want_extra=False, fn_without=None):
+    """The evaluate-at-points shape of the ensemble one-point acquisitions: fn(*pre, *post, pending, p, points, C, want_grad, value,
+    grad[, extra], err).  pre / post: the objective's own arguments, those before and behind (gd_params, bounds) in the other two
+    shapes.  extra_shape: the symbol has a trailing per-member output of that shape with [C] appended, filled with want_extra and
+    NULL without.  fn_without: the symbol without the pending arguments, called when there are no pending points.  Returns value
+    [C], with want_grad (value, grad [C][dim]), with want_extra the extra output last."""
     pts, pp = _d(points)
     C_ = pts.reshape(-1, d).shape[0]
-    kg = np.zeros(max(C_, 1))
+    value = np.zeros(max(C_, 1))
     grad = np.zeros((max(C_, 1), d)) if want_grad else None
+    extra = np.zeros(tuple(extra_shape) + (max(C_, 1),)) if want_extra else None
+    pend, pendp, p = _acq1_pending(points_being_sampled, d)
     err = _lib.MoeError()
-    p = _num_pending(points_being_sampled, d)
-    if p:
-        pend, pendp = _d(points_being_sampled)
-        _check(_lib.load().moe_kg_discrete_mcmc_pending(arr, E, int(num_fidelity), disc.ctypes.data_as(dp), counts.ctypes.data_as(ip),
-                                                        best.ctypes.data_as(dp), pendp, p, pp, C_, 1 if want_grad else 0,
-                                                        kg.ctypes.data_as(dp), grad.ctypes.data_as(dp) if want_grad else None,
-                                                        C.byref(err)), err)
-        return (kg, grad) if want_grad else kg
-    _check(_lib.load().moe_kg_discrete_mcmc(arr, E, int(num_fidelity), disc.ctypes.data_as(dp), counts.ctypes.data_as(ip),
-                                            best.ctypes.data_as(dp), pp, C_, 1 if want_grad else 0, kg.ctypes.data_as(dp),
-                                            grad.ctypes.data_as(dp) if want_grad else None, C.byref(err)), err)
-    return (kg, grad) if want_grad else kg
+    if fn_without is not None and not p:
+        fn, pending = fn_without, ()
+    else:
+        pending = (pendp, p)
+    args = tuple(pre) + tuple(post) + pending + (pp, C_, 1 if want_grad else 0, value.ctypes.data_as(dp),
+                                                 grad.ctypes.data_as(dp) if want_grad else None)
+    if extra_shape is not None:
+        args += (extra.ctypes.data_as(dp) if want_extra else None,)
+    _check(fn(*(args + (C.byref(err),))), err)
+    out = (value, grad) if want_grad else (value,)
+    if extra is not None:
+        out = out + (extra,)
+    return out if len(out) > 1 else out[0]
 
 
-def kg_discrete_multistart(gps, gd_params, bounds, discrete_all, best_so_far_all, starts, num_fidelity=0, gradient_ascent=True,
-                           want_path=False, points_being_sampled=None):
-    """moe_kg_discrete_mcmc_multistart: one suggestion by the ensemble-averaged discretised knowledge gradient -- the value at
-    every start [S][dim], the 20 best kept, restarted gradient ascent on all of them on the device, the value at every end point,
-    the best one returned.  Returns a dict: point [dim], value, found, start_values [S], and with gradient_ascent kept_index [K],
-    end_points [K][dim], end_values [K], steps_taken [K] (None without), with want_path path [K][restarts steps + 1][dim].
-    points_being_sampled [p][dim] (None or empty: the symbol and bits of before): moe_kg_discrete_mcmc_multistart_pending, the same
-    ascent on the knowledge gradient conditioned on the pending points."""
-    arr, E, d, keep, disc, counts, best = _kg_discrete_members(gps, discrete_all, best_so_far_all, num_fidelity)
+def _acq1_multistart(fn, pre, post, d, gd_params, bounds, starts, gradient_ascent, want_path, points_being_sampled, fn_without=None):
+    """The multistart shape: fn(*pre, gd_params, bounds, *post, pending, p, starts, S, gradient_ascent, the nine outputs, err);
+    fn_without as in _acq1_evaluate.  Returns the dict of kg_discrete_multistart."""
     g = DeviceGP._gd(gd_params)
     bounds, bp = _d(bounds)
     starts, sp = _d(starts)
@@ -918,23 +920,69 @@ def kg_discrete_multistart(gps, gd_params, bounds, discrete_all, best_so_far_all
     steps = np.zeros(K, dtype=np.int32)
     path = np.zeros((K, rows, d)) if (want_path and gradient_ascent) else None
     value, found = C.c_double(0.0), C.c_int(0)
+    pend, pendp, p = _acq1_pending(points_being_sampled, d)
     err = _lib.MoeError()
-    tail = (sp, S, 1 if gradient_ascent else 0, point.ctypes.data_as(dp), C.byref(value), C.byref(found), start_values.ctypes.data_as(dp),
-            kept.ctypes.data_as(ip), ends.ctypes.data_as(dp), end_values.ctypes.data_as(dp),
-            path.ctypes.data_as(dp) if path is not None else None, steps.ctypes.data_as(ip), C.byref(err))
-    head = (arr, E, int(num_fidelity), C.byref(g), bp, disc.ctypes.data_as(dp), counts.ctypes.data_as(ip), best.ctypes.data_as(dp))
-    p = _num_pending(points_being_sampled, d)
-    if p:
-        pend, pendp = _d(points_being_sampled)
-        _check(_lib.load().moe_kg_discrete_mcmc_multistart_pending(*(head + (pendp, p) + tail)), err)
+    if fn_without is not None and not p:
+        fn, pending = fn_without, ()
     else:
-        _check(_lib.load().moe_kg_discrete_mcmc_multistart(*(head + tail)), err)
+        pending = (pendp, p)
+    _check(fn(*(tuple(pre) + (C.byref(g), bp) + tuple(post) + pending + (
+        sp, S, 1 if gradient_ascent else 0, point.ctypes.data_as(dp), C.byref(value), C.byref(found), start_values.ctypes.data_as(dp),
+        kept.ctypes.data_as(ip), ends.ctypes.data_as(dp), end_values.ctypes.data_as(dp),
+        path.ctypes.data_as(dp) if path is not None else None, steps.ctypes.data_as(ip), C.byref(err)))), err)
     out = {"point": point, "value": value.value, "found": bool(found.value), "start_values": start_values,
            "kept_index": kept if gradient_ascent else None, "end_points": ends if gradient_ascent else None,
            "end_values": end_values if gradient_ascent else None, "steps_taken": steps if gradient_ascent else None}
     if want_path:
         out["path"] = path
     return out
+
+
+def _acq1_suggest(fn, pre, post, d, gd_params, bounds, starts, num_to_sample, gradient_ascent, points_being_sampled):
+    """The greedy-batch shape: fn(*pre, gd_params, bounds, *post, pending, p, starts, S, gradient_ascent, q, points, values, found,
+    err).  Returns a dict: points [q][dim], values [q], found [q]."""
+    g = DeviceGP._gd(gd_params)
+    bounds, bp = _d(bounds)
+    starts, sp = _d(starts)
+    S = starts.reshape(-1, d).shape[0]
+    q = int(num_to_sample)
+    pend, pendp, p = _acq1_pending(points_being_sampled, d)
+    points, values = np.zeros((max(q, 1), d)), np.zeros(max(q, 1))
+    found = np.zeros(max(q, 1), dtype=np.int32)
+    err = _lib.MoeError()
+    _check(fn(*(tuple(pre) + (C.byref(g), bp) + tuple(post) + (
+        pendp, p, sp, S, 1 if gradient_ascent else 0, q, points.ctypes.data_as(dp), values.ctypes.data_as(dp), found.ctypes.data_as(ip),
+        C.byref(err)))), err)
+    return {"points": points, "values": values, "found": found.astype(bool)}
+
+
+def kg_discrete_ensemble(gps, discrete_all, points, best_so_far_all, num_fidelity=0, want_grad=True, points_being_sampled=None):
+    """moe_kg_discrete_mcmc: what kg_discrete_mcmc returns, bit for bit, in one device call for the whole ensemble (one upload, one
+    stream, one wait; every kernel launched once for all members where their launches line up).  gps: a DeviceGPMCMC, a list of
+    DeviceGP (they need not share their sampled points) or one DeviceGP.  Returns kg [C], with want_grad (kg, grad [C][dim]).
+    SingularMatrixException(e, i): member e, candidate i.
+    points_being_sampled [p][dim] (None or empty: the symbol and bits of before): moe_kg_discrete_mcmc_pending -- every member's
+    posterior covariance conditioned on the pending points, its mean left alone; SingularMatrixException(e, j) for pending point j."""
+    arr, E, d, keep, disc, counts, best = _kg_discrete_members(gps, discrete_all, best_so_far_all, num_fidelity)
+    pre, post = (arr, E, int(num_fidelity)), (disc.ctypes.data_as(dp), counts.ctypes.data_as(ip), best.ctypes.data_as(dp))
+    lib = _lib.load()
+    return _acq1_evaluate(lib.moe_kg_discrete_mcmc_pending, pre, post, d, points, want_grad, points_being_sampled,
+                          fn_without=lib.moe_kg_discrete_mcmc)
+
+
+def kg_discrete_multistart(gps, gd_params, bounds, discrete_all, best_so_far_all, starts, num_fidelity=0, gradient_ascent=True,
+                           want_path=False, points_being_sampled=None):
+    """moe_kg_discrete_mcmc_multistart: one suggestion by the ensemble-averaged discretised knowledge gradient -- the value at
+    every start [S][dim], the 20 best kept, restarted gradient ascent on all of them on the device, the value at every end point,
+    the best one returned.  Returns a dict: point [dim], value, found, start_values [S], and with gradient_ascent kept_index [K],
+    end_points [K][dim], end_values [K], steps_taken [K] (None without), with want_path path [K][restarts steps + 1][dim].
+    points_being_sampled [p][dim] (None or empty: the symbol and bits of before): moe_kg_discrete_mcmc_multistart_pending, the same
+    ascent on the knowledge gradient conditioned on the pending points."""
+    arr, E, d, keep, disc, counts, best = _kg_discrete_members(gps, discrete_all, best_so_far_all, num_fidelity)
+    pre, post = (arr, E, int(num_fidelity)), (disc.ctypes.data_as(dp), counts.ctypes.data_as(ip), best.ctypes.data_as(dp))
+    lib = _lib.load()
+    return _acq1_multistart(lib.moe_kg_discrete_mcmc_multistart_pending, pre, post, d, gd_params, bounds, starts, gradient_ascent,
+                            want_path, points_being_sampled, fn_without=lib.moe_kg_discrete_mcmc_multistart)
 
 
 def kg_discrete_suggest(gps, gd_params, bounds, discrete_all, best_so_far_all, starts, num_to_sample, num_fidelity=0,
@@ -944,21 +992,9 @@ def kg_discrete_suggest(gps, gd_params, bounds, discrete_all, best_so_far_all, s
     followed by the points of the rounds before, bit for bit, in one device call: the set phase runs once and a round appends one
     row to every member's extension.  p + num_to_sample - 1 <= 64.  Returns a dict: points [q][dim], values [q], found [q]."""
     arr, E, d, keep, disc, counts, best = _kg_discrete_members(gps, discrete_all, best_so_far_all, num_fidelity)
-    g = DeviceGP._gd(gd_params)
-    bounds, bp = _d(bounds)
-    starts, sp = _d(starts)
-    S = starts.reshape(-1, d).shape[0]
-    q = int(num_to_sample)
-    p = _num_pending(points_being_sampled, d)
-    pend, pendp = _d(points_being_sampled) if p else (None, None)
-    points, values = np.zeros((max(q, 1), d)), np.zeros(max(q, 1))
-    found = np.zeros(max(q, 1), dtype=np.int32)
-    err = _lib.MoeError()
-    _check(_lib.load().moe_kg_discrete_mcmc_suggest(
-        arr, E, int(num_fidelity), C.byref(g), bp, disc.ctypes.data_as(dp), counts.ctypes.data_as(ip), best.ctypes.data_as(dp), pendp, p,
-        sp, S, 1 if gradient_ascent else 0, q, points.ctypes.data_as(dp), values.ctypes.data_as(dp), found.ctypes.data_as(ip),
-        C.byref(err)), err)
-    return {"points": points, "values": values, "found": found.astype(bool)}
+    pre, post = (arr, E, int(num_fidelity)), (disc.ctypes.data_as(dp), counts.ctypes.data_as(ip), best.ctypes.data_as(dp))
+    return _acq1_suggest(_lib.load().moe_kg_discrete_mcmc_suggest, pre, post, d, gd_params, bounds, starts, num_to_sample,
+                         gradient_ascent, points_being_sampled)
 
 
 def _ei_analytic_members(gps, best_so_far):
@@ -982,16 +1018,8 @@ def ei_analytic_ensemble(gps, points, best_so_far, points_being_sampled=None, wa
     1 + g rows with noise_variance[a] on row a, and p (1 + g) <= 64 (BoundsException(p, 0, 64 // (1 + g))).  Returns ei [C], with
     want_grad (ei, grad [C][dim]).  SingularMatrixException(e, j): member e, pending point j; a candidate never raises."""
     arr, E, d, keep, best = _ei_analytic_members(gps, best_so_far)
-    pts, pp = _d(points)
-    C_ = pts.reshape(-1, d).shape[0]
-    ei = np.zeros(max(C_, 1))
-    grad = np.zeros((max(C_, 1), d)) if want_grad else None
-    p = _num_pending(points_being_sampled, d)
-    pend, pendp = _d(points_being_sampled) if p else (None, None)
-    err = _lib.MoeError()
-    _check(_lib.load().moe_ei_analytic_mcmc(arr, E, best.ctypes.data_as(dp), pendp, p, pp, C_, 1 if want_grad else 0,
-                                            ei.ctypes.data_as(dp), grad.ctypes.data_as(dp) if want_grad else None, C.byref(err)), err)
-    return (ei, grad) if want_grad else ei
+    pre, post = (arr, E), (best.ctypes.data_as(dp),)
+    return _acq1_evaluate(_lib.load().moe_ei_analytic_mcmc, pre, post, d, points, want_grad, points_being_sampled)
 
 
 def ei_analytic_multistart(gps, gd_params, bounds, best_so_far, starts, gradient_ascent=True, want_path=False,
@@ -1002,33 +1030,9 @@ def ei_analytic_multistart(gps, gd_params, bounds, best_so_far, starts, gradient
     kept_index [K], end_points [K][dim], end_values [K], steps_taken [K] (None without), with want_path path [K][restarts steps +
     1][dim].  Members with derivative observations as in ei_analytic_ensemble."""
     arr, E, d, keep, best = _ei_analytic_members(gps, best_so_far)
-    g = DeviceGP._gd(gd_params)
-    bounds, bp = _d(bounds)
-    starts, sp = _d(starts)
-    S = starts.reshape(-1, d).shape[0]
-    K = max(min(S, 20), 1)
-    rows = max(g.max_num_restarts, 0) * max(g.max_num_steps, 0) + 1
-    point = np.zeros(d)
-    start_values = np.zeros(max(S, 1))
-    kept = np.zeros(K, dtype=np.int32)
-    ends, end_values = np.zeros((K, d)), np.zeros(K)
-    steps = np.zeros(K, dtype=np.int32)
-    path = np.zeros((K, rows, d)) if (want_path and gradient_ascent) else None
-    value, found = C.c_double(0.0), C.c_int(0)
-    p = _num_pending(points_being_sampled, d)
-    pend, pendp = _d(points_being_sampled) if p else (None, None)
-    err = _lib.MoeError()
-    _check(_lib.load().moe_ei_analytic_mcmc_multistart(
-        arr, E, C.byref(g), bp, best.ctypes.data_as(dp), pendp, p, sp, S, 1 if gradient_ascent else 0, point.ctypes.data_as(dp),
-        C.byref(value), C.byref(found), start_values.ctypes.data_as(dp), kept.ctypes.data_as(ip), ends.ctypes.data_as(dp),
-        end_values.ctypes.data_as(dp), path.ctypes.data_as(dp) if path is not None else None, steps.ctypes.data_as(ip), C.byref(err)),
-        err)
-    out = {"point": point, "value": value.value, "found": bool(found.value), "start_values": start_values,
-           "kept_index": kept if gradient_ascent else None, "end_points": ends if gradient_ascent else None,
-           "end_values": end_values if gradient_ascent else None, "steps_taken": steps if gradient_ascent else None}
-    if want_path:
-        out["path"] = path
-    return out
+    pre, post = (arr, E), (best.ctypes.data_as(dp),)
+    return _acq1_multistart(_lib.load().moe_ei_analytic_mcmc_multistart, pre, post, d, gd_params, bounds, starts, gradient_ascent, want_path,
+                            points_being_sampled)
 
 
 def ei_analytic_suggest(gps, gd_params, bounds, best_so_far, starts, num_to_sample, gradient_ascent=True, points_being_sampled=None):
@@ -1037,20 +1041,9 @@ def ei_analytic_suggest(gps, gd_params, bounds, best_so_far, starts, num_to_samp
     followed by the points of the rounds before, bit for bit, in one device call.  p + num_to_sample - 1 <= 64; with g observed
     derivatives per point (p + num_to_sample - 1) (1 + g) <= 64.  Returns a dict: points [q][dim], values [q], found [q]."""
     arr, E, d, keep, best = _ei_analytic_members(gps, best_so_far)
-    g = DeviceGP._gd(gd_params)
-    bounds, bp = _d(bounds)
-    starts, sp = _d(starts)
-    S = starts.reshape(-1, d).shape[0]
-    q = int(num_to_sample)
-    p = _num_pending(points_being_sampled, d)
-    pend, pendp = _d(points_being_sampled) if p else (None, None)
-    points, values = np.zeros((max(q, 1), d)), np.zeros(max(q, 1))
-    found = np.zeros(max(q, 1), dtype=np.int32)
-    err = _lib.MoeError()
-    _check(_lib.load().moe_ei_analytic_mcmc_suggest(
-        arr, E, C.byref(g), bp, best.ctypes.data_as(dp), pendp, p, sp, S, 1 if gradient_ascent else 0, q, points.ctypes.data_as(dp),
-        values.ctypes.data_as(dp), found.ctypes.data_as(ip), C.byref(err)), err)
-    return {"points": points, "values": values, "found": found.astype(bool)}
+    pre, post = (arr, E), (best.ctypes.data_as(dp),)
+    return _acq1_suggest(_lib.load().moe_ei_analytic_mcmc_suggest, pre, post, d, gd_params, bounds, starts, num_to_sample, gradient_ascent,
+                         points_being_sampled)
 
 
 def _ei_constrained_members(gps, constraint_gps, thresholds, best_so_far):
@@ -1084,22 +1077,9 @@ def ei_constrained_ensemble(gps, constraint_gps, thresholds, points, best_so_far
     want_factors additionally factors [E][1 + K][C] (the improvement factor, then the K feasibility factors) as the last item.
     SingularMatrixException(e (1 + K) + role, j): the GP, counted flat, and the pending point; a candidate never raises."""
     arr, E, d, keep, carr, K, tau, best = _ei_constrained_members(gps, constraint_gps, thresholds, best_so_far)
-    pts, pp = _d(points)
-    C_ = pts.reshape(-1, d).shape[0]
-    value = np.zeros(max(C_, 1))
-    grad = np.zeros((max(C_, 1), d)) if want_grad else None
-    factors = np.zeros((E, 1 + K, max(C_, 1))) if want_factors else None
-    p = _num_pending(points_being_sampled, d)
-    pend, pendp = _d(points_being_sampled) if p else (None, None)
-    err = _lib.MoeError()
-    _check(_lib.load().moe_ei_constrained_mcmc(
-        arr, E, carr, K, tau.ctypes.data_as(dp) if K else None, best.ctypes.data_as(dp), pendp, p, pp, C_, 1 if want_grad else 0,
-        value.ctypes.data_as(dp), grad.ctypes.data_as(dp) if want_grad else None,
-        factors.ctypes.data_as(dp) if want_factors else None, C.byref(err)), err)
-    out = (value, grad) if want_grad else (value,)
-    if want_factors:
-        out = out + (factors,)
-    return out if len(out) > 1 else out[0]
+    pre, post = (arr, E, carr, K, tau.ctypes.data_as(dp) if K else None), (best.ctypes.data_as(dp),)
+    return _acq1_evaluate(_lib.load().moe_ei_constrained_mcmc, pre, post, d, points, want_grad, points_being_sampled,
+                          extra_shape=(E, 1 + K), want_extra=want_factors)
 
 
 def ei_constrained_multistart(gps, constraint_gps, thresholds, gd_params, bounds, best_so_far, starts, gradient_ascent=True,
@@ -1107,33 +1087,9 @@ def ei_constrained_multistart(gps, constraint_gps, thresholds, gd_params, bounds
     """moe_ei_constrained_mcmc_multistart: one suggestion by the ensemble-averaged constrained expected improvement --
     ei_analytic_multistart's screening, 20 kept starts, restarted ascent on the device and end-point selection, and its dict."""
     arr, E, d, keep, carr, K, tau, best = _ei_constrained_members(gps, constraint_gps, thresholds, best_so_far)
-    g = DeviceGP._gd(gd_params)
-    bounds, bp = _d(bounds)
-    starts, sp = _d(starts)
-    S = starts.reshape(-1, d).shape[0]
-    Kk = max(min(S, 20), 1)
-    rows = max(g.max_num_restarts, 0) * max(g.max_num_steps, 0) + 1
-    point = np.zeros(d)
-    start_values = np.zeros(max(S, 1))
-    kept = np.zeros(Kk, dtype=np.int32)
-    ends, end_values = np.zeros((Kk, d)), np.zeros(Kk)
-    steps = np.zeros(Kk, dtype=np.int32)
-    path = np.zeros((Kk, rows, d)) if (want_path and gradient_ascent) else None
-    value, found = C.c_double(0.0), C.c_int(0)
-    p = _num_pending(points_being_sampled, d)
-    pend, pendp = _d(points_being_sampled) if p else (None, None)
-    err = _lib.MoeError()
-    _check(_lib.load().moe_ei_constrained_mcmc_multistart(
-        arr, E, carr, K, tau.ctypes.data_as(dp) if K else None, C.byref(g), bp, best.ctypes.data_as(dp), pendp, p, sp, S,
-        1 if gradient_ascent else 0, point.ctypes.data_as(dp), C.byref(value), C.byref(found), start_values.ctypes.data_as(dp),
-        kept.ctypes.data_as(ip), ends.ctypes.data_as(dp), end_values.ctypes.data_as(dp),
-        path.ctypes.data_as(dp) if path is not None else None, steps.ctypes.data_as(ip), C.byref(err)), err)
-    out = {"point": point, "value": value.value, "found": bool(found.value), "start_values": start_values,
-           "kept_index": kept if gradient_ascent else None, "end_points": ends if gradient_ascent else None,
-           "end_values": end_values if gradient_ascent else None, "steps_taken": steps if gradient_ascent else None}
-    if want_path:
-        out["path"] = path
-    return out
+    pre, post = (arr, E, carr, K, tau.ctypes.data_as(dp) if K else None), (best.ctypes.data_as(dp),)
+    return _acq1_multistart(_lib.load().moe_ei_constrained_mcmc_multistart, pre, post, d, gd_params, bounds, starts, gradient_ascent, want_path,
+                            points_being_sampled)
 
 
 def ei_constrained_suggest(gps, constraint_gps, thresholds, gd_params, bounds, best_so_far, starts, num_to_sample,
@@ -1143,21 +1099,9 @@ def ei_constrained_suggest(gps, constraint_gps, thresholds, gd_params, bounds, b
     None) followed by the points of the rounds before, bit for bit, in one device call.  (p + num_to_sample - 1) (1 + g) <= 64.
     Returns a dict: points [q][dim], values [q], found [q]."""
     arr, E, d, keep, carr, K, tau, best = _ei_constrained_members(gps, constraint_gps, thresholds, best_so_far)
-    g = DeviceGP._gd(gd_params)
-    bounds, bp = _d(bounds)
-    starts, sp = _d(starts)
-    S = starts.reshape(-1, d).shape[0]
-    q = int(num_to_sample)
-    p = _num_pending(points_being_sampled, d)
-    pend, pendp = _d(points_being_sampled) if p else (None, None)
-    points, values = np.zeros((max(q, 1), d)), np.zeros(max(q, 1))
-    found = np.zeros(max(q, 1), dtype=np.int32)
-    err = _lib.MoeError()
-    _check(_lib.load().moe_ei_constrained_mcmc_suggest(
-        arr, E, carr, K, tau.ctypes.data_as(dp) if K else None, C.byref(g), bp, best.ctypes.data_as(dp), pendp, p, sp, S,
-        1 if gradient_ascent else 0, q, points.ctypes.data_as(dp), values.ctypes.data_as(dp), found.ctypes.data_as(ip), C.byref(err)),
-        err)
-    return {"points": points, "values": values, "found": found.astype(bool)}
+    pre, post = (arr, E, carr, K, tau.ctypes.data_as(dp) if K else None), (best.ctypes.data_as(dp),)
+    return _acq1_suggest(_lib.load().moe_ei_constrained_mcmc_suggest, pre, post, d, gd_params, bounds, starts, num_to_sample, gradient_ascent,
+                         points_being_sampled)
 
 
 def _ehvi_members(gps, gps2, reference_point, front):
@@ -1189,22 +1133,9 @@ def ehvi_ensemble(gps, gps2, reference_point, front, points, points_being_sample
     Returns value [C], with want_grad (value, grad [C][dim]), and with want_member_values additionally the members' values [E][C] as
     the last item.  SingularMatrixException(2 e + objective - 1, j): the GP, counted flat, and the pending point."""
     arr, arr2, E, d, keep, ref, fr, F = _ehvi_members(gps, gps2, reference_point, front)
-    pts, pp = _d(points)
-    C_ = pts.reshape(-1, d).shape[0]
-    value = np.zeros(max(C_, 1))
-    grad = np.zeros((max(C_, 1), d)) if want_grad else None
-    members = np.zeros((E, max(C_, 1))) if want_member_values else None
-    p = _num_pending(points_being_sampled, d)
-    pend, pendp = _d(points_being_sampled) if p else (None, None)
-    err = _lib.MoeError()
-    _check(_lib.load().moe_ehvi_mcmc(
-        arr, arr2, E, ref.ctypes.data_as(dp), fr.ctypes.data_as(dp) if F else None, F, pendp, p, pp, C_, 1 if want_grad else 0,
-        value.ctypes.data_as(dp), grad.ctypes.data_as(dp) if want_grad else None,
-        members.ctypes.data_as(dp) if want_member_values else None, C.byref(err)), err)
-    out = (value, grad) if want_grad else (value,)
-    if want_member_values:
-        out = out + (members,)
-    return out if len(out) > 1 else out[0]
+    pre, post = (arr, arr2, E, ref.ctypes.data_as(dp), fr.ctypes.data_as(dp) if F else None, F), ()
+    return _acq1_evaluate(_lib.load().moe_ehvi_mcmc, pre, post, d, points, want_grad, points_being_sampled,
+                          extra_shape=(E,), want_extra=want_member_values)
 
 
 def ehvi_multistart(gps, gps2, reference_point, front, gd_params, bounds, starts, gradient_ascent=True, want_path=False,
@@ -1212,33 +1143,9 @@ def ehvi_multistart(gps, gps2, reference_point, front, gd_params, bounds, starts
     """moe_ehvi_mcmc_multistart: one suggestion by the ensemble-averaged expected hypervolume improvement -- ei_analytic_multistart's
     screening, 20 kept starts, restarted ascent on the device and end-point selection, and its dict."""
     arr, arr2, E, d, keep, ref, fr, F = _ehvi_members(gps, gps2, reference_point, front)
-    g = DeviceGP._gd(gd_params)
-    bounds, bp = _d(bounds)
-    starts, sp = _d(starts)
-    S = starts.reshape(-1, d).shape[0]
-    Kk = max(min(S, 20), 1)
-    rows = max(g.max_num_restarts, 0) * max(g.max_num_steps, 0) + 1
-    point = np.zeros(d)
-    start_values = np.zeros(max(S, 1))
-    kept = np.zeros(Kk, dtype=np.int32)
-    ends, end_values = np.zeros((Kk, d)), np.zeros(Kk)
-    steps = np.zeros(Kk, dtype=np.int32)
-    path = np.zeros((Kk, rows, d)) if (want_path and gradient_ascent) else None
-    value, found = C.c_double(0.0), C.c_int(0)
-    p = _num_pending(points_being_sampled, d)
-    pend, pendp = _d(points_being_sampled) if p else (None, None)
-    err = _lib.MoeError()
-    _check(_lib.load().moe_ehvi_mcmc_multistart(
-        arr, arr2, E, ref.ctypes.data_as(dp), fr.ctypes.data_as(dp) if F else None, F, C.byref(g), bp, pendp, p, sp, S,
-        1 if gradient_ascent else 0, point.ctypes.data_as(dp), C.byref(value), C.byref(found), start_values.ctypes.data_as(dp),
-        kept.ctypes.data_as(ip), ends.ctypes.data_as(dp), end_values.ctypes.data_as(dp),
-        path.ctypes.data_as(dp) if path is not None else None, steps.ctypes.data_as(ip), C.byref(err)), err)
-    out = {"point": point, "value": value.value, "found": bool(found.value), "start_values": start_values,
-           "kept_index": kept if gradient_ascent else None, "end_points": ends if gradient_ascent else None,
-           "end_values": end_values if gradient_ascent else None, "steps_taken": steps if gradient_ascent else None}
-    if want_path:
-        out["path"] = path
-    return out
+    pre, post = (arr, arr2, E, ref.ctypes.data_as(dp), fr.ctypes.data_as(dp) if F else None, F), ()
+    return _acq1_multistart(_lib.load().moe_ehvi_mcmc_multistart, pre, post, d, gd_params, bounds, starts, gradient_ascent, want_path,
+                            points_being_sampled)
 
 
 def ehvi_suggest(gps, gps2, reference_point, front, gd_params, bounds, starts, num_to_sample, gradient_ascent=True,
@@ -1248,21 +1155,9 @@ def ehvi_suggest(gps, gps2, reference_point, front, gd_params, bounds, starts, n
     the points of the rounds before, bit for bit, in one device call.  p + num_to_sample - 1 <= 64.  Returns a dict: points
     [q][dim], values [q], found [q]."""
     arr, arr2, E, d, keep, ref, fr, F = _ehvi_members(gps, gps2, reference_point, front)
-    g = DeviceGP._gd(gd_params)
-    bounds, bp = _d(bounds)
-    starts, sp = _d(starts)
-    S = starts.reshape(-1, d).shape[0]
-    q = int(num_to_sample)
-    p = _num_pending(points_being_sampled, d)
-    pend, pendp = _d(points_being_sampled) if p else (None, None)
-    points, values = np.zeros((max(q, 1), d)), np.zeros(max(q, 1))
-    found = np.zeros(max(q, 1), dtype=np.int32)
-    err = _lib.MoeError()
-    _check(_lib.load().moe_ehvi_mcmc_suggest(
-        arr, arr2, E, ref.ctypes.data_as(dp), fr.ctypes.data_as(dp) if F else None, F, C.byref(g), bp, pendp, p, sp, S,
-        1 if gradient_ascent else 0, q, points.ctypes.data_as(dp), values.ctypes.data_as(dp), found.ctypes.data_as(ip), C.byref(err)),
-        err)
-    return {"points": points, "values": values, "found": found.astype(bool)}
+    pre, post = (arr, arr2, E, ref.ctypes.data_as(dp), fr.ctypes.data_as(dp) if F else None, F), ()
+    return _acq1_suggest(_lib.load().moe_ehvi_mcmc_suggest, pre, post, d, gd_params, bounds, starts, num_to_sample, gradient_ascent,
+                         points_being_sampled)
 
 
 def _gibbon_members(gps, min_values):
@@ -1287,49 +1182,17 @@ def gibbon_ensemble(gps, points, min_values, points_being_sampled=None, want_gra
     limit as in ei_analytic_ensemble.  Returns value [C], with want_grad (value, grad [C][dim]).  SingularMatrixException(e, j):
     member e, pending point j; a candidate never raises."""
     arr, E, d, keep, mins, K = _gibbon_members(gps, min_values)
-    pts, pp = _d(points)
-    C_ = pts.reshape(-1, d).shape[0]
-    value = np.zeros(max(C_, 1))
-    grad = np.zeros((max(C_, 1), d)) if want_grad else None
-    p = _num_pending(points_being_sampled, d)
-    pend, pendp = _d(points_being_sampled) if p else (None, None)
-    err = _lib.MoeError()
-    _check(_lib.load().moe_gibbon_mcmc(arr, E, mins.ctypes.data_as(dp), K, pendp, p, pp, C_, 1 if want_grad else 0,
-                                       value.ctypes.data_as(dp), grad.ctypes.data_as(dp) if want_grad else None, C.byref(err)), err)
-    return (value, grad) if want_grad else value
+    pre, post = (arr, E), (mins.ctypes.data_as(dp), K)
+    return _acq1_evaluate(_lib.load().moe_gibbon_mcmc, pre, post, d, points, want_grad, points_being_sampled)
 
 
 def gibbon_multistart(gps, gd_params, bounds, min_values, starts, gradient_ascent=True, want_path=False, points_being_sampled=None):
     """moe_gibbon_mcmc_multistart: one suggestion by the ensemble-averaged min-value entropy acquisition -- ei_analytic_multistart's
     screening, kept starts, restarted ascent on the device and end-point selection, and its dict."""
-    arr, E, d, keep, mins, Kmin = _gibbon_members(gps, min_values)
-    g = DeviceGP._gd(gd_params)
-    bounds, bp = _d(bounds)
-    starts, sp = _d(starts)
-    S = starts.reshape(-1, d).shape[0]
-    K = max(min(S, 20), 1)
-    rows = max(g.max_num_restarts, 0) * max(g.max_num_steps, 0) + 1
-    point = np.zeros(d)
-    start_values = np.zeros(max(S, 1))
-    kept = np.zeros(K, dtype=np.int32)
-    ends, end_values = np.zeros((K, d)), np.zeros(K)
-    steps = np.zeros(K, dtype=np.int32)
-    path = np.zeros((K, rows, d)) if (want_path and gradient_ascent) else None
-    value, found = C.c_double(0.0), C.c_int(0)
-    p = _num_pending(points_being_sampled, d)
-    pend, pendp = _d(points_being_sampled) if p else (None, None)
-    err = _lib.MoeError()
-    _check(_lib.load().moe_gibbon_mcmc_multistart(
-        arr, E, C.byref(g), bp, mins.ctypes.data_as(dp), Kmin, pendp, p, sp, S, 1 if gradient_ascent else 0, point.ctypes.data_as(dp),
-        C.byref(value), C.byref(found), start_values.ctypes.data_as(dp), kept.ctypes.data_as(ip), ends.ctypes.data_as(dp),
-        end_values.ctypes.data_as(dp), path.ctypes.data_as(dp) if path is not None else None, steps.ctypes.data_as(ip), C.byref(err)),
-        err)
-    out = {"point": point, "value": value.value, "found": bool(found.value), "start_values": start_values,
-           "kept_index": kept if gradient_ascent else None, "end_points": ends if gradient_ascent else None,
-           "end_values": end_values if gradient_ascent else None, "steps_taken": steps if gradient_ascent else None}
-    if want_path:
-        out["path"] = path
-    return out
+    arr, E, d, keep, mins, K = _gibbon_members(gps, min_values)
+    pre, post = (arr, E), (mins.ctypes.data_as(dp), K)
+    return _acq1_multistart(_lib.load().moe_gibbon_mcmc_multistart, pre, post, d, gd_params, bounds, starts, gradient_ascent, want_path,
+                            points_being_sampled)
 
 
 def gibbon_suggest(gps, gd_params, bounds, min_values, starts, num_to_sample, gradient_ascent=True, points_being_sampled=None):
@@ -1337,21 +1200,10 @@ def gibbon_suggest(gps, gd_params, bounds, min_values, starts, num_to_sample, gr
     gibbon_multistart from the same starts [S][dim] with the pending points points_being_sampled [p][dim] (may be None) followed by
     the points of the rounds before, bit for bit, in one device call; the limits of ei_analytic_suggest.  Returns a dict: points
     [q][dim], values [q], found [q]."""
-    arr, E, d, keep, mins, Kmin = _gibbon_members(gps, min_values)
-    g = DeviceGP._gd(gd_params)
-    bounds, bp = _d(bounds)
-    starts, sp = _d(starts)
-    S = starts.reshape(-1, d).shape[0]
-    q = int(num_to_sample)
-    p = _num_pending(points_being_sampled, d)
-    pend, pendp = _d(points_being_sampled) if p else (None, None)
-    points, values = np.zeros((max(q, 1), d)), np.zeros(max(q, 1))
-    found = np.zeros(max(q, 1), dtype=np.int32)
-    err = _lib.MoeError()
-    _check(_lib.load().moe_gibbon_mcmc_suggest(
-        arr, E, C.byref(g), bp, mins.ctypes.data_as(dp), Kmin, pendp, p, sp, S, 1 if gradient_ascent else 0, q,
-        points.ctypes.data_as(dp), values.ctypes.data_as(dp), found.ctypes.data_as(ip), C.byref(err)), err)
-    return {"points": points, "values": values, "found": found.astype(bool)}
+    arr, E, d, keep, mins, K = _gibbon_members(gps, min_values)
+    pre, post = (arr, E), (mins.ctypes.data_as(dp), K)
+    return _acq1_suggest(_lib.load().moe_gibbon_mcmc_suggest, pre, post, d, gd_params, bounds, starts, num_to_sample, gradient_ascent,
+                         points_being_sampled)
 
 
 def recommend(gps, candidates, gd_params, domain_bounds, num_fidelity=0, num_starts=1, want_values=False, want_path=False):

@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <random>
 #include <string>
@@ -11,6 +12,7 @@
 
 #include "gp.hpp"
 #include "kg.hpp"
+#include "kg1_ascent.hpp"
 
 struct moe_gp {
   moe::GpDev dev;
@@ -60,7 +62,7 @@ moe::GpDev& lock_gp(const moe_gp_t* gp_c, std::unique_lock<std::mutex>& lk) {
   return gp->dev;
 }
 
-// The preamble of the ensemble one-point acquisitions' entry points (moe_kg_discrete_mcmc*, moe_ei_analytic_mcmc*, moe_gibbon_mcmc*).
+// The first check of the ensemble one-point acquisitions' entry points (Acq1::check_num_mcmc; moe_ehvi_mcmc* have their own).
 void check_num_mcmc(int num_mcmc) {
   if (num_mcmc < 1 || num_mcmc > 1024) throw moe::Error(MOE_ERR_BOUNDS, "num_mcmc must be between 1 and 1024", num_mcmc, 1, 1024);
 }
@@ -878,6 +880,161 @@ int moe_gp_paths_minimize(const moe_gp_t* const* gps, int num_mcmc, const double
   });
 }
 
+// ---- the ensemble forms of the one-point acquisitions (kg1_ascent.hpp): five objectives, three shapes of entry point each ----
+extern "C++" {  // (the helpers return C++ types)
+namespace {
+
+// What an entry point says of its objective.  The three helpers below own the ladder of checks, in its one order: the num_mcmc
+// check, the NULL pointers (the objective's own and the shape's, one message), what needs no handle (the objective's own, then the
+// shapes), the pending points, the ascent's parameters, the handles flat, their locks, the members' check, the driver.
+struct Acq1 {
+  int num_mcmc = 0;
+  void (*check_num_mcmc)(int num_mcmc) = ::check_num_mcmc;
+  bool pointers = false;                                  // the objective's own pointers are all there
+  std::function<void(int num_points)> check_shapes;       // what needs no handle
+  const char* name = "";                                  // whose ascent it is, as check_ascent_params names it
+  std::function<std::vector<const moe_gp_t*>()> handles;  // the GPs of the call, flat
+  std::function<moe::Kg1Call()> call;                     // the client's description (made once the checks above have passed)
+};
+
+// the GPs of a call locked for the caller's scope, and the client's description with its members checked
+struct Acq1Locked {
+  std::vector<std::unique_lock<std::mutex>> locks;
+  std::vector<moe::GpDev*> gps;
+  moe::Kg1Call call;
+};
+Acq1Locked acq1_lock(const Acq1& a, int pending_room) {
+  const std::vector<const moe_gp_t*> flat = a.handles();
+  Acq1Locked l;
+  l.locks = lock_ensemble(flat.data(), (int)flat.size());
+  l.gps = ensemble(flat.data(), (int)flat.size());
+  l.call = a.call();
+  l.call.check_members(l.call.o, l.gps, pending_room);
+  return l;
+}
+
+void acq1_evaluate(const Acq1& a, const double* pending, int num_pending, const double* points, int num_points, int want_grad,
+                   double* value, double* grad, double* members_out) {
+  a.check_num_mcmc(a.num_mcmc);
+  require(a.pointers && points && value && (want_grad == 0 || grad), "NULL argument");
+  a.check_shapes(num_points);
+  moe::check_kg_discrete_pending(pending, num_pending, 1);
+  const Acq1Locked l = acq1_lock(a, num_pending);
+  moe::kg1_ensemble_evaluate(l.call.o, l.gps, points, num_points, want_grad != 0, value, grad, pending, num_pending, members_out);
+}
+
+void acq1_multistart(const Acq1& a, const moe_gd_params_t* outer, const double* domain_bounds, const double* pending, int num_pending,
+                     const double* starts, int num_starts, int do_gradient_ascent, const moe::Kg1MultistartOut& out) {
+  a.check_num_mcmc(a.num_mcmc);
+  require(a.pointers && outer && domain_bounds && starts && out.best_point && out.best_value && out.found, "NULL argument");
+  a.check_shapes(num_starts);
+  moe::check_kg_discrete_pending(pending, num_pending, 1);
+  check_ascent_params(outer, do_gradient_ascent, a.name);
+  const Acq1Locked l = acq1_lock(a, num_pending);
+  moe::kg1_ensemble_multistart(l.call.o, l.gps, *outer, domain_bounds, starts, num_starts, do_gradient_ascent, pending, num_pending, out);
+}
+
+void acq1_suggest(const Acq1& a, const moe_gd_params_t* outer, const double* domain_bounds, const double* pending, int num_pending,
+                  const double* starts, int num_starts, int do_gradient_ascent, int num_to_sample, const moe::Kg1BatchOut& out) {
+  a.check_num_mcmc(a.num_mcmc);
+  require(a.pointers && outer && domain_bounds && starts && out.best_points && out.best_values && out.found, "NULL argument");
+  a.check_shapes(num_starts);
+  moe::check_kg_discrete_pending(pending, num_pending, num_to_sample);
+  check_ascent_params(outer, do_gradient_ascent, a.name);
+  const Acq1Locked l = acq1_lock(a, num_pending + num_to_sample - 1);
+  moe::kg1_ensemble_suggest(l.call.o, l.gps, *outer, domain_bounds, starts, num_starts, do_gradient_ascent, pending, num_pending,
+                            num_to_sample, out);
+}
+
+// an objective with one GP per member: the handles as they come
+Acq1 acq1_of(const moe_gp_t* const* gps, int num_mcmc, const char* name) {
+  Acq1 a;
+  a.num_mcmc = num_mcmc;
+  a.name = name;
+  a.handles = [=] { return std::vector<const moe_gp_t*>(gps, gps + num_mcmc); };
+  return a;
+}
+
+Acq1 kg_discrete(const moe_gp_t* const* gps, int num_mcmc, int num_fidelity, const double* discrete_all, const int* num_discrete,
+                 const double* best_so_far) {
+  Acq1 a = acq1_of(gps, num_mcmc, "the discretised knowledge gradient");
+  a.pointers = gps && discrete_all && num_discrete && best_so_far;
+  a.check_shapes = [=](int num_points) { moe::check_kg_discrete_ensemble_shapes(num_mcmc, num_fidelity, num_discrete, num_points); };
+  a.call = [=] { return moe::kg1_call(num_fidelity, discrete_all, num_discrete, best_so_far); };
+  return a;
+}
+
+Acq1 ei_analytic(const moe_gp_t* const* gps, int num_mcmc, const double* best_so_far) {
+  Acq1 a = acq1_of(gps, num_mcmc, "the analytic expected improvement");
+  a.pointers = gps && best_so_far;
+  a.check_shapes = [=](int num_points) { moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_points); };
+  a.call = [=] { return moe::ei1_call(best_so_far); };
+  return a;
+}
+
+Acq1 gibbon(const moe_gp_t* const* gps, int num_mcmc, const double* min_values, int num_min_values) {
+  Acq1 a = acq1_of(gps, num_mcmc, "the min-value entropy acquisition");
+  a.pointers = gps && min_values;
+  a.check_shapes = [=](int num_points) {
+    moe::check_gibbon_min_values(min_values, num_mcmc, num_min_values);
+    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_points);
+  };
+  a.call = [=] { return moe::gibbon1_call(min_values, num_min_values); };
+  return a;
+}
+
+// The GPs of a constrained call, flat and ordered [e][role]: role 0 the objective GP of member e, role k constraint k's.
+std::vector<const moe_gp_t*> constrained_handles(const moe_gp_t* const* gps, int num_mcmc, const moe_gp_t* const* constraint_gps,
+                                                 int num_constraints) {
+  const int G = 1 + num_constraints;
+  std::vector<const moe_gp_t*> flat((size_t)num_mcmc * G);
+  for (int e = 0; e < num_mcmc; ++e) {
+    flat[(size_t)e * G] = gps[e];
+    for (int k = 0; k < num_constraints; ++k) flat[(size_t)e * G + 1 + k] = constraint_gps[(size_t)k * num_mcmc + e];
+  }
+  return flat;
+}
+
+Acq1 ei_constrained(const moe_gp_t* const* gps, int num_mcmc, const moe_gp_t* const* constraint_gps, int num_constraints,
+                    const double* thresholds, const double* best_so_far) {
+  Acq1 a = acq1_of(gps, num_mcmc, "the constrained expected improvement");
+  a.pointers = gps && best_so_far;
+  a.check_shapes = [=](int num_points) {
+    moe::check_ei_constrained_shapes(num_mcmc, num_constraints, constraint_gps, thresholds, best_so_far);
+    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_points);
+  };
+  a.handles = [=] { return constrained_handles(gps, num_mcmc, constraint_gps, num_constraints); };
+  a.call = [=] { return moe::cei1_call(num_mcmc, num_constraints, thresholds, best_so_far); };
+  return a;
+}
+
+// The GPs of a two-objective call, flat and ordered [e][objective]
+std::vector<const moe_gp_t*> two_objective_handles(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, int num_mcmc) {
+  std::vector<const moe_gp_t*> flat(2 * (size_t)num_mcmc);
+  for (int e = 0; e < num_mcmc; ++e) {
+    flat[2 * (size_t)e] = gps[e];
+    flat[2 * (size_t)e + 1] = gps2[e];
+  }
+  return flat;
+}
+
+Acq1 ehvi(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, int num_mcmc, const double* reference_point, const double* front,
+          int num_front) {
+  Acq1 a = acq1_of(gps, num_mcmc, "the expected hypervolume improvement");
+  a.check_num_mcmc = moe::check_ehvi_num_mcmc;
+  a.pointers = gps && gps2 && reference_point && (num_front <= 0 || front);
+  a.check_shapes = [=](int num_points) {
+    moe::check_ehvi_front(reference_point, front, num_front);
+    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_points);
+  };
+  a.handles = [=] { return two_objective_handles(gps, gps2, num_mcmc); };
+  a.call = [=] { return moe::ehvi1_call(num_mcmc, reference_point, front, num_front); };
+  return a;
+}
+
+}  // namespace
+}  // extern "C++"
+
 int moe_kg_discrete_mcmc(const moe_gp_t* const* gps, int num_mcmc, int num_fidelity, const double* discrete_all,
                          const int* num_discrete, const double* best_so_far, const double* points, int num_points, int want_grad,
                          double* kg, double* grad, moe_error_t* err) {
@@ -901,14 +1058,8 @@ int moe_kg_discrete_mcmc_pending(const moe_gp_t* const* gps, int num_mcmc, int n
                                  int num_being_sampled, const double* points, int num_points, int want_grad, double* kg, double* grad,
                                  moe_error_t* err) {
   return guarded(err, [&] {
-    check_num_mcmc(num_mcmc);
-    require(gps && discrete_all && num_discrete && best_so_far && points && kg && (want_grad == 0 || grad), "NULL argument");
-    moe::check_kg_discrete_ensemble_shapes(num_mcmc, num_fidelity, num_discrete, num_points);  // (what needs no handle)
-    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, 1);
-    const auto locks = lock_ensemble(gps, num_mcmc);
-    const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
-    moe::kg_discrete_mcmc_on_device(v, num_fidelity, discrete_all, num_discrete, best_so_far, points, num_points, want_grad != 0, kg,
-                                    grad, points_being_sampled, num_being_sampled);
+    acq1_evaluate(kg_discrete(gps, num_mcmc, num_fidelity, discrete_all, num_discrete, best_so_far), points_being_sampled,
+                  num_being_sampled, points, num_points, want_grad, kg, grad, nullptr);
   });
 }
 
@@ -920,17 +1071,9 @@ int moe_kg_discrete_mcmc_multistart_pending(const moe_gp_t* const* gps, int num_
                                             double* end_points, double* end_values, double* path, int* steps_taken,
                                             moe_error_t* err) {
   return guarded(err, [&] {
-    check_num_mcmc(num_mcmc);
-    require(gps && outer && domain_bounds && discrete_all && num_discrete && best_so_far && starts && best_point && best_value && found,
-            "NULL argument");
-    moe::check_kg_discrete_ensemble_shapes(num_mcmc, num_fidelity, num_discrete, num_starts);
-    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, 1);
-    check_ascent_params(outer, do_gradient_ascent, "the discretised knowledge gradient");
-    const auto locks = lock_ensemble(gps, num_mcmc);
-    const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
-    moe::kg_discrete_mcmc_multistart(v, num_fidelity, *outer, domain_bounds, discrete_all, num_discrete, best_so_far, starts, num_starts,
-                                     do_gradient_ascent, best_point, best_value, found, start_values, kept_index, end_points,
-                                     end_values, path, steps_taken, points_being_sampled, num_being_sampled);
+    acq1_multistart(kg_discrete(gps, num_mcmc, num_fidelity, discrete_all, num_discrete, best_so_far), outer, domain_bounds,
+                    points_being_sampled, num_being_sampled, starts, num_starts, do_gradient_ascent,
+                    {best_point, best_value, found, start_values, kept_index, end_points, end_values, path, steps_taken});
   });
 }
 
@@ -940,17 +1083,9 @@ int moe_kg_discrete_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, int n
                                  const double* starts, int num_starts, int do_gradient_ascent, int num_to_sample, double* best_points,
                                  double* best_values, int* found, moe_error_t* err) {
   return guarded(err, [&] {
-    check_num_mcmc(num_mcmc);
-    require(gps && outer && domain_bounds && discrete_all && num_discrete && best_so_far && starts && best_points && best_values && found,
-            "NULL argument");
-    moe::check_kg_discrete_ensemble_shapes(num_mcmc, num_fidelity, num_discrete, num_starts);
-    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, num_to_sample);
-    check_ascent_params(outer, do_gradient_ascent, "the discretised knowledge gradient");
-    const auto locks = lock_ensemble(gps, num_mcmc);
-    const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
-    moe::kg_discrete_mcmc_suggest(v, num_fidelity, *outer, domain_bounds, discrete_all, num_discrete, best_so_far, starts, num_starts,
-                                  do_gradient_ascent, points_being_sampled, num_being_sampled, num_to_sample, best_points,
-                                  best_values, found);
+    acq1_suggest(kg_discrete(gps, num_mcmc, num_fidelity, discrete_all, num_discrete, best_so_far), outer, domain_bounds,
+                 points_being_sampled, num_being_sampled, starts, num_starts, do_gradient_ascent, num_to_sample,
+                 {best_points, best_values, found});
   });
 }
 
@@ -960,14 +1095,8 @@ int moe_ei_analytic_mcmc(const moe_gp_t* const* gps, int num_mcmc, const double*
                          int num_being_sampled, const double* points, int num_points, int want_grad, double* ei, double* grad,
                          moe_error_t* err) {
   return guarded(err, [&] {
-    check_num_mcmc(num_mcmc);
-    require(gps && best_so_far && points && ei && (want_grad == 0 || grad), "NULL argument");
-    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_points);  // (what needs no handle)
-    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, 1);
-    const auto locks = lock_ensemble(gps, num_mcmc);
-    const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
-    moe::ei_analytic_mcmc_on_device(v, best_so_far, points, num_points, want_grad != 0, ei, grad, points_being_sampled,
-                                    num_being_sampled);
+    acq1_evaluate(ei_analytic(gps, num_mcmc, best_so_far), points_being_sampled, num_being_sampled, points, num_points, want_grad, ei,
+                  grad, nullptr);
   });
 }
 
@@ -977,16 +1106,9 @@ int moe_ei_analytic_mcmc_multistart(const moe_gp_t* const* gps, int num_mcmc, co
                                     double* best_value, int* found, double* start_values, int* kept_index, double* end_points,
                                     double* end_values, double* path, int* steps_taken, moe_error_t* err) {
   return guarded(err, [&] {
-    check_num_mcmc(num_mcmc);
-    require(gps && outer && domain_bounds && best_so_far && starts && best_point && best_value && found, "NULL argument");
-    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_starts);
-    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, 1);
-    check_ascent_params(outer, do_gradient_ascent, "the analytic expected improvement");
-    const auto locks = lock_ensemble(gps, num_mcmc);
-    const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
-    moe::ei_analytic_mcmc_multistart(v, *outer, domain_bounds, best_so_far, starts, num_starts, do_gradient_ascent, best_point,
-                                     best_value, found, start_values, kept_index, end_points, end_values, path, steps_taken,
-                                     points_being_sampled, num_being_sampled);
+    acq1_multistart(ei_analytic(gps, num_mcmc, best_so_far), outer, domain_bounds, points_being_sampled, num_being_sampled, starts,
+                    num_starts, do_gradient_ascent,
+                    {best_point, best_value, found, start_values, kept_index, end_points, end_values, path, steps_taken});
   });
 }
 
@@ -995,15 +1117,8 @@ int moe_ei_analytic_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, const
                                  const double* starts, int num_starts, int do_gradient_ascent, int num_to_sample, double* best_points,
                                  double* best_values, int* found, moe_error_t* err) {
   return guarded(err, [&] {
-    check_num_mcmc(num_mcmc);
-    require(gps && outer && domain_bounds && best_so_far && starts && best_points && best_values && found, "NULL argument");
-    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_starts);
-    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, num_to_sample);
-    check_ascent_params(outer, do_gradient_ascent, "the analytic expected improvement");
-    const auto locks = lock_ensemble(gps, num_mcmc);
-    const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
-    moe::ei_analytic_mcmc_suggest(v, *outer, domain_bounds, best_so_far, starts, num_starts, do_gradient_ascent, points_being_sampled,
-                                  num_being_sampled, num_to_sample, best_points, best_values, found);
+    acq1_suggest(ei_analytic(gps, num_mcmc, best_so_far), outer, domain_bounds, points_being_sampled, num_being_sampled, starts,
+                 num_starts, do_gradient_ascent, num_to_sample, {best_points, best_values, found});
   });
 }
 
@@ -1011,15 +1126,8 @@ int moe_gibbon_mcmc(const moe_gp_t* const* gps, int num_mcmc, const double* min_
                     const double* points_being_sampled, int num_being_sampled, const double* points, int num_points, int want_grad,
                     double* value, double* grad, moe_error_t* err) {
   return guarded(err, [&] {
-    check_num_mcmc(num_mcmc);
-    require(gps && min_values && points && value && (want_grad == 0 || grad), "NULL argument");
-    moe::check_gibbon_min_values(min_values, num_mcmc, num_min_values);  // (what needs no handle)
-    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_points);
-    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, 1);
-    const auto locks = lock_ensemble(gps, num_mcmc);
-    const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
-    moe::gibbon_mcmc_on_device(v, min_values, num_min_values, points, num_points, want_grad != 0, value, grad, points_being_sampled,
-                               num_being_sampled);
+    acq1_evaluate(gibbon(gps, num_mcmc, min_values, num_min_values), points_being_sampled, num_being_sampled, points, num_points,
+                  want_grad, value, grad, nullptr);
   });
 }
 
@@ -1029,17 +1137,9 @@ int moe_gibbon_mcmc_multistart(const moe_gp_t* const* gps, int num_mcmc, const m
                                double* best_point, double* best_value, int* found, double* start_values, int* kept_index,
                                double* end_points, double* end_values, double* path, int* steps_taken, moe_error_t* err) {
   return guarded(err, [&] {
-    check_num_mcmc(num_mcmc);
-    require(gps && outer && domain_bounds && min_values && starts && best_point && best_value && found, "NULL argument");
-    moe::check_gibbon_min_values(min_values, num_mcmc, num_min_values);
-    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_starts);
-    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, 1);
-    check_ascent_params(outer, do_gradient_ascent, "the min-value entropy acquisition");
-    const auto locks = lock_ensemble(gps, num_mcmc);
-    const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
-    moe::gibbon_mcmc_multistart(v, *outer, domain_bounds, min_values, num_min_values, starts, num_starts, do_gradient_ascent,
-                                best_point, best_value, found, start_values, kept_index, end_points, end_values, path, steps_taken,
-                                points_being_sampled, num_being_sampled);
+    acq1_multistart(gibbon(gps, num_mcmc, min_values, num_min_values), outer, domain_bounds, points_being_sampled, num_being_sampled,
+                    starts, num_starts, do_gradient_ascent,
+                    {best_point, best_value, found, start_values, kept_index, end_points, end_values, path, steps_taken});
   });
 }
 
@@ -1048,29 +1148,9 @@ int moe_gibbon_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, const moe_
                             const double* starts, int num_starts, int do_gradient_ascent, int num_to_sample, double* best_points,
                             double* best_values, int* found, moe_error_t* err) {
   return guarded(err, [&] {
-    check_num_mcmc(num_mcmc);
-    require(gps && outer && domain_bounds && min_values && starts && best_points && best_values && found, "NULL argument");
-    moe::check_gibbon_min_values(min_values, num_mcmc, num_min_values);
-    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_starts);
-    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, num_to_sample);
-    check_ascent_params(outer, do_gradient_ascent, "the min-value entropy acquisition");
-    const auto locks = lock_ensemble(gps, num_mcmc);
-    const std::vector<moe::GpDev*> v = ensemble(gps, num_mcmc);
-    moe::gibbon_mcmc_suggest(v, *outer, domain_bounds, min_values, num_min_values, starts, num_starts, do_gradient_ascent,
-                             points_being_sampled, num_being_sampled, num_to_sample, best_points, best_values, found);
+    acq1_suggest(gibbon(gps, num_mcmc, min_values, num_min_values), outer, domain_bounds, points_being_sampled, num_being_sampled,
+                 starts, num_starts, do_gradient_ascent, num_to_sample, {best_points, best_values, found});
   });
-}
-
-// The GPs of a constrained call, flat and ordered [e][role]: role 0 the objective GP of member e, role k constraint k's.
-static std::vector<const moe_gp_t*> constrained_handles(const moe_gp_t* const* gps, int num_mcmc, const moe_gp_t* const* constraint_gps,
-                                                        int num_constraints) {
-  const int G = 1 + num_constraints;
-  std::vector<const moe_gp_t*> flat((size_t)num_mcmc * G);
-  for (int e = 0; e < num_mcmc; ++e) {
-    flat[(size_t)e * G] = gps[e];
-    for (int k = 0; k < num_constraints; ++k) flat[(size_t)e * G + 1 + k] = constraint_gps[(size_t)k * num_mcmc + e];
-  }
-  return flat;
 }
 
 int moe_ei_constrained_mcmc(const moe_gp_t* const* gps, int num_mcmc, const moe_gp_t* const* constraint_gps, int num_constraints,
@@ -1078,16 +1158,8 @@ int moe_ei_constrained_mcmc(const moe_gp_t* const* gps, int num_mcmc, const moe_
                             int num_being_sampled, const double* points, int num_points, int want_grad, double* value, double* grad,
                             double* factors, moe_error_t* err) {
   return guarded(err, [&] {
-    check_num_mcmc(num_mcmc);
-    require(gps && best_so_far && points && value && (want_grad == 0 || grad), "NULL argument");
-    moe::check_ei_constrained_shapes(num_mcmc, num_constraints, constraint_gps, thresholds, best_so_far);  // (what needs no handle)
-    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_points);
-    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, 1);
-    const std::vector<const moe_gp_t*> flat = constrained_handles(gps, num_mcmc, constraint_gps, num_constraints);
-    const auto locks = lock_ensemble(flat.data(), (int)flat.size());
-    const std::vector<moe::GpDev*> v = ensemble(flat.data(), (int)flat.size());
-    moe::ei_constrained_mcmc_on_device(v, num_constraints, thresholds, best_so_far, points, num_points, want_grad != 0, value, grad,
-                                       factors, points_being_sampled, num_being_sampled);
+    acq1_evaluate(ei_constrained(gps, num_mcmc, constraint_gps, num_constraints, thresholds, best_so_far), points_being_sampled,
+                  num_being_sampled, points, num_points, want_grad, value, grad, factors);
   });
 }
 
@@ -1098,18 +1170,9 @@ int moe_ei_constrained_mcmc_multistart(const moe_gp_t* const* gps, int num_mcmc,
                                        double* best_point, double* best_value, int* found, double* start_values, int* kept_index,
                                        double* end_points, double* end_values, double* path, int* steps_taken, moe_error_t* err) {
   return guarded(err, [&] {
-    check_num_mcmc(num_mcmc);
-    require(gps && outer && domain_bounds && best_so_far && starts && best_point && best_value && found, "NULL argument");
-    moe::check_ei_constrained_shapes(num_mcmc, num_constraints, constraint_gps, thresholds, best_so_far);
-    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_starts);
-    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, 1);
-    check_ascent_params(outer, do_gradient_ascent, "the constrained expected improvement");
-    const std::vector<const moe_gp_t*> flat = constrained_handles(gps, num_mcmc, constraint_gps, num_constraints);
-    const auto locks = lock_ensemble(flat.data(), (int)flat.size());
-    const std::vector<moe::GpDev*> v = ensemble(flat.data(), (int)flat.size());
-    moe::ei_constrained_mcmc_multistart(v, num_constraints, thresholds, *outer, domain_bounds, best_so_far, starts, num_starts,
-                                        do_gradient_ascent, best_point, best_value, found, start_values, kept_index, end_points,
-                                        end_values, path, steps_taken, points_being_sampled, num_being_sampled);
+    acq1_multistart(ei_constrained(gps, num_mcmc, constraint_gps, num_constraints, thresholds, best_so_far), outer, domain_bounds,
+                    points_being_sampled, num_being_sampled, starts, num_starts, do_gradient_ascent,
+                    {best_point, best_value, found, start_values, kept_index, end_points, end_values, path, steps_taken});
   });
 }
 
@@ -1119,45 +1182,18 @@ int moe_ei_constrained_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, co
                                     int num_being_sampled, const double* starts, int num_starts, int do_gradient_ascent,
                                     int num_to_sample, double* best_points, double* best_values, int* found, moe_error_t* err) {
   return guarded(err, [&] {
-    check_num_mcmc(num_mcmc);
-    require(gps && outer && domain_bounds && best_so_far && starts && best_points && best_values && found, "NULL argument");
-    moe::check_ei_constrained_shapes(num_mcmc, num_constraints, constraint_gps, thresholds, best_so_far);
-    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_starts);
-    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, num_to_sample);
-    check_ascent_params(outer, do_gradient_ascent, "the constrained expected improvement");
-    const std::vector<const moe_gp_t*> flat = constrained_handles(gps, num_mcmc, constraint_gps, num_constraints);
-    const auto locks = lock_ensemble(flat.data(), (int)flat.size());
-    const std::vector<moe::GpDev*> v = ensemble(flat.data(), (int)flat.size());
-    moe::ei_constrained_mcmc_suggest(v, num_constraints, thresholds, *outer, domain_bounds, best_so_far, starts, num_starts,
-                                     do_gradient_ascent, points_being_sampled, num_being_sampled, num_to_sample, best_points,
-                                     best_values, found);
+    acq1_suggest(ei_constrained(gps, num_mcmc, constraint_gps, num_constraints, thresholds, best_so_far), outer, domain_bounds,
+                 points_being_sampled, num_being_sampled, starts, num_starts, do_gradient_ascent, num_to_sample,
+                 {best_points, best_values, found});
   });
-}
-
-// The GPs of a two-objective call, flat and ordered [e][objective]
-static std::vector<const moe_gp_t*> two_objective_handles(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, int num_mcmc) {
-  std::vector<const moe_gp_t*> flat(2 * (size_t)num_mcmc);
-  for (int e = 0; e < num_mcmc; ++e) {
-    flat[2 * (size_t)e] = gps[e];
-    flat[2 * (size_t)e + 1] = gps2[e];
-  }
-  return flat;
 }
 
 int moe_ehvi_mcmc(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, int num_mcmc, const double* reference_point,
                   const double* front, int num_front, const double* points_being_sampled, int num_being_sampled, const double* points,
                   int num_points, int want_grad, double* value, double* grad, double* member_values_out, moe_error_t* err) {
   return guarded(err, [&] {
-    moe::check_ehvi_num_mcmc(num_mcmc);
-    require(gps && gps2 && reference_point && points && value && (want_grad == 0 || grad) && (num_front <= 0 || front), "NULL argument");
-    moe::check_ehvi_front(reference_point, front, num_front);  // (what needs no handle)
-    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_points);
-    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, 1);
-    const std::vector<const moe_gp_t*> flat = two_objective_handles(gps, gps2, num_mcmc);
-    const auto locks = lock_ensemble(flat.data(), (int)flat.size());
-    const std::vector<moe::GpDev*> v = ensemble(flat.data(), (int)flat.size());
-    moe::ehvi_mcmc_on_device(v, reference_point, front, num_front, points, num_points, want_grad != 0, value, grad, member_values_out,
-                             points_being_sampled, num_being_sampled);
+    acq1_evaluate(ehvi(gps, gps2, num_mcmc, reference_point, front, num_front), points_being_sampled, num_being_sampled, points,
+                  num_points, want_grad, value, grad, member_values_out);
   });
 }
 
@@ -1168,20 +1204,9 @@ int moe_ehvi_mcmc_multistart(const moe_gp_t* const* gps, const moe_gp_t* const* 
                              int* kept_index, double* end_points, double* end_values, double* path, int* steps_taken,
                              moe_error_t* err) {
   return guarded(err, [&] {
-    moe::check_ehvi_num_mcmc(num_mcmc);
-    require(gps && gps2 && reference_point && outer && domain_bounds && starts && best_point && best_value && found &&
-                (num_front <= 0 || front),
-            "NULL argument");
-    moe::check_ehvi_front(reference_point, front, num_front);
-    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_starts);
-    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, 1);
-    check_ascent_params(outer, do_gradient_ascent, "the expected hypervolume improvement");
-    const std::vector<const moe_gp_t*> flat = two_objective_handles(gps, gps2, num_mcmc);
-    const auto locks = lock_ensemble(flat.data(), (int)flat.size());
-    const std::vector<moe::GpDev*> v = ensemble(flat.data(), (int)flat.size());
-    moe::ehvi_mcmc_multistart(v, reference_point, front, num_front, *outer, domain_bounds, starts, num_starts, do_gradient_ascent,
-                              best_point, best_value, found, start_values, kept_index, end_points, end_values, path, steps_taken,
-                              points_being_sampled, num_being_sampled);
+    acq1_multistart(ehvi(gps, gps2, num_mcmc, reference_point, front, num_front), outer, domain_bounds, points_being_sampled,
+                    num_being_sampled, starts, num_starts, do_gradient_ascent,
+                    {best_point, best_value, found, start_values, kept_index, end_points, end_values, path, steps_taken});
   });
 }
 
@@ -1191,19 +1216,8 @@ int moe_ehvi_mcmc_suggest(const moe_gp_t* const* gps, const moe_gp_t* const* gps
                           int do_gradient_ascent, int num_to_sample, double* best_points, double* best_values, int* found,
                           moe_error_t* err) {
   return guarded(err, [&] {
-    moe::check_ehvi_num_mcmc(num_mcmc);
-    require(gps && gps2 && reference_point && outer && domain_bounds && starts && best_points && best_values && found &&
-                (num_front <= 0 || front),
-            "NULL argument");
-    moe::check_ehvi_front(reference_point, front, num_front);
-    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_starts);
-    moe::check_kg_discrete_pending(points_being_sampled, num_being_sampled, num_to_sample);
-    check_ascent_params(outer, do_gradient_ascent, "the expected hypervolume improvement");
-    const std::vector<const moe_gp_t*> flat = two_objective_handles(gps, gps2, num_mcmc);
-    const auto locks = lock_ensemble(flat.data(), (int)flat.size());
-    const std::vector<moe::GpDev*> v = ensemble(flat.data(), (int)flat.size());
-    moe::ehvi_mcmc_suggest(v, reference_point, front, num_front, *outer, domain_bounds, starts, num_starts, do_gradient_ascent,
-                           points_being_sampled, num_being_sampled, num_to_sample, best_points, best_values, found);
+    acq1_suggest(ehvi(gps, gps2, num_mcmc, reference_point, front, num_front), outer, domain_bounds, points_being_sampled,
+                 num_being_sampled, starts, num_starts, do_gradient_ascent, num_to_sample, {best_points, best_values, found});
   });
 }
 

@@ -1,10 +1,10 @@
 // cornell_moe_amd/csrc/cei1.hip -- the constrained expected improvement (expected improvement times the probability of feasibility:
 // Schonlau, Welch & Jones 1998; Gardner et al. 2014; Gelbart, Snoek & Adams 2014) averaged over a hyper-parameter ensemble, with
 // pending points, its multistart ascent and greedy q-point batches, on the device (moe_ei_constrained_mcmc,
-// moe_ei_constrained_mcmc_multistart, moe_ei_constrained_mcmc_suggest): the fourth client of kg1_ascent.hip's staging, ascent and
-// drivers.  The pending-row extension is kg1_pending.hip's, the layout, the members' check and the gradient's tail are ei1.hip's
-// (ei1.hpp); this file keeps the candidate kernel with its two roles, the combine kernel, the believed-feasible incumbent, a
-// sub-member's chain and the description of the objective.
+// moe_ei_constrained_mcmc_multistart, moe_ei_constrained_mcmc_suggest): a client of kg1_ascent.hip's staging, ascent and drivers.
+// The pending-row extension is kg1_pending.hip's, the layout, the members' check, the pass and the gradient's tail are ei1.hip's
+// (ei1.hpp); this file keeps the candidate kernel with its two roles, the combine kernel, the believed-feasible incumbent and the
+// description of the call (cei1_call).
 //
 // A call takes E joint hyper-samples and K constraints, 0 <= K <= 8.  Member e is 1 + K GPs: the objective GP and the constraint GPs
 // c_1 .. c_K, constraint k satisfied where c_k(x) <= tau_k.  The E (1 + K) GPs are the SUB-MEMBERS of one Kg1Ensemble, ordered
@@ -35,6 +35,7 @@
 #include <cfloat>
 #include <cmath>
 
+#include "acq1_device.hpp"
 #include "device_cov.hpp"
 #include "ei1.hpp"
 #include "kg1_ascent.hpp"
@@ -43,33 +44,14 @@ namespace moe {
 
 namespace {
 
-constexpr double kMinVarCei = DBL_MIN;                                  // the value's floor (ei1.hip: kMinVarEI)
-constexpr double kMinVarGradCei = 150.0 * DBL_EPSILON * DBL_EPSILON;  // the gradient's (ei1.hip: kMinVarGradEI)
-
-__device__ __forceinline__ double cei1_pdf(double x) { return 0.3989422804014326779399460599343818684759 * exp(-0.5 * x * x); }
-// Phi through erfc on the side of x's sign (ei1.hip: ei1_cdf)
-__device__ __forceinline__ double cei1_cdf(double x) {
-  const double r = 0.7071067811865475244008443621048490392848;
-  return (x <= 0.0) ? 0.5 * erfc(-x * r) : 1.0 - 0.5 * erfc(x * r);
-}
-
-// One wavefront per candidate: ei1_cand_kernel's chain for the variance (the lanes load 64 rows at a time and every lane runs the
-// whole chain on the broadcast entries; rows past R add exact zeros), then the scalars of the sub-member's role.  *best is b' (role
-// 0) or tau_k (role k); val_out takes the factor, and with want_grad s_out the scalar s and T the column w v'_x.
+// One wavefront per candidate: ei1_cand_kernel's chain for the variance (row_chain), then the scalars of the sub-member's role.
+// *best is b' (role 0) or tau_k (role k); val_out takes the factor, and with want_grad s_out the scalar s and T the column w v'_x.
 struct cei1_cand_kernel_body {
   static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, int R, int ld, int ncols, int col0, const CovParams& cp, int want_grad, int role, const double* __restrict__ best, const double* __restrict__ mu, const double* __restrict__ Vx, double* __restrict__ val_out, double* __restrict__ s_out, double* __restrict__ T) {
     const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (c >= ncols) return;
     const double* v = Vx + (size_t)c * ld;
-    double ss = 0.0;
-    for (int r0 = 0; r0 < R; r0 += 64) {
-      const double x = (r0 + lane < R) ? v[r0 + lane] : 0.0;
-  #pragma unroll
-      for (int i = 0; i < 64; ++i) {
-        const double xi = __shfl(x, i, 64);
-        ss = fma(xi, xi, ss);
-      }
-    }
+    const double ss = row_chain(v, 0, R, lane, 0.0);
     const double var = radial_scalars(cp.type, cp.alpha, 0.0).base - ss;
     const double b = *best;
     double* tc = T + (size_t)c * ld;
@@ -82,21 +64,21 @@ struct cei1_cand_kernel_body {
     }
     const double t = b - mu[c];
     if (lane == 0) {
-      const double sigma = sqrt(fmax(kMinVarCei, var));
+      const double sigma = sqrt(fmax(kMinVarEI, var));
       const double cc = t / sigma;
       if (role == 0)
-        val_out[col0 + c] = fmax(0.0, t * cei1_cdf(cc) + sigma * cei1_pdf(cc));
+        val_out[col0 + c] = fmax(0.0, t * normal_cdf(cc) + sigma * normal_pdf(cc));
       else
-        val_out[col0 + c] = cei1_cdf(cc);
+        val_out[col0 + c] = normal_cdf(cc);
     }
     if (want_grad == 0) return;
-    const double sg = sqrt(fmax(kMinVarGradCei, var));
+    const double sg = sqrt(fmax(kMinVarGradEI, var));
     const double cg = t / sg;
-    const double pg = cei1_pdf(cg) / sg;
+    const double pg = normal_pdf(cg) / sg;
     double w;
     if (role == 0) {
       w = pg;
-      if (lane == 0) s_out[c] = cei1_cdf(cg);
+      if (lane == 0) s_out[c] = normal_cdf(cg);
     } else {
       w = -(pg * cg) / sg;
       if (lane == 0) s_out[c] = pg;
@@ -170,26 +152,14 @@ __global__ void cei1_best_kernel(Cei1Best a, int G, int first, int count) {
 }
 
 // ei1.hip's pass with cei1_cand_kernel in the place of ei1_cand_kernel (dScal holds s)
-void cei1_eval_pass(const Kg1Member& m, const double* Px, int nc, int c0, bool with_grad, hipStream_t s) {
-  GpDev& gp = *m.gp;
-  if (nc < 1 || nc > m.widest || c0 < 0 || c0 + nc > m.C || (with_grad && !m.with_grad))
-    throw Error(MOE_ERR_RUNTIME, "cei1_eval_pass: the pass does not fit the member's buffers");
-  const int N = gp.N, n = gp.n, R = N + m.p, ld = m.ld;
-  const DerivList none = no_derivs();  // (the candidate is a function value)
-  launch_cov_build(gp.cp, gp.dX.p, n, gp.derivs, Px, nc, none, nullptr, gp.dE.p, N, 0, s);
-  tri_cols(gp, 'N', nc, gp.dE.p, N, m.dVx, ld, s);
-  launch_mean(gp.cp, gp.dX.p, n, gp.derivs, gp.dKinvY.p, Px, nc, gp.mean, false, m.dMuh, s);
-  if (m.p > 0) kg1_pending_rows(m, Px, m.dVx, nc, 0, m.p, s);
-  launch_kernel_ens<cei1_cand_kernel_body, 256>(cei1_cand_kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, s, R, ld, nc, c0, gp.cp,
-                                                with_grad ? 1 : 0, m.role, (const double*)m.dBp, (const double*)m.dMuh,
+void cand_step(const Kg1Member& m, int nc, int c0, bool with_grad, hipStream_t s) {
+  launch_kernel_ens<cei1_cand_kernel_body, 256>(cei1_cand_kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, s, m.gp->N + m.p, m.ld, nc,
+                                                c0, m.gp->cp, with_grad ? 1 : 0, m.role, (const double*)m.dBp, (const double*)m.dMuh,
                                                 (const double*)m.dVx, m.dKg, m.dScal, m.dT);
-  MOE_HIP_CHECK(hipGetLastError());
-  if (with_grad) ei1_grad_tail(m, Px, nc, c0, s);
 }
 
 void cei1_eval_points(const Kg1Member& m, const double* Px, const double*, int C, bool with_grad, hipStream_t s) {
-  const int dp = m.gp->dp;
-  for (int c0 = 0; c0 < C; c0 += m.per_pass) cei1_eval_pass(m, Px + (size_t)c0 * dp, std::min(m.per_pass, C - c0), c0, with_grad, s);
+  ei1_eval_passes(m, Px, C, with_grad, s, "cei1_eval_pass", cand_step, ei1_grad_tail);
 }
 
 // mu of every sub-member at P_j0 .. j0 + count - 1 (the function values alone), then every member's believed-feasible incumbent
@@ -235,22 +205,28 @@ void combine(const Kg1Ensemble& T, int C, double* value_out, double* grad_out) {
   MOE_HIP_CHECK(hipGetLastError());
 }
 
-// the sub-members' limits [E (1 + K)] of a call
-std::vector<double> limits(int E, int K, const double* best_so_far, const double* thresholds) {
-  std::vector<double> lim((size_t)E * (1 + K));
-  for (int e = 0; e < E; ++e) {
-    lim[(size_t)e * (1 + K)] = best_so_far[e];
-    for (int k = 0; k < K; ++k) lim[(size_t)e * (1 + K) + 1 + k] = thresholds[k];
-  }
-  return lim;
-}
-
-// No sets, no fidelity coordinates; groups of 1 + K sub-members under the product rule (K = 0: one GP per member and the mean)
-Kg1Objective objective(const double* lim, int K) {
-  return Kg1Objective{0, nullptr, nullptr, lim, member, cei1_eval_points, nullptr, all_extended, pick_appended, nullptr, 0, 1 + K, combine};
-}
-
 }  // namespace
+
+// No sets, no fidelity coordinates; groups of 1 + K sub-members under the product rule (K = 0: one GP per member and the mean).
+// The call keeps the sub-members' limits [E (1 + K)].
+Kg1Call cei1_call(int num_mcmc, int num_constraints, const double* thresholds, const double* best_so_far) {
+  const int E = num_mcmc, K = num_constraints;
+  Kg1Call call;
+  call.doubles.resize((size_t)E * (1 + K));
+  for (int e = 0; e < E; ++e) {
+    call.doubles[(size_t)e * (1 + K)] = best_so_far[e];
+    for (int k = 0; k < K; ++k) call.doubles[(size_t)e * (1 + K) + 1 + k] = thresholds[k];
+  }
+  call.o.best_so_far = call.doubles.data();
+  call.o.member = member;
+  call.o.eval_points = cei1_eval_points;
+  call.o.all_extended = all_extended;
+  call.o.pick_appended = pick_appended;
+  call.o.group = 1 + K;
+  call.o.combine = combine;
+  call.check_members = ei1_check_members;
+  return call;
+}
 
 void check_ei_constrained_shapes(int num_mcmc, int num_constraints, const void* constraint_gps, const double* thresholds,
                                  const double* best_so_far) {
@@ -265,39 +241,6 @@ void check_ei_constrained_shapes(int num_mcmc, int num_constraints, const void* 
   for (int e = 0; e < num_mcmc; ++e)
     if (std::isnan(best_so_far[e]) || best_so_far[e] == -INFINITY)
       throw Error(MOE_ERR_INVALID_VALUE, "best_so_far must be finite or +infinity (no feasible observation yet)", best_so_far[e], e, 0);
-}
-
-void ei_constrained_mcmc_on_device(const std::vector<GpDev*>& gps, int num_constraints, const double* thresholds,
-                                   const double* best_so_far, const double* pts, int C, bool want_grad, double* value_out,
-                                   double* grad_out, double* factors_out, const double* pending, int num_pending) {
-  ei1_check_members(gps, num_pending);
-  const std::vector<double> lim = limits((int)gps.size() / (1 + num_constraints), num_constraints, best_so_far, thresholds);
-  kg1_ensemble_evaluate(objective(lim.data(), num_constraints), gps, pts, C, want_grad, value_out, grad_out, pending, num_pending,
-                        factors_out);
-}
-
-void ei_constrained_mcmc_multistart(const std::vector<GpDev*>& gps, int num_constraints, const double* thresholds,
-                                    const moe_gd_params_t& outer, const double* domain_bounds, const double* best_so_far,
-                                    const double* starts, int num_starts, int do_gradient_ascent, double* best_point, double* best_value,
-                                    int* found, double* start_values, int* kept_index, double* end_points, double* end_values,
-                                    double* path, int* steps_taken, const double* pending, int num_pending) {
-  ei1_check_members(gps, num_pending);
-  const std::vector<double> lim = limits((int)gps.size() / (1 + num_constraints), num_constraints, best_so_far, thresholds);
-  kg1_ensemble_multistart(objective(lim.data(), num_constraints), gps, outer, domain_bounds, starts, num_starts, do_gradient_ascent,
-                          best_point, best_value, found, start_values, kept_index, end_points, end_values, path, steps_taken, pending,
-                          num_pending);
-}
-
-// q points greedily: a round appends the pick's rows to every sub-member's extension and the pick's believed value, where the
-// member believes it feasible, to the member's incumbent.
-void ei_constrained_mcmc_suggest(const std::vector<GpDev*>& gps, int num_constraints, const double* thresholds,
-                                 const moe_gd_params_t& outer, const double* domain_bounds, const double* best_so_far,
-                                 const double* starts, int num_starts, int do_gradient_ascent, const double* pending, int num_pending,
-                                 int num_to_sample, double* best_points, double* best_values, int* found) {
-  ei1_check_members(gps, num_pending + num_to_sample - 1);
-  const std::vector<double> lim = limits((int)gps.size() / (1 + num_constraints), num_constraints, best_so_far, thresholds);
-  kg1_ensemble_suggest(objective(lim.data(), num_constraints), gps, outer, domain_bounds, starts, num_starts, do_gradient_ascent, pending,
-                       num_pending, num_to_sample, best_points, best_values, found);
 }
 
 }  // namespace moe

@@ -1,9 +1,10 @@
 // cornell_moe_amd/csrc/ehvi1.hip -- the two-objective expected hypervolume improvement (Emmerich, Giannakoglou & Naujoks 2006;
 // Emmerich, Deutz & Klinkenberg 2011; Yang et al. 2019) averaged over a hyper-parameter ensemble, with pending points, its
-// multistart ascent and greedy q-point batches, on the device (moe_ehvi_mcmc, moe_ehvi_mcmc_multistart, moe_ehvi_mcmc_suggest): the
-// fifth client of kg1_ascent.hip's staging, ascent and drivers.  The pending-row extension is kg1_pending.hip's, the layout and the
-// members' check are ei1.hip's (ei1.hpp); this file keeps a sub-member's chain (candidate kernel and the two-sum gradient kernel),
-// the front kernel, the strip kernel, the combine kernel and the description of the objective.
+// multistart ascent and greedy q-point batches, on the device (moe_ehvi_mcmc, moe_ehvi_mcmc_multistart, moe_ehvi_mcmc_suggest): a
+// client of kg1_ascent.hip's staging, ascent and drivers.  The pending-row extension is kg1_pending.hip's, the
+// layout and the pass are ei1.hip's (ei1.hpp); this file keeps a sub-member's candidate kernel and the two-sum gradient kernel
+// with its tail, the front kernel, the strip kernel, the combine kernel, the members' check and the description of the call
+// (ehvi1_call).
 //
 // Minimisation.  A call takes E joint hyper-samples; member e is two GPs, objective 1 and objective 2, the 2 E GPs being the
 // SUB-MEMBERS of one Kg1Ensemble ordered [e][role].  r = (r1, r2) is the reference point, the front F >= 0 points (u_i, v_i) with
@@ -44,6 +45,7 @@
 #include <cfloat>
 #include <cmath>
 
+#include "acq1_device.hpp"
 #include "device_cov.hpp"
 #include "ei1.hpp"
 #include "kg1_ascent.hpp"
@@ -52,16 +54,7 @@ namespace moe {
 
 namespace {
 
-constexpr double kMinVarEhvi = DBL_MIN;                                  // the value's floor (ei1.hip: kMinVarEI)
-constexpr double kMinVarGradEhvi = 150.0 * DBL_EPSILON * DBL_EPSILON;  // the gradient's (ei1.hip: kMinVarGradEI)
-constexpr int kEhviCap = kEhviMaxFront + kKg1MaxPending;               // a member's front at its largest
-
-__device__ __forceinline__ double ehvi1_pdf(double x) { return 0.3989422804014326779399460599343818684759 * exp(-0.5 * x * x); }
-// Phi through erfc on the side of x's sign (ei1.hip: ei1_cdf)
-__device__ __forceinline__ double ehvi1_cdf(double x) {
-  const double r = 0.7071067811865475244008443621048490392848;
-  return (x <= 0.0) ? 0.5 * erfc(-x * r) : 1.0 - 0.5 * erfc(x * r);
-}
+constexpr int kEhviCap = kEhviMaxFront + kKg1MaxPending;  // a member's front at its largest
 
 // what the hooks need of the call (Kg1Objective::client)
 struct Ehvi1Call {
@@ -98,15 +91,7 @@ struct ehvi1_cand_kernel_body {
     const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (c >= ncols) return;
     const double* v = Vx + (size_t)c * ld;
-    double ss = 0.0;
-    for (int r0 = 0; r0 < R; r0 += 64) {
-      const double x = (r0 + lane < R) ? v[r0 + lane] : 0.0;
-  #pragma unroll
-      for (int i = 0; i < 64; ++i) {
-        const double xi = __shfl(x, i, 64);
-        ss = fma(xi, xi, ss);
-      }
-    }
+    const double ss = row_chain(v, 0, R, lane, 0.0);
     const double var = radial_scalars(cp.type, cp.alpha, 0.0).base - ss;
     if (lane == 0) {
       out[col0 + c] = mu[c];
@@ -252,7 +237,7 @@ __global__ __launch_bounds__(64) void ehvi1_front_kernel(const double* const* __
 // psi and, with a gradient, its two derivatives at the edge t of a GP with mean mu and floored deviations sigma / sg
 __device__ __forceinline__ void ehvi1_edge(double t, double mu, double sigma, double sg, bool want_grad, double& psi, double& dmu, double& dvar) {
   const double z = (t - mu) / sigma;
-  const double cdf = ehvi1_cdf(z), pdf = ehvi1_pdf(z);
+  const double cdf = normal_cdf(z), pdf = normal_pdf(z);
   psi = (t - mu) * cdf + sigma * pdf;
   dmu = 0.0;
   dvar = 0.0;
@@ -262,8 +247,8 @@ __device__ __forceinline__ void ehvi1_edge(double t, double mu, double sigma, do
     dvar = pdf / (2.0 * sg);
   } else {
     const double zg = (t - mu) / sg;
-    dmu = -ehvi1_cdf(zg);
-    dvar = ehvi1_pdf(zg) / (2.0 * sg);
+    dmu = -normal_cdf(zg);
+    dvar = normal_pdf(zg) / (2.0 * sg);
   }
 }
 
@@ -286,8 +271,8 @@ __global__ __launch_bounds__(256) void ehvi1_strip_kernel(int C, int Cs, const d
   const bool wg = want_grad != 0;
   const double mu1 = kg[2 * e][c], var1 = kg[2 * e][(size_t)Cs + c];
   const double mu2 = kg[2 * e + 1][c], var2 = kg[2 * e + 1][(size_t)Cs + c];
-  const double sd1 = sqrt(fmax(kMinVarEhvi, var1)), sg1 = sqrt(fmax(kMinVarGradEhvi, var1));
-  const double sd2 = sqrt(fmax(kMinVarEhvi, var2)), sg2 = sqrt(fmax(kMinVarGradEhvi, var2));
+  const double sd1 = sqrt(fmax(kMinVarEI, var1)), sg1 = sqrt(fmax(kMinVarGradEI, var1));
+  const double sd2 = sqrt(fmax(kMinVarEI, var2)), sg2 = sqrt(fmax(kMinVarGradEI, var2));
   double accA = 0.0, accM1 = 0.0, accV1 = 0.0, accM2 = 0.0, accV2 = 0.0;
   double carryP = 0.0, carryM = 0.0, carryV = 0.0;  // the left edge of strip 0: psi_1(-infinity) = 0
   for (int s0 = 0; s0 <= n; s0 += 64) {
@@ -374,21 +359,16 @@ __global__ __launch_bounds__(256) void ehvi1_combine_kernel(int E, long C, int C
   grad_out[k] = sum / (double)E;
 }
 
-// ei1.hip's pass with ehvi1_cand_kernel and the two-sum gradient kernel
-void ehvi1_eval_pass(const Kg1Member& m, const double* Px, int nc, int c0, bool with_grad, hipStream_t s) {
+// ei1.hip's pass with ehvi1_cand_kernel and, in the place of ei1_grad_tail, the two-sum gradient kernel behind the same L'^-T
+void cand_step(const Kg1Member& m, int nc, int c0, bool with_grad, hipStream_t s) {
+  launch_kernel_ens<ehvi1_cand_kernel_body, 256>(ehvi1_cand_kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, s, m.gp->N + m.p, m.ld,
+                                                 nc, c0, m.C, m.gp->cp, with_grad ? 1 : 0, (const double*)m.dMuh, (const double*)m.dVx,
+                                                 m.dKg, m.dT);
+}
+
+void grad_tail(const Kg1Member& m, const double* Px, int nc, int c0, hipStream_t s) {
   GpDev& gp = *m.gp;
-  if (nc < 1 || nc > m.widest || c0 < 0 || c0 + nc > m.C || (with_grad && !m.with_grad))
-    throw Error(MOE_ERR_RUNTIME, "ehvi1_eval_pass: the pass does not fit the member's buffers");
-  const int N = gp.N, n = gp.n, d = gp.d, R = N + m.p, ld = m.ld;
-  const DerivList none = no_derivs();
-  launch_cov_build(gp.cp, gp.dX.p, n, gp.derivs, Px, nc, none, nullptr, gp.dE.p, N, 0, s);
-  tri_cols(gp, 'N', nc, gp.dE.p, N, m.dVx, ld, s);
-  launch_mean(gp.cp, gp.dX.p, n, gp.derivs, gp.dKinvY.p, Px, nc, gp.mean, false, m.dMuh, s);
-  if (m.p > 0) kg1_pending_rows(m, Px, m.dVx, nc, 0, m.p, s);
-  launch_kernel_ens<ehvi1_cand_kernel_body, 256>(ehvi1_cand_kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, s, R, ld, nc, c0, m.C,
-                                                 gp.cp, with_grad ? 1 : 0, (const double*)m.dMuh, (const double*)m.dVx, m.dKg, m.dT);
-  MOE_HIP_CHECK(hipGetLastError());
-  if (!with_grad) return;
+  const int d = gp.d, R = gp.N + m.p, ld = m.ld;
   const double* Xr = m.p > 0 ? m.dXe : gp.dX.p;
   const double* Kr = m.p > 0 ? m.dKe : gp.dKinvY.p;
   if (m.p > 0) kg1_pending_back(m, nc, s);
@@ -401,8 +381,7 @@ void ehvi1_eval_pass(const Kg1Member& m, const double* Px, int nc, int c0, bool 
 }
 
 void ehvi1_eval_points(const Kg1Member& m, const double* Px, const double*, int C, bool with_grad, hipStream_t s) {
-  const int dp = m.gp->dp;
-  for (int c0 = 0; c0 < C; c0 += m.per_pass) ehvi1_eval_pass(m, Px + (size_t)c0 * dp, std::min(m.per_pass, C - c0), c0, with_grad, s);
+  ei1_eval_passes(m, Px, C, with_grad, s, "ehvi1_eval_pass", cand_step, grad_tail);
 }
 
 // EI's layout with two result sets: dKg [mu C | var C], dGrad [grad mu C d | grad var C d]
@@ -461,21 +440,13 @@ void combine(const Kg1Ensemble& T, int C, double* value_out, double* grad_out) {
   MOE_HIP_CHECK(hipGetLastError());
 }
 
-// No sets, no fidelity coordinates, no incumbents; groups of two sub-members under the strip rule, the members' own values kept
-Kg1Objective objective(const std::vector<double>& zeros, const Ehvi1Call& call) {
-  Kg1Objective o{0, nullptr, nullptr, zeros.data(), member, ehvi1_eval_points, nullptr, all_extended, pick_appended, nullptr, 0, 2, combine};
-  o.client = &call;
-  o.group_values = true;
-  return o;
-}
-
 void check_member(const GpDev& g, const GpDev&, size_t e, int) {
   if (g.g != 0)
     throw Error(MOE_ERR_INVALID_VALUE, "the expected hypervolume improvement takes GPs without derivative observations", g.g, 0,
                 (double)e);
 }
 
-void check_members(const std::vector<GpDev*>& gps, int pending_room) {
+void check_members(const Kg1Objective&, const std::vector<GpDev*>& gps, int pending_room) {
   kg1_check_members(gps, 0, check_member);
   if (pending_room > kKg1MaxPending)
     throw Error(MOE_ERR_BOUNDS, "pending points (num_being_sampled + num_to_sample - 1) must fit 64 extension rows", pending_room, 0,
@@ -483,6 +454,25 @@ void check_members(const std::vector<GpDev*>& gps, int pending_room) {
 }
 
 }  // namespace
+
+// No sets, no fidelity coordinates, no incumbents (the members' best values are zeros, kept by the call); groups of two sub-members
+// under the strip rule, the members' own values kept
+Kg1Call ehvi1_call(int num_mcmc, const double* reference_point, const double* front, int num_front) {
+  Kg1Call call;
+  call.doubles.assign(2 * (size_t)num_mcmc, 0.0);
+  call.client = std::make_shared<const Ehvi1Call>(Ehvi1Call{front, num_front, reference_point[0], reference_point[1]});
+  call.o.best_so_far = call.doubles.data();
+  call.o.member = member;
+  call.o.eval_points = ehvi1_eval_points;
+  call.o.all_extended = all_extended;
+  call.o.pick_appended = pick_appended;
+  call.o.group = 2;
+  call.o.combine = combine;
+  call.o.client = call.client.get();
+  call.o.group_values = true;
+  call.check_members = check_members;
+  return call;
+}
 
 void check_ehvi_num_mcmc(int num_mcmc) {
   if (num_mcmc < 1 || num_mcmc > kEhviMaxMembers)
@@ -506,39 +496,6 @@ void check_ehvi_front(const double* reference_point, const double* front, int nu
                   "non-dominated (the second objective descending)",
                   i, 0, 0);
   }
-}
-
-void ehvi_mcmc_on_device(const std::vector<GpDev*>& gps, const double* reference_point, const double* front, int num_front,
-                         const double* pts, int C, bool want_grad, double* value_out, double* grad_out, double* member_values_out,
-                         const double* pending, int num_pending) {
-  check_members(gps, num_pending);
-  const Ehvi1Call call{front, num_front, reference_point[0], reference_point[1]};
-  const std::vector<double> zeros(gps.size(), 0.0);
-  kg1_ensemble_evaluate(objective(zeros, call), gps, pts, C, want_grad, value_out, grad_out, pending, num_pending, member_values_out);
-}
-
-void ehvi_mcmc_multistart(const std::vector<GpDev*>& gps, const double* reference_point, const double* front, int num_front,
-                          const moe_gd_params_t& outer, const double* domain_bounds, const double* starts, int num_starts,
-                          int do_gradient_ascent, double* best_point, double* best_value, int* found, double* start_values,
-                          int* kept_index, double* end_points, double* end_values, double* path, int* steps_taken,
-                          const double* pending, int num_pending) {
-  check_members(gps, num_pending);
-  const Ehvi1Call call{front, num_front, reference_point[0], reference_point[1]};
-  const std::vector<double> zeros(gps.size(), 0.0);
-  kg1_ensemble_multistart(objective(zeros, call), gps, outer, domain_bounds, starts, num_starts, do_gradient_ascent, best_point,
-                          best_value, found, start_values, kept_index, end_points, end_values, path, steps_taken, pending, num_pending);
-}
-
-// q points greedily: a round appends the pick's row to every sub-member's extension and its believed outcome to every member's front
-void ehvi_mcmc_suggest(const std::vector<GpDev*>& gps, const double* reference_point, const double* front, int num_front,
-                       const moe_gd_params_t& outer, const double* domain_bounds, const double* starts, int num_starts,
-                       int do_gradient_ascent, const double* pending, int num_pending, int num_to_sample, double* best_points,
-                       double* best_values, int* found) {
-  check_members(gps, num_pending + num_to_sample - 1);
-  const Ehvi1Call call{front, num_front, reference_point[0], reference_point[1]};
-  const std::vector<double> zeros(gps.size(), 0.0);
-  kg1_ensemble_suggest(objective(zeros, call), gps, outer, domain_bounds, starts, num_starts, do_gradient_ascent, pending, num_pending,
-                       num_to_sample, best_points, best_values, found);
 }
 
 }  // namespace moe

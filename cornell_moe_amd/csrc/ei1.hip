@@ -3,8 +3,8 @@
 // batches, on the device (moe_ei_analytic_mcmc, moe_ei_analytic_mcmc_multistart, moe_ei_analytic_mcmc_suggest): the EI twin of
 // kg1_opt.hip.  The staging, the ascent and the drivers of the three entry points are the shared ones of kg1_ascent.hip (declared in
 // kg1_ascent.hpp), the pending-row extension is kg1_pending.hip's; this file keeps the kernels, a member's layout and chain, the
-// believed best, the row bound and the description of the objective, and lends the layout, the members' check and the gradient's tail
-// to gibbon1.hip (ei1.hpp).
+// believed best, the row bound and the description of the call (ei1_call), and lends the layout, the members' check, the pass over
+// the candidates and the gradient's tail to gibbon1.hip, cei1.hip and ehvi1.hip (ei1.hpp).
 //
 // Member e: posterior mean mu_e, posterior covariance of the latent function conditioned on the pending points P with the member's
 // noise on P's diagonal (the Kriging-believer fantasy: the mean is left alone), believed best b'_e = min(b_e, min_j mu_e(P_j)).  With
@@ -42,6 +42,7 @@
 #include <algorithm>
 #include <cfloat>
 
+#include "acq1_device.hpp"
 #include "device_cov.hpp"
 #include "ei1.hpp"
 #include "kg1_ascent.hpp"
@@ -49,16 +50,6 @@
 namespace moe {
 
 namespace {
-
-constexpr double kMinVarEI = DBL_MIN;                                  // gpp_math.hpp:1316
-constexpr double kMinVarGradEI = 150.0 * DBL_EPSILON * DBL_EPSILON;  // gpp_math.hpp:1323
-
-__device__ __forceinline__ double ei1_pdf(double x) { return 0.3989422804014326779399460599343818684759 * exp(-0.5 * x * x); }
-// Phi through erfc on the side of x's sign: no cancellation in either tail
-__device__ __forceinline__ double ei1_cdf(double x) {
-  const double r = 0.7071067811865475244008443621048490392848;
-  return (x <= 0.0) ? 0.5 * erfc(-x * r) : 1.0 - 0.5 * erfc(x * r);
-}
 
 // b' = min(b, mu(P_0), ..., mu(P_count-1)); first == 0: b is the believed best as it stands (a greedy batch's next pick joins)
 __global__ void ei1_best_kernel(double b, int first, const double* __restrict__ mu, int count, double* __restrict__ out) {
@@ -68,35 +59,26 @@ __global__ void ei1_best_kernel(double b, int first, const double* __restrict__ 
   *out = v;
 }
 
-// One wavefront per candidate.  var = k(x, x) - sum_r v_r^2 as ONE fused multiply-add chain over the R = N + p rows in order: the
-// lanes load 64 rows at a time and every lane runs the whole chain on the broadcast entries (rows past R add exact zeros).  Then the
-// scalars, and with want_grad the column (phi(c_g) / sigma_g) v'_x for the transposed triangular product.
+// One wavefront per candidate.  var = k(x, x) - sum_r v_r^2 as ONE fused multiply-add chain over the R = N + p rows in order
+// (row_chain).  Then the scalars, and with want_grad the column (phi(c_g) / sigma_g) v'_x for the transposed triangular product.
 struct ei1_cand_kernel_body {
   static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, int R, int ld, int ncols, int col0, const CovParams& cp, int want_grad, const double* __restrict__ best, const double* __restrict__ mu, const double* __restrict__ Vx, double* __restrict__ ei_out, double* __restrict__ cdf_out, double* __restrict__ T) {
     const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (c >= ncols) return;
     const double* v = Vx + (size_t)c * ld;
-    double ss = 0.0;
-    for (int r0 = 0; r0 < R; r0 += 64) {
-      const double x = (r0 + lane < R) ? v[r0 + lane] : 0.0;
-  #pragma unroll
-      for (int i = 0; i < 64; ++i) {
-        const double xi = __shfl(x, i, 64);
-        ss = fma(xi, xi, ss);
-      }
-    }
+    const double ss = row_chain(v, 0, R, lane, 0.0);
     const double var = radial_scalars(cp.type, cp.alpha, 0.0).base - ss;
     const double t = *best - mu[c];
     if (lane == 0) {
       const double sigma = sqrt(fmax(kMinVarEI, var));
       const double cc = t / sigma;
-      ei_out[col0 + c] = fmax(0.0, t * ei1_cdf(cc) + sigma * ei1_pdf(cc));
+      ei_out[col0 + c] = fmax(0.0, t * normal_cdf(cc) + sigma * normal_pdf(cc));
     }
     if (want_grad == 0) return;
     const double sg = sqrt(fmax(kMinVarGradEI, var));
     const double cg = t / sg;
-    const double w = ei1_pdf(cg) / sg;
-    if (lane == 0) cdf_out[c] = ei1_cdf(cg);
+    const double w = normal_pdf(cg) / sg;
+    if (lane == 0) cdf_out[c] = normal_cdf(cg);
     double* tc = T + (size_t)c * ld;
     for (int r = lane; r < R; r += 64) tc[r] = w * v[r];
   }
@@ -278,35 +260,40 @@ void ei1_grad_tail(const Kg1Member& m, const double* Px, int nc, int c0, hipStre
   MOE_HIP_CHECK(hipGetLastError());
 }
 
+void ei1_eval_passes(const Kg1Member& m, const double* Px, int C, bool with_grad, hipStream_t s, const char* who, Ei1CandStep cand,
+                     Ei1PassStep grad_tail) {
+  GpDev& gp = *m.gp;
+  const int N = gp.N, n = gp.n, dp = gp.dp;
+  const DerivList none = no_derivs();  // (the candidate is a function value)
+  for (int c0 = 0; c0 < C; c0 += m.per_pass) {
+    const int nc = std::min(m.per_pass, C - c0);
+    const double* P = Px + (size_t)c0 * dp;
+    if (nc < 1 || nc > m.widest || c0 < 0 || c0 + nc > m.C || (with_grad && !m.with_grad))
+      throw Error(MOE_ERR_RUNTIME, std::string(who) + ": the pass does not fit the member's buffers");
+    launch_cov_build(gp.cp, gp.dX.p, n, gp.derivs, P, nc, none, nullptr, gp.dE.p, N, 0, s);
+    tri_cols(gp, 'N', nc, gp.dE.p, N, m.dVx, m.ld, s);
+    launch_mean(gp.cp, gp.dX.p, n, gp.derivs, gp.dKinvY.p, P, nc, gp.mean, false, m.dMuh, s);
+    if (m.p > 0) kg1_pending_rows(m, P, m.dVx, nc, 0, m.p, s);
+    cand(m, nc, c0, with_grad, s);
+    MOE_HIP_CHECK(hipGetLastError());
+    if (with_grad) grad_tail(m, P, nc, c0, s);
+  }
+}
+
 namespace {
 
-void ei1_eval_pass(const Kg1Member& m, const double* Px, int nc, int c0, bool with_grad, hipStream_t s) {
-  GpDev& gp = *m.gp;
-  if (nc < 1 || nc > m.widest || c0 < 0 || c0 + nc > m.C || (with_grad && !m.with_grad))
-    throw Error(MOE_ERR_RUNTIME, "ei1_eval_pass: the pass does not fit the member's buffers");
-  const int N = gp.N, n = gp.n, R = N + m.p, ld = m.ld;
-  const DerivList none = no_derivs();  // (the candidate is a function value)
-  const dim3 b256(256);
-  launch_cov_build(gp.cp, gp.dX.p, n, gp.derivs, Px, nc, none, nullptr, gp.dE.p, N, 0, s);
-  tri_cols(gp, 'N', nc, gp.dE.p, N, m.dVx, ld, s);
-  launch_mean(gp.cp, gp.dX.p, n, gp.derivs, gp.dKinvY.p, Px, nc, gp.mean, false, m.dMuh, s);
-  if (m.p > 0) kg1_pending_rows(m, Px, m.dVx, nc, 0, m.p, s);
-  launch_kernel_ens<ei1_cand_kernel_body, 256>(ei1_cand_kernel, dim3((unsigned)((nc + 3) / 4)), b256, 0, s, R, ld, nc, c0, gp.cp,
-                                               with_grad ? 1 : 0, (const double*)m.dBp, (const double*)m.dMuh, (const double*)m.dVx,
-                                               m.dKg, m.dScal, m.dT);
-  MOE_HIP_CHECK(hipGetLastError());
-  if (!with_grad) return;
-  ei1_grad_tail(m, Px, nc, c0, s);
+void cand_step(const Kg1Member& m, int nc, int c0, bool with_grad, hipStream_t s) {
+  launch_kernel_ens<ei1_cand_kernel_body, 256>(ei1_cand_kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, s, m.gp->N + m.p, m.ld, nc,
+                                               c0, m.gp->cp, with_grad ? 1 : 0, (const double*)m.dBp, (const double*)m.dMuh,
+                                               (const double*)m.dVx, m.dKg, m.dScal, m.dT);
 }
 
 // (Ph: the staging's second view of the points, the same as Px where there are no fidelity coordinates)
 void ei1_eval_points(const Kg1Member& m, const double* Px, const double*, int C, bool with_grad, hipStream_t s) {
-  const int dp = m.gp->dp;
-  for (int c0 = 0; c0 < C; c0 += m.per_pass) ei1_eval_pass(m, Px + (size_t)c0 * dp, std::min(m.per_pass, C - c0), c0, with_grad, s);
+  ei1_eval_passes(m, Px, C, with_grad, s, "ei1_eval_pass", cand_step, ei1_grad_tail);
 }
 
-// the members' own check (kg1_ascent.hpp: kg1_check_members); ei1_check_members adds the room for pending_room pending points (the
-// caller's and a greedy batch's picks)
+// the members' own check (kg1_ascent.hpp: kg1_check_members); ei1_check_members adds the room for the call's pending points
 void check_member(const GpDev& g, const GpDev& g0, size_t e, int) {
   if (g.g != g0.g || !std::equal(g.derivs.idx, g.derivs.idx + g.g, g0.derivs.idx))
     throw Error(MOE_ERR_INVALID_VALUE,
@@ -339,15 +326,22 @@ void pick_appended(Kg1Ensemble& T) {
   join_believed_best(T, T.p, 1, false);
 }
 
-// No sets and no fidelity coordinates: the upload is [EI pointers E | grad pointers E | bounds 2 d | points C dp | pending points
-// pcap dp]; the extensions of all members first, then their believed bests.
-Kg1Objective objective(const double* best_so_far) {
-  return Kg1Objective{0, nullptr, nullptr, best_so_far, member, ei1_eval_points, nullptr, all_extended, pick_appended, nullptr, 0};
-}
-
 }  // namespace
 
-void ei1_check_members(const std::vector<GpDev*>& gps, int pending_room) {
+// No sets and no fidelity coordinates: the upload is [EI pointers E | grad pointers E | bounds 2 d | points C dp | pending points
+// pcap dp]; the extensions of all members first, then their believed bests.
+Kg1Call ei1_call(const double* best_so_far) {
+  Kg1Call call;
+  call.o.best_so_far = best_so_far;
+  call.o.member = member;
+  call.o.eval_points = ei1_eval_points;
+  call.o.all_extended = all_extended;
+  call.o.pick_appended = pick_appended;
+  call.check_members = ei1_check_members;
+  return call;
+}
+
+void ei1_check_members(const Kg1Objective&, const std::vector<GpDev*>& gps, int pending_room) {
   kg1_check_members(gps, 0, check_member);
   const int g1 = 1 + gps[0]->g;
   if ((long)pending_room * g1 > kKg1MaxPending)
@@ -366,32 +360,6 @@ int ei1_pass_size(int N) {
 void check_ei_analytic_mcmc_shapes(int num_mcmc, int num_points) {
   if (num_mcmc < 1 || num_mcmc > 1024) throw Error(MOE_ERR_BOUNDS, "num_mcmc must be between 1 and 1024", num_mcmc, 1, 1024);
   if (num_points < 1) throw Error(MOE_ERR_BOUNDS, "the number of candidates must be positive", num_points, 1, 1e9);
-}
-
-void ei_analytic_mcmc_on_device(const std::vector<GpDev*>& gps, const double* best_so_far, const double* pts, int C, bool want_grad,
-                                double* ei_out, double* grad_out, const double* pending, int num_pending) {
-  ei1_check_members(gps, num_pending);
-  kg1_ensemble_evaluate(objective(best_so_far), gps, pts, C, want_grad, ei_out, grad_out, pending, num_pending);
-}
-
-void ei_analytic_mcmc_multistart(const std::vector<GpDev*>& gps, const moe_gd_params_t& outer, const double* domain_bounds,
-                                 const double* best_so_far, const double* starts, int num_starts, int do_gradient_ascent,
-                                 double* best_point, double* best_value, int* found, double* start_values, int* kept_index,
-                                 double* end_points, double* end_values, double* path, int* steps_taken, const double* pending,
-                                 int num_pending) {
-  ei1_check_members(gps, num_pending);
-  kg1_ensemble_multistart(objective(best_so_far), gps, outer, domain_bounds, starts, num_starts, do_gradient_ascent, best_point,
-                          best_value, found, start_values, kept_index, end_points, end_values, path, steps_taken, pending, num_pending);
-}
-
-// q points greedily: a round appends one column to every member's extension and one value mu_e(pick) to its believed best.
-void ei_analytic_mcmc_suggest(const std::vector<GpDev*>& gps, const moe_gd_params_t& outer, const double* domain_bounds,
-                              const double* best_so_far, const double* starts, int num_starts, int do_gradient_ascent,
-                              const double* pending, int num_pending, int num_to_sample, double* best_points, double* best_values,
-                              int* found) {
-  ei1_check_members(gps, num_pending + num_to_sample - 1);
-  kg1_ensemble_suggest(objective(best_so_far), gps, outer, domain_bounds, starts, num_starts, do_gradient_ascent, pending, num_pending,
-                       num_to_sample, best_points, best_values, found);
 }
 
 }  // namespace moe

@@ -1,9 +1,9 @@
 // cornell_moe_amd/csrc/gibbon1.hip -- the min-value entropy acquisition GIBBON (Moss, Leslie, Gonzalez & Rayson, JMLR 2021: the
 // max-value entropy search of Wang & Jegelka 2017 made right under observation noise and for batches), for minimisation, averaged over
 // a hyper-parameter ensemble, with pending points, its multistart ascent and greedy q-point batches, on the device (moe_gibbon_mcmc,
-// moe_gibbon_mcmc_multistart, moe_gibbon_mcmc_suggest): the third client of kg1_ascent.hip's staging, ascent and drivers.  The
-// pending-row extension is kg1_pending.hip's, the member's layout, the members' check and the gradient's tail are ei1.hip's (ei1.hpp);
-// this file keeps the candidate kernel, a member's chain and the description of the objective.
+// moe_gibbon_mcmc_multistart, moe_gibbon_mcmc_suggest): a client of kg1_ascent.hip's staging, ascent and drivers.  The pending-row
+// extension is kg1_pending.hip's, the member's layout, the members' check, the pass and the gradient's tail are ei1.hip's (ei1.hpp);
+// this file keeps the candidate kernel and the description of the call (gibbon1_call).
 //
 // Member e: posterior mean mu, noise sigma^2 = noise_variance[0], K samples m_k of the global minimum VALUE (the caller's), pending
 // points P (the member's noise on P's diagonal, the mean left alone; 1 + g rows per point under derivative observations).  With
@@ -41,6 +41,7 @@
 #include <cfloat>
 #include <cmath>
 
+#include "acq1_device.hpp"
 #include "device_cov.hpp"
 #include "ei1.hpp"
 #include "kg1_ascent.hpp"
@@ -49,47 +50,29 @@ namespace moe {
 
 namespace {
 
-constexpr double kMinVarGibbon = DBL_MIN;                                  // the value's floor (ei1.hip: kMinVarEI)
-constexpr double kMinVarGradGibbon = 150.0 * DBL_EPSILON * DBL_EPSILON;  // the gradient's (ei1.hip: kMinVarGradEI)
-
 // r = phi / Phi at gamma and q = clamp(r (gamma + r), 0, 1).  erfcx overflows to +infinity from gamma ~ 37 on: r = q = 0 exactly.
 __device__ __forceinline__ void gibbon1_ratio(double gamma, double& r, double& q) {
   r = 0.7978845608028653558798921198687637369517 / erfcx(-gamma * 0.7071067811865475244008443621048490392848);
   q = fmin(1.0, fmax(0.0, r * (gamma + r)));
 }
 
-// One wavefront per candidate.  The chain over the rows is ei1_cand_kernel's (the lanes load 64 rows at a time and every lane runs
-// the whole chain on the broadcast entries; rows past a part's end add exact zeros), run over the member's N rows, tapped, and
-// carried on over the extension's rows.  Then the K terms: lane l takes k = l, l + 64, ..., the four running sums go through one
-// butterfly, lane 0 writes the value and -A, all lanes write the column [2 (B0 + Bc) v_x ; 2 Bc r_x].
+// One wavefront per candidate.  The chain over the rows is ei1_cand_kernel's (row_chain; rows past a part's end add exact zeros),
+// run over the member's N rows, tapped, and carried on over the extension's rows.  Then the K terms: lane l takes k = l, l + 64,
+// ..., the four running sums go through one butterfly, lane 0 writes the value and -A, all lanes write the column
+// [2 (B0 + Bc) v_x ; 2 Bc r_x].
 struct gibbon1_cand_kernel_body {
   static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, int N, int R, int ld, int ncols, int col0, const CovParams& cp, int want_grad, double noise, int K, const double* __restrict__ mins, const double* __restrict__ mu, const double* __restrict__ Vx, double* __restrict__ val_out, double* __restrict__ na_out, double* __restrict__ T) {
     const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (c >= ncols) return;
     const double* v = Vx + (size_t)c * ld;
-    double ss = 0.0;
-    for (int r0 = 0; r0 < N; r0 += 64) {
-      const double x = (r0 + lane < N) ? v[r0 + lane] : 0.0;
-  #pragma unroll
-      for (int i = 0; i < 64; ++i) {
-        const double xi = __shfl(x, i, 64);
-        ss = fma(xi, xi, ss);
-      }
-    }
+    double ss = row_chain(v, 0, N, lane, 0.0);
     const double base = radial_scalars(cp.type, cp.alpha, 0.0).base;
     const double var0 = base - ss;
-    for (int r0 = N; r0 < R; r0 += 64) {
-      const double x = (r0 + lane < R) ? v[r0 + lane] : 0.0;
-  #pragma unroll
-      for (int i = 0; i < 64; ++i) {
-        const double xi = __shfl(x, i, 64);
-        ss = fma(xi, xi, ss);
-      }
-    }
+    ss = row_chain(v, N, R, lane, ss);
     const double varc = base - ss;
     const bool pending = R > N;
-    const double s0 = fmax(kMinVarGibbon, var0), sc = fmax(kMinVarGibbon, varc);
-    const double s0g = fmax(kMinVarGradGibbon, var0), scg = fmax(kMinVarGradGibbon, varc);
+    const double s0 = fmax(kMinVarEI, var0), sc = fmax(kMinVarEI, varc);
+    const double s0g = fmax(kMinVarGradEI, var0), scg = fmax(kMinVarGradEI, varc);
     const double sigma0 = sqrt(s0), rho2 = s0 / (s0 + noise);
     const double sigma0g = sqrt(s0g), rho2g = s0g / (s0g + noise);
     const bool floored = s0g != s0;  // (the gradient's factors then take their own gamma and rho^2)
@@ -145,26 +128,17 @@ __global__ __launch_bounds__(256) void gibbon1_cand_kernel(int N, int R, int ld,
 }
 
 // ei1.hip's pass with gibbon1_cand_kernel in the place of ei1_cand_kernel (dScal holds -A)
-void gibbon1_eval_pass(const Kg1Member& m, const double* Px, int nc, int c0, bool with_grad, hipStream_t s) {
-  GpDev& gp = *m.gp;
-  if (nc < 1 || nc > m.widest || c0 < 0 || c0 + nc > m.C || (with_grad && !m.with_grad) || m.dExtra == nullptr || m.nExtra < 1)
-    throw Error(MOE_ERR_RUNTIME, "gibbon1_eval_pass: the pass does not fit the member's buffers");
-  const int N = gp.N, n = gp.n, R = N + m.p, ld = m.ld;
-  const DerivList none = no_derivs();  // (the candidate is a function value)
-  launch_cov_build(gp.cp, gp.dX.p, n, gp.derivs, Px, nc, none, nullptr, gp.dE.p, N, 0, s);
-  tri_cols(gp, 'N', nc, gp.dE.p, N, m.dVx, ld, s);
-  launch_mean(gp.cp, gp.dX.p, n, gp.derivs, gp.dKinvY.p, Px, nc, gp.mean, false, m.dMuh, s);
-  if (m.p > 0) kg1_pending_rows(m, Px, m.dVx, nc, 0, m.p, s);
-  launch_kernel_ens<gibbon1_cand_kernel_body, 256>(gibbon1_cand_kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, s, N, R, ld, nc, c0,
-                                                   gp.cp, with_grad ? 1 : 0, gp.noise[0], m.nExtra, m.dExtra, (const double*)m.dMuh,
-                                                   (const double*)m.dVx, m.dKg, m.dScal, m.dT);
-  MOE_HIP_CHECK(hipGetLastError());
-  if (with_grad) ei1_grad_tail(m, Px, nc, c0, s);
+void cand_step(const Kg1Member& m, int nc, int c0, bool with_grad, hipStream_t s) {
+  const GpDev& gp = *m.gp;
+  launch_kernel_ens<gibbon1_cand_kernel_body, 256>(gibbon1_cand_kernel, dim3((unsigned)((nc + 3) / 4)), dim3(256), 0, s, gp.N, gp.N + m.p,
+                                                   m.ld, nc, c0, gp.cp, with_grad ? 1 : 0, gp.noise[0], m.nExtra, m.dExtra,
+                                                   (const double*)m.dMuh, (const double*)m.dVx, m.dKg, m.dScal, m.dT);
 }
 
 void gibbon1_eval_points(const Kg1Member& m, const double* Px, const double*, int C, bool with_grad, hipStream_t s) {
-  const int dp = m.gp->dp;
-  for (int c0 = 0; c0 < C; c0 += m.per_pass) gibbon1_eval_pass(m, Px + (size_t)c0 * dp, std::min(m.per_pass, C - c0), c0, with_grad, s);
+  if (C > 0 && (m.dExtra == nullptr || m.nExtra < 1))  // (the staging has not laid out the member's min-values)
+    throw Error(MOE_ERR_RUNTIME, "gibbon1_eval_pass: the pass does not fit the member's buffers");
+  ei1_eval_passes(m, Px, C, with_grad, s, "gibbon1_eval_pass", cand_step, ei1_grad_tail);
 }
 
 // EI's layout (an empty set, no best value); the staging adds the address of the member's min-values (Kg1Member::dExtra)
@@ -177,13 +151,20 @@ void pick_appended(Kg1Ensemble& T) {
   for (Kg1Member& m : T.mem) kg1_pending_append(m, 1, false, T.z);
 }
 
+}  // namespace
+
 // No sets, no fidelity coordinates and no believed best: the upload is [value pointers E | grad pointers E | bounds 2 d | points
 // C dp | pending points pcap dp | min-values E K].
-Kg1Objective objective(const double* min_values, int num_min_values) {
-  return Kg1Objective{0, nullptr, nullptr, nullptr, member, gibbon1_eval_points, nullptr, nullptr, pick_appended, min_values, num_min_values};
+Kg1Call gibbon1_call(const double* min_values, int num_min_values) {
+  Kg1Call call;
+  call.o.member = member;
+  call.o.eval_points = gibbon1_eval_points;
+  call.o.pick_appended = pick_appended;
+  call.o.member_extra = min_values;
+  call.o.num_member_extra = num_min_values;
+  call.check_members = ei1_check_members;
+  return call;
 }
-
-}  // namespace
 
 void check_gibbon_min_values(const double* min_values, int num_mcmc, int num_min_values) {
   if (num_min_values < 1 || num_min_values > kGibbonMaxMinValues)
@@ -193,34 +174,6 @@ void check_gibbon_min_values(const double* min_values, int num_mcmc, int num_min
       const double v = min_values[(size_t)e * num_min_values + k];
       if (!std::isfinite(v)) throw Error(MOE_ERR_INVALID_VALUE, "min_values must be finite", v, e, k);
     }
-}
-
-void gibbon_mcmc_on_device(const std::vector<GpDev*>& gps, const double* min_values, int num_min_values, const double* pts, int C,
-                           bool want_grad, double* value_out, double* grad_out, const double* pending, int num_pending) {
-  ei1_check_members(gps, num_pending);
-  kg1_ensemble_evaluate(objective(min_values, num_min_values), gps, pts, C, want_grad, value_out, grad_out, pending, num_pending);
-}
-
-void gibbon_mcmc_multistart(const std::vector<GpDev*>& gps, const moe_gd_params_t& outer, const double* domain_bounds,
-                            const double* min_values, int num_min_values, const double* starts, int num_starts, int do_gradient_ascent,
-                            double* best_point, double* best_value, int* found, double* start_values, int* kept_index,
-                            double* end_points, double* end_values, double* path, int* steps_taken, const double* pending,
-                            int num_pending) {
-  ei1_check_members(gps, num_pending);
-  kg1_ensemble_multistart(objective(min_values, num_min_values), gps, outer, domain_bounds, starts, num_starts, do_gradient_ascent,
-                          best_point, best_value, found, start_values, kept_index, end_points, end_values, path, steps_taken, pending,
-                          num_pending);
-}
-
-// q points greedily: a round appends the pick's rows to every member's extension, and the bracket of the next round is the exact
-// increment of the batch term.
-void gibbon_mcmc_suggest(const std::vector<GpDev*>& gps, const moe_gd_params_t& outer, const double* domain_bounds,
-                         const double* min_values, int num_min_values, const double* starts, int num_starts, int do_gradient_ascent,
-                         const double* pending, int num_pending, int num_to_sample, double* best_points, double* best_values,
-                         int* found) {
-  ei1_check_members(gps, num_pending + num_to_sample - 1);
-  kg1_ensemble_suggest(objective(min_values, num_min_values), gps, outer, domain_bounds, starts, num_starts, do_gradient_ascent, pending,
-                       num_pending, num_to_sample, best_points, best_values, found);
 }
 
 }  // namespace moe

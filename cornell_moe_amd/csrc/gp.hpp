@@ -293,104 +293,42 @@ void kg1_eval_pass(const Kg1Member& m, const double* Px, const double* Ph, int n
 // ... the same for C <= m.C candidates, pass after pass of m.per_pass
 void kg1_eval_points(const Kg1Member& m, const double* Px, const double* Ph, int C, bool with_grad, hipStream_t s);
 void kg1_clear_fail(int* fail, int count, hipStream_t s);  // INT_MAX: no candidate has failed
-// kg1_opt.hip: the ensemble average (moe_kg_discrete_mcmc) and its multistart ascent (moe_kg_discrete_mcmc_multistart); the caller
-// has made the checks that need no handle (check_kg_discrete_ensemble_shapes).  discrete_all: the members' sets back to back.
+// The ensemble forms of the one-point acquisitions: evaluate at points, multistart ascent and greedy batches of each, with pending
+// points [num_pending][dim] by the Kriging-believer fantasy of kg1_pending.hip.  Every client describes its call in one function
+// (kg1_ascent.hpp: kg1_call, ei1_call, gibbon1_call, cei1_call, ehvi1_call) and the three drivers of kg1_ascent.hip run it; here are
+// the checks that need no handle, which the entry points make first, and the limits.
+// kg1_opt.hip: the discretised knowledge gradient (moe_kg_discrete_mcmc*).  discrete_all: the members' sets back to back.
 void check_kg_discrete_ensemble_shapes(int num_mcmc, int num_fidelity, const int* num_discrete, int num_points);
-void kg_discrete_mcmc_on_device(const std::vector<GpDev*>& gps, int num_fidelity, const double* discrete_all, const int* num_discrete,
-                                const double* best_so_far, const double* pts, int C, bool want_grad, double* kg_out, double* grad_out,
-                                const double* pending = nullptr, int num_pending = 0);
-void kg_discrete_mcmc_multistart(const std::vector<GpDev*>& gps, int num_fidelity, const moe_gd_params_t& outer,
-                                 const double* domain_bounds, const double* discrete_all, const int* num_discrete,
-                                 const double* best_so_far, const double* starts, int num_starts, int do_gradient_ascent,
-                                 double* best_point, double* best_value, int* found, double* start_values, int* kept_index,
-                                 double* end_points, double* end_values, double* path, int* steps_taken,
-                                 const double* pending = nullptr, int num_pending = 0);
-// ... with pending points [num_pending][dim] (kg1_pending.hip; 0: the launches of before), and num_to_sample points greedily, each
-// round the ascent with the points picked so far appended to the pending ones; check_kg_discrete_pending: what needs no handle.
+// pending points (0: the launches of before) and num_to_sample points greedily, each round the ascent with the points picked so
+// far appended to the pending ones
 void check_kg_discrete_pending(const double* pending, int num_pending, int num_to_sample);
-void kg_discrete_mcmc_suggest(const std::vector<GpDev*>& gps, int num_fidelity, const moe_gd_params_t& outer,
-                              const double* domain_bounds, const double* discrete_all, const int* num_discrete,
-                              const double* best_so_far, const double* starts, int num_starts, int do_gradient_ascent,
-                              const double* pending, int num_pending, int num_to_sample, double* best_points, double* best_values,
-                              int* found);
-// ei1.hip: the analytic one-point expected improvement averaged over an ensemble (moe_ei_analytic_mcmc), its multistart ascent
-// (moe_ei_analytic_mcmc_multistart) and greedy batches (moe_ei_analytic_mcmc_suggest), with pending points [num_pending][dim] by the
-// Kriging-believer fantasy of kg1_pending.hip; the caller has made the checks that need no handle (check_ei_analytic_mcmc_shapes,
-// check_kg_discrete_pending).  Candidates go through in passes of ei1_pass_size(N).  Members may carry derivative observations (one
-// observed-derivative list for all of them): a pending point then believes its value and those derivatives, 1 + g rows, and
-// (num_pending + num_to_sample - 1) (1 + g) <= kKg1MaxPending (MOE_ERR_BOUNDS after the handle checks).
+// ei1.hip: the analytic one-point expected improvement (moe_ei_analytic_mcmc*).  Candidates go through in passes of
+// ei1_pass_size(N).  Members may carry derivative observations (one observed-derivative list for all of them): a pending point
+// then believes its value and those derivatives, 1 + g rows, and (num_pending + num_to_sample - 1) (1 + g) <= kKg1MaxPending
+// (MOE_ERR_BOUNDS after the handle checks).
 int ei1_pass_size(int N);
 void check_ei_analytic_mcmc_shapes(int num_mcmc, int num_points);
-void ei_analytic_mcmc_on_device(const std::vector<GpDev*>& gps, const double* best_so_far, const double* pts, int C, bool want_grad,
-                                double* ei_out, double* grad_out, const double* pending, int num_pending);
-void ei_analytic_mcmc_multistart(const std::vector<GpDev*>& gps, const moe_gd_params_t& outer, const double* domain_bounds,
-                                 const double* best_so_far, const double* starts, int num_starts, int do_gradient_ascent,
-                                 double* best_point, double* best_value, int* found, double* start_values, int* kept_index,
-                                 double* end_points, double* end_values, double* path, int* steps_taken, const double* pending,
-                                 int num_pending);
-void ei_analytic_mcmc_suggest(const std::vector<GpDev*>& gps, const moe_gd_params_t& outer, const double* domain_bounds,
-                              const double* best_so_far, const double* starts, int num_starts, int do_gradient_ascent,
-                              const double* pending, int num_pending, int num_to_sample, double* best_points, double* best_values,
-                              int* found);
-// gibbon1.hip: the min-value entropy acquisition GIBBON averaged over an ensemble (moe_gibbon_mcmc), its multistart ascent
-// (moe_gibbon_mcmc_multistart) and greedy batches (moe_gibbon_mcmc_suggest): ei1.hip's three with the members' samples of the
+// gibbon1.hip: the min-value entropy acquisition GIBBON (moe_gibbon_mcmc*): ei1.hip's three with the members' samples of the
 // minimum value min_values [E][num_min_values] in the place of best_so_far; the same pending points, passes, derivative-observing
-// members and row limit.  check_gibbon_min_values: what needs no handle (the count, then every value finite).
+// members and row limit.  check_gibbon_min_values: the count, then every value finite.
 constexpr int kGibbonMaxMinValues = 1024;
 void check_gibbon_min_values(const double* min_values, int num_mcmc, int num_min_values);
-void gibbon_mcmc_on_device(const std::vector<GpDev*>& gps, const double* min_values, int num_min_values, const double* pts, int C,
-                           bool want_grad, double* value_out, double* grad_out, const double* pending, int num_pending);
-void gibbon_mcmc_multistart(const std::vector<GpDev*>& gps, const moe_gd_params_t& outer, const double* domain_bounds,
-                            const double* min_values, int num_min_values, const double* starts, int num_starts, int do_gradient_ascent,
-                            double* best_point, double* best_value, int* found, double* start_values, int* kept_index,
-                            double* end_points, double* end_values, double* path, int* steps_taken, const double* pending,
-                            int num_pending);
-void gibbon_mcmc_suggest(const std::vector<GpDev*>& gps, const moe_gd_params_t& outer, const double* domain_bounds,
-                         const double* min_values, int num_min_values, const double* starts, int num_starts, int do_gradient_ascent,
-                         const double* pending, int num_pending, int num_to_sample, double* best_points, double* best_values,
-                         int* found);
-// cei1.hip: the constrained expected improvement averaged over an ensemble (moe_ei_constrained_mcmc), its multistart ascent
-// (moe_ei_constrained_mcmc_multistart) and greedy batches (moe_ei_constrained_mcmc_suggest): ei1.hip's three over members of 1 + K
-// GPs each.  gps [E (1 + K)]: the sub-members ordered [e][role], role 0 the objective GP, role k constraint k (satisfied where
-// c_k <= thresholds[k - 1]); best_so_far [E] may hold +infinity.  check_ei_constrained_shapes: what needs no handle (K, the
-// product limit, the arrays K > 0 needs, finite thresholds, best_so_far neither NaN nor -infinity).  factors_out (may be NULL):
-// [E (1 + K)][C], the sub-members' factor values.
+// cei1.hip: the constrained expected improvement (moe_ei_constrained_mcmc*): ei1.hip's three over members of 1 + K GPs each.  The
+// GPs of a call [E (1 + K)] are the sub-members ordered [e][role], role 0 the objective GP, role k constraint k (satisfied where
+// c_k <= thresholds[k - 1]); best_so_far [E] may hold +infinity.  check_ei_constrained_shapes: K, the product limit, the arrays
+// K > 0 needs, finite thresholds, best_so_far neither NaN nor -infinity.  The members' own values of an evaluation are the
+// sub-members' factor values [E (1 + K)][C].
 constexpr int kCeiMaxConstraints = 8;
 void check_ei_constrained_shapes(int num_mcmc, int num_constraints, const void* constraint_gps, const double* thresholds,
                                  const double* best_so_far);
-void ei_constrained_mcmc_on_device(const std::vector<GpDev*>& gps, int num_constraints, const double* thresholds,
-                                   const double* best_so_far, const double* pts, int C, bool want_grad, double* value_out,
-                                   double* grad_out, double* factors_out, const double* pending, int num_pending);
-void ei_constrained_mcmc_multistart(const std::vector<GpDev*>& gps, int num_constraints, const double* thresholds,
-                                    const moe_gd_params_t& outer, const double* domain_bounds, const double* best_so_far,
-                                    const double* starts, int num_starts, int do_gradient_ascent, double* best_point, double* best_value,
-                                    int* found, double* start_values, int* kept_index, double* end_points, double* end_values,
-                                    double* path, int* steps_taken, const double* pending, int num_pending);
-void ei_constrained_mcmc_suggest(const std::vector<GpDev*>& gps, int num_constraints, const double* thresholds,
-                                 const moe_gd_params_t& outer, const double* domain_bounds, const double* best_so_far,
-                                 const double* starts, int num_starts, int do_gradient_ascent, const double* pending, int num_pending,
-                                 int num_to_sample, double* best_points, double* best_values, int* found);
-// ehvi1.hip: the two-objective expected hypervolume improvement averaged over an ensemble (moe_ehvi_mcmc), its multistart ascent
-// (moe_ehvi_mcmc_multistart) and greedy batches (moe_ehvi_mcmc_suggest): ei1.hip's three over members of two GPs each, gps [2 E]
-// ordered [e][objective], without derivative observations.  reference_point [2]; front [num_front][2] sorted by the first objective
-// ascending, mutually non-dominated, strictly inside the reference point.  check_ehvi_num_mcmc / check_ehvi_front: what needs no
-// handle.  member_values_out (may be NULL): [E][C], every member's own value A_e.
+// ehvi1.hip: the two-objective expected hypervolume improvement (moe_ehvi_mcmc*): ei1.hip's three over members of two GPs each,
+// the GPs of a call [2 E] ordered [e][objective], without derivative observations.  reference_point [2]; front [num_front][2]
+// sorted by the first objective ascending, mutually non-dominated, strictly inside the reference point.  The members' own values
+// of an evaluation are [E][C], every member's A_e.
 constexpr int kEhviMaxFront = 960;
 constexpr int kEhviMaxMembers = 512;
 void check_ehvi_num_mcmc(int num_mcmc);
 void check_ehvi_front(const double* reference_point, const double* front, int num_front);
-void ehvi_mcmc_on_device(const std::vector<GpDev*>& gps, const double* reference_point, const double* front, int num_front,
-                         const double* pts, int C, bool want_grad, double* value_out, double* grad_out, double* member_values_out,
-                         const double* pending, int num_pending);
-void ehvi_mcmc_multistart(const std::vector<GpDev*>& gps, const double* reference_point, const double* front, int num_front,
-                          const moe_gd_params_t& outer, const double* domain_bounds, const double* starts, int num_starts,
-                          int do_gradient_ascent, double* best_point, double* best_value, int* found, double* start_values,
-                          int* kept_index, double* end_points, double* end_values, double* path, int* steps_taken,
-                          const double* pending, int num_pending);
-void ehvi_mcmc_suggest(const std::vector<GpDev*>& gps, const double* reference_point, const double* front, int num_front,
-                       const moe_gd_params_t& outer, const double* domain_bounds, const double* starts, int num_starts,
-                       int do_gradient_ascent, const double* pending, int num_pending, int num_to_sample, double* best_points,
-                       double* best_values, int* found);
 // loo.hip: leave-one-out cross-validation on the GP's current factorisation, every one of the N = n (1 + g) scalar observations left
 // out by itself.  mean_out / var_out [n][1 + g]: the LOO predictive mean (function values in the caller's units) and variance.
 void loo_predict_on_device(GpDev& gp, double* mean_out, double* var_out);

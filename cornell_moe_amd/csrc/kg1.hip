@@ -39,6 +39,7 @@
 #include <cstring>
 #include <vector>
 
+#include "acq1_device.hpp"
 #include "device_cov.hpp"
 #include "gp.hpp"
 
@@ -130,8 +131,6 @@ __global__ __launch_bounds__(256) void kg1_slope_kernel(int N, int ld, int A, in
 __device__ __forceinline__ bool line_before(double b1, double a1, int i1, double b2, double a2, int i2) {
   return b1 > b2 || (b1 == b2 && (a1 < a2 || (a1 == a2 && i1 < i2)));
 }
-
-__device__ __forceinline__ double normal_pdf(double x) { return 0.3989422804014326779399460599343818684759 * exp(-0.5 * x * x); }
 
 // Phi(hi) - Phi(lo) for lo < hi, erfc on the side of the common sign: no cancellation in the tails
 __device__ __forceinline__ double normal_cdf_diff(double lo, double hi) {

@@ -326,8 +326,10 @@ void stage_ascent(Kg1Ensemble& T, const Kg1Objective& o, const moe_gd_params_t& 
 // pending points in use are the members' p): screening, the kept starts, the rounds, the end values.  Returns where the returned point
 // lies in device memory, padded [dp] -- a greedy batch appends it to the pending points without a trip through the host.
 const double* ascend(Kg1Ensemble& T, const moe_gd_params_t& outer, const double* starts, int num_starts, int do_gradient_ascent,
-                     double* best_point, double* best_value, int* found, double* start_values, int* kept_index, double* end_points,
-                     double* end_values, double* path, int* steps_taken) {
+                     const Kg1MultistartOut& out) {
+  double* const best_point = out.best_point;
+  double* const best_value = out.best_value;
+  int* const found = out.found;
   GpDev& g0 = *T.gps[0];
   const int E = T.E, W = T.W, d = T.d, dp = T.dp, S = num_starts;
   const int R = std::max(outer.max_num_restarts, 0), Tn = outer.max_num_steps;
@@ -353,7 +355,7 @@ const double* ascend(Kg1Ensemble& T, const moe_gd_params_t& outer, const double*
   MOE_HIP_CHECK(hipStreamSynchronize(z));
   throw_if_singular(T, h);
   const std::vector<double> vals(h + oVals, h + oVals + S);
-  if (start_values) std::copy(vals.begin(), vals.end(), start_values);
+  if (out.start_values) std::copy(vals.begin(), vals.end(), out.start_values);
   *found = 0;
   *best_value = -INFINITY;
   if (!ascent) {
@@ -431,15 +433,15 @@ const double* ascend(Kg1Ensemble& T, const moe_gd_params_t& outer, const double*
   throw_if_singular(T, h);
   for (int k = 0; k < K; ++k) {
     const double* xk = h + oX + (size_t)k * dp;
-    if (kept_index) kept_index[k] = order[k];
-    if (steps_taken) steps_taken[k] = (int)h[W + k];
-    if (end_points) std::copy(xk, xk + d, end_points + (size_t)k * d);
-    if (end_values) end_values[k] = h[oVals + k];
+    if (out.kept_index) out.kept_index[k] = order[k];
+    if (out.steps_taken) out.steps_taken[k] = (int)h[W + k];
+    if (out.end_points) std::copy(xk, xk + d, out.end_points + (size_t)k * d);
+    if (out.end_values) out.end_values[k] = h[oVals + k];
     if (want_path) {
       const double* pk = h + oPath + (size_t)k * rows * d;
-      double* out = path + (size_t)k * rows * d;
-      std::copy(pk, pk + (size_t)(1 + rows_done) * d, out);
-      for (int row = 1 + rows_done; row < rows; ++row) std::copy(xk, xk + d, out + (size_t)row * d);  // (rounds that never ran)
+      double* path_k = out.path + (size_t)k * rows * d;
+      std::copy(pk, pk + (size_t)(1 + rows_done) * d, path_k);
+      for (int row = 1 + rows_done; row < rows; ++row) std::copy(xk, xk + d, path_k + (size_t)row * d);  // (rounds that never ran)
     }
     if (h[oVals + k] > *best_value) {  // strict: the first of equal values wins
       *best_value = h[oVals + k];
@@ -523,28 +525,27 @@ void kg1_ensemble_evaluate(const Kg1Objective& o, const std::vector<GpDev*>& gps
 
 void kg1_ensemble_multistart(const Kg1Objective& o, const std::vector<GpDev*>& gps, const moe_gd_params_t& outer,
                              const double* domain_bounds, const double* starts, int num_starts, int do_gradient_ascent,
-                             double* best_point, double* best_value, int* found, double* start_values, int* kept_index,
-                             double* end_points, double* end_values, double* path, int* steps_taken, const double* pending,
-                             int num_pending) {
+                             const double* pending, int num_pending, const Kg1MultistartOut& out) {
   Kg1Ensemble T(gps, o, num_pending);
   const bool ascent = do_gradient_ascent != 0;
-  stage_ascent(T, o, outer, domain_bounds, starts, num_starts, ascent, ascent && path != nullptr, pending, num_pending);
-  ascend(T, outer, starts, num_starts, do_gradient_ascent, best_point, best_value, found, start_values, kept_index, end_points,
-         end_values, path, steps_taken);
+  stage_ascent(T, o, outer, domain_bounds, starts, num_starts, ascent, ascent && out.path != nullptr, pending, num_pending);
+  ascend(T, outer, starts, num_starts, do_gradient_ascent, out);
 }
 
 // q points greedily: round t is the ascent above with the caller's pending points and the t points already picked; the staging
 // runs once, a round appends one column to every member's extension (and what the objective keeps beside it).
 void kg1_ensemble_suggest(const Kg1Objective& o, const std::vector<GpDev*>& gps, const moe_gd_params_t& outer,
                           const double* domain_bounds, const double* starts, int num_starts, int do_gradient_ascent,
-                          const double* pending, int num_pending, int num_to_sample, double* best_points, double* best_values,
-                          int* found) {
+                          const double* pending, int num_pending, int num_to_sample, const Kg1BatchOut& out) {
   Kg1Ensemble T(gps, o, num_pending + num_to_sample - 1);
   stage_ascent(T, o, outer, domain_bounds, starts, num_starts, do_gradient_ascent != 0, false, pending, num_pending);
   const int d = T.d;
   for (int t = 0; t < num_to_sample; ++t) {
-    const double* dBest = ascend(T, outer, starts, num_starts, do_gradient_ascent, best_points + (size_t)t * d, best_values + t,
-                                 found + t, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    Kg1MultistartOut round;
+    round.best_point = out.best_points + (size_t)t * d;
+    round.best_value = out.best_values + t;
+    round.found = out.found + t;
+    const double* dBest = ascend(T, outer, starts, num_starts, do_gradient_ascent, round);
     if (t + 1 == num_to_sample) break;
     copy_async(T.dPending + (size_t)T.p * T.dp, dBest, sizeof(double) * (size_t)T.dp, hipMemcpyDeviceToDevice, T.z);
     o.pick_appended(T);

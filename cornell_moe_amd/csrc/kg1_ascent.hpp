@@ -1,11 +1,13 @@
 // cornell_moe_amd/csrc/kg1_ascent.hpp -- what the ensemble forms of the one-point acquisition functions share, declared here and
 // compiled once in kg1_ascent.hip: the members' common checks, the staging of a call, the ensemble mean, the multistart ascent and
 // the drivers behind the three shapes of entry point (evaluate at points, multistart, greedy batch).  None of it knows the
-// objective; each client describes its own in a Kg1Objective.  The clients: kg1_opt.hip (the discretised knowledge gradient),
-// ei1.hip (the analytic expected improvement), gibbon1.hip (the min-value entropy acquisition) and cei1.hip (the constrained
-// expected improvement, whose members are groups of 1 + K GPs combined by its own rule in the place of the ensemble mean) and
-// ehvi1.hip (the two-objective expected hypervolume improvement: groups of two GPs and a Pareto front per group).
+// objective; each client describes a call of its own in a Kg1Call (its Kg1Objective, what that points into, its members' check),
+// and the entry points (api.hip) hand that to a driver.  The clients: kg1_opt.hip (the discretised knowledge gradient), ei1.hip
+// (the analytic expected improvement), gibbon1.hip (the min-value entropy acquisition), cei1.hip (the constrained expected
+// improvement, whose members are groups of 1 + K GPs combined by its own rule in the place of the ensemble mean) and ehvi1.hip
+// (the two-objective expected hypervolume improvement: groups of two GPs and a Pareto front per group).
 #pragma once
+#include <memory>
 #include <vector>
 
 #include "gp.hpp"
@@ -61,26 +63,27 @@ struct Kg1Ensemble {
   Kg1AscentSizes sz = {};
 };
 
-// An objective as the staging and the drivers see it (the hooks but `member`, `eval_points` and `pick_appended` may be NULL).
+// An objective as the staging and the drivers see it: a client names the fields it sets (the hooks but `member`, `eval_points` and
+// `pick_appended` may stay NULL).
 struct Kg1Objective {
-  int nf;                      // fidelity coordinates (0: one view of the points)
-  const double* discrete_all;  // the members' discrete sets back to back [sum A_e][d - nf]; NULL: the objective has none
-  const int* num_discrete;     // [E]: A_e
-  const double* best_so_far;   // [E]
+  int nf = 0;                            // fidelity coordinates (0: one view of the points)
+  const double* discrete_all = nullptr;  // the members' discrete sets back to back [sum A_e][d - nf]; NULL: the objective has none
+  const int* num_discrete = nullptr;     // [E]: A_e
+  const double* best_so_far = nullptr;   // [E]
   // member e's layout for at most C candidates and pcap pending points (fail, fail_pending: its failure words)
-  Kg1Member (*member)(const Kg1Objective& o, GpDev& gp, int e, int C, bool with_grad, int* fail, int pcap, int* fail_pending);
+  Kg1Member (*member)(const Kg1Objective& o, GpDev& gp, int e, int C, bool with_grad, int* fail, int pcap, int* fail_pending) = nullptr;
   // the member's chain (Kg1Ensemble::eval_points)
-  void (*eval_points)(const Kg1Member& m, const double* Px, const double* Ph, int C, bool with_grad, hipStream_t s);
+  void (*eval_points)(const Kg1Member& m, const double* Px, const double* Ph, int C, bool with_grad, hipStream_t s) = nullptr;
   // staging, once a member's extension by the caller's pending points stands ...
-  void (*member_extended)(const Kg1Member& m, hipStream_t s);
+  void (*member_extended)(const Kg1Member& m, hipStream_t s) = nullptr;
   // ... and once every member's does: the first p of T.dPending are in use
-  void (*all_extended)(Kg1Ensemble& T, int p);
+  void (*all_extended)(Kg1Ensemble& T, int p) = nullptr;
   // a greedy batch has written its pick to row T.p of T.dPending: every member's extension takes it (T.p is raised afterwards)
-  void (*pick_appended)(Kg1Ensemble& T);
+  void (*pick_appended)(Kg1Ensemble& T) = nullptr;
   // num_member_extra doubles per member that travel in the call's one upload, behind the pending points: [E][num_member_extra];
   // member e's reach it as Kg1Member::dExtra / nExtra.  NULL: the objective has none and the upload is laid out without the block.
-  const double* member_extra;
-  int num_member_extra;
+  const double* member_extra = nullptr;
+  int num_member_extra = 0;
   // group > 1 and combine set: the E members are E / group groups of `group` consecutive members, and combine forms the ensemble's
   // value [C] and / or gradient [C][d] (either may be NULL) from the members' dKg / dGrad (T.dKgTab, T.dGradTab) on T.z, in the
   // place of the mean of the members.  With combine NULL or group <= 1 the drivers issue the launches they always did.
@@ -97,19 +100,54 @@ struct Kg1Objective {
 // the objective's own check of member e, made before that member's duplicate check.
 void kg1_check_members(const std::vector<GpDev*>& gps, int nf, void (*check_member)(const GpDev& g, const GpDev& g0, size_t e, int nf));
 
-// The drivers (the members are checked).  Their arguments are those of kg_discrete_mcmc_on_device / _multistart / _suggest (gp.hpp)
-// without the objective's own.  members_out (may be NULL): every member's own value [E][C], in the same copy back.
+// A client's description of one call: the objective, the storage the objective points into (cei1.hip: the sub-members' limits,
+// ehvi1.hip: its zeros and what its hooks need of the call) and the members' check -- one dim, one device, no member listed twice
+// and the client's own conditions, with room for pending_room pending points (the caller's and a greedy batch's picks).
+struct Kg1Call {
+  Kg1Call() = default;
+  Kg1Call(Kg1Call&&) = default;  // (moved, never copied: o points into the storage, which a move leaves where it is)
+  Kg1Call& operator=(Kg1Call&&) = default;
+  Kg1Objective o;
+  std::vector<double> doubles;
+  std::shared_ptr<const void> client;
+  void (*check_members)(const Kg1Objective& o, const std::vector<GpDev*>& gps, int pending_room) = nullptr;
+};
+// The five clients' descriptions, one function each (the caller has made the checks that need no handle; the arrays are the
+// caller's and outlive the call).  gp.hpp says what the arguments are.
+Kg1Call kg1_call(int num_fidelity, const double* discrete_all, const int* num_discrete, const double* best_so_far);  // kg1_opt.hip
+Kg1Call ei1_call(const double* best_so_far);                                                                       // ei1.hip
+Kg1Call gibbon1_call(const double* min_values, int num_min_values);                                                // gibbon1.hip
+Kg1Call cei1_call(int num_mcmc, int num_constraints, const double* thresholds, const double* best_so_far);         // cei1.hip
+Kg1Call ehvi1_call(int num_mcmc, const double* reference_point, const double* front, int num_front);               // ehvi1.hip
+
+// what a multistart hands back (all but the first three may be NULL) ...
+struct Kg1MultistartOut {
+  double* best_point = nullptr;  // [d]
+  double* best_value = nullptr;
+  int* found = nullptr;
+  double* start_values = nullptr;  // [S]
+  int* kept_index = nullptr;       // [K]
+  double* end_points = nullptr;    // [K][d]
+  double* end_values = nullptr;    // [K]
+  double* path = nullptr;          // [K][rows][d]
+  int* steps_taken = nullptr;      // [K]
+};
+// ... and a greedy batch of q points
+struct Kg1BatchOut {
+  double* best_points = nullptr;  // [q][d]
+  double* best_values = nullptr;  // [q]
+  int* found = nullptr;           // [q]
+};
+
+// The drivers behind the three shapes of entry point (the members are checked: Kg1Call::check_members with num_pending, a batch
+// with num_pending + num_to_sample - 1).  members_out (may be NULL): every member's own value [E][C], in the same copy back.
 void kg1_ensemble_evaluate(const Kg1Objective& o, const std::vector<GpDev*>& gps, const double* pts, int C, bool want_grad,
-                           double* value_out, double* grad_out, const double* pending, int num_pending,
-                           double* members_out = nullptr);
+                           double* value_out, double* grad_out, const double* pending, int num_pending, double* members_out);
 void kg1_ensemble_multistart(const Kg1Objective& o, const std::vector<GpDev*>& gps, const moe_gd_params_t& outer,
                              const double* domain_bounds, const double* starts, int num_starts, int do_gradient_ascent,
-                             double* best_point, double* best_value, int* found, double* start_values, int* kept_index,
-                             double* end_points, double* end_values, double* path, int* steps_taken, const double* pending,
-                             int num_pending);
+                             const double* pending, int num_pending, const Kg1MultistartOut& out);
 void kg1_ensemble_suggest(const Kg1Objective& o, const std::vector<GpDev*>& gps, const moe_gd_params_t& outer,
                           const double* domain_bounds, const double* starts, int num_starts, int do_gradient_ascent,
-                          const double* pending, int num_pending, int num_to_sample, double* best_points, double* best_values,
-                          int* found);
+                          const double* pending, int num_pending, int num_to_sample, const Kg1BatchOut& out);
 
 }  // namespace moe

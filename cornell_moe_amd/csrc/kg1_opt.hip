@@ -18,9 +18,9 @@
 // batch, appending the picked point to every member's extension in between.
 // The staging, the kernels of the mean, step and round phases, the recorded evaluation, the ascent and the drivers of the three entry
 // points know nothing of the objective and are compiled once in kg1_ascent.hip (declared in kg1_ascent.hpp), which ei1.hip (the
-// ensemble analytic expected improvement) goes through too; this file keeps what is the knowledge gradient's own: the description
-// of the objective (its sets, how a member is built, the set phase behind a member's extension), the member check and the entry
-// points as calls of the drivers.
+// ensemble analytic expected improvement) and its relatives go through too; this file keeps what is the knowledge gradient's own:
+// the description of the call (kg1_call: its sets, how a member is built, the set phase behind a member's extension, the members'
+// check) and the check of the shapes that needs no handle.
 //
 // Bits.  A member's evaluation is kg1.hip's own kernels in kg1.hip's own pass structure, launched by itself or as the member's share of
 // an ensemble twin: the same instructions on the same operands.  The mean adds the members in member order and divides once.  The
@@ -34,6 +34,9 @@ namespace {
 
 void check_member(const GpDev& g, const GpDev&, size_t, int nf) { check_kg_discrete_member(g, nf); }
 
+// (the row limit is the pending check's: a point is one row here)
+void check_members(const Kg1Objective& o, const std::vector<GpDev*>& gps, int) { kg1_check_members(gps, o.nf, check_member); }
+
 Kg1Member member(const Kg1Objective& o, GpDev& gp, int e, int C, bool with_grad, int* fail, int pcap, int* fail_pending) {
   return kg1_member(gp, o.nf, o.num_discrete[e], C, o.best_so_far[e], with_grad, fail, pcap, fail_pending);
 }
@@ -43,47 +46,28 @@ void pick_appended(Kg1Ensemble& T) {
   for (Kg1Member& m : T.mem) kg1_pending_append(m, 1, true, T.z);
 }
 
-// (begin -> append -> the set phase, member after member; nothing left once every extension stands)
-Kg1Objective objective(int nf, const double* discrete_all, const int* num_discrete, const double* best_so_far) {
-  return Kg1Objective{nf, discrete_all, num_discrete, best_so_far, member, kg1_eval_points, kg1_prepare_set, nullptr, pick_appended, nullptr, 0};
-}
-
 }  // namespace
+
+// (begin -> append -> the set phase, member after member; nothing left once every extension stands)
+Kg1Call kg1_call(int nf, const double* discrete_all, const int* num_discrete, const double* best_so_far) {
+  Kg1Call call;
+  call.o.nf = nf;
+  call.o.discrete_all = discrete_all;
+  call.o.num_discrete = num_discrete;
+  call.o.best_so_far = best_so_far;
+  call.o.member = member;
+  call.o.eval_points = kg1_eval_points;
+  call.o.member_extended = kg1_prepare_set;
+  call.o.pick_appended = pick_appended;
+  call.check_members = check_members;
+  return call;
+}
 
 void check_kg_discrete_ensemble_shapes(int num_mcmc, int num_fidelity, const int* num_discrete, int num_points) {
   if (num_mcmc < 1 || num_mcmc > 1024) throw Error(MOE_ERR_BOUNDS, "num_mcmc must be between 1 and 1024", num_mcmc, 1, 1024);
   if (num_discrete == nullptr) throw Error(MOE_ERR_RUNTIME, "NULL argument");
   for (int e = 0; e < num_mcmc; ++e) check_kg_discrete_shapes(0, num_discrete[e], 1);
   check_kg_discrete_shapes(num_fidelity, 1, num_points);  // (the number of points, then num_fidelity >= 0)
-}
-
-void kg_discrete_mcmc_on_device(const std::vector<GpDev*>& gps, int nf, const double* discrete_all, const int* num_discrete,
-                                const double* best_so_far, const double* pts, int C, bool want_grad, double* kg_out, double* grad_out,
-                                const double* pending, int num_pending) {
-  kg1_check_members(gps, nf, check_member);
-  kg1_ensemble_evaluate(objective(nf, discrete_all, num_discrete, best_so_far), gps, pts, C, want_grad, kg_out, grad_out, pending,
-                        num_pending);
-}
-
-void kg_discrete_mcmc_multistart(const std::vector<GpDev*>& gps, int nf, const moe_gd_params_t& outer, const double* domain_bounds,
-                                 const double* discrete_all, const int* num_discrete, const double* best_so_far,
-                                 const double* starts, int num_starts, int do_gradient_ascent, double* best_point,
-                                 double* best_value, int* found, double* start_values, int* kept_index, double* end_points,
-                                 double* end_values, double* path, int* steps_taken, const double* pending, int num_pending) {
-  kg1_check_members(gps, nf, check_member);
-  kg1_ensemble_multistart(objective(nf, discrete_all, num_discrete, best_so_far), gps, outer, domain_bounds, starts, num_starts,
-                          do_gradient_ascent, best_point, best_value, found, start_values, kept_index, end_points, end_values, path,
-                          steps_taken, pending, num_pending);
-}
-
-// q points greedily: the set phase runs once, a round appends one column to every member's extension and one row under its set.
-void kg_discrete_mcmc_suggest(const std::vector<GpDev*>& gps, int nf, const moe_gd_params_t& outer, const double* domain_bounds,
-                              const double* discrete_all, const int* num_discrete, const double* best_so_far, const double* starts,
-                              int num_starts, int do_gradient_ascent, const double* pending, int num_pending, int num_to_sample,
-                              double* best_points, double* best_values, int* found) {
-  kg1_check_members(gps, nf, check_member);
-  kg1_ensemble_suggest(objective(nf, discrete_all, num_discrete, best_so_far), gps, outer, domain_bounds, starts, num_starts,
-                       do_gradient_ascent, pending, num_pending, num_to_sample, best_points, best_values, found);
 }
 
 }  // namespace moe
