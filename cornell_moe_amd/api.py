@@ -1104,6 +1104,43 @@ def ei_constrained_suggest(gps, constraint_gps, thresholds, gd_params, bounds, b
                          points_being_sampled)
 
 
+def log_ei_constrained_ensemble(gps, constraint_gps, thresholds, points, best_so_far, points_being_sampled=None, want_grad=True,
+                                want_log_factors=False):
+    """moe_log_ei_constrained_mcmc: the LOG of what ei_constrained_ensemble returns, computed so that it stays finite with a useful
+    gradient where that value and its gradient are exactly 0 in float64 (an incumbent dozens of posterior standard deviations below
+    the mean, a constraint far from feasible).  Arguments as there; constraint_gps=None / thresholds=None is K = 0, the log of the
+    ensemble-averaged analytic expected improvement.  Returns value [C], with want_grad (value, grad [C][dim]), and with
+    want_log_factors additionally log_factors [E][1 + K][C] (the log improvement factor, then the K log feasibility factors) as
+    the last item; the value is the log-mean-exp over e of the members' sums.  SingularMatrixException as there."""
+    arr, E, d, keep, carr, K, tau, best = _ei_constrained_members(gps, constraint_gps, thresholds, best_so_far)
+    pre, post = (arr, E, carr, K, tau.ctypes.data_as(dp) if K else None), (best.ctypes.data_as(dp),)
+    return _acq1_evaluate(_lib.load().moe_log_ei_constrained_mcmc, pre, post, d, points, want_grad, points_being_sampled,
+                          extra_shape=(E, 1 + K), want_extra=want_log_factors)
+
+
+def log_ei_constrained_multistart(gps, constraint_gps, thresholds, gd_params, bounds, best_so_far, starts, gradient_ascent=True,
+                                  want_path=False, points_being_sampled=None):
+    """moe_log_ei_constrained_mcmc_multistart: one suggestion by the log of the ensemble-averaged constrained expected improvement
+    -- ei_constrained_multistart's screening, 20 kept starts, restarted ascent on the device and end-point selection, and its dict,
+    on an objective whose screening values do not tie at 0 and whose gradient does not vanish."""
+    arr, E, d, keep, carr, K, tau, best = _ei_constrained_members(gps, constraint_gps, thresholds, best_so_far)
+    pre, post = (arr, E, carr, K, tau.ctypes.data_as(dp) if K else None), (best.ctypes.data_as(dp),)
+    return _acq1_multistart(_lib.load().moe_log_ei_constrained_mcmc_multistart, pre, post, d, gd_params, bounds, starts, gradient_ascent,
+                            want_path, points_being_sampled)
+
+
+def log_ei_constrained_suggest(gps, constraint_gps, thresholds, gd_params, bounds, best_so_far, starts, num_to_sample,
+                               gradient_ascent=True, points_being_sampled=None):
+    """moe_log_ei_constrained_mcmc_suggest: num_to_sample points greedily by the log of the ensemble-averaged constrained expected
+    improvement -- round t is log_ei_constrained_multistart from the same starts [S][dim] with the pending points
+    points_being_sampled [p][dim] (may be None) followed by the points of the rounds before, bit for bit, in one device call.
+    (p + num_to_sample - 1) (1 + g) <= 64.  Returns a dict: points [q][dim], values [q], found [q]."""
+    arr, E, d, keep, carr, K, tau, best = _ei_constrained_members(gps, constraint_gps, thresholds, best_so_far)
+    pre, post = (arr, E, carr, K, tau.ctypes.data_as(dp) if K else None), (best.ctypes.data_as(dp),)
+    return _acq1_suggest(_lib.load().moe_log_ei_constrained_mcmc_suggest, pre, post, d, gd_params, bounds, starts, num_to_sample,
+                         gradient_ascent, points_being_sampled)
+
+
 def _ehvi_members(gps, gps2, reference_point, front):
     """(objective-1 handles, objective-2 handles, E, dim, GPs kept alive, reference point [2], front [F][2] or None, F) of the
     ensemble forms of the expected hypervolume improvement; gps and gps2 shaped alike (a DeviceGPMCMC, a list of DeviceGP or one

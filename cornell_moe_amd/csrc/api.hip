@@ -880,7 +880,7 @@ int moe_gp_paths_minimize(const moe_gp_t* const* gps, int num_mcmc, const double
   });
 }
 
-// ---- the ensemble forms of the one-point acquisitions (kg1_ascent.hpp): five objectives, three shapes of entry point each ----
+// ---- the ensemble forms of the one-point acquisitions (kg1_ascent.hpp): six objectives, three shapes of entry point each ----
 extern "C++" {  // (the helpers return C++ types)
 namespace {
 
@@ -1005,6 +1005,15 @@ Acq1 ei_constrained(const moe_gp_t* const* gps, int num_mcmc, const moe_gp_t* co
   };
   a.handles = [=] { return constrained_handles(gps, num_mcmc, constraint_gps, num_constraints); };
   a.call = [=] { return moe::cei1_call(num_mcmc, num_constraints, thresholds, best_so_far); };
+  return a;
+}
+
+// the constrained expected improvement's ladder under the log form's name and kernels
+Acq1 log_ei_constrained(const moe_gp_t* const* gps, int num_mcmc, const moe_gp_t* const* constraint_gps, int num_constraints,
+                        const double* thresholds, const double* best_so_far) {
+  Acq1 a = ei_constrained(gps, num_mcmc, constraint_gps, num_constraints, thresholds, best_so_far);
+  a.name = "the log constrained expected improvement";
+  a.call = [=] { return moe::logcei1_call(num_mcmc, num_constraints, thresholds, best_so_far); };
   return a;
 }
 
@@ -1183,6 +1192,42 @@ int moe_ei_constrained_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, co
                                     int num_to_sample, double* best_points, double* best_values, int* found, moe_error_t* err) {
   return guarded(err, [&] {
     acq1_suggest(ei_constrained(gps, num_mcmc, constraint_gps, num_constraints, thresholds, best_so_far), outer, domain_bounds,
+                 points_being_sampled, num_being_sampled, starts, num_starts, do_gradient_ascent, num_to_sample,
+                 {best_points, best_values, found});
+  });
+}
+
+int moe_log_ei_constrained_mcmc(const moe_gp_t* const* gps, int num_mcmc, const moe_gp_t* const* constraint_gps, int num_constraints,
+                                const double* thresholds, const double* best_so_far, const double* points_being_sampled,
+                                int num_being_sampled, const double* points, int num_points, int want_grad, double* value,
+                                double* grad, double* log_factors, moe_error_t* err) {
+  return guarded(err, [&] {
+    acq1_evaluate(log_ei_constrained(gps, num_mcmc, constraint_gps, num_constraints, thresholds, best_so_far), points_being_sampled,
+                  num_being_sampled, points, num_points, want_grad, value, grad, log_factors);
+  });
+}
+
+int moe_log_ei_constrained_mcmc_multistart(const moe_gp_t* const* gps, int num_mcmc, const moe_gp_t* const* constraint_gps,
+                                           int num_constraints, const double* thresholds, const moe_gd_params_t* outer,
+                                           const double* domain_bounds, const double* best_so_far,
+                                           const double* points_being_sampled, int num_being_sampled, const double* starts,
+                                           int num_starts, int do_gradient_ascent, double* best_point, double* best_value, int* found,
+                                           double* start_values, int* kept_index, double* end_points, double* end_values, double* path,
+                                           int* steps_taken, moe_error_t* err) {
+  return guarded(err, [&] {
+    acq1_multistart(log_ei_constrained(gps, num_mcmc, constraint_gps, num_constraints, thresholds, best_so_far), outer, domain_bounds,
+                    points_being_sampled, num_being_sampled, starts, num_starts, do_gradient_ascent,
+                    {best_point, best_value, found, start_values, kept_index, end_points, end_values, path, steps_taken});
+  });
+}
+
+int moe_log_ei_constrained_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, const moe_gp_t* const* constraint_gps,
+                                        int num_constraints, const double* thresholds, const moe_gd_params_t* outer,
+                                        const double* domain_bounds, const double* best_so_far, const double* points_being_sampled,
+                                        int num_being_sampled, const double* starts, int num_starts, int do_gradient_ascent,
+                                        int num_to_sample, double* best_points, double* best_values, int* found, moe_error_t* err) {
+  return guarded(err, [&] {
+    acq1_suggest(log_ei_constrained(gps, num_mcmc, constraint_gps, num_constraints, thresholds, best_so_far), outer, domain_bounds,
                  points_being_sampled, num_being_sampled, starts, num_starts, do_gradient_ascent, num_to_sample,
                  {best_points, best_values, found});
   });

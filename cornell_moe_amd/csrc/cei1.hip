@@ -4,7 +4,7 @@
 // moe_ei_constrained_mcmc_multistart, moe_ei_constrained_mcmc_suggest): a client of kg1_ascent.hip's staging, ascent and drivers.
 // The pending-row extension is kg1_pending.hip's, the layout, the members' check, the pass and the gradient's tail are ei1.hip's
 // (ei1.hpp); this file keeps the candidate kernel with its two roles, the combine kernel, the believed-feasible incumbent and the
-// description of the call (cei1_call).
+// description of the call (cei1_call).  The sub-member's layout and the incumbent's hooks are lent to logcei1.hip (cei1.hpp).
 //
 // A call takes E joint hyper-samples and K constraints, 0 <= K <= 8.  Member e is 1 + K GPs: the objective GP and the constraint GPs
 // c_1 .. c_K, constraint k satisfied where c_k(x) <= tau_k.  The E (1 + K) GPs are the SUB-MEMBERS of one Kg1Ensemble, ordered
@@ -36,6 +36,7 @@
 #include <cmath>
 
 #include "acq1_device.hpp"
+#include "cei1.hpp"
 #include "device_cov.hpp"
 #include "ei1.hpp"
 #include "kg1_ascent.hpp"
@@ -162,8 +163,10 @@ void cei1_eval_points(const Kg1Member& m, const double* Px, const double*, int C
   ei1_eval_passes(m, Px, C, with_grad, s, "cei1_eval_pass", cand_step, ei1_grad_tail);
 }
 
+}  // namespace
+
 // mu of every sub-member at P_j0 .. j0 + count - 1 (the function values alone), then every member's believed-feasible incumbent
-void join_believed_feasible(Kg1Ensemble& T, int j0, int count, bool first) {
+void cei1_join_believed_feasible(Kg1Ensemble& T, int j0, int count, bool first) {
   const int G = std::max(T.group, 1);
   for (Kg1Member& m : T.mem) {
     GpDev& gp = *m.gp;
@@ -183,19 +186,21 @@ void join_believed_feasible(Kg1Ensemble& T, int j0, int count, bool first) {
 }
 
 // EI's layout; o.best_so_far holds the sub-members' limits [E G]: b_e for role 0, tau_k for role k
-Kg1Member member(const Kg1Objective& o, GpDev& gp, int e, int C, bool with_grad, int* fail, int pcap, int* fail_pending) {
+Kg1Member cei1_member(const Kg1Objective& o, GpDev& gp, int e, int C, bool with_grad, int* fail, int pcap, int* fail_pending) {
   Kg1Member m = ei1_member(gp, C, o.best_so_far[e], with_grad, fail, pcap * (1 + gp.g), fail_pending);  // (pcap points: 1 + g rows each)
   m.role = e % std::max(o.group, 1);
   return m;
 }
 
-void all_extended(Kg1Ensemble& T, int p) { join_believed_feasible(T, 0, p, true); }
+void cei1_all_extended(Kg1Ensemble& T, int p) { cei1_join_believed_feasible(T, 0, p, true); }
 
 // a pick joins every sub-member's extension, then the members' incumbents under the feasibility test, inside device memory
-void pick_appended(Kg1Ensemble& T) {
+void cei1_pick_appended(Kg1Ensemble& T) {
   for (Kg1Member& m : T.mem) kg1_pending_append(m, 1, false, T.z);
-  join_believed_feasible(T, T.p, 1, false);
+  cei1_join_believed_feasible(T, T.p, 1, false);
 }
+
+namespace {
 
 void combine(const Kg1Ensemble& T, int C, double* value_out, double* grad_out) {
   const long n = (value_out != nullptr ? (long)C : 0) + (grad_out != nullptr ? (long)C * T.d : 0);
@@ -218,10 +223,10 @@ Kg1Call cei1_call(int num_mcmc, int num_constraints, const double* thresholds, c
     for (int k = 0; k < K; ++k) call.doubles[(size_t)e * (1 + K) + 1 + k] = thresholds[k];
   }
   call.o.best_so_far = call.doubles.data();
-  call.o.member = member;
+  call.o.member = cei1_member;
   call.o.eval_points = cei1_eval_points;
-  call.o.all_extended = all_extended;
-  call.o.pick_appended = pick_appended;
+  call.o.all_extended = cei1_all_extended;
+  call.o.pick_appended = cei1_pick_appended;
   call.o.group = 1 + K;
   call.o.combine = combine;
   call.check_members = ei1_check_members;

@@ -295,7 +295,7 @@ void kg1_eval_points(const Kg1Member& m, const double* Px, const double* Ph, int
 void kg1_clear_fail(int* fail, int count, hipStream_t s);  // INT_MAX: no candidate has failed
 // The ensemble forms of the one-point acquisitions: evaluate at points, multistart ascent and greedy batches of each, with pending
 // points [num_pending][dim] by the Kriging-believer fantasy of kg1_pending.hip.  Every client describes its call in one function
-// (kg1_ascent.hpp: kg1_call, ei1_call, gibbon1_call, cei1_call, ehvi1_call) and the three drivers of kg1_ascent.hip run it; here are
+// (kg1_ascent.hpp: kg1_call, ei1_call, gibbon1_call, cei1_call, ehvi1_call, logcei1_call) and the three drivers of kg1_ascent.hip run it; here are
 // the checks that need no handle, which the entry points make first, and the limits.
 // kg1_opt.hip: the discretised knowledge gradient (moe_kg_discrete_mcmc*).  discrete_all: the members' sets back to back.
 void check_kg_discrete_ensemble_shapes(int num_mcmc, int num_fidelity, const int* num_discrete, int num_points);
@@ -317,7 +317,8 @@ void check_gibbon_min_values(const double* min_values, int num_mcmc, int num_min
 // GPs of a call [E (1 + K)] are the sub-members ordered [e][role], role 0 the objective GP, role k constraint k (satisfied where
 // c_k <= thresholds[k - 1]); best_so_far [E] may hold +infinity.  check_ei_constrained_shapes: K, the product limit, the arrays
 // K > 0 needs, finite thresholds, best_so_far neither NaN nor -infinity.  The members' own values of an evaluation are the
-// sub-members' factor values [E (1 + K)][C].
+// sub-members' factor values [E (1 + K)][C].  logcei1.hip: the log of the same quantity (moe_log_ei_constrained_mcmc*), the same
+// arguments, checks and limits; the members' own values are the sub-members' logs.
 constexpr int kCeiMaxConstraints = 8;
 void check_ei_constrained_shapes(int num_mcmc, int num_constraints, const void* constraint_gps, const double* thresholds,
                                  const double* best_so_far);

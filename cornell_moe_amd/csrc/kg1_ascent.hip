@@ -1,6 +1,7 @@
 // cornell_moe_amd/csrc/kg1_ascent.hip -- what the ensemble forms of the one-point acquisition functions share (kg1_opt.hip: the
 // discretised knowledge gradient; ei1.hip: the analytic expected improvement; gibbon1.hip: the min-value entropy acquisition;
-// cei1.hip: the constrained expected improvement; ehvi1.hip: the expected hypervolume improvement), compiled once: the ensemble mean, the multistart
+// cei1.hip: the constrained expected improvement; ehvi1.hip: the expected hypervolume improvement; logcei1.hip: the log of the
+// constrained expected improvement), compiled once: the ensemble mean, the multistart
 // ascent's gather, step and round kernels, the recorded and zipped evaluation of the members' chains, the ascent itself (ascend()),
 // the staging of a call (stage(), stage_ascent()) and the three drivers behind the entry points (kg1_ascent.hpp).  None of it knows
 // the objective: a Kg1Objective says how a member is built, which chain evaluates it and what follows its extension.
@@ -458,10 +459,10 @@ const double* ascend(Kg1Ensemble& T, const moe_gd_params_t& outer, const double*
 Kg1Ensemble::Kg1Ensemble(const std::vector<GpDev*>& members, const Kg1Objective& o, int pending_room)
     : gps(members), z(members[0]->stream), ens(ensemble_launches() && members.size() > 1), E((int)members.size()), d(members[0]->d),
       dp(members[0]->dp), nf(o.nf), eval_points(o.eval_points), fid(o.nf > 0), pcap(pending_room), W(pending_room > 0 ? 2 * E : E) {
-  if (o.combine != nullptr && o.group > 1) {
-    if (E % o.group != 0) throw Error(MOE_ERR_RUNTIME, "the members do not fill their groups");
+  if (o.combine != nullptr && (o.group > 1 || o.combine_single_groups)) {
+    if (E % std::max(o.group, 1) != 0) throw Error(MOE_ERR_RUNTIME, "the members do not fill their groups");
     combine = o.combine;
-    group = o.group;
+    group = std::max(o.group, 1);
     group_values = o.group_values;
   }
   client = o.client;

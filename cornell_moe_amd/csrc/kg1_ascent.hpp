@@ -4,8 +4,9 @@
 // objective; each client describes a call of its own in a Kg1Call (its Kg1Objective, what that points into, its members' check),
 // and the entry points (api.hip) hand that to a driver.  The clients: kg1_opt.hip (the discretised knowledge gradient), ei1.hip
 // (the analytic expected improvement), gibbon1.hip (the min-value entropy acquisition), cei1.hip (the constrained expected
-// improvement, whose members are groups of 1 + K GPs combined by its own rule in the place of the ensemble mean) and ehvi1.hip
-// (the two-objective expected hypervolume improvement: groups of two GPs and a Pareto front per group).
+// improvement, whose members are groups of 1 + K GPs combined by its own rule in the place of the ensemble mean), ehvi1.hip
+// (the two-objective expected hypervolume improvement: groups of two GPs and a Pareto front per group) and logcei1.hip (the log of
+// the constrained expected improvement: cei1.hip's groups under a log-sum-exp, taken with groups of one GP too).
 #pragma once
 #include <memory>
 #include <vector>
@@ -89,6 +90,10 @@ struct Kg1Objective {
   // place of the mean of the members.  With combine NULL or group <= 1 the drivers issue the launches they always did.
   int group = 0;
   void (*combine)(const Kg1Ensemble& T, int C, double* value_out, double* grad_out) = nullptr;
+  // combine is taken with groups of ONE member too (group <= 1 reads as 1): an objective whose ensemble rule is no mean of the
+  // members even where every member is one GP (logcei1.hip: a log-sum-exp).  false: the gate above stands, as every other client
+  // relies on (cei1.hip with K = 0 is ei1.hip's launches).
+  bool combine_single_groups = false;
   // what the objective's hooks need of the call beside the members (Kg1Ensemble::client); nothing here reads it
   const void* client = nullptr;
   // with combine: kg1_ensemble_evaluate's members_out is the groups' own values [E / group][C], taken from Kg1Ensemble::dGroupVals,
@@ -112,13 +117,14 @@ struct Kg1Call {
   std::shared_ptr<const void> client;
   void (*check_members)(const Kg1Objective& o, const std::vector<GpDev*>& gps, int pending_room) = nullptr;
 };
-// The five clients' descriptions, one function each (the caller has made the checks that need no handle; the arrays are the
+// The six clients' descriptions, one function each (the caller has made the checks that need no handle; the arrays are the
 // caller's and outlive the call).  gp.hpp says what the arguments are.
 Kg1Call kg1_call(int num_fidelity, const double* discrete_all, const int* num_discrete, const double* best_so_far);  // kg1_opt.hip
 Kg1Call ei1_call(const double* best_so_far);                                                                       // ei1.hip
 Kg1Call gibbon1_call(const double* min_values, int num_min_values);                                                // gibbon1.hip
 Kg1Call cei1_call(int num_mcmc, int num_constraints, const double* thresholds, const double* best_so_far);         // cei1.hip
 Kg1Call ehvi1_call(int num_mcmc, const double* reference_point, const double* front, int num_front);               // ehvi1.hip
+Kg1Call logcei1_call(int num_mcmc, int num_constraints, const double* thresholds, const double* best_so_far);      // logcei1.hip
 
 // what a multistart hands back (all but the first three may be NULL) ...
 struct Kg1MultistartOut {

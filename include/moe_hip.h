@@ -532,6 +532,46 @@ int moe_ei_constrained_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, co
                                     const double* domain_bounds, const double* best_so_far, const double* points_being_sampled,
                                     int num_being_sampled, const double* starts, int num_starts, int do_gradient_ascent,
                                     int num_to_sample, double* best_points, double* best_values, int* found, moe_error_t* err);
+/* The LOG of moe_ei_constrained_mcmc's quantity (Ament et al. 2023, "Unexpected improvements to expected improvement"), computed
+ * without ever forming a Phi or phi that float64 would underflow: finite, with a useful gradient, for every finite input -- where
+ * the plain form and its gradient are exactly 0 (c = (b' - mu) / sigma below about -38, or one constraint far from feasible).
+ * The call is moe_ei_constrained_mcmc's, argument for argument: the members, their order, the pending points and the believed-
+ * feasible incumbent b'_e are those.  num_constraints = 0 is the log of the ensemble-averaged analytic expected improvement.
+ * Per member e at x, with ONE variance floor for value and gradient, sigma = sqrt(max(150 eps^2, var)):
+ *   improvement   c = (b'_e - mu) / sigma,  h(c) = c Phi(c) + phi(c):   l_{e,0} = log sigma + log h(c),
+ *                 grad l = -(lambda / sigma) grad mu + (kappa / (2 sigma^2)) grad var,  lambda = Phi / h,  kappa = phi / h
+ *                 (c >= 0 directly; -6 <= c < 0 through h / phi = 1 + c sqrt(pi / 2) erfcx(-c / sqrt 2); c < -6 through 20 terms
+ *                 of Laplace's continued fraction of the Mills ratio);  b'_e = +infinity: l_{e,0} = 0 with a zero gradient
+ *   feasibility   z = (tau_k - mu) / sigma:   l_{e,k} = log Phi(z),  grad l = -(r / sigma) grad mu - (r z / (2 sigma^2)) grad var,
+ *                 r = phi / Phi  (z < 0 through erfcx, z >= 0 through log1p(-erfc / 2))
+ *   member        L_e = l_{e,0} + ... + l_{e,K}, the gradient g_e likewise, added in the order objective, k = 1 .. K
+ *   ensemble      m = max_e L_e, w_e = exp(L_e - m), W = w_0 + ... + w_{E-1}:  value[i] = m + log W - log E,
+ *                 grad[i] = (w_0 g_0 + ... + w_{E-1} g_{E-1}) / W; members in member order, no fused multiply-add in the rule
+ * log_factors (may be NULL): [E][1 + K][num_points], every l_{e,r}.  With E = 1 and K = 0 value[i] is log_factors[0][0][i] bit for
+ * bit.  A candidate's bits do not depend on how many share the call, on want_grad or on ensemble-wide launches.
+ * Errors: moe_ei_constrained_mcmc's, in its order and with its payloads. */
+int moe_log_ei_constrained_mcmc(const moe_gp_t* const* gps, int num_mcmc, const moe_gp_t* const* constraint_gps, int num_constraints,
+                                const double* thresholds, const double* best_so_far, const double* points_being_sampled,
+                                int num_being_sampled, const double* points, int num_points, int want_grad, double* value,
+                                double* grad, double* log_factors, moe_error_t* err);
+/* moe_ei_constrained_mcmc_multistart with moe_log_ei_constrained_mcmc's objective: the same screening, top-20 rule, restarted
+ * ascent and outputs, bit for bit the path a host loop over moe_log_ei_constrained_mcmc walks.  Errors: that function's, the
+ * ascent's named "the log constrained expected improvement". */
+int moe_log_ei_constrained_mcmc_multistart(const moe_gp_t* const* gps, int num_mcmc, const moe_gp_t* const* constraint_gps,
+                                           int num_constraints, const double* thresholds, const moe_gd_params_t* outer,
+                                           const double* domain_bounds, const double* best_so_far,
+                                           const double* points_being_sampled, int num_being_sampled, const double* starts,
+                                           int num_starts, int do_gradient_ascent, double* best_point, double* best_value, int* found,
+                                           double* start_values, int* kept_index, double* end_points, double* end_values, double* path,
+                                           int* steps_taken, moe_error_t* err);
+/* moe_ei_constrained_mcmc_suggest with moe_log_ei_constrained_mcmc's objective: num_to_sample points greedily, bit for bit what
+ * num_to_sample calls of moe_log_ei_constrained_mcmc_multistart return when each is fed its predecessors' points.  Errors: that
+ * function's. */
+int moe_log_ei_constrained_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, const moe_gp_t* const* constraint_gps,
+                                        int num_constraints, const double* thresholds, const moe_gd_params_t* outer,
+                                        const double* domain_bounds, const double* best_so_far, const double* points_being_sampled,
+                                        int num_being_sampled, const double* starts, int num_starts, int do_gradient_ascent,
+                                        int num_to_sample, double* best_points, double* best_values, int* found, moe_error_t* err);
 /* The two-objective expected hypervolume improvement (EHVI; Emmerich, Giannakoglou & Naujoks 2006; Emmerich, Deutz & Klinkenberg
  * 2011; Yang et al. 2019) averaged over a hyper-parameter ensemble, at points [num_points][dim], with pending points.  Minimisation.
  * Member e is two GPs, gps[e] for objective 1 and gps2[e] for objective 2: one dim, one device, no derivative observations; their
