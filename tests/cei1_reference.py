@@ -192,12 +192,17 @@ CASES = [
     Case("e2_k1_d3_n20_p2_inf_feasible", 9, 2, 1, 3, _grid(2, 1, 20), 2, (), ("inf", "median"), (0.0,), ((-0.5,), (-0.2,)), 6, None),
     Case("e1_k8_d3_n20_p1", 10, 1, 8, 3, _grid(1, 8, 20), 1, (), "median", (0.3,) * 8, None, 6, (3, 4, 5)),
 ]
+# The staging of groups of 1 + K sub-members at a wide padded dimension (24) with unequal members: rows (20, 300, 600) shuffled over
+# the three roles per member as ENSEMBLE shuffles its own -- a different R per sub-member, three strides of 256 rows
+WIDE = Case("e3_k2_d20_n20_300_600_p3", 11, 3, 2, 20, ((20, 300, 600), (300, 600, 20), (600, 20, 300)), 3, (), "median", (0.1, 0.0), None, 6,
+            None)
+WIDE_CASES = [WIDE]
 MIXED, INF, INF_FEASIBLE = "e2_k1_d3_n20_p2_mixed", "e2_k1_d3_n20_p2_inf", "e2_k1_d3_n20_p2_inf_feasible"
 ENSEMBLE = "e3_k2_d3_n12_130_40_p3"
 
 
 def case(name):
-    return next(c for c in CASES if c.name == name)
+    return next(c for c in CASES + WIDE_CASES if c.name == name)
 
 
 def make_problem(c):

@@ -167,8 +167,22 @@ ENSEMBLE = "e3_d3_n20_130_300_p3_f300"
 BELIEVED = Case("e2_d3_n20_p3_believed", 21, 2, 3, ((20, 20),) * 2, 3, 4, 0.0, 8, None, 6.0e-15)
 
 
+# Every instantiation of the gradient kernel that CASES leaves out (padded dimensions 8, 16, 24, 32 with 2, 3, 4 and 0 padded
+# coordinates), each with pending points and a front past one sweep; d20: past one 256-row stride at padded dimension 24; the wide
+# ensemble: three strides of 256 rows and tri_cols' K slices of 64 and 128 at padded dimension 24 beside GPs of 20 rows (below its
+# 128-row switch), the rows shuffled over the roles as in ENSEMBLE
+WIDE_CASES = [
+    Case("e1_d6_n20_p3_f65", 10, 1, 6, ((20, 20),), 3, 65, 0.0, 8, None, 6.6e-16),
+    Case("e1_d13_n20_p3_f65", 11, 1, 13, ((20, 20),), 3, 65, 0.0, 8, None, 3.7e-16),
+    Case("e1_d20_n300_20_p3_f65", 12, 1, 20, ((300, 20),), 3, 65, 0.0, 8, None, 1.8e-16),
+    Case("e1_d32_n20_p3_f65", 13, 1, 32, ((20, 20),), 3, 65, 0.0, 8, None, 1.6e-16),
+    Case("e3_d20_n20_300_520_p3_f65", 14, 3, 20, ((20, 300), (300, 520), (520, 20)), 3, 65, 0.0, 8, None, 3.6e-16),
+]
+ENSEMBLE_WIDE = "e3_d20_n20_300_520_p3_f65"
+
+
 def case(name):
-    return next(c for c in CASES + [BELIEVED] if c.name == name)
+    return next(c for c in CASES + WIDE_CASES + [BELIEVED] if c.name == name)
 
 
 def random_front(rng, F, shift, ref=REF):

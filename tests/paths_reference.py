@@ -110,8 +110,9 @@ def run(paths, s, gd, bounds, candidates):
 
 
 # ---- the cases of tests/test_gpu_paths.py ----
-# seed, n, d, E, cov_type, M, S, C: values and gradients against long double.  d = 3, 10, 17, 32 pad to 4, 12, 24, 32; n on both sides
-# of the 256-thread stride; M on both sides of it and at the limit; S on both sides of the chunk of 8
+# seed, n, d, E, cov_type, M, S, C: values and gradients against long double.  d = 3, 6, 10, 13, 17, 32 pad to 4, 8, 12, 16, 24, 32; n
+# on both sides of the 256-thread stride; M on both sides of it and at the limit; S on both sides of the chunk of 8; n = 260 with
+# S = 70: more than 64 columns through the split-K side (n >= 128) of the set phase's triangular products
 EVAL_CASES = [
     (1, 20, 3, 1, SE, 64, 1, 7),
     (2, 130, 10, 3, MATERN, 100, 3, 5),
@@ -119,6 +120,9 @@ EVAL_CASES = [
     (4, 20, 17, 1, SE, 1024, 8, 4),
     (5, 20, 32, 3, MATERN, 64, 70, 3),
     (6, 300, 3, 1, SE, 4096, 1, 1),
+    (7, 20, 6, 1, SE, 64, 3, 5),
+    (8, 20, 13, 3, MATERN, 100, 9, 4),
+    (9, 260, 3, 1, MATERN, 64, 70, 3),
 ]
 # seed, n, d, E, cov_type, M, S, C, gd: the minimiser.  tests/test_paths_reference.py asserts that every decision of every path has a
 # margin of at least 1e-7: the seeds were chosen on the CPU so that this holds
@@ -129,7 +133,21 @@ DESCENT_CASES = [
     (3, 20, 17, 1, MATERN, 64, 9, 30, MAIN_INNER),
     (4, 20, 32, 1, SE, 64, 2, 30, MAIN_INNER),
     (20, 300, 3, 1, MATERN, 257, 2, 310, LONG12),
+    (5, 20, 6, 1, SE, 64, 3, 30, MAIN_INNER),
+    (6, 20, 13, 1, MATERN, 64, 3, 30, MAIN_INNER),
 ]
+# Rows past the evaluator's row cache (csrc/paths.hip keeps the first 3584 covariance entries of a point in LDS and recomputes the
+# rows behind them for every chunk of 8 paths): two chunks over 3600 rows at the feature limit, the largest LDS request there is.
+# Kept out of EVAL_CASES (gap() stays fast) and checked against the float64 form: CACHE_GAP is the float64-against-long-double
+# difference of this very case at cache_problem()'s points, as tests/test_paths_reference.py's measure_cache_gap() found it (value 5.92e-12,
+# gradient 2.98e-12; a minute of long-double factorisation, so the figure is recorded, not recomputed); the device's bound is
+# max(tolerance(), 4 CACHE_GAP)
+ROW_CACHE = 3584
+CACHE_CASE = (31, 3600, 3, 1, MATERN, 4096, 9, 5)
+CACHE_GAP = 6.0e-12
+# Two launches of the point kernels: 16384 points per launch (tests/test_gpu_paths.py asserts the figure by the launches it sees)
+PASS = 16384
+PASS_CASE = (32, 20, 3, 1, SE, 8, 1, PASS + 3)
 
 
 def case_problem(case, dtype=LD):
@@ -145,6 +163,22 @@ def case_problem(case, dtype=LD):
     rng = np.random.default_rng(7000 + seed)
     pts = np.vstack([rng.uniform(0.05, 0.95, size=(C_ - n, d)), a["X"]]) if C_ > n else rng.uniform(0.05, 0.95, size=(C_, d))
     return members, a, tables, np.array([[0.0, 1.0]] * d), pts
+
+
+def cache_problem(dtype=np.float64):
+    """case_problem for CACHE_CASE with its points each within 0.02 (per coordinate) of a sampled point behind the row cache"""
+    members, a, tables, bounds, _ = case_problem(CACHE_CASE, dtype)
+    n, d, C_ = CACHE_CASE[1], CACHE_CASE[2], CACHE_CASE[7]
+    rng = np.random.default_rng(7000 + CACHE_CASE[0])
+    rows = ROW_CACHE + rng.choice(n - ROW_CACHE, size=C_, replace=False)
+    pts = np.clip(a["X"][rows] + rng.uniform(-0.02, 0.02, size=(C_, d)), 0.0, 1.0)
+    return members, a, tables, bounds, pts, rows
+
+
+def tail_rows(paths, P, first=ROW_CACHE):
+    """sum_{j >= first} v_sj k(P_c, X_j) [S][C]: what the rows behind the cache add to f_s"""
+    P = np.asarray(P, dtype=np.float64).reshape(-1, paths.size)
+    return paths.v[:, first:] @ paths.m.cov(paths.m.X[first:], P)
 
 
 _GAP = {}

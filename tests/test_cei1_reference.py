@@ -20,7 +20,7 @@ from cornell_moe_amd import _lib, build as moe_build
 LD = cr.LD
 dp, ip = _lib.dp, _lib.ip
 
-CASES = cr.CASES
+CASES = cr.CASES + cr.WIDE_CASES
 
 
 def _ids(cases):
@@ -89,6 +89,21 @@ def test_every_case_is_qualified(case):
         assert abs(float(cr.evaluate(free, x).value - w.value)) >= 1e-3 * w.scale, (case.name, i)
         if case.p:
             assert abs(float(cr.evaluate(bare, x).value - w.value)) >= 1e-5 * w.scale, (case.name, i)
+
+
+def test_the_wide_case_stages_unequal_members_at_a_wide_padded_dimension():
+    from test_ei1_reference import padded_dim
+    c = cr.WIDE
+    assert c.E == 3 and c.K == 2 and c.p == 3 and c.C == 6 and padded_dim(c.d) == 24 and c.d % 8
+    assert all(sorted(row) == [20, 300, 600] for row in c.n) and len({row for row in c.n}) == 3
+    assert all(len({row[r] for row in c.n}) == 3 for r in range(3))  # (every role sees every row count)
+    # the believed-feasible rule takes both branches among the members: some pending point lowers an incumbent, another member's stays
+    for T in (LD, np.float64):
+        members = cr.ensemble(cr.make_problem(c), T)
+        assert any(m.mask.any() and float(m.bprime) < m.best - 1e-3 for m in members)
+        assert any(not m.mask.any() and float(m.bprime) == m.best for m in members)
+        for m in members:
+            assert min(abs(float(v) - t) for base, t in zip(m.bases[1:], m.taus) for v in cr.mean_at(base, m.P)) >= 1e-3
 
 
 def test_both_branches_of_the_incumbent_rule_bind():

@@ -21,7 +21,7 @@ from cornell_moe_amd import _lib, build as moe_build, expected_hypervolume_impro
 LD = hr.LD
 dp, ip = _lib.dp, _lib.ip
 
-CASES = hr.CASES + [hr.BELIEVED]
+CASES = hr.CASES + [hr.BELIEVED] + hr.WIDE_CASES
 
 
 def _ids(cases):
@@ -139,6 +139,41 @@ def test_every_case_is_qualified(case):
     # (with neither a front nor pending points there is nothing to dominate a candidate)
     if case.F or case.p:
         assert any(dominated) and not all(dominated), (case.name, dominated)
+
+
+def test_the_wide_cases_reach_every_instantiation_of_the_gradient_kernel():
+    from test_ei1_reference import padded_dim
+    reached = {}
+    for c in hr.CASES + hr.WIDE_CASES:
+        reached.setdefault(padded_dim(c.d), set()).add(padded_dim(c.d) - c.d)
+    assert set(reached) == {4, 8, 12, 16, 24, 32}
+    assert {0, 1, 2, 3, 4} <= set().union(*reached.values())  # (the padded coordinates)
+    for c in hr.WIDE_CASES:
+        p = hr.make_problem(c)
+        assert c.C == 8 and c.p == 3 and c.F >= 65 and len(p.checked) >= 4, c.name
+    # past one 256-row stride at a padded dimension other than 4, and three strides in the wide ensemble, one GP below 128 rows
+    assert any(c.E == 1 and padded_dim(c.d) == 24 and max(c.n[0]) + c.p > 256 for c in hr.WIDE_CASES)
+    w = hr.case(hr.ENSEMBLE_WIDE)
+    rows = sorted(n for row in w.n for n in row)
+    assert w.E == 3 and padded_dim(w.d) == 24 and rows[0] < 128 and rows[-1] + w.p > 512 and any(256 < n <= 512 for n in rows)
+    assert len({row for row in w.n}) == 3 and all(row[0] != row[1] for row in w.n)  # (the chains do not line up)
+
+
+def test_the_ensemble_compacts_a_front_tail_that_spans_lane_chunks():
+    """some member's believed-front log has a join in which at least 2 front points leave and at least 65 points behind them move
+    (the device moves the tail 64 lanes at a time)"""
+    p = hr.make_problem(hr.case(hr.ENSEMBLE))
+    seen = []
+    for m in hr.ensemble(p, np.float64):
+        for j, (what, left) in enumerate(m.log):
+            if what != "joined":
+                continue
+            before, _ = hr.believed_front(p.front, m.outcomes[:j], p.ref, np.float64)
+            a = float(m.outcomes[j][0])
+            lower = int(np.sum(before[:, 0] < a))
+            seen.append((left, len(before) - lower - left))
+    print("%s: (front points that leave, points behind them that move) per join %s" % (hr.ENSEMBLE, seen))
+    assert any(left >= 2 and moved >= 65 for left, moved in seen), seen
 
 
 # ---- 5. the believed-front rule ----

@@ -1,6 +1,7 @@
 """The constrained expected improvement on the device (csrc/cei1.hip: moe_ei_constrained_mcmc, moe_ei_constrained_mcmc_multistart,
-moe_ei_constrained_mcmc_suggest) against the long-double restatement of tests/cei1_reference.py, on the cases cei1_reference.CASES,
-whose inputs tests/test_cei1_reference.py qualifies on the CPU (float64 within 2.5e-11 scale of long double; at the checked
+moe_ei_constrained_mcmc_suggest) against the long-double restatement of tests/cei1_reference.py, on the cases cei1_reference.CASES
+and WIDE_CASES (three members of 20, 300 and 600 rows shuffled over the roles at padded dimension 24), whose inputs
+tests/test_cei1_reference.py qualifies on the CPU (float64 within 2.5e-11 scale of long double; at the checked
 candidates every feasibility factor in [0.02, 0.98], the value above 1e-3 scale, the gradient above 1e-2, and the constraints and
 the pending points each moving the value by far more than the bound here: a device that returned zeros, ignored the constraints or
 ignored P fails).
@@ -102,7 +103,10 @@ def _host_product(factors):
 
 
 # ---- 1. value, gradient and factors against long double; the bits of one call ----
-@pytest.mark.parametrize("case", cr.CASES, ids=[c.name for c in cr.CASES])
+ALL_CASES = cr.CASES + cr.WIDE_CASES
+
+
+@pytest.mark.parametrize("case", ALL_CASES, ids=[c.name for c in ALL_CASES])
 def test_against_the_long_double_restatement(case):
     p, want = cr.expected(case, LD)
     D = _Device(p)

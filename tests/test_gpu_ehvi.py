@@ -1,5 +1,6 @@
 """The two-objective expected hypervolume improvement on the device (csrc/ehvi1.hip: moe_ehvi_mcmc, moe_ehvi_mcmc_multistart,
-moe_ehvi_mcmc_suggest) against the long-double restatement of tests/ehvi_reference.py, on the cases ehvi_reference.CASES, whose
+moe_ehvi_mcmc_suggest) against the long-double restatement of tests/ehvi_reference.py, on the cases ehvi_reference.CASES and
+WIDE_CASES (every instantiation of the gradient kernel: padded dimensions 8, 16, 24 and 32, up to three 256-row strides), whose
 inputs tests/test_ehvi_reference.py qualifies on the CPU (at the checked candidates the value above 1e-3 scale, the gradient above
 1e-2, the front and the pending points each moving the value by far more than the bound here, some candidates' mean pairs dominated
 and some not: a device that returned zeros, ignored the front or ignored P fails).
@@ -28,7 +29,7 @@ LD = hr.LD
 dp, ip = _lib.dp, _lib.ip
 _Launches, _host_loop, _same_run = tc._Launches, tc._host_loop, tc._same_run
 
-CASES = hr.CASES + [hr.BELIEVED]
+CASES = hr.CASES + [hr.BELIEVED] + hr.WIDE_CASES
 
 
 class _Device(object):
@@ -200,6 +201,59 @@ def test_the_ascent_is_the_host_driven_loop_bit_for_bit(tolerance):
     none = api.ehvi_multistart(D.one, D.two, p.ref, p.front, gd, bounds, starts, gradient_ascent=False, points_being_sampled=pending)
     best = int(np.argmax(want["start_values"]))
     assert np.array_equal(none["point"], starts[best]) and none["value"] == want["start_values"][best] and none["found"]
+    D.close()
+
+
+MS_WIDE = dict(MS, starts=6, steps=4, restarts=1)  # (the host-driven loop over six GPs of up to 523 rows in 20 dimensions stays within seconds)
+
+
+def _wide_ascent_inputs(d):
+    rng = np.random.default_rng(77)
+    starts = rng.uniform(0.02, 0.98, size=(MS_WIDE["starts"], d))
+    gd = (MS_WIDE["starts"], MS_WIDE["steps"], MS_WIDE["restarts"], 0, MS_WIDE["gamma"], MS_WIDE["pre_mult"], MS_WIDE["max_rel"], 1e-10)
+    return starts, gd, np.array([[0.0, 1.0]] * d)
+
+
+def test_the_ascent_on_the_wide_ensemble_is_the_host_driven_loop_bit_for_bit():
+    """the ascent's own staging and step at padded dimension 24 over members of 20, 300 and 520 rows"""
+    p = hr.make_problem(hr.case(hr.ENSEMBLE_WIDE))
+    D = _Device(p)
+    starts, gd, bounds = _wide_ascent_inputs(p.points.shape[1])
+    pending = p.pending[:2]
+    want = _host_loop(lambda x, g: _eval(D, p, x, pending=pending, want_grad=g), starts, gd, bounds)
+    plain = api.ehvi_multistart(D.one, D.two, p.ref, p.front, gd, bounds, starts)
+    assert not np.array_equal(plain["start_values"], want["start_values"])  # (the pending points are not ignored)
+    bare = api.ehvi_multistart(D.one, D.two, p.ref, None, gd, bounds, starts, points_being_sampled=pending)
+    assert not np.array_equal(bare["start_values"], want["start_values"])  # (nor is the front)
+    for on in (True, False):
+        with _Launches(on):
+            got = api.ehvi_multistart(D.one, D.two, p.ref, p.front, gd, bounds, starts, want_path=True, points_being_sampled=pending)
+        diff = np.argwhere(np.any(got["path"] != want["path"], axis=2))
+        assert diff.size == 0, (on, "the paths part at (start, row)", diff[np.argmin(diff[:, 1])])
+        _same_run(got, want)
+    moved = float(np.max(np.abs(want["end_points"] - starts[want["kept_index"]])))
+    print("wide ensemble: %d kept starts, steps taken %s, value %.12g against the best start's %.12g; the ends lie up to %.3g from "
+          "their starts" % (len(want["kept_index"]), [int(k) for k in want["steps_taken"]], want["value"], want["start_values"].max(), moved))
+    assert want["found"] and len(want["kept_index"]) == MS_WIDE["starts"] and moved > 1e-3 and int(want["steps_taken"].max()) == 4
+    D.close()
+
+
+def test_the_batch_on_the_wide_ensemble_is_the_ascent_fed_its_predecessor_bit_for_bit():
+    p = hr.make_problem(hr.case(hr.ENSEMBLE_WIDE))
+    D = _Device(p)
+    starts, gd, bounds = _wide_ascent_inputs(p.points.shape[1])
+    pending = p.pending[:1]
+    first = api.ehvi_multistart(D.one, D.two, p.ref, p.front, gd, bounds, starts, points_being_sampled=pending)
+    second = api.ehvi_multistart(D.one, D.two, p.ref, p.front, gd, bounds, starts,
+                                 points_being_sampled=np.vstack([pending, first["point"][None, :]]))
+    assert first["found"] and second["found"]
+    for on in (True, False):
+        with _Launches(on):
+            got = api.ehvi_suggest(D.one, D.two, p.ref, p.front, gd, bounds, starts, 2, points_being_sampled=pending)
+        assert np.array_equal(got["points"], np.array([first["point"], second["point"]])), on
+        assert np.array_equal(got["values"], np.array([first["value"], second["value"]])) and np.all(got["found"])
+    print("wide ensemble: greedy values %.12g, %.12g; the second pick lies %.3g from the first" % (
+        first["value"], second["value"], float(np.max(np.abs(second["point"] - first["point"])))))
     D.close()
 
 

@@ -1,6 +1,7 @@
 """The log constrained expected improvement on the device (csrc/logcei1.hip: moe_log_ei_constrained_mcmc,
 moe_log_ei_constrained_mcmc_multistart, moe_log_ei_constrained_mcmc_suggest) against the long-double restatement of
-tests/logcei1_reference.py, on cei1_reference.CASES at the three shifts of logcei1_reference.SHIFTS, whose inputs
+tests/logcei1_reference.py, on cei1_reference.CASES at the three shifts of logcei1_reference.SHIFTS and cei1_reference.WIDE_CASES
+(unequal members at padded dimension 24) unshifted and at the deepest shift, whose inputs
 tests/test_logcei1_reference.py qualifies on the CPU (float64 within 2.5e-11 of long double, the pending points moving a checked
 value by at least 1e-5, the stall problems stalling the plain form in float64 and letting the log form climb).
 
@@ -29,7 +30,8 @@ LD = lr.LD
 dp, ip = _lib.dp, _lib.ip
 BOUND = 1e-10
 
-CASE_SHIFTS = [(c, s) for c in lr.CASES for s in lr.SHIFTS]
+CASE_SHIFTS = [(c, s) for c in lr.CASES for s in lr.SHIFTS] + [(c, s) for c in lr.WIDE_CASES for s in lr.WIDE_SHIFTS]
+ALL_CASES = lr.CASES + lr.WIDE_CASES
 IDS = ["%s-b%g-t%g" % (c.name, s[0], s[1]) for c, s in CASE_SHIFTS]
 
 
@@ -126,7 +128,7 @@ def test_against_the_long_double_restatement(case, shift):
 
 
 # ---- 2. against the plain form ----
-@pytest.mark.parametrize("case", lr.CASES, ids=[c.name for c in lr.CASES])
+@pytest.mark.parametrize("case", ALL_CASES, ids=[c.name for c in ALL_CASES])
 def test_exp_of_the_value_is_the_constrained_expected_improvement(case):
     p, plain = cr.expected(case, LD)
     D = _Device(p)

@@ -1,6 +1,8 @@
 """Posterior function paths and their minimisers on the device (csrc/paths.hip: moe_gp_paths_evaluate, moe_gp_paths_minimize) against
-tests/paths_reference.py, at the smallest shapes that reach every dispatch edge: d = 3, 10, 17, 32 (padded to 4, 12, 24, 32), n on
-both sides of the 256-thread stride, M = 64 .. 4096, S on both sides of the chunk of 8, one and three members, both covariances.
+tests/paths_reference.py, at the smallest shapes that reach every dispatch edge: d = 3, 6, 10, 13, 17, 32 (padded to 4, 8, 12, 16,
+24, 32), n on both sides of the 256-thread stride, M = 64 .. 4096, S on both sides of the chunk of 8 and of 64 columns on the split-K
+side of the set phase, one and three members, both covariances; rows behind the evaluator's row cache (n = 3600) and points behind
+its first launch (C = 16384 + 3) in tests of their own.
 
 Values and gradients are held to paths_reference.tolerance() = max(1e-10, 4 gap()) against the extended-precision form, relative to
 max(1, |f|) (a gradient: to max(1, its largest component)).  A (path, point) value must carry the same bits whatever C, S, E and
@@ -10,6 +12,10 @@ on the CPU); the descent is checked step by step along the device's own trace, |
 max(1, |grad f|_inf) per coordinate, and end to end within 10 x paths_reference.end_gap() floored at 1e-12, as
 tests/test_gpu_pm_members.py derives its own.  Every test prints the worst figures it saw (pytest -s)."""
 import ctypes as C
+import os
+import re
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -68,6 +74,111 @@ def test_values_and_gradients(case, problems):
     one_v, one_g = api.paths_evaluate([gps[e]], *_tab(tab, [e], [s]), pts[c:c + 1], want_grad=True)
     assert one_v[0, 0, 0] == values[e, s, c] and np.array_equal(one_g[0, 0, 0], grad[e, s, c])
     assert all(np.array_equal(u, g.mean(probe)) for u, g in zip(before, gps))  # the handles answer as before
+
+
+def test_rows_behind_the_row_cache():
+    """paths_reference.CACHE_CASE: n = 3600 rows, M = 4096 features (the largest LDS request), S = 9 paths in two chunks -- the second
+    reads the cached rows back and recomputes rows 3584 .. 3599 -- at points beside sampled points behind the cache, where those rows
+    add at least 1e-3 to every value (tests/test_paths_reference.py).  Against the float64 form within max(tolerance(), 4 CACHE_GAP);
+    the cached kernel, the evaluation kernel that has no cache, a (path, point) alone and the minimiser's screening carry the same
+    bits."""
+    members, a, tab, bounds, pts, rows = pp.cache_problem(np.float64)
+    S, C_ = pp.CACHE_CASE[6], pp.CACHE_CASE[7]
+    gps = _gps(a, pp.CACHE_CASE[4])
+    values, grad = api.paths_evaluate(gps, *_tab(tab), pts, want_grad=True)
+    want, wg = members[0].values(pts), members[0].grads(pts)
+    bound = max(pp.tolerance(), 4.0 * pp.CACHE_GAP)
+    e_v = float(np.max(np.abs(values[0] - want) / np.maximum(1.0, np.abs(want))))
+    e_g = float(np.max(np.abs(grad[0] - wg)) / max(1.0, float(np.max(np.abs(wg)))))
+    tail = float(np.min(np.abs(pp.tail_rows(members[0], pts))))
+    print("n = %d, M = %d, S = %d: value error %.3g, gradient error %.3g against float64 (bound %.3g); the rows behind the cache add at "
+          "least %.3g" % (pp.CACHE_CASE[1], pp.CACHE_CASE[5], S, e_v, e_g, bound, tail))
+    assert e_v <= bound and e_g <= bound
+    plain = api.paths_evaluate(gps, *_tab(tab), pts)  # (the cached kernel against the evaluation that has no cache)
+    assert np.array_equal(plain, values)
+    for s, c in ((3, 1), (S - 1, C_ - 1)):  # a path of the first chunk, one of the second
+        one = api.paths_evaluate(gps, *_tab(tab, [0], [s]), pts[c:c + 1])
+        assert one[0, 0, 0] == values[0, s, c], (s, c)
+        one_v, one_g = api.paths_evaluate(gps, *_tab(tab, [0], [s]), pts[c:c + 1], want_grad=True)
+        assert one_v[0, 0, 0] == values[0, s, c] and np.array_equal(one_g[0, 0, 0], grad[0, s, c]), (s, c)
+    res = api.paths_minimize(gps, *_tab(tab), pp.MAIN_INNER, bounds, pts, want_screened=True)
+    assert np.array_equal(res["screened"], values)
+
+
+def test_points_behind_the_first_launch():
+    """paths_reference.PASS_CASE: C = 16384 + 3 points make a second launch of the point kernels, without and with the gradient.  The
+    points on both sides of the boundary against long double at tolerance(), and bit for bit against themselves alone in a call."""
+    case = pp.PASS_CASE
+    members, a, tab, bounds, pts = pp.case_problem(case, LD)
+    C_ = case[7]
+    assert C_ == pp.PASS + 3 and len(pts) == C_
+    checked = [0, pp.PASS - 1, pp.PASS, C_ - 1]
+    gps = _gps(a, case[4])
+    plain = api.paths_evaluate(gps, *_tab(tab), pts)
+    values, grad = api.paths_evaluate(gps, *_tab(tab), pts, want_grad=True)
+    assert np.array_equal(plain, values) and np.all(np.isfinite(values)) and np.all(np.isfinite(grad))
+    want, wg = members[0].values(pts[checked]), members[0].grads(pts[checked])
+    tol = pp.tolerance()
+    e_v = float(np.max(np.abs(values[0][:, checked] - want) / np.maximum(1.0, np.abs(want.astype(np.float64)))))
+    e_g = float(np.max(np.abs(grad[0][:, checked] - wg)) / max(1.0, float(np.max(np.abs(wg)))))
+    print("C = %d: value error %.3g, gradient error %.3g at the points %s (bound %.3g)" % (C_, e_v, e_g, checked, tol))
+    assert e_v <= tol and e_g <= tol
+    for c in checked:
+        one = api.paths_evaluate(gps, *_tab(tab), pts[c:c + 1])
+        one_v, one_g = api.paths_evaluate(gps, *_tab(tab), pts[c:c + 1], want_grad=True)
+        assert one[0, 0, 0] == values[0, 0, c] and one_v[0, 0, 0] == values[0, 0, c] and np.array_equal(one_g[0, 0, 0], grad[0, 0, c]), c
+    # (no point was left at the output's initial zeros, and the points behind the boundary are not copies of those before it)
+    assert np.all(values != 0.0) and not np.array_equal(values[0, 0, pp.PASS:], values[0, 0, :3])
+
+
+_LAUNCH_PROBE = r"""
+import sys
+sys.path[:0] = [%r, %r]
+import numpy as np
+import paths_reference as pp
+from cornell_moe_amd import api
+case = pp.PASS_CASE
+members, a, tab, bounds, pts = pp.case_problem(case, np.float64)
+gps = [api.DeviceGP(a["hypers"][0], a["X"], a["y"], a["noises"][0], cov_type=case[4])]
+tables = (tab["frequencies"], tab["phases"], tab["weights"], tab["noise_normals"])
+for C_ in (pp.PASS, pp.PASS + 3):
+    for grad in (0, 1):
+        sys.stderr.write("\nCALL %%d %%d\n" %% (C_, grad))
+        sys.stderr.flush()
+        api.paths_evaluate(gps, *tables, pts[:C_], want_grad=bool(grad))
+"""
+
+
+def test_the_point_kernels_take_16384_points_per_launch():
+    """what test_points_behind_the_first_launch assumes of csrc/paths.hip, by the behaviour: a fresh process under the HIP runtime's
+    launch log (AMD_LOG_LEVEL=3: a launch's grid, then the kernel's name) evaluates 16384 and 16384 + 3 points without and with the
+    gradient; the point kernel and the gradient kernel go out once over 16384 points, then over 16384 and over 3"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, AMD_LOG_LEVEL="3")
+    env.pop("AMD_LOG_MASK", None)
+    env.pop("AMD_LOG_LEVEL_FILE", None)
+    run = subprocess.run([sys.executable, "-c", _LAUNCH_PROBE % (root, os.path.join(root, "tests"))], env=env, stdout=subprocess.PIPE,
+                         stderr=subprocess.PIPE, universal_newlines=True, timeout=300)
+    assert run.returncode == 0, run.stderr[-2000:]
+    launches, call, grid = {}, None, None
+    for line in run.stderr.splitlines():
+        m = re.match(r"CALL (\d+) (\d+)$", line)
+        if m:
+            call = (int(m.group(1)), int(m.group(2)))
+            launches[call] = []
+            continue
+        m = re.search(r"hipLaunchKernel \( *\S+, *\{(\d+),(\d+),(\d+)\}", line)
+        if m:
+            grid = tuple(int(v) for v in m.groups())
+            continue
+        m = re.search(r"ShaderName : .*\b(paths_points_kernel|paths_grad_kernel)<", line)
+        if m and call is not None:
+            launches[call].append((m.group(1), grid))
+    print("launches of the point kernels per call (points, want_grad): %s" % launches)
+    assert pp.PASS == 16384
+    for grad, name in ((0, "paths_points_kernel"), (1, "paths_grad_kernel")):
+        assert launches[(pp.PASS, grad)] == [(name, (pp.PASS, 1, 1))]
+        assert launches[(pp.PASS + 3, grad)] == [(name, (pp.PASS, 1, 1)), (name, (3, 1, 1))]
 
 
 def test_feature_limit():

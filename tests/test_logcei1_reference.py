@@ -22,7 +22,8 @@ LD = lr.LD
 dp, ip = _lib.dp, _lib.ip
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "moe_hip.h")
 
-CASE_SHIFTS = [(c, s) for c in lr.CASES for s in lr.SHIFTS]
+CASE_SHIFTS = [(c, s) for c in lr.CASES for s in lr.SHIFTS] + [(c, s) for c in lr.WIDE_CASES for s in lr.WIDE_SHIFTS]
+ALL_CASES = lr.CASES + lr.WIDE_CASES
 IDS = ["%s-b%g-t%g" % (c.name, s[0], s[1]) for c, s in CASE_SHIFTS]
 
 SCALAR_POINTS = list(np.linspace(-12.0, 12.0, 97)) + [-20.0, -38.5, -50.0, -100.0, -1e3, -1e5, -1e8, -1e12, -3e15, 20.0, 40.0, 100.0]
@@ -81,7 +82,7 @@ def test_float64_agrees_with_long_double(case, shift):
     assert worst_v <= 2.5e-11 and worst_g <= 2.5e-11 and worst_f <= 2.5e-11
 
 
-@pytest.mark.parametrize("case", lr.CASES, ids=[c.name for c in lr.CASES])
+@pytest.mark.parametrize("case", ALL_CASES, ids=[c.name for c in ALL_CASES])
 def test_exp_of_the_value_is_the_plain_form(case):
     """shift (0, 0), long double: exp(value) is tests/cei1_reference.py's value, the log factors the logs of its factors"""
     p, want = lr.expected(case, lr.SHIFTS[0], LD)
@@ -96,11 +97,11 @@ def test_exp_of_the_value_is_the_plain_form(case):
     assert worst <= 1e-15
 
 
-@pytest.mark.parametrize("case", [c for c in lr.CASES if c.p], ids=[c.name for c in lr.CASES if c.p])
+@pytest.mark.parametrize("case", [c for c in ALL_CASES if c.p], ids=[c.name for c in ALL_CASES if c.p])
 def test_the_pending_points_move_the_value(case):
     p0 = lr.make_problem(case)
     bare = cr.ensemble(p0, LD, pending=p0.pending[:0])
-    for shift in lr.SHIFTS:
+    for shift in (lr.WIDE_SHIFTS if case in lr.WIDE_CASES else lr.SHIFTS):
         p, want = lr.expected(case, shift, LD)
         without = lr.relimited(bare, p.best, p.thresholds)
         moved = max(abs(float(lr.evaluate(without, p.points[i]).value - want[i].value)) for i in p.checked)

@@ -88,6 +88,42 @@ def test_descent_case_margins(case):
     assert worst >= MARGIN
 
 
+def test_the_cases_reach_every_padded_dimension_and_the_split_k_side_with_many_columns():
+    from test_ei1_reference import padded_dim
+    assert {padded_dim(c[2]) for c in pp.EVAL_CASES} == {4, 8, 12, 16, 24, 32}
+    assert {padded_dim(c[2]) for c in pp.DESCENT_CASES} == {4, 8, 12, 16, 24, 32}
+    assert any(padded_dim(c[2]) in (8, 16) and c[3] == 3 for c in pp.EVAL_CASES)
+    assert any(c[1] >= 128 and c[6] > 64 for c in pp.EVAL_CASES)  # (n on the split-K side, more than 64 columns)
+
+
+def measure_cache_gap():
+    """(value, gradient): the float64-against-long-double difference of CACHE_CASE at its points, as paths_reference.gap() measures
+    EVAL_CASES -- about a minute for the long-double factor of 3600 rows, so paths_reference.CACHE_GAP records the result and no
+    test calls this"""
+    m64, _, _, _, pts, _ = pp.cache_problem(np.float64)
+    mld = pp.cache_problem(LD)[0]
+    want, got = mld[0].values(pts), m64[0].values(pts)
+    wg, gg = mld[0].grads(pts), m64[0].grads(pts)
+    return (float(np.max(np.abs(got - want) / np.maximum(1.0, np.abs(want.astype(np.float64))))),
+            float(np.max(np.abs(gg - wg)) / max(1.0, float(np.max(np.abs(wg))))))
+
+
+def test_the_rows_behind_the_cache_carry_every_checked_value():
+    """at every (path, point) of CACHE_CASE the rows j >= 3584 add at least 1e-3 to f_s: a device that drops, repeats or mis-indexes
+    them misses the value by ten million times tests/test_gpu_paths.py's bound"""
+    members, a, tab, bounds, pts, rows = pp.cache_problem(np.float64)
+    n, S, C_ = pp.CACHE_CASE[1], pp.CACHE_CASE[6], pp.CACHE_CASE[7]
+    assert n > pp.ROW_CACHE and S > 8 and len(members) == 1 and pp.CACHE_CASE[5] == 4096
+    assert np.all(rows >= pp.ROW_CACHE) and len(set(rows.tolist())) == C_ and float(np.max(np.abs(pts - a["X"][rows]))) <= 0.02
+    tail = np.abs(pp.tail_rows(members[0], pts))
+    assert tail.shape == (S, C_)
+    print("n = %d: the rows behind %d add between %.3g and %.3g to f_s; recorded float64 - long double %.3g" % (
+        n, pp.ROW_CACHE, float(tail.min()), float(tail.max()), pp.CACHE_GAP))
+    assert float(tail.min()) >= 1e-3
+    # the bound the device is held to stays far below what the rows carry
+    assert 0.0 < pp.CACHE_GAP and max(pp.tolerance(), 4.0 * pp.CACHE_GAP) <= 1e-4 * float(tail.min())
+
+
 def test_the_two_arithmetics_agree():
     g = pp.gap()
     print("gap %.3g, device tolerance %.3g" % (g, pp.tolerance()))
