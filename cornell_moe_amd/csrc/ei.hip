@@ -539,8 +539,6 @@ EiPending ei_launch(GpDev& gp, const double* Xq_all, int num_evals, const double
 #define MOE_EI_STATE(FUSED, UM)                                                                                                      \
   {                                                                                                                                \
     auto kern = ei_state_kernel<FUSED, UM>;                                                                                        \
-    if (shm > 48 * 1024)                                                                                                           \
-      MOE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm)); \
     launch_kernel_ens<ei_state_kernel_body<FUSED, UM>, 256>(kern, dim3(E), dim3(256), shm, s, sp);                                 \
   }
     if (se.fused) {

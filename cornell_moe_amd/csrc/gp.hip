@@ -565,7 +565,7 @@ KgStateEnqueued enqueue_kg_state_batch(GpDev& gp, const double* U_all, int u, in
   const int m = lay.m, ng = bl.ngrad, R = ng + A, N = gp.N;
   const long ctot = bl.total();
   const long cm = (long)E * m;
-  gp.dVE.reserve((size_t)N * cm * 2);  // (the second half: workspace of the gradient tail's K^-1 TB, kg.hip)
+  gp.dVE.reserve((size_t)N * cm * 2);  // (the second half: workspace of the gradient tail's K^-1 TB, kg_tail.hip)
   gp.dWE.reserve((size_t)N * cm);
   // (one workspace for the split-K partials of the triangular products -- here and in the gradient tail -- and of the Gram kernels)
   // (the two Gram kernels' partials side by side: with m <= 8 they stay there for kg_state.hip to add up)

@@ -48,7 +48,7 @@ struct GpDev {
   PinnedBuf<double> hYc;  // y - mean on its way to the device, and the factorisation's status word on its way back
   // reusable workspaces of the KG evaluator (kg.hip)
   DevBuf<double> kBlob, kNormals, kTab, kBestPoint, kBestValue, kBeta, kT, kC, kTB, kOut, kSW, kSWpart, kZcPart, kV;
-  DevBuf<double> kStartTab;  // the start table of the line searches, [E][A][1 + m][dp + 1] (kg.hip: kg_start_table_kernel)
+  DevBuf<double> kStartTab;  // the start table of the line searches, [E][A][1 + m][dp + 1] (kg_prep.hip: kg_start_table_kernel)
   DevBuf<unsigned long long> kCounters;
   DevBuf<unsigned int> kEiTicket;  // arrival counters of ei_mc_kernel's fused final sum (ei.hip)
   bool ei_ticket_dirty = false;  // a launch of ei_mc_kernel was enqueued and its completion not yet seen: an aborted launch leaves

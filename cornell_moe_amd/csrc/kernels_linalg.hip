@@ -841,8 +841,6 @@ void launch_tri_skinny(char op, int N, int c, const double* T, long ldt, const d
     // (LDS: reduction slots 8 x CB x 64 + B chunk 512 x CB doubles: 64 KB at CB = 8)
     auto kern = tri_skinny_n_kernel<CB, 16>;
     const size_t shm = sizeof(double) * ((size_t)8 * CB * 64 + (size_t)512 * CB);
-    if (shm > 48 * 1024)
-      MOE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
     launch_kernel_ens<tri_skinny_n_kernel_body<CB, 16>, 1024>(kern, dim3((N + 63) / 64, groups), dim3(1024), shm, s, N, T, ldt, B, ldb, c, C, ldc);
   } else {
     // (several columns of T per wavefront where the call has the columns of many evaluations: MOE_TRI_SKINNY_TJ=1: one, A/B runs)

@@ -1,41 +1,31 @@
 // cornell_moe_amd/csrc/kg.hip -- q-KG / d-KG Monte-Carlo evaluation (value + gradient) on gfx950: host orchestration of
-// one BATCH of independent evaluations (the multistart axis) and the kernels of the gradient tail.
+// one BATCH of independent evaluations (the multistart axis).  This unit is the driver alone -- argument checks, the plan of the MC
+// step, the records, the phases of one kg_launch and the batching around it; every kernel it launches lives in a unit of its own.
 //
 // Pipeline for a batch of E evaluations (every stage is one launch, or one launch per kind, for the whole batch):
-//   1. state set-up (gp.hip compute_state_batch): K*(X, Xu_e), dK*/dXq_e, K(X, discretised set_e) -> L^-1 / K^-1 applies
-//      (tile GEMMs against the explicit inverse factor) -> Gram matrices; ONE device->host sync brings the c x c Grams back
-//      and the m x m algebra of PointsToSampleState / KnowledgeGradientState (gpp_math.cpp:600-653,
-//      gpp_knowledge_gradient_optimization.cpp:292-317) runs on the host (host_math.hip);
-//   2. MC kernel (kg_mc.hpp and its family headers kg_mc_{wave,lane,stream,block}.hpp): persistent wavefronts, one MC sample at a time per wave, all E evaluations in one launch;
-//   3. gradient tail (.cpp:199-225 restated so that nothing of size M x (q d) is ever formed):
-//        T   = K(X, x*_i) for every sample                      (covariance build, N x M per evaluation, HBM write-bound)
-//        c_i = L^-1 ( K(Xu, x*_i) - W^T T_i )                   (kg_sw_kernel: one wave per sample)
-//        TB  = sum_i T_i beta_i^T                               (kg_tb_kernel + fixed-order chunk reduction)
-//      and three small reductions  ZC = sum_i z_i c_i^T (m x m),  DIR = sum_i beta_i,(k,b) dK(Xu_k, x*_i)[b,0]/dXu_k,
-//      GTB = (K^-1 dK*/dXq)^T TB,  from which the host assembles
-//        grad KG[k,dd] = ( [winner = k] M grad mu_k  -  sum_b (DIR - GTB)[(k,b),dd]  +  < L^-1 dL/dXq_k,dd , ZC > ) / M.
-//      This is  sum_i z_i^T d(c_i)/dXq_k  of the reference (gpp_math.cpp:1601-1651) with the sum over samples pulled inside.
-//      (q-KG, m <= 8: T is never written and, by default, c_i never formed -- ZC = L^T (KB - TB^T W) L^-T, see launch_fused_tail.)
+//   1. state set-up (gp.hip enqueue_kg_state_batch): K*(X, Xu_e), dK*/dXq_e, K(X, discretised set_e) -> L^-1 / K^-1 applies
+//      (tile GEMMs against the explicit inverse factor) -> Gram matrices, then the m x m algebra of PointsToSampleState /
+//      KnowledgeGradientState (gpp_math.cpp:600-653, gpp_knowledge_gradient_optimization.cpp:292-317) on the device (kg_state.hip);
+//   2. the coordinate tables, the start table, the sample pre-pass and the weight table where the plan has them (kg_prep.hip), and the
+//      MC kernel (kg_mc.hpp, its family headers kg_mc_{wave,lane,stream,block}.hpp and the kg_mc_dp*.hip units): persistent wavefronts,
+//      one MC sample at a time per wave, all E evaluations in one launch;
+//   3. gradient tail (kg_tail.hip: T-free for q-KG, else through the materialised N x M covariance matrix), or the sum of the samples'
+//      values, and the finish kernels of kg_state.hip.
 // All reductions use fixed orders, so results are bitwise reproducible for a given shard layout.
 #include "kg.hpp"
 
 #include <algorithm>
 #include <array>
-#include <atomic>
-#include <exception>
-#include <mutex>
-#include <thread>
 #include <memory>
 #include <optional>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
 
-#include "device_cov.hpp"
-#include "fastmath.hpp"
-#include "gemm128.hpp"
 #include "kg_mc.hpp"
+#include "kg_prep.hpp"
 #include "kg_state.hpp"
+#include "kg_tail.hpp"
 
 namespace moe {
 
@@ -46,929 +36,6 @@ void set_ensemble_members_hint(int members) { t_ens_members_hint = members > 1 ?
 
 
 namespace {
-
-__device__ __forceinline__ double wave_sum64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// Sum over a 256-thread workgroup in a fixed order; result valid in thread 0.
-__device__ __forceinline__ double block_sum_256(double v, double* red) {
-  const double w = wave_sum64(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-struct TabParams {
-  int perm[kMaxDimPadded];
-  double inv_lp[kMaxDimPadded];
-  double center[kMaxDimPadded];  // training-set mean per table row (unscaled)
-};
-
-// XsTab[e][tile][r][lane] = coordinate perm[r] of point (tile*64 + lane) of evaluation e, minus the training-set mean of that
-// coordinate, divided by its length scale (centred first: the difference of two nearby numbers is exact, so the scaled
-// coordinates carry the precision of the distances however far from the origin the domain sits):
-// the n training points, then the u union points of that evaluation, zero beyond.
-// (r5: the workgroups of evaluation 0 also clear the call's counter block -- pass counters, sample tickets -- which a memset did before)
-struct build_xs_tab_kernel_body {
-  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, const double* __restrict__ X, int n, const double* __restrict__ XuAll, int u, int dp, int ntiles, const TabParams& tp, double* __restrict__ tab, long tab_stride, int pair_rows, unsigned long long* __restrict__ ctr, long n_ctr) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    const int e = blockIdx.y;
-    if (e == 0)
-      for (long i = idx; i < n_ctr; i += (long)gridDim.x * blockDim.x) ctr[i] = 0ull;
-    if (idx >= ntiles * dp * 64) return;
-    const int l = idx & 63, r = (idx >> 6) % dp, t = (idx >> 6) / dp;
-    const int j = t * 64 + l;
-    const int k = tp.perm[r];
-    double v = tp.center[r];  // padded points sit at the centre (zero weight; a far-away pad would only stress the exp)
-    if (j < n)
-      v = X[(long)j * dp + k];
-    else if (j < n + u)
-      v = XuAll[((long)e * u + (j - n)) * dp + k];
-    // (pair_rows: the rows of a point in pairs, [tile][dp / 2][64][2] -- one 16-byte load per lane and pair, kg_mc_lds.hpp WideEval)
-    const long out = pair_rows ? (((long)t * (dp / 2) + (r >> 1)) * 64 + l) * 2 + (r & 1) : idx;
-    tab[(long)e * tab_stride + out] = (v - tp.center[r]) * tp.inv_lp[r];
-  }
-};
-__global__ __launch_bounds__(256) void build_xs_tab_kernel(const double* __restrict__ X, int n, const double* __restrict__ XuAll, int u, int dp,
-                                    int ntiles, TabParams tp, double* __restrict__ tab, long tab_stride, int pair_rows,
-                                    unsigned long long* __restrict__ ctr, long n_ctr) {
-  build_xs_tab_kernel_body::run(MOE_VBLOCK, MOE_VGRID, nullptr, X, n, XuAll, u, dp, ntiles, tp, tab, tab_stride, pair_rows, ctr, n_ctr);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Gradient tail kernels
-// ---------------------------------------------------------------------------------------------------------------------
-struct KgTailParams {
-  CovParams cp;
-  DerivList derivs;  // the GP's derivative observations (carried by the union points too)
-  int u, q, m, g, N, E, num_local, first_sample, ngrad, chunks, sw_chunk;
-  int chunk_len;  // samples per TB partial (kTbChunk, or kFusedChunk on the T-free q-KG path): chunks = ceil(num_local / chunk_len)
-  const double* T;           // [N x E*num_local], ld N
-  const double* SW;          // optional precomputed W^T T, [m x E*num_local] col-major (large m: tile GEMM); else null
-  const double* W;           // evaluation e at W + e * w_stride, [N x m], ld N
-  long w_stride;
-  const double* Gm;          // dK*/dXq: evaluation e at Gm + e * g_stride, [N x ngrad], ld N
-  long g_stride;
-  const double* Linv;        // the GP's explicit inverse factor (ld ldL) and 2 N E m doubles of workspace: K^-1 TB (launch_gtb)
-  long ldL;
-  double* work;
-  double* tri_work;          // tri_cols_work_doubles(N, E m) doubles (split-K partials)
-  const double* blob;
-  KgRec rec;
-  int rec_bp;                // offset of best_posterior inside a record
-  const double* best_point;  // [E][num_local][dp]
-  const double* best_value;  // [E][num_local]
-  const double* beta;        // [E][num_local][m]
-  const double* normals;     // [ceil(M/2)][m]
-  double* C;                 // [E][num_local][m]   c_i = L^-1 cov_n(Xu, x*_i)
-  double* TBpart;            // [E][chunks][m][N]
-  double* out;               // [E][out_stride]: kg_sum | ZC (m*m, col-major) | DIR (ngrad) | GTB (ngrad)
-  int out_stride;
-};
-
-constexpr int kTbChunk = 256;  // samples per workgroup of kg_tb_kernel
-constexpr int kTbChunkWide = 2048;  // m > 64: samples per partial of the matrix-pipe TB product (kg_tb128_kernel)
-// ... and of kg_fused_point_kernel: 128, so that ONE q-KG evaluation (n = 1000: 4 row blocks x 79 chunks) puts more than one
-// workgroup on every CU -- 40.7 -> ~20 us of a batch-1 evaluation's tail.  Fixed per path, not per batch size: an evaluation's
-// bits do not depend on what it is batched with.
-constexpr int kFusedChunk = 128;
-constexpr int kDirSlices = 32;  // sample ranges of kg_dir_kernel
-
-// c_i = L^-1 ( K(Xu, x*_i)[:, 0] - W^T T_i ) for every sample; one wavefront per sample at a time, lane r owns component r.
-// S_W = W^T T_i comes either precomputed (P.SW: tile GEMM, large m) or is formed here by lanes striding the N rows with
-// W_e staged ONCE per workgroup in LDS ([c][row], conflict-free) and reused for the kSwChunk samples of the workgroup --
-// re-reading W from L2 for every sample (N m 8 bytes each) made this the slowest kernel of the tail.
-constexpr int kSwChunk = 64;  // samples per workgroup (16 per wavefront); 16 when the batch is too small to fill the chip
-
-// SLOTS = 2: components lane and lane + 64 (m up to 128; S_W always precomputed there).
-template <int DP, int MU, int SLOTS = 1>
-struct kg_sw_kernel_body {
-  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, const KgTailParams& P) {
-    extern __shared__ __attribute__((aligned(16))) double Ws[];  // [m][N] when P.SW == nullptr
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int e = blockIdx.y;
-    const int m = P.m, g1 = 1 + P.g, N = P.N;
-    const double* rec = P.blob + (long)e * P.rec.stride;
-    const double* Lsm = rec + P.rec.L;
-    if (P.SW == nullptr) {
-      const double* We = P.W + (long)e * P.w_stride;
-      for (int t = threadIdx.x; t < N * m; t += 256) Ws[t] = We[t];  // W_e is [N x m] col-major == [c][row]
-      __syncthreads();
-    }
-    const int i1 = min(P.num_local, (int)(blockIdx.x + 1) * P.sw_chunk);
-    for (int i = blockIdx.x * P.sw_chunk + wave; i < i1; i += 4) {
-      const long w = (long)e * P.num_local + i;
-      double mine[SLOTS];
-  #pragma unroll
-      for (int sl = 0; sl < SLOTS; ++sl) mine[sl] = 0.0;
-      if (P.SW != nullptr) {
-  #pragma unroll
-        for (int sl = 0; sl < SLOTS; ++sl)
-          if (lane + 64 * sl < m) mine[sl] = P.SW[w * m + lane + 64 * sl];
-      } else {
-        const double* Tc = P.T + w * N;
-        double acc[MU];
-  #pragma unroll
-        for (int c = 0; c < MU; ++c) acc[c] = 0.0;
-  #pragma unroll 4
-        for (int row = lane; row < N; row += 64) {
-          const double t = Tc[row];
-  #pragma unroll
-          for (int c = 0; c < MU; ++c)
-            if (c < m) acc[c] = fma(Ws[c * N + row], t, acc[c]);
-        }
-  #pragma unroll
-        for (int c = 0; c < MU; ++c) {
-          const double v = wave_sum64(acc[c]);
-          if (lane == c) mine[0] = v;
-        }
-      }
-      double R[SLOTS], cv[SLOTS];
-  #pragma unroll
-      for (int sl = 0; sl < SLOTS; ++sl) {
-        R[sl] = 0.0;
-        cv[sl] = 0.0;
-        const int comp = lane + 64 * sl;
-        if (comp < m) {
-          const int r = comp / g1, b = comp - r * g1;
-          const double* Xu = rec + P.rec.XuP + (long)r * DP;
-          const double* xs = P.best_point + w * DP;
-          double diff[DP];
-          double r2 = 0.0;
-  #pragma unroll
-          for (int k = 0; k < DP; ++k) {
-            diff[k] = Xu[k] - xs[k];
-            r2 = fma(diff[k] * diff[k], P.cp.inv_l2[k], r2);
-          }
-          const Radial rd = radial_scalars(P.cp.type, P.cp.alpha, r2);
-          DerivList none;
-          none.g = 0;
-          R[sl] = cov_entry<DP>(P.cp, rd, diff, b, 0, P.derivs, none) - mine[sl];
-        }
-      }
-      for (int r = 0; r < m; ++r) {
-        double part = 0.0;
-  #pragma unroll
-        for (int sl = 0; sl < SLOTS; ++sl)
-          if (lane + 64 * sl < r) part = fma(Lsm[r + (long)(lane + 64 * sl) * m], cv[sl], part);
-        const double tot = wave_sum64(part);
-  #pragma unroll
-        for (int sl = 0; sl < SLOTS; ++sl)
-          if (lane + 64 * sl == r) cv[sl] = (R[sl] - tot) / Lsm[r + (long)r * m];
-      }
-  #pragma unroll
-      for (int sl = 0; sl < SLOTS; ++sl)
-        if (lane + 64 * sl < m) P.C[w * m + lane + 64 * sl] = cv[sl];
-    }
-  }
-};
-template <int DP, int MU, int SLOTS = 1>
-__global__ __launch_bounds__(256) void kg_sw_kernel(KgTailParams P) {
-  kg_sw_kernel_body<DP, MU, SLOTS>::run(MOE_VBLOCK, MOE_VGRID, nullptr, P);
-}
-
-// TBpart[e][chunk][c][row] = sum over the chunk's samples of T[row, i] beta_i[c]   (thread = row; T read coalesced, the
-// beta row is wave-uniform).
-template <int MU>
-struct kg_tb_kernel_body {
-  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, const KgTailParams& P, int c_lo) {    // columns [c_lo, c_lo + MU) of beta / TB
-    const int row = blockIdx.x * 256 + threadIdx.x;
-    const int chunk = blockIdx.y, e = blockIdx.z;
-    const int m = P.m;
-    const int i0 = chunk * P.chunk_len, i1 = min(P.num_local, i0 + P.chunk_len);
-    double acc[MU];
-  #pragma unroll
-    for (int c = 0; c < MU; ++c) acc[c] = 0.0;
-    const bool ok = row < P.N;
-    const double* __restrict__ Tcol = P.T + (ok ? row : 0);
-    const double* __restrict__ beta = P.beta;
-  #pragma unroll 4
-    for (int i = i0; i < i1; ++i) {
-      const long w = (long)e * P.num_local + i;
-      const double t = Tcol[w * P.N];
-      const double* __restrict__ b = beta + w * m + c_lo;
-      // all MU entries unconditionally (uniform, contiguous: wide scalar loads, no branch per entry); the entries beyond m
-      // belong to the next sample / the pad behind the buffer and only feed accumulators that are never stored
-  #pragma unroll
-      for (int c = 0; c < MU; ++c) acc[c] = fma(t, b[c], acc[c]);
-    }
-    if (ok) {
-      double* dst = P.TBpart + ((long)e * P.chunks + chunk) * m * P.N;
-  #pragma unroll
-      for (int c = 0; c < MU; ++c)
-        if (c_lo + c < m) dst[(long)(c_lo + c) * P.N + row] = acc[c];
-    }
-  }
-};
-template <int MU>
-__global__ __launch_bounds__(256) void kg_tb_kernel(KgTailParams P, int c_lo = 0) {
-  kg_tb_kernel_body<MU>::run(MOE_VBLOCK, MOE_VGRID, nullptr, P, c_lo);
-}
-
-// The same partial sums for m > 64 (r4; the stretch point's m = 104) as a product on the matrix pipe: TBpart[e][chunk] (N x m) =
-// T_e[:, chunk] (N x len) beta_e[chunk, :] (len x m) through gemm128.hpp's tile core -- one pass over T instead of one per 64 columns
-// of beta, chunks of kTbChunkWide samples (ten partials instead of 79 at M = 20 000).  Grid (row tiles of 128, chunks, E).
-struct kg_tb128_kernel_body {
-  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, const KgTailParams& P) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    const int chunk = blockIdx.y, e = blockIdx.z, m = P.m;
-    const int i0 = chunk * P.chunk_len, len = min(P.num_local - i0, P.chunk_len);
-    const long w0 = (long)e * P.num_local + i0;
-    g128::Operand A{P.T + w0 * P.N, (long)P.N, P.N, len, 1};     // T[row + sample N]: rows contiguous
-    g128::Operand B{P.beta + w0 * m, (long)m, m, len, 1};        // beta[sample m + c]: the output column contiguous
-    g128::f64x4 acc[4][4];
-    const int r0 = blockIdx.x * g128::TM;
-    g128::tile_product<false, false>(A, B, r0, 0, 0, len, smem, acc);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int wi = (wave & 1) * 64, wj = (wave >> 1) * 64;
-    const int lk = lane >> 4, lx = lane & 15;
-    double* dst = P.TBpart + ((long)e * P.chunks + chunk) * m * P.N;
-  #pragma unroll
-    for (int a = 0; a < 4; ++a)
-  #pragma unroll
-      for (int b = 0; b < 4; ++b)
-  #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = r0 + wi + 16 * a + lx, c = wj + 16 * b + lk + 4 * r;
-          if (row < P.N && c < m) dst[(long)c * P.N + row] = acc[a][b][r];
-        }
-  }
-};
-__global__ __launch_bounds__(256, 2) void kg_tb128_kernel(KgTailParams P) {
-  kg_tb128_kernel_body::run(MOE_VBLOCK, MOE_VGRID, nullptr, P);
-}
-
-// S_W = W_e^T T_e (m x samples) for 64 < m <= 128 on the same tile core: one 128-row tile holds all m rows, so T is read ONCE (the
-// 64-tile kernel reads it once per row tile: twice at m = 104).  K = N is cut into `slices`; slice sl of evaluation e goes to
-// SWpart[sl][e] (dense m x num_local), summed in slice order by sum_slices_kernel.  Grid (column tiles of 128 samples, slices, E).
-struct kg_sw128_kernel_body {
-  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, const KgTailParams& P, double* __restrict__ SWpart, int slices) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    const int sl = blockIdx.y, e = blockIdx.z, m = P.m;
-    const int ks = ((P.N + slices - 1) / slices + g128::TK - 1) / g128::TK * g128::TK;
-    const int k_lo = sl * ks, k_hi = min(P.N, k_lo + ks);
-    g128::Operand A{P.W + (long)e * P.w_stride, (long)P.N, m, P.N, 1};                        // W[row + c N]: K (= row) contiguous
-    g128::Operand B{P.T + (long)e * P.num_local * P.N, (long)P.N, P.num_local, P.N, 1};      // T[row + sample N]: K contiguous
-    g128::f64x4 acc[4][4];
-    const int j0 = blockIdx.x * g128::TM;
-    g128::tile_product<true, true>(A, B, 0, j0, k_lo, k_hi, smem, acc);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int wi = (wave & 1) * 64, wj = (wave >> 1) * 64;
-    const int lk = lane >> 4, lx = lane & 15;
-    double* dst = SWpart + ((long)sl * P.E + e) * m * P.num_local;
-  #pragma unroll
-    for (int a = 0; a < 4; ++a)
-  #pragma unroll
-      for (int b = 0; b < 4; ++b)
-  #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int c = wi + 16 * a + lx, smp = j0 + wj + 16 * b + lk + 4 * r;
-          if (c < m && smp < P.num_local) dst[(long)smp * m + c] = acc[a][b][r];
-        }
-  }
-};
-__global__ __launch_bounds__(256, 2) void kg_sw128_kernel(KgTailParams P, double* __restrict__ SWpart, int slices) {
-  kg_sw128_kernel_body::run(MOE_VBLOCK, MOE_VGRID, nullptr, P, SWpart, slices);
-}
-
-// TB[e][c][row] = sum of the chunk partials in chunk order (one pass over TBpart instead of one per gradient column).
-struct kg_tbsum_kernel_body {
-  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, const KgTailParams& P, double* __restrict__ TBsum) {
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;  // over m * N
-    const int e = blockIdx.y;
-    const long mn = (long)P.m * P.N;
-    if (idx >= mn) return;
-    const double* part = P.TBpart + (long)e * P.chunks * mn + idx;
-    double tb = 0.0;
-  #pragma unroll 8
-    for (int ch = 0; ch < P.chunks; ++ch) tb += part[(long)ch * mn];  // (independent loads, issued eight at a time)
-    TBsum[(long)e * mn + idx] = tb;
-  }
-};
-__global__ __launch_bounds__(256) void kg_tbsum_kernel(KgTailParams P, double* __restrict__ TBsum) {
-  kg_tbsum_kernel_body::run(MOE_VBLOCK, MOE_VGRID, nullptr, P, TBsum);
-}
-
-// GTB[e][gc] = sum_row dK*_e[row, gc] * (K^-1 TB_e)[row, col(gc)];  gc = (k (1+g) + b) d + dd  ->  col = k (1+g) + b.
-struct kg_gtb_kernel_body {
-  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, const KgTailParams& P, const double* __restrict__ TBsum) {
-    __shared__ double red[4];
-    const int gc = blockIdx.x, e = blockIdx.y;
-    const int col = gc / P.cp.dim;
-    const double* Gc = P.Gm + (long)e * P.g_stride + (long)gc * P.N;
-    const double* tb = TBsum + ((long)e * P.m + col) * P.N;
-    double acc = 0.0;
-    for (int row = threadIdx.x; row < P.N; row += 256) acc = fma(Gc[row], tb[row], acc);
-    const double tot = block_sum_256(acc, red);
-    if (threadIdx.x == 0) P.out[(long)e * P.out_stride + 1 + P.m * P.m + P.ngrad + gc] = tot;
-  }
-};
-__global__ __launch_bounds__(256) void kg_gtb_kernel(KgTailParams P, const double* __restrict__ TBsum) {
-  kg_gtb_kernel_body::run(MOE_VBLOCK, MOE_VGRID, nullptr, P, TBsum);
-}
-
-// The summed TB lives behind the chunk partials in the same buffer (the host reserves E (chunks + 1) m N doubles).
-void launch_gtb(const KgTailParams& P, hipStream_t s) {
-  const long mn = (long)P.m * P.N;
-  double* TBsum = P.TBpart + (long)P.E * P.chunks * mn;
-  launch_kernel_ens<kg_tbsum_kernel_body, 256>(kg_tbsum_kernel, dim3((unsigned)((mn + 255) / 256), P.E), dim3(256), 0, s, P, TBsum);
-  // (K^-1 dK*)^T TB = dK*^T (K^-1 TB): the two triangular products run over the m columns of TB, not over the q (1 + g) d columns of
-  // dK* (r4: 32 against 384 per evaluation at C5)
-  const int cm = P.E * P.m;
-  double* half = P.work;
-  double* KinvTB = P.work + (long)P.N * cm;
-  launch_tri_gemm_cols('N', P.N, cm, P.m, P.Linv, P.ldL, TBsum, P.N, half, P.N, P.tri_work, s);
-  launch_tri_gemm_cols('T', P.N, cm, P.m, P.Linv, P.ldL, half, P.N, KinvTB, P.N, P.tri_work, s);
-  launch_kernel_ens<kg_gtb_kernel_body, 256>(kg_gtb_kernel, dim3(P.ngrad, P.E), dim3(256), 0, s, P, (const double*)KinvTB);
-}
-
-// ZC[e][r + j m] = sum_i z_i[r] c_i[j] and kg_sum = sum_i (best_posterior + best_value_i)   (.cpp:196).
-// Without a strided sample walk (round 1: one workgroup per (r, j) reading c_i[j] every m doubles: 254 us for two
-// C5 evaluations): a workgroup takes a chunk of kZcChunk samples, stages their z and c rows in LDS with coalesced loads and forms all
-// m x m partial products; kg_zc_sum_kernel adds the chunk partials in chunk order and forms kg_sum exactly as kg_sum_kernel does.
-constexpr int kZcChunk = 64;  // samples per chunk (32 for m > 32: the two staged blocks stay within 32 KB)
-inline int zc_chunk_len(int m) { return m > 32 ? kZcChunk / 2 : kZcChunk; }  // (r4: m > 64 too -- 2 x 32 x 128 doubles: 64 KB, opted in)
-struct kg_zc_part_kernel_body {
-  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, const KgTailParams& P, double* __restrict__ part, int chunks, int len) {
-    extern __shared__ __attribute__((aligned(16))) double zc_sm[];  // z [len][m] | c [len][m]
-    const int chunk = blockIdx.x, e = blockIdx.y, m = P.m;
-    const int i0 = chunk * len, cnt = min(len, P.num_local - i0);
-    double* zs = zc_sm;
-    double* cs = zc_sm + len * m;
-    for (int t = threadIdx.x; t < cnt * m; t += 256) {
-      const int ii = t / m, r = t - ii * m;
-      const int s = P.first_sample + i0 + ii;
-      zs[t] = ((s & 1) ? -1.0 : 1.0) * P.normals[(long)(s >> 1) * m + r];
-      cs[t] = P.C[((long)e * P.num_local + i0 + ii) * m + r];
-    }
-    __syncthreads();
-    for (int o = threadIdx.x; o < m * m; o += 256) {
-      const int r = o % m, j = o / m;
-      double acc = 0.0;
-  #pragma unroll 4
-      for (int ii = 0; ii < cnt; ++ii) acc = fma(zs[ii * m + r], cs[ii * m + j], acc);
-      part[((long)e * chunks + chunk) * m * m + o] = acc;
-    }
-  }
-};
-__global__ __launch_bounds__(256) void kg_zc_part_kernel(KgTailParams P, double* __restrict__ part, int chunks, int len) {
-  kg_zc_part_kernel_body::run(MOE_VBLOCK, MOE_VGRID, nullptr, P, part, chunks, len);
-}
-
-// (r4: `gs` lanes share an output -- a power of two, m m gs <= 256 -- and stride the chunks, then a fixed butterfly: a lane per output
-//  walked all the chunks in batches of eight loads, one memory round trip per batch: 19 us for the 157 chunks of one C3 evaluation)
-struct kg_zc_sum_kernel_body {
-  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, const KgTailParams& P, const double* __restrict__ part, int chunks, int gs) {
-    __shared__ double red[4];
-    const int e = blockIdx.y, m = P.m;
-    const int per_block = 256 / gs;
-    const int o = blockIdx.x * per_block + (int)threadIdx.x / gs, g = (int)threadIdx.x % gs;
-    double* out = P.out + (long)e * P.out_stride;
-    {
-      const bool ok = o < m * m;
-      const double* p = part + (long)e * chunks * m * m + (ok ? o : 0);
-      double v = 0.0;
-  #pragma unroll 8
-      for (int ch = g; ch < chunks; ch += gs) v += p[(long)ch * m * m];
-      for (int off = gs >> 1; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-      if (ok && g == 0) out[1 + o] = v;
-    }
-    if (blockIdx.x == 0) {  // kg_sum = sum_i (best_posterior + best_value_i): the summation of kg_sum_kernel, bit for bit
-      const double bp = P.blob[(long)e * P.rec.stride + P.rec_bp];
-      double acc = 0.0;
-  #pragma unroll 8
-      for (int i = threadIdx.x; i < P.num_local; i += 256) acc += bp + P.best_value[(long)e * P.num_local + i];
-      const double tot = block_sum_256(acc, red);
-      if (threadIdx.x == 0) out[0] = tot;
-    }
-  }
-};
-__global__ __launch_bounds__(256) void kg_zc_sum_kernel(KgTailParams P, const double* __restrict__ part, int chunks, int gs) {
-  kg_zc_sum_kernel_body::run(MOE_VBLOCK, MOE_VGRID, nullptr, P, part, chunks, gs);
-}
-
-int env_int(const char* name, int dflt);
-inline int zc_sum_lanes(int m) {  // lanes that share an entry of ZC in kg_zc_sum_kernel
-  int gs = 1;
-  while (gs < 64 && m * m * gs * 2 <= 256) gs *= 2;
-  return gs;
-}
-// r5: for small m and few chunks the sum of the partials is taken by kg_finish_kernel itself (one launch less on the latency path)
-inline bool zc_sum_in_finish(int m, int num_local) {
-  const long chunks = (num_local + zc_chunk_len(m) - 1) / zc_chunk_len(m);
-  return m <= 8 && chunks * m * m <= 16384;
-}
-
-// host side of the two: part = E * chunks * m * m doubles of workspace
-void launch_zc(const KgTailParams& P, double* part, hipStream_t s, bool sum_here = true) {
-  const int len = zc_chunk_len(P.m);
-  const int chunks = (P.num_local + len - 1) / len;
-  const size_t shm = sizeof(double) * 2 * len * P.m;
-  if (shm > 48 * 1024)
-    MOE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kg_zc_part_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-  launch_kernel_ens<kg_zc_part_kernel_body, 256>(kg_zc_part_kernel, dim3(chunks, P.E), dim3(256), shm, s, P, part, chunks, len);
-  if (!sum_here) return;
-  const int gs = zc_sum_lanes(P.m);
-  const int per_block = 256 / gs;
-  launch_kernel_ens<kg_zc_sum_kernel_body, 256>(kg_zc_sum_kernel, dim3((P.m * P.m + per_block - 1) / per_block, P.E), dim3(256), 0, s, P, (const double*)part, chunks, gs);
-}
-
-// DIR[e][(k (1+g) + b) d + dd] = sum_i beta_i[(k,b)] * d cov(Xu_k, x*_i)[b, 0] / d Xu_k,dd ; workgroup (k, e).
-template <int DP>
-struct kg_dir_kernel_body {
-  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, const KgTailParams& P, double* __restrict__ part, int slices) {
-    __shared__ double red[4];
-    const int k = blockIdx.x, e = blockIdx.y, sl = blockIdx.z;
-    // the samples are cut into `slices` contiguous ranges (grid.z) so that q x E workgroups become q x E x slices -- at C5
-    // eight workgroups walked 20 000 samples each while 248 CUs idled; kg_dir_sum_kernel adds the partials in slice order
-    const int per = (P.num_local + slices - 1) / slices;
-    const int i_lo = sl * per, i_hi = min(P.num_local, i_lo + per);
-    const int m = P.m, g1 = 1 + P.g, d = P.cp.dim;
-    const double* Xu = P.blob + (long)e * P.rec.stride + P.rec.XuP + (long)k * DP;
-    DerivList none;
-    none.g = 0;
-    double xk[DP];
-  #pragma unroll
-    for (int kk = 0; kk < DP; ++kk) xk[kk] = Xu[kk];
-    for (int b = 0; b < g1; ++b) {
-      double acc[DP];
-  #pragma unroll
-      for (int dd = 0; dd < DP; ++dd) acc[dd] = 0.0;
-      for (int i = i_lo + threadIdx.x; i < i_hi; i += 256) {
-        const long w = (long)e * P.num_local + i;
-        const double* xs = P.best_point + w * DP;
-        double diff[DP];
-        double r2 = 0.0;
-  #pragma unroll
-        for (int kk = 0; kk < DP; ++kk) {
-          diff[kk] = xk[kk] - xs[kk];
-          r2 = fma(diff[kk] * diff[kk], P.cp.inv_l2[kk], r2);
-        }
-        const Radial rd = radial_scalars(P.cp.type, P.cp.alpha, r2);
-        const double bt = P.beta[w * m + k * g1 + b];
-  #pragma unroll
-        for (int dd = 0; dd < DP; ++dd)
-          if (dd < d) acc[dd] = fma(bt, grad_cov_entry<DP>(P.cp, rd, diff, b, 0, dd, P.derivs, none), acc[dd]);
-      }
-  #pragma unroll
-      for (int dd = 0; dd < DP; ++dd) {
-        if (dd < d) {  // d is workgroup-uniform
-          const double tot = block_sum_256(acc[dd], red);
-          if (threadIdx.x == 0) part[((long)e * P.ngrad + (k * g1 + b) * d + dd) * slices + sl] = tot;
-        }
-      }
-    }
-  }
-};
-template <int DP>
-__global__ __launch_bounds__(256) void kg_dir_kernel(KgTailParams P, double* __restrict__ part, int slices) {
-  kg_dir_kernel_body<DP>::run(MOE_VBLOCK, MOE_VGRID, nullptr, P, part, slices);
-}
-
-// (the slices are added up in order by kg_finish_kernel, where DIR is consumed -- r5; a kernel of its own before)
-inline int dir_slices(int num_local) { return std::max(1, std::min(kDirSlices, (num_local + 255) / 256)); }
-inline double* dir_partials(const KgTailParams& P) {
-  // behind the summed TB in the TB buffer (the host reserves E * ngrad * kDirSlices doubles more)
-  return P.TBpart + (long)P.E * (P.chunks + 1) * (long)P.m * P.N;
-}
-
-// (T-free tail, S_W-free form) the KB chunk partials [E][chunks][m][m] behind the DIR partials (the host reserves E chunks m m doubles more)
-__host__ __device__ inline double* kb_partials(const KgTailParams& P) {
-  return P.TBpart + (long)P.E * (P.chunks + 1) * (long)P.m * P.N + (long)P.E * P.ngrad * kDirSlices;
-}
-
-template <int DP>
-void launch_dir(const KgTailParams& P, hipStream_t s) {
-  const int slices = dir_slices(P.num_local);
-  launch_kernel_ens<kg_dir_kernel_body<DP>, 256>(kg_dir_kernel<DP>, dim3(P.q, P.E, slices), dim3(256), 0, s, P, dir_partials(P), slices);
-}
-
-template <int DP, int MU>
-void launch_sw_inst(const KgTailParams& P, hipStream_t s) {
-  dim3 grid((P.num_local + P.sw_chunk - 1) / P.sw_chunk, P.E);
-  const size_t shm = (P.SW == nullptr) ? sizeof(double) * (size_t)P.N * P.m : 0;
-  auto kern = kg_sw_kernel<DP, MU>;
-  if (shm > 48 * 1024)
-    MOE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-  launch_kernel_ens<kg_sw_kernel_body<DP, MU>, 256>(kern, grid, dim3(256), shm, s, P);
-}
-
-template <int DP>
-void launch_sw_dp(const KgTailParams& P, hipStream_t s) {
-  if (P.m <= 4)
-    launch_sw_inst<DP, 4>(P, s);
-  else if (P.m <= 8)
-    launch_sw_inst<DP, 8>(P, s);
-  else if (P.m <= 16)
-    launch_sw_inst<DP, 16>(P, s);
-  else if (P.m <= 32)
-    launch_sw_inst<DP, 32>(P, s);
-  else if (P.m <= 64)
-    launch_sw_inst<DP, 64>(P, s);
-  else {  // two components per lane; S_W comes precomputed (the host always forms it by GEMM for m > 8)
-    if (P.SW == nullptr) throw Error(MOE_ERR_RUNTIME, "m > 64 needs the precomputed W^T T");
-    dim3 grid((P.num_local + P.sw_chunk - 1) / P.sw_chunk, P.E);
-    launch_kernel_ens<kg_sw_kernel_body<DP, 1, 2>, 256>(kg_sw_kernel<DP, 1, 2>, grid, dim3(256), 0, s, P);
-  }
-  launch_dir<DP>(P, s);
-}
-
-void launch_tail(const KgTailParams& P, hipStream_t s) {
-  switch (P.cp.dp) {
-    case 4: launch_sw_dp<4>(P, s); break;
-    case 8: launch_sw_dp<8>(P, s); break;
-    case 12: launch_sw_dp<12>(P, s); break;
-    case 16: launch_sw_dp<16>(P, s); break;
-    case 24: launch_sw_dp<24>(P, s); break;
-    case 32: launch_sw_dp<32>(P, s); break;
-    default: throw Error(MOE_ERR_RUNTIME, "unsupported padded dimension");
-  }
-  dim3 gtb((P.N + 255) / 256, P.chunks, P.E);
-  if (P.m <= 4)
-    launch_kernel_ens<kg_tb_kernel_body<4>, 256>(kg_tb_kernel<4>, gtb, dim3(256), 0, s, P, 0);
-  else if (P.m <= 8)
-    launch_kernel_ens<kg_tb_kernel_body<8>, 256>(kg_tb_kernel<8>, gtb, dim3(256), 0, s, P, 0);
-  else if (P.m <= 16)
-    launch_kernel_ens<kg_tb_kernel_body<16>, 256>(kg_tb_kernel<16>, gtb, dim3(256), 0, s, P, 0);
-  else if (P.m <= 32)
-    launch_kernel_ens<kg_tb_kernel_body<32>, 256>(kg_tb_kernel<32>, gtb, dim3(256), 0, s, P, 0);
-  else if (P.m <= 64) {
-    launch_kernel_ens<kg_tb_kernel_body<64>, 256>(kg_tb_kernel<64>, gtb, dim3(256), 0, s, P, 0);
-  } else {  // (m <= kMaxMB = 128: one column tile)
-    MOE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kg_tb128_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)g128::kSmemBytes));
-    launch_kernel_ens<kg_tb128_kernel_body, 256, 2>(kg_tb128_kernel, dim3((P.N + g128::TM - 1) / g128::TM, P.chunks, P.E), dim3(256), g128::kSmemBytes, s, P);
-  }
-  launch_gtb(P, s);
-  MOE_HIP_CHECK(hipGetLastError());
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Fused tail for q-KG (no derivative observations, m = q + p <= 8): the N x M matrix T = K(X, x*_i) is never written.
-// Its entries are recomputed where they are consumed -- once with a thread per SAMPLE (S_W = W^T T_i, then c_i), once with a
-// thread per training POINT (TB partials) -- which costs ~2 x 46 FP64 instructions per entry against 16 B written + 24 B
-// re-read per entry through HBM: at C3 the covariance build + S_W + TB kernels took 86 us per evaluation, these two take
-// about half.  Operands that are uniform over the workgroup (the point tile in the first kernel, the sample chunk in the
-// second) are staged in LDS pre-scaled by 1/length and read as broadcasts.
-// By default only the second of the two runs (the S_W-free form further down: ZC from the chunk sums, no per-sample quantity);
-// MOE_KG_FUSED_ONE_PASS=0 keeps both, with kg_fused_c_kernel and the ZC chunk partials behind them, as the comparator of the tests.
-// ---------------------------------------------------------------------------------------------------------------------
-constexpr int kFusedTile = 256;  // points (kernel A) / samples (kernel B, at most: KgTailParams::chunk_len) staged per LDS tile
-
-template <int COV>
-__device__ __forceinline__ double radial_base(double r2, const double* __restrict__ etab) {
-  if (COV == MOE_COV_SQUARE_EXPONENTIAL) return exp_nonpos_tab(fmax(-0.5 * r2, -1000.0), etab);  // (table exp range)
-  const double a = 2.236067977499789696409173668731276235 * sqrt_pos(r2);
-  return exp_nonpos_tab(-a, etab) * fma(a, fma(a, 1.0 / 3.0, 1.0), 1.0);
-}
-
-// thread = sample, blockIdx.z = slice of the training points: SWpart[e][i][slice][c] = sum over the slice of W[j, c] k(X_j, x*_i)
-// (the slices only exist to give the chip enough wavefronts: E * M / 64 alone is ~1 per SIMD at the headline shape)
-template <int DP, int MU, int COV>
-struct kg_fused_sample_kernel_body {
-  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, const KgTailParams& P, const double* __restrict__ X, int n, double* __restrict__ SWpart) {
-    __shared__ double etab[kExpTabLen];
-    __shared__ double Xt[kFusedTile][DP];
-    __shared__ double Wt[kFusedTile][MU];
-    const int e = blockIdx.y, m = P.m, N = P.N;
-    const int slices = gridDim.z, slice = blockIdx.z;
-    const int per = ((n + slices - 1) / slices + 63) / 64 * 64;
-    const int j_lo = slice * per, j_hi = min(n, j_lo + per);
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const bool ok = i < P.num_local;
-    const long w = (long)e * P.num_local + (ok ? i : 0);
-    if (threadIdx.x < kExpTabLen) etab[threadIdx.x] = kExp2Tab64[threadIdx.x];
-    double xs[DP], acc[MU];
-  #pragma unroll
-    for (int k = 0; k < DP; ++k) xs[k] = P.best_point[w * DP + k] * P.cp.inv_l[k];
-  #pragma unroll
-    for (int c = 0; c < MU; ++c) acc[c] = 0.0;
-    const double* We = P.W + (long)e * P.w_stride;
-    for (int j0 = j_lo; j0 < j_hi; j0 += kFusedTile) {
-      __syncthreads();
-      for (int t = threadIdx.x; t < kFusedTile * DP; t += 256) {
-        const int jj = t / DP, k = t % DP;
-        Xt[jj][k] = (j0 + jj < j_hi) ? X[(long)(j0 + jj) * DP + k] * P.cp.inv_l[k] : 0.0;
-      }
-      for (int t = threadIdx.x; t < kFusedTile * MU; t += 256) {
-        const int jj = t % kFusedTile, c = t / kFusedTile;  // W_e is [N x m] col-major: consecutive jj are contiguous
-        Wt[jj][c] = (j0 + jj < j_hi && c < m) ? We[(long)c * N + j0 + jj] : 0.0;  // zero weight: padded points drop out
-      }
-      __syncthreads();
-      const int cnt = min(kFusedTile, j_hi - j0);
-  #pragma unroll 2
-      for (int jj = 0; jj < cnt; ++jj) {
-        double r2 = 1.0e-300;
-  #pragma unroll
-        for (int k = 0; k < DP; ++k) {
-          const double dlt = Xt[jj][k] - xs[k];
-          r2 = fma(dlt, dlt, r2);
-        }
-        const double t = radial_base<COV>(r2, etab);
-  #pragma unroll
-        for (int c = 0; c < MU; ++c) acc[c] = fma(Wt[jj][c], t, acc[c]);
-      }
-    }
-    if (!ok) return;
-  #pragma unroll
-    for (int c = 0; c < MU; ++c) SWpart[(w * slices + slice) * MU + c] = acc[c];
-  }
-};
-template <int DP, int MU, int COV>
-__global__ __launch_bounds__(256) void kg_fused_sample_kernel(KgTailParams P, const double* __restrict__ X, int n,
-                                                             double* __restrict__ SWpart) {
-  kg_fused_sample_kernel_body<DP, MU, COV>::run(MOE_VBLOCK, MOE_VGRID, nullptr, P, X, n, SWpart);
-}
-
-// thread = sample: S_W = sum of the slices (fixed order); R_r = alpha (k(Xu_r, x*_i) - S_W[r]); c_i = L^-1 R by forward
-// substitution (L is m x m, column-major, workgroup-uniform)
-template <int DP, int MU, int COV>
-struct kg_fused_c_kernel_body {
-  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, const KgTailParams& P, const double* __restrict__ SWpart, int slices) {
-    __shared__ double etab[kExpTabLen];
-    const int e = blockIdx.y, m = P.m;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (threadIdx.x < kExpTabLen) etab[threadIdx.x] = kExp2Tab64[threadIdx.x];
-    __syncthreads();
-    if (i >= P.num_local) return;
-    const long w = (long)e * P.num_local + i;
-    double xs[DP], sw[MU], cv[MU];
-  #pragma unroll
-    for (int k = 0; k < DP; ++k) xs[k] = P.best_point[w * DP + k] * P.cp.inv_l[k];
-  #pragma unroll
-    for (int c = 0; c < MU; ++c) {
-      sw[c] = 0.0;
-      for (int sl = 0; sl < slices; ++sl) sw[c] += SWpart[(w * slices + sl) * MU + c];
-    }
-    const double* rec = P.blob + (long)e * P.rec.stride;
-    const double* Lsm = rec + P.rec.L;
-  #pragma unroll
-    for (int r = 0; r < MU; ++r) {
-      cv[r] = 0.0;
-      if (r < m) {
-        const double* Xu = rec + P.rec.XuP + (long)r * DP;
-        double r2 = 1.0e-300;
-  #pragma unroll
-        for (int k = 0; k < DP; ++k) {
-          const double dlt = Xu[k] * P.cp.inv_l[k] - xs[k];
-          r2 = fma(dlt, dlt, r2);
-        }
-        double R = P.cp.alpha * (radial_base<COV>(r2, etab) - sw[r]);
-  #pragma unroll
-        for (int c = 0; c < MU; ++c)
-          if (c < r) R -= Lsm[r + c * m] * cv[c];
-        cv[r] = R / Lsm[r + r * m];
-        P.C[w * m + r] = cv[r];
-      }
-    }
-  }
-};
-template <int DP, int MU, int COV>
-__global__ __launch_bounds__(256) void kg_fused_c_kernel(KgTailParams P, const double* __restrict__ SWpart, int slices) {
-  kg_fused_c_kernel_body<DP, MU, COV>::run(MOE_VBLOCK, MOE_VGRID, nullptr, P, SWpart, slices);
-}
-
-// thread = training point: TBpart[e][chunk][c][row] = sum over the chunk's samples of K(X_row, x*_i) beta_i[c]
-// kb_rows > 0 (the S_W-free form below; kb_rows = m): the evaluation's union points follow the training points as rows n .. n + m - 1
-// of the same launch -- the same contraction at Xu_r, KBpart[e][chunk][c][r] = alpha sum_i beta_i[c] k(Xu_r, x*_i), through the same
-// radial_base on the same scaled differences as kg_fused_c_kernel's k(Xu_r, x*_i).  A training point's sums do not depend on kb_rows.
-template <int DP, int MU, int COV>
-struct kg_fused_point_kernel_body {
-  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, const KgTailParams& P, const double* __restrict__ X, int n, int kb_rows) {
-    __shared__ double etab[kExpTabLen];
-    __shared__ double St[kFusedTile][DP];
-    __shared__ double Bt[kFusedTile][MU];
-    const int row = blockIdx.x * 256 + threadIdx.x;
-    const int chunk = blockIdx.y, e = blockIdx.z;
-    const int m = P.m;
-    const int i0 = chunk * P.chunk_len, cnt = min(P.num_local - i0, P.chunk_len);  // (chunk_len <= kFusedTile)
-    if (threadIdx.x < kExpTabLen) etab[threadIdx.x] = kExp2Tab64[threadIdx.x];
-    for (int t = threadIdx.x; t < kFusedTile * DP; t += 256) {
-      const int ii = t / DP, k = t % DP;
-      St[ii][k] = (ii < cnt) ? P.best_point[((long)e * P.num_local + i0 + ii) * DP + k] * P.cp.inv_l[k] : 0.0;
-    }
-    for (int t = threadIdx.x; t < kFusedTile * MU; t += 256) {
-      const int ii = t / MU, c = t % MU;
-      Bt[ii][c] = (ii < cnt && c < m) ? P.beta[((long)e * P.num_local + i0 + ii) * m + c] : 0.0;
-    }
-    __syncthreads();
-    if (row >= n + kb_rows) return;  // (no barrier below)
-    const bool ok = row < n;
-    const double* __restrict__ xp = ok ? X + (long)row * DP : P.blob + (long)e * P.rec.stride + P.rec.XuP + (long)(row - n) * DP;
-    double xr[DP], acc[MU];
-  #pragma unroll
-    for (int k = 0; k < DP; ++k) xr[k] = xp[k] * P.cp.inv_l[k];
-  #pragma unroll
-    for (int c = 0; c < MU; ++c) acc[c] = 0.0;
-  #pragma unroll 2
-    for (int ii = 0; ii < cnt; ++ii) {
-      double r2 = 1.0e-300;
-  #pragma unroll
-      for (int k = 0; k < DP; ++k) {
-        const double dlt = xr[k] - St[ii][k];
-        r2 = fma(dlt, dlt, r2);
-      }
-      const double t = radial_base<COV>(r2, etab);
-  #pragma unroll
-      for (int c = 0; c < MU; ++c) acc[c] = fma(t, Bt[ii][c], acc[c]);
-    }
-    if (ok) {
-      double* dst = P.TBpart + ((long)e * P.chunks + chunk) * m * P.N;
-  #pragma unroll
-      for (int c = 0; c < MU; ++c)
-        if (c < m) dst[(long)c * P.N + row] = P.cp.alpha * acc[c];
-    } else {
-      double* dst = kb_partials(P) + ((long)e * P.chunks + chunk) * m * m;
-  #pragma unroll
-      for (int c = 0; c < MU; ++c)
-        if (c < m) dst[c * m + (row - n)] = P.cp.alpha * acc[c];
-    }
-  }
-};
-template <int DP, int MU, int COV>
-__global__ __launch_bounds__(256) void kg_fused_point_kernel(KgTailParams P, const double* __restrict__ X, int n, int kb_rows) {
-  kg_fused_point_kernel_body<DP, MU, COV>::run(MOE_VBLOCK, MOE_VGRID, nullptr, P, X, n, kb_rows);
-}
-
-// The S_W-free form of the T-free tail (the default: MOE_KG_FUSED_ONE_PASS=1; every shape of the T-free path).  S_W,i = W^T T_i is
-// only ever used in c_i = L^-1 alpha (k(Xu, x*_i) - S_W,i), and c_i only in ZC = sum_i z_i c_i^T.  With z_i = L^T beta_i (the MC
-// kernel's own beta_i = L^-T z_i) the sum over the samples moves inside:
-//     ZC = L^T ( KB - TB^T W ) L^-T,    KB[c][r] = alpha sum_i beta_i[c] k(Xu_r, x*_i),    TB = the alpha-scaled sum GTB already uses,
-// so the second contraction of T (kg_fused_sample_kernel, or the one-pass kg_fused_pair_kernel that held both sets of partial sums
-// in registers and was LDS-bound at low occupancy: 1.71 ms per 64 C3 evaluations against kg_fused_point_kernel's 0.89) and every
-// per-sample quantity of the tail (S_W, c_i, the ZC chunk partials) drop out: KB is the TB contraction at m more rows of the point
-// kernel, TB^T W is m m dot products of length N per evaluation.  The gradient changes by rounding only; where the posterior
-// covariance between Xu and x* is far below the prior one the subtraction happens after the sum over the samples instead of inside
-// every sample (tests/test_gpu_sw_free_tail.py bounds that case against the CPU oracle).
-// One workgroup per evaluation: thread = row (stride 256) with all m x m products in registers, a fixed butterfly per wavefront and
-// the four wavefronts added as (0 + 1) + (2 + 3); the KB chunk partials by groups of m m lanes striding the chunks, the groups added
-// in order.  Every order is a function of (N, m, num_local) alone.  Then A = L^T B and ZC = A L^-T by substitution along each row.
-template <int MU>
-struct kg_zc_direct_kernel_body {
-  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, const KgTailParams& P, const double* __restrict__ TBsum) {
-    __shared__ double red[4][MU * MU], kbs[256], Bs[MU * MU], As[MU * MU];
-    const int e = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int m = P.m, N = P.N, mm = m * m;
-    const double* __restrict__ tb = TBsum + (long)e * m * N;
-    const double* __restrict__ We = P.W + (long)e * P.w_stride;
-    double acc[MU][MU];
-  #pragma unroll
-    for (int c = 0; c < MU; ++c)
-  #pragma unroll
-      for (int r = 0; r < MU; ++r) acc[c][r] = 0.0;
-  #pragma unroll 2
-    for (int row = tid; row < N; row += 256) {
-      double t[MU], w[MU];
-  #pragma unroll
-      for (int c = 0; c < MU; ++c) {  // (m is uniform; columns beyond it feed sums that are never read)
-        t[c] = (c < m) ? tb[(long)c * N + row] : 0.0;
-        w[c] = (c < m) ? We[(long)c * N + row] : 0.0;
-      }
-  #pragma unroll
-      for (int c = 0; c < MU; ++c)
-  #pragma unroll
-        for (int r = 0; r < MU; ++r) acc[c][r] = fma(t[c], w[r], acc[c][r]);
-    }
-  #pragma unroll
-    for (int c = 0; c < MU; ++c)
-  #pragma unroll
-      for (int r = 0; r < MU; ++r) {
-        const double v = wave_sum64(acc[c][r]);
-        if (lane == 0) red[wave][c * MU + r] = v;
-      }
-    {
-      const int groups = 256 / mm;  // >= 4
-      const int o = tid % mm, g = tid / mm;
-      const double* __restrict__ kp = kb_partials(P) + (long)e * P.chunks * mm + o;
-      double v = 0.0;
-      if (g < groups) {
-  #pragma unroll 4
-        for (int ch = g; ch < P.chunks; ch += groups) v += kp[(long)ch * mm];
-      }
-      kbs[tid] = v;
-    }
-    __syncthreads();
-    if (tid < mm) {
-      const int groups = 256 / mm;
-      const int c = tid / m, r = tid - c * m;
-      double kb = 0.0;
-      for (int g = 0; g < groups; ++g) kb += kbs[g * mm + tid];
-      const int o = c * MU + r;
-      Bs[tid] = kb - ((red[0][o] + red[1][o]) + (red[2][o] + red[3][o]));
-    }
-    __syncthreads();
-    const double* Lsm = P.blob + (long)e * P.rec.stride + P.rec.L;  // m x m, column-major, lower
-    if (tid < mm) {  // A[a][r] = sum_{c >= a} L[c][a] B[c][r]
-      const int a = tid / m, r = tid - a * m;
-      double v = 0.0;
-      for (int c = a; c < m; ++c) v = fma(Lsm[c + a * m], Bs[c * m + r], v);
-      As[tid] = v;
-    }
-    __syncthreads();
-    if (tid < m) {  // row tid of ZC L^T = A, ascending columns
-      double* out = P.out + (long)e * P.out_stride + 1;
-      double zc[MU];
-  #pragma unroll
-      for (int j = 0; j < MU; ++j) {
-        zc[j] = 0.0;
-        if (j < m) {
-          double v = As[tid * m + j];
-  #pragma unroll
-          for (int k = 0; k < MU; ++k)
-            if (k < j) v = fma(-zc[k], Lsm[j + k * m], v);
-          zc[j] = v / Lsm[j + j * m];
-          out[tid + j * m] = zc[j];
-        }
-      }
-    }
-  }
-};
-template <int MU>
-__global__ __launch_bounds__(256) void kg_zc_direct_kernel(KgTailParams P, const double* __restrict__ TBsum) {
-  kg_zc_direct_kernel_body<MU>::run(MOE_VBLOCK, MOE_VGRID, nullptr, P, TBsum);
-}
-
-// which form the T-free tail takes: a switch of the process, never a function of the batch
-inline bool fused_tail_sw_free() { return env_int("MOE_KG_FUSED_ONE_PASS", 1) != 0; }
-
-template <int DP, int MU, int COV>
-void launch_fused_tail_cov(const KgTailParams& P, const double* X, int n, double* SWpart, int slices, hipStream_t s) {
-  if (fused_tail_sw_free()) {
-    dim3 gb((n + P.m + 255) / 256, P.chunks, P.E);  // (the m union rows behind the training points)
-    launch_kernel_ens<kg_fused_point_kernel_body<DP, MU, COV>, 256>(kg_fused_point_kernel<DP, MU, COV>, gb, dim3(256), 0, s, P, X, n, P.m);
-    launch_dir<DP>(P, s);
-    launch_gtb(P, s);
-    const double* TBsum = P.TBpart + (long)P.E * P.chunks * (long)P.m * P.N;  // (launch_gtb)
-    launch_kernel_ens<kg_zc_direct_kernel_body<MU>, 256>(kg_zc_direct_kernel<MU>, dim3(P.E), dim3(256), 0, s, P, TBsum);
-    MOE_HIP_CHECK(hipGetLastError());
-    return;
-  }
-  dim3 ga((P.num_local + 255) / 256, P.E, slices), gc((P.num_local + 255) / 256, P.E), gb((n + 255) / 256, P.chunks, P.E);
-  launch_kernel_ens<kg_fused_sample_kernel_body<DP, MU, COV>, 256>(kg_fused_sample_kernel<DP, MU, COV>, ga, dim3(256), 0, s, P, X, n, SWpart);
-  launch_kernel_ens<kg_fused_c_kernel_body<DP, MU, COV>, 256>(kg_fused_c_kernel<DP, MU, COV>, gc, dim3(256), 0, s, P, SWpart, slices);
-  launch_dir<DP>(P, s);
-  launch_kernel_ens<kg_fused_point_kernel_body<DP, MU, COV>, 256>(kg_fused_point_kernel<DP, MU, COV>, gb, dim3(256), 0, s, P, X, n, 0);
-  launch_gtb(P, s);
-  MOE_HIP_CHECK(hipGetLastError());
-}
-
-template <int DP, int MU>
-void launch_fused_tail_inst(const KgTailParams& P, const double* X, int n, double* SWpart, int slices, hipStream_t s) {
-  if (P.cp.type == MOE_COV_SQUARE_EXPONENTIAL)
-    launch_fused_tail_cov<DP, MU, MOE_COV_SQUARE_EXPONENTIAL>(P, X, n, SWpart, slices, s);
-  else
-    launch_fused_tail_cov<DP, MU, MOE_COV_MATERN_NU_2P5>(P, X, n, SWpart, slices, s);
-}
-
-// number of point slices of kg_fused_sample_kernel: enough wavefronts for ~4 per SIMD when ONE evaluation runs alone.  It does not
-// depend on the batch size: the slices are summed in order, so an evaluation's bits would otherwise change with its batch.
-int fused_tail_slices(int /*E*/, int num_local, int n, int num_cu) {
-  const long waves = (long)((num_local + 255) / 256) * 4;
-  const long want = (long)num_cu * 4 * 4;
-  int s = (int)std::min<long>(8, std::max<long>(1, (want + waves - 1) / waves));
-  return std::max(1, std::min(s, (n + 63) / 64));
-}
-
-// T-free tail (requires g == 0, m <= 8, chunk_len <= kFusedTile)
-void launch_fused_tail(const KgTailParams& P, const double* X, int n, double* SWpart, int slices, hipStream_t s) {
-  static_assert(kFusedChunk <= kFusedTile, "a chunk of samples is staged in one LDS tile");
-  const bool m4 = P.m <= 4;
-  switch (P.cp.dp) {
-    case 4: m4 ? launch_fused_tail_inst<4, 4>(P, X, n, SWpart, slices, s) : launch_fused_tail_inst<4, 8>(P, X, n, SWpart, slices, s); break;
-    case 8: m4 ? launch_fused_tail_inst<8, 4>(P, X, n, SWpart, slices, s) : launch_fused_tail_inst<8, 8>(P, X, n, SWpart, slices, s); break;
-    case 12: m4 ? launch_fused_tail_inst<12, 4>(P, X, n, SWpart, slices, s) : launch_fused_tail_inst<12, 8>(P, X, n, SWpart, slices, s); break;
-    case 16: m4 ? launch_fused_tail_inst<16, 4>(P, X, n, SWpart, slices, s) : launch_fused_tail_inst<16, 8>(P, X, n, SWpart, slices, s); break;
-    case 24: m4 ? launch_fused_tail_inst<24, 4>(P, X, n, SWpart, slices, s) : launch_fused_tail_inst<24, 8>(P, X, n, SWpart, slices, s); break;
-    case 32: m4 ? launch_fused_tail_inst<32, 4>(P, X, n, SWpart, slices, s) : launch_fused_tail_inst<32, 8>(P, X, n, SWpart, slices, s); break;
-    default: throw Error(MOE_ERR_RUNTIME, "unsupported padded dimension");
-  }
-}
-
-// value-only finish: kg_sum per evaluation (same summation as block 0 of kg_zc_sum_kernel)
-struct kg_sum_kernel_body {
-  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, const KgTailParams& P, double* __restrict__ fin, const unsigned long long* __restrict__ counters, const int* __restrict__ flags) {
-    __shared__ double red[4];
-    const int e = blockIdx.x;
-    const double bp = P.blob[(long)e * P.rec.stride + P.rec_bp];
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < P.num_local; i += 256) acc += bp + P.best_value[(long)e * P.num_local + i];
-    const double tot = block_sum_256(acc, red);
-    if (threadIdx.x == 0) {  // the record the host reads back: kg_sum | value passes | gradient passes | singular flag
-      fin[4 * e] = tot;
-      fin[4 * e + 1] = (double)counters[2 * e];
-      fin[4 * e + 2] = (double)counters[2 * e + 1];
-      fin[4 * e + 3] = (double)flags[e];
-    }
-  }
-};
-__global__ __launch_bounds__(256) void kg_sum_kernel(KgTailParams P, double* __restrict__ fin, const unsigned long long* __restrict__ counters,
-                                                     const int* __restrict__ flags) {
-  kg_sum_kernel_body::run(MOE_VBLOCK, MOE_VGRID, nullptr, P, fin, counters, flags);
-}
 
 struct EventTimer {
   hipEvent_t a = nullptr, b = nullptr;  // (created on first use: a recorded evaluation -- launch.hpp -- times nothing)
@@ -1006,397 +73,28 @@ std::optional<int> env_opt(const char* name) {  // unset and empty: no value
   if (v && *v) return std::atoi(v);
   return std::nullopt;
 }
-int env_int(const char* name, int dflt) { return env_opt(name).value_or(dflt); }
 
-// z, beta = L^-T z and the discretised-set winner of EVERY sample (they depend on the normal draws alone): one wavefront
-// per sample, grid-stride, the same device functions the MC kernels use -- so the values are the ones they would compute.
-struct kg_sample_prep_kernel_body {
-  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, const KgMcParams& P, int* __restrict__ best_j) {
-    __shared__ double zbs[4][2 * kMaxM];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    double* zb = zbs[wave];
-    const long total = (long)P.E * P.num_local;
-    for (long idx = (long)blockIdx.x * 4 + wave; idx < total; idx += (long)gridDim.x * 4) {
-      const int e = (int)(idx / P.num_local), sl = (int)(idx % P.num_local);
-      const double* rec = P.blob + (long)e * P.rec.stride;
-      double zc, bc;
-      mc::draw_z_beta(P, rec + P.rec.L, P.first_sample + sl, lane, zb, zc, bc);
-      const int bj = mc::discrete_scan(P, rec, zb, lane);
-      if (lane < P.m) P.beta[idx * P.m + lane] = bc;
-      if (lane == 0) best_j[idx] = bj;
-      __builtin_amdgcn_wave_barrier();
-    }
-  }
-};
-__global__ __launch_bounds__(256) void kg_sample_prep_kernel(KgMcParams P, int* __restrict__ best_j) {
-  kg_sample_prep_kernel_body::run(MOE_VBLOCK, MOE_VGRID, nullptr, P, best_j);
-}
-
-// The same for m > 64 (more components than lanes): one THREAD per sample, serial O(m^2) back substitution and O(A m) scan
-// against operands in L2 -- a few hundred microseconds for 2 x 10^4 samples at m = 104; only the workgroup-per-sample kernel
-// consumes it.  z_i (antithetic pairs, .cpp:171-180), beta_i = L^-T z_i, first best discretised point (.cpp:436-449).
-struct kg_sample_prep_generic_kernel_body {
-  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, const KgMcParams& P, int* __restrict__ best_j) {
-    const long idx = (long)blockIdx.x * 64 + threadIdx.x;
-    const long total = (long)P.E * P.num_local;
-    if (idx >= total) return;
-    const int e = (int)(idx / P.num_local), sl = (int)(idx % P.num_local);
-    const int m = P.m, s = P.first_sample + sl;
-    const double* rec = P.blob + (long)e * P.rec.stride;
-    const double* L = rec + P.rec.L;
-    const double sign = (s & 1) ? -1.0 : 1.0;
-    const double* zrow = P.normals + (long)(s >> 1) * m;
-    double beta[kMaxMB];
-    for (int r = m - 1; r >= 0; --r) {
-      double acc = 0.0;
-      for (int l = m - 1; l > r; --l) acc = fma(L[l + (long)r * m], beta[l], acc);
-      beta[r] = (sign * zrow[r] - acc) / L[r + (long)r * m];
-    }
-    for (int c = 0; c < m; ++c) P.beta[idx * m + c] = beta[c];
-    const double* mu_disc = rec + P.rec.mu_disc;
-    const double* C_disc = rec + P.rec.C_disc;
-    double best_f = -INFINITY;
-    int bj = 0;
-    for (int j = 0; j < P.A; ++j) {
-      double v = mu_disc[j];
-      for (int c = 0; c < m; ++c) v = fma(C_disc[(long)j * m + c], sign * zrow[c], v);
-      if (-v > best_f) {  // strict: the first best point wins
-        best_f = -v;
-        bj = j;
-      }
-    }
-    best_j[idx] = bj;
-  }
-};
-__global__ __launch_bounds__(64) void kg_sample_prep_generic_kernel(KgMcParams P, int* __restrict__ best_j) {
-  kg_sample_prep_generic_kernel_body::run(MOE_VBLOCK, MOE_VGRID, nullptr, P, best_j);
-}
-
-// The START TABLE of an evaluation without derivative observations (mc::start_from_table, kg_mc.hpp): for every discretised point x_c
-// -- where the line searches start -- the coefficients of [1 ; beta] in f = -mu_after(x_c) and in its frame gradient:
-//   column 0:      -(mean + sum_j alpha KinvY_j b_j)              | -sum_j alpha KinvY_j b'_j (x_j - x_c)_k
-//   column 1 + l:  -(alpha b_{n+l} - sum_j alpha W_jl b_j)        | the same with b' (x - x_c)_k
-// (b, b' = radial3's base and first-derivative coefficient of |x_j - x_c|^2, j over the training points, n + l = fantasy point l): the
-// sums of a value + gradient pass (grad_pass_parked) with the sample's weights alpha (KinvY - W beta | beta) taken apart by beta's
-// components.  The kernel reads what the pass reads -- the frame table XsTab, KinvY, W -- through radial3, so an entry differs from
-// the pass's sum by the order of additions alone.
-// One WAVEFRONT per (discretised point, group of kStartCols<DP> columns, evaluation): every lane walks the tiles in order (one fma
-// chain per sum), then the fixed butterfly -- the order depends on n + u and DP alone, never on the batch or the ensemble.  A group's
-// columns share the radial terms, and at m <= 4 (q-KG up to four points; DP <= 8) one group is all there is.
-template <int DP>
-constexpr int kStartCols = DP <= 8 ? 5 : (DP <= 12 ? 3 : 2);
-
-template <int DP, int COV>
-__device__ __forceinline__ void start_table_sums(const KgMcParams& P, const double* __restrict__ xg, const double* __restrict__ We,
-                                                 const double* __restrict__ etab, const double (&xq)[DP], int col0, int lane,
-                                                 double* __restrict__ out) {
-  constexpr int CG = kStartCols<DP>;
-  const int n = P.n, u = P.u, m = P.m, ntiles = P.ntiles;
-  double accf[CG], accg[CG][DP];
-#pragma unroll
-  for (int i = 0; i < CG; ++i) {
-    accf[i] = 0.0;
-#pragma unroll
-    for (int k = 0; k < DP; ++k) accg[i][k] = 0.0;
-  }
-  // column col0 + i reads W's column col0 + i - 1 (clamped: a column beyond m, or column 0 here, is masked below)
-  long wcol[CG];
-#pragma unroll
-  for (int i = 0; i < CG; ++i) wcol[i] = (long)min(max(col0 + i - 1, 0), m - 1) * P.N;
-  for (int t0 = 0; t0 < ntiles; t0 += 2) {
-    // the loads of two tiles in one batch (clamped addresses: always valid)
-    double cx[2][DP], wv[2][CG];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int t = min(t0 + h, ntiles - 1);
-      const long row = min(t * 64 + lane, n - 1);
-#pragma unroll
-      for (int k = 0; k < DP; ++k) cx[h][k] = xg[((long)t * DP + k) * 64 + lane];
-#pragma unroll
-      for (int i = 0; i < CG; ++i) wv[h][i] = (col0 + i == 0) ? P.KinvY[row] : -We[row + wcol[i]];
-    }
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int t = t0 + h;
-      if (t < ntiles) {
-        const int j = t * 64 + lane;
-        double diff[DP];
-        double r2 = 1.0e-300;
-#pragma unroll
-        for (int k = 0; k < DP; ++k) {
-          diff[k] = cx[h][k] - xq[k];
-          r2 = fma(diff[k], diff[k], r2);
-        }
-        double base, first, second;
-        mc::radial3<COV, true, false>(r2, etab, base, first, second);
-#pragma unroll
-        for (int i = 0; i < CG; ++i) {
-          const int col = col0 + i;
-          double w = wv[h][i];
-          if (j >= n) w = (col >= 1 && j - n == col - 1 && j < n + u) ? 1.0 : 0.0;  // fantasy point l carries beta_l; padding nothing
-          if (col > m) w = 0.0;
-          w *= P.alpha;
-          accf[i] = fma(w, base, accf[i]);
-          const double coef = w * first;
-#pragma unroll
-          for (int k = 0; k < DP; ++k) accg[i][k] = fma(coef, diff[k], accg[i][k]);
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < CG; ++i) {
-    const int col = col0 + i;
-    const double f = mc::wave_sum_uniform(accf[i]);
-    double v = -((col == 0 ? P.mean : 0.0) + f);  // entry DP: the value
-#pragma unroll
-    for (int k = 0; k < DP; ++k) {
-      const double gk = mc::wave_sum_uniform(accg[i][k]);
-      v = (lane == k) ? -gk : v;
-    }
-    if (col <= m && lane <= DP) out[(long)col * (DP + 1) + lane] = v;
-  }
-}
-
-template <int DP>
-struct kg_start_table_kernel_body {
-  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, const KgMcParams& P, double* __restrict__ tab) {
-    __shared__ double etab[kExpTabLen];
-    const int lane = threadIdx.x;
-    const int c = blockIdx.x, col0 = blockIdx.y * kStartCols<DP>, e = blockIdx.z;
-    const int size = P.dim - P.f;
-    etab[lane] = kExp2Tab64[lane];  // (kExpTabLen == 64 == the workgroup)
-    __syncthreads();
-    const double* rec = P.blob + (long)e * P.rec.stride;
-    // the discretised point in the frame, as the line searches enter it: its coordinates on the optimised rows, 1 on fidelity rows,
-    // 0 on pads (.cpp:353-357)
-    double xq[DP];
-#pragma unroll
-    for (int k = 0; k < DP; ++k) {
-      const int pk = P.perm[k];
-      const double xo = (pk < size) ? rec[P.rec.disc + c * size + min(pk, size - 1)] : ((pk < P.dim) ? 1.0 : 0.0);
-      xq[k] = (xo - P.center[k]) * P.inv_lp[k];
-    }
-    const double* xg = P.XsTab + (long)e * P.tab_stride;
-    const double* We = P.W + (long)e * P.w_stride;
-    double* out = tab + (long)e * P.start_stride + (long)c * (1 + P.m) * (DP + 1);
-    if (P.cov_type == MOE_COV_SQUARE_EXPONENTIAL)
-      start_table_sums<DP, MOE_COV_SQUARE_EXPONENTIAL>(P, xg, We, etab, xq, col0, lane, out);
-    else
-      start_table_sums<DP, MOE_COV_MATERN_NU_2P5>(P, xg, We, etab, xq, col0, lane, out);
-  }
-};
-template <int DP>
-__global__ __launch_bounds__(64) void kg_start_table_kernel(KgMcParams P, double* __restrict__ tab) {
-  kg_start_table_kernel_body<DP>::run(MOE_VBLOCK, MOE_VGRID, nullptr, P, tab);
-}
-
-template <int DP>
-void launch_start_table_dp(const KgMcParams& P, double* tab, hipStream_t s) {
-  const dim3 grid((unsigned)P.A, (unsigned)((1 + P.m + kStartCols<DP> - 1) / kStartCols<DP>), (unsigned)P.E);
-  launch_kernel_ens<kg_start_table_kernel_body<DP>, 64>(kg_start_table_kernel<DP>, grid, dim3(64), 0, s, P, tab);
-  MOE_HIP_CHECK(hipGetLastError());
-}
-void launch_start_table(const KgMcParams& P, int dp, double* tab, hipStream_t s) {
-  switch (dp) {
-    case 4: launch_start_table_dp<4>(P, tab, s); break;
-    case 8: launch_start_table_dp<8>(P, tab, s); break;
-    case 12: launch_start_table_dp<12>(P, tab, s); break;
-    case 16: launch_start_table_dp<16>(P, tab, s); break;
-    default: throw Error(MOE_ERR_RUNTIME, "the start table is built for padded dimensions up to 16");
-  }
-}
-
-// Per-sample weights of the training rows for every sample, V[(e, sl)][r] = scale_a (KinvY[r] - sum_c W_e[r, c] beta[(e, sl), c])
-// (r = (j, a); scale_0 = alpha, scale_a = -alpha / l_{d_a}): what point_weights computes inside the MC kernel, same
-// operation order, hence the same bits.  Inside the workgroup-per-sample kernel that computation reads all of W_e
-// (N x m) per sample and CU through a few dozen loads in flight -- a sixth of the kernel at m = 16; here one thread keeps
-// a row of W in registers, beta arrives through scalar loads, and the chip writes N x M doubles at streaming speed.
-// m > 64 (r4): the columns go down in passes of 64 -- pass [c_lo, c_lo + MB) continues the fma chain from the partial sum the previous
-// pass left in V (plain store), the last pass scales and streams the result out; one pass (first = last) is the code of m <= 64.
-template <int MB>
-struct kg_sample_weights_kernel_body {
-  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, const KgMcParams& P, double* __restrict__ V, int samples_per_block, int c_lo, int first, int last) {
-    // table entry t = (point j, slot a) <-> row r = j (1 + g) + a of the N training rows / the m fantasy rows; slots beyond the GP's
-    // 1 + g (r4: a streamed-weights instantiation with more derivative slots than observed derivatives) hold zeros
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    const int e = blockIdx.z;
-    const int m = P.m, g1 = 1 + P.g;
-    const int pj = t / P.v_slots1, pa = t - pj * P.v_slots1;
-    const bool slot_ok = pa < g1;
-    const int r = slot_ok ? pj * g1 + pa : P.N + m;  // (an unused slot: behind everything, stored as 0)
-    const double* __restrict__ We = P.W + (long)e * P.w_stride;
-    const double* __restrict__ beta = P.beta;
-    double l[MB];
-    const int rr = min(r, P.N - 1);
-  #pragma unroll
-    for (int c = 0; c < MB; ++c) {  // zero beyond m: the unconditional fma below then leaves v untouched
-      const double t = We[rr + (long)min(c_lo + c, m - 1) * P.N];
-      l[c] = (c_lo + c < m) ? t : 0.0;
-    }
-    const double kiy = P.KinvY[rr];
-    const int a = rr % g1;
-    const double scale = (a == 0) ? P.alpha : -P.alpha * P.inv_lp[a > 0 ? a - 1 : 0];
-    const int s0 = blockIdx.y * samples_per_block, s1 = min(P.num_local, s0 + samples_per_block);
-    // rows behind the training set (v_stride > N: the streamed-weights MC kernel reads whole tiles): the fantasy points' weights are the
-    // sample's beta itself, scaled like a training row (kg_mc_wave.hpp kg_sample), then zeros up to the end of the last tile
-    const int cf = r - P.N;
-    const bool fantasy = cf >= 0 && cf < m;
-    const double fscale = ((cf % g1) == 0) ? P.alpha : -P.alpha * P.inv_lp[max(cf % g1, 1) - 1];
-    for (int sl = s0; sl < s1; ++sl) {
-      const long so = (long)e * P.num_local + sl;
-      const double* __restrict__ bs = beta + so * m + c_lo;
-      double v = first ? kiy : V[so * P.v_stride + min(t, (int)P.v_stride - 1)];
-  #pragma unroll
-      for (int c = 0; c < MB; ++c) v = fma(-l[c], bs[c], v);  // uniform, contiguous: wide scalar loads (reads up to MB - m
-                                                              // doubles past the row: next rows / the zeroed pad, times l = 0)
-      if (t >= P.v_stride) continue;
-      if (r < P.N) {
-        if (last)
-          __builtin_nontemporal_store(v * scale, &V[so * P.v_stride + t]);  // (streaming: 1.28 GB at C5, read once by the MC kernel)
-        else
-          V[so * P.v_stride + t] = v;
-      } else if (last) {
-        V[so * P.v_stride + t] = fantasy ? beta[so * m + min(cf, m - 1)] * fscale : 0.0;
-      }
-    }
-  }
-};
-template <int MB>
-__global__ __launch_bounds__(256) void kg_sample_weights_kernel(KgMcParams P, double* __restrict__ V, int samples_per_block,
-                                                               int c_lo = 0, int first = 1, int last = 1) {
-  kg_sample_weights_kernel_body<MB>::run(MOE_VBLOCK, MOE_VGRID, nullptr, P, V, samples_per_block, c_lo, first, last);
-}
-
-// The same table for m > 64 (r4; the stretch point's m = 104) with its sums on the matrix pipe: V_e (table rows x samples) = K^-1 y -
-// W_e beta_e^T through gemm128.hpp's tile core, scaled and written ONCE (the kernel above needs two passes over a partially written
-// table there: 2 x 5.1 ms per evaluation against the MC kernel's own 9.4).  Needs the table's rows to BE the training rows
-// (v_slots1 == 1 + g).  The sums are formed in the MFMA's order, not in the c-order of the in-kernel weights: for these shapes a result
-// depends at rounding level on whether the table fitted its cap (the m <= 64 paths keep their bit-for-bit equality).
-// Grid (row tiles of 128 table entries, column tiles of 128 samples, E).
-struct kg_table128_kernel_body {
-  static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridDim, const void*, const KgMcParams& P, double* __restrict__ V) {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    const int e = blockIdx.z, m = P.m, g1 = 1 + P.g;
-    const long s0 = (long)e * P.num_local;
-    g128::Operand A{P.W + (long)e * P.w_stride, (long)P.N, P.N, m, 1};   // W[t + c N]: table rows contiguous
-    g128::Operand B{P.beta + s0 * m, (long)m, P.num_local, m, 1};        // beta[sample m + c]: K (= c) contiguous
-    g128::f64x4 acc[4][4];
-    const int t0 = blockIdx.x * g128::TM, j0 = blockIdx.y * g128::TM;
-    if (t0 < P.N) g128::tile_product<false, true>(A, B, t0, j0, 0, m, smem, acc);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int wi = (wave & 1) * 64, wj = (wave >> 1) * 64;
-    const int lk = lane >> 4, lx = lane & 15;
-  #pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      const int t = t0 + wi + 16 * a + lx;
-      const int tt = min(t, P.N - 1);
-      const double kiy = P.KinvY[tt];
-      const int sa = tt % g1;
-      const double scale = (sa == 0) ? P.alpha : -P.alpha * P.inv_lp[sa > 0 ? sa - 1 : 0];
-      // rows behind the training set: the fantasy points' weights are the sample's beta itself, scaled like a training row, then zeros
-      const int cf = t - P.N;
-      const bool fantasy = cf >= 0 && cf < m;
-      const double fscale = ((cf % g1) == 0) ? P.alpha : -P.alpha * P.inv_lp[max(cf % g1, 1) - 1];
-  #pragma unroll
-      for (int b = 0; b < 4; ++b)
-  #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int smp = j0 + wj + 16 * b + lk + 4 * r;
-          if (t < P.v_stride && smp < P.num_local) {
-            const long so = s0 + smp;
-            double v;
-            if (t < P.N)
-              v = (kiy - acc[a][b][r]) * scale;
-            else
-              v = fantasy ? P.beta[so * m + min(cf, m - 1)] * fscale : 0.0;
-            __builtin_nontemporal_store(v, &V[so * P.v_stride + t]);
-          }
-        }
-    }
-  }
-};
-__global__ __launch_bounds__(256, 2) void kg_table128_kernel(KgMcParams P, double* __restrict__ V) {
-  kg_table128_kernel_body::run(MOE_VBLOCK, MOE_VGRID, nullptr, P, V);
-}
-
-void launch_sample_weights(const KgMcParams& P, double* V, hipStream_t s, bool table_only = false) {
-  // r6: `table_only` -- the consumer (the streamed-weights kernel) has no in-kernel form of the weights whose bits the table would have
-  // to reproduce -- takes the matrix-pipe kernel from m = 16 on: per (row, sample) entry the fma version's loop is one dependent chain
-  // of m fmas behind a scalar-load round trip and the previous store's acknowledgement (1.17 ms per 2.56 GB at C5 = 2.2 TB/s)
-  const bool mfma = P.v_slots1 == 1 + P.g && (P.m > 64 || (table_only && P.m >= 16));
-  if (mfma) {
-    MOE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kg_table128_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)g128::kSmemBytes));
-    launch_kernel_ens<kg_table128_kernel_body, 256, 2>(kg_table128_kernel, dim3((unsigned)((P.v_stride + g128::TM - 1) / g128::TM), (P.num_local + g128::TM - 1) / g128::TM, P.E),
-                       dim3(256), g128::kSmemBytes, s, P, V);
-    MOE_HIP_CHECK(hipGetLastError());
-    return;
-  }
-  const int spb = 64;
-  dim3 grid((unsigned)((P.v_stride + 255) / 256), (P.num_local + spb - 1) / spb, P.E);
-  if (P.m <= 16)
-    launch_kernel_ens<kg_sample_weights_kernel_body<16>, 256>(kg_sample_weights_kernel<16>, grid, dim3(256), 0, s, P, V, spb, 0, 1, 1);
-  else if (P.m <= 32)
-    launch_kernel_ens<kg_sample_weights_kernel_body<32>, 256>(kg_sample_weights_kernel<32>, grid, dim3(256), 0, s, P, V, spb, 0, 1, 1);
-  else  // (m > 64 in passes of 64 columns; ONE pass with a 128-column row of W in registers -- 256 of them, half in the accumulation file --
-        //  measured slower: 34 against 21 ms of MC phase per evaluation at the stretch point, m = 104)
-    for (int c_lo = 0; c_lo < P.m; c_lo += 64)
-      launch_kernel_ens<kg_sample_weights_kernel_body<64>, 256>(kg_sample_weights_kernel<64>, grid, dim3(256), 0, s, P, V, spb, c_lo, c_lo == 0 ? 1 : 0, c_lo + 64 >= P.m ? 1 : 0);
-  MOE_HIP_CHECK(hipGetLastError());
-}
-
+// the MC kernel families (kg_mc.hpp: instantiated per padded dimension in the kg_mc_dp*.hip units)
 void launch_mc(const KgMcParams& P, int dp, int G, bool xlds, int blocks, int waves, size_t shm, hipStream_t s) {
-  switch (dp) {
-    case 4: mc::launch_dp<4>(P, G, xlds, blocks, waves, shm, s); break;
-    case 8: mc::launch_dp<8>(P, G, xlds, blocks, waves, shm, s); break;
-    case 12: mc::launch_dp<12>(P, G, xlds, blocks, waves, shm, s); break;
-    case 16: mc::launch_dp<16>(P, G, xlds, blocks, waves, shm, s); break;
-    case 24: mc::launch_dp<24>(P, G, xlds, blocks, waves, shm, s); break;
-    case 32: mc::launch_dp<32>(P, G, xlds, blocks, waves, shm, s); break;
-    default: throw Error(MOE_ERR_RUNTIME, "unsupported padded dimension");
-  }
+  dispatch_dp(dp, [&](auto DP) { mc::launch_dp<decltype(DP)::value>(P, G, xlds, blocks, waves, shm, s); });
 }
 
 void launch_mc_lane(const KgMcParams& P, int dp, int G, int rec_head, int blocks, int waves, size_t shm, hipStream_t s) {
-  switch (dp) {
-    case 4: mc::launch_lane_dp<4>(P, G, rec_head, blocks, waves, shm, s); break;
-    case 8: mc::launch_lane_dp<8>(P, G, rec_head, blocks, waves, shm, s); break;
-    case 12: mc::launch_lane_dp<12>(P, G, rec_head, blocks, waves, shm, s); break;
-    case 16: mc::launch_lane_dp<16>(P, G, rec_head, blocks, waves, shm, s); break;
-    default: throw Error(MOE_ERR_RUNTIME, "unsupported padded dimension in the lane-parked MC kernel");
-  }
+  dispatch_dp(dp, [&](auto DP) {
+    if constexpr (decltype(DP)::value <= 16)  // (kg_mc_lane.hpp kMaxLaneDP)
+      mc::launch_lane_dp<decltype(DP)::value>(P, G, rec_head, blocks, waves, shm, s);
+    else
+      throw Error(MOE_ERR_RUNTIME, "unsupported padded dimension in the lane-parked MC kernel");
+  });
 }
 
 void launch_mc_stream(const KgMcParams& P, int dp, int G, int blocks, int waves, size_t shm, hipStream_t s) {
-  switch (dp) {
-    case 4: mc::launch_stream_dp<4>(P, G, blocks, waves, shm, s); break;
-    case 8: mc::launch_stream_dp<8>(P, G, blocks, waves, shm, s); break;
-    case 12: mc::launch_stream_dp<12>(P, G, blocks, waves, shm, s); break;
-    case 16: mc::launch_stream_dp<16>(P, G, blocks, waves, shm, s); break;
-    case 24: mc::launch_stream_dp<24>(P, G, blocks, waves, shm, s); break;
-    case 32: mc::launch_stream_dp<32>(P, G, blocks, waves, shm, s); break;
-    default: throw Error(MOE_ERR_RUNTIME, "unsupported padded dimension");
-  }
+  dispatch_dp(dp, [&](auto DP) { mc::launch_stream_dp<decltype(DP)::value>(P, G, blocks, waves, shm, s); });
 }
 
 void launch_mc_block(const KgMcParams& P, int dp, int G, int tr, int num_lds_tiles, int blocks, int waves, hipStream_t s) {
-  switch (dp) {
-    case 4: mc::launch_block_dp<4>(P, G, tr, num_lds_tiles, blocks, waves, s); break;
-    case 8: mc::launch_block_dp<8>(P, G, tr, num_lds_tiles, blocks, waves, s); break;
-    case 12: mc::launch_block_dp<12>(P, G, tr, num_lds_tiles, blocks, waves, s); break;
-    case 16: mc::launch_block_dp<16>(P, G, tr, num_lds_tiles, blocks, waves, s); break;
-    case 24: mc::launch_block_dp<24>(P, G, tr, num_lds_tiles, blocks, waves, s); break;
-    case 32: mc::launch_block_dp<32>(P, G, tr, num_lds_tiles, blocks, waves, s); break;
-    default: throw Error(MOE_ERR_RUNTIME, "unsupported padded dimension");
-  }
+  dispatch_dp(dp, [&](auto DP) { mc::launch_block_dp<decltype(DP)::value>(P, G, tr, num_lds_tiles, blocks, waves, s); });
 }
-
-// q-KG fast path: the gradient tail never materialises the N x M covariance matrix (see launch_fused_tail).  A function of the
-// evaluation's shape and MOE_KG_FUSED_TAIL -- kg_launch (plan_mc) and kg_max_batch both ask here, so they cannot disagree.
-bool fused_tail_taken(bool want_grad, int g, int m) { return want_grad && g == 0 && m <= 8 && env_int("MOE_KG_FUSED_TAIL", 1) != 0; }
-// samples per TB partial of the gradient tail
-int tail_chunk_len(bool fused_tail, int m) { return fused_tail ? kFusedChunk : (m > 64 ? kTbChunkWide : kTbChunk); }
 
 // The shape of one kg_launch: the union of u = q + p points with 1 + g rows each (m rows), A = u + P points in the discretised set,
 // `size` = d - num_fidelity coordinates the inner optimisations move, E evaluations of num_local samples each.
@@ -1942,14 +640,7 @@ KgMcParams launch_mc_step(GpDev& gp, const KgDims& k, const McPlan& pl, const mo
   if (pl.prep) {
     gp.kBestJ.reserve((size_t)total);
     mp.best_j = gp.kBestJ.p;
-    int* best_j_p = gp.kBestJ.p;
-    if (m > kMaxM) {  // more components than lanes: thread-per-sample pre-pass (mandatory there)
-      launch_kernel_ens<kg_sample_prep_generic_kernel_body, 64>(kg_sample_prep_generic_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64), 0, s, mp, best_j_p);
-    } else {
-      const int pb = (int)std::min<long>((total + 3) / 4, (long)gp.num_cu * 8);
-      launch_kernel_ens<kg_sample_prep_kernel_body, 256>(kg_sample_prep_kernel, dim3(pb), dim3(256), 0, s, mp, best_j_p);
-    }
-    MOE_HIP_CHECK(hipGetLastError());
+    launch_sample_prep(mp, gp.kBestJ.p, gp.num_cu, s);
   }
   if (pl.weight_table) {  // (m > 64: the table kernel takes the columns of W 64 at a time, r4)
     gp.kV.reserve((size_t)mp.v_stride * (size_t)total + (size_t)64 * mp.v_slots1);  // (+ one tile: the sweeps prefetch one tile ahead)
@@ -2041,12 +732,7 @@ KgTailParams launch_tail_step(GpDev& gp, const KgDims& k, const McPlan& pl, cons
       const int sw_slices = N >= 1024 ? 8 : (N >= 256 ? 4 : 1);  // (m > 64 too: the stretch point's 104 x 20 000 over N = 26 000 walked 1625 stages unsplit)
       if (sw_slices > 1) gp.kSWpart.reserve((size_t)sw_slices * m * num_local * E);
       if (m > 64 && sw_slices > 1) {  // (the kernel takes W / T / strides from `tl`)
-        MOE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kg_sw128_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)g128::kSmemBytes));
-        double* sw_part_p = gp.kSWpart.p;
-        launch_kernel_ens<kg_sw128_kernel_body, 256, 2>(kg_sw128_kernel, dim3((num_local + g128::TM - 1) / g128::TM, sw_slices, E), dim3(256), g128::kSmemBytes, s, tl,
-                   sw_part_p, sw_slices);
-        launch_sum_slices(gp.kSWpart.p, sw_slices, (long)m * num_local * E, gp.kSW.p, s);
+        launch_sw128(tl, gp.kSWpart.p, sw_slices, gp.kSW.p, s);
       } else {
         launch_gemm_tn_splitk(m, num_local, N, tl.W, N, gp.kT.p, N, gp.kSW.p, gp.kSWpart.p, sw_slices, s, E, tl.w_stride, (long)num_local * N);
       }
@@ -2057,9 +743,7 @@ KgTailParams launch_tail_step(GpDev& gp, const KgDims& k, const McPlan& pl, cons
     gp.kZcPart.reserve((size_t)E * ((num_local + zc_chunk_len(m) - 1) / zc_chunk_len(m)) * m * m);
     launch_zc(tl, gp.kZcPart.p, s, !zc_sum_in_finish(m, num_local));
   } else {
-    const unsigned long long* ctr_p = gp.kCounters.p;
-    const int* flags_p = gp.kStateI.p;
-    launch_kernel_ens<kg_sum_kernel_body, 256>(kg_sum_kernel, dim3(E), dim3(256), 0, s, tl, dFin, ctr_p, flags_p);
+    launch_kg_sum(tl, dFin, gp.kCounters.p, gp.kStateI.p, s);
   }
   MOE_HIP_CHECK(hipGetLastError());
   return tl;
@@ -2277,15 +961,7 @@ KgPending kg_launch(GpDev& gp, int num_fidelity, const moe_gd_params_t& gd, cons
   }
 
   // ---- coordinate tables ----
-  {
-    dim3 grid((unsigned)((tab_stride + 255) / 256), E);
-    const double *dXp = gp.dX.p, *dUnionP = gp.dUnion;
-    double* dTabP = gp.kTab.p;
-    unsigned long long* dCtrP = gp.kCounters.p;
-    launch_kernel_ens<build_xs_tab_kernel_body, 256>(build_xs_tab_kernel, grid, dim3(256), 0, s, dXp, k.n, dUnionP, u, dp, pl.ntiles, tp, dTabP, tab_stride,
-                                                     pl.pair_rows, dCtrP, (long)n_ctr);
-    MOE_HIP_CHECK(hipGetLastError());
-  }
+  launch_xs_tab(gp.dX.p, k.n, gp.dUnion, u, dp, pl.ntiles, tp, gp.kTab.p, tab_stride, pl.pair_rows, gp.kCounters.p, (long)n_ctr, E, s);
 
   // ---- 2. MC kernel (the start table in front of it closes the state phase) ----
   const KgMcParams mp = launch_mc_step(gp, k, pl, gd, tp, R, dBlobP, dNormalsP, se.bl, tab_stride, n_ctr, t_state, t_mc, s);

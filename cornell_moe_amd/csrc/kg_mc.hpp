@@ -3,7 +3,7 @@
 // of a sample every family uses.  One header per kernel family sits on top of it -- kg_mc_wave.hpp (wave-per-sample), kg_mc_lane.hpp
 // (its lane-parked form), kg_mc_stream.hpp (streamed weights), kg_mc_block.hpp (workgroup-per-sample), and kg_mc_lds.hpp (the
 // LDS-state line search three of them share) -- instantiated by the per-dimension translation units kg_mc_dp*.hip (compiled in
-// parallel).  kg.hip includes this header only.
+// parallel).  kg.hip, kg_prep.hip and kg_tail.hip include this header only.
 //
 // What the reference does per MC sample i (gpp_knowledge_gradient_optimization.cpp:170-196): draw z_i, set the fantasy
 // observations y_i = mu(Xu) + L z_i, RE-SOLVE K_after^-1 (y - mean) with two O((N+m)^2) triangular sweeps
@@ -96,14 +96,14 @@ struct KgMcParams {
   unsigned long long* counters;  // [E][2]: value passes, value + gradient passes
   unsigned int* next_sample;     // [E] work counters (zeroed before launch)
   unsigned long long* prof;      // 16 spare words behind the counters (MOE_BLOCK_PROF builds)
-  const double* V;               // [E][num_local][v_stride] per-sample weights alpha-scaled (kg_sample_weights_kernel, kg.hip), or NULL
+  const double* V;               // [E][num_local][v_stride] per-sample weights alpha-scaled (kg_sample_weights_kernel, kg_prep.hip), or NULL
   long v_stride;                 // N (workgroup-per-sample kernel) or ntiles * 64 * v_slots1: the fantasy points' weights and the zero
                                  // padding included (streamed-weights kernel, kg_mc_stream_kernel)
   int v_slots1;                  // weights per point in the table: 1 + g, or 1 + G of the streamed-weights instantiation when it has
                                  // more derivative slots than the GP observes (g = 5 .. 7 -> 8, 9 .. 11 -> 12: the extra slots hold 0)
   const int* best_j;             // [E][num_local] start point of every sample's line search, precomputed with beta by
-                                 // kg_sample_prep_kernel (kg.hip); NULL = each sample computes them itself
-  const double* start_tab;       // [E][A][1 + m][DP + 1] the start table (kg_start_table_kernel, kg.hip; mc::start_from_table), or NULL:
+                                 // kg_sample_prep_kernel (kg_prep.hip); NULL = each sample computes them itself
+  const double* start_tab;       // [E][A][1 + m][DP + 1] the start table (kg_start_table_kernel, kg_prep.hip; mc::start_from_table), or NULL:
   long start_stride;             // f and grad f at the discretised points as (1 + m)-term dot products with [1 ; beta]
 };
 
@@ -257,7 +257,7 @@ __device__ __forceinline__ double uniform(double v) {
   return __hiloint2double(hi, lo);
 }
 
-// The first gradient of a sample's line search from the evaluation's START TABLE (kg_start_table_kernel, kg.hip).  A line search
+// The first gradient of a sample's line search from the evaluation's START TABLE (kg_start_table_kernel, kg_prep.hip).  A line search
 // starts at a discretised point x_c, and mu_after,i(x) = mu_n(x) + cov_n(Xu, x)^T beta_i is linear in the sample's beta: f = -mu_after
 // and its frame gradient at x_c are (1 + m)-term dot products whose coefficients depend on the evaluation alone.  `row` = the table
 // row of x_c, [1 + m][DP + 1] doubles: column 0 the mu_n part, column 1 + l the coefficient of beta_l; entry k < DP the frame gradient's

@@ -612,7 +612,6 @@ __global__ __launch_bounds__(kLaneMaxThreads) void kg_mc_lane_kernel(KgMcParams 
 template <int DP, int G, bool EXACT = false>
 inline void launch_lane_inst(const KgMcParams& P, int rec_head, int blocks, int waves, size_t shm, hipStream_t s) {
   auto kern = kg_mc_lane_kernel<DP, G, EXACT>;
-  MOE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
   // (the ensemble twin is built on the body WITHOUT the lookup-first order: see kLaneLookupFirst)
   launch_kernel_ens<kg_mc_lane_kernel_body<DP, G, EXACT>, kLaneMaxThreads>(kern, dim3(blocks), dim3(waves * 64), shm, s, P, rec_head);
   MOE_HIP_CHECK(hipGetLastError());

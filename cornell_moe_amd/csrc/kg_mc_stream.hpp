@@ -84,7 +84,6 @@ __global__ __launch_bounds__(512) void kg_mc_stream_kernel(KgMcParams P) {
 template <int DP, int G>
 inline void launch_stream_inst(const KgMcParams& P, int blocks, int waves, size_t shm, hipStream_t s) {
   auto kern = kg_mc_stream_kernel<DP, G>;
-  MOE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
   launch_kernel_ens<kg_mc_stream_kernel_body<DP, G>, 512>(kern, dim3(blocks), dim3(waves * 64), shm, s, P);
   MOE_HIP_CHECK(hipGetLastError());
 }

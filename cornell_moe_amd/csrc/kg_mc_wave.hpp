@@ -562,7 +562,6 @@ __global__ __launch_bounds__(SMALL ? 1024 : 512) void kg_mc_kernel(KgMcParams P)
 template <int DP, int G, bool XLDS, bool SMALL>
 inline void launch_inst2(const KgMcParams& P, int blocks, int waves, size_t shm, hipStream_t s) {
   auto kern = kg_mc_kernel<DP, G, XLDS, SMALL>;
-  MOE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
   launch_kernel_ens<kg_mc_kernel_body<DP, G, XLDS, SMALL>, (SMALL ? 1024 : 512)>(kern, dim3(blocks), dim3(waves * 64), shm, s, P);
   MOE_HIP_CHECK(hipGetLastError());
 }

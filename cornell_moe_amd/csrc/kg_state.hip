@@ -399,13 +399,6 @@ __global__ __launch_bounds__(256) void kg_finish_small_kernel(KgFinishParams P) 
   kg_finish_small_kernel_body::run(MOE_VBLOCK, MOE_VGRID, nullptr, P);
 }
 
-template <class K>
-void opt_in_lds(K kern, size_t shm) {
-  // (set on every launch: the attribute is per device where the runtime enforces it, and one process may drive several devices)
-  if (shm > 48 * 1024)
-    MOE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-}
-
 }  // namespace
 
 void launch_kg_state(const KgStateParams& P, hipStream_t s) {
@@ -413,7 +406,6 @@ void launch_kg_state(const KgStateParams& P, hipStream_t s) {
   const size_t room = kLdsBudget / sizeof(double) - mm;
   const int rchunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(P.A, 1), room / P.m));
   const size_t shm = sizeof(double) * (mm + (size_t)rchunk * P.m);
-  opt_in_lds(kg_state_kernel, shm);
   launch_kernel_ens<kg_state_kernel_body, 256>(kg_state_kernel, dim3(P.E), dim3(256), shm, s, P, rchunk);
   MOE_HIP_CHECK(hipGetLastError());
 }
@@ -421,7 +413,6 @@ void launch_kg_state(const KgStateParams& P, hipStream_t s) {
 void launch_kg_dchol(const KgStateParams& P, hipStream_t s) {
   if (P.ng <= 0) return;
   const size_t shm = sizeof(double) * ((size_t)P.m * (P.m + 1) / 2 + 3 * (size_t)P.m);
-  opt_in_lds(kg_dchol_kernel, shm);
   launch_kernel_ens<kg_dchol_kernel_body, 256>(kg_dchol_kernel, dim3(P.q * P.d, P.E), dim3(256), shm, s, P);
   MOE_HIP_CHECK(hipGetLastError());
 }
@@ -431,7 +422,6 @@ void launch_kg_finish(const KgFinishParams& P, double* Y, hipStream_t s) {
     launch_kernel_ens<kg_finish_small_kernel_body, 256>(kg_finish_small_kernel, dim3(P.q * P.d, P.E), dim3(256), 0, s, P);
   } else {
     const size_t shm = sizeof(double) * (size_t)P.m * (P.m + 1);
-    opt_in_lds(kg_y_kernel, shm);
     launch_kernel_ens<kg_y_kernel_body, 128>(kg_y_kernel, dim3(P.E), dim3(128), shm, s, P, Y);
     launch_kernel_ens<kg_finish_kernel_body, 64>(kg_finish_kernel, dim3(P.q * P.d, P.E), dim3(64), 0, s, P, (const double*)Y);
   }

@@ -154,6 +154,10 @@ inline void ens_launch_impl(const void* table_dev, int members, dim3 grid, dim3 
 template <class Body, int MaxThreads, int MinBlocks = 1, class... P, class... A>
 inline void launch_kernel_ens(void (*kernel)(P...), dim3 grid, dim3 block, size_t shm, hipStream_t s, A&&... a) {
   static_assert(sizeof...(P) == sizeof...(A), "kernel argument count");
+  // more than 48 KB of dynamic LDS is opted into here, on the current device, for immediate launches and per-member replays alike
+  // (on every launch, like the twin's own in ens_launch_impl: the attribute is per device)
+  if (shm > 48 * 1024)
+    MOE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
   Recorder* r = Recorder::current();
   if (r == nullptr) {
     kernel<<<grid, block, shm, s>>>(static_cast<P>(std::forward<A>(a))...);

@@ -1,6 +1,6 @@
 """GPU tests (-m gpu) of the start table: without derivative observations the LDS-table wave-per-sample kernels (lane-parked and frame
 line search) take the FIRST gradient of every sample's line search -- at the sample's discretised point -- from a per-evaluation table
-of (1 + m)-term dot products with [1 ; beta] (kg.hip: kg_start_table_kernel; kg_mc.hpp: start_from_table) instead of a pass over the
+of (1 + m)-term dot products with [1 ; beta] (kg_prep.hip: kg_start_table_kernel; kg_mc.hpp: start_from_table) instead of a pass over the
 n + u points.  Checked against the plain-C oracle at test_gpu_parity.py's KG tolerances (helpers.TOL; end points 1e-8 on all but 0.2 %
 of the samples; gradient passes counted as the oracle counts them, value passes never more -- test_gpu_sweep.py's relation), and for
 the bit-for-bit properties the table must not disturb: lane = frame, alone = in a batch, ensemble-wide = member by member."""

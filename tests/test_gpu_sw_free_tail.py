@@ -1,4 +1,4 @@
-"""GPU tests (-m gpu) of the S_W-free form of the T-free q-KG gradient tail (kg.hip: kg_fused_point_kernel's union rows and
+"""GPU tests (-m gpu) of the S_W-free form of the T-free q-KG gradient tail (kg_tail.hip: kg_fused_point_kernel's union rows and
 kg_zc_direct_kernel; MOE_KG_FUSED_ONE_PASS=1, the default).  The form replaces the per-sample S_W,i = W^T T_i and
 c_i = L^-1 alpha (k(Xu, x*_i) - S_W,i) by ZC = L^T (KB - TB^T W) L^-T, with the sum over the samples taken first.  It is held
   * to the two-kernel form (MOE_KG_FUSED_ONE_PASS=0: kg_fused_sample_kernel + kg_fused_c_kernel + kg_fused_point_kernel + kg_zc_part)

@@ -343,6 +343,51 @@ def test_fused_tail_matches_materialised_tail(monkeypatch):
         assert np.abs(a["grad_sum"] - b["grad_sum"]).max() <= 1e-11 * scale
 
 
+def test_materialised_tail_beyond_48_kb_of_lds(monkeypatch):
+    """The materialised tail with W^T T formed in kg_sw_kernel from W staged in LDS, N m 8 = 800 x 8 x 8 = 51 200 bytes: more than the
+    48 KB a kernel may take without opting in, less than the 96 KB from which the driver forms W^T T by GEMM.  A single evaluation
+    against the batch, ensemble-wide against member-by-member launches (the twin's opt-in against the per-member kernel's), and
+    the T-free tail as the comparator at the neighbouring test's bound."""
+    from cornell_moe_amd import api
+    from cornell_moe_amd.workloads import make_workload
+    w = make_workload(n=800, d=2, q=8, p=0, M=64, P=6, derivs=(), num_restarts=3)
+    assert w.X.shape[0] * w.q * 8 > 48 * 1024
+    G = api.DeviceGP(w.hyperparameters, w.X, w.y, w.noise, ())
+    best = float(G.additional_mean(w.discrete).min())
+    monkeypatch.setenv("MOE_KG_FUSED_TAIL", "0")
+    a = G.kg(w.inner_gd, w.bounds, w.discrete, w.Xq, None, w.M, best, w.kg_normals)
+    assert G.last_kernel_info()["fused_tail"] == 0
+    batch = G.kg_batch(w.inner_gd, w.bounds, w.discrete, w.Xq_restarts, None, w.M, best, w.kg_normals)
+    assert a["kg_sum"] == batch["kg_sum"][0] and np.array_equal(a["grad_sum"], batch["grad_sum"][0])
+    # two members with the same hyper-parameters: their chains line up, every kernel of the tail runs as an ensemble twin
+    hypers = np.tile(np.concatenate([[w.alpha], w.lengths]), (2, 1))
+    noises = np.tile(np.asarray(w.noise, dtype=np.float64).reshape(1, -1), (2, 1))
+    disc = np.tile(w.discrete.reshape(1, -1), (2, 1))
+    Gm = api.DeviceGPMCMC(hypers, noises, w.X, w.y, ())
+    bests = np.array([best, best])
+    try:
+        api.set_ensemble_launches(1)
+        s0 = api.ensemble_launch_stats()
+        k1, g1 = Gm.kg_batch(w.inner_gd, w.bounds, disc, w.Xq_restarts, None, w.M, bests, w.kg_normals)
+        s1 = api.ensemble_launch_stats()
+        api.set_ensemble_launches(0)
+        k0, g0 = Gm.kg_batch(w.inner_gd, w.bounds, disc, w.Xq_restarts, None, w.M, bests, w.kg_normals)
+    finally:
+        api.set_ensemble_launches(-1)
+    assert all(gp.last_kernel_info()["fused_tail"] == 0 for gp in Gm.gps)
+    assert s1[0] > s0[0] and s1[1] == s0[1] and s1[2] > s0[2], (s0, s1)  # merged evaluations, no fall-back, launches they issued
+    assert np.all(np.isfinite(k1)) and np.abs(g1).max() > 0
+    assert np.array_equal(k0, k1) and np.array_equal(g0, g1)
+    monkeypatch.setenv("MOE_KG_FUSED_TAIL", "1")
+    b = G.kg(w.inner_gd, w.bounds, w.discrete, w.Xq, None, w.M, best, w.kg_normals)
+    assert G.last_kernel_info()["fused_tail"] == 1
+    assert a["kg_sum"] == b["kg_sum"]
+    scale = max(np.abs(a["grad_sum"]).max(), abs(a["kg_sum"]))
+    dev = np.abs(a["grad_sum"] - b["grad_sum"]).max()
+    print("materialised against T-free tail at n = 800: max |d grad_sum| = %.3e, bound %.3e" % (dev, 1e-11 * scale))
+    assert dev <= 1e-11 * scale
+
+
 def test_one_pass_tail_matches_two_kernel_tail(monkeypatch):
     """r6: for m <= 4 and d <= 8 the T-free tail computes every entry of T once, for both of its contractions, in one kernel
     (kg_fused_pair_kernel) instead of once in each of two: same gradient to rounding (the partial sums of S_W and TB are taken in
