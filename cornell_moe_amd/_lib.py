@@ -182,6 +182,8 @@ SIGNATURES = {
     "moe_ensemble_launch_stats": (C.c_int, [C.POINTER(C.c_longlong)]),
     "moe_last_kernel_ms": (C.c_int, [_GP, dp]),
     "moe_last_kernel_info": (C.c_int, [_GP, C.POINTER(C.c_int)]),
+    "moe_last_kg_moves": (C.c_int, [_GP, C.POINTER(C.c_longlong)]),
+    "moe_last_kg_best_points": (C.c_int, [_GP, C.POINTER(C.c_int), C.POINTER(C.c_int), dp, C.c_longlong]),
 }
 
 _lib = None

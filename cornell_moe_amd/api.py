@@ -623,6 +623,24 @@ class DeviceGP(object):
         info["xlds"] &= 1
         return info
 
+    def last_kg_moves(self):
+        """moe_last_kg_moves: how often a workgroup of the last KG call's MC kernel moved to another evaluation."""
+        out = C.c_longlong(0)
+        if _lib.load().moe_last_kg_moves(self._h, C.byref(out)):
+            raise RuntimeError("moe_last_kg_moves failed")
+        return int(out.value)
+
+    def last_kg_best_points(self):
+        """moe_last_kg_best_points: the inner optimisations' end points of the last KG call, [evaluations][samples][dim]."""
+        L = _lib.load()
+        E, M = C.c_int(0), C.c_int(0)
+        if L.moe_last_kg_best_points(self._h, C.byref(E), C.byref(M), None, 0):
+            raise RuntimeError("moe_last_kg_best_points failed")
+        out = np.zeros((E.value, M.value, self.d))
+        if out.size and L.moe_last_kg_best_points(self._h, C.byref(E), C.byref(M), out.ctypes.data_as(dp), out.size):
+            raise RuntimeError("moe_last_kg_best_points failed")
+        return out
+
 
 def kg_batch_multi(gps, shard, inner_params, bounds, discrete, Xq_all, Xp, num_mc, best_so_far, normals, want_grad=True,
                    num_fidelity=0):

@@ -565,6 +565,41 @@ int moe_last_kernel_info(const moe_gp_t* gp, int* out8) {
   return MOE_OK;
 }
 
+int moe_last_kg_moves(const moe_gp_t* gp_c, long long* moves) {
+  if (gp_c == nullptr || moves == nullptr) return MOE_ERR_RUNTIME;
+  return guarded(nullptr, [&] {
+    std::unique_lock<std::mutex> lk;
+    moe::GpDev& gp = lock_gp(gp_c, lk);
+    unsigned long long w = 0;
+    if (gp.last_moves != nullptr) {
+      gp.use_device();
+      MOE_HIP_CHECK(hipStreamSynchronize(gp.stream));
+      MOE_HIP_CHECK(hipMemcpy(&w, gp.last_moves, sizeof(w), hipMemcpyDeviceToHost));
+    }
+    *moves = (long long)w;
+  });
+}
+
+int moe_last_kg_best_points(const moe_gp_t* gp_c, int* num_evals, int* num_local, double* out, long long capacity) {
+  if (gp_c == nullptr || num_evals == nullptr || num_local == nullptr) return MOE_ERR_RUNTIME;
+  return guarded(nullptr, [&] {
+    std::unique_lock<std::mutex> lk;
+    moe::GpDev& gp = lock_gp(gp_c, lk);
+    const int E = gp.last_best_shape[0], M = gp.last_best_shape[1], d = gp.d, dp = gp.dp;
+    *num_evals = E;
+    *num_local = M;
+    const size_t rows = (size_t)E * M;
+    if (out == nullptr || rows == 0) return;
+    require(capacity >= (long long)(rows * d), "moe_last_kg_best_points: output too small");
+    gp.use_device();
+    MOE_HIP_CHECK(hipStreamSynchronize(gp.stream));
+    std::vector<double> padded(rows * dp);
+    MOE_HIP_CHECK(hipMemcpy(padded.data(), gp.kBestPoint.p, sizeof(double) * padded.size(), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < rows; ++i)
+      for (int k = 0; k < d; ++k) out[i * d + k] = padded[i * dp + k];
+  });
+}
+
 int moe_ei(const moe_gp_t* gp_c, const double* points_to_sample, const double* points_being_sampled, int num_to_sample,
            int num_being_sampled, int num_mc, double best_so_far, const double* normals, double* ei, double* grad_ei,
            moe_error_t* err) {

@@ -100,6 +100,11 @@ struct GpDev {
   // table | T-free gradient tail | workgroups | sample pre-pass; bits 1 .. 4 of the second word: far frame | wide frame | lane-parked
   // kernel | the line searches took their first gradient from the start table
   int last_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // device word in which the last KG launch's MC kernel counted its workgroups' moves between evaluations (moe_last_kg_moves;
+  // kg_mc.hpp next_evaluation), or NULL before the first launch
+  const unsigned long long* last_moves = nullptr;
+  // evaluations and samples per evaluation of the last KG launch: the shape of kBestPoint (moe_last_kg_best_points)
+  int last_best_shape[2] = {0, 0};
 
   GpDev(const double* hyper, int cov_type, const double* X_in, const double* y_in, const double* noise_in,
         const int* derivs_in, int g_in, int d_in, int n_in, int device_in);

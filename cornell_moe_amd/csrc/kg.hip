@@ -37,6 +37,10 @@ void set_ensemble_members_hint(int members) { t_ens_members_hint = members > 1 ?
 
 namespace {
 
+// tickets per wavefront that the fullest evaluation must have left for an idle workgroup to move to it (plan_mc; DESIGN 7: the A/B of
+// 1, 2 and 4 -- 29.11 / 29.05 / 29.12 ms per headline step, the three runs of 2 within 0.005 ms; MOE_KG_STEAL_MIN_PER_WAVE overrides)
+constexpr int kStealWaves = 2;
+
 struct EventTimer {
   hipEvent_t a = nullptr, b = nullptr;  // (created on first use: a recorded evaluation -- launch.hpp -- times nothing)
   bool on = false;
@@ -154,6 +158,8 @@ struct McPlan {
   bool weight_table = false;  // the per-sample weight table is built
   long v_stride = 0;          // its doubles per sample, and its slots per point
   int v_slots1 = 0;
+  int steal_min = 0;          // KgMcParams::steal_min (0: static assignment) and ::steal_skew
+  int steal_skew = 0;
   bool fused_tail = false;    // the T-free q-KG tail
   int chunk_len = 0;          // samples per TB partial of the tail
 };
@@ -169,6 +175,8 @@ McPlan plan_mc(const GpDev& gp, const KgDims& k, const double* bounds, const dou
   const std::optional<int> forced_variant = env_opt("MOE_KG_VARIANT");
   const int prep_mode = env_int("MOE_KG_PREP", -1);  // 1: the sample pre-pass for every kernel, 0: only where it is mandatory
   const bool stream_weights = env_int("MOE_KG_STREAM_WEIGHTS", 1) != 0;
+  const bool steal = env_int("MOE_KG_STEAL", 1) != 0;           // 0: a workgroup keeps to its static share of the evaluations
+  const bool steal_skew = env_int("MOE_KG_STEAL_SKEW", 0) != 0;  // test switch: every workgroup starts on evaluation 0
   // the weight table's cap: the caller's share of the workspace budget (kg_evaluate_batch, kg_mcmc_sums), 4 GB for a bare kg_launch
   const double v_cap = std::getenv("MOE_KG_V_MAX_GB") ? (double)env_int("MOE_KG_V_MAX_GB", 4)
                                                       : (weight_table_gb >= 0.0 ? weight_table_gb : 4.0);
@@ -386,6 +394,12 @@ McPlan plan_mc(const GpDev& gp, const KgDims& k, const double* bounds, const dou
   pl.wide_lds_tiles = wide_lds_tiles;
   pl.pair_rows = (wide_dp || variant == 2 || (variant == 0 && mc::wide_eval(dp, xlds))) ? 1 : 0;
   pl.rec_head = rec_head;
+  // A workgroup out of tickets moves on while the fullest evaluation has at least kStealWaves tickets per wavefront of the workgroup
+  // left (mc::next_evaluation; the workgroup-per-sample kernel draws one ticket per workgroup).  Under the test switch the
+  // evaluations other than the first have no workgroup of their own: every ticket left counts.
+  if (steal_skew && !steal) throw Error(MOE_ERR_INVALID_VALUE, "MOE_KG_STEAL_SKEW=1 needs MOE_KG_STEAL=1", 0, 0, 0);
+  pl.steal_min = !steal ? 0 : (steal_skew ? 1 : std::max(1, env_int("MOE_KG_STEAL_MIN_PER_WAVE", kStealWaves) * (variant == 1 ? 1 : waves)));
+  pl.steal_skew = steal_skew ? 1 : 0;
   pl.multi_trial = (far_frame || small_lane) ? 0 : 1;
   // r6: the small shapes on the lane-parked kernel take their Armijo trials several per sweep, too -- each trial computed exactly as
   // a single-trial pass computes it (kg_mc.hpp eval_multi_exact: same bits as one trial per pass; MOE_KG_SMALL_MULTI=0: one per pass)
@@ -627,6 +641,8 @@ KgMcParams launch_mc_step(GpDev& gp, const KgDims& k, const McPlan& pl, const mo
   mp.v_slots1 = pl.v_slots1;
   mp.start_tab = nullptr;
   mp.start_stride = 0;
+  mp.steal_min = pl.steal_min;
+  mp.steal_skew = pl.steal_skew;
   if (pl.start_table) {  // the last kernel of the state phase: it reads the coordinate tables, K^-1 y, W and the records' discretised set
     mp.start_stride = (long)k.A * (1 + m) * (dp + 1);
     gp.kStartTab.reserve((size_t)mp.start_stride * E);
@@ -974,6 +990,9 @@ KgPending kg_launch(GpDev& gp, int num_fidelity, const moe_gd_params_t& gd, cons
                          pl.waves, pl.variant == 1 ? pl.tr : pl.wide_lds_tiles, pl.weight_table ? 1 : 0, pl.fused_tail ? 1 : 0, pl.blocks,
                          pl.prep ? 1 : 0};
     std::copy(info, info + 8, gp.last_info);
+    gp.last_moves = mp.prof + kMovesWord;
+    gp.last_best_shape[0] = E;
+    gp.last_best_shape[1] = k.num_local;
   }
 
   // ---- 3. gradient tail ----

@@ -105,7 +105,11 @@ struct KgMcParams {
                                  // kg_sample_prep_kernel (kg_prep.hip); NULL = each sample computes them itself
   const double* start_tab;       // [E][A][1 + m][DP + 1] the start table (kg_start_table_kernel, kg_prep.hip; mc::start_from_table), or NULL:
   long start_stride;             // f and grad f at the discretised points as (1 + m)-term dot products with [1 ; beta]
+  int steal_min;                 // a workgroup out of tickets moves to the evaluation with the most tickets left while that has at
+                                 // least this many (mc::next_evaluation); 0: it exits, the static assignment (MOE_KG_STEAL=0)
+  int steal_skew;                // test switch (MOE_KG_STEAL_SKEW=1): every workgroup starts on evaluation 0
 };
+constexpr int kMovesWord = 15;  // word of KgMcParams::prof that counts the moves of a call (product builds: the words are otherwise unused)
 
 #if defined(__HIPCC__)
 namespace mc {
@@ -1025,6 +1029,69 @@ __device__ __forceinline__ int discrete_scan(const KgMcParams& P, const double* 
     }
   }
   return __builtin_amdgcn_readfirstlane(best_j);
+}
+
+// ---- which evaluation a workgroup serves: the same rule in all four kernel families ----
+// Static share first: workgroups b, b + E, b + 2E, ... serve evaluation b mod E (b mod 8 is also the XCD, so with E = 8 each
+// evaluation's W / table stay in one XCD's L2); with fewer workgroups than evaluations a workgroup walks b, b + gridDim.x, ...
+// Evaluations differ in cost (the line searches' pass counts), so a workgroup whose share has no tickets left does not exit while
+// others still run: it MOVES to the evaluation with the most tickets left and draws from that one's counter.  Which wavefront takes
+// which sample never mattered to the result -- every per-sample output has its own slot, the pass counters are integer atomics -- so
+// the bits are those of the static assignment.
+//   first_evaluation: where a workgroup starts.
+//   next_evaluation:  called by every thread of the workgroup where a ticket loop has ended (workgroup-uniform control flow); returns the
+//     evaluation to stage and draw from next, or -1: exit.  `moved` is the workgroup's own flag (false at first), `slot` one LDS word
+//     that no wavefront uses between two samples.  The move: a barrier, then wave 0 reads the ticket counters of all E evaluations
+//     (device-scope relaxed atomic loads: a plain load may be served stale), takes the largest num_local - min(counter, num_local), ties
+//     to the first in cyclic order behind `e` so that thieves spread out, and exits below P.steal_min; the choice goes to the other
+//     wavefronts through `slot`.  An evaluation that was left has nothing remaining ever again (the counters only grow), so a workgroup
+//     moves at most E times.
+__device__ __forceinline__ int first_evaluation(const KgMcParams& P, const VIdx& blockIdx) {
+  return P.steal_skew != 0 ? 0 : (int)(blockIdx.x % (unsigned)P.E);
+}
+// (the move itself, on scalars.  Inlined: as an out-of-line call it put the headline kernel kg_mc_lane_kernel<8,0> at 256 VGPRs with 16
+//  bytes of scratch per lane and added ~100 bytes to the frame kernels; inlined the headline stays at 255 VGPRs without scratch, and the
+//  instantiations that already spilt gain 4 .. 20 bytes -- DESIGN 5.3 item 3)
+__device__ __forceinline__ int move_to_fullest(const unsigned int* next_sample, unsigned long long* moves, int E, int num_local,
+                                            int steal_min, int e, int* slot) {
+  __syncthreads();  // every wavefront is out of its ticket loop: `slot` is free
+  if (threadIdx.x < 64) {
+    const int lane = threadIdx.x;
+    unsigned long long key = 0;  // remaining tickets << 32 | ~(cyclic distance behind e)
+    for (int c = lane; c < E; c += 64) {
+      const unsigned int drawn = __hip_atomic_load(next_sample + (long)c * kTicketStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const unsigned int nl = (unsigned int)num_local;
+      const unsigned int remaining = nl - min(drawn, nl);
+      int dist = c - e - 1;
+      if (dist < 0) dist += E;
+      const unsigned long long k2 = ((unsigned long long)remaining << 32) | (0xffffffffu - (unsigned int)dist);
+      key = k2 > key ? k2 : key;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const unsigned long long o = __shfl_xor(key, off, 64);
+      key = o > key ? o : key;
+    }
+    if (lane == 0) {
+      const unsigned int remaining = (unsigned int)(key >> 32);
+      const int dist = (int)(0xffffffffu - (unsigned int)key);
+      const int to = (remaining >= (unsigned int)steal_min) ? (e + 1 + dist) % E : -1;
+      *(volatile int*)slot = to;
+#if !MOE_BLOCK_PROF
+      if (to >= 0) atomicAdd(moves, 1ull);
+#endif
+    }
+  }
+  __syncthreads();
+  const int to = __builtin_amdgcn_readfirstlane(*(volatile int*)slot);
+  __syncthreads();  // `slot` goes back to its wavefront
+  return to;
+}
+__device__ __forceinline__ int next_evaluation(const KgMcParams& P, const VIdx& gridDim, int e, bool& moved, int* slot) {
+  if (!moved && P.steal_skew == 0 && gridDim.x < (unsigned)P.E && e + (int)gridDim.x < P.E) return e + (int)gridDim.x;
+  if (P.steal_min <= 0 || P.E == 1) return -1;
+  moved = true;
+  return move_to_fullest(P.next_sample, P.prof + kMovesWord, P.E, P.num_local, P.steal_min, e, slot);
 }
 
 }  // namespace mc

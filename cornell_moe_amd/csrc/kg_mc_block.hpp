@@ -585,7 +585,9 @@ struct kg_mc_block_kernel_body {
     ev.lane = lane;
     ev.cov_type = P.cov_type;
     ev.par = 0;
-    for (int e = blockIdx.x % P.E; e < P.E; e += (gridDim.x < (unsigned)P.E ? gridDim.x : P.E)) {
+    // (which evaluations this workgroup serves, and in what order: kg_mc.hpp next_evaluation; its LDS word is the sample index's)
+    bool moved = false;
+    for (int e = first_evaluation(P, blockIdx); e >= 0; e = next_evaluation(P, gridDim, e, moved, ctl)) {
       const double* tab = P.XsTab + (long)e * P.tab_stride;
       const double* rec = P.blob + (long)e * P.rec.stride;
       const double* Lsm = rec + P.rec.L;
@@ -718,7 +720,6 @@ struct kg_mc_block_kernel_body {
         atomicAdd(&P.prof[15], ev.seg[2] + ev.seg[3]);
       }
   #endif
-      if (gridDim.x >= (unsigned)P.E) break;
     }
   }
 };

@@ -560,7 +560,10 @@ static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridD
   double* zb = aw + ntiles * (1 + G) * 64;
   if (threadIdx.x < kExpTabLen) smem[threadIdx.x] = kExp2Tab64[threadIdx.x];
   fill_lane_constants<DP>(P, cst);
-  for (int e = blockIdx.x % P.E; e < P.E; e += (gridDim.x < (unsigned)P.E ? gridDim.x : P.E)) {
+  bool moved = false;
+  // (which evaluations this workgroup serves, and in what order: kg_mc.hpp next_evaluation; its LDS word is wave 0's scratch)
+  for (int e = first_evaluation(P, blockIdx); e >= 0;
+       e = next_evaluation(P, gridDim, e, moved, reinterpret_cast<int*>(wshared + ntiles * (1 + G) * 64))) {
     const double* xg = P.XsTab + (long)e * P.tab_stride;
     __syncthreads();  // previous evaluation's readers are done
     for (int pt = threadIdx.x; pt < ntiles * 64; pt += blockDim.x) {  // one point per thread and step
@@ -600,7 +603,6 @@ static __device__ __forceinline__ void run(const VIdx blockIdx, const VIdx gridD
       atomicAdd(&P.counters[2 * e], (unsigned long long)tot_val);
       atomicAdd(&P.counters[2 * e + 1], (unsigned long long)tot_grad);
     }
-    if (gridDim.x >= (unsigned)P.E) break;
   }
 }
 };

@@ -27,7 +27,9 @@ struct kg_mc_stream_kernel_body {
     double* st = coords + wtab + wave * kWideScratch;
     if (threadIdx.x < kExpTabLen) smem[threadIdx.x] = kExp2Tab64[threadIdx.x];
     const int size = P.dim - P.f;
-    for (int e = blockIdx.x % P.E; e < P.E; e += (gridDim.x < (unsigned)P.E ? gridDim.x : P.E)) {
+    // (which evaluations this workgroup serves, and in what order: kg_mc.hpp next_evaluation; its LDS word is wave 0's scratch)
+    bool moved = false;
+    for (int e = first_evaluation(P, blockIdx); e >= 0; e = next_evaluation(P, gridDim, e, moved, reinterpret_cast<int*>(coords + wtab))) {
       const double* xs = P.XsTab + (long)e * P.tab_stride;
       const double* rec = P.blob + (long)e * P.rec.stride;
       __syncthreads();  // previous evaluation's readers are done (and the exp table is visible)
@@ -72,7 +74,6 @@ struct kg_mc_stream_kernel_body {
         atomicAdd(&P.counters[2 * e], tot_val);
         atomicAdd(&P.counters[2 * e + 1], tot_grad);
       }
-      if (gridDim.x >= (unsigned)P.E) break;
     }
   }
 };

@@ -505,9 +505,10 @@ struct kg_mc_kernel_body {
     if (threadIdx.x < kExpTabLen) smem[threadIdx.x] = kExp2Tab64[threadIdx.x];
     fill_frame_constants<DP>(P, cst);
     if (!XLDS) __syncthreads();
-    // evaluation of this workgroup: workgroups b, b + E, b + 2E, ... serve evaluation b mod E (b mod 8 is also the XCD, so
-    // with E = 8 each evaluation's W / table stay in one XCD's L2); with fewer workgroups than evaluations they loop.
-    for (int e = blockIdx.x % P.E; e < P.E; e += (gridDim.x < (unsigned)P.E ? gridDim.x : P.E)) {
+    // (which evaluations this workgroup serves, and in what order: kg_mc.hpp next_evaluation; its LDS word is wave 0's scratch)
+    bool moved = false;
+    for (int e = first_evaluation(P, blockIdx); e >= 0;
+         e = next_evaluation(P, gridDim, e, moved, reinterpret_cast<int*>(coords + (XLDS ? tab : wtab) + ntiles * (1 + G) * 64))) {
       const double* xs = P.XsTab + (long)e * P.tab_stride;
       if (XLDS) {
         __syncthreads();  // previous evaluation's readers are done
@@ -550,7 +551,6 @@ struct kg_mc_kernel_body {
         atomicAdd(&P.counters[2 * e], tot_val);
         atomicAdd(&P.counters[2 * e + 1], tot_grad);
       }
-      if (gridDim.x >= (unsigned)P.E) break;
     }
   }
 };

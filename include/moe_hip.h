@@ -1193,6 +1193,14 @@ int moe_last_kernel_ms(const moe_gp_t* gp, double* out5);
  * leading tiles of the paired-row table kept in LDS (variant 0, d > 16),
  * out[4] = streamed per-sample weight table, out[5] = T-free gradient tail, out[6] = workgroups, out[7] = sample pre-pass. */
 int moe_last_kernel_info(const moe_gp_t* gp, int* out8);
+/* How many times a workgroup of the last moe_kg* call's Monte-Carlo kernel moved from an evaluation whose samples were all drawn to
+ * one that still had some (diagnostics; 0 with MOE_KG_STEAL=0, with one evaluation per call, and before the first call).  Reads one
+ * word back from the device: call it after the evaluation has returned. */
+int moe_last_kg_moves(const moe_gp_t* gp, long long* moves);
+/* The end points of the inner optimisations of the last moe_kg* call on this handle, all evaluations of the call (moe_kg returns them
+ * for its one evaluation only): *num_evals and *num_local are set to the call's shape; `out`, if not NULL, receives
+ * [num_evals][num_local][dim] doubles (capacity: doubles available in out).  Diagnostics: reads the points back from the device. */
+int moe_last_kg_best_points(const moe_gp_t* gp, int* num_evals, int* num_local, double* out, long long capacity);
 
 #ifdef __cplusplus
 }
