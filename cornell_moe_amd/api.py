@@ -1215,6 +1215,65 @@ def ehvi_suggest(gps, gps2, reference_point, front, gd_params, bounds, starts, n
                          points_being_sampled)
 
 
+def _ehvi3_members(gps, gps2, gps3, reference_point, front):
+    """(the three objectives' handles, E, dim, GPs kept alive, reference point [3], front [F][3] or None, F) of the ensemble forms
+    of the three-objective expected hypervolume improvement; gps, gps2 and gps3 shaped alike (a DeviceGPMCMC, a list of DeviceGP or
+    one DeviceGP), E members each"""
+    arrs, keeps, E, d = [], [], None, None
+    for g in (gps, gps2, gps3):
+        arr, Ek, dk, keep = _ensemble_handles([g] if isinstance(g, DeviceGP) else g)
+        if E is None:
+            E, d = Ek, dk
+        if E == 0 or Ek != E:
+            raise BoundsException("one GP per ensemble member and objective", Ek, E, E)
+        arrs.append(arr)
+        keeps.append(keep)
+    ref = np.ascontiguousarray(reference_point, dtype=np.float64).ravel()
+    if ref.size != 3:
+        raise BoundsException("the reference point has three coordinates", ref.size, 3, 3)
+    fr = np.ascontiguousarray([] if front is None else front, dtype=np.float64).reshape(-1, 3)
+    F = fr.shape[0]
+    return arrs, E, d, keeps, ref, (fr if F else None), F
+
+
+def ehvi3_ensemble(gps, gps2, gps3, reference_point, front, points, points_being_sampled=None, want_grad=True,
+                   want_member_values=False):
+    """moe_ehvi3_mcmc: the three-objective expected hypervolume improvement (minimisation) averaged over the ensemble at points
+    [C][dim], in one device call.  Member e is gps[e], gps2[e] and gps3[e] (objectives 1, 2, 3), without derivative observations.
+    reference_point [3]; front [F][3] (None or empty: none; F <= 192) mutually non-dominated, strictly inside the reference point
+    and in the canonical order: the third objective ascending, ties by the first, then by the second (pareto_front_3 of
+    expected_hypervolume_improvement.py returns that form).  points_being_sampled [p][dim] condition the three GPs' covariances, and
+    their believed outcomes join every member's own front.  Returns value [C], with want_grad (value, grad [C][dim]), and with
+    want_member_values additionally the members' values [E][C] as the last item.  SingularMatrixException(3 e + objective - 1, j):
+    the GP, counted flat, and the pending point."""
+    arrs, E, d, keep, ref, fr, F = _ehvi3_members(gps, gps2, gps3, reference_point, front)
+    pre, post = (arrs[0], arrs[1], arrs[2], E, ref.ctypes.data_as(dp), fr.ctypes.data_as(dp) if F else None, F), ()
+    return _acq1_evaluate(_lib.load().moe_ehvi3_mcmc, pre, post, d, points, want_grad, points_being_sampled,
+                          extra_shape=(E,), want_extra=want_member_values)
+
+
+def ehvi3_multistart(gps, gps2, gps3, reference_point, front, gd_params, bounds, starts, gradient_ascent=True, want_path=False,
+                     points_being_sampled=None):
+    """moe_ehvi3_mcmc_multistart: one suggestion by the ensemble-averaged three-objective expected hypervolume improvement --
+    ei_analytic_multistart's screening, 20 kept starts, restarted ascent on the device and end-point selection, and its dict."""
+    arrs, E, d, keep, ref, fr, F = _ehvi3_members(gps, gps2, gps3, reference_point, front)
+    pre, post = (arrs[0], arrs[1], arrs[2], E, ref.ctypes.data_as(dp), fr.ctypes.data_as(dp) if F else None, F), ()
+    return _acq1_multistart(_lib.load().moe_ehvi3_mcmc_multistart, pre, post, d, gd_params, bounds, starts, gradient_ascent, want_path,
+                            points_being_sampled)
+
+
+def ehvi3_suggest(gps, gps2, gps3, reference_point, front, gd_params, bounds, starts, num_to_sample, gradient_ascent=True,
+                  points_being_sampled=None):
+    """moe_ehvi3_mcmc_suggest: num_to_sample points greedily by the ensemble-averaged three-objective expected hypervolume
+    improvement -- round t is ehvi3_multistart from the same starts [S][dim] with the pending points points_being_sampled [p][dim]
+    (may be None) followed by the points of the rounds before, bit for bit, in one device call.  p + num_to_sample - 1 <= 64.
+    Returns a dict: points [q][dim], values [q], found [q]."""
+    arrs, E, d, keep, ref, fr, F = _ehvi3_members(gps, gps2, gps3, reference_point, front)
+    pre, post = (arrs[0], arrs[1], arrs[2], E, ref.ctypes.data_as(dp), fr.ctypes.data_as(dp) if F else None, F), ()
+    return _acq1_suggest(_lib.load().moe_ehvi3_mcmc_suggest, pre, post, d, gd_params, bounds, starts, num_to_sample, gradient_ascent,
+                         points_being_sampled)
+
+
 def _gibbon_members(gps, min_values):
     """(handles, count, dim, members kept alive, min-values [E][K], K) of the ensemble forms of the min-value entropy acquisition; a
     single DeviceGP counts as a list of one"""

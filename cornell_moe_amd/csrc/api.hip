@@ -62,7 +62,7 @@ moe::GpDev& lock_gp(const moe_gp_t* gp_c, std::unique_lock<std::mutex>& lk) {
   return gp->dev;
 }
 
-// The first check of the ensemble one-point acquisitions' entry points (Acq1::check_num_mcmc; moe_ehvi_mcmc* have their own).
+// The first check of the ensemble one-point acquisitions' entry points (Acq1::check_num_mcmc; moe_ehvi_mcmc* and moe_ehvi3_mcmc* have their own).
 void check_num_mcmc(int num_mcmc) {
   if (num_mcmc < 1 || num_mcmc > 1024) throw moe::Error(MOE_ERR_BOUNDS, "num_mcmc must be between 1 and 1024", num_mcmc, 1, 1024);
 }
@@ -915,7 +915,7 @@ int moe_gp_paths_minimize(const moe_gp_t* const* gps, int num_mcmc, const double
   });
 }
 
-// ---- the ensemble forms of the one-point acquisitions (kg1_ascent.hpp): six objectives, three shapes of entry point each ----
+// ---- the ensemble forms of the one-point acquisitions (kg1_ascent.hpp): seven objectives, three shapes of entry point each ----
 extern "C++" {  // (the helpers return C++ types)
 namespace {
 
@@ -1073,6 +1073,32 @@ Acq1 ehvi(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, int num_mcmc,
   };
   a.handles = [=] { return two_objective_handles(gps, gps2, num_mcmc); };
   a.call = [=] { return moe::ehvi1_call(num_mcmc, reference_point, front, num_front); };
+  return a;
+}
+
+// The GPs of a three-objective call, flat and ordered [e][objective]
+std::vector<const moe_gp_t*> three_objective_handles(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* gps3,
+                                                    int num_mcmc) {
+  std::vector<const moe_gp_t*> flat(3 * (size_t)num_mcmc);
+  for (int e = 0; e < num_mcmc; ++e) {
+    flat[3 * (size_t)e] = gps[e];
+    flat[3 * (size_t)e + 1] = gps2[e];
+    flat[3 * (size_t)e + 2] = gps3[e];
+  }
+  return flat;
+}
+
+Acq1 ehvi3(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* gps3, int num_mcmc,
+           const double* reference_point, const double* front, int num_front) {
+  Acq1 a = acq1_of(gps, num_mcmc, "the expected hypervolume improvement");
+  a.check_num_mcmc = moe::check_ehvi3_num_mcmc;
+  a.pointers = gps && gps2 && gps3 && reference_point && (num_front <= 0 || front);
+  a.check_shapes = [=](int num_points) {
+    moe::check_ehvi3_front(reference_point, front, num_front);
+    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_points);
+  };
+  a.handles = [=] { return three_objective_handles(gps, gps2, gps3, num_mcmc); };
+  a.call = [=] { return moe::ehvi3_call(num_mcmc, reference_point, front, num_front); };
   return a;
 }
 
@@ -1297,6 +1323,40 @@ int moe_ehvi_mcmc_suggest(const moe_gp_t* const* gps, const moe_gp_t* const* gps
                           moe_error_t* err) {
   return guarded(err, [&] {
     acq1_suggest(ehvi(gps, gps2, num_mcmc, reference_point, front, num_front), outer, domain_bounds, points_being_sampled,
+                 num_being_sampled, starts, num_starts, do_gradient_ascent, num_to_sample, {best_points, best_values, found});
+  });
+}
+
+int moe_ehvi3_mcmc(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* gps3, int num_mcmc,
+                   const double* reference_point, const double* front, int num_front, const double* points_being_sampled,
+                   int num_being_sampled, const double* points, int num_points, int want_grad, double* value, double* grad,
+                   double* member_values_out, moe_error_t* err) {
+  return guarded(err, [&] {
+    acq1_evaluate(ehvi3(gps, gps2, gps3, num_mcmc, reference_point, front, num_front), points_being_sampled, num_being_sampled, points,
+                  num_points, want_grad, value, grad, member_values_out);
+  });
+}
+
+int moe_ehvi3_mcmc_multistart(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* gps3, int num_mcmc,
+                              const double* reference_point, const double* front, int num_front, const moe_gd_params_t* outer,
+                              const double* domain_bounds, const double* points_being_sampled, int num_being_sampled,
+                              const double* starts, int num_starts, int do_gradient_ascent, double* best_point, double* best_value,
+                              int* found, double* start_values, int* kept_index, double* end_points, double* end_values, double* path,
+                              int* steps_taken, moe_error_t* err) {
+  return guarded(err, [&] {
+    acq1_multistart(ehvi3(gps, gps2, gps3, num_mcmc, reference_point, front, num_front), outer, domain_bounds, points_being_sampled,
+                    num_being_sampled, starts, num_starts, do_gradient_ascent,
+                    {best_point, best_value, found, start_values, kept_index, end_points, end_values, path, steps_taken});
+  });
+}
+
+int moe_ehvi3_mcmc_suggest(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* gps3, int num_mcmc,
+                           const double* reference_point, const double* front, int num_front, const moe_gd_params_t* outer,
+                           const double* domain_bounds, const double* points_being_sampled, int num_being_sampled,
+                           const double* starts, int num_starts, int do_gradient_ascent, int num_to_sample, double* best_points,
+                           double* best_values, int* found, moe_error_t* err) {
+  return guarded(err, [&] {
+    acq1_suggest(ehvi3(gps, gps2, gps3, num_mcmc, reference_point, front, num_front), outer, domain_bounds, points_being_sampled,
                  num_being_sampled, starts, num_starts, do_gradient_ascent, num_to_sample, {best_points, best_values, found});
   });
 }

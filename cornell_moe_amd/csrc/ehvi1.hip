@@ -4,7 +4,7 @@
 // client of kg1_ascent.hip's staging, ascent and drivers.  The pending-row extension is kg1_pending.hip's, the
 // layout and the pass are ei1.hip's (ei1.hpp); this file keeps a sub-member's candidate kernel and the two-sum gradient kernel
 // with its tail, the front kernel, the strip kernel, the combine kernel, the members' check and the description of the call
-// (ehvi1_call).
+// (ehvi1_call).  ehvi3.hip, the three-objective form, takes the sub-member's chain, the members' check and psi from here (ehvi1.hpp).
 //
 // Minimisation.  A call takes E joint hyper-samples; member e is two GPs, objective 1 and objective 2, the 2 E GPs being the
 // SUB-MEMBERS of one Kg1Ensemble ordered [e][role].  r = (r1, r2) is the reference point, the front F >= 0 points (u_i, v_i) with
@@ -47,6 +47,7 @@
 
 #include "acq1_device.hpp"
 #include "device_cov.hpp"
+#include "ehvi1.hpp"
 #include "ei1.hpp"
 #include "kg1_ascent.hpp"
 
@@ -234,24 +235,6 @@ __global__ __launch_bounds__(64) void ehvi1_front_kernel(const double* const* __
   if (lane == 0) counts[e] = n;
 }
 
-// psi and, with a gradient, its two derivatives at the edge t of a GP with mean mu and floored deviations sigma / sg
-__device__ __forceinline__ void ehvi1_edge(double t, double mu, double sigma, double sg, bool want_grad, double& psi, double& dmu, double& dvar) {
-  const double z = (t - mu) / sigma;
-  const double cdf = normal_cdf(z), pdf = normal_pdf(z);
-  psi = (t - mu) * cdf + sigma * pdf;
-  dmu = 0.0;
-  dvar = 0.0;
-  if (!want_grad) return;
-  if (sg == sigma) {  // (the same inputs give the same bits)
-    dmu = -cdf;
-    dvar = pdf / (2.0 * sg);
-  } else {
-    const double zg = (t - mu) / sg;
-    dmu = -normal_cdf(zg);
-    dvar = normal_pdf(zg) / (2.0 * sg);
-  }
-}
-
 // The strip sums (the header's reduction order).  Grid (ceil(C / 4), E), four wavefronts, one candidate each; kg: the sub-members'
 // [mu Cs | var Cs]; fronts / counts as ehvi1_front_kernel leaves them; vals [E][Cs] takes A_e and, with want_grad, coef [E][Cs][4]
 // takes dA/dmu_1, dA/dvar_1, dA/dmu_2, dA/dvar_2.
@@ -380,15 +363,22 @@ void grad_tail(const Kg1Member& m, const double* Px, int nc, int c0, hipStream_t
   MOE_HIP_CHECK(hipGetLastError());
 }
 
+}  // namespace
+
 void ehvi1_eval_points(const Kg1Member& m, const double* Px, const double*, int C, bool with_grad, hipStream_t s) {
   ei1_eval_passes(m, Px, C, with_grad, s, "ehvi1_eval_pass", cand_step, grad_tail);
 }
 
-// EI's layout with two result sets: dKg [mu C | var C], dGrad [grad mu C d | grad var C d]
-Kg1Member member(const Kg1Objective&, GpDev& gp, int e, int C, bool with_grad, int* fail, int pcap, int* fail_pending) {
+Kg1Member ehvi1_member(GpDev& gp, int role, int C, bool with_grad, int* fail, int pcap, int* fail_pending) {
   Kg1Member m = ei1_member(gp, C, 0.0, with_grad, fail, pcap, fail_pending, 2);
-  m.role = e % 2;
+  m.role = role;
   return m;
+}
+
+namespace {
+
+Kg1Member member(const Kg1Objective&, GpDev& gp, int e, int C, bool with_grad, int* fail, int pcap, int* fail_pending) {
+  return ehvi1_member(gp, e % 2, C, with_grad, fail, pcap, fail_pending);
 }
 
 // mu of every sub-member at P_j0 .. j0 + count - 1, then every member's front takes the believed outcomes
@@ -446,14 +436,14 @@ void check_member(const GpDev& g, const GpDev&, size_t e, int) {
                 (double)e);
 }
 
-void check_members(const Kg1Objective&, const std::vector<GpDev*>& gps, int pending_room) {
+}  // namespace
+
+void ehvi1_check_members(const Kg1Objective&, const std::vector<GpDev*>& gps, int pending_room) {
   kg1_check_members(gps, 0, check_member);
   if (pending_room > kKg1MaxPending)
     throw Error(MOE_ERR_BOUNDS, "pending points (num_being_sampled + num_to_sample - 1) must fit 64 extension rows", pending_room, 0,
                 kKg1MaxPending);
 }
-
-}  // namespace
 
 // No sets, no fidelity coordinates, no incumbents (the members' best values are zeros, kept by the call); groups of two sub-members
 // under the strip rule, the members' own values kept
@@ -470,7 +460,7 @@ Kg1Call ehvi1_call(int num_mcmc, const double* reference_point, const double* fr
   call.o.combine = combine;
   call.o.client = call.client.get();
   call.o.group_values = true;
-  call.check_members = check_members;
+  call.check_members = ehvi1_check_members;
   return call;
 }
 

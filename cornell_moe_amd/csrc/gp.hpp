@@ -72,7 +72,7 @@ struct GpDev {
   // integers (the members' failure words first)
   DevBuf<double> kg1oD;
   DevBuf<int> kg1oI;
-  // the expected hypervolume improvement (ehvi1.hip; held by the ensemble's first member): the caller's front, the members' fronts
+  // the expected hypervolume improvement (ehvi1.hip, ehvi3.hip; held by the ensemble's first member): the caller's front, the members' fronts
   // and their counts, the members' values and gradient coefficients
   DevBuf<double> ehviD;
   // the ensemble-averaged posterior mean and the recommendation (recommend.hip; held by the ensemble's first member): the call's
@@ -300,7 +300,7 @@ void kg1_eval_points(const Kg1Member& m, const double* Px, const double* Ph, int
 void kg1_clear_fail(int* fail, int count, hipStream_t s);  // INT_MAX: no candidate has failed
 // The ensemble forms of the one-point acquisitions: evaluate at points, multistart ascent and greedy batches of each, with pending
 // points [num_pending][dim] by the Kriging-believer fantasy of kg1_pending.hip.  Every client describes its call in one function
-// (kg1_ascent.hpp: kg1_call, ei1_call, gibbon1_call, cei1_call, ehvi1_call, logcei1_call) and the three drivers of kg1_ascent.hip run it; here are
+// (kg1_ascent.hpp: kg1_call, ei1_call, gibbon1_call, cei1_call, ehvi1_call, logcei1_call, ehvi3_call) and the three drivers of kg1_ascent.hip run it; here are
 // the checks that need no handle, which the entry points make first, and the limits.
 // kg1_opt.hip: the discretised knowledge gradient (moe_kg_discrete_mcmc*).  discrete_all: the members' sets back to back.
 void check_kg_discrete_ensemble_shapes(int num_mcmc, int num_fidelity, const int* num_discrete, int num_points);
@@ -335,6 +335,13 @@ constexpr int kEhviMaxFront = 960;
 constexpr int kEhviMaxMembers = 512;
 void check_ehvi_num_mcmc(int num_mcmc);
 void check_ehvi_front(const double* reference_point, const double* front, int num_front);
+// ehvi3.hip: the three-objective expected hypervolume improvement (moe_ehvi3_mcmc*): the same over members of three GPs each, the
+// GPs of a call [3 E] ordered [e][objective].  reference_point [3]; front [num_front][3] in the canonical order (the third
+// objective ascending, ties by the first, then by the second), mutually non-dominated, strictly inside the reference point.
+constexpr int kEhvi3MaxFront = 192;
+constexpr int kEhvi3MaxMembers = 341;
+void check_ehvi3_num_mcmc(int num_mcmc);
+void check_ehvi3_front(const double* reference_point, const double* front, int num_front);
 // loo.hip: leave-one-out cross-validation on the GP's current factorisation, every one of the N = n (1 + g) scalar observations left
 // out by itself.  mean_out / var_out [n][1 + g]: the LOO predictive mean (function values in the caller's units) and variance.
 void loo_predict_on_device(GpDev& gp, double* mean_out, double* var_out);

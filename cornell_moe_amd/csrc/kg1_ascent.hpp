@@ -5,8 +5,9 @@
 // and the entry points (api.hip) hand that to a driver.  The clients: kg1_opt.hip (the discretised knowledge gradient), ei1.hip
 // (the analytic expected improvement), gibbon1.hip (the min-value entropy acquisition), cei1.hip (the constrained expected
 // improvement, whose members are groups of 1 + K GPs combined by its own rule in the place of the ensemble mean), ehvi1.hip
-// (the two-objective expected hypervolume improvement: groups of two GPs and a Pareto front per group) and logcei1.hip (the log of
-// the constrained expected improvement: cei1.hip's groups under a log-sum-exp, taken with groups of one GP too).
+// (the two-objective expected hypervolume improvement: groups of two GPs and a Pareto front per group), logcei1.hip (the log of
+// the constrained expected improvement: cei1.hip's groups under a log-sum-exp, taken with groups of one GP too) and ehvi3.hip (the
+// three-objective expected hypervolume improvement: groups of three GPs, a front and its box table per group).
 #pragma once
 #include <memory>
 #include <vector>
@@ -117,7 +118,7 @@ struct Kg1Call {
   std::shared_ptr<const void> client;
   void (*check_members)(const Kg1Objective& o, const std::vector<GpDev*>& gps, int pending_room) = nullptr;
 };
-// The six clients' descriptions, one function each (the caller has made the checks that need no handle; the arrays are the
+// The seven clients' descriptions, one function each (the caller has made the checks that need no handle; the arrays are the
 // caller's and outlive the call).  gp.hpp says what the arguments are.
 Kg1Call kg1_call(int num_fidelity, const double* discrete_all, const int* num_discrete, const double* best_so_far);  // kg1_opt.hip
 Kg1Call ei1_call(const double* best_so_far);                                                                       // ei1.hip
@@ -125,6 +126,7 @@ Kg1Call gibbon1_call(const double* min_values, int num_min_values);             
 Kg1Call cei1_call(int num_mcmc, int num_constraints, const double* thresholds, const double* best_so_far);         // cei1.hip
 Kg1Call ehvi1_call(int num_mcmc, const double* reference_point, const double* front, int num_front);               // ehvi1.hip
 Kg1Call logcei1_call(int num_mcmc, int num_constraints, const double* thresholds, const double* best_so_far);      // logcei1.hip
+Kg1Call ehvi3_call(int num_mcmc, const double* reference_point, const double* front, int num_front);              // ehvi3.hip
 
 // what a multistart hands back (all but the first three may be NULL) ...
 struct Kg1MultistartOut {

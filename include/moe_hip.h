@@ -631,6 +631,64 @@ int moe_ehvi_mcmc_suggest(const moe_gp_t* const* gps, const moe_gp_t* const* gps
                           const double* points_being_sampled, int num_being_sampled, const double* starts, int num_starts,
                           int do_gradient_ascent, int num_to_sample, double* best_points, double* best_values, int* found,
                           moe_error_t* err);
+/* The three-objective expected hypervolume improvement averaged over a hyper-parameter ensemble, at points [num_points][dim], with
+ * pending points.  Minimisation.  Member e is three GPs, gps[e], gps2[e] and gps3[e] for objectives 1, 2 and 3: one dim, one
+ * device, no derivative observations; their observation lists may differ.  reference_point [3] = (r1, r2, r3); front
+ * [num_front][3] = (u_i, v_i, w_i), 0 <= num_front <= 192, finite, strictly inside the reference point, mutually non-dominated
+ * (no point <= another in all three objectives; equal points count as dominated) and in the CANONICAL ORDER: w ascending, ties by
+ * u, then by v (may be NULL with num_front = 0).  psi_k, sigma_k and the gradient's floor are moe_ehvi_mcmc's.  With w_0 =
+ * -infinity and w_{F+1} = r3, the slab between w_k and w_{k+1} has the two-dimensional non-dominated region of the first k points'
+ * (u, v) projections as its cross-section:
+ *   S2_k           = sum over the strips of the staircase of points 1 .. k in (u, v) of [psi_1(right) - psi_1(left)] psi_2(height)
+ *   member value   A_e = max(0, sum_{k = 0 .. F} S2_k [psi_3(w_{k+1}) - psi_3(w_k)])
+ *   its gradient   through the six coefficients dA/dmu_k and dA/dvar_k applied to grad mu_k and grad var_k; 0 where A_e is clipped
+ *   ensemble       value[i] = (A_0 + ... + A_{E-1}) / E, grad likewise: members added in member order and divided once
+ * With num_front = 0 a member's value is (EI_1 EI_2) EI_3, the analytic expected improvements with the incumbents r1, r2 and r3,
+ * each product rounded once.  Pending points: all three GPs' variances are conditioned on them (the means are left alone), and the
+ * believed outcome (mu_{e,1}, mu_{e,2}, mu_{e,3})(P_j) joins member e's OWN front, in the order of j, when it is finite, strictly
+ * inside the reference point and no front point is <= it in all three objectives; the front points >= it in all three leave, and
+ * the canonical order is kept.
+ * member_values_out (may be NULL): [E][num_points], every A_e; value[i] is, bit for bit, their mean formed in member order on the host.
+ * A candidate's bits do not depend on how many share the call (passes of moe_ei1_pass_size(N) candidates), nor on want_grad, nor on
+ * ensemble-wide launches; the box sum's order is fixed by the member's front alone (csrc/ehvi3.hip).  No handle is modified.
+ * Errors, in this order, everything that needs no handle before a handle or the device is touched: num_mcmc outside 1 .. 341 ->
+ * MOE_ERR_BOUNDS, payload (num_mcmc, 1, 341); a NULL array (gps, gps2, gps3, reference_point, points, value, grad with want_grad,
+ * front with num_front > 0) -> MOE_ERR_RUNTIME; num_front outside 0 .. 192 -> MOE_ERR_BOUNDS, payload (num_front, 0, 192); a
+ * reference point that is not finite -> MOE_ERR_INVALID_VALUE, payload (the value, its index, 0); a front point that is not
+ * finite, not strictly inside the reference point, not behind its predecessor in the canonical order, or >= an earlier point
+ * in all three objectives -> MOE_ERR_INVALID_VALUE, payload (the point's index, 0, 0); num_points < 1 -> MOE_ERR_BOUNDS;
+ * num_being_sampled outside 0 .. 64 -> MOE_ERR_BOUNDS; points_being_sampled NULL with num_being_sampled > 0 -> MOE_ERR_RUNTIME;
+ * then, "member" counting the GPs flat as 3 e + objective - 1: a NULL handle -> MOE_ERR_RUNTIME; a GP of another dim, then of
+ * another device -> MOE_ERR_INVALID_VALUE; a GP with derivative observations -> MOE_ERR_INVALID_VALUE, payload (its
+ * num_derivatives, 0, the flat index); a handle listed twice -> MOE_ERR_INVALID_VALUE, payload (the later flat index, the earlier, 0).
+ * MOE_ERR_SINGULAR only for a pending point: payload (the flat index of the first failing GP, the pending point), reported at the
+ * next wait.  A candidate never raises. */
+int moe_ehvi3_mcmc(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* gps3, int num_mcmc,
+                   const double* reference_point, const double* front, int num_front, const double* points_being_sampled,
+                   int num_being_sampled, const double* points, int num_points, int want_grad, double* value, double* grad,
+                   double* member_values_out, moe_error_t* err);
+/* One suggestion by moe_ehvi3_mcmc's objective, the whole loop on the device, as moe_ehvi_mcmc_multistart is for moe_ehvi_mcmc: the
+ * path is, bit for bit, the one a host loop over moe_ehvi3_mcmc walks.  Tensor-product domains only.
+ * Errors, in this order: those of moe_ehvi3_mcmc that need no handle (outer, domain_bounds, starts, best_point, best_value and found
+ * among the arrays that must not be NULL; num_starts for num_points); max_num_steps < 1 with do_gradient_ascent != 0 ->
+ * MOE_ERR_BOUNDS; domain_type other than MOE_DOMAIN_TENSOR_PRODUCT -> MOE_ERR_INVALID_VALUE; then those that need the handles. */
+int moe_ehvi3_mcmc_multistart(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* gps3, int num_mcmc,
+                              const double* reference_point, const double* front, int num_front, const moe_gd_params_t* outer,
+                              const double* domain_bounds, const double* points_being_sampled, int num_being_sampled,
+                              const double* starts, int num_starts, int do_gradient_ascent, double* best_point, double* best_value,
+                              int* found, double* start_values, int* kept_index, double* end_points, double* end_values, double* path,
+                              int* steps_taken, moe_error_t* err);
+/* num_to_sample points greedily: round t is moe_ehvi3_mcmc_multistart from the same starts with pending points =
+ * points_being_sampled followed by the picks of the rounds before -- bit for bit what num_to_sample calls of that function return
+ * when each is fed its predecessors' points.  Staged once; a round appends ONE row to the extension of each of the 3 E GPs and the
+ * pick's believed outcome to every member's front, whose box table is rebuilt, inside device memory.
+ * Errors: those of moe_ehvi3_mcmc_multistart, with num_to_sample < 1 or num_being_sampled + num_to_sample - 1 > 64 ->
+ * MOE_ERR_BOUNDS behind num_being_sampled. */
+int moe_ehvi3_mcmc_suggest(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* gps3, int num_mcmc,
+                           const double* reference_point, const double* front, int num_front, const moe_gd_params_t* outer,
+                           const double* domain_bounds, const double* points_being_sampled, int num_being_sampled,
+                           const double* starts, int num_starts, int do_gradient_ascent, int num_to_sample, double* best_points,
+                           double* best_values, int* found, moe_error_t* err);
 /* compute_grad_variance_of_points -> ComputeGradVarianceOfPoints (gpp_math.cpp:1359-1373); out[num_derivs][m][m][dim] */
 int moe_gp_grad_variance(const moe_gp_t* gp, const double* pts, int num_pts, int num_derivs, double* out, moe_error_t* err);
 /* compute_grad_cholesky_variance_of_points -> ComputeGradCholeskyVarianceOfPoints (gpp_math.cpp:1454-1474) */
