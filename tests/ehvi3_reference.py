@@ -100,23 +100,47 @@ def box_sum(moments3, front, ref, T=LD, table=None):
     return total, c
 
 
-def believed_front(front, outcomes, ref, T=LD):
+def believed_front(front, outcomes, ref, T=LD, detail=None):
     """(the front after the believed outcomes [p][3] have joined in order, a log with one entry per outcome: ("outside", 0, False),
-    ("dominated", 0, False) or ("joined", the number of front points that left, whether a front point that stays ties it in w))"""
+    ("dominated", 0, False) or ("joined", the number of front points that left, whether a front point that stays ties it in w)).
+    detail: a list that takes one dict per outcome -- n: the front's size as the outcome meets it; dominators: the indices of the
+    front points <= it in all three; left: the indices of those that leave; place: where it is inserted (None unless it joins)"""
     f = [tuple(T(x) for x in row) for row in np.asarray(front, dtype=T).reshape(-1, 3)]
     log = []
     for o in outcomes:
         o = tuple(T(x) for x in o)
+        d = dict(n=len(f), dominators=[], left=[], place=None)
+        if detail is not None:
+            detail.append(d)
         if not (all(np.isfinite(x) for x in o) and all(o[k] < T(ref[k]) for k in range(3))):
             log.append(("outside", 0, False))
             continue
-        if any(all(q[k] <= o[k] for k in range(3)) for q in f):
+        d["dominators"] = [i for i, q in enumerate(f) if all(q[k] <= o[k] for k in range(3))]
+        if d["dominators"]:
             log.append(("dominated", 0, False))
             continue
+        d["left"] = [i for i, q in enumerate(f) if all(q[k] >= o[k] for k in range(3))]
         kept = [q for q in f if not all(q[k] >= o[k] for k in range(3))]
         log.append(("joined", len(f) - len(kept), any(q[2] == o[2] for q in kept)))
         f = sorted(kept + [o], key=lambda q: (q[2], q[0], q[1]))
+        d["place"] = f.index(o)
     return np.array(f, dtype=T).reshape(-1, 3), log
+
+
+def floor_bound(front, ref, y, sigma):
+    """how far the box sum can lie from the deterministic gain hypervolume_3(front u {y}) - hypervolume_3(front) when every mean is
+    y_k exactly and every deviation at most sigma: psi(t) is within sigma phi(0) < 0.4 sigma of max(t - mu, 0), so a box's factors
+    (two differences of two psi and one psi) each lie within 0.8 sigma of the clipped edge lengths; the excess of the widened
+    products over the exact ones, box by box"""
+    f = np.asarray(front, dtype=np.float64).reshape(-1, 3)
+    edge = [np.concatenate([[-np.inf], f[:, k], [ref[k]]]) for k in range(3)]
+    e, total = 0.8 * float(sigma), 0.0
+    for left, right, height, slab in box_table(f):
+        du = max(edge[0][right] - max(edge[0][left], y[0]), 0.0)
+        dv = max(edge[1][height] - y[1], 0.0)
+        dw = max(edge[2][slab + 1] - max(edge[2][slab], y[2]), 0.0)
+        total += (du + e) * (dv + e) * (dw + e) - du * dv * dw
+    return total
 
 
 def member_scale(gps, ref):
@@ -137,7 +161,8 @@ class Member(object):
             self.outcomes = list(zip(*[cr.mean_at(b, self.P) for b in self.bases]))
         else:
             self.outcomes = []
-        self.front, self.log = believed_front(front, self.outcomes, self.ref, T)
+        self.detail = []
+        self.front, self.log = believed_front(front, self.outcomes, self.ref, T, self.detail)
         self.table = box_table(self.front)
         self.scale = member_scale(gps, ref)
 
@@ -200,6 +225,9 @@ CASES = [
     Case("e3_d3_n20_130_300_p3_f60", 10, 3, 3, ((20, 130, 300), (130, 300, 20), (300, 20, 130)), 3, 60, "random", None, 8, 3.3e-13),
     # the <24> gradient kernel, three 256-row strides, tri_cols' K slices, groups of three
     Case("e2_d20_n20_300_520_p2_f30", 11, 2, 20, ((20, 300, 520), (520, 20, 300)), 2, 30, "random", None, 8, 1.0e-15),
+    # random fronts of 192 points: the u order is not the w order, slabs past 64 evict staircase points with index >= 64
+    Case("e1_d3_n20_p0_rand192", 12, 1, 3, _grid(1, 20), 0, 192, "random", 3020, 8, 2.8e-14),
+    Case("e2_d3_n20_130_300_p3_rand192", 13, 2, 3, ((20, 130, 300), (300, 20, 130)), 3, 192, "random", 3205, 8, 1.5e-13),
 ]
 FLAT = "e1_d3_n20_p0_flat12"
 ENSEMBLE = "e3_d3_n20_130_300_p3_f60"
@@ -212,7 +240,7 @@ BELIEVED = Case("e2_d3_n20_p5_believed", 21, 2, 3, _grid(2, 20), 5, None, "belie
 
 
 def case(name):
-    return next(c for c in CASES + [BELIEVED] if c.name == name)
+    return next(c for c in CASES + [BELIEVED] + LIMIT_CASES if c.name == name)
 
 
 def staircase_front(F, w_flat=None):
@@ -243,9 +271,166 @@ def random_front(rng, F, shift=0.0):
             return np.ascontiguousarray(f[keep])
 
 
+# ---- the full member: 256 points, 33 153 boxes ----
+# Member 0: three GPs on the same 8 rows whose believed outcomes along the pending line x2 = 0.5 have u strictly ascending and v
+# strictly descending in x1 (mutually non-dominated whatever w is); the caller's 192 points continue that staircase on its low-u,
+# high-v side, their w a fixed permutation of a linspace that brackets the outcomes' w: all 64 outcomes join, nobody leaves, the
+# front holds 256 points in a w order that is not the u order and every slab k keeps all its k points.  Member 1: objectives 2 and 3
+# observed higher, so that every outcome it believes is dominated by every front point: its front stays the caller's 192 and its table
+# lies directly behind member 0's full one.  The candidates lie beside the high-u end of the pending line, where mass lies to the
+# right of the staircase (the table's last box, strip 256 of slab 256, carries far more than the tolerance).
+FULL = Case("e2_d2_n8_p64_f192_full", 31, 2, 2, _grid(2, 8), 64, 192, "full", 18721, 4, 1.5e-15)
+FULL_PENDING_X1 = np.linspace(0.04, 0.96, 64)
+
+
+def full_front():
+    """192 points below every outcome of FULL's member 0 in u and above it in v: u ascending, v descending, w permuted"""
+    u = np.linspace(-0.9, -0.2, 192)
+    v = np.linspace(1.0, 0.8, 192)
+    w = np.linspace(-0.6, 0.6, 192)[np.random.default_rng(192).permutation(192)]
+    return canonical(np.stack([u, v, w], axis=1))
+
+
+def _full_problem(c):
+    rng = np.random.default_rng(9900 + c.seed)
+    x1 = np.linspace(0.0, 1.0, 8)
+    X = np.ascontiguousarray(np.stack([x1, rng.uniform(0, 1, size=8)], axis=1))
+    kinds, lengths = (MATERN, SE, MATERN), (0.6, 0.6, 0.3)
+    ys = ((0.9 * x1 - 0.1, 0.8 - 0.9 * x1, 0.4 * np.sin(7.0 * x1)),
+          (0.9 * x1 - 0.1, 1.3 - 0.2 * x1, 0.9 + 0.2 * np.sin(7.0 * x1)))
+    gps = [[GP(kinds[k], np.array([1.0, lengths[k], 3.0 if e == 0 else 0.5]), X.copy(), ys[e][k].reshape(-1, 1).copy(), [1e-2], ())
+            for k in range(3)] for e in range(2)]
+    pending = np.stack([FULL_PENDING_X1, np.full(64, 0.5)], axis=1)[rng.permutation(64)]
+    points = np.array([(0.97, 0.62), (0.98, 0.41), (0.99, 0.57), (1.0, 0.35)])
+    return Problem(c.name, gps, REF, full_front(), points, np.ascontiguousarray(pending), tuple(range(c.C)))
+
+
+def full_starts(pending):
+    """four starts of the value-only batch that reaches the full front through a pick: on the pending line, in the hole the 64th
+    pending point leaves and halfway between three pairs of neighbours, the last pair at the high-u end, where the table's last box
+    carries far more than the tolerance"""
+    x = np.sort(FULL_PENDING_X1)
+    return np.array([(float(pending[63, 0]) + 0.3 * float(x[1] - x[0]), 0.5), (0.5 * float(x[10] + x[11]), 0.5),
+                     (0.5 * float(x[50] + x[51]), 0.5), (0.5 * float(x[62] + x[63]), 0.5)])
+
+
+def last_box_share(member, x):
+    """what the table's last box adds to the member's box sum at x, in the member's arithmetic"""
+    mo = [cr.moments(m, b, x) for m, b in zip(member.models, member.bases)]
+    mom = [(q[0], q[1]) for q in mo]
+    whole = box_sum(mom, member.front, member.ref, member.T, member.table)[0]
+    return whole - box_sum(mom, member.front, member.ref, member.T, member.table[:-1])[0]
+
+
+# ---- the believed-front rule past 64 points ----
+# The six pending points are chosen from a pool by member 0's float64 outcomes and fed in the order of their roles; the caller's
+# 192 points are then placed relative to both members' outcomes, every compared coordinate at least 2e-3 from an outcome's:
+#   0 "first":  the smallest w of all, nothing >= it in (u, v): joins at place 0, nobody leaves
+#   1 "middle": nothing <= it, nothing >= it: joins in the middle, nobody leaves
+#   2 "sweep":  well ahead of the front with more than 64 points below it in w; it meets 194 points and the ones that leave lie
+#               in the index ranges 64-127, 128-191 and 192-255 (a point with the largest w of the front is placed >= it)
+#   3 "behind": the only front point <= it is placed just under it, with more than 128 points below that in w
+#   4 "last":   the largest w of all, nothing <= it in (u, v): joins at the last place
+#   5 any other outcome of the pool
+# Member 1's third objective has observed zeros only: w = 0 exactly; the front point (below every u, above every v of member 1's
+# outcomes, w = 0) is never evicted by them and ties each one that joins, with more than 64 front points of w < 0 before it.
+# F = 192, not fewer: a point that leaves sorts behind the outcome, so with the place >= 64 the ranges that lose a point are the
+# upper three, and index 192 exists only in a front of 193 or more.
+BELIEVED_WIDE = Case("e2_d3_n20_p6_f192_believed", 55, 2, 3, _grid(2, 20), 6, 192, "believed_wide", 4230, 8, 5.0e-15)
+ROLES = ("first", "middle", "sweep", "behind", "last", "other")
+
+
+def _le(a, b):
+    return a[0] <= b[0] and a[1] <= b[1] and a[2] <= b[2]
+
+
+def _believed_wide_problem(c):
+    rng = np.random.default_rng(9900 + c.seed)
+    length = LENGTH_0 + LENGTH_D * math.sqrt(c.d)
+    Xc = rng.uniform(0, 1, size=(20, c.d))
+    gps = []
+    for e in range(c.E):
+        row = []
+        for r in range(3):
+            y = 0.3 * rng.normal(size=(20, 1))
+            if r == 2 and e == 1:
+                y[:] = 0.0
+            f = 1.0 + 0.15 * ((e + 2 * r) % 4)
+            row.append(GP(MATERN if (e + r) % 2 == 0 else SE, np.array([1.3] + [length] * c.d) * f, Xc.copy(), y, [1e-2 * f], ()))
+        gps.append(row)
+    points = rng.uniform(0.1, 0.9, size=(c.C, c.d))
+    pool = rng.uniform(0, 1, size=(80, c.d))
+    bases = [[cr.base_model(g, np.float64) for g in row] for row in gps]
+    out = [np.array([[float(x) for x in cr.mean_at(b, pool)] for b in row]).T for row in bases]  # [e][pool][3]
+    o, t = out[0], out[0].sum(axis=1)
+    first, last = int(np.argmin(o[:, 2])), int(np.argmax(o[:, 2]))
+    wlo, whi = o[first, 2], o[last, 2]
+    ok = lambda lo, hi: [i for i in range(len(o)) if lo <= o[i, 2] <= hi and abs(o[i, 2]) >= 0.03]  # noqa: E731
+    sweep = min(ok(wlo + 0.08, -0.05), key=lambda i: t[i])
+    behind = max(ok(0.1, whi - 0.08), key=lambda i: t[i])
+    s = t[sweep] + 0.35
+    middle = min(ok(o[sweep, 2] + 0.05, o[behind, 2] - 0.05), key=lambda i: abs(t[i] - s))
+    taken = (first, last, sweep, behind, middle)
+    other = next(i for i in ok(wlo + 0.05, whi - 0.05) if all(abs(o[i, 2] - o[j, 2]) >= 0.03 for j in taken))
+    chosen = [first, middle, sweep, behind, last, other]
+    pending = np.ascontiguousarray(pool[chosen])
+    m0, m1 = out[0][chosen], out[1][chosen]
+    both = np.vstack([m0, m1])
+    F, M, S, B, L = m0[0], m0[1], m0[2], m0[3], m0[4]
+    tie = int(np.argmin(m1[:, 0] + m1[:, 1]))  # the outcome of member 1 that certainly joins
+    special = [(B[0] - 0.05, B[1] - 0.05, B[2] - 0.01), (S[0] + 0.03, S[1] + 0.04, L[2] - 0.005),
+               (float(np.min(m1[:, 0])) - 0.1, float(np.max(m1[:, 1])) + 0.1, 0.0)]
+    bands = ((wlo + 0.01, S[2] - 0.01, 72), (S[2] + 0.01, B[2] - 0.03, 96), (B[2] + 0.01, L[2] - 0.01, 21))
+    front = list(special)
+    for lo, hi, quota in bands:
+        got = 0
+        for _ in range(40000):
+            if got == quota:
+                break
+            w = rng.uniform(lo, hi)
+            u = rng.uniform(-0.8, 0.9)
+            q = (u, s - u - w + rng.uniform(-0.1, 0.1), w)
+            if not -0.9 < q[1] < 1.3:
+                continue
+            if np.min(np.abs(both - np.array(q))) < 2e-3:
+                continue
+            if any(_le(a, q) or _le(q, a) for a in front):
+                continue
+            if (q[0] >= F[0] and q[1] >= F[1]) or (q[0] <= L[0] and q[1] <= L[1]) or _le(q, M) or _le(M, q) or _le(q, B):
+                continue
+            if q[0] <= m1[tie, 0] and q[1] <= m1[tie, 1] and q[2] <= 0.0:
+                continue
+            front.append(q)
+            got += 1
+        assert got == quota, (c.name, lo, hi, got)
+    return Problem(c.name, gps, REF, canonical(np.array(front, dtype=np.float64)), points, pending, tuple(range(c.C)))
+
+
+# ---- E = 341: 1023 GPs, the hyper-parameters moving with the member so that no two members' values agree ----
+MANY = Case("e341_d2_n4_p1_f2", 41, 341, 2, _grid(341, 4), 1, 2, "many", 6, 3, 3.2e-14)
+
+
+def _many_problem(c):
+    rng = np.random.default_rng(9900 + c.seed)
+    X = rng.uniform(0, 1, size=(4, c.d))
+    ys = [0.3 * rng.normal(size=(4, 1)) for _ in range(3)]
+    gps = [[GP(MATERN if (e + k) % 2 == 0 else SE, np.array([1.0 + 0.1 * k + 0.003 * e, 0.35 + 0.001 * e, 0.6 - 0.0007 * e]), X.copy(),
+               ys[k].copy(), [1e-2], ()) for k in range(3)] for e in range(c.E)]
+    front = canonical(np.array([(-0.3, 0.4, -0.2), (0.3, -0.3, 0.1)]))
+    points = rng.uniform(0.1, 0.9, size=(c.C, c.d))
+    pending = rng.uniform(0.1, 0.9, size=(c.p, c.d))
+    return Problem(c.name, gps, REF, front, points, pending, tuple(range(c.C)))
+
+
+_BUILDERS = {"full": _full_problem, "believed_wide": _believed_wide_problem, "many": _many_problem}
+LIMIT_CASES = [FULL, BELIEVED_WIDE, MANY]
+
+
 def make_problem(c):
     """the inputs of a case.  The GPs of a case observe nested point lists; the first pending point lies within 0.05 of candidate 0
     in every coordinate (conditioning on P moves that candidate by far more than the tolerance)."""
+    if c.kind in _BUILDERS:
+        return _BUILDERS[c.kind](c)
     rng = np.random.default_rng(9900 + c.seed)
     length = LENGTH_0 + LENGTH_D * math.sqrt(c.d)
     Xc = rng.uniform(0, 1, size=(max(max(row) for row in c.n), c.d))

@@ -3,7 +3,10 @@ tests/test_gpu_ehvi3.py checks the device against, is itself checked here -- the
 of hypervolume_3 over seeded normal draws), the empty front against the product of three analytic expected improvements, a front
 flat in the third objective against the two-objective strip sum of tests/ehvi_reference.py, float64 against long double, the
 gradient against central differences of the long-double value, hypervolume_3 against inclusion-exclusion, every branch of the
-believed-front rule, the table's box counts -- and the C ABI's refusals in the header's order, which need no device."""
+believed-front rule, the table's box counts -- and the C ABI's refusals in the header's order, which need no device.  Sections 7 to
+10 qualify the cases that reach the limits (the full member of 256 points and 33 153 boxes, random fronts of 192 points, the
+believed-front rule past 64 points, 341 members): each reaches the branch it is there for, in float64 and in long double alike, with
+1e-3 between the coordinates that decide it."""
 import ctypes as C
 import itertools
 import math
@@ -20,7 +23,9 @@ from cornell_moe_amd import _lib, build as moe_build, expected_hypervolume_impro
 LD = h3.LD
 dp, ip = _lib.dp, _lib.ip
 
-CASES = h3.CASES + [h3.BELIEVED]
+CASES = h3.CASES + [h3.BELIEVED] + h3.LIMIT_CASES
+# (the gradient's formula does not know E: the 341 members are left to float64 against long double)
+FD_CASES = [c for c in CASES if c.E <= 3]
 
 
 def _ids(cases):
@@ -125,7 +130,7 @@ def test_float64_agrees_with_long_double(case):
     assert len(big) >= 3, (case.name, [float(w.value) for w in want])
 
 
-@pytest.mark.parametrize("case", CASES, ids=_ids(CASES))
+@pytest.mark.parametrize("case", FD_CASES, ids=_ids(FD_CASES))
 def test_gradient_agrees_with_central_differences(case):
     p, want = h3.expected(case, LD)
     members = h3.ensemble(p, LD)
@@ -243,7 +248,179 @@ def test_the_tables_box_counts():
     assert len(h3.box_table(h3.staircase_front(256))) == 33153
 
 
-# ---- 7. the C ABI without a device ----
+# ---- 7. the full member ----
+def _gap(a, b):
+    """the smallest distance between a number of a and one of b"""
+    a, b = np.asarray(a, dtype=np.float64).ravel(), np.asarray(b, dtype=np.float64).ravel()
+    return float(np.min(np.abs(a[:, None] - b[None, :])))
+
+
+def _own_gap(a):
+    return float(np.min(np.diff(np.sort(np.asarray(a, dtype=np.float64).ravel()))))
+
+
+def _full_member_0(m, front):
+    """what decides member 0's log -- every outcome above every front point in u and below it in v, the outcomes' own u and v
+    apart -- holds with 1e-3 to spare; w decides the order alone"""
+    o = np.array([[float(x) for x in row] for row in m.outcomes])
+    assert float(np.min(o[:, 0])) - float(np.max(front[:, 0])) >= 1e-3 and float(np.min(front[:, 1])) - float(np.max(o[:, 1])) >= 1e-3
+    assert _own_gap(o[:, 0]) >= 1e-3 and _own_gap(o[:, 1]) >= 1e-3
+    assert float(np.max(o)) <= min(h3.REF) - 1e-3
+    return o
+
+
+def test_the_full_member_holds_256_points_and_33153_boxes():
+    c = h3.FULL
+    p = h3.make_problem(c)
+    assert len(p.front) == 192 and np.array_equal(h3.canonical(p.front), p.front) and len(h3.box_table(p.front)) == c.B == 193 * 194 // 2
+    assert np.array_equal(ehvi.pareto_front_3(p.front, p.ref), p.front)
+    assert not np.array_equal(np.sort(p.pending[:, 0]), p.pending[:, 0]) and np.all(p.pending[:, 1] == 0.5)  # on one line, shuffled
+    tables = []
+    for T in (np.float64, LD):
+        m0, m1 = h3.ensemble(p, T)
+        assert m0.log == [("joined", 0, False)] * 64 and len(m0.front) == 256 and len(m0.table) == 33153
+        o = _full_member_0(m0, p.front)
+        # w orders the points and decides nothing else; the device's means agree with these to 1e-10 scale, far inside the gaps
+        w_gap = min(_own_gap(o[:, 2]), _gap(o[:, 2], p.front[:, 2]))
+        assert w_gap >= 1e-6
+        slabs = np.bincount(m0.table[:, 3], minlength=257)
+        assert np.array_equal(slabs, np.arange(257) + 1)  # slab k holds k + 1 strips
+        inside = 0
+        for k in range(1, 257):
+            place = h3.staircase(m0.front, k).index(k - 1)
+            inside += 1 if 0 < place < k - 1 else 0
+        assert inside >= 32
+        assert tuple(m0.table[-1]) == (int(m0.table[-2][1]), 257, int(m0.table[-2][1]), 256)  # strip 256 of slab 256
+        # member 1: every outcome lies above EVERY front point in all three objectives by 1e-3 or more: dominated, its front the caller's
+        o1 = np.array([[float(x) for x in row] for row in m1.outcomes])
+        assert m1.log == [("dominated", 0, False)] * 64 and len(m1.front) == 192 and len(m1.table) == c.B
+        assert float(np.min(np.min(o1, axis=0) - np.max(p.front, axis=0))) >= 1e-3 and float(np.max(o1)) <= min(h3.REF) - 1e-3
+        print("full member, %s: outcomes' smallest gaps %.2e in u, %.2e in v, %.2e in w (order only); %d of 256 slabs insert their "
+              "point inside the staircase" % (T.__name__, _own_gap(o[:, 0]), _own_gap(o[:, 1]), w_gap, inside))
+        tables.append(m0.table)
+    assert np.array_equal(tables[0], tables[1])  # the same order in both arithmetics
+    # sensitivity: the table's last box, and its last sweep of 129, each carry at least 100 times the device test's bound
+    p, want = h3.expected(c, LD)
+    m0 = h3.ensemble(p, LD)[0]
+    bound = max(1e-10, 4.0 * c.ld_diff)
+    factors = []
+    for x in p.points:
+        mo = [h3.cr.moments(mm, b, x) for mm, b in zip(m0.models, m0.bases)]
+        mom = [(q[0], q[1]) for q in mo]
+        whole = h3.box_sum(mom, m0.front, m0.ref, LD, m0.table)[0]
+        for cut in (33152, 33024):
+            part = h3.box_sum(mom, m0.front, m0.ref, LD, m0.table[:cut])[0]
+            factors.append(abs(float(whole - part)) / (bound * m0.scale))
+    print("full member: dropping the last box / the last sweep moves member 0's value by %s times the bound" % (
+        ["%.3g" % f for f in factors]))
+    assert min(factors) >= 100.0
+
+
+def test_the_full_front_is_reached_through_a_pick_too():
+    """the first 63 pending points fed, the value-only batch's first pick on the pending line: whichever start is picked, its outcome
+    joins member 0's front as the 256th point, with u and v 1e-3 or more from every other outcome's"""
+    p = h3.make_problem(h3.FULL)
+    starts = h3.full_starts(p.pending)
+    assert np.all(starts[:, 1] == 0.5) and _gap(starts[:, 0], p.pending[:63, 0]) >= 4e-3
+    for T in (np.float64, LD):
+        for s in starts:
+            m0, m1 = h3.ensemble(p, T, pending=np.vstack([p.pending[:63], s[None, :]]))
+            assert m0.log == [("joined", 0, False)] * 64 and len(m0.front) == 256 and len(m0.table) == 33153
+            _full_member_0(m0, p.front)
+            assert m1.log == [("dominated", 0, False)] * 64 and len(m1.front) == 192
+            o1 = np.array([float(x) for x in m1.outcomes[63]])
+            assert float(np.min(o1 - np.max(p.front, axis=0))) >= 1e-3 and float(np.max(o1)) <= min(h3.REF) - 1e-3
+
+
+# ---- 8. random fronts of 192 points ----
+RANDOM_192 = [c for c in h3.CASES if c.F == 192]
+
+
+@pytest.mark.parametrize("case", RANDOM_192, ids=_ids(RANDOM_192))
+def test_a_random_front_of_192_evicts_staircase_points_past_one_wavefront(case):
+    p = h3.make_problem(case)
+    f = p.front
+    assert len(RANDOM_192) == 2 and len(f) == 192 and len(h3.box_table(f)) == case.B
+    evicting, several, high, identity = 0, 0, 0, 0
+    before = h3.staircase(f, 64)
+    for k in range(65, 193):
+        after = h3.staircase(f, k)
+        gone = [i for i in before if i not in after]
+        evicting += 1 if gone else 0
+        several += 1 if len(gone) >= 2 else 0
+        high += sum(1 for i in gone if i >= 64)
+        identity += 1 if after == sorted(after) else 0
+        before = after
+    print("%s: %d boxes; of the slabs past 64, %d evict a staircase point, %d evict two or more, %d evictions of a survivor with index "
+          ">= 64; %d of them in ascending index order" % (case.name, case.B, evicting, several, high, identity))
+    assert evicting >= 10 and several >= 1 and high >= 1
+    assert 128 - identity >= 100  # (the u order is not the w order: the ordering step rearranges in nearly every slab past 64)
+
+
+# ---- 9. the believed-front rule past 64 points ----
+def test_the_believed_front_rule_binds_past_64_points():
+    c = h3.BELIEVED_WIDE
+    p = h3.make_problem(c)
+    assert len(p.front) == 192 and np.array_equal(ehvi.pareto_front_3(p.front, p.ref), p.front) and len(h3.box_table(p.front)) == c.B
+    assert int(np.sum(p.front[:, 2] < 0.0)) >= 64 and int(np.sum(p.front[:, 2] == 0.0)) == 1
+    seen = []
+    for T in (np.float64, LD):
+        m0, m1 = h3.ensemble(p, T)
+        d0, d1 = m0.detail, m1.detail
+        role = dict(zip(h3.ROLES, range(6)))
+        ranges = lambda d: sorted(set(i // 64 for i in d["left"]))  # noqa: E731
+        print("believed-front case past 64 points, %s: member 0 %s, places %s, the ranges that lose points %s; member 1 %s, places %s" % (
+            T.__name__, m0.log, [d["place"] for d in d0], [ranges(d) for d in d0], m1.log, [d["place"] for d in d1]))
+        # a join at place 0 with the smallest w of all
+        j = role["first"]
+        assert m0.log[j][0] == "joined" and d0[j]["place"] == 0 and float(m0.outcomes[j][2]) < float(np.min(p.front[:, 2])) - 1e-3
+        # a join that evicts nobody, in the middle
+        j = role["middle"]
+        assert m0.log[j] == ("joined", 0, False) and 64 <= d0[j]["place"] < d0[j]["n"] - 64
+        # a join at a place >= 64 whose evictions lie in three of the four index ranges (the lower one cannot lose a point then)
+        j = role["sweep"]
+        assert m0.log[j][0] == "joined" and d0[j]["place"] >= 64 and d0[j]["n"] >= 193 and ranges(d0[j]) == [1, 2, 3]
+        # an outcome dominated only by front points with index >= 128
+        j = role["behind"]
+        assert m0.log[j][0] == "dominated" and min(d0[j]["dominators"]) >= 128
+        # a join at the last place with the largest w
+        j = role["last"]
+        assert m0.log[j][0] == "joined" and d0[j]["place"] == d0[j]["n"] - m0.log[j][1] == len(m0.front) - 1
+        assert float(m0.outcomes[j][2]) > float(np.max(p.front[:, 2])) + 1e-3
+        # member 1: w = 0 exactly; an outcome joins beside the kept front point at w = 0, which has index >= 64
+        assert all(float(o[2]) == 0.0 for o in m1.outcomes)
+        ties = [(log, d) for log, d in zip(m1.log, d1) if log[0] == "joined" and log[2]]
+        assert ties and all(d["place"] >= 64 for _, d in ties)
+        zero = int(np.flatnonzero(np.asarray(m1.front[:, 2], dtype=np.float64) == 0.0)[0])
+        assert zero >= 64 and np.array_equal(np.asarray(m1.front[zero], dtype=np.float64), p.front[p.front[:, 2] == 0.0][0])
+        # margins: 1e-3 between an outcome and every caller's point, the reference point and every other outcome of its member, in
+        # each objective; the exact ties in w made on purpose excepted
+        for m in (m0, m1):
+            o = np.array([[float(x) for x in row] for row in m.outcomes])
+            for k in range(3):
+                exact = k == 2 and m is m1
+                assert exact or (_gap(o[:, k], p.front[:, k]) >= 1e-3 and _own_gap(o[:, k]) >= 1e-3), (k, _gap(o[:, k], p.front[:, k]))
+                assert p.ref[k] - float(np.max(o[:, k])) >= 1e-3
+            if m is m1:
+                others = p.front[p.front[:, 2] != 0.0]
+                assert np.all(o[:, 2] == 0.0) and float(np.min(np.abs(others[:, 2]))) >= 1e-3
+        seen.append((m0.log, m1.log, [d["place"] for d in d0 + d1], [d["left"] for d in d0 + d1]))
+    assert seen[0] == seen[1]  # float64 and long double take the same branches
+
+
+# ---- 10. 341 members ----
+def test_no_two_of_the_341_members_agree():
+    p, want = h3.expected(h3.MANY, LD)
+    assert len(p.gps) == 341 and sum(len(row) for row in p.gps) == 1023 and len(p.front) == 2 and len(p.pending) == 1
+    for w in want:
+        vals = [float(a) for a in w.members]
+        assert len(set(vals)) == 341 and _own_gap(vals) >= 1e-8 * w.scale and min(vals) > 1e-3
+    logs = [[m.log for m in h3.ensemble(p, T)] for T in (np.float64, LD)]
+    print("341 members: the believed outcome is %s" % sorted(set(log[0][0] for log in logs[1])))
+    assert logs[0] == logs[1]  # every member takes the same branch in both arithmetics
+
+
+# ---- 11. the C ABI without a device ----
 @pytest.fixture(scope="module")
 def lib():
     moe_build.build()

@@ -11,8 +11,9 @@ of the restatement, and the margin of 4 covers another summation order over up t
 value-only against value + gradient, a candidate alone against itself in a batch and across the pass boundary, the value against
 the mean of the members' values formed on the host, an empty pending array against NULL, ensemble-wide launches on against off, the
 ascent against a host-driven loop over the evaluator (tests/ms_restatement.py), the greedy batch against calls of the ascent fed
-their predecessors' points.  Every test prints the worst figures it saw (pytest -s); DESIGN.md section 5.19 records those of the
-first run."""
+their predecessors' points.  On sampled points of noise-free GPs, where the variance floors decide, the value is held to 0 and to
+the deterministic hypervolume gain.  Every test prints the worst figures it saw (pytest -s); DESIGN.md
+section 5.19 records those of the first run."""
 import ctypes as C
 
 import numpy as np
@@ -290,6 +291,46 @@ def test_means_far_beyond_the_reference_point_give_exactly_zero():
     for ref in ((low, low), (low, p.ref[1]), (p.ref[0], low)):
         v, g = api.ehvi_ensemble(D.one, D.two, ref, None, p.points, points_being_sampled=p.pending)
         assert np.all(v == 0.0) and np.all(np.isfinite(g))
+    D.close()
+
+
+def test_sampled_points_of_noise_free_gps_meet_the_variance_floors():
+    """tests/test_gpu_ei1.py's construction for the strip kernel's floors: two noise-free GPs on shared rows; candidate 0 on an
+    observation a front point dominates by 0.15 in both objectives, candidate 1 on one no front point dominates, candidate 2
+    anywhere.  At candidate 1 the limit as the variances go to 0 is the deterministic gain of hypervolume; a device variance there
+    is rounding noise, so the bound is formed from the float64 restatement's variances at that point: |psi - max(t - mu, 0)| <=
+    sigma phi(0) < 0.4 sigma, so a strip's width (a difference of two psi) lies within 0.8 sigma of its clipped length and its
+    height within 0.4 sigma; the excess of the widened products over the exact ones, strip by strip, with ten times the largest
+    such sigma."""
+    rng = np.random.default_rng(17)
+    d, n = 2, 6
+    X, Y = rng.uniform(0, 1, size=(n, d)), 0.3 * rng.normal(size=(n, 2))
+    i0, i1 = int(np.argmax(Y[:, 0])), int(np.argmin(Y[:, 0]))
+    front = ehvi.pareto_front(np.array([Y[i0] - 0.15, Y[i1] + (0.1, -0.2)]), hr.REF)
+    assert len(front) == 2 and Y[i0, 0] - Y[i1, 0] >= 0.3 and not any(np.all(q <= Y[i1]) for q in front)
+    gps = [hr.GP(kind, np.array([1.3, 0.3, 0.3]), X, Y[:, k:k + 1].copy(), [0.0], ()) for k, kind in enumerate((kr.MATERN, kr.SE))]
+    pts = np.vstack([X[i0], X[i1], rng.uniform(0.1, 0.9, size=d)])
+    p = hr.Problem("floors", [gps], hr.REF, front, pts, np.zeros((0, d)), (0, 1, 2))
+    scale = hr.member_scale(gps, hr.REF)
+    m = hr.Member(gps, p.ref, front, p.pending, np.float64)
+    sigma = max(np.sqrt(abs(float(hr.cr.moments(mm, b, X[i1])[1]))) for mm, b in zip(m.models, m.bases))
+    gain = ehvi.hypervolume(np.vstack([front, Y[i1:i1 + 1]]), p.ref) - ehvi.hypervolume(front, p.ref)
+    e, bound = 0.8 * 10.0 * sigma, 0.0
+    lefts = np.concatenate([[-np.inf], front[:, 0]])
+    rights = np.concatenate([front[:, 0], [p.ref[0]]])
+    heights = np.concatenate([[p.ref[1]], front[:, 1]])
+    for left, right, height in zip(lefts, rights, heights):
+        du, dv = max(right - max(left, Y[i1, 0]), 0.0), max(height - Y[i1, 1], 0.0)
+        bound += (du + e) * (dv + e) - du * dv
+    D = _Device(p)
+    v, g = _eval(D, p, pts)
+    print("on sampled points of noise-free GPs: dominated %.3g, gradient %s; undominated %.12g against the deterministic gain %.12g "
+          "(difference %.3g, bound %.3g from the restatement's sigma %.3g; 1e-6 scale is %.3g); beside them %.3g" % (
+              v[0], g[0], v[1], gain, abs(v[1] - gain), bound, sigma, 1e-6 * scale, v[2]))
+    assert np.all(np.isfinite(v)) and np.all(np.isfinite(g)) and np.all(v >= 0.0)
+    assert 0.0 <= v[0] <= 1e-10 * scale and v[2] > 1e-6
+    assert gain > 1e-3 and bound <= 1e-6 * scale  # (the bound binds: the assertion on candidate 1 is kept)
+    assert abs(v[1] - gain) <= bound
     D.close()
 
 

@@ -1,15 +1,19 @@
 """The three-objective expected hypervolume improvement on the device (csrc/ehvi3.hip: moe_ehvi3_mcmc, moe_ehvi3_mcmc_multistart,
-moe_ehvi3_mcmc_suggest) against the long-double restatement of tests/ehvi3_reference.py, on the cases ehvi3_reference.CASES and
-BELIEVED, which tests/test_ehvi3_reference.py checks on the CPU (box counts, the branches of the believed-front rule, values and
-gradients far above the bound here, the front and the pending points each moving the value).
+moe_ehvi3_mcmc_suggest) against the long-double restatement of tests/ehvi3_reference.py, on the cases ehvi3_reference.CASES,
+BELIEVED, BELIEVED_WIDE, FULL and MANY, which tests/test_ehvi3_reference.py checks on the CPU (box counts, the branches of the
+believed-front rule, values and gradients far above the bound here, the front and the pending points each moving the value, each
+limit case reaching the branch it is there for).
 
 Tolerances: |value - want| and |A_e - want| <= max(1e-10, 4 ld_diff) scale, the gradient likewise as tests/test_gpu_ehvi.py applies
 it.  Everything else is bit for bit: value-only against value + gradient, a candidate alone against itself in a batch and across
 the pass boundary, the value against the mean of the members' values formed on the host, an empty pending array against NULL,
 ensemble-wide launches on against off, the empty front against the product of three analytic expected improvements, the ascent
-against a host-driven loop over the evaluator, the greedy batch against calls of the ascent fed their predecessors' points.  Every
+against a host-driven loop over the evaluator (at d = 3 and at the padded dimension 24), the greedy batch against calls of the ascent
+fed their predecessors' points.  The limits run: a member of 256 points and 33 153 boxes, reached through the pending points and
+through a greedy pick; 341 members; sampled points of noise-free GPs, where the variance floors decide.  Every
 test prints the worst figures it saw (pytest -s); DESIGN.md section 5.23 records those of the first run."""
 import ctypes as C
+import time
 
 import numpy as np
 import pytest
@@ -26,7 +30,8 @@ LD = h3.LD
 dp, ip = _lib.dp, _lib.ip
 _Launches, _host_loop, _same_run = tc._Launches, tc._host_loop, tc._same_run
 
-CASES = h3.CASES + [h3.BELIEVED]
+# (BELIEVED_WIDE: the front kernel past lane stride 0; FULL: a member of 256 points and 33 153 boxes with member 1's table behind it)
+CASES = h3.CASES + [h3.BELIEVED, h3.BELIEVED_WIDE, h3.FULL]
 
 
 class _Device(object):
@@ -247,6 +252,60 @@ def test_the_batch_is_the_ascent_fed_its_predecessors_bit_for_bit():
     D.close()
 
 
+# ---- 6b. the ascent and the batch at padded dimension 24 ----
+# (tests/test_gpu_ehvi.py's settings: the host-driven loop over six GPs of up to 522 rows in 20 dimensions stays within seconds)
+MS_WIDE = dict(MS, starts=6, steps=4, restarts=1)
+
+
+def _wide_ascent_inputs(d):
+    rng = np.random.default_rng(77)
+    starts = rng.uniform(0.02, 0.98, size=(MS_WIDE["starts"], d))
+    gd = (MS_WIDE["starts"], MS_WIDE["steps"], MS_WIDE["restarts"], 0, MS_WIDE["gamma"], MS_WIDE["pre_mult"], MS_WIDE["max_rel"], 1e-10)
+    return starts, gd, np.array([[0.0, 1.0]] * d)
+
+
+def test_the_ascent_on_the_wide_ensemble_is_the_host_driven_loop_bit_for_bit():
+    """the ascent's own staging and step at padded dimension 24 over members of 20, 300 and 520 rows, groups of three"""
+    p = h3.make_problem(h3.case(h3.WIDE))
+    D = _Device(p)
+    starts, gd, bounds = _wide_ascent_inputs(p.points.shape[1])
+    pending = p.pending[:2]
+    want = _host_loop(lambda x, g: _eval(D, p, x, pending=pending, want_grad=g), starts, gd, bounds)
+    plain = _multistart(D, p, p.front, gd, bounds, starts)
+    assert not np.array_equal(plain["start_values"], want["start_values"])  # (the pending points are not ignored)
+    bare = _multistart(D, p, None, gd, bounds, starts, points_being_sampled=pending)
+    assert not np.array_equal(bare["start_values"], want["start_values"])  # (nor is the front)
+    for on in (True, False):
+        with _Launches(on):
+            got = _multistart(D, p, p.front, gd, bounds, starts, want_path=True, points_being_sampled=pending)
+        diff = np.argwhere(np.any(got["path"] != want["path"], axis=2))
+        assert diff.size == 0, (on, "the paths part at (start, row)", diff[np.argmin(diff[:, 1])])
+        _same_run(got, want)
+    moved = float(np.max(np.abs(want["end_points"] - starts[want["kept_index"]])))
+    print("wide ensemble: %d kept starts, steps taken %s, value %.12g against the best start's %.12g; the ends lie up to %.3g from "
+          "their starts" % (len(want["kept_index"]), [int(k) for k in want["steps_taken"]], want["value"], want["start_values"].max(), moved))
+    assert want["found"] and len(want["kept_index"]) == MS_WIDE["starts"] and moved > 1e-3 and int(want["steps_taken"].max()) == 4
+    D.close()
+
+
+def test_the_batch_on_the_wide_ensemble_is_the_ascent_fed_its_predecessor_bit_for_bit():
+    p = h3.make_problem(h3.case(h3.WIDE))
+    D = _Device(p)
+    starts, gd, bounds = _wide_ascent_inputs(p.points.shape[1])
+    pending = p.pending[:1]
+    first = _multistart(D, p, p.front, gd, bounds, starts, points_being_sampled=pending)
+    second = _multistart(D, p, p.front, gd, bounds, starts, points_being_sampled=np.vstack([pending, first["point"][None, :]]))
+    assert first["found"] and second["found"]
+    for on in (True, False):
+        with _Launches(on):
+            got = _suggest(D, p, p.front, gd, bounds, starts, 2, points_being_sampled=pending)
+        assert np.array_equal(got["points"], np.array([first["point"], second["point"]])), on
+        assert np.array_equal(got["values"], np.array([first["value"], second["value"]])) and np.all(got["found"])
+    print("wide ensemble: greedy values %.12g, %.12g; the second pick lies %.3g from the first" % (
+        first["value"], second["value"], float(np.max(np.abs(second["point"] - first["point"])))))
+    D.close()
+
+
 # ---- 7. behaviour ----
 def test_means_far_beyond_the_reference_point_give_exactly_zero():
     p = h3.make_problem(h3.case(h3.ENSEMBLE))
@@ -310,6 +369,108 @@ def test_a_front_of_192_with_64_pending_points_and_the_refusals():
         api.ehvi3_ensemble(D.objs[0], D.objs[1], [deriv], p.ref, p.front, p.points)
     assert "derivative" in str(e.value)
     deriv.close()
+    D.close()
+
+
+def test_the_full_front_is_reached_through_a_greedy_pick():
+    """63 of the full case's pending points fed, a value-only batch of 2 from starts on the pending line: the first pick's outcome
+    joins as member 0's 256th point inside device memory (tests/test_ehvi3_reference.py asserts it for whichever start is picked),
+    and the second round runs on 33 153 boxes"""
+    c = h3.FULL
+    p = h3.make_problem(c)
+    D = _Device(p)
+    starts, fed = h3.full_starts(p.pending), p.pending[:63]
+    gd = (len(starts), 3, 1, 0, 0.7, 1.0, 0.5, 1e-10)
+    got = _suggest(D, p, p.front, gd, [[0, 1]] * 2, starts, 2, gradient_ascent=False, points_being_sampled=fed)
+    assert got["points"].shape == (2, 2) and np.all(got["found"])
+    picks = [int(np.flatnonzero(np.all(starts == x, axis=1))[0]) for x in got["points"]]  # (a noisy GP may pick a start twice)
+    bound = max(1e-10, 4.0 * c.ld_diff)
+    worst, sizes = [], []
+    for t in range(2):
+        members = h3.ensemble(p, LD, pending=np.vstack([fed, got["points"][:t]]))
+        want = h3.evaluate(members, got["points"][t])
+        worst.append(abs(got["values"][t] - float(want.value)) / want.scale)
+        sizes.append((len(members[0].front), len(members[0].table)))
+    assert sizes == [(255, 32896), (256, 33153)]
+    # (the second round's value would miss the bound by far without the table's last box, strip 256 of slab 256)
+    share = float(h3.last_box_share(members[0], got["points"][1])) / len(members) / (bound * want.scale)
+    assert share >= 100.0
+    # the second round is the evaluator's with all 64 fed, bit for bit, and that within the bound at every start
+    all64 = np.vstack([fed, got["points"][:1]])
+    v, g, m = _eval(D, p, starts, pending=all64, want_member_values=True)
+    assert float(np.max(v)) == got["values"][1] and int(np.argmax(v)) == picks[1]
+    e_v, e_g, e_m = _errors(v, g, m, [h3.evaluate(members, x) for x in starts])
+    print("the full front through a pick (starts %s picked): the rounds' value errors %.3g and %.3g scale on %s (points, boxes), the last "
+          "box %.3g times the bound; all 64 fed: value error %.3g scale, gradient error %.3g, members' error %.3g scale (bound %.3g)" % (
+              picks, worst[0], worst[1], sizes, share, e_v, e_g, e_m, bound))
+    assert max(worst) <= bound and e_v <= bound and e_g <= bound and e_m <= bound
+    D.close()
+
+
+def test_341_members():
+    """E at its limit: 1023 handles, pointer tables of 1023 entries, a box-kernel grid of (C, 341)"""
+    t0 = time.perf_counter()
+    c = h3.MANY
+    p, want = h3.expected(c, LD)
+    t1 = time.perf_counter()
+    D = _Device(p)
+    t2 = time.perf_counter()
+    assert len(D.objs[0]) == 341 and sum(len(row) for row in D.all) == 1023
+    runs = []
+    for on in (True, False):
+        with _Launches(on):
+            runs.append(_eval(D, p, p.points, want_member_values=True))
+    value, grad, members = runs[0]
+    for a, b in zip(runs[0], runs[1]):
+        assert np.array_equal(a, b)  # ensemble-wide launches on against off
+    assert members.shape == (341, c.C) and np.all(np.isfinite(grad))
+    bound = max(1e-10, 4.0 * c.ld_diff)
+    e_v, e_g, e_m = _errors(value, grad, members, want)
+    assert e_v <= bound and e_g <= bound and e_m <= bound, (e_v, e_g, e_m)
+    assert np.array_equal(value, _host_mean(members))
+    assert all(len(set(members[:, i])) == 341 for i in range(c.C))  # (no two members' values agree)
+    starts = np.random.default_rng(341).uniform(0.1, 0.9, size=(3, c.d))
+    res = _multistart(D, p, p.front, (3, 2, 1, 0, 0.7, 1.0, 0.5, 1e-10), [[0, 1]] * c.d, starts, points_being_sampled=p.pending)
+    assert res["found"] and np.isfinite(res["value"]) and res["value"] > 0.0 and np.all(np.isfinite(res["point"]))
+    t3 = time.perf_counter()
+    D.close()
+    t4 = time.perf_counter()
+    print("E = 341: value error %.3g scale, gradient error %.3g, members' error %.3g scale (bound %.3g); an ascent of 3 starts and 2 steps "
+          "ends at %.6g; wall time %.2f s: the long-double restatement %.2f (0 when another test built it), 1023 handles built in %.2f, "
+          "the device calls %.2f, the handles closed in %.2f" % (e_v, e_g, e_m, bound, res["value"], t4 - t0, t1 - t0, t2 - t1, t3 - t2,
+                                                                 t4 - t3))
+
+
+def test_sampled_points_of_noise_free_gps_meet_the_variance_floors():
+    """tests/test_gpu_ei1.py's construction for the box kernel's floors: three noise-free GPs on shared rows; candidate 0 on an
+    observation a front point dominates by 0.15 in every objective, candidate 1 on one no front point dominates, candidate 2
+    anywhere.  At candidate 1 the limit as the variances go to 0 is the deterministic gain of hypervolume_3; a device variance there
+    is rounding noise, so the bound is formed from the float64 restatement's variances at that point: |psi - max(t - mu, 0)| <=
+    0.4 sigma, carried through the box sum by h3.floor_bound with ten times the largest such sigma."""
+    rng = np.random.default_rng(17)
+    d, n = 2, 6
+    X, Y = rng.uniform(0, 1, size=(n, d)), 0.3 * rng.normal(size=(n, 3))
+    i0, i1 = int(np.argmax(Y[:, 0])), int(np.argmin(Y[:, 0]))
+    front = ehvi.pareto_front_3(np.array([Y[i0] - 0.15, Y[i1] + (0.1, -0.2, 0.1)]), h3.REF)
+    assert len(front) == 2 and Y[i0, 0] - Y[i1, 0] >= 0.3 and not any(np.all(q <= Y[i1]) for q in front)
+    kinds = (kr.MATERN, kr.SE, kr.MATERN)
+    gps = [h3.GP(kinds[k], np.array([1.3, 0.3, 0.3]), X, Y[:, k:k + 1].copy(), [0.0], ()) for k in range(3)]
+    pts = np.vstack([X[i0], X[i1], rng.uniform(0.1, 0.9, size=d)])
+    p = h3.Problem("floors", [gps], h3.REF, front, pts, np.zeros((0, d)), (0, 1, 2))
+    scale = h3.member_scale(gps, h3.REF)
+    m = h3.Member(gps, p.ref, front, p.pending, np.float64)
+    sigma = max(np.sqrt(abs(float(h3.cr.moments(mm, b, X[i1])[1]))) for mm, b in zip(m.models, m.bases))
+    gain = ehvi.hypervolume_3(np.vstack([front, Y[i1:i1 + 1]]), p.ref) - ehvi.hypervolume_3(front, p.ref)
+    bound = h3.floor_bound(front, p.ref, Y[i1], 10.0 * sigma)
+    D = _Device(p)
+    v, g = _eval(D, p, pts)
+    print("on sampled points of noise-free GPs: dominated %.3g, gradient %s; undominated %.12g against the deterministic gain %.12g "
+          "(difference %.3g, bound %.3g from the restatement's sigma %.3g; 1e-6 scale is %.3g); beside them %.3g" % (
+              v[0], g[0], v[1], gain, abs(v[1] - gain), bound, sigma, 1e-6 * scale, v[2]))
+    assert np.all(np.isfinite(v)) and np.all(np.isfinite(g)) and np.all(v >= 0.0)
+    assert 0.0 <= v[0] <= 1e-10 * scale and v[2] > 1e-6
+    assert gain > 1e-3 and bound <= 1e-6 * scale  # (the bound binds: the assertion on candidate 1 is kept)
+    assert abs(v[1] - gain) <= bound
     D.close()
 
 
