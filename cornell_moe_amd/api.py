@@ -1274,6 +1274,75 @@ def ehvi3_suggest(gps, gps2, gps3, reference_point, front, gd_params, bounds, st
                          points_being_sampled)
 
 
+def _ehvi_constrained_call(objective_gps, constraint_gps, thresholds, reference_point, front):
+    """(which entry points: "ehvi" or "ehvi3", the arguments in front of the shape's own, E, dim, K, what must stay alive) of the
+    ensemble forms of the constrained expected hypervolume improvement.  objective_gps: 2 or 3 ensembles shaped alike (a
+    DeviceGPMCMC, a list of DeviceGP or one DeviceGP), E members each; constraint_gps: K ensembles of the same shape (None: K = 0)."""
+    objs = list(objective_gps)
+    M = len(objs)
+    if M == 2:
+        arr, arr2, E, d, keep, ref, fr, F = _ehvi_members(objs[0], objs[1], reference_point, front)
+        arrs, stem = [arr, arr2], "moe_ehvi_constrained_mcmc"
+    elif M == 3:
+        arrs, E, d, keep, ref, fr, F = _ehvi3_members(objs[0], objs[1], objs[2], reference_point, front)
+        stem = "moe_ehvi3_constrained_mcmc"
+    else:
+        raise BoundsException("two or three objectives", M, 2, 3)
+    cons = [] if constraint_gps is None else list(constraint_gps)
+    K = len(cons)
+    tau = np.ascontiguousarray([] if thresholds is None else thresholds, dtype=np.float64).ravel()
+    if tau.size != K:
+        raise BoundsException("one threshold per constraint", tau.size, K, K)
+    per = []
+    for c in cons:
+        members = [c] if isinstance(c, DeviceGP) else (list(c.gps) if isinstance(c, DeviceGPMCMC) else list(c))
+        if len(members) != E:
+            raise BoundsException("one constraint GP per ensemble member and constraint", len(members), E, E)
+        per.append(members)
+    flat = [per[k][e] for e in range(E) for k in range(K)]  # [E][K]
+    carr = (C.c_void_p * max(len(flat), 1))(*[g._h.value for g in flat]) if K else None
+    pre = tuple(arrs) + (carr, K, tau.ctypes.data_as(dp) if K else None, E, ref.ctypes.data_as(dp),
+                         fr.ctypes.data_as(dp) if F else None, F)
+    return stem, pre, E, d, K, (keep, flat, tau, ref, fr, carr)
+
+
+def ehvi_constrained_ensemble(objective_gps, constraint_gps, thresholds, reference_point, front, points, points_being_sampled=None,
+                              want_grad=True, want_factors=False):
+    """moe_ehvi_constrained_mcmc / moe_ehvi3_constrained_mcmc: the expected hypervolume improvement times the probability of
+    feasibility (minimisation), averaged over the ensemble at points [C][dim], in one device call.  objective_gps: 2 or 3 ensembles
+    (the number decides which); member e is objective_gps[r][e] and the constraint GPs constraint_gps[k][e], constraint k satisfied
+    where c_k(x) <= thresholds[k] (0 <= K <= 8; K = 0 is ehvi_ensemble / ehvi3_ensemble bit for bit).  reference_point and front as
+    there, the front that of the FEASIBLE observations (feasible_pareto_front of expected_hypervolume_improvement_constrained.py).
+    points_being_sampled [p][dim] condition every GP's covariance; a pending point's believed outcome is offered to member e's front
+    only where the member believes it feasible.  Returns value [C], with want_grad (value, grad [C][dim]), and with want_factors
+    additionally factors [E][1 + K][C] (the hypervolume term, then the K feasibility factors) as the last item.
+    SingularMatrixException(e (M + K) + role, j): the GP, counted flat, and the pending point; a candidate never raises."""
+    stem, pre, E, d, K, keep = _ehvi_constrained_call(objective_gps, constraint_gps, thresholds, reference_point, front)
+    return _acq1_evaluate(getattr(_lib.load(), stem), pre, (), d, points, want_grad, points_being_sampled,
+                          extra_shape=(E, 1 + K), want_extra=want_factors)
+
+
+def ehvi_constrained_multistart(objective_gps, constraint_gps, thresholds, reference_point, front, gd_params, bounds, starts,
+                                gradient_ascent=True, want_path=False, points_being_sampled=None):
+    """moe_ehvi_constrained_mcmc_multistart / moe_ehvi3_constrained_mcmc_multistart: one suggestion by the ensemble-averaged
+    constrained expected hypervolume improvement -- ei_analytic_multistart's screening, 20 kept starts, restarted ascent on the
+    device and end-point selection, and its dict."""
+    stem, pre, E, d, K, keep = _ehvi_constrained_call(objective_gps, constraint_gps, thresholds, reference_point, front)
+    return _acq1_multistart(getattr(_lib.load(), stem + "_multistart"), pre, (), d, gd_params, bounds, starts, gradient_ascent,
+                            want_path, points_being_sampled)
+
+
+def ehvi_constrained_suggest(objective_gps, constraint_gps, thresholds, reference_point, front, gd_params, bounds, starts,
+                             num_to_sample, gradient_ascent=True, points_being_sampled=None):
+    """moe_ehvi_constrained_mcmc_suggest / moe_ehvi3_constrained_mcmc_suggest: num_to_sample points greedily -- round t is
+    ehvi_constrained_multistart from the same starts [S][dim] with the pending points points_being_sampled [p][dim] (may be None)
+    followed by the points of the rounds before, bit for bit, in one device call.  p + num_to_sample - 1 <= 64.  Returns a dict:
+    points [q][dim], values [q], found [q]."""
+    stem, pre, E, d, K, keep = _ehvi_constrained_call(objective_gps, constraint_gps, thresholds, reference_point, front)
+    return _acq1_suggest(getattr(_lib.load(), stem + "_suggest"), pre, (), d, gd_params, bounds, starts, num_to_sample,
+                         gradient_ascent, points_being_sampled)
+
+
 def _gibbon_members(gps, min_values):
     """(handles, count, dim, members kept alive, min-values [E][K], K) of the ensemble forms of the min-value entropy acquisition; a
     single DeviceGP counts as a list of one"""

@@ -62,7 +62,7 @@ moe::GpDev& lock_gp(const moe_gp_t* gp_c, std::unique_lock<std::mutex>& lk) {
   return gp->dev;
 }
 
-// The first check of the ensemble one-point acquisitions' entry points (Acq1::check_num_mcmc; moe_ehvi_mcmc* and moe_ehvi3_mcmc* have their own).
+// The first check of the ensemble one-point acquisitions' entry points (Acq1::check_num_mcmc; moe_ehvi_mcmc* and moe_ehvi3_mcmc* have their own, which their constrained forms take).
 void check_num_mcmc(int num_mcmc) {
   if (num_mcmc < 1 || num_mcmc > 1024) throw moe::Error(MOE_ERR_BOUNDS, "num_mcmc must be between 1 and 1024", num_mcmc, 1, 1024);
 }
@@ -915,7 +915,7 @@ int moe_gp_paths_minimize(const moe_gp_t* const* gps, int num_mcmc, const double
   });
 }
 
-// ---- the ensemble forms of the one-point acquisitions (kg1_ascent.hpp): seven objectives, three shapes of entry point each ----
+// ---- the ensemble forms of the one-point acquisitions (kg1_ascent.hpp): nine objectives, three shapes of entry point each ----
 extern "C++" {  // (the helpers return C++ types)
 namespace {
 
@@ -1099,6 +1099,50 @@ Acq1 ehvi3(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp
   };
   a.handles = [=] { return three_objective_handles(gps, gps2, gps3, num_mcmc); };
   a.call = [=] { return moe::ehvi3_call(num_mcmc, reference_point, front, num_front); };
+  return a;
+}
+
+// The GPs of a constrained multi-objective call, flat and ordered [e][role]: the objectives of `base` (M per member), then member
+// e's constraint GPs constraint_gps[e K + k]
+std::vector<const moe_gp_t*> constrained_objective_handles(const std::vector<const moe_gp_t*>& base, int M, int num_mcmc,
+                                                          const moe_gp_t* const* constraint_gps, int num_constraints) {
+  const int G = M + num_constraints;
+  std::vector<const moe_gp_t*> flat((size_t)num_mcmc * G);
+  for (int e = 0; e < num_mcmc; ++e) {
+    for (int r = 0; r < M; ++r) flat[(size_t)e * G + r] = base[(size_t)e * M + r];
+    for (int k = 0; k < num_constraints; ++k) flat[(size_t)e * G + M + k] = constraint_gps[(size_t)e * num_constraints + k];
+  }
+  return flat;
+}
+
+// the unconstrained twin's ladder with the constraints' checks in front of its front's, and M + K GPs per member
+Acq1 ehvi_constrained(Acq1 a, int M, const moe_gp_t* const* constraint_gps, int num_constraints, const double* thresholds) {
+  const int num_mcmc = a.num_mcmc;
+  a.name = "the constrained expected hypervolume improvement";
+  const std::function<void(int)> twin_shapes = a.check_shapes;
+  a.check_shapes = [=](int num_points) {
+    moe::check_ehvi_constrained_shapes(M, num_mcmc, num_constraints, constraint_gps, thresholds);
+    twin_shapes(num_points);
+  };
+  const std::function<std::vector<const moe_gp_t*>()> twin_handles = a.handles;
+  a.handles = [=] { return constrained_objective_handles(twin_handles(), M, num_mcmc, constraint_gps, num_constraints); };
+  return a;
+}
+
+Acq1 ehvi_constrained2(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* constraint_gps,
+                       int num_constraints, const double* thresholds, int num_mcmc, const double* reference_point, const double* front,
+                       int num_front) {
+  Acq1 a = ehvi_constrained(ehvi(gps, gps2, num_mcmc, reference_point, front, num_front), 2, constraint_gps, num_constraints, thresholds);
+  a.call = [=] { return moe::cehvi1_call(num_mcmc, num_constraints, thresholds, reference_point, front, num_front); };
+  return a;
+}
+
+Acq1 ehvi_constrained3(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* gps3,
+                       const moe_gp_t* const* constraint_gps, int num_constraints, const double* thresholds, int num_mcmc,
+                       const double* reference_point, const double* front, int num_front) {
+  Acq1 a = ehvi_constrained(ehvi3(gps, gps2, gps3, num_mcmc, reference_point, front, num_front), 3, constraint_gps, num_constraints,
+                            thresholds);
+  a.call = [=] { return moe::cehvi3_call(num_mcmc, num_constraints, thresholds, reference_point, front, num_front); };
   return a;
 }
 
@@ -1358,6 +1402,85 @@ int moe_ehvi3_mcmc_suggest(const moe_gp_t* const* gps, const moe_gp_t* const* gp
   return guarded(err, [&] {
     acq1_suggest(ehvi3(gps, gps2, gps3, num_mcmc, reference_point, front, num_front), outer, domain_bounds, points_being_sampled,
                  num_being_sampled, starts, num_starts, do_gradient_ascent, num_to_sample, {best_points, best_values, found});
+  });
+}
+
+int moe_ehvi_constrained_mcmc(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* constraint_gps,
+                              int num_constraints, const double* thresholds, int num_mcmc, const double* reference_point,
+                              const double* front, int num_front, const double* points_being_sampled, int num_being_sampled,
+                              const double* points, int num_points, int want_grad, double* value, double* grad, double* factors_out,
+                              moe_error_t* err) {
+  return guarded(err, [&] {
+    acq1_evaluate(ehvi_constrained2(gps, gps2, constraint_gps, num_constraints, thresholds, num_mcmc, reference_point, front, num_front),
+                  points_being_sampled, num_being_sampled, points, num_points, want_grad, value, grad, factors_out);
+  });
+}
+
+int moe_ehvi_constrained_mcmc_multistart(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* constraint_gps,
+                                         int num_constraints, const double* thresholds, int num_mcmc, const double* reference_point,
+                                         const double* front, int num_front, const moe_gd_params_t* outer, const double* domain_bounds,
+                                         const double* points_being_sampled, int num_being_sampled, const double* starts,
+                                         int num_starts, int do_gradient_ascent, double* best_point, double* best_value, int* found,
+                                         double* start_values, int* kept_index, double* end_points, double* end_values, double* path,
+                                         int* steps_taken, moe_error_t* err) {
+  return guarded(err, [&] {
+    acq1_multistart(ehvi_constrained2(gps, gps2, constraint_gps, num_constraints, thresholds, num_mcmc, reference_point, front, num_front),
+                    outer, domain_bounds, points_being_sampled, num_being_sampled, starts, num_starts, do_gradient_ascent,
+                    {best_point, best_value, found, start_values, kept_index, end_points, end_values, path, steps_taken});
+  });
+}
+
+int moe_ehvi_constrained_mcmc_suggest(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* constraint_gps,
+                                      int num_constraints, const double* thresholds, int num_mcmc, const double* reference_point,
+                                      const double* front, int num_front, const moe_gd_params_t* outer, const double* domain_bounds,
+                                      const double* points_being_sampled, int num_being_sampled, const double* starts, int num_starts,
+                                      int do_gradient_ascent, int num_to_sample, double* best_points, double* best_values, int* found,
+                                      moe_error_t* err) {
+  return guarded(err, [&] {
+    acq1_suggest(ehvi_constrained2(gps, gps2, constraint_gps, num_constraints, thresholds, num_mcmc, reference_point, front, num_front),
+                 outer, domain_bounds, points_being_sampled, num_being_sampled, starts, num_starts, do_gradient_ascent, num_to_sample,
+                 {best_points, best_values, found});
+  });
+}
+
+int moe_ehvi3_constrained_mcmc(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* gps3,
+                               const moe_gp_t* const* constraint_gps, int num_constraints, const double* thresholds, int num_mcmc,
+                               const double* reference_point, const double* front, int num_front, const double* points_being_sampled,
+                               int num_being_sampled, const double* points, int num_points, int want_grad, double* value, double* grad,
+                               double* factors_out, moe_error_t* err) {
+  return guarded(err, [&] {
+    acq1_evaluate(
+        ehvi_constrained3(gps, gps2, gps3, constraint_gps, num_constraints, thresholds, num_mcmc, reference_point, front, num_front),
+        points_being_sampled, num_being_sampled, points, num_points, want_grad, value, grad, factors_out);
+  });
+}
+
+int moe_ehvi3_constrained_mcmc_multistart(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* gps3,
+                                          const moe_gp_t* const* constraint_gps, int num_constraints, const double* thresholds,
+                                          int num_mcmc, const double* reference_point, const double* front, int num_front,
+                                          const moe_gd_params_t* outer, const double* domain_bounds, const double* points_being_sampled,
+                                          int num_being_sampled, const double* starts, int num_starts, int do_gradient_ascent,
+                                          double* best_point, double* best_value, int* found, double* start_values, int* kept_index,
+                                          double* end_points, double* end_values, double* path, int* steps_taken, moe_error_t* err) {
+  return guarded(err, [&] {
+    acq1_multistart(
+        ehvi_constrained3(gps, gps2, gps3, constraint_gps, num_constraints, thresholds, num_mcmc, reference_point, front, num_front),
+        outer, domain_bounds, points_being_sampled, num_being_sampled, starts, num_starts, do_gradient_ascent,
+        {best_point, best_value, found, start_values, kept_index, end_points, end_values, path, steps_taken});
+  });
+}
+
+int moe_ehvi3_constrained_mcmc_suggest(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* gps3,
+                                       const moe_gp_t* const* constraint_gps, int num_constraints, const double* thresholds,
+                                       int num_mcmc, const double* reference_point, const double* front, int num_front,
+                                       const moe_gd_params_t* outer, const double* domain_bounds, const double* points_being_sampled,
+                                       int num_being_sampled, const double* starts, int num_starts, int do_gradient_ascent,
+                                       int num_to_sample, double* best_points, double* best_values, int* found, moe_error_t* err) {
+  return guarded(err, [&] {
+    acq1_suggest(
+        ehvi_constrained3(gps, gps2, gps3, constraint_gps, num_constraints, thresholds, num_mcmc, reference_point, front, num_front),
+        outer, domain_bounds, points_being_sampled, num_being_sampled, starts, num_starts, do_gradient_ascent, num_to_sample,
+        {best_points, best_values, found});
   });
 }
 

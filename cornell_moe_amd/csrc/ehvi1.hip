@@ -4,7 +4,8 @@
 // client of kg1_ascent.hip's staging, ascent and drivers.  The pending-row extension is kg1_pending.hip's, the
 // layout and the pass are ei1.hip's (ei1.hpp); this file keeps a sub-member's candidate kernel and the two-sum gradient kernel
 // with its tail, the front kernel, the strip kernel, the combine kernel, the members' check and the description of the call
-// (ehvi1_call).  ehvi3.hip, the three-objective form, takes the sub-member's chain, the members' check and psi from here (ehvi1.hpp).
+// (ehvi1_call).  ehvi3.hip, the three-objective form, takes the sub-member's chain, the members' check and psi from here (ehvi1.hpp);
+// cehvi1.hip, the constrained form, also the layout and the launches of the front kernel (with its mask) and the strip kernel.
 //
 // Minimisation.  A call takes E joint hyper-samples; member e is two GPs, objective 1 and objective 2, the 2 E GPs being the
 // SUB-MEMBERS of one Kg1Ensemble ordered [e][role].  r = (r1, r2) is the reference point, the front F >= 0 points (u_i, v_i) with
@@ -57,32 +58,9 @@ namespace {
 
 constexpr int kEhviCap = kEhviMaxFront + kKg1MaxPending;  // a member's front at its largest
 
-// what the hooks need of the call (Kg1Objective::client)
-struct Ehvi1Call {
-  const double* front;  // [F][2], the caller's
-  int F;
-  double r1, r2;
-};
-
-// where the call's own device memory lies inside the first GP's ehviD, in doubles
-struct Ehvi1Layout {
-  int E, F, cap, C;
-  size_t oCaller, oFront, oCount, oVals, oCoef, total;
-};
 Ehvi1Layout layout_of(const Kg1Ensemble& T) {
   const Ehvi1Call& k = *static_cast<const Ehvi1Call*>(T.client);
-  Ehvi1Layout l;
-  l.E = T.E / 2;
-  l.F = k.F;
-  l.cap = std::max(1, k.F + T.pcap);
-  l.C = T.mem[0].C;
-  l.oCaller = 0;
-  l.oFront = l.oCaller + 2 * (size_t)std::max(1, k.F);
-  l.oCount = l.oFront + 2 * (size_t)l.E * l.cap;
-  l.oVals = l.oCount + (size_t)l.E;  // (the counts are integers in the front halves of E doubles' room)
-  l.oCoef = l.oVals + (size_t)l.E * l.C;
-  l.total = l.oCoef + 4 * (size_t)l.E * l.C;
-  return l;
+  return ehvi1_layout(T.E / 2, k.F, T.pcap, T.mem[0].C);
 }
 
 // One wavefront per candidate: ei1_cand_kernel's chain for the variance (rows past R add exact zeros).  out [2][Cs]: mu and var of
@@ -169,8 +147,9 @@ __global__ __launch_bounds__(256) void ehvi1_grad_kernel(int R, int ld, int d, i
 
 // One wavefront per member (blockIdx.x).  kg: the sub-members' dKg, their mu at the pending points `aa` doubles behind.  first != 0:
 // the member's front is the caller's [F][2]; otherwise the front as it stands.  Then the believed outcomes of `count` pending points
-// join in order under the header's rule.  fronts: [E][2][cap], counts [E].
-__global__ __launch_bounds__(64) void ehvi1_front_kernel(const double* const* __restrict__ kg, size_t aa, const double* __restrict__ caller, int F, double r1, double r2, double* __restrict__ fronts, int cap, int* __restrict__ counts, int first, int count) {
+// join in order under the header's rule.  fronts: [E][2][cap], counts [E].  mask (NULL: every outcome is offered): member e offers
+// pending point j only where mask[e mask_ld + j] != 0 (cehvi1.hip's believed feasibility).
+__global__ __launch_bounds__(64) void ehvi1_front_kernel(const double* const* __restrict__ kg, size_t aa, const double* __restrict__ caller, int F, double r1, double r2, double* __restrict__ fronts, int cap, int* __restrict__ counts, int first, int count, const int* __restrict__ mask, int mask_ld) {
   const int e = blockIdx.x, lane = threadIdx.x;
   double* u = fronts + (size_t)e * 2 * cap;
   double* v = u + cap;
@@ -188,6 +167,7 @@ __global__ __launch_bounds__(64) void ehvi1_front_kernel(const double* const* __
   const double* mu1 = kg[2 * e] + aa;
   const double* mu2 = kg[2 * e + 1] + aa;
   for (int j = 0; j < count; ++j) {
+    if (mask != nullptr && mask[(size_t)e * mask_ld + j] == 0) continue;  // (the same word for every lane)
     const double a = mu1[j], b = mu2[j];
     if (!(a < r1 && b < r2)) continue;  // (not strictly inside r; NaN included)
     int lo = 0, ev = 0, dom = 0;
@@ -365,6 +345,35 @@ void grad_tail(const Kg1Member& m, const double* Px, int nc, int c0, hipStream_t
 
 }  // namespace
 
+Ehvi1Layout ehvi1_layout(int E, int F, int pcap, int C) {
+  Ehvi1Layout l;
+  l.E = E;
+  l.F = F;
+  l.cap = std::max(1, F + pcap);
+  l.C = C;
+  l.oCaller = 0;
+  l.oFront = l.oCaller + 2 * (size_t)std::max(1, F);
+  l.oCount = l.oFront + 2 * (size_t)l.E * l.cap;
+  l.oVals = l.oCount + (size_t)l.E;  // (the counts are integers in the front halves of E doubles' room)
+  l.oCoef = l.oVals + (size_t)l.E * l.C;
+  l.total = l.oCoef + 4 * (size_t)l.E * l.C;
+  return l;
+}
+
+void ehvi1_launch_front(const Ehvi1Call& k, const Ehvi1Layout& l, double* base, const double* const* kg, size_t aa, const int* mask,
+                        int mask_ld, bool first, int count, hipStream_t s) {
+  MOE_LAUNCH_NOW(ehvi1_front_kernel, dim3((unsigned)l.E), dim3(64), 0, s, kg, aa, (const double*)(base + l.oCaller), l.F, k.r1, k.r2,
+                 base + l.oFront, l.cap, reinterpret_cast<int*>(base + l.oCount), first ? 1 : 0, count, mask, mask_ld);
+  MOE_HIP_CHECK(hipGetLastError());
+}
+
+void ehvi1_launch_strip(const Ehvi1Call& k, const Ehvi1Layout& l, double* base, const double* const* kg, int C, bool want_grad,
+                        hipStream_t s) {
+  MOE_LAUNCH_NOW(ehvi1_strip_kernel, dim3((unsigned)((C + 3) / 4), (unsigned)l.E), dim3(256), 0, s, C, l.C, kg,
+                 (const double*)(base + l.oFront), l.cap, reinterpret_cast<const int*>(base + l.oCount), k.r1, k.r2, want_grad ? 1 : 0,
+                 base + l.oVals, base + l.oCoef);
+}
+
 void ehvi1_eval_points(const Kg1Member& m, const double* Px, const double*, int C, bool with_grad, hipStream_t s) {
   ei1_eval_passes(m, Px, C, with_grad, s, "ehvi1_eval_pass", cand_step, grad_tail);
 }
@@ -391,11 +400,8 @@ void join_believed_outcomes(Kg1Ensemble& T, int j0, int count, bool first) {
     if (count > 0)
       launch_mean(gp.cp, gp.dX.p, gp.n, gp.derivs, gp.dKinvY.p, T.dPending + (size_t)j0 * T.dp, count, gp.mean, false, m.dAA, T.z);
   }
-  double* base = g0.ehviD.p;
   const size_t aa = (size_t)(T.mem[0].dAA - T.mem[0].dKg);  // (one layout for every sub-member: ei1_member's, from C, d and with_grad)
-  MOE_LAUNCH_NOW(ehvi1_front_kernel, dim3((unsigned)l.E), dim3(64), 0, T.z, T.dKgTab, aa, (const double*)(base + l.oCaller), l.F, k.r1,
-                 k.r2, base + l.oFront, l.cap, reinterpret_cast<int*>(base + l.oCount), first ? 1 : 0, count);
-  MOE_HIP_CHECK(hipGetLastError());
+  ehvi1_launch_front(k, l, g0.ehviD.p, T.dKgTab, aa, nullptr, 0, first, count, T.z);
 }
 
 // every sub-member's extension stands: the call's own device memory, the caller's front, then the members' fronts
@@ -421,9 +427,7 @@ void combine(const Kg1Ensemble& T, int C, double* value_out, double* grad_out) {
   const Ehvi1Layout l = layout_of(T);
   if (C < 1 || C > l.C) throw Error(MOE_ERR_RUNTIME, "ehvi1: more candidates than the call was staged for");
   double* base = T.gps[0]->ehviD.p;
-  MOE_LAUNCH_NOW(ehvi1_strip_kernel, dim3((unsigned)((C + 3) / 4), (unsigned)l.E), dim3(256), 0, T.z, C, l.C, T.dKgTab,
-                 (const double*)(base + l.oFront), l.cap, reinterpret_cast<const int*>(base + l.oCount), k.r1, k.r2,
-                 grad_out != nullptr ? 1 : 0, base + l.oVals, base + l.oCoef);
+  ehvi1_launch_strip(k, l, base, T.dKgTab, C, grad_out != nullptr, T.z);
   const long n = (value_out != nullptr ? (long)C : 0) + (grad_out != nullptr ? (long)C * T.d : 0);
   MOE_LAUNCH_NOW(ehvi1_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, T.z, l.E, (long)C, l.C, T.d,
                  (const double*)(base + l.oVals), (const double*)(base + l.oCoef), T.dGradTab, value_out, grad_out);

@@ -2,7 +2,8 @@
 // with pending points, its multistart ascent and greedy q-point batches, on the device (moe_ehvi3_mcmc, moe_ehvi3_mcmc_multistart,
 // moe_ehvi3_mcmc_suggest): the seventh client of kg1_ascent.hip's staging, ascent and drivers.  The sub-member's chain, the members'
 // check and psi are ehvi1.hip's (ehvi1.hpp); this file keeps the front kernel, the table kernel, the box kernel, the combine kernel
-// and the description of the call (ehvi3_call).
+// and the description of the call (ehvi3_call).  cehvi1.hip, the constrained form, takes the layout and the launches of the front
+// kernel (with its mask), the table kernel and the box kernel from here (ehvi3.hpp).
 //
 // Minimisation.  A call takes E joint hyper-samples; member e is three GPs, one per objective, the 3 E GPs being the SUB-MEMBERS of
 // one Kg1Ensemble ordered [e][objective].  r = (r1, r2, r3) is the reference point, the member's front n >= 0 mutually non-dominated
@@ -51,6 +52,7 @@
 
 #include "acq1_device.hpp"
 #include "ehvi1.hpp"
+#include "ehvi3.hpp"
 #include "kg1_ascent.hpp"
 
 namespace moe {
@@ -61,43 +63,18 @@ constexpr int kEhvi3Cap = kEhvi3MaxFront + kKg1MaxPending;  // a member's front 
 constexpr int kEhvi3Edges = kEhvi3Cap + 2;                  // -infinity, the points, the reference point
 static_assert(kEhvi3Cap == 256, "the table kernel gives every point a thread, the front kernel every lane four points");
 
-// what the hooks need of the call (Kg1Objective::client)
-struct Ehvi3Call {
-  const double* front;  // [F][3], the caller's
-  int F;
-  double r1, r2, r3;
-};
-
 size_t max_boxes(int cap) { return (size_t)(cap + 1) * (size_t)(cap + 2) / 2; }
 
-// where the call's own device memory lies inside the first GP's ehviD, in doubles (a box fills one double's room)
-struct Ehvi3Layout {
-  int E, F, cap, C;
-  size_t tstride, oCaller, oFront, oCount, oNbox, oTable, oVals, oCoef, total;
-};
 Ehvi3Layout layout_of(const Kg1Ensemble& T) {
   const Ehvi3Call& k = *static_cast<const Ehvi3Call*>(T.client);
-  Ehvi3Layout l;
-  l.E = T.E / 3;
-  l.F = k.F;
-  l.cap = std::min(kEhvi3Cap, std::max(1, k.F + T.pcap));
-  l.C = T.mem[0].C;
-  l.tstride = max_boxes(l.cap);
-  l.oCaller = 0;
-  l.oFront = l.oCaller + 3 * (size_t)std::max(1, k.F);
-  l.oCount = l.oFront + 3 * (size_t)l.E * l.cap;
-  l.oNbox = l.oCount + (size_t)l.E;  // (the counts are integers in the front halves of E doubles' room, the box counts likewise)
-  l.oTable = l.oNbox + (size_t)l.E;
-  l.oVals = l.oTable + (size_t)l.E * l.tstride;
-  l.oCoef = l.oVals + (size_t)l.E * l.C;
-  l.total = l.oCoef + 6 * (size_t)l.E * l.C;
-  return l;
+  return ehvi3_layout(T.E / 3, k.F, T.pcap, T.mem[0].C);
 }
 
 // One wavefront per member (blockIdx.x).  kg: the sub-members' dKg, their mu at the pending points `aa` doubles behind.  first != 0:
 // the member's front is the caller's [F][3]; otherwise the front as it stands.  Then the believed outcomes of `count` pending points
-// join in order under the header's rule.  fronts: [E][3][cap], counts [E].
-__global__ __launch_bounds__(64) void ehvi3_front_kernel(const double* const* __restrict__ kg, size_t aa, const double* __restrict__ caller, int F, double r1, double r2, double r3, double* __restrict__ fronts, int cap, int* __restrict__ counts, int first, int count) {
+// join in order under the header's rule.  fronts: [E][3][cap], counts [E].  mask (NULL: every outcome is offered): member e offers
+// pending point j only where mask[e mask_ld + j] != 0 (cehvi1.hip's believed feasibility).
+__global__ __launch_bounds__(64) void ehvi3_front_kernel(const double* const* __restrict__ kg, size_t aa, const double* __restrict__ caller, int F, double r1, double r2, double r3, double* __restrict__ fronts, int cap, int* __restrict__ counts, int first, int count, const int* __restrict__ mask, int mask_ld) {
   __shared__ double s_u[kEhvi3Cap], s_v[kEhvi3Cap], s_w[kEhvi3Cap];
   __shared__ int s_keep[kEhvi3Cap];
   const int e = blockIdx.x, lane = threadIdx.x;
@@ -126,6 +103,7 @@ __global__ __launch_bounds__(64) void ehvi3_front_kernel(const double* const* __
   const double* mu2 = kg[3 * e + 1] + aa;
   const double* mu3 = kg[3 * e + 2] + aa;
   for (int j = 0; j < count; ++j) {
+    if (mask != nullptr && mask[(size_t)e * mask_ld + j] == 0) continue;  // (the same word for every lane)
     const double a = mu1[j], b = mu2[j], c = mu3[j];
     if (!(isfinite(a) && isfinite(b) && isfinite(c) && a < r1 && b < r2 && c < r3)) continue;  // (not finite or not strictly inside r)
     int dom = 0, kept = 0, before = 0;
@@ -355,6 +333,45 @@ __global__ __launch_bounds__(256) void ehvi3_combine_kernel(int E, long C, int C
   grad_out[k] = sum / (double)E;
 }
 
+}  // namespace
+
+Ehvi3Layout ehvi3_layout(int E, int F, int pcap, int C) {
+  Ehvi3Layout l;
+  l.E = E;
+  l.F = F;
+  l.cap = std::min(kEhvi3Cap, std::max(1, F + pcap));
+  l.C = C;
+  l.tstride = max_boxes(l.cap);
+  l.oCaller = 0;
+  l.oFront = l.oCaller + 3 * (size_t)std::max(1, F);
+  l.oCount = l.oFront + 3 * (size_t)l.E * l.cap;
+  l.oNbox = l.oCount + (size_t)l.E;  // (the counts are integers in the front halves of E doubles' room, the box counts likewise)
+  l.oTable = l.oNbox + (size_t)l.E;
+  l.oVals = l.oTable + (size_t)l.E * l.tstride;
+  l.oCoef = l.oVals + (size_t)l.E * l.C;
+  l.total = l.oCoef + 6 * (size_t)l.E * l.C;
+  return l;
+}
+
+void ehvi3_launch_front(const Ehvi3Call& k, const Ehvi3Layout& l, double* base, const double* const* kg, size_t aa, const int* mask,
+                        int mask_ld, bool first, int count, hipStream_t s) {
+  int* counts = reinterpret_cast<int*>(base + l.oCount);
+  MOE_LAUNCH_NOW(ehvi3_front_kernel, dim3((unsigned)l.E), dim3(64), 0, s, kg, aa, (const double*)(base + l.oCaller), l.F, k.r1, k.r2,
+                 k.r3, base + l.oFront, l.cap, counts, first ? 1 : 0, count, mask, mask_ld);
+  MOE_LAUNCH_NOW(ehvi3_table_kernel, dim3((unsigned)l.E), dim3(256), 0, s, (const double*)(base + l.oFront), l.cap, (const int*)counts,
+                 reinterpret_cast<ushort4*>(base + l.oTable), l.tstride, reinterpret_cast<int*>(base + l.oNbox));
+  MOE_HIP_CHECK(hipGetLastError());
+}
+
+void ehvi3_launch_box(const Ehvi3Call& k, const Ehvi3Layout& l, double* base, const double* const* kg, int C, bool want_grad,
+                      hipStream_t s) {
+  MOE_LAUNCH_NOW(ehvi3_box_kernel, dim3((unsigned)C, (unsigned)l.E), dim3(256), 0, s, l.C, kg, (const double*)(base + l.oFront), l.cap,
+                 reinterpret_cast<const int*>(base + l.oCount), reinterpret_cast<const ushort4*>(base + l.oTable), l.tstride,
+                 reinterpret_cast<const int*>(base + l.oNbox), k.r1, k.r2, k.r3, want_grad ? 1 : 0, base + l.oVals, base + l.oCoef);
+}
+
+namespace {
+
 Kg1Member member(const Kg1Objective&, GpDev& gp, int e, int C, bool with_grad, int* fail, int pcap, int* fail_pending) {
   return ehvi1_member(gp, e % 3, C, with_grad, fail, pcap, fail_pending);
 }
@@ -369,14 +386,8 @@ void join_believed_outcomes(Kg1Ensemble& T, int j0, int count, bool first) {
     if (count > 0)
       launch_mean(gp.cp, gp.dX.p, gp.n, gp.derivs, gp.dKinvY.p, T.dPending + (size_t)j0 * T.dp, count, gp.mean, false, m.dAA, T.z);
   }
-  double* base = g0.ehviD.p;
   const size_t aa = (size_t)(T.mem[0].dAA - T.mem[0].dKg);  // (one layout for every sub-member: ei1_member's, from C, d and with_grad)
-  int* counts = reinterpret_cast<int*>(base + l.oCount);
-  MOE_LAUNCH_NOW(ehvi3_front_kernel, dim3((unsigned)l.E), dim3(64), 0, T.z, T.dKgTab, aa, (const double*)(base + l.oCaller), l.F, k.r1,
-                 k.r2, k.r3, base + l.oFront, l.cap, counts, first ? 1 : 0, count);
-  MOE_LAUNCH_NOW(ehvi3_table_kernel, dim3((unsigned)l.E), dim3(256), 0, T.z, (const double*)(base + l.oFront), l.cap, (const int*)counts,
-                 reinterpret_cast<ushort4*>(base + l.oTable), l.tstride, reinterpret_cast<int*>(base + l.oNbox));
-  MOE_HIP_CHECK(hipGetLastError());
+  ehvi3_launch_front(k, l, g0.ehviD.p, T.dKgTab, aa, nullptr, 0, first, count, T.z);
 }
 
 // every sub-member's extension stands: the call's own device memory, the caller's front, then the members' fronts and tables
@@ -402,10 +413,7 @@ void combine(const Kg1Ensemble& T, int C, double* value_out, double* grad_out) {
   const Ehvi3Layout l = layout_of(T);
   if (C < 1 || C > l.C) throw Error(MOE_ERR_RUNTIME, "ehvi3: more candidates than the call was staged for");
   double* base = T.gps[0]->ehviD.p;
-  MOE_LAUNCH_NOW(ehvi3_box_kernel, dim3((unsigned)C, (unsigned)l.E), dim3(256), 0, T.z, l.C, T.dKgTab, (const double*)(base + l.oFront),
-                 l.cap, reinterpret_cast<const int*>(base + l.oCount), reinterpret_cast<const ushort4*>(base + l.oTable), l.tstride,
-                 reinterpret_cast<const int*>(base + l.oNbox), k.r1, k.r2, k.r3, grad_out != nullptr ? 1 : 0, base + l.oVals,
-                 base + l.oCoef);
+  ehvi3_launch_box(k, l, base, T.dKgTab, C, grad_out != nullptr, T.z);
   const long n = (value_out != nullptr ? (long)C : 0) + (grad_out != nullptr ? (long)C * T.d : 0);
   MOE_LAUNCH_NOW(ehvi3_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, T.z, l.E, (long)C, l.C, T.d,
                  (const double*)(base + l.oVals), (const double*)(base + l.oCoef), T.dGradTab, value_out, grad_out);

@@ -300,7 +300,7 @@ void kg1_eval_points(const Kg1Member& m, const double* Px, const double* Ph, int
 void kg1_clear_fail(int* fail, int count, hipStream_t s);  // INT_MAX: no candidate has failed
 // The ensemble forms of the one-point acquisitions: evaluate at points, multistart ascent and greedy batches of each, with pending
 // points [num_pending][dim] by the Kriging-believer fantasy of kg1_pending.hip.  Every client describes its call in one function
-// (kg1_ascent.hpp: kg1_call, ei1_call, gibbon1_call, cei1_call, ehvi1_call, logcei1_call, ehvi3_call) and the three drivers of kg1_ascent.hip run it; here are
+// (kg1_ascent.hpp: kg1_call, ei1_call, gibbon1_call, cei1_call, ehvi1_call, logcei1_call, ehvi3_call, cehvi1_call, cehvi3_call) and the three drivers of kg1_ascent.hip run it; here are
 // the checks that need no handle, which the entry points make first, and the limits.
 // kg1_opt.hip: the discretised knowledge gradient (moe_kg_discrete_mcmc*).  discrete_all: the members' sets back to back.
 void check_kg_discrete_ensemble_shapes(int num_mcmc, int num_fidelity, const int* num_discrete, int num_points);
@@ -342,6 +342,12 @@ constexpr int kEhvi3MaxFront = 192;
 constexpr int kEhvi3MaxMembers = 341;
 void check_ehvi3_num_mcmc(int num_mcmc);
 void check_ehvi3_front(const double* reference_point, const double* front, int num_front);
+// cehvi1.hip: the constrained expected hypervolume improvement (moe_ehvi_constrained_mcmc*, moe_ehvi3_constrained_mcmc*): the two
+// above over members of M + K GPs each, the GPs of a call [E (M + K)] ordered [e][role], roles 0 .. M - 1 the objectives, role
+// M - 1 + k constraint k (satisfied where c_k <= thresholds[k - 1]).  check_ehvi_constrained_shapes: K, the product limit, the
+// arrays K > 0 needs, finite thresholds.  The groups' own values of an evaluation are [E][1 + K][C]: H_e, F_{e,1} .. F_{e,K}.
+void check_ehvi_constrained_shapes(int num_objectives, int num_mcmc, int num_constraints, const void* constraint_gps,
+                                   const double* thresholds);
 // loo.hip: leave-one-out cross-validation on the GP's current factorisation, every one of the N = n (1 + g) scalar observations left
 // out by itself.  mean_out / var_out [n][1 + g]: the LOO predictive mean (function values in the caller's units) and variance.
 void loo_predict_on_device(GpDev& gp, double* mean_out, double* var_out);

@@ -464,6 +464,7 @@ Kg1Ensemble::Kg1Ensemble(const std::vector<GpDev*>& members, const Kg1Objective&
     combine = o.combine;
     group = std::max(o.group, 1);
     group_values = o.group_values;
+    group_value_rows = std::max(o.group_value_rows, 1);
   }
   client = o.client;
   gps[0]->use_device();
@@ -494,7 +495,7 @@ void kg1_ensemble_evaluate(const Kg1Objective& o, const std::vector<GpDev*>& gps
   const int d = T.d, W = T.W;
   // the call's doubles, all of them the copy back: [failure words | value C | grad C d | the members' values E C (members_out)]
   const size_t oMem = (size_t)W + (size_t)C * (want_grad ? 1 + d : 1);
-  const size_t nMem = (size_t)(T.group_values ? T.E / T.group : T.E) * C;
+  const size_t nMem = (size_t)(T.group_values ? (T.E / T.group) * T.group_value_rows : T.E) * C;
   const size_t nOut = oMem + (members_out != nullptr ? nMem : 0);
   g0.kg1oD.reserve(nOut);
   g0.hStateOut.reserve(nOut);

@@ -7,7 +7,9 @@
 // improvement, whose members are groups of 1 + K GPs combined by its own rule in the place of the ensemble mean), ehvi1.hip
 // (the two-objective expected hypervolume improvement: groups of two GPs and a Pareto front per group), logcei1.hip (the log of
 // the constrained expected improvement: cei1.hip's groups under a log-sum-exp, taken with groups of one GP too) and ehvi3.hip (the
-// three-objective expected hypervolume improvement: groups of three GPs, a front and its box table per group).
+// three-objective expected hypervolume improvement: groups of three GPs, a front and its box table per group) and cehvi1.hip (the
+// constrained expected hypervolume improvement for two and for three objectives, the eighth and ninth client: groups of M + K GPs,
+// ehvi1.hip's or ehvi3.hip's front and kernels over the objective GPs, times cei1.hip's probabilities of feasibility).
 #pragma once
 #include <memory>
 #include <vector>
@@ -61,6 +63,7 @@ struct Kg1Ensemble {
   // combine leaves whenever it forms the value: the objective's all_extended hook says where they lie
   const void* client = nullptr;
   bool group_values = false;
+  int group_value_rows = 1;  // Kg1Objective::group_value_rows
   const double* dGroupVals = nullptr;
   Kg1AscentSizes sz = {};
 };
@@ -98,8 +101,10 @@ struct Kg1Objective {
   // what the objective's hooks need of the call beside the members (Kg1Ensemble::client); nothing here reads it
   const void* client = nullptr;
   // with combine: kg1_ensemble_evaluate's members_out is the groups' own values [E / group][C], taken from Kg1Ensemble::dGroupVals,
-  // in the place of the members' [E][C]
+  // in the place of the members' [E][C]; with group_value_rows = R > 1 every group leaves R rows, [E / group][R][C] (cehvi1.hip:
+  // the member's hypervolume term and its K feasibility factors)
   bool group_values = false;
+  int group_value_rows = 1;
 };
 
 // One dim, one device, no member listed twice (MOE_ERR_INVALID_VALUE), behind num_fidelity < dim (MOE_ERR_BOUNDS); check_member:
@@ -118,7 +123,7 @@ struct Kg1Call {
   std::shared_ptr<const void> client;
   void (*check_members)(const Kg1Objective& o, const std::vector<GpDev*>& gps, int pending_room) = nullptr;
 };
-// The seven clients' descriptions, one function each (the caller has made the checks that need no handle; the arrays are the
+// The nine clients' descriptions, one function each (the caller has made the checks that need no handle; the arrays are the
 // caller's and outlive the call).  gp.hpp says what the arguments are.
 Kg1Call kg1_call(int num_fidelity, const double* discrete_all, const int* num_discrete, const double* best_so_far);  // kg1_opt.hip
 Kg1Call ei1_call(const double* best_so_far);                                                                       // ei1.hip
@@ -127,6 +132,11 @@ Kg1Call cei1_call(int num_mcmc, int num_constraints, const double* thresholds, c
 Kg1Call ehvi1_call(int num_mcmc, const double* reference_point, const double* front, int num_front);               // ehvi1.hip
 Kg1Call logcei1_call(int num_mcmc, int num_constraints, const double* thresholds, const double* best_so_far);      // logcei1.hip
 Kg1Call ehvi3_call(int num_mcmc, const double* reference_point, const double* front, int num_front);              // ehvi3.hip
+// (with num_constraints = 0 the two below return ehvi1_call / ehvi3_call themselves)
+Kg1Call cehvi1_call(int num_mcmc, int num_constraints, const double* thresholds, const double* reference_point, const double* front,
+                    int num_front);  // cehvi1.hip
+Kg1Call cehvi3_call(int num_mcmc, int num_constraints, const double* thresholds, const double* reference_point, const double* front,
+                    int num_front);  // cehvi1.hip
 
 // what a multistart hands back (all but the first three may be NULL) ...
 struct Kg1MultistartOut {

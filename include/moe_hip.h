@@ -689,6 +689,107 @@ int moe_ehvi3_mcmc_suggest(const moe_gp_t* const* gps, const moe_gp_t* const* gp
                            const double* domain_bounds, const double* points_being_sampled, int num_being_sampled,
                            const double* starts, int num_starts, int do_gradient_ascent, int num_to_sample, double* best_points,
                            double* best_values, int* found, moe_error_t* err);
+/* The constrained expected hypervolume improvement for two objectives: moe_ehvi_mcmc's quantity times the probability of
+ * feasibility (Schonlau, Welch & Jones 1998; Gardner et al. 2014), averaged over a hyper-parameter ensemble, at points
+ * [num_points][dim], with pending points.  Minimisation.  Member e is 2 + K GPs: gps[e] and gps2[e] for the objectives and the
+ * constraint GPs constraint_gps[e * num_constraints + k] (one flat array [E][K]), 0 <= K = num_constraints <= 8; constraint k is
+ * satisfied where c_k(x) <= thresholds[k].  One dim, one device, no derivative observations; the observation lists may differ.
+ * reference_point and front are moe_ehvi_mcmc's, the front being that of the FEASIBLE observations.  Per member e at x, with mu and
+ * var the posterior mean and the conditioned latent variance of the GP in question:
+ *   hypervolume term     H_e: moe_ehvi_mcmc's A_e, the same strip sum in the same order, the same clip at 0, and its four
+ *                        coefficients dH/dmu_r, dH/dvar_r
+ *   feasibility factor   F_{e,k} = Phi(z),  z = (tau_k - mu) / sigma,  sigma = sqrt(max(DBL_MIN, var))
+ *   its gradient         sigma_g = sqrt(max(150 eps^2, var)),  z_g = (tau_k - mu) / sigma_g,
+ *                        grad F = -(phi(z_g) / sigma_g) grad mu - (phi(z_g) z_g / (2 sigma_g^2)) grad var
+ *   member value         A_e = H_e F_{e,1} ... F_{e,K}, multiplied left to right; grad A_e by the product rule, each excluded
+ *                        product formed by the same left-to-right multiplication with its factor skipped, the terms added in the
+ *                        order H, k = 1 .. K; grad H_e from its coefficients in moe_ehvi_mcmc's order
+ *   ensemble             value[i] = (A_0 + ... + A_{E-1}) / E, grad likewise: members added in member order and divided once, no
+ *                        fused multiply-add anywhere in the product rule or the mean
+ * Pending points: every GP's variance is conditioned on them as in moe_ei_analytic_mcmc (the means are left alone), whichever way
+ * the belief falls.  P_j is BELIEVED FEASIBLE under member e when mu_{e,k}(P_j) <= tau_k for every k; its believed outcome
+ * (mu_{e,1}(P_j), mu_{e,2}(P_j)) is offered to member e's own front, in the order of j and under moe_ehvi_mcmc's join rule, only
+ * where member e believes it feasible: a believed-infeasible point does not shrink the non-dominated region.
+ * factors_out (may be NULL): [E][1 + K][num_points], the values H_e, F_{e,1}, ..., F_{e,K} at every point; value[i] is, bit for bit,
+ * what the rule above makes of them on the host.  With K = 0 the call is moe_ehvi_mcmc bit for bit (factors_out is then its
+ * member_values_out).  A candidate's bits do not depend on how many share the call (passes of moe_ei1_pass_size(N) candidates),
+ * nor on want_grad, nor on ensemble-wide launches (csrc/cehvi1.hip).  No handle is modified.
+ * Errors, in this order, everything that needs no handle before a handle or the device is touched: num_mcmc outside 1 .. 512 ->
+ * MOE_ERR_BOUNDS, payload (num_mcmc, 1, 512); a NULL array (gps, gps2, reference_point, points, value, grad with want_grad, front
+ * with num_front > 0) -> MOE_ERR_RUNTIME; num_constraints outside 0 .. 8 -> MOE_ERR_BOUNDS, payload (num_constraints, 0, 8);
+ * num_mcmc (2 + num_constraints) > 1024 -> MOE_ERR_BOUNDS, payload (num_mcmc, 1, 1024 / (2 + num_constraints) rounded down);
+ * constraint_gps or thresholds NULL with num_constraints > 0 -> MOE_ERR_RUNTIME; a threshold that is not finite ->
+ * MOE_ERR_INVALID_VALUE, payload (the value, k, 0); then moe_ehvi_mcmc's from num_front on, in its order and with its payloads,
+ * "member" counting the GPs flat as e (2 + K) + role (roles 0 and 1: the objectives, role 1 + k: constraint k = 1 .. K): a NULL
+ * handle; a GP of another dim, then of another device; a GP with derivative observations, objective or constraint, payload (its
+ * num_derivatives, 0, the flat index); a handle listed twice, across roles too, payload (the later flat index, the earlier, 0).
+ * MOE_ERR_SINGULAR only for a pending point: payload (the flat index e (2 + K) + role of the first failing GP, the pending point),
+ * reported at the next wait.  A candidate never raises. */
+int moe_ehvi_constrained_mcmc(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* constraint_gps,
+                              int num_constraints, const double* thresholds, int num_mcmc, const double* reference_point,
+                              const double* front, int num_front, const double* points_being_sampled, int num_being_sampled,
+                              const double* points, int num_points, int want_grad, double* value, double* grad, double* factors_out,
+                              moe_error_t* err);
+/* One suggestion by moe_ehvi_constrained_mcmc's objective, the whole loop on the device, as moe_ehvi_mcmc_multistart is for
+ * moe_ehvi_mcmc: the path is, bit for bit, the one a host loop over moe_ehvi_constrained_mcmc walks.  Tensor-product domains only.
+ * With K = 0 the call is moe_ehvi_mcmc_multistart bit for bit.
+ * Errors, in this order: those of moe_ehvi_constrained_mcmc that need no handle (outer, domain_bounds, starts, best_point,
+ * best_value and found among the arrays that must not be NULL; num_starts for num_points); max_num_steps < 1 with
+ * do_gradient_ascent != 0 -> MOE_ERR_BOUNDS; domain_type other than MOE_DOMAIN_TENSOR_PRODUCT -> MOE_ERR_INVALID_VALUE; then those
+ * that need the handles. */
+int moe_ehvi_constrained_mcmc_multistart(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* constraint_gps,
+                                         int num_constraints, const double* thresholds, int num_mcmc, const double* reference_point,
+                                         const double* front, int num_front, const moe_gd_params_t* outer, const double* domain_bounds,
+                                         const double* points_being_sampled, int num_being_sampled, const double* starts,
+                                         int num_starts, int do_gradient_ascent, double* best_point, double* best_value, int* found,
+                                         double* start_values, int* kept_index, double* end_points, double* end_values, double* path,
+                                         int* steps_taken, moe_error_t* err);
+/* num_to_sample points greedily: round t is moe_ehvi_constrained_mcmc_multistart from the same starts with pending points =
+ * points_being_sampled followed by the picks of the rounds before -- bit for bit what num_to_sample calls of that function return
+ * when each is fed its predecessors' points.  Staged once; a round appends ONE row to the extension of each of the E (2 + K) GPs
+ * and offers the pick's believed outcome to the fronts of the members that believe it feasible, inside device memory.
+ * Errors: those of moe_ehvi_constrained_mcmc_multistart, with num_to_sample < 1 or num_being_sampled + num_to_sample - 1 > 64 ->
+ * MOE_ERR_BOUNDS behind num_being_sampled. */
+int moe_ehvi_constrained_mcmc_suggest(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* constraint_gps,
+                                      int num_constraints, const double* thresholds, int num_mcmc, const double* reference_point,
+                                      const double* front, int num_front, const moe_gd_params_t* outer, const double* domain_bounds,
+                                      const double* points_being_sampled, int num_being_sampled, const double* starts, int num_starts,
+                                      int do_gradient_ascent, int num_to_sample, double* best_points, double* best_values, int* found,
+                                      moe_error_t* err);
+/* The constrained expected hypervolume improvement for three objectives: moe_ehvi_constrained_mcmc with moe_ehvi3_mcmc's hypervolume
+ * term in the place of moe_ehvi_mcmc's.  Member e is 3 + K GPs, gps[e], gps2[e], gps3[e] and constraint_gps[e * num_constraints +
+ * k]; reference_point [3], front [num_front][3] and the join rule are moe_ehvi3_mcmc's, H_e is its A_e with its six coefficients
+ * (the same box sum in the same order, the member's box table rebuilt whenever its front changes), and the feasibility factors,
+ * the product rule, the ensemble mean, the believed-feasible rule for pending points and factors_out [E][1 + K][num_points] are
+ * moe_ehvi_constrained_mcmc's.  With K = 0 the call is moe_ehvi3_mcmc bit for bit.
+ * Errors: moe_ehvi_constrained_mcmc's, in its order, with moe_ehvi3_mcmc's limits and checks where that has moe_ehvi_mcmc's:
+ * num_mcmc outside 1 .. 341, payload (num_mcmc, 1, 341); gps3 among the arrays that must not be NULL; num_mcmc (3 +
+ * num_constraints) > 1024 -> MOE_ERR_BOUNDS, payload (num_mcmc, 1, 1024 / (3 + num_constraints) rounded down); num_front outside
+ * 0 .. 192; the canonical order; "member" counting the GPs flat as e (3 + K) + role (roles 0 .. 2: the objectives, role 2 + k:
+ * constraint k = 1 .. K). */
+int moe_ehvi3_constrained_mcmc(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* gps3,
+                               const moe_gp_t* const* constraint_gps, int num_constraints, const double* thresholds, int num_mcmc,
+                               const double* reference_point, const double* front, int num_front, const double* points_being_sampled,
+                               int num_being_sampled, const double* points, int num_points, int want_grad, double* value, double* grad,
+                               double* factors_out, moe_error_t* err);
+/* moe_ehvi_constrained_mcmc_multistart with moe_ehvi3_constrained_mcmc's objective; with K = 0 moe_ehvi3_mcmc_multistart bit for bit.
+ * Errors: moe_ehvi3_constrained_mcmc's that need no handle, the ascent's parameters, then those that need the handles. */
+int moe_ehvi3_constrained_mcmc_multistart(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* gps3,
+                                          const moe_gp_t* const* constraint_gps, int num_constraints, const double* thresholds,
+                                          int num_mcmc, const double* reference_point, const double* front, int num_front,
+                                          const moe_gd_params_t* outer, const double* domain_bounds, const double* points_being_sampled,
+                                          int num_being_sampled, const double* starts, int num_starts, int do_gradient_ascent,
+                                          double* best_point, double* best_value, int* found, double* start_values, int* kept_index,
+                                          double* end_points, double* end_values, double* path, int* steps_taken, moe_error_t* err);
+/* moe_ehvi_constrained_mcmc_suggest with moe_ehvi3_constrained_mcmc's objective: num_to_sample points greedily, bit for bit what
+ * num_to_sample calls of moe_ehvi3_constrained_mcmc_multistart return when each is fed its predecessors' points; with K = 0
+ * moe_ehvi3_mcmc_suggest bit for bit.  Errors: those of moe_ehvi3_constrained_mcmc_multistart with moe_ehvi3_mcmc_suggest's additions. */
+int moe_ehvi3_constrained_mcmc_suggest(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* gps3,
+                                       const moe_gp_t* const* constraint_gps, int num_constraints, const double* thresholds,
+                                       int num_mcmc, const double* reference_point, const double* front, int num_front,
+                                       const moe_gd_params_t* outer, const double* domain_bounds, const double* points_being_sampled,
+                                       int num_being_sampled, const double* starts, int num_starts, int do_gradient_ascent,
+                                       int num_to_sample, double* best_points, double* best_values, int* found, moe_error_t* err);
 /* compute_grad_variance_of_points -> ComputeGradVarianceOfPoints (gpp_math.cpp:1359-1373); out[num_derivs][m][m][dim] */
 int moe_gp_grad_variance(const moe_gp_t* gp, const double* pts, int num_pts, int num_derivs, double* out, moe_error_t* err);
 /* compute_grad_cholesky_variance_of_points -> ComputeGradCholeskyVarianceOfPoints (gpp_math.cpp:1454-1474) */
