@@ -116,6 +116,13 @@ SIGNATURES = {
                                                        dp, C.c_int, dp, C.c_int, C.c_int, dp, dp, ip, dp, ip, dp, dp, dp, ip, _EP]),
     "moe_ehvi_constrained_mcmc_suggest": (C.c_int, [_GPA, _GPA, _GPA, C.c_int, dp, C.c_int, dp, dp, C.c_int, C.POINTER(GdParams), dp,
                                                     dp, C.c_int, dp, C.c_int, C.c_int, C.c_int, dp, dp, ip, _EP]),
+    "moe_log_ehvi_constrained_mcmc": (C.c_int, [_GPA, _GPA, _GPA, C.c_int, dp, C.c_int, dp, dp, C.c_int, dp, C.c_int, dp, C.c_int,
+                                                C.c_int, dp, dp, dp, _EP]),
+    "moe_log_ehvi_constrained_mcmc_multistart": (C.c_int, [_GPA, _GPA, _GPA, C.c_int, dp, C.c_int, dp, dp, C.c_int,
+                                                           C.POINTER(GdParams), dp, dp, C.c_int, dp, C.c_int, C.c_int, dp, dp, ip, dp, ip,
+                                                           dp, dp, dp, ip, _EP]),
+    "moe_log_ehvi_constrained_mcmc_suggest": (C.c_int, [_GPA, _GPA, _GPA, C.c_int, dp, C.c_int, dp, dp, C.c_int, C.POINTER(GdParams),
+                                                        dp, dp, C.c_int, dp, C.c_int, C.c_int, C.c_int, dp, dp, ip, _EP]),
     "moe_ehvi3_constrained_mcmc": (C.c_int, [_GPA, _GPA, _GPA, _GPA, C.c_int, dp, C.c_int, dp, dp, C.c_int, dp, C.c_int, dp, C.c_int,
                                              C.c_int, dp, dp, dp, _EP]),
     "moe_ehvi3_constrained_mcmc_multistart": (C.c_int, [_GPA, _GPA, _GPA, _GPA, C.c_int, dp, C.c_int, dp, dp, C.c_int,

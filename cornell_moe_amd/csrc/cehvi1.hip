@@ -5,7 +5,8 @@
 // and ninth client of kg1_ascent.hip's staging, ascent and drivers.  The sub-member's chain, layout and check are ehvi1.hip's
 // (ehvi1.hpp); the fronts, the strip kernel (M = 2) and the table and box kernels (M = 3) are ehvi1.hip's and ehvi3.hip's, launched
 // through ehvi1.hpp / ehvi3.hpp over a table of the objective sub-members alone; this file keeps the believed-feasibility kernel,
-// the feasibility kernel, the combine kernel and the description of the call (cehvi1_call, cehvi3_call).
+// the feasibility kernel, the combine kernel and the description of the call (cehvi1_call, cehvi3_call).  logehvi1.hip, the log form
+// for two objectives, takes the call's record, its layout and the same description under another combine hook (cehvi1.hpp).
 //
 // Minimisation.  A call takes E joint hyper-samples, M in {2, 3} objectives and K constraints, 1 <= K <= 8 here (K = 0 is the
 // unconstrained client itself).  Member e is M + K GPs, the E (M + K) GPs being the SUB-MEMBERS of one Kg1Ensemble ordered
@@ -40,6 +41,7 @@
 #include <cmath>
 
 #include "acq1_device.hpp"
+#include "cehvi1.hpp"
 #include "ehvi1.hpp"
 #include "ehvi3.hpp"
 #include "kg1_ascent.hpp"
@@ -48,27 +50,6 @@ namespace moe {
 
 namespace {
 
-struct CehviTau {
-  double t[kCeiMaxConstraints];
-};
-
-// what the hooks need of the call (Kg1Objective::client)
-struct CehviCall {
-  int M, K;
-  CehviTau tau;
-  Ehvi1Call c2;  // M = 2
-  Ehvi3Call c3;  // M = 3
-};
-
-// The call's device memory inside the first GP's ehviD, in doubles: the unconstrained client's block first (l2 or l3), then the
-// table of the objective sub-members' dKg [E][M] (pointers), the believed-feasibility words [E][mask_ld] (integers), the
-// feasibility kernel's [E][K][C][F, dF/dmu, dF/dvar] and the group values [E][1 + K][C].
-struct CehviLayout {
-  int E, M, K, C, mask_ld;
-  Ehvi1Layout l2;
-  Ehvi3Layout l3;
-  size_t oObj, oMask, oFeas, oFactors, total;
-};
 CehviLayout layout_of(const Kg1Ensemble& T) {
   const CehviCall& k = *static_cast<const CehviCall*>(T.client);
   CehviLayout l = {};
@@ -311,6 +292,17 @@ CehviCall constraints_of(int M, int num_constraints, const double* thresholds) {
 }
 
 }  // namespace
+
+// what logehvi1.hip takes (cehvi1.hpp)
+CehviLayout cehvi_layout(const Kg1Ensemble& T) { return layout_of(T); }
+
+CehviCall cehvi_constraints_of(int M, int num_constraints, const double* thresholds) { return constraints_of(M, num_constraints, thresholds); }
+
+Kg1Call cehvi_call_combined_by(int num_mcmc, const CehviCall& c, void (*combine_by)(const Kg1Ensemble& T, int C, double* value_out, double* grad_out)) {
+  Kg1Call call = constrained_call(num_mcmc, c);
+  call.o.combine = combine_by;
+  return call;
+}
 
 Kg1Call cehvi1_call(int num_mcmc, int num_constraints, const double* thresholds, const double* reference_point, const double* front,
                     int num_front) {

@@ -9,7 +9,9 @@
 // the constrained expected improvement: cei1.hip's groups under a log-sum-exp, taken with groups of one GP too) and ehvi3.hip (the
 // three-objective expected hypervolume improvement: groups of three GPs, a front and its box table per group) and cehvi1.hip (the
 // constrained expected hypervolume improvement for two and for three objectives, the eighth and ninth client: groups of M + K GPs,
-// ehvi1.hip's or ehvi3.hip's front and kernels over the objective GPs, times cei1.hip's probabilities of feasibility).
+// ehvi1.hip's or ehvi3.hip's front and kernels over the objective GPs, times cei1.hip's probabilities of feasibility) and logehvi1.hip
+// (the log of the two-objective constrained expected hypervolume improvement, the tenth: cehvi1.hip's groups and fronts under a
+// log-sum-exp over the strips and over the members, taken with K = 0 too).
 #pragma once
 #include <memory>
 #include <vector>
@@ -123,7 +125,7 @@ struct Kg1Call {
   std::shared_ptr<const void> client;
   void (*check_members)(const Kg1Objective& o, const std::vector<GpDev*>& gps, int pending_room) = nullptr;
 };
-// The nine clients' descriptions, one function each (the caller has made the checks that need no handle; the arrays are the
+// The ten clients' descriptions, one function each (the caller has made the checks that need no handle; the arrays are the
 // caller's and outlive the call).  gp.hpp says what the arguments are.
 Kg1Call kg1_call(int num_fidelity, const double* discrete_all, const int* num_discrete, const double* best_so_far);  // kg1_opt.hip
 Kg1Call ei1_call(const double* best_so_far);                                                                       // ei1.hip
@@ -137,6 +139,9 @@ Kg1Call cehvi1_call(int num_mcmc, int num_constraints, const double* thresholds,
                     int num_front);  // cehvi1.hip
 Kg1Call cehvi3_call(int num_mcmc, int num_constraints, const double* thresholds, const double* reference_point, const double* front,
                     int num_front);  // cehvi1.hip
+// (K = 0 is taken by the log form itself)
+Kg1Call logehvi1_call(int num_mcmc, int num_constraints, const double* thresholds, const double* reference_point, const double* front,
+                      int num_front);  // logehvi1.hip
 
 // what a multistart hands back (all but the first three may be NULL) ...
 struct Kg1MultistartOut {

@@ -1,0 +1,314 @@
+// cornell_moe_amd/csrc/logehvi1.hip -- the LOG of the two-objective expected hypervolume improvement, with 0 to 8 constraints (the log
+// of cehvi1.hip's quantity, in the way of Ament, Daulton, Eriksson, Balandat & Bakshy, "Unexpected improvements to expected
+// improvement", NeurIPS 2023), averaged over a hyper-parameter ensemble, with pending points, its multistart ascent and greedy
+// q-point batches, on the device (moe_log_ehvi_constrained_mcmc, moe_log_ehvi_constrained_mcmc_multistart,
+// moe_log_ehvi_constrained_mcmc_suggest): the tenth client of kg1_ascent.hip's staging, ascent and drivers.  The sub-member's chain,
+// layout and check are ehvi1.hip's (ehvi1.hpp); the fronts kept per member in device memory, the join rule, the believed-feasibility
+// mask, the pending-row extension and the greedy batch's hand-over of a pick are cehvi1.hip's (cehvi1.hpp), K = 0 included; this file
+// keeps the log-strip kernel, the log-feasibility kernel, the combine kernel and the description of the call (logehvi1_call).
+//
+// Why.  A member's plain value is a product of two psi factors and K probabilities of feasibility in float64: psi_1 or psi_2 is
+// exactly 0 wherever the candidate's mean lies a few dozen deviations above the reference point in either objective, Phi from 38
+// deviations down, and every start of an ascent then ties at 0 with a zero gradient.  The log is finite with a useful gradient for
+// every finite input.
+//
+// Minimisation.  E joint hyper-samples; member e is 2 + K GPs (roles 0, 1 the objectives, role 1 + k constraint k, satisfied where
+// c_k(x) <= tau_k), 0 <= K <= 8, the E (2 + K) GPs the SUB-MEMBERS of one Kg1Ensemble ordered [e][role].  r = (r1, r2) is the
+// reference point; a member's front is F' points u_1 < ... < u_F' < r1, r2 > v_1 > ... > v_F'; u_0 = -infinity, u_{F'+1} = r1,
+// v_0 = r2.  Every sub-member runs ehvi1_eval_points and leaves [mu | var] and [grad mu | grad var].  ONE variance floor for value and
+// gradient, sigma = sqrt(max(150 eps^2, var)) (logcei1.hip's).  For objective role r and an edge t:
+//   z = (t - mu_r) / sigma_r,  (log h, lam, kap) = log_h_parts(z),  lambda_r(t) = log sigma_r + log h = log psi_r(t)
+//   lambda_1(-infinity) = -infinity with lam = kap = 0
+// Strip i = 0 .. F', a = u_i, b = u_{i+1}:
+//   D = lambda_1(a) - lambda_1(b),  rho = exp(D) in [0, 1]
+//   one_minus = 1 - rho (rho <= 1/2) or -expm1(D) (above);  log Delta = lambda_1(b) + log1p(-rho) or lambda_1(b) + log(-expm1(D))
+//   l_i = log Delta + lambda_2(v_i)
+//   dl/dmu_1 = -(lam_b - rho lam_a) / (sigma_1 one_minus),  dl/dvar_1 = (kap_b - rho kap_a) / (2 sigma_1^2 one_minus)
+//   dl/dmu_2 = -lam(v_i) / sigma_2,                          dl/dvar_2 = kap(v_i) / (2 sigma_2^2)
+//   a strip whose edges do not give lambda_1(a) < lambda_1(b) in float64 (rho = 1: neighbours an ulp apart) carries weight 0 and its
+//   terms are skipped, not evaluated: no 0 / 0.  Strip 0 always counts (its left edge is -infinity), so a member's sum is positive.
+// Member:  L_e = log sum_i exp l_i, its four coefficients c = (sum_i w_i dl_i/d.) / W_e.  L_e is never clipped: no "S <= 0" branch.
+//   log F_{e,k} = log Phi(z), z = (tau_k - mu) / sigma: log_cdf_parts, r = phi / Phi,
+//                 d/dmu = -r / sigma,  d/dvar = -r z / (2 sigma^2)                                    (logcei1.hip's role-k form)
+//   LL_e = L_e + log F_{e,1} + ... + log F_{e,K}                                                      added in that order
+//   g_e  = ((c_mu1 grad mu_1 + c_var1 grad var_1) + c_mu2 grad mu_2) + c_var2 grad var_2, then + grad log F_{e,k}, k = 1 .. K
+// Ensemble (logcei1_combine_kernel's rule):
+//   m = max_e LL_e,  w_e = exp(LL_e - m),  W = w_0 + ... + w_{E-1} in member order
+//   value = m + log W - log E,  grad = (w_0 g_0 + ... + w_{E-1} g_{E-1}) / W
+// every operation rounded by itself, no atomics.  With E = 1 the value is LL_0 bit for bit (w = 1, W = 1, log 1 = 0).
+//
+// Log-strip kernel and its REDUCTION ORDER.  ehvi1_strip_kernel's grid: one workgroup of four wavefronts per (four candidates,
+// member), the member's front in LDS once (16 KiB at cap 1024, nothing else: eight workgroups fit a CU's 160 KiB), a wavefront serves
+// one candidate.  Lane l of sweep s owns strip i = 64 s + l: it computes lambda_1, lam, kap at the strip's RIGHT edge once and takes
+// the left edge's from lane l - 1 (lane 0: from lane 63 of the sweep before; -infinity, 0, 0 for strip 0), and lambda_2, lam, kap at
+// v_i.  The log-sum-exp is a PER-LANE RUNNING MAXIMUM: every lane keeps (m, W, S_1 .. S_4) over its own strips, sweep after sweep in
+// ascending s -- a strip above the lane's maximum rescales (W, S) by exp(m - l_i) and enters with weight 1, one below enters with
+// weight exp(l_i - m) -- and the lanes' records are then merged by the fixed butterfly (xor 32, 16, 8, 4, 2, 1): the merged maximum is
+// the larger one, the two records are scaled by exp(m_own - m) and exp(m_other - m), multiplied out first and then added, so that
+// both lanes of a pair hold the same bits; a record that holds no strip (m = -infinity) yields to the other.  Lane 0 writes
+// L_e = m + log W and S / W.  The order depends on F' alone: not on the candidates that share the launch, not on want_grad (m and W
+// do not see the flag), not on ensemble-wide launches (the strip, feasibility and combine kernels are never recorded).
+//
+// The group values of the evaluator are [E][1 + K][C]: L_e, log F_{e,1} .. log F_{e,K}, from which the value is the rule above.
+//
+// Limits: the plain form's -- F <= 960 and at most 64 pending points, so cap <= 1024; E <= 512 and E (2 + K) <= 1024; no derivative
+// observations.  A candidate never raises; only a pending point whose Schur pivot fails does, payload (the flat index e (2 + K) +
+// role, the point).
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+
+#include "acq1_device.hpp"
+#include "cehvi1.hpp"
+#include "ehvi1.hpp"
+#include "kg1_ascent.hpp"
+
+namespace moe {
+
+namespace {
+
+constexpr int kLogEhviCap = kEhviMaxFront + kKg1MaxPending;  // a member's front at its largest
+
+// a lane's log-sum-exp over the strips it has seen: their maximum, the weights' sum and the four weighted derivative sums
+struct LogStripRecord {
+  double m, W, S[4];
+};
+
+// the record takes a strip of log l with derivatives dl (the header's rule)
+__device__ __forceinline__ void record_take(LogStripRecord& a, double l, const double* dl, bool wg) {
+#pragma clang fp contract(off)
+  if (l > a.m) {
+    const double sc = exp(a.m - l);  // (exp(-infinity) = 0 for the first strip, W and S being 0)
+    a.W = a.W * sc + 1.0;
+    if (wg) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) a.S[q] = a.S[q] * sc + dl[q];
+    }
+    a.m = l;
+  } else {
+    const double w = exp(l - a.m);
+    a.W = a.W + w;
+    if (wg) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) a.S[q] = a.S[q] + w * dl[q];
+    }
+  }
+}
+
+// one butterfly step: the lane's record and its partner's become their merge, the same bits in both lanes
+__device__ __forceinline__ void record_merge(LogStripRecord& a, int off, bool wg) {
+#pragma clang fp contract(off)
+  LogStripRecord b;
+  b.m = __shfl_xor(a.m, off, 64);
+  b.W = __shfl_xor(a.W, off, 64);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) b.S[q] = __shfl_xor(a.S[q], off, 64);
+  if (b.m == -INFINITY) return;  // (the partner holds no strip; it takes this lane's record below)
+  if (a.m == -INFINITY) {
+    a = b;
+    return;
+  }
+  const double m = fmax(a.m, b.m);
+  const double ea = exp(a.m - m), eb = exp(b.m - m);
+  const double wa = a.W * ea, wb = b.W * eb;
+  a.W = wa + wb;
+  if (wg) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const double sa = a.S[q] * ea, sb = b.S[q] * eb;
+      a.S[q] = sa + sb;
+    }
+  }
+  a.m = m;
+}
+
+// The log strip sums (the header's reduction order).  Grid (ceil(C / 4), E), four wavefronts, one candidate each; kg: the objective
+// sub-members' [mu Cs | var Cs] ordered [e][2]; fronts / counts as ehvi1_front_kernel leaves them; vals [E][Cs] takes L_e and, with
+// want_grad, coef [E][Cs][4] takes dL/dmu_1, dL/dvar_1, dL/dmu_2, dL/dvar_2.
+__global__ __launch_bounds__(256) void logehvi1_strip_kernel(int C, int Cs, const double* const* __restrict__ kg, const double* __restrict__ fronts, int cap, const int* __restrict__ counts, double r1, double r2, int want_grad, double* __restrict__ vals, double* __restrict__ coef) {
+#pragma clang fp contract(off)
+  __shared__ double s_u[kLogEhviCap], s_v[kLogEhviCap];
+  const int e = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+  const int n = min(counts[e], min(cap, kLogEhviCap));
+  const double* fu = fronts + (size_t)e * 2 * cap;
+  const double* fv = fu + cap;
+  for (int i = tid; i < n; i += 256) {
+    s_u[i] = fu[i];
+    s_v[i] = fv[i];
+  }
+  __syncthreads();
+  const int c = blockIdx.x * 4 + (tid >> 6);
+  if (c >= C) return;
+  const bool wg = want_grad != 0;
+  const double mu1 = kg[2 * e][c], var1 = kg[2 * e][(size_t)Cs + c];
+  const double mu2 = kg[2 * e + 1][c], var2 = kg[2 * e + 1][(size_t)Cs + c];
+  const double s1 = sqrt(fmax(kMinVarGradEI, var1)), s2 = sqrt(fmax(kMinVarGradEI, var2));
+  const double ls1 = log(s1), ls2 = log(s2);
+  LogStripRecord rec = {-INFINITY, 0.0, {0.0, 0.0, 0.0, 0.0}};
+  double carryL = -INFINITY, carryM = 0.0, carryK = 0.0;  // the left edge of strip 0: lambda_1(-infinity)
+  for (int s0 = 0; s0 <= n; s0 += 64) {
+    const int i = s0 + lane;
+    const bool active = i <= n;
+    double lb = 0.0, lamb = 0.0, kapb = 0.0, lq = 0.0, lamq = 0.0, kapq = 0.0;
+    if (active) {
+      double lh;
+      log_h_parts(((i < n ? s_u[i] : r1) - mu1) / s1, lh, lamb, kapb);
+      lb = ls1 + lh;
+      log_h_parts(((i == 0 ? r2 : s_v[i - 1]) - mu2) / s2, lh, lamq, kapq);
+      lq = ls2 + lh;
+    }
+    double la = __shfl_up(lb, 1, 64), lama = __shfl_up(lamb, 1, 64), kapa = __shfl_up(kapb, 1, 64);
+    if (lane == 0) {
+      la = carryL;
+      lama = carryM;
+      kapa = carryK;
+    }
+    carryL = __shfl(lb, 63, 64);
+    carryM = __shfl(lamb, 63, 64);
+    carryK = __shfl(kapb, 63, 64);
+    const double D = la - lb;
+    if (active && D < 0.0) {  // (not so: rho = 1, the strip carries weight 0)
+      const double rho = exp(D);
+      double one_minus, log_one_minus;
+      if (rho <= 0.5) {
+        one_minus = 1.0 - rho;
+        log_one_minus = log1p(-rho);
+      } else {
+        one_minus = -expm1(D);
+        log_one_minus = log(one_minus);
+      }
+      const double l = (lb + log_one_minus) + lq;
+      double dl[4] = {0.0, 0.0, 0.0, 0.0};
+      if (wg) {
+        dl[0] = -(lamb - rho * lama) / (s1 * one_minus);
+        dl[1] = (kapb - rho * kapa) / (2.0 * (s1 * s1) * one_minus);
+        dl[2] = -lamq / s2;
+        dl[3] = kapq / (2.0 * (s2 * s2));
+      }
+      record_take(rec, l, dl, wg);
+    }
+  }
+  #pragma unroll
+  for (int off = 32; off > 0; off >>= 1) record_merge(rec, off, wg);
+  if (lane != 0) return;
+  const size_t o = (size_t)e * Cs + c;
+  vals[o] = rec.m + log(rec.W);
+  if (wg) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) coef[4 * o + q] = rec.S[q] / rec.W;
+  }
+}
+
+// One thread per (member, constraint, candidate): log F and, with want_grad, its derivatives by mu and var (the header's forms)
+// from the constraint sub-member's [mu Cs | var Cs].  kg: the E (2 + K) sub-members'; feas [E][K][Cs][3].
+__global__ __launch_bounds__(256) void logehvi1_feas_kernel(const double* const* __restrict__ kg, int E, int K, const CehviTau tau, int C, int Cs, int want_grad, double* __restrict__ feas) {
+#pragma clang fp contract(off)
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)E * K * C) return;
+  const int c = (int)(i % C);
+  const int ek = (int)(i / C), k = ek % K, e = ek / K;
+  const double* src = kg[(size_t)e * (2 + K) + 2 + k];
+  const double mu = src[c], var = src[(size_t)Cs + c];
+  const double sigma = sqrt(fmax(kMinVarGradEI, var));
+  const double z = (tau.t[k] - mu) / sigma;
+  double l, ratio;
+  log_cdf_parts(z, l, ratio);
+  double* out = feas + 3 * ((size_t)ek * Cs + c);
+  out[0] = l;
+  if (want_grad == 0) return;
+  out[1] = -(ratio / sigma);
+  out[2] = -(ratio * z) / (2.0 * (sigma * sigma));
+}
+
+// candidate c's LL_e: L_e and the K log feasibilities added in the order k = 1 .. K
+__device__ __forceinline__ double logehvi1_member_log(const double* __restrict__ hv, const double* __restrict__ feas, int e, int K, int Cs, long c) {
+#pragma clang fp contract(off)
+  double L = hv[(size_t)e * Cs + c];
+  for (int k = 0; k < K; ++k) L = L + feas[3 * (((size_t)e * K + k) * Cs + c)];
+  return L;
+}
+
+// The log-sum-exp over the members, one thread per output element (logcei1_combine_kernel's shape and rule): element i < nv of
+// value_out (NULL: nv = 0) is candidate i's value, the elements behind are grad_out's (c, j).  hv [E][Cs] and coef [E][Cs][4]: the
+// log-strip kernel's; feas: logehvi1_feas_kernel's; grads: the E (2 + K) sub-members' [grad mu Cs d | grad var Cs d].  A value thread
+// also leaves its candidate's group values in factors [E][1 + K][Cs].  Every operation rounded by itself, in the header's order; as
+// there a thread works out every member's LL_e twice and nothing is kept between threads.
+__global__ __launch_bounds__(256) void logehvi1_combine_kernel(int E, int K, long C, int Cs, int d, const double* __restrict__ hv, const double* __restrict__ coef, const double* __restrict__ feas, const double* const* __restrict__ grads, double* __restrict__ value_out, double* __restrict__ grad_out, double* __restrict__ factors) {
+#pragma clang fp contract(off)
+  const long nv = value_out != nullptr ? C : 0, ng = grad_out != nullptr ? C * d : 0;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nv + ng) return;
+  const long k = i - nv, c = (i < nv) ? i : k / d;
+  const int G = 2 + K;
+  const size_t gv = (size_t)Cs * d;
+  double m = logehvi1_member_log(hv, feas, 0, K, Cs, c);
+  for (int e = 1; e < E; ++e) m = fmax(m, logehvi1_member_log(hv, feas, e, K, Cs, c));
+  double W = 0.0, sum = 0.0;
+  for (int e = 0; e < E; ++e) {
+    const double w = exp(logehvi1_member_log(hv, feas, e, K, Cs, c) - m);
+    W = (e == 0) ? w : W + w;
+    if (i < nv) {
+      factors[(size_t)e * (1 + K) * Cs + c] = hv[(size_t)e * Cs + c];
+      for (int q = 0; q < K; ++q) factors[((size_t)e * (1 + K) + 1 + q) * Cs + c] = feas[3 * (((size_t)e * K + q) * Cs + c)];
+      continue;
+    }
+    const double* co = coef + 4 * ((size_t)e * Cs + c);
+    const double* g1 = grads[(size_t)e * G];
+    const double* g2 = grads[(size_t)e * G + 1];
+    double g = co[0] * g1[k];
+    const double t1 = co[1] * g1[gv + k];
+    g = g + t1;
+    const double t2 = co[2] * g2[k];
+    g = g + t2;
+    const double t3 = co[3] * g2[gv + k];
+    g = g + t3;
+    for (int q = 0; q < K; ++q) {
+      const double* f = feas + 3 * (((size_t)e * K + q) * Cs + c);
+      const double* gq = grads[(size_t)e * G + 2 + q];
+      const double tm = f[1] * gq[k];
+      const double tv = f[2] * gq[gv + k];
+      const double gF = tm + tv;
+      g = g + gF;
+    }
+    const double term = w * g;
+    sum = (e == 0) ? term : sum + term;
+  }
+  if (i < nv)
+    value_out[i] = m + log(W) - log((double)E);
+  else
+    grad_out[k] = sum / W;
+}
+
+void combine(const Kg1Ensemble& T, int C, double* value_out, double* grad_out) {
+  if (value_out == nullptr && grad_out == nullptr) return;
+  const CehviCall& k = *static_cast<const CehviCall*>(T.client);
+  const CehviLayout l = cehvi_layout(T);
+  if (C < 1 || C > l.C) throw Error(MOE_ERR_RUNTIME, "logehvi1: more candidates than the call was staged for");
+  double* base = T.gps[0]->ehviD.p;
+  const double* const* obj = reinterpret_cast<const double* const*>(base + l.oObj);
+  const bool wg = grad_out != nullptr;
+  MOE_LAUNCH_NOW(logehvi1_strip_kernel, dim3((unsigned)((C + 3) / 4), (unsigned)l.E), dim3(256), 0, T.z, C, l.C, obj,
+                 (const double*)(base + l.l2.oFront), l.l2.cap,reinterpret_cast<const int*>(base + l.l2.oCount), k.c2.r1, k.c2.r2, wg ? 1 : 0,
+                 base + l.l2.oVals, base + l.l2.oCoef);
+  if (l.K > 0) {
+    const long nf = (long)l.E * l.K * C;
+    MOE_LAUNCH_NOW(logehvi1_feas_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, T.z, T.dKgTab, l.E, l.K, k.tau, C, l.C,
+                   wg ? 1 : 0, base + l.oFeas);
+  }
+  const long n = (value_out != nullptr ? (long)C : 0) + (wg ? (long)C * T.d : 0);
+  MOE_LAUNCH_NOW(logehvi1_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, T.z, l.E, l.K, (long)C, l.C, T.d,
+                 (const double*)(base + l.l2.oVals), (const double*)(base + l.l2.oCoef), (const double*)(base + l.oFeas), T.dGradTab,
+                 value_out, grad_out, base + l.oFactors);
+  MOE_HIP_CHECK(hipGetLastError());
+}
+
+}  // namespace
+
+Kg1Call logehvi1_call(int num_mcmc, int num_constraints, const double* thresholds, const double* reference_point, const double* front,
+                      int num_front) {
+  CehviCall c = cehvi_constraints_of(2, num_constraints, thresholds);
+  c.c2 = Ehvi1Call{front, num_front, reference_point[0], reference_point[1]};
+  return cehvi_call_combined_by(num_mcmc, c, combine);
+}
+
+}  // namespace moe

@@ -790,6 +790,60 @@ int moe_ehvi3_constrained_mcmc_suggest(const moe_gp_t* const* gps, const moe_gp_
                                        const moe_gd_params_t* outer, const double* domain_bounds, const double* points_being_sampled,
                                        int num_being_sampled, const double* starts, int num_starts, int do_gradient_ascent,
                                        int num_to_sample, double* best_points, double* best_values, int* found, moe_error_t* err);
+/* The LOG of moe_ehvi_constrained_mcmc's quantity (two objectives, 0 <= K = num_constraints <= 8; K = 0 is the log of
+ * moe_ehvi_mcmc's), computed so that it stays finite with a useful gradient where that value and its gradient are exactly 0 in
+ * float64: psi underflows where a candidate's mean lies a few dozen deviations above the reference point in either objective, Phi
+ * from 38 deviations down.  Arguments, members, fronts, the join rule, the believed-feasible rule for pending points and the limits
+ * are moe_ehvi_constrained_mcmc's.  A member's front is F' points u_1 < ... < u_F' < r1, r2 > v_1 > ... > v_F'; u_0 = -infinity,
+ * u_{F'+1} = r1, v_0 = r2.  ONE variance floor for value and gradient, sigma = sqrt(max(150 eps^2, var)).  For objective r and an
+ * edge t:  z = (t - mu_r) / sigma_r, h(z) = z Phi(z) + phi(z), lam = Phi / h, kap = phi / h,
+ *   lambda_r(t) = log sigma_r + log h(z) = log psi_r(t);  lambda_1(-infinity) = -infinity with lam = kap = 0
+ * (log h, lam and kap as in moe_log_ei_constrained_mcmc: none is the log of a float64 Phi or phi that could have underflowed).
+ *   strip i = 0 .. F'    a = u_i, b = u_{i+1}:  rho_i = exp(lambda_1(a) - lambda_1(b)) in [0, 1],
+ *                        log Delta_i = lambda_1(b) + log(1 - rho_i)  (log1p(-rho) for rho <= 1/2, log(-expm1(lambda_1(a) -
+ *                        lambda_1(b))) above),  l_i = log Delta_i + lambda_2(v_i)
+ *   its derivatives      dl_i/dmu_1 = -(lam_b - rho_i lam_a) / (sigma_1 (1 - rho_i)),  dl_i/dvar_1 = (kap_b - rho_i kap_a) / (2 sigma_1^2
+ *                        (1 - rho_i)),  dl_i/dmu_2 = -lam(v_i) / sigma_2,  dl_i/dvar_2 = kap(v_i) / (2 sigma_2^2); 1 - rho from the same
+ *                        expm1 where rho > 1/2.  A strip whose two edges do not give lambda_1(a) < lambda_1(b) in float64 (rho = 1)
+ *                        carries weight 0 and its terms are skipped, not evaluated.
+ *   hypervolume term     L_e = log sum_i exp l_i as a log-sum-exp whose order depends on F' alone (csrc/logehvi1.hip), its four
+ *                        coefficients (sum_i w_i dl_i/d.) / W_e.  Never clipped: the sum is positive for every finite input.
+ *   feasibility          log F_{e,k} = log Phi(z), z = (tau_k - mu) / sigma, r = phi(z) / Phi(z),
+ *                        grad log F = -(r / sigma) grad mu - (r z / (2 sigma^2)) grad var   (moe_log_ei_constrained_mcmc's role k)
+ *   member               LL_e = L_e + log F_{e,1} + ... + log F_{e,K}, added in that order;  g_e = ((c_mu1 grad mu_1 + c_var1 grad
+ *                        var_1) + c_mu2 grad mu_2) + c_var2 grad var_2, then + grad log F_{e,k} for k = 1 .. K
+ *   ensemble             m = max_e LL_e, w_e = exp(LL_e - m), W = w_0 + ... + w_{E-1} in member order;
+ *                        value[i] = m + log W - log E,  grad = (w_0 g_0 + ... + w_{E-1} g_{E-1}) / W, every operation rounded by
+ *                        itself, no atomics
+ * factors_out (may be NULL): [E][1 + K][num_points], L_e, log F_{e,1}, ..., log F_{e,K} at every point; value[i] is what the rule
+ * above makes of them (with E = 1 their sum, bit for bit).  A candidate's bits do not depend on how many share the call, nor on
+ * want_grad, nor on ensemble-wide launches.  No handle is modified.
+ * Errors: moe_ehvi_constrained_mcmc's, in its order and with its payloads. */
+int moe_log_ehvi_constrained_mcmc(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* constraint_gps,
+                                  int num_constraints, const double* thresholds, int num_mcmc, const double* reference_point,
+                                  const double* front, int num_front, const double* points_being_sampled, int num_being_sampled,
+                                  const double* points, int num_points, int want_grad, double* value, double* grad, double* factors_out,
+                                  moe_error_t* err);
+/* moe_ehvi_constrained_mcmc_multistart with moe_log_ehvi_constrained_mcmc's objective: the same screening, top-20 rule, restarted
+ * ascent and outputs, bit for bit the path a host loop over moe_log_ehvi_constrained_mcmc walks.  Tensor-product domains only.
+ * Errors: that function's, in its order. */
+int moe_log_ehvi_constrained_mcmc_multistart(const moe_gp_t* const* gps, const moe_gp_t* const* gps2,
+                                             const moe_gp_t* const* constraint_gps, int num_constraints, const double* thresholds,
+                                             int num_mcmc, const double* reference_point, const double* front, int num_front,
+                                             const moe_gd_params_t* outer, const double* domain_bounds,
+                                             const double* points_being_sampled, int num_being_sampled, const double* starts,
+                                             int num_starts, int do_gradient_ascent, double* best_point, double* best_value, int* found,
+                                             double* start_values, int* kept_index, double* end_points, double* end_values,
+                                             double* path, int* steps_taken, moe_error_t* err);
+/* moe_ehvi_constrained_mcmc_suggest with moe_log_ehvi_constrained_mcmc's objective: num_to_sample points greedily, bit for bit what
+ * num_to_sample calls of moe_log_ehvi_constrained_mcmc_multistart return when each is fed its predecessors' points.  Errors: that
+ * function's, in its order. */
+int moe_log_ehvi_constrained_mcmc_suggest(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* constraint_gps,
+                                          int num_constraints, const double* thresholds, int num_mcmc, const double* reference_point,
+                                          const double* front, int num_front, const moe_gd_params_t* outer,
+                                          const double* domain_bounds, const double* points_being_sampled, int num_being_sampled,
+                                          const double* starts, int num_starts, int do_gradient_ascent, int num_to_sample,
+                                          double* best_points, double* best_values, int* found, moe_error_t* err);
 /* compute_grad_variance_of_points -> ComputeGradVarianceOfPoints (gpp_math.cpp:1359-1373); out[num_derivs][m][m][dim] */
 int moe_gp_grad_variance(const moe_gp_t* gp, const double* pts, int num_pts, int num_derivs, double* out, moe_error_t* err);
 /* compute_grad_cholesky_variance_of_points -> ComputeGradCholeskyVarianceOfPoints (gpp_math.cpp:1454-1474) */
