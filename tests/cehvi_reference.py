@@ -18,6 +18,7 @@ Every GP's variance is conditioned on every pending point, whichever way the bel
 scale = max(1, |r_k|, max |y|, sqrt(alpha)) over the member's M + K GPs; an ensemble takes its largest member scale.
 """
 import collections
+import copy
 import math
 
 import numpy as np
@@ -218,11 +219,55 @@ MARGIN = 0.05
 _BELIEVED_OBJECTIVE = ((-0.3, 0.7, 0.5), (0.25, -0.4, 0.6))
 _BELIEVED_CONSTRAINT = ((-0.5, -0.5, -0.5), (-0.5, 0.5, -0.5))
 
-ALL_CASES = CASES + [BELIEVED2, BELIEVED3]
+# E >= 2 members and K >= 2 constraints TOGETHER, so that no [e][k] stride collapses (with E = 1 the term e K vanishes, with K = 1
+# it equals e): row counts that differ per role and member, the padded-16 gradient kernel (d = 13), thresholds that are all
+# distinct.  tests/test_cehvi_reference.py asserts that exchanging two constraint GPs within a member, the two members' GPs of one
+# constraint, or two thresholds each moves the value by at least SWAP_MOVES scale at every checked candidate.
+EDGE_TAUS = {2: (0.1, -0.05), 8: (0.2, 0.25, 0.3, 0.35, 0.4, 0.45, 0.5, 0.55)}
+MIXED2 = Case("m2_e2_k2_d13_n20_130_40_p3_f10", 541, 2, 2, 2, 13, ((20, 130, 40, 20), (130, 20, 20, 40)), 3, 10, EDGE_TAUS[2], 8,
+              None, 2.6e-16)
+MIXED3 = Case("m3_e2_k2_d13_n20_130_40_p3_f20", 542, 3, 2, 2, 13, ((20, 130, 40, 20, 130), (130, 20, 20, 40, 20)), 3, 20, EDGE_TAUS[2], 8,
+              None, 9.7e-16)
+MIXED2_K8 = Case("m2_e2_k8_d3_n20_p3_f10", 1543, 2, 2, 8, 3, _grid(2, 10, 20), 3, 10, EDGE_TAUS[8], 8, (0, 1, 2, 3, 4, 5, 6), 1.8e-15)
+MIXED = {2: MIXED2, 3: MIXED3}
+SWAP_MOVES = 1e-6       # (10^4 times the GPU bound)
+FACTORS_APART = 1e-3
+# The constraint roles' variance floors, E = 1, K = 2: constraint 1's GP is noise free and candidates 0 and 1 lie on two of its
+# sampled points, whose observations are set by hand FLOOR_GAP below and above tau_1 -- there F_1 is exactly 1 and exactly 0 (the
+# value floor DBL_MIN under a mean FLOOR_GAP from tau) and its gradient exactly 0 (the gradient floor 150 eps^2).  Candidate 1,
+# whose value is 0, is the one candidate the qualification leaves out.
+FLOOR2 = Case("m2_e1_k2_d3_n20_p3_f2_floor", 51, 2, 1, 2, 3, _grid(1, 4, 20), 3, 2, TAUS[2], 8, (0, 2, 3, 4, 5, 6, 7), 4.3e-15)
+FLOOR3 = Case("m3_e1_k2_d3_n20_p3_f2_floor", 52, 3, 1, 2, 3, _grid(1, 5, 20), 3, 2, TAUS[2], 8, (0, 2, 3, 4, 5, 6, 7), 1.3e-14)
+FLOOR = {2: FLOOR2, 3: FLOOR3}
+FLOOR_ROWS, FLOOR_GAP = {2: (16, 12), 3: (5, 0)}, 0.2  # (rows whose float64 variance comes out under the floor)
+
+EDGE_CASES = [MIXED2, MIXED3, MIXED2_K8, FLOOR2, FLOOR3]
+ALL_CASES = CASES + [BELIEVED2, BELIEVED3] + EDGE_CASES
 
 
 def case(name):
     return next(c for c in ALL_CASES if c.name == name)
+
+
+def swapped(p):
+    """the problems that part from p by ONE exchange, as (what, problem): two constraint GPs within a member (neighbours k, k + 1,
+    cyclically), the two members' GPs of one constraint, two thresholds (neighbours, cyclically)"""
+    M, K, out = p.M, len(p.taus), []
+    pairs = [(k, (k + 1) % K) for k in range(K if K > 2 else 1)]
+    for e in range(len(p.gps)):
+        for a, b in pairs:
+            gps = [list(row) for row in p.gps]
+            gps[e][M + a], gps[e][M + b] = gps[e][M + b], gps[e][M + a]
+            out.append(("member %d: constraint GPs %d and %d" % (e, a, b), p._replace(gps=gps)))
+    for k in range(K):
+        gps = [list(row) for row in p.gps]
+        gps[0][M + k], gps[1][M + k] = gps[1][M + k], gps[0][M + k]
+        out.append(("constraint %d: the members' GPs" % k, p._replace(gps=gps)))
+    for a, b in pairs:
+        taus = list(p.taus)
+        taus[a], taus[b] = taus[b], taus[a]
+        out.append(("thresholds %d and %d" % (a, b), p._replace(taus=taus)))
+    return out
 
 
 def make_problem(c):
@@ -233,6 +278,7 @@ def make_problem(c):
     length = LENGTH_0 + LENGTH_D * math.sqrt(c.d)
     Xc = rng.uniform(0, 1, size=(max(max(row) for row in c.n), c.d))
     believed = c.name in (BELIEVED2.name, BELIEVED3.name)
+    floor = c.name in (FLOOR2.name, FLOOR3.name)
     gps = []
     for e in range(c.E):
         row = []
@@ -243,9 +289,14 @@ def make_problem(c):
                 y[:3, 0] = _BELIEVED_OBJECTIVE[e] if r < c.M else _BELIEVED_CONSTRAINT[e]
             f = 1.0 + 0.15 * ((e + 2 * r) % 4)
             hyper = np.array([1.3] + [length] * c.d) * f
-            row.append(GP(MATERN if (e + r) % 2 == 0 else SE, hyper, Xc[:n].copy(), y, [1e-2 * f], ()))
+            noise = 1e-2 * f
+            if floor and r == c.M:
+                y[FLOOR_ROWS[c.M][0], 0], y[FLOOR_ROWS[c.M][1], 0], noise = c.tau[0] - FLOOR_GAP, c.tau[0] + FLOOR_GAP, 0.0
+            row.append(GP(MATERN if (e + r) % 2 == 0 else SE, hyper, Xc[:n].copy(), y, [noise], ()))
         gps.append(row)
     points = rng.uniform(0.1, 0.9, size=(c.C, c.d))
+    if floor:
+        points[0], points[1] = Xc[FLOOR_ROWS[c.M][0]], Xc[FLOOR_ROWS[c.M][1]]
     pending = rng.uniform(0, 1, size=(c.p, c.d))
     if c.p:
         pending[0] = points[0] + rng.uniform(-0.05, 0.05, size=c.d)
@@ -262,6 +313,140 @@ def make_problem(c):
     return Problem(c.name, c.M, gps, list(c.tau), REF2 if c.M == 2 else REF3, np.ascontiguousarray(front), points, pending, checked)
 
 
+# A belief that CHANGES along a greedy batch, E = 2, K = 1, tau = 0: member 0's constraint GP observes values about -0.6 (it believes
+# every point feasible); member 1's observes CHANGING_SLOPE (0.5 - x_0) under length scales that span the cube, so that its mean
+# falls through tau at x_0 = 0.5 -- it believes a point infeasible to the left and feasible to the right.  The one pending point
+# lies on the left, the starts in two clusters, one on each side.  Each pick's mask word is written at another relative index and
+# must be worked out anew: a device that kept the pending point's word for every pick computes `stale`'s value.
+CHANGING = {2: Case("m2_e2_k1_d3_n20_p1_f3_changing", 71, 2, 2, 1, 3, _grid(2, 3, 20), 1, 3, (0.0,), 8, None, 0.0),
+            3: Case("m3_e2_k1_d3_n20_p1_f4_changing", 72, 3, 2, 1, 3, _grid(2, 4, 20), 1, 4, (0.0,), 8, None, 0.0)}
+CHANGING_SLOPE, CHANGING_Q = 3.0, {2: 4, 3: 3}
+
+
+def changing_problem(M):
+    """(problem, starts [12][3]) of CHANGING[M]"""
+    c = CHANGING[M]
+    p = make_problem(c._replace(name=BELIEVED[M].name))  # (BELIEVED's front and observations at the three shared points)
+    rng = np.random.default_rng(12400 + c.seed)
+    gps = []
+    for e, row in enumerate(p.gps):
+        con = row[M]
+        X = np.asarray(con.X)
+        if e == 0:
+            y = -0.6 + 0.05 * rng.normal(size=(len(X), 1))
+            gps.append(list(row[:M]) + [GP(con.cov_type, con.hyper, con.X, y, con.noise, ())])
+        else:
+            y = CHANGING_SLOPE * (0.5 - X[:, :1]) + 0.01 * rng.normal(size=(len(X), 1))
+            gps.append(list(row[:M]) + [GP(SE, np.array([2.0, 1.5, 3.0, 3.0]), con.X, y, [1e-3], ())])
+    pending = np.array([[0.2, 0.5, 0.5]])
+    starts = np.vstack([rng.uniform([0.08, 0.1, 0.1], [0.32, 0.9, 0.9], size=(6, 3)), rng.uniform([0.68, 0.1, 0.1], [0.92, 0.9, 0.9], size=(6, 3))])
+    return p._replace(name=c.name, gps=gps, pending=pending), starts
+
+
+def remasked(m, mask, front):
+    """member m under ANOTHER believed-feasibility mask [p] than its own, from the caller's front: what its front would be under
+    the other decisions"""
+    n = copy.copy(m)
+    n.mask = np.asarray(mask, dtype=bool)
+    n.offered = [o for o, ok in zip(n.outcomes, n.mask) if ok]
+    n.front, n.log = (hr.believed_front if m.M == 2 else h3.believed_front)(front, n.offered, n.ref, n.T)
+    n.table = h3.box_table(n.front) if m.M == 3 else None
+    return n
+
+
+# Sixty-four pending points under a MIXED mask, E = 5, K = 1, tau = 0: cehvi_believed_kernel over 5 x 64 threads (a second
+# workgroup) with a mask row of 64 words, and the front kernels' masked `continue` in front of evictions past index 64 and, for
+# M = 3, of a table rebuild.  The pending points lie on the line x_0 = 0.1 .. 0.9 through the middle of the cube and every GP
+# observes about 20 points scattered 0.02 about that line: objective 1 rises and objective 2 falls along it, both carry a common
+# wave g (where g < 0 the believed outcome lies below the caller's front u + v = 0 and evicts the points about it, where g > 0 it
+# is dominated; on g's rising flanks an outcome dominates the ones that follow it); each member's constraint observes a wave of
+# another period whose phase moves with the member, so that the members skip different outcomes.  Not among ALL_CASES (p = 64).
+MASKED = {2: Case("m2_e5_k1_d3_n20_p64_f200_masked", 81, 2, 5, 1, 3, ((20, 19, 21), (21, 20, 19), (19, 21, 20), (20, 21, 19), (19, 20, 21)),
+                  64, 200, (0.0,), 8, None, 8.3e-15),
+          3: Case("m3_e5_k1_d3_n20_p64_f100_masked", 82, 3, 5, 1, 3, ((20, 19, 21, 20), (21, 20, 19, 21), (19, 21, 20, 19), (20, 21, 19, 20),
+                  (19, 20, 21, 21)), 64, 100, (0.0,), 8, None, 2.1e-14)}
+
+
+MASKED_WAVE = {2: 0.06, 3: 0.12}  # (M = 2: the members' fronts keep 130 to 160 of the 200 points, three sweeps of strips)
+
+
+def masked_problem(M):
+    c = MASKED[M]
+    rng = np.random.default_rng(12400 + c.seed)
+    wave = lambda x0, e: MASKED_WAVE[M] * np.sin(2.0 * np.pi * 4.0 * x0 + 0.3 * e)  # noqa: E731
+    gps = []
+    for e in range(c.E):
+        row = []
+        for r in range(M + 1):
+            n = c.n[e][r]
+            X = np.stack([np.linspace(0.02, 0.98, n) + 0.01 * rng.normal(size=n), 0.5 + 0.02 * rng.normal(size=n),
+                          0.5 + 0.02 * rng.normal(size=n)], axis=1)
+            x0 = X[:, 0]
+            if r == 0:
+                y = (x0 - 0.5) + wave(x0, e)
+            elif r == 1:
+                y = -(x0 - 0.5) + wave(x0, e)
+            elif r < M:
+                y = 0.3 * (x0 - 0.5) + 0.02 * np.cos(2.0 * np.pi * 2.0 * x0 + e)  # (rising, so that an outcome can dominate a later one)
+            else:
+                y = 0.5 * np.sin(2.0 * np.pi * 2.5 * x0 + 2.0 * np.pi * e / c.E)
+            f = 1.0 + 0.1 * ((e + 2 * r) % 4)
+            row.append(GP(MATERN if (e + r) % 2 == 0 else SE, np.array([1.0 * f, 0.1 * f, 1.0, 1.0]), X, y.reshape(-1, 1), [1e-3 * f], ()))
+        gps.append(row)
+    pending = np.full((c.p, 3), 0.5)
+    pending[:, 0] = np.linspace(0.1, 0.9, c.p)
+    u = np.linspace(-0.55, 0.55, c.F) + rng.uniform(-0.001, 0.001, size=c.F)
+    if M == 2:
+        front = np.stack([u, -u], axis=1)
+    else:
+        front = h3.canonical(np.stack([u, -u, rng.uniform(-0.3, 0.3, size=c.F)], axis=1))
+    points = np.stack([rng.uniform(0.1, 0.9, size=c.C), rng.uniform(0.2, 0.8, size=c.C), rng.uniform(0.2, 0.8, size=c.C)], axis=1)
+    return Problem(c.name, M, gps, list(c.tau), REF2 if M == 2 else REF3, np.ascontiguousarray(front), points, pending, tuple(range(c.C)))
+
+
+def dominates(a, b):
+    return all(float(x) <= float(y) for x, y in zip(a, b))
+
+
+def mask_effects(m, caller_front):
+    """what member m's mask does to its front, for the qualification of MASKED: (the offered outcomes that evict a front point whose
+    index, in the front as they meet it, is 64 or more; the skipped outcomes j that would have joined the front as it stood when
+    their turn came and that dominate an outcome offered after them)"""
+    rule = hr.believed_front if m.M == 2 else h3.believed_front
+    evicting, missed = [], []
+    offered_before = []
+    for j, (o, ok) in enumerate(zip(m.outcomes, m.mask)):
+        before, _ = rule(caller_front, offered_before, m.ref, m.T)
+        before = np.asarray(before, dtype=np.float64).reshape(-1, m.M)
+        joins = all(float(o[k]) < m.ref[k] for k in range(m.M)) and not any(dominates(q, o) for q in before)
+        if ok:
+            if joins and any(dominates(o, q) for q in before[64:]):
+                evicting.append(j)
+            offered_before.append(o)
+        elif joins and any(m.mask[t] and dominates(o, m.outcomes[t]) for t in range(j + 1, len(m.outcomes))):
+            missed.append(j)
+    return evicting, missed
+
+
+# E (M + K) = 1024 exactly, the limit: 128 members of 2 + 6 GPs, the hyper-parameters moving with the member and the role so that
+# no two members agree; six distinct thresholds.  Not one of ALL_CASES (C = 4, p = 1): tests/test_cehvi_reference.py and
+# tests/test_log_ehvi_reference.py measure its float64-against-long-double differences for the plain and the log form.
+LIMIT = Case("m2_e128_k6_d2_n6_p1_f2_limit", 61, 2, 128, 6, 2, _grid(128, 8, 6), 1, 2, (0.25, 0.3, 0.35, 0.4, 0.45, 0.5), 4, None, 2.9e-14)
+LIMIT_MEMBERS = (0, 63, 127)
+
+
+def limit_problem(c=LIMIT):
+    rng = np.random.default_rng(12400 + c.seed)
+    X = rng.uniform(0, 1, size=(c.n[0][0], c.d))
+    ys = [0.3 * rng.normal(size=(len(X), 1)) for _ in range(c.M + c.K)]
+    gps = [[GP(MATERN if (e + r) % 2 == 0 else SE, np.array([1.0 + 0.1 * r + 0.003 * e, 0.35 + 0.001 * e, 0.6 - 0.0007 * e]), X.copy(),
+               ys[r], [1e-2], ()) for r in range(c.M + c.K)] for e in range(c.E)]
+    front = np.array([(-0.4, 0.2), (0.1, -0.3)])
+    points = rng.uniform(0.1, 0.9, size=(c.C, c.d))
+    pending = rng.uniform(0.1, 0.9, size=(c.p, c.d))
+    return Problem(c.name, c.M, gps, list(c.tau), REF2, front, points, pending, tuple(range(c.C)))
+
+
 _WANT = {}
 
 
@@ -269,7 +454,12 @@ def expected(c, T=LD):
     """(problem, [Result per candidate]) in the arithmetic of T, once per process"""
     key = (c.name, T)
     if key not in _WANT:
-        p = make_problem(c)
+        if c.name == LIMIT.name:
+            p = limit_problem(c)
+        elif c.name in (MASKED[2].name, MASKED[3].name):
+            p = masked_problem(c.M)
+        else:
+            p = make_problem(c)
         members = ensemble(p, T)
         _WANT[key] = (p, [evaluate(members, x) for x in p.points])
     return _WANT[key]

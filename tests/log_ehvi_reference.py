@@ -76,6 +76,92 @@ def log_strips(mu1, var1, mu2, var2, front, ref, T=LD):
     return m + np.log(W), c, low, skipped
 
 
+def lane_replay(mu1, var1, mu2, var2, front, ref):
+    """logehvi1_strip_kernel's reduction order replayed in float64 for one member and candidate: strip i belongs to lane i mod 64,
+    the sweeps ascend, a lane's record (m, W) takes its strips by record_take's two branches, and the 64 records merge by the fixed
+    butterfly (xor 32, 16, 8, 4, 2, 1; every pair counted once).  Returns the counts of what ran -- which branch decides nothing
+    about the value, so nothing but such a count shows that a branch was reached:
+        rho_low / rho_high / rho_one   strips with rho <= 1/2, above, and skipped at rho = 1 (with their indices in `skipped_at`)
+        first / rescales / below       record_take: a lane's first strip; later strips above its running maximum (W and S are
+                                       scaled by exp(m - l)); later strips at or below it (weight exp(l - m))
+        later_sweeps                   (rescales, below) counted over the strips of the second and later sweeps alone -- a lane
+                                       whose strip of the first sweep was skipped meets its FIRST strip there, which counts in neither
+        won_low / won_high / empty     merges whose maximum is the lower lane's (ties included) / the upper lane's; merges in which
+                                       a record holds no strip
+        lane_spread / merge_spread     the largest |l - m| a record_take met after a lane's first strip, the largest |m_a - m_b| a
+                                       merge of two records met
+        zero_weights                   the scalings exp(.) of record_take and of the merges that came out exactly 0
+        L                              m + log W of lane 0 at the end: the kernel's value in this order"""
+    T = np.float64
+    front = np.asarray(front, dtype=T).reshape(-1, 2)
+    F = len(front)
+    s1, s2 = np.sqrt(max(T(er.MIN_VAR_GRAD_EI), T(var1))), np.sqrt(max(T(er.MIN_VAR_GRAD_EI), T(var2)))
+    out = dict(rho_low=0, rho_high=0, rho_one=0, skipped_at=[], first=0, rescales=0, below=0, later_sweeps=[0, 0], won_low=0,
+               won_high=0, empty=0, lane_spread=0.0, merge_spread=0.0, zero_weights=0)
+    m, W = [-math.inf] * 64, [0.0] * 64
+    la = T(-np.inf)
+    with np.errstate(over="ignore", under="ignore"):
+        for i in range(F + 1):
+            lb = np.log(s1) + lr.log_h_parts(((front[i, 0] if i < F else T(ref[0])) - T(mu1)) / s1, T)[0]
+            lq = np.log(s2) + lr.log_h_parts(((T(ref[1]) if i == 0 else front[i - 1, 1]) - T(mu2)) / s2, T)[0]
+            D = la - lb
+            la = lb
+            if not D < 0:
+                out["rho_one"] += 1
+                out["skipped_at"].append(i)
+                continue
+            rho = np.exp(D)
+            out["rho_low" if rho <= 0.5 else "rho_high"] += 1
+            l = float((lb + (np.log1p(-rho) if rho <= 0.5 else np.log(-np.expm1(D)))) + lq)
+            lane = i % 64
+            if m[lane] == -math.inf:
+                out["first"] += 1
+                m[lane], W[lane] = l, 1.0
+                continue
+            out["lane_spread"] = max(out["lane_spread"], abs(l - m[lane]))
+            if l > m[lane]:
+                sc = math.exp(m[lane] - l)
+                out["rescales"] += 1
+                out["later_sweeps"][0] += i >= 64
+                m[lane], W[lane] = l, W[lane] * sc + 1.0
+            else:
+                sc = math.exp(l - m[lane])
+                out["below"] += 1
+                out["later_sweeps"][1] += i >= 64
+                W[lane] = W[lane] + sc
+            out["zero_weights"] += sc == 0.0
+    for off in (32, 16, 8, 4, 2, 1):
+        nm, nW = list(m), list(W)
+        for a in range(64):
+            b = a ^ off
+            if a > b:
+                continue
+            if m[a] == -math.inf or m[b] == -math.inf:
+                out["empty"] += 1
+                k = b if m[a] == -math.inf else a
+                nm[a] = nm[b] = m[k]
+                nW[a] = nW[b] = W[k]
+                continue
+            top = max(m[a], m[b])
+            out["won_low" if m[a] >= m[b] else "won_high"] += 1
+            out["merge_spread"] = max(out["merge_spread"], abs(m[a] - m[b]))
+            ea, eb = math.exp(m[a] - top), math.exp(m[b] - top)
+            out["zero_weights"] += (ea == 0.0) + (eb == 0.0)
+            nm[a] = nm[b] = top
+            nW[a] = nW[b] = W[a] * ea + W[b] * eb
+        m, W = nm, nW
+    out["later_sweeps"] = tuple(out["later_sweeps"])
+    out["L"] = m[0] + math.log(W[0])
+    return out
+
+
+def member_replay(m, x):
+    """lane_replay of a float64 ch.Member (M = 2) at x"""
+    assert m.T is np.float64
+    mo = [cr.moments(model, base, x) for model, base in zip(m.models[:2], m.bases[:2])]
+    return lane_replay(mo[0][0], mo[0][1], mo[1][0], mo[1][1], m.front, m.ref)
+
+
 def member_logs(m, x):
     """([L_e, log F_1 .. log F_K], g_e, the four coefficients, the lowest z or strip argument, strips skipped) of a ch.Member (M = 2)
     at x"""
@@ -159,12 +245,40 @@ FLOOR = Case("log_e1_k1_d3_n20_p0_f2_floor", 308, 2, 1, 1, 3, _grid(1, 3, 20), 0
 FLOOR_SHIFTS = ((0.0, 0.0), (0.3, 0.0), (0.6, 2.0))
 
 M2_CASES = [c for c in ch.CASES if c.M == 2]  # (E = 3 with n = (20, 130, 300) at F = 65, K = 1 and d = 10 at F = 2 among them)
-ALL_CASES = M2_CASES + OWN_CASES + [FULL, ULP, FLOOR]
+# cehvi_reference.EDGE_CASES, named one by one: E = 2 with K = 2 (d = 13, rows that differ per role and member) and with K = 8,
+# the thresholds all distinct -- tests/test_log_ehvi_reference.py qualifies them against exchanges of GPs and thresholds
+MIXED = [ch.MIXED2, ch.MIXED2_K8]
+# candidate 0 on a sampled point of the noise-free GP of constraint 1 whose observation lies 0.2 BELOW tau_1: logehvi1_feas_kernel's
+# floor, log F_1 = 0 there.  It is cehvi_reference.FLOOR2 without its candidate on the infeasible side, where the mean lies 1e14
+# floored deviations above tau and log F_1 is of order -1e28 with a derivative by var of order 1e57 against a grad var that is 0
+# up to rounding: float64 and long double do not agree there and the candidate does not qualify (FLOOR_SHIFTS' reason).  A lowered
+# threshold would put candidate 0 on that side, so this case's shifts lower the reference point and the front alone.
+CFLOOR = ch.FLOOR2._replace(name="log_e1_k2_d3_n20_p3_f2_constraint_floor", checked=None, ld_diff=0.0)
+CFLOOR_SHIFTS = ((0.0, 0.0), (3.0, 0.0), (8.0, 0.0))
+# The log-strip kernel's per-lane branches (lane_replay counts them; tests/test_log_ehvi_reference.py asserts the counts), E = 2,
+# K = 1.  LANES: F = 200 and three pending points, four sweeps of a front that differs per member; the objective GPs observe with
+# noise 1e-6 and candidates 0 and 1 lie 0.01 from sampled points, where the deviations are so small that under shift 8 the strips'
+# logs spread by far more than 745 (exp of the difference is exactly 0) within a lane and across a merge.  ULP64: a front of 70
+# whose points 63 and 64 are a unit in the last place apart in u -- the rho = 1 strip is strip 64, lane 0 of the second sweep,
+# whose left edge comes through the carry.  ULP_LAST: F = 64 and u_63 a unit in the last place below r1 -- the rho = 1 strip is the
+# last one, the second sweep's only strip.
+LANES = Case("log_e2_k1_d3_n20_p3_f200_lanes", 311, 2, 2, 1, 3, _grid(2, 3, 20), 3, 200, ch.TAUS[1], 5, None, 0.0)
+ULP64 = Case("log_e2_k1_d3_n20_p0_f70_ulp64", 312, 2, 2, 1, 3, _grid(2, 3, 20), 0, 70, ch.TAUS[1], 5, None, 0.0)
+ULP_LAST = Case("log_e2_k1_d3_n20_p0_f64_ulp_last", 313, 2, 2, 1, 3, _grid(2, 3, 20), 0, 64, ch.TAUS[1], 5, None, 0.0)
+LANE_CASES = [LANES, ULP64, ULP_LAST]
+LANES_NOISE, LANES_OFFSET, LANES_ROWS = 1e-6, 0.01, (3, 7)
+# A member whose weight underflows, E = 2, K = 1: member 1's constraint GP observes values HOPELESS_LEVEL above tau with noise 1e-2
+# under length scales that span the cube, so that its log feasibility lies more than 800 below member 0's total at every candidate
+# and exp(LL_1 - m) is exactly 0 in logehvi1_combine_kernel's member log-sum-exp.
+HOPELESS = Case("log_e2_k1_d3_n20_p3_f2_hopeless", 314, 2, 2, 1, 3, _grid(2, 3, 20), 3, 2, ch.TAUS[1], 5, None, 0.0)
+HOPELESS_LEVEL, HOPELESS_GAP = 3.0, -800.0
+EDGE_CASES = MIXED + [CFLOOR] + LANE_CASES + [HOPELESS]
+ALL_CASES = M2_CASES + OWN_CASES + [FULL, ULP, FLOOR] + EDGE_CASES
 BELIEVED2 = ch.BELIEVED2
 
 
 def shifts_of(c):
-    return FLOOR_SHIFTS if c.name == FLOOR.name else SHIFTS
+    return {FLOOR.name: FLOOR_SHIFTS, CFLOOR.name: CFLOOR_SHIFTS}.get(c.name, SHIFTS)
 
 
 CASE_SHIFTS = [(c, s) for c in ALL_CASES for s in shifts_of(c)]
@@ -201,14 +315,44 @@ def _full_problem(c):
     return ch.Problem(c.name, 2, gps, [], ch.REF2, np.ascontiguousarray(front), points, pending, tuple(range(c.C)))
 
 
+def _one_ulp(c, front, ref):
+    """the front of ULP64 / ULP_LAST with its two neighbouring edges a unit in the last place apart (again, after a shift)"""
+    if c.name == ULP64.name:
+        front[64, 0] = np.nextafter(front[63, 0], np.inf)
+        assert front[63, 0] < front[64, 0] < front[65, 0]
+    else:
+        front[63, 0] = np.nextafter(ref[0], -np.inf)
+        assert front[62, 0] < front[63, 0] < ref[0]
+    return np.ascontiguousarray(front)
+
+
 def make_problem(c):
-    """ch.make_problem, with the three constructions of this file"""
+    """ch.make_problem, with the constructions of this file"""
     if c.name == FULL.name:
         return _full_problem(c)
+    if c.name == CFLOOR.name:
+        p = ch.make_problem(ch.FLOOR2)
+        points = p.points.copy()
+        points[1] = 0.5 * (points[2] + points[3])  # (an ordinary point in place of the infeasible side's)
+        return p._replace(name=c.name, points=points, checked=tuple(range(c.C)))
     p = ch.make_problem(c)
     if c.name == ULP.name:
         front = np.array([(-0.2, 0.4), (np.nextafter(-0.2, 1.0), 0.1), (0.3, -0.3)])
         p = p._replace(front=np.ascontiguousarray(front))
+    if c.name in (ULP64.name, ULP_LAST.name):
+        p = p._replace(front=_one_ulp(c, p.front.copy(), p.ref))
+    if c.name == HOPELESS.name:
+        rng = np.random.default_rng(c.seed)
+        g = p.gps[1][2]
+        y = p.taus[0] + HOPELESS_LEVEL + 0.01 * rng.normal(size=np.asarray(g.y).shape)
+        far = ch.GP(ch.SE, np.array([1.3, 3.0, 3.0, 3.0]), g.X, y, [1e-2], ())
+        p = p._replace(gps=[p.gps[0], list(p.gps[1][:2]) + [far]])
+    if c.name == LANES.name:
+        gps = [[ch.GP(g.cov_type, g.hyper, g.X, g.y, [LANES_NOISE], ()) for g in row[:2]] + list(row[2:]) for row in p.gps]
+        points = p.points.copy()
+        X = p.gps[0][0].X
+        points[0], points[1] = X[LANES_ROWS[0]] + LANES_OFFSET, X[LANES_ROWS[1]] - LANES_OFFSET
+        p = p._replace(gps=gps, points=points)
     if c.name == FLOOR.name:
         row = list(p.gps[0])
         g = row[0]
@@ -254,6 +398,8 @@ def shifted(c, shift, T=LD):
     front = np.ascontiguousarray(np.asarray(p.front, dtype=np.float64).reshape(-1, 2) - shift[0])
     if c.name == ULP.name:  # (the lowered neighbours would round to one number: one unit in the last place apart again)
         front[1, 0] = np.nextafter(front[0, 0], np.inf)
+    if c.name in (ULP64.name, ULP_LAST.name):
+        front = _one_ulp(c, front, ref)
     taus = [t - shift[1] for t in p.taus]
     return p._replace(ref=ref, front=front, taus=taus), reshifted(members, ref, front, taus)
 

@@ -10,7 +10,11 @@ float64-against-long-double difference of the restatement.  Everything else is b
 formed on the host from factors_out, value-only against value + gradient, a candidate alone against itself in a batch and across the
 pass boundary, ensemble-wide launches on against off, K = 0 against the unconstrained entry points in all three call shapes, an
 empty front with K = 1 against moe_ei_constrained_mcmc's factors, the ascent against a host-driven loop over the evaluator, the
-greedy batch against calls of the ascent fed their predecessors' points.  Every test prints the worst figures it saw (pytest -s)."""
+greedy batch against calls of the ascent fed their predecessors' points.  cehvi_reference.EDGE_CASES and the constructions behind
+them add what the first cases could not tell apart: E >= 2 with K >= 2 together (every [e][k] stride, distinct thresholds, across
+the pass boundary and through a batch), a belief that changes along a batch (against the restatement under a stale mask word), 64
+pending points under masks that differ per member, the constraint roles' variance floors, and E (M + K) = 1024 run once for the
+plain and the log form over the same handles.  Every test prints the worst figures it saw (pytest -s)."""
 import numpy as np
 import pytest
 
@@ -155,12 +159,11 @@ def test_with_an_empty_front_a_member_is_the_product_of_two_improvements_and_the
 
 
 # ---- 4. across the pass boundary ----
-@pytest.mark.parametrize("M", (2, 3))
-def test_a_candidate_carries_its_bits_across_the_pass_boundary_and_want_grad(M):
+def _across_the_pass_boundary(M, E, K, taus):
     per_pass = _lib.load().moe_ei1_pass_size(8)
     C_ = per_pass + 4
     assert per_pass == 4096
-    c = ch.Case("m%d_e1_k1_d2_n8_p2_f5_two_passes" % M, 44, M, 1, 1, 2, ch._grid(1, M + 1, 8), 2, 5, (0.0,), C_, None, 0.0)
+    c = ch.Case("m%d_e%d_k%d_d2_n8_p2_f5_two_passes" % (M, E, K), 44, M, E, K, 2, ch._grid(E, M + K, 8), 2, 5, taus, C_, None, 0.0)
     p = ch.make_problem(c)
     checked = (0, per_pass - 1, per_pass, C_ - 1)
     ref_members = ch.ensemble(p, LD)
@@ -180,6 +183,18 @@ def test_a_candidate_carries_its_bits_across_the_pass_boundary_and_want_grad(M):
             print("%s: value error %.3g scale, gradient error %.3g on both sides of the pass boundary" % (p.name, e_v, e_g))
             assert e_v <= 1e-10 and e_g <= 1e-10 and e_f <= 1e-10
     D.close()
+
+
+@pytest.mark.parametrize("M", (2, 3))
+def test_a_candidate_carries_its_bits_across_the_pass_boundary_and_want_grad(M):
+    _across_the_pass_boundary(M, 1, 1, (0.0,))
+
+
+@pytest.mark.parametrize("M", (2, 3))
+def test_two_members_with_two_constraints_cross_the_pass_boundary(M):
+    """the second pass holds 4 candidates where the first held 4096: every [e][k] block of the per-pass arrays is strided by a pass
+    size that is not the call's number of candidates"""
+    _across_the_pass_boundary(M, 2, 2, ch.EDGE_TAUS[2])
 
 
 # ---- 5. the ascent against the host-driven loop ----
@@ -269,6 +284,106 @@ def test_the_batch_is_the_ascent_fed_its_predecessors_bit_for_bit(M):
     D.close()
 
 
+@pytest.mark.parametrize("M", (2, 3))
+def test_the_batch_of_two_members_with_two_constraints_is_the_ascent_fed_its_predecessor(M):
+    """cehvi_reference.MIXED: E = 2, K = 2, d = 13, rows that differ per role and member -- the hand-over between the rounds of a
+    batch (the appended pending row, the constraint means [e][k] the beliefs are taken from) at strides that do not collapse"""
+    p = ch.make_problem(ch.MIXED[M])
+    D = _Device(p)
+    starts, gd, bounds = _ascent_inputs(p.points.shape[1], 1e-10)
+    pending, q = p.pending[:1], 2
+    want_points, want_values = [], []
+    for t in range(q):
+        fed = np.vstack([pending] + [x[None, :] for x in want_points])
+        res = api.ehvi_constrained_multistart(D.objs, D.cons, p.taus, p.ref, p.front, gd, bounds, starts, points_being_sampled=fed)
+        assert res["found"]
+        want_points.append(res["point"])
+        want_values.append(res["value"])
+    for on in (True, False):
+        with _Launches(on):
+            got = api.ehvi_constrained_suggest(D.objs, D.cons, p.taus, p.ref, p.front, gd, bounds, starts, q, points_being_sampled=pending)
+        assert np.array_equal(got["points"], np.array(want_points)), on
+        assert np.array_equal(got["values"], np.array(want_values)) and np.all(got["found"])
+    gap = float(np.max(np.abs(want_points[1] - want_points[0])))
+    print("M = %d, E = 2, K = 2: greedy values %s, the picks %.3g apart" % (M, want_values, gap))
+    assert want_values[0] > 0.0 and want_values[1] > 0.0 and gap >= 1e-3
+    D.close()
+
+
+@pytest.mark.parametrize("M", (2, 3))
+def test_a_belief_that_changes_along_the_batch_is_worked_out_anew_for_every_pick(M):
+    """cehvi_reference.changing_problem: member 1's constraint mean falls through tau at x_0 = 0.5, the pending point lies on the
+    infeasible side and the starts on both.  The batch is the ascent fed its predecessors bit for bit; member 1's beliefs along
+    pending point and picks, from its own means, are not constant; and every pick's value is the restatement's under the beliefs of
+    ALL the points before it, while the restatement that gives every point the FIRST point's belief (a mask word never worked out
+    again) lies more than 1e-3 away at a later pick."""
+    p, starts = ch.changing_problem(M)
+    D = _Device(p)
+    _, gd, bounds = _ascent_inputs(3, 1e-10)
+    q, tau = ch.CHANGING_Q[M], p.taus[0]
+    want_points, want_values = [], []
+    for t in range(q):
+        fed = np.vstack([p.pending] + [x[None, :] for x in want_points])
+        res = api.ehvi_constrained_multistart(D.objs, D.cons, p.taus, p.ref, p.front, gd, bounds, starts, points_being_sampled=fed)
+        assert res["found"]
+        want_points.append(res["point"])
+        want_values.append(res["value"])
+    for on in (True, False):
+        with _Launches(on):
+            got = api.ehvi_constrained_suggest(D.objs, D.cons, p.taus, p.ref, p.front, gd, bounds, starts, q, points_being_sampled=p.pending)
+        assert np.array_equal(got["points"], np.array(want_points)), on
+        assert np.array_equal(got["values"], np.array(want_values)) and np.all(got["found"])
+    every = np.vstack([p.pending] + [x[None, :] for x in want_points])
+    mu0, mu1 = D.cons[0][0].mean(every), D.cons[0][1].mean(every)
+    belief = [bool(m <= tau) for m in mu1]
+    true_gap, stale_gap = _gaps_to_the_restatement(p, every, want_values)
+    print("M = %d: member 1's constraint means at the pending point and the %d picks %s (tau = 0): believed feasible %s; member 0's %s; "
+          "values %s; against the restatement %s scale, against the one under the first point's belief %s" % (
+              M, q, np.round(mu1, 4).tolist(), belief, np.round(mu0, 3).tolist(), want_values, true_gap, stale_gap))
+    assert np.all(np.abs(mu1 - tau) >= ch.MARGIN) and np.all(mu0 <= tau - ch.MARGIN)
+    assert len(set(belief)) == 2 and any(belief[j] != belief[t] for t in range(1, q + 1) for j in range(t))
+    assert max(true_gap) <= 1e-10 and max(stale_gap[1:]) > 1e-3
+    D.close()
+
+
+def _gaps_to_the_restatement(p, every, values):
+    """pick t's value against the restatement conditioned on the points before it, in units of scale: under the believed-feasible
+    rule, and with the first point's belief given to every point (member by member)"""
+    true_gap, stale_gap = [], []
+    for t, v in enumerate(values):
+        fed = every[:1 + t]
+        members = ch.ensemble(p, LD, pending=fed)
+        stale = [ch.remasked(m, [m.mask[0]] * len(fed), p.front) for m in members]
+        a, b = ch.evaluate(members, every[1 + t]), ch.evaluate(stale, every[1 + t])
+        true_gap.append(abs(v - float(a.value)) / a.scale)
+        stale_gap.append(abs(v - float(b.value)) / a.scale)
+    return true_gap, stale_gap
+
+
+# ---- 6b. the constraint roles' floors ----
+@pytest.mark.parametrize("M", (2, 3))
+def test_on_a_noise_free_constraints_sampled_points_the_feasibility_is_exactly_one_and_zero(M):
+    """cehvi_reference.FLOOR: candidates 0 and 1 on sampled points of the noise-free GP of constraint 1, observed 0.2 below and above
+    its threshold (tests/test_cehvi_reference.py: the float64 variance there lies under 150 eps^2).  cehvi_feas_kernel's own two
+    floors: F under DBL_MIN is exactly 1 and exactly 0, its gradient under 150 eps^2 exactly 0."""
+    case = ch.FLOOR[M]
+    p, want = ch.expected(case, LD)
+    D = _Device(p)
+    value, grad, factors = _eval(D, p, p.points, want_factors=True)
+    print("M = %d: F_1 at the two sampled points %r, %r; values %r, %r; F_1 elsewhere %s" % (
+        M, factors[0, 1, 0], factors[0, 1, 1], value[0], value[1], np.round(factors[0, 1, 2:], 4).tolist()))
+    assert factors[0, 1, 0] == 1.0 and factors[0, 1, 1] == 0.0
+    assert value[1] == 0.0 and not np.any(grad[1]) and np.all(np.isfinite(grad)) and np.all(np.isfinite(factors))
+    # candidate 0 is the product without F_1, and its gradient that of the other factors: against the restatement
+    assert value[0] == factors[0, 0, 0] * 1.0 * factors[0, 2, 0] and value[0] > 0.0
+    bound = max(1e-10, 4.0 * case.ld_diff)
+    e_v, e_g, e_f = _errors(value, grad, factors, want, (0, 1))
+    print("M = %d: at the two floored candidates value error %.3g scale, gradient error %.3g, factors' error %.3g scale" % (M, e_v, e_g, e_f))
+    assert e_v <= bound and e_g <= bound and e_f <= bound
+    assert np.all(factors[0, 1, 2:] > 0.0) and np.all(factors[0, 1, 2:] < 1.0)  # (elsewhere the same GP's factor is a probability)
+    D.close()
+
+
 # ---- 7. the believed-feasible rule through the members' values ----
 @pytest.mark.parametrize("M", (2, 3))
 def test_a_believed_infeasible_point_does_not_shrink_the_members_region(M):
@@ -287,6 +402,34 @@ def test_a_believed_infeasible_point_does_not_shrink_the_members_region(M):
     assert np.array_equal(f[0, 0], tm[0])  # member 0 believes all three feasible: the unconstrained member's bits
     assert gap[1] >= 1e-3                  # member 1 holds pending point 1 back: its region stays larger
     assert np.all(f[1, 0] >= tm[1] - 1e-12)
+    D.close()
+
+
+# ---- 7b. sixty-four pending points under a mixed mask ----
+@pytest.mark.parametrize("M", (2, 3))
+def test_sixty_four_pending_points_under_a_mask_that_differs_per_member(M):
+    """cehvi_reference.MASKED (tests/test_cehvi_reference.py qualifies it): cehvi_believed_kernel over 5 x 64 threads with mask rows
+    of 64 words; in every member offered outcomes evict front points past index 64 behind skipped ones, and skipped outcomes would
+    have joined and dominated later ones.  A member whose mask were all ones gives the other restatement, 1e-3 scale away."""
+    case = ch.MASKED[M]
+    p, want = ch.expected(case, LD)
+    D = _Device(p)
+    runs = []
+    for on in (True, False):
+        with _Launches(on):
+            runs.append(_eval(D, p, p.points, want_factors=True))
+    value, grad, factors = runs[0]
+    for a, b in zip(runs[0], runs[1]):
+        assert np.array_equal(a, b)
+    bound = max(1e-10, 4.0 * case.ld_diff)
+    e_v, e_g, e_f = _errors(value, grad, factors, want, range(case.C))
+    assert e_v <= bound and e_g <= bound and e_f <= bound, (e_v, e_g, e_f)
+    assert np.array_equal(value, ch.host_value(factors))
+    ones = [ch.remasked(m, [True] * len(p.pending), p.front) for m in ch.ensemble(p, LD)]
+    apart = [max(abs(factors[e, 0, i] - float(ones[e].evaluate(x)[2][0])) for i, x in enumerate(p.points)) / want[0].scale for e in range(case.E)]
+    print("%s: value error %.3g scale, gradient error %.3g, factors' error %.3g scale (bound %.3g); H_e against the restatement under "
+          "the all-ones mask, per member: %s scale" % (case.name, e_v, e_g, e_f, bound, np.round(apart, 5).tolist()))
+    assert min(apart) > 1e-3
     D.close()
 
 
@@ -338,6 +481,58 @@ def test_a_pending_point_listed_twice_in_a_noise_free_constraint_gp_is_singular(
     deriv.close()
     for g in objs[0] + objs[1] + cons[0]:
         g.close()
+
+
+# ---- 8b. E (M + K) = 1024 exactly, the plain and the log form over the same handles ----
+def test_1024_gps_at_the_limit_and_one_member_more_is_refused():
+    """E = 128, M = 2, K = 6: pointer tables of 1024 entries, feasibility blocks [128][6], factors_out [128][7][C]"""
+    import time
+    import log_ehvi_reference as lh
+    t0 = time.perf_counter()
+    c = ch.LIMIT
+    p, want = ch.expected(c, LD)
+    want_log = [lh.evaluate(ch.ensemble(p, LD), x) for x in p.points]
+    t1 = time.perf_counter()
+    D = _Device(p)
+    t2 = time.perf_counter()
+    assert len(D.objs[0]) == 128 and len(D.cons) == 6 and sum(len(row) for row in D.all) == 1024
+    value, grad, factors = _eval(D, p, p.points, want_factors=True)
+    assert factors.shape == (128, 7, c.C) and np.all(np.isfinite(grad))
+    bound = max(1e-10, 4.0 * c.ld_diff)
+    e_v, e_g, e_f = _errors(value, grad, factors, want, range(c.C))
+    e_3 = max(abs(factors[e, k, i] - float(want[i].factors[e][k])) / want[i].scale for i in range(c.C) for e in ch.LIMIT_MEMBERS
+              for k in range(7))
+    assert e_v <= bound and e_g <= bound and e_f <= bound and e_3 <= bound, (e_v, e_g, e_f, e_3)
+    assert np.array_equal(value, ch.host_value(factors))
+    lv, lg, logs = api.log_ehvi_constrained_ensemble(D.objs, D.cons, p.taus, p.ref, p.front, p.points, points_being_sampled=p.pending,
+                                                     want_log_factors=True)
+    assert logs.shape == (128, 7, c.C) and np.all(np.isfinite(lv)) and np.all(np.isfinite(lg)) and np.all(np.isfinite(logs))
+    l_v = max(abs(lv[i] - float(w.value)) / max(1.0, abs(float(w.value))) for i, w in enumerate(want_log))
+    l_g = max(float(np.max(np.abs(lg[i] - w.grad.astype(np.float64)))) / max(1.0, float(np.max(np.abs(w.grad)))) for i, w in enumerate(want_log))
+    l_f = max(abs(logs[e, r, i] - float(f)) / max(1.0, abs(float(f))) for i, w in enumerate(want_log) for e, row in enumerate(w.log_factors)
+              for r, f in enumerate(row))
+    l_3 = max(abs(logs[e, r, i] - float(w.log_factors[e][r])) / max(1.0, abs(float(w.log_factors[e][r]))) for i, w in enumerate(want_log)
+              for e in ch.LIMIT_MEMBERS for r in range(7))
+    assert l_v <= 1e-10 and l_g <= 1e-10 and l_f <= 1e-10 and l_3 <= 1e-10, (l_v, l_g, l_f, l_3)
+    assert np.array_equal(lv, lh.host_value(logs))
+    t3 = time.perf_counter()
+    # one member more: E (M + K) = 1032
+    g = p.gps[0]
+    extra = [api.DeviceGP(x.hyper * 1.01, x.X, x.y, x.noise, [], cov_type=x.cov_type) for x in g]
+    objs = [D.objs[r] + [extra[r]] for r in range(2)]
+    cons = [D.cons[k] + [extra[2 + k]] for k in range(6)]
+    for call in (api.ehvi_constrained_ensemble, api.log_ehvi_constrained_ensemble):
+        with pytest.raises(api.BoundsException) as e:
+            call(objs, cons, p.taus, p.ref, p.front, p.points)
+        assert (e.value.value, e.value.min, e.value.max) == (129, 1, 128), str(e.value)
+    for x in extra:
+        x.close()
+    D.close()
+    t4 = time.perf_counter()
+    print("E = 128, K = 6: plain value error %.3g scale, gradient %.3g, factors %.3g (members 0, 63, 127: %.3g; bound %.3g); log value "
+          "error %.3g, gradient %.3g, log factors %.3g (members 0, 63, 127: %.3g; bound 1e-10); wall time %.2f s: the long-double "
+          "restatements %.2f (less when another test built them), 1024 handles built in %.2f, the device calls %.2f, E = 129 and the "
+          "handles closed in %.2f" % (e_v, e_g, e_f, e_3, bound, l_v, l_g, l_f, l_3, t4 - t0, t1 - t0, t2 - t1, t3 - t2, t4 - t3))
 
 
 # ---- 9. the wrapper, on competing objectives inside a disc ----

@@ -8,8 +8,11 @@ max(1, |want|_inf), every log factor like the value.  Against the plain forms th
 Everything else is bit for bit: value-only against value + gradient, a candidate alone against itself in a batch and across the pass
 boundary, ensemble-wide launches on against off, an empty pending list against none, the value against the documented rule over
 factors_out, the ascent against a host-driven loop over the evaluator (tests/ms_restatement.py), the greedy batch against calls of
-the ascent fed their predecessors' points.  Every test prints the worst figures it saw (pytest -s); DESIGN.md section 5.25 records
-those of the first run."""
+the ascent fed their predecessors' points.  log_ehvi_reference.EDGE_CASES add E = 2 with K = 2 and K = 8 (distinct thresholds), the
+constraint role's floor, the log-strip kernel's lane branches (four sweeps, weights that underflow, the rho = 1 strip at lane 0 of
+the second sweep and as the last strip; tests/test_log_ehvi_reference.py counts the branches on a replay of the lane order) and a
+member whose weight underflows in the member log-sum-exp.  Every test prints the worst figures it saw (pytest -s); DESIGN.md
+section 5.25 records those of the first run."""
 import ctypes as C
 import math
 
@@ -138,6 +141,51 @@ def test_a_candidate_carries_its_bits_across_the_pass_boundary():
     D.close()
 
 
+def test_two_members_with_two_constraints_cross_the_pass_boundary():
+    """E = 2, K = 2, distinct thresholds: the second pass holds 4 candidates where the first held 4096, so every [e][k] block of the
+    per-pass arrays is strided by a pass size that is not the call's number of candidates"""
+    per_pass = _lib.load().moe_ei1_pass_size(8)
+    C_ = per_pass + 4
+    assert per_pass == 4096
+    c = ch.Case("m2_e2_k2_d2_n8_p2_f5_two_passes", 44, 2, 2, 2, 2, ch._grid(2, 4, 8), 2, 5, ch.EDGE_TAUS[2], C_, None, 0.0)
+    p0 = ch.make_problem(c)
+    s = lh.SHIFTS[1]
+    p = p0._replace(ref=tuple(r - s[0] for r in p0.ref), front=np.ascontiguousarray(p0.front - s[0]))
+    checked = (0, per_pass - 1, per_pass, C_ - 1)
+    members = lh.reshifted(ch.ensemble(p0, LD), p.ref, p.front, p.taus)
+    D = _Device(p)
+    value, grad, logs = _eval(D, p, p.points, want_log_factors=True)
+    assert np.all(np.isfinite(value)) and np.all(np.isfinite(grad)) and logs.shape == (2, 3, C_)
+    v_only, f_only = _eval(D, p, p.points, want_grad=False, want_log_factors=True)
+    assert np.array_equal(v_only, value) and np.array_equal(f_only, logs)
+    idx = list(checked)
+    assert np.array_equal(value[idx], lh.host_value(logs[:, :, idx]))
+    for i in checked:
+        v1, g1, f1 = _eval(D, p, p.points[i:i + 1], want_log_factors=True)
+        assert v1[0] == value[i] and np.array_equal(g1[0], grad[i]) and np.array_equal(f1[:, :, 0], logs[:, :, i]), i
+    want = [lh.evaluate(members, p.points[i]) for i in checked]
+    e_v, e_g, e_f = _errors(value[idx], grad[idx], logs[:, :, idx], want)
+    print("%s: value error %.3g, gradient error %.3g, log factor error %.3g on both sides of the pass boundary" % (p.name, e_v, e_g, e_f))
+    assert e_v <= BOUND and e_g <= BOUND and e_f <= BOUND
+    D.close()
+
+
+def test_on_a_noise_free_constraints_sampled_point_the_log_feasibility_is_exactly_zero():
+    """log_ehvi_reference.CFLOOR: candidate 0 on a sampled point of the noise-free GP of constraint 1, observed 0.2 below tau_1:
+    logehvi1_feas_kernel's own floor, log F_1 = 0 and a gradient that the factor does not move"""
+    for shift in lh.CFLOOR_SHIFTS:
+        p, _, want = lh.expected(lh.CFLOOR, shift, LD)
+        D = _Device(p)
+        value, grad, logs = _eval(D, p, p.points, want_log_factors=True)
+        assert logs[0, 1, 0] == 0.0 and np.all(logs[0, 1, 1:] < 0.0) and np.all(np.isfinite(grad))
+        assert value[0] == logs[0, 0, 0] + 0.0 + logs[0, 2, 0]
+        e_v, e_g, e_f = _errors(value[:1], grad[:1], logs[:, :, :1], want[:1])
+        print("the constraint floor %s: at the floored candidate value error %.3g, gradient error %.3g, log factor error %.3g" % (
+            shift, e_v, e_g, e_f))
+        assert e_v <= BOUND and e_g <= BOUND and e_f <= BOUND
+        D.close()
+
+
 # ---- 3. no front, no constraints, one member: the sum of two log expected improvements ----
 def test_with_an_empty_front_the_value_is_the_sum_of_two_log_expected_improvements():
     p, _, _ = lh.expected(lh.case("log_e1_k0_d3_n20_p3_f0"), lh.SHIFTS[0], LD)
@@ -205,6 +253,25 @@ def test_the_mask_rule_decides_which_believed_outcomes_join():
     free = api.log_ehvi_constrained_ensemble(D.objs, None, None, p.ref, p.front, p.points, points_being_sampled=p.pending,
                                              want_grad=False, want_log_factors=True)[1]
     assert np.array_equal(free[0, 0], logs[0, 0]) and float(np.max(np.abs(free[1, 0] - logs[1, 0]))) >= 1e-3
+    D.close()
+
+
+def test_sixty_four_pending_points_under_a_mask_that_differs_per_member():
+    """cehvi_reference.MASKED[2] through the log form: E = 5, p = 64, every member's own mask row of 64 words and its own front of
+    130 to 160 points (three sweeps of strips)"""
+    p, _ = ch.expected(ch.MASKED[2], LD)
+    members = ch.ensemble(p, LD)
+    want = [lh.evaluate(members, x) for x in p.points]
+    D = _Device(p)
+    value, grad, logs = _eval(D, p, p.points, want_log_factors=True)
+    e_v, e_g, e_f = _errors(value, grad, logs, want)
+    assert np.array_equal(value, lh.host_value(logs))
+    ones = [ch.remasked(m, [True] * len(p.pending), p.front) for m in members]
+    apart = [max(abs(logs[e, 0, i] - float(lh.member_logs(ones[e], x)[0][0])) for i, x in enumerate(p.points)) for e in range(5)]
+    print("%s: value error %.3g, gradient error %.3g, log factor error %.3g (relative, bounds 1e-10); the log hypervolume term against "
+          "the restatement under the all-ones mask, per member: %s" % (p.name, e_v, e_g, e_f, np.round(apart, 4).tolist()))
+    assert e_v <= BOUND and e_g <= BOUND and e_f <= BOUND
+    assert min(apart) > 1e-3
     D.close()
 
 
@@ -289,6 +356,94 @@ def test_the_batch_is_the_ascent_fed_its_predecessors_bit_for_bit():
     gaps = [float(np.min(np.max(np.abs(np.array(want_points)[:t] - want_points[t]), axis=1))) for t in range(1, q)]
     print("greedy values %s, largest coordinate gap of each pick to the nearest pick before it %s" % (want_values, gaps))
     assert np.all(np.isfinite(want_values)) and min(gaps) >= 1e-3
+    D.close()
+
+
+def test_the_batch_of_two_members_with_two_constraints_is_the_ascent_fed_its_predecessor():
+    """cehvi_reference.MIXED2: E = 2, K = 2, d = 13, rows that differ per role and member, through the log form's hand-over"""
+    p, _ = lh.shifted(ch.MIXED2, lh.SHIFTS[1], np.float64)
+    D = _Device(p)
+    starts, gd, bounds = _ascent_inputs(p.points.shape[1], 1e-10)
+    pending, q = p.pending[:1], 2
+    want_points, want_values = [], []
+    for t in range(q):
+        fed = np.vstack([pending] + [x[None, :] for x in want_points])
+        res = api.log_ehvi_constrained_multistart(D.objs, D.cons, D.tau, p.ref, p.front, gd, bounds, starts, points_being_sampled=fed)
+        assert res["found"]
+        want_points.append(res["point"])
+        want_values.append(res["value"])
+    for on in (True, False):
+        with _Launches(on):
+            got = api.log_ehvi_constrained_suggest(D.objs, D.cons, D.tau, p.ref, p.front, gd, bounds, starts, q,
+                                                   points_being_sampled=pending)
+        assert np.array_equal(got["points"], np.array(want_points)), on
+        assert np.array_equal(got["values"], np.array(want_values)) and np.all(got["found"])
+    gap = float(np.max(np.abs(want_points[1] - want_points[0])))
+    print("E = 2, K = 2: greedy log values %s, the picks %.3g apart" % (want_values, gap))
+    assert np.all(np.isfinite(want_values)) and gap >= 1e-3
+    D.close()
+
+
+def test_a_belief_that_changes_along_the_batch_is_worked_out_anew_for_every_pick():
+    """cehvi_reference.changing_problem (M = 2) through the log form: tests/test_gpu_cehvi.py's test of the same name"""
+    p, starts = ch.changing_problem(2)
+    D = _Device(p)
+    _, gd, bounds = _ascent_inputs(3, 1e-10)
+    q, tau = ch.CHANGING_Q[2], p.taus[0]
+    want_points, want_values = [], []
+    for t in range(q):
+        fed = np.vstack([p.pending] + [x[None, :] for x in want_points])
+        res = api.log_ehvi_constrained_multistart(D.objs, D.cons, D.tau, p.ref, p.front, gd, bounds, starts, points_being_sampled=fed)
+        assert res["found"]
+        want_points.append(res["point"])
+        want_values.append(res["value"])
+    for on in (True, False):
+        with _Launches(on):
+            got = api.log_ehvi_constrained_suggest(D.objs, D.cons, D.tau, p.ref, p.front, gd, bounds, starts, q,
+                                                   points_being_sampled=p.pending)
+        assert np.array_equal(got["points"], np.array(want_points)), on
+        assert np.array_equal(got["values"], np.array(want_values)) and np.all(got["found"])
+    every = np.vstack([p.pending] + [x[None, :] for x in want_points])
+    mu0, mu1 = D.cons[0][0].mean(every), D.cons[0][1].mean(every)
+    belief = [bool(m <= tau) for m in mu1]
+    true_gap, stale_gap = [], []
+    for t, v in enumerate(want_values):
+        fed = every[:1 + t]
+        members = ch.ensemble(p, LD, pending=fed)
+        stale = [ch.remasked(m, [m.mask[0]] * len(fed), p.front) for m in members]
+        a, b = lh.evaluate(members, every[1 + t]), lh.evaluate(stale, every[1 + t])
+        true_gap.append(abs(v - float(a.value)) / max(1.0, abs(float(a.value))))
+        stale_gap.append(abs(v - float(b.value)) / max(1.0, abs(float(a.value))))
+    print("member 1's constraint means at the pending point and the %d picks %s (tau = 0): believed feasible %s; member 0's %s; log "
+          "values %s; against the restatement %s, against the one under the first point's belief %s" % (
+              q, np.round(mu1, 4).tolist(), belief, np.round(mu0, 3).tolist(), want_values, true_gap, stale_gap))
+    assert np.all(np.abs(mu1 - tau) >= ch.MARGIN) and np.all(mu0 <= tau - ch.MARGIN)
+    assert len(set(belief)) == 2 and any(belief[j] != belief[t] for t in range(1, q + 1) for j in range(t))
+    assert max(true_gap) <= BOUND and max(stale_gap[1:]) > 1e-3
+    D.close()
+
+
+# ---- 7b. a member whose weight underflows ----
+def test_a_hopeless_member_leaves_the_other_members_bits_less_log_two():
+    """log_ehvi_reference.HOPELESS: LL_1 lies more than 800 below LL_0 at every candidate (tests/test_log_ehvi_reference.py), so
+    w_1 = exp(LL_1 - m) is exactly 0 in the member log-sum-exp: W = 1 + 0, the gradient (1 g_0 + 0 g_1) / 1.  Member 0's log factors
+    and the gradient are those of the call on member 0's GPs alone, and the value is that call's less log 2 under the documented
+    rule m + log W - log E, bit for bit."""
+    p, _, want = lh.expected(lh.HOPELESS, lh.SHIFTS[0], LD)
+    D = _Device(p)
+    value, grad, logs = _eval(D, p, p.points, want_log_factors=True)
+    assert np.all(np.isfinite(logs)) and np.all(np.isfinite(value)) and np.all(np.isfinite(grad))
+    LL = logs[:, 0] + logs[:, 1]
+    assert np.all(LL[1] - LL[0] < lh.HOPELESS_GAP)
+    assert np.array_equal(value, lh.host_value(logs))
+    alone = api.log_ehvi_constrained_ensemble([D.objs[0][:1], D.objs[1][:1]], [D.cons[0][:1]], D.tau, p.ref, p.front, p.points,
+                                              points_being_sampled=p.pending, want_log_factors=True)
+    e_v, e_g, e_f = _errors(value, grad, logs, want)
+    print("hopeless: LL_1 - LL_0 on the device %s; errors %.3g %.3g %.3g; value - (member 0 alone - log 2) %s" % (
+        np.round(LL[1] - LL[0], 1).tolist(), e_v, e_g, e_f, (value - (alone[0] - math.log(2.0))).tolist()))
+    assert e_v <= BOUND and e_g <= BOUND and e_f <= BOUND
+    assert np.array_equal(logs[0], alone[2][0]) and np.array_equal(grad, alone[1])
+    assert np.array_equal(value, alone[0] - math.log(2.0))
     D.close()
 
 
