@@ -1386,6 +1386,49 @@ def log_ehvi_constrained_suggest(objective_gps, constraint_gps, thresholds, refe
                          gradient_ascent, points_being_sampled)
 
 
+def _log_ehvi3_constrained_call(objective_gps, constraint_gps, thresholds, reference_point, front):
+    """_ehvi_constrained_call for the three-objective log form"""
+    objs = list(objective_gps)
+    if len(objs) != 3:
+        raise BoundsException("the three-objective log expected hypervolume improvement takes three objectives", len(objs), 3, 3)
+    stem, pre, E, d, K, keep = _ehvi_constrained_call(objs, constraint_gps, thresholds, reference_point, front)
+    return "moe_log_ehvi3_constrained_mcmc", pre, E, d, K, keep
+
+
+def log_ehvi3_constrained_ensemble(objective_gps, constraint_gps, thresholds, reference_point, front, points,
+                                   points_being_sampled=None, want_grad=True, want_log_factors=False):
+    """moe_log_ehvi3_constrained_mcmc: the LOG of what ehvi_constrained_ensemble returns for three objectives, computed so that it
+    stays finite with a useful gradient where that value and its gradient are exactly 0 in float64 (a mean dozens of posterior
+    standard deviations above the reference point in any one objective, a constraint far from feasible).  Arguments as there, the
+    front [F][3] in the canonical order; constraint_gps=None / thresholds=None is K = 0, the log of ehvi3_ensemble's value.  Returns
+    value [C], with want_grad (value, grad [C][dim]), and with want_log_factors additionally log_factors [E][1 + K][C] (the log
+    hypervolume term, then the K log feasibility factors) as the last item; the value is the log-mean-exp over e of the members'
+    sums.  SingularMatrixException as there."""
+    stem, pre, E, d, K, keep = _log_ehvi3_constrained_call(objective_gps, constraint_gps, thresholds, reference_point, front)
+    return _acq1_evaluate(getattr(_lib.load(), stem), pre, (), d, points, want_grad, points_being_sampled,
+                          extra_shape=(E, 1 + K), want_extra=want_log_factors)
+
+
+def log_ehvi3_constrained_multistart(objective_gps, constraint_gps, thresholds, reference_point, front, gd_params, bounds, starts,
+                                     gradient_ascent=True, want_path=False, points_being_sampled=None):
+    """moe_log_ehvi3_constrained_mcmc_multistart: one suggestion by the log of the ensemble-averaged three-objective constrained
+    expected hypervolume improvement -- ehvi_constrained_multistart's screening, 20 kept starts, restarted ascent on the device and
+    end-point selection, and its dict, on an objective whose screening values do not tie at 0 and whose gradient does not vanish."""
+    stem, pre, E, d, K, keep = _log_ehvi3_constrained_call(objective_gps, constraint_gps, thresholds, reference_point, front)
+    return _acq1_multistart(getattr(_lib.load(), stem + "_multistart"), pre, (), d, gd_params, bounds, starts, gradient_ascent,
+                            want_path, points_being_sampled)
+
+
+def log_ehvi3_constrained_suggest(objective_gps, constraint_gps, thresholds, reference_point, front, gd_params, bounds, starts,
+                                  num_to_sample, gradient_ascent=True, points_being_sampled=None):
+    """moe_log_ehvi3_constrained_mcmc_suggest: num_to_sample points greedily -- round t is log_ehvi3_constrained_multistart from the
+    same starts [S][dim] with the pending points points_being_sampled [p][dim] (may be None) followed by the points of the rounds
+    before, bit for bit, in one device call.  p + num_to_sample - 1 <= 64.  Returns a dict: points [q][dim], values [q], found [q]."""
+    stem, pre, E, d, K, keep = _log_ehvi3_constrained_call(objective_gps, constraint_gps, thresholds, reference_point, front)
+    return _acq1_suggest(getattr(_lib.load(), stem + "_suggest"), pre, (), d, gd_params, bounds, starts, num_to_sample,
+                         gradient_ascent, points_being_sampled)
+
+
 def _gibbon_members(gps, min_values):
     """(handles, count, dim, members kept alive, min-values [E][K], K) of the ensemble forms of the min-value entropy acquisition; a
     single DeviceGP counts as a list of one"""

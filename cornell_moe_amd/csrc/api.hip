@@ -1156,6 +1156,16 @@ Acq1 ehvi_constrained3(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, 
   return a;
 }
 
+// the three-objective constrained ladder under the log form's name and kernels (K = 0 is taken by the log form itself)
+Acq1 log_ehvi_constrained3(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* gps3,
+                           const moe_gp_t* const* constraint_gps, int num_constraints, const double* thresholds, int num_mcmc,
+                           const double* reference_point, const double* front, int num_front) {
+  Acq1 a = ehvi_constrained3(gps, gps2, gps3, constraint_gps, num_constraints, thresholds, num_mcmc, reference_point, front, num_front);
+  a.name = "the log expected hypervolume improvement";
+  a.call = [=] { return moe::logehvi3_call(num_mcmc, num_constraints, thresholds, reference_point, front, num_front); };
+  return a;
+}
+
 }  // namespace
 }  // extern "C++"
 
@@ -1531,6 +1541,47 @@ int moe_ehvi3_constrained_mcmc_suggest(const moe_gp_t* const* gps, const moe_gp_
   return guarded(err, [&] {
     acq1_suggest(
         ehvi_constrained3(gps, gps2, gps3, constraint_gps, num_constraints, thresholds, num_mcmc, reference_point, front, num_front),
+        outer, domain_bounds, points_being_sampled, num_being_sampled, starts, num_starts, do_gradient_ascent, num_to_sample,
+        {best_points, best_values, found});
+  });
+}
+
+int moe_log_ehvi3_constrained_mcmc(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* gps3,
+                                   const moe_gp_t* const* constraint_gps, int num_constraints, const double* thresholds, int num_mcmc,
+                                   const double* reference_point, const double* front, int num_front, const double* points_being_sampled,
+                                   int num_being_sampled, const double* points, int num_points, int want_grad, double* value, double* grad,
+                                   double* factors_out, moe_error_t* err) {
+  return guarded(err, [&] {
+    acq1_evaluate(
+        log_ehvi_constrained3(gps, gps2, gps3, constraint_gps, num_constraints, thresholds, num_mcmc, reference_point, front, num_front),
+        points_being_sampled, num_being_sampled, points, num_points, want_grad, value, grad, factors_out);
+  });
+}
+
+int moe_log_ehvi3_constrained_mcmc_multistart(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* gps3,
+                                              const moe_gp_t* const* constraint_gps, int num_constraints, const double* thresholds,
+                                              int num_mcmc, const double* reference_point, const double* front, int num_front,
+                                              const moe_gd_params_t* outer, const double* domain_bounds, const double* points_being_sampled,
+                                              int num_being_sampled, const double* starts, int num_starts, int do_gradient_ascent,
+                                              double* best_point, double* best_value, int* found, double* start_values, int* kept_index,
+                                              double* end_points, double* end_values, double* path, int* steps_taken, moe_error_t* err) {
+  return guarded(err, [&] {
+    acq1_multistart(
+        log_ehvi_constrained3(gps, gps2, gps3, constraint_gps, num_constraints, thresholds, num_mcmc, reference_point, front, num_front),
+        outer, domain_bounds, points_being_sampled, num_being_sampled, starts, num_starts, do_gradient_ascent,
+        {best_point, best_value, found, start_values, kept_index, end_points, end_values, path, steps_taken});
+  });
+}
+
+int moe_log_ehvi3_constrained_mcmc_suggest(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* gps3,
+                                           const moe_gp_t* const* constraint_gps, int num_constraints, const double* thresholds,
+                                           int num_mcmc, const double* reference_point, const double* front, int num_front,
+                                           const moe_gd_params_t* outer, const double* domain_bounds, const double* points_being_sampled,
+                                           int num_being_sampled, const double* starts, int num_starts, int do_gradient_ascent,
+                                           int num_to_sample, double* best_points, double* best_values, int* found, moe_error_t* err) {
+  return guarded(err, [&] {
+    acq1_suggest(
+        log_ehvi_constrained3(gps, gps2, gps3, constraint_gps, num_constraints, thresholds, num_mcmc, reference_point, front, num_front),
         outer, domain_bounds, points_being_sampled, num_being_sampled, starts, num_starts, do_gradient_ascent, num_to_sample,
         {best_points, best_values, found});
   });

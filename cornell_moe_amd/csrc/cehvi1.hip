@@ -5,8 +5,9 @@
 // and ninth client of kg1_ascent.hip's staging, ascent and drivers.  The sub-member's chain, layout and check are ehvi1.hip's
 // (ehvi1.hpp); the fronts, the strip kernel (M = 2) and the table and box kernels (M = 3) are ehvi1.hip's and ehvi3.hip's, launched
 // through ehvi1.hpp / ehvi3.hpp over a table of the objective sub-members alone; this file keeps the believed-feasibility kernel,
-// the feasibility kernel, the combine kernel and the description of the call (cehvi1_call, cehvi3_call).  logehvi1.hip, the log form
-// for two objectives, takes the call's record, its layout and the same description under another combine hook (cehvi1.hpp).
+// the feasibility kernel, the combine kernel and the description of the call (cehvi1_call, cehvi3_call).  logehvi1.hip and
+// logehvi3.hip, the log forms for two and for three objectives, take the call's record, its layout and the same description under
+// another combine hook (cehvi1.hpp).
 //
 // Minimisation.  A call takes E joint hyper-samples, M in {2, 3} objectives and K constraints, 1 <= K <= 8 here (K = 0 is the
 // unconstrained client itself).  Member e is M + K GPs, the E (M + K) GPs being the SUB-MEMBERS of one Kg1Ensemble ordered
@@ -293,7 +294,7 @@ CehviCall constraints_of(int M, int num_constraints, const double* thresholds) {
 
 }  // namespace
 
-// what logehvi1.hip takes (cehvi1.hpp)
+// what logehvi1.hip and logehvi3.hip take (cehvi1.hpp)
 CehviLayout cehvi_layout(const Kg1Ensemble& T) { return layout_of(T); }
 
 CehviCall cehvi_constraints_of(int M, int num_constraints, const double* thresholds) { return constraints_of(M, num_constraints, thresholds); }

@@ -1,5 +1,5 @@
-// cornell_moe_amd/csrc/cehvi1.hpp -- what cehvi1.hip (the constrained expected hypervolume improvement) lends to logehvi1.hip (its log
-// form for two objectives): the call's record, where its device memory lies, and the description of a call whose members, fronts,
+// cornell_moe_amd/csrc/cehvi1.hpp -- what cehvi1.hip (the constrained expected hypervolume improvement) lends to logehvi1.hip and logehvi3.hip (its log
+// forms for two and for three objectives): the call's record, where its device memory lies, and the description of a call whose members, fronts,
 // believed-feasibility mask, pending-row extension and greedy hand-over are cehvi1.hip's while the rule that combines the members is
 // the borrower's.  The host functions are compiled once in cehvi1.hip.
 #pragma once

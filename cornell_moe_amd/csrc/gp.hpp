@@ -301,7 +301,7 @@ void kg1_clear_fail(int* fail, int count, hipStream_t s);  // INT_MAX: no candid
 // The ensemble forms of the one-point acquisitions: evaluate at points, multistart ascent and greedy batches of each, with pending
 // points [num_pending][dim] by the Kriging-believer fantasy of kg1_pending.hip.  Every client describes its call in one function
 // (kg1_ascent.hpp: kg1_call, ei1_call, gibbon1_call, cei1_call, ehvi1_call, logcei1_call, ehvi3_call, cehvi1_call, cehvi3_call,
-// logehvi1_call) and the three drivers of kg1_ascent.hip run it; here are the checks that need no handle, which the entry points
+// logehvi1_call, logehvi3_call) and the three drivers of kg1_ascent.hip run it; here are the checks that need no handle, which the entry points
 // make first, and the limits.
 // kg1_opt.hip: the discretised knowledge gradient (moe_kg_discrete_mcmc*).  discrete_all: the members' sets back to back.
 void check_kg_discrete_ensemble_shapes(int num_mcmc, int num_fidelity, const int* num_discrete, int num_points);
@@ -348,7 +348,8 @@ void check_ehvi3_front(const double* reference_point, const double* front, int n
 // M - 1 + k constraint k (satisfied where c_k <= thresholds[k - 1]).  check_ehvi_constrained_shapes: K, the product limit, the
 // arrays K > 0 needs, finite thresholds.  The groups' own values of an evaluation are [E][1 + K][C]: H_e, F_{e,1} .. F_{e,K}.
 // logehvi1.hip: the log of the two-objective form (moe_log_ehvi_constrained_mcmc*), K = 0 included: the same arguments, checks and
-// limits; the groups' own values are the logs L_e, log F_{e,1} .. log F_{e,K}.
+// limits; the groups' own values are the logs L_e, log F_{e,1} .. log F_{e,K}.  logehvi3.hip: the log of the three-objective form
+// (moe_log_ehvi3_constrained_mcmc*), likewise.
 void check_ehvi_constrained_shapes(int num_objectives, int num_mcmc, int num_constraints, const void* constraint_gps,
                                    const double* thresholds);
 // loo.hip: leave-one-out cross-validation on the GP's current factorisation, every one of the N = n (1 + g) scalar observations left

@@ -125,7 +125,7 @@ struct Kg1Call {
   std::shared_ptr<const void> client;
   void (*check_members)(const Kg1Objective& o, const std::vector<GpDev*>& gps, int pending_room) = nullptr;
 };
-// The ten clients' descriptions, one function each (the caller has made the checks that need no handle; the arrays are the
+// The eleven clients' descriptions, one function each (the caller has made the checks that need no handle; the arrays are the
 // caller's and outlive the call).  gp.hpp says what the arguments are.
 Kg1Call kg1_call(int num_fidelity, const double* discrete_all, const int* num_discrete, const double* best_so_far);  // kg1_opt.hip
 Kg1Call ei1_call(const double* best_so_far);                                                                       // ei1.hip
@@ -142,6 +142,8 @@ Kg1Call cehvi3_call(int num_mcmc, int num_constraints, const double* thresholds,
 // (K = 0 is taken by the log form itself)
 Kg1Call logehvi1_call(int num_mcmc, int num_constraints, const double* thresholds, const double* reference_point, const double* front,
                       int num_front);  // logehvi1.hip
+Kg1Call logehvi3_call(int num_mcmc, int num_constraints, const double* thresholds, const double* reference_point, const double* front,
+                      int num_front);  // logehvi3.hip
 
 // what a multistart hands back (all but the first three may be NULL) ...
 struct Kg1MultistartOut {

@@ -5,7 +5,8 @@
 // moe_log_ehvi_constrained_mcmc_suggest): the tenth client of kg1_ascent.hip's staging, ascent and drivers.  The sub-member's chain,
 // layout and check are ehvi1.hip's (ehvi1.hpp); the fronts kept per member in device memory, the join rule, the believed-feasibility
 // mask, the pending-row extension and the greedy batch's hand-over of a pick are cehvi1.hip's (cehvi1.hpp), K = 0 included; this file
-// keeps the log-strip kernel, the log-feasibility kernel, the combine kernel and the description of the call (logehvi1_call).
+// keeps the log-strip kernel, the combine kernel and the description of the call (logehvi1_call); the log-sum-exp record and the
+// log-feasibility kernel, which logehvi3.hip (three objectives) shares, are in logehvi1.hpp.
 //
 // Why.  A member's plain value is a product of two psi factors and K probabilities of feasibility in float64: psi_1 or psi_2 is
 // exactly 0 wherever the candidate's mean lies a few dozen deviations above the reference point in either objective, Phi from 38
@@ -62,65 +63,13 @@
 #include "cehvi1.hpp"
 #include "ehvi1.hpp"
 #include "kg1_ascent.hpp"
+#include "logehvi1.hpp"
 
 namespace moe {
 
 namespace {
 
 constexpr int kLogEhviCap = kEhviMaxFront + kKg1MaxPending;  // a member's front at its largest
-
-// a lane's log-sum-exp over the strips it has seen: their maximum, the weights' sum and the four weighted derivative sums
-struct LogStripRecord {
-  double m, W, S[4];
-};
-
-// the record takes a strip of log l with derivatives dl (the header's rule)
-__device__ __forceinline__ void record_take(LogStripRecord& a, double l, const double* dl, bool wg) {
-#pragma clang fp contract(off)
-  if (l > a.m) {
-    const double sc = exp(a.m - l);  // (exp(-infinity) = 0 for the first strip, W and S being 0)
-    a.W = a.W * sc + 1.0;
-    if (wg) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) a.S[q] = a.S[q] * sc + dl[q];
-    }
-    a.m = l;
-  } else {
-    const double w = exp(l - a.m);
-    a.W = a.W + w;
-    if (wg) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) a.S[q] = a.S[q] + w * dl[q];
-    }
-  }
-}
-
-// one butterfly step: the lane's record and its partner's become their merge, the same bits in both lanes
-__device__ __forceinline__ void record_merge(LogStripRecord& a, int off, bool wg) {
-#pragma clang fp contract(off)
-  LogStripRecord b;
-  b.m = __shfl_xor(a.m, off, 64);
-  b.W = __shfl_xor(a.W, off, 64);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) b.S[q] = __shfl_xor(a.S[q], off, 64);
-  if (b.m == -INFINITY) return;  // (the partner holds no strip; it takes this lane's record below)
-  if (a.m == -INFINITY) {
-    a = b;
-    return;
-  }
-  const double m = fmax(a.m, b.m);
-  const double ea = exp(a.m - m), eb = exp(b.m - m);
-  const double wa = a.W * ea, wb = b.W * eb;
-  a.W = wa + wb;
-  if (wg) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const double sa = a.S[q] * ea, sb = b.S[q] * eb;
-      a.S[q] = sa + sb;
-    }
-  }
-  a.m = m;
-}
 
 // The log strip sums (the header's reduction order).  Grid (ceil(C / 4), E), four wavefronts, one candidate each; kg: the objective
 // sub-members' [mu Cs | var Cs] ordered [e][2]; fronts / counts as ehvi1_front_kernel leaves them; vals [E][Cs] takes L_e and, with
@@ -144,7 +93,7 @@ __global__ __launch_bounds__(256) void logehvi1_strip_kernel(int C, int Cs, cons
   const double mu2 = kg[2 * e + 1][c], var2 = kg[2 * e + 1][(size_t)Cs + c];
   const double s1 = sqrt(fmax(kMinVarGradEI, var1)), s2 = sqrt(fmax(kMinVarGradEI, var2));
   const double ls1 = log(s1), ls2 = log(s2);
-  LogStripRecord rec = {-INFINITY, 0.0, {0.0, 0.0, 0.0, 0.0}};
+  LogStripRecord<4> rec = {-INFINITY, 0.0, {0.0, 0.0, 0.0, 0.0}};
   double carryL = -INFINITY, carryM = 0.0, carryK = 0.0;  // the left edge of strip 0: lambda_1(-infinity)
   for (int s0 = 0; s0 <= n; s0 += 64) {
     const int i = s0 + lane;
@@ -197,35 +146,6 @@ __global__ __launch_bounds__(256) void logehvi1_strip_kernel(int C, int Cs, cons
 #pragma unroll
     for (int q = 0; q < 4; ++q) coef[4 * o + q] = rec.S[q] / rec.W;
   }
-}
-
-// One thread per (member, constraint, candidate): log F and, with want_grad, its derivatives by mu and var (the header's forms)
-// from the constraint sub-member's [mu Cs | var Cs].  kg: the E (2 + K) sub-members'; feas [E][K][Cs][3].
-__global__ __launch_bounds__(256) void logehvi1_feas_kernel(const double* const* __restrict__ kg, int E, int K, const CehviTau tau, int C, int Cs, int want_grad, double* __restrict__ feas) {
-#pragma clang fp contract(off)
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (long)E * K * C) return;
-  const int c = (int)(i % C);
-  const int ek = (int)(i / C), k = ek % K, e = ek / K;
-  const double* src = kg[(size_t)e * (2 + K) + 2 + k];
-  const double mu = src[c], var = src[(size_t)Cs + c];
-  const double sigma = sqrt(fmax(kMinVarGradEI, var));
-  const double z = (tau.t[k] - mu) / sigma;
-  double l, ratio;
-  log_cdf_parts(z, l, ratio);
-  double* out = feas + 3 * ((size_t)ek * Cs + c);
-  out[0] = l;
-  if (want_grad == 0) return;
-  out[1] = -(ratio / sigma);
-  out[2] = -(ratio * z) / (2.0 * (sigma * sigma));
-}
-
-// candidate c's LL_e: L_e and the K log feasibilities added in the order k = 1 .. K
-__device__ __forceinline__ double logehvi1_member_log(const double* __restrict__ hv, const double* __restrict__ feas, int e, int K, int Cs, long c) {
-#pragma clang fp contract(off)
-  double L = hv[(size_t)e * Cs + c];
-  for (int k = 0; k < K; ++k) L = L + feas[3 * (((size_t)e * K + k) * Cs + c)];
-  return L;
 }
 
 // The log-sum-exp over the members, one thread per output element (logcei1_combine_kernel's shape and rule): element i < nv of
@@ -292,8 +212,8 @@ void combine(const Kg1Ensemble& T, int C, double* value_out, double* grad_out) {
                  base + l.l2.oVals, base + l.l2.oCoef);
   if (l.K > 0) {
     const long nf = (long)l.E * l.K * C;
-    MOE_LAUNCH_NOW(logehvi1_feas_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, T.z, T.dKgTab, l.E, l.K, k.tau, C, l.C,
-                   wg ? 1 : 0, base + l.oFeas);
+    MOE_LAUNCH_NOW(logehvi1_feas_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, T.z, T.dKgTab, l.E, 2, l.K, k.tau, C,
+                   l.C, wg ? 1 : 0, base + l.oFeas);
   }
   const long n = (value_out != nullptr ? (long)C : 0) + (wg ? (long)C * T.d : 0);
   MOE_LAUNCH_NOW(logehvi1_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, T.z, l.E, l.K, (long)C, l.C, T.d,

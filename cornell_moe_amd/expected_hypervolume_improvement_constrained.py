@@ -14,8 +14,8 @@ gain.
 
 ``ConstrainedExpectedHypervolumeImprovementMCMC`` carries the method names ``ExpectedHypervolumeImprovementMCMC`` carries.
 ``multistart_constrained_expected_hypervolume_improvement_optimization`` is the whole suggestion; ``feasible_pareto_front`` is the
-bookkeeping around it.  The log form for two objectives is log_expected_hypervolume_improvement.py; the log form for three
-objectives, derivative observations and four or more objectives are out of scope.
+bookkeeping around it.  The log forms for two and for three objectives are log_expected_hypervolume_improvement.py;
+derivative observations and four or more objectives are out of scope.
 """
 import numpy as np
 

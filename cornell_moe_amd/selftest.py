@@ -208,6 +208,25 @@ def check_lcb():
     return bool(ok and _close(std[:8] ** 2, np.diag(var), 1e-10) and _close(mean[:8], G.mean(cand[:8]), 1e-10))
 
 
+def check_log_ehvi3():
+    """exp of the log three-objective constrained expected hypervolume improvement is the plain form's value where that does not
+    underflow; the log form's gradient against central differences of its value."""
+    rng, X, y, hyper = _problem(seed=19)
+    ys = [y, np.cos(2.5 * X + 0.7).sum(1, keepdims=True), ((X - 0.4) ** 2).sum(1, keepdims=True), ((X - 0.5) ** 2).sum(1, keepdims=True)]
+    gps = [api.DeviceGP(hyper * (1.0 + 0.1 * r), X, v, [0.01]) for r, v in enumerate(ys)]
+    objs, cons, tau = [[g] for g in gps[:3]], [[gps[3]]], [0.5]
+    ref = [float(v.max()) + 0.5 for v in ys[:3]]
+    front = np.array([(ref[0] - 2.0, ref[1] - 1.0, ref[2] - 1.5), (ref[0] - 1.0, ref[1] - 2.0, ref[2] - 1.0)])  # (w ascending)
+    pts = rng.uniform(0.1, 0.9, size=(4, 3))
+    pending = rng.uniform(size=(1, 3))
+    log = lambda p, g: api.log_ehvi3_constrained_ensemble(objs, cons, tau, ref, front, p, points_being_sampled=pending, want_grad=g)  # noqa: E731
+    value, grad = log(pts, True)
+    plain = api.ehvi_constrained_ensemble(objs, cons, tau, ref, front, pts, points_being_sampled=pending, want_grad=False)
+    ok = np.all(plain > 1e-6) and _close(np.exp(value), plain, 1e-10) and np.array_equal(log(pts, False), value)
+    fd = np.stack([_fd(lambda q: log(q[None, :], False)[0], x) for x in pts])
+    return bool(ok and _close(grad, fd, 1e-5))
+
+
 CHECKS = (
     ("linear algebra: Cholesky factor and inverse factor", check_linear_algebra),
     ("ping GP mean", check_ping_gp_mean),
@@ -220,6 +239,7 @@ CHECKS = (
     ("random number sources and Latin hypercube", check_random_sources),
     ("optimisers: posterior-mean descent, q-KG multistart", check_optimisers),
     ("LCB selection: q = 1 is the argmin of mean - std, std^2 the variance diagonal", check_lcb),
+    ("log three-objective EHVI: exp of the value is the plain constrained value, ping of its gradient", check_log_ehvi3),
 )
 
 

@@ -844,6 +844,51 @@ int moe_log_ehvi_constrained_mcmc_suggest(const moe_gp_t* const* gps, const moe_
                                           const double* domain_bounds, const double* points_being_sampled, int num_being_sampled,
                                           const double* starts, int num_starts, int do_gradient_ascent, int num_to_sample,
                                           double* best_points, double* best_values, int* found, moe_error_t* err);
+/* The LOG of moe_ehvi3_constrained_mcmc's quantity (three objectives, 0 <= K = num_constraints <= 8; K = 0 is the log of
+ * moe_ehvi3_mcmc's), computed so that it stays finite with a useful gradient where that value and its gradient are exactly 0 in
+ * float64 -- with three psi factors sooner than with two.  Arguments, members, fronts, box tables, the join rule, the
+ * believed-feasible rule for pending points and the limits are moe_ehvi3_constrained_mcmc's; sigma, lambda_r(t), lam, kap, the
+ * feasibility terms, the member's sum and the ensemble's log-sum-exp are moe_log_ehvi_constrained_mcmc's.  For an objective r and
+ * edges a < b the DIFFERENCE RULE is that function's strip rule:
+ *   rho = exp(lambda_r(a) - lambda_r(b)),  log[psi_r(b) - psi_r(a)] = lambda_r(b) + log(1 - rho)  (log1p(-rho) for rho <= 1/2,
+ *   log(-expm1(.)) above),  d/dmu_r = -(lam_b - rho lam_a) / (sigma_r (1 - rho)),  d/dvar_r = (kap_b - rho kap_a) / (2 sigma_r^2
+ *   (1 - rho));  edges that do not give lambda_r(a) < lambda_r(b) in float64 carry weight 0.
+ *   box b of the member's table (left, right, height, slab k):  l_b = ((log P) + lambda_2(height)) + log W_k, log P by the rule
+ *                        from objective 1 at (left, right), log W_k from objective 3 at (w_k, w_{k+1}); every term of the plain
+ *                        sum is P Q W >= 0, so no signed terms arise.  dl_b/d(mu_2, var_2) = (-lam / sigma_2, kap / (2 sigma_2^2))
+ *                        at the height.  A box whose P or W has weight 0 is skipped, not evaluated; the box of slab 0 always counts.
+ *   hypervolume term     L_e = log sum_b exp l_b as a log-sum-exp whose order depends on the member's table alone
+ *                        (csrc/logehvi3.hip), its six coefficients (sum_b w_b dl_b/d.) / W_e.  Never clipped.
+ *   member               LL_e = L_e + log F_{e,1} + ... + log F_{e,K};  g_e = ((((c_mu1 grad mu_1 + c_var1 grad var_1) + c_mu2 grad
+ *                        mu_2) + c_var2 grad var_2) + c_mu3 grad mu_3) + c_var3 grad var_3, then + grad log F_{e,k} for k = 1 .. K
+ * factors_out (may be NULL): [E][1 + K][num_points], L_e, log F_{e,1}, ..., log F_{e,K}; value[i] is what the ensemble rule makes
+ * of them (with E = 1 their sum, bit for bit).  A candidate's bits do not depend on how many share the call, nor on want_grad, nor
+ * on ensemble-wide launches.  No handle is modified.
+ * Errors: moe_ehvi3_constrained_mcmc's, in its order and with its payloads. */
+int moe_log_ehvi3_constrained_mcmc(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* gps3,
+                                   const moe_gp_t* const* constraint_gps, int num_constraints, const double* thresholds, int num_mcmc,
+                                   const double* reference_point, const double* front, int num_front, const double* points_being_sampled,
+                                   int num_being_sampled, const double* points, int num_points, int want_grad, double* value, double* grad,
+                                   double* factors_out, moe_error_t* err);
+/* moe_ehvi3_constrained_mcmc_multistart with moe_log_ehvi3_constrained_mcmc's objective: the same screening, top-20 rule, restarted
+ * ascent and outputs, bit for bit the path a host loop over moe_log_ehvi3_constrained_mcmc walks.  Tensor-product domains only.
+ * Errors: that function's, in its order. */
+int moe_log_ehvi3_constrained_mcmc_multistart(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* gps3,
+                                              const moe_gp_t* const* constraint_gps, int num_constraints, const double* thresholds,
+                                              int num_mcmc, const double* reference_point, const double* front, int num_front,
+                                              const moe_gd_params_t* outer, const double* domain_bounds, const double* points_being_sampled,
+                                              int num_being_sampled, const double* starts, int num_starts, int do_gradient_ascent,
+                                              double* best_point, double* best_value, int* found, double* start_values, int* kept_index,
+                                              double* end_points, double* end_values, double* path, int* steps_taken, moe_error_t* err);
+/* moe_ehvi3_constrained_mcmc_suggest with moe_log_ehvi3_constrained_mcmc's objective: num_to_sample points greedily, bit for bit
+ * what num_to_sample calls of moe_log_ehvi3_constrained_mcmc_multistart return when each is fed its predecessors' points.  Errors:
+ * that function's, in its order. */
+int moe_log_ehvi3_constrained_mcmc_suggest(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, const moe_gp_t* const* gps3,
+                                           const moe_gp_t* const* constraint_gps, int num_constraints, const double* thresholds,
+                                           int num_mcmc, const double* reference_point, const double* front, int num_front,
+                                           const moe_gd_params_t* outer, const double* domain_bounds, const double* points_being_sampled,
+                                           int num_being_sampled, const double* starts, int num_starts, int do_gradient_ascent,
+                                           int num_to_sample, double* best_points, double* best_values, int* found, moe_error_t* err);
 /* compute_grad_variance_of_points -> ComputeGradVarianceOfPoints (gpp_math.cpp:1359-1373); out[num_derivs][m][m][dim] */
 int moe_gp_grad_variance(const moe_gp_t* gp, const double* pts, int num_pts, int num_derivs, double* out, moe_error_t* err);
 /* compute_grad_cholesky_variance_of_points -> ComputeGradCholeskyVarianceOfPoints (gpp_math.cpp:1454-1474) */
