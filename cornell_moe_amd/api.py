@@ -1274,6 +1274,76 @@ def ehvi3_suggest(gps, gps2, gps3, reference_point, front, gd_params, bounds, st
                          points_being_sampled)
 
 
+def _ei_chebyshev_call(objective_gps, scalarisations, best_so_far, num_rounds):
+    """(the arguments in front of the shape's own, E, dim, what must stay alive) of the ensemble forms of the Chebyshev-scalarised
+    expected improvement.  objective_gps: M ensembles shaped alike (a DeviceGPMCMC, a list of DeviceGP or one DeviceGP), E members
+    each; scalarisations [R][2 M] (a, then b); best_so_far [R][E] (one row [E] or one number is spread over the rounds and members)."""
+    objs = list(objective_gps)
+    M = len(objs)
+    members, E, d = [], None, 0
+    for g in objs:
+        arr, Ek, dk, keep = _ensemble_handles([g] if isinstance(g, DeviceGP) else g)
+        if E is None:
+            E, d = Ek, dk
+        if E == 0 or Ek != E:
+            raise BoundsException("one GP per ensemble member and objective", Ek, E, E)
+        members.append(keep)
+    if E is None:
+        raise BoundsException("num_objectives must be between 2 and 8", 0, 2, 8)
+    flat = [members[j][e] for e in range(E) for j in range(M)]
+    arr = (C.c_void_p * max(len(flat), 1))(*[g._h.value for g in flat])
+    R = max(int(num_rounds), 1)
+    scal = np.ascontiguousarray(scalarisations, dtype=np.float64).reshape(-1)
+    if scal.size != R * 2 * M:
+        raise BoundsException("a scalarisation is 2 num_objectives numbers per round", scal.size, R * 2 * M, R * 2 * M)
+    best = np.asarray(best_so_far, dtype=np.float64)
+    if best.size == R * E:
+        best = best.reshape(R, E)
+    elif best.size == 1:
+        best = np.full((R, E), float(best.ravel()[0]))
+    elif best.size == E:
+        best = np.broadcast_to(best.reshape(1, E), (R, E))
+    else:
+        raise BoundsException("one incumbent per round and ensemble member", best.size, R * E, R * E)
+    best = np.ascontiguousarray(best, dtype=np.float64)
+    return (arr, M, E, scal.ctypes.data_as(dp), best.ctypes.data_as(dp)), E, d, (flat, scal, best)
+
+
+def ei_chebyshev_ensemble(objective_gps, scalarisation, best_so_far, points, points_being_sampled=None, want_grad=True,
+                          want_member_values=False):
+    """moe_ei_chebyshev_mcmc: the expected improvement of the weighted Chebyshev scalarisation max_j (a_j Y_j + b_j) of 2 <= M <= 8
+    objectives (minimisation) averaged over the ensemble at points [C][dim], in one device call: a fixed quadrature of a product of
+    normal CDFs, exact to rounding.  Member e is objective_gps[j][e], j = 0 .. M - 1, without derivative observations; E M <= 1024.
+    scalarisation [2 M]: a > 0, then b (chebyshev_scalarisation of expected_scalarised_improvement.py returns that pair);
+    best_so_far [E] (or one number): the members' smallest scalarised values so far.  points_being_sampled [p][dim] condition all M
+    GPs' covariances, and a member's incumbent is lowered to the smallest scalarised outcome it believes of them.  Returns value
+    [C], with want_grad (value, grad [C][dim]), and with want_member_values additionally the members' values [E][C] as the last
+    item.  SingularMatrixException(e M + j, i): the GP, counted flat, and the pending point."""
+    pre, E, d, keep = _ei_chebyshev_call(objective_gps, scalarisation, best_so_far, 1)
+    return _acq1_evaluate(_lib.load().moe_ei_chebyshev_mcmc, pre, (), d, points, want_grad, points_being_sampled,
+                          extra_shape=(E,), want_extra=want_member_values)
+
+
+def ei_chebyshev_multistart(objective_gps, scalarisation, best_so_far, gd_params, bounds, starts, gradient_ascent=True,
+                            want_path=False, points_being_sampled=None):
+    """moe_ei_chebyshev_mcmc_multistart: one suggestion by the ensemble-averaged Chebyshev-scalarised expected improvement --
+    ei_analytic_multistart's screening, 20 kept starts, restarted ascent on the device and end-point selection, and its dict."""
+    pre, E, d, keep = _ei_chebyshev_call(objective_gps, scalarisation, best_so_far, 1)
+    return _acq1_multistart(_lib.load().moe_ei_chebyshev_mcmc_multistart, pre, (), d, gd_params, bounds, starts, gradient_ascent,
+                            want_path, points_being_sampled)
+
+
+def ei_chebyshev_suggest(objective_gps, scalarisations, best_so_far, gd_params, bounds, starts, num_to_sample, gradient_ascent=True,
+                         points_being_sampled=None):
+    """moe_ei_chebyshev_mcmc_suggest: num_to_sample points greedily, point t under scalarisations[t] [2 M] and the incumbents
+    best_so_far[t] [E] -- round t is ei_chebyshev_multistart with that scalarisation from the same starts [S][dim] with the pending
+    points points_being_sampled [p][dim] (may be None) followed by the points of the rounds before, bit for bit, in one device
+    call.  p + num_to_sample - 1 <= 64.  Returns a dict: points [q][dim], values [q], found [q]."""
+    pre, E, d, keep = _ei_chebyshev_call(objective_gps, scalarisations, best_so_far, num_to_sample)
+    return _acq1_suggest(_lib.load().moe_ei_chebyshev_mcmc_suggest, pre, (), d, gd_params, bounds, starts, num_to_sample,
+                         gradient_ascent, points_being_sampled)
+
+
 def _ehvi_constrained_call(objective_gps, constraint_gps, thresholds, reference_point, front):
     """(which entry points: "ehvi" or "ehvi3", the arguments in front of the shape's own, E, dim, K, what must stay alive) of the
     ensemble forms of the constrained expected hypervolume improvement.  objective_gps: 2 or 3 ensembles shaped alike (a

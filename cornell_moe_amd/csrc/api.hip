@@ -1166,6 +1166,23 @@ Acq1 log_ehvi_constrained3(const moe_gp_t* const* gps, const moe_gp_t* const* gp
   return a;
 }
 
+// The GPs of a Chebyshev call come flat, ordered [e][objective].  The two checks that come before the arrays' are made here, where
+// the number of objectives is known (Acq1::check_num_mcmc sees num_mcmc alone).
+Acq1 ei_chebyshev(const moe_gp_t* const* objective_gps, int num_objectives, int num_mcmc, int num_rounds, const double* scalarisations,
+                  const double* best_so_far) {
+  moe::check_chebei_objectives(num_objectives, num_mcmc);
+  Acq1 a = acq1_of(objective_gps, num_mcmc, "the Chebyshev-scalarised expected improvement");
+  a.check_num_mcmc = [](int) {};
+  a.pointers = objective_gps && scalarisations && best_so_far;
+  a.check_shapes = [=](int num_points) {
+    moe::check_chebei_values(num_objectives, num_mcmc, num_rounds, scalarisations, best_so_far);
+    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_points);
+  };
+  a.handles = [=] { return std::vector<const moe_gp_t*>(objective_gps, objective_gps + (size_t)num_mcmc * num_objectives); };
+  a.call = [=] { return moe::chebei1_call(num_mcmc, num_objectives, std::max(num_rounds, 1), scalarisations, best_so_far); };
+  return a;
+}
+
 }  // namespace
 }  // extern "C++"
 
@@ -1422,6 +1439,40 @@ int moe_ehvi3_mcmc_suggest(const moe_gp_t* const* gps, const moe_gp_t* const* gp
   return guarded(err, [&] {
     acq1_suggest(ehvi3(gps, gps2, gps3, num_mcmc, reference_point, front, num_front), outer, domain_bounds, points_being_sampled,
                  num_being_sampled, starts, num_starts, do_gradient_ascent, num_to_sample, {best_points, best_values, found});
+  });
+}
+
+int moe_ei_chebyshev_mcmc(const moe_gp_t* const* objective_gps, int num_objectives, int num_mcmc, const double* scalarisations,
+                          const double* best_so_far, const double* points_being_sampled, int num_being_sampled, const double* points,
+                          int num_points, int want_grad, double* value, double* grad, double* member_values_out, moe_error_t* err) {
+  return guarded(err, [&] {
+    acq1_evaluate(ei_chebyshev(objective_gps, num_objectives, num_mcmc, 1, scalarisations, best_so_far), points_being_sampled,
+                  num_being_sampled, points, num_points, want_grad, value, grad, member_values_out);
+  });
+}
+
+int moe_ei_chebyshev_mcmc_multistart(const moe_gp_t* const* objective_gps, int num_objectives, int num_mcmc,
+                                     const double* scalarisations, const double* best_so_far, const moe_gd_params_t* outer,
+                                     const double* domain_bounds, const double* points_being_sampled, int num_being_sampled,
+                                     const double* starts, int num_starts, int do_gradient_ascent, double* best_point,
+                                     double* best_value, int* found, double* start_values, int* kept_index, double* end_points,
+                                     double* end_values, double* path, int* steps_taken, moe_error_t* err) {
+  return guarded(err, [&] {
+    acq1_multistart(ei_chebyshev(objective_gps, num_objectives, num_mcmc, 1, scalarisations, best_so_far), outer, domain_bounds,
+                    points_being_sampled, num_being_sampled, starts, num_starts, do_gradient_ascent,
+                    {best_point, best_value, found, start_values, kept_index, end_points, end_values, path, steps_taken});
+  });
+}
+
+int moe_ei_chebyshev_mcmc_suggest(const moe_gp_t* const* objective_gps, int num_objectives, int num_mcmc, const double* scalarisations,
+                                  const double* best_so_far, const moe_gd_params_t* outer, const double* domain_bounds,
+                                  const double* points_being_sampled, int num_being_sampled, const double* starts, int num_starts,
+                                  int do_gradient_ascent, int num_to_sample, double* best_points, double* best_values, int* found,
+                                  moe_error_t* err) {
+  return guarded(err, [&] {
+    acq1_suggest(ei_chebyshev(objective_gps, num_objectives, num_mcmc, num_to_sample, scalarisations, best_so_far), outer,
+                 domain_bounds, points_being_sampled, num_being_sampled, starts, num_starts, do_gradient_ascent, num_to_sample,
+                 {best_points, best_values, found});
   });
 }
 

@@ -16,7 +16,7 @@ bookkeeping around it.
 Three objectives (error, cost and latency, say) have the same four under the names ``pareto_front_3``, ``hypervolume_3``,
 ``ExpectedHypervolumeImprovement3MCMC`` and ``multistart_expected_hypervolume_improvement_3_optimization``: three GPs per
 hyper-sample, and the quantity an exact sum over the boxes of the non-dominated region, cut into slabs by the third objective
-(csrc/ehvi3.hip).  Four or more objectives are out of scope.
+(csrc/ehvi3.hip).  Four or more objectives: expected_scalarised_improvement.py.
 """
 import numpy as np
 

@@ -889,6 +889,70 @@ int moe_log_ehvi3_constrained_mcmc_suggest(const moe_gp_t* const* gps, const moe
                                            const moe_gd_params_t* outer, const double* domain_bounds, const double* points_being_sampled,
                                            int num_being_sampled, const double* starts, int num_starts, int do_gradient_ascent,
                                            int num_to_sample, double* best_points, double* best_values, int* found, moe_error_t* err);
+/* The Chebyshev-scalarised expected improvement for 2 <= M = num_objectives <= 8 objectives (ParEGO, Knowles 2006; the analytic
+ * one-point form of qParEGO, Daulton et al. 2020), averaged over a hyper-parameter ensemble, at points [num_points][dim], with
+ * pending points.  Minimisation.  Member e is M GPs, objective_gps[e * M + j] (one flat array [E][M]), without derivative
+ * observations; E M <= 1024.  scalarisations [R][2 M]: a_0 .. a_{M-1} > 0, then b_0 .. b_{M-1}, all finite (from weights w, an
+ * ideal and a nadir point: a_j = w_j / (nadir_j - ideal_j), b_j = -a_j ideal_j); best_so_far [R][E]: the members' incumbents, the
+ * smallest scalarised value observed, finite.  R = 1 here and in the multistart call.  With mu_j, var_j the posterior mean and the
+ * conditioned latent variance of GP j at x, sigma_j = sqrt(max(150 eps^2, var_j)) for the value and the gradient alike,
+ * s_j = a_j mu_j + b_j (product and sum each rounded), tau_j = a_j sigma_j, L = max_j (s_j - 38 tau_j):
+ *   member value   A_e = E[(g*_e - max_j (a_j Y_j + b_j))^+] = integral over L <= t <= g*_e of prod_j Phi((t - s_j) / tau_j);
+ *                  exactly 0, with zero coefficients, where g*_e <= L (L is a constant in the gradient)
+ *   coefficients   dA/dmu_j = -a_j integral phi(z_j) / tau_j prod_{k != j} Phi(z_k),  dA/dvar_j = -(a_j / (2 sigma_j)) integral
+ *                  z_j phi(z_j) / tau_j prod_{k != j} Phi(z_k),  z_j = (t - s_j) / tau_j; the products without j are formed from
+ *                  prefix and suffix products, never by a division
+ *   quadrature     FIXED: the 14 M + 2 breakpoints s_j + c tau_j, c in {-38, -8, -6, -4, -3, -2, -1, 0, 1, 2, 3, 4, 6, 8}, each
+ *                  clamped to [L, g*_e], with L and g*_e, sorted ascending (list position 14 j + the place of c, then L, then
+ *                  g*_e, breaks ties); on each of the 14 M + 1 panels the 8-point Gauss-Legendre rule; a panel of zero width
+ *                  contributes an exact 0.  The sum's order depends on M alone (csrc/chebei1.hip).
+ *   ensemble       value[i] = (A_0 + ... + A_{E-1}) / E; grad: per member sum_j (c_mu_j grad mu_j + c_var_j grad var_j) in the order
+ *                  of j, mu before var; members added in member order and divided once
+ * Pending points: the variances of all M GPs are conditioned on them (the means are left alone); member e keeps the believed
+ * outcomes mu_{e,j}(P_i) and its incumbent is g*_e = min(best_so_far[e], min_i max_j (a_j mu_{e,j}(P_i) + b_j)) over the pending
+ * points whose scalarised outcome is finite.
+ * member_values_out (may be NULL): [E][num_points], every A_e; value[i] is, bit for bit, their mean formed in member order on the
+ * host.  A candidate's bits do not depend on how many share the call, nor on want_grad, nor on ensemble-wide launches.  No handle
+ * is modified.
+ * Errors, in this order, everything that needs no handle before a handle or the device is touched: num_objectives outside 2 .. 8
+ * -> MOE_ERR_BOUNDS, payload (num_objectives, 2, 8); num_mcmc < 1 or num_mcmc num_objectives > 1024 -> MOE_ERR_BOUNDS, payload
+ * (num_mcmc, 1, 1024 / num_objectives rounded down); a NULL array (objective_gps, scalarisations, best_so_far, points, value, grad
+ * with want_grad) -> MOE_ERR_RUNTIME; an a_j that is not positive, or an a_j or b_j that is not finite -> MOE_ERR_INVALID_VALUE,
+ * payload (the value, its flat index in scalarisations, 0); an incumbent that is not finite -> MOE_ERR_INVALID_VALUE, payload (the
+ * value, its flat index in best_so_far, 1); num_points < 1 -> MOE_ERR_BOUNDS; num_being_sampled outside 0 .. 64 -> MOE_ERR_BOUNDS;
+ * points_being_sampled NULL with num_being_sampled > 0 -> MOE_ERR_RUNTIME; then, "member" counting the GPs flat as e M + j: a NULL
+ * handle -> MOE_ERR_RUNTIME; a GP of another dim, then of another device -> MOE_ERR_INVALID_VALUE; a GP with derivative
+ * observations -> MOE_ERR_INVALID_VALUE, payload (its num_derivatives, 0, the flat index); a handle listed twice ->
+ * MOE_ERR_INVALID_VALUE.  MOE_ERR_SINGULAR only for a pending point: payload (the flat index of the first failing GP, the pending
+ * point).  A candidate never raises. */
+int moe_ei_chebyshev_mcmc(const moe_gp_t* const* objective_gps, int num_objectives, int num_mcmc, const double* scalarisations,
+                          const double* best_so_far, const double* points_being_sampled, int num_being_sampled, const double* points,
+                          int num_points, int want_grad, double* value, double* grad, double* member_values_out, moe_error_t* err);
+/* One suggestion by moe_ei_chebyshev_mcmc's objective, the whole loop on the device, as moe_ehvi3_mcmc_multistart is for
+ * moe_ehvi3_mcmc: the path is, bit for bit, the one a host loop over moe_ei_chebyshev_mcmc walks.  Tensor-product domains only.
+ * Errors, in this order: those of moe_ei_chebyshev_mcmc that need no handle (outer, domain_bounds, starts, best_point, best_value
+ * and found among the arrays that must not be NULL; num_starts for num_points); max_num_steps < 1 with do_gradient_ascent != 0 ->
+ * MOE_ERR_BOUNDS; domain_type other than MOE_DOMAIN_TENSOR_PRODUCT -> MOE_ERR_INVALID_VALUE; then those that need the handles. */
+int moe_ei_chebyshev_mcmc_multistart(const moe_gp_t* const* objective_gps, int num_objectives, int num_mcmc,
+                                     const double* scalarisations, const double* best_so_far, const moe_gd_params_t* outer,
+                                     const double* domain_bounds, const double* points_being_sampled, int num_being_sampled,
+                                     const double* starts, int num_starts, int do_gradient_ascent, double* best_point,
+                                     double* best_value, int* found, double* start_values, int* kept_index, double* end_points,
+                                     double* end_values, double* path, int* steps_taken, moe_error_t* err);
+/* num_to_sample points greedily with a scalarisation of its own per point: scalarisations [num_to_sample][2 M] and best_so_far
+ * [num_to_sample][E].  Round t is moe_ei_chebyshev_mcmc_multistart from the same starts with scalarisation t, row t of best_so_far
+ * and pending points = points_being_sampled followed by the picks of the rounds before -- bit for bit what num_to_sample calls of
+ * that function return when each is fed its predecessors' points.  Staged once; a round appends ONE row to the extension of each
+ * of the E M GPs and the pick's believed outcomes to every member's list, from which the round's incumbents are formed, inside
+ * device memory.
+ * Errors: those of moe_ei_chebyshev_mcmc_multistart, every row of scalarisations and best_so_far checked (num_to_sample < 1 reads
+ * as one row there), with num_to_sample < 1 or num_being_sampled + num_to_sample - 1 > 64 -> MOE_ERR_BOUNDS behind
+ * num_being_sampled. */
+int moe_ei_chebyshev_mcmc_suggest(const moe_gp_t* const* objective_gps, int num_objectives, int num_mcmc, const double* scalarisations,
+                                  const double* best_so_far, const moe_gd_params_t* outer, const double* domain_bounds,
+                                  const double* points_being_sampled, int num_being_sampled, const double* starts, int num_starts,
+                                  int do_gradient_ascent, int num_to_sample, double* best_points, double* best_values, int* found,
+                                  moe_error_t* err);
 /* compute_grad_variance_of_points -> ComputeGradVarianceOfPoints (gpp_math.cpp:1359-1373); out[num_derivs][m][m][dim] */
 int moe_gp_grad_variance(const moe_gp_t* gp, const double* pts, int num_pts, int num_derivs, double* out, moe_error_t* err);
 /* compute_grad_cholesky_variance_of_points -> ComputeGradCholeskyVarianceOfPoints (gpp_math.cpp:1454-1474) */
