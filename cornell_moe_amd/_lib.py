@@ -142,6 +142,13 @@ SIGNATURES = {
                                                    C.c_int, dp, dp, ip, dp, ip, dp, dp, dp, ip, _EP]),
     "moe_ei_chebyshev_mcmc_suggest": (C.c_int, [_GPA, C.c_int, C.c_int, dp, dp, C.POINTER(GdParams), dp, dp, C.c_int, dp, C.c_int,
                                                 C.c_int, C.c_int, dp, dp, ip, _EP]),
+    "moe_log_ei_chebyshev_constrained_mcmc": (C.c_int, [_GPA, C.c_int, _GPA, C.c_int, dp, C.c_int, dp, dp, dp, C.c_int, dp, C.c_int,
+                                                        C.c_int, dp, dp, dp, _EP]),
+    "moe_log_ei_chebyshev_constrained_mcmc_multistart": (C.c_int, [_GPA, C.c_int, _GPA, C.c_int, dp, C.c_int, dp, dp,
+                                                                   C.POINTER(GdParams), dp, dp, C.c_int, dp, C.c_int, C.c_int, dp, dp, ip,
+                                                                   dp, ip, dp, dp, dp, ip, _EP]),
+    "moe_log_ei_chebyshev_constrained_mcmc_suggest": (C.c_int, [_GPA, C.c_int, _GPA, C.c_int, dp, C.c_int, dp, dp, C.POINTER(GdParams),
+                                                                dp, dp, C.c_int, dp, C.c_int, C.c_int, C.c_int, dp, dp, ip, _EP]),
     "moe_gp_grad_variance": (C.c_int, [_GP, dp, C.c_int, C.c_int, dp, _EP]),
     "moe_gp_grad_cholesky_variance": (C.c_int, [_GP, dp, C.c_int, C.c_int, dp, _EP]),
     "moe_posterior_mean": (C.c_int, [_GP, C.c_int, dp, dp, dp, _EP]),

@@ -1344,6 +1344,62 @@ def ei_chebyshev_suggest(objective_gps, scalarisations, best_so_far, gd_params, 
                          gradient_ascent, points_being_sampled)
 
 
+def _log_ei_chebyshev_call(objective_gps, constraint_gps, thresholds, scalarisations, best_so_far, num_rounds):
+    """(the arguments in front of the shape's own, E, dim, K, what must stay alive) of the log forms of the Chebyshev-scalarised
+    expected improvement: _ei_chebyshev_call's with constraint_gps, K ensembles shaped like the objectives' (None: K = 0), passed
+    flat as [K][E], and thresholds [K] behind the objectives."""
+    pre, E, d, keep = _ei_chebyshev_call(objective_gps, scalarisations, best_so_far, num_rounds)
+    cons = [] if constraint_gps is None else list(constraint_gps)
+    K = len(cons)
+    tau = np.ascontiguousarray([] if thresholds is None else thresholds, dtype=np.float64).ravel()
+    if tau.size != K:
+        raise BoundsException("one threshold per constraint", tau.size, K, K)
+    flat = []
+    for c in cons:
+        members = [c] if isinstance(c, DeviceGP) else (list(c.gps) if isinstance(c, DeviceGPMCMC) else list(c))
+        if len(members) != E:
+            raise BoundsException("one constraint GP per ensemble member and constraint", len(members), E, E)
+        flat += members  # [K][E]
+    carr = (C.c_void_p * max(len(flat), 1))(*[g._h.value for g in flat]) if K else None
+    arr, M, E_, scal, best = pre
+    return (arr, M, carr, K, tau.ctypes.data_as(dp) if K else None, E_, scal, best), E, d, K, (keep, flat, tau, carr)
+
+
+def log_ei_chebyshev_constrained_ensemble(objective_gps, constraint_gps, thresholds, scalarisation, best_so_far, points,
+                                          points_being_sampled=None, want_grad=True, want_factors=False):
+    """moe_log_ei_chebyshev_constrained_mcmc: the LOG of ei_chebyshev_ensemble's member value times the probabilities of feasibility,
+    under the ensemble's log-sum-exp, at points [C][dim] in one device call -- finite with a useful gradient where the plain form
+    and its gradient are exactly 0.  objective_gps, scalarisation and best_so_far as there (every incumbent finite, that of the
+    FEASIBLE observations); member e's constraint GPs are constraint_gps[k][e], constraint k satisfied where c_k(x) <=
+    thresholds[k] (0 <= K <= 8; None: K = 0); E (M + K) <= 1024.  points_being_sampled [p][dim] condition every GP's covariance; a
+    pending point's scalarised outcome lowers member e's incumbent only where the member believes the point feasible.  Returns
+    value [C], with want_grad (value, grad [C][dim]), and with want_factors additionally log_factors [E][1 + K][C] (LA_e, then log
+    F_{e,1..K}) as the last item.  SingularMatrixException(e (M + K) + role, j): the GP, counted flat, and the pending point."""
+    pre, E, d, K, keep = _log_ei_chebyshev_call(objective_gps, constraint_gps, thresholds, scalarisation, best_so_far, 1)
+    return _acq1_evaluate(_lib.load().moe_log_ei_chebyshev_constrained_mcmc, pre, (), d, points, want_grad, points_being_sampled,
+                          extra_shape=(E, 1 + K), want_extra=want_factors)
+
+
+def log_ei_chebyshev_constrained_multistart(objective_gps, constraint_gps, thresholds, scalarisation, best_so_far, gd_params, bounds,
+                                            starts, gradient_ascent=True, want_path=False, points_being_sampled=None):
+    """moe_log_ei_chebyshev_constrained_mcmc_multistart: one suggestion by log_ei_chebyshev_constrained_ensemble's objective --
+    ei_analytic_multistart's screening, 20 kept starts, restarted ascent on the device and end-point selection, and its dict."""
+    pre, E, d, K, keep = _log_ei_chebyshev_call(objective_gps, constraint_gps, thresholds, scalarisation, best_so_far, 1)
+    return _acq1_multistart(_lib.load().moe_log_ei_chebyshev_constrained_mcmc_multistart, pre, (), d, gd_params, bounds, starts,
+                            gradient_ascent, want_path, points_being_sampled)
+
+
+def log_ei_chebyshev_constrained_suggest(objective_gps, constraint_gps, thresholds, scalarisations, best_so_far, gd_params, bounds,
+                                         starts, num_to_sample, gradient_ascent=True, points_being_sampled=None):
+    """moe_log_ei_chebyshev_constrained_mcmc_suggest: num_to_sample points greedily, point t under scalarisations[t] [2 M] and the
+    incumbents best_so_far[t] [E] -- round t is log_ei_chebyshev_constrained_multistart with that scalarisation from the same starts
+    with points_being_sampled followed by the points of the rounds before, bit for bit, in one device call.  p + num_to_sample - 1
+    <= 64.  Returns a dict: points [q][dim], values [q], found [q]."""
+    pre, E, d, K, keep = _log_ei_chebyshev_call(objective_gps, constraint_gps, thresholds, scalarisations, best_so_far, num_to_sample)
+    return _acq1_suggest(_lib.load().moe_log_ei_chebyshev_constrained_mcmc_suggest, pre, (), d, gd_params, bounds, starts,
+                         num_to_sample, gradient_ascent, points_being_sampled)
+
+
 def _ehvi_constrained_call(objective_gps, constraint_gps, thresholds, reference_point, front):
     """(which entry points: "ehvi" or "ehvi3", the arguments in front of the shape's own, E, dim, K, what must stay alive) of the
     ensemble forms of the constrained expected hypervolume improvement.  objective_gps: 2 or 3 ensembles shaped alike (a

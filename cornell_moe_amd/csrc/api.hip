@@ -1183,6 +1183,40 @@ Acq1 ei_chebyshev(const moe_gp_t* const* objective_gps, int num_objectives, int 
   return a;
 }
 
+// The GPs of a log Chebyshev call, flat and ordered [e][role]: member e's M objectives, objective_gps[e M + j], then its
+// constraint GPs constraint_gps[k E + e]
+std::vector<const moe_gp_t*> log_chebyshev_handles(const moe_gp_t* const* objective_gps, int M, const moe_gp_t* const* constraint_gps,
+                                                  int K, int num_mcmc) {
+  const int G = M + K;
+  std::vector<const moe_gp_t*> flat((size_t)num_mcmc * G);
+  for (int e = 0; e < num_mcmc; ++e) {
+    for (int j = 0; j < M; ++j) flat[(size_t)e * G + j] = objective_gps[(size_t)e * M + j];
+    for (int k = 0; k < K; ++k) flat[(size_t)e * G + M + k] = constraint_gps[(size_t)k * num_mcmc + e];
+  }
+  return flat;
+}
+
+// ei_chebyshev's ladder with the constraints: M, K and the product limit first, then the arrays (those K > 0 needs among them),
+// then every a, b, threshold and incumbent
+Acq1 log_ei_chebyshev(const moe_gp_t* const* objective_gps, int num_objectives, const moe_gp_t* const* constraint_gps,
+                      int num_constraints, const double* thresholds, int num_mcmc, int num_rounds, const double* scalarisations,
+                      const double* best_so_far) {
+  moe::check_logchebei_shapes(num_objectives, num_constraints, num_mcmc);
+  Acq1 a = acq1_of(objective_gps, num_mcmc, "the log Chebyshev-scalarised expected improvement");
+  a.check_num_mcmc = [](int) {};
+  a.pointers = objective_gps && scalarisations && best_so_far && (num_constraints == 0 || (constraint_gps && thresholds));
+  a.check_shapes = [=](int num_points) {
+    moe::check_logchebei_values(num_objectives, num_constraints, num_mcmc, num_rounds, scalarisations, thresholds, best_so_far);
+    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_points);
+  };
+  a.handles = [=] { return log_chebyshev_handles(objective_gps, num_objectives, constraint_gps, num_constraints, num_mcmc); };
+  a.call = [=] {
+    return moe::logchebei1_call(num_mcmc, num_objectives, num_constraints, thresholds, std::max(num_rounds, 1), scalarisations,
+                                best_so_far);
+  };
+  return a;
+}
+
 }  // namespace
 }  // extern "C++"
 
@@ -1472,6 +1506,49 @@ int moe_ei_chebyshev_mcmc_suggest(const moe_gp_t* const* objective_gps, int num_
   return guarded(err, [&] {
     acq1_suggest(ei_chebyshev(objective_gps, num_objectives, num_mcmc, num_to_sample, scalarisations, best_so_far), outer,
                  domain_bounds, points_being_sampled, num_being_sampled, starts, num_starts, do_gradient_ascent, num_to_sample,
+                 {best_points, best_values, found});
+  });
+}
+
+int moe_log_ei_chebyshev_constrained_mcmc(const moe_gp_t* const* objective_gps, int num_objectives, const moe_gp_t* const* constraint_gps,
+                                          int num_constraints, const double* thresholds, int num_mcmc, const double* scalarisations,
+                                          const double* best_so_far, const double* points_being_sampled, int num_being_sampled,
+                                          const double* points, int num_points, int want_grad, double* value, double* grad,
+                                          double* factors_out, moe_error_t* err) {
+  return guarded(err, [&] {
+    acq1_evaluate(log_ei_chebyshev(objective_gps, num_objectives, constraint_gps, num_constraints, thresholds, num_mcmc, 1,
+                                   scalarisations, best_so_far),
+                  points_being_sampled, num_being_sampled, points, num_points, want_grad, value, grad, factors_out);
+  });
+}
+
+int moe_log_ei_chebyshev_constrained_mcmc_multistart(const moe_gp_t* const* objective_gps, int num_objectives,
+                                                     const moe_gp_t* const* constraint_gps, int num_constraints, const double* thresholds,
+                                                     int num_mcmc, const double* scalarisations, const double* best_so_far,
+                                                     const moe_gd_params_t* outer, const double* domain_bounds,
+                                                     const double* points_being_sampled, int num_being_sampled, const double* starts,
+                                                     int num_starts, int do_gradient_ascent, double* best_point, double* best_value,
+                                                     int* found, double* start_values, int* kept_index, double* end_points,
+                                                     double* end_values, double* path, int* steps_taken, moe_error_t* err) {
+  return guarded(err, [&] {
+    acq1_multistart(log_ei_chebyshev(objective_gps, num_objectives, constraint_gps, num_constraints, thresholds, num_mcmc, 1,
+                                     scalarisations, best_so_far),
+                    outer, domain_bounds, points_being_sampled, num_being_sampled, starts, num_starts, do_gradient_ascent,
+                    {best_point, best_value, found, start_values, kept_index, end_points, end_values, path, steps_taken});
+  });
+}
+
+int moe_log_ei_chebyshev_constrained_mcmc_suggest(const moe_gp_t* const* objective_gps, int num_objectives,
+                                                  const moe_gp_t* const* constraint_gps, int num_constraints, const double* thresholds,
+                                                  int num_mcmc, const double* scalarisations, const double* best_so_far,
+                                                  const moe_gd_params_t* outer, const double* domain_bounds,
+                                                  const double* points_being_sampled, int num_being_sampled, const double* starts,
+                                                  int num_starts, int do_gradient_ascent, int num_to_sample, double* best_points,
+                                                  double* best_values, int* found, moe_error_t* err) {
+  return guarded(err, [&] {
+    acq1_suggest(log_ei_chebyshev(objective_gps, num_objectives, constraint_gps, num_constraints, thresholds, num_mcmc, num_to_sample,
+                                  scalarisations, best_so_far),
+                 outer, domain_bounds, points_being_sampled, num_being_sampled, starts, num_starts, do_gradient_ascent, num_to_sample,
                  {best_points, best_values, found});
   });
 }

@@ -301,7 +301,7 @@ void kg1_clear_fail(int* fail, int count, hipStream_t s);  // INT_MAX: no candid
 // The ensemble forms of the one-point acquisitions: evaluate at points, multistart ascent and greedy batches of each, with pending
 // points [num_pending][dim] by the Kriging-believer fantasy of kg1_pending.hip.  Every client describes its call in one function
 // (kg1_ascent.hpp: kg1_call, ei1_call, gibbon1_call, cei1_call, ehvi1_call, logcei1_call, ehvi3_call, cehvi1_call, cehvi3_call,
-// logehvi1_call, logehvi3_call, chebei1_call) and the three drivers of kg1_ascent.hip run it; here are the checks that need no handle, which the entry points
+// logehvi1_call, logehvi3_call, chebei1_call, logchebei1_call) and the three drivers of kg1_ascent.hip run it; here are the checks that need no handle, which the entry points
 // make first, and the limits.
 // kg1_opt.hip: the discretised knowledge gradient (moe_kg_discrete_mcmc*).  discrete_all: the members' sets back to back.
 void check_kg_discrete_ensemble_shapes(int num_mcmc, int num_fidelity, const int* num_discrete, int num_points);
@@ -360,6 +360,13 @@ constexpr int kChebMinObjectives = 2;
 constexpr int kChebMaxObjectives = 8;
 void check_chebei_objectives(int num_objectives, int num_mcmc);
 void check_chebei_values(int num_objectives, int num_mcmc, int num_rounds, const double* scalarisations, const double* best_so_far);
+// logchebei1.hip: the log of the same with 0 <= K <= 8 constraints (moe_log_ei_chebyshev_constrained_mcmc*): members of M + K GPs
+// each, the GPs of a call [E (M + K)] ordered [e][role], the objectives first.  check_logchebei_shapes: M, K, then the product
+// limit; check_logchebei_values: every a, b, threshold and incumbent (all finite).  The groups' own values of an evaluation are
+// [E][1 + K][C]: LA_e, log F_{e,1} .. log F_{e,K}.
+void check_logchebei_shapes(int num_objectives, int num_constraints, int num_mcmc);
+void check_logchebei_values(int num_objectives, int num_constraints, int num_mcmc, int num_rounds, const double* scalarisations,
+                            const double* thresholds, const double* best_so_far);
 // loo.hip: leave-one-out cross-validation on the GP's current factorisation, every one of the N = n (1 + g) scalar observations left
 // out by itself.  mean_out / var_out [n][1 + g]: the LOO predictive mean (function values in the caller's units) and variance.
 void loo_predict_on_device(GpDev& gp, double* mean_out, double* var_out);

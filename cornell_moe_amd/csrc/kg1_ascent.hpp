@@ -13,7 +13,9 @@
 // (the log of the two-objective constrained expected hypervolume improvement, the tenth: cehvi1.hip's groups and fronts under a
 // log-sum-exp over the strips and over the members, taken with K = 0 too) and logehvi3.hip (the log of the three-objective one, the
 // eleventh) and chebei1.hip (the Chebyshev-scalarised expected improvement for 2 to 8 objectives, the twelfth: groups of M GPs on
-// ehvi1.hip's chain, a fixed quadrature per member, and a scalarisation and incumbents of its own for every point of a batch).
+// ehvi1.hip's chain, a fixed quadrature per member, and a scalarisation and incumbents of its own for every point of a batch) and
+// logchebei1.hip (the log of that with constraints, the thirteenth: groups of M + K GPs, a log-sum-exp over the quadrature's nodes
+// and over the members).
 #pragma once
 #include <memory>
 #include <vector>
@@ -127,7 +129,7 @@ struct Kg1Call {
   std::shared_ptr<const void> client;
   void (*check_members)(const Kg1Objective& o, const std::vector<GpDev*>& gps, int pending_room) = nullptr;
 };
-// The twelve clients' descriptions, one function each (the caller has made the checks that need no handle; the arrays are the
+// The thirteen clients' descriptions, one function each (the caller has made the checks that need no handle; the arrays are the
 // caller's and outlive the call).  gp.hpp says what the arguments are.
 Kg1Call kg1_call(int num_fidelity, const double* discrete_all, const int* num_discrete, const double* best_so_far);  // kg1_opt.hip
 Kg1Call ei1_call(const double* best_so_far);                                                                       // ei1.hip
@@ -149,6 +151,8 @@ Kg1Call logehvi3_call(int num_mcmc, int num_constraints, const double* threshold
 // (scalarisations [num_rounds][2 M], best_so_far [num_rounds][E]; round 0 until a greedy batch's pick moves on to the next)
 Kg1Call chebei1_call(int num_mcmc, int num_objectives, int num_rounds, const double* scalarisations,
                      const double* best_so_far);  // chebei1.hip
+Kg1Call logchebei1_call(int num_mcmc, int num_objectives, int num_constraints, const double* thresholds, int num_rounds,
+                        const double* scalarisations, const double* best_so_far);  // logchebei1.hip
 
 // what a multistart hands back (all but the first three may be NULL) ...
 struct Kg1MultistartOut {

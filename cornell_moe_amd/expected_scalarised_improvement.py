@@ -177,3 +177,97 @@ def multistart_chebyshev_expected_improvement_optimization(objective_models, ide
     res = api.ei_chebyshev_suggest(_objective_members(objective_models), np.array(scal), np.array(best), gd_params, bounds, starts, q,
                                    points_being_sampled=points_being_sampled)
     return res["points"], res["values"], res["found"]
+
+
+# ---- the log form, constrained too (csrc/logchebei1.hip) ----
+def feasible_chebyshev_best_so_far(objective_values, constraint_values, thresholds, a, b):
+    """The incumbent of the FEASIBLE observations: chebyshev_best_so_far over the rows of objective_values [n][M] whose
+    constraint_values [n][K] satisfy constraint_values[i][k] <= thresholds[k] for every k.  The log form integrates up to its
+    incumbent, so the incumbent must be finite: where no observation is feasible the cap is the LARGEST finite scalarised
+    observation -- every outcome better than the worst seen then counts as an improvement, and the probabilities of feasibility
+    steer the search towards the feasible region."""
+    a = np.asarray(a, dtype=np.float64).ravel()
+    tau = np.asarray([] if thresholds is None else thresholds, dtype=np.float64).ravel()
+    y = np.asarray(objective_values, dtype=np.float64).reshape(-1, a.size)
+    if tau.size == 0:
+        return chebyshev_best_so_far(y, a, b)
+    con = np.asarray(constraint_values, dtype=np.float64).reshape(-1, tau.size)
+    if con.shape[0] != y.shape[0]:
+        raise ValueError("the feasible incumbent needs objectives and constraints observed at the same points: %d and %d rows" % (
+            y.shape[0], con.shape[0]))
+    feasible = np.all(con <= tau[None, :], axis=1)
+    g = np.max(a[None, :] * y + np.asarray(b, dtype=np.float64).ravel()[None, :], axis=1)
+    if np.any(feasible & np.isfinite(g)):
+        return float(np.min(g[feasible & np.isfinite(g)]))
+    g = g[np.isfinite(g)]
+    if g.size == 0:
+        raise ValueError("no observed outcome is finite: there is no incumbent")
+    return float(np.max(g))
+
+
+def _feasible_incumbents(objective_models, constraint_models, thresholds, a, b):
+    """per member the incumbent of its feasible observations (the constraints observed where the objectives are)"""
+    outcomes = _observed_outcomes(objective_models)
+    if not constraint_models:
+        return [chebyshev_best_so_far(y, a, b) for y in outcomes]
+    constraints = _observed_outcomes(constraint_models)
+    return [feasible_chebyshev_best_so_far(y, c, thresholds, a, b) for y, c in zip(outcomes, constraints)]
+
+
+class LogChebyshevExpectedImprovementMCMC(ChebyshevExpectedImprovementMCMC):
+    """The LOG of ChebyshevExpectedImprovementMCMC's quantity times the probabilities of feasibility of K <= 8 constraints
+    (constraint_models: K ensembles shaped like the objectives', constraint k satisfied where c_k(x) <= thresholds[k]; None: none),
+    under the ensemble's log-sum-exp: finite with a useful gradient where the plain form is exactly 0.  best_so_far defaults to
+    every member's smallest scalarised FEASIBLE observation (feasible_chebyshev_best_so_far)."""
+
+    def __init__(self, objective_models, weights, ideal_point, nadir_point, best_so_far=None, points_being_sampled=None,
+                 constraint_models=None, thresholds=None, points_to_sample=None):
+        self._constraints = [] if constraint_models is None else _objective_members(constraint_models)
+        self._thresholds = np.ascontiguousarray([] if thresholds is None else thresholds, dtype=np.float64).ravel()
+        if self._thresholds.size != len(self._constraints):
+            raise ValueError("one threshold per constraint: %d for %d" % (self._thresholds.size, len(self._constraints)))
+        if best_so_far is None:
+            a, b = chebyshev_scalarisation(weights, ideal_point, nadir_point)
+            best_so_far = _feasible_incumbents(objective_models, constraint_models, self._thresholds, a, b)
+        super(LogChebyshevExpectedImprovementMCMC, self).__init__(objective_models, weights, ideal_point, nadir_point,
+                                                                  best_so_far=best_so_far, points_being_sampled=points_being_sampled,
+                                                                  points_to_sample=points_to_sample)
+
+    @property
+    def num_constraints(self):
+        return len(self._constraints)
+
+    def evaluate_at_point_list(self, points, want_grad=False, want_factors=False):
+        """value [C] of points [C][dim] in one device call; with want_grad (value, grad [C][dim]); with want_factors the groups'
+        own logs [E][1 + K][C] as the last item"""
+        from . import api
+        points = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, self._dim)
+        return api.log_ei_chebyshev_constrained_ensemble(self._members, self._constraints, self._thresholds,
+                                                         np.concatenate([self._a, self._b]), self._best_so_far, points,
+                                                         points_being_sampled=self._points_being_sampled, want_grad=want_grad,
+                                                         want_factors=want_factors)
+
+
+def multistart_log_chebyshev_expected_improvement_optimization(objective_models, ideal_point, nadir_point, bounds, gd_params,
+                                                               num_multistarts, num_to_sample=1, points_being_sampled=None,
+                                                               weights=None, seed=0, constraint_models=None, thresholds=None):
+    """multistart_chebyshev_expected_improvement_optimization by the log form, with constraints: the same starts, weights and greedy
+    rounds; every round's incumbents come from the FEASIBLE observations only, and a pick lowers a member's incumbent only where
+    that member believes it feasible.  Returns (points [q][dim], values [q], found [q]); the values are logs."""
+    from . import api
+    q = int(num_to_sample)
+    M = len(list(objective_models))
+    w = sample_simplex_weights(q, M, seed) if weights is None else np.asarray(weights, dtype=np.float64).reshape(-1, M)
+    if w.shape[0] != q:
+        raise ValueError("one weight vector per point: %d for %d points" % (w.shape[0], q))
+    scal, best = [], []
+    for t in range(q):
+        a, b = chebyshev_scalarisation(w[t], ideal_point, nadir_point)
+        scal.append(np.concatenate([a, b]))
+        best.append(_feasible_incumbents(objective_models, constraint_models, thresholds, a, b))
+    starts = api.latin_hypercube(seed, bounds, num_multistarts)
+    cons = None if not constraint_models else _objective_members(constraint_models)
+    res = api.log_ei_chebyshev_constrained_suggest(_objective_members(objective_models), cons, thresholds, np.array(scal),
+                                                   np.array(best), gd_params, bounds, starts, q,
+                                                   points_being_sampled=points_being_sampled)
+    return res["points"], res["values"], res["found"]

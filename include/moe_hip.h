@@ -953,6 +953,76 @@ int moe_ei_chebyshev_mcmc_suggest(const moe_gp_t* const* objective_gps, int num_
                                   const double* points_being_sampled, int num_being_sampled, const double* starts, int num_starts,
                                   int do_gradient_ascent, int num_to_sample, double* best_points, double* best_values, int* found,
                                   moe_error_t* err);
+/* The LOG of moe_ei_chebyshev_mcmc's quantity with 0 <= K = num_constraints <= 8 constraints, computed so that it stays finite with
+ * a useful gradient where that value and its gradient are exactly 0 in float64 (the incumbent at or below L, or a product of M
+ * normal CDFs too small to tell the starts of an ascent apart).  Minimisation.  Member e is M + K GPs without derivative
+ * observations: its objectives objective_gps[e * M + j] ([E][M]), then its constraint GPs constraint_gps[k * E + e] ([K][E]; may
+ * be NULL with K = 0), constraint k satisfied where c_k(x) <= thresholds[k]; E (M + K) <= 1024.  scalarisations and best_so_far
+ * as in moe_ei_chebyshev_mcmc, best_so_far being the incumbents of the FEASIBLE observations.  Every incumbent must be finite:
+ * the integral's upper limit is the incumbent, so a caller without a feasible observation passes a finite cap of its own (the
+ * Python wrapper takes the largest scalarised observation).  With that function's s_j, tau_j, sigma_j, L and the incumbent g:
+ *   integrand      z_j(t) = (t - s_j) / tau_j, log f(t) = sum_j log Phi(z_j(t)) added in the order of j, r_j = phi(z_j) / Phi(z_j)
+ *   decay length   ell = min(1 / sum_j (r_j(g) / tau_j), max_j tau_j): f is log-concave, so f(t) <= f(g) exp((t - g) sum_j r_j(g) /
+ *                  tau_j) below g; the cap binds only where f does not decay at g
+ *   member         LA_e = log integral over Lambda <= t <= g of f, Lambda = min(L, g - 40 ell): finite for every finite input,
+ *                  there is no `g <= L` branch.  dLA/dmu_j = -a_j <r_j / tau_j>, dLA/dvar_j = -(a_j / (2 sigma_j)) <z_j r_j /
+ *                  tau_j>, <.> the f-weighted mean over [Lambda, g], accumulated as signed sums of scaled terms.  Lambda and
+ *                  the breakpoints are constants in the gradient (Lambda's boundary term is below e^-40 relative).
+ *   quadrature     FIXED, and formed in OFFSETS u = g - t below the incumbent from d_j = g - s_j (rounded once), z_j = (d_j - u) /
+ *                  tau_j, so that no node is lost where ell lies below an ulp of g (a floored sigma_j under an s_j above the
+ *                  incumbent): moe_ei_chebyshev_mcmc's 14 M breakpoints, d_j - c tau_j, and the ladder kappa ell, kappa in {1/2, 1,
+ *                  2, 3, 4.5, 6, 8, 10.5, 13, 16, 20, 24, 29, 34}, each clamped to [0, U], U = g - Lambda = max(min_j (d_j + 38
+ *                  tau_j), 40 ell), with U and 0: 14 M + 16 points sorted ascending in the offset (list position breaks ties:
+ *                  objectives, ladder, U, 0); the 8-point Gauss-Legendre rule per
+ *                  panel; the nodes' terms log(weight) + log f enter a log-sum-exp whose order depends on M alone
+ *                  (csrc/logchebei1.hip)
+ *   feasibility    log F_{e,k} and its derivatives: moe_log_ehvi_constrained_mcmc's
+ *   ensemble       LL_e = LA_e + log F_{e,1} + ... + log F_{e,K};  m = max_e LL_e, value = m + log(sum_e exp(LL_e - m)) - log E;
+ *                  grad = sum_e w_e g_e / sum_e w_e with g_e = sum_j (c_mu_j grad mu_j + c_var_j grad var_j) in the order of j,
+ *                  mu before var, then + grad log F_{e,k} for k = 1 .. K.  With E = 1 the value is LL_0 bit for bit.
+ * Pending points condition every GP's variance; member e keeps the believed outcomes mu_{e,j}(P_i), and P_i's scalarised outcome
+ * lowers its incumbent only where the member believes the point feasible, mu_{e,c_k}(P_i) <= thresholds[k] for every k (K = 0:
+ * moe_ei_chebyshev_mcmc's rule bit for bit).
+ * factors_out (may be NULL): [E][1 + K][num_points], LA_e, log F_{e,1}, ..., log F_{e,K}; value[i] is what the ensemble rule makes
+ * of them: with E = 1 their sum, bit for bit; with more members the rule takes exp and log, which a host's library and the
+ * device's round alike only within a unit in the last place, so a host's value agrees within a few units in the last place of
+ * max(1, |value|), not in every bit.  A candidate's bits do not depend on how many share the call, nor on want_grad, nor on
+ * ensemble-wide launches.  No handle is modified.
+ * Errors, in this order, everything that needs no handle before a handle or the device is touched: num_objectives outside 2 .. 8
+ * -> MOE_ERR_BOUNDS, payload (num_objectives, 2, 8); num_constraints outside 0 .. 8 -> MOE_ERR_BOUNDS, payload (num_constraints,
+ * 0, 8); num_mcmc < 1 or num_mcmc (M + K) > 1024 -> MOE_ERR_BOUNDS, payload (num_mcmc, 1, 1024 / (M + K) rounded down); a NULL
+ * array (moe_ei_chebyshev_mcmc's, and constraint_gps and thresholds with K > 0) -> MOE_ERR_RUNTIME; an a_j that is not positive,
+ * or an a_j or b_j that is not finite -> MOE_ERR_INVALID_VALUE, payload (the value, its flat index in scalarisations, 0); a
+ * threshold that is not finite -> MOE_ERR_INVALID_VALUE, payload (the value, k, 2); an incumbent that is not finite, +infinity
+ * included -> MOE_ERR_INVALID_VALUE, payload (the value, its flat index in best_so_far, 1); then moe_ei_chebyshev_mcmc's from
+ * num_points on, "member" counting the GPs flat as e (M + K) + role. */
+int moe_log_ei_chebyshev_constrained_mcmc(const moe_gp_t* const* objective_gps, int num_objectives, const moe_gp_t* const* constraint_gps,
+                                          int num_constraints, const double* thresholds, int num_mcmc, const double* scalarisations,
+                                          const double* best_so_far, const double* points_being_sampled, int num_being_sampled,
+                                          const double* points, int num_points, int want_grad, double* value, double* grad,
+                                          double* factors_out, moe_error_t* err);
+/* moe_ei_chebyshev_mcmc_multistart with moe_log_ei_chebyshev_constrained_mcmc's objective: the same screening, top-20 rule,
+ * restarted ascent and outputs, bit for bit the path a host loop over moe_log_ei_chebyshev_constrained_mcmc walks.  Tensor-product
+ * domains only.  Errors: those two functions', in their order. */
+int moe_log_ei_chebyshev_constrained_mcmc_multistart(const moe_gp_t* const* objective_gps, int num_objectives,
+                                                     const moe_gp_t* const* constraint_gps, int num_constraints, const double* thresholds,
+                                                     int num_mcmc, const double* scalarisations, const double* best_so_far,
+                                                     const moe_gd_params_t* outer, const double* domain_bounds,
+                                                     const double* points_being_sampled, int num_being_sampled, const double* starts,
+                                                     int num_starts, int do_gradient_ascent, double* best_point, double* best_value,
+                                                     int* found, double* start_values, int* kept_index, double* end_points,
+                                                     double* end_values, double* path, int* steps_taken, moe_error_t* err);
+/* moe_ei_chebyshev_mcmc_suggest with moe_log_ei_chebyshev_constrained_mcmc's objective: num_to_sample points greedily with a
+ * scalarisation and incumbents per point, bit for bit what num_to_sample calls of moe_log_ei_chebyshev_constrained_mcmc_multistart
+ * return when each is fed its predecessors' points; a pick lowers a member's incumbent only where the member believes it
+ * feasible.  Errors: those functions', in their order. */
+int moe_log_ei_chebyshev_constrained_mcmc_suggest(const moe_gp_t* const* objective_gps, int num_objectives,
+                                                  const moe_gp_t* const* constraint_gps, int num_constraints, const double* thresholds,
+                                                  int num_mcmc, const double* scalarisations, const double* best_so_far,
+                                                  const moe_gd_params_t* outer, const double* domain_bounds,
+                                                  const double* points_being_sampled, int num_being_sampled, const double* starts,
+                                                  int num_starts, int do_gradient_ascent, int num_to_sample, double* best_points,
+                                                  double* best_values, int* found, moe_error_t* err);
 /* compute_grad_variance_of_points -> ComputeGradVarianceOfPoints (gpp_math.cpp:1359-1373); out[num_derivs][m][m][dim] */
 int moe_gp_grad_variance(const moe_gp_t* gp, const double* pts, int num_pts, int num_derivs, double* out, moe_error_t* err);
 /* compute_grad_cholesky_variance_of_points -> ComputeGradCholeskyVarianceOfPoints (gpp_math.cpp:1454-1474) */
