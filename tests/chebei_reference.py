@@ -370,10 +370,33 @@ BELIEVED = [
 # the limit of 1024 GPs, value only (tests/test_gpu_chebei.py holds members 0, 63 and 127 to long double)
 MANY = Case("m8_e128_d3_n4_p0", 31, 8, 128, 3, _grid(128, 8, 4), 0, 2, "plain", 1.9e-18)
 ALL_CASES = CASES + BELIEVED
+# ---- the cases of tests/test_gpu_chebei_edges.py ----
+# M = 6 and M = 7 (86 and 100 breakpoints, 680 and 792 nodes: last sweeps of 40 and 24 lanes), M = 7 with n on both sides of
+# tri_cols' 128-row switch, alternating over the roles and the members
+M6, M7 = "m6_e1_d3_n20_p2", "m7_e2_d3_n20_130_p2"
+M6_ABOVE, M7_ABOVE = "m6_e1_d3_n20_p0_above", "m7_e1_d3_n20_p0_above"
+# mixed: member 0's incumbent lies below L at every candidate (exact zeros, zero coefficients) beside a live member 1
+MIXED = "m3_e2_d3_n20_p0_mixed"
+# p64: 64 pending points, every incumbent above every believed outcome, ordered so that member 0's lowest believed scalarised
+# outcome is point 63 and member 1's is point 40, each at least P64_MARGIN below the member's runner-up
+P64 = "m3_e2_d3_n20_p64"
+P64_MARGIN = 1e-3
+P64_SLOTS = ((0, 0, 63), (1, 0, 40))  # (member, rank among the member's outcomes from the lowest, the pending point's index)
+EDGE_CASES = [
+    Case(M6, 51, 6, 1, 3, _grid(1, 6, 20), 2, 6, "plain", 7.8e-17),
+    Case(M7, 52, 7, 2, 3, ((20, 130, 20, 130, 20, 130, 20), (130, 20, 130, 20, 130, 20, 130)), 2, 6, "plain", 3.6e-15),
+    # With an observed incumbent most breakpoints clamp to g*, the panels at the top have no width and the last, partly filled sweep
+    # adds exact zeros (tests/test_chebei_reference.py asserts it of M6 and M7).  With g* above every s_j + 8 tau_j every panel has
+    # a width and the last sweep carries nearly all of the value.
+    Case(M6_ABOVE, 55, 6, 1, 3, _grid(1, 6, 20), 0, 6, "above", 1.1e-15),
+    Case(M7_ABOVE, 56, 7, 1, 3, _grid(1, 7, 20), 0, 6, "above", 3.5e-15),
+    Case(MIXED, 53, 3, 2, 3, _grid(2, 3, 20), 0, 6, "mixed", 2.0e-16),
+    Case(P64, 54, 3, 2, 3, _grid(2, 3, 20), 64, 2, "p64", 8.7e-17),
+]
 
 
 def case(name):
-    return next(c for c in ALL_CASES + [MANY] if c.name == name)
+    return next(c for c in ALL_CASES + EDGE_CASES + [MANY] if c.name == name)
 
 
 def _random_gps(rng, c):
@@ -410,6 +433,29 @@ def _float64_outcomes(gps, pending, scal):
     return [[float(v) for v in scalarised_outcomes(a, b, Member(row, pending, np.float64).outcomes, np.float64)] for row in gps]
 
 
+def place_pending(rng, gps, scal, p, d, slots):
+    """p pending points, drawn until they can be ordered as `slots` asks: for every (member, rank, index) the member's rank-th
+    lowest believed scalarised outcome (float64) is point `index`, the slots name different points, and each of these outcomes
+    and the member's next one lie at least 2 P64_MARGIN apart (the outcomes are the unconditioned means: an order of the points
+    changes none)"""
+    top = {}
+    for e, r, _ in slots:
+        top[e] = max(top.get(e, 0), r)
+    while True:
+        pending = rng.uniform(0, 1, size=(p, d))
+        G = _float64_outcomes(gps, pending, scal)
+        order = [np.argsort(g) for g in G]
+        clear = all(G[e][order[e][k + 1]] - G[e][order[e][k]] >= 2.0 * P64_MARGIN for e, r in top.items() for k in range(r + 1))
+        chosen = [int(order[e][r]) for e, r, _ in slots]
+        if clear and len(set(chosen)) == len(chosen):
+            break
+    perm = [None] * p
+    for src, (_, _, index) in zip(chosen, slots):
+        perm[index] = src
+    rest = iter(i for i in range(p) if i not in chosen)
+    return np.ascontiguousarray(pending[[next(rest) if v is None else v for v in perm]])
+
+
 def make_problem(c):
     rng = np.random.default_rng(9700 + c.seed)
     gps = _random_gps(rng, c)
@@ -433,6 +479,11 @@ def make_problem(c):
         bests = [[-1e3]]
     elif c.kind == "above":
         bests = [[50.0]]
+    elif c.kind == "mixed":
+        bests = [[-1e3] + best[1:]]
+    elif c.kind == "p64":
+        pending = place_pending(rng, gps, scal, c.p, c.d, P64_SLOTS)
+        bests = [[max(max(row) for row in _float64_outcomes(gps, pending, scal)) + 0.05] * c.E]
     elif c.kind.startswith("believed"):
         G = _float64_outcomes(gps, pending, scal)
         if c.kind == "believed_one":

@@ -74,15 +74,21 @@ def offsets(s, tau, g, T):
     return [T(g) - s[j] for j in range(len(s))]
 
 
-def decay_length(d, tau, T):
-    """ell: f(t) <= f(g) exp((t - g) / (1 / sum_j r_j(g) / tau_j)) below g, f being log-concave; capped at the largest tau_j"""
+def decay_rate(d, tau, T):
+    """sum_j r_j(g) / tau_j in the order of j: the rate at which log f falls below g"""
     total = None
     for j in range(len(d)):
         _, r = lr.log_cdf_parts(d[j] / tau[j], T)
         term = r / tau[j]
         total = term if total is None else total + term
+    return total
+
+
+def decay_length(d, tau, T):
+    """ell: f(t) <= f(g) exp((t - g) / (1 / sum_j r_j(g) / tau_j)) below g, f being log-concave; capped at the largest tau_j
+    (where every r_j(g) underflows the rate is exactly 0 and 1 / 0 = infinity yields to the cap)"""
     with np.errstate(divide="ignore"):
-        return min(T(1) / total, max(tau))
+        return min(T(1) / decay_rate(d, tau, T), max(tau))
 
 
 def log_breakpoints(s, tau, g, T):
@@ -385,16 +391,60 @@ BELIEVED = Case("log_m2_e2_k1_d3_n20_p4_believed", 21, 2, 2, 1, 3, _grid(2, 3, 2
 FLOOR_ABOVE = Case("log_m3_e1_k0_d3_floor_above", 5, 3, 1, 0, 3, ((20, 1, 20),), 0, 8, "floor", TAUS[0], 0.5, 0.0, 0.0)
 MANY = Case("log_m8_e64_k8_d3_n4_p0", 31, 8, 64, 8, 3, _grid(64, 16, 4), 0, 2, "plain", TAUS[8], 0.0, 0.0, 0.0)
 ALL_CASES = CASES + [BELIEVED]
+# ---- the cases of tests/test_gpu_chebei_edges.py ----
+TAUS.update({3: (0.1, 0.0, 0.2), 5: (0.1, 0.0, 0.2, -0.1, 0.3)})
+# M = 6 and M = 7 (100 and 114 breakpoints, 792 and 904 nodes; LogStripRecord<12> and <14>), K = 3 and K = 5, an odd dimension
+# under two members
+M67 = [
+    Case("log_m6_e2_k3_d7_n20_p3", 51, 6, 2, 3, 7, _grid(2, 9, 20), 3, 6, "plain", TAUS[3], 0.0, 0.0, 4.4e-14),
+    Case("log_m7_e2_k5_d3_n20_p2", 52, 7, 2, 5, 3, _grid(2, 12, 20), 2, 6, "plain", TAUS[5], 0.0, 0.0, 3.1e-14),
+    Case("log_m6_e1_k0_d3_n20_p0", 53, 6, 1, 0, 3, _grid(1, 6, 20), 0, 6, "plain", TAUS[0], 0.0, 0.0, 8.3e-14),
+    Case("log_m7_e1_k0_d3_n20_p0", 54, 7, 1, 0, 3, _grid(1, 7, 20), 0, 6, "plain", TAUS[0], 0.0, 0.0, 1.5e-14),
+]
+# the incumbent 50 above the observed one: every r_j(g) underflows, the rate is exactly 0 and ell is the cap max_j tau_j
+ABOVE_RAISE = 50.0
+ABOVE = [
+    Case("log_m3_e1_k0_d3_n20_p0_above", 55, 3, 1, 0, 3, _grid(1, 3, 20), 0, 6, "plain", TAUS[0], -ABOVE_RAISE, 0.0, 6.4e-14),
+    Case("log_m6_e1_k0_d3_n20_p0_above", 56, 6, 1, 0, 3, _grid(1, 6, 20), 0, 6, "plain", TAUS[0], -ABOVE_RAISE, 0.0, 2.8e-14),
+]
+# a live member beside one whose incumbent is lowered by STALL_DROP (kind mixed: member 1; mixed_swapped: the same two members in
+# the other order): the stalled member's weight exp(LL - m) is exactly 0.  ld_diff covers the stalled member's LA, of order -1e6;
+# MIXED_LIVE[name] is the same figure without that member's group values, which is what the value, the gradient and the live
+# member's group values are held to
+MIXED = [
+    Case("log_m3_e2_k0_d3_n20_p0_mixed", 57, 3, 2, 0, 3, _grid(2, 3, 20), 0, 6, "mixed", TAUS[0], STALL_DROP, 0.0, 8.5e-9),
+    Case("log_m3_e2_k0_d3_n20_p0_mixed_swapped", 57, 3, 2, 0, 3, _grid(2, 3, 20), 0, 6, "mixed_swapped", TAUS[0], STALL_DROP, 0.0, 8.5e-9),
+    Case("log_m3_e2_k1_d3_n20_p0_mixed", 58, 3, 2, 1, 3, _grid(2, 4, 20), 0, 6, "mixed", TAUS[1], STALL_DROP, 0.0, 1.7e-9),
+    Case("log_m3_e2_k1_d3_n20_p0_mixed_swapped", 58, 3, 2, 1, 3, _grid(2, 4, 20), 0, 6, "mixed_swapped", TAUS[1], STALL_DROP, 0.0, 1.7e-9),
+]
+MIXED_LIVE = {"log_m3_e2_k0_d3_n20_p0_mixed": 7.2e-15, "log_m3_e2_k0_d3_n20_p0_mixed_swapped": 7.2e-15,
+              "log_m3_e2_k1_d3_n20_p0_mixed": 2.4e-15, "log_m3_e2_k1_d3_n20_p0_mixed_swapped": 2.4e-15}
+
+
+def stalled_member(c):
+    return {"mixed": 1, "mixed_swapped": 0}[c.kind]
+
+
+# 64 pending points: member 0 believes its lowest believed outcome, point 62, infeasible, so that its incumbent is its second
+# lowest, point 63; member 1 believes all feasible and its lowest is point 40; every incumbent lies above every believed outcome
+P64 = Case("log_m3_e2_k1_d3_n20_p64", 59, 3, 2, 1, 3, _grid(2, 4, 20), 64, 2, "p64", TAUS[1], 0.0, 0.0, 3.3e-12)
+P64_SLOTS = ((0, 0, 62), (0, 1, 63), (1, 0, 40))
+# the believed-and-feasible rule inside a greedy batch: member 0's constraint GP observes +0.5 on one half of the box and -0.5 on
+# the other, member 1's -0.5 everywhere; every incumbent is HIGH_BEST, above every outcome a member can believe, so that what a
+# member believes feasible among the pending points and the picks decides its incumbent
+HALF = Case("log_m2_e2_k1_d3_n20_p2_half", 60, 2, 2, 1, 3, _grid(2, 3, 20), 2, 4, "half", TAUS[1], 0.0, 0.0, 5.6e-14)
+HIGH_BEST = 2.0
+EDGE_CASES = M67 + ABOVE + MIXED + [P64, HALF]
 
 
 def case(name):
-    return next(c for c in ALL_CASES + [MANY, FLOOR_ABOVE] if c.name == name)
+    return next(c for c in ALL_CASES + EDGE_CASES + [MANY, FLOOR_ABOVE] if c.name == name)
 
 
 def make_problem(c):
     """chebei_reference's problem of the same seed and kind over M + K GPs per member; the GPs behind the first M are the
     constraints"""
-    base = ch.Case(c.name, c.seed, c.M + c.K, c.E, c.d, c.n, c.p, c.C, "plain" if c.kind == "believed" else c.kind, 0.0)
+    base = ch.Case(c.name, c.seed, c.M + c.K, c.E, c.d, c.n, c.p, c.C, c.kind if c.kind in ("floor", "decades") else "plain", 0.0)
     if c.kind in ("floor", "decades"):
         p = ch.make_problem(base._replace(M=c.M))
         gps, scal, best = p.gps, p.scal[0], list(p.best[0])
@@ -408,10 +458,20 @@ def make_problem(c):
     taus = list(c.taus)
     if c.far:
         taus[0] = taus[0] - c.far * float(np.sqrt(np.asarray(gps[0][c.M].hyper).ravel()[0]))
-    best = [v - c.drop for v in best]
+    if c.kind.startswith("mixed"):
+        best = [best[0]] + [v - c.drop for v in best[1:]]
+    else:
+        best = [v - c.drop for v in best]
     pending = p.pending
     if c.kind == "believed":
         pending, gps, best = _believed(c, gps, p, scal)
+    elif c.kind == "mixed_swapped":
+        gps, best = gps[::-1], best[::-1]
+    elif c.kind == "p64":
+        placed = ch.place_pending(rng, [row[:c.M] for row in gps], scal, c.p, c.d, P64_SLOTS)
+        pending, gps, best = _believed(c, gps, p._replace(pending=placed), scal)
+    elif c.kind == "half":
+        gps, best = _believed_half(c, gps, p.pending, scal), [HIGH_BEST] * c.E
     return Problem(c.name, c.M, c.K, gps, tuple(taus), np.asarray(scal, dtype=np.float64), [float(v) for v in best], p.points,
                    np.ascontiguousarray(pending))
 
@@ -433,6 +493,41 @@ def _believed(c, gps, p, scal):
     return pending, gps, best
 
 
+def half_region(c, gps, pending, scal):
+    """(k, upper): the half of the box, cut at 0.5 along coordinate k, that member 0 of the `half` problem believes infeasible.
+    It is the half that holds, deepest inside it, the best of 64 probe points under the objectives alone (K = 0, float64, the
+    problem's pending points, every incumbent HIGH_BEST): where the first picks of a batch go"""
+    probes = np.random.default_rng(7300 + c.seed).uniform(0.05, 0.95, size=(64, c.d))
+    ms = ensemble([row[:c.M] for row in gps], c.M, (), pending, np.float64)
+    x = probes[int(np.argmax([float(evaluate(ms, q, scal, [HIGH_BEST] * c.E).value) for q in probes]))]
+    k = int(np.argmax(np.abs(x - 0.5)))
+    return k, bool(x[k] > 0.5)
+
+
+def _believed_half(c, gps, pending, scal):
+    """member 0's constraint GP observes +0.5 at its points inside half_region and -0.5 at the others, member 1's -0.5 at all;
+    both with lengths of 0.6, so that the believed mean is a smooth step across the box"""
+    k, upper = half_region(c, gps, pending, scal)
+    gps = [list(row) for row in gps]
+    for e in range(c.E):
+        g = gps[e][c.M]
+        X = np.asarray(g.X, dtype=np.float64)
+        inside = (X[:, k] > 0.5) == upper
+        y = np.where(inside & (e == 0), 0.5, -0.5).reshape(-1, 1)
+        gps[e][c.M] = ch.GP(g.cov_type, np.array([float(np.asarray(g.hyper).ravel()[0])] + [0.6] * c.d), X.copy(), y, [1e-2], ())
+    return gps
+
+
+def batch_rounds(p, q):
+    """q scalarisations, the problem's own first, and the incumbents [q][E] of the `half` problem's batch"""
+    rng = np.random.default_rng(8805)
+    rows = [p.scal]
+    for _ in range(q - 1):
+        w = rng.exponential(size=p.M) + 0.2
+        rows.append(ch.scalarisation(w / w.sum(), [ch.IDEAL] * p.M, [ch.NADIR] * p.M))
+    return np.array(rows), np.full((q, len(p.gps)), HIGH_BEST)
+
+
 _WANT = {}
 
 
@@ -447,14 +542,15 @@ def expected(c, T=LD, members=None):
     return _WANT[key]
 
 
-def ld_difference(c):
-    """the worst float64-against-long-double difference of a case: the value and every group value (absolute), the gradient
-    relative to its largest entry"""
+def ld_difference(c, without=None):
+    """the worst float64-against-long-double difference of a case: the value and every group value (absolute; `without`: but
+    those of that member), the gradient relative to its largest entry"""
     _, hi = expected(c, LD)
     _, lo = expected(c, np.float64)
     worst = 0.0
     for h, l in zip(hi, lo):
         worst = max(worst, abs(float(h.value - LD(l.value))))
-        worst = max(worst, max(abs(float(x - LD(y))) for hv, lv in zip(h.log_factors, l.log_factors) for x, y in zip(hv, lv)))
+        worst = max(worst, max(abs(float(x - LD(y))) for e, (hv, lv) in enumerate(zip(h.log_factors, l.log_factors)) if e != without
+                               for x, y in zip(hv, lv)))
         worst = max(worst, float(np.max(np.abs(h.grad - l.grad.astype(LD)))) / float(np.max(np.abs(h.grad))))
     return worst

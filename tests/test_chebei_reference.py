@@ -103,7 +103,10 @@ def test_with_the_other_objectives_irrelevant_it_is_the_analytic_expected_improv
 
 
 # ---- 4. float64 against long double: ld_diff ----
-@pytest.mark.parametrize("case", ch.ALL_CASES, ids=[c.name for c in ch.ALL_CASES])
+_QUALIFIED = ch.ALL_CASES + ch.EDGE_CASES
+
+
+@pytest.mark.parametrize("case", _QUALIFIED, ids=[c.name for c in _QUALIFIED])
 def test_float64_against_long_double_on_the_cases_of_the_gpu_tests(case):
     measured = ch.ld_difference(case)
     p, want = ch.expected(case, LD)
@@ -162,6 +165,81 @@ def test_the_cases_reach_what_they_are_there_for():
                 assert all(p.best[0][0] > s[j] + 8.0 * tau[j] for j in range(3))
             else:
                 assert p.best[0][0] < L
+
+
+def test_the_edge_cases_reach_what_they_are_there_for():
+    """the cases of tests/test_gpu_chebei_edges.py: M = 6 and 7 with their breakpoint and node counts, n on both sides of 128, a
+    member of exact zeros beside a live one, and 64 pending points whose deciding ones sit at the indices P64_SLOTS names"""
+    for name, M, breaks, nodes in ((ch.M6, 6, 86, 680), (ch.M7, 7, 100, 792)):
+        c = ch.case(name)
+        p = ch.make_problem(c)
+        assert c.M == M == len(p.gps[0]) and len(p.gps) == c.E and nodes % 64 != 0
+        m = ch.Member(p.gps[0], p.pending, np.float64)
+        a, b = ch.split(p.scal[0])
+        mo = m.moments(p.points[0])
+        s, tau, sg = ch.scalarised_moments(a, b, [q[0] for q in mo], [q[1] for q in mo], np.float64)
+        L, bp = ch.breakpoints(s, tau, m.incumbent(p.scal[0], p.best[0][0]), np.float64)
+        assert len(bp) == breaks and 8 * (len(bp) - 1) == nodes
+    sizes = {len(g.X) for row in ch.make_problem(ch.case(ch.M7)).gps for g in row}
+    assert min(sizes) < 128 < max(sizes)
+    # the last, partly filled sweep (40 lanes at M = 6, 24 at M = 7): under an observed incumbent every one of its panels is clamped
+    # to no width and it adds exact zeros; with g* above every s_j + 8 tau_j all its nodes have a weight and carry most of the value
+    for name, live_last in ((ch.M6, False), (ch.M7, False), (ch.M6_ABOVE, True), (ch.M7_ABOVE, True)):
+        c = ch.case(name)
+        p = ch.make_problem(c)
+        a, b = ch.split(p.scal[0])
+        m = ch.Member(p.gps[0], p.pending, np.float64)
+        shares = []
+        for x in p.points:
+            mo = m.moments(x)
+            s, tau, sg = ch.scalarised_moments(a, b, [q[0] for q in mo], [q[1] for q in mo], np.float64)
+            g = m.incumbent(p.scal[0], p.best[0][0])
+            L, bp = ch.breakpoints(s, tau, g, np.float64)
+            lo, hi = np.array(bp[:-1]), np.array(bp[1:])
+            half, mid = 0.5 * (hi - lo), 0.5 * (lo + hi)
+            t = (mid[:, None] + half[:, None] * np.array(ch.GL8_X)[None, :]).ravel()
+            wt = (half[:, None] * np.array(ch.GL8_W)[None, :]).ravel()
+            first = (len(wt) // 64) * 64
+            assert len(wt) - first == {6: 40, 7: 24}[c.M]
+            if live_last:
+                assert np.all(wt[first:] > 0.0) and all(g > s[j] + 8.0 * tau[j] for j in range(c.M))
+                terms = wt * ch.integrand(t, s, tau, np.float64, False)[0]
+                shares.append(float(terms[first:].sum() / terms.sum()))
+            else:
+                assert not np.any(wt[first:])
+        if live_last:
+            print("%s: the last sweep carries %.3g .. %.3g of the value" % (name, min(shares), max(shares)))
+            assert min(shares) > 0.5
+    # mixed: member 0's incumbent at or below L at every candidate, exact zeros in both arithmetics; member 1 is live and the
+    # ensemble's value is its value halved
+    c = ch.case(ch.MIXED)
+    for T in (LD, np.float64):
+        p, want = ch.expected(c, T)
+        ms = ch.ensemble(p, T)
+        a, b = ch.split(p.scal[0])
+        for x, w in zip(p.points, want):
+            mo = ms[0].moments(x)
+            s, tau, sg = ch.scalarised_moments(a, b, [q[0] for q in mo], [q[1] for q in mo], T)
+            assert T(p.best[0][0]) < ch.breakpoints(s, tau, p.best[0][0], T)[0]
+            A0, g0 = ms[0].evaluate(x, p.scal[0], p.best[0][0])
+            A1, g1 = ms[1].evaluate(x, p.scal[0], p.best[0][1])
+            assert A0 == 0 and not np.any(g0) and A1 > 0 and np.any(g1)
+            assert w.members[0] == 0 and w.value == w.members[1] / T(2) and np.array_equal(w.grad, g1 / T(2))
+    # p64: the placements and their margins from the float64 outcomes; every incumbent above every outcome
+    c = ch.case(ch.P64)
+    p = ch.make_problem(c)
+    assert p.pending.shape == (64, 3) and c.E == 2 and c.C == 2
+    G = ch._float64_outcomes(p.gps, p.pending, p.scal[0])
+    margins = []
+    for e, rank, index in ch.P64_SLOTS:
+        order = np.argsort(G[e])
+        assert rank == 0 and int(order[0]) == index
+        margins.append(G[e][order[1]] - G[e][order[0]])
+        assert p.best[0][e] > max(G[e]) and float(ch.Member(p.gps[e], p.pending, np.float64).incumbent(p.scal[0], p.best[0][e])) == G[e][index]
+    assert ch.P64_SLOTS[0][2] == 63 and 32 <= ch.P64_SLOTS[1][2] <= 62
+    print("p64: member 0's lowest outcome at point %d, member 1's at point %d, leading their runners-up by %s" % (
+        ch.P64_SLOTS[0][2], ch.P64_SLOTS[1][2], margins))
+    assert min(margins) >= ch.P64_MARGIN
 
 
 # ---- 5. the coefficients against central differences ----

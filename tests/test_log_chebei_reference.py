@@ -228,6 +228,113 @@ def test_float64_against_long_double_on_the_cases_of_the_gpu_tests(case):
         assert all(float(w.log_factors[0][1]) < -400.0 for w in want)
 
 
+@pytest.mark.parametrize("case", lc.EDGE_CASES, ids=[c.name for c in lc.EDGE_CASES])
+def test_float64_against_long_double_on_the_edge_cases(case):
+    worst = lc.ld_difference(case)
+    print("%s: float64 against long double %.3g (recorded %.3g)" % (case.name, worst, case.ld_diff))
+    assert worst <= 1.05 * case.ld_diff
+    if case.kind.startswith("mixed"):
+        live = lc.ld_difference(case, without=lc.stalled_member(case))
+        print("%s: without the stalled member's group values %.3g (recorded %.3g)" % (case.name, live, lc.MIXED_LIVE[case.name]))
+        assert live <= 1.05 * lc.MIXED_LIVE[case.name]
+    _, want = lc.expected(case, LD)
+    assert all(np.isfinite(float(w.value)) and np.all(np.isfinite(w.grad.astype(np.float64))) and float(np.max(np.abs(w.grad))) > 0.0
+               for w in want)
+
+
+def _moments_of(member, p, x, T):
+    """(s, tau, the offsets d) of a member's objectives at x under the problem's scalarisation and the member's incumbent"""
+    a, b = ch.split(p.scal)
+    mo = [lc.cr.moments(m, bs, x) for m, bs in zip(member.models[:p.M], member.bases[:p.M])]
+    s, tau, _ = ch.scalarised_moments(a, b, [q[0] for q in mo], [q[1] for q in mo], T)
+    return s, tau
+
+
+def test_the_edge_cases_reach_what_they_are_there_for():
+    """the cases of tests/test_gpu_chebei_edges.py, from the restatement alone"""
+    # M = 6 and 7: 100 and 114 breakpoints, 792 and 904 nodes; K = 3 and 5 among them, an odd dimension under two members
+    for c in lc.M67:
+        p = lc.make_problem(c)
+        m = lc.ensemble(p.gps, p.M, p.taus, p.pending, np.float64)[0]
+        s, tau = _moments_of(m, p, p.points[0], np.float64)
+        U, ell, bp, d = lc.log_breakpoints(s, tau, m.incumbent(p.scal, p.best[0]), np.float64)
+        assert len(bp) == 14 * c.M + 16 == {6: 100, 7: 114}[c.M] and 8 * (len(bp) - 1) == {6: 792, 7: 904}[c.M]
+        assert len(p.taus) == c.K and len(p.gps) == c.E and all(len(row) == c.M + c.K for row in p.gps)
+    assert {(c.M, c.E, c.K, c.d) for c in lc.M67} == {(6, 2, 3, 7), (7, 2, 5, 3), (6, 1, 0, 3), (7, 1, 0, 3)}
+    # above: at every candidate the rate is exactly 0, in both arithmetics, and ell is the cap; the plain form is positive
+    for c in lc.ABOVE:
+        p = lc.make_problem(c)
+        assert c.E == 1 and c.K == 0 and c.M in (3, 6)
+        observed = ch.observed_best([row[:p.M] for row in p.gps], p.scal)
+        assert p.best[0] == observed[0] + lc.ABOVE_RAISE
+        for T in (np.float64, LD):
+            m = lc.ensemble(p.gps, p.M, p.taus, p.pending, T)[0]
+            for x in p.points:
+                s, tau = _moments_of(m, p, x, T)
+                d = lc.offsets(s, tau, p.best[0], T)
+                assert lc.decay_rate(d, tau, T) == 0 and lc.decay_length(d, tau, T) == max(tau)
+                U, ell, bp, _ = lc.log_breakpoints(s, tau, p.best[0], T)
+                assert ell == max(tau) and sum(1 for u in bp if u == T(34.0) * ell) >= 1  # (the ladder stands on the cap)
+        plain = ch.ensemble(ch.Problem(p.name, p.M, [row[:p.M] for row in p.gps], [p.scal], [p.best], p.points, p.pending, ()), np.float64)
+        assert all(float(plain[0].evaluate(x, p.scal, p.best[0])[0]) > 0.0 for x in p.points)
+    # mixed: the stalled member's LL lies more than 745 below the live one's at every candidate, so that its weight is exactly 0,
+    # the value is the live member's LL - log 2 and the gradient the live member's
+    for c in lc.MIXED:
+        p, want = lc.expected(c, np.float64)
+        dead = lc.stalled_member(c)
+        assert c.E == 2 and c.M == 3 and c.drop == lc.STALL_DROP
+        gaps = []
+        for w in want:
+            LL = [sum(row[1:], row[0]) for row in w.log_factors]
+            gaps.append(float(LL[dead] - LL[1 - dead]))
+            assert gaps[-1] < -745.0 and np.exp(LL[dead] - LL[1 - dead]) == 0.0
+            assert w.value == LL[1 - dead] + np.log(np.float64(1.0)) - np.log(np.float64(2.0))
+            assert np.array_equal(w.grad, w.members_grad[1 - dead]) and np.all(np.isfinite(w.members_grad[dead]))
+        print("%s: LL of the stalled member below the live one's by %.6g .. %.6g" % (c.name, -max(gaps), -min(gaps)))
+    a, b = lc.make_problem(lc.MIXED[0]), lc.make_problem(lc.MIXED[1])
+    assert a.best == b.best[::-1] and all(np.array_equal(x.y, y.y) for r, q in zip(a.gps, b.gps[::-1]) for x, y in zip(r, q))
+    # p64: the placements, the mask and the margins from the float64 beliefs
+    c = lc.P64
+    p = lc.make_problem(c)
+    sa, sb = ch.split(p.scal)
+    assert p.pending.shape == (64, 3) and c.K == 1 and c.E == 2
+    for T in (np.float64, LD):
+        ms = lc.ensemble(p.gps, p.M, p.taus, p.pending, T)
+        out = [[float(v) for v in ch.scalarised_outcomes(sa, sb, m.outcomes, T)] for m in ms]
+        o0, o1 = np.argsort(out[0]), np.argsort(out[1])
+        assert [int(o0[0]), int(o0[1]), int(o1[0])] == [index for _, _, index in lc.P64_SLOTS] == [62, 63, 40]
+        assert list(ms[0].mask) == [i != 62 for i in range(64)] and all(ms[1].mask)
+        assert float(ms[0].incumbent(p.scal, p.best[0])) == out[0][63] and float(ms[1].incumbent(p.scal, p.best[1])) == out[1][40]
+        assert min(p.best) > max(max(o) for o in out)
+        margins = [out[0][o0[1]] - out[0][o0[0]], out[0][o0[2]] - out[0][o0[1]], out[1][o1[1]] - out[1][o1[0]]]
+        clear = min(abs(float(v) - p.taus[0]) for m in ms for v in m.constraint_means[0])
+        assert min(margins) >= ch.P64_MARGIN and clear > 0.1
+    print("p64: outcome margins %s, the constraint means at least %.3g from the threshold" % (margins, clear))
+    # half: member 0 believes the region infeasible and the rest feasible, member 1 the whole box feasible, away from the cut;
+    # HIGH_BEST lies above everything a member believes anywhere
+    c = lc.HALF
+    p = lc.make_problem(c)
+    k, upper = lc.half_region(c, p.gps, p.pending, p.scal)
+    probes = np.random.default_rng(1).uniform(0, 1, size=(400, c.d))
+    deep = np.abs(probes[:, k] - 0.5) > 0.25
+    inside = (probes[:, k] > 0.5) == upper
+    bases = [[lc.cr.base_model(g, np.float64) for g in row] for row in p.gps]
+    mean0 = np.array([float(v) for v in lc.cr.mean_at(bases[0][c.M], probes)])
+    mean1 = np.array([float(v) for v in lc.cr.mean_at(bases[1][c.M], probes)])
+    # (20 observations leave corners of the region where the believed mean falls back towards the other side: nine tenths suffice)
+    assert p.taus == (0.0,) and np.mean(mean0[deep & inside] > 1e-3) >= 0.9 and np.all(mean0[deep & ~inside] < -1e-3) and np.all(mean1 < -1e-3)
+    scal, best = lc.batch_rounds(p, 3)
+    assert np.array_equal(scal[0], p.scal) and best.shape == (3, 2) and np.all(best == lc.HIGH_BEST) and p.best == [lc.HIGH_BEST] * 2
+    for t in range(3):
+        ta, tb = ch.split(scal[t])
+        for row in bases:
+            outcomes = [lc.cr.mean_at(bs, probes) for bs in row[:c.M]]
+            assert max(float(v) for v in ch.scalarised_outcomes(ta, tb, outcomes, np.float64)) < lc.HIGH_BEST - 0.5
+    print("half: member 0 believes x[%d] %s 0.5 infeasible: means %.3g .. %.3g deep inside, %.3g .. %.3g deep outside; member 1's below %.3g"
+          % (k, ">" if upper else "<", mean0[deep & inside].min(), mean0[deep & inside].max(), mean0[deep & ~inside].min(),
+             mean0[deep & ~inside].max(), mean1.max()))
+
+
 def test_a_floored_objective_above_the_incumbent_keeps_its_nodes():
     """where ell is far below an ulp of g the ladder g - kappa ell would round to g and leave no node: in offsets LA and its
     coefficients are finite, in both arithmetics alike"""
