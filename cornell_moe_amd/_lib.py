@@ -100,6 +100,12 @@ SIGNATURES = {
                                                          dp, C.c_int, C.c_int, dp, dp, ip, dp, ip, dp, dp, dp, ip, _EP]),
     "moe_log_ei_constrained_mcmc_suggest": (C.c_int, [_GPA, C.c_int, _GPA, C.c_int, dp, C.POINTER(GdParams), dp, dp, dp, C.c_int, dp,
                                                       C.c_int, C.c_int, C.c_int, dp, dp, ip, _EP]),
+    "moe_log_ei_per_cost_mcmc": (C.c_int, [_GPA, C.c_int, _GPA, C.c_int, dp, _GPA, C.c_double, dp, dp, C.c_int, dp, C.c_int, C.c_int, dp,
+                                           dp, dp, _EP]),
+    "moe_log_ei_per_cost_mcmc_multistart": (C.c_int, [_GPA, C.c_int, _GPA, C.c_int, dp, _GPA, C.c_double, C.POINTER(GdParams), dp, dp, dp,
+                                                      C.c_int, dp, C.c_int, C.c_int, dp, dp, ip, dp, ip, dp, dp, dp, ip, _EP]),
+    "moe_log_ei_per_cost_mcmc_suggest": (C.c_int, [_GPA, C.c_int, _GPA, C.c_int, dp, _GPA, C.c_double, C.POINTER(GdParams), dp, dp, dp,
+                                                   C.c_int, dp, C.c_int, C.c_int, C.c_int, dp, dp, ip, _EP]),
     "moe_ehvi_mcmc": (C.c_int, [_GPA, _GPA, C.c_int, dp, dp, C.c_int, dp, C.c_int, dp, C.c_int, C.c_int, dp, dp, dp, _EP]),
     "moe_ehvi_mcmc_multistart": (C.c_int, [_GPA, _GPA, C.c_int, dp, dp, C.c_int, C.POINTER(GdParams), dp, dp, C.c_int, dp, C.c_int,
                                            C.c_int, dp, dp, ip, dp, ip, dp, dp, dp, ip, _EP]),

@@ -1159,6 +1159,64 @@ def log_ei_constrained_suggest(gps, constraint_gps, thresholds, gd_params, bound
                          gradient_ascent, points_being_sampled)
 
 
+def _ei_per_cost_members(gps, constraint_gps, thresholds, cost_gps, cost_exponent, best_so_far):
+    """_ei_constrained_members' tuple with (cost handles [E], the exponent as a C double) behind the thresholds, of the ensemble
+    forms of the log expected improvement per unit cost.  cost_gps: an ensemble shaped like gps (a DeviceGPMCMC, a list of DeviceGP or
+    one DeviceGP) of GPs of the LOG of the evaluation cost, E members; cost_exponent finite and >= 0."""
+    arr, E, d, keep, carr, K, tau, best = _ei_constrained_members(gps, constraint_gps, thresholds, best_so_far)
+    if cost_gps is None:
+        raise BoundsException("one cost GP per ensemble member", 0, E, E)
+    costs = [cost_gps] if isinstance(cost_gps, DeviceGP) else (list(cost_gps.gps) if isinstance(cost_gps, DeviceGPMCMC) else list(cost_gps))
+    if len(costs) != E:
+        raise BoundsException("one cost GP per ensemble member", len(costs), E, E)
+    alpha = float(cost_exponent)
+    if not np.isfinite(alpha) or alpha < 0.0:
+        raise InvalidValueException("cost_exponent must be finite and not negative", alpha, 0.0, 0.0)
+    costarr = (C.c_void_p * E)(*[g._h.value for g in costs])
+    return arr, E, d, (keep, costs), carr, K, tau, costarr, C.c_double(alpha), best
+
+
+def _ei_per_cost_args(gps, constraint_gps, thresholds, cost_gps, cost_exponent, best_so_far):
+    """(pre, post, E, K, dim, what must stay alive) of the three shapes below"""
+    arr, E, d, keep, carr, K, tau, costarr, alpha, best = _ei_per_cost_members(gps, constraint_gps, thresholds, cost_gps, cost_exponent,
+                                                                               best_so_far)
+    pre, post = (arr, E, carr, K, tau.ctypes.data_as(dp) if K else None, costarr, alpha), (best.ctypes.data_as(dp),)
+    return pre, post, E, K, d, (keep, tau, best)
+
+
+def log_ei_per_cost_ensemble(gps, constraint_gps, thresholds, cost_gps, cost_exponent, points, best_so_far, points_being_sampled=None,
+                             want_grad=True, want_log_factors=False):
+    """moe_log_ei_per_cost_mcmc: the log of the constrained expected improvement per unit cost, log_ei_constrained_ensemble's member
+    log plus -cost_exponent (mu_c + var_c / 2) from cost_gps[e], a GP of the LOG of the evaluation cost (the log of
+    E[cost]^-cost_exponent under a log-normal cost).  The other arguments as there; every GP's covariance, the cost GP's too, is
+    conditioned on points_being_sampled.  Returns value [C], with want_grad (value, grad [C][dim]), and with want_log_factors
+    additionally log_factors [E][2 + K][C] (the cost row last) as the last item.  cost_exponent = 0 is log_ei_constrained_ensemble
+    bit for bit.  SingularMatrixException(e (2 + K) + role, j): the GP, counted flat, and the pending point."""
+    pre, post, E, K, d, keep = _ei_per_cost_args(gps, constraint_gps, thresholds, cost_gps, cost_exponent, best_so_far)
+    return _acq1_evaluate(_lib.load().moe_log_ei_per_cost_mcmc, pre, post, d, points, want_grad, points_being_sampled,
+                          extra_shape=(E, 2 + K), want_extra=want_log_factors)
+
+
+def log_ei_per_cost_multistart(gps, constraint_gps, thresholds, cost_gps, cost_exponent, gd_params, bounds, best_so_far, starts,
+                               gradient_ascent=True, want_path=False, points_being_sampled=None):
+    """moe_log_ei_per_cost_mcmc_multistart: one suggestion by log_ei_per_cost_ensemble's objective --
+    log_ei_constrained_multistart's screening, 20 kept starts, restarted ascent on the device and end-point selection, and its dict."""
+    pre, post, E, K, d, keep = _ei_per_cost_args(gps, constraint_gps, thresholds, cost_gps, cost_exponent, best_so_far)
+    return _acq1_multistart(_lib.load().moe_log_ei_per_cost_mcmc_multistart, pre, post, d, gd_params, bounds, starts, gradient_ascent,
+                            want_path, points_being_sampled)
+
+
+def log_ei_per_cost_suggest(gps, constraint_gps, thresholds, cost_gps, cost_exponent, gd_params, bounds, best_so_far, starts,
+                            num_to_sample, gradient_ascent=True, points_being_sampled=None):
+    """moe_log_ei_per_cost_mcmc_suggest: num_to_sample points greedily by log_ei_per_cost_ensemble's objective -- round t is
+    log_ei_per_cost_multistart from the same starts [S][dim] with the pending points points_being_sampled [p][dim] (may be None)
+    followed by the points of the rounds before, bit for bit, in one device call.  (p + num_to_sample - 1) (1 + g) <= 64.
+    Returns a dict: points [q][dim], values [q], found [q]."""
+    pre, post, E, K, d, keep = _ei_per_cost_args(gps, constraint_gps, thresholds, cost_gps, cost_exponent, best_so_far)
+    return _acq1_suggest(_lib.load().moe_log_ei_per_cost_mcmc_suggest, pre, post, d, gd_params, bounds, starts, num_to_sample,
+                         gradient_ascent, points_being_sampled)
+
+
 def _ehvi_members(gps, gps2, reference_point, front):
     """(objective-1 handles, objective-2 handles, E, dim, GPs kept alive, reference point [2], front [F][2] or None, F) of the
     ensemble forms of the expected hypervolume improvement; gps and gps2 shaped alike (a DeviceGPMCMC, a list of DeviceGP or one

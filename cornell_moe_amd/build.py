@@ -16,7 +16,7 @@ OBJ = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "lib", "libmoe_hip.so")
 SOURCES = ["kernels_cov.hip", "kernels_linalg.hip", "host_math.hip", "gp.hip", "kg.hip", "kg_tail.hip", "kg_prep.hip", "kg_state.hip", "kg_mc_dp4.hip", "kg_mc_dp8.hip",
            "kg_mc_dp12.hip", "kg_mc_dp16.hip", "kg_mc_dp4b.hip", "kg_mc_dp8b.hip", "kg_mc_dp12b.hip", "kg_mc_dp16b.hip", "kg_mc_dp24.hip", "kg_mc_dp32.hip", "multistart.hip", "mcmc.hip", "ei.hip", "api.hip", "rccl_comm.hip", "query_grad.hip",
-           "sample.hip", "hyper_mcmc.hip", "lcb.hip", "loo.hip", "recommend.hip", "pm_members.hip", "kg1.hip", "kg1_ascent.hip", "kg1_opt.hip", "kg1_pending.hip", "ei1.hip", "gibbon1.hip", "cei1.hip", "logcei1.hip", "ehvi1.hip", "ehvi3.hip", "cehvi1.hip", "logehvi1.hip", "logehvi3.hip", "chebei1.hip", "logchebei1.hip", "paths.hip"]
+           "sample.hip", "hyper_mcmc.hip", "lcb.hip", "loo.hip", "recommend.hip", "pm_members.hip", "kg1.hip", "kg1_ascent.hip", "kg1_opt.hip", "kg1_pending.hip", "ei1.hip", "gibbon1.hip", "cei1.hip", "logcei1.hip", "logeipc1.hip", "ehvi1.hip", "ehvi3.hip", "cehvi1.hip", "logehvi1.hip", "logehvi3.hip", "chebei1.hip", "logchebei1.hip", "paths.hip"]
 HEADERS = sorted(h for h in os.listdir(CSRC) if h.endswith(".hpp")) + [os.path.join("..", "..", "include", "moe_hip.h")]  # every header there is
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function",
          # MFMA accumulators stay in VGPRs: left to its heuristics the compiler parks them in AGPRs and copies all of them

@@ -1052,6 +1052,30 @@ Acq1 log_ei_constrained(const moe_gp_t* const* gps, int num_mcmc, const moe_gp_t
   return a;
 }
 
+// The log constrained expected improvement's ladder over members of 2 + K GPs, flat and ordered [e][role]: the constrained call's
+// roles, then the GP of the log cost.
+Acq1 log_ei_per_cost(const moe_gp_t* const* gps, int num_mcmc, const moe_gp_t* const* constraint_gps, int num_constraints,
+                     const double* thresholds, const moe_gp_t* const* cost_gps, double cost_exponent, const double* best_so_far) {
+  Acq1 a = acq1_of(gps, num_mcmc, "the log expected improvement per unit cost");
+  a.pointers = gps && cost_gps && best_so_far;
+  a.check_shapes = [=](int num_points) {
+    moe::check_log_ei_per_cost_shapes(num_mcmc, num_constraints, constraint_gps, thresholds, cost_exponent, best_so_far);
+    moe::check_ei_analytic_mcmc_shapes(num_mcmc, num_points);
+  };
+  a.handles = [=] {
+    const int G = 2 + num_constraints;
+    std::vector<const moe_gp_t*> flat((size_t)num_mcmc * G);
+    for (int e = 0; e < num_mcmc; ++e) {
+      flat[(size_t)e * G] = gps[e];
+      for (int k = 0; k < num_constraints; ++k) flat[(size_t)e * G + 1 + k] = constraint_gps[(size_t)k * num_mcmc + e];
+      flat[(size_t)e * G + 1 + num_constraints] = cost_gps[e];
+    }
+    return flat;
+  };
+  a.call = [=] { return moe::logeipc1_call(num_mcmc, num_constraints, thresholds, cost_exponent, best_so_far); };
+  return a;
+}
+
 // The GPs of a two-objective call, flat and ordered [e][objective]
 std::vector<const moe_gp_t*> two_objective_handles(const moe_gp_t* const* gps, const moe_gp_t* const* gps2, int num_mcmc) {
   std::vector<const moe_gp_t*> flat(2 * (size_t)num_mcmc);
@@ -1405,6 +1429,44 @@ int moe_log_ei_constrained_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc
   return guarded(err, [&] {
     acq1_suggest(log_ei_constrained(gps, num_mcmc, constraint_gps, num_constraints, thresholds, best_so_far), outer, domain_bounds,
                  points_being_sampled, num_being_sampled, starts, num_starts, do_gradient_ascent, num_to_sample,
+                 {best_points, best_values, found});
+  });
+}
+
+int moe_log_ei_per_cost_mcmc(const moe_gp_t* const* gps, int num_mcmc, const moe_gp_t* const* constraint_gps, int num_constraints,
+                             const double* thresholds, const moe_gp_t* const* cost_gps, double cost_exponent,
+                             const double* best_so_far, const double* points_being_sampled, int num_being_sampled,
+                             const double* points, int num_points, int want_grad, double* value, double* grad, double* log_factors,
+                             moe_error_t* err) {
+  return guarded(err, [&] {
+    acq1_evaluate(log_ei_per_cost(gps, num_mcmc, constraint_gps, num_constraints, thresholds, cost_gps, cost_exponent, best_so_far),
+                  points_being_sampled, num_being_sampled, points, num_points, want_grad, value, grad, log_factors);
+  });
+}
+
+int moe_log_ei_per_cost_mcmc_multistart(const moe_gp_t* const* gps, int num_mcmc, const moe_gp_t* const* constraint_gps,
+                                        int num_constraints, const double* thresholds, const moe_gp_t* const* cost_gps,
+                                        double cost_exponent, const moe_gd_params_t* outer, const double* domain_bounds,
+                                        const double* best_so_far, const double* points_being_sampled, int num_being_sampled,
+                                        const double* starts, int num_starts, int do_gradient_ascent, double* best_point,
+                                        double* best_value, int* found, double* start_values, int* kept_index, double* end_points,
+                                        double* end_values, double* path, int* steps_taken, moe_error_t* err) {
+  return guarded(err, [&] {
+    acq1_multistart(log_ei_per_cost(gps, num_mcmc, constraint_gps, num_constraints, thresholds, cost_gps, cost_exponent, best_so_far),
+                    outer, domain_bounds, points_being_sampled, num_being_sampled, starts, num_starts, do_gradient_ascent,
+                    {best_point, best_value, found, start_values, kept_index, end_points, end_values, path, steps_taken});
+  });
+}
+
+int moe_log_ei_per_cost_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, const moe_gp_t* const* constraint_gps,
+                                     int num_constraints, const double* thresholds, const moe_gp_t* const* cost_gps,
+                                     double cost_exponent, const moe_gd_params_t* outer, const double* domain_bounds,
+                                     const double* best_so_far, const double* points_being_sampled, int num_being_sampled,
+                                     const double* starts, int num_starts, int do_gradient_ascent, int num_to_sample,
+                                     double* best_points, double* best_values, int* found, moe_error_t* err) {
+  return guarded(err, [&] {
+    acq1_suggest(log_ei_per_cost(gps, num_mcmc, constraint_gps, num_constraints, thresholds, cost_gps, cost_exponent, best_so_far),
+                 outer, domain_bounds, points_being_sampled, num_being_sampled, starts, num_starts, do_gradient_ascent, num_to_sample,
                  {best_points, best_values, found});
   });
 }

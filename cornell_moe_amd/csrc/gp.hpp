@@ -301,7 +301,7 @@ void kg1_clear_fail(int* fail, int count, hipStream_t s);  // INT_MAX: no candid
 // The ensemble forms of the one-point acquisitions: evaluate at points, multistart ascent and greedy batches of each, with pending
 // points [num_pending][dim] by the Kriging-believer fantasy of kg1_pending.hip.  Every client describes its call in one function
 // (kg1_ascent.hpp: kg1_call, ei1_call, gibbon1_call, cei1_call, ehvi1_call, logcei1_call, ehvi3_call, cehvi1_call, cehvi3_call,
-// logehvi1_call, logehvi3_call, chebei1_call, logchebei1_call) and the three drivers of kg1_ascent.hip run it; here are the checks that need no handle, which the entry points
+// logehvi1_call, logehvi3_call, chebei1_call, logchebei1_call, logeipc1_call) and the three drivers of kg1_ascent.hip run it; here are the checks that need no handle, which the entry points
 // make first, and the limits.
 // kg1_opt.hip: the discretised knowledge gradient (moe_kg_discrete_mcmc*).  discrete_all: the members' sets back to back.
 void check_kg_discrete_ensemble_shapes(int num_mcmc, int num_fidelity, const int* num_discrete, int num_points);
@@ -367,6 +367,13 @@ void check_chebei_values(int num_objectives, int num_mcmc, int num_rounds, const
 void check_logchebei_shapes(int num_objectives, int num_constraints, int num_mcmc);
 void check_logchebei_values(int num_objectives, int num_constraints, int num_mcmc, int num_rounds, const double* scalarisations,
                             const double* thresholds, const double* best_so_far);
+// logeipc1.hip: the log of the constrained expected improvement per unit cost (moe_log_ei_per_cost_mcmc*): logcei1.hip's three over
+// members of 2 + K GPs each, the GPs of a call [E (2 + K)] ordered [e][role], the last role a GP of the log of the evaluation cost;
+// cost_exponent >= 0 (alpha).  check_log_ei_per_cost_shapes: K, the product limit E (2 + K) <= 1024, check_ei_constrained_shapes'
+// remaining checks, then the exponent finite and not negative.  The members' own values of an evaluation are the sub-members'
+// logs [E (2 + K)][C], the cost row last.
+void check_log_ei_per_cost_shapes(int num_mcmc, int num_constraints, const void* constraint_gps, const double* thresholds,
+                                  double cost_exponent, const double* best_so_far);
 // loo.hip: leave-one-out cross-validation on the GP's current factorisation, every one of the N = n (1 + g) scalar observations left
 // out by itself.  mean_out / var_out [n][1 + g]: the LOO predictive mean (function values in the caller's units) and variance.
 void loo_predict_on_device(GpDev& gp, double* mean_out, double* var_out);

@@ -15,7 +15,8 @@
 // eleventh) and chebei1.hip (the Chebyshev-scalarised expected improvement for 2 to 8 objectives, the twelfth: groups of M GPs on
 // ehvi1.hip's chain, a fixed quadrature per member, and a scalarisation and incumbents of its own for every point of a batch) and
 // logchebei1.hip (the log of that with constraints, the thirteenth: groups of M + K GPs, a log-sum-exp over the quadrature's nodes
-// and over the members).
+// and over the members) and logeipc1.hip (the log of the constrained expected improvement per unit cost, the fourteenth: logcei1.hip's
+// groups with one more GP, of the log of the evaluation cost, whose role adds -alpha (mu + var / 2) to the member's log).
 #pragma once
 #include <memory>
 #include <vector>
@@ -129,7 +130,7 @@ struct Kg1Call {
   std::shared_ptr<const void> client;
   void (*check_members)(const Kg1Objective& o, const std::vector<GpDev*>& gps, int pending_room) = nullptr;
 };
-// The thirteen clients' descriptions, one function each (the caller has made the checks that need no handle; the arrays are the
+// The fourteen clients' descriptions, one function each (the caller has made the checks that need no handle; the arrays are the
 // caller's and outlive the call).  gp.hpp says what the arguments are.
 Kg1Call kg1_call(int num_fidelity, const double* discrete_all, const int* num_discrete, const double* best_so_far);  // kg1_opt.hip
 Kg1Call ei1_call(const double* best_so_far);                                                                       // ei1.hip
@@ -153,6 +154,9 @@ Kg1Call chebei1_call(int num_mcmc, int num_objectives, int num_rounds, const dou
                      const double* best_so_far);  // chebei1.hip
 Kg1Call logchebei1_call(int num_mcmc, int num_objectives, int num_constraints, const double* thresholds, int num_rounds,
                         const double* scalarisations, const double* best_so_far);  // logchebei1.hip
+// (members of 2 + K GPs: the objective, the K constraints, the GP of the log cost)
+Kg1Call logeipc1_call(int num_mcmc, int num_constraints, const double* thresholds, double cost_exponent,
+                      const double* best_so_far);  // logeipc1.hip
 
 // what a multistart hands back (all but the first three may be NULL) ...
 struct Kg1MultistartOut {

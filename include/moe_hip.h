@@ -572,6 +572,57 @@ int moe_log_ei_constrained_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc
                                         const double* domain_bounds, const double* best_so_far, const double* points_being_sampled,
                                         int num_being_sampled, const double* starts, int num_starts, int do_gradient_ascent,
                                         int num_to_sample, double* best_points, double* best_values, int* found, moe_error_t* err);
+/* The LOG of the constrained expected improvement PER UNIT COST (Snoek, Larochelle & Adams 2012, "EI per second"; the exponent of
+ * cost-cooling, Lee et al. 2020) averaged over a hyper-parameter ensemble.  The call is moe_log_ei_constrained_mcmc's with
+ * (cost_gps, cost_exponent) behind thresholds: cost_gps [E], cost_gps[e] member e's GP of the LOG of the evaluation cost;
+ * cost_exponent = alpha >= 0 (1: improvement per unit cost; lowered towards 0 as a budget runs out; 0: the cost plays no part).
+ * Member e is 2 + K GPs, counted flat as e (2 + K) + role: role 0 the objective, roles 1 .. K the constraints, role K + 1 the cost
+ * GP.  All 2 + K GPs of a call carry one dim, one device and ONE observed-derivative list (a pending point is 1 + g extension rows
+ * of at most 64), and every GP's covariance, the cost GP's too, is conditioned on the pending points with the mean left alone: one
+ * staging serves every sub-member, so the cost's variance term is the conditioned one.  The believed-feasible incumbent b'_e is
+ * moe_ei_constrained_mcmc's; the cost GP takes no part in it.  Per member e at x, with ONE variance floor for value and gradient,
+ * v = max(150 eps^2, var), sigma = sqrt(v):
+ *   improvement   l_{e,0} and its gradient exactly moe_log_ei_constrained_mcmc's (b'_e = +infinity: 0 with a zero gradient)
+ *   feasibility   l_{e,k} and its gradient exactly moe_log_ei_constrained_mcmc's
+ *   cost          l_{e,c} = -(alpha (mu_c + v_c / 2)), the log of E[cost]^-alpha under a log-normal cost,
+ *                 grad l = -alpha grad mu_c - (alpha / 2) grad var_c, the second term 0 where var_c lies below the floor
+ *   member        L_e = ((l_{e,0} + l_{e,1}) + ... + l_{e,K}) + l_{e,c}, the gradient g_e likewise, in that order
+ *   ensemble      m = max_e L_e, w_e = exp(L_e - m), W = w_0 + ... + w_{E-1}:  value[i] = m + log W - log E,
+ *                 grad[i] = (w_0 g_0 + ... + w_{E-1} g_{E-1}) / W; members in member order, every operation rounded by itself, no
+ *                 fused multiply-add in the rule, no atomics
+ * log_factors (may be NULL): [E][2 + K][num_points], every l_{e,r}, the cost row last.  With E = 1 value[i] is the member's log
+ * factors added left to right, bit for bit; with cost_exponent = 0 value, grad and rows 0 .. K are moe_log_ei_constrained_mcmc's bit
+ * for bit and the cost row is 0.  A candidate's bits do not depend on how many share the call, on want_grad or on ensemble-wide
+ * launches.  The value is finite with a useful gradient for every finite input.
+ * Errors: moe_log_ei_constrained_mcmc's, in its order and with its payloads, with these changes: cost_gps is among the arrays
+ * that must not be NULL (MOE_ERR_RUNTIME); the product limit is num_mcmc (2 + num_constraints) > 1024 -> MOE_ERR_BOUNDS, payload
+ * (num_mcmc, 1, 1024 / (2 + num_constraints) rounded down); behind the best_so_far check, a cost_exponent that is not finite or is
+ * negative -> MOE_ERR_INVALID_VALUE, payload (the value, 0, 0); the handle checks count the GPs flat as e (2 + K) + role, and so does
+ * MOE_ERR_SINGULAR's payload for a pending point. */
+int moe_log_ei_per_cost_mcmc(const moe_gp_t* const* gps, int num_mcmc, const moe_gp_t* const* constraint_gps, int num_constraints,
+                             const double* thresholds, const moe_gp_t* const* cost_gps, double cost_exponent,
+                             const double* best_so_far, const double* points_being_sampled, int num_being_sampled,
+                             const double* points, int num_points, int want_grad, double* value, double* grad, double* log_factors,
+                             moe_error_t* err);
+/* moe_log_ei_constrained_mcmc_multistart with moe_log_ei_per_cost_mcmc's objective: the same screening, top-20 rule, restarted
+ * ascent and outputs, bit for bit the path a host loop over moe_log_ei_per_cost_mcmc walks.  Errors: that function's, the ascent's
+ * named "the log expected improvement per unit cost". */
+int moe_log_ei_per_cost_mcmc_multistart(const moe_gp_t* const* gps, int num_mcmc, const moe_gp_t* const* constraint_gps,
+                                        int num_constraints, const double* thresholds, const moe_gp_t* const* cost_gps,
+                                        double cost_exponent, const moe_gd_params_t* outer, const double* domain_bounds,
+                                        const double* best_so_far, const double* points_being_sampled, int num_being_sampled,
+                                        const double* starts, int num_starts, int do_gradient_ascent, double* best_point,
+                                        double* best_value, int* found, double* start_values, int* kept_index, double* end_points,
+                                        double* end_values, double* path, int* steps_taken, moe_error_t* err);
+/* moe_log_ei_constrained_mcmc_suggest with moe_log_ei_per_cost_mcmc's objective: num_to_sample points greedily, bit for bit what
+ * num_to_sample calls of moe_log_ei_per_cost_mcmc_multistart return when each is fed its predecessors' points; a pick joins the
+ * extension of each of the E (2 + K) GPs.  Errors: that function's. */
+int moe_log_ei_per_cost_mcmc_suggest(const moe_gp_t* const* gps, int num_mcmc, const moe_gp_t* const* constraint_gps,
+                                     int num_constraints, const double* thresholds, const moe_gp_t* const* cost_gps,
+                                     double cost_exponent, const moe_gd_params_t* outer, const double* domain_bounds,
+                                     const double* best_so_far, const double* points_being_sampled, int num_being_sampled,
+                                     const double* starts, int num_starts, int do_gradient_ascent, int num_to_sample,
+                                     double* best_points, double* best_values, int* found, moe_error_t* err);
 /* The two-objective expected hypervolume improvement (EHVI; Emmerich, Giannakoglou & Naujoks 2006; Emmerich, Deutz & Klinkenberg
  * 2011; Yang et al. 2019) averaged over a hyper-parameter ensemble, at points [num_points][dim], with pending points.  Minimisation.
  * Member e is two GPs, gps[e] for objective 1 and gps2[e] for objective 2: one dim, one device, no derivative observations; their
